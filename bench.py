@@ -1,8 +1,11 @@
 """bench.py — AR-decode throughput of the HIP engine on the BASELINE.json configuration
 "English 830M zero-shot TTS, cfg_stride=5 top-k sampling, batch=1 on one MI355X" (configs[1]).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
   (N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...)
+
+`--dump-outputs DIR` writes what the K timed steps computed (`dump_outputs`) as DIR/<name>.npy; the inputs depend on the
+arguments only, so the files of two builds can be compared array for array.
 
 A "step" is one decode step of the hot path (one codec frame = 4 codec tokens per utterance) over one
 batch of synthetic input: 830M-shape weights from the deterministic generator (seed 0, fp32), L=130 random
@@ -76,6 +79,29 @@ def synth_inputs(args_lm, rank, L=130, N=160, prompt_codes=None):
     if prompt_codes is not None and prompt_codes.shape[1] == N:
         y = prompt_codes.clone()                 # same draws from `g` either way: the text ids do not depend on the prompt's source
     return x, y, unc
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, eng, warmup, steps):
+    """`--dump-outputs`: what the timed decode steps handed back, as `out_dir/<name>.npy` (float64 / float32), for comparing two
+    builds output for output. tokens [U, steps, K]: the codec tokens of the timed steps; logits_last_step [2U, K, card]: the
+    logits buffer after the last timed step; sampler_state [U, 12]: the per-utterance state (`_lib.SamplerState`, pad excluded).
+    Untimed; called right after the timed pass, before anything else advances the engine."""
+    total = warmup + steps
+    tokens = np.stack([eng.tokens(u, total)[warmup:] for u in range(eng.n_utt)])
+    states = eng.states()
+    fields = [f for f, _ in states[0]._fields_ if f not in ("span_end", "pad")]
+    state = np.asarray([[getattr(s, f) for f in fields] + list(s.span_end) for s in states], dtype=np.float64)
+    arrays = {"tokens": tokens.astype(np.float64), "logits_last_step": eng.logits.detach().float().cpu().numpy(),
+              "sampler_state": state}
+    assert tokens.shape[1] == steps, (tokens.shape, steps)
+    assert sum(v.nbytes for v in arrays.values()) <= DUMP_LIMIT_BYTES
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    return {name: list(arr.shape) for name, arr in arrays.items()}
 
 
 def cpu_baseline(args_lm, sd_gpu, x, y, unc, n_steps=25):
@@ -496,7 +522,11 @@ def main():
     ap.add_argument("--no-ctx700", action="store_true", help="skip the second timed region around context 700 (counter-collection runs: rocprofv3 --pmc "
                     "crashed with ~400 graph replays in flight behind one synchronisation, round 6)")
     ap.add_argument("--legs", type=str, default="", help="comma separated subset of the extra legs to run (default: all)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="after the timed steps, write what they computed (codec tokens of the "
+                    "timed steps, logits of the last step, sampler state) as DIR/<name>.npy (rank 0)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -554,6 +584,7 @@ def main():
             break
         seed_try += 1           # the sampler drew <eog> inside the timed region: different stream, same workload
     elapsed = t1 - t0
+    dumped = dump_outputs(a.dump_outputs, eng, a.warmup, a.steps) if a.dump_outputs and rank == 0 else None
     # the same W + K steps again (restart, warm-up, K timed steps: same context range), listed beside the headline: the driver's timed region
     # is ~17 ms and boxes differ by 3-5 %, so one pass cannot resolve a 1 % change. `ms_per_step` stays the FIRST pass.
     extra_passes = []
@@ -696,6 +727,8 @@ def main():
         }
         if allgather_ms is not None:
             out["allgather_ms"] = round(allgather_ms, 3)
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": a.dump_outputs, "shapes": dumped}
     else:
         out = None
 

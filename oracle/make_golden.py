@@ -4,18 +4,24 @@ tests/golden/*.npz.  Re-run:  python -m oracle.make_golden  (from the repo root)
 
 Weights are not stored: they are re-created from `ssr_speech_amd.weights` (name/seed hash), the
 fixture holds the seed.  Every fixture records torch.__version__ (the reference pins no torch
-version).
+version). The reference runs in the host-independent CPU mode of oracle/numerics.py, so the recorded
+fp32 outputs are bit-exact on any host that recomputes them in that mode.
 """
 from __future__ import annotations
 
 import os
 import sys
 
-import numpy as np
-import torch
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+from oracle import numerics  # noqa: E402
+
+assert "torch" not in sys.modules, "oracle/numerics.py's mode must be set before torch starts"
+os.environ.update(numerics.ENV)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
 
 from oracle import ref_import  # noqa: E402
 import ssr_speech_amd  # noqa: E402,F401
@@ -299,7 +305,7 @@ def make_state_machine():
 if __name__ == "__main__":
     os.makedirs(GOLD, exist_ok=True)
     which = sys.argv[1:] or ["layout", "sampler", "lm", "codec"]
-    torch.set_num_threads(8)
+    torch.set_num_threads(numerics.THREADS)
     if "layout" in which:
         make_layout()
     if "sampler" in which:
