@@ -34,7 +34,7 @@ typedef void* ssrhip_stream_t;
 int ssrhip_version(void);
 /* sizeof() of the ABI structs, for binding self-checks: 0 kv, 1 gemv_args, 2 attn_args, 3 embed_args,
  * 4 sampler_cfg, 5 sampler_state, 6 sample_args, 7 gemm_args, 8 lm_weights, 9 lm_dims, 10 lm_buffers, 11 prefill_args,
- * 12 lstm_args */
+ * 12 lstm_args, 13 resblock_args, 14 score_args */
 int ssrhip_sizeof(int which);
 const char* ssrhip_last_error(void);
 
@@ -439,6 +439,46 @@ int ssrhip_lm_prefill(ssrhip_lm* lm, const ssrhip_prefill_args* p, ssrhip_stream
 /* x[b] = embedding of row b's pending input token (next_tok / next_pos) for EVERY row of the engine — the closing step of ssrhip_lm_prefill
  * on its own (rows in mid-decode get exactly what the sampler's fused embedding left there: same function, same inputs). */
 int ssrhip_lm_embed_pending(ssrhip_lm* lm, ssrhip_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Teacher-forced scoring (the numbers of the reference's training forward, models/ssr.py:280-379, without autograd):
+ * the same flattened [text || audio] rows as a prefill, the same layer loop (one internal function serves both entries), then the
+ * final LayerNorm of the SCORED rows only, the prediction heads and cross entropy / rank per codebook. Needs no decode engine.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct ssrhip_score_args {
+  /* prefill rows, exactly as in ssrhip_prefill_args: device arrays [R]; seq_start [n_seq + 1] (device), rows of a sequence contiguous and in
+   * position order (the tiled prefill attention) */
+  const int32_t* tok; const int32_t* pos; const int32_t* kind;
+  const int32_t* row_seq; const int32_t* row_pos; const int32_t* row_len;
+  const int32_t* seq_start;
+  int32_t R, n_seq, max_len;
+  float* x; float* xn; float* qkv; float* o; float* h;   /* workspaces [R][D], [R][D], [R][3D], [R][D], [R][d_ffn] */
+  /* scratch KV pool: kv.n_layer must be 1 (every layer writes and reads layer 0 of the pool: stream order makes the reuse safe);
+   * kv.table [n_seq][kv.max_pages] */
+  ssrhip_kv kv;
+  /* scored rows, HOST arrays [n_seq]: sequence s scores its rows score_first[s] .. score_first[s] + score_count[s] - 1 (absolute row
+   * indices into the R rows); M = sum of score_count. Scored row m (in that order) predicts target[k * M + m] of codebook k. */
+  const int32_t* score_first; const int32_t* score_count;
+  int32_t M;
+  const int32_t* target;   /* device [K][M], 0 <= target < card */
+  float* nll;              /* device [K][M]: -log softmax(logits)[target] */
+  int32_t* rank;           /* device [K][M]: classes whose logit is STRICTLY greater than the target's (ssrhip_xent_rank) */
+  float* hs;               /* workspace [M][D]: final-LayerNorm output of the scored rows (may alias xn) */
+  float* head_h;           /* workspace [head_chunk][K * head_hidden] */
+  float* logits;           /* workspace [head_chunk][ldc], ldc = card rounded up to a multiple of 4 */
+  int32_t head_chunk;      /* rows per head pass (bounds the logits buffer) */
+  /* optional (both or none; NULL = the fp32 chain): three bf16 planes (ssrhip_split_weights) of head1_w as one [3][K*Hh][D] and of each
+   * codebook's head2_w[k] separately, [K][3][card][Hh]. Used under the prefill's rule (not with SSRHIP_PREFILL_SPLIT=0). */
+  const uint16_t* head1_ws; const uint16_t* head2_ws;
+} ssrhip_score_args;
+/* Writes nll / rank of every scored row and codebook. Layer GEMMs use the ssrhip_lm_weights split planes when present (same rule as
+ * ssrhip_lm_prefill). The workspaces, the scratch pool and the output belong to the caller. */
+int ssrhip_lm_score(const ssrhip_lm_dims* d, const ssrhip_lm_weights* w, const ssrhip_score_args* a, ssrhip_stream_t stream);
+/* Cross entropy and rank of M rows of logits [M][ld] (one codebook) against target [M]: one wave64 per row, one pass with an online max and
+ * rescaled fp32 exp-sum. nll[m] = logsumexp(row) - row[target]; rank[m] = #{c != target : row[c] > row[target]} (top-10 hit = rank < 10;
+ * exact ties at the 10th place count as hits, where torch.topk's order is arbitrary). ld % 4 == 0, card <= ld. */
+int ssrhip_xent_rank(const float* logits, int32_t ld, int32_t card, const int32_t* target, int32_t M, float* nll, int32_t* rank,
+                     ssrhip_stream_t stream);
 /* 0 = fine, 1 = a paired GEMV launch of this engine's decode step gave up waiting (ssrhip_gemv_pair): every token since the last call
  * that returned 0 is invalid and so are the KV cache and the residual stream of the rows in flight; reported ONCE (the workspace is
  * re-zeroed: after a new prefill the engine decodes correctly again). Synchronises `stream`. Engines that do not pair always return 0

@@ -153,6 +153,17 @@ class PrefillArgs(C.Structure):
                 ("table", C.c_void_p), ("no_embed", C.c_int32), ("reserved_", C.c_int32)]
 
 
+class ScoreArgs(C.Structure):
+    _fields_ = [("tok", C.c_void_p), ("pos", C.c_void_p), ("kind", C.c_void_p),
+                ("row_seq", C.c_void_p), ("row_pos", C.c_void_p), ("row_len", C.c_void_p), ("seq_start", C.c_void_p),
+                ("R", C.c_int32), ("n_seq", C.c_int32), ("max_len", C.c_int32),
+                ("x", C.c_void_p), ("xn", C.c_void_p), ("qkv", C.c_void_p), ("o", C.c_void_p), ("h", C.c_void_p),
+                ("kv", KV), ("score_first", C.c_void_p), ("score_count", C.c_void_p), ("M", C.c_int32),
+                ("target", C.c_void_p), ("nll", C.c_void_p), ("rank", C.c_void_p),
+                ("hs", C.c_void_p), ("head_h", C.c_void_p), ("logits", C.c_void_p), ("head_chunk", C.c_int32),
+                ("head1_ws", C.c_void_p), ("head2_ws", C.c_void_p)]
+
+
 # every symbol include/ssrhip.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("ssrhip_version", C.c_int, []),
@@ -186,6 +197,8 @@ SYMBOLS = [
     ("ssrhip_lm_decode", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     ("ssrhip_lm_prefill", C.c_int, [C.c_void_p, C.POINTER(PrefillArgs), C.c_void_p]),
     ("ssrhip_lm_embed_pending", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("ssrhip_lm_score", C.c_int, [C.POINTER(LMDims), C.POINTER(LMWeights), C.POINTER(ScoreArgs), C.c_void_p]),
+    ("ssrhip_xent_rank", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("ssrhip_lm_pairing", C.c_int, [C.c_void_p, C.c_char_p, C.c_int32]),
     ("ssrhip_lm_pair_status", C.c_int, [C.c_void_p, C.c_void_p]),
     ("ssrhip_debug_occupy", C.c_int, [C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
@@ -194,7 +207,7 @@ SYMBOLS = [
 ]
 
 ABI_STRUCTS = [KV, GemvArgs, AttnArgs, EmbedArgs, SamplerCfg, SamplerState, SampleArgs, GemmArgs, LMWeights, LMDims,
-               LMBuffers, PrefillArgs, LstmArgs, ResblockArgs]
+               LMBuffers, PrefillArgs, LstmArgs, ResblockArgs, ScoreArgs]
 
 _lib = None
 
@@ -223,7 +236,10 @@ def lib():
     except OSError as e:  # e.g. libamdhip64 absent
         raise SsrHipUnavailable(f"cannot load {LIB_PATH}: {e}") from e
     for name, res, args in SYMBOLS:
-        fn = getattr(L, name)
+        try:
+            fn = getattr(L, name)
+        except AttributeError as e:      # a library built from older sources
+            raise SsrHipUnavailable(f"{LIB_PATH} does not export {name}: rebuild it (make -C {CSRC})") from e
         fn.restype = res
         fn.argtypes = args
     if L.ssrhip_version() != ABI_VERSION:

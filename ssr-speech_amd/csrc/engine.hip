@@ -47,6 +47,7 @@ extern "C" int ssrhip_sizeof(int which) {
     case 11: return sizeof(ssrhip_prefill_args);
     case 12: return sizeof(ssrhip_lstm_args);
     case 13: return sizeof(ssrhip_resblock_args);
+    case 14: return sizeof(ssrhip_score_args);
     default: return -1;
   }
 }
@@ -575,16 +576,13 @@ extern "C" int ssrhip_lm_time_category(ssrhip_lm* lm, int32_t category, int32_t 
   return 0;
 }
 
-extern "C" int ssrhip_lm_prefill(ssrhip_lm* lm, const ssrhip_prefill_args* p, ssrhip_stream_t stream) {
-  SSR_REQUIRE(lm && p && p->tok && p->pos && p->kind && p->row_seq && p->row_pos && p->row_len, "ssrhip_lm_prefill: null argument");
-  const bool tiled_attn = p->seq_start && p->n_seq > 0 && p->max_len > 0 && !getenv_flag("SSRHIP_PREFILL_ATTN_ROWWISE");
-  SSR_REQUIRE(p->x && p->xn && p->qkv && p->o && p->h && (tiled_attn || (p->part_o && p->part_ml)), "ssrhip_lm_prefill: null workspace");
-  const ssrhip_lm_dims& d = lm->d;
-  const ssrhip_lm_weights& w = lm->w;
+// The layer loop over R flattened rows (embedding, then n_layer x [LN1 -> QKV GEMM -> KV scatter -> attention -> out-proj + residual
+// -> LN2 -> FFN1 + ReLU -> FFN2 + residual]), shared by the prefill and the scoring entry. `kv` is the cache the rows write and read;
+// with kv.n_layer == 1 (a scoring scratch pool) every layer uses layer 0 of it. `split`: GEMMs on the bf16 planes of `w`.
+static int lm_layer_loop(const ssrhip_lm_dims& d, const ssrhip_lm_weights& w, bool split, const ssrhip_kv& kv, const ssrhip_prefill_args* p,
+                         bool tiled_attn, hipStream_t s) {
   const int D = d.d_model, R = p->R;
-  hipStream_t s = (hipStream_t)stream;
-  ssrhip_kv kv = lm->b.kv;
-  if (p->table) kv.table = p->table;              // two-phase admission: the rows being filled are not in the decode step's table yet
+  const bool one_layer_kv = kv.n_layer == 1;
 
   ssrhip_embed_args ea;
   memset(&ea, 0, sizeof(ea));
@@ -595,18 +593,19 @@ extern "C" int ssrhip_lm_prefill(ssrhip_lm* lm, const ssrhip_prefill_args* p, ss
   if (int rc = ssrhip_embed(&ea, s)) return rc;
 
   for (int l = 0; l < d.n_layer; ++l) {
+    const int kl = one_layer_kv ? 0 : l;
     if (int rc = ssrhip_layernorm(p->x, w.ln1_w[l], w.ln1_b[l], 1e-5f, p->xn, R, D, s)) return rc;
     ssrhip_gemm_args g;
     memset(&g, 0, sizeof(g));
     g.A = p->xn; g.W = w.in_proj_w[l]; g.bias = w.in_proj_b[l]; g.C = p->qkv;
     g.M = R; g.N = 3 * D; g.K = D; g.lda = D; g.ldc = 3 * D;
-    if (lm->prefill_split) g.W_split = w.in_proj_ws[l];
+    if (split) g.W_split = w.in_proj_ws[l];
     if (int rc = ssrhip_gemm(&g, s)) return rc;
-    if (int rc = ssrhip_kv_scatter(p->qkv, &kv, l, p->row_seq, p->row_pos, R, s)) return rc;
+    if (int rc = ssrhip_kv_scatter(p->qkv, &kv, kl, p->row_seq, p->row_pos, R, s)) return rc;
 
     ssrhip_attn_args at;
     memset(&at, 0, sizeof(at));
-    at.kv = kv; at.layer = l; at.row_seq = p->row_seq; at.row_len = p->row_len;
+    at.kv = kv; at.layer = kl; at.row_seq = p->row_seq; at.row_len = p->row_len;
     at.R = R; at.max_splits = p->max_splits; at.scale = 1.0f / sqrtf((float)(D / d.n_head));
     at.part_o = p->part_o; at.part_ml = p->part_ml;
     at.q = p->qkv; at.q_stride = 3 * D;   // q is the first third of each packed qkv row
@@ -621,23 +620,99 @@ extern "C" int ssrhip_lm_prefill(ssrhip_lm* lm, const ssrhip_prefill_args* p, ss
     memset(&g, 0, sizeof(g));
     g.A = p->o; g.W = w.out_proj_w[l]; g.bias = w.out_proj_b[l]; g.C = p->x;
     g.M = R; g.N = D; g.K = D; g.lda = D; g.ldc = D; g.residual = 1;
-    if (lm->prefill_split) g.W_split = w.out_proj_ws[l];
+    if (split) g.W_split = w.out_proj_ws[l];
     if (int rc = ssrhip_gemm(&g, s)) return rc;
 
     if (int rc = ssrhip_layernorm(p->x, w.ln2_w[l], w.ln2_b[l], 1e-5f, p->xn, R, D, s)) return rc;
     memset(&g, 0, sizeof(g));
     g.A = p->xn; g.W = w.ffn1_w[l]; g.bias = w.ffn1_b[l]; g.C = p->h;
     g.M = R; g.N = d.d_ffn; g.K = D; g.lda = D; g.ldc = d.d_ffn; g.act = SSRHIP_ACT_RELU;
-    if (lm->prefill_split) g.W_split = w.ffn1_ws[l];
+    if (split) g.W_split = w.ffn1_ws[l];
     if (int rc = ssrhip_gemm(&g, s)) return rc;
     memset(&g, 0, sizeof(g));
     g.A = p->h; g.W = w.ffn2_w[l]; g.bias = w.ffn2_b[l]; g.C = p->x;
     g.M = R; g.N = D; g.K = d.d_ffn; g.lda = d.d_ffn; g.ldc = D; g.residual = 1;
-    if (lm->prefill_split) g.W_split = w.ffn2_ws[l];
+    if (split) g.W_split = w.ffn2_ws[l];
     if (int rc = ssrhip_gemm(&g, s)) return rc;
   }
+  return 0;
+}
+
+extern "C" int ssrhip_lm_prefill(ssrhip_lm* lm, const ssrhip_prefill_args* p, ssrhip_stream_t stream) {
+  SSR_REQUIRE(lm && p && p->tok && p->pos && p->kind && p->row_seq && p->row_pos && p->row_len, "ssrhip_lm_prefill: null argument");
+  const bool tiled_attn = p->seq_start && p->n_seq > 0 && p->max_len > 0 && !getenv_flag("SSRHIP_PREFILL_ATTN_ROWWISE");
+  SSR_REQUIRE(p->x && p->xn && p->qkv && p->o && p->h && (tiled_attn || (p->part_o && p->part_ml)), "ssrhip_lm_prefill: null workspace");
+  ssrhip_kv kv = lm->b.kv;
+  if (p->table) kv.table = p->table;              // two-phase admission: the rows being filled are not in the decode step's table yet
+  if (int rc = lm_layer_loop(lm->d, lm->w, lm->prefill_split, kv, p, tiled_attn, (hipStream_t)stream)) return rc;
   if (p->no_embed) return 0;
   return ssrhip_lm_embed_pending(lm, stream);
+}
+
+extern "C" int ssrhip_lm_score(const ssrhip_lm_dims* d, const ssrhip_lm_weights* w, const ssrhip_score_args* a, ssrhip_stream_t stream) {
+  SSR_REQUIRE(d && w && a, "ssrhip_lm_score: null argument");
+  SSR_REQUIRE(a->tok && a->pos && a->kind && a->row_seq && a->row_pos && a->row_len && a->seq_start && a->score_first && a->score_count &&
+              a->target && a->nll && a->rank, "ssrhip_lm_score: null row / target / output array");
+  SSR_REQUIRE(a->x && a->xn && a->qkv && a->o && a->h && a->hs && a->head_h && a->logits && a->kv.pool && a->kv.table,
+              "ssrhip_lm_score: null workspace");
+  SSR_REQUIRE(a->kv.n_layer == 1, "ssrhip_lm_score: the scratch pool holds one layer (kv.n_layer = %d)", a->kv.n_layer);
+  SSR_REQUIRE(a->kv.n_head == d->n_head && a->kv.head_dim * d->n_head == d->d_model, "ssrhip_lm_score: kv heads do not match the dims");
+  SSR_REQUIRE(a->R > 0 && a->n_seq > 0 && a->max_len > 0 && a->M > 0 && a->head_chunk > 0, "ssrhip_lm_score: empty problem");
+  SSR_REQUIRE(d->n_codebooks >= 1 && d->n_codebooks <= SSRHIP_MAX_CODEBOOKS, "ssrhip_lm_score: n_codebooks %d", d->n_codebooks);
+  SSR_REQUIRE(w->lnf_w && w->lnf_b && w->head1_w && w->head1_b && w->head2_w && w->head2_b, "ssrhip_lm_score: null head weights");
+  SSR_REQUIRE(!a->head1_ws == !a->head2_ws, "ssrhip_lm_score: head split planes come both or none");
+  // the scored rows: inside the R rows, M in total (host arrays; checked before anything is launched)
+  long m_sum = 0;
+  for (int sq = 0; sq < a->n_seq; ++sq) {
+    const int f = a->score_first[sq], c = a->score_count[sq];
+    SSR_REQUIRE(f >= 0 && c >= 0 && (long)f + c <= a->R, "ssrhip_lm_score: scored rows of sequence %d outside the %d rows", sq, a->R);
+    m_sum += c;
+  }
+  SSR_REQUIRE(m_sum == a->M, "ssrhip_lm_score: score_count sums to %ld, M = %d", m_sum, a->M);
+  const int D = d->d_model, K = d->n_codebooks, Hh = d->head_hidden, card = d->card, ldc = (card + 3) / 4 * 4;
+  hipStream_t s = (hipStream_t)stream;
+  const char* e = getenv("SSRHIP_PREFILL_SPLIT");
+  const bool split_ok = !(e && e[0] == '0');
+  const bool layer_split = split_ok && w->in_proj_ws && w->out_proj_ws && w->ffn1_ws && w->ffn2_ws;
+  const bool head_split = split_ok && a->head1_ws;
+
+  ssrhip_prefill_args p;
+  memset(&p, 0, sizeof(p));
+  p.tok = a->tok; p.pos = a->pos; p.kind = a->kind;
+  p.row_seq = a->row_seq; p.row_pos = a->row_pos; p.row_len = a->row_len;
+  p.R = a->R; p.max_splits = (a->max_len + SSRHIP_PAGE - 1) / SSRHIP_PAGE;
+  p.x = a->x; p.xn = a->xn; p.qkv = a->qkv; p.o = a->o; p.h = a->h;
+  p.seq_start = a->seq_start; p.n_seq = a->n_seq; p.max_len = a->max_len;
+  if (int rc = lm_layer_loop(*d, *w, layer_split, a->kv, &p, true, s)) return rc;
+
+  // final LayerNorm of the scored rows only, gathered by the launch itself: one launch per sequence (its scored rows are contiguous)
+  long off = 0;
+  for (int sq = 0; sq < a->n_seq; ++sq) {
+    const int c = a->score_count[sq];
+    if (c == 0) continue;
+    if (int rc = ssrhip_layernorm(a->x + (size_t)a->score_first[sq] * D, w->lnf_w, w->lnf_b, 1e-5f, a->hs + (size_t)off * D, c, D, s)) return rc;
+    off += c;
+  }
+  // prediction heads in chunks of rows: head 1 of all codebooks in one GEMM (+GELU), then per codebook head 2 -> logits -> CE / rank
+  for (int m0 = 0; m0 < a->M; m0 += a->head_chunk) {
+    const int mc = a->M - m0 < a->head_chunk ? a->M - m0 : a->head_chunk;
+    ssrhip_gemm_args g;
+    memset(&g, 0, sizeof(g));
+    g.A = a->hs + (size_t)m0 * D; g.W = w->head1_w; g.bias = w->head1_b; g.C = a->head_h;
+    g.M = mc; g.N = K * Hh; g.K = D; g.lda = D; g.ldc = K * Hh; g.act = SSRHIP_ACT_GELU_ERF;
+    if (head_split) g.W_split = a->head1_ws;
+    if (int rc = ssrhip_gemm(&g, s)) return rc;
+    for (int k = 0; k < K; ++k) {
+      memset(&g, 0, sizeof(g));
+      g.A = a->head_h + (size_t)k * Hh; g.W = w->head2_w + (size_t)k * card * Hh; g.bias = w->head2_b + (size_t)k * card; g.C = a->logits;
+      g.M = mc; g.N = card; g.K = Hh; g.lda = K * Hh; g.ldc = ldc;
+      if (head_split) g.W_split = a->head2_ws + (size_t)k * 3 * card * Hh;
+      if (int rc = ssrhip_gemm(&g, s)) return rc;
+      const size_t o = (size_t)k * a->M + m0;
+      if (int rc = ssrhip_xent_rank(a->logits, ldc, card, a->target + o, mc, a->nll + o, a->rank + o, stream)) return rc;
+    }
+  }
+  return 0;
 }
 
 extern "C" int ssrhip_lm_embed_pending(ssrhip_lm* lm, ssrhip_stream_t stream) {

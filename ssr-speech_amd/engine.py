@@ -142,6 +142,25 @@ class LMWeightsArena:
         self.generation += 1
         return True
 
+    def ensure_head_split_planes(self) -> bool:
+        """The two head matrices as three bf16 planes each for the many-row head GEMMs of `ssrhip_lm_score` (ssrhip_score_args.head1_ws /
+        head2_ws): head1_w [K*Hh][D] as one [3][K*Hh][D], each codebook's head2_w[k] separately, [K][3][card][Hh] (+6 bytes per head
+        weight = +~100 MB at 830M). Not built under `SSRHIP_PREFILL_SPLIT=0`. Returns True when created now. The decode step never reads
+        them, so the engines' pointers do not change."""
+        if getattr(self, "_hs_ready", False) or os.environ.get("SSRHIP_PREFILL_SPLIT", "1")[:1] == "0":
+            return False
+        lib = _lib.lib()
+
+        def split(Wm):
+            planes = torch.empty(3 * Wm.numel(), dtype=torch.int16, device=Wm.device)
+            _lib.check(lib.ssrhip_split_weights(Wm.data_ptr(), planes.data_ptr(), Wm.numel(), _lib.stream_ptr()), "ssrhip_split_weights")
+            return planes
+
+        self.head1_ws = split(self.head1_w)
+        self.head2_ws = torch.cat([split(self.head2_w[k]) for k in range(self.K)])
+        self._hs_ready = True
+        return True
+
     def ensure_positions(self, n: int) -> bool:
         """Grow the sinusoidal table so that positions [0, n) exist, like `SinePositionalEmbedding.extend_pe` does on demand
         (models/modules/embedding.py:66-92: no length limit in the reference). Returns True when the table was rebuilt

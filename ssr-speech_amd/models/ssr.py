@@ -4,11 +4,13 @@
 libssrhip.so (hand-written HIP for gfx950); this file holds only host orchestration.
 
 There is no CPU fallback: `inference` raises if the HIP library or a GPU is missing.
-`forward(batch)` (the training loss, models/ssr.py:280-379) is outside this package's scope and raises.
+`forward(batch)` (the training loss, models/ssr.py:280-379) is outside this package's scope and raises; `score(batch)` returns the
+same numbers (loss, top-10 accuracy, token counts) for evaluation, without autograd.
 """
 from __future__ import annotations
 
 import copy
+import ctypes as C
 import logging
 import time
 from argparse import Namespace
@@ -18,7 +20,9 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from .. import _lib
 from .. import layout as LY
+from .. import score as SC
 from ..engine import MAX_ROWS, DecodeEngine, DecodeKnobs, LMWeightsArena, TorchCpuNoiseFeed
 from ..weights import lm_param_specs
 
@@ -92,7 +96,8 @@ class SSR_Speech(nn.Module):
 
     def forward(self, batch):
         raise NotImplementedError("SSR_Speech.forward (training loss, reference models/ssr.py:280-379) is outside the "
-                                  "scope of ssr_speech_amd: only the inference hot path is implemented.")
+                                  "scope of ssr_speech_amd: only the inference hot path is implemented. SSR_Speech.score(batch) "
+                                  "returns its loss, top-10 accuracy and token counts without autograd.")
 
     # ------------------------------------------------------------------ engine management
     def _get_engine(self, n_utt: int, use_cfg: bool, need_seq: int, need_steps: int, need_pages: Optional[int] = None) -> DecodeEngine:
@@ -132,6 +137,93 @@ class SSR_Speech(nn.Module):
         eng = DecodeEngine(self._arena, n_utt, use_cfg, cap_seq, cap_steps, debug_logits=self.debug_logits, pool_pages=pool, page_order=order)
         self._engines[key] = eng
         return eng
+
+    # ------------------------------------------------------------------ teacher-forced scoring
+    @torch.no_grad()
+    def score(self, batch: dict, max_rows: int = 16384) -> Optional[dict]:
+        """What the reference's `forward(batch)` returns (models/ssr.py:280-379), computed for evaluation: `loss`, `top10acc`,
+        `top10acc_by_codebook`, `effective_ntoken` with the reference's types, on the model's device; plus `nll_by_item` [B] (cross entropy
+        summed over every codebook's loss positions, unweighted) and `ntoken_by_item` [B] (their count) for rescoring.
+
+        batch: the collated batch of data/gigaspeech.py:298-321 — x [B,S], x_lens [B], y [B,K,T] (rearranged / shifted / mask-inserted,
+        padded with audio_pad_token), y_lens [B]. An empty batch returns None. The items are packed without padding rows into launches of
+        at most `max_rows` rows (an item longer than that is a launch of its own); scratch memory grows with `max_rows` (DESIGN I.9).
+        Top-10 hits count targets with fewer than 10 strictly larger logits: exact ties at the 10th place count as hits."""
+        items = SC.validate(batch, self.args)          # ValueError before anything reaches the device
+        if items is None:
+            return None
+        dev = self.device
+        if dev.type != "cuda":
+            raise RuntimeError("ssr_speech_amd.SSR_Speech.score needs the model on a ROCm GPU (model.to('cuda')); "
+                               "there is no CPU path in this package.")
+        if self._arena is None:
+            self._arena = LMWeightsArena(self.args, self.state_dict(), dev)
+        a = self._arena
+        B, K = len(items), a.K
+        work = [it for it in items if it.n_scored > 0]                      # an item with y_len < 2 has no scored position
+        longest = max([max(it.text.shape[0], it.audio.shape[1]) for it in work], default=0)
+        if a.ensure_positions(longest + 1):            # long items: grow the position table, and drop the engines built on the old one
+            for e in self._engines.values():
+                e.close()
+            self._engines = {}
+        a.ensure_split_planes()
+        a.ensure_head_split_planes()
+        lib = _lib.lib()
+        dims = a.dims()
+        w = a.c_struct()
+        keep = dict(a._arrays)
+        chunks = SC.plan_chunks([it.rows for it in work], max_rows)
+        nlls, ranks, tgts = [], [], []
+        f32 = dict(dtype=torch.float32, device=dev)
+        ldc = (a.card + 3) // 4 * 4
+        hd = a.D // a.H
+        ws = None
+        for ch in chunks:
+            pk = SC.pack_items([work[i] for i in ch], K)
+            R, M, S = int(pk["tok"].shape[0]), int(pk["target"].shape[1]), len(ch)
+            Rc = max(R, ws["R"] if ws is not None else 0)
+            if ws is None or ws["R"] < R:
+                ws = dict(R=Rc, x=torch.empty(Rc, a.D, **f32), xn=torch.empty(Rc, a.D, **f32), qkv=torch.empty(Rc, 3 * a.D, **f32),
+                          o=torch.empty(Rc, a.D, **f32), h=torch.empty(Rc, a.F, **f32))
+            hc = min(M, 4096)
+            if ws.get("hc", 0) < hc:
+                ws.update(hc=hc, head_h=torch.empty(hc, K * a.Hh, **f32), logits=torch.empty(hc, ldc, **f32))
+            npg = int(pk["n_pages"])
+            if ws.get("pages", 0) < npg:
+                ws.update(pages=npg, pool=torch.empty(npg * 2 * a.H * _lib.PAGE * hd, **f32))
+            # every integer array of the chunk in ONE host -> device copy, addressed by views
+            parts = [pk[k].reshape(-1).astype(np.int32) for k in ("tok", "pos", "kind", "row_seq", "row_pos", "row_len", "seq_start", "target", "table")]
+            offs = np.concatenate([[0], np.cumsum([p_.size for p_ in parts])])
+            ints = torch.from_numpy(np.concatenate(parts)).pin_memory().to(dev, non_blocking=True)
+            view = lambda i: ints[int(offs[i]): int(offs[i + 1])]
+            nll = torch.empty(K, M, **f32)
+            rank = torch.empty(K, M, dtype=torch.int32, device=dev)
+            sa = _lib.ScoreArgs()
+            for i, name in enumerate(("tok", "pos", "kind", "row_seq", "row_pos", "row_len", "seq_start")):
+                setattr(sa, name, view(i).data_ptr())
+            sa.R, sa.n_seq, sa.max_len = R, S, int(pk["max_len"])
+            sa.x, sa.xn, sa.qkv, sa.o, sa.h = (ws[k].data_ptr() for k in ("x", "xn", "qkv", "o", "h"))
+            sa.kv = _lib.KV(ws["pool"].data_ptr(), view(8).data_ptr(), int(pk["table"].shape[1]), 1, a.H, hd)
+            first, count = np.ascontiguousarray(pk["score_first"]), np.ascontiguousarray(pk["score_count"])
+            sa.score_first, sa.score_count, sa.M = first.ctypes.data, count.ctypes.data, M
+            sa.target, sa.nll, sa.rank = view(7).data_ptr(), nll.data_ptr(), rank.data_ptr()
+            sa.hs = ws["xn"].data_ptr()                # the final LayerNorm's output of the scored rows: xn is free after the layer loop
+            sa.head_h, sa.logits, sa.head_chunk = ws["head_h"].data_ptr(), ws["logits"].data_ptr(), hc
+            if getattr(a, "_hs_ready", False):
+                sa.head1_ws, sa.head2_ws = a.head1_ws.data_ptr(), a.head2_ws.data_ptr()
+            _lib.check(lib.ssrhip_lm_score(C.byref(dims), C.byref(w), C.byref(sa), _lib.stream_ptr()), "ssrhip_lm_score")
+            nlls.append(nll)
+            ranks.append(rank)
+            tgts.append(view(7).view(K, M))
+        del keep
+        idx = SC.scored_index(work)
+        if nlls:
+            nll, rank, tgt = torch.cat(nlls, 1), torch.cat(ranks, 1), torch.cat(tgts, 1)
+        else:
+            nll, rank, tgt = torch.zeros(K, 0, **f32), torch.zeros(K, 0, dtype=torch.int32, device=dev), torch.zeros(K, 0, dtype=torch.int32, device=dev)
+        out = SC.reduce(nll, rank, tgt, torch.from_numpy(idx["item"]).to(dev), torch.from_numpy(idx["pos"]).to(dev), B, self.args)
+        self.last_score = dict(chunks=len(chunks), rows=sum(it.rows for it in work), scored_rows=int(nll.shape[1]), nll=nll, rank=rank)
+        return out
 
     # ------------------------------------------------------------------ inference
     @torch.no_grad()
