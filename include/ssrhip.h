@@ -75,26 +75,30 @@ typedef struct ssrhip_gemv_args {
   const int32_t* row_len;                                        /* [B] keys visible to each row */
   /* EPI_QKV_APPEND: N == 3K; q -> y, k/v -> cache at position kv_pos[b] of sequence b */
   ssrhip_kv kv; int32_t layer; const int32_t* kv_pos;
-  /* 5..16 rows only (matrix-core path): activations in the 16-column tiled layout SSRHIP_TILED(b,k) below instead of
-   * row-major [B][stride]; x_stride / y_stride are ignored for a tiled operand. QKV_APPEND's q output is always row-major. */
+  /* 5..32 rows only (matrix-core path): activations in the 16-column tiled layout SSRHIP_TILED_P(b,k,K) below instead of
+   * row-major [B][stride] (K = the operand's full width: groups*K for x, groups*N for y); x_stride / y_stride are ignored for a
+   * tiled operand. QKV_APPEND's q output is always row-major. */
   int32_t x_tiled, y_tiled;
-  /* 5..16 rows only: W is stored in the matrix core's streaming order instead of [N][K] (see SSRHIP_WTILED_INDEX): one
+  /* 5..32 rows only: W is stored in the matrix core's streaming order instead of [N][K] (see SSRHIP_WTILED_INDEX): one
    * wave-level load then reads 8 full 128-byte lines instead of 64 sixteen-byte pieces of 16 different rows. */
   int32_t w_tiled;
 } ssrhip_gemv_args;
 
-/* Streaming-order weight layout for the 5..16-row GEMV (`w_tiled`): rows are grouped in 8-row units (the last unit zero-padded),
+/* Streaming-order weight layout for the 5..32-row GEMV (`w_tiled`): rows are grouped in 8-row units (the last unit zero-padded),
  * K in 16-float steps; the 512-byte block of (unit u, k-step t) holds, at float4 index ks*8 + c, the four weights
  * W[8u + c][16t + 4ks .. 16t + 4ks + 3]   (c = 0..7 row inside the unit, ks = 0..3 k-slot of the 16x16x4 MFMA).
  * Blocks of one unit are contiguous along t, units follow each other: float index of W[n][k] is
  *   ((n/8) * (K/16) + k/16) * 128 + (((k%16)/4) * 8 + n%8) * 4 + k%4 ;  a group's matrix takes ceil(N/8)*8*K floats. */
 #define SSRHIP_WTILED_INDEX(n, k, K) ((((size_t)(n) / 8) * ((size_t)(K) / 16) + (size_t)(k) / 16) * 128 + ((((k) % 16) / 4) * 8 + (n) % 8) * 4 + (k) % 4)
 
-/* 16-column tiled activation layout used between the kernels of the 5..16-row decode step: element (row b, feature k) of a
+/* 16-column tiled activation layout used between the kernels of the 5..32-row decode step: element (row b, feature k) of a
  * [<=16][K] activation lives at float index ((k/4)*16 + b)*4 + k%4, i.e. 4 consecutive features of the 16 rows are 256
- * contiguous bytes — exactly what one 64-lane MFMA B-operand load wants (a whole KiB per wave instruction). Buffer size is
- * always 16*K floats. */
+ * contiguous bytes — exactly what one 64-lane MFMA B-operand load wants (a whole KiB per wave instruction). */
 #define SSRHIP_TILED(b, k) ((((size_t)(k) >> 2) * 16 + (size_t)(b)) * 4 + ((k) & 3))
+/* Paneled form for up to 32 rows: row b of a [B][K] tiled activation lives in panel b/16, panel p starts at float offset p*16*K,
+ * and inside a panel the layout is SSRHIP_TILED(b % 16, k). For b < 16 this is SSRHIP_TILED(b, k). A buffer holds
+ * ceil(B/16)*16*K floats (16*K for 5..16 rows). */
+#define SSRHIP_TILED_P(b, k, K) (((size_t)(b) >> 4) * 16 * (size_t)(K) + SSRHIP_TILED((b) & 15, k))
 
 int ssrhip_gemv(const ssrhip_gemv_args* a, ssrhip_stream_t stream);
 
@@ -139,7 +143,7 @@ typedef struct ssrhip_attn_args {
   int32_t R, max_splits;   /* max_splits >= ceil(max(row_len)/SSRHIP_PAGE) */
   float scale;             /* 1/sqrt(head_dim) */
   float* part_o; float* part_ml;
-  int32_t out_tiled;       /* ssrhip_attn_combine only: write `out` in the SSRHIP_TILED layout (R <= 16) */
+  int32_t out_tiled;       /* ssrhip_attn_combine / ssrhip_attn_rows: write `out` in the SSRHIP_TILED_P layout (R <= 32) */
   /* ssrhip_attn_decode only, optional (NULL = off; an experiment that did not pay, DESIGN.md Part I.5): while this latency-bound launch runs, workgroup i (linear launch index, the first 256)
    * touches floats [i * prefetch_floats, (i + 1) * prefetch_floats) of `prefetch` with plain loads whose results nobody reads — the weights
    * the NEXT launch's workgroup i will stream (workgroup i of both launches runs on XCD i % 8, so they land in the right L2). */
@@ -151,7 +155,7 @@ int ssrhip_attn_combine(const ssrhip_attn_args* a, float* out /* [R][n_head*head
 /* The same attention (activation.py:634, tgt_len == 1) WITHOUT splitting over pages: one workgroup per (row, head) walks the
  * row's pages with an online softmax and writes the normalised output row directly (part_o / part_ml unused, may be NULL;
  * `out` must not alias q; out_tiled as for ssrhip_attn_combine). Meant for many rows (rows x heads >= the number of CUs): the
- * 5..16-row decode step. */
+ * 5..32-row decode step. */
 int ssrhip_attn_rows(const ssrhip_attn_args* a, float* out /* [R][n_head*head_dim] */, ssrhip_stream_t stream);
 /* Causal attention of whole PROMPTS (activation.py:634 with the mask of ssr.py:227-255, tgt_len = prompt length): the rows of
  * sequence s are rows seq_start[s] .. seq_start[s+1]-1 of q / out (positions 0 .. len-1, in order); K/V are read from the paged
@@ -178,7 +182,7 @@ typedef struct ssrhip_embed_args {
   const int32_t* kind;     /* [R] or NULL (all audio) */
   int32_t R, D, K, card;
   float* out;              /* [R][D] */
-  int32_t out_tiled;       /* write `out` in the SSRHIP_TILED layout (R <= 16) */
+  int32_t out_tiled;       /* write `out` in the SSRHIP_TILED_P layout (R <= 32) */
 } ssrhip_embed_args;
 
 int ssrhip_embed(const ssrhip_embed_args* a, ssrhip_stream_t stream);
@@ -372,7 +376,7 @@ typedef struct ssrhip_lm_weights {      /* device pointers; per-layer arrays hav
   const float* lnf_w; const float* lnf_b;
   const float* head1_w; const float* head1_b;   /* [K*Hh][D], [K*Hh]   (predict_layer.k.0 stacked) */
   const float* head2_w; const float* head2_b;   /* [K][card][Hh], [K][card] (predict_layer.k.2 stacked) */
-  /* optional second copy of the six matrices in the streaming order of the 5..16-row GEMV (SSRHIP_WTILED_INDEX; all NULL = absent).
+  /* optional second copy of the six matrices in the streaming order of the 5..32-row GEMV (SSRHIP_WTILED_INDEX; all NULL = absent).
    * Used by the decode steps of engines with more than 4 rows; the prefill GEMMs and the <= 4-row GEMV read the [N][K] copies. */
   const float* const* in_proj_wt; const float* const* out_proj_wt; const float* const* ffn1_wt; const float* const* ffn2_wt;
   const float* head1_wt; const float* head2_wt;
@@ -389,7 +393,7 @@ typedef struct ssrhip_lm_dims {
 } ssrhip_lm_dims;
 
 typedef struct ssrhip_lm_buffers {      /* caller-allocated device workspaces */
-  int32_t B, n_utt, max_splits;
+  int32_t B, n_utt, max_splits;   /* B in {1, 2, 4} or 5..32 rows; with B > 4, x / q / h hold ceil(B/16)*16 rows (SSRHIP_TILED_P) */
   int32_t pair_mode;   /* 2-row engines: 0 = pair launches if this engine may hold the device's pairing slot (ssrhip_lm_create), 1 = never,
                           2 = always (tests of the give-up path: no slot taken, no guard) */
   float* x;        /* [B][D] residual stream */

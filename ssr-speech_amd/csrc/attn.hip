@@ -219,7 +219,7 @@ __global__ __launch_bounds__(64) void attn_combine_kernel(const ssrhip_attn_args
   if (!live) return;
   const float inv = 1.0f / den;
   const int e = h * HD + d;
-  float* dst = a.out_tiled ? out + SSRHIP_TILED(r, e) : out + (size_t)r * D + e;
+  float* dst = a.out_tiled ? out + SSRHIP_TILED_P(r, e, D) : out + (size_t)r * D + e;
   *reinterpret_cast<float4*>(dst) = make_float4(acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv);
 }
 
@@ -342,7 +342,7 @@ __global__ __launch_bounds__(512) void attn_rows_kernel(const ssrhip_attn_args a
     }
     const float inv = 1.0f / L;
     const int e = h * HD + c4;
-    float* dst = a.out_tiled ? out + SSRHIP_TILED(r, e) : out + (size_t)r * H * HD + e;
+    float* dst = a.out_tiled ? out + SSRHIP_TILED_P(r, e, H * HD) : out + (size_t)r * H * HD + e;
     *reinterpret_cast<float4*>(dst) = make_float4(acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv);
   }
 }
@@ -522,7 +522,7 @@ extern "C" int ssrhip_attn_prefill(const ssrhip_attn_args* a, const int32_t* seq
 extern "C" int ssrhip_attn_rows(const ssrhip_attn_args* a, float* out, ssrhip_stream_t stream) {
   if (int e = check(a, "ssrhip_attn_rows")) return e;
   SSR_REQUIRE(out && out != a->q, "ssrhip_attn_rows: out is null or aliases q");
-  SSR_REQUIRE(!a->out_tiled || a->R <= 16, "ssrhip_attn_rows: tiled output needs R <= 16");
+  SSR_REQUIRE(!a->out_tiled || a->R <= 32, "ssrhip_attn_rows: tiled output needs R <= 32");
   SSR_REQUIRE(a->R <= MAX_GRID_ROWS, "ssrhip_attn_rows: R too large");
   SSR_REQUIRE(a->kv.max_pages <= ATTN_ROWS_MAX_PAGES, "ssrhip_attn_rows: more than %d pages per row", ATTN_ROWS_MAX_PAGES);
   dim3 grid(a->kv.n_head, a->R);
@@ -564,7 +564,7 @@ extern "C" int ssrhip_attn_decode(const ssrhip_attn_args* a, ssrhip_stream_t str
 extern "C" int ssrhip_attn_combine(const ssrhip_attn_args* a, float* out, ssrhip_stream_t stream) {
   if (int e = check(a, "ssrhip_attn_combine")) return e;
   SSR_REQUIRE(out && a->part_o && a->part_ml, "ssrhip_attn_combine: out or the partial buffers are null");
-  SSR_REQUIRE(!a->out_tiled || a->R <= 16, "ssrhip_attn_combine: tiled output needs R <= 16");
+  SSR_REQUIRE(!a->out_tiled || a->R <= 32, "ssrhip_attn_combine: tiled output needs R <= 32");
   const size_t D = (size_t)a->kv.n_head * a->kv.head_dim;
   for (int r0 = 0; r0 < a->R; r0 += MAX_GRID_ROWS) {
     const int n = min(a->R - r0, (int)MAX_GRID_ROWS);

@@ -169,7 +169,7 @@ struct StepShapes {
   const ssrhip_lm_weights& w;
   const ssrhip_lm_buffers& b;
   const int D, B, K, Hh;
-  const int tiled;     // 5..16 rows: x, the combined attention output and h live in the 16-column tiled layout (SSRHIP_TILED)
+  const int tiled;     // 5..32 rows: x, the combined attention output and h live in the 16-column tiled layout (SSRHIP_TILED_P)
   const bool wt;       // streaming-order weight copies for the matrix-core GEMV (include/ssrhip.h w_tiled)
   explicit StepShapes(const ssrhip_lm* lm)
       : d(lm->d), w(lm->w), b(lm->b), D(lm->d.d_model), B(lm->b.B), K(lm->d.n_codebooks), Hh(lm->d.head_hidden), tiled(lm->b.B > 4 ? 1 : 0),
@@ -253,8 +253,8 @@ int enqueue_step(ssrhip_lm* lm, hipStream_t s, Timer* tm) {
   const ssrhip_lm_weights& w = lm->w;
   const ssrhip_lm_buffers& b = lm->b;
   const int D = d.d_model, B = b.B, K = d.n_codebooks, Hh = d.head_hidden;
-  // 5..16 rows: the residual stream x, the combined attention output and the hidden h live in the 16-column tiled layout
-  // (include/ssrhip.h SSRHIP_TILED) so that the matrix-core GEMV's operand loads are contiguous KiBs
+  // 5..32 rows: the residual stream x, the combined attention output and the hidden h live in the 16-column tiled layout
+  // (include/ssrhip.h SSRHIP_TILED_P: one 16-row panel per 16 rows) so that the matrix-core GEMV's operand loads are contiguous KiBs
   const int tiled = B > 4 ? 1 : 0;
   const bool wt = tiled && w.in_proj_wt;      // streaming-order weight copies for the matrix-core GEMV (include/ssrhip.h w_tiled)
 
@@ -297,7 +297,7 @@ int enqueue_step(ssrhip_lm* lm, hipStream_t s, Timer* tm) {
       at.prefetch = w.out_proj_w[l];
       at.prefetch_floats = (D / 256) * D;                    // workgroup i of the pair launch owns rows [8 i, 8 i + 8) of W_o [D][D]
     }
-    // 5..16 rows with enough (row, head) pairs to give every CU one: the fused walk over the pages (no partials, no merge
+    // 5..32 rows with enough (row, head) pairs to give every CU one: the fused walk over the pages (no partials, no merge
     // launch); its output goes to b.h (free until FFN1 of this layer) because q is still being read by other workgroups
     const bool fused_attn = B > 4 && B * d.n_head >= 192 && b.kv.max_pages <= 256 && !getenv_flag("SSRHIP_ATTN_SPLIT");   // 256 pages: the kernel's page-id registers
     // split-KV combine + out-proj + residual
@@ -385,7 +385,7 @@ extern "C" int ssrhip_lm_create(const ssrhip_lm_dims* d, const ssrhip_lm_weights
   SSR_REQUIRE(d->d_model % d->n_head == 0, "ssrhip_lm_create: d_model %% n_head != 0");
   const int hd = d->d_model / d->n_head;
   SSR_REQUIRE(hd == 64 || hd == 128, "ssrhip_lm_create: head_dim %d not in {64,128}", hd);
-  SSR_REQUIRE(b->B == 1 || b->B == 2 || b->B == 4 || (b->B >= 5 && b->B <= 16), "ssrhip_lm_create: B=%d rows not in {1,2,4,5..16}", b->B);
+  SSR_REQUIRE(b->B == 1 || b->B == 2 || b->B == 4 || (b->B >= 5 && b->B <= 32), "ssrhip_lm_create: B=%d rows not in {1,2,4,5..32}", b->B);
   SSR_REQUIRE(b->B <= 4 || d->ln_folded, "ssrhip_lm_create: B > 4 rows needs LayerNorm gamma/beta folded into the weights (ln_folded)");
   SSR_REQUIRE(d->n_codebooks <= SSRHIP_MAX_CODEBOOKS, "ssrhip_lm_create: too many codebooks");
   // a row's text and audio positions are both below its sequence capacity: the sinusoidal table must cover it (embed reads pe[pos])

@@ -1392,6 +1392,7 @@ int g_blocks_per_cu = 3;   // A/B in the real (dependent-launch) decode step: 1 
 }  // namespace
 
 int ssrhip_gemv_mfma_launch(const ssrhip_gemv_args* a, hipStream_t s);   // gemv_mfma.hip: 5..16 rows on the matrix core
+int ssrhip_gemv_mfma32_launch(const ssrhip_gemv_args* a, hipStream_t s); // gemv_mfma32.hip: 17..32 rows, two column panels
 
 #ifdef SSR_GEMV_PROFILE
 // debug hook of a profiling build (not part of the ABI; tools/gemv_prof.py): per-workgroup time stamps of every later gemv_seg_kernel launch
@@ -1538,9 +1539,10 @@ extern "C" int ssrhip_gemv_pair_status(const void* ws, ssrhip_stream_t stream) {
 extern "C" int ssrhip_gemv(const ssrhip_gemv_args* a, ssrhip_stream_t stream) {
   SSR_REQUIRE(a && a->W && a->y, "ssrhip_gemv: null argument");
   SSR_REQUIRE(a->N > 0 && a->groups >= 1 && a->K > 0, "ssrhip_gemv: bad N/K/groups");
+  if (a->B > 16) return ssrhip_gemv_mfma32_launch(a, (hipStream_t)stream);
   if (a->B > 4) return ssrhip_gemv_mfma_launch(a, (hipStream_t)stream);
-  SSR_REQUIRE(a->B == 1 || a->B == 2 || a->B == 4, "ssrhip_gemv: B=%d not in {1,2,4} or 5..16", a->B);
-  SSR_REQUIRE(!a->x_tiled && !a->y_tiled && !a->w_tiled, "ssrhip_gemv: the tiled activation / weight layouts are for 5..16 rows only");
+  SSR_REQUIRE(a->B == 1 || a->B == 2 || a->B == 4, "ssrhip_gemv: B=%d not in {1,2,4} or 5..32", a->B);
+  SSR_REQUIRE(!a->x_tiled && !a->y_tiled && !a->w_tiled, "ssrhip_gemv: the tiled activation / weight layouts are for 5..32 rows only");
   SSR_REQUIRE(a->pro != SSRHIP_PRO_ATTN_COMBINE || (a->kv.head_dim > 0 && a->K <= 2048 && a->B * (a->K / a->kv.head_dim) <= 256), "ssrhip_gemv: combine prologue needs K <= 2048 and B*H <= 256");
   SSR_REQUIRE(a->K > 0 && a->K % 4 == 0 && a->K <= 8192, "ssrhip_gemv: K=%d must be a multiple of 4, <= 8192", a->K);
   SSR_REQUIRE(a->N > 0 && a->groups >= 1, "ssrhip_gemv: bad N/groups");

@@ -1,0 +1,462 @@
+// gemv_mfma32.hip — the fused weight-streaming GEMV for 17..32 rows: 16 utterances x CFG rows decoded in lock-step on one GPU,
+// the weights read ONCE per step for all of them.
+//
+//   y[b][n] = epi( sum_k pro(x)[b][k] * W[n][k] + bias[n] ),   16 < B <= 32
+//
+// Same structure as the 5..16-row rows-per-workgroup kernels of gemv_mfma.hip (gemv_rows_xreg_kernel / gemv_rows_stream_kernel): rows dealt
+// in 8-row units per workgroup, K split over <= 8 waves, rolling weight requests, the LayerNorm on register-resident x, the split epilogue.
+// The one difference: the batch is two 16-column panels (include/ssrhip.h SSRHIP_TILED_P) and every weight fragment a lane loads feeds BOTH
+// column tiles — 8 v_mfma_f32_16x16x4_f32 per float4 of W instead of 4 (16 instead of 8 in the k-step-pair form), into two accumulator sets,
+// against x panel 0 and x panel 1. The HBM stream is the 16-row launch's; the matrix work doubles.
+//
+// Bit-identity: each output column gets exactly the arithmetic of the 16-row kernel — same wave K-split, same a0 / a1 interleave (or the
+// same k-step pairs where the 16-row dispatcher picks them), same wave-order merge, same LayerNorm expressions — and an fp32 MFMA column
+// does not depend on the other columns. Row b of a 32-row launch is therefore bit-identical to the same row in a 16-row launch. The host
+// plan (waves, workgroups, pair form) is the 16-row dispatcher's, so that the pair decision, which changes the order, is the same too.
+//
+// Registers (one 8-wave workgroup per CU: up to 256 VGPR + AGPR per lane): both x panels of a K <= 2048 wave slice stay resident
+// (2 x 16 float4 = 128) beside two accumulator sets and both panels' epilogue operands; the weight pipeline is 8 loads deep (16 in the
+// k-step-pair forms), the depth that fits without scratch. K > 2048 (FFN2) streams both panels beside W.
+// Columns >= B are clamped on load (row-major x) or read from the padded panel (tiled x) and masked on store.
+#include <stdlib.h>
+#include "common.h"
+#include "gemv_mfma_tile.h"
+
+namespace {
+
+struct Gemv32 {
+  ssrhip_gemv_args a;
+  int nw;       // waves per workgroup (K split)
+  int steps;    // K / 16 MFMA k-steps in total
+  int spw;      // k-steps per wave (stream kernel: multiple of 16)
+  int units;    // ceil(N / 8) 8-row units per group
+  int wgs;      // workgroups per group (gridDim.x)
+  int hd;
+};
+
+constexpr int MAXT32 = 4;   // 16-row tiles per workgroup (as gemv_mfma.hip MAXT: the plan is the 16-row dispatcher's)
+// Weight loads in flight per wave in the one-tile-per-k-step forms. 16 (the 16-row kernels' depth) does not fit 256 registers beside both
+// x panels and both epilogues without scratch, so the depth is halved (8 KiB per wave, 64 KiB per CU); the k-step-pair forms keep theirs.
+constexpr int DEP32 = 8;
+
+// The launch seen from one 16-column panel: panel 1 is rows 16..B-1 as a (B-16)-row launch, so the 16-row tile epilogue applies unchanged.
+__device__ __forceinline__ ssrhip_gemv_args panel_args(const ssrhip_gemv_args& a, int p) {
+  ssrhip_gemv_args q = a;
+  if (p == 0) { q.B = 16; return q; }
+  q.B = a.B - 16;
+  q.y = a.y + (a.y_tiled ? (size_t)16 * a.N * a.groups : (size_t)16 * a.y_stride);
+  if (a.kv_pos) q.kv_pos = a.kv_pos + 16;
+  if (a.kv.table) q.kv.table = a.kv.table + (size_t)16 * a.kv.max_pages;
+  return q;
+}
+
+// per-lane x pointer of panel p at k-step 0 (tiled: one contiguous KiB per wave instruction per k-step; row-major: row clamped to B-1)
+__device__ __forceinline__ const float* panel_xptr(const ssrhip_gemv_args& a, int grp, int p, int c, int ks) {
+  if (a.x_tiled) return a.x + (size_t)p * 16 * a.K * a.groups + (size_t)grp * a.K * 16 + (unsigned)(ks * 16 + c) * 4;
+  return a.x + (size_t)grp * a.K + (size_t)min(16 * p + c, a.B - 1) * a.x_stride + ks * 4;
+}
+
+// two-pass LayerNorm statistics of one panel's wave slice (the expressions of gemv_rows_xreg_kernel)
+template <int SPWX>
+__device__ __forceinline__ void ln_slice(const float4 (&xr)[SPWX], int tbase, int last, float* mw_out, float* q_out) {
+  const int nval = max(0, min(SPWX, last + 1 - tbase)) * 16;
+  float s = 0.f;
+#pragma unroll
+  for (int t = 0; t < SPWX; ++t) s += (xr[t].x + xr[t].y) + (xr[t].z + xr[t].w);
+  s = kslot_sum(s);
+  const float mw = nval > 0 ? s / (float)nval : 0.f;
+  float q = 0.f;
+#pragma unroll
+  for (int t = 0; t < SPWX; ++t) {
+    if (tbase + t <= last) {
+      const float dx = xr[t].x - mw, dy = xr[t].y - mw, dz = xr[t].z - mw, dw = xr[t].w - mw;
+      q += (dx * dx + dy * dy) + (dz * dz + dw * dw);
+    }
+  }
+  *mw_out = mw;
+  *q_out = kslot_sum(q);
+}
+
+template <int SPWX>
+__device__ __forceinline__ void ln_apply(float4 (&xr)[SPWX], const float (&red)[2][8][16], int nw, int c, int tbase, int last, int K, float eps) {
+  float mean = 0.f;
+  for (int v = 0; v < nw; ++v) mean += red[0][v][c] * (float)(max(0, min(SPWX, last + 1 - v * SPWX)) * 16);
+  mean /= (float)K;
+  float var = 0.f;
+  for (int v = 0; v < nw; ++v) {
+    const float d = red[0][v][c] - mean;
+    var += red[1][v][c] + (float)(max(0, min(SPWX, last + 1 - v * SPWX)) * 16) * d * d;
+  }
+  var /= (float)K;
+  const float rstd = 1.0f / sqrtf(var + eps);
+#pragma unroll
+  for (int t = 0; t < SPWX; ++t) {
+    if (tbase + t <= last) {
+      xr[t].x = (xr[t].x - mean) * rstd;
+      xr[t].y = (xr[t].y - mean) * rstd;
+      xr[t].z = (xr[t].z - mean) * rstd;
+      xr[t].w = (xr[t].w - mean) * rstd;
+    }
+  }
+}
+
+// one k-step against both panels: the a0 / a1 interleave of the 16-row kernels, once per panel, on the same weight fragment
+__device__ __forceinline__ void kstep2(const float4 wv, const float4 xa, const float4 xb, f4v& a0, f4v& a1, f4v& b0, f4v& b1) {
+  a0 = mfma4(wv.x, xa.x, a0);
+  a1 = mfma4(wv.y, xa.y, a1);
+  b0 = mfma4(wv.x, xb.x, b0);
+  b1 = mfma4(wv.y, xb.y, b1);
+  a0 = mfma4(wv.z, xa.z, a0);
+  a1 = mfma4(wv.w, xa.w, a1);
+  b0 = mfma4(wv.z, xb.z, b0);
+  b1 = mfma4(wv.w, xb.w, b1);
+}
+
+// one k-step PAIR against both panels (k-step-pair form, see gemv_rows_xreg_kernel's PAIR): per panel the aA / aB order of the 16-row kernel
+__device__ __forceinline__ void kpair2(const float4 wv, const float4 xa0, const float4 xb0, const float4 xa1, const float4 xb1,
+                                       f4v& aA0, f4v& aB0, f4v& aA1, f4v& aB1) {
+  aA0 = mfma4(wv.x, xa0.x, aA0);
+  aB0 = mfma4(wv.x, xb0.x, aB0);
+  aA1 = mfma4(wv.x, xa1.x, aA1);
+  aB1 = mfma4(wv.x, xb1.x, aB1);
+  aA0 = mfma4(wv.y, xa0.y, aA0);
+  aB0 = mfma4(wv.y, xb0.y, aB0);
+  aA1 = mfma4(wv.y, xa1.y, aA1);
+  aB1 = mfma4(wv.y, xb1.y, aB1);
+  aA0 = mfma4(wv.z, xa0.z, aA0);
+  aB0 = mfma4(wv.z, xb0.z, aB0);
+  aA1 = mfma4(wv.z, xa1.z, aA1);
+  aB1 = mfma4(wv.z, xb1.z, aB1);
+  aA0 = mfma4(wv.w, xa0.w, aA0);
+  aB0 = mfma4(wv.w, xb0.w, aB0);
+  aA1 = mfma4(wv.w, xa1.w, aA1);
+  aB1 = mfma4(wv.w, xb1.w, aB1);
+}
+
+__device__ __forceinline__ f4v pair_fold(f4v aA, f4v aB) {
+  f4v acc;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) acc[e] = aA[e] + xor32_f(aB[e]);          // rows 0..7 (lanes < 32) = own rows + rows 8..15 of lane + 32
+  return acc;
+}
+
+// K <= 2048 (SPWX = 16 k-steps per wave): both x panels of the wave's K slice in VGPRs for all of the workgroup's tiles.
+template <int PRO, bool PAIR>
+__global__ __launch_bounds__(512) void gemv_rows32_xreg(const Gemv32 p) {
+  constexpr int SPWX = 16, DEP = PAIR ? SPWX / 2 : DEP32;
+  __shared__ float red[2][2][8][16];
+  __shared__ f4v part[2][MAXT32][8][64];
+  const ssrhip_gemv_args& a = p.a;
+  const ssrhip_gemv_args a0p = panel_args(a, 0), a1p = panel_args(a, 1);
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int c = lane & 15, ks = lane >> 4;
+  const int grp = blockIdx.y;
+  const int N = a.N, K = a.K;
+  const int u_lo = (int)((long long)blockIdx.x * p.units / p.wgs), u_hi = (int)((long long)(blockIdx.x + 1) * p.units / p.wgs);
+  const int nun = u_hi - u_lo;
+  if (nun <= 0) return;                                                 // uniform; only when wgs > units
+  const int ntile = (nun + 1) >> 1;
+  const int row_lo = u_lo * 8;
+  const int last = p.steps - 1;
+  const int tbase = wave * SPWX;
+  const float* wbase = a.W + (size_t)grp * (a.w_tiled ? (size_t)p.units * 8 : (size_t)N) * K;
+  const int wstep = a.w_tiled ? 128 : 16;
+  const float* xb0 = panel_xptr(a, grp, 0, c, ks);
+  const float* xb1 = panel_xptr(a, grp, 1, c, ks);
+  const int xstep = a.x_tiled ? 256 : 16;
+
+  float4 w[PAIR ? SPWX / 2 : DEP];
+  float4 x0[SPWX], x1[SPWX];
+  const int kvpos0 = tile_kvpos(a0p, lane), kvpos1 = tile_kvpos(a1p, lane);   // the wave's oldest loads (QKV launch only)
+  __builtin_amdgcn_sched_barrier(0);
+  const float* wp = tile_wptr(wbase, row_lo, nun, 0, c, ks, N, K, a.w_tiled) + (PAIR ? (c >> 3) * 128 : 0);
+#pragma unroll
+  for (int t = 0; t < SPWX; ++t) x0[t] = ld4(xb0 + min(tbase + t, last) * xstep);
+#pragma unroll
+  for (int t = 0; t < SPWX; ++t) x1[t] = ld4(xb1 + min(tbase + t, last) * xstep);
+  __builtin_amdgcn_sched_barrier(0);
+  if (PAIR) {
+#pragma unroll
+    for (int i = 0; i < SPWX / 2; ++i) w[i] = ld_nt(wp + min(tbase + 2 * i, last - 1) * wstep);   // host: steps even
+  } else {
+#pragma unroll
+    for (int i = 0; i < DEP; ++i) w[i] = ld_nt(wp + min(tbase + i, last) * wstep);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  const bool epi_mine = wave < ntile;
+  const int mine_rows = epi_mine ? ((2 * wave + 1 < nun) ? 16 : 8) : 0;
+  const TileEpi e0 = tile_epilogue_fetch(a0p, p.hd, grp, row_lo + wave * 16, mine_rows, lane, kvpos0);
+  const TileEpi e1 = tile_epilogue_fetch(a1p, p.hd, grp, row_lo + wave * 16, mine_rows, lane, kvpos1);
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int t = 0; t < SPWX; ++t) {
+    asm volatile("" : "+v"(x0[t].x), "+v"(x0[t].y), "+v"(x0[t].z), "+v"(x0[t].w));
+    asm volatile("" : "+v"(x1[t].x), "+v"(x1[t].y), "+v"(x1[t].z), "+v"(x1[t].w));
+  }
+#pragma unroll
+  for (int t = 0; t < SPWX; ++t)
+    if (tbase + t > last) { x0[t] = make_float4(0.f, 0.f, 0.f, 0.f); x1[t] = x0[t]; }
+
+  if (PRO == SSRHIP_PRO_LAYERNORM) {
+    // per panel: the 16-row kernel's LayerNorm (per-wave two-pass, slices merged by the pairwise-update identity), ONE barrier for both
+    float m0, q0, m1, q1;
+    ln_slice<SPWX>(x0, tbase, last, &m0, &q0);
+    ln_slice<SPWX>(x1, tbase, last, &m1, &q1);
+    if (ks == 0) { red[0][0][wave][c] = m0; red[0][1][wave][c] = q0; red[1][0][wave][c] = m1; red[1][1][wave][c] = q1; }
+    __syncthreads();
+    ln_apply<SPWX>(x0, red[0], p.nw, c, tbase, last, K, a.ln_eps);
+    ln_apply<SPWX>(x1, red[1], p.nw, c, tbase, last, K, a.ln_eps);
+  }
+
+  if (PAIR) {
+    f4v aA0 = {0.f, 0.f, 0.f, 0.f}, aB0 = aA0, aA1 = aA0, aB1 = aA0;
+#pragma unroll
+    for (int i = 0; i < SPWX / 2; ++i) kpair2(w[i], x0[2 * i], x0[2 * i + 1], x1[2 * i], x1[2 * i + 1], aA0, aB0, aA1, aB1);
+    part[0][0][wave][lane] = pair_fold(aA0, aB0);
+    part[1][0][wave][lane] = pair_fold(aA1, aB1);
+    __syncthreads();
+    if (wave == 0) {
+      f4v s0 = part[0][0][0][lane], s1 = part[1][0][0][lane];
+      for (int v = 1; v < p.nw; ++v) { s0 += part[0][0][v][lane]; s1 += part[1][0][v][lane]; }
+      tile_epilogue_finish(a0p, e0, s0, p.hd);
+      tile_epilogue_finish(a1p, e1, s1, p.hd);
+    }
+    return;
+  }
+  // all tiles but the last: the refills past this tile's k-range fetch the head of the next tile
+  for (int tile = 0; tile < ntile - 1; ++tile) {
+    const float* wn = tile_wptr(wbase, row_lo, nun, tile + 1, c, ks, N, K, a.w_tiled);
+    f4v a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0, b0 = a0, b1 = a0;
+#pragma unroll
+    for (int t = 0; t < SPWX; ++t) {
+      kstep2(w[t % DEP], x0[t], x1[t], a0, a1, b0, b1);
+      if (t + DEP < SPWX) w[t % DEP] = ld_nt(wp + min(tbase + t + DEP, last) * wstep);
+      else w[t % DEP] = ld_nt(wn + min(tbase + t + DEP - SPWX, last) * wstep);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    part[0][tile][wave][lane] = a0 + a1;
+    part[1][tile][wave][lane] = b0 + b1;
+    wp = wn;
+  }
+  {
+    f4v a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0, b0 = a0, b1 = a0;
+#pragma unroll
+    for (int t = 0; t < SPWX; ++t) {
+      kstep2(w[t % DEP], x0[t], x1[t], a0, a1, b0, b1);
+      if (t + DEP < SPWX) w[t % DEP] = ld_nt(wp + min(tbase + t + DEP, last) * wstep);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    part[0][ntile - 1][wave][lane] = a0 + a1;
+    part[1][ntile - 1][wave][lane] = b0 + b1;
+  }
+  __syncthreads();
+  for (int tile = wave; tile < ntile; tile += p.nw) {
+    f4v s0 = part[0][tile][0][lane], s1 = part[1][tile][0][lane];
+    for (int v = 1; v < p.nw; ++v) { s0 += part[0][tile][v][lane]; s1 += part[1][tile][v][lane]; }
+    if (tile == wave) {
+      tile_epilogue_finish(a0p, e0, s0, p.hd);
+      tile_epilogue_finish(a1p, e1, s1, p.hd);
+    } else {
+      const int rows = (2 * tile + 1 < nun) ? 16 : 8;
+      tile_epilogue(a0p, p.hd, grp, row_lo + tile * 16, rows, lane, s0);
+      tile_epilogue(a1p, p.hd, grp, row_lo + tile * 16, rows, lane, s1);
+    }
+  }
+}
+
+// K > 2048 without a LayerNorm prologue (FFN2, K = 8192): both x panels are streamed beside W (L2 hits), 16 k-steps of each in flight.
+template <bool PAIR>
+__global__ __launch_bounds__(512) void gemv_rows32_stream(const Gemv32 p) {
+  constexpr int DEP = PAIR ? 16 : DEP32;     // k-steps per refill group (the k order of a column does not depend on it)
+  __shared__ f4v part[2][MAXT32][8][64];
+  const ssrhip_gemv_args& a = p.a;
+  const ssrhip_gemv_args a0p = panel_args(a, 0), a1p = panel_args(a, 1);
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int c = lane & 15, ks = lane >> 4;
+  const int grp = blockIdx.y;
+  const int N = a.N, K = a.K;
+  const int u_lo = (int)((long long)blockIdx.x * p.units / p.wgs), u_hi = (int)((long long)(blockIdx.x + 1) * p.units / p.wgs);
+  const int nun = u_hi - u_lo;
+  if (nun <= 0) return;
+  const int ntile = (nun + 1) >> 1;
+  const int row_lo = u_lo * 8;
+  const int last = p.steps - 1;
+  const int tbase = wave * p.spw;
+  const int ngrp = p.spw / DEP;                  // groups of DEP k-steps per tile for this wave
+  const float* wbase = a.W + (size_t)grp * (a.w_tiled ? (size_t)p.units * 8 : (size_t)N) * K;
+  const int wstep = a.w_tiled ? 128 : 16;
+  const float* xp0 = panel_xptr(a, grp, 0, c, ks);
+  const float* xp1 = panel_xptr(a, grp, 1, c, ks);
+  const int xstep = a.x_tiled ? 256 : 16;
+  const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+
+  float4 x0[DEP], x1[DEP];
+  const int kvpos0 = tile_kvpos(a0p, lane), kvpos1 = tile_kvpos(a1p, lane);
+  __builtin_amdgcn_sched_barrier(0);
+  const float* wp = tile_wptr(wbase, row_lo, nun, 0, c, ks, N, K, a.w_tiled) + (PAIR ? (c >> 3) * 128 : 0);
+  if (PAIR) {
+    // one 8-row unit per workgroup: per group of 16 k-steps 8 weight loads (k-step pairs) + 2 x 16 x loads
+    float4 wq[DEP / 2];
+#pragma unroll
+    for (int i = 0; i < DEP; ++i) { x0[i] = ld4(xp0 + min(tbase + i, last) * xstep); x1[i] = ld4(xp1 + min(tbase + i, last) * xstep); }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < DEP / 2; ++i) wq[i] = ld_nt(wp + min(tbase + 2 * i, last - 1) * wstep);
+    __builtin_amdgcn_sched_barrier(0);
+    const TileEpi e0 = tile_epilogue_fetch(a0p, p.hd, grp, row_lo, wave == 0 ? 8 : 0, lane, kvpos0);
+    const TileEpi e1 = tile_epilogue_fetch(a1p, p.hd, grp, row_lo, wave == 0 ? 8 : 0, lane, kvpos1);
+    __builtin_amdgcn_sched_barrier(0);
+    f4v aA0 = {0.f, 0.f, 0.f, 0.f}, aB0 = aA0, aA1 = aA0, aB1 = aA0;
+    for (int g = 0; g < ngrp - 1; ++g) {                                   // all groups but the last: refill for group g + 1
+      const int kb = tbase + g * DEP, kbn = kb + DEP;
+#pragma unroll
+      for (int i = 0; i < DEP / 2; ++i) {
+        const bool out = kb + 2 * i > last;                                // steps is even: a pair is in or out as a whole
+        kpair2(wq[i], out ? z4 : x0[2 * i], out ? z4 : x0[2 * i + 1], out ? z4 : x1[2 * i], out ? z4 : x1[2 * i + 1], aA0, aB0, aA1, aB1);
+        x0[2 * i] = ld4(xp0 + min(kbn + 2 * i, last) * xstep);
+        x0[2 * i + 1] = ld4(xp0 + min(kbn + 2 * i + 1, last) * xstep);
+        x1[2 * i] = ld4(xp1 + min(kbn + 2 * i, last) * xstep);
+        x1[2 * i + 1] = ld4(xp1 + min(kbn + 2 * i + 1, last) * xstep);
+        wq[i] = ld_nt(wp + min(kbn + 2 * i, last - 1) * wstep);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    {
+      const int kb = tbase + (ngrp - 1) * DEP;
+#pragma unroll
+      for (int i = 0; i < DEP / 2; ++i) {
+        const bool out = kb + 2 * i > last;
+        kpair2(wq[i], out ? z4 : x0[2 * i], out ? z4 : x0[2 * i + 1], out ? z4 : x1[2 * i], out ? z4 : x1[2 * i + 1], aA0, aB0, aA1, aB1);
+      }
+    }
+    part[0][0][wave][lane] = pair_fold(aA0, aB0);
+    part[1][0][wave][lane] = pair_fold(aA1, aB1);
+    __syncthreads();
+    if (wave == 0) {
+      f4v s0 = part[0][0][0][lane], s1 = part[1][0][0][lane];
+      for (int v = 1; v < p.nw; ++v) { s0 += part[0][0][v][lane]; s1 += part[1][0][v][lane]; }
+      tile_epilogue_finish(a0p, e0, s0, p.hd);
+      tile_epilogue_finish(a1p, e1, s1, p.hd);
+    }
+    return;
+  }
+  float4 w[DEP];
+#pragma unroll
+  for (int i = 0; i < DEP; ++i) { x0[i] = ld4(xp0 + min(tbase + i, last) * xstep); x1[i] = ld4(xp1 + min(tbase + i, last) * xstep); }
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int i = 0; i < DEP; ++i) w[i] = ld_nt(wp + min(tbase + i, last) * wstep);
+  __builtin_amdgcn_sched_barrier(0);
+  const bool epi_mine = wave < ntile;
+  const int mine_rows = epi_mine ? ((2 * wave + 1 < nun) ? 16 : 8) : 0;
+  const TileEpi e0 = tile_epilogue_fetch(a0p, p.hd, grp, row_lo + wave * 16, mine_rows, lane, kvpos0);
+  const TileEpi e1 = tile_epilogue_fetch(a1p, p.hd, grp, row_lo + wave * 16, mine_rows, lane, kvpos1);
+  __builtin_amdgcn_sched_barrier(0);
+  const int total = ntile * ngrp;
+  f4v a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0, b0 = a0, b1 = a0;
+  int tile = 0, kg = 0;
+  for (int g = 0; g < total - 1; ++g) {
+    // group g = (tile, kg); the refills fetch group g + 1
+    int tile_n = tile, kg_n = kg + 1;
+    if (kg_n == ngrp) { kg_n = 0; tile_n = tile + 1; }
+    const float* wn = (tile_n == tile) ? wp : tile_wptr(wbase, row_lo, nun, tile_n, c, ks, N, K, a.w_tiled);
+    const int kb = tbase + kg * DEP, kbn = tbase + kg_n * DEP;
+#pragma unroll
+    for (int t = 0; t < DEP; ++t) {
+      const bool out = kb + t > last;                                      // uniform: k-steps past the end of K contribute nothing
+      kstep2(w[t], out ? z4 : x0[t], out ? z4 : x1[t], a0, a1, b0, b1);
+      const int kk = min(kbn + t, last);
+      x0[t] = ld4(xp0 + kk * xstep);
+      x1[t] = ld4(xp1 + kk * xstep);
+      w[t] = ld_nt(wn + kk * wstep);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if (kg_n == 0) {                                                      // uniform: tile finished
+      part[0][tile][wave][lane] = a0 + a1;
+      part[1][tile][wave][lane] = b0 + b1;
+      a0 = (f4v){0.f, 0.f, 0.f, 0.f}; a1 = a0; b0 = a0; b1 = a0;
+    }
+    tile = tile_n; kg = kg_n; wp = wn;
+  }
+  {
+    const int kb = tbase + kg * DEP;
+#pragma unroll
+    for (int t = 0; t < DEP; ++t) {
+      const bool out = kb + t > last;
+      kstep2(w[t], out ? z4 : x0[t], out ? z4 : x1[t], a0, a1, b0, b1);
+    }
+    part[0][ntile - 1][wave][lane] = a0 + a1;
+    part[1][ntile - 1][wave][lane] = b0 + b1;
+  }
+  __syncthreads();
+  for (int t2 = wave; t2 < ntile; t2 += p.nw) {
+    f4v s0 = part[0][t2][0][lane], s1 = part[1][t2][0][lane];
+    for (int v = 1; v < p.nw; ++v) { s0 += part[0][t2][v][lane]; s1 += part[1][t2][v][lane]; }
+    if (t2 == wave) {
+      tile_epilogue_finish(a0p, e0, s0, p.hd);
+      tile_epilogue_finish(a1p, e1, s1, p.hd);
+    } else {
+      const int rows = (2 * t2 + 1 < nun) ? 16 : 8;
+      tile_epilogue(a0p, p.hd, grp, row_lo + t2 * 16, rows, lane, s0);
+      tile_epilogue(a1p, p.hd, grp, row_lo + t2 * 16, rows, lane, s1);
+    }
+  }
+}
+
+}  // namespace
+
+// called by ssrhip_gemv for 16 < B (validated here)
+int ssrhip_gemv_mfma32_launch(const ssrhip_gemv_args* a, hipStream_t s) {
+  SSR_REQUIRE(a->B > 16 && a->B <= 32, "ssrhip_gemv: B=%d rows not in {1,2,4} or 5..32", a->B);
+  SSR_REQUIRE(a->K % 16 == 0, "ssrhip_gemv (B>16): K=%d must be a multiple of 16", a->K);
+  SSR_REQUIRE(a->pro == SSRHIP_PRO_NONE || a->pro == SSRHIP_PRO_LAYERNORM,
+              "ssrhip_gemv (B>16): the split-KV combine prologue is not fused; run ssrhip_attn_combine first");
+  SSR_REQUIRE(a->x, "ssrhip_gemv: x is null");
+  SSR_REQUIRE(!a->y_tiled || (a->N % 4 == 0 && a->epi != SSRHIP_EPI_QKV_APPEND), "ssrhip_gemv: tiled y needs N %% 4 == 0 and is not available for the q output");
+  if (a->pro == SSRHIP_PRO_LAYERNORM) {
+    SSR_REQUIRE(a->K <= 2048, "ssrhip_gemv (B>16): LayerNorm prologue needs K=%d <= 2048", a->K);
+    SSR_REQUIRE(!a->ln_w && !a->ln_b, "ssrhip_gemv (B>16): LayerNorm gamma/beta must be folded into W/bias (ln_w == ln_b == NULL)");
+  }
+  if (a->epi == SSRHIP_EPI_QKV_APPEND) {
+    SSR_REQUIRE(a->N == 3 * a->K && a->groups == 1 && a->kv.pool && a->kv.table && a->kv_pos && a->kv.head_dim > 0 && a->kv.head_dim % 4 == 0,
+                "ssrhip_gemv: QKV epilogue needs N==3K and a kv cache");
+  }
+  // the plan is the 16-row dispatcher's (gemv_mfma.hip ssrhip_gemv_mfma_launch, rows-per-workgroup form), with the same tuning knobs:
+  // the k-step-pair decision changes the accumulation order, and a row must get the same arithmetic at 32 rows as at 16
+  static int g_cus = 0, g_wpc = 0, g_nopair = 0;
+  if (g_cus == 0) {
+    int dev = 0, cu = 0;
+    g_cus = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cu > 0) ? cu : 256;
+    const char* w = getenv("SSRHIP_GEMVM_WPC");
+    g_wpc = (w && atoi(w) >= 1 && atoi(w) <= 4) ? atoi(w) : 1;
+    g_nopair = getenv("SSRHIP_GEMVM_NOPAIR") != nullptr;
+  }
+  Gemv32 r;
+  r.a = *a;
+  r.steps = a->K / 16;
+  r.hd = a->kv.head_dim > 0 ? a->kv.head_dim : 1;
+  r.units = (a->N + 7) / 8;
+  const bool xreg = a->K <= 2048;                      // x slices of both panels in registers; else streamed beside W
+  if (xreg) {
+    r.nw = (r.steps + 15) / 16;
+    r.spw = 16;
+  } else {
+    r.nw = 8;
+    r.spw = ((r.steps + 7) / 8 + 15) / 16 * 16;
+  }
+  int target = g_cus * g_wpc * (r.nw <= 4 ? 2 : 1) / a->groups;
+  if (target < 1) target = 1;
+  r.wgs = r.units < target ? r.units : target;
+  const int need = (r.units + 2 * MAXT32 - 1) / (2 * MAXT32);
+  if (r.wgs < need) r.wgs = need;
+  SSR_REQUIRE(r.wgs <= 65535 * 32, "ssrhip_gemv (B>16): N too large");
+  dim3 grid(r.wgs, a->groups), block(r.nw * 64);
+  const bool pair = a->w_tiled && r.units <= r.wgs && r.steps % 2 == 0 && !g_nopair;
+  if (!xreg && pair) hipLaunchKernelGGL(gemv_rows32_stream<true>, grid, block, 0, s, r);
+  else if (!xreg) hipLaunchKernelGGL(gemv_rows32_stream<false>, grid, block, 0, s, r);
+  else if (a->pro == SSRHIP_PRO_LAYERNORM) hipLaunchKernelGGL((gemv_rows32_xreg<SSRHIP_PRO_LAYERNORM, false>), grid, block, 0, s, r);
+  else if (pair) hipLaunchKernelGGL((gemv_rows32_xreg<SSRHIP_PRO_NONE, true>), grid, block, 0, s, r);
+  else hipLaunchKernelGGL((gemv_rows32_xreg<SSRHIP_PRO_NONE, false>), grid, block, 0, s, r);
+  SSR_LAUNCH_CHECK();
+  return 0;
+}

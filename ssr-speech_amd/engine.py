@@ -212,7 +212,8 @@ class LMWeightsArena:
         return _lib.LMDims(self.D, self.H, self.L, self.F, self.K, self.card, self.Hh, self.n_text, self.max_pos, int(self.ln_folded))
 
 
-MAX_ROWS = 16   # gemv_mfma.hip: one 16-column MFMA tile
+MAX_ROWS = 32             # rows of one lock-step engine: two 16-column MFMA panels (gemv_mfma32.hip)
+DEFAULT_GROUP_ROWS = 16   # rows per engine pass that inference_batch / dp.* use unless `group` says otherwise (8 utterances with CFG)
 
 
 class PagePool:
@@ -379,7 +380,8 @@ class DecodeEngine:
         self._warm_pinned = self._warm_dev = None
         self._warm_free = None                    # event: the last activation has read the warm staging buffers
         self.t_first_chunk = 0.0
-        rows = self.B if self.B <= 4 else MAX_ROWS      # > 4 rows: x / q / h are 16-column tiled buffers (include/ssrhip.h SSRHIP_TILED)
+        # > 4 rows: x / q / h are 16-column tiled buffers, one 16-row panel per 16 rows (include/ssrhip.h SSRHIP_TILED_P)
+        rows = self.B if self.B <= 4 else 16 * ((self.B + 15) // 16)
         self.x = torch.zeros(rows, D, **f32)
         self.q = torch.zeros(rows, D, **f32)
         self.h = torch.zeros(rows, max(arena.F, K * arena.Hh), **f32)

@@ -23,7 +23,7 @@ import torch.nn as nn
 from .. import _lib
 from .. import layout as LY
 from .. import score as SC
-from ..engine import MAX_ROWS, DecodeEngine, DecodeKnobs, LMWeightsArena, TorchCpuNoiseFeed
+from ..engine import DEFAULT_GROUP_ROWS, MAX_ROWS, DecodeEngine, DecodeKnobs, LMWeightsArena, TorchCpuNoiseFeed
 from ..weights import lm_param_specs
 
 
@@ -363,7 +363,7 @@ class SSR_Speech(nn.Module):
         assert cfg_coef >= 1.0, cfg_coef
         rows = 2 if aug_text else 1
         if group is None:
-            group = MAX_ROWS // rows               # 16 rows per engine pass: 8 utterances with CFG
+            group = DEFAULT_GROUP_ROWS // rows     # 16 rows per engine pass: 8 utterances with CFG; up to 32 on request
         assert 1 <= group * rows <= MAX_ROWS, (group, rows)
         dev = self.device
         greedy = top_k == 1

@@ -4,8 +4,11 @@ bench.py's config-2 input and timed exactly like bench.py's headline (W untimed 
 the per-category graph-chained launch times. Variants alternate over `--reps` rounds; per variant the list of ms/step is printed with
 its minimum and median (box-to-box spread is 3-5 %, so only same-box alternating runs can resolve a 1 % change).
 
-  python tools/decode_ab.py [--utts U] [--steps K] [--warmup W] [--reps R] name:KNOB=v,KNOB=v ...
+  python tools/decode_ab.py [--utts U] [--steps K] [--warmup W] [--reps R] name[@U]:KNOB=v,KNOB=v ...
   e.g. python tools/decode_ab.py base:SSRHIP_GEMV_SEGU=0,SSRHIP_ATTN_PIN=0 segu4: segu2:SSRHIP_GEMV_SEGU=2
+`@U` gives a variant its own utterance count (default --utts), so that step widths can be compared in one process, alternating:
+  python tools/decode_ab.py --warmup 180 --steps 100 rows16@8: rows32@16:     (16 against 32 rows, timed around context ~520)
+Utterance u decodes bench.py's synth_inputs(u) prompt (config 4's input); codec-tokens/s = 4 codebooks x U / step time.
 """
 import argparse
 import dataclasses
@@ -35,8 +38,11 @@ ap.add_argument("variants", nargs="+")
 a = ap.parse_args()
 
 variants = []
+utts_of = {}
 for v in a.variants:
     name, _, kn = v.partition(":")
+    name, _, nu = name.partition("@")
+    utts_of[name] = int(nu) if nu else a.utts
     variants.append((name, dict(kv.split("=", 1) for kv in kn.split(",") if kv)))
 all_knobs = sorted({k for _, d in variants for k in d})
 
@@ -48,9 +54,8 @@ L, N = x.shape[1], y.shape[1]
 total = a.warmup + a.steps
 cated, _, num_task, _ = LY.build_layout(y[0].T.numpy(), np.asarray([[N, N]]), args_lm)
 T0 = cated.shape[1]
-U = a.utts
 text_rows = []
-for u in range(U):
+for u in range(max(utts_of.values())):
     xu, _, uu = (x, y, unc) if u == 0 else synth_inputs(args_lm, u)
     text_rows += [xu[0].numpy(), uu[0].numpy()]
 kn = DecodeKnobs(top_k=1 if a.greedy else 40, top_p=1.0 if a.greedy else 0.8, temperature=1.0, stop_repetition=2, cfg_coef=1.5, cfg_stride=5,
@@ -62,8 +67,9 @@ for rep in range(a.reps):
         for k in all_knobs:
             os.environ.pop(k, None)
         os.environ.update(knobs)
+        U = utts_of[name]
         eng = DecodeEngine(arena, U, True, ((L + T0 + total + 8 + 1023) // 1024) * 1024, ((total + 255) // 256) * 256)
-        eng.start(text_rows, [cated] * U, [dataclasses.replace(kn, seed=2024 + u) for u in range(U)], noise=None)
+        eng.start(text_rows[:2 * U], [cated] * U, [dataclasses.replace(kn, seed=2024 + u) for u in range(U)], noise=None)
         torch.cuda.synchronize()
         eng.decode(a.warmup)
         torch.cuda.synchronize()
@@ -77,15 +83,22 @@ for rep in range(a.reps):
         r["ms"].append(ms)
         r["gemv"].append(eng.time_category("gemv", 50)[0])
         r["attn"].append(eng.time_category("attn", 50)[0])
+        us_s, n_s = eng.time_category("sample", 20)
+        r["sample"].append(us_s)
+        r.setdefault("launches", {"gemv": eng.time_category("gemv", 1)[1], "attn": eng.time_category("attn", 1)[1], "sample": n_s})
         if r["tok"] is None:
             r["tok"] = tok
         del eng
         torch.cuda.empty_cache()
 
 base = variants[0][0]
-print(f"# {U} utterance(s) x CFG = {2 * U} rows, {a.steps} timed steps after {a.warmup}, {a.reps} alternating rounds; ms per step (wall), us per launch (graph-chained)")
+print(f"# {a.steps} timed steps after {a.warmup} (context {L + T0 + a.warmup} .. {L + T0 + total}), {a.reps} alternating rounds; "
+      f"ms per step (wall), codec-tokens/s at the median, us per launch (graph-chained)")
 for name, knobs in variants:
     r = res[name]
     same = "" if r["tok"] is None or res[base]["tok"] is None else f"  tokens == {base}: {bool(np.array_equal(r['tok'], res[base]['tok']))}"
-    print(f"{name:14s} ms/step min {min(r['ms']):.4f} med {statistics.median(r['ms']):.4f}  all {' '.join(f'{v:.4f}' for v in r['ms'])} | "
-          f"gemv {min(r['gemv']):.3f} attn {min(r['attn']):.3f} us{same}   [{' '.join(f'{k}={v}' for k, v in knobs.items()) or 'defaults'}]")
+    U = utts_of[name]
+    print(f"{name:14s} {U:2d} utts x CFG = {2 * U:2d} rows  tok/s {4 * U / (statistics.median(r['ms']) * 1e-3):9.1f}  "
+          f"ms/step min {min(r['ms']):.4f} med {statistics.median(r['ms']):.4f}  all {' '.join(f'{v:.4f}' for v in r['ms'])} | "
+          f"gemv {min(r['gemv']):.3f} x {r['launches']['gemv']} attn {min(r['attn']):.3f} x {r['launches']['attn']} "
+          f"sample {min(r['sample']):.3f} x {r['launches']['sample']} us{same}   [{' '.join(f'{k}={v}' for k, v in knobs.items()) or 'defaults'}]")

@@ -1,0 +1,68 @@
+"""One-GPU config 4 (bench.py's dp64 input: 64 utterances, L = 67, 150-frame prompts, seeds 1000+i / 2000+i, greedy, CFG stride 5)
+through `dp.generate` with 8 utterances x CFG per engine pass (group=8, the default: 16 rows) and 16 (group=16: 32 rows), alternating in
+ONE process. Prints one JSON line: per group the decode wall time of every round, codec-tokens/s at the best round, and whether the tokens
+of the two groupings are identical. The first pass of each grouping (engine build, graph capture) is untimed.
+
+  python tools/dp64_group_ab.py [--reps 2] [--out profiles/xxx.json]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch  # noqa: E402
+
+import ssr_speech_amd  # noqa: E402,F401
+from ssr_speech_amd import dp  # noqa: E402
+from ssr_speech_amd import weights as W  # noqa: E402
+from ssr_speech_amd.models.ssr import SSR_Speech  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--reps", type=int, default=2)
+ap.add_argument("--groups", default="8,16")
+ap.add_argument("--out", default=None)
+a = ap.parse_args()
+
+dev = torch.device("cuda", 0)
+args = W.lm_args_830m()
+model = SSR_Speech(args)
+model.load_state_dict(W.lm_state_dict(args, seed=0, device=dev))
+model = model.to(dev).eval()
+utts = []
+for i in range(64):
+    gx = torch.Generator().manual_seed(1000 + i)
+    gy = torch.Generator().manual_seed(2000 + i)
+    utts.append({"x": torch.randint(0, 100, (1, 67), generator=gx), "y": torch.randint(0, 2048, (1, 150, 4), generator=gy),
+                 "mask_interval": torch.LongTensor([[[150, 150]]])})
+kw = dict(top_k=1, top_p=1.0, temperature=1.0, stop_repetition=2, cfg_coef=1.5, cfg_stride=5, aug_text=True)
+groups = [int(g) for g in a.groups.split(",")]
+
+res = {g: {"decode_ms": [], "tokens": None} for g in groups}
+for g in groups:                                   # untimed: engine, graph capture
+    dp.generate(model, utts[:2 * g], seed=0, group=g, **kw)
+for rep in range(a.reps):
+    for g in groups:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        toks, _ = dp.generate(model, utts, seed=0, group=g, **kw)
+        torch.cuda.synchronize()
+        res[g]["decode_ms"].append(1000 * (time.perf_counter() - t0))
+        if res[g]["tokens"] is None:
+            res[g]["tokens"] = [t.cpu() for t in toks]
+n_new = sum(int(t.shape[-1]) - 150 for t in res[groups[0]]["tokens"])
+out = {"workload": "bench.py dp64 input on one GPU through dp.generate (decode only, no codec)", "new_frames_total": n_new, "reps": a.reps}
+for g in groups:
+    best = min(res[g]["decode_ms"])
+    out[f"group{g}"] = {"rows_per_engine": 2 * g, "decode_ms": [round(v, 1) for v in res[g]["decode_ms"]],
+                        "codec_tokens_per_s": round(4 * n_new / (best * 1e-3), 1)}
+ref = res[groups[0]]["tokens"]
+out["tokens_identical"] = all(len(res[g]["tokens"]) == len(ref) and all(torch.equal(x, y) for x, y in zip(res[g]["tokens"], ref)) for g in groups)
+line = json.dumps(out)
+print(line)
+if a.out:
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(line + "\n")
