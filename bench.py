@@ -1,7 +1,7 @@
 """bench.py — AR-decode throughput of the HIP engine on the BASELINE.json configuration
 "English 830M zero-shot TTS, cfg_stride=5 top-k sampling, batch=1 on one MI355X" (configs[1]).
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...)
 
 `--dump-outputs DIR` writes what the K timed steps computed (`dump_outputs`) as DIR/<name>.npy; the inputs depend on the
@@ -11,13 +11,19 @@ A "step" is one decode step of the hot path (one codec frame = 4 codec tokens pe
 batch of synthetic input: 830M-shape weights from the deterministic generator (seed 0, fp32), L=130 random
 phoneme ids, a 160-frame random prompt, CFG doubling (2 rows), top_k=40/top_p=0.8 sampling. Inputs and
 weights are resident in HBM before the timed region. One utterance per GPU (weak scaling: rank r decodes
-utterance r with seed+r, no data-path collective during decode; ONE all_gather of the generated tokens
-afterwards, timed separately).
+utterance r with seed+r, no data-path collective during decode).
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel = the weight-streaming GEMV, HBM-bound) and
-`cpu_baseline` (the oracle = CPU restatement of the reference, timed on this box's host cores, bounded sample).
+A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps, `--dump-outputs`, and ONE JSON line
+(rank 0) with `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` and the workload's description.
 
-Extras on the same line (never `value`):
+`--full` adds, on the same line, everything else the benchmark measures and checks (never `value`): four more passes of the same
+W + K steps (`ms_per_step_passes`), the same workload around context 700 (`ctx700`), `roofline` (dominant kernel = the
+weight-streaming GEMV, HBM-bound, from per-kernel timing passes of its own), with N > 1 the ONE all_gather of the generated
+tokens (`allgather_ms`, timed separately), `cpu_baseline` (the oracle = CPU restatement of the reference, timed on the host's
+cores, bounded sample) and the extra legs below. `--no-ctx700`, `--no-extras`, `--legs` and `--no-cpu-baseline` trim what
+`--full` adds.
+
+Extras of `--full` (never `value`):
   rtf_10s_tts  wav -> wav through the public API (`inference_one_sample`: codec encode of the prompt wav, prefill, sampled AR
                decode with the host-side torch RNG stream, wmencodec decode), ~10 s generated; + time to the first 16 frames.
   dp64         BASELINE config 4: 64 utterances (L=67, 150-frame prompts, seeds 1000+i / 2000+i, greedy) through `dp.generate`
@@ -524,9 +530,13 @@ def main():
     ap.add_argument("--legs", type=str, default="", help="comma separated subset of the extra legs to run (default: all)")
     ap.add_argument("--dump-outputs", metavar="DIR", default="", help="after the timed steps, write what they computed (codec tokens of the "
                     "timed steps, logits of the last step, sampler state) as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true", help="beside the headline, also the repeat passes, the context-700 region, the roofline, "
+                    "the all_gather (N > 1), the extra legs and the CPU baseline (default: the headline alone)")
     a = ap.parse_args()
     if a.steps < 1 or a.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not a.full and (a.no_cpu_baseline or a.no_extras or a.no_ctx700 or a.legs):
+        ap.error("--no-cpu-baseline, --no-extras, --no-ctx700 and --legs trim what --full adds: give --full with them")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -588,7 +598,7 @@ def main():
     # the same W + K steps again (restart, warm-up, K timed steps: same context range), listed beside the headline: the driver's timed region
     # is ~17 ms and boxes differ by 3-5 %, so one pass cannot resolve a 1 % change. `ms_per_step` stays the FIRST pass.
     extra_passes = []
-    if dist is None:
+    if a.full and dist is None:
         for _rep in range(4):
             eng.start(text_rows, [cated] * U, kns, noise=None)
             torch.cuda.synchronize()
@@ -602,6 +612,7 @@ def main():
         tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if a.full and dist is not None:
         # the one collective of the path: gather every rank's generated codec tokens (before wmencodec decode)
         from ssr_speech_amd import dp
         mine = eng.generated[0, : st.n_steps].t().contiguous()          # [K, steps] of this rank's utterance
@@ -614,10 +625,29 @@ def main():
     else:
         allgather_ms = None
 
+    out = None
     if rank == 0:
         ms_per_step = 1000 * elapsed / a.steps
         tokens_per_step = 4 * world * U                  # K=4 codebooks x 1 frame x U utterances per GPU
         value = tokens_per_step * a.steps / elapsed
+        out = {
+            "metric": "codec-tokens/sec/GPU (AR decode) + RTF for 10 s TTS, English 830M",
+            "value": round(value, 1), "unit": "codec-tokens/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+            "ms_per_step": round(ms_per_step, 4),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic",
+            "config": {"workload": f"English-830M-shape zero-shot TTS decode, cfg_stride=5, top_k=40/top_p=0.8 sampling, batch={U} ({2 * U} CFG rows) per GPU; "
+                                   f"L={L} phonemes, {N}-frame prompt ({'demo/5895_34622_000026_000002.wav, first 3.2 s, wmencodec codes' if demo_y is not None else 'random codes'}), "
+                                   f"context {L + T0 + a.warmup}..{L + T0 + total}",
+                       "utterances_per_gpu": U, "rows": 2 * U, "graph": not a.no_graph, "steps_completed": int(st.n_steps),
+                       "pair_launches": bool(eng.pairing), "pair_launches_why": eng.pairing_why},
+            "per_gpu_value": round(value / world, 1),
+            "decode_rtf_10s": round((500 * ms_per_step / 1000) / 10.0, 4),
+        }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": a.dump_outputs, "shapes": dumped}
+
+    if rank == 0 and a.full:
         # ---- roofline of the dominant kernel (weight-streaming GEMV). Two HIP-event measurements on the launch stream:
         #  * per-slot: an event pair around every launch of eager steps (per-shape view; carries ~3 us event overhead each);
         #  * category: the 66 GEMV launches of a step replayed as a hipGraph between ONE event pair -> the average launch
@@ -692,20 +722,9 @@ def main():
         S_mid = L + T0 + a.warmup + a.steps // 2
         kv_bytes = 262144 * 2 * U * S_mid * (arena.L / 16) * (arena.D / 2048)
         step_gbs = (arena.nbytes_per_step() + kv_bytes) / (ms_per_step * 1e-3) / 1e9
-        out = {
-            "metric": "codec-tokens/sec/GPU (AR decode) + RTF for 10 s TTS, English 830M",
-            "value": round(value, 1), "unit": "codec-tokens/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": round(ms_per_step, 4), "ms_per_step_passes": [round(ms_per_step, 4)] + [round(v, 4) for v in extra_passes],
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"English-830M-shape zero-shot TTS decode, cfg_stride=5, top_k=40/top_p=0.8 sampling, batch={U} ({2 * U} CFG rows) per GPU; "
-                                   f"L={L} phonemes, {N}-frame prompt ({'demo/5895_34622_000026_000002.wav, first 3.2 s, wmencodec codes' if demo_y is not None else 'random codes'}), "
-                                   f"context {L + T0 + a.warmup}..{L + T0 + total}",
-                       "utterances_per_gpu": U, "rows": 2 * U, "graph": not a.no_graph, "steps_completed": int(st.n_steps),
-                       "pair_launches": bool(eng.pairing), "pair_launches_why": eng.pairing_why},
-            "per_gpu_value": round(value / world, 1),
+        out.update({
+            "ms_per_step_passes": [round(ms_per_step, 4)] + [round(v, 4) for v in extra_passes],
             "ms_per_step_ctx700": (ctx700["ms_per_step"] if ctx700 else None), "ctx700": ctx700, "attention_share_of_step": attn_share,
-            "decode_rtf_10s": round((500 * ms_per_step / 1000) / 10.0, 4),
             "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": round(achieved / HBM_PEAK_GBS, 4),
                          # rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command (profiles/r06_pmc_*.md; `--no-ctx700`), gfx950 x2 correction
@@ -724,17 +743,13 @@ def main():
                          "step_level": {"bytes_per_step": int(arena.nbytes_per_step() + kv_bytes), "achieved": round(step_gbs, 1),
                                         "frac": round(step_gbs / HBM_PEAK_GBS, 4)},
                          "event_timed_us_per_launch": per_shape},
-        }
+        })
         if allgather_ms is not None:
             out["allgather_ms"] = round(allgather_ms, 3)
-        if dumped is not None:
-            out["dumped_outputs"] = {"dir": a.dump_outputs, "shapes": dumped}
-    else:
-        out = None
 
     # ---- extras (every rank takes part: dp64 ends in a collective). None of them feeds `value`.
     extras = {}
-    if not a.no_extras and U == 1:
+    if a.full and not a.no_extras and U == 1:
         eng.close()                              # gives the device's pairing slot back (csrc/engine.hip): the API model's engine takes it next
         del eng
         torch.cuda.empty_cache()
@@ -787,7 +802,7 @@ def main():
 
     if rank == 0:
         out.update(extras)
-        if world == 1 and not a.no_cpu_baseline and U == 1:
+        if world == 1 and a.full and not a.no_cpu_baseline and U == 1:
             out["cpu_baseline"] = cpu_baseline(args_lm, sd, x, y, unc)
             out["speedup_vs_cpu"] = round(out["value"] / out["cpu_baseline"]["value"], 1)
         print(json.dumps(out), flush=True)

@@ -3,14 +3,14 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r2z; mkdir -p $O
 cd $R
 python -m pytest tests -q -m gpu --durations=8 > $O/pytest.log 2>&1; echo "pytest rc=$?" >> $O/pytest.log; tail -14 $O/pytest.log
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1; tail -1 $O/smoke.log
-python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
-python bench.py --utts 8 --no-extras --no-cpu-baseline > $O/bench8.json 2> $O/bench8.err; echo "bench8 rc=$?"
-python bench.py --utts 2 --no-extras --no-cpu-baseline --steps 200 > $O/bench2.json 2> $O/bench2.err
-python bench.py --utts 4 --no-extras --no-cpu-baseline --steps 200 > $O/bench4.json 2> $O/bench4.err
+python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+python bench.py --full --utts 8 --no-extras --no-cpu-baseline > $O/bench8.json 2> $O/bench8.err; echo "bench8 rc=$?"
+python bench.py --full --utts 2 --no-extras --no-cpu-baseline --steps 200 > $O/bench2.json 2> $O/bench2.err
+python bench.py --full --utts 4 --no-extras --no-cpu-baseline --steps 200 > $O/bench4.json 2> $O/bench4.err
 cd /tmp; export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt1 -- python $R/bench.py --steps 200 --warmup 20 --no-extras --no-cpu-baseline > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt1 -- python $R/bench.py --full --steps 200 --warmup 20 --no-extras --no-cpu-baseline > /dev/null 2>&1
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc1_$c -- python $R/bench.py --steps 40 --warmup 5 --no-extras --no-cpu-baseline > /dev/null 2>&1
+  rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc1_$c -- python $R/bench.py --full --steps 40 --warmup 5 --no-extras --no-cpu-baseline > /dev/null 2>&1
 done
 cd $R
 python tools/prof_summary.py $(ls $O/kt1/*/*kernel_trace.csv | head -1) $O/r02_decode_kernel_trace_summary.md > /dev/null

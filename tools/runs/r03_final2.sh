@@ -10,4 +10,4 @@ cd $R
 python tools/prof_summary.py $(ls $O/kt256/*/*kernel_trace.csv | head -1) $O/r03_codec_b256_kernel_trace_summary.md > /dev/null
 rm -rf $O/kt256
 tail -1 $O/codec256.txt; head -16 $O/r03_codec_b256_kernel_trace_summary.md
-timeout 170 python bench.py --steps 200 --warmup 20 --no-cpu-baseline --legs codec256 > $O/bench_codec.json 2> $O/bench_codec.err; echo "bench rc=$?"; tail -c 1500 $O/bench_codec.json
+timeout 170 python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --legs codec256 > $O/bench_codec.json 2> $O/bench_codec.err; echo "bench rc=$?"; tail -c 1500 $O/bench_codec.json

@@ -10,5 +10,5 @@ rocprofv3 --kernel-trace --stats --output-format csv -d $O/ktw -- python $R/tool
 cd $R
 python tools/prof_summary.py $(ls $O/ktw/*/*kernel_trace.csv | head -1) $O/r03_wmdecode_b32_kernel_trace_summary.md > /dev/null
 rm -rf $O/ktw
-timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?" >> $O/rccl.log
+timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?" >> $O/rccl.log
 cat $O/rccl.log $O/codec32_wm.txt $O/codec64_wm.txt; tail -c 3000 $O/bench.json; tail -5 $O/bench.err

@@ -6,5 +6,5 @@ timeout 300 python -m pytest tests/test_gpu_kernels.py -x -q -k "resblock or gem
 SSRHIP_EPILOGUE_WIDE=0 timeout 300 python -m pytest tests/test_gpu_kernels.py -x -q -k "resblock or gemm" 2>&1 | tail -2
 python -m pytest tests -q -m gpu > $O/pytest.log 2>&1; echo "pytest rc=$?" >> $O/pytest.log; tail -5 $O/pytest.log
 python tools/codec_bench.py 256 30 2>&1 | grep "B=" | tee $O/codec256.log
-python bench.py --steps 200 --no-cpu-baseline --legs codec256 > $O/bench_codec256.json 2> $O/bench.err; echo "bench rc=$?"
+python bench.py --full --steps 200 --no-cpu-baseline --legs codec256 > $O/bench_codec256.json 2> $O/bench.err; echo "bench rc=$?"
 SSRHIP_EPILOGUE_WIDE=0 python tools/codec_bench.py 256 30 2>&1 | grep "B=" | tee $O/codec256_dword.log

@@ -7,6 +7,6 @@ d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); r=d['roofline']
 print(sys.argv[2], d['value'], d['ms_per_step'], r['us_per_launch'], r['other_kernels_us_per_launch'], r['event_timed_us_per_launch'])
 " $1 $2; }
 for rep in 1 2; do
-  SSRHIP_GEMV_SEG_TWO=0 python bench.py --no-extras --no-cpu-baseline --steps 300 --warmup 20 > $O/ab_inplace$rep.json 2>$O/ab_inplace$rep.err; show $O/ab_inplace$rep.json inplace
-  SSRHIP_GEMV_SEG_TWO=1 python bench.py --no-extras --no-cpu-baseline --steps 300 --warmup 20 > $O/ab_two$rep.json 2>$O/ab_two$rep.err; show $O/ab_two$rep.json twounits
+  SSRHIP_GEMV_SEG_TWO=0 python bench.py --full --no-extras --no-cpu-baseline --steps 300 --warmup 20 > $O/ab_inplace$rep.json 2>$O/ab_inplace$rep.err; show $O/ab_inplace$rep.json inplace
+  SSRHIP_GEMV_SEG_TWO=1 python bench.py --full --no-extras --no-cpu-baseline --steps 300 --warmup 20 > $O/ab_two$rep.json 2>$O/ab_two$rep.err; show $O/ab_two$rep.json twounits
 done

@@ -7,6 +7,6 @@ d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); r=d['roofline']
 print(sys.argv[2], d['value'], d['ms_per_step'], r['us_per_launch'], r['other_kernels_us_per_launch'], r['event_timed_us_per_launch'])
 " $1 $2; }
 for rep in 1 2; do
-  SSRHIP_GEMV_SEG_XLDS=0 python bench.py --no-extras --no-cpu-baseline --steps 300 --warmup 20 > $O/ab_off$rep.json 2>/dev/null; show $O/ab_off$rep.json perwave
-  SSRHIP_GEMV_SEG_XLDS=1 python bench.py --no-extras --no-cpu-baseline --steps 300 --warmup 20 > $O/ab_on$rep.json 2>/dev/null; show $O/ab_on$rep.json xlds
+  SSRHIP_GEMV_SEG_XLDS=0 python bench.py --full --no-extras --no-cpu-baseline --steps 300 --warmup 20 > $O/ab_off$rep.json 2>/dev/null; show $O/ab_off$rep.json perwave
+  SSRHIP_GEMV_SEG_XLDS=1 python bench.py --full --no-extras --no-cpu-baseline --steps 300 --warmup 20 > $O/ab_on$rep.json 2>/dev/null; show $O/ab_on$rep.json xlds
 done

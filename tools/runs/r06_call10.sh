@@ -4,7 +4,7 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r6c10; mkdir -p $O
 cd /tmp; export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout 900 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc1_$c -- python $R/bench.py --steps 40 --warmup 5 --no-extras --no-cpu-baseline --no-ctx700 > $O/pmc_$c.out 2> $O/pmc_$c.err
+  timeout 900 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc1_$c -- python $R/bench.py --full --steps 40 --warmup 5 --no-extras --no-cpu-baseline --no-ctx700 > $O/pmc_$c.out 2> $O/pmc_$c.err
   echo "pmc $c rc=$? files $(ls $O/pmc1_$c/*/*counter_collection.csv 2>/dev/null | wc -l)"
 done
 cd $R

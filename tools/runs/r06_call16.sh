@@ -1,7 +1,7 @@
 #!/bin/bash
 # round 6, call 16: the driver's own bench command line on the final build
 O=gpurun_out/r6c16; mkdir -p $O
-T0=$(date +%s); python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err; echo "rc=$?"
+T0=$(date +%s); python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err; echo "rc=$?"
 echo "wall $(( $(date +%s) - T0 )) s"
 wc -l $O/bench_driver_cmd.json
 python - <<PY

@@ -2,12 +2,12 @@
 # round 6, call 20: final bench lines, decode traces and PMC passes again (the merge pair launch changed), driver command line, whole suite
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r6z; mkdir -p $O
 cd $R
-python bench.py > $O/r06_bench_n1.json 2> $O/bench.err; echo "bench rc=$?"
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/r06_bench_n1_driver_cmd.json 2>/dev/null; echo "driver-cmd bench rc=$?"
+python bench.py --full > $O/r06_bench_n1.json 2> $O/bench.err; echo "bench rc=$?"
+python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/r06_bench_n1_driver_cmd.json 2>/dev/null; echo "driver-cmd bench rc=$?"
 cd /tmp; export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt1 -- python $R/bench.py --steps 200 --warmup 20 --no-extras --no-cpu-baseline > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt1 -- python $R/bench.py --full --steps 200 --warmup 20 --no-extras --no-cpu-baseline > /dev/null 2>&1
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc1_$c -- python $R/bench.py --steps 40 --warmup 5 --no-extras --no-cpu-baseline --no-ctx700 > /dev/null 2>&1
+  rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc1_$c -- python $R/bench.py --full --steps 40 --warmup 5 --no-extras --no-cpu-baseline --no-ctx700 > /dev/null 2>&1
 done
 cd $R
 python tools/prof_summary.py $(ls $O/kt1/*/*kernel_trace.csv | head -1) $O/r06_decode_kernel_trace_summary.md | tail -2

@@ -8,7 +8,7 @@ timeout 900 python -m pytest tests/test_gpu_kernels.py -x -q -k "edge_kernel or 
 timeout 900 python -m pytest tests/test_gpu_pair_guard.py tests/test_gpu_pipeline.py -x -q -k "pair or squat or engine or process or mask_spans" 2>&1 | tail -8 | tee $O/pytest_guard_cli.log
 timeout 900 python -m pytest tests/test_gpu_codec.py -x -q -k "sized or concurrent_streams" 2>&1 | tail -8 | tee $O/pytest_codec_sized.log
 for e in 1 0 1 0; do SSRHIP_GEMVM_EDGE=$e tools/bin/gemvm_bench 16 1 1 2>&1 | grep -v amdgpu.ids | sed "s/^/edge=$e /"; done | tee $O/gemvm_bench_16_edge.log
-for e in 1 0; do SSRHIP_GEMVM_EDGE=$e timeout 600 python bench.py --utts 8 --no-extras --no-cpu-baseline 2> $O/bench8_$e.err > $O/bench_n1_8utts_edge$e.json; python - <<PY
+for e in 1 0; do SSRHIP_GEMVM_EDGE=$e timeout 600 python bench.py --full --utts 8 --no-extras --no-cpu-baseline 2> $O/bench8_$e.err > $O/bench_n1_8utts_edge$e.json; python - <<PY
 import json; d=json.loads(open("$O/bench_n1_8utts_edge$e.json").read().strip().splitlines()[-1]); print("edge=$e", d["ms_per_step"], d["value"], d["roofline"]["us_per_launch"], d["roofline"]["event_timed_us_per_launch"])
 PY
 done | tee $O/bench8_edge.log

@@ -9,7 +9,7 @@ timeout 900 python -m pytest tests/test_gpu_codec.py -x -q -k "sized or concurre
 for i in 1 2 3; do timeout 300 python -m pytest tests/test_gpu_codec.py -x -q -k "concurrent_streams" 2>&1 | tail -2; done | tee -a $O/pytest_codec_sized.log
 timeout 900 python -m pytest tests/test_gpu_pair_guard.py -x -q 2>&1 | tail -8 | tee $O/pytest_guard.log
 timeout 600 python -m pytest tests/test_gpu_kernels.py -x -q -k "xcd_tile or edge_kernel or gemm_split" 2>&1 | tail -3 | tee $O/pytest_kernels.log
-timeout 900 python bench.py > $O/bench_n1.json 2> $O/bench.err; echo "bench rc=$?"; tail -c 1500 $O/bench_n1.json | head -c 400; echo
+timeout 900 python bench.py --full > $O/bench_n1.json 2> $O/bench.err; echo "bench rc=$?"; tail -c 1500 $O/bench_n1.json | head -c 400; echo
 python - <<PY
 import json; d=json.loads(open("$O/bench_n1.json").read().strip().splitlines()[-1])
 print({k: d.get(k) for k in ("value","ms_per_step","ms_per_step_passes","ms_per_step_ctx700","ctx700","attention_share_of_step")}); print(d["config"]); print(d["roofline"]["frac"], d["roofline"]["us_per_launch"]); print(d.get("cpu_baseline")); print({k: (v if not isinstance(v, dict) else {kk: vv for kk, vv in list(v.items())[:8]}) for k, v in d.get("extras", {}).items()})

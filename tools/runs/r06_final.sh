@@ -3,14 +3,14 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r6z; mkdir -p $O
 cd $R
 part=${1:-all}
 if [ "$part" = all ] || [ "$part" = bench ]; then
-python bench.py > $O/r06_bench_n1.json 2> $O/bench.err; echo "bench rc=$?"
-python bench.py --utts 8 --no-extras --no-cpu-baseline > $O/r06_bench_n1_8utts.json 2> $O/bench8.err; echo "bench8 rc=$?"
+python bench.py --full > $O/r06_bench_n1.json 2> $O/bench.err; echo "bench rc=$?"
+python bench.py --full --utts 8 --no-extras --no-cpu-baseline > $O/r06_bench_n1_8utts.json 2> $O/bench8.err; echo "bench8 rc=$?"
 fi
 cd /tmp; export TMPDIR=/tmp
 if [ "$part" = all ] || [ "$part" = prof1 ]; then
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt1 -- python $R/bench.py --steps 200 --warmup 20 --no-extras --no-cpu-baseline > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt1 -- python $R/bench.py --full --steps 200 --warmup 20 --no-extras --no-cpu-baseline > /dev/null 2>&1
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc1_$c -- python $R/bench.py --steps 40 --warmup 5 --no-extras --no-cpu-baseline --no-ctx700 > /dev/null 2>&1
+  rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc1_$c -- python $R/bench.py --full --steps 40 --warmup 5 --no-extras --no-cpu-baseline --no-ctx700 > /dev/null 2>&1
 done
 cd $R
 python tools/prof_summary.py $(ls $O/kt1/*/*kernel_trace.csv | head -1) $O/r06_decode_kernel_trace_summary.md > /dev/null
@@ -21,7 +21,7 @@ rm -rf $O/kt1 $O/pmc1_*
 cd /tmp
 fi
 if [ "$part" = all ] || [ "$part" = prof16 ]; then
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt8 -- python $R/bench.py --steps 200 --warmup 20 --utts 8 --no-extras --no-cpu-baseline > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt8 -- python $R/bench.py --full --steps 200 --warmup 20 --utts 8 --no-extras --no-cpu-baseline > /dev/null 2>&1
 cd $R
 python tools/prof_summary.py $(ls $O/kt8/*/*kernel_trace.csv | head -1) $O/r06_decode16rows_kernel_trace_summary.md > /dev/null
 cp $(ls $O/kt8/*/*kernel_stats.csv | head -1) $O/r06_rocprofv3_kernel_stats_16rows.csv
