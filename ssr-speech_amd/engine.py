@@ -18,6 +18,7 @@ import torch
 
 from . import _lib
 from ._lib import PAGE, MAX_CODEBOOKS
+from .layout import pack_prefill_rows
 
 
 def sine_pe_table(n: int, dim: int) -> torch.Tensor:
@@ -255,6 +256,50 @@ class PagePool:
             self._free.append(p)
 
 
+class IntStaging:
+    """One-copy staging of an admission's integer arrays: packed back to back into a pinned int32 buffer, sent asynchronously into its
+    persistent device twin, addressed there by views (ten small synchronous pageable copies per admit stalled the rows that
+    were still decoding). When the buffers may be reused, and what must be idle before larger ones replace them, differs between the
+    blocking and the two-phase admission and stays with them."""
+
+    def __init__(self):
+        self.pinned = self.dev = None
+        self.capacity = 0
+
+    @staticmethod
+    def offsets(sizes: Sequence[int]):
+        """(where each part starts, total) for parts of these sizes packed back to back"""
+        offs = [0]
+        for n in sizes:
+            offs.append(offs[-1] + int(n))
+        return offs[:-1], offs[-1]
+
+    @staticmethod
+    def grown(total: int, old: int) -> int:
+        return max(int(total), 2 * int(old), 4096)
+
+    def grow(self, total: int, device):
+        self.capacity = self.grown(total, self.capacity)
+        self.pinned = torch.empty(self.capacity, dtype=torch.int32).pin_memory()
+        self.dev = torch.empty(self.capacity, dtype=torch.int32, device=device)
+
+    def pack(self, parts: Sequence[np.ndarray]):
+        """Write the parts, flattened, into the host buffer; returns `offsets` of their sizes."""
+        offs, total = self.offsets([p.size for p in parts])
+        host = self.pinned.numpy()
+        for o, p in zip(offs, parts):
+            host[o:o + p.size] = p.astype(np.int32, copy=False).reshape(-1)
+        return offs, total
+
+    def send(self, parts: Sequence[np.ndarray], stream=None) -> List[torch.Tensor]:
+        """Pack the parts (the capacity must suffice) and issue the ONE host-to-device copy on `stream` (None: the current one);
+        returns the device view of each part."""
+        offs, total = self.pack(parts)
+        with torch.cuda.stream(stream):
+            self.dev[:total].copy_(self.pinned[:total], non_blocking=True)
+        return [self.dev[o:o + p.size] for o, p in zip(offs, parts)]
+
+
 class TorchCpuNoiseFeed:
     """The Exp(1) tensors `torch.multinomial(probs[K, card], 1)` draws on the CPU — one `exponential_` of the logits' shape per
     decode step (reference models/ssr.py:85 via :713/:732; checked in oracle/make_golden.py::make_sampler) — produced a chunk of
@@ -377,7 +422,7 @@ class DecodeEngine:
         self.page_table_warm = torch.full((self.B, self.max_pages), self.scratch_page, **i32)
         self._table_warm_host = np.full((self.B, self.max_pages), self.scratch_page, dtype=np.int32)
         self._side_stream = None
-        self._warm_pinned = self._warm_dev = None
+        self._warm_stage = IntStaging()           # one-copy staging of a two-phase admission's integer arrays
         self._warm_free = None                    # event: the last activation has read the warm staging buffers
         self.t_first_chunk = 0.0
         # > 4 rows: x / q / h are 16-column tiled buffers, one 16-row panel per 16 rows (include/ssrhip.h SSRHIP_TILED_P)
@@ -400,7 +445,8 @@ class DecodeEngine:
         self.noise = torch.empty(n_utt, max_steps, K, arena.card, **f32)
         self._pinned = None
         self._copy_stream = None
-        self._admit_pinned = self._admit_dev = self._admit_sent = None      # one-copy staging of an admission's integer arrays
+        self._admit_stage = IntStaging()          # one-copy staging of a blocking admission's integer arrays ...
+        self._admit_sent = None                   # ... and the event of its last copy
         self._prefill_ws = None
         self._arena_gen = arena.generation
         self.dbg_logits = torch.zeros(n_utt, K, arena.card, **f32) if debug_logits else None
@@ -460,15 +506,7 @@ class DecodeEngine:
         a = self.a
         K = a.K
         assert len(text_rows) == self.B and len(audio_cols) == self.n_utt and len(knobs) == self.n_utt
-        # KV pages: everything back to the pool; every slot is (re)admitted
-        self.pages.reset()
-        self._table_host[:] = self.scratch_page
-        self._row_pages = [[] for _ in range(self.B)]
-        self._kv0 = [0] * self.B
-        self._steps_enqueued = 0
-        self._admit_step = [0] * self.n_utt
-        self._utt_live = [False] * self.n_utt
-        self.n_admitted = self.n_refills = 0
+        self._reset_generation()                 # KV pages: everything back to the pool; every slot is (re)admitted
         if noise is not None:
             assert noise.dim() == 4 and noise.shape[0] == self.n_utt and tuple(noise.shape[2:]) == (K, a.card), noise.shape
             n = min(noise.shape[1], self.max_steps)
@@ -479,163 +517,54 @@ class DecodeEngine:
         return self.admit(list(range(self.n_utt)), [text_rows[u * rpu:(u + 1) * rpu] for u in range(self.n_utt)], list(audio_cols), list(knobs),
                           use_noise=(noise is not None or host_noise))
 
-    def admit_begin(self, slots: Sequence[int], text_rows: Sequence[Sequence[np.ndarray]], audio_cols: Sequence[np.ndarray],
-                    knobs: Sequence[DecodeKnobs], use_noise: bool = False) -> dict:
-        """First half of a TWO-PHASE admission (continuous batching without stalling the live rows): KV pages for the new rows, the
-        integer arrays and the PREFILL of just those rows on a SIDE stream — concurrently with the decode chunks of the rows that keep
-        running; the decode step does not see the new rows yet (their slots stay parked: `done` set, table rows on the scratch page; the
-        prefill reads `page_table_warm`). `admit_finish(handle)` later puts them into the lock-step batch. Returns the handle."""
-        return self.admit(slots, text_rows, audio_cols, knobs, use_noise=use_noise, _two_phase=True)
+    def _reset_generation(self):
+        """What `start` and `run_queue` begin from: every KV page back in the pool, every slot free, the counters at zero. The two-phase
+        form's warm state goes too (a `run_queue` that raised between `admit_begin` and `admit_finish` must not leave any behind)."""
+        self.pages.reset()
+        self._table_host[:] = self.scratch_page
+        self._table_warm_host[:] = self.scratch_page
+        self._row_pages = [[] for _ in range(self.B)]
+        self._kv0 = [0] * self.B
+        self._steps_enqueued = 0
+        self._admit_step = [0] * self.n_utt
+        self._utt_live = [False] * self.n_utt
+        self._utt_warm = [False] * self.n_utt
+        self.n_admitted = self.n_refills = 0
 
-    def admit_finish(self, h: dict) -> None:
-        """Second half: on the caller's (decode) stream, behind the side stream's prefill — sampler configuration / state, pending token,
-        cache position and the table rows of the new slots, then the embedding of the pending tokens (every row: for rows in mid-decode
-        that re-writes what the sampler's fused embedding left). A few small device copies; the rows step with the next chunk."""
-        dev = self.device
-        main = torch.cuda.current_stream(dev)
-        main.wait_event(h["prefill_done"])
-        csz, ssz = C.sizeof(_lib.SamplerCfg), C.sizeof(_lib.SamplerState)
-        for i, u in enumerate(h["slots"]):
-            self.cfg_dev[u * csz:(u + 1) * csz].copy_(torch.frombuffer(bytearray(bytes(h["cfgs"][i])), dtype=torch.uint8))
-            self.state_dev[u * ssz:(u + 1) * ssz].copy_(torch.frombuffer(bytearray(bytes(h["sts"][i])), dtype=torch.uint8))
-        idx = h["rows_d"].long()
-        self.next_tok.index_copy_(0, idx, h["nt_d"])
-        self.next_pos.index_copy_(0, idx, h["t0s"])
-        self.kv_pos.index_copy_(0, idx, h["kv0"])
-        self.row_len.index_copy_(0, idx, h["kv0"] + 1)
-        for u in h["slots"]:
-            self._utt_warm[u] = False
-            self._utt_live[u] = True
-            self._admit_step[u] = self._steps_enqueued
-            for b in range(u * self.rows_per_utt, (u + 1) * self.rows_per_utt):
-                self._table_host[b, :] = self._table_warm_host[b, :]
-                self._table_warm_host[b, :] = self.scratch_page
-        self.page_table.copy_(torch.from_numpy(self._table_host))
-        _lib.check(self.lib.ssrhip_lm_embed_pending(self._ctx, _lib.stream_ptr()), "ssrhip_lm_embed_pending")
-        self._warm_free = torch.cuda.Event()
-        self._warm_free.record(main)
-        self._keep_warm = h                       # staging views stay alive until the stream has consumed them
-
-    def admit(self, slots: Sequence[int], text_rows: Sequence[Sequence[np.ndarray]], audio_cols: Sequence[np.ndarray],
-              knobs: Sequence[DecodeKnobs], use_noise: bool = False, _two_phase: bool = False):
-        """Put new utterances into the utterance slots `slots` (free ones: never used, or released by `release_utterance`) while
-        the other slots keep decoding: KV pages from the pool, sampler configuration / state, pending input token, and the
-        PREFILL of just those rows (the reference prefills one utterance at a time anyway: models/ssr.py:627-642). Everything is
-        ordered on the caller's stream between two decode chunks; the captured step graph is untouched (it only holds pointers).
-        text_rows[i]: the 1 (or 2 with CFG) text rows of slot slots[i]; audio_cols[i]: [K, T0]. Returns the prefilled row count."""
-        a, dev = self.a, self.device
-        K = a.K
-        rpu = self.rows_per_utt
+    # ------------------------------------------------------------------ admission: the steps both forms are made of
+    def _book_admission(self, slots, text_rows, audio_cols, knobs):
+        """Checks the slots (free, their rows without KV pages, every sequence within the engine's capacity: ValueError before anything is
+        booked or enqueued), packs the prefill rows of the new sequences — one per engine row b, with b as its seq_id — and books their
+        prompt lengths. Returns (rows b, packed rows, the int32 parts of the ONE staged copy: tok[R][4] | pos[R] | kind[R] | seq[R] |
+        rpos[R] | rlen[R] | seq_start[n+1] | next_tok[rows][4] | t0[rows] | kv0[rows] | row index[rows])."""
+        K, rpu = self.a.K, self.rows_per_utt
         assert len(slots) == len(text_rows) == len(audio_cols) == len(knobs) and len(set(slots)) == len(slots)
-        toks, poss, kinds, seqs, rposs, lens = [], [], [], [], [], []
-        rows_b: List[int] = []
+        seqs = []
         for u, trs, au in zip(slots, text_rows, audio_cols):
             assert 0 <= u < self.n_utt and not self._utt_live[u] and len(trs) == rpu, (u, len(trs))
-            au = np.asarray(au, dtype=np.int64)
-            T0 = au.shape[1]
             for r in range(rpu):
-                b = u * rpu + r
-                tx = np.asarray(trs[r], dtype=np.int64).reshape(-1)
-                Lb = tx.shape[0]
-                if Lb + T0 + 1 > self.max_seq:
-                    raise ValueError("sequence exceeds engine capacity")
-                t = np.zeros((Lb + T0, MAX_CODEBOOKS), dtype=np.int32)
-                t[:Lb, 0] = tx
-                t[Lb:, :K] = au.T
-                toks.append(t)
-                poss.append(np.concatenate([np.arange(Lb), np.arange(T0)]).astype(np.int32))
-                kinds.append(np.concatenate([np.zeros(Lb), np.ones(T0)]).astype(np.int32))
-                seqs.append(np.full(Lb + T0, b, dtype=np.int32))
-                rposs.append(np.arange(Lb + T0, dtype=np.int32))
-                lens.append(Lb + T0)
-                rows_b.append(b)
-                assert not self._row_pages[b], "slot still owns KV pages"
-                self._kv0[b] = Lb + T0
-            if _two_phase:
-                assert not self._utt_warm[u]
-                self._utt_warm[u] = True
-            else:
-                self._utt_live[u] = True
-                self._admit_step[u] = self._steps_enqueued
-            self.n_admitted += 1
-        if _two_phase:                           # pages for the prompts (+ the first decoded position), entered in the WARM table only
-            for b in rows_b:
-                for have in range(min(self._kv0[b] // PAGE + 1, self.max_pages)):
-                    pg = self.pages.take(b)
-                    self._row_pages[b].append(pg)
-                    self._table_warm_host[b, have] = pg
-        else:
-            self._grow_pages(0)                  # pages for the prompts (+ the first decoded position) of the new rows
-        # Every integer array of this admission goes to the device in ONE copy: packed into a pinned staging buffer, sent asynchronously
-        # into a persistent int32 workspace, addressed by views (ADVICE r3: ten small synchronous pageable copies per admit stalled the
-        # rows that were still decoding). Layout (int32): tok[R][4] | pos[R] | kind[R] | seq[R] | rpos[R] | rlen[R] | seq_start[n+1] |
-        # next_tok[rows][4] | t0[rows] | kv0[rows] | row index[rows].
-        tok_h = np.concatenate(toks)
-        R = tok_h.shape[0]
-        nrow = len(rows_b)
-        nt_h = np.zeros((nrow, MAX_CODEBOOKS), dtype=np.int32)
-        nt_h[:, :K] = int(a.args.mts)
-        t0_h = np.asarray([int(np.asarray(audio_cols[i // rpu]).shape[1]) for i in range(nrow)], dtype=np.int32)
-        kv0_h = np.asarray(lens, dtype=np.int32)
-        starts = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
-        rpos_h = np.concatenate(rposs)
-        parts = [tok_h.reshape(-1), np.concatenate(poss), np.concatenate(kinds), np.concatenate(seqs), rpos_h, rpos_h + 1, starts,
-                 nt_h.reshape(-1), t0_h, kv0_h, np.asarray(rows_b, dtype=np.int32)]
-        total = sum(int(p_.size) for p_ in parts)
-        side = None
-        if _two_phase:
-            if self._side_stream is None:
-                self._side_stream = torch.cuda.Stream(dev)
-            side = self._side_stream
-            if self._warm_pinned is None or self._warm_pinned.numel() < total:
-                cap_n = max(total, 2 * (self._warm_pinned.numel() if self._warm_pinned is not None else 0), 4096)
-                torch.cuda.synchronize(dev)       # growth is rare: nothing in flight may still read the old buffer, and the new block (allocated
-                self._warm_pinned = torch.empty(cap_n, dtype=torch.int32).pin_memory()
-                self._warm_dev = torch.empty(cap_n, dtype=torch.int32, device=dev)     # on this stream, used on the side stream) has no pending user
-            side.synchronize()                    # the previous two-phase prefill is through (>= one 16-step chunk ago): its staging is free
-            if self._warm_free is not None:
-                side.wait_event(self._warm_free)  # ... and the activation that read the staging views has run
-            stage_np = self._warm_pinned.numpy()
-            offs, o = [], 0
-            for p_ in parts:
-                stage_np[o:o + p_.size] = p_.astype(np.int32, copy=False).reshape(-1)
-                offs.append(o)
-                o += int(p_.size)
-            with torch.cuda.stream(side):
-                self._warm_dev[:total].copy_(self._warm_pinned[:total], non_blocking=True)
-                self.page_table_warm.copy_(torch.from_numpy(self._table_warm_host))
-            stage_dev = self._warm_dev
-        elif self._admit_pinned is None or self._admit_pinned.numel() < total:
-            cap_n = max(total, 2 * (self._admit_pinned.numel() if self._admit_pinned is not None else 0), 4096)
-            self._admit_pinned = torch.empty(cap_n, dtype=torch.int32).pin_memory()
-            self._admit_dev = torch.empty(cap_n, dtype=torch.int32, device=dev)
-            self._admit_sent = None
-        if not _two_phase:
-            if self._admit_sent is not None:
-                self._admit_sent.synchronize()   # the previous admission's copy has left the staging buffer (admissions are >= 16 steps apart)
-            stage_np = self._admit_pinned.numpy()
-            offs, o = [], 0
-            for p_ in parts:
-                stage_np[o:o + p_.size] = p_.astype(np.int32, copy=False).reshape(-1)
-                offs.append(o)
-                o += int(p_.size)
-            self._admit_dev[:total].copy_(self._admit_pinned[:total], non_blocking=True)
-            self._admit_sent = torch.cuda.Event()
-            self._admit_sent.record(torch.cuda.current_stream(dev))
-            stage_dev = self._admit_dev
-        view = lambda i, n: stage_dev[offs[i]: offs[i] + n]
-        tok, pos, kind, seq, rpos, rlen = view(0, 4 * R).view(R, MAX_CODEBOOKS), view(1, R), view(2, R), view(3, R), view(4, R), view(5, R)
-        seq_start = view(6, len(lens) + 1)
-        nt_d, t0s, kv0, rows_d = view(7, 4 * nrow).view(nrow, MAX_CODEBOOKS), view(8, nrow), view(9, nrow), view(10, nrow)
+                assert not self._row_pages[u * rpu + r], "slot still owns KV pages"
+                seqs.append((u * rpu + r, trs[r], au))
+        pk = pack_prefill_rows(seqs, K)
+        if int(pk["lens"].max()) + 1 > self.max_seq:
+            raise ValueError("sequence exceeds engine capacity")
+        rows_b = [b for b, _, _ in seqs]
+        for b, n in zip(rows_b, pk["lens"]):
+            self._kv0[b] = int(n)
+        self.n_admitted += len(slots)
+        # first decode input of the new rows: the span-0 mask token at audio position T0 (ssr.py:655-662)
+        nt = np.zeros((len(rows_b), MAX_CODEBOOKS), dtype=np.int32)
+        nt[:, :K] = int(self.a.args.mts)
+        t0 = np.asarray([np.asarray(au).shape[1] for _, _, au in seqs], dtype=np.int32)
+        parts = [pk[k] for k in ("tok", "pos", "kind", "row_seq", "row_pos", "row_len", "seq_start")]
+        return rows_b, pk, parts + [nt, t0, pk["lens"], np.asarray(rows_b, dtype=np.int32)]
 
-        # sampler configuration / state of the slots
-        args = a.args
-        csz, ssz = C.sizeof(_lib.SamplerCfg), C.sizeof(_lib.SamplerState)
-        whole = list(slots) == list(range(self.n_utt))
+    def _slot_records(self, slots, knobs, audio_cols, use_noise: bool):
+        """Sampler configuration / initial state of the slots, as the arrays of C records the device reads."""
+        args = self.a.args
         cfgs = (_lib.SamplerCfg * len(slots))()
         sts = (_lib.SamplerState * len(slots))()
-        for i, (u, kn, au) in enumerate(zip(slots, knobs, audio_cols)):
-            c = cfgs[i]
+        for c, st, kn, au in zip(cfgs, sts, knobs, audio_cols):
             c.top_k, c.top_p, c.temperature, c.stop_repetition = int(kn.top_k), float(kn.top_p), float(kn.temperature), int(kn.stop_repetition)
             c.cfg_coef, c.cfg_one_minus = float(kn.cfg_coef), float(1 - kn.cfg_coef)
             c.cfg_stride, c.use_cfg = int(kn.cfg_stride), int(self.use_cfg)
@@ -648,77 +577,172 @@ class DecodeEngine:
             c.mts, c.max_n_spans, c.max_steps = int(args.mts), int(args.max_n_spans), int(self.max_steps)
             c.seed_lo, c.seed_hi = int(kn.seed) & 0xFFFFFFFF, (int(kn.seed) >> 32) & 0xFFFFFFFF
             c.use_noise = int(use_noise)
-            st = sts[i]
             st.span, st.num_gen, st.num_eog, st.num_cfg_tag, st.prev_token, st.consec_silence = 0, 0, 0, 1, -1, 0
             st.audio_pos = int(np.asarray(au).shape[1])
             st.n_steps, st.done = 0, 0
-        if _two_phase:
-            pass                                 # the decode step must not see the new slots yet: admit_finish writes cfg / state / pending token
-        elif whole:
-            self.cfg_dev.copy_(torch.frombuffer(bytearray(bytes(cfgs)), dtype=torch.uint8))
-            self.state_dev.copy_(torch.frombuffer(bytearray(bytes(sts)), dtype=torch.uint8))
-        else:
-            for i, u in enumerate(slots):
-                self.cfg_dev[u * csz:(u + 1) * csz].copy_(torch.frombuffer(bytearray(bytes(cfgs[i])), dtype=torch.uint8))
-                self.state_dev[u * ssz:(u + 1) * ssz].copy_(torch.frombuffer(bytearray(bytes(sts[i])), dtype=torch.uint8))
-        if _two_phase:
-            assert self._arena_gen == a.generation and self._ctx is not None, "two-phase admission needs the running engine's context"
-        if self._arena_gen != a.generation:          # the arena re-allocated a table (position table grown): refresh the pointers
-            self._w = a.c_struct()
-            self._arena_gen = a.generation
-            self.close()
-        if self._ctx is None:
-            self._create_ctx()
+        return cfgs, sts
 
-        # first decode input of the new rows: the span-0 mask token at audio position T0 (ssr.py:655-662)
-        idx = rows_d.long() if (rows_b != list(range(self.B)) and not _two_phase) else None
-        if _two_phase:
-            pass                                 # admit_finish
-        elif idx is None:                        # every row (the first fill): plain copies, no index tensor
-            self.next_tok.copy_(nt_d)
-            self.next_pos.copy_(t0s)
+    def _write_slot_records(self, slots, cfgs=None, sts=None):
+        """`cfgs[i]` / `sts[i]` (ctypes arrays of SamplerCfg / SamplerState; None: leave alone) into slot slots[i] of `cfg_dev` /
+        `state_dev`, on the caller's stream: ONE copy per buffer when the slots are all of them in order, one per slot otherwise."""
+        as_bytes = lambda rec: torch.frombuffer(bytearray(bytes(rec)), dtype=torch.uint8)
+        pairs = [(dst, recs) for dst, recs in ((self.cfg_dev, cfgs), (self.state_dev, sts)) if recs is not None]
+        if list(slots) == list(range(self.n_utt)):
+            for dst, recs in pairs:
+                dst.copy_(as_bytes(recs))
+            return
+        for i, u in enumerate(slots):
+            for dst, recs in pairs:
+                n = C.sizeof(recs[i])
+                dst[u * n:(u + 1) * n].copy_(as_bytes(recs[i]))
+
+    def _arm_rows(self, rows_b, nt, t0, kv0, rows_d):
+        """Pending input token, its audio position, cache position and row length of the new rows, from the staged views (the last four
+        parts of `_book_admission`), on the caller's stream. Returns the index tensor it used (None when every row is armed)."""
+        nt = nt.view(-1, MAX_CODEBOOKS)
+        if rows_b == list(range(self.B)):        # every row (the first fill): plain copies, no index tensor
+            self.next_tok.copy_(nt)
+            self.next_pos.copy_(t0)
             self.kv_pos.copy_(kv0)
             self.row_len.copy_(kv0 + 1)
-        else:
-            self.next_tok.index_copy_(0, idx, nt_d)
-            self.next_pos.index_copy_(0, idx, t0s)
-            self.kv_pos.index_copy_(0, idx, kv0)
-            self.row_len.index_copy_(0, idx, kv0 + 1)
+            return None
+        idx = rows_d.long()
+        self.next_tok.index_copy_(0, idx, nt)
+        self.next_pos.index_copy_(0, idx, t0)
+        self.kv_pos.index_copy_(0, idx, kv0)
+        self.row_len.index_copy_(0, idx, kv0 + 1)
+        return idx
 
-        # prefill workspaces: kept across admissions, grown when a larger prompt arrives
-        f32 = dict(dtype=torch.float32, device=dev)
+    def _prefill_ws_rows(self) -> int:
+        return 0 if self._prefill_ws is None else self._prefill_ws["x"].shape[0]
+
+    def _prefill_args(self, pk, views):
+        """The prefill workspaces (kept across admissions, grown when a larger prompt arrives) and the argument block of ONE
+        `ssrhip_lm_prefill` over the packed rows, whose integer arrays are the first seven staged views. Returns (args, workspaces): the
+        caller launches, and keeps the workspaces alive until its stream has consumed them."""
+        a = self.a
+        f32 = dict(dtype=torch.float32, device=self.device)
         D, F, H = a.D, a.F, a.H
-        ms = (max(lens) + PAGE - 1) // PAGE
-        if self._prefill_ws is None or self._prefill_ws["x"].shape[0] < R:
-            if _two_phase:
-                torch.cuda.synchronize(dev)      # (rare) the workspace is allocated on this stream and used on the side stream
-            Rc = max(R, int(1.25 * (self._prefill_ws["x"].shape[0] if self._prefill_ws is not None else 0)))
+        R, max_len = int(pk["tok"].shape[0]), int(pk["lens"].max())
+        ms = (max_len + PAGE - 1) // PAGE
+        if self._prefill_ws_rows() < R:
+            Rc = max(R, int(1.25 * self._prefill_ws_rows()))
             self._prefill_ws = dict(x=torch.empty(Rc, D, **f32), xn=torch.empty(Rc, D, **f32), qkv=torch.empty(Rc, 3 * D, **f32),
                                     o=torch.empty(Rc, D, **f32), h=torch.empty(Rc, F, **f32))
         ws = dict(self._prefill_ws)
         if os.environ.get("SSRHIP_PREFILL_ATTN_ROWWISE", "0") not in ("", "0"):      # A/B knob: the round-1 per-row attention needs its partials
             ws.update(part_o=torch.empty(R * H * ms * self.hd, **f32), part_ml=torch.empty(R * H * ms * 2, **f32))
-        # rows of one sequence are contiguous and in position order: the tiled prefill attention needs only where each starts (seq_start above)
+        # rows of one sequence are contiguous and in position order: the tiled prefill attention needs only where each starts (seq_start)
         p = _lib.PrefillArgs()
-        p.tok, p.pos, p.kind = tok.data_ptr(), pos.data_ptr(), kind.data_ptr()
-        p.row_seq, p.row_pos, p.row_len = seq.data_ptr(), rpos.data_ptr(), rlen.data_ptr()
-        p.R, p.max_splits = R, ms
+        for name, v in zip(("tok", "pos", "kind", "row_seq", "row_pos", "row_len", "seq_start"), views):
+            setattr(p, name, v.data_ptr())
+        p.R, p.max_splits, p.n_seq, p.max_len = R, ms, len(pk["lens"]), max_len
         for k, v in ws.items():
             setattr(p, k, v.data_ptr())
-        p.seq_start, p.n_seq, p.max_len = seq_start.data_ptr(), len(lens), int(max(lens))
-        if _two_phase:
-            # on the SIDE stream, against the warm table, without the closing embedding (x is live decode state): see admit_begin
-            p.table, p.no_embed = self.page_table_warm.data_ptr(), 1
-            with torch.cuda.stream(side):
-                _lib.check(self.lib.ssrhip_lm_prefill(self._ctx, C.byref(p), _lib.stream_ptr()), "ssrhip_lm_prefill")
-                done = torch.cuda.Event()
-                done.record(side)
-            return dict(slots=list(slots), rows=R, prefill_done=done, cfgs=cfgs, sts=sts, nt_d=nt_d, t0s=t0s, kv0=kv0, rows_d=rows_d, ws=ws)
+        return p, ws
+
+    # ------------------------------------------------------------------ admission: the blocking and the two-phase form
+    def admit(self, slots: Sequence[int], text_rows: Sequence[Sequence[np.ndarray]], audio_cols: Sequence[np.ndarray],
+              knobs: Sequence[DecodeKnobs], use_noise: bool = False):
+        """Put new utterances into the utterance slots `slots` (free ones: never used, or released by `release_utterance`) while
+        the other slots keep decoding: KV pages from the pool, sampler configuration / state, pending input token, and the
+        PREFILL of just those rows (the reference prefills one utterance at a time anyway: models/ssr.py:627-642). Everything is
+        ordered on the caller's stream between two decode chunks; the captured step graph is untouched (it only holds pointers).
+        text_rows[i]: the 1 (or 2 with CFG) text rows of slot slots[i]; audio_cols[i]: [K, T0]. Returns the prefilled row count."""
+        a, dev = self.a, self.device
+        rows_b, pk, parts = self._book_admission(slots, text_rows, audio_cols, knobs)
+        for u in slots:
+            self._utt_live[u] = True
+            self._admit_step[u] = self._steps_enqueued
+        self._grow_pages(0)                      # pages for the prompts (+ the first decoded position) of the new rows
+        stage = self._admit_stage
+        total = sum(p_.size for p_ in parts)
+        if stage.capacity < total:
+            stage.grow(total, dev)
+            self._admit_sent = None
+        if self._admit_sent is not None:
+            self._admit_sent.synchronize()       # the previous admission's copy has left the staging buffer (admissions are >= 16 steps apart)
+        views = stage.send(parts)
+        self._admit_sent = torch.cuda.Event()
+        self._admit_sent.record(torch.cuda.current_stream(dev))
+        self._write_slot_records(slots, *self._slot_records(slots, knobs, audio_cols, use_noise))
+        if self._arena_gen != a.generation:      # the arena re-allocated a table (position table grown): refresh the pointers
+            self._w = a.c_struct()
+            self._arena_gen = a.generation
+            self.close()
+        if self._ctx is None:
+            self._create_ctx()
+        idx = self._arm_rows(rows_b, *views[7:])
+        p, ws = self._prefill_args(pk, views)
         # (the prefill ends by embedding the pending input token of EVERY row into x: for rows in mid-decode that re-writes the
         # very values the sampler's fused embedding left there — same function, same inputs)
         _lib.check(self.lib.ssrhip_lm_prefill(self._ctx, C.byref(p), _lib.stream_ptr()), "ssrhip_lm_prefill")
         self._keep = (ws, idx)                   # alive until the stream has consumed them (the integer arrays live in the engine's workspace)
-        return R
+        return int(pk["tok"].shape[0])
+
+    def admit_begin(self, slots: Sequence[int], text_rows: Sequence[Sequence[np.ndarray]], audio_cols: Sequence[np.ndarray],
+                    knobs: Sequence[DecodeKnobs], use_noise: bool = False) -> dict:
+        """First half of a TWO-PHASE admission (continuous batching without stalling the live rows): KV pages for the new rows, the
+        integer arrays and the PREFILL of just those rows on a SIDE stream — concurrently with the decode chunks of the rows that keep
+        running; the decode step does not see the new rows yet (their slots stay parked: `done` set, table rows on the scratch page; the
+        prefill reads `page_table_warm`). `admit_finish(handle)` later puts them into the lock-step batch. Returns the handle."""
+        dev = self.device
+        assert self._arena_gen == self.a.generation and self._ctx is not None, "two-phase admission needs the running engine's context"
+        assert not any(self._utt_warm[u] for u in slots)
+        rows_b, pk, parts = self._book_admission(slots, text_rows, audio_cols, knobs)
+        for u in slots:
+            self._utt_warm[u] = True
+        for b in rows_b:                         # pages for the prompts (+ the first decoded position), entered in the WARM table only
+            for have in range(min(self._kv0[b] // PAGE + 1, self.max_pages)):
+                pg = self.pages.take(b)
+                self._row_pages[b].append(pg)
+                self._table_warm_host[b, have] = pg
+        if self._side_stream is None:
+            self._side_stream = torch.cuda.Stream(dev)
+        side, stage = self._side_stream, self._warm_stage
+        total = sum(p_.size for p_ in parts)
+        if stage.capacity < total:
+            torch.cuda.synchronize(dev)          # growth is rare: nothing in flight may still read the old buffer, and the new block (allocated
+            stage.grow(total, dev)               # on this stream, used on the side stream) has no pending user
+        side.synchronize()                       # the previous two-phase prefill is through (>= one 16-step chunk ago): its staging is free
+        if self._warm_free is not None:
+            side.wait_event(self._warm_free)     # ... and the activation that read the staging views has run
+        views = stage.send(parts, side)
+        with torch.cuda.stream(side):
+            self.page_table_warm.copy_(torch.from_numpy(self._table_warm_host))
+        # the decode step must not see the new slots yet: admit_finish writes cfg / state / pending token
+        cfgs, sts = self._slot_records(slots, knobs, audio_cols, use_noise)
+        if self._prefill_ws_rows() < pk["tok"].shape[0]:
+            torch.cuda.synchronize(dev)          # (rare) the workspace is allocated on this stream and used on the side stream
+        p, ws = self._prefill_args(pk, views)
+        # on the SIDE stream, against the warm table, without the closing embedding (x is live decode state)
+        p.table, p.no_embed = self.page_table_warm.data_ptr(), 1
+        with torch.cuda.stream(side):
+            _lib.check(self.lib.ssrhip_lm_prefill(self._ctx, C.byref(p), _lib.stream_ptr()), "ssrhip_lm_prefill")
+            done = torch.cuda.Event()
+            done.record(side)
+        return dict(slots=list(slots), rows_b=rows_b, prefill_done=done, cfgs=cfgs, sts=sts, arm=views[7:], ws=ws)
+
+    def admit_finish(self, h: dict) -> None:
+        """Second half: on the caller's (decode) stream, behind the side stream's prefill — sampler configuration / state, pending token,
+        cache position and the table rows of the new slots, then the embedding of the pending tokens (every row: for rows in mid-decode
+        that re-writes what the sampler's fused embedding left). A few small device copies; the rows step with the next chunk."""
+        main = torch.cuda.current_stream(self.device)
+        main.wait_event(h["prefill_done"])
+        self._write_slot_records(h["slots"], h["cfgs"], h["sts"])
+        self._arm_rows(h["rows_b"], *h["arm"])
+        for u in h["slots"]:
+            self._utt_warm[u] = False
+            self._utt_live[u] = True
+            self._admit_step[u] = self._steps_enqueued
+            for b in range(u * self.rows_per_utt, (u + 1) * self.rows_per_utt):
+                self._table_host[b, :] = self._table_warm_host[b, :]
+                self._table_warm_host[b, :] = self.scratch_page
+        self.page_table.copy_(torch.from_numpy(self._table_host))
+        _lib.check(self.lib.ssrhip_lm_embed_pending(self._ctx, _lib.stream_ptr()), "ssrhip_lm_embed_pending")
+        self._warm_free = torch.cuda.Event()
+        self._warm_free.record(main)
+        self._keep_warm = h                       # the workspaces and the staging views stay alive until the stream has consumed them
 
     # ------------------------------------------------------------------ KV page bookkeeping
     def _grow_pages(self, steps_ahead: int):
@@ -913,58 +937,39 @@ class DecodeEngine:
             take = [pending.pop(0) for _ in slots[: len(pending)]]
             return list(slots[: len(take)]), take
 
-        def admit_into(slots: Sequence[int]):
-            """blocking admission (the first fill; refills with SSRHIP_ADMIT_TWO_PHASE=0): prefill on the decode stream"""
-            slots, take = take_jobs(slots)
-            if not take:
-                return
+        def job_args(take: Sequence[int]):
+            return [jobs[j]["text_rows"] for j in take], [jobs[j]["audio_cols"] for j in take], [jobs[j]["knobs"] for j in take]
+
+        def now_running(slots: Sequence[int], take: Sequence[int]):
+            """slots[i] runs job take[i] from the next chunk on: the queue's bookkeeping, the slot's noise stream"""
             for u, j in zip(slots, take):
                 slot_job[u] = j
                 local[u] = 0
                 if sampling:
                     feed.reset_slot(u, jobs[j].get("gen"))
-            self.admit(slots, [jobs[j]["text_rows"] for j in take], [jobs[j]["audio_cols"] for j in take], [jobs[j]["knobs"] for j in take],
-                       use_noise=sampling)
             if sampling:
                 waits.append(upload(2, slots))                 # the new utterances' first chunk, before their first step
 
+        def admit_into(slots: Sequence[int]):
+            """blocking admission (the first fill; refills with SSRHIP_ADMIT_TWO_PHASE=0): prefill on the decode stream"""
+            slots, take = take_jobs(slots)
+            if take:
+                self.admit(slots, *job_args(take), use_noise=sampling)
+                now_running(slots, take)
+
         def begin_into(slots: Sequence[int]):
             """two-phase admission, first half: the prefill of the new rows starts on the side stream NOW and overlaps the decode chunk that
-            is already enqueued; the slots join the lock-step batch at the next poll (`finish_warm`)"""
+            is already enqueued; the slots join the lock-step batch at the next poll (`admit_finish`, then `now_running`)"""
             slots, take = take_jobs(slots)
-            if not take:
-                return None
-            h = self.admit_begin(slots, [jobs[j]["text_rows"] for j in take], [jobs[j]["audio_cols"] for j in take],
-                                 [jobs[j]["knobs"] for j in take], use_noise=sampling)
-            h["jobs"] = take
-            return h
-
-        def finish_warm(h: dict):
-            self.admit_finish(h)
-            for u, j in zip(h["slots"], h["jobs"]):
-                slot_job[u] = j
-                local[u] = 0
-                if sampling:
-                    feed.reset_slot(u, jobs[j].get("gen"))
-            if sampling:
-                waits.append(upload(2, h["slots"]))             # the new utterances' first chunk, before their first step
+            return (self.admit_begin(slots, *job_args(take), use_noise=sampling), take) if take else None
 
         # first fill: as `start` (pool reset), but only as many slots as there are jobs; the others stay parked on the scratch page
-        self.pages.reset()
-        self._table_host[:] = self.scratch_page
-        self._table_warm_host[:] = self.scratch_page
-        self._row_pages = [[] for _ in range(self.B)]
-        self._kv0 = [0] * self.B
-        self._steps_enqueued = 0
-        self._admit_step = [0] * self.n_utt
-        self._utt_live = [False] * self.n_utt
-        self._utt_warm = [False] * self.n_utt
-        self.n_admitted = self.n_refills = 0
+        self._reset_generation()
         # idle slots: done = 1 so that the sampler leaves them alone
         idle = (_lib.SamplerState * self.n_utt)()
         for st in idle:
             st.done = 1
-        self.state_dev.copy_(torch.frombuffer(bytearray(bytes(idle)), dtype=torch.uint8))
+        self._write_slot_records(range(self.n_utt), sts=idle)
         self.page_table.copy_(torch.from_numpy(self._table_host))
         admit_into(list(range(self.n_utt)))
         ci = 0
@@ -1010,17 +1015,17 @@ class DecodeEngine:
                     if sampling:
                         feed.finish(u, n)
                     if not st.done:                             # ran into its cap without finishing: park the slot (the caller raises)
-                        parked = _lib.SamplerState.from_buffer_copy(bytes(st))
-                        parked.done = 1
-                        ssz = C.sizeof(_lib.SamplerState)
-                        self.state_dev[u * ssz:(u + 1) * ssz].copy_(torch.frombuffer(bytearray(bytes(parked)), dtype=torch.uint8))
+                        parked = (_lib.SamplerState * 1)(_lib.SamplerState.from_buffer_copy(bytes(st)))
+                        parked[0].done = 1
+                        self._write_slot_records([u], sts=parked)
                     self.release_utterance(u)
                     slot_job[u] = None
                     freed.append(u)
             in_flight = []
             # the slots whose prefill was started one poll ago join the batch now (their prefill had a whole chunk to finish)
             if warm is not None:
-                finish_warm(warm)
+                self.admit_finish(warm[0])
+                now_running(warm[0]["slots"], warm[1])
                 warm = None
             free_slots = [u for u in range(self.n_utt) if slot_job[u] is None]
             any_live = any(j is not None for j in slot_job)

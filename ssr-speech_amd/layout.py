@@ -6,12 +6,15 @@ Restates, vectorised:
                    interval arithmetic in inference()   (reference models/ssr.py:381-436, 466-502, 604-625)
   undelay       <- revert_pattern_sequence              (models/ssr.py:438-464)
   assemble      <- the tail of inference()              (models/ssr.py:776-812)
+and `pack_prefill_rows`, the flattened [text || audio] rows every prefill launch of the library reads.
 """
 from __future__ import annotations
 
 from typing import List, Sequence, Tuple
 
 import numpy as np
+
+from ._lib import MAX_CODEBOOKS
 
 
 def delay_pattern(seg: np.ndarray, fill: int) -> np.ndarray:
@@ -77,6 +80,33 @@ def build_layout(y: np.ndarray, mask_interval: np.ndarray, args):
     cated = np.concatenate(pieces, 1)
     num_task = len(mask_position) // 2
     return cated[:, : mask_position[num_task]], mask_position, num_task, nmi
+
+
+def pack_prefill_rows(seqs, K: int) -> dict:
+    """The flattened [text || audio] rows one prefill launch reads (include/ssrhip.h ssrhip_prefill_args / ssrhip_score_args), written
+    ONCE for the engine's admissions and `score`. seqs: (seq_id, text ids [L], audio ids [K, T]) per sequence; a sequence's rows are
+    contiguous and in position order. Returns int32 arrays: tok [R][4] (text id in column 0, the K codebooks of an audio position in
+    columns 0..K-1, the rest 0), pos / kind (text 0 / audio 1, each part's sine position from 0: models/ssr.py:305-307, :205-206),
+    row_seq (the row's seq_id: which page-table row its K/V go to), row_pos / row_len (position in its sequence, and how many keys it
+    attends to), seq_start [n+1] (row index where each sequence starts) and lens [n]."""
+    toks, poss, kinds, ids, rposs, lens = [], [], [], [], [], []
+    for sid, text, audio in seqs:
+        tx = np.asarray(text, dtype=np.int64).reshape(-1)
+        au = np.asarray(audio, dtype=np.int64)
+        L, T = tx.shape[0], au.shape[1]
+        t = np.zeros((L + T, MAX_CODEBOOKS), dtype=np.int32)
+        t[:L, 0] = tx
+        t[L:, :K] = au.T
+        toks.append(t)
+        poss.append(np.concatenate([np.arange(L), np.arange(T)]).astype(np.int32))
+        kinds.append(np.concatenate([np.zeros(L), np.ones(T)]).astype(np.int32))
+        ids.append(np.full(L + T, sid, dtype=np.int32))
+        rposs.append(np.arange(L + T, dtype=np.int32))
+        lens.append(L + T)
+    rpos = np.concatenate(rposs)
+    return dict(tok=np.concatenate(toks), pos=np.concatenate(poss), kind=np.concatenate(kinds), row_seq=np.concatenate(ids),
+                row_pos=rpos, row_len=rpos + 1, seq_start=np.concatenate([[0], np.cumsum(lens)]).astype(np.int32),
+                lens=np.asarray(lens, dtype=np.int32))
 
 
 def assemble(y: np.ndarray, spans: Sequence[np.ndarray], non_mask_intervals, args):

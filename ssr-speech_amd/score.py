@@ -18,7 +18,8 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from ._lib import MAX_CODEBOOKS, PAGE
+from ._lib import PAGE
+from .layout import pack_prefill_rows
 
 
 @dataclass
@@ -106,29 +107,11 @@ def plan_chunks(row_counts: Sequence[int], max_rows: int) -> List[List[int]]:
 
 
 def pack_items(items: Sequence[Item], K: int) -> Dict[str, np.ndarray]:
-    """The prefill's row format (DecodeEngine.admit) for the items of one chunk, sequence s = items[s]: tok [R][4], pos / kind (text 0 /
-    audio 1, each part's sine position from 0: ssr.py:305-307, :205-206), row_seq / row_pos / row_len, seq_start [n+1]; the scored rows
-    (score_first / score_count: audio positions 0 .. T-2 of each item) and their targets [K][M] = y[:, t + 1]; the KV page table of a
-    scratch pool that holds every item's positions once (one layer)."""
-    toks, poss, kinds, seqs, rposs, tgts, firsts, counts, lens = [], [], [], [], [], [], [], [], []
-    start = 0
-    for s, it in enumerate(items):
-        L, T = it.text.shape[0], it.audio.shape[1]
-        n = L + T
-        t = np.zeros((n, MAX_CODEBOOKS), dtype=np.int32)
-        t[:L, 0] = it.text
-        t[L:, :K] = it.audio.T
-        toks.append(t)
-        poss.append(np.concatenate([np.arange(L), np.arange(T)]).astype(np.int32))
-        kinds.append(np.concatenate([np.zeros(L), np.ones(T)]).astype(np.int32))
-        seqs.append(np.full(n, s, dtype=np.int32))
-        rposs.append(np.arange(n, dtype=np.int32))
-        firsts.append(start + L)
-        counts.append(it.n_scored)
-        tgts.append(it.audio[:, 1:].astype(np.int32))
-        lens.append(n)
-        start += n
-    rpos = np.concatenate(rposs)
+    """The prefill's rows (`layout.pack_prefill_rows`) for the items of one chunk, sequence s = items[s]: tok [R][4], pos / kind, row_seq /
+    row_pos / row_len, seq_start [n+1]; the scored rows (score_first / score_count: audio positions 0 .. T-2 of each item) and their
+    targets [K][M] = y[:, t + 1]; the KV page table of a scratch pool that holds every item's positions once (one layer)."""
+    pk = pack_prefill_rows([(s, it.text, it.audio) for s, it in enumerate(items)], K)
+    lens = [int(n) for n in pk.pop("lens")]
     max_len = max(lens)
     max_pages = (max_len + PAGE - 1) // PAGE
     table = np.zeros((len(items), max_pages), dtype=np.int32)
@@ -138,9 +121,9 @@ def pack_items(items: Sequence[Item], K: int) -> Dict[str, np.ndarray]:
         table[s, :npg] = np.arange(nxt, nxt + npg)
         table[s, npg:] = nxt                       # never read (positions >= n are masked out); a valid page all the same
         nxt += npg
-    return dict(tok=np.concatenate(toks), pos=np.concatenate(poss), kind=np.concatenate(kinds), row_seq=np.concatenate(seqs),
-                row_pos=rpos, row_len=rpos + 1, seq_start=np.concatenate([[0], np.cumsum(lens)]).astype(np.int32),
-                score_first=np.asarray(firsts, dtype=np.int32), score_count=np.asarray(counts, dtype=np.int32),
+    tgts = [it.audio[:, 1:].astype(np.int32) for it in items]
+    return dict(pk, score_first=np.asarray([s + it.text.shape[0] for s, it in zip(pk["seq_start"], items)], dtype=np.int32),
+                score_count=np.asarray([it.n_scored for it in items], dtype=np.int32),
                 target=np.concatenate(tgts, axis=1) if tgts else np.zeros((K, 0), dtype=np.int32),
                 table=table, n_pages=np.asarray(nxt), max_len=np.asarray(max_len))
 
