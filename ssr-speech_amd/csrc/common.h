@@ -40,6 +40,15 @@ struct ssr_once_per_device {
   }
 };
 
+// CU count of the current device, asked once per process by whichever GEMV launcher runs first (256 where there is no device to ask)
+inline int ssr_num_cu() {
+  static const int n = [] {
+    int dev = 0, cu = 0;
+    return (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cu > 0) ? cu : 256;
+  }();
+  return n;
+}
+
 // profiling aid (tools/prof_summary.py --gemm-log): one line per GEMM launch — M N K batch, the launch grid, split (1) or fp32 chain (0) —
 // so that a kernel trace's GEMM rows get their problem size and a TFLOP/s column. Off unless SSRHIP_GEMM_LOG names a file.
 #include <stdio.h>

@@ -163,13 +163,26 @@ struct Timer {   // optional per-launch event timing: one accumulator per launch
     }                                                           \
   } while (0)
 
-// Launch descriptors of the five GEMVs of a decode step (shared by enqueue_step and by ssrhip_lm_create's "would this engine pair?")
+// The embedding launch of R rows into `out`: tables and sizes. The caller adds where the tokens come from (tok / pos / kind).
+ssrhip_embed_args embed_args(const ssrhip_lm_dims& d, const ssrhip_lm_weights& w, int R, float* out, int out_tiled) {
+  ssrhip_embed_args ea;
+  memset(&ea, 0, sizeof(ea));
+  ea.text_emb = w.text_emb; ea.audio_emb = w.audio_emb; ea.pe = w.pe;
+  ea.alpha_text = w.alpha_text; ea.alpha_audio = w.alpha_audio;
+  ea.R = R; ea.D = d.d_model; ea.K = d.n_codebooks; ea.card = d.card; ea.out = out; ea.out_tiled = out_tiled;
+  return ea;
+}
+
+// Launch descriptors of a decode step: every launch enqueue_step makes is built here, and ssrhip_lm_create's "would this engine pair?"
+// asks with the same descriptors the step later hands to ssrhip_gemv_pair
 struct StepShapes {
   const ssrhip_lm_dims& d;
   const ssrhip_lm_weights& w;
   const ssrhip_lm_buffers& b;
   const int D, B, K, Hh;
-  const int tiled;     // 5..32 rows: x, the combined attention output and h live in the 16-column tiled layout (SSRHIP_TILED_P)
+  // 5..32 rows: the residual stream x, the combined attention output and the hidden h live in the 16-column tiled layout
+  // (include/ssrhip.h SSRHIP_TILED_P: one 16-row panel per 16 rows) so that the matrix-core GEMV's operand loads are contiguous KiBs
+  const int tiled;
   const bool wt;       // streaming-order weight copies for the matrix-core GEMV (include/ssrhip.h w_tiled)
   explicit StepShapes(const ssrhip_lm* lm)
       : d(lm->d), w(lm->w), b(lm->b), D(lm->d.d_model), B(lm->b.B), K(lm->d.n_codebooks), Hh(lm->d.head_hidden), tiled(lm->b.B > 4 ? 1 : 0),
@@ -211,6 +224,14 @@ struct StepShapes {
     g.kv = b.kv;
     return g;
   }
+  // 5..32 rows: the attention output is already combined (in `attn_out`, tiled), so the out-projection is a plain GEMV + residual
+  ssrhip_gemv_args outproj_rows_args(int l, const float* attn_out) const {
+    ssrhip_gemv_args g = outproj_args(l);
+    g.x = attn_out;
+    g.pro = SSRHIP_PRO_NONE; g.x_tiled = 1; g.y_tiled = 1;
+    if (wt) { g.W = w.out_proj_wt[l]; g.w_tiled = 1; }
+    return g;
+  }
   ssrhip_gemv_args ffn1_args(int l) const {
     ssrhip_gemv_args g;
     // LN2 + FFN1 + ReLU
@@ -234,6 +255,36 @@ struct StepShapes {
     if (wt) { g.W = w.ffn2_wt[l]; g.w_tiled = 1; }
     return g;
   }
+  ssrhip_gemv_args head2_args() const {
+    ssrhip_gemv_args g;
+    // second Linear of each head: K groups
+    memset(&g, 0, sizeof(g));
+    g.W = w.head2_w; g.bias = w.head2_b; g.x = b.h; g.y = b.logits;
+    g.B = B; g.N = d.card; g.K = Hh; g.groups = K; g.x_stride = K * Hh; g.y_stride = K * d.card;
+    g.pro = SSRHIP_PRO_NONE; g.act = SSRHIP_ACT_NONE; g.epi = SSRHIP_EPI_STORE;
+    g.x_tiled = tiled;                         // logits stay row-major for the sampler
+    if (wt) { g.W = w.head2_wt; g.w_tiled = 1; }
+    return g;
+  }
+  ssrhip_attn_args attn_args(int l) const {
+    ssrhip_attn_args at;
+    memset(&at, 0, sizeof(at));
+    at.q = b.q; at.kv = b.kv; at.layer = l; at.row_seq = nullptr; at.row_len = b.row_len;
+    at.R = B; at.max_splits = b.max_splits; at.scale = 1.0f / sqrtf((float)(D / d.n_head));
+    at.part_o = b.part_o; at.part_ml = b.part_ml;
+    return at;
+  }
+  ssrhip_sample_args sample_args() const {
+    ssrhip_sample_args sa;
+    memset(&sa, 0, sizeof(sa));
+    sa.logits = b.logits; sa.n_utt = b.n_utt; sa.K = K; sa.card = d.card;
+    sa.cfg = b.cfg; sa.state = b.state; sa.noise = b.noise; sa.generated = b.generated;
+    sa.next_tok = b.next_tok; sa.next_pos = b.next_pos; sa.kv_pos = b.kv_pos; sa.row_len = b.row_len;
+    sa.dbg_logits = b.dbg_logits;
+    // the sampler also embeds the tokens it chose: x of the next step (no separate embed launch)
+    sa.embed = embed_args(d, w, B, b.x, tiled);
+    return sa;
+  }
   // which launches of the 2-row step qualify for the pair forms, and how many pair launches a step then has (0: fewer than 2 -> none)
   int pair_plan(bool* qkv, bool* head, bool* ffn1) const {
     *qkv = *head = *ffn1 = false;
@@ -249,20 +300,9 @@ struct StepShapes {
 };
 
 int enqueue_step(ssrhip_lm* lm, hipStream_t s, Timer* tm) {
-  const ssrhip_lm_dims& d = lm->d;
-  const ssrhip_lm_weights& w = lm->w;
-  const ssrhip_lm_buffers& b = lm->b;
-  const int D = d.d_model, B = b.B, K = d.n_codebooks, Hh = d.head_hidden;
-  // 5..32 rows: the residual stream x, the combined attention output and the hidden h live in the 16-column tiled layout
-  // (include/ssrhip.h SSRHIP_TILED_P: one 16-row panel per 16 rows) so that the matrix-core GEMV's operand loads are contiguous KiBs
-  const int tiled = B > 4 ? 1 : 0;
-  const bool wt = tiled && w.in_proj_wt;      // streaming-order weight copies for the matrix-core GEMV (include/ssrhip.h w_tiled)
-
   const StepShapes sh(lm);
-  auto qkv_args = [&](int l) { return sh.qkv_args(l); };
-  auto head1_args = [&]() { return sh.head1_args(); };
-  auto ffn1_args = [&](int l) { return sh.ffn1_args(l); };
-  auto ffn2_args = [&](int l) { return sh.ffn2_args(l); };
+  const ssrhip_lm_dims& d = lm->d;
+  const ssrhip_lm_buffers& b = lm->b;
   // 2-row step: FFN2 of layer l and the launch that consumes its output (QKV of layer l + 1; the head MLP after the last layer) run as ONE
   // launch with the all-to-all edge inside it (csrc/gemv.hip gemv_pair_kernel), and so do the out-projection (with its split-KV merge
   // prologue) and FFN1 (gemv_pair_merge_kernel): attention, pair, pair per layer. The pairs of a step use the three granule buffers of
@@ -270,110 +310,78 @@ int enqueue_step(ssrhip_lm* lm, hipStream_t s, Timer* tm) {
   // replays (and eager steps) always find their buffer reset by the launch before them; with n % 3 == 1 the last pair takes buffer 1.
   bool pair_qkv = false, pair_head = false, pair_ffn1 = false;
   const int n_pairs = lm->pair_ws ? sh.pair_plan(&pair_qkv, &pair_head, &pair_ffn1) : 0;
-  auto pair_buf = [&](int i) { return ssrhip_pair_buffer(i, n_pairs); };
   int pair_i = 0;
+  // the launch (a, b) that pair_plan found applicable, on this pair's granule buffer
+  auto pair_call = [&](const ssrhip_gemv_args& ga, const ssrhip_gemv_args& gb) {
+    const int bufi = ssrhip_pair_buffer(pair_i, n_pairs), bufn = ssrhip_pair_buffer((pair_i + 1) % n_pairs, n_pairs);
+    pair_i += 1;
+    return ssrhip_gemv_pair(&ga, &gb, lm->pair_ws, bufi, bufn, (ssrhip_stream_t)s);
+  };
   bool qkv_done = false;                        // this layer's QKV already ran inside the previous layer's pair launch
+  // 5..32 rows with enough (row, head) pairs to give every CU one: the fused walk over the pages (no partials, no merge
+  // launch); its output goes to b.h (free until FFN1 of this layer) because q is still being read by other workgroups
+  const bool fused_attn = sh.B > 4 && sh.B * d.n_head >= 192 && b.kv.max_pages <= 256 && !getenv_flag("SSRHIP_ATTN_SPLIT");   // 256 pages: the kernel's page-id registers
 
   if (tm) tm->slot = 0;
 
   for (int l = 0; l < d.n_layer; ++l) {
-    ssrhip_gemv_args g;
     if (!qkv_done) {
-      g = qkv_args(l);
+      const ssrhip_gemv_args g = sh.qkv_args(l);
       STEP_CALL(CAT_GEMV, ssrhip_gemv(&g, s));
     }
     qkv_done = false;
 
-    ssrhip_attn_args at;
-    memset(&at, 0, sizeof(at));
-    at.q = b.q; at.kv = b.kv; at.layer = l; at.row_seq = nullptr; at.row_len = b.row_len;
-    at.R = B; at.max_splits = b.max_splits; at.scale = 1.0f / sqrtf((float)(D / d.n_head));
-    at.part_o = b.part_o; at.part_ml = b.part_ml;
+    ssrhip_attn_args at = sh.attn_args(l);
     // 2-row paired step, OPT-IN experiment (SSRHIP_ATTN_PREFETCH=1, read when the step is enqueued): the attention launch pre-touches the
     // out-projection slice the merge pair launch behind it starts with (include/ssrhip.h ssrhip_attn_args.prefetch). Measured: the attention
     // launch pays for the 16.8 MB (6.55 -> 8.80 us) and the pair launch gains nothing (18.33 vs 18.35 us): 0.7477 -> 0.7707 ms/step
     // (profiles/r06_microbench/decode_ab_attn_prefetch.log). Like every cross-launch prefetch tried since round 1, it loses.
-    if (pair_ffn1 && D % 256 == 0 && getenv("SSRHIP_ATTN_PREFETCH") && getenv("SSRHIP_ATTN_PREFETCH")[0] == '1') {
-      at.prefetch = w.out_proj_w[l];
-      at.prefetch_floats = (D / 256) * D;                    // workgroup i of the pair launch owns rows [8 i, 8 i + 8) of W_o [D][D]
+    if (pair_ffn1 && sh.D % 256 == 0 && getenv("SSRHIP_ATTN_PREFETCH") && getenv("SSRHIP_ATTN_PREFETCH")[0] == '1') {
+      at.prefetch = lm->w.out_proj_w[l];
+      at.prefetch_floats = (sh.D / 256) * sh.D;              // workgroup i of the pair launch owns rows [8 i, 8 i + 8) of W_o [D][D]
     }
-    // 5..32 rows with enough (row, head) pairs to give every CU one: the fused walk over the pages (no partials, no merge
-    // launch); its output goes to b.h (free until FFN1 of this layer) because q is still being read by other workgroups
-    const bool fused_attn = B > 4 && B * d.n_head >= 192 && b.kv.max_pages <= 256 && !getenv_flag("SSRHIP_ATTN_SPLIT");   // 256 pages: the kernel's page-id registers
-    // split-KV combine + out-proj + residual
-    memset(&g, 0, sizeof(g));
-    g.W = w.out_proj_w[l]; g.bias = w.out_proj_b[l]; g.x = nullptr; g.y = b.x;
-    g.B = B; g.N = D; g.K = D; g.groups = 1; g.x_stride = D; g.y_stride = D;
-    g.pro = SSRHIP_PRO_ATTN_COMBINE; g.act = SSRHIP_ACT_NONE; g.epi = SSRHIP_EPI_RESIDUAL;
-    g.part_o = b.part_o; g.part_ml = b.part_ml; g.max_splits = b.max_splits; g.row_len = b.row_len;
-    g.kv = b.kv;
+    // attention, then split-KV combine + out-proj + residual: <= 4 rows fuse the combine into the out-projection's prologue
+    ssrhip_gemv_args op;
     if (fused_attn) {
       at.out_tiled = 1;
       STEP_CALL(CAT_ATTN, ssrhip_attn_rows(&at, b.h, s));
+      op = sh.outproj_rows_args(l, b.h);
     } else {
       STEP_CALL(CAT_ATTN, ssrhip_attn_decode(&at, s));
-    }
-    if (B > 4) {
-      if (fused_attn) {
-        g.x = b.h;
-      } else {
+      if (sh.B > 4) {
         // the combine is its own small launch; q is dead after the attention, reuse it
         at.out_tiled = 1;
         STEP_CALL(CAT_ATTN, ssrhip_attn_combine(&at, b.q, s));
-        g.x = b.q;
+        op = sh.outproj_rows_args(l, b.q);
+      } else {
+        op = sh.outproj_args(l);
       }
-      g.pro = SSRHIP_PRO_NONE; g.x_tiled = 1; g.y_tiled = 1;
-      if (wt) { g.W = w.out_proj_wt[l]; g.w_tiled = 1; }
     }
+    const ssrhip_gemv_args f1 = sh.ffn1_args(l);
     if (pair_ffn1) {                              // out-projection + FFN1 as one launch (2 rows)
-      const ssrhip_gemv_args f1 = ffn1_args(l);
-      const int bufi = pair_buf(pair_i), bufn = pair_buf((pair_i + 1) % n_pairs);
-      STEP_CALL(CAT_GEMV, ssrhip_gemv_pair(&g, &f1, lm->pair_ws, bufi, bufn, (ssrhip_stream_t)s));
-      pair_i += 1;
+      STEP_CALL(CAT_GEMV, pair_call(op, f1));
     } else {
-      STEP_CALL(CAT_GEMV, ssrhip_gemv(&g, s));
-      g = ffn1_args(l);
-      STEP_CALL(CAT_GEMV, ssrhip_gemv(&g, s));
+      STEP_CALL(CAT_GEMV, ssrhip_gemv(&op, s));
+      STEP_CALL(CAT_GEMV, ssrhip_gemv(&f1, s));
     }
 
     // FFN2 + residual — paired with the next launch where that applies
-    g = ffn2_args(l);
+    const ssrhip_gemv_args f2 = sh.ffn2_args(l);
     const bool last = l == d.n_layer - 1;
     if (last ? pair_head : pair_qkv) {
-      const ssrhip_gemv_args nx = last ? head1_args() : qkv_args(l + 1);
-      const int bufi = pair_buf(pair_i), bufn = pair_buf((pair_i + 1) % n_pairs);
-      STEP_CALL(CAT_GEMV, ssrhip_gemv_pair(&g, &nx, lm->pair_ws, bufi, bufn, (ssrhip_stream_t)s));
-      pair_i += 1;
+      STEP_CALL(CAT_GEMV, pair_call(f2, last ? sh.head1_args() : sh.qkv_args(l + 1)));
       qkv_done = true;                          // (after the last layer: the head MLP's first launch)
     } else {
-      STEP_CALL(CAT_GEMV, ssrhip_gemv(&g, s));
+      STEP_CALL(CAT_GEMV, ssrhip_gemv(&f2, s));
     }
   }
-  {
-    ssrhip_gemv_args g;
-    if (!qkv_done) {
-      g = head1_args();
-      STEP_CALL(CAT_GEMV, ssrhip_gemv(&g, s));
-    }
-    // second Linear of each head: K groups
-    memset(&g, 0, sizeof(g));
-    g.W = w.head2_w; g.bias = w.head2_b; g.x = b.h; g.y = b.logits;
-    g.B = B; g.N = d.card; g.K = Hh; g.groups = K; g.x_stride = K * Hh; g.y_stride = K * d.card;
-    g.pro = SSRHIP_PRO_NONE; g.act = SSRHIP_ACT_NONE; g.epi = SSRHIP_EPI_STORE;
-    g.x_tiled = tiled;                         // logits stay row-major for the sampler
-    if (wt) { g.W = w.head2_wt; g.w_tiled = 1; }
+  if (!qkv_done) {
+    const ssrhip_gemv_args g = sh.head1_args();
     STEP_CALL(CAT_GEMV, ssrhip_gemv(&g, s));
   }
-  ssrhip_sample_args sa;
-  memset(&sa, 0, sizeof(sa));
-  sa.logits = b.logits; sa.n_utt = b.n_utt; sa.K = K; sa.card = d.card;
-  sa.cfg = b.cfg; sa.state = b.state; sa.noise = b.noise; sa.generated = b.generated;
-  sa.next_tok = b.next_tok; sa.next_pos = b.next_pos; sa.kv_pos = b.kv_pos; sa.row_len = b.row_len;
-  sa.dbg_logits = b.dbg_logits;
-  // the sampler also embeds the tokens it chose: x of the next step (no separate embed launch)
-  sa.embed.text_emb = w.text_emb; sa.embed.audio_emb = w.audio_emb; sa.embed.pe = w.pe;
-  sa.embed.alpha_text = w.alpha_text; sa.embed.alpha_audio = w.alpha_audio;
-  sa.embed.R = B; sa.embed.D = D; sa.embed.K = K; sa.embed.card = d.card; sa.embed.out = b.x; sa.embed.out_tiled = tiled;
+  const ssrhip_gemv_args h2 = sh.head2_args();
+  STEP_CALL(CAT_GEMV, ssrhip_gemv(&h2, s));
+  const ssrhip_sample_args sa = sh.sample_args();
   STEP_CALL(CAT_SAMPLE, ssrhip_sample(&sa, s));
   return 0;
 }
@@ -584,12 +592,8 @@ static int lm_layer_loop(const ssrhip_lm_dims& d, const ssrhip_lm_weights& w, bo
   const int D = d.d_model, R = p->R;
   const bool one_layer_kv = kv.n_layer == 1;
 
-  ssrhip_embed_args ea;
-  memset(&ea, 0, sizeof(ea));
-  ea.text_emb = w.text_emb; ea.audio_emb = w.audio_emb; ea.pe = w.pe;
-  ea.alpha_text = w.alpha_text; ea.alpha_audio = w.alpha_audio;
+  ssrhip_embed_args ea = embed_args(d, w, R, p->x, 0);
   ea.tok = p->tok; ea.pos = p->pos; ea.kind = p->kind;
-  ea.R = R; ea.D = D; ea.K = d.n_codebooks; ea.card = d.card; ea.out = p->x;
   if (int rc = ssrhip_embed(&ea, s)) return rc;
 
   for (int l = 0; l < d.n_layer; ++l) {
@@ -717,17 +721,9 @@ extern "C" int ssrhip_lm_score(const ssrhip_lm_dims* d, const ssrhip_lm_weights*
 
 extern "C" int ssrhip_lm_embed_pending(ssrhip_lm* lm, ssrhip_stream_t stream) {
   SSR_REQUIRE(lm, "ssrhip_lm_embed_pending: null argument");
-  const ssrhip_lm_dims& d = lm->d;
-  const ssrhip_lm_weights& w = lm->w;
-  const int D = d.d_model;
-  hipStream_t s = (hipStream_t)stream;
   // x of the first decode step: the rows' pending input tokens (the span-0 mask token, ssr.py:655-662)
   const ssrhip_lm_buffers& b = lm->b;
-  ssrhip_embed_args ea;
-  memset(&ea, 0, sizeof(ea));
-  ea.text_emb = w.text_emb; ea.audio_emb = w.audio_emb; ea.pe = w.pe;
-  ea.alpha_text = w.alpha_text; ea.alpha_audio = w.alpha_audio;
+  ssrhip_embed_args ea = embed_args(lm->d, lm->w, b.B, b.x, b.B > 4 ? 1 : 0);
   ea.tok = b.next_tok; ea.pos = b.next_pos; ea.kind = nullptr;
-  ea.R = b.B; ea.D = D; ea.K = d.n_codebooks; ea.card = d.card; ea.out = b.x; ea.out_tiled = b.B > 4 ? 1 : 0;
-  return ssrhip_embed(&ea, s);
+  return ssrhip_embed(&ea, (hipStream_t)stream);
 }

@@ -1385,9 +1385,16 @@ bool try_seg(const ssrhip_gemv_args* a, int num_cu, hipStream_t s) {
   return true;
 }
 
-int g_num_cu = 0;
-int g_blocks_per_cu = 3;   // A/B in the real (dependent-launch) decode step: 1 -> 1.536, 2 -> 1.109, 3 -> 1.065 ms/step. (Independent
-                          // back-to-back launches, tools/gemv_bench.hip, prefer 2: 12.5 us vs 12.6 for 67 MB; the chain wants the faster ramp.)
+// Resident workgroups per CU of the row-per-wave kernels (tuning knob SSRHIP_GEMV_BLOCKS_PER_CU = 1..3, read once per process).
+// A/B in the real (dependent-launch) decode step: 1 -> 1.536, 2 -> 1.109, 3 -> 1.065 ms/step. (Independent back-to-back launches,
+// tools/gemv_bench.hip, prefer 2: 12.5 us vs 12.6 for 67 MB; the chain wants the faster ramp.)
+int blocks_per_cu() {
+  static const int n = [] {
+    const char* e = getenv("SSRHIP_GEMV_BLOCKS_PER_CU");
+    return (e && atoi(e) >= 1 && atoi(e) <= 3) ? atoi(e) : 3;
+  }();
+  return n;
+}
 
 }  // namespace
 
@@ -1463,15 +1470,6 @@ static int pair_nuwb(const ssrhip_gemv_args* a, const ssrhip_gemv_args* b, int n
   return nuwb;
 }
 
-static void ensure_num_cu() {
-  if (g_num_cu == 0) {
-    int dev = 0, cu = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cu > 0) g_num_cu = cu;
-    else g_num_cu = 256;
-    if (const char* e = getenv("SSRHIP_GEMV_BLOCKS_PER_CU")) { const int v = atoi(e); if (v >= 1 && v <= 3) g_blocks_per_cu = v; }   // tuning knob
-  }
-}
-
 // Granule buffer of the i-th of n pair launches that follow each other cyclically (a decode step's pairs, replayed step after step):
 // i % 3, except that the last launch takes buffer 1 when n % 3 == 1 (it would otherwise share buffer 0 with launch 0 of the next cycle).
 // Any two cyclically consecutive launches use different buffers for every n >= 2 (tests/test_capi.py checks 2..200).
@@ -1482,17 +1480,15 @@ extern "C" int ssrhip_pair_buffer(int32_t i, int32_t n) {
 
 extern "C" int ssrhip_gemv_pair_applicable(const ssrhip_gemv_args* a, const ssrhip_gemv_args* b) {
   if (!a || !b) return 0;
-  ensure_num_cu();
   bool merge;
-  return pair_nuwb(a, b, g_num_cu, &merge) != 0;
+  return pair_nuwb(a, b, ssr_num_cu(), &merge) != 0;
 }
 
 extern "C" int ssrhip_gemv_pair(const ssrhip_gemv_args* a, const ssrhip_gemv_args* b, void* ws, int32_t buf, int32_t buf_next, ssrhip_stream_t stream) {
   SSR_REQUIRE(a && b && ws, "ssrhip_gemv_pair: null argument");
   SSR_REQUIRE(buf >= 0 && buf < 3 && buf_next >= 0 && buf_next < 3 && buf != buf_next, "ssrhip_gemv_pair: granule buffers %d -> %d (0..2, different)", buf, buf_next);
-  ensure_num_cu();
   bool merge = false;
-  const int nuwb = pair_nuwb(a, b, g_num_cu, &merge);
+  const int nuwb = pair_nuwb(a, b, ssr_num_cu(), &merge);
   if (!nuwb) return 1;
   PairK p;
   auto fill = [](GemvK& k, const ssrhip_gemv_args* g, int S) {
@@ -1545,8 +1541,6 @@ extern "C" int ssrhip_gemv(const ssrhip_gemv_args* a, ssrhip_stream_t stream) {
   SSR_REQUIRE(!a->x_tiled && !a->y_tiled && !a->w_tiled, "ssrhip_gemv: the tiled activation / weight layouts are for 5..32 rows only");
   SSR_REQUIRE(a->pro != SSRHIP_PRO_ATTN_COMBINE || (a->kv.head_dim > 0 && a->K <= 2048 && a->B * (a->K / a->kv.head_dim) <= 256), "ssrhip_gemv: combine prologue needs K <= 2048 and B*H <= 256");
   SSR_REQUIRE(a->K > 0 && a->K % 4 == 0 && a->K <= 8192, "ssrhip_gemv: K=%d must be a multiple of 4, <= 8192", a->K);
-  SSR_REQUIRE(a->N > 0 && a->groups >= 1, "ssrhip_gemv: bad N/groups");
-  ensure_num_cu();
   if (a->pro != SSRHIP_PRO_NONE) {
     SSR_REQUIRE(a->groups == 1 || a->pro == SSRHIP_PRO_LAYERNORM, "ssrhip_gemv: combine prologue needs groups==1");
     if (a->pro == SSRHIP_PRO_LAYERNORM) SSR_REQUIRE(a->x && ((a->ln_w && a->ln_b) || (!a->ln_w && !a->ln_b)), "ssrhip_gemv: LayerNorm prologue needs x and either both or none of ln_w/ln_b");
@@ -1562,15 +1556,18 @@ extern "C" int ssrhip_gemv(const ssrhip_gemv_args* a, ssrhip_stream_t stream) {
                 "ssrhip_gemv: QKV epilogue needs N==3K and a kv cache");
   }
   if (g_seg_mode < 0) { const char* e = getenv("SSRHIP_GEMV_SEG"); g_seg_mode = (e && e[0] == '0') ? 0 : 1; }
+  const int num_cu = ssr_num_cu();
+  hipStream_t s = (hipStream_t)stream;
   if (g_seg_mode) {
     bool done = false;
     switch (a->B) {
-      case 1: done = try_seg<1>(a, g_num_cu, (hipStream_t)stream); break;
-      case 2: done = try_seg<2>(a, g_num_cu, (hipStream_t)stream); break;
-      default: done = try_seg<4>(a, g_num_cu, (hipStream_t)stream); break;
+      case 1: done = try_seg<1>(a, num_cu, s); break;
+      case 2: done = try_seg<2>(a, num_cu, s); break;
+      default: done = try_seg<4>(a, num_cu, s); break;
     }
     if (done) { SSR_LAUNCH_CHECK(); return 0; }
   }
+  // the row-per-wave kernels take what the segment kernel did not
   GemvK p;
   p.a = *a;
   p.seg_shift = 0;
@@ -1585,7 +1582,7 @@ extern "C" int ssrhip_gemv(const ssrhip_gemv_args* a, ssrhip_stream_t stream) {
               "ssrhip_gemv: the row-per-wave kernels take a folded LayerNorm (ln_w == NULL) only for K <= 2048 (the segment kernel covers K = 4096 / 8192)");
   const int n_rg = 4 / p.nslice;
   // resident grid: <= 3 workgroups per CU in total (over all groups); rows dealt round-robin to wave-groups
-  int max_blocks_x = (g_blocks_per_cu * g_num_cu) / a->groups;
+  int max_blocks_x = (blocks_per_cu() * num_cu) / a->groups;
   if (max_blocks_x < 1) max_blocks_x = 1;
   // exactly `max_blocks_x` workgroups (every CU gets the same share) unless there are fewer rows than wave-groups
   int blocks_x = (a->N + n_rg - 1) / n_rg;
@@ -1596,24 +1593,11 @@ extern "C" int ssrhip_gemv(const ssrhip_gemv_args* a, ssrhip_stream_t stream) {
   p.hd = (a->kv.head_dim > 0) ? a->kv.head_dim : 1;
   size_t smem = (4 * MAX_IT * a->B + 16) * sizeof(float);
   if (a->pro != SSRHIP_PRO_NONE) {
-    SSR_REQUIRE(a->groups == 1 || a->pro == SSRHIP_PRO_LAYERNORM, "ssrhip_gemv: combine prologue needs groups==1");
     SSR_REQUIRE((size_t)a->B * a->K * 4 <= 60 * 1024 && a->K <= 4096, "ssrhip_gemv: staged prologue needs B*K*4 <= 60 KiB and K <= 4096");
     smem += (size_t)a->B * a->K * sizeof(float);
     if (a->pro == SSRHIP_PRO_ATTN_COMBINE) smem += (size_t)a->B * (a->K / a->kv.head_dim) * a->max_splits * sizeof(float) + 64;
-    if (a->pro == SSRHIP_PRO_LAYERNORM) SSR_REQUIRE(a->x && ((a->ln_w && a->ln_b) || (!a->ln_w && !a->ln_b)), "ssrhip_gemv: LayerNorm prologue needs x and either both or none of ln_w/ln_b");
-    if (a->pro == SSRHIP_PRO_ATTN_COMBINE) {
-      SSR_REQUIRE(a->part_o && a->part_ml && a->row_len && a->kv.head_dim > 0 && a->K % a->kv.head_dim == 0 && a->kv.head_dim % 4 == 0,
-                  "ssrhip_gemv: combine prologue needs part_o, part_ml, row_len, kv.head_dim");
-    }
-  } else {
-    SSR_REQUIRE(a->x, "ssrhip_gemv: x is null");
-  }
-  if (a->epi == SSRHIP_EPI_QKV_APPEND) {
-    SSR_REQUIRE(a->N == 3 * a->K && a->groups == 1 && a->kv.pool && a->kv.table && a->kv_pos && a->kv.head_dim > 0,
-                "ssrhip_gemv: QKV epilogue needs N==3K and a kv cache");
   }
   dim3 grid(blocks_x, a->groups);
-  hipStream_t s = (hipStream_t)stream;
   switch (a->B) {
     case 1: launch_b<1>(p, grid, smem, s); break;
     case 2: launch_b<2>(p, grid, smem, s); break;

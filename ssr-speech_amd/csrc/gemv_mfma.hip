@@ -168,18 +168,8 @@ __global__ __launch_bounds__(512) void gemv_mfma_kernel(const GemvM p) {
 //     a separate code path without the cross-tile refills, so no load is predicated and none is wasted;
 //   * per-tile partial sums of the waves go to LDS once (no barrier inside the row loop); after ONE barrier the waves run the
 //     epilogues of different tiles in parallel, adding the K-slices in wave order (deterministic).
+// The kernel parameter (GemvR), MAXT and the host plan that fills them are in gemv_mfma_tile.h, shared with the 17..32-row kernels.
 // =====================================================================================================================
-struct GemvR {
-  ssrhip_gemv_args a;
-  int nw;       // waves per workgroup (K split)
-  int steps;    // K / 16 MFMA k-steps in total
-  int spw;      // k-steps per wave (stream kernel: multiple of 16)
-  int units;    // ceil(N / 8) 8-row units per group
-  int wgs;      // workgroups per group (gridDim.x)
-  int hd;
-};
-
-constexpr int MAXT = 4;     // 16-row tiles per workgroup (LDS: MAXT x 8 waves x 1 KiB of partial sums)
 
 // Where a 16-row launch spends its time (round 5, VERDICT r4 item 3: "attribute, do not guess") — the stamps of tools/gemvm_lab.hip on an
 // LN + QKV launch (us after entry, median over 256 workgroups, wave 0), and an experiment built on them that did NOT pay:
@@ -672,65 +662,28 @@ __global__ __launch_bounds__(512) void gemv_rows_stream_kernel(const GemvR p) {
 
 }  // namespace
 
-// called by ssrhip_gemv for 4 < B <= 16 (arguments already validated there)
+// called by ssrhip_gemv for 4 < B <= 16 (validated here)
 int ssrhip_gemv_mfma_launch(const ssrhip_gemv_args* a, hipStream_t s) {
-  SSR_REQUIRE(a->B > 0 && a->B <= 16, "ssrhip_gemv: B=%d rows > 16", a->B);
-  SSR_REQUIRE(a->K % 16 == 0, "ssrhip_gemv (B>4): K=%d must be a multiple of 16", a->K);
-  SSR_REQUIRE(a->pro == SSRHIP_PRO_NONE || a->pro == SSRHIP_PRO_LAYERNORM,
-              "ssrhip_gemv (B>4): the split-KV combine prologue is not fused; run ssrhip_attn_combine first");
-  SSR_REQUIRE(a->x, "ssrhip_gemv: x is null");
-  SSR_REQUIRE(!a->y_tiled || (a->N % 4 == 0 && a->epi != SSRHIP_EPI_QKV_APPEND), "ssrhip_gemv: tiled y needs N %% 4 == 0 and is not available for the q output");
-  static int g_ver = -1, g_cus = 0, g_wpc = 0, g_dep8 = 0, g_nopair = 0;
+  if (int rc = gemv_rows_check(a, 1, 16, 4096)) return rc;
+  static int g_ver = -1, g_dep8 = 0;
   if (g_ver < 0) {
     const char* e = getenv("SSRHIP_GEMVM_V");          // 1: the per-tile kernel (round 1), 2: rows-per-workgroup kernels (default)
-    g_ver = (e && atoi(e) == 1) ? 1 : 2;
-    int dev = 0, cu = 0;
-    g_cus = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cu > 0) ? cu : 256;
-    const char* w = getenv("SSRHIP_GEMVM_WPC");        // tuning knob: 512-thread workgroups per CU (default 1)
-    g_wpc = (w && atoi(w) >= 1 && atoi(w) <= 4) ? atoi(w) : 1;
-    g_nopair = getenv("SSRHIP_GEMVM_NOPAIR") != nullptr;   // A/B knob: 8-row tiles with duplicated rows instead of k-step pairs
     g_dep8 = getenv("SSRHIP_GEMVM_DEP8") != nullptr;   // experiment: 8 instead of 16 weight loads in flight per wave (LayerNorm launches)
-  }
-  const int hd = a->kv.head_dim > 0 ? a->kv.head_dim : 1;
-  if (a->pro == SSRHIP_PRO_LAYERNORM) {
-    SSR_REQUIRE(a->K <= 4096, "ssrhip_gemv (B>4): LayerNorm prologue needs K <= 4096");
-    SSR_REQUIRE(!a->ln_w && !a->ln_b, "ssrhip_gemv (B>4): LayerNorm gamma/beta must be folded into W/bias (ln_w == ln_b == NULL)");
-  }
-  if (a->epi == SSRHIP_EPI_QKV_APPEND) {
-    SSR_REQUIRE(a->N == 3 * a->K && a->groups == 1 && a->kv.pool && a->kv.table && a->kv_pos && a->kv.head_dim > 0 && a->kv.head_dim % 4 == 0,
-                "ssrhip_gemv: QKV epilogue needs N==3K and a kv cache");
+    g_ver = (e && atoi(e) == 1) ? 1 : 2;
   }
   SSR_REQUIRE(!a->w_tiled || g_ver == 2, "ssrhip_gemv (B>4): the streaming-order weight layout needs the rows-per-workgroup kernels (SSRHIP_GEMVM_V=2)");
   if (g_ver == 2) {
-    GemvR r;
-    r.a = *a;
-    r.steps = a->K / 16;
-    r.hd = hd;
-    r.units = (a->N + 7) / 8;
-    const bool xreg = a->K <= 2048 || a->pro == SSRHIP_PRO_LAYERNORM;   // x slice of every wave in registers; else streamed beside W
-    const int spwx = a->K <= 2048 ? 16 : 32;             // k-steps of x a wave keeps in registers
-    if (xreg) {
-      r.nw = (r.steps + spwx - 1) / spwx;
-      r.spw = spwx;
-    } else {
-      r.nw = 8;
-      r.spw = ((r.steps + 7) / 8 + 15) / 16 * 16;
-    }
-    // one 512-thread workgroup per CU (two when the K split leaves it <= 4 waves), all groups together
-    int target = g_cus * g_wpc * (r.nw <= 4 ? 2 : 1) / a->groups;
-    if (target < 1) target = 1;
-    r.wgs = r.units < target ? r.units : target;
-    const int need = (r.units + 2 * MAXT - 1) / (2 * MAXT);   // LDS holds MAXT tiles of partials per workgroup
-    if (r.wgs < need) r.wgs = need;
-    SSR_REQUIRE(r.wgs <= 65535 * 32, "ssrhip_gemv (B>4): N too large");
+    const ssr_rows_knobs& knobs = ssr_rows_knobs_get();
+    RowsPlan pl;
+    if (int rc = gemv_rows_plan(a, /*ln_keeps_x=*/true, ssr_num_cu(), knobs, &pl)) return rc;
+    const GemvR& r = pl.r;
+    const bool ln = a->pro == SSRHIP_PRO_LAYERNORM;
     dim3 grid(r.wgs, a->groups), block(r.nw * 64);
-    // every workgroup owns exactly one 8-row unit (out-proj, FFN2) and the weights are in streaming order: k-step pairs per load
-    const bool pair = a->w_tiled && r.units <= r.wgs && r.steps % 2 == 0 && !g_nopair;
+    // the forms below exist at 5..16 rows only and are chosen on top of the plan
     // round 6, opt-in (measured slower): LayerNorm launches with the LayerNorm on four extra waves and every weight request posted at entry
     const char* ee = getenv("SSRHIP_GEMVM_EDGE");
     const int per = r.wgs > 0 ? r.units / r.wgs : 0;
-    if (a->pro == SSRHIP_PRO_LAYERNORM && a->K == 2048 && a->x_tiled && ee && ee[0] == '1' && g_wpc == 1 && a->groups == 1 &&
-        r.units % r.wgs == 0 && per >= 1 && per <= 4) {
+    if (ln && a->K == 2048 && a->x_tiled && ee && ee[0] == '1' && knobs.wpc == 1 && a->groups == 1 && r.units % r.wgs == 0 && per >= 1 && per <= 4) {
       static ssr_once_per_device once;
       if (once.need()) {
         SSR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemv_rows_edge_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, edge_lds(1)));
@@ -741,15 +694,16 @@ int ssrhip_gemv_mfma_launch(const ssrhip_gemv_args* a, hipStream_t s) {
       SSR_LAUNCH_CHECK();
       return 0;
     }
-    if (!xreg && pair) hipLaunchKernelGGL(gemv_rows_stream_kernel<true>, grid, block, 0, s, r);
-    else if (!xreg) hipLaunchKernelGGL(gemv_rows_stream_kernel<false>, grid, block, 0, s, r);
-    else if (pair && a->pro == SSRHIP_PRO_NONE && spwx == 16) hipLaunchKernelGGL((gemv_rows_xreg_kernel<SSRHIP_PRO_NONE, 16, 16, true>), grid, block, 0, s, r);
-    else if (g_dep8 && a->pro == SSRHIP_PRO_LAYERNORM && spwx == 16) hipLaunchKernelGGL((gemv_rows_xreg_kernel<SSRHIP_PRO_LAYERNORM, 16, 8>), grid, block, 0, s, r);
-    else if (a->pro == SSRHIP_PRO_LAYERNORM && spwx == 16 && getenv("SSRHIP_GEMVM_WFIRST") && getenv("SSRHIP_GEMVM_WFIRST")[0] == '1')
+    const bool x16 = r.spw == 16;                        // (x in registers) 16 k-steps of it per wave: K <= 2048
+    if (!pl.xreg && pl.pair) hipLaunchKernelGGL(gemv_rows_stream_kernel<true>, grid, block, 0, s, r);
+    else if (!pl.xreg) hipLaunchKernelGGL(gemv_rows_stream_kernel<false>, grid, block, 0, s, r);
+    else if (pl.pair && !ln && x16) hipLaunchKernelGGL((gemv_rows_xreg_kernel<SSRHIP_PRO_NONE, 16, 16, true>), grid, block, 0, s, r);
+    else if (g_dep8 && ln && x16) hipLaunchKernelGGL((gemv_rows_xreg_kernel<SSRHIP_PRO_LAYERNORM, 16, 8>), grid, block, 0, s, r);
+    else if (ln && x16 && getenv("SSRHIP_GEMVM_WFIRST") && getenv("SSRHIP_GEMVM_WFIRST")[0] == '1')
       hipLaunchKernelGGL((gemv_rows_xreg_kernel<SSRHIP_PRO_LAYERNORM, 16, 16, false, true>), grid, block, 0, s, r);
-    else if (a->pro == SSRHIP_PRO_LAYERNORM && spwx == 16) hipLaunchKernelGGL((gemv_rows_xreg_kernel<SSRHIP_PRO_LAYERNORM, 16>), grid, block, 0, s, r);
-    else if (a->pro == SSRHIP_PRO_LAYERNORM) hipLaunchKernelGGL((gemv_rows_xreg_kernel<SSRHIP_PRO_LAYERNORM, 32>), grid, block, 0, s, r);
-    else if (spwx == 16) hipLaunchKernelGGL((gemv_rows_xreg_kernel<SSRHIP_PRO_NONE, 16>), grid, block, 0, s, r);
+    else if (ln && x16) hipLaunchKernelGGL((gemv_rows_xreg_kernel<SSRHIP_PRO_LAYERNORM, 16>), grid, block, 0, s, r);
+    else if (ln) hipLaunchKernelGGL((gemv_rows_xreg_kernel<SSRHIP_PRO_LAYERNORM, 32>), grid, block, 0, s, r);
+    else if (x16) hipLaunchKernelGGL((gemv_rows_xreg_kernel<SSRHIP_PRO_NONE, 16>), grid, block, 0, s, r);
     else hipLaunchKernelGGL((gemv_rows_xreg_kernel<SSRHIP_PRO_NONE, 32>), grid, block, 0, s, r);
     SSR_LAUNCH_CHECK();
     return 0;
@@ -760,7 +714,7 @@ int ssrhip_gemv_mfma_launch(const ssrhip_gemv_args* a, hipStream_t s) {
   p.nw = (p.steps + SPW - 1) / SPW;
   if (p.nw > 8) p.nw = 8;
   p.nchunk = (p.steps + p.nw * SPW - 1) / (p.nw * SPW);
-  p.hd = hd;
+  p.hd = a->kv.head_dim > 0 ? a->kv.head_dim : 1;
   // 16-row tiles unless that gives fewer workgroups than CUs (out-proj, FFN2: N/16 = 128) — then 8-row tiles
   p.rows = (a->N / 16) * a->groups >= 256 ? 16 : 8;
   if (const char* e = getenv("SSRHIP_GEMVM_ROWS")) { const int v = atoi(e); if (v == 8 || v == 16) p.rows = v; }   // tuning knob

@@ -24,17 +24,6 @@
 
 namespace {
 
-struct Gemv32 {
-  ssrhip_gemv_args a;
-  int nw;       // waves per workgroup (K split)
-  int steps;    // K / 16 MFMA k-steps in total
-  int spw;      // k-steps per wave (stream kernel: multiple of 16)
-  int units;    // ceil(N / 8) 8-row units per group
-  int wgs;      // workgroups per group (gridDim.x)
-  int hd;
-};
-
-constexpr int MAXT32 = 4;   // 16-row tiles per workgroup (as gemv_mfma.hip MAXT: the plan is the 16-row dispatcher's)
 // Weight loads in flight per wave in the one-tile-per-k-step forms. 16 (the 16-row kernels' depth) does not fit 256 registers beside both
 // x panels and both epilogues without scratch, so the depth is halved (8 KiB per wave, 64 KiB per CU); the k-step-pair forms keep theirs.
 constexpr int DEP32 = 8;
@@ -142,10 +131,10 @@ __device__ __forceinline__ f4v pair_fold(f4v aA, f4v aB) {
 
 // K <= 2048 (SPWX = 16 k-steps per wave): both x panels of the wave's K slice in VGPRs for all of the workgroup's tiles.
 template <int PRO, bool PAIR>
-__global__ __launch_bounds__(512) void gemv_rows32_xreg(const Gemv32 p) {
+__global__ __launch_bounds__(512) void gemv_rows32_xreg(const GemvR p) {
   constexpr int SPWX = 16, DEP = PAIR ? SPWX / 2 : DEP32;
   __shared__ float red[2][2][8][16];
-  __shared__ f4v part[2][MAXT32][8][64];
+  __shared__ f4v part[2][MAXT][8][64];
   const ssrhip_gemv_args& a = p.a;
   const ssrhip_gemv_args a0p = panel_args(a, 0), a1p = panel_args(a, 1);
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -266,9 +255,9 @@ __global__ __launch_bounds__(512) void gemv_rows32_xreg(const Gemv32 p) {
 
 // K > 2048 without a LayerNorm prologue (FFN2, K = 8192): both x panels are streamed beside W (L2 hits), 16 k-steps of each in flight.
 template <bool PAIR>
-__global__ __launch_bounds__(512) void gemv_rows32_stream(const Gemv32 p) {
+__global__ __launch_bounds__(512) void gemv_rows32_stream(const GemvR p) {
   constexpr int DEP = PAIR ? 16 : DEP32;     // k-steps per refill group (the k order of a column does not depend on it)
-  __shared__ f4v part[2][MAXT32][8][64];
+  __shared__ f4v part[2][MAXT][8][64];
   const ssrhip_gemv_args& a = p.a;
   const ssrhip_gemv_args a0p = panel_args(a, 0), a1p = panel_args(a, 1);
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -407,55 +396,17 @@ __global__ __launch_bounds__(512) void gemv_rows32_stream(const Gemv32 p) {
 
 // called by ssrhip_gemv for 16 < B (validated here)
 int ssrhip_gemv_mfma32_launch(const ssrhip_gemv_args* a, hipStream_t s) {
-  SSR_REQUIRE(a->B > 16 && a->B <= 32, "ssrhip_gemv: B=%d rows not in {1,2,4} or 5..32", a->B);
-  SSR_REQUIRE(a->K % 16 == 0, "ssrhip_gemv (B>16): K=%d must be a multiple of 16", a->K);
-  SSR_REQUIRE(a->pro == SSRHIP_PRO_NONE || a->pro == SSRHIP_PRO_LAYERNORM,
-              "ssrhip_gemv (B>16): the split-KV combine prologue is not fused; run ssrhip_attn_combine first");
-  SSR_REQUIRE(a->x, "ssrhip_gemv: x is null");
-  SSR_REQUIRE(!a->y_tiled || (a->N % 4 == 0 && a->epi != SSRHIP_EPI_QKV_APPEND), "ssrhip_gemv: tiled y needs N %% 4 == 0 and is not available for the q output");
-  if (a->pro == SSRHIP_PRO_LAYERNORM) {
-    SSR_REQUIRE(a->K <= 2048, "ssrhip_gemv (B>16): LayerNorm prologue needs K=%d <= 2048", a->K);
-    SSR_REQUIRE(!a->ln_w && !a->ln_b, "ssrhip_gemv (B>16): LayerNorm gamma/beta must be folded into W/bias (ln_w == ln_b == NULL)");
-  }
-  if (a->epi == SSRHIP_EPI_QKV_APPEND) {
-    SSR_REQUIRE(a->N == 3 * a->K && a->groups == 1 && a->kv.pool && a->kv.table && a->kv_pos && a->kv.head_dim > 0 && a->kv.head_dim % 4 == 0,
-                "ssrhip_gemv: QKV epilogue needs N==3K and a kv cache");
-  }
-  // the plan is the 16-row dispatcher's (gemv_mfma.hip ssrhip_gemv_mfma_launch, rows-per-workgroup form), with the same tuning knobs:
-  // the k-step-pair decision changes the accumulation order, and a row must get the same arithmetic at 32 rows as at 16
-  static int g_cus = 0, g_wpc = 0, g_nopair = 0;
-  if (g_cus == 0) {
-    int dev = 0, cu = 0;
-    g_cus = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cu > 0) ? cu : 256;
-    const char* w = getenv("SSRHIP_GEMVM_WPC");
-    g_wpc = (w && atoi(w) >= 1 && atoi(w) <= 4) ? atoi(w) : 1;
-    g_nopair = getenv("SSRHIP_GEMVM_NOPAIR") != nullptr;
-  }
-  Gemv32 r;
-  r.a = *a;
-  r.steps = a->K / 16;
-  r.hd = a->kv.head_dim > 0 ? a->kv.head_dim : 1;
-  r.units = (a->N + 7) / 8;
-  const bool xreg = a->K <= 2048;                      // x slices of both panels in registers; else streamed beside W
-  if (xreg) {
-    r.nw = (r.steps + 15) / 16;
-    r.spw = 16;
-  } else {
-    r.nw = 8;
-    r.spw = ((r.steps + 7) / 8 + 15) / 16 * 16;
-  }
-  int target = g_cus * g_wpc * (r.nw <= 4 ? 2 : 1) / a->groups;
-  if (target < 1) target = 1;
-  r.wgs = r.units < target ? r.units : target;
-  const int need = (r.units + 2 * MAXT32 - 1) / (2 * MAXT32);
-  if (r.wgs < need) r.wgs = need;
-  SSR_REQUIRE(r.wgs <= 65535 * 32, "ssrhip_gemv (B>16): N too large");
+  if (int rc = gemv_rows_check(a, 17, 32, 2048)) return rc;
+  // the plan is the one the 16-row launcher takes for this shape: the k-step-pair decision changes the accumulation order, and a row must
+  // get the same arithmetic at 32 rows as at 16
+  RowsPlan pl;
+  if (int rc = gemv_rows_plan(a, /*ln_keeps_x=*/false, ssr_num_cu(), ssr_rows_knobs_get(), &pl)) return rc;
+  const GemvR& r = pl.r;
   dim3 grid(r.wgs, a->groups), block(r.nw * 64);
-  const bool pair = a->w_tiled && r.units <= r.wgs && r.steps % 2 == 0 && !g_nopair;
-  if (!xreg && pair) hipLaunchKernelGGL(gemv_rows32_stream<true>, grid, block, 0, s, r);
-  else if (!xreg) hipLaunchKernelGGL(gemv_rows32_stream<false>, grid, block, 0, s, r);
+  if (!pl.xreg && pl.pair) hipLaunchKernelGGL(gemv_rows32_stream<true>, grid, block, 0, s, r);
+  else if (!pl.xreg) hipLaunchKernelGGL(gemv_rows32_stream<false>, grid, block, 0, s, r);
   else if (a->pro == SSRHIP_PRO_LAYERNORM) hipLaunchKernelGGL((gemv_rows32_xreg<SSRHIP_PRO_LAYERNORM, false>), grid, block, 0, s, r);
-  else if (pair) hipLaunchKernelGGL((gemv_rows32_xreg<SSRHIP_PRO_NONE, true>), grid, block, 0, s, r);
+  else if (pl.pair) hipLaunchKernelGGL((gemv_rows32_xreg<SSRHIP_PRO_NONE, true>), grid, block, 0, s, r);
   else hipLaunchKernelGGL((gemv_rows32_xreg<SSRHIP_PRO_NONE, false>), grid, block, 0, s, r);
   SSR_LAUNCH_CHECK();
   return 0;

@@ -1,7 +1,21 @@
 // gemv_mfma_tile.h — pieces shared by the matrix-core GEMV kernels (gemv_mfma.hip: 5..16 rows, gemv_mfma32.hip: 17..32 rows):
-// the 16x16x4 fp32 MFMA, the k-slot reduction, the per-lane weight pointer of a tile and the split tile epilogue.
+// the 16x16x4 fp32 MFMA, the k-slot reduction, the per-lane weight pointer of a tile and the split tile epilogue; and, for the host, the
+// argument check and the launch plan of the rows-per-workgroup kernels, which both launchers take from here.
 #pragma once
 #include "common.h"
+
+// The two environment knobs of the rows-per-workgroup launch plan, read once per process for both launchers
+struct ssr_rows_knobs {
+  int wpc;       // tuning knob: 512-thread workgroups per CU (1..4, default 1)
+  bool nopair;   // A/B knob: 8-row tiles with duplicated rows instead of k-step pairs
+};
+inline const ssr_rows_knobs& ssr_rows_knobs_get() {
+  static const ssr_rows_knobs k = [] {
+    const char* w = getenv("SSRHIP_GEMVM_WPC");
+    return ssr_rows_knobs{(w && atoi(w) >= 1 && atoi(w) <= 4) ? atoi(w) : 1, getenv("SSRHIP_GEMVM_NOPAIR") != nullptr};
+  }();
+  return k;
+}
 
 namespace {
 
@@ -108,6 +122,77 @@ __device__ __forceinline__ const float* tile_wptr(const float* wbase, int row_lo
   const int rr = row_lo + tile * 16 + (c & (rows - 1));
   if (w_tiled) return wbase + (size_t)(rr >> 3) * 8 * K + (ks * 8 + (rr & 7)) * 4;   // streaming order: see SSRHIP_WTILED_INDEX (units are zero-padded)
   return wbase + (size_t)min(rr, N - 1) * K + ks * 4;
+}
+
+// ---- host: one argument check and one launch plan for the rows-per-workgroup kernels at 5..32 rows ----
+
+// Parameter of the rows-per-workgroup kernels (gemv_rows_*_kernel at 5..16 rows, gemv_rows32_* at 17..32)
+struct GemvR {
+  ssrhip_gemv_args a;
+  int nw;       // waves per workgroup (K split)
+  int steps;    // K / 16 MFMA k-steps in total
+  int spw;      // k-steps per wave (stream kernel: multiple of 16)
+  int units;    // ceil(N / 8) 8-row units per group
+  int wgs;      // workgroups per group (gridDim.x)
+  int hd;
+};
+
+constexpr int MAXT = 4;     // 16-row tiles per workgroup (LDS: MAXT x 8 waves x 1 KiB of partial sums, per column panel)
+
+// What ssrhip_gemv has not checked when it hands 5..32 rows to a matrix-core launcher. Runs before the first HIP runtime call.
+// [b_lo, b_hi]: the rows the launcher's kernels take; ln_kmax: the largest K whose LayerNorm prologue they fuse.
+inline int gemv_rows_check(const ssrhip_gemv_args* a, int b_lo, int b_hi, int ln_kmax) {
+  SSR_REQUIRE(a->B >= b_lo && a->B <= b_hi, "ssrhip_gemv: B=%d rows not in {1,2,4} or 5..32", a->B);
+  SSR_REQUIRE(a->K % 16 == 0, "ssrhip_gemv (B>4): K=%d must be a multiple of 16", a->K);
+  SSR_REQUIRE(a->pro == SSRHIP_PRO_NONE || a->pro == SSRHIP_PRO_LAYERNORM,
+              "ssrhip_gemv (B>4): the split-KV combine prologue is not fused; run ssrhip_attn_combine first");
+  SSR_REQUIRE(a->x, "ssrhip_gemv: x is null");
+  SSR_REQUIRE(!a->y_tiled || (a->N % 4 == 0 && a->epi != SSRHIP_EPI_QKV_APPEND), "ssrhip_gemv: tiled y needs N %% 4 == 0 and is not available for the q output");
+  if (a->pro == SSRHIP_PRO_LAYERNORM) {
+    SSR_REQUIRE(a->K <= ln_kmax, "ssrhip_gemv (B=%d): LayerNorm prologue needs K=%d <= %d", a->B, a->K, ln_kmax);
+    SSR_REQUIRE(!a->ln_w && !a->ln_b, "ssrhip_gemv (B>4): LayerNorm gamma/beta must be folded into W/bias (ln_w == ln_b == NULL)");
+  }
+  if (a->epi == SSRHIP_EPI_QKV_APPEND) {
+    SSR_REQUIRE(a->N == 3 * a->K && a->groups == 1 && a->kv.pool && a->kv.table && a->kv_pos && a->kv.head_dim > 0 && a->kv.head_dim % 4 == 0,
+                "ssrhip_gemv: QKV epilogue needs N==3K and a kv cache");
+  }
+  return 0;
+}
+
+struct RowsPlan {
+  GemvR r;      // the kernel parameter: grid = (r.wgs, a.groups), block = r.nw * 64
+  bool xreg;    // every wave keeps its x slice in registers (r.spw = 16 or 32 k-steps of it); else x is streamed beside W
+  bool pair;    // k-step pairs per weight load: it changes the accumulation order, so a row must get the same answer at every row count
+};
+
+// The plan is a function of the SHAPE alone (N, K, groups, prologue, weight layout), never of B: that is what makes row b of a 32-row
+// launch bit-identical to row b of a 16-row launch (tests/test_gpu_rows32.py). The one thing that differs between the two row counts:
+// ln_keeps_x — at 5..16 rows a LayerNorm launch keeps x in registers up to K = 4096 (32 k-steps per wave); at 17..32 rows two panels of
+// 32 k-steps do not fit, the launcher refuses LayerNorm beyond K = 2048 and x is in registers for K <= 2048 only.
+inline int gemv_rows_plan(const ssrhip_gemv_args* a, bool ln_keeps_x, int num_cu, const ssr_rows_knobs& knobs, RowsPlan* out) {
+  GemvR& r = out->r;
+  r.a = *a;
+  r.steps = a->K / 16;
+  r.hd = a->kv.head_dim > 0 ? a->kv.head_dim : 1;
+  r.units = (a->N + 7) / 8;
+  out->xreg = a->K <= 2048 || (ln_keeps_x && a->pro == SSRHIP_PRO_LAYERNORM);
+  if (out->xreg) {
+    r.spw = a->K <= 2048 ? 16 : 32;                      // k-steps of x a wave keeps in registers
+    r.nw = (r.steps + r.spw - 1) / r.spw;
+  } else {
+    r.nw = 8;
+    r.spw = ((r.steps + 7) / 8 + 15) / 16 * 16;
+  }
+  // one 512-thread workgroup per CU (two when the K split leaves it <= 4 waves), all groups together
+  int target = num_cu * knobs.wpc * (r.nw <= 4 ? 2 : 1) / a->groups;
+  if (target < 1) target = 1;
+  r.wgs = r.units < target ? r.units : target;
+  const int need = (r.units + 2 * MAXT - 1) / (2 * MAXT);   // LDS holds MAXT tiles of partials per workgroup
+  if (r.wgs < need) r.wgs = need;
+  SSR_REQUIRE(r.wgs <= 65535 * 32, "ssrhip_gemv (B>4): N too large");
+  // every workgroup owns exactly one 8-row unit (out-proj, FFN2) and the weights are in streaming order: k-step pairs per load
+  out->pair = a->w_tiled && r.units <= r.wgs && r.steps % 2 == 0 && !knobs.nopair;
+  return 0;
 }
 
 }  // namespace
