@@ -692,6 +692,9 @@ extern "C" int ssrhip_conv_few_out(const float* x, const float* w, const float* 
   while (TT > 32 && (size_t)(TT + k - 1) * (Cin + 4) * sizeof(float) + wbytes > 78 * 1024) TT >>= 1;     // two workgroups per CU
   const size_t smem = (size_t)(TT + k - 1) * (Cin + 4) * sizeof(float) + wbytes;
   SSR_REQUIRE(smem <= 160 * 1024, "ssrhip_conv_few_out: C_in * k too large");
+  // up to 160 KB of dynamic LDS (71 KB at the product's own shape): above the 64 KB a kernel gets unasked
+  static ssr_once_per_device once;
+  if (once.need()) SSR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_few_out_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   dim3 grid((T_out + TT - 1) / TT, B);
   hipLaunchKernelGGL(conv_few_out_kernel, grid, dim3(256), smem, (hipStream_t)stream, x, w, bias, out, T_out, k, Cin, Cout, act_in,
                      (long)x_bstride, (long)out_bstride, TT);

@@ -63,6 +63,42 @@ def test_codec_matches_reference(golden_dir, name):
         assert ((top2[..., 1] - top2[..., 0])[bad] < 2 * ATOL).all(), (det.cpu().numpy(), ref_det)
 
 
+@pytest.mark.parametrize("name", [n for n in CASES if n.startswith("tiny")])
+def test_decode_through_the_few_output_channel_kernel_matches_reference(golden_dir, name):
+    """`WMEncodecModel.force_few_out`: the decoder's 1-channel last layer on `ssrhip_conv_few_out` also for short inputs (the product
+    takes it from 4096 output steps on, which no tiny fixture reaches). At the tiny config that layer is (C_out, C_in, k) = (1, 8, 7):
+    the LDS form of the kernel, end to end against the reference fixture at the file's bar."""
+    g, cfg, sd = load_case(golden_dir, name)
+    assert cfg.n_filters % 8 == 0 and cfg.n_filters != 64
+    m = WMEncodecModel(cfg, sd, "cuda")
+
+    class CountingLib:
+        few_out_calls = 0
+
+        def __init__(self, lib):
+            self._lib = lib
+
+        def __getattr__(self, attr):
+            fn = getattr(self._lib, attr)
+            if attr != "ssrhip_conv_few_out":
+                return fn
+
+            def counted(*a):
+                CountingLib.few_out_calls += 1
+                return fn(*a)
+            return counted
+
+    m.lib = CountingLib(m.lib)
+    ref_codes = torch.from_numpy(g["codes"]).cuda()
+    plain = m.decode(ref_codes)
+    assert CountingLib.few_out_calls == 0
+    m.force_few_out = True
+    dec = m.decode(ref_codes)
+    assert CountingLib.few_out_calls >= 1, "the hook did not route the last layer to ssrhip_conv_few_out"
+    np.testing.assert_allclose(dec.cpu().numpy(), g["decoded"], rtol=0, atol=ATOL)
+    np.testing.assert_allclose(dec.cpu().numpy(), plain.cpu().numpy(), rtol=0, atol=2e-5)
+
+
 def test_codec_roundtrip_shapes_and_errors():
     cfg = W.codec_config_tiny()
     sd = W.codec_state_dict(cfg, seed=3)

@@ -14,6 +14,7 @@ import ssr_speech_amd  # noqa: F401
 from ssr_speech_amd import _lib
 from ssr_speech_amd import weights as W
 from oracle import lm as O
+from helpers_codec import lstm_ref, pack_whh
 
 pytestmark = pytest.mark.gpu
 
@@ -1275,18 +1276,9 @@ def test_lstm_split_step_matches_fp64(L, B, Cc, T, skip, out_act):
     whh = torch.randn(4 * Cc, Cc, generator=g) / math.sqrt(Cc)
     gin = torch.randn(B, T, 4 * Cc, generator=g)
     xs = torch.randn(B, T, Cc, generator=g)
-    h, c = torch.zeros(B, Cc, dtype=torch.float64), torch.zeros(B, Cc, dtype=torch.float64)
-    want = []
-    for t in range(T):
-        gt = gin[:, t].double() + h @ whh.double().t()
-        i, f, gg, o = gt[:, :Cc], gt[:, Cc:2 * Cc], gt[:, 2 * Cc:3 * Cc], gt[:, 3 * Cc:]
-        c = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(gg)
-        h = torch.sigmoid(o) * torch.tanh(c)
-        y = h + xs[:, t].double() if skip else h
-        want.append(F.elu(y) if out_act else y)
-    want = torch.stack(want, 1)
+    want = lstm_ref(gin, whh, xs if skip else None, bool(out_act))        # the float64 cell, shared with test_gpu_codec_kernels.py
     dw, dgin, dxs = dev(whh), dev(gin), dev(xs)
-    packed_fp32 = dev(whh.view(4, Cc // 4, 4, Cc // 16, 4, 4).permute(1, 3, 4, 2, 0, 5).contiguous())        # ssrhip_lstm_args.w_packed
+    packed_fp32 = dev(pack_whh(whh))                                        # ssrhip_lstm_args.w_packed
     planes = torch.empty(3, 4 * Cc, Cc, dtype=torch.int16, device="cuda")
     _lib.check(L.ssrhip_split_weights(dw.data_ptr(), planes.data_ptr(), dw.numel(), _lib.stream_ptr()))
     wsplit = pack_lstm_whh_planes(planes)
