@@ -233,6 +233,29 @@ class _SeaNet:
         return [n for n in self.nodes if n[0] >= lo and (hi is None or n[0] < hi)]
 
 
+# the three truth rules of the switches below (kept apart: "" counts as on for the first, as off for the second)
+_not0 = lambda v: v != "0"                                             # noqa: E731
+_on = lambda v: v not in ("", "0")                                     # noqa: E731
+_ints = lambda v: tuple(int(c) for c in v.split(",") if c)             # noqa: E731
+
+# WMEncodecModel's environment switches, read once in __init__: (attribute, switch, value when unset, parser). Tests and bench.py assign the
+# attributes directly. INTEGRATION.md §4 lists the switches; the measurements behind the defaults are in DESIGN.md (Part II, codec).
+_ENV_KNOBS = (
+    ("lstm_packed", "SSRHIP_LSTM_PACKED", "1", _not0),             # the recurrent matrix in the matrix-core step kernel's lane order
+    ("lstm_split", "SSRHIP_LSTM_SPLIT", "1", _on),                 # the recurrence on the bf16 matrix cores with split operands (csrc/lstm_split.hip)
+    ("lstm_split_min_b", "SSRHIP_LSTM_SPLIT_MIN_B", "128", int),   # ... from this many items on; below it, and with 0 above, the fp32 pipe
+    ("split_gemm", "SSRHIP_GEMM_SPLIT", "1", _not0),               # fp32 GEMMs as exactly split bf16 operands (csrc/gemm_split.hip); 0: the fp32 FMA chain
+    ("elu_on_store", "SSRHIP_ELU_ON_STORE", "1", _not0),           # ELU on store wherever a tensor is only read through ELU; 0: every consumer applies it
+    ("lanes", "SSRHIP_CODEC_LANES", "1", int),                     # batch lanes, a memory knob (`_in_lanes`) ...
+    ("lane_min_items", "SSRHIP_CODEC_LANE_MIN", "8", int),         # ... of at least this many items each
+    # the two-stream LSTM pipeline (`_lstm`) only from this many items on: a single-utterance call keeps to ONE hardware queue (DESIGN.md Part I.4)
+    ("lstm_pipe_min_b", "SSRHIP_LSTM_PIPE_MIN_B", "8", int),
+    ("presize", "SSRHIP_CODEC_PRESIZE", "1", _on),                 # the sizing passes of `_sized`; 0 is the A/B arm of tools/race_trials.py
+    # channel counts whose residual block runs as one kernel: 64 and 128 pay, 256 / 512 lose to two GEMM launches
+    ("fuse_channels", "SSRHIP_RESBLOCK_FUSE", "64,128", _ints),
+)
+
+
 class WMEncodecModel:
     def __init__(self, cfg: CodecConfig, state_dict: dict, device):
         self.cfg = cfg
@@ -242,45 +265,15 @@ class WMEncodecModel:
         self.lib = _lib.lib()
         self.fuse_resblock = True            # tests switch it off to compare with the two-GEMM path
         self.force_few_out = False           # tests: take the few-output-channel kernel also for short inputs
-        self.lstm_packed = os.environ.get("SSRHIP_LSTM_PACKED", "1") != "0"      # A/B knob for the packed recurrent matrix
-        # the recurrence on the bf16 matrix cores with split operands (csrc/lstm_split.hip). Written blind at the end of round 4; round 5's
-        # first GPU call ran it: kernel test vs fp64 green, all codec fixtures green with it, 21.0 us per step alone / 35.6 with both layers'
-        # chains sharing the GPU against 31.0 / 56.8 for the fp32-pipe kernel at 256 items, config 5 373.9 / 383.6 -> 335.7 / 344.3 ms
-        # (profiles/r05_microbench/codec256_ab.log). Default for batches of `lstm_split_min_b` items and more; SSRHIP_LSTM_SPLIT=0 = fp32 pipe.
-        self.lstm_split = os.environ.get("SSRHIP_LSTM_SPLIT", "1") not in ("", "0")
-        self.lstm_split_min_b = int(os.environ.get("SSRHIP_LSTM_SPLIT_MIN_B", "128"))
-        # channel counts whose residual block runs as one kernel (env knob for A/B runs: e.g. SSRHIP_RESBLOCK_FUSE=64,128,256,512).
-        # Measured at 32 clips x 30 s (encode / decode ms): {64}: 86.9 / 88.8; {64,128}: 86.4 / 87.7 and 1.9 GB less memory;
-        # adding 256 or 512 (short time axes, wide weights): 88.3 / 89.1-90.5 — the chained kernel's LDS footprint leaves one
-        # workgroup per CU there and loses to two ordinary GEMM launches. So 64 and 128 are fused, 256 / 512 stay two GEMMs.
-        # Batch lanes: the items of a batch are independent, so a batch can be cut into `lanes` groups that run one after the other
-        # in host order on their own HIP streams: peak memory falls with the group size (256 clips x 30 s: 81 GB in one lane, 50 GB in
-        # two, 34 GB in four) at 2-4 % of the throughput. It was built hoping that one group's LSTM (a latency-bound launch per time
-        # step) would hide under the other group's convolutions; measured, the step launches queue behind the convolutions'
-        # workgroups instead (32 clips: 85 -> 94 ms with two lanes, 122 ms with high-priority LSTM streams), so the default is ONE
-        # lane and this is a memory knob (SSRHIP_CODEC_LANES, at least `lane_min_items` items per lane).
-        # fp32 GEMMs on the bf16 matrix cores with exactly split operands (csrc/gemm_split.hip; SSRHIP_GEMM_SPLIT=0: the fp32 FMA chain)
-        self.split_gemm = os.environ.get("SSRHIP_GEMM_SPLIT", "1") != "0"
+        for attr, switch, unset, parse in _ENV_KNOBS:
+            setattr(self, attr, parse(os.environ.get(switch, unset)))
         self._plane_cache = {}
-        # ELU on store instead of ELU on load wherever a tensor is only read through ELU (SSRHIP_ELU_ON_STORE=0: every consumer applies it)
-        self.elu_on_store = os.environ.get("SSRHIP_ELU_ON_STORE", "1") != "0"
-        self.lanes = int(os.environ.get("SSRHIP_CODEC_LANES", "1"))
-        self.lane_min_items = int(os.environ.get("SSRHIP_CODEC_LANE_MIN", "8"))
         self._side_streams, self._keep = {}, {}
-        # the two-stream LSTM pipeline (`_lstm`) only where it pays: from this many items on (SSRHIP_LSTM_PIPE_MIN_B). Below it the two layers
-        # run one after the other on the calling stream — at batch 1 the pipeline saves ~3 ms of a 10 s utterance's codec time, and a second
-        # hardware queue in flight is one half of the trigger of DESIGN.md Part I.4: a single-utterance call keeps to ONE queue.
-        self.lstm_pipe_min_b = int(os.environ.get("SSRHIP_LSTM_PIPE_MIN_B", "8"))
-        # Round 6 — NO DEVICE MEMORY IS MAPPED WHILE CODEC KERNELS ARE IN FLIGHT (`_sized`; DESIGN.md "the multi-stream failure"):
-        # SSRHIP_CODEC_PRESIZE=0 switches the sizing passes off (the A/B arm of tools/race_trials.py).
-        self.presize = os.environ.get("SSRHIP_CODEC_PRESIZE", "1") not in ("", "0")
         self._envelopes = {}                 # (entry point, stream) -> [(items, samples-or-frames)] already sized
         self._small_reserved = set()
         self.passes_repeated = 0             # passes run again because the driver was asked for memory while they were in flight
         self.mallocs_in_flight = 0           # hipMallocs that happened during a call although it had been sized (tests assert 0)
         self.sizing_passes = 0
-        env = os.environ.get("SSRHIP_RESBLOCK_FUSE")
-        self.fuse_channels = tuple(int(v) for v in env.split(",") if v) if env is not None else (64, 128)
         sd = {k: v.detach().to(torch.float32).cpu() for k, v in state_dict.items()}
         dev = self.device
         self.encoder = _SeaNet(sd, "encoder.", cfg, False, dev)
@@ -340,18 +333,15 @@ class WMEncodecModel:
         """Run one dense codec pass `run()` so that the caching allocator never has to map device memory (hipMalloc) while the pass's
         kernels are in flight.
 
-        Why (round 6, DESIGN.md "the multi-stream failure"): on this platform a kernel that runs while ANOTHER hardware queue of the
-        process is busy and the host maps fresh device memory can come back with wrong values — one register of one quarter-wave, in
-        the codec's plainest kernel; 36 of 206 fresh processes on round 5's code path against 0 of 260 with these sizing passes
-        (and 0 of 147 with a warm allocator or a single hardware queue; tools/race_trials.py, profiles/r06_microbench/). A codec pass IS several queues — the two LSTM layers run on two streams —
-        and a cold process maps memory for every layer, so the first call of every process was exposed, single-stream callers
-        included. What the pass will allocate is a deterministic function of (entry point, items, length): the first time a shape is
-        not covered by one already seen on this stream, the pass runs once DRY — the device idle (synchronised), every library launch
-        a no-op, the same tensors allocated and freed in the same order — which leaves the allocator holding exactly the blocks the
-        real pass then reuses. Later calls of that size or smaller find them there. `mallocs_in_flight` counts the driver allocations
-        that still happened during real passes (a smaller shape can fall into another size class, the caller may hold more live tensors
-        than the sizing pass saw): such a pass is REPEATED — its results are dropped, the device synchronised, and it runs again from the
-        now sufficient pool (`passes_repeated`)."""
+        Why: on this platform a kernel that runs while ANOTHER hardware queue of the process is busy and the host maps fresh device memory
+        can come back with wrong values (DESIGN.md "the multi-stream failure" has the trials). A codec pass IS several queues — the two LSTM
+        layers run on two streams — and a cold process maps memory for every layer. What the pass will allocate is a deterministic function
+        of (entry point, items, length): the first time a shape is not covered by one already seen on this stream, the pass runs once DRY —
+        the device idle (synchronised), every library launch a no-op, the same tensors allocated and freed in the same order — which leaves
+        the allocator holding exactly the blocks the real pass then reuses. Later calls of that size or smaller find them there.
+        `mallocs_in_flight` counts the driver allocations that still happened during real passes (a smaller shape can fall into another
+        size class, the caller may hold more live tensors than the sizing pass saw): such a pass is REPEATED — its results are dropped,
+        the device synchronised, and it runs again from the now sufficient pool (`passes_repeated`)."""
         if not self.presize:
             return run()
         stream = torch.cuda.current_stream(self.device).cuda_stream
@@ -393,8 +383,10 @@ class WMEncodecModel:
         return run()
 
     # ------------------------------------------------------------------ low-level launches
-    def _s(self):
-        return _lib.stream_ptr()
+    def _call(self, name: str, *args):
+        """One library launch on the current stream. The entry point is looked up at call time: `_sized` swaps `self.lib` for its dry pass
+        and tests wrap it."""
+        _lib.check(getattr(self.lib, name)(*args, _lib.stream_ptr()), name)
 
     def _planes(self, W: torch.Tensor) -> Optional[torch.Tensor]:
         """bf16 planes [3][N][K] of a weight matrix for the split GEMM (csrc/gemm_split.hip: the fp32 operand as the exact sum of three
@@ -404,15 +396,13 @@ class WMEncodecModel:
         key = W.data_ptr()
         hit = self._plane_cache.get(key)
         if hit is None:
-            hit = torch.empty(3, W.shape[0], W.shape[1], dtype=torch.int16, device=W.device)
-            _lib.check(self.lib.ssrhip_split_weights(W.data_ptr(), hit.data_ptr(), W.numel(), self._s()), "ssrhip_split_weights")
-            self._plane_cache[key] = hit
+            hit = self._plane_cache[key] = self._split_planes(W)
         return hit
 
     def _split_planes(self, W: torch.Tensor) -> torch.Tensor:
         """bf16 planes [3][N][K] of any fp32 matrix (uncached: for callers that repack them, e.g. pack_lstm_whh_planes)"""
         out = torch.empty(3, W.shape[0], W.shape[1], dtype=torch.int16, device=W.device)
-        _lib.check(self.lib.ssrhip_split_weights(W.data_ptr(), out.data_ptr(), W.numel(), self._s()), "ssrhip_split_weights")
+        self._call("ssrhip_split_weights", W.data_ptr(), out.data_ptr(), W.numel())
         return out
 
     def _resblock_planes(self, c3, c1):
@@ -432,8 +422,8 @@ class WMEncodecModel:
             w3 = c3.W.reshape(Hh, -1).contiguous()
             p3 = torch.empty(3, w3.shape[0], w3.shape[1], dtype=torch.int16, device=w3.device)
             p1 = torch.empty(3, w1p.shape[0], w1p.shape[1], dtype=torch.int16, device=w3.device)
-            _lib.check(self.lib.ssrhip_split_weights(w3.data_ptr(), p3.data_ptr(), w3.numel(), self._s()), "ssrhip_split_weights")
-            _lib.check(self.lib.ssrhip_split_weights(w1p.data_ptr(), p1.data_ptr(), w1p.numel(), self._s()), "ssrhip_split_weights")
+            self._call("ssrhip_split_weights", w3.data_ptr(), p3.data_ptr(), w3.numel())
+            self._call("ssrhip_split_weights", w1p.data_ptr(), p1.data_ptr(), w1p.numel())
             torch.cuda.current_stream(w3.device).synchronize()       # w1p / w3 temporaries may be freed after this call
             hit = (p3, p1)
             self._plane_cache[key] = hit
@@ -451,7 +441,7 @@ class WMEncodecModel:
         a.tm_c, a.tm_lo, a.tm_hi = tm
         if rowcls is not None:           # (class bias [n_class][N], class ids int32 [batch][n], rows per id)
             a.rbias, a.rclass, a.rrep, a.rclass_stride = rowcls[0].data_ptr(), rowcls[1].data_ptr(), int(rowcls[2]), int(rowcls[1].shape[1])
-        _lib.check(self.lib.ssrhip_gemm(C.byref(a), self._s()), "ssrhip_gemm")
+        self._call("ssrhip_gemm", C.byref(a))
 
     def _fill_pads(self, buf: TM, structural_zero: bool = False):
         if self.cfg.pad_mode not in ("constant", "reflect"):
@@ -460,11 +450,11 @@ class WMEncodecModel:
             # ragged batch: every item gets ITS OWN halo right behind its last valid row (and in front, for reflect)
             if buf.padL + buf.padR > 0:
                 refl = int(self.cfg.pad_mode == "reflect" and not structural_zero)
-                _lib.check(self.lib.ssrhip_pad_ragged(buf.base, buf.lens.dev.data_ptr(), buf.B, buf.T, buf.padL, buf.padR, buf.C, buf.bstride,
-                                                      refl, self._s()), "ssrhip_pad_ragged")
+                self._call("ssrhip_pad_ragged", buf.base, buf.lens.dev.data_ptr(), buf.B, buf.T, buf.padL, buf.padR, buf.C, buf.bstride,
+                           refl)
             return
         if self.cfg.pad_mode == "reflect" and not structural_zero and (buf.padL + buf.padR) > 0:
-            _lib.check(self.lib.ssrhip_pad_reflect(buf.base, buf.B, buf.T, buf.padL, buf.padR, buf.C, buf.bstride, self._s()), "ssrhip_pad_reflect")
+            self._call("ssrhip_pad_reflect", buf.base, buf.B, buf.T, buf.padL, buf.padR, buf.C, buf.bstride)
         elif self.cfg.pad_mode not in ("constant", "reflect"):
             raise ValueError(self.cfg.pad_mode)
 
@@ -503,12 +493,12 @@ class WMEncodecModel:
         act_in = self._act_in(bool(c.act_in), x)
         if c.Cin == 1:
             assert c.act_in == 0 and not post_elu
-            _lib.check(self.lib.ssrhip_conv_cin1(x.base, c.Wraw.data_ptr(), c.b.data_ptr(), out.interior, B, T_out, c.k, c.s, c.Cout,
-                                                 x.bstride, out.bstride, self._s()), "ssrhip_conv_cin1")
+            self._call("ssrhip_conv_cin1", x.base, c.Wraw.data_ptr(), c.b.data_ptr(), out.interior, B, T_out, c.k, c.s, c.Cout,
+                       x.bstride, out.bstride)
         elif c.Cout <= 4 and c.s == 1 and R is None and c.Cin % 8 == 0 and (T_out >= 4096 or self.force_few_out) and not post_elu:
             # the 1-channel output layer at the sample rate: a read-bound dot-product kernel instead of a GEMM tile with 1 useful column
-            _lib.check(self.lib.ssrhip_conv_few_out(x.base, c.W.data_ptr(), c.b.data_ptr(), out.interior, B, T_out, c.k, c.Cin, c.Cout,
-                                                    act_in, x.bstride, out.bstride, self._s()), "ssrhip_conv_few_out")
+            self._call("ssrhip_conv_few_out", x.base, c.W.data_ptr(), c.b.data_ptr(), out.interior, B, T_out, c.k, c.Cin, c.Cout,
+                       act_in, x.bstride, out.bstride)
         else:
             self._gemm(x.base, c.W, c.b, out.interior, T_out, c.Cout, c.k * c.Cin, c.s * c.Cin, c.Cout, act_in=act_in,
                        R=(R.interior if R is not None else 0), ldr=(R.C if R is not None else 0), batch=B, sA=x.bstride, sC=out.bstride,
@@ -543,7 +533,7 @@ class WMEncodecModel:
             planes = self._resblock_planes(c3, c1)
             if planes is not None:
                 a.w3_split, a.w1_split = planes[0].data_ptr(), planes[1].data_ptr()
-            _lib.check(self.lib.ssrhip_resblock(C.byref(a), self._s()), "ssrhip_resblock")
+            self._call("ssrhip_resblock", C.byref(a))
             out.elu = post_elu
             self._fill_pads(out, structural_zero=(nxt is not None and nxt[1] == "convtr"))
             return out
@@ -591,17 +581,15 @@ class WMEncodecModel:
             a.gin_bstride, a.out_bstride, a.skip_bstride = T * 4 * Cc, outs[l].bstride, x.bstride
             a.t_begin, a.t_end = t0, t1
             a.out_act = _lib.ACT_ELU if (post_elu and l == nl - 1) else 0
-            _lib.check(self.lib.ssrhip_lstm_layer(C.byref(a), self._s()), "ssrhip_lstm_layer")
+            self._call("ssrhip_lstm_layer", C.byref(a))
 
         if nl == 2 and T > self.LSTM_CHUNK and B >= self.lstm_pipe_min_b:
             main = torch.cuda.current_stream(dev)
             side = self._side_stream()
             # Every tensor the side stream touches was allocated on `main`, and `main` joins the side stream (`fin`) before this function
-            # returns — also when a launch fails half way (the `finally`). A block freed later goes back to MAIN's pool and can only be handed
-            # to an allocation whose kernels run on `main`, i.e. behind `fin`: the stream order alone makes reuse safe. Rounds 4-5 ALSO called
-            # `record_stream(side)` on these tensors; that defers their reuse until the GPU has passed an event recorded at release time — in a
-            # real pass the host is far ahead of the GPU, in a sizing pass (`_sized`) there is nothing to wait for, so the two would allocate
-            # differently and the real pass would map memory while its kernels are in flight. SSRHIP_RECORD_STREAM=1 brings the calls back.
+            # returns — also when a launch fails half way (the `finally`): the stream order alone makes reuse of a freed block safe.
+            # `record_stream(side)` would defer reuse until the GPU passes an event recorded at release time, which a sizing pass (`_sized`)
+            # never waits for: the two would allocate differently. SSRHIP_RECORD_STREAM=1 brings the calls back.
             if os.environ.get("SSRHIP_RECORD_STREAM", "0") not in ("", "0"):
                 for tns in gins + hbufs + cbufs + [o.data for o in outs] + [x.data] + [h for h in hsplits if h is not None]:
                     tns.record_stream(side)
@@ -647,11 +635,7 @@ class WMEncodecModel:
     def _in_lanes(self, B: int, body):
         """Run `body(lo, hi) -> tuple of tensors` for the batch lanes [lo, hi) ONE AFTER THE OTHER on the calling stream and return
         the list of per-lane results. Lanes are a memory knob: a lane's intermediates are freed before the next lane allocates its
-        own, so the peak falls with the lane size (256 clips x 30 s: 81 GB in one lane, 34 GB in four). Round 2 ran the lanes
-        concurrently on their own streams, hoping to hide one lane's LSTM under another's convolutions; measured, that was SLOWER
-        (32 clips: 85 -> 94 ms with two lanes: the step launches queue behind the other lane's resident workgroups), and round 3 found
-        it unsafe as well (with the faster split GEMM the last lane's LSTM state was intermittently corrupted: tests/test_gpu_codec.py
-        ::test_batch_lanes_equal_one_lane failed one run in two) — so the streams are gone."""
+        own, so the peak falls with the lane size. Lanes on streams of their own were slower and unsafe (DESIGN.md "Batch lanes")."""
         cuts = self._lane_cuts(B)
         if cuts is None:
             return [body(0, B)]
@@ -703,8 +687,8 @@ class WMEncodecModel:
             emb = self._run(self.encoder.nodes, inp)
             B, T, D = emb.B, emb.T, emb.C
             codes = _empty(B, self.cfg.n_q, T, dtype=torch.int32, device=self.device)
-            _lib.check(self.lib.ssrhip_rvq_encode(emb.interior, self.codebooks.data_ptr(), self.e2.data_ptr(), codes.data_ptr(), B, T, D,
-                                                  self.cfg.n_q, self.cfg.bins, emb.bstride, self._s()), "ssrhip_rvq_encode")
+            self._call("ssrhip_rvq_encode", emb.interior, self.codebooks.data_ptr(), self.e2.data_ptr(), codes.data_ptr(), B, T, D,
+                       self.cfg.n_q, self.cfg.bins, emb.bstride)
             return codes.to(torch.int64), emb.interior_view().transpose(1, 2).contiguous()
 
         parts = self._in_lanes(x.shape[0], lambda lo, hi: self._sized("encode", hi - lo, int(x.shape[-1]), lambda: body(lo, hi)))
@@ -725,8 +709,8 @@ class WMEncodecModel:
         B, K, T = c32.shape
         c32 = c32.contiguous()
         out = self._alloc_for(B, T, self.cfg.dimension, nxt, lens)
-        _lib.check(self.lib.ssrhip_rvq_decode(c32.data_ptr(), self.codebooks.data_ptr(), out.interior, B, T, self.cfg.dimension, K,
-                                              self.cfg.bins, out.bstride, self._s()), "ssrhip_rvq_decode")
+        self._call("ssrhip_rvq_decode", c32.data_ptr(), self.codebooks.data_ptr(), out.interior, B, T, self.cfg.dimension, K,
+                   self.cfg.bins, out.bstride)
         self._fill_pads(out)
         return out
 

@@ -651,6 +651,17 @@ inline int nblocks(long total, int cap = 4096) {
   return (int)(n < 1 ? 1 : (n > cap ? cap : n));
 }
 
+// ssrhip_lstm_layer's matrix-core step (16-item batch tiles; any C % 16 == 0, any B), planned once per call. Wide: 16 hidden units per
+// workgroup, W_hh slice in registers, `wide_nq` batch tiles walked in sequence (from 8 tiles on: at 4 it measured slower);
+// otherwise two / one batch tile per workgroup.
+enum lstm_mfma_form { LSTM_WIDE, LSTM_MFMA2, LSTM_MFMA1 };
+struct lstm_mfma_plan { lstm_mfma_form form; dim3 grid, block; int wide_nq; };
+lstm_mfma_plan plan_lstm_mfma(const ssrhip_lstm_args* a, int nbt, int nw, const codec_knobs& k) {
+  if (a->w_packed && nbt >= 8 && a->C % 16 == 0 && a->C >= 64 && !k.lstm_nowide) return {LSTM_WIDE, dim3(a->C / 16, (nbt + 3) / 4), dim3(256), 4};
+  if (nbt >= 2 && nw >= 2) return {LSTM_MFMA2, dim3((a->C + 3) / 4, (nbt + 1) / 2), dim3(nw * 64), 0};
+  return {LSTM_MFMA1, dim3((a->C + 3) / 4, nbt), dim3(nw * 64), 0};
+}
+
 }  // namespace
 
 extern "C" int ssrhip_conv_cin1(const float* x, const float* w, const float* bias, float* out, int32_t B, int32_t T_out, int32_t k,
@@ -679,8 +690,7 @@ extern "C" int ssrhip_conv_few_out(const float* x, const float* w, const float* 
   SSR_REQUIRE(Cin % 8 == 0 && Cout <= 4 && B <= 65535, "ssrhip_conv_few_out: needs C_in %% 8 == 0 and C_out <= 4");
   SSR_REQUIRE(act_in == SSRHIP_ACT_NONE || act_in == SSRHIP_ACT_ELU, "ssrhip_conv_few_out: act_in must be NONE or ELU");
   // one output channel, 64 input channels, at most 16 taps (SEANet's last layer): the matrix-core form (SSRHIP_CONV_FEW_MFMA=0: the LDS form)
-  static const bool mfma_off = getenv("SSRHIP_CONV_FEW_MFMA") && getenv("SSRHIP_CONV_FEW_MFMA")[0] == '0';
-  if (!mfma_off && Cout == 1 && Cin == 64 && k <= 16) {
+  if (ssr_codec_knobs().conv_few_mfma && Cout == 1 && Cin == 64 && k <= 16) {
     dim3 grid((T_out + 255) / 256, B);
     if (act_in == SSRHIP_ACT_ELU) hipLaunchKernelGGL((conv_one_out_mfma_kernel<4, true>), grid, dim3(256), 0, (hipStream_t)stream, x, w, bias, out, T_out, k, (long)x_bstride, (long)out_bstride);
     else hipLaunchKernelGGL((conv_one_out_mfma_kernel<4, false>), grid, dim3(256), 0, (hipStream_t)stream, x, w, bias, out, T_out, k, (long)x_bstride, (long)out_bstride);
@@ -693,8 +703,7 @@ extern "C" int ssrhip_conv_few_out(const float* x, const float* w, const float* 
   const size_t smem = (size_t)(TT + k - 1) * (Cin + 4) * sizeof(float) + wbytes;
   SSR_REQUIRE(smem <= 160 * 1024, "ssrhip_conv_few_out: C_in * k too large");
   // up to 160 KB of dynamic LDS (71 KB at the product's own shape): above the 64 KB a kernel gets unasked
-  static ssr_once_per_device once;
-  if (once.need()) SSR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_few_out_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  SSR_RAISE_LDS(160 * 1024, conv_few_out_kernel);
   dim3 grid((T_out + TT - 1) / TT, B);
   hipLaunchKernelGGL(conv_few_out_kernel, grid, dim3(256), smem, (hipStream_t)stream, x, w, bias, out, T_out, k, Cin, Cout, act_in,
                      (long)x_bstride, (long)out_bstride, TT);
@@ -740,39 +749,33 @@ extern "C" int ssrhip_lstm_layer(const ssrhip_lstm_args* a, ssrhip_stream_t stre
   SSR_REQUIRE(!a->w_split == !a->hsplit, "ssrhip_lstm_layer: w_split and hsplit go together");
   if (!small_b && ssrhip_lstm_split_eligible(a)) return ssrhip_lstm_split_steps(a, t_lo, t_hi, s);   // bf16 matrix cores, split operands
   if (t_lo == 0) hipLaunchKernelGGL(zero_kernel, dim3(nblocks(2 * hc)), dim3(256), 0, s, a->hbuf, (long)(2 * hc));   // h_0 = 0
-  {
-    // small-batch kernel: C in {256, 512, 1024, 2048}; anything else (e.g. the narrow test configs) takes the matrix-core
-    // path, which handles any C % 16 == 0 and any B
-    if (small_b) {
-      SSR_REQUIRE(!a->w_packed, "ssrhip_lstm_layer: the small-batch path reads W_hh in torch's [4C][C] layout");
-      for (int t = t_lo; t < t_hi; ++t) {
-        const float* hp = a->hbuf + (size_t)(t & 1) * hc;
-        float* hn = a->hbuf + (size_t)((t + 1) & 1) * hc;
-        switch (a->B) {
-          case 1: launch_lstm_step<1>(*a, t, hp, hn, s); break;
-          case 2: launch_lstm_step<2>(*a, t, hp, hn, s); break;
-          case 3: launch_lstm_step<3>(*a, t, hp, hn, s); break;
-          default: launch_lstm_step<4>(*a, t, hp, hn, s); break;
-        }
+  // small-batch kernel: C in {256, 512, 1024, 2048}; anything else (e.g. the narrow test configs) takes the matrix-core path
+  if (small_b) {
+    SSR_REQUIRE(!a->w_packed, "ssrhip_lstm_layer: the small-batch path reads W_hh in torch's [4C][C] layout");
+    for (int t = t_lo; t < t_hi; ++t) {
+      const float* hp = a->hbuf + (size_t)(t & 1) * hc;
+      float* hn = a->hbuf + (size_t)((t + 1) & 1) * hc;
+      switch (a->B) {
+        case 1: launch_lstm_step<1>(*a, t, hp, hn, s); break;
+        case 2: launch_lstm_step<2>(*a, t, hp, hn, s); break;
+        case 3: launch_lstm_step<3>(*a, t, hp, hn, s); break;
+        default: launch_lstm_step<4>(*a, t, hp, hn, s); break;
       }
-    } else {
-      // hbuf holds [2][ceil(B/16)][C/4][16][4] (tiled per 16-item batch tile) on this path
-      const int steps = a->C / 16;
-      SSR_REQUIRE(!a->w_packed || a->C % 16 == 0, "ssrhip_lstm_layer: packed W_hh needs C %% 16 == 0");
-      SSR_REQUIRE(a->C <= 1024, "ssrhip_lstm_layer: the matrix-core path (B > 4, or C not in {256,512,1024,2048}) needs C <= 1024");
-      const int nw = (steps + 15) / 16;                        // 256 columns of W_hh per wave -> <= 4 waves
-      // large batches: 16 hidden units per workgroup, W_hh slice in registers, batch tiles walked in sequence (lstm_step_wide_kernel)
-      static const bool no_wide = getenv("SSRHIP_LSTM_NOWIDE") != nullptr;
-      // measured (encode / decode ms): 256 x 30 s: 602 / 611 -> 595 / 604 (step 63.9 -> 56.1 us with the two layers' launches sharing
-      // the GPU, 36.8 -> 27.8 us alone); 64 x 30 s (4 tiles -> 128 workgroups): 156.5 / 159.0 -> 158.3 / 161.8, so it starts at 8 tiles
-      const bool wide = a->w_packed && nbt >= 8 && a->C % 16 == 0 && a->C >= 64 && !no_wide;
-      const int wide_nq = 4;
-      for (int t = t_lo; t < t_hi; ++t) {
-        const float* hp = a->hbuf + (size_t)(t & 1) * hc;
-        float* hn = a->hbuf + (size_t)((t + 1) & 1) * hc;
-        if (wide) hipLaunchKernelGGL((lstm_step_wide_kernel<4>), dim3(a->C / 16, (nbt + wide_nq - 1) / wide_nq), dim3(256), 0, s, *a, t, hp, hn, nw, steps, nbt, wide_nq);
-        else if (nbt >= 2 && nw >= 2) hipLaunchKernelGGL((lstm_step_mfma_kernel<2>), dim3((a->C + 3) / 4, (nbt + 1) / 2), dim3(nw * 64), 0, s, *a, t, hp, hn, nw, steps, nbt);
-        else hipLaunchKernelGGL((lstm_step_mfma_kernel<1>), dim3((a->C + 3) / 4, nbt), dim3(nw * 64), 0, s, *a, t, hp, hn, nw, steps, nbt);
+    }
+  } else {
+    // hbuf holds [2][ceil(B/16)][C/4][16][4] (tiled per 16-item batch tile) on this path
+    const int steps = a->C / 16;
+    SSR_REQUIRE(!a->w_packed || a->C % 16 == 0, "ssrhip_lstm_layer: packed W_hh needs C %% 16 == 0");
+    SSR_REQUIRE(a->C <= 1024, "ssrhip_lstm_layer: the matrix-core path (B > 4, or C not in {256,512,1024,2048}) needs C <= 1024");
+    const int nw = (steps + 15) / 16;                        // 256 columns of W_hh per wave -> <= 4 waves
+    const lstm_mfma_plan p = plan_lstm_mfma(a, nbt, nw, ssr_codec_knobs());   // outside the loop, which issues thousands of launches per pass
+    for (int t = t_lo; t < t_hi; ++t) {
+      const float* hp = a->hbuf + (size_t)(t & 1) * hc;
+      float* hn = a->hbuf + (size_t)((t + 1) & 1) * hc;
+      switch (p.form) {
+        case LSTM_WIDE: hipLaunchKernelGGL((lstm_step_wide_kernel<4>), p.grid, p.block, 0, s, *a, t, hp, hn, nw, steps, nbt, p.wide_nq); break;
+        case LSTM_MFMA2: hipLaunchKernelGGL((lstm_step_mfma_kernel<2>), p.grid, p.block, 0, s, *a, t, hp, hn, nw, steps, nbt); break;
+        case LSTM_MFMA1: hipLaunchKernelGGL((lstm_step_mfma_kernel<1>), p.grid, p.block, 0, s, *a, t, hp, hn, nw, steps, nbt); break;
       }
     }
   }
@@ -784,7 +787,7 @@ extern "C" int ssrhip_rvq_encode(const float* emb, const float* codebooks, const
                                  int32_t D, int32_t n_q, int32_t bins, int64_t emb_bstride, ssrhip_stream_t stream) {
   SSR_REQUIRE(emb && codebooks && e2 && codes && B > 0 && T > 0 && D > 0 && D % 4 == 0 && n_q > 0 && bins > 0, "ssrhip_rvq_encode: bad argument");
   SSR_REQUIRE(B <= 65535, "ssrhip_rvq_encode: B too large");
-  const bool mfma = bins % 16 == 0 && bins >= 64 && (D == 32 || D == 64 || D == 128 || D == 256) && !getenv("SSRHIP_RVQ_SCALAR");
+  const bool mfma = bins % 16 == 0 && bins >= 64 && (D == 32 || D == 64 || D == 128 || D == 256) && !getenv_set("SSRHIP_RVQ_SCALAR");   // read at every call
   if (mfma) {
     dim3 grid((T + 15) / 16, B);
     hipStream_t s = (hipStream_t)stream;

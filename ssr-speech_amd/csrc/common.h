@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
 #include "ssrhip.h"
 
 #define SSR_WAVE 64
@@ -40,6 +42,33 @@ struct ssr_once_per_device {
   }
 };
 
+// Raise a kernel's dynamic-LDS limit (64 KB unasked) to `bytes`, once per device at this call site: SSR_RAISE_LDS(bytes, kernel<...>)
+#define SSR_RAISE_LDS(bytes, ...)                                             \
+  do {                                                                        \
+    static ssr_once_per_device _once;                                         \
+    if (_once.need()) SSR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&__VA_ARGS__), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes))); \
+  } while (0)
+
+// ---- environment switches of the codec / prefill launchers: three parse rules ...
+inline bool getenv_on(const char* name, bool unset) { const char* e = getenv(name); return e ? e[0] != '0' : unset; }   // off iff "0..."
+inline bool getenv_set(const char* name) { return getenv(name) != nullptr; }    // on iff set (any value, the empty one included)
+inline int getenv_int(const char* name, int unset) { const char* e = getenv(name); return e ? atoi(e) : unset; }
+// ... and the once-per-process switches, read together at the first launch that asks. SSRHIP_RVQ_SCALAR and SSRHIP_GEMM_XCD are NOT here:
+// they are read at every call (tests flip them inside one process).
+struct codec_knobs {
+  bool gemm_split = getenv_on("SSRHIP_GEMM_SPLIT", true);            // A/B knobs, on unless "0...": 0 = the exact fp32 chain everywhere,
+  bool gemm_split_dma = getenv_on("SSRHIP_GEMM_SPLIT_DMA", true);    // the 4-wave split kernels,
+  bool resblock_dma = getenv_on("SSRHIP_RESBLOCK_DMA", true);        // the chained residual-block kernels,
+  bool epilogue_tm = getenv_on("SSRHIP_EPILOGUE_TM", true);          // the time mask in the general per-element epilogue,
+  bool conv_few_mfma = getenv_on("SSRHIP_CONV_FEW_MFMA", true);      // the LDS form of the one-output-channel convolution
+  bool gemm_wide = getenv_on("SSRHIP_EPILOGUE_WIDE", true);          // the 16-byte epilogue: the split GEMM's default ...
+  bool resblock_wide = getenv_on("SSRHIP_EPILOGUE_WIDE", false);     // ... but in the residual block only when set and not "0..."
+  bool lstm_nowide = getenv_set("SSRHIP_LSTM_NOWIDE");
+  int gemm_big = getenv_int("SSRHIP_GEMM_BIG", 0), reschain_big = getenv_int("SSRHIP_RESCHAIN_BIG", 0);   // experiments: larger tiles / row blocks
+  int resblock_ring = getenv_int("SSRHIP_RESBLOCK_RING", 2);         // any value other than 2 takes the ring-of-4 kernels
+};
+inline const codec_knobs& ssr_codec_knobs() { static const codec_knobs k; return k; }
+
 // CU count of the current device, asked once per process by whichever GEMV launcher runs first (256 where there is no device to ask)
 inline int ssr_num_cu() {
   static const int n = [] {
@@ -51,8 +80,6 @@ inline int ssr_num_cu() {
 
 // profiling aid (tools/prof_summary.py --gemm-log): one line per GEMM launch — M N K batch, the launch grid, split (1) or fp32 chain (0) —
 // so that a kernel trace's GEMM rows get their problem size and a TFLOP/s column. Off unless SSRHIP_GEMM_LOG names a file.
-#include <stdio.h>
-#include <stdlib.h>
 static inline void ssr_gemm_log(const ssrhip_gemm_args* a, unsigned gx, unsigned gy, unsigned gz, int split) {
   static FILE* glog = getenv("SSRHIP_GEMM_LOG") ? fopen(getenv("SSRHIP_GEMM_LOG"), "a") : nullptr;
   if (glog) {

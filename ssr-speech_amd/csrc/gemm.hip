@@ -227,20 +227,19 @@ extern "C" int ssrhip_gemm(const ssrhip_gemm_args* a, ssrhip_stream_t stream) {
   SSR_REQUIRE(a->M > 0 && a->N > 0 && a->K > 0 && a->K % 4 == 0 && a->lda % 4 == 0, "ssrhip_gemm: K and lda must be multiples of 4");
   SSR_REQUIRE(!a->rbias || (a->rclass && a->rrep > 0), "ssrhip_gemm: rbias needs rclass and rrep > 0");
   if (ssrhip_gemm_split_eligible(a)) return ssrhip_gemm_split_launch(a, (hipStream_t)stream);    // caller supplied bf16 weight planes
+  const int nb = a->batch > 1 ? a->batch : 1;
   int bm = a->N <= 64 ? 256 : 64, bn = a->N <= 32 ? 32 : (a->N <= 64 ? 64 : 128);
-  const long wide_wgs = (long)((a->N + 127) / 128) * ((a->M + 63) / 64) * (a->batch > 1 ? a->batch : 1);
+  const long wide_wgs = (long)((a->N + 127) / 128) * ((a->M + 63) / 64) * nb;
   const bool small_grid = a->N > 64 && wide_wgs < 256;
   if (small_grid) bn = 64;
   SSR_REQUIRE(a->batch <= 65535 && (a->M + bm - 1) / bm <= 65535, "ssrhip_gemm: grid too large (M=%d batch=%d)", a->M, a->batch);
-  dim3 grid((a->N + bn - 1) / bn, (a->M + bm - 1) / bm, a->batch > 1 ? a->batch : 1);
+  dim3 grid((a->N + bn - 1) / bn, (a->M + bm - 1) / bm, nb);
   ssr_gemm_log(a, grid.x, grid.y, grid.z, 0);
-  // Experiment knob (off): 128 x 128 tiles (each wave 64 x 64: twice the FLOPs per operand byte staged through LDS). Measured
-  // SLOWER on the codec (32 clips x 30 s: encode 86.6 -> 96.7 ms, decode 88.5 -> 98.2 ms): one workgroup per CU no longer
-  // hides the two barriers per k-tile.
-  static const int big_tiles = getenv("SSRHIP_GEMM_BIG") ? atoi(getenv("SSRHIP_GEMM_BIG")) : 0;
-  const long big_wgs = (long)((a->N + 127) / 128) * ((a->M + 127) / 128) * (a->batch > 1 ? a->batch : 1);
-  if (big_tiles && a->N >= 128 && big_wgs >= 512) {
-    dim3 g2((a->N + 127) / 128, (a->M + 127) / 128, a->batch > 1 ? a->batch : 1);
+  // Experiment knob SSRHIP_GEMM_BIG (off): 128 x 128 tiles (each wave 64 x 64: twice the FLOPs per operand byte staged through LDS).
+  // Measured SLOWER on the codec: one workgroup per CU no longer hides the two barriers per k-tile.
+  const long big_wgs = (long)((a->N + 127) / 128) * ((a->M + 127) / 128) * nb;
+  if (ssr_codec_knobs().gemm_big && a->N >= 128 && big_wgs >= 512) {
+    dim3 g2((a->N + 127) / 128, (a->M + 127) / 128, nb);
     SSR_REQUIRE(g2.y <= 65535, "ssrhip_gemm: grid too large (M=%d)", a->M);
     hipLaunchKernelGGL((gemm_kernel<2, 2, 2, 2>), g2, dim3(256), 0, (hipStream_t)stream, *a);
     SSR_LAUNCH_CHECK();

@@ -556,71 +556,74 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(4, 4))) 
 // (never a silent fallback) when the runtime refuses it.
 bool ssrhip_gemm_split_eligible(const ssrhip_gemm_args* a) {
   if (!a->W_split || a->N <= 64 || a->K % 8 != 0 || a->lda % 4 != 0) return false;
-  static const int off = getenv("SSRHIP_GEMM_SPLIT") && getenv("SSRHIP_GEMM_SPLIT")[0] == '0';   // A/B knob: always the exact fp32 chain
-  return !off && (a->M + 63) / 64 <= 65535 && a->batch <= 65535;
+  return ssr_codec_knobs().gemm_split && (a->M + 63) / 64 <= 65535 && a->batch <= 65535;   // SSRHIP_GEMM_SPLIT=0: always the exact fp32 chain
 }
 
-int ssrhip_gemm_split_launch(const ssrhip_gemm_args* a, hipStream_t s) {
-  const long nb = a->batch > 1 ? a->batch : 1;
+namespace {
+
+// BM 128 / 64 x (8-wave DMA kernel | 4-wave kernel); the DMA kernel at BM = 128 also with the time mask folded into the 16-byte epilogue
+enum gemm_split_form { GS_DMA128, GS_DMA64, GS_DMA128_TM, GS_4WAVE128, GS_4WAVE64 };
+struct gemm_split_plan { gemm_split_form form; dim3 grid, block; int lds, flags; };      // `flags`: the DMA kernels' flag word
+
+// `xcd` is SSRHIP_GEMM_XCD as of this call (read at every launch: tests flip it inside one process)
+gemm_split_plan plan_gemm_split(const ssrhip_gemm_args* a, const codec_knobs& k, const char* xcd) {
+  const unsigned nb = a->batch > 1 ? a->batch : 1;
   const long tiles128 = (long)((a->N + BN - 1) / BN) * ((a->M + 127) / 128) * nb;
-  const bool elu = a->act_in == SSRHIP_ACT_ELU;
   // 128-row tiles when there are enough of them for two workgroups on most CUs — unless they would be half empty: the LSTM's second
   // layer projects 64-step chunks (M = 64 per item: a 128-row tile wastes half of its MFMAs; seen in the codec trace: 96 launches of
   // 212 us at 32 clips)
   const int waste128 = (a->M + 127) / 128 * 128 - a->M, waste64 = (a->M + 63) / 64 * 64 - a->M;
   const bool half_empty = waste128 - waste64 >= 64 && 8 * (waste128 - waste64) >= a->M;
+  const int bm = tiles128 >= 384 && !half_empty ? 128 : 64;
   // the DMA kernels address a tile through 32-bit buffer offsets: 128 rows of A (and of a W plane) have to stay below 2 GiB
-  static const bool dma_off = getenv("SSRHIP_GEMM_SPLIT_DMA") && getenv("SSRHIP_GEMM_SPLIT_DMA")[0] == '0';   // A/B knob: the 4-wave kernels
-  const bool dma = !dma_off && ((size_t)127 * a->lda + a->K) * 4 < 0x7FFFFFF0ull && (size_t)128 * a->K * 2 < 0x7FFFFFF0ull;
-  static const int wide1 = !(getenv("SSRHIP_EPILOGUE_WIDE") && getenv("SSRHIP_EPILOGUE_WIDE")[0] == '0');     // A/B knob: 0 = dword epilogue
-  // XCD-aware tile order of the DMA kernels (read at every launch: tests flip it inside one process); total tiles must fit 32 bits
-  const char* xe = getenv("SSRHIP_GEMM_XCD");
-  // N-tile group width of the XCD order: W tiles of one group (3 bf16 planes of 128 rows x K) within ~2.5 MB of an XCD's 4 MB L2
+  const bool dma = k.gemm_split_dma && ((size_t)127 * a->lda + a->K) * 4 < 0x7FFFFFF0ull && (size_t)128 * a->K * 2 < 0x7FFFFFF0ull;
+  // the transposed convolutions' time mask as a row predicate of the 16-byte epilogue (SSRHIP_EPILOGUE_TM=0: the general per-element loop)
+  const bool tmf = k.epilogue_tm && k.gemm_wide && a->tm_c > 0 && a->N % a->tm_c == 0 && a->tm_c % 4 == 0 && !a->R && !a->residual && !a->rbias &&
+                   a->ldc % 4 == 0 && a->strideC % 4 == 0 && ((uintptr_t)a->C & 15) == 0 && (long)a->M * (a->N / a->tm_c) < 0x7FFFFFFFL;
+  const dim3 grid((a->N + BN - 1) / BN, (a->M + bm - 1) / bm, nb);
+  if (!dma) return {bm == 128 ? GS_4WAVE128 : GS_4WAVE64, grid, dim3(256), 0, 0};
+  gemm_split_plan p{bm == 64 ? GS_DMA64 : tmf ? GS_DMA128_TM : GS_DMA128, grid, dim3(512), dma_lds(bm), 0};
+  // flag word: bit 0 the 16-byte epilogue, bit 1 the XCD-aware tile order ("0...": plain order), bits 8.. its N-tile group width: W tiles
+  // of one group (3 bf16 planes of 128 rows x K) within ~2.5 MB of an XCD's 4 MB L2; "d:<GN>" (d in 1..9) forces the width (lab)
   const long wtile = 128L * a->K * 6;
   long gn = wtile > 0 ? (2560L * 1024) / wtile : 1;
   if (gn < 1) gn = 1;
   if (gn > 255) gn = 255;
-  if (xe && xe[0] >= '1' && xe[0] <= '9' && xe[1] == ':') gn = atoi(xe + 2) > 0 ? atoi(xe + 2) : gn;   // "1:<GN>": force the group width (lab)
-  const int flags0 = wide1 | ((xe && xe[0] == '0') ? 0 : 2) | (int)(gn << 8);
-  // the transposed convolutions' time mask as a row predicate of the 16-byte epilogue (SSRHIP_EPILOGUE_TM=0: the general per-element loop)
-  static const bool tm_knob = !(getenv("SSRHIP_EPILOGUE_TM") && getenv("SSRHIP_EPILOGUE_TM")[0] == '0');
-  const bool tmf = tm_knob && wide1 && a->tm_c > 0 && a->N % a->tm_c == 0 && a->tm_c % 4 == 0 && !a->R && !a->residual && !a->rbias && a->ldc % 4 == 0 &&
-                   a->strideC % 4 == 0 && ((uintptr_t)a->C & 15) == 0 && (long)a->M * (a->N / a->tm_c) < 0x7FFFFFFFL;
-  if (dma) {
-    static ssr_once_per_device once;
-    if (once.need()) {
-      SSR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_split_dma_kernel<128, true>), hipFuncAttributeMaxDynamicSharedMemorySize, dma_lds(128)));
-      SSR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_split_dma_kernel<128, false>), hipFuncAttributeMaxDynamicSharedMemorySize, dma_lds(128)));
-      SSR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_split_dma_kernel<64, true>), hipFuncAttributeMaxDynamicSharedMemorySize, dma_lds(64)));
-      SSR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_split_dma_kernel<64, false>), hipFuncAttributeMaxDynamicSharedMemorySize, dma_lds(64)));
-      if (tm_knob) {
-        SSR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_split_dma_kernel<128, true, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, dma_lds(128)));
-        SSR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_split_dma_kernel<128, false, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, dma_lds(128)));
-      }
-    }
+  if (xcd && xcd[0] >= '1' && xcd[0] <= '9' && xcd[1] == ':') gn = atoi(xcd + 2) > 0 ? atoi(xcd + 2) : gn;
+  p.flags = (int)k.gemm_wide | ((xcd && xcd[0] == '0') ? 0 : 2) | (int)(gn << 8);
+  if ((long)p.grid.x * p.grid.y * p.grid.z > 0x7FFFFFFFL) p.flags &= 1;      // the remap counts tiles in 32 bits
+  return p;
+}
+
+// One form's launch. ELU on load is a template parameter of the kernels, so every form is an ELU / no-ELU pair, which launch_split picks from.
+// The DMA kernels need more than the 64 KB of dynamic LDS a kernel gets unasked; TM is theirs alone.
+template <bool DMA, int BM, bool TM, bool ELU>
+int launch_split_one(const gemm_split_plan& p, const ssrhip_gemm_args* a, hipStream_t s) {
+  if constexpr (DMA) {
+    SSR_RAISE_LDS(p.lds, gemm_split_dma_kernel<BM, ELU, 0, TM>);
+    hipLaunchKernelGGL((gemm_split_dma_kernel<BM, ELU, 0, TM>), p.grid, p.block, p.lds, s, *a, p.flags);
+  } else hipLaunchKernelGGL((gemm_split_kernel<BM, ELU>), p.grid, p.block, 0, s, *a);
+  return 0;
+}
+template <bool DMA, int BM, bool TM = false>
+int launch_split(const gemm_split_plan& p, const ssrhip_gemm_args* a, hipStream_t s) {
+  return a->act_in == SSRHIP_ACT_ELU ? launch_split_one<DMA, BM, TM, true>(p, a, s) : launch_split_one<DMA, BM, TM, false>(p, a, s);
+}
+
+}  // namespace
+
+int ssrhip_gemm_split_launch(const ssrhip_gemm_args* a, hipStream_t s) {
+  const gemm_split_plan p = plan_gemm_split(a, ssr_codec_knobs(), getenv("SSRHIP_GEMM_XCD"));
+  ssr_gemm_log(a, p.grid.x, p.grid.y, p.grid.z, 1);
+  int rc = 0;
+  switch (p.form) {      // in this order: hipcc emits the kernels in the order of their first use
+    case GS_DMA128: rc = launch_split<true, 128>(p, a, s); break;
+    case GS_DMA64: rc = launch_split<true, 64>(p, a, s); break;
+    case GS_DMA128_TM: rc = launch_split<true, 128, true>(p, a, s); break;
+    case GS_4WAVE128: rc = launch_split<false, 128>(p, a, s); break;
+    case GS_4WAVE64: rc = launch_split<false, 64>(p, a, s); break;
   }
-  if (tiles128 >= 384 && !half_empty) {
-    dim3 grid((a->N + BN - 1) / BN, (a->M + 127) / 128, (unsigned)nb);
-    ssr_gemm_log(a, grid.x, grid.y, grid.z, 1);
-    const int wide = ((long)grid.x * grid.y * grid.z > 0x7FFFFFFFL) ? (flags0 & 1) : flags0;      // the remap counts tiles in 32 bits
-    if (dma && tmf) {
-      if (elu) hipLaunchKernelGGL((gemm_split_dma_kernel<128, true, 0, true>), grid, dim3(512), dma_lds(128), s, *a, wide);
-      else hipLaunchKernelGGL((gemm_split_dma_kernel<128, false, 0, true>), grid, dim3(512), dma_lds(128), s, *a, wide);
-    } else if (dma) {
-      if (elu) hipLaunchKernelGGL((gemm_split_dma_kernel<128, true>), grid, dim3(512), dma_lds(128), s, *a, wide);
-      else hipLaunchKernelGGL((gemm_split_dma_kernel<128, false>), grid, dim3(512), dma_lds(128), s, *a, wide);
-    } else if (elu) hipLaunchKernelGGL((gemm_split_kernel<128, true>), grid, dim3(256), 0, s, *a);
-    else hipLaunchKernelGGL((gemm_split_kernel<128, false>), grid, dim3(256), 0, s, *a);
-  } else {
-    dim3 grid((a->N + BN - 1) / BN, (a->M + 63) / 64, (unsigned)nb);
-    ssr_gemm_log(a, grid.x, grid.y, grid.z, 1);
-    const int wide = ((long)grid.x * grid.y * grid.z > 0x7FFFFFFFL) ? (flags0 & 1) : flags0;
-    if (dma) {
-      if (elu) hipLaunchKernelGGL((gemm_split_dma_kernel<64, true>), grid, dim3(512), dma_lds(64), s, *a, wide);
-      else hipLaunchKernelGGL((gemm_split_dma_kernel<64, false>), grid, dim3(512), dma_lds(64), s, *a, wide);
-    } else if (elu) hipLaunchKernelGGL((gemm_split_kernel<64, true>), grid, dim3(256), 0, s, *a);
-    else hipLaunchKernelGGL((gemm_split_kernel<64, false>), grid, dim3(256), 0, s, *a);
-  }
+  if (rc) return rc;
   SSR_LAUNCH_CHECK();
   return 0;
 }

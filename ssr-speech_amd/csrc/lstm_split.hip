@@ -173,11 +173,8 @@ int ssrhip_lstm_split_steps(const ssrhip_lstm_args* a, int t_lo, int t_hi, hipSt
   const size_t he = ssrhip_lstm_split_hplane_elems(a->B, a->C);
   unsigned short* hs = reinterpret_cast<unsigned short*>(a->hsplit);
   if (t_lo == 0) hipLaunchKernelGGL(zero_u32_kernel, dim3(1024), dim3(256), 0, s, reinterpret_cast<unsigned*>(hs), (long)he);   // both buffers: h_0 = 0
-  static ssr_once_per_device once;
-  if (once.need()) {
-    SSR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&lstm_step_split_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, ls_lds()));
-    SSR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&lstm_step_split_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, ls_lds()));
-  }
+  SSR_RAISE_LDS(ls_lds(), lstm_step_split_kernel<2>);
+  SSR_RAISE_LDS(ls_lds(), lstm_step_split_kernel<4>);
   dim3 grid(a->C / LS_UN, (a->B + LS_BN - 1) / LS_BN);
   for (int t = t_lo; t < t_hi; ++t) {
     const unsigned short* hp = hs + (size_t)(t & 1) * he;

@@ -461,8 +461,7 @@ template <int CC, int BM>
 int launch_resblock_chain(const ssrhip_resblock_args* a, hipStream_t s) {
   constexpr int HH = CC / 2;
   const size_t smem = ((size_t)BM * (HH + 4) + (size_t)BM * 20 + (size_t)CC * 20) * sizeof(float);
-  static ssr_once_per_device once;
-  if (once.need()) SSR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&resblock_chain_kernel<CC, BM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+  SSR_RAISE_LDS(smem, resblock_chain_kernel<CC, BM>);
   hipLaunchKernelGGL((resblock_chain_kernel<CC, BM>), dim3((a->T + BM - 1) / BM, a->B), dim3(256), smem, s, *a);
   return 0;
 }
@@ -475,37 +474,28 @@ extern "C" int ssrhip_resblock(const ssrhip_resblock_args* a, ssrhip_stream_t st
   SSR_REQUIRE(a && a->x && a->y && a->w3 && a->b3 && a->w1 && a->b1, "ssrhip_resblock: null argument");
   SSR_REQUIRE(a->B > 0 && a->B <= 65535 && a->T > 0, "ssrhip_resblock: bad B / T");
   SSR_REQUIRE(!a->w3_split == !a->w1_split, "ssrhip_resblock: w3_split and w1_split come together");
-  if (a->w3_split && (a->C == 64 || a->C == 128)) {                // the caller prepared the bf16 planes: the DMA kernel (round 4)
-    static const bool split_off2 = (getenv("SSRHIP_GEMM_SPLIT") && getenv("SSRHIP_GEMM_SPLIT")[0] == '0') ||
-                                   (getenv("SSRHIP_RESBLOCK_DMA") && getenv("SSRHIP_RESBLOCK_DMA")[0] == '0');   // A/B knobs
-    if (!split_off2) return ssrhip_resblock_split_launch(a, (hipStream_t)stream);
+  const codec_knobs& k = ssr_codec_knobs();
+  hipStream_t s = (hipStream_t)stream;
+  // the caller prepared the bf16 planes: the DMA kernel (A/B knobs: SSRHIP_GEMM_SPLIT=0, the fp32 FMA chain everywhere; SSRHIP_RESBLOCK_DMA=0)
+  if (a->w3_split && (a->C == 64 || a->C == 128) && k.gemm_split && k.resblock_dma) return ssrhip_resblock_split_launch(a, s);
+  const bool big = k.reschain_big != 0;                   // tuning knob: the larger row block
+  int rc = 0;
+  if (a->C == 128 && k.gemm_split && !big) {              // the planes are split in the kernel
+    constexpr int SPLIT_SMEM = 128 * 68 * 4 + 3 * 128 * 24 * 2 + 3 * 128 * 24 * 2;     // Hs + As planes + Ws planes = 71,680 B
+    SSR_RAISE_LDS(SPLIT_SMEM, resblock_chain_split_kernel<128, 128>);
+    hipLaunchKernelGGL((resblock_chain_split_kernel<128, 128>), dim3((a->T + 127) / 128, a->B), dim3(256), SPLIT_SMEM, s, *a);
+  } else if (a->C == 128) rc = big ? launch_resblock_chain<128, 256>(a, s) : launch_resblock_chain<128, 128>(a, s);
+  else if (a->C == 256) rc = big ? launch_resblock_chain<256, 128>(a, s) : launch_resblock_chain<256, 64>(a, s);
+  else if (a->C == 512) rc = launch_resblock_chain<512, 64>(a, s);
+  else {
+    SSR_REQUIRE(a->C == 64, "ssrhip_resblock: fused for C in {64, 128, 256, 512} (C=%d)", a->C);
+    int gx = (256 + a->B - 1) / a->B;                     // ~1 eight-wave workgroup per CU in total; every wave then walks many tiles
+    const int need = (a->T + 32 * NWAVE - 1) / (32 * NWAVE);
+    if (gx > need) gx = need;
+    if (gx < 1) gx = 1;
+    hipLaunchKernelGGL(resblock64_kernel, dim3(gx, a->B), dim3(NWAVE * 64), 0, s, *a);
   }
-  if (a->C == 128 || a->C == 256 || a->C == 512) {
-    static const int big = getenv("SSRHIP_RESCHAIN_BIG") ? atoi(getenv("SSRHIP_RESCHAIN_BIG")) : 0;   // tuning knob: the larger row block
-    hipStream_t s = (hipStream_t)stream;
-    int rc;
-    static const bool split_off = getenv("SSRHIP_GEMM_SPLIT") && getenv("SSRHIP_GEMM_SPLIT")[0] == '0';   // A/B knob: the fp32 FMA chain everywhere
-    if (a->C == 128 && !split_off && !big) {
-      constexpr int SPLIT_SMEM = 128 * 68 * 4 + 3 * 128 * 24 * 2 + 3 * 128 * 24 * 2;     // Hs + As planes + Ws planes = 71,680 B
-      static ssr_once_per_device once;
-      if (once.need()) SSR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&resblock_chain_split_kernel<128, 128>), hipFuncAttributeMaxDynamicSharedMemorySize, SPLIT_SMEM));
-      hipLaunchKernelGGL((resblock_chain_split_kernel<128, 128>), dim3((a->T + 127) / 128, a->B), dim3(256), SPLIT_SMEM, s, *a);
-      SSR_LAUNCH_CHECK();
-      return 0;
-    }
-    if (a->C == 128) rc = big ? launch_resblock_chain<128, 256>(a, s) : launch_resblock_chain<128, 128>(a, s);
-    else if (a->C == 256) rc = big ? launch_resblock_chain<256, 128>(a, s) : launch_resblock_chain<256, 64>(a, s);
-    else rc = launch_resblock_chain<512, 64>(a, s);
-    if (rc) return rc;
-    SSR_LAUNCH_CHECK();
-    return 0;
-  }
-  SSR_REQUIRE(a->C == 64, "ssrhip_resblock: fused for C in {64, 128, 256, 512} (C=%d)", a->C);
-  int gx = (256 + a->B - 1) / a->B;                       // ~1 eight-wave workgroup per CU in total; every wave then walks many tiles
-  const int need = (a->T + 32 * NWAVE - 1) / (32 * NWAVE);
-  if (gx > need) gx = need;
-  if (gx < 1) gx = 1;
-  hipLaunchKernelGGL(resblock64_kernel, dim3(gx, a->B), dim3(NWAVE * 64), 0, (hipStream_t)stream, *a);
+  if (rc) return rc;
   SSR_LAUNCH_CHECK();
   return 0;
 }

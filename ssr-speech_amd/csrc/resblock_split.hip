@@ -438,19 +438,14 @@ int ssrhip_resblock_split_launch(const ssrhip_resblock_args* a, hipStream_t s) {
   SSR_REQUIRE(a->C == 64 || a->C == 128, "ssrhip_resblock (split planes): C=%d not in {64, 128}", a->C);
   SSR_REQUIRE((size_t)(a->T + 2) * a->C * 4 < 0x7FFFFFF0ull, "ssrhip_resblock (split planes): item too long");
   dim3 grid((a->T + RB_BM - 1) / RB_BM, a->B);
-  // ring of 2 (one tile ahead, three workgroups per CU) measured FASTER than a ring of 4 (three ahead, two workgroups per CU): 4.76 vs 5.46 ms
-  // at 32 clips, C = 128 (profiles/r04_microbench/resblock_pmc.log): a third workgroup hides more than the deeper prefetch does
-  static const int ring = getenv("SSRHIP_RESBLOCK_RING") ? atoi(getenv("SSRHIP_RESBLOCK_RING")) : 2;      // A/B knob
-  // the 16-byte epilogue (accumulator blocks turned through LDS) measured 1-3 % SLOWER here than the dword form (3.29 vs 3.21 ms at C = 128,
-  // 2.33 vs 2.29 at C = 64, 32 clips, alternating runs, bit-identical outputs: profiles/r04_microbench/resblock_lab_ab.log) — unlike in the GEMM,
-  // whose default it is; kept behind the same knob for A/B runs
-  static const int wide = getenv("SSRHIP_EPILOGUE_WIDE") ? getenv("SSRHIP_EPILOGUE_WIDE")[0] != '0' : 0;
-  if (ring == 2) {
+  // Defaults: the ring of 2 (one tile ahead, three workgroups per CU; any other SSRHIP_RESBLOCK_RING: three ahead, two per CU) and the dword
+  // epilogue. Both measured faster here than their A/B alternatives (profiles/r04_microbench/resblock_pmc.log, resblock_lab_ab.log)
+  const int wide = ssr_codec_knobs().resblock_wide;
+  if (ssr_codec_knobs().resblock_ring == 2) {
     if (a->C == 128) hipLaunchKernelGGL((resblock_split_dma_kernel<128, 2>), grid, dim3(RB_TH), rb_lds(128, 2), s, *a, wide);
     else hipLaunchKernelGGL((resblock_split_dma_kernel<64, 2>), grid, dim3(RB_TH), rb_lds(64, 2), s, *a, wide);
   } else if (a->C == 128) {
-    static ssr_once_per_device once;
-    if (once.need()) SSR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&resblock_split_dma_kernel<128, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, rb_lds(128, 4)));
+    SSR_RAISE_LDS(rb_lds(128, 4), resblock_split_dma_kernel<128, 4>);      // 74,496 B: the only form above the 64 KB a kernel gets unasked
     hipLaunchKernelGGL((resblock_split_dma_kernel<128, 4>), grid, dim3(RB_TH), rb_lds(128, 4), s, *a, wide);
   } else {
     hipLaunchKernelGGL((resblock_split_dma_kernel<64, 4>), grid, dim3(RB_TH), rb_lds(64, 4), s, *a, wide);

@@ -14,10 +14,12 @@ def _read(*parts):
 def test_every_environment_switch_is_listed_in_integration_md():
     names = set()
     for fn in glob.glob(os.path.join(ROOT, "ssr-speech_amd", "csrc", "*.hip")) + glob.glob(os.path.join(ROOT, "ssr-speech_amd", "csrc", "*.h")):
-        names |= set(re.findall(r'getenv(?:_flag)?\("(SSRHIP_[A-Z0-9_]+)"', open(fn).read()))
+        names |= set(re.findall(r'getenv(?:_[a-z]+)?\("(SSRHIP_[A-Z0-9_]+)"', open(fn).read()))      # getenv and csrc/common.h's getenv_on / _set / _int
     for fn in glob.glob(os.path.join(ROOT, "ssr-speech_amd", "**", "*.py"), recursive=True):
         names |= set(re.findall(r'environ(?:\.get\(|\[)"(SSRHIP_[A-Z0-9_]+)"', open(fn).read()))
-    assert len(names) >= 15, sorted(names)
+    # ... and codec/wmencodec.py's _ENV_KNOBS table: any "SSRHIP_X" literal of that file, however the table is laid out
+    names |= set(re.findall(r'"(SSRHIP_[A-Z0-9_]+)"', _read("ssr-speech_amd", "codec", "wmencodec.py")))
+    assert len(names) >= 40, sorted(names)      # 46 today; was 15 when only some were found
     doc = _read("INTEGRATION.md")
     missing = sorted(n for n in names if n not in doc)
     assert not missing, f"environment switches read by the code but not documented in INTEGRATION.md §4: {missing}"
