@@ -300,6 +300,12 @@ int ssrhip_pad_ragged(float* buf, const int32_t* lens, int32_t B, int32_t T, int
                       int32_t reflect, ssrhip_stream_t stream);
 /* one LSTM layer over T steps (torch.nn.LSTM semantics, gates i,f,g,o; modules/lstm.py:10-25):
  * gin[b][t][4C] = x_t W_ih^T + b_ih + b_hh (precomputed by ssrhip_gemm); h,c start at 0.
+ * One call runs the steps [t_begin, t_end) (t_end <= 0: up to T). A call with t_begin == 0 starts from h = c = 0 whatever hbuf / cbuf
+ * hold; a call with t_begin > 0 CONTINUES from the hbuf / cbuf (and hsplit) the call that ended at t_begin left there — h_t lives in
+ * half (t & 1) of hbuf by the ABSOLUTE step, so the buffers, B, C and the path must be the same from call to call and nothing else may
+ * write them in between. Any split of [0, n) into consecutive calls writes the bits of the one call over [0, n). T is the CAPACITY of
+ * gin and out in steps (their row count per item), not the number of steps run: a caller that does not know the final length yet
+ * (codec/wmencodec.py DecodeStream) sizes them for the longest case and advances as inputs arrive.
  * out[b][t][C] = h_t (+ skip[b][t][C] when skip != NULL).  cbuf: [B][C]; hbuf: [2][ceil(B/16)*16][C] floats (row-major
  * [B][C] on the small-batch path B <= 4 && C in {256,512,1024,2048}; otherwise kept in the SSRHIP_TILED layout per 16-item
  * tile, which needs C <= 1024); gates: unused (may be NULL). C % 16 == 0. */

@@ -68,7 +68,9 @@ def _device_mallocs(device) -> int:
 class TM:
     """Time-major activation buffer with halo rows."""
 
-    def __init__(self, B: int, T: int, Cc: int, padL: int, padR: int, device, lens: "Optional[Ragged]" = None):
+    def __init__(self, B: int, T: int, Cc: int, padL: int, padR: int, device, lens: "Optional[Ragged]" = None, data=None, keep_halo=False):
+        """`data`: caller-owned memory [B][padL + T + padR][C] to use instead of a fresh allocation (`DecodeStream`); `keep_halo`: its halo
+        rows already hold what the consumer must read."""
         self.B, self.T, self.C, self.padL, self.padR = B, T, Cc, padL, padR
         self.lens = lens                   # ragged batch: per-item valid rows (None = every item has T rows)
         self.elu = False                   # True: the producer stored ELU(y) (its only consumers read it through ELU: they skip theirs)
@@ -76,7 +78,10 @@ class TM:
         # every producer writes the whole interior; only the halo rows need a defined value before the consumer reads them
         # (zero for constant / structural padding; reflect padding overwrites them). A torch.zeros of the whole buffer was 24
         # full-size memsets per encode+decode (6.7 ms at 32 clips x 30 s).
-        self.data = _empty(B, self.rows, Cc, dtype=torch.float32, device=device)
+        self.data = _empty(B, self.rows, Cc, dtype=torch.float32, device=device) if data is None else data
+        assert tuple(self.data.shape) == (B, self.rows, Cc), (tuple(self.data.shape), B, self.rows, Cc)
+        if keep_halo:
+            return
         if padL:
             self.data[:, :padL].zero_()
         if padR:
@@ -233,6 +238,44 @@ class _SeaNet:
         return [n for n in self.nodes if n[0] >= lo and (hi is None or n[0] < hi)]
 
 
+# ----------------------------------------------------------------------------- streamed decode: the window plan (host arithmetic only)
+def _conv_pads(k: int, s: int) -> Tuple[int, int]:
+    """(left, right) padding of a non-causal StreamableConv1d (conv.py:185-201), without the length-dependent extra padding (0 at stride 1)"""
+    pt = k - s
+    return pt - pt // 2, pt // 2
+
+
+def stream_lookahead(cfg: CodecConfig) -> int:
+    """Frames of look-ahead the decoder's first convolution needs before its output at a frame is final."""
+    return _conv_pads(cfg.kernel_size, 1)[1]
+
+
+def stream_margins(cfg: CodecConfig) -> Tuple[int, int]:
+    """(left, right) margin, in frames, a window of the decoder's part BEHIND the LSTM (transposed convolutions, residual blocks, last
+    convolution) needs so that every sample of its core is computed from true neighbours only: the chain's receptive field, walked from
+    the output back to the frames. (L, R) = samples of context the outputs of a layer need on either side; a stride-1 convolution adds
+    its paddings; a transposed convolution (kernel 2s, `trim_l` raw samples cut in front) maps output o to the inputs
+    floor((o + trim_l) / s) - 1 and floor((o + trim_l) / s), so a core that starts / ends on a frame boundary needs
+    1 + ceil((L - trim_l) / s) inputs in front and 1 + floor((R + trim_l - 1) / s) behind."""
+    L, R = _conv_pads(cfg.last_kernel_size, 1)
+    for s in reversed(cfg.ratios):
+        for _ in range(cfg.n_residual_layers):
+            for k in (1, cfg.residual_kernel_size):                  # the block's 1x1 and its k-tap convolution (seanet.py:16-60)
+                pl, pr = _conv_pads(k, 1)
+                L, R = L + pl, R + pr
+        pt = 2 * s - s
+        trim_l = pt - pt // 2
+        L, R = 1 + -((trim_l - L) // s), 1 + (R + trim_l - 1) // s
+    return max(L, 0), max(R, 0)
+
+
+def stream_window(c0: int, c1: int, n: int, margins: Tuple[int, int]) -> Tuple[int, int]:
+    """The frames [lo, hi) a window with the core [c0, c1) reads when frames [0, n) exist: the core plus the margins, cut at the ends —
+    an end at 0, or at n once n is the utterance's length, is a true edge that gets the layers' own padding and no margin."""
+    assert 0 <= c0 < c1 <= n, (c0, c1, n)
+    return max(0, c0 - margins[0]), min(n, c1 + margins[1])
+
+
 # the three truth rules of the switches below (kept apart: "" counts as on for the first, as off for the second)
 _not0 = lambda v: v != "0"                                             # noqa: E731
 _on = lambda v: v not in ("", "0")                                     # noqa: E731
@@ -265,6 +308,8 @@ class WMEncodecModel:
         self.lib = _lib.lib()
         self.fuse_resblock = True            # tests switch it off to compare with the two-GEMM path
         self.force_few_out = False           # tests: take the few-output-channel kernel also for short inputs
+        self._stream_few_out = False         # set while a `DecodeStream` window runs whose whole utterance takes that kernel
+        self._tm_pool = None                 # set while a `DecodeStream` window runs: where `_alloc_for` takes its buffers from
         for attr, switch, unset, parse in _ENV_KNOBS:
             setattr(self, attr, parse(os.environ.get(switch, unset)))
         self._plane_cache = {}
@@ -274,6 +319,7 @@ class WMEncodecModel:
         self.passes_repeated = 0             # passes run again because the driver was asked for memory while they were in flight
         self.mallocs_in_flight = 0           # hipMallocs that happened during a call although it had been sized (tests assert 0)
         self.sizing_passes = 0
+        self.n_launches = 0                  # library entry points called so far, dry passes included (tools/stream_latency.py)
         sd = {k: v.detach().to(torch.float32).cpu() for k, v in state_dict.items()}
         dev = self.device
         self.encoder = _SeaNet(sd, "encoder.", cfg, False, dev)
@@ -386,6 +432,7 @@ class WMEncodecModel:
     def _call(self, name: str, *args):
         """One library launch on the current stream. The entry point is looked up at call time: `_sized` swaps `self.lib` for its dry pass
         and tests wrap it."""
+        self.n_launches += 1
         _lib.check(getattr(self.lib, name)(*args, _lib.stream_ptr()), name)
 
     def _planes(self, W: torch.Tensor) -> Optional[torch.Tensor]:
@@ -475,6 +522,8 @@ class WMEncodecModel:
 
     def _alloc_for(self, B, T, Cc, nxt, lens: Optional[Ragged] = None) -> TM:
         pl, pr, _ = self._need(nxt, T)
+        if self._tm_pool is not None:                # a `DecodeStream` window: its buffers exist since the stream was created
+            return self._tm_pool.take(B, T, Cc, pl, pr, self.device)
         return TM(B, T, Cc, pl, pr, self.device, lens)
 
     # ------------------------------------------------------------------ nodes
@@ -484,6 +533,8 @@ class WMEncodecModel:
         if x.elu and not wants_elu:
             raise AssertionError("a layer that reads its input without ELU was given a tensor stored through ELU")
         return _lib.ACT_ELU if (wants_elu and not x.elu) else 0
+
+    FEW_OUT_MIN_T = 4096     # output rows from which the 1-channel last layer runs as `ssrhip_conv_few_out`
 
     def _conv(self, c: _Conv, x: TM, nxt, R: Optional[TM] = None, post_elu: bool = False) -> TM:
         """`post_elu`: store ELU(result) (the caller knows that every consumer reads this output through ELU; `self.elu_on_store`)."""
@@ -495,7 +546,7 @@ class WMEncodecModel:
             assert c.act_in == 0 and not post_elu
             self._call("ssrhip_conv_cin1", x.base, c.Wraw.data_ptr(), c.b.data_ptr(), out.interior, B, T_out, c.k, c.s, c.Cout,
                        x.bstride, out.bstride)
-        elif c.Cout <= 4 and c.s == 1 and R is None and c.Cin % 8 == 0 and (T_out >= 4096 or self.force_few_out) and not post_elu:
+        elif c.Cout <= 4 and c.s == 1 and R is None and c.Cin % 8 == 0 and (T_out >= self.FEW_OUT_MIN_T or self.force_few_out or self._stream_few_out) and not post_elu:
             # the 1-channel output layer at the sample rate: a read-bound dot-product kernel instead of a GEMM tile with 1 useful column
             self._call("ssrhip_conv_few_out", x.base, c.W.data_ptr(), c.b.data_ptr(), out.interior, B, T_out, c.k, c.Cin, c.Cout,
                        act_in, x.bstride, out.bstride)
@@ -542,6 +593,36 @@ class WMEncodecModel:
 
     LSTM_CHUNK = 64          # time steps per pipeline stage of the two stacked LSTM layers
 
+    def _lstm_use_split(self, L: _Lstm, B: int) -> bool:
+        return bool(self.lstm_split and B >= self.lstm_split_min_b and not (B <= 4 and L.C in (256, 512, 1024, 2048)))
+
+    def _lstm_in_gemm(self, L: _Lstm, l: int, src_ptr: int, src_bs: int, gin: torch.Tensor, B: int, T: int, t0: int, t1: int):
+        """gin[:, t0:t1] = in[:, t0:t1] W_ih^T + b of layer l; `T` = rows per item of `gin`."""
+        Cc = L.C
+        wih, _, bias = L.layers[l]
+        self._gemm(src_ptr + 4 * t0 * Cc, wih, bias, gin.data_ptr() + 4 * t0 * 4 * Cc, t1 - t0, 4 * Cc, Cc, Cc, 4 * Cc,
+                   batch=B, sA=src_bs, sC=T * 4 * Cc)
+
+    def _lstm_steps(self, L: _Lstm, l: int, gin, hbuf, cbuf, hsplit, out_ptr: int, out_bs: int, skip_ptr: int, skip_bs: int,
+                    B: int, T: int, t0: int, t1: int, out_elu: bool):
+        """The time steps [t0, t1) of layer l (`ssrhip_lstm_layer`; t0 > 0 continues from the state the call that ended at t0 left in
+        `hbuf` / `cbuf`); `T` = rows per item of `gin` and of the output."""
+        Cc = L.C
+        a = _lib.LstmArgs()
+        small_b = B <= 4 and Cc in (256, 512, 1024, 2048)            # ssrhip_lstm_layer's path choice
+        use_packed = (not small_b) and L.packed[l] is not None and self.lstm_packed
+        a.gin, a.w_hh, a.out = gin.data_ptr(), (L.packed[l] if use_packed else L.layers[l][1]).data_ptr(), out_ptr
+        a.w_packed = int(use_packed)
+        if hsplit is not None:
+            a.w_split, a.hsplit = L.split[l].data_ptr(), hsplit.data_ptr()
+        a.skip = skip_ptr                                             # y = lstm(x) + x (lstm.py:21-23) on the last layer
+        a.hbuf, a.cbuf, a.gates = hbuf.data_ptr(), cbuf.data_ptr(), 0
+        a.B, a.T, a.C = B, T, Cc
+        a.gin_bstride, a.out_bstride, a.skip_bstride = T * 4 * Cc, out_bs, skip_bs
+        a.t_begin, a.t_end = t0, t1
+        a.out_act = _lib.ACT_ELU if out_elu else 0
+        self._call("ssrhip_lstm_layer", C.byref(a))
+
     def _lstm(self, L: _Lstm, x: TM, nxt, post_elu: bool = False) -> TM:
         """2-layer LSTM + skip (lstm.py:10-25). Each layer: input GEMM over time (MFMA) + one launch per time step. With two
         layers the recurrences are software-pipelined over chunks of LSTM_CHUNK steps on two streams: layer 2 works on chunk
@@ -557,31 +638,17 @@ class WMEncodecModel:
         cbufs = [_empty(B, Cc, dtype=torch.float32, device=dev) for _ in range(nl)]
         outs = [self._alloc_for(B, T, Cc, nxt, x.lens) if l == nl - 1 else TM(B, T, Cc, 0, 0, dev) for l in range(nl)]
         # h of the split-operand path: two buffers of bf16 planes in fragment order (zeroed by the library at t = 0)
-        use_split = self.lstm_split and B >= self.lstm_split_min_b and not (B <= 4 and Cc in (256, 512, 1024, 2048))
+        use_split = self._lstm_use_split(L, B)
         hsplits = [_empty(2 * ((B + 63) // 64) * 64 * Cc * 3, dtype=torch.int16, device=dev) if (use_split and L.split[l] is not None) else None
                    for l in range(nl)]
 
         def in_gemm(l, t0, t1):                                        # gin_l[:, t0:t1] = in_l[:, t0:t1] W_ih^T + b
             src_ptr, src_bs = (x.interior, x.bstride) if l == 0 else (outs[l - 1].interior, outs[l - 1].bstride)
-            wih, _, bias = L.layers[l]
-            self._gemm(src_ptr + 4 * t0 * Cc, wih, bias, gins[l].data_ptr() + 4 * t0 * 4 * Cc, t1 - t0, 4 * Cc, Cc, Cc, 4 * Cc,
-                       batch=B, sA=src_bs, sC=T * 4 * Cc)
+            self._lstm_in_gemm(L, l, src_ptr, src_bs, gins[l], B, T, t0, t1)
 
         def steps(l, t0, t1):
-            a = _lib.LstmArgs()
-            small_b = B <= 4 and Cc in (256, 512, 1024, 2048)            # ssrhip_lstm_layer's path choice
-            use_packed = (not small_b) and L.packed[l] is not None and self.lstm_packed
-            a.gin, a.w_hh, a.out = gins[l].data_ptr(), (L.packed[l] if use_packed else L.layers[l][1]).data_ptr(), outs[l].interior
-            a.w_packed = int(use_packed)
-            if use_split and L.split[l] is not None:
-                a.w_split, a.hsplit = L.split[l].data_ptr(), hsplits[l].data_ptr()
-            a.skip = x.interior if l == nl - 1 else 0                   # y = lstm(x) + x (lstm.py:21-23)
-            a.hbuf, a.cbuf, a.gates = hbufs[l].data_ptr(), cbufs[l].data_ptr(), 0
-            a.B, a.T, a.C = B, T, Cc
-            a.gin_bstride, a.out_bstride, a.skip_bstride = T * 4 * Cc, outs[l].bstride, x.bstride
-            a.t_begin, a.t_end = t0, t1
-            a.out_act = _lib.ACT_ELU if (post_elu and l == nl - 1) else 0
-            self._call("ssrhip_lstm_layer", C.byref(a))
+            self._lstm_steps(L, l, gins[l], hbufs[l], cbufs[l], hsplits[l], outs[l].interior, outs[l].bstride,
+                             (x.interior if l == nl - 1 else 0), x.bstride, B, T, t0, t1, post_elu and l == nl - 1)
 
         if nl == 2 and T > self.LSTM_CHUNK and B >= self.lstm_pipe_min_b:
             main = torch.cuda.current_stream(dev)
@@ -737,6 +804,14 @@ class WMEncodecModel:
             return (self._channel_major(self._run(self.decoder.nodes, z)),)
 
         return self._join(self._in_lanes(c32.shape[0], lambda lo, hi: self._sized("decode", hi - lo, int(c32.shape[-1]), lambda: body(lo, hi))), 0)
+
+    # ------------------------------------------------------------------ streamed decode
+    def decode_stream(self, max_frames: int, max_window: int = 16) -> "DecodeStream":
+        """`decode` of ONE utterance in pieces, while its codes are still being generated: `push(codes [1, K, n])` returns the samples
+        that have become final, `finish()` the rest; their concatenation is bit-identical to `decode` of all the codes. Every buffer is
+        allocated here, for up to `max_frames` frames (create the stream before the decode engine's first launch); `max_window` = frames
+        of one pass over the layers behind the LSTM."""
+        return DecodeStream(self, int(max_frames), int(max_window))
 
     # ------------------------------------------------------------------ ragged batches (items of different lengths in one pass)
     # cost model of one dense pass over a bucket, in microseconds per frame of its longest item: every frame is one LSTM time step
@@ -901,3 +976,214 @@ class WMEncodecModel:
             return (torch.argmax(mk.squeeze(-1), dim=-1),)
 
         return self._join(self._in_lanes(x.shape[0], lambda lo, hi: self._sized("detect", hi - lo, int(x.shape[-1]), lambda: body(lo, hi))), 0)
+
+
+class _WindowPool:
+    """The activation buffers of a `DecodeStream` window: allocated once, by a dry pass over the largest window, and handed out again in
+    the same order for every later window (`WMEncodecModel._alloc_for`)."""
+
+    def __init__(self):
+        self.bufs: List[torch.Tensor] = []
+        self.at, self.frozen = 0, False
+
+    def take(self, B: int, T: int, Cc: int, padL: int, padR: int, device) -> TM:
+        n = B * (padL + T + padR) * Cc
+        if not self.frozen:
+            self.bufs.append(_empty(n, dtype=torch.float32, device=device))
+        if self.at >= len(self.bufs) or self.bufs[self.at].numel() < n:
+            raise RuntimeError("DecodeStream: a window asks for a buffer the stream did not allocate when it was created")
+        flat = self.bufs[self.at]
+        self.at += 1
+        return TM(B, T, Cc, padL, padR, device, data=flat[:n].view(B, padL + T + padR, Cc))
+
+
+class DecodeStream:
+    """`WMEncodecModel.decode_stream`: the decoder of one utterance (B = 1), advanced as its frames arrive.
+
+    Stage 1 — dequantiser, first convolution, LSTM + skip — runs once over every frame: the convolution over the frames whose
+    look-ahead (`stream_lookahead`) has arrived, the LSTM behind it as `ssrhip_lstm_layer` calls that continue (`t_begin` > 0) on the
+    stream's own `gin` / `hbuf` / `cbuf`. Stage 2 — everything behind the LSTM — runs over windows of stage-1 output with the margins
+    of `stream_margins` on either side, whose samples are dropped; an end of the utterance is a true edge (the layers' own padding, no
+    margin). Frames nearer to the current end than look-ahead + margin wait for more frames or for `finish()`. Every launch is the one
+    `decode` issues for the same layer, over fewer rows, on the caller's stream; where a launcher chooses by length (`_conv`'s
+    few-output kernel from `FEW_OUT_MIN_T` rows on) the stream waits until the whole utterance's choice is known and takes it."""
+
+    def __init__(self, model: WMEncodecModel, max_frames: int, max_window: int):
+        cfg, dev = model.cfg, model.device
+        if max_frames < 1 or max_window < 1:
+            raise ValueError("decode_stream needs max_frames >= 1 and max_window >= 1")
+        nodes = model.decoder.nodes
+        self.m, self.cap, self.max_window = model, max_frames, max_window
+        self.hop = int(math.prod(cfg.ratios))
+        self.conv0: _Conv = nodes[0][2]
+        self.lstm: Optional[_Lstm] = nodes[1][2] if nodes[1][1] == "lstm" else None
+        self.tail = nodes[2:] if self.lstm is not None else nodes[1:]
+        c0 = self.conv0
+        if not (nodes[0][1] == "conv" and c0.s == 1 and c0.Cin > 1 and c0.Cout > 4 and self.tail and self.tail[0][1] == "convtr"):
+            raise NotImplementedError("decode_stream: the decoder does not start with a stride-1 convolution into a transposed convolution")
+        self.pl0, self.pr0 = c0.pads(max_frames)                      # stride 1: no length-dependent extra padding
+        assert (self.pl0, self.pr0) == (c0.pl, c0.pr)
+        self.margins = stream_margins(cfg)
+        self.reflect = cfg.pad_mode == "reflect"
+        last = nodes[-1][2]
+        self._few_eligible = last.Cout <= 4 and last.s == 1 and last.Cin % 8 == 0       # `_conv`'s conditions on the layer itself
+        f32 = dict(dtype=torch.float32, device=dev)
+        K, D, C0 = cfg.n_q, cfg.dimension, c0.Cout
+        # stage 1 (zero-filled: halo rows, and rows behind the last frame, must read as zeros)
+        self.codes = torch.zeros(K * max_frames, dtype=torch.int32, device=dev)
+        self.lohi = torch.zeros(2, dtype=torch.int32, device=dev)
+        self.z = TM(1, max_frames, D, self.pl0, self.pr0, dev, data=torch.zeros(1, self.pl0 + max_frames + self.pr0, D, **f32))
+        self.s1 = TM(1, max_frames, C0, 1, 1, dev, data=torch.zeros(1, max_frames + 2, C0, **f32))      # what the first convtr reads
+        self.s1.elu = bool(model.elu_on_store and self.lstm is not None)
+        if self.lstm is not None:
+            L, nl = self.lstm, len(self.lstm.layers)
+            assert L.C == C0
+            self.y0 = torch.zeros(1, max_frames, C0, **f32)
+            self.gins = [torch.zeros(1, max_frames, 4 * C0, **f32) for _ in range(nl)]
+            self.hbufs = [torch.zeros(2, 16, C0, **f32) for _ in range(nl)]
+            self.cbufs = [torch.zeros(1, C0, **f32) for _ in range(nl)]
+            self.mids = [torch.zeros(1, max_frames, C0, **f32) for _ in range(nl - 1)]
+            split = model._lstm_use_split(L, 1)
+            self.hsplits = [torch.zeros(2 * 64 * C0 * 3, dtype=torch.int16, device=dev) if (split and L.split[l] is not None) else None
+                            for l in range(nl)]
+        self.wav = torch.zeros(1, 1, max_frames * self.hop, **f32)
+        self.n_pushed = 0          # frames whose codes have arrived
+        self.n1 = 0                # frames whose stage-1 output is final
+        self.n2 = 0                # frames whose samples have been written (and, from `emit_from` on, returned)
+        self.emit_from: Optional[int] = None
+        self.finished = False
+        self.windows = 0           # stage-2 passes so far
+        # stage 2: the buffers of the largest window, allocated by a dry pass (no launch) — an interior window of max_window frames
+        self.pool = _WindowPool()
+        real, model.lib = model.lib, _NoLaunch()
+        try:
+            n = min(max_frames, max_window + self.margins[0] + self.margins[1])
+            self._tail_pass(0, n)
+        finally:
+            model.lib = real
+        self.pool.frozen = True
+        torch.cuda.current_stream(dev).synchronize()                  # the fills above are done before anything else is enqueued
+
+    def _tail_pass(self, lo: int, hi: int) -> TM:
+        """The layers behind the LSTM over the stage-1 frames [lo, hi), read in place (the rows next to the window are its halo: a true
+        neighbour, or the zero row an end of the utterance needs)."""
+        m, s1 = self.m, self.s1
+        x = TM(1, hi - lo, s1.C, 1, 1, m.device, data=s1.data[:, lo: hi + 2], keep_halo=True)
+        x.elu = s1.elu
+        self.pool.at = 0
+        m._tm_pool = self.pool
+        try:
+            return m._run(self.tail, x)
+        finally:
+            m._tm_pool = None
+
+    def _stage1(self, final: bool):
+        m, z, c0 = self.m, self.z, self.conv0
+        n, D = self.n_pushed, z.C
+        ready = n if final else n - self.pr0
+        if self.reflect and not final and n <= max(self.pl0, self.pr0):
+            ready = 0                                                 # reflect padding of so short an input depends on its length
+        a, b = self.n1, max(ready, self.n1)
+        if b == a:
+            return
+        if self.reflect:                                             # (constant padding: the zero rows the buffer was created with)
+            if final:
+                m._call("ssrhip_pad_reflect", z.base, 1, n, self.pl0, self.pr0, D, z.bstride)
+            elif a == 0:
+                m._call("ssrhip_pad_reflect", z.base, 1, n, self.pl0, 0, D, z.bstride)
+        C0 = c0.Cout
+        dst = self.y0.data_ptr() if self.lstm is not None else self.s1.interior
+        # `_conv`'s GEMM over the rows [a, b): row t of the im2col view starts at padded row t
+        m._gemm(z.base + 4 * a * D, c0.W, c0.b, dst + 4 * a * C0, b - a, C0, c0.k * c0.Cin, c0.s * c0.Cin, C0, act_in=m._act_in(bool(c0.act_in), z),
+                batch=1, sA=z.bstride, sC=self.cap * C0)
+        if self.lstm is not None:
+            L, nl, T = self.lstm, len(self.lstm.layers), self.cap
+            for l in range(nl):
+                src = self.y0 if l == 0 else self.mids[l - 1]
+                m._lstm_in_gemm(L, l, src.data_ptr(), T * C0, self.gins[l], 1, T, a, b)
+                out_ptr = self.s1.interior if l == nl - 1 else self.mids[l].data_ptr()
+                m._lstm_steps(L, l, self.gins[l], self.hbufs[l], self.cbufs[l], self.hsplits[l], out_ptr, T * C0,
+                              (self.y0.data_ptr() if l == nl - 1 else 0), T * C0, 1, T, a, b, self.s1.elu and l == nl - 1)
+        self.n1 = b
+
+    def _few_out(self, final: bool) -> Optional[bool]:
+        """Does `decode` of the whole utterance run its last layer as the few-output kernel? None: not known yet."""
+        m = self.m
+        if not self._few_eligible or m.force_few_out:
+            return False                                              # (forced: `_conv` takes it whatever this says)
+        if self.n_pushed * self.hop >= m.FEW_OUT_MIN_T:
+            return True
+        return False if final else None
+
+    def _stage2(self, final: bool):
+        if self.emit_from is None:
+            return
+        few = self._few_out(final)
+        if few is None:
+            return
+        limit = self.n_pushed if final else self.n1 - self.margins[1]
+        m = self.m
+        while self.n2 < limit:
+            c0, c1 = self.n2, min(self.n2 + self.max_window, limit)
+            lo, hi = stream_window(c0, c1, self.n1, self.margins)
+            m._stream_few_out = few
+            try:
+                y = self._tail_pass(lo, hi)
+            finally:
+                m._stream_few_out = False
+            assert y.C == 1 and y.padL == 0 and y.T == (hi - lo) * self.hop
+            self.wav[0, 0, c0 * self.hop: c1 * self.hop].copy_(y.data.view(-1)[(c0 - lo) * self.hop: (c1 - lo) * self.hop])
+            self.windows += 1
+            self.n2 = c1
+
+    def _out(self, a: int) -> torch.Tensor:
+        return self.wav[:, :, a * self.hop: self.n2 * self.hop]
+
+    @torch.no_grad()
+    def push(self, codes: torch.Tensor, emit: bool = True) -> torch.Tensor:
+        """codes [1, K, n] (any device; n may be 0): the next n frames. Returns the samples that became final, [1, 1, m * hop] (a view
+        of the stream's output buffer; m may be 0). `emit=False` (only in front of every emitted frame): the frames run through stage
+        1 — the LSTM state has to pass through them — and are never returned."""
+        if self.finished:
+            raise RuntimeError("DecodeStream.push after finish()")
+        cfg = self.m.cfg
+        assert codes.dim() == 3 and codes.shape[0] == 1 and codes.shape[1] == cfg.n_q, tuple(codes.shape)
+        n = int(codes.shape[-1])
+        if self.n_pushed + n > self.cap:
+            raise ValueError(f"DecodeStream: {self.n_pushed} + {n} frames exceed max_frames = {self.cap}")
+        if not emit and self.emit_from is not None:
+            raise ValueError("DecodeStream: emit=False frames must come before every emitted frame")
+        if emit and self.emit_from is None:
+            self.emit_from = self.n2 = self.n_pushed
+        a = self.n2
+        if n == 0:
+            return self._out(a)
+        c32 = self.codes[: cfg.n_q * n].view(1, cfg.n_q, n)
+        c32.copy_(codes)
+        # the range check `decode` makes (core_vq.py:175 raises in the reference), before the ids index the codebooks
+        torch.amin(c32, dim=(0, 1, 2), out=self.lohi[0])
+        torch.amax(c32, dim=(0, 1, 2), out=self.lohi[1])
+        lo, hi = self.lohi.tolist()
+        if hi >= cfg.bins or lo < 0:
+            raise IndexError("index out of range in self")
+        z = self.z
+        self.m._call("ssrhip_rvq_decode", c32.data_ptr(), self.m.codebooks.data_ptr(), z.interior + 4 * self.n_pushed * z.C, 1, n, z.C, cfg.n_q,
+                   cfg.bins, z.bstride)
+        self.n_pushed += n
+        self._stage1(False)
+        self._stage2(False)
+        return self._out(a)
+
+    @torch.no_grad()
+    def finish(self) -> torch.Tensor:
+        """The utterance ends here: its right edge gets the layers' own padding, and the samples still held back are returned."""
+        if self.finished:
+            raise RuntimeError("DecodeStream.finish called twice")
+        self.finished = True
+        if self.emit_from is None:
+            self.emit_from = self.n2 = self.n_pushed
+        a = self.n2
+        if self.n_pushed:
+            self._stage1(True)
+            self._stage2(True)
+        return self._out(a)

@@ -170,6 +170,14 @@ class AudioTokenizer:
     def decode(self, frames: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
         return self.codec.decode(frames, scale)
 
+    def decode_stream(self, max_frames: int, max_window: int = 16, use_watermark: bool = False):
+        """`decode` in pieces while the frames are still being generated (`WMEncodecModel.decode_stream`): `push(frames [1, K, n],
+        emit=True)` / `finish()` return waveform chunks whose concatenation is bit-identical to `decode` of all the frames. The
+        watermarked decode is not streamed: `wmdecode` runs its skip encoder over the kept-audio track of the WHOLE utterance."""
+        if use_watermark:
+            raise ValueError("decode_stream: the watermarked decode (use_watermark=True) is not streamed; use wmdecode on the finished frames")
+        return self.codec.decode_stream(max_frames, max_window)
+
     def wmdecode(self, frames: torch.Tensor, marks: torch.Tensor, wav: torch.Tensor, scale: torch.Tensor):
         # the reference discards the detector output here (tokenizer.py:133): skip computing it
         out, _ = self.codec.wmdecode(frames.to(self.device), marks.to(self.device), wav.to(self.device), scale, with_mark=False)

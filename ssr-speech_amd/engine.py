@@ -809,17 +809,30 @@ class DecodeEngine:
         arr = (_lib.SamplerState * self.n_utt).from_buffer_copy(raw)
         return list(arr)
 
-    def tokens(self, u: int, n: int) -> np.ndarray:
-        """The first n generated steps of slot u as int64 [n, K] — after the pair-launch check (never read `generated` directly)."""
-        out = self.generated[u, :n].cpu().numpy().astype(np.int64)
+    def tokens(self, u: int, n: int, start: int = 0) -> np.ndarray:
+        """The generated steps [start, n) of slot u as int64 [n - start, K] — after the pair-launch check (never read `generated`
+        directly)."""
+        out = self.generated[u, start:n].cpu().numpy().astype(np.int64)
         self.check_pairs()
         return out
 
     def run_to_completion(self, chunk: int = 16, use_graph: bool = True, max_total: Optional[int] = None,
-                          feed: Optional[TorchCpuNoiseFeed] = None):
+                          feed: Optional[TorchCpuNoiseFeed] = None, on_chunk=None):
         """Decode in chunks of `chunk` steps until every utterance reports done (the flags are polled once per chunk).
         With `feed`, the host draws the NEXT chunk's sampling noise into pinned memory and uploads it on a copy stream while
-        the GPU runs the current chunk (a 16-step chunk is ~14 ms of GPU time at 830M; its draws ~3 ms of host time)."""
+        the GPU runs the current chunk (a 16-step chunk is ~14 ms of GPU time at 830M; its draws ~3 ms of host time).
+        `on_chunk(states)` is called after every poll with the states read there (`iter_chunks` is the same loop as a generator)."""
+        states = None
+        for states in self.iter_chunks(chunk, use_graph, max_total, feed):
+            if on_chunk is not None:
+                on_chunk(states)
+        return states
+
+    def iter_chunks(self, chunk: int = 16, use_graph: bool = True, max_total: Optional[int] = None,
+                    feed: Optional[TorchCpuNoiseFeed] = None):
+        """`run_to_completion` as a generator: yields the sampler states after every poll (the rows they count exist on the device; read
+        them with `tokens`), the last yield being the final states. The consumer's work runs between two chunks on the caller's stream;
+        the noise feed is put back (`feed.finish`) when the loop ends, so a sampled run has to be consumed to its end."""
         total = 0
         limit = self.max_steps if max_total is None else min(max_total, self.max_steps)
         dev = self.device
@@ -867,14 +880,18 @@ class DecodeEngine:
             for u in range(self.n_utt):
                 if not live[u]:
                     self.release_utterance(u)
-            if not any(live):
-                break
-        if states is None:
-            states = self.states()
+            last = not any(live) or total >= limit
+            if last and feed is not None:
+                for u, s_ in enumerate(states):
+                    feed.finish(u, int(s_.n_steps))
+            yield states
+            if last:
+                return
+        states = self.states()                                  # a limit of 0 steps: nothing was decoded
         if feed is not None:
             for u, s_ in enumerate(states):
                 feed.finish(u, int(s_.n_steps))
-        return states
+        yield states
 
     # ------------------------------------------------------------------ continuous batching
     def run_queue(self, jobs: Sequence[dict], chunk: int = 16, use_graph: bool = True, sampling: bool = False):

@@ -148,3 +148,45 @@ def inference_one_sample(model, model_args, phn2num, text_tokenizer, audio_token
     if tts:
         wave = wave[..., int(kept_new[0][1]) * HOP:]
     return wave
+
+
+@torch.no_grad()
+def inference_one_sample_stream(model, model_args, phn2num, text_tokenizer, audio_tokenizer, audio_fn, prompt_text, target_text, mask_interval,
+                                cfg_coef, cfg_stride, aug_text, aug_context, use_watermark, tts, device, decode_config):
+    """`inference_one_sample` as a generator of waveform chunks [1, 1, n] (views of one buffer), handed out while the AR decode still
+    runs: `SSR_Speech.inference_stream` releases the frames that are final after every 16-step poll, `AudioTokenizer.decode_stream`
+    turns them into samples. The concatenation of the chunks is bit-identical to `inference_one_sample` with the same inputs and seed.
+    For `tts` the prompt (the first kept interval) only warms the codec's LSTM state up and is never yielded. The watermarked decode is
+    not streamed (`use_watermark=True` raises ValueError): its skip encoder reads the kept-audio track of the whole utterance."""
+    if use_watermark:
+        raise ValueError("inference_one_sample_stream: the watermarked decode (use_watermark=True) is not streamed; use inference_one_sample")
+    K = int(model_args.n_codebooks)
+    target_ids = _phoneme_ids(text_tokenizer, phn2num, target_text)
+    prompt_ids = _phoneme_ids(text_tokenizer, phn2num, prompt_text)
+    prompt_frames, scale = _prompt_codes(audio_tokenizer, audio_fn, K)
+    if scale is not None:
+        raise AssertionError("renormalize=False codec: scale must be None")
+    n_spans = int(mask_interval.reshape(-1, 2).shape[0])
+    # the most frames the result can have: the prompt's + the decode's step cap (models/ssr.py `cap`: a span ends at the latest when the
+    # audio is 10x the text, + K + 1 eog steps each). The codec stream allocates everything NOW, ahead of the engine's first launch.
+    max_frames = int(prompt_frames.shape[1]) + 10 * int(target_ids.shape[1]) + 2 + n_spans * (K + 1)
+    codec = audio_tokenizer.decode_stream(max_frames)
+    on_dev = lambda t: t.to(device)
+    frames = model.inference_stream(
+        on_dev(target_ids), on_dev(torch.tensor([target_ids.shape[1]])), on_dev(prompt_ids), on_dev(torch.tensor([prompt_ids.shape[1]])),
+        on_dev(prompt_frames), on_dev(prompt_frames), mask_interval=on_dev(mask_interval.unsqueeze(0)),
+        top_k=decode_config["top_k"], top_p=decode_config["top_p"], temperature=decode_config["temperature"],
+        stop_repetition=decode_config["stop_repetition"], kvcache=decode_config["kvcache"],
+        cfg_coef=cfg_coef, cfg_stride=cfg_stride, aug_text=aug_text)
+    first = True
+    for inc in frames:
+        # the first increment is the first kept interval: for `tts` the prompt, which `inference_one_sample` cuts off (:85-86)
+        chunk = codec.push(inc.codes.unsqueeze(0), emit=not (tts and first and inc.kept))
+        first = False
+        if chunk.shape[-1]:
+            yield chunk
+    if frames.result is None:
+        raise RuntimeError("generation did not finish")
+    chunk = codec.finish()
+    if chunk.shape[-1]:
+        yield chunk

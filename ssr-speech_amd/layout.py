@@ -6,11 +6,12 @@ Restates, vectorised:
                    interval arithmetic in inference()   (reference models/ssr.py:381-436, 466-502, 604-625)
   undelay       <- revert_pattern_sequence              (models/ssr.py:438-464)
   assemble      <- the tail of inference()              (models/ssr.py:776-812)
+  FrameAssembler   `assemble` in increments: the frames of the result that are already final while the decode loop still runs
 and `pack_prefill_rows`, the flattened [text || audio] rows every prefill launch of the library reads.
 """
 from __future__ import annotations
 
-from typing import List, Sequence, Tuple
+from typing import List, NamedTuple, Sequence, Tuple
 
 import numpy as np
 
@@ -128,3 +129,122 @@ def assemble(y: np.ndarray, spans: Sequence[np.ndarray], non_mask_intervals, arg
         masks.append((tmp, tmp + le - ls))
         marks += [0] * (le - ls)
     return np.concatenate(res, 1), np.asarray(marks, dtype=np.int64), masks, list(non_mask_intervals)
+
+
+class FrameIncrement(NamedTuple):
+    """Consecutive frames of the final `res`, in final time order: codes [K, n], marks [n] (0 kept / 1 generated), and whether they
+    are kept (original) frames or generated ones (one increment never mixes the two)."""
+    codes: np.ndarray
+    marks: np.ndarray
+    kept: bool
+
+
+class FrameAssembler:
+    """`assemble` while the spans are still being generated: fed the generated rows as they arrive, it hands out the frames of the
+    final `res` that can no longer change, in final time order, and never takes one back.
+
+      * the first kept segment is final at once (`start()`);
+      * generated frame t of a span is final once the span's local rows 0 .. t+K-1 exist (codebook q of frame t sits in row t+q:
+        `undelay` applied to a partial pattern) and row t's codebook 0 is not `eog` — the `eog` column is never released;
+      * the kept segment behind span i is final when span i has ended;
+      * the closing segment follows `assemble`'s last lines (the reference quirk included), and `out_len` frames are dropped in front
+        (the `aug_context` crop of models/ssr.py:806-810).
+
+    After the last span has ended the concatenation of everything handed out equals `assemble(...)[0]` / `[1]` (cropped by `out_len`),
+    and `result()` returns the 4-tuple with `masks` / `non_mask_intervals` shifted the same way."""
+
+    def __init__(self, y: np.ndarray, non_mask_intervals, args, out_len: int = 0):
+        self.y = np.asarray(y, dtype=np.int64)
+        self.K = int(self.y.shape[0])
+        self.nmi = [(int(s), int(e)) for s, e in non_mask_intervals]
+        self.n_spans = len(self.nmi) - 1              # `assemble` zips the intervals with the spans: one span behind each but the last
+        self.eog, self.empty = int(args.eog), int(args.empty_token)
+        self.out_len = int(out_len)
+        self._skip = self.out_len                     # frames still to drop in front
+        self._rows = np.zeros((0, self.K), dtype=np.int64)
+        self._cur = 0                                 # span whose frames are being released
+        self._starts = [0]                            # first row of span i
+        self._rel = 0                                 # generated frames of span `_cur` released so far
+        self._kept_out = False                        # the kept segment in front of span `_cur` has been released
+        self._tail_out = False
+        self._codes: List[np.ndarray] = []
+        self._marks: List[np.ndarray] = []
+        self._masks: List[Tuple[int, int]] = []
+        self._tmp = 0
+        self.n_released = 0                           # frames handed out (after the crop)
+
+    @property
+    def finished(self) -> bool:
+        return self._tail_out
+
+    @property
+    def rows(self) -> np.ndarray:
+        """every generated row fed so far, [n, K]"""
+        return self._rows
+
+    def _emit(self, out: List[FrameIncrement], codes: np.ndarray, kept: bool):
+        n = codes.shape[1]
+        marks = np.full(n, 0 if kept else 1, dtype=np.int64)
+        self._codes.append(codes)
+        self._marks.append(marks)
+        drop = min(self._skip, n)
+        self._skip -= drop
+        if n - drop > 0:
+            out.append(FrameIncrement(np.ascontiguousarray(codes[:, drop:]), marks[drop:], kept))
+            self.n_released += n - drop
+
+    def _kept(self, out, s: int, e: int):
+        self._masks.append((self._tmp, self._tmp + e - s))
+        self._tmp += e - s
+        self._emit(out, self.y[:, s:e], True)
+
+    def start(self) -> List[FrameIncrement]:
+        """What is final before any row exists (the first kept segment; everything when there is no span)."""
+        return self.feed(np.zeros((0, self.K), dtype=np.int64), 0, ())
+
+    def feed(self, rows: np.ndarray, span: int, span_end: Sequence[int]) -> List[FrameIncrement]:
+        """rows [n, K]: the generated rows that follow the ones already fed; `span`: how many spans have ended (the sampler state's
+        `span`); span_end[i]: the row count at which span i ended (valid for i < span). Returns the new increments, in order."""
+        rows = np.asarray(rows, dtype=np.int64).reshape(-1, self.K)
+        if rows.shape[0]:
+            self._rows = np.concatenate([self._rows, rows], 0)
+        n_rows, K = self._rows.shape[0], self.K
+        out: List[FrameIncrement] = []
+        while self._cur < self.n_spans:
+            i = self._cur
+            if not self._kept_out:
+                self._kept(out, *self.nmi[i])
+                self._kept_out = True
+            ended = i < int(span)
+            r0 = self._starts[i]
+            r1 = int(span_end[i]) if ended else n_rows
+            if r1 > n_rows:
+                raise ValueError(f"span {i} ended at row {r1}, only {n_rows} rows were fed")
+            t = self._rel
+            while t + K - 1 < r1 - r0 and self._rows[r0 + t, 0] != self.eog:
+                t += 1
+            if t > self._rel:
+                loc = self._rows[r0:r1]
+                self._emit(out, np.stack([loc[q + self._rel: q + t, q] for q in range(K)]), False)
+                self._tmp += t - self._rel
+                self._rel = t
+            if not ended:
+                return out
+            if self._rel != max(r1 - r0 - K, 0):
+                raise ValueError(f"span {i}: {r1 - r0} rows hold {max(r1 - r0 - K, 0)} frames, {self._rel} were released")
+            self._starts.append(r1)
+            self._cur, self._rel, self._kept_out = i + 1, 0, False
+        if not self._tail_out:
+            ls, le = self.nmi[-1]
+            if self.y.shape[1] != le + 1:            # reference quirk kept verbatim (ssr.py:799)
+                self._kept(out, ls, le)
+            self._tail_out = True
+        return out
+
+    def result(self):
+        """-> (res [K, T'], marks [T'], masks, non_mask_intervals) of the finished utterance: `assemble`'s, cropped by `out_len`."""
+        if not self._tail_out:
+            raise RuntimeError("FrameAssembler.result() before the last span has ended")
+        o = self.out_len
+        res, marks = np.concatenate(self._codes, 1)[:, o:], np.concatenate(self._marks)[o:]
+        return res, marks, [(a - o, b - o) for a, b in self._masks], [(a - o, b - o) for a, b in self.nmi]

@@ -37,6 +37,52 @@ def _set_param(root: nn.Module, dotted: str, p: nn.Parameter):
     mod.register_parameter(parts[-1], p)
 
 
+class InferenceStream:
+    """Iterator returned by `SSR_Speech.inference_stream`; `.result` is set when it is exhausted, `.steps_enqueued` is how many decode
+    steps the engine has been given so far."""
+
+    def __init__(self, model: "SSR_Speech", setup_args: tuple, use_graph: bool):
+        self.model, self.result, self.steps_enqueued = model, None, 0
+        self._it = self._run(setup_args, use_graph)
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        return next(self._it)
+
+    def _run(self, setup_args, use_graph):
+        m = self.model
+        with torch.no_grad():
+            K, held = m.args.n_codebooks, {}
+            # every frame the run can release, on the device: ONE buffer, allocated ahead of the engine's first launch
+            run = m._begin_inference(*setup_args, before_start=lambda n: held.update(buf=torch.empty(K * n, dtype=torch.int64, device=m.device)))
+            eng, buf = run["eng"], held["buf"]
+            asm = LY.FrameAssembler(run["y_np"], run["nmi"], m.args, run["out_len"] if run["aug_context"] else 0)
+            at = 0
+
+            def on_device(incs):
+                nonlocal at
+                for inc in incs:
+                    n = inc.codes.shape[1]
+                    view = buf[K * at: K * (at + n)].view(K, n)      # contiguous: one plain host-to-device copy
+                    view.copy_(torch.from_numpy(inc.codes))
+                    at += n
+                    yield LY.FrameIncrement(view, inc.marks, inc.kept)
+
+            yield from on_device(asm.start())
+            have, st = 0, None
+            for states in eng.iter_chunks(chunk=16, use_graph=use_graph, max_total=run["cap"], feed=run["feed"]):
+                st = states[0]
+                self.steps_enqueued = eng._steps_enqueued
+                n = int(st.n_steps)
+                rows = eng.tokens(0, n, have)                   # through `tokens`: the pair-launch check guards every row that leaves
+                have = n
+                yield from on_device(asm.feed(rows, int(st.span), list(st.span_end)))
+            self.result = m._end_inference(run, st, asm.rows)
+            return self.result
+
+
 class SSR_Speech(nn.Module):
     def __init__(self, args: Optional[Namespace] = None, config: Optional[Dict] = None):
         super().__init__()
@@ -147,7 +193,7 @@ class SSR_Speech(nn.Module):
 
         batch: the collated batch of data/gigaspeech.py:298-321 — x [B,S], x_lens [B], y [B,K,T] (rearranged / shifted / mask-inserted,
         padded with audio_pad_token), y_lens [B]. An empty batch returns None. The items are packed without padding rows into launches of
-        at most `max_rows` rows (an item longer than that is a launch of its own); scratch memory grows with `max_rows` (DESIGN I.9).
+        at most `max_rows` rows (an item longer than that is a launch of its own); scratch memory grows with `max_rows` (DESIGN I.7).
         Top-10 hits count targets with fewer than 10 strictly larger logits: exact ties at the 10th place count as hits."""
         items = SC.validate(batch, self.args)          # ValueError before anything reaches the device
         if items is None:
@@ -259,6 +305,18 @@ class SSR_Speech(nn.Module):
         produces identical tokens for kvcache 0/1).  Keyword-only extras (not in the reference):
         `noise` [steps,K,card] Exp(1) draws replacing the multinomial generator draw, `uncond_x`
         overriding the random CFG text (ssr.py:574), `max_new_steps` (tests), `use_graph`."""
+        run = self._begin_inference(x, x_lens, prompt_x, prompt, y, mask_interval, top_k, top_p, temperature, stop_repetition, silence_tokens,
+                                    cfg_coef, cfg_stride, aug_text, aug_context, cfg_pretrained, noise, uncond_x, max_new_steps)
+        eng = run["eng"]
+        states = eng.run_to_completion(chunk=16, use_graph=use_graph, max_total=run["cap"], feed=run["feed"])
+        st = states[0]
+        return self._end_inference(run, st, eng.tokens(0, int(st.n_steps)))
+
+    def _begin_inference(self, x, x_lens, prompt_x, prompt, y, mask_interval, top_k, top_p, temperature, stop_repetition, silence_tokens,
+                         cfg_coef, cfg_stride, aug_text, aug_context, cfg_pretrained, noise, uncond_x, max_new_steps, before_start=None) -> dict:
+        """Everything `inference` does before the decode loop (shared with `inference_stream`): argument checks, prompt layout, engine,
+        prefill. `before_start(n)` is called ahead of the engine's first launch with the most frames the result can have. Returns what
+        the loop and `_end_inference` need."""
         t_call = time.perf_counter()
         K = self.args.n_codebooks
         assert cfg_coef >= 1.0, cfg_coef
@@ -275,7 +333,6 @@ class SSR_Speech(nn.Module):
         context_len = int(sum(int(item[1] - item[0]) for item in mask_interval[0]))
         aug_context = bool(aug_context and context_len < 2 * 50)
 
-        dev = self.device
         x_np = x.detach().cpu().numpy().astype(np.int64)
         y_np = y[0].detach().cpu().numpy().astype(np.int64)
         mi = mask_interval[0].detach().cpu().numpy().astype(np.int64)
@@ -311,6 +368,8 @@ class SSR_Speech(nn.Module):
         knobs = DecodeKnobs(top_k=top_k, top_p=top_p, temperature=temperature, stop_repetition=stop_repetition,
                             silence_tokens=tuple(int(s) for s in silence_tokens), cfg_coef=cfg_coef, cfg_stride=cfg_stride,
                             use_cfg=bool(aug_text), text_len=L, n_spans=num_task, seed=int(torch.initial_seed()))
+        if before_start is not None:
+            before_start(y_np.shape[1] + cap)
         greedy = top_k == 1
         feed = None
         if noise is not None:
@@ -322,26 +381,43 @@ class SSR_Speech(nn.Module):
             eng.start(text_rows, [cated], [knobs], host_noise=True)
         else:
             eng.start(text_rows, [cated], [knobs])
-        states = eng.run_to_completion(chunk=16, use_graph=use_graph, max_total=cap, feed=feed)
-        st = states[0]
-        gen = eng.tokens(0, int(st.n_steps))
-        self.last_run = dict(steps=st.n_steps, done=st.done, span_end=list(st.span_end), prefill_rows=(L + T0) * (2 if aug_text else 1),
-                             t_start=t_call, t_first_chunk=eng.t_first_chunk, t_end=time.perf_counter())
+        return dict(eng=eng, feed=feed, cap=cap, y_np=y_np, nmi=nmi, num_task=num_task, out_len=out_len, aug_context=aug_context,
+                    prefill_rows=(L + T0) * (2 if aug_text else 1), t_call=t_call, max_new_steps=max_new_steps)
+
+    def _end_inference(self, run: dict, st, gen: np.ndarray):
+        """What `inference` does after the decode loop: `last_run`, the not-finished cases, span re-assembly, the 4-tuple."""
+        eng, cap, num_task, out_len = run["eng"], run["cap"], run["num_task"], run["out_len"]
+        self.last_run = dict(steps=st.n_steps, done=st.done, span_end=list(st.span_end), prefill_rows=run["prefill_rows"],
+                             t_start=run["t_call"], t_first_chunk=eng.t_first_chunk, t_end=time.perf_counter())
         if st.done != 1:
-            if max_new_steps is not None:
+            if run["max_new_steps"] is not None:
                 return None
             raise RuntimeError(f"generation did not finish within {cap} steps (done={st.done})")
         ends = [0] + [st.span_end[i] for i in range(num_task)]
         spans = [gen[ends[i]:ends[i + 1]] for i in range(num_task)]
-        res, marks, masks, nmi_out = LY.assemble(y_np, spans, nmi, self.args)
-        if aug_context:                                         # ssr.py:806-810
+        res, marks, masks, nmi_out = LY.assemble(run["y_np"], spans, run["nmi"], self.args)
+        if run["aug_context"]:                                  # ssr.py:806-810
             res, marks = res[:, out_len:], marks[out_len:]
             masks = [(a - out_len, b - out_len) for a, b in masks]
             nmi_out = [(a - out_len, b - out_len) for a, b in nmi_out]
-        res_t = torch.from_numpy(np.ascontiguousarray(res)).unsqueeze(0).to(dev)
+        res_t = torch.from_numpy(np.ascontiguousarray(res)).unsqueeze(0).to(self.device)
         marks_t = torch.from_numpy(np.ascontiguousarray(marks)).unsqueeze(0)          # CPU tensor, as the reference (ssr.py:805)
         logging.info(f"ssr_speech_amd: generated {st.n_steps} steps")
         return res_t, marks_t, masks, nmi_out
+
+    @torch.no_grad()
+    def inference_stream(self, x, x_lens, prompt_x, prompt_x_lens, y, prompt, mask_interval, top_k: int = -100, top_p: float = 1.0,
+                         temperature: float = 1.0, stop_repetition: int = -1, kvcache: int = 1, silence_tokens: List[int] = [1388, 1898, 131],
+                         cfg_coef: float = 1.5, cfg_stride: int = 1, aug_text: bool = False, aug_context: bool = False,
+                         cfg_pretrained: bool = False, *, noise: Optional[torch.Tensor] = None, uncond_x: Optional[torch.Tensor] = None,
+                         max_new_steps: Optional[int] = None, use_graph: bool = True) -> "InferenceStream":
+        """`inference` that hands the result out while the decode loop still runs: an iterator of `layout.FrameIncrement`s — the frames
+        of the final `res` that can no longer change, in final time order, `codes` [K, n] int64 on the model's device (views of one buffer
+        allocated before the first launch) — released after every 16-step poll of the engine. Same arguments, same tokens, same use of
+        the CPU generator as `inference`; after exhaustion `.result` holds the 4-tuple `inference` would have returned (it is also the
+        generator's `StopIteration.value`) and `last_run` is filled the same way. Nothing runs before the first `next()`."""
+        return InferenceStream(self, (x, x_lens, prompt_x, prompt, y, mask_interval, top_k, top_p, temperature, stop_repetition, silence_tokens,
+                                      cfg_coef, cfg_stride, aug_text, aug_context, cfg_pretrained, noise, uncond_x, max_new_steps), use_graph)
 
     # ------------------------------------------------------------------ batched decode (new capability)
     @torch.no_grad()
