@@ -34,7 +34,7 @@ typedef void* ssrhip_stream_t;
 int ssrhip_version(void);
 /* sizeof() of the ABI structs, for binding self-checks: 0 kv, 1 gemv_args, 2 attn_args, 3 embed_args,
  * 4 sampler_cfg, 5 sampler_state, 6 sample_args, 7 gemm_args, 8 lm_weights, 9 lm_dims, 10 lm_buffers, 11 prefill_args,
- * 12 lstm_args, 13 resblock_args, 14 score_args */
+ * 12 lstm_args, 13 resblock_args, 14 score_args, 15 lm_w16 */
 int ssrhip_sizeof(int which);
 const char* ssrhip_last_error(void);
 
@@ -101,6 +101,24 @@ typedef struct ssrhip_gemv_args {
 #define SSRHIP_TILED_P(b, k, K) (((size_t)(b) >> 4) * 16 * (size_t)(K) + SSRHIP_TILED((b) & 15, k))
 
 int ssrhip_gemv(const ssrhip_gemv_args* a, ssrhip_stream_t stream);
+
+/* Packed bf16 weight layout of the opt-in bf16 weight stream (<= 4 rows, csrc/gemv_w16.hip; K % 1024 == 0). The unit is the fp32 segment
+ * kernels' (row, 1024-element segment of K) = 2 KiB; inside it lane l's 16-byte load j (j = 0, 1) sits at byte j*1024 + l*16 and holds the
+ * 8 weights of that kernel's float4 #2j followed by #2j+1 of the same lane (float4 #i of lane l = elements i*256 + 4l .. 4l+3 of the
+ * segment): a wave-level load is one contiguous KiB and, widened, meets the same pieces of x as in the fp32 kernel. uint16 index of W[n][k]:
+ *   r = k % 1024, i = r / 256, lane = (r % 256) / 4:   (n*(K/1024) + k/1024)*1024 + (i/2)*512 + lane*8 + (i%2)*4 + k%4
+ * A group's matrix takes N*K uint16; groups follow each other. Each uint16 is the upper half of the fp32 weight rounded to nearest even. */
+#define SSRHIP_W16_INDEX(n, k, K) \
+  (((size_t)(n) * ((size_t)(K) / 1024) + (size_t)(k) / 1024) * 1024 + ((((k) % 1024) / 256) / 2) * 512 + ((((k) % 1024) % 256) / 4) * 8 + ((((k) % 1024) / 256) % 2) * 4 + (k) % 4)
+
+/* ssrhip_gemv(a) streaming the PACKED bf16 copy `W16` (SSRHIP_W16_INDEX) of a->W instead of a->W itself. a->W must hold exactly the
+ * bf16-representable values of W16 (the fp32 "master": what a->W rounds to is what W16 stores); the result is then BIT-IDENTICAL to
+ * ssrhip_gemv(a): the weights are widened in registers (a 16-bit shift, exact) and every sum runs in the order of the fp32 kernel.
+ *   returns 0 = launched, 1 = `a` does not qualify and NOTHING was launched (call ssrhip_gemv(a)), < 0 = contract error.
+ *   Qualifies exactly when ssrhip_gemv takes its segment kernels: B in {1, 2, 4}; K % 1024 == 0 and K / 1024 in {1, 2, 4, 8}; a LayerNorm
+ *   prologue only with folded gamma / beta (ln_w == NULL); a split-KV merge prologue only with K == 2048, one group; SSRHIP_GEMV_SEG != 0. */
+int ssrhip_gemv_w16(const ssrhip_gemv_args* a, const uint16_t* W16, ssrhip_stream_t stream);
+int ssrhip_gemv_w16_applicable(const ssrhip_gemv_args* a);
 
 /* Two consecutive launches of the 2-row decode step as ONE: `a` = a GEMV with the residual epilogue and `b` = the LayerNorm + Linear that
  * reads a's output, with the all-to-all edge between them inside the launch (csrc/gemv.hip gemv_pair_kernel / gemv_pair_merge_kernel:
@@ -427,6 +445,21 @@ int ssrhip_lm_create(const ssrhip_lm_dims* d, const ssrhip_lm_weights* w, const 
 /* 1 = this engine's decode step uses pair launches, 0 = it does not; `why` (may be NULL) receives the reason as text */
 int ssrhip_lm_pairing(const ssrhip_lm* lm, char* why, int32_t why_len);
 void ssrhip_lm_destroy(ssrhip_lm* lm);
+/* The opt-in bf16 weight stream of the <= 4-row decode step: packed bf16 copies (SSRHIP_W16_INDEX) of the six matrix families, device
+ * pointers; the per-layer fields are HOST arrays of n_layer entries (copied by ssrhip_lm_set_w16). A NULL field (or a NULL entry of a
+ * per-layer array) means that matrix streams its fp32 master. The masters in ssrhip_lm_weights must hold the rounded values (ssrhip_gemv_w16). */
+typedef struct ssrhip_lm_w16 {
+  const uint16_t* const* in_proj_w16; const uint16_t* const* out_proj_w16; const uint16_t* const* ffn1_w16; const uint16_t* const* ffn2_w16;
+  const uint16_t* head1_w16; const uint16_t* head2_w16;
+} ssrhip_lm_w16;
+/* Hand the engine the packed copies: from now on every GEMV launch of its decode step whose family has one and whose shape qualifies
+ * (ssrhip_gemv_w16) streams 2-byte weights; the others run ssrhip_gemv on the masters. Same tokens, bit for bit, as the same engine without
+ * this call. To be called before the first decode step is enqueued or captured; refused (< 0) afterwards and for engines of more than 4
+ * rows. The pair launches read fp32 weights: an engine that holds its device's pairing slot gives it back and steps unpaired
+ * (ssrhip_lm_pairing then reports 0 and names the bf16 stream). Prefill and scoring read the masters and are not affected. */
+int ssrhip_lm_set_w16(ssrhip_lm* lm, const ssrhip_lm_w16* w16);
+/* how many GEMV launches of the last enqueued (or captured) decode step ran a bf16-stream kernel (4 * n_layer + 2 when every family qualifies) */
+int ssrhip_lm_w16_launches(const ssrhip_lm* lm);
 /* enqueue `n_steps` decode steps (graph replays when use_graph!=0) */
 int ssrhip_lm_decode(ssrhip_lm* lm, int32_t n_steps, int32_t use_graph, ssrhip_stream_t stream);
 /* prefill R rows ([text || audio] of every sequence, flattened): fills the cache for all layers.

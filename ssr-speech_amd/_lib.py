@@ -164,12 +164,19 @@ class ScoreArgs(C.Structure):
                 ("head1_ws", C.c_void_p), ("head2_ws", C.c_void_p)]
 
 
+class LMW16(C.Structure):
+    _fields_ = [("in_proj_w16", _PP), ("out_proj_w16", _PP), ("ffn1_w16", _PP), ("ffn2_w16", _PP),
+                ("head1_w16", C.c_void_p), ("head2_w16", C.c_void_p)]
+
+
 # every symbol include/ssrhip.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("ssrhip_version", C.c_int, []),
     ("ssrhip_sizeof", C.c_int, [C.c_int]),
     ("ssrhip_last_error", C.c_char_p, []),
     ("ssrhip_gemv", C.c_int, [C.POINTER(GemvArgs), C.c_void_p]),
+    ("ssrhip_gemv_w16", C.c_int, [C.POINTER(GemvArgs), C.c_void_p, C.c_void_p]),
+    ("ssrhip_gemv_w16_applicable", C.c_int, [C.POINTER(GemvArgs)]),
     ("ssrhip_pair_buffer", C.c_int, [C.c_int32, C.c_int32]),
     ("ssrhip_gemv_pair_applicable", C.c_int, [C.POINTER(GemvArgs), C.POINTER(GemvArgs)]),
     ("ssrhip_gemv_pair", C.c_int, [C.POINTER(GemvArgs), C.POINTER(GemvArgs), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
@@ -201,13 +208,15 @@ SYMBOLS = [
     ("ssrhip_xent_rank", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("ssrhip_lm_pairing", C.c_int, [C.c_void_p, C.c_char_p, C.c_int32]),
     ("ssrhip_lm_pair_status", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("ssrhip_lm_set_w16", C.c_int, [C.c_void_p, C.POINTER(LMW16)]),
+    ("ssrhip_lm_w16_launches", C.c_int, [C.c_void_p]),
     ("ssrhip_debug_occupy", C.c_int, [C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
     ("ssrhip_lm_time_steps", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, c_f32p, c_i32p, C.c_int32]),
     ("ssrhip_lm_time_category", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, c_f32p, c_i32p]),
 ]
 
 ABI_STRUCTS = [KV, GemvArgs, AttnArgs, EmbedArgs, SamplerCfg, SamplerState, SampleArgs, GemmArgs, LMWeights, LMDims,
-               LMBuffers, PrefillArgs, LstmArgs, ResblockArgs, ScoreArgs]
+               LMBuffers, PrefillArgs, LstmArgs, ResblockArgs, ScoreArgs, LMW16]
 
 _lib = None
 

@@ -48,6 +48,7 @@ extern "C" int ssrhip_sizeof(int which) {
     case 12: return sizeof(ssrhip_lstm_args);
     case 13: return sizeof(ssrhip_resblock_args);
     case 14: return sizeof(ssrhip_score_args);
+    case 15: return sizeof(ssrhip_lm_w16);
     default: return -1;
   }
 }
@@ -65,6 +66,11 @@ struct ssrhip_lm {
   void* pair_ws = nullptr;      // granules of the paired GEMV launches (2-row step; SSRHIP_PAIR_WS_BYTES, owned)
   int pair_dev = -1;            // >= 0: this engine holds the pairing slot of that device (released in ssrhip_lm_destroy)
   char pair_why[200] = "";      // why the step pairs / does not pair (ssrhip_lm_pairing)
+  // the bf16 weight stream (ssrhip_lm_set_w16): packed copies of the six families, NULL = that matrix streams its fp32 master
+  std::vector<const uint16_t*> w16[4];      // in_proj, out_proj, ffn1, ffn2 per layer (empty: none)
+  const uint16_t* head1_w16 = nullptr;
+  const uint16_t* head2_w16 = nullptr;
+  int w16_launches = 0;         // launches of the last enqueued step that ran a w16 kernel (ssrhip_lm_w16_launches)
 };
 
 namespace {
@@ -317,6 +323,18 @@ int enqueue_step(ssrhip_lm* lm, hipStream_t s, Timer* tm) {
     pair_i += 1;
     return ssrhip_gemv_pair(&ga, &gb, lm->pair_ws, bufi, bufn, (ssrhip_stream_t)s);
   };
+  // Every single GEMV launch of the step goes through here: the packed bf16 copy of the matrix when the engine has one and the shape
+  // qualifies (ssrhip_gemv_w16 answers 1 without launching when it does not), the fp32 weights otherwise. Same bits either way.
+  int n_w16 = 0;
+  auto gemv_call = [&](const ssrhip_gemv_args& ga, const uint16_t* w16) -> int {
+    if (w16) {
+      const int rc = ssrhip_gemv_w16(&ga, w16, (ssrhip_stream_t)s);
+      if (rc <= 0) { n_w16 += rc == 0; return rc; }
+    }
+    return ssrhip_gemv(&ga, s);
+  };
+  auto w16_of = [&](int family, int l) -> const uint16_t* { return lm->w16[family].empty() ? nullptr : lm->w16[family][l]; };
+  enum { W16_IN = 0, W16_OUT = 1, W16_FFN1 = 2, W16_FFN2 = 3 };
   bool qkv_done = false;                        // this layer's QKV already ran inside the previous layer's pair launch
   // 5..32 rows with enough (row, head) pairs to give every CU one: the fused walk over the pages (no partials, no merge
   // launch); its output goes to b.h (free until FFN1 of this layer) because q is still being read by other workgroups
@@ -327,7 +345,7 @@ int enqueue_step(ssrhip_lm* lm, hipStream_t s, Timer* tm) {
   for (int l = 0; l < d.n_layer; ++l) {
     if (!qkv_done) {
       const ssrhip_gemv_args g = sh.qkv_args(l);
-      STEP_CALL(CAT_GEMV, ssrhip_gemv(&g, s));
+      STEP_CALL(CAT_GEMV, gemv_call(g, w16_of(W16_IN, l)));
     }
     qkv_done = false;
 
@@ -361,8 +379,8 @@ int enqueue_step(ssrhip_lm* lm, hipStream_t s, Timer* tm) {
     if (pair_ffn1) {                              // out-projection + FFN1 as one launch (2 rows)
       STEP_CALL(CAT_GEMV, pair_call(op, f1));
     } else {
-      STEP_CALL(CAT_GEMV, ssrhip_gemv(&op, s));
-      STEP_CALL(CAT_GEMV, ssrhip_gemv(&f1, s));
+      STEP_CALL(CAT_GEMV, gemv_call(op, w16_of(W16_OUT, l)));
+      STEP_CALL(CAT_GEMV, gemv_call(f1, w16_of(W16_FFN1, l)));
     }
 
     // FFN2 + residual — paired with the next launch where that applies
@@ -372,17 +390,18 @@ int enqueue_step(ssrhip_lm* lm, hipStream_t s, Timer* tm) {
       STEP_CALL(CAT_GEMV, pair_call(f2, last ? sh.head1_args() : sh.qkv_args(l + 1)));
       qkv_done = true;                          // (after the last layer: the head MLP's first launch)
     } else {
-      STEP_CALL(CAT_GEMV, ssrhip_gemv(&f2, s));
+      STEP_CALL(CAT_GEMV, gemv_call(f2, w16_of(W16_FFN2, l)));
     }
   }
   if (!qkv_done) {
     const ssrhip_gemv_args g = sh.head1_args();
-    STEP_CALL(CAT_GEMV, ssrhip_gemv(&g, s));
+    STEP_CALL(CAT_GEMV, gemv_call(g, lm->head1_w16));
   }
   const ssrhip_gemv_args h2 = sh.head2_args();
-  STEP_CALL(CAT_GEMV, ssrhip_gemv(&h2, s));
+  STEP_CALL(CAT_GEMV, gemv_call(h2, lm->head2_w16));
   const ssrhip_sample_args sa = sh.sample_args();
   STEP_CALL(CAT_SAMPLE, ssrhip_sample(&sa, s));
+  if (!tm || tm->only < 0) lm->w16_launches = n_w16;         // (a category-timing pass enqueues only part of a step)
   return 0;
 }
 
@@ -479,6 +498,26 @@ extern "C" int ssrhip_lm_pairing(const ssrhip_lm* lm, char* why, int32_t why_len
   if (why && why_len > 0) snprintf(why, (size_t)why_len, "%s", lm->pair_why);
   return lm->pair_ws ? 1 : 0;
 }
+
+extern "C" int ssrhip_lm_set_w16(ssrhip_lm* lm, const ssrhip_lm_w16* w16) {
+  SSR_REQUIRE(lm && w16, "ssrhip_lm_set_w16: null argument");
+  SSR_REQUIRE(lm->b.B <= 4, "ssrhip_lm_set_w16: the bf16 weight stream exists for the <= 4-row decode step only (this engine has %d rows)", lm->b.B);
+  SSR_REQUIRE(!lm->exec, "ssrhip_lm_set_w16: the decode step of this engine is already captured (call it before the first ssrhip_lm_decode)");
+  const uint16_t* const* src[4] = {w16->in_proj_w16, w16->out_proj_w16, w16->ffn1_w16, w16->ffn2_w16};
+  for (int f = 0; f < 4; ++f) {
+    if (src[f]) lm->w16[f].assign(src[f], src[f] + lm->d.n_layer);
+    else lm->w16[f].clear();
+  }
+  lm->head1_w16 = w16->head1_w16;
+  lm->head2_w16 = w16->head2_w16;
+  // the pair launches stream fp32 weights: this engine steps unpaired and gives the device's pairing slot back
+  if (lm->pair_ws) { hipFree(lm->pair_ws); lm->pair_ws = nullptr; }
+  if (lm->pair_dev >= 0) { pair_slot_release(lm->pair_dev); lm->pair_dev = -1; }
+  snprintf(lm->pair_why, sizeof(lm->pair_why), "this engine streams bf16 weights (ssrhip_lm_set_w16): the pair launches exist for fp32 weights only");
+  return 0;
+}
+
+extern "C" int ssrhip_lm_w16_launches(const ssrhip_lm* lm) { return lm ? lm->w16_launches : 0; }
 
 extern "C" int ssrhip_lm_pair_status(ssrhip_lm* lm, ssrhip_stream_t stream) {
   SSR_REQUIRE(lm, "ssrhip_lm_pair_status: null engine");

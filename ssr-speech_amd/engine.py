@@ -59,10 +59,38 @@ def to_streaming_order(W: torch.Tensor) -> torch.Tensor:
     return W.reshape(*lead, U, 8, K // 16, 4, 4).permute(*range(len(lead)), -5, -3, -2, -4, -1).contiguous()
 
 
-class LMWeightsArena:
-    """Device-resident fp32 weights in the layout the kernels want (one-time repack at load)."""
+def to_w16_order(W: torch.Tensor) -> torch.Tensor:
+    """[.., N, K] (K % 1024 == 0) -> the packed bf16 order of the <= 4-row bf16 weight stream (include/ssrhip.h SSRHIP_W16_INDEX) as an
+    int16 tensor of the same shape: per (row, 1024-element segment) two KiB-sized wave loads, lane l's 16 bytes of load j holding the fp32
+    kernel's float4 #2j and #2j+1 of that lane. Values are rounded to bf16 (nearest even); already rounded masters pack exactly."""
+    *lead, N, K = W.shape
+    assert K % 1024 == 0, K
+    Wb = W.to(torch.bfloat16).reshape(*lead, N, K // 1024, 2, 2, 64, 4)          # [n][segment][i / 2][i % 2][lane][k % 4]
+    n = len(lead)
+    return Wb.permute(*range(n), n, n + 1, n + 2, n + 4, n + 3, n + 5).contiguous().view(torch.int16).reshape(*lead, N, K)
 
-    def __init__(self, args, sd: dict, device, max_pos: int = 8192):
+
+W16_FAMILIES = ("in_proj", "out_proj", "ffn1", "ffn2")      # per layer; plus head1 and head2
+WEIGHT_DTYPES = ("fp32", "bf16")
+
+
+def w16_streamable(K: int) -> bool:
+    """Can a matrix with this inner dimension have a packed copy (the shapes ssrhip_gemv_w16 takes)?"""
+    return K % 1024 == 0 and K // 1024 in (1, 2, 4, 8)
+
+
+class LMWeightsArena:
+    """Device-resident fp32 weights in the layout the kernels want (one-time repack at load).
+
+    weight_dtype="bf16": the six matrix families of the decode step (in_proj / out_proj / ffn1 / ffn2 per layer, head1, head2) are rounded
+    ONCE to bf16 (nearest even) as the arena holds them, i.e. after the LayerNorm fold, and kept as fp32 "masters" in the usual fields:
+    prefill, score, the streaming-order copies and the split planes all read the same rounded values. `ensure_w16_copies` adds the
+    packed 2-byte copies the <= 4-row decode step streams. Biases, embeddings and the position table stay fp32."""
+
+    def __init__(self, args, sd: dict, device, max_pos: int = 8192, weight_dtype: str = "fp32"):
+        if weight_dtype not in WEIGHT_DTYPES:
+            raise ValueError(f"weight_dtype {weight_dtype!r} not in {WEIGHT_DTYPES}")
+        self.weight_dtype = weight_dtype
         f32 = dict(dtype=torch.float32, device=device)
         self.args = args
         self.device = device
@@ -111,6 +139,41 @@ class LMWeightsArena:
         self.head1_b = (h1b.double() + h1w.double() @ bet.double()).to(torch.float32).contiguous()
         self.head2_w = torch.stack([g(f"predict_layer.{k}.2.weight") for k in range(self.K)]).contiguous()
         self.head2_b = torch.stack([g(f"predict_layer.{k}.2.bias") for k in range(self.K)]).contiguous()
+        if weight_dtype == "bf16":
+            rnd = lambda t: t.to(torch.bfloat16).to(torch.float32).contiguous()
+            for lay in self.layers:
+                for name in W16_FAMILIES:
+                    lay[name + "_w"] = rnd(lay[name + "_w"])
+            self.head1_w, self.head2_w = rnd(self.head1_w), rnd(self.head2_w)
+
+    def ensure_w16_copies(self) -> bool:
+        """Packed bf16 copies (`to_w16_order`) of the six matrix families for the <= 4-row decode step of a bf16 arena (+2 bytes per
+        weight = +1.65 GB at 830M, built once on first use). A family whose inner dimension the kernels do not take (`w16_streamable`,
+        e.g. d_model 128) gets none and streams its master. Returns True when the copies were created now."""
+        if self.weight_dtype != "bf16":
+            raise ValueError("packed bf16 copies need an arena built with weight_dtype='bf16' (the masters must hold the rounded values)")
+        if getattr(self, "_w16_ready", False):
+            return False
+        pack = lambda Wm: to_w16_order(Wm) if w16_streamable(Wm.shape[-1]) else None
+        for lay in self.layers:
+            for name in W16_FAMILIES:
+                lay[name + "_w16"] = pack(lay[name + "_w"])
+        self.head1_w16, self.head2_w16 = pack(self.head1_w), pack(self.head2_w)
+        self._w16_ready = True
+        self.generation += 1
+        return True
+
+    def w16_struct(self):
+        """ssrhip_lm_w16 of the packed copies (NULL where a family has none)."""
+        w = _lib.LMW16()
+        self._w16_arrays = {}
+        for name in W16_FAMILIES:
+            if all(lay[name + "_w16"] is not None for lay in self.layers):
+                arr = (C.c_void_p * self.L)(*[lay[name + "_w16"].data_ptr() for lay in self.layers])
+                self._w16_arrays[name] = arr
+                setattr(w, name + "_w16", C.cast(arr, C.POINTER(C.c_void_p)))
+        w.head1_w16, w.head2_w16 = _lib.ptr(self.head1_w16), _lib.ptr(self.head2_w16)
+        return w
 
     def ensure_streaming_copies(self) -> bool:
         """Second copy of the six matrices of a decode step in the streaming order of the 5..16-row GEMV (one-time repack; used
@@ -177,11 +240,15 @@ class LMWeightsArena:
         """Algorithmic weight bytes one decode step must stream."""
         n = 0
         for lay in self.layers:
-            n += sum(t.numel() for k, t in lay.items() if not k.endswith("_wt") and not k.endswith("_ws"))     # incl. the (now constant) LayerNorm vectors, as SURVEY §8d counts them
+            n += sum(t.numel() for k, t in lay.items() if not k.endswith(("_wt", "_ws", "_w16")))     # incl. the (now constant) LayerNorm vectors, as SURVEY §8d counts them
         n += self.lnf_w.numel() + self.lnf_b.numel()
         n += self.head1_w.numel() + self.head1_b.numel() + self.head2_w.numel() + self.head2_b.numel()
         n += (self.K + 1) * self.D  # K embedding rows + one pe row
-        return 4 * n
+        half = 0                    # weights that have a packed bf16 copy stream 2 bytes each
+        if getattr(self, "_w16_ready", False):
+            half = sum(lay[name + "_w16"].numel() for lay in self.layers for name in W16_FAMILIES if lay[name + "_w16"] is not None)
+            half += sum(t.numel() for t in (self.head1_w16, self.head2_w16) if t is not None)
+        return 4 * n - 2 * half
 
     def c_struct(self):
         w = _lib.LMWeights()
@@ -377,11 +444,14 @@ class DecodeEngine:
     """B rows (= n_utt x (2 if CFG else 1)) decoded in lock-step; one captured hipGraph per engine."""
 
     def __init__(self, arena: LMWeightsArena, n_utt: int, use_cfg: bool, max_seq: int, max_steps: int, debug_logits: bool = False,
-                 pool_pages: Optional[int] = None, page_order: Optional[Sequence[int]] = None, pair_mode: int = 0):
+                 pool_pages: Optional[int] = None, page_order: Optional[Sequence[int]] = None, pair_mode: int = 0,
+                 stream_w16: Optional[bool] = None):
         """max_seq: longest sequence (text + audio positions) any ONE row may reach; pool_pages: physical KV pages shared by all
         rows (default rows x pages-per-row, the no-sharing worst case; a batch of short and long utterances needs only the sum
         of their own page counts). pair_mode (2-row engines; include/ssrhip.h ssrhip_lm_buffers): 0 = pair launches if this engine
-        gets its device's pairing slot, 1 = never, 2 = always (tests of the give-up path)."""
+        gets its device's pairing slot, 1 = never, 2 = always (tests of the give-up path). stream_w16: the decode step streams the arena's
+        packed bf16 copies (include/ssrhip.h ssrhip_lm_set_w16; needs a bf16 arena and <= 4 rows, steps unpaired); None = on when the arena
+        is bf16, the engine has <= 4 rows and `SSRHIP_GEMV_W16` (read here) does not start with '0'."""
         self.lib = _lib.lib()
         self.a = arena
         dev = arena.device
@@ -392,12 +462,21 @@ class DecodeEngine:
         self.B = n_utt * self.rows_per_utt
         if self.B not in (1, 2, 4) and not (5 <= self.B <= MAX_ROWS):
             raise ValueError(f"rows B={self.B} not supported by this build (1, 2, 4 or 5..{MAX_ROWS})")
+        if stream_w16 is None:
+            stream_w16 = arena.weight_dtype == "bf16" and self.B <= 4 and os.environ.get("SSRHIP_GEMV_W16", "1")[:1] != "0"
+        elif stream_w16 and self.B > 4:
+            raise ValueError(f"stream_w16: the bf16 weight stream exists for the <= 4-row decode step only (this engine has {self.B} rows)")
+        elif stream_w16 and arena.weight_dtype != "bf16":
+            raise ValueError("stream_w16 needs an arena built with weight_dtype='bf16'")
+        self.stream_w16 = bool(stream_w16)
         self.max_pages = (max_seq + PAGE - 1) // PAGE
         self.max_seq = self.max_pages * PAGE
         arena.ensure_positions(self.max_seq)      # every text / audio position of a row is < its sequence capacity
         if self.B > 4:
             arena.ensure_streaming_copies()       # the matrix-core GEMV streams W in its own order
         arena.ensure_split_planes()               # the prefill GEMMs run on the bf16 matrix cores with exactly split operands
+        if self.stream_w16:
+            arena.ensure_w16_copies()             # the <= 4-row step streams packed 2-byte weights
         self.max_steps = max_steps
         D, H, L, K = arena.D, arena.H, arena.L, arena.K
         self.hd = D // H
@@ -479,9 +558,18 @@ class DecodeEngine:
         ctx = C.c_void_p()
         _lib.check(self.lib.ssrhip_lm_create(C.byref(d), C.byref(self._w), C.byref(b), C.byref(ctx)), "ssrhip_lm_create")
         self._ctx = ctx
+        if self.stream_w16:                       # before the first step is enqueued or captured; gives the pairing slot back
+            w16 = self.a.w16_struct()
+            _lib.check(self.lib.ssrhip_lm_set_w16(ctx, C.byref(w16)), "ssrhip_lm_set_w16")
         why = C.create_string_buffer(256)
         self.pairing = bool(self.lib.ssrhip_lm_pairing(ctx, why, 256))
         self.pairing_why = why.value.decode(errors="replace")
+
+    @property
+    def w16_launches_per_step(self) -> int:
+        """GEMV launches of the last enqueued decode step that ran a bf16-stream kernel (4 * layers + 2 when every family qualifies;
+        0 for an engine that streams fp32 weights or has not stepped yet)."""
+        return 0 if self._ctx is None else int(self.lib.ssrhip_lm_w16_launches(self._ctx))
 
     def close(self):
         if self._ctx is not None:

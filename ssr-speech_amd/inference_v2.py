@@ -53,6 +53,9 @@ EXTRA_FLAGS = [
     ("--mask_end", dict(type=float, default=None, help="edit span end in seconds (speech editing)")),
     ("--mask_spans", dict(type=str, default=None, help="speech editing with up to max_n_spans (3) edits: 'a-b,c-d[,e-f]' in seconds — what the "
                                                        "reference derives from the word alignment of the edited transcript (one span per edit)")),
+    ("--weight_dtype", dict(type=str, choices=["fp32", "bf16"], default="fp32",
+                            help="bf16: round the decoder's matrices once to bf16 and stream them as 2-byte weights in the decode step "
+                                 "(SSR_Speech.set_weight_dtype); fp32 (default): the checkpoint's weights as they are")),
     ("--prompt_end", dict(type=float, default=None, help="--tts: cut the prompt audio at this time in seconds (default --prompt_length)")),
     ("--phoneme_ids", dict(type=str, default=None, help="comma separated phoneme ids of the target transcript (skips espeak)")),
     ("--prompt_phoneme_ids", dict(type=str, default=None, help="comma separated phoneme ids of the prompt transcript")),
@@ -224,6 +227,7 @@ def main(argv=None):
     ckpt = torch.load(args.model_path, map_location="cpu", weights_only=False)      # inference_v2.py:197-204
     model = SSR_Speech(ckpt["config"])
     model.load_state_dict(ckpt["model"])
+    model.set_weight_dtype(args.weight_dtype)
     config = vars(model.args)
     phn2num = ckpt["phn2num"]
     model.to(device)

@@ -23,7 +23,7 @@ import torch.nn as nn
 from .. import _lib
 from .. import layout as LY
 from .. import score as SC
-from ..engine import DEFAULT_GROUP_ROWS, MAX_ROWS, DecodeEngine, DecodeKnobs, LMWeightsArena, TorchCpuNoiseFeed
+from ..engine import DEFAULT_GROUP_ROWS, MAX_ROWS, WEIGHT_DTYPES, DecodeEngine, DecodeKnobs, LMWeightsArena, TorchCpuNoiseFeed
 from ..weights import lm_param_specs
 
 
@@ -113,6 +113,7 @@ class SSR_Speech(nn.Module):
             _set_param(self, name, nn.Parameter(torch.zeros(shape, dtype=torch.float32), requires_grad=False))
         self._arena: Optional[LMWeightsArena] = None
         self._engines: Dict[tuple, DecodeEngine] = {}
+        self._weight_dtype = "fp32"
         self.debug_logits = False          # tests: keep the per-step post-edit logits
         self.page_order = None             # tests: permutation deciding which physical KV pages the allocator hands out first
         self.last_run: dict = {}
@@ -140,6 +141,21 @@ class SSR_Speech(nn.Module):
     def device(self):
         return next(self.parameters()).device
 
+    @property
+    def weight_dtype(self) -> str:
+        return self._weight_dtype
+
+    def set_weight_dtype(self, weight_dtype: str) -> None:
+        """"bf16": the decode step's six matrix families are rounded once to bf16 (engine.LMWeightsArena) and every path — `inference`,
+        `inference_stream`, `inference_batch`, `score`, `dp.*` — computes with the rounded values; engines of <= 4 rows stream them as
+        2-byte weights. "fp32" (the default) restores today's numbers bit for bit: the arena is rebuilt from `state_dict()`. Drops the
+        arena and the cached engines."""
+        if weight_dtype not in WEIGHT_DTYPES:
+            raise ValueError(f"weight_dtype {weight_dtype!r} not in {WEIGHT_DTYPES}")
+        if weight_dtype != self._weight_dtype:
+            self._weight_dtype = weight_dtype
+            self._invalidate()
+
     def forward(self, batch):
         raise NotImplementedError("SSR_Speech.forward (training loss, reference models/ssr.py:280-379) is outside the "
                                   "scope of ssr_speech_amd: only the inference hot path is implemented. SSR_Speech.score(batch) "
@@ -152,7 +168,7 @@ class SSR_Speech(nn.Module):
             raise RuntimeError("ssr_speech_amd.SSR_Speech.inference needs the model on a ROCm GPU (model.to('cuda')); "
                                "there is no CPU path in this package.")
         if self._arena is None:
-            self._arena = LMWeightsArena(self.args, self.state_dict(), dev)
+            self._arena = LMWeightsArena(self.args, self.state_dict(), dev, weight_dtype=self._weight_dtype)
         cap_seq = ((need_seq + 1023) // 1024) * 1024
         cap_steps = ((need_steps + 255) // 256) * 256
         if self._arena.ensure_positions(cap_seq):      # long text / long utterances: grow the position table (reference: extend_pe)
@@ -203,7 +219,7 @@ class SSR_Speech(nn.Module):
             raise RuntimeError("ssr_speech_amd.SSR_Speech.score needs the model on a ROCm GPU (model.to('cuda')); "
                                "there is no CPU path in this package.")
         if self._arena is None:
-            self._arena = LMWeightsArena(self.args, self.state_dict(), dev)
+            self._arena = LMWeightsArena(self.args, self.state_dict(), dev, weight_dtype=self._weight_dtype)
         a = self._arena
         B, K = len(items), a.K
         work = [it for it in items if it.n_scored > 0]                      # an item with y_len < 2 has no scored position

@@ -9,6 +9,10 @@ its minimum and median (box-to-box spread is 3-5 %, so only same-box alternating
 `@U` gives a variant its own utterance count (default --utts), so that step widths can be compared in one process, alternating:
   python tools/decode_ab.py --warmup 180 --steps 100 rows16@8: rows32@16:     (16 against 32 rows, timed around context ~520)
 Utterance u decodes bench.py's synth_inputs(u) prompt (config 4's input); codec-tokens/s = 4 codebooks x U / step time.
+A lower-case `weight_dtype=bf16` among a variant's knobs is not an environment variable: that variant runs on a second arena built with
+weight_dtype="bf16" (rounded masters + packed copies, 3.3 + 1.65 GB beside the fp32 one), e.g. the four arms of the bf16 weight stream:
+  python tools/decode_ab.py fp32_paired: fp32_unpaired:SSRHIP_GEMV_PAIR=0 bf16_masters:weight_dtype=bf16,SSRHIP_GEMV_W16=0 bf16_w16:weight_dtype=bf16
+(`tokens == <first variant>` is then expected to be False across dtypes and True between the two bf16 arms.)
 """
 import argparse
 import dataclasses
@@ -44,11 +48,14 @@ for v in a.variants:
     name, _, nu = name.partition("@")
     utts_of[name] = int(nu) if nu else a.utts
     variants.append((name, dict(kv.split("=", 1) for kv in kn.split(",") if kv)))
+dtype_of = {name: d.pop("weight_dtype", "fp32") for name, d in variants}
 all_knobs = sorted({k for _, d in variants for k in d})
 
 dev = torch.device("cuda", 0)
 args_lm = W.lm_args_830m()
-arena = LMWeightsArena(args_lm, W.lm_state_dict(args_lm, seed=0, device=dev), dev)
+sd = W.lm_state_dict(args_lm, seed=0, device=dev)
+arenas = {dt: LMWeightsArena(args_lm, sd, dev, weight_dtype=dt) for dt in sorted(set(dtype_of.values()))}
+del sd
 x, y, unc = synth_inputs(args_lm, 0)
 L, N = x.shape[1], y.shape[1]
 total = a.warmup + a.steps
@@ -61,14 +68,14 @@ for u in range(max(utts_of.values())):
 kn = DecodeKnobs(top_k=1 if a.greedy else 40, top_p=1.0 if a.greedy else 0.8, temperature=1.0, stop_repetition=2, cfg_coef=1.5, cfg_stride=5,
                  use_cfg=True, text_len=L, n_spans=num_task, seed=2024)
 
-res = {name: {"ms": [], "gemv": [], "attn": [], "sample": [], "tok": None} for name, _ in variants}
+res = {name: {"ms": [], "gemv": [], "attn": [], "sample": [], "tok": None, "w16": 0} for name, _ in variants}
 for rep in range(a.reps):
     for name, knobs in variants:
         for k in all_knobs:
             os.environ.pop(k, None)
         os.environ.update(knobs)
         U = utts_of[name]
-        eng = DecodeEngine(arena, U, True, ((L + T0 + total + 8 + 1023) // 1024) * 1024, ((total + 255) // 256) * 256)
+        eng = DecodeEngine(arenas[dtype_of[name]], U, True, ((L + T0 + total + 8 + 1023) // 1024) * 1024, ((total + 255) // 256) * 256)
         eng.start(text_rows[:2 * U], [cated] * U, [dataclasses.replace(kn, seed=2024 + u) for u in range(U)], noise=None)
         torch.cuda.synchronize()
         eng.decode(a.warmup)
@@ -80,6 +87,7 @@ for rep in range(a.reps):
         n_done = int(eng.states()[0].n_steps)
         tok = eng.generated[0, :n_done].cpu().numpy().copy()
         r = res[name]
+        r["w16"] = eng.w16_launches_per_step
         r["ms"].append(ms)
         r["gemv"].append(eng.time_category("gemv", 50)[0])
         r["attn"].append(eng.time_category("attn", 50)[0])
@@ -101,4 +109,4 @@ for name, knobs in variants:
     print(f"{name:14s} {U:2d} utts x CFG = {2 * U:2d} rows  tok/s {4 * U / (statistics.median(r['ms']) * 1e-3):9.1f}  "
           f"ms/step min {min(r['ms']):.4f} med {statistics.median(r['ms']):.4f}  all {' '.join(f'{v:.4f}' for v in r['ms'])} | "
           f"gemv {min(r['gemv']):.3f} x {r['launches']['gemv']} attn {min(r['attn']):.3f} x {r['launches']['attn']} "
-          f"sample {min(r['sample']):.3f} x {r['launches']['sample']} us{same}   [{' '.join(f'{k}={v}' for k, v in knobs.items()) or 'defaults'}]")
+          f"sample {min(r['sample']):.3f} x {r['launches']['sample']} us{same}   [{dtype_of[name]}, {r['w16']} w16 launches; {' '.join(f'{k}={v}' for k, v in knobs.items()) or 'defaults'}]")

@@ -3,7 +3,9 @@
 `inference_one_sample` and of `inference_one_sample_stream`, then 3 alternating rounds of the two with the same seeds. Reports the
 host time to the first yielded chunk (after a stream synchronize on it), that chunk's length, both paths' total wall time, and the
 codec launches per stage-2 window. One JSON line on stdout; `--out FILE` also writes it there.
-Usage: python tools/stream_latency.py [--out profiles/stream_latency_830m.json]"""
+`--weight_dtype bf16` measures the bf16 weight stream (`SSR_Speech.set_weight_dtype`); the output also carries the real-time factor
+(wall time / seconds of audio) of both paths.
+Usage: python tools/stream_latency.py [--weight_dtype bf16] [--out profiles/stream_latency_830m.json]"""
 import argparse
 import json
 import os
@@ -32,6 +34,7 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--weight_dtype", choices=["fp32", "bf16"], default="fp32")
     opt = ap.parse_args(argv)
     dev = torch.device("cuda")
     args_lm = W.lm_args_830m()
@@ -44,6 +47,7 @@ def main(argv=None):
     model.load_state_dict({k: v.cpu() for k, v in sd.items()})
     del sd
     model = model.to(dev).eval()
+    model.set_weight_dtype(opt.weight_dtype)
     ccfg = W.codec_config_full()
     tok = AudioTokenizer(device=dev, config=ccfg, state_dict=W.codec_state_dict(ccfg, seed=0))
     g = torch.Generator().manual_seed(7)
@@ -73,7 +77,7 @@ def main(argv=None):
         t1 = time.perf_counter()
         lr = model.last_run
         return wav, dict(total_ms=1000 * (t1 - t0), first_16_frames_ms=1000 * (lr["t_first_chunk"] - t0), steps=int(lr["steps"]),
-                         lm_ms=1000 * (lr["t_end"] - lr["t_start"]))
+                         lm_ms=1000 * (lr["t_end"] - lr["t_start"]), audio_s=wav.shape[-1] / 16000.0)
 
     def streamed(seed):
         torch.manual_seed(seed)
@@ -92,7 +96,7 @@ def main(argv=None):
         wav = torch.cat(chunks, -1)
         return wav, dict(total_ms=1000 * (t1 - t0), first_chunk_ms=first_ms, first_chunk_samples=int(chunks[0].shape[-1]),
                          first_16_frames_ms=1000 * (lr["t_first_chunk"] - t0), chunks=len(chunks), steps=int(lr["steps"]),
-                         lm_ms=1000 * (lr["t_end"] - lr["t_start"]), codec_launches=codec.n_launches - n0)
+                         lm_ms=1000 * (lr["t_end"] - lr["t_start"]), codec_launches=codec.n_launches - n0, audio_s=wav.shape[-1] / 16000.0)
 
     one_pass(1)
     streamed(1)
@@ -136,8 +140,11 @@ def main(argv=None):
     med = lambda xs: sorted(xs)[len(xs) // 2]
     out = {
         "tool": "tools/stream_latency.py", "shape": "830M LM, full codec (8,5,4,2), 160-frame demo prompt, 67 phonemes, sampled, CFG stride 5",
+        "weight_dtype": opt.weight_dtype,
         "rounds": rounds,
         "median": {
+            "one_pass_rtf": round(med([r["one_pass"]["total_ms"] / 1000 / r["one_pass"]["audio_s"] for r in rounds]), 5),
+            "stream_rtf": round(med([r["stream"]["total_ms"] / 1000 / r["stream"]["audio_s"] for r in rounds]), 5),
             "one_pass_total_ms": round(med([r["one_pass"]["total_ms"] for r in rounds]), 2),
             "stream_total_ms": round(med([r["stream"]["total_ms"] for r in rounds]), 2),
             "stream_first_chunk_ms": round(med([r["stream"]["first_chunk_ms"] for r in rounds]), 2),

@@ -1,0 +1,122 @@
+"""Per-launch time of the decode step's GEMV shapes, fp32 weights (`ssrhip_gemv`) against packed bf16 weights (`ssrhip_gemv_w16`), the
+way the step runs them: CHAIN launches of one shape are captured into one graph on one stream (so they follow each other like the
+dependent launches of a step), the graph is replayed and the elapsed time divided by the launches. Every launch of a chain streams its own
+matrix (the chain's weights exceed the 256 MB of last-level cache several times over), activations stay in L2 as in the step.
+Beside each figure: the project's chain floor `2.6 us + bytes / 7.3 TB/s` (DESIGN.md Part I.5) for that launch's weight bytes.
+
+    python tools/w16_launch_bench.py [--rows 2] [--chain 16] [--replays 30] [--out FILE]
+    SSRHIP_GEMV_W16_DEPTH=4 python tools/w16_launch_bench.py        (the ring-of-4 form of the straight-line kernel)
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch  # noqa: E402
+
+import ssr_speech_amd  # noqa: E402,F401
+from ssr_speech_amd import _lib  # noqa: E402
+from ssr_speech_amd.engine import to_w16_order  # noqa: E402
+
+# name, G, N, K, prologue, activation, epilogue: the six launches of the 830M step
+SHAPES = [
+    ("ln1+qkv", 1, 6144, 2048, _lib.PRO_LAYERNORM, _lib.ACT_NONE, _lib.EPI_QKV_APPEND),
+    ("merge+out", 1, 2048, 2048, _lib.PRO_ATTN_COMBINE, _lib.ACT_NONE, _lib.EPI_RESIDUAL),
+    ("ln2+ffn1", 1, 8192, 2048, _lib.PRO_LAYERNORM, _lib.ACT_RELU, _lib.EPI_STORE),
+    ("ffn2", 1, 2048, 8192, _lib.PRO_NONE, _lib.ACT_NONE, _lib.EPI_RESIDUAL),
+    ("lnf+head1", 1, 4096, 2048, _lib.PRO_LAYERNORM, _lib.ACT_GELU_ERF, _lib.EPI_STORE),
+    ("head2", 4, 2056, 1024, _lib.PRO_NONE, _lib.ACT_NONE, _lib.EPI_STORE),
+]
+H, HD, MAX_PAGES = 16, 128, 6
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=2, choices=[1, 2, 4])
+    ap.add_argument("--chain", type=int, default=16)
+    ap.add_argument("--replays", type=int, default=30)
+    ap.add_argument("--out", default=None)
+    opt = ap.parse_args(argv)
+    L = _lib.lib()
+    B, dev = opt.rows, torch.device("cuda")
+    g = torch.Generator(device="cuda").manual_seed(1)
+    rows = []
+    for name, G, N, K, pro, act, epi in SHAPES:
+        ny = K if epi == _lib.EPI_QKV_APPEND else G * N
+        masters = [(torch.randn(G, N, K, device=dev, generator=g) / K ** 0.5).to(torch.bfloat16).float() for _ in range(opt.chain)]
+        packed = [to_w16_order(m) for m in masters]
+        bias = torch.randn(G, N, device=dev, generator=g)
+        x = torch.randn(B, G * K, device=dev, generator=g)
+        y = torch.zeros(B, ny, device=dev)
+        pool = torch.zeros(B * MAX_PAGES + 1, 1, 2, H, _lib.PAGE, HD, device=dev)
+        table = torch.arange(B * MAX_PAGES, dtype=torch.int32, device=dev).view(B, MAX_PAGES)
+        pos = torch.full((B,), 600, dtype=torch.int32, device=dev)
+        lens = torch.full((B,), 601, dtype=torch.int32, device=dev)
+        part_o = torch.randn(B, H, MAX_PAGES, HD, device=dev, generator=g)
+        part_ml = torch.rand(B, H, MAX_PAGES, 2, device=dev, generator=g) + 0.5
+
+        def args_of(i):
+            a = _lib.GemvArgs()
+            a.W, a.bias, a.x, a.y = masters[i].data_ptr(), bias.data_ptr(), x.data_ptr(), y.data_ptr()
+            a.B, a.N, a.K, a.groups, a.x_stride, a.y_stride = B, N, K, G, G * K, ny
+            a.pro, a.act, a.epi, a.ln_eps = pro, act, epi, 1e-5
+            if epi == _lib.EPI_QKV_APPEND:
+                a.kv = _lib.KV(pool.data_ptr(), table.data_ptr(), MAX_PAGES, 1, H, HD)
+                a.layer, a.kv_pos = 0, pos.data_ptr()
+            if pro == _lib.PRO_ATTN_COMBINE:
+                a.x = 0
+                a.part_o, a.part_ml, a.max_splits, a.row_len = part_o.data_ptr(), part_ml.data_ptr(), MAX_PAGES, lens.data_ptr()
+                a.kv = _lib.KV(0, 0, MAX_PAGES, 1, H, HD)
+            return a
+
+        us = {}
+        for form in ("fp32", "w16"):
+            def chain():
+                for i in range(opt.chain):
+                    a = args_of(i)
+                    if form == "w16":
+                        rc = L.ssrhip_gemv_w16(C.byref(a), packed[i].data_ptr(), _lib.stream_ptr())
+                        assert rc == 0, (name, rc, L.ssrhip_last_error())
+                    else:
+                        _lib.check(L.ssrhip_gemv(C.byref(a), _lib.stream_ptr()))
+            side = torch.cuda.Stream()
+            with torch.cuda.stream(side):
+                chain()                                           # module load, first-launch costs
+            side.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, stream=side):
+                chain()
+            for _ in range(3):
+                graph.replay()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            best = None
+            for _ in range(3):
+                e0.record()
+                for _ in range(opt.replays):
+                    graph.replay()
+                e1.record()
+                e1.synchronize()
+                t = 1000.0 * e0.elapsed_time(e1) / (opt.replays * opt.chain)
+                best = t if best is None else min(best, t)
+            us[form] = best
+            del graph
+        floor = lambda nbytes: 2.6 + nbytes / 7.3e6                # us: 7.3 TB/s = 7.3e6 bytes per us
+        nw = G * N * K
+        rows.append(dict(shape=name, G=G, N=N, K=K, rows=B, fp32_us=round(us["fp32"], 2), w16_us=round(us["w16"], 2),
+                         fp32_floor_us=round(floor(4 * nw), 2), w16_floor_us=round(floor(2 * nw), 2),
+                         fp32_TBps=round(4 * nw / us["fp32"] / 1e6, 2), w16_TBps=round(2 * nw / us["w16"] / 1e6, 2)))
+        print(json.dumps(rows[-1]), flush=True)
+        del masters, packed
+        torch.cuda.empty_cache()
+    out = dict(tool="tools/w16_launch_bench.py", chain=opt.chain, replays=opt.replays, depth_knob=os.environ.get("SSRHIP_GEMV_W16_DEPTH", "unset"), shapes=rows)
+    if opt.out:
+        with open(opt.out, "w") as f:
+            f.write(json.dumps(out, indent=1) + "\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
