@@ -120,6 +120,28 @@ int ssrhip_gemv(const ssrhip_gemv_args* a, ssrhip_stream_t stream);
 int ssrhip_gemv_w16(const ssrhip_gemv_args* a, const uint16_t* W16, ssrhip_stream_t stream);
 int ssrhip_gemv_w16_applicable(const ssrhip_gemv_args* a);
 
+/* Packed bf16 weight layout of the bf16 weight stream at 5..16 rows (csrc/gemv_mfma_w16.hip; K % 64 == 0): the streaming order
+ * SSRHIP_WTILED_INDEX in 2-byte weights. Rows in 8-row units (the last unit zero-padded), K in QUADS of four 16-float k-steps. With
+ *   n = 8u + c,  k = 64q + 16j + 4ks + e,  h = j % 2,  g = j / 2
+ * the uint16 index of W[n][k] is ((u*(K/64) + q)*2 + h)*256 + (ks*8 + c)*8 + g*4 + e: the 512-byte block (u, q, h) holds, at 16-byte piece
+ * ks*8 + c, the four weights of k-step 4q + h followed by the four of k-step 4q + h + 2. The layout does not depend on the kernel form the
+ * launch plan picks: the plain form (lanes c >= 8 = the next unit) reads blocks h = 0 and h = 1 of a quad as two wave-level loads of two
+ * 512-byte runs each, the k-step-pair form (lanes c >= 8 = the other k-step of a pair) reads both blocks of (u, q) as ONE contiguous KiB.
+ * A group's matrix takes ceil(N/8)*8*K uint16; groups follow each other. Each uint16 is the upper half of the (rounded) fp32 master. */
+#define SSRHIP_WT16_INDEX(n, k, K) \
+  (((((size_t)(n) / 8) * ((size_t)(K) / 64) + (size_t)(k) / 64) * 2 + (((k) % 64) / 16) % 2) * 256 + ((((k) % 16) / 4) * 8 + (n) % 8) * 8 + ((((k) % 64) / 16) / 2) * 4 + (k) % 4)
+
+/* ssrhip_gemv(a) for 5..16 rows streaming the PACKED bf16 copy `Wt16` (SSRHIP_WT16_INDEX) of the weights instead of a->W. `a` is the call as
+ * ssrhip_gemv takes it, with a->w_tiled = 1 and a->W = the fp32 streaming-order copy, which must hold exactly the bf16-representable values
+ * of Wt16 (the rounded master); the result is then BIT-IDENTICAL to ssrhip_gemv(a): the same launch plan, the weights widened in registers
+ * (a 16-bit shift, exact), every MFMA and every sum in the order of the fp32 kernel.
+ *   returns 0 = launched, 1 = `a` does not qualify and NOTHING was launched (call ssrhip_gemv(a)), < 0 = contract error (decided before
+ *   any HIP call). Qualifies: 5 <= B <= 16, w_tiled == 1, K % 64 == 0, the arguments ssrhip_gemv accepts at these rows, and the
+ *   rows-per-workgroup kernels selected (SSRHIP_GEMVM_V != 1). SSRHIP_GEMVM_WPC / _NOPAIR act as on ssrhip_gemv; the fp32 unit's opt-in
+ *   experiments (SSRHIP_GEMVM_EDGE, _WFIRST, _DEP8) are ignored — they are bit-identical to the default. */
+int ssrhip_gemv_wt16(const ssrhip_gemv_args* a, const uint16_t* Wt16, ssrhip_stream_t stream);
+int ssrhip_gemv_wt16_applicable(const ssrhip_gemv_args* a);
+
 /* Two consecutive launches of the 2-row decode step as ONE: `a` = a GEMV with the residual epilogue and `b` = the LayerNorm + Linear that
  * reads a's output, with the all-to-all edge between them inside the launch (csrc/gemv.hip gemv_pair_kernel / gemv_pair_merge_kernel:
  * tagged 8-byte granules, write-through stores, one gather round trip). Two forms:
@@ -460,6 +482,14 @@ typedef struct ssrhip_lm_w16 {
 int ssrhip_lm_set_w16(ssrhip_lm* lm, const ssrhip_lm_w16* w16);
 /* how many GEMV launches of the last enqueued (or captured) decode step ran a bf16-stream kernel (4 * n_layer + 2 when every family qualifies) */
 int ssrhip_lm_w16_launches(const ssrhip_lm* lm);
+/* The same for the 5..16-row decode step: the record's pointers are SSRHIP_WT16_INDEX copies of the six families (NULL field / NULL entry:
+ * that family streams the fp32 streaming-order copy of its master). From now on every GEMV launch of the step tries ssrhip_gemv_wt16 first
+ * and falls back to ssrhip_gemv; same tokens, bit for bit; the step stays one captured graph. Refused (< 0) for engines of <= 4 rows (they
+ * have ssrhip_lm_set_w16), of more than 16 rows, engines already captured and engines created without the fp32 streaming-order copies. */
+int ssrhip_lm_set_wt16(ssrhip_lm* lm, const ssrhip_lm_w16* wt16);
+/* how many GEMV launches of the last enqueued (or captured) decode step ran a kernel of csrc/gemv_mfma_w16.hip (4 * n_layer + 2 when every
+ * family qualifies); a counter of its own: ssrhip_lm_w16_launches stays 0 for these engines */
+int ssrhip_lm_wt16_launches(const ssrhip_lm* lm);
 /* enqueue `n_steps` decode steps (graph replays when use_graph!=0) */
 int ssrhip_lm_decode(ssrhip_lm* lm, int32_t n_steps, int32_t use_graph, ssrhip_stream_t stream);
 /* prefill R rows ([text || audio] of every sequence, flattened): fills the cache for all layers.

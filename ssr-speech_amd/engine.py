@@ -70,13 +70,46 @@ def to_w16_order(W: torch.Tensor) -> torch.Tensor:
     return Wb.permute(*range(n), n, n + 1, n + 2, n + 4, n + 3, n + 5).contiguous().view(torch.int16).reshape(*lead, N, K)
 
 
+def to_wt16_order(W: torch.Tensor) -> torch.Tensor:
+    """[.., N, K] (K % 64 == 0) -> the packed bf16 streaming order of the 5..16-row bf16 weight stream (include/ssrhip.h SSRHIP_WT16_INDEX)
+    as an int16 tensor [.., ceil(N/8)*8, K]: rows in 8-row units (zero-padded), K in quads of four k-steps; the 512-byte block (unit, quad,
+    h) holds at 16-byte piece ks*8 + c the four weights of k-step 4q + h followed by the four of k-step 4q + h + 2. Values are rounded to
+    bf16 (nearest even); already rounded masters pack exactly."""
+    *lead, N, K = W.shape
+    assert K % 64 == 0, K
+    U = (N + 7) // 8
+    if U * 8 != N:
+        W = torch.cat([W, W.new_zeros(*lead, U * 8 - N, K)], dim=-2)
+    Wb = W.to(torch.bfloat16).reshape(*lead, U, 8, K // 64, 2, 2, 4, 4)          # [u][c][q][g][h][ks][e]
+    n = len(lead)
+    return Wb.permute(*range(n), n, n + 2, n + 4, n + 5, n + 1, n + 3, n + 6).contiguous().view(torch.int16).reshape(*lead, U * 8, K)
+
+
+def from_wt16_order(P: torch.Tensor, N: int) -> torch.Tensor:
+    """Inverse of `to_wt16_order`: the packed int16 tensor [.., ceil(N/8)*8, K] -> the fp32 values [.., N, K] it stores (exact: << 16)."""
+    *lead, NP, K = P.shape
+    U = NP // 8
+    n = len(lead)
+    Wb = P.view(torch.bfloat16).reshape(*lead, U, K // 64, 2, 4, 8, 2, 4)         # [u][q][h][ks][c][g][e]
+    Wb = Wb.permute(*range(n), n, n + 4, n + 1, n + 5, n + 2, n + 3, n + 6).reshape(*lead, NP, K)
+    return Wb[..., :N, :].to(torch.float32).contiguous()
+
+
 W16_FAMILIES = ("in_proj", "out_proj", "ffn1", "ffn2")      # per layer; plus head1 and head2
 WEIGHT_DTYPES = ("fp32", "bf16")
+# What an unset SSRHIP_GEMVM_W16 means for a 5..16-row engine of a bf16 arena (DecodeEngine stream_wt16=None): "1" = stream the
+# SSRHIP_WT16_INDEX copies, "0" = stream the fp32 streaming-order masters. Decided by the measurement in DESIGN.md Part I.11.
+WT16_DEFAULT = "0"
 
 
 def w16_streamable(K: int) -> bool:
     """Can a matrix with this inner dimension have a packed copy (the shapes ssrhip_gemv_w16 takes)?"""
     return K % 1024 == 0 and K // 1024 in (1, 2, 4, 8)
+
+
+def wt16_streamable(K: int) -> bool:
+    """Can a matrix with this inner dimension have a SSRHIP_WT16_INDEX copy (whole quads of four k-steps)?"""
+    return K > 0 and K % 64 == 0
 
 
 class LMWeightsArena:
@@ -175,6 +208,35 @@ class LMWeightsArena:
         w.head1_w16, w.head2_w16 = _lib.ptr(self.head1_w16), _lib.ptr(self.head2_w16)
         return w
 
+    def ensure_wt16_copies(self) -> bool:
+        """Packed bf16 streaming-order copies (`to_wt16_order`) of the six matrix families for the 5..16-row decode step of a bf16 arena
+        (+2 bytes per weight = +1.65 GB at 830M beside the fp32 streaming copies, built once on first use). A family whose inner dimension
+        is no multiple of 64 (`wt16_streamable`) gets none and streams its fp32 streaming-order copy. Returns True when created now."""
+        if self.weight_dtype != "bf16":
+            raise ValueError("packed bf16 copies need an arena built with weight_dtype='bf16' (the masters must hold the rounded values)")
+        if getattr(self, "_wt16_ready", False):
+            return False
+        pack = lambda Wm: to_wt16_order(Wm) if wt16_streamable(Wm.shape[-1]) else None
+        for lay in self.layers:
+            for name in W16_FAMILIES:
+                lay[name + "_wt16"] = pack(lay[name + "_w"])
+        self.head1_wt16, self.head2_wt16 = pack(self.head1_w), pack(self.head2_w)
+        self._wt16_ready = True
+        self.generation += 1
+        return True
+
+    def wt16_struct(self):
+        """ssrhip_lm_w16 record of the SSRHIP_WT16_INDEX copies for ssrhip_lm_set_wt16 (NULL where a family has none)."""
+        w = _lib.LMW16()
+        self._wt16_arrays = {}
+        for name in W16_FAMILIES:
+            if all(lay[name + "_wt16"] is not None for lay in self.layers):
+                arr = (C.c_void_p * self.L)(*[lay[name + "_wt16"].data_ptr() for lay in self.layers])
+                self._wt16_arrays[name] = arr
+                setattr(w, name + "_w16", C.cast(arr, C.POINTER(C.c_void_p)))
+        w.head1_w16, w.head2_w16 = _lib.ptr(self.head1_wt16), _lib.ptr(self.head2_wt16)
+        return w
+
     def ensure_streaming_copies(self) -> bool:
         """Second copy of the six matrices of a decode step in the streaming order of the 5..16-row GEMV (one-time repack; used
         only by engines with more than 4 rows, +3.3 GB at 830M). Returns True when the copies were created now."""
@@ -240,7 +302,7 @@ class LMWeightsArena:
         """Algorithmic weight bytes one decode step must stream."""
         n = 0
         for lay in self.layers:
-            n += sum(t.numel() for k, t in lay.items() if not k.endswith(("_wt", "_ws", "_w16")))     # incl. the (now constant) LayerNorm vectors, as SURVEY §8d counts them
+            n += sum(t.numel() for k, t in lay.items() if not k.endswith(("_wt", "_ws", "_w16", "_wt16")))     # incl. the (now constant) LayerNorm vectors, as SURVEY §8d counts them
         n += self.lnf_w.numel() + self.lnf_b.numel()
         n += self.head1_w.numel() + self.head1_b.numel() + self.head2_w.numel() + self.head2_b.numel()
         n += (self.K + 1) * self.D  # K embedding rows + one pe row
@@ -248,6 +310,9 @@ class LMWeightsArena:
         if getattr(self, "_w16_ready", False):
             half = sum(lay[name + "_w16"].numel() for lay in self.layers for name in W16_FAMILIES if lay[name + "_w16"] is not None)
             half += sum(t.numel() for t in (self.head1_w16, self.head2_w16) if t is not None)
+        elif getattr(self, "_wt16_ready", False):   # the 5..16-row copies (their zero-padded rows are not weights)
+            half = sum(lay[name + "_w"].numel() for lay in self.layers for name in W16_FAMILIES if lay[name + "_wt16"] is not None)
+            half += sum(m.numel() for m, t in ((self.head1_w, self.head1_wt16), (self.head2_w, self.head2_wt16)) if t is not None)
         return 4 * n - 2 * half
 
     def c_struct(self):
@@ -445,13 +510,16 @@ class DecodeEngine:
 
     def __init__(self, arena: LMWeightsArena, n_utt: int, use_cfg: bool, max_seq: int, max_steps: int, debug_logits: bool = False,
                  pool_pages: Optional[int] = None, page_order: Optional[Sequence[int]] = None, pair_mode: int = 0,
-                 stream_w16: Optional[bool] = None):
+                 stream_w16: Optional[bool] = None, stream_wt16: Optional[bool] = None):
         """max_seq: longest sequence (text + audio positions) any ONE row may reach; pool_pages: physical KV pages shared by all
         rows (default rows x pages-per-row, the no-sharing worst case; a batch of short and long utterances needs only the sum
         of their own page counts). pair_mode (2-row engines; include/ssrhip.h ssrhip_lm_buffers): 0 = pair launches if this engine
         gets its device's pairing slot, 1 = never, 2 = always (tests of the give-up path). stream_w16: the decode step streams the arena's
         packed bf16 copies (include/ssrhip.h ssrhip_lm_set_w16; needs a bf16 arena and <= 4 rows, steps unpaired); None = on when the arena
-        is bf16, the engine has <= 4 rows and `SSRHIP_GEMV_W16` (read here) does not start with '0'."""
+        is bf16, the engine has <= 4 rows and `SSRHIP_GEMV_W16` (read here) does not start with '0'. stream_wt16: the same for the 5..16-row
+        matrix-core step (ssrhip_lm_set_wt16: SSRHIP_WT16_INDEX copies beside the fp32 streaming-order copies, which stay the fallback);
+        None = on when the arena is bf16, the engine has 5..16 rows and `SSRHIP_GEMVM_W16` (read here; unset = WT16_DEFAULT) does not
+        start with '0'."""
         self.lib = _lib.lib()
         self.a = arena
         dev = arena.device
@@ -469,6 +537,15 @@ class DecodeEngine:
         elif stream_w16 and arena.weight_dtype != "bf16":
             raise ValueError("stream_w16 needs an arena built with weight_dtype='bf16'")
         self.stream_w16 = bool(stream_w16)
+        if stream_wt16 is None:
+            stream_wt16 = arena.weight_dtype == "bf16" and 5 <= self.B <= 16 and os.environ.get("SSRHIP_GEMVM_W16", WT16_DEFAULT)[:1] != "0"
+        elif stream_wt16 and self.B <= 4:
+            raise ValueError(f"stream_wt16 is the bf16 weight stream of the 5..16-row step; an engine of {self.B} rows takes stream_w16")
+        elif stream_wt16 and self.B > 16:
+            raise ValueError(f"stream_wt16: the bf16 weight stream of the matrix-core step exists for 5..16 rows only (this engine has {self.B} rows)")
+        elif stream_wt16 and arena.weight_dtype != "bf16":
+            raise ValueError("stream_wt16 needs an arena built with weight_dtype='bf16'")
+        self.stream_wt16 = bool(stream_wt16)
         self.max_pages = (max_seq + PAGE - 1) // PAGE
         self.max_seq = self.max_pages * PAGE
         arena.ensure_positions(self.max_seq)      # every text / audio position of a row is < its sequence capacity
@@ -477,6 +554,8 @@ class DecodeEngine:
         arena.ensure_split_planes()               # the prefill GEMMs run on the bf16 matrix cores with exactly split operands
         if self.stream_w16:
             arena.ensure_w16_copies()             # the <= 4-row step streams packed 2-byte weights
+        if self.stream_wt16:
+            arena.ensure_wt16_copies()            # the 5..16-row step streams packed 2-byte weights in streaming order
         self.max_steps = max_steps
         D, H, L, K = arena.D, arena.H, arena.L, arena.K
         self.hd = D // H
@@ -561,6 +640,9 @@ class DecodeEngine:
         if self.stream_w16:                       # before the first step is enqueued or captured; gives the pairing slot back
             w16 = self.a.w16_struct()
             _lib.check(self.lib.ssrhip_lm_set_w16(ctx, C.byref(w16)), "ssrhip_lm_set_w16")
+        if self.stream_wt16:                      # before the first step is enqueued or captured
+            wt16 = self.a.wt16_struct()
+            _lib.check(self.lib.ssrhip_lm_set_wt16(ctx, C.byref(wt16)), "ssrhip_lm_set_wt16")
         why = C.create_string_buffer(256)
         self.pairing = bool(self.lib.ssrhip_lm_pairing(ctx, why, 256))
         self.pairing_why = why.value.decode(errors="replace")
@@ -570,6 +652,12 @@ class DecodeEngine:
         """GEMV launches of the last enqueued decode step that ran a bf16-stream kernel (4 * layers + 2 when every family qualifies;
         0 for an engine that streams fp32 weights or has not stepped yet)."""
         return 0 if self._ctx is None else int(self.lib.ssrhip_lm_w16_launches(self._ctx))
+
+    @property
+    def wt16_launches_per_step(self) -> int:
+        """GEMV launches of the last enqueued decode step that ran a kernel of the 5..16-row bf16 weight stream (4 * layers + 2 when every
+        family qualifies; 0 for an engine that streams fp32 weights or has not stepped yet)."""
+        return 0 if self._ctx is None else int(self.lib.ssrhip_lm_wt16_launches(self._ctx))
 
     def close(self):
         if self._ctx is not None:

@@ -4,6 +4,10 @@ ONE process. Prints one JSON line: per group the decode wall time of every round
 of the two groupings are identical. The first pass of each grouping (engine build, graph capture) is untimed.
 
   python tools/dp64_group_ab.py [--reps 2] [--out profiles/xxx.json]
+`--wt16` compares, at ONE grouping (the first of --groups, default 8 = 16 rows), a bf16 model whose 16-row engine streams the rounded fp32
+masters (SSRHIP_GEMVM_W16=0) against one that streams the packed bf16 streaming-order copies (SSRHIP_GEMVM_W16=1; DESIGN.md Part I.11):
+the arena and the engine are rebuilt for every arm of every round (the switch is read when an engine is built), one untimed pass, one timed.
+  python tools/dp64_group_ab.py --wt16 --reps 2 --out profiles/wt16_dp64_group8.json
 """
 import argparse
 import json
@@ -24,6 +28,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--reps", type=int, default=2)
 ap.add_argument("--groups", default="8,16")
 ap.add_argument("--out", default=None)
+ap.add_argument("--wt16", action="store_true", help="bf16 model, group 8: fp32 masters against the packed bf16 stream of the 16-row step")
 a = ap.parse_args()
 
 dev = torch.device("cuda", 0)
@@ -39,6 +44,42 @@ for i in range(64):
                  "mask_interval": torch.LongTensor([[[150, 150]]])})
 kw = dict(top_k=1, top_p=1.0, temperature=1.0, stop_repetition=2, cfg_coef=1.5, cfg_stride=5, aug_text=True)
 groups = [int(g) for g in a.groups.split(",")]
+
+if a.wt16:
+    g = groups[0]
+    arms = (("bf16_masters", "0"), ("bf16_wt16", "1"))
+    res = {name: {"decode_ms": [], "tokens": None, "wt16_launches": 0} for name, _ in arms}
+    for rep in range(a.reps):
+        for name, sw in arms:
+            os.environ["SSRHIP_GEMVM_W16"] = sw
+            model.set_weight_dtype("fp32")
+            model.set_weight_dtype("bf16")              # drops the arena and the engines: the next call builds them under this switch
+            dp.generate(model, utts[:2 * g], seed=0, group=g, **kw)      # untimed: arena, engine, graph capture
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            toks, _ = dp.generate(model, utts, seed=0, group=g, **kw)
+            torch.cuda.synchronize()
+            res[name]["decode_ms"].append(1000 * (time.perf_counter() - t0))
+            res[name]["wt16_launches"] = next(iter(model._engines.values())).wt16_launches_per_step
+            if res[name]["tokens"] is None:
+                res[name]["tokens"] = [t.cpu() for t in toks]
+    ref = res["bf16_masters"]["tokens"]
+    n_new = sum(int(t.shape[-1]) - 150 for t in ref)
+    out = {"workload": "bench.py dp64 input on one GPU through dp.generate (decode only, no codec), bf16 weights", "group": g,
+           "rows_per_engine": 2 * g, "new_frames_total": n_new, "reps": a.reps}
+    for name, _ in arms:
+        best = min(res[name]["decode_ms"])
+        out[name] = {"decode_ms": [round(v, 1) for v in res[name]["decode_ms"]], "codec_tokens_per_s": round(4 * n_new / (best * 1e-3), 1),
+                     "wt16_launches_per_step": res[name]["wt16_launches"]}
+    out["tokens_identical"] = all(torch.equal(x, y) for x, y in zip(res["bf16_wt16"]["tokens"], ref))
+    assert out["tokens_identical"], "the two bf16 arms must choose the same tokens"
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    sys.exit(0)
 
 res = {g: {"decode_ms": [], "tokens": None} for g in groups}
 for g in groups:                                   # untimed: engine, graph capture

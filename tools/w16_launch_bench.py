@@ -6,6 +6,10 @@ Beside each figure: the project's chain floor `2.6 us + bytes / 7.3 TB/s` (DESIG
 
     python tools/w16_launch_bench.py [--rows 2] [--chain 16] [--replays 30] [--out FILE]
     SSRHIP_GEMV_W16_DEPTH=4 python tools/w16_launch_bench.py        (the ring-of-4 form of the straight-line kernel)
+`--rows 5..16` measures the matrix-core step's launches instead (DESIGN.md Part I.11): the fp32 streaming-order copy (`ssrhip_gemv`,
+w_tiled) against the packed bf16 streaming-order copy (`ssrhip_gemv_wt16`) with 8 loads in flight per wave (the default) and with 16
+(`SSRHIP_GEMVM_W16_DEPTH=16`, set by the tool for that arm), activations in the tiled layout as the step keeps them.
+    python tools/w16_launch_bench.py --rows 16 --out profiles/wt16_launch_bench_rows16.json
 """
 import argparse
 import ctypes as C
@@ -19,7 +23,7 @@ import torch  # noqa: E402
 
 import ssr_speech_amd  # noqa: E402,F401
 from ssr_speech_amd import _lib  # noqa: E402
-from ssr_speech_amd.engine import to_w16_order  # noqa: E402
+from ssr_speech_amd.engine import to_streaming_order, to_w16_order, to_wt16_order  # noqa: E402
 
 # name, G, N, K, prologue, activation, epilogue: the six launches of the 830M step
 SHAPES = [
@@ -35,7 +39,7 @@ H, HD, MAX_PAGES = 16, 128, 6
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--rows", type=int, default=2, choices=[1, 2, 4])
+    ap.add_argument("--rows", type=int, default=2, choices=[1, 2, 4] + list(range(5, 17)))
     ap.add_argument("--chain", type=int, default=16)
     ap.add_argument("--replays", type=int, default=30)
     ap.add_argument("--out", default=None)
@@ -44,13 +48,19 @@ def main(argv=None):
     B, dev = opt.rows, torch.device("cuda")
     g = torch.Generator(device="cuda").manual_seed(1)
     rows = []
+    mc = B > 4                                                    # the matrix-core step: tiled activations, streaming-order weights
+    forms = ("fp32", "wt16", "wt16_depth16") if mc else ("fp32", "w16")
     for name, G, N, K, pro, act, epi in SHAPES:
+        if mc and pro == _lib.PRO_ATTN_COMBINE:
+            pro = _lib.PRO_NONE                                   # at 5..32 rows the split-KV merge is a launch of its own
         ny = K if epi == _lib.EPI_QKV_APPEND else G * N
         masters = [(torch.randn(G, N, K, device=dev, generator=g) / K ** 0.5).to(torch.bfloat16).float() for _ in range(opt.chain)]
-        packed = [to_w16_order(m) for m in masters]
+        packed = [to_wt16_order(m) if mc else to_w16_order(m) for m in masters]
+        if mc:
+            masters = [to_streaming_order(m) for m in masters]
         bias = torch.randn(G, N, device=dev, generator=g)
-        x = torch.randn(B, G * K, device=dev, generator=g)
-        y = torch.zeros(B, ny, device=dev)
+        x = torch.randn(16 if mc else B, G * K, device=dev, generator=g)       # (tiled: 16 columns, any values)
+        y = torch.zeros(16 if mc else B, ny, device=dev)
         pool = torch.zeros(B * MAX_PAGES + 1, 1, 2, H, _lib.PAGE, HD, device=dev)
         table = torch.arange(B * MAX_PAGES, dtype=torch.int32, device=dev).view(B, MAX_PAGES)
         pos = torch.full((B,), 600, dtype=torch.int32, device=dev)
@@ -63,6 +73,8 @@ def main(argv=None):
             a.W, a.bias, a.x, a.y = masters[i].data_ptr(), bias.data_ptr(), x.data_ptr(), y.data_ptr()
             a.B, a.N, a.K, a.groups, a.x_stride, a.y_stride = B, N, K, G, G * K, ny
             a.pro, a.act, a.epi, a.ln_eps = pro, act, epi, 1e-5
+            if mc:
+                a.x_tiled, a.y_tiled, a.w_tiled = 1, int(epi != _lib.EPI_QKV_APPEND), 1
             if epi == _lib.EPI_QKV_APPEND:
                 a.kv = _lib.KV(pool.data_ptr(), table.data_ptr(), MAX_PAGES, 1, H, HD)
                 a.layer, a.kv_pos = 0, pos.data_ptr()
@@ -73,12 +85,20 @@ def main(argv=None):
             return a
 
         us = {}
-        for form in ("fp32", "w16"):
+        for form in forms:
+            if form == "wt16_depth16":
+                os.environ["SSRHIP_GEMVM_W16_DEPTH"] = "16"           # read at every launch, i.e. while the chain is captured
+            else:
+                os.environ.pop("SSRHIP_GEMVM_W16_DEPTH", None)
+
             def chain():
                 for i in range(opt.chain):
                     a = args_of(i)
                     if form == "w16":
                         rc = L.ssrhip_gemv_w16(C.byref(a), packed[i].data_ptr(), _lib.stream_ptr())
+                        assert rc == 0, (name, rc, L.ssrhip_last_error())
+                    elif form.startswith("wt16"):
+                        rc = L.ssrhip_gemv_wt16(C.byref(a), packed[i].data_ptr(), _lib.stream_ptr())
                         assert rc == 0, (name, rc, L.ssrhip_last_error())
                     else:
                         _lib.check(L.ssrhip_gemv(C.byref(a), _lib.stream_ptr()))
@@ -105,9 +125,13 @@ def main(argv=None):
             del graph
         floor = lambda nbytes: 2.6 + nbytes / 7.3e6                # us: 7.3 TB/s = 7.3e6 bytes per us
         nw = G * N * K
-        rows.append(dict(shape=name, G=G, N=N, K=K, rows=B, fp32_us=round(us["fp32"], 2), w16_us=round(us["w16"], 2),
-                         fp32_floor_us=round(floor(4 * nw), 2), w16_floor_us=round(floor(2 * nw), 2),
-                         fp32_TBps=round(4 * nw / us["fp32"] / 1e6, 2), w16_TBps=round(2 * nw / us["w16"] / 1e6, 2)))
+        os.environ.pop("SSRHIP_GEMVM_W16_DEPTH", None)
+        row = dict(shape=name, G=G, N=N, K=K, rows=B, fp32_us=round(us["fp32"], 2), fp32_floor_us=round(floor(4 * nw), 2),
+                   fp32_TBps=round(4 * nw / us["fp32"] / 1e6, 2), w16_floor_us=round(floor(2 * nw), 2))
+        for form in forms[1:]:
+            row[form + "_us"] = round(us[form], 2)
+            row[form + "_TBps"] = round(2 * nw / us[form] / 1e6, 2)
+        rows.append(row)
         print(json.dumps(rows[-1]), flush=True)
         del masters, packed
         torch.cuda.empty_cache()
