@@ -484,20 +484,15 @@ __global__ __launch_bounds__(SEG_TH, (TWO && PRO == SSRHIP_PRO_ATTN_COMBINE) ? 2
   // units; hipcc packs the merge / dot arithmetic into v_pk_fma_f32 and one of those register PAIRS held the residual in its unused half, so
   // the first use of a prefetched partial waited for the youngest load of the wave — `s_waitcnt vmcnt(0)`, the whole weight slice drained
   // before the merge arithmetic (read off the ISA, round 5). As the oldest loads such a false dependency costs nothing.
-  RowEpi efin = {0.f, 0.f};
   const int bfin = t % B, rfin = min(t / B, nrows - 1), nfin = r0 + rfin;
-  efin.bias = a.bias ? a.bias[(size_t)g * N + nfin] : 0.f;
-  efin.resid = (a.epi == SSRHIP_EPI_RESIDUAL) ? a.y[(size_t)bfin * a.y_stride + (size_t)g * N + nfin] : 0.f;
+  const RowEpi efin = seg_epi_fetch(a, g, nfin, bfin);
   // ---- 1. activations (L2) — issued first, they return first
   float4 xr[B][4];
   float4 co[(PRO == SSRHIP_PRO_ATTN_COMBINE) ? B : 1][SEG_CS];
   float2 cml[SEG_CS];                                              // (m, l) of the first SEG_CS pages of this thread's (row, head)
   int ns[(PRO == SSRHIP_PRO_ATTN_COMBINE) ? B : 1];
   if constexpr (PRO != SSRHIP_PRO_ATTN_COMBINE) {
-#pragma unroll
-    for (int b = 0; b < B; ++b)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) xr[b][i] = ld4(a.x + (size_t)b * a.x_stride + (size_t)g * K + seg * SEG + (i * 64 + lane) * 4);
+    seg_load_x<B>(xr, a.x + (size_t)g * K, (size_t)a.x_stride, seg, lane);
   } else {                                                         // K == 2048: thread t owns float4 column t*4 of every row
     const int hd = p.hd, H = K / hd, MS = a.max_splits;
 #pragma unroll
@@ -533,38 +528,10 @@ __global__ __launch_bounds__(SEG_TH, (TWO && PRO == SSRHIP_PRO_ATTN_COMBINE) ? 2
   GSTAMP(1);
   float* kvb[2] = {nullptr, nullptr};
   if (a.epi == SSRHIP_EPI_QKV_APPEND) kv_append_bases<B>(a, bfin, kvb);   // scalar-path address chain (kv_pos -> page table -> pool)
-  // ---- 3. prologue math, under the latency of the first units
-  if constexpr (PRO == SSRHIP_PRO_LAYERNORM) {
-    float m[B], q[B];
-#pragma unroll
-    for (int b = 0; b < B; ++b) {
-      float s0 = 0.f;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) s0 += (xr[b][i].x + xr[b][i].y) + (xr[b][i].z + xr[b][i].w);
-      m[b] = wave_sum(s0) * (1.0f / SEG);
-      float q0 = 0.f;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const float dx = xr[b][i].x - m[b], dy = xr[b][i].y - m[b], dz = xr[b][i].z - m[b], dw = xr[b][i].w - m[b];
-        q0 += (dx * dx + dy * dy) + (dz * dz + dw * dw);
-      }
-      q[b] = wave_sum(q0);
-      if (wave < S && lane == 0) { aux[(wave * B + b) * 2] = m[b]; aux[(wave * B + b) * 2 + 1] = q[b]; }   // wave w < S holds segment w
-    }
-    __syncthreads();
-#pragma unroll
-    for (int b = 0; b < B; ++b) {
-      float mean = 0.f, M2 = 0.f, dev = 0.f;
-      for (int s2 = 0; s2 < S; ++s2) mean += aux[(s2 * B + b) * 2];
-      mean /= (float)S;
-      for (int s2 = 0; s2 < S; ++s2) { const float dm = aux[(s2 * B + b) * 2] - mean; M2 += aux[(s2 * B + b) * 2 + 1]; dev = fmaf(dm, dm, dev); }
-      const float var = (M2 + (float)SEG * dev) / (float)K;
-      const float rstd = 1.0f / sqrtf(var + a.ln_eps);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        xr[b][i] = make_float4((xr[b][i].x - mean) * rstd, (xr[b][i].y - mean) * rstd, (xr[b][i].z - mean) * rstd, (xr[b][i].w - mean) * rstd);
-    }
-  }
+  // ---- 3. prologue math, under the latency of the first units. The split-KV merge (loads above, arithmetic below) is written out here, in
+  // gemv_pair_merge_kernel and in w16_seg_kernel — keep the three alike: behind a shared helper, in every form tried, hipcc allocated other
+  // SGPR / VGPR counts or split the merge's waits into partial `s_waitcnt vmcnt(n)` (profiles/seg_gemv_refactor_ab.md)
+  if constexpr (PRO == SSRHIP_PRO_LAYERNORM) seg_layernorm<B>(xr, aux, S, K, a.ln_eps, wave, lane);
   if constexpr (PRO == SSRHIP_PRO_ATTN_COMBINE) {
     const int hd = p.hd, H = K / hd, MS = a.max_splits;
     float* xs = aux;                                               // [B][K]
@@ -615,22 +582,10 @@ __global__ __launch_bounds__(SEG_TH, (TWO && PRO == SSRHIP_PRO_ATTN_COMBINE) ? 2
       *reinterpret_cast<float4*>(xs + b * K + e) = acc;
     }
     __syncthreads();
-#pragma unroll
-    for (int b = 0; b < B; ++b)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) xr[b][i] = *reinterpret_cast<const float4*>(xs + b * K + seg * SEG + (i * 64 + lane) * 4);
+    seg_load_x<B>(xr, xs, K, seg, lane);
   }
   GSTAMP(2);
   // ---- 4. stream the units: every 16-byte piece is re-requested for the next unit as soon as it has been used
-  auto reduce_park = [&](float (&acc)[B][2], int u) {
-    float mine = 0.f;
-#pragma unroll
-    for (int b = 0; b < B; ++b) {
-      const float sum = wave_sum(acc[b][0] + acc[b][1]);
-      if (lane == b) mine = sum;
-    }
-    if (lane < B) part[u * B + lane] = mine;                       // u = local_row * S + seg
-  };
   if constexpr (TWO) {
     auto unit = [&](const float4 (&w)[4], int u) {
       float acc[B][2];
@@ -640,7 +595,7 @@ __global__ __launch_bounds__(SEG_TH, (TWO && PRO == SSRHIP_PRO_ATTN_COMBINE) ? 2
       for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int b = 0; b < B; ++b) acc[b][i & 1] = dot4(w[i], xr[b][i], acc[b][i & 1]);
-      reduce_park(acc, u);
+      seg_park<B>(acc, part, u, lane);
     };
     if (ua < nu) unit(wa, ua);
     if (ua + SEG_NW < nu) unit(reinterpret_cast<const float4 (&)[4]>(wb), ua + SEG_NW);
@@ -659,7 +614,7 @@ __global__ __launch_bounds__(SEG_TH, (TWO && PRO == SSRHIP_PRO_ATTN_COMBINE) ? 2
         wa[i] = ld_nt(wn + i * 256);
         __builtin_amdgcn_sched_barrier(0);
       }
-      reduce_park(acc, ua);
+      seg_park<B>(acc, part, ua, lane);
       ua = un;
     }
     float acc[B][2];                                                // the last unit: nothing left to request
@@ -669,16 +624,12 @@ __global__ __launch_bounds__(SEG_TH, (TWO && PRO == SSRHIP_PRO_ATTN_COMBINE) ? 2
     for (int i = 0; i < 4; ++i)
 #pragma unroll
       for (int b = 0; b < B; ++b) acc[b][i & 1] = dot4(wa[i], xr[b][i], acc[b][i & 1]);
-    reduce_park(acc, ua);
+    seg_park<B>(acc, part, ua, lane);
   }
   GSTAMP(3);
   __syncthreads();
   GSTAMP(4);
-  if (t < nrows * B) {
-    float v = 0.f;
-    for (int s2 = 0; s2 < S; ++s2) v += part[(rfin * S + s2) * B + bfin];
-    finalize(p, g, nfin, bfin, v, efin, kvb);
-  }
+  if (t < nrows * B) seg_finish_row<B>(p, g, part, S, rfin, nfin, bfin, efin, kvb);
   GSTAMP(5);
 #undef GSTAMP
 }
@@ -716,16 +667,11 @@ __global__ __launch_bounds__(SEG_TH, 2) void gemv_segu_kernel(const GemvK p) {
   const float* Wg = a.W + ((size_t)g * N + r0) * K + seg * SEG + lane * 4;
 
   // ---- 0. epilogue operands of the (row, b) this thread finalises: the wave's oldest loads (see gemv_seg_kernel)
-  RowEpi efin = {0.f, 0.f};
   const int bfin = t % B, rfin = min(t / B, nrows - 1), nfin = r0 + rfin;
-  efin.bias = a.bias ? a.bias[(size_t)g * N + nfin] : 0.f;
-  efin.resid = (a.epi == SSRHIP_EPI_RESIDUAL) ? a.y[(size_t)bfin * a.y_stride + (size_t)g * N + nfin] : 0.f;
+  const RowEpi efin = seg_epi_fetch(a, g, nfin, bfin);
   // ---- 1. the wave's x slice (L2), then its first DEPTH units (HBM, non-temporal)
   float4 xr[B][4];
-#pragma unroll
-  for (int b = 0; b < B; ++b)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) xr[b][i] = ld4(a.x + (size_t)b * a.x_stride + (size_t)g * K + seg * SEG + (i * 64 + lane) * 4);
+  seg_load_x<B>(xr, a.x + (size_t)g * K, (size_t)a.x_stride, seg, lane);
   float4 w[DEPTH][4];
 #pragma unroll
   for (int j = 0; j < DEPTH; ++j)
@@ -733,38 +679,8 @@ __global__ __launch_bounds__(SEG_TH, 2) void gemv_segu_kernel(const GemvK p) {
     for (int i = 0; i < 4; ++i) w[j][i] = ld_nt(Wg + (size_t)((wave + SEG_NW * j) >> sh) * K + i * 256);
   float* kvb[2] = {nullptr, nullptr};
   if (a.epi == SSRHIP_EPI_QKV_APPEND) kv_append_bases<B>(a, bfin, kvb);
-  // ---- 2. LayerNorm statistics under the latency of the first units (the arithmetic of gemv_seg_kernel, operation for operation)
-  if constexpr (PRO == SSRHIP_PRO_LAYERNORM) {
-    float m[B], q[B];
-#pragma unroll
-    for (int b = 0; b < B; ++b) {
-      float s0 = 0.f;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) s0 += (xr[b][i].x + xr[b][i].y) + (xr[b][i].z + xr[b][i].w);
-      m[b] = wave_sum(s0) * (1.0f / SEG);
-      float q0 = 0.f;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const float dx = xr[b][i].x - m[b], dy = xr[b][i].y - m[b], dz = xr[b][i].z - m[b], dw = xr[b][i].w - m[b];
-        q0 += (dx * dx + dy * dy) + (dz * dz + dw * dw);
-      }
-      q[b] = wave_sum(q0);
-      if (wave < S && lane == 0) { aux[(wave * B + b) * 2] = m[b]; aux[(wave * B + b) * 2 + 1] = q[b]; }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int b = 0; b < B; ++b) {
-      float mean = 0.f, M2 = 0.f, dev = 0.f;
-      for (int s2 = 0; s2 < S; ++s2) mean += aux[(s2 * B + b) * 2];
-      mean /= (float)S;
-      for (int s2 = 0; s2 < S; ++s2) { const float dm = aux[(s2 * B + b) * 2] - mean; M2 += aux[(s2 * B + b) * 2 + 1]; dev = fmaf(dm, dm, dev); }
-      const float var = (M2 + (float)SEG * dev) / (float)K;
-      const float rstd = 1.0f / sqrtf(var + a.ln_eps);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        xr[b][i] = make_float4((xr[b][i].x - mean) * rstd, (xr[b][i].y - mean) * rstd, (xr[b][i].z - mean) * rstd, (xr[b][i].w - mean) * rstd);
-    }
-  }
+  // ---- 2. LayerNorm statistics under the latency of the first units
+  if constexpr (PRO == SSRHIP_PRO_LAYERNORM) seg_layernorm<B>(xr, aux, S, K, a.ln_eps, wave, lane);
   // ---- 3. the units, straight-line: use a piece, then re-request it in place for unit j + DEPTH
 #pragma unroll
   for (int j = 0; j < NUW; ++j) {
@@ -782,20 +698,10 @@ __global__ __launch_bounds__(SEG_TH, 2) void gemv_segu_kernel(const GemvK p) {
         __builtin_amdgcn_sched_barrier(0);
       }
     }
-    float mine = 0.f;
-#pragma unroll
-    for (int b = 0; b < B; ++b) {
-      const float sum = wave_sum(acc[b][0] + acc[b][1]);
-      if (lane == b) mine = sum;
-    }
-    if (lane < B) part[(wave + SEG_NW * j) * B + lane] = mine;     // unit u = local_row * S + seg
+    seg_park<B>(acc, part, wave + SEG_NW * j, lane);                // unit u = local_row * S + seg
   }
   __syncthreads();
-  if (t < nrows * B) {
-    float v = 0.f;
-    for (int s2 = 0; s2 < S; ++s2) v += part[(rfin * S + s2) * B + bfin];
-    finalize(p, g, nfin, bfin, v, efin, kvb);
-  }
+  if (t < nrows * B) seg_finish_row<B>(p, g, part, S, rfin, nfin, bfin, efin, kvb);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -867,46 +773,12 @@ __device__ __forceinline__ void pair_stream_b(const PairK& p, int t, int lane, i
 #pragma unroll
     for (int i = 0; i < 4; ++i) w[(j + EARLY) % DEPTH][i] = ld_nt(WgB + (size_t)((wave + SEG_NW * j) >> SHB) * bb.K + i * 256);
   __syncthreads();                                                  // (2) x' is in LDS
-#pragma unroll
-  for (int b = 0; b < B; ++b)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) xr[b][i] = *reinterpret_cast<const float4*>(xs + b * PAIR_D + segB * SEG + (i * 64 + lane) * 4);
+  seg_load_x<B>(xr, xs, PAIR_D, segB, lane);
 #pragma unroll
   for (int j = PF; j < DEPTH; ++j)
 #pragma unroll
     for (int i = 0; i < 4; ++i) w[(j + EARLY) % DEPTH][i] = ld_nt(WgB + (size_t)((wave + SEG_NW * j) >> SHB) * bb.K + i * 256);
-  // LayerNorm
-  {
-    float m[B], q[B];
-#pragma unroll
-    for (int b = 0; b < B; ++b) {
-      float s0 = 0.f;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) s0 += (xr[b][i].x + xr[b][i].y) + (xr[b][i].z + xr[b][i].w);
-      m[b] = wave_sum(s0) * (1.0f / SEG);
-      float q0 = 0.f;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const float dx = xr[b][i].x - m[b], dy = xr[b][i].y - m[b], dz = xr[b][i].z - m[b], dw = xr[b][i].w - m[b];
-        q0 += (dx * dx + dy * dy) + (dz * dz + dw * dw);
-      }
-      q[b] = wave_sum(q0);
-      if (wave < SB && lane == 0) { aux[(wave * B + b) * 2] = m[b]; aux[(wave * B + b) * 2 + 1] = q[b]; }
-    }
-    __syncthreads();                                                // (3)
-#pragma unroll
-    for (int b = 0; b < B; ++b) {
-      float mean = 0.f, M2 = 0.f, dev = 0.f;
-      for (int s2 = 0; s2 < SB; ++s2) mean += aux[(s2 * B + b) * 2];
-      mean /= (float)SB;
-      for (int s2 = 0; s2 < SB; ++s2) { const float dm = aux[(s2 * B + b) * 2] - mean; M2 += aux[(s2 * B + b) * 2 + 1]; dev = fmaf(dm, dm, dev); }
-      const float var = (M2 + (float)SEG * dev) / (float)bb.K;
-      const float rstd = 1.0f / sqrtf(var + bb.ln_eps);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        xr[b][i] = make_float4((xr[b][i].x - mean) * rstd, (xr[b][i].y - mean) * rstd, (xr[b][i].z - mean) * rstd, (xr[b][i].w - mean) * rstd);
-    }
-  }
+  seg_layernorm<B>(xr, aux, SB, bb.K, bb.ln_eps, wave, lane);       // its barrier is (3)
   // units
 #pragma unroll
   for (int j = 0; j < NUWB; ++j) {
@@ -924,22 +796,14 @@ __device__ __forceinline__ void pair_stream_b(const PairK& p, int t, int lane, i
         __builtin_amdgcn_sched_barrier(0);
       }
     }
-    float mine = 0.f;
-#pragma unroll
-    for (int b = 0; b < B; ++b) {
-      const float sum = wave_sum(acc[b][0] + acc[b][1]);
-      if (lane == b) mine = sum;
-    }
-    if (lane < B) partB[(wave + SEG_NW * j) * B + lane] = mine;
+    seg_park<B>(acc, partB, wave + SEG_NW * j, lane);
   }
   __syncthreads();                                                  // (4)
   if (t < RB * B) {
-    float v = 0.f;
-    for (int s2 = 0; s2 < SB; ++s2) v += partB[(rfinB * SB + s2) * B + bfin];
     // K / V append addresses: resolved by the edge role (wave 9) while this role streamed — the kv_pos -> page table -> pool chain costs
     // the streaming waves nothing here (in gemv_segu_kernel it is two scalar round trips per wave under the first units' latency)
     float* kvb[2] = {bb.kv.pool + kvoff[bfin * 2], bb.kv.pool + kvoff[bfin * 2 + 1]};
-    finalize(p.b, 0, nfinB, bfin, v, efinB, kvb);
+    seg_finish_row<B>(p.b, 0, partB, SB, rfinB, nfinB, bfin, efinB, kvb);
   }
 }
 
@@ -1063,13 +927,7 @@ __global__ __launch_bounds__(PAIR_TH, 2) void gemv_pair_kernel(const PairK p) {
           __builtin_amdgcn_sched_barrier(0);
         }
       }
-      float mine = 0.f;
-#pragma unroll
-      for (int b = 0; b < B; ++b) {
-        const float sum = wave_sum(acc[b][0] + acc[b][1]);
-        if (lane == b) mine = sum;
-      }
-      if (lane < B) partA[(wave + SEG_NW * j) * B + lane] = mine;
+      seg_park<B>(acc, partA, wave + SEG_NW * j, lane);
     }
     __syncthreads();                                                // (1) A's partial sums are parked
     pair_stream_b<NUWB>(p, t, lane, wave, xr, w, efinB, partB, aux, xs, kvoff);
@@ -1106,6 +964,7 @@ __global__ __launch_bounds__(PAIR_TH, 2) void gemv_pair_merge_kernel(const PairK
     RowEpi efinB = {0.f, 0.f};
     efinB.bias = bb.bias ? bb.bias[(int)blockIdx.x * RB + min(t / B, RB - 1)] : 0.f;
     // ---- 1. the attention partials this thread merges (L2): (m, l) of its (row, head), the first SEG_CS pages of its column
+    // (gemv_seg_kernel's merge, written out here too: see the note there)
     const int hd = p.a.hd, H = K / hd, MS = a.max_splits;
     float4 co[B][SEG_CS];
     float2 cml[SEG_CS];
@@ -1207,7 +1066,7 @@ __global__ __launch_bounds__(PAIR_TH, 2) void gemv_pair_merge_kernel(const PairK
       for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int b = 0; b < B; ++b) acc[b][i & 1] = dot4(w[j][i], xr[b][i], acc[b][i & 1]);
-      float mine = 0.f;
+      float mine = 0.f;                                             // seg_park, written out: through the helper hipcc moves two lgkmcnt waits here
 #pragma unroll
       for (int b = 0; b < B; ++b) {
         const float sum = wave_sum(acc[b][0] + acc[b][1]);
@@ -1228,63 +1087,35 @@ int g_seg_mode = -1;   // SSRHIP_GEMV_SEG: 1 (default) = take the segment kernel
 // true if the segment kernel was launched
 template <int B>
 bool try_seg(const ssrhip_gemv_args* a, int num_cu, hipStream_t s) {
-  if (a->K % SEG != 0) return false;
-  const int S = a->K / SEG;
-  if (S != 1 && S != 2 && S != 4 && S != 8) return false;
-  if (a->pro == SSRHIP_PRO_LAYERNORM && a->ln_w != nullptr) return false;
-  const int H = a->kv.head_dim > 0 ? a->K / a->kv.head_dim : 0;
-  if (a->pro == SSRHIP_PRO_ATTN_COMBINE && (a->K != 2048 || a->max_splits < 1 || a->groups != 1 || B * H > SEG_TH || a->kv.head_dim % 4 != 0)) return false;
-  int G = (2 * num_cu) / a->groups;                                // two resident workgroups per CU over all groups
-  // the combine prologue makes EVERY workgroup read all the attention partials (~100 KB at 6 pages): with two workgroups per CU that is
-  // 3x the CU's share of the weights through its 64 B/clk L2 port; one workgroup per CU halves it
-  if (a->pro == SSRHIP_PRO_ATTN_COMBINE && !getenv("SSRHIP_GEMV_SEG_COMBINE_2")) G = num_cu;
-  if (G > a->N) G = a->N;                                          // fewer rows than workgroups: one row each
-  if (G < 1) G = 1;
-  const int rows_max = (a->N + G - 1) / G;
-  if (rows_max * B > SEG_TH) return false;
-  GemvK p;
-  p.a = *a;
-  p.nslice = S;
-  p.slice_len = SEG;
-  p.nch = 4;
-  p.seg_shift = (S == 1) ? 0 : (S == 2) ? 1 : (S == 4) ? 2 : 3;
-  p.rows_max = rows_max;
-  p.rows_per = a->N / G;
-  p.rows_rem = a->N % G;
+  SegPlan pl;
+  const char* why;
+  if (!seg_plan(a, num_cu, getenv("SSRHIP_GEMV_SEG_COMBINE_2") != nullptr, &pl, &why)) return false;   // read at every call
+  GemvK& p = pl.k;
   p.prof = g_gemv_prof;
-  p.groups_x = G;
-  p.hd = (a->kv.head_dim > 0) ? a->kv.head_dim : 1;
-  size_t smem = (size_t)rows_max * S * B * sizeof(float);
-  if (a->pro == SSRHIP_PRO_LAYERNORM) smem += (size_t)S * B * 2 * sizeof(float);
-  if (a->pro == SSRHIP_PRO_ATTN_COMBINE) smem += ((size_t)B * a->K + (size_t)B * H * a->max_splits) * sizeof(float);
-  smem = (smem + 15) / 16 * 16;
+  const int S = p.nslice, G = pl.G, rows_max = p.rows_max;
+  const size_t smem = pl.smem;
   // round 5: one workgroup per CU, NUW units per wave straight-line, DEPTH in flight (gemv_segu_kernel) when the shape divides evenly
   int segu_depth = 4;                                               // SSRHIP_GEMV_SEGU = 0 (off) | 2 | 4 (default): units in flight per wave; read at
   if (const char* e = getenv("SSRHIP_GEMV_SEGU")) { segu_depth = atoi(e); if (segu_depth != 0 && segu_depth != 2) segu_depth = 4; }   // every call
   if constexpr (B == 2) {
-    const int G1 = num_cu / a->groups;
-    if (segu_depth && a->pro != SSRHIP_PRO_ATTN_COMBINE && G1 >= 1 && a->N % G1 == 0 && ((a->N / G1) * S) % SEG_NW == 0) {
-      const int nuw = (a->N / G1) * S / SEG_NW;
-      if (nuw == 4 || nuw == 6 || nuw == 8) {
-        p.rows_max = p.rows_per = a->N / G1;
-        p.rows_rem = 0;
-        p.groups_x = G1;
-        size_t sm = (size_t)p.rows_per * S * B * sizeof(float) + (size_t)S * B * 2 * sizeof(float);
-        sm = (sm + 15) / 16 * 16;
-        const dim3 g1(G1, a->groups);
+    if (segu_depth && pl.segu_nuw) {
+      const int nuw = pl.segu_nuw;
+      seg_fill(&p, a, S, pl.segu_G1);
+      p.prof = g_gemv_prof;
+      const size_t sm = pl.segu_smem;
+      const dim3 g1(pl.segu_G1, a->groups);
 #define SEGU_LAUNCH(PRO_, NUW_)                                                                                                       \
-        do {                                                                                                                           \
-          if (segu_depth == 2) hipLaunchKernelGGL((gemv_segu_kernel<B, PRO_, NUW_, 2>), g1, dim3(SEG_TH), sm, s, p);                    \
-          else hipLaunchKernelGGL((gemv_segu_kernel<B, PRO_, NUW_, 4>), g1, dim3(SEG_TH), sm, s, p);                                    \
-        } while (0)
-        if (a->pro == SSRHIP_PRO_LAYERNORM) {
-          if (nuw == 4) SEGU_LAUNCH(SSRHIP_PRO_LAYERNORM, 4); else if (nuw == 6) SEGU_LAUNCH(SSRHIP_PRO_LAYERNORM, 6); else SEGU_LAUNCH(SSRHIP_PRO_LAYERNORM, 8);
-        } else {
-          if (nuw == 4) SEGU_LAUNCH(SSRHIP_PRO_NONE, 4); else if (nuw == 6) SEGU_LAUNCH(SSRHIP_PRO_NONE, 6); else SEGU_LAUNCH(SSRHIP_PRO_NONE, 8);
-        }
-#undef SEGU_LAUNCH
-        return true;
+      do {                                                                                                                             \
+        if (segu_depth == 2) hipLaunchKernelGGL((gemv_segu_kernel<B, PRO_, NUW_, 2>), g1, dim3(SEG_TH), sm, s, p);                      \
+        else hipLaunchKernelGGL((gemv_segu_kernel<B, PRO_, NUW_, 4>), g1, dim3(SEG_TH), sm, s, p);                                      \
+      } while (0)
+      if (a->pro == SSRHIP_PRO_LAYERNORM) {
+        if (nuw == 4) SEGU_LAUNCH(SSRHIP_PRO_LAYERNORM, 4); else if (nuw == 6) SEGU_LAUNCH(SSRHIP_PRO_LAYERNORM, 6); else SEGU_LAUNCH(SSRHIP_PRO_LAYERNORM, 8);
+      } else {
+        if (nuw == 4) SEGU_LAUNCH(SSRHIP_PRO_NONE, 4); else if (nuw == 6) SEGU_LAUNCH(SSRHIP_PRO_NONE, 6); else SEGU_LAUNCH(SSRHIP_PRO_NONE, 8);
       }
+#undef SEGU_LAUNCH
+      return true;
     }
   }
   dim3 grid(G, a->groups);
@@ -1415,12 +1246,8 @@ extern "C" int ssrhip_gemv_pair(const ssrhip_gemv_args* a, const ssrhip_gemv_arg
   const int nuwb = pair_nuwb(a, b, ssr_num_cu(), &merge);
   if (!nuwb) return 1;
   PairK p;
-  auto fill = [](GemvK& k, const ssrhip_gemv_args* g, int S) {
-    k.a = *g; k.nslice = S; k.slice_len = SEG; k.nch = 4; k.groups_x = 256; k.hd = (g->kv.head_dim > 0) ? g->kv.head_dim : 1;
-    k.seg_shift = (S == 8) ? 3 : 1; k.rows_max = k.rows_per = g->N / 256; k.rows_rem = 0; k.prof = nullptr;
-  };
-  fill(p.a, a, merge ? 2 : 8);
-  fill(p.b, b, 2);
+  seg_fill(&p.a, a, merge ? 2 : 8, 256);                            // one workgroup per CU: 8 rows of A, N / 256 rows of B
+  seg_fill(&p.b, b, 2, 256);
   unsigned long long* gran = (unsigned long long*)ws;
   p.gran = gran + (size_t)buf * PAIR_GRAN;
   p.gran_next = gran + (size_t)buf_next * PAIR_GRAN;
@@ -1462,23 +1289,7 @@ extern "C" int ssrhip_gemv(const ssrhip_gemv_args* a, ssrhip_stream_t stream) {
   if (a->B > 16) return ssrhip_gemv_mfma32_launch(a, (hipStream_t)stream);
   if (a->B > 4) return ssrhip_gemv_mfma_launch(a, (hipStream_t)stream);
   SSR_REQUIRE(a->B == 1 || a->B == 2 || a->B == 4, "ssrhip_gemv: B=%d not in {1,2,4} or 5..32", a->B);
-  SSR_REQUIRE(!a->x_tiled && !a->y_tiled && !a->w_tiled, "ssrhip_gemv: the tiled activation / weight layouts are for 5..32 rows only");
-  SSR_REQUIRE(a->pro != SSRHIP_PRO_ATTN_COMBINE || (a->kv.head_dim > 0 && a->K <= 2048 && a->B * (a->K / a->kv.head_dim) <= 256), "ssrhip_gemv: combine prologue needs K <= 2048 and B*H <= 256");
-  SSR_REQUIRE(a->K > 0 && a->K % 4 == 0 && a->K <= 8192, "ssrhip_gemv: K=%d must be a multiple of 4, <= 8192", a->K);
-  if (a->pro != SSRHIP_PRO_NONE) {
-    SSR_REQUIRE(a->groups == 1 || a->pro == SSRHIP_PRO_LAYERNORM, "ssrhip_gemv: combine prologue needs groups==1");
-    if (a->pro == SSRHIP_PRO_LAYERNORM) SSR_REQUIRE(a->x && ((a->ln_w && a->ln_b) || (!a->ln_w && !a->ln_b)), "ssrhip_gemv: LayerNorm prologue needs x and either both or none of ln_w/ln_b");
-    if (a->pro == SSRHIP_PRO_ATTN_COMBINE) {
-      SSR_REQUIRE(a->part_o && a->part_ml && a->row_len && a->kv.head_dim > 0 && a->K % a->kv.head_dim == 0 && a->kv.head_dim % 4 == 0,
-                  "ssrhip_gemv: combine prologue needs part_o, part_ml, row_len, kv.head_dim");
-    }
-  } else {
-    SSR_REQUIRE(a->x, "ssrhip_gemv: x is null");
-  }
-  if (a->epi == SSRHIP_EPI_QKV_APPEND) {
-    SSR_REQUIRE(a->N == 3 * a->K && a->groups == 1 && a->kv.pool && a->kv.table && a->kv_pos && a->kv.head_dim > 0,
-                "ssrhip_gemv: QKV epilogue needs N==3K and a kv cache");
-  }
+  if (int rc = gemv_small_check(a, "ssrhip_gemv")) return rc;
   if (g_seg_mode < 0) { const char* e = getenv("SSRHIP_GEMV_SEG"); g_seg_mode = (e && e[0] == '0') ? 0 : 1; }
   const int num_cu = ssr_num_cu();
   hipStream_t s = (hipStream_t)stream;

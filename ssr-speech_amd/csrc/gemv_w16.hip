@@ -49,40 +49,6 @@ __device__ __forceinline__ void w16_piece(const w16_v4u u, int j, const float4 (
   for (int b = 0; b < B; ++b) acc[b][1] = dot4(w1, xr[b][2 * j + 1], acc[b][1]);
 }
 
-// per-segment two-pass LayerNorm statistics, exchanged through LDS and merged exactly (Chan): the arithmetic of gemv_seg_kernel
-template <int B>
-__device__ __forceinline__ void w16_layernorm(float4 (&xr)[B][4], float* aux, int S, int K, float eps, int wave, int lane) {
-  float m[B], q[B];
-#pragma unroll
-  for (int b = 0; b < B; ++b) {
-    float s0 = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) s0 += (xr[b][i].x + xr[b][i].y) + (xr[b][i].z + xr[b][i].w);
-    m[b] = wave_sum(s0) * (1.0f / SEG);
-    float q0 = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float dx = xr[b][i].x - m[b], dy = xr[b][i].y - m[b], dz = xr[b][i].z - m[b], dw = xr[b][i].w - m[b];
-      q0 += (dx * dx + dy * dy) + (dz * dz + dw * dw);
-    }
-    q[b] = wave_sum(q0);
-    if (wave < S && lane == 0) { aux[(wave * B + b) * 2] = m[b]; aux[(wave * B + b) * 2 + 1] = q[b]; }   // wave w < S holds segment w
-  }
-  __syncthreads();
-#pragma unroll
-  for (int b = 0; b < B; ++b) {
-    float mean = 0.f, M2 = 0.f, dev = 0.f;
-    for (int s2 = 0; s2 < S; ++s2) mean += aux[(s2 * B + b) * 2];
-    mean /= (float)S;
-    for (int s2 = 0; s2 < S; ++s2) { const float dm = aux[(s2 * B + b) * 2] - mean; M2 += aux[(s2 * B + b) * 2 + 1]; dev = fmaf(dm, dm, dev); }
-    const float var = (M2 + (float)SEG * dev) / (float)K;
-    const float rstd = 1.0f / sqrtf(var + eps);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      xr[b][i] = make_float4((xr[b][i].x - mean) * rstd, (xr[b][i].y - mean) * rstd, (xr[b][i].z - mean) * rstd, (xr[b][i].w - mean) * rstd);
-  }
-}
-
 struct W16K {
   GemvK k;
   const uint16_t* W16;   // [groups][N][K] in SSRHIP_W16_INDEX order
@@ -112,20 +78,15 @@ __global__ __launch_bounds__(SEG_TH, (PRO == SSRHIP_PRO_ATTN_COMBINE) ? 2 : 4) v
   const uint16_t* Wg = q.W16 + ((size_t)g * N + r0) * K + seg * SEG + lane * 8;   // unit of local row c: + c * K; piece j: + j * 512
 
   // ---- 0. epilogue operands of the (row, b) this thread finalises: the wave's oldest loads (see gemv_seg_kernel)
-  RowEpi efin = {0.f, 0.f};
   const int bfin = t % B, rfin = min(t / B, nrows - 1), nfin = r0 + rfin;
-  efin.bias = a.bias ? a.bias[(size_t)g * N + nfin] : 0.f;
-  efin.resid = (a.epi == SSRHIP_EPI_RESIDUAL) ? a.y[(size_t)bfin * a.y_stride + (size_t)g * N + nfin] : 0.f;
+  const RowEpi efin = seg_epi_fetch(a, g, nfin, bfin);
   // ---- 1. activations (L2)
   float4 xr[B][4];
   float4 co[(PRO == SSRHIP_PRO_ATTN_COMBINE) ? B : 1][SEG_CS];
   float2 cml[SEG_CS];
   int ns[(PRO == SSRHIP_PRO_ATTN_COMBINE) ? B : 1];
   if constexpr (PRO != SSRHIP_PRO_ATTN_COMBINE) {
-#pragma unroll
-    for (int b = 0; b < B; ++b)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) xr[b][i] = ld4(a.x + (size_t)b * a.x_stride + (size_t)g * K + seg * SEG + (i * 64 + lane) * 4);
+    seg_load_x<B>(xr, a.x + (size_t)g * K, (size_t)a.x_stride, seg, lane);
   } else {                                                         // K == 2048: thread t owns float4 column t * 4 of every row
     const int hd = p.hd, H = K / hd, MS = a.max_splits;
 #pragma unroll
@@ -155,8 +116,8 @@ __global__ __launch_bounds__(SEG_TH, (PRO == SSRHIP_PRO_ATTN_COMBINE) ? 2 : 4) v
   float* kvb[2] = {nullptr, nullptr};
   if (a.epi == SSRHIP_EPI_QKV_APPEND) kv_append_bases<B>(a, bfin, kvb);
   // ---- 3. prologue math, under the latency of the first units
-  if constexpr (PRO == SSRHIP_PRO_LAYERNORM) w16_layernorm<B>(xr, aux, S, K, a.ln_eps, wave, lane);
-  if constexpr (PRO == SSRHIP_PRO_ATTN_COMBINE) {                  // gemv_seg_kernel's merge, operation for operation
+  if constexpr (PRO == SSRHIP_PRO_LAYERNORM) seg_layernorm<B>(xr, aux, S, K, a.ln_eps, wave, lane);
+  if constexpr (PRO == SSRHIP_PRO_ATTN_COMBINE) {                  // gemv_seg_kernel's merge, operation for operation (written out: see the note there)
     const int hd = p.hd, H = K / hd, MS = a.max_splits;
     float* xs = aux;                                               // [B][K]
     float* wtab = aux + B * K;                                     // [B*H][MS]
@@ -206,21 +167,9 @@ __global__ __launch_bounds__(SEG_TH, (PRO == SSRHIP_PRO_ATTN_COMBINE) ? 2 : 4) v
       *reinterpret_cast<float4*>(xs + b * K + e) = acc;
     }
     __syncthreads();
-#pragma unroll
-    for (int b = 0; b < B; ++b)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) xr[b][i] = *reinterpret_cast<const float4*>(xs + b * K + seg * SEG + (i * 64 + lane) * 4);
+    seg_load_x<B>(xr, xs, K, seg, lane);
   }
   // ---- 4. stream the units through the ring of two
-  auto reduce_park = [&](float (&acc)[B][2], int un) {
-    float mine = 0.f;
-#pragma unroll
-    for (int b = 0; b < B; ++b) {
-      const float sum = wave_sum(acc[b][0] + acc[b][1]);
-      if (lane == b) mine = sum;
-    }
-    if (lane < B) part[un * B + lane] = mine;                      // un = local_row * S + seg
-  };
   // unit `un` sits in `w`; when `next` >= 0 every 16-byte piece is re-requested for unit `next` right after its use, in place
   auto unit = [&](w16_v4u (&w)[2], int un, int next) {
     float acc[B][2];
@@ -239,7 +188,7 @@ __global__ __launch_bounds__(SEG_TH, (PRO == SSRHIP_PRO_ATTN_COMBINE) ? 2 : 4) v
 #pragma unroll
       for (int j = 0; j < 2; ++j) w16_piece<B>(w[j], j, xr, acc);
     }
-    reduce_park(acc, un);
+    seg_park<B>(acc, part, un, lane);
   };
   while (u + 3 * SEG_NW < nu) {                                     // both ring slots have a successor
     unit(w0, u, u + 2 * SEG_NW);
@@ -255,11 +204,7 @@ __global__ __launch_bounds__(SEG_TH, (PRO == SSRHIP_PRO_ATTN_COMBINE) ? 2 : 4) v
     if (u + SEG_NW < nu) unit(w1, u + SEG_NW, -1);
   }
   __syncthreads();
-  if (t < nrows * B) {
-    float v = 0.f;
-    for (int s2 = 0; s2 < S; ++s2) v += part[(rfin * S + s2) * B + bfin];
-    finalize(p, g, nfin, bfin, v, efin, kvb);
-  }
+  if (t < nrows * B) seg_finish_row<B>(p, g, part, S, rfin, nfin, bfin, efin, kvb);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -288,15 +233,10 @@ __global__ __launch_bounds__(SEG_TH, 2) void w16_segu_kernel(const W16K q) {
   float* aux = smem + nrows * S * B;                               // LayerNorm statistics of the S segments
   const uint16_t* Wg = q.W16 + ((size_t)g * N + r0) * K + seg * SEG + lane * 8;
 
-  RowEpi efin = {0.f, 0.f};
   const int bfin = t % B, rfin = min(t / B, nrows - 1), nfin = r0 + rfin;
-  efin.bias = a.bias ? a.bias[(size_t)g * N + nfin] : 0.f;
-  efin.resid = (a.epi == SSRHIP_EPI_RESIDUAL) ? a.y[(size_t)bfin * a.y_stride + (size_t)g * N + nfin] : 0.f;
+  const RowEpi efin = seg_epi_fetch(a, g, nfin, bfin);
   float4 xr[B][4];
-#pragma unroll
-  for (int b = 0; b < B; ++b)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) xr[b][i] = ld4(a.x + (size_t)b * a.x_stride + (size_t)g * K + seg * SEG + (i * 64 + lane) * 4);
+  seg_load_x<B>(xr, a.x + (size_t)g * K, (size_t)a.x_stride, seg, lane);
   w16_v4u w[DEPTH][2];
 #pragma unroll
   for (int j = 0; j < DEPTH; ++j)
@@ -304,7 +244,7 @@ __global__ __launch_bounds__(SEG_TH, 2) void w16_segu_kernel(const W16K q) {
     for (int i = 0; i < 2; ++i) w[j][i] = ld16_nt(Wg + (size_t)((wave + SEG_NW * j) >> sh) * K + i * 512);
   float* kvb[2] = {nullptr, nullptr};
   if (a.epi == SSRHIP_EPI_QKV_APPEND) kv_append_bases<B>(a, bfin, kvb);
-  if constexpr (PRO == SSRHIP_PRO_LAYERNORM) w16_layernorm<B>(xr, aux, S, K, a.ln_eps, wave, lane);
+  if constexpr (PRO == SSRHIP_PRO_LAYERNORM) seg_layernorm<B>(xr, aux, S, K, a.ln_eps, wave, lane);
 #pragma unroll
   for (int j = 0; j < NUW; ++j) {
     w16_v4u (&wj)[2] = w[j % DEPTH];
@@ -320,7 +260,7 @@ __global__ __launch_bounds__(SEG_TH, 2) void w16_segu_kernel(const W16K q) {
         __builtin_amdgcn_sched_barrier(0);
       }
     }
-    float mine = 0.f;
+    float mine = 0.f;                                              // seg_park, written out: through the helper hipcc gives <1, LN, 6|8, 2> two more VGPRs
 #pragma unroll
     for (int b = 0; b < B; ++b) {
       const float sum = wave_sum(acc[b][0] + acc[b][1]);
@@ -329,145 +269,76 @@ __global__ __launch_bounds__(SEG_TH, 2) void w16_segu_kernel(const W16K q) {
     if (lane < B) part[(wave + SEG_NW * j) * B + lane] = mine;     // unit u = local_row * S + seg
   }
   __syncthreads();
-  if (t < nrows * B) {
-    float v = 0.f;
-    for (int s2 = 0; s2 < S; ++s2) v += part[(rfin * S + s2) * B + bfin];
-    finalize(p, g, nfin, bfin, v, efin, kvb);
-  }
+  if (t < nrows * B) seg_finish_row<B>(p, g, part, S, rfin, nfin, bfin, efin, kvb);
 }
 
-// Does `a` qualify, i.e. would gemv.hip's try_seg take it? (`why` receives the answer as text.) The fp32 dispatch must be on its
-// segment kernels too (SSRHIP_GEMV_SEG != 0): the row-per-wave kernels add in another order and the promise is bit-identity with ssrhip_gemv.
-bool w16_qualifies(const ssrhip_gemv_args* a, int num_cu, const char** why) {
-  auto no = [&](const char* w) { *why = w; return false; };
-  if (a->B != 1 && a->B != 2 && a->B != 4) return no("B not in {1, 2, 4}");
-  if (a->x_tiled || a->y_tiled || a->w_tiled) return no("tiled layouts are for 5..32 rows");
-  if (a->K % SEG != 0) return no("K is not a multiple of 1024");
-  const int S = a->K / SEG;
-  if (S != 1 && S != 2 && S != 4 && S != 8) return no("K / 1024 not in {1, 2, 4, 8}");
-  if (a->pro == SSRHIP_PRO_LAYERNORM && a->ln_w != nullptr) return no("LayerNorm gamma / beta not folded into the weights");
-  const int H = a->kv.head_dim > 0 ? a->K / a->kv.head_dim : 0;
-  if (a->pro == SSRHIP_PRO_ATTN_COMBINE && (a->K != 2048 || a->max_splits < 1 || a->groups != 1 || a->B * H > SEG_TH || a->kv.head_dim % 4 != 0))
-    return no("split-KV merge prologue needs K = 2048, one group, B * H <= 512");
-  int G = (2 * num_cu) / a->groups;
-  if (a->pro == SSRHIP_PRO_ATTN_COMBINE) G = num_cu;
-  if (G > a->N) G = a->N;
-  if (G < 1) G = 1;
-  if ((a->N + G - 1) / G * a->B > SEG_TH) return no("too many rows per workgroup");
-  if (const char* e = getenv("SSRHIP_GEMV_SEG")) if (e[0] == '0') return no("SSRHIP_GEMV_SEG=0");
-  *why = "";
+// Does `a` qualify, i.e. would ssrhip_gemv take it with its segment kernels? seg_plan (gemv_shared.h) is the decision of gemv.hip's try_seg;
+// the fp32 dispatch must be on those kernels too (SSRHIP_GEMV_SEG != 0, read at every call): the row-per-wave kernels add in another order
+// and the promise is bit-identity with ssrhip_gemv.
+bool w16_plan(const ssrhip_gemv_args* a, int num_cu, SegPlan* pl) {
+  const char* why;
+  if (a->B != 1 && a->B != 2 && a->B != 4) return false;
+  if (a->x_tiled || a->y_tiled || a->w_tiled) return false;          // tiled layouts are for 5..32 rows
+  if (!seg_plan(a, num_cu, false, pl, &why)) return false;           // one workgroup per CU behind the merge prologue, always
+  if (const char* e = getenv("SSRHIP_GEMV_SEG")) if (e[0] == '0') return false;
   return true;
 }
 
-// the contract of ssrhip_gemv for <= 4 rows (same checks: a launch that ssrhip_gemv would refuse is refused here too)
-int w16_check(const ssrhip_gemv_args* a, const uint16_t* W16) {
-  SSR_REQUIRE(a && a->W && a->y && W16, "ssrhip_gemv_w16: null argument");
-  SSR_REQUIRE(a->N > 0 && a->groups >= 1 && a->K > 0, "ssrhip_gemv_w16: bad N/K/groups");
-  SSR_REQUIRE(a->B == 1 || a->B == 2 || a->B == 4, "ssrhip_gemv_w16: B=%d not in {1,2,4} (the bf16 weight stream exists for the <= 4-row step only)", a->B);
-  SSR_REQUIRE(!a->x_tiled && !a->y_tiled && !a->w_tiled, "ssrhip_gemv_w16: the tiled activation / weight layouts are for 5..32 rows only");
-  SSR_REQUIRE(a->pro != SSRHIP_PRO_ATTN_COMBINE || (a->kv.head_dim > 0 && a->K <= 2048 && a->B * (a->K / a->kv.head_dim) <= 256), "ssrhip_gemv_w16: combine prologue needs K <= 2048 and B*H <= 256");
-  SSR_REQUIRE(a->K % 4 == 0 && a->K <= 8192, "ssrhip_gemv_w16: K=%d must be a multiple of 4, <= 8192", a->K);
-  if (a->pro != SSRHIP_PRO_NONE) {
-    SSR_REQUIRE(a->groups == 1 || a->pro == SSRHIP_PRO_LAYERNORM, "ssrhip_gemv_w16: combine prologue needs groups==1");
-    if (a->pro == SSRHIP_PRO_LAYERNORM) SSR_REQUIRE(a->x && ((a->ln_w && a->ln_b) || (!a->ln_w && !a->ln_b)), "ssrhip_gemv_w16: LayerNorm prologue needs x and either both or none of ln_w/ln_b");
-    if (a->pro == SSRHIP_PRO_ATTN_COMBINE) {
-      SSR_REQUIRE(a->part_o && a->part_ml && a->row_len && a->kv.head_dim > 0 && a->K % a->kv.head_dim == 0 && a->kv.head_dim % 4 == 0,
-                  "ssrhip_gemv_w16: combine prologue needs part_o, part_ml, row_len, kv.head_dim");
-    }
-  } else {
-    SSR_REQUIRE(a->x, "ssrhip_gemv_w16: x is null");
-  }
-  if (a->epi == SSRHIP_EPI_QKV_APPEND) {
-    SSR_REQUIRE(a->N == 3 * a->K && a->groups == 1 && a->kv.pool && a->kv.table && a->kv_pos && a->kv.head_dim > 0,
-                "ssrhip_gemv_w16: QKV epilogue needs N==3K and a kv cache");
-  }
-  return 0;
-}
-
 template <int B>
-void w16_launch(const ssrhip_gemv_args* a, const uint16_t* W16, int num_cu, hipStream_t s) {
-  const int S = a->K / SEG;
-  const int H = a->kv.head_dim > 0 ? a->K / a->kv.head_dim : 0;
-  int G = (2 * num_cu) / a->groups;                                // two resident workgroups per CU over all groups ...
-  if (a->pro == SSRHIP_PRO_ATTN_COMBINE) G = num_cu;               // ... one behind the merge prologue (every workgroup reads all the partials)
-  if (G > a->N) G = a->N;
-  if (G < 1) G = 1;
-  const int rows_max = (a->N + G - 1) / G;
+void w16_launch(const SegPlan& pl, const uint16_t* W16, hipStream_t s) {
+  const ssrhip_gemv_args* a = &pl.k.a;
   W16K q;
+  q.k = pl.k;
   q.W16 = W16;
-  GemvK& p = q.k;
-  p.a = *a;
-  p.nslice = S;
-  p.slice_len = SEG;
-  p.nch = 4;
-  p.seg_shift = (S == 1) ? 0 : (S == 2) ? 1 : (S == 4) ? 2 : 3;
-  p.rows_max = rows_max;
-  p.rows_per = a->N / G;
-  p.rows_rem = a->N % G;
-  p.prof = nullptr;
-  p.groups_x = G;
-  p.hd = (a->kv.head_dim > 0) ? a->kv.head_dim : 1;
-  size_t smem = (size_t)rows_max * S * B * sizeof(float);
-  if (a->pro == SSRHIP_PRO_LAYERNORM) smem += (size_t)S * B * 2 * sizeof(float);
-  if (a->pro == SSRHIP_PRO_ATTN_COMBINE) smem += ((size_t)B * a->K + (size_t)B * H * a->max_splits) * sizeof(float);
-  smem = (smem + 15) / 16 * 16;
-  {
-    // one workgroup per CU, NUW units per wave straight-line, when the shape divides evenly (the shapes gemv_segu_kernel takes at 2 rows)
-    int depth = (B == 4) ? 2 : 4;                                   // SSRHIP_GEMV_W16_DEPTH = 2 | 4 (default: 4, 2 at 4 rows): units in flight per wave; 8: every unit
-    if (const char* e = getenv("SSRHIP_GEMV_W16_DEPTH")) depth = atoi(e);   // at entry; 0: never this form. Read at every call.
-    const bool off = depth == 0;
-    const int G1 = num_cu / a->groups;
-    if (!off && a->pro != SSRHIP_PRO_ATTN_COMBINE && G1 >= 1 && a->N % G1 == 0 && ((a->N / G1) * S) % SEG_NW == 0) {
-      const int nuw = (a->N / G1) * S / SEG_NW;
-      if (nuw == 4 || nuw == 6 || nuw == 8) {
-        p.rows_max = p.rows_per = a->N / G1;
-        p.rows_rem = 0;
-        p.groups_x = G1;
-        size_t sm = (size_t)p.rows_per * S * B * sizeof(float) + (size_t)S * B * 2 * sizeof(float);
-        sm = (sm + 15) / 16 * 16;
-        const dim3 g1(G1, a->groups);
+  // one workgroup per CU, NUW units per wave straight-line, when the shape divides evenly (the shapes gemv_segu_kernel takes at 2 rows)
+  int depth = (B == 4) ? 2 : 4;                                     // SSRHIP_GEMV_W16_DEPTH = 2 | 4 (default: 4, 2 at 4 rows): units in flight per wave; 8: every unit
+  if (const char* e = getenv("SSRHIP_GEMV_W16_DEPTH")) depth = atoi(e);   // at entry; 0: never this form. Read at every call.
+  if (depth != 0 && pl.segu_nuw) {
+    const int nuw = pl.segu_nuw;
+    seg_fill(&q.k, a, pl.k.nslice, pl.segu_G1);
+    const size_t sm = pl.segu_smem;
+    const dim3 g1(pl.segu_G1, a->groups);
 #define W16U_LAUNCH(PRO_, NUW_)                                                                                                       \
-        do {                                                                                                                           \
-          if (depth == 2) hipLaunchKernelGGL((w16_segu_kernel<B, PRO_, NUW_, 2>), g1, dim3(SEG_TH), sm, s, q);                          \
-          else if (depth == 8) hipLaunchKernelGGL((w16_segu_kernel<B, PRO_, NUW_, NUW_>), g1, dim3(SEG_TH), sm, s, q);                  \
-          else hipLaunchKernelGGL((w16_segu_kernel<B, PRO_, NUW_, 4>), g1, dim3(SEG_TH), sm, s, q);                                     \
-        } while (0)
-        if (a->pro == SSRHIP_PRO_LAYERNORM) {
-          if (nuw == 4) W16U_LAUNCH(SSRHIP_PRO_LAYERNORM, 4); else if (nuw == 6) W16U_LAUNCH(SSRHIP_PRO_LAYERNORM, 6); else W16U_LAUNCH(SSRHIP_PRO_LAYERNORM, 8);
-        } else {
-          if (nuw == 4) W16U_LAUNCH(SSRHIP_PRO_NONE, 4); else if (nuw == 6) W16U_LAUNCH(SSRHIP_PRO_NONE, 6); else W16U_LAUNCH(SSRHIP_PRO_NONE, 8);
-        }
-#undef W16U_LAUNCH
-        return;
-      }
+    do {                                                                                                                               \
+      if (depth == 2) hipLaunchKernelGGL((w16_segu_kernel<B, PRO_, NUW_, 2>), g1, dim3(SEG_TH), sm, s, q);                              \
+      else if (depth == 8) hipLaunchKernelGGL((w16_segu_kernel<B, PRO_, NUW_, NUW_>), g1, dim3(SEG_TH), sm, s, q);                      \
+      else hipLaunchKernelGGL((w16_segu_kernel<B, PRO_, NUW_, 4>), g1, dim3(SEG_TH), sm, s, q);                                         \
+    } while (0)
+    if (a->pro == SSRHIP_PRO_LAYERNORM) {
+      if (nuw == 4) W16U_LAUNCH(SSRHIP_PRO_LAYERNORM, 4); else if (nuw == 6) W16U_LAUNCH(SSRHIP_PRO_LAYERNORM, 6); else W16U_LAUNCH(SSRHIP_PRO_LAYERNORM, 8);
+    } else {
+      if (nuw == 4) W16U_LAUNCH(SSRHIP_PRO_NONE, 4); else if (nuw == 6) W16U_LAUNCH(SSRHIP_PRO_NONE, 6); else W16U_LAUNCH(SSRHIP_PRO_NONE, 8);
     }
+#undef W16U_LAUNCH
+    return;
   }
-  const dim3 grid(G, a->groups);
+  const dim3 grid(pl.G, a->groups);
   switch (a->pro) {
-    case SSRHIP_PRO_LAYERNORM: hipLaunchKernelGGL((w16_seg_kernel<B, SSRHIP_PRO_LAYERNORM>), grid, dim3(SEG_TH), smem, s, q); break;
-    case SSRHIP_PRO_ATTN_COMBINE: hipLaunchKernelGGL((w16_seg_kernel<B, SSRHIP_PRO_ATTN_COMBINE>), grid, dim3(SEG_TH), smem, s, q); break;
-    default: hipLaunchKernelGGL((w16_seg_kernel<B, SSRHIP_PRO_NONE>), grid, dim3(SEG_TH), smem, s, q); break;
+    case SSRHIP_PRO_LAYERNORM: hipLaunchKernelGGL((w16_seg_kernel<B, SSRHIP_PRO_LAYERNORM>), grid, dim3(SEG_TH), pl.smem, s, q); break;
+    case SSRHIP_PRO_ATTN_COMBINE: hipLaunchKernelGGL((w16_seg_kernel<B, SSRHIP_PRO_ATTN_COMBINE>), grid, dim3(SEG_TH), pl.smem, s, q); break;
+    default: hipLaunchKernelGGL((w16_seg_kernel<B, SSRHIP_PRO_NONE>), grid, dim3(SEG_TH), pl.smem, s, q); break;
   }
 }
 
 }  // namespace
 
 extern "C" int ssrhip_gemv_w16_applicable(const ssrhip_gemv_args* a) {
-  if (!a) return 0;
-  const char* why;
-  return w16_qualifies(a, ssr_num_cu(), &why) ? 1 : 0;
+  SegPlan pl;
+  return (a && w16_plan(a, ssr_num_cu(), &pl)) ? 1 : 0;
 }
 
 extern "C" int ssrhip_gemv_w16(const ssrhip_gemv_args* a, const uint16_t* W16, ssrhip_stream_t stream) {
-  if (int rc = w16_check(a, W16)) return rc;
-  const int num_cu = ssr_num_cu();
-  const char* why;
-  if (!w16_qualifies(a, num_cu, &why)) return 1;
+  SSR_REQUIRE(a && a->W && a->y && W16, "ssrhip_gemv_w16: null argument");
+  SSR_REQUIRE(a->N > 0 && a->groups >= 1 && a->K > 0, "ssrhip_gemv_w16: bad N/K/groups");
+  SSR_REQUIRE(a->B == 1 || a->B == 2 || a->B == 4, "ssrhip_gemv_w16: B=%d not in {1,2,4} (the bf16 weight stream exists for the <= 4-row step only)", a->B);
+  if (int rc = gemv_small_check(a, "ssrhip_gemv_w16")) return rc;   // the contract of ssrhip_gemv: what it would refuse is refused here too
+  SegPlan pl;
+  if (!w16_plan(a, ssr_num_cu(), &pl)) return 1;
   hipStream_t s = (hipStream_t)stream;
   switch (a->B) {
-    case 1: w16_launch<1>(a, W16, num_cu, s); break;
-    case 2: w16_launch<2>(a, W16, num_cu, s); break;
-    default: w16_launch<4>(a, W16, num_cu, s); break;
+    case 1: w16_launch<1>(pl, W16, s); break;
+    case 2: w16_launch<2>(pl, W16, s); break;
+    default: w16_launch<4>(pl, W16, s); break;
   }
   SSR_LAUNCH_CHECK();
   return 0;

@@ -551,6 +551,53 @@ def test_gemv_seg_combine_and_qkv_append_at_2048(L, B, max_pages):
         want = y0 + F.linear(att.double(), Wo.double(), bo.double()).float()
         torch.testing.assert_close(dy.cpu(), want, rtol=3e-5, atol=3e-5)
 
+
+@pytest.mark.parametrize("B", [1, 2, 4])
+def test_gemv_seg_combine_gives_the_same_bits_at_one_and_two_workgroups_per_cu(L, B, monkeypatch):
+    """The merge prologue's workgroups per CU are a parameter of the segment plan (SSRHIP_GEMV_SEG_COMBINE_2, read at every call): 256 or
+    512 workgroups split N = 520 raggedly both ways, and a row's result must not depend on which workgroup owns it. Pages beyond a row
+    hold NaN, a poisoned tail sits behind y; both outputs against the fp64 merge + linear."""
+    N, K, H, hd, MS, PAD, POISON = 520, 2048, 16, 128, 3, 64, -777.25
+    g = torch.Generator().manual_seed(520 + B)
+    lens_l = [300, 129, 384, 1][:B]                                       # 3, 2, 3 and 1 pages of partials
+    part_o = torch.randn(B, H, MS, hd, generator=g)
+    part_ml = torch.stack([torch.randn(B, H, MS, generator=g) * 2, torch.rand(B, H, MS, generator=g) + 0.5], dim=-1).contiguous()
+    xin = torch.zeros(B, K, dtype=torch.float64)
+    for b in range(B):
+        n_pg = (lens_l[b] + _lib.PAGE - 1) // _lib.PAGE
+        m, l_ = part_ml[b, :, :n_pg, 0].double(), part_ml[b, :, :n_pg, 1].double()
+        e = torch.exp(m - m.max(dim=1, keepdim=True).values)
+        w = e / (e * l_).sum(dim=1, keepdim=True)                         # [H][pages]
+        xin[b] = (w.unsqueeze(-1) * part_o[b, :, :n_pg].double()).sum(dim=1).reshape(-1)
+        part_o[b, :, n_pg:] = float("nan")                                # what the kernel must not use
+        part_ml[b, :, n_pg:] = float("nan")
+    Wt = torch.randn(N, K, generator=g) / math.sqrt(K)
+    bias = torch.randn(N, generator=g)
+    y0 = torch.full((B * N + PAD,), POISON)
+    y0[:B * N] = torch.randn(B * N, generator=g)
+    want = (y0[:B * N].view(B, N).double() + F.linear(xin, Wt.double(), bias.double())).float()
+    d_po, d_pml, dW, db, dlen = dev(part_o), dev(part_ml), dev(Wt), dev(bias), dev(torch.tensor(lens_l, dtype=torch.int32))
+
+    def run():
+        dy = dev(y0.clone())
+        a = _lib.GemvArgs()
+        a.W, a.bias, a.y, a.B, a.N, a.K, a.groups, a.x_stride, a.y_stride = dW.data_ptr(), db.data_ptr(), dy.data_ptr(), B, N, K, 1, K, N
+        a.pro, a.act, a.epi = _lib.PRO_ATTN_COMBINE, 0, _lib.EPI_RESIDUAL
+        a.part_o, a.part_ml, a.max_splits, a.row_len = d_po.data_ptr(), d_pml.data_ptr(), MS, dlen.data_ptr()
+        a.kv = _lib.KV(0, 0, MS, 1, H, hd)
+        _lib.check(L.ssrhip_gemv(C.byref(a), _lib.stream_ptr()))
+        sync()
+        return dy.cpu()
+
+    monkeypatch.delenv("SSRHIP_GEMV_SEG_COMBINE_2", raising=False)
+    y_one = run()
+    monkeypatch.setenv("SSRHIP_GEMV_SEG_COMBINE_2", "1")
+    y_two = run()
+    assert torch.equal(y_one, y_two), float((y_one - y_two).abs().max())  # whole buffers, poison tail included
+    assert torch.equal(y_one[B * N:], y0[B * N:])
+    for y in (y_one, y_two):
+        torch.testing.assert_close(y[:B * N].view(B, N), want, rtol=3e-5, atol=3e-5)   # the bound of the test above
+
 # ------------------------------------------------------------------------------------------ attention
 def _make_cache(n_seq, max_pages, n_layer, H, hd, g):
     n_pages = n_seq * max_pages
