@@ -142,6 +142,14 @@ int ssrhip_gemv_w16_applicable(const ssrhip_gemv_args* a);
 int ssrhip_gemv_wt16(const ssrhip_gemv_args* a, const uint16_t* Wt16, ssrhip_stream_t stream);
 int ssrhip_gemv_wt16_applicable(const ssrhip_gemv_args* a);
 
+/* The same for 17..32 rows (csrc/gemv_mfma32_w16.hip: the two-panel kernels over the SAME packed copy `Wt16`, SSRHIP_WT16_INDEX): the
+ * result is BIT-IDENTICAL to ssrhip_gemv(a) at that row count on the fp32 streaming-order copy of the rounded master.
+ *   returns 0 = launched, 1 = `a` does not qualify and NOTHING was launched (call ssrhip_gemv(a)): B outside 17..32, w_tiled != 1 or
+ *   K % 64 != 0; < 0 = contract error, decided before any HIP call: what ssrhip_gemv refuses at these rows, e.g. a LayerNorm prologue with
+ *   K > 2048. SSRHIP_GEMVM_WPC / _NOPAIR act as on ssrhip_gemv. ssrhip_gemv_wt16 keeps answering 1 for these rows. */
+int ssrhip_gemv_wt32(const ssrhip_gemv_args* a, const uint16_t* Wt16, ssrhip_stream_t stream);
+int ssrhip_gemv_wt32_applicable(const ssrhip_gemv_args* a);
+
 /* Two consecutive launches of the 2-row decode step as ONE: `a` = a GEMV with the residual epilogue and `b` = the LayerNorm + Linear that
  * reads a's output, with the all-to-all edge between them inside the launch (csrc/gemv.hip gemv_pair_kernel / gemv_pair_merge_kernel:
  * tagged 8-byte granules, write-through stores, one gather round trip). Two forms:
@@ -490,6 +498,14 @@ int ssrhip_lm_set_wt16(ssrhip_lm* lm, const ssrhip_lm_w16* wt16);
 /* how many GEMV launches of the last enqueued (or captured) decode step ran a kernel of csrc/gemv_mfma_w16.hip (4 * n_layer + 2 when every
  * family qualifies); a counter of its own: ssrhip_lm_w16_launches stays 0 for these engines */
 int ssrhip_lm_wt16_launches(const ssrhip_lm* lm);
+/* The same for the 17..32-row decode step: the record is the one ssrhip_lm_set_wt16 takes (SSRHIP_WT16_INDEX copies; NULL = that family
+ * streams its fp32 streaming-order copy). Every GEMV launch of the step tries ssrhip_gemv_wt32 first and falls back to ssrhip_gemv; same
+ * tokens, bit for bit; the step stays one captured graph. Refused (< 0) for engines of <= 16 rows (the error names their setter), engines
+ * already captured and engines created without the fp32 streaming-order copies. */
+int ssrhip_lm_set_wt32(ssrhip_lm* lm, const ssrhip_lm_w16* wt16);
+/* how many GEMV launches of the last enqueued (or captured) decode step ran a kernel of csrc/gemv_mfma32_w16.hip (4 * n_layer + 2 when
+ * every family qualifies); the other two counters stay 0 for these engines */
+int ssrhip_lm_wt32_launches(const ssrhip_lm* lm);
 /* enqueue `n_steps` decode steps (graph replays when use_graph!=0) */
 int ssrhip_lm_decode(ssrhip_lm* lm, int32_t n_steps, int32_t use_graph, ssrhip_stream_t stream);
 /* prefill R rows ([text || audio] of every sequence, flattened): fills the cache for all layers.

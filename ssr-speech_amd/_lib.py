@@ -179,6 +179,8 @@ SYMBOLS = [
     ("ssrhip_gemv_w16_applicable", C.c_int, [C.POINTER(GemvArgs)]),
     ("ssrhip_gemv_wt16", C.c_int, [C.POINTER(GemvArgs), C.c_void_p, C.c_void_p]),
     ("ssrhip_gemv_wt16_applicable", C.c_int, [C.POINTER(GemvArgs)]),
+    ("ssrhip_gemv_wt32", C.c_int, [C.POINTER(GemvArgs), C.c_void_p, C.c_void_p]),
+    ("ssrhip_gemv_wt32_applicable", C.c_int, [C.POINTER(GemvArgs)]),
     ("ssrhip_pair_buffer", C.c_int, [C.c_int32, C.c_int32]),
     ("ssrhip_gemv_pair_applicable", C.c_int, [C.POINTER(GemvArgs), C.POINTER(GemvArgs)]),
     ("ssrhip_gemv_pair", C.c_int, [C.POINTER(GemvArgs), C.POINTER(GemvArgs), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
@@ -214,6 +216,8 @@ SYMBOLS = [
     ("ssrhip_lm_w16_launches", C.c_int, [C.c_void_p]),
     ("ssrhip_lm_set_wt16", C.c_int, [C.c_void_p, C.POINTER(LMW16)]),
     ("ssrhip_lm_wt16_launches", C.c_int, [C.c_void_p]),
+    ("ssrhip_lm_set_wt32", C.c_int, [C.c_void_p, C.POINTER(LMW16)]),
+    ("ssrhip_lm_wt32_launches", C.c_int, [C.c_void_p]),
     ("ssrhip_debug_occupy", C.c_int, [C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
     ("ssrhip_lm_time_steps", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, c_f32p, c_i32p, C.c_int32]),
     ("ssrhip_lm_time_category", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, c_f32p, c_i32p]),

@@ -71,11 +71,13 @@ struct ssrhip_lm {
   const uint16_t* head1_w16 = nullptr;
   const uint16_t* head2_w16 = nullptr;
   int w16_launches = 0;         // launches of the last enqueued step that ran a w16 kernel (ssrhip_lm_w16_launches)
-  // the same at 5..16 rows (ssrhip_lm_set_wt16): SSRHIP_WT16_INDEX copies, NULL = that matrix streams its fp32 streaming-order copy
+  // the same at 5..16 rows (ssrhip_lm_set_wt16) and at 17..32 rows (ssrhip_lm_set_wt32; an engine has one row count, so one record):
+  // SSRHIP_WT16_INDEX copies, NULL = that matrix streams its fp32 streaming-order copy
   std::vector<const uint16_t*> wt16[4];
   const uint16_t* head1_wt16 = nullptr;
   const uint16_t* head2_wt16 = nullptr;
   int wt16_launches = 0;        // launches of the last enqueued step that ran a kernel of gemv_mfma_w16.hip (ssrhip_lm_wt16_launches)
+  int wt32_launches = 0;        // ... of gemv_mfma32_w16.hip (ssrhip_lm_wt32_launches)
 };
 
 namespace {
@@ -332,14 +334,18 @@ int enqueue_step(ssrhip_lm* lm, hipStream_t s, Timer* tm) {
   };
   // Every single GEMV launch of the step goes through here: the packed bf16 copy of the matrix when the engine has one and the shape
   // qualifies (ssrhip_gemv_w16 answers 1 without launching when it does not), the fp32 weights otherwise. Same bits either way.
-  // An engine has either kind of packed copy, by its rows: SSRHIP_W16_INDEX at <= 4 (w16), SSRHIP_WT16_INDEX at 5..16 (wt16).
-  int n_w16 = 0, n_wt16 = 0;
+  // An engine has either kind of packed copy, by its rows: SSRHIP_W16_INDEX at <= 4 (w16), SSRHIP_WT16_INDEX at 5..32 (wt16: the 5..16-row
+  // kernels of gemv_mfma_w16.hip and the two-panel kernels of gemv_mfma32_w16.hip read the same copy).
+  int n_w16 = 0, n_wt16 = 0, n_wt32 = 0;
   auto gemv_call = [&](const ssrhip_gemv_args& ga, const W16Pair& pk) -> int {
     if (pk.w16) {
       const int rc = ssrhip_gemv_w16(&ga, pk.w16, (ssrhip_stream_t)s);
       if (rc <= 0) { n_w16 += rc == 0; return rc; }
     }
-    if (pk.wt16 && sh.B > 4) {
+    if (pk.wt16 && sh.B > 16) {
+      const int rc = ssrhip_gemv_wt32(&ga, pk.wt16, (ssrhip_stream_t)s);
+      if (rc <= 0) { n_wt32 += rc == 0; return rc; }
+    } else if (pk.wt16 && sh.B > 4) {
       const int rc = ssrhip_gemv_wt16(&ga, pk.wt16, (ssrhip_stream_t)s);
       if (rc <= 0) { n_wt16 += rc == 0; return rc; }
     }
@@ -415,7 +421,7 @@ int enqueue_step(ssrhip_lm* lm, hipStream_t s, Timer* tm) {
   STEP_CALL(CAT_GEMV, gemv_call(h2, W16Pair{lm->head2_w16, lm->head2_wt16}));
   const ssrhip_sample_args sa = sh.sample_args();
   STEP_CALL(CAT_SAMPLE, ssrhip_sample(&sa, s));
-  if (!tm || tm->only < 0) { lm->w16_launches = n_w16; lm->wt16_launches = n_wt16; }   // (a category-timing pass enqueues only part of a step)
+  if (!tm || tm->only < 0) { lm->w16_launches = n_w16; lm->wt16_launches = n_wt16; lm->wt32_launches = n_wt32; }   // (a category-timing pass enqueues only part of a step)
   return 0;
 }
 
@@ -533,12 +539,8 @@ extern "C" int ssrhip_lm_set_w16(ssrhip_lm* lm, const ssrhip_lm_w16* w16) {
 
 extern "C" int ssrhip_lm_w16_launches(const ssrhip_lm* lm) { return lm ? lm->w16_launches : 0; }
 
-extern "C" int ssrhip_lm_set_wt16(ssrhip_lm* lm, const ssrhip_lm_w16* wt16) {
-  SSR_REQUIRE(lm && wt16, "ssrhip_lm_set_wt16: null argument");
-  SSR_REQUIRE(lm->b.B > 4, "ssrhip_lm_set_wt16: engines of <= 4 rows stream bf16 weights through ssrhip_lm_set_w16 (this engine has %d rows)", lm->b.B);
-  SSR_REQUIRE(lm->b.B <= 16, "ssrhip_lm_set_wt16: the bf16 weight stream of the matrix-core step exists for 5..16 rows only (this engine has %d rows)", lm->b.B);
-  SSR_REQUIRE(!lm->exec, "ssrhip_lm_set_wt16: the decode step of this engine is already captured (call it before the first ssrhip_lm_decode)");
-  SSR_REQUIRE(lm->w.in_proj_wt, "ssrhip_lm_set_wt16: this engine was created without the fp32 streaming-order copies (ssrhip_lm_weights *_wt)");
+// the SSRHIP_WT16_INDEX record of an engine of 5..32 rows (ssrhip_lm_set_wt16 / ssrhip_lm_set_wt32, each after its own checks)
+static void lm_store_wt16(ssrhip_lm* lm, const ssrhip_lm_w16* wt16) {
   const uint16_t* const* src[4] = {wt16->in_proj_w16, wt16->out_proj_w16, wt16->ffn1_w16, wt16->ffn2_w16};
   for (int f = 0; f < 4; ++f) {
     if (src[f]) lm->wt16[f].assign(src[f], src[f] + lm->d.n_layer);
@@ -546,10 +548,32 @@ extern "C" int ssrhip_lm_set_wt16(ssrhip_lm* lm, const ssrhip_lm_w16* wt16) {
   }
   lm->head1_wt16 = wt16->head1_w16;
   lm->head2_wt16 = wt16->head2_w16;
+}
+
+extern "C" int ssrhip_lm_set_wt16(ssrhip_lm* lm, const ssrhip_lm_w16* wt16) {
+  SSR_REQUIRE(lm && wt16, "ssrhip_lm_set_wt16: null argument");
+  SSR_REQUIRE(lm->b.B > 4, "ssrhip_lm_set_wt16: engines of <= 4 rows stream bf16 weights through ssrhip_lm_set_w16 (this engine has %d rows)", lm->b.B);
+  SSR_REQUIRE(lm->b.B <= 16, "ssrhip_lm_set_wt16: the bf16 weight stream of the matrix-core step exists for 5..16 rows only (this engine has %d rows)", lm->b.B);
+  SSR_REQUIRE(!lm->exec, "ssrhip_lm_set_wt16: the decode step of this engine is already captured (call it before the first ssrhip_lm_decode)");
+  SSR_REQUIRE(lm->w.in_proj_wt, "ssrhip_lm_set_wt16: this engine was created without the fp32 streaming-order copies (ssrhip_lm_weights *_wt)");
+  lm_store_wt16(lm, wt16);
   return 0;
 }
 
 extern "C" int ssrhip_lm_wt16_launches(const ssrhip_lm* lm) { return lm ? lm->wt16_launches : 0; }
+
+extern "C" int ssrhip_lm_set_wt32(ssrhip_lm* lm, const ssrhip_lm_w16* wt16) {
+  SSR_REQUIRE(lm && wt16, "ssrhip_lm_set_wt32: null argument");
+  SSR_REQUIRE(lm->b.B > 4, "ssrhip_lm_set_wt32: engines of <= 4 rows stream bf16 weights through ssrhip_lm_set_w16 (this engine has %d rows)", lm->b.B);
+  SSR_REQUIRE(lm->b.B > 16, "ssrhip_lm_set_wt32: engines of 5..16 rows stream bf16 weights through ssrhip_lm_set_wt16 (this engine has %d rows)", lm->b.B);
+  SSR_REQUIRE(lm->b.B <= 32, "ssrhip_lm_set_wt32: the bf16 weight stream of the two-panel step exists for 17..32 rows only (this engine has %d rows)", lm->b.B);
+  SSR_REQUIRE(!lm->exec, "ssrhip_lm_set_wt32: the decode step of this engine is already captured (call it before the first ssrhip_lm_decode)");
+  SSR_REQUIRE(lm->w.in_proj_wt, "ssrhip_lm_set_wt32: this engine was created without the fp32 streaming-order copies (ssrhip_lm_weights *_wt)");
+  lm_store_wt16(lm, wt16);
+  return 0;
+}
+
+extern "C" int ssrhip_lm_wt32_launches(const ssrhip_lm* lm) { return lm ? lm->wt32_launches : 0; }
 
 extern "C" int ssrhip_lm_pair_status(ssrhip_lm* lm, ssrhip_stream_t stream) {
   SSR_REQUIRE(lm, "ssrhip_lm_pair_status: null engine");

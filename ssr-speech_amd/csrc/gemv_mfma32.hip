@@ -28,107 +28,6 @@ namespace {
 // x panels and both epilogues without scratch, so the depth is halved (8 KiB per wave, 64 KiB per CU); the k-step-pair forms keep theirs.
 constexpr int DEP32 = 8;
 
-// The launch seen from one 16-column panel: panel 1 is rows 16..B-1 as a (B-16)-row launch, so the 16-row tile epilogue applies unchanged.
-__device__ __forceinline__ ssrhip_gemv_args panel_args(const ssrhip_gemv_args& a, int p) {
-  ssrhip_gemv_args q = a;
-  if (p == 0) { q.B = 16; return q; }
-  q.B = a.B - 16;
-  q.y = a.y + (a.y_tiled ? (size_t)16 * a.N * a.groups : (size_t)16 * a.y_stride);
-  if (a.kv_pos) q.kv_pos = a.kv_pos + 16;
-  if (a.kv.table) q.kv.table = a.kv.table + (size_t)16 * a.kv.max_pages;
-  return q;
-}
-
-// per-lane x pointer of panel p at k-step 0 (tiled: one contiguous KiB per wave instruction per k-step; row-major: row clamped to B-1)
-__device__ __forceinline__ const float* panel_xptr(const ssrhip_gemv_args& a, int grp, int p, int c, int ks) {
-  if (a.x_tiled) return a.x + (size_t)p * 16 * a.K * a.groups + (size_t)grp * a.K * 16 + (unsigned)(ks * 16 + c) * 4;
-  return a.x + (size_t)grp * a.K + (size_t)min(16 * p + c, a.B - 1) * a.x_stride + ks * 4;
-}
-
-// two-pass LayerNorm statistics of one panel's wave slice (the expressions of gemv_rows_xreg_kernel)
-template <int SPWX>
-__device__ __forceinline__ void ln_slice(const float4 (&xr)[SPWX], int tbase, int last, float* mw_out, float* q_out) {
-  const int nval = max(0, min(SPWX, last + 1 - tbase)) * 16;
-  float s = 0.f;
-#pragma unroll
-  for (int t = 0; t < SPWX; ++t) s += (xr[t].x + xr[t].y) + (xr[t].z + xr[t].w);
-  s = kslot_sum(s);
-  const float mw = nval > 0 ? s / (float)nval : 0.f;
-  float q = 0.f;
-#pragma unroll
-  for (int t = 0; t < SPWX; ++t) {
-    if (tbase + t <= last) {
-      const float dx = xr[t].x - mw, dy = xr[t].y - mw, dz = xr[t].z - mw, dw = xr[t].w - mw;
-      q += (dx * dx + dy * dy) + (dz * dz + dw * dw);
-    }
-  }
-  *mw_out = mw;
-  *q_out = kslot_sum(q);
-}
-
-template <int SPWX>
-__device__ __forceinline__ void ln_apply(float4 (&xr)[SPWX], const float (&red)[2][8][16], int nw, int c, int tbase, int last, int K, float eps) {
-  float mean = 0.f;
-  for (int v = 0; v < nw; ++v) mean += red[0][v][c] * (float)(max(0, min(SPWX, last + 1 - v * SPWX)) * 16);
-  mean /= (float)K;
-  float var = 0.f;
-  for (int v = 0; v < nw; ++v) {
-    const float d = red[0][v][c] - mean;
-    var += red[1][v][c] + (float)(max(0, min(SPWX, last + 1 - v * SPWX)) * 16) * d * d;
-  }
-  var /= (float)K;
-  const float rstd = 1.0f / sqrtf(var + eps);
-#pragma unroll
-  for (int t = 0; t < SPWX; ++t) {
-    if (tbase + t <= last) {
-      xr[t].x = (xr[t].x - mean) * rstd;
-      xr[t].y = (xr[t].y - mean) * rstd;
-      xr[t].z = (xr[t].z - mean) * rstd;
-      xr[t].w = (xr[t].w - mean) * rstd;
-    }
-  }
-}
-
-// one k-step against both panels: the a0 / a1 interleave of the 16-row kernels, once per panel, on the same weight fragment
-__device__ __forceinline__ void kstep2(const float4 wv, const float4 xa, const float4 xb, f4v& a0, f4v& a1, f4v& b0, f4v& b1) {
-  a0 = mfma4(wv.x, xa.x, a0);
-  a1 = mfma4(wv.y, xa.y, a1);
-  b0 = mfma4(wv.x, xb.x, b0);
-  b1 = mfma4(wv.y, xb.y, b1);
-  a0 = mfma4(wv.z, xa.z, a0);
-  a1 = mfma4(wv.w, xa.w, a1);
-  b0 = mfma4(wv.z, xb.z, b0);
-  b1 = mfma4(wv.w, xb.w, b1);
-}
-
-// one k-step PAIR against both panels (k-step-pair form, see gemv_rows_xreg_kernel's PAIR): per panel the aA / aB order of the 16-row kernel
-__device__ __forceinline__ void kpair2(const float4 wv, const float4 xa0, const float4 xb0, const float4 xa1, const float4 xb1,
-                                       f4v& aA0, f4v& aB0, f4v& aA1, f4v& aB1) {
-  aA0 = mfma4(wv.x, xa0.x, aA0);
-  aB0 = mfma4(wv.x, xb0.x, aB0);
-  aA1 = mfma4(wv.x, xa1.x, aA1);
-  aB1 = mfma4(wv.x, xb1.x, aB1);
-  aA0 = mfma4(wv.y, xa0.y, aA0);
-  aB0 = mfma4(wv.y, xb0.y, aB0);
-  aA1 = mfma4(wv.y, xa1.y, aA1);
-  aB1 = mfma4(wv.y, xb1.y, aB1);
-  aA0 = mfma4(wv.z, xa0.z, aA0);
-  aB0 = mfma4(wv.z, xb0.z, aB0);
-  aA1 = mfma4(wv.z, xa1.z, aA1);
-  aB1 = mfma4(wv.z, xb1.z, aB1);
-  aA0 = mfma4(wv.w, xa0.w, aA0);
-  aB0 = mfma4(wv.w, xb0.w, aB0);
-  aA1 = mfma4(wv.w, xa1.w, aA1);
-  aB1 = mfma4(wv.w, xb1.w, aB1);
-}
-
-__device__ __forceinline__ f4v pair_fold(f4v aA, f4v aB) {
-  f4v acc;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) acc[e] = aA[e] + xor32_f(aB[e]);          // rows 0..7 (lanes < 32) = own rows + rows 8..15 of lane + 32
-  return acc;
-}
-
 // K <= 2048 (SPWX = 16 k-steps per wave): both x panels of the wave's K slice in VGPRs for all of the workgroup's tiles.
 template <int PRO, bool PAIR>
 __global__ __launch_bounds__(512) void gemv_rows32_xreg(const GemvR p) {

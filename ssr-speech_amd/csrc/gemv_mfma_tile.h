@@ -1,6 +1,7 @@
-// gemv_mfma_tile.h — pieces shared by the matrix-core GEMV kernels (gemv_mfma.hip: 5..16 rows, gemv_mfma32.hip: 17..32 rows):
-// the 16x16x4 fp32 MFMA, the k-slot reduction, the per-lane weight pointer of a tile and the split tile epilogue; and, for the host, the
-// argument check and the launch plan of the rows-per-workgroup kernels, which both launchers take from here.
+// gemv_mfma_tile.h — pieces shared by the matrix-core GEMV kernels (gemv_mfma.hip: 5..16 rows, gemv_mfma32.hip: 17..32 rows, and their
+// bf16 weight streams gemv_mfma_w16.hip / gemv_mfma32_w16.hip): the 16x16x4 fp32 MFMA, the k-slot reduction, the per-lane weight pointer of
+// a tile and the split tile epilogue; the two-panel helpers of the 17..32-row kernels; the loads and the widening of the packed bf16 layout;
+// and, for the host, the argument check and the launch plan of the rows-per-workgroup kernels, which every launcher takes from here.
 #pragma once
 #include "common.h"
 
@@ -124,6 +125,109 @@ __device__ __forceinline__ const float* tile_wptr(const float* wbase, int row_lo
   return wbase + (size_t)min(rr, N - 1) * K + ks * 4;
 }
 
+// ---- two 16-column panels per launch (17..32 rows): gemv_mfma32.hip and its bf16 stream gemv_mfma32_w16.hip ----
+
+// The launch seen from one 16-column panel: panel 1 is rows 16..B-1 as a (B-16)-row launch, so the 16-row tile epilogue applies unchanged.
+__device__ __forceinline__ ssrhip_gemv_args panel_args(const ssrhip_gemv_args& a, int p) {
+  ssrhip_gemv_args q = a;
+  if (p == 0) { q.B = 16; return q; }
+  q.B = a.B - 16;
+  q.y = a.y + (a.y_tiled ? (size_t)16 * a.N * a.groups : (size_t)16 * a.y_stride);
+  if (a.kv_pos) q.kv_pos = a.kv_pos + 16;
+  if (a.kv.table) q.kv.table = a.kv.table + (size_t)16 * a.kv.max_pages;
+  return q;
+}
+
+// per-lane x pointer of panel p at k-step 0 (tiled: one contiguous KiB per wave instruction per k-step; row-major: row clamped to B-1)
+__device__ __forceinline__ const float* panel_xptr(const ssrhip_gemv_args& a, int grp, int p, int c, int ks) {
+  if (a.x_tiled) return a.x + (size_t)p * 16 * a.K * a.groups + (size_t)grp * a.K * 16 + (unsigned)(ks * 16 + c) * 4;
+  return a.x + (size_t)grp * a.K + (size_t)min(16 * p + c, a.B - 1) * a.x_stride + ks * 4;
+}
+
+// two-pass LayerNorm statistics of one panel's wave slice (the expressions of gemv_rows_xreg_kernel)
+template <int SPWX>
+__device__ __forceinline__ void ln_slice(const float4 (&xr)[SPWX], int tbase, int last, float* mw_out, float* q_out) {
+  const int nval = max(0, min(SPWX, last + 1 - tbase)) * 16;
+  float s = 0.f;
+#pragma unroll
+  for (int t = 0; t < SPWX; ++t) s += (xr[t].x + xr[t].y) + (xr[t].z + xr[t].w);
+  s = kslot_sum(s);
+  const float mw = nval > 0 ? s / (float)nval : 0.f;
+  float q = 0.f;
+#pragma unroll
+  for (int t = 0; t < SPWX; ++t) {
+    if (tbase + t <= last) {
+      const float dx = xr[t].x - mw, dy = xr[t].y - mw, dz = xr[t].z - mw, dw = xr[t].w - mw;
+      q += (dx * dx + dy * dy) + (dz * dz + dw * dw);
+    }
+  }
+  *mw_out = mw;
+  *q_out = kslot_sum(q);
+}
+
+template <int SPWX>
+__device__ __forceinline__ void ln_apply(float4 (&xr)[SPWX], const float (&red)[2][8][16], int nw, int c, int tbase, int last, int K, float eps) {
+  float mean = 0.f;
+  for (int v = 0; v < nw; ++v) mean += red[0][v][c] * (float)(max(0, min(SPWX, last + 1 - v * SPWX)) * 16);
+  mean /= (float)K;
+  float var = 0.f;
+  for (int v = 0; v < nw; ++v) {
+    const float d = red[0][v][c] - mean;
+    var += red[1][v][c] + (float)(max(0, min(SPWX, last + 1 - v * SPWX)) * 16) * d * d;
+  }
+  var /= (float)K;
+  const float rstd = 1.0f / sqrtf(var + eps);
+#pragma unroll
+  for (int t = 0; t < SPWX; ++t) {
+    if (tbase + t <= last) {
+      xr[t].x = (xr[t].x - mean) * rstd;
+      xr[t].y = (xr[t].y - mean) * rstd;
+      xr[t].z = (xr[t].z - mean) * rstd;
+      xr[t].w = (xr[t].w - mean) * rstd;
+    }
+  }
+}
+
+// one k-step against both panels: the a0 / a1 interleave of the 16-row kernels, once per panel, on the same weight fragment
+__device__ __forceinline__ void kstep2(const float4 wv, const float4 xa, const float4 xb, f4v& a0, f4v& a1, f4v& b0, f4v& b1) {
+  a0 = mfma4(wv.x, xa.x, a0);
+  a1 = mfma4(wv.y, xa.y, a1);
+  b0 = mfma4(wv.x, xb.x, b0);
+  b1 = mfma4(wv.y, xb.y, b1);
+  a0 = mfma4(wv.z, xa.z, a0);
+  a1 = mfma4(wv.w, xa.w, a1);
+  b0 = mfma4(wv.z, xb.z, b0);
+  b1 = mfma4(wv.w, xb.w, b1);
+}
+
+// one k-step PAIR against both panels (k-step-pair form, see gemv_rows_xreg_kernel's PAIR): per panel the aA / aB order of the 16-row kernel
+__device__ __forceinline__ void kpair2(const float4 wv, const float4 xa0, const float4 xb0, const float4 xa1, const float4 xb1,
+                                       f4v& aA0, f4v& aB0, f4v& aA1, f4v& aB1) {
+  aA0 = mfma4(wv.x, xa0.x, aA0);
+  aB0 = mfma4(wv.x, xb0.x, aB0);
+  aA1 = mfma4(wv.x, xa1.x, aA1);
+  aB1 = mfma4(wv.x, xb1.x, aB1);
+  aA0 = mfma4(wv.y, xa0.y, aA0);
+  aB0 = mfma4(wv.y, xb0.y, aB0);
+  aA1 = mfma4(wv.y, xa1.y, aA1);
+  aB1 = mfma4(wv.y, xb1.y, aB1);
+  aA0 = mfma4(wv.z, xa0.z, aA0);
+  aB0 = mfma4(wv.z, xb0.z, aB0);
+  aA1 = mfma4(wv.z, xa1.z, aA1);
+  aB1 = mfma4(wv.z, xb1.z, aB1);
+  aA0 = mfma4(wv.w, xa0.w, aA0);
+  aB0 = mfma4(wv.w, xb0.w, aB0);
+  aA1 = mfma4(wv.w, xa1.w, aA1);
+  aB1 = mfma4(wv.w, xb1.w, aB1);
+}
+
+__device__ __forceinline__ f4v pair_fold(f4v aA, f4v aB) {
+  f4v acc;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) acc[e] = aA[e] + xor32_f(aB[e]);          // rows 0..7 (lanes < 32) = own rows + rows 8..15 of lane + 32
+  return acc;
+}
+
 // ---- host: one argument check and one launch plan for the rows-per-workgroup kernels at 5..32 rows ----
 
 // Parameter of the rows-per-workgroup kernels (gemv_rows_*_kernel at 5..16 rows, gemv_rows32_* at 17..32)
@@ -138,6 +242,34 @@ struct GemvR {
 };
 
 constexpr int MAXT = 4;     // 16-row tiles per workgroup (LDS: MAXT x 8 waves x 1 KiB of partial sums, per column panel)
+
+// ---- packed bf16 weights (include/ssrhip.h SSRHIP_WT16_INDEX): gemv_mfma_w16.hip (5..16 rows) and gemv_mfma32_w16.hip (17..32 rows) ----
+
+typedef unsigned wt16_v4u __attribute__((ext_vector_type(4)));
+
+struct GemvWt16 {
+  GemvR r;               // the fp32 launch's parameter, from the same plan
+  const uint16_t* w16;   // [groups][units * 8][K] in SSRHIP_WT16_INDEX order
+};
+
+// 8 packed bf16 of a streamed-once weight block: non-temporal 16-byte load (global_load_dwordx4 ... nt)
+__device__ __forceinline__ wt16_v4u ldw_nt(const uint16_t* p) { return __builtin_nontemporal_load(reinterpret_cast<const wt16_v4u*>(p)); }
+
+// the float4 of one k-step: half g of a 16-byte piece (g = 0: dwords 0, 1; g = 1: dwords 2, 3); element 2m in the low half of a dword
+__device__ __forceinline__ float4 wt16_widen(const wt16_v4u u, int g) {
+  const unsigned d0 = g ? u.z : u.x, d1 = g ? u.w : u.y;
+  return make_float4(__uint_as_float(d0 << 16), __uint_as_float(d0 & 0xffff0000u), __uint_as_float(d1 << 16), __uint_as_float(d1 & 0xffff0000u));
+}
+
+// per-lane pointer to (row of this lane in tile `tile`, k-slot of this lane) of the packed matrix: block (unit, quad 0, h = 0)
+__device__ __forceinline__ const uint16_t* wt16_ptr(const uint16_t* wbase, int row_lo, int nun, int tile, int c, int ks, int K) {
+  const int rows = (2 * tile + 1 < nun) ? 16 : 8;
+  const int rr = row_lo + tile * 16 + (c & (rows - 1));
+  return wbase + (size_t)(rr >> 3) * 8 * K + (ks * 8 + (rr & 7)) * 8;     // units are zero-padded: no row clamp
+}
+
+// uint16 offset of load m (m = 2 * quad + h, counted from the wave's first quad `qbase`) behind wt16_ptr; quads past the end are clamped
+__device__ __forceinline__ int wt16_off(int qbase, int m, int lastq) { return (min(qbase + (m >> 1), lastq) * 2 + (m & 1)) * 256; }
 
 // What ssrhip_gemv has not checked when it hands 5..32 rows to a matrix-core launcher. Runs before the first HIP runtime call.
 // [b_lo, b_hi]: the rows the launcher's kernels take; ln_kmax: the largest K whose LayerNorm prologue they fuse.

@@ -32,32 +32,6 @@
 
 namespace {
 
-typedef unsigned wt16_v4u __attribute__((ext_vector_type(4)));
-
-struct GemvWt16 {
-  GemvR r;               // the fp32 launch's parameter, from the same plan
-  const uint16_t* w16;   // [groups][units * 8][K] in SSRHIP_WT16_INDEX order
-};
-
-// 8 packed bf16 of a streamed-once weight block: non-temporal 16-byte load (global_load_dwordx4 ... nt)
-__device__ __forceinline__ wt16_v4u ldw_nt(const uint16_t* p) { return __builtin_nontemporal_load(reinterpret_cast<const wt16_v4u*>(p)); }
-
-// the float4 of one k-step: half g of a 16-byte piece (g = 0: dwords 0, 1; g = 1: dwords 2, 3); element 2m in the low half of a dword
-__device__ __forceinline__ float4 wt16_widen(const wt16_v4u u, int g) {
-  const unsigned d0 = g ? u.z : u.x, d1 = g ? u.w : u.y;
-  return make_float4(__uint_as_float(d0 << 16), __uint_as_float(d0 & 0xffff0000u), __uint_as_float(d1 << 16), __uint_as_float(d1 & 0xffff0000u));
-}
-
-// per-lane pointer to (row of this lane in tile `tile`, k-slot of this lane) of the packed matrix: block (unit, quad 0, h = 0)
-__device__ __forceinline__ const uint16_t* wt16_ptr(const uint16_t* wbase, int row_lo, int nun, int tile, int c, int ks, int K) {
-  const int rows = (2 * tile + 1 < nun) ? 16 : 8;
-  const int rr = row_lo + tile * 16 + (c & (rows - 1));
-  return wbase + (size_t)(rr >> 3) * 8 * K + (ks * 8 + (rr & 7)) * 8;     // units are zero-padded: no row clamp
-}
-
-// uint16 offset of load m (m = 2 * quad + h, counted from the wave's first quad `qbase`) behind wt16_ptr; quads past the end are clamped
-__device__ __forceinline__ int wt16_off(int qbase, int m, int lastq) { return (min(qbase + (m >> 1), lastq) * 2 + (m & 1)) * 256; }
-
 // x in registers (K <= 2048: SPWX = 16 k-steps per wave; LayerNorm launches up to K = 4096: SPWX = 32): gemv_rows_xreg_kernel over bf16.
 // NT = 0: a ring of DL loads that rolls over the workgroup's tiles. NT = 2 (host-selected when EVERY workgroup owns exactly two tiles: QKV,
 // FFN1 at 830M): no ring — both tiles' loads, 2 x SPWX / 2 = 16 per wave (16 KiB, the fp32 kernels' bytes in flight), are requested at

@@ -100,6 +100,9 @@ WEIGHT_DTYPES = ("fp32", "bf16")
 # What an unset SSRHIP_GEMVM_W16 means for a 5..16-row engine of a bf16 arena (DecodeEngine stream_wt16=None): "1" = stream the
 # SSRHIP_WT16_INDEX copies, "0" = stream the fp32 streaming-order masters. Decided by the measurement in DESIGN.md Part I.11.
 WT16_DEFAULT = "0"
+# The same switch for a 17..32-row engine of a bf16 arena (DecodeEngine stream_wt32=None): "1" = the two-panel step streams the same
+# SSRHIP_WT16_INDEX copies. Decided by the measurement in DESIGN.md Part I.12.
+WT32_DEFAULT = "0"
 
 
 def w16_streamable(K: int) -> bool:
@@ -510,7 +513,7 @@ class DecodeEngine:
 
     def __init__(self, arena: LMWeightsArena, n_utt: int, use_cfg: bool, max_seq: int, max_steps: int, debug_logits: bool = False,
                  pool_pages: Optional[int] = None, page_order: Optional[Sequence[int]] = None, pair_mode: int = 0,
-                 stream_w16: Optional[bool] = None, stream_wt16: Optional[bool] = None):
+                 stream_w16: Optional[bool] = None, stream_wt16: Optional[bool] = None, stream_wt32: Optional[bool] = None):
         """max_seq: longest sequence (text + audio positions) any ONE row may reach; pool_pages: physical KV pages shared by all
         rows (default rows x pages-per-row, the no-sharing worst case; a batch of short and long utterances needs only the sum
         of their own page counts). pair_mode (2-row engines; include/ssrhip.h ssrhip_lm_buffers): 0 = pair launches if this engine
@@ -519,7 +522,8 @@ class DecodeEngine:
         is bf16, the engine has <= 4 rows and `SSRHIP_GEMV_W16` (read here) does not start with '0'. stream_wt16: the same for the 5..16-row
         matrix-core step (ssrhip_lm_set_wt16: SSRHIP_WT16_INDEX copies beside the fp32 streaming-order copies, which stay the fallback);
         None = on when the arena is bf16, the engine has 5..16 rows and `SSRHIP_GEMVM_W16` (read here; unset = WT16_DEFAULT) does not
-        start with '0'."""
+        start with '0'. stream_wt32: the same for the 17..32-row two-panel step (ssrhip_lm_set_wt32, the same SSRHIP_WT16_INDEX copies); None =
+        on when the arena is bf16, the engine has 17..32 rows and `SSRHIP_GEMVM_W16` (unset = WT32_DEFAULT) does not start with '0'."""
         self.lib = _lib.lib()
         self.a = arena
         dev = arena.device
@@ -546,6 +550,15 @@ class DecodeEngine:
         elif stream_wt16 and arena.weight_dtype != "bf16":
             raise ValueError("stream_wt16 needs an arena built with weight_dtype='bf16'")
         self.stream_wt16 = bool(stream_wt16)
+        if stream_wt32 is None:
+            stream_wt32 = arena.weight_dtype == "bf16" and self.B > 16 and os.environ.get("SSRHIP_GEMVM_W16", WT32_DEFAULT)[:1] != "0"
+        elif stream_wt32 and self.B <= 4:
+            raise ValueError(f"stream_wt32 is the bf16 weight stream of the 17..32-row step; an engine of {self.B} rows takes stream_w16")
+        elif stream_wt32 and self.B <= 16:
+            raise ValueError(f"stream_wt32 is the bf16 weight stream of the 17..32-row step; an engine of {self.B} rows takes stream_wt16")
+        elif stream_wt32 and arena.weight_dtype != "bf16":
+            raise ValueError("stream_wt32 needs an arena built with weight_dtype='bf16'")
+        self.stream_wt32 = bool(stream_wt32)
         self.max_pages = (max_seq + PAGE - 1) // PAGE
         self.max_seq = self.max_pages * PAGE
         arena.ensure_positions(self.max_seq)      # every text / audio position of a row is < its sequence capacity
@@ -554,8 +567,8 @@ class DecodeEngine:
         arena.ensure_split_planes()               # the prefill GEMMs run on the bf16 matrix cores with exactly split operands
         if self.stream_w16:
             arena.ensure_w16_copies()             # the <= 4-row step streams packed 2-byte weights
-        if self.stream_wt16:
-            arena.ensure_wt16_copies()            # the 5..16-row step streams packed 2-byte weights in streaming order
+        if self.stream_wt16 or self.stream_wt32:
+            arena.ensure_wt16_copies()            # the 5..32-row step streams packed 2-byte weights in streaming order
         self.max_steps = max_steps
         D, H, L, K = arena.D, arena.H, arena.L, arena.K
         self.hd = D // H
@@ -643,6 +656,9 @@ class DecodeEngine:
         if self.stream_wt16:                      # before the first step is enqueued or captured
             wt16 = self.a.wt16_struct()
             _lib.check(self.lib.ssrhip_lm_set_wt16(ctx, C.byref(wt16)), "ssrhip_lm_set_wt16")
+        if self.stream_wt32:                      # the same record, read by the two-panel kernels
+            wt16 = self.a.wt16_struct()
+            _lib.check(self.lib.ssrhip_lm_set_wt32(ctx, C.byref(wt16)), "ssrhip_lm_set_wt32")
         why = C.create_string_buffer(256)
         self.pairing = bool(self.lib.ssrhip_lm_pairing(ctx, why, 256))
         self.pairing_why = why.value.decode(errors="replace")
@@ -658,6 +674,12 @@ class DecodeEngine:
         """GEMV launches of the last enqueued decode step that ran a kernel of the 5..16-row bf16 weight stream (4 * layers + 2 when every
         family qualifies; 0 for an engine that streams fp32 weights or has not stepped yet)."""
         return 0 if self._ctx is None else int(self.lib.ssrhip_lm_wt16_launches(self._ctx))
+
+    @property
+    def wt32_launches_per_step(self) -> int:
+        """GEMV launches of the last enqueued decode step that ran a kernel of the 17..32-row bf16 weight stream (4 * layers + 2 when every
+        family qualifies; 0 for an engine that streams fp32 weights or has not stepped yet)."""
+        return 0 if self._ctx is None else int(self.lib.ssrhip_lm_wt32_launches(self._ctx))
 
     def close(self):
         if self._ctx is not None:

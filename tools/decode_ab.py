@@ -15,6 +15,8 @@ weight_dtype="bf16" (rounded masters + packed copies, 3.3 + 1.65 GB beside the f
 (`tokens == <first variant>` is then expected to be False across dtypes and True between the two bf16 arms.)
 The same at 5..16 rows (DESIGN.md Part I.11; `SSRHIP_GEMVM_W16` is the switch of those engines, `wt16 launches` their counter):
   python tools/decode_ab.py --utts 8 --greedy --warmup 180 --steps 100 fp32: bf16_masters:weight_dtype=bf16,SSRHIP_GEMVM_W16=0 bf16_wt16:weight_dtype=bf16,SSRHIP_GEMVM_W16=1
+and at 17..32 rows (DESIGN.md Part I.12; the same switch, `wt32 launches` the counter):
+  python tools/decode_ab.py --utts 16 --greedy --warmup 180 --steps 100 fp32: bf16_masters:weight_dtype=bf16,SSRHIP_GEMVM_W16=0 bf16_wt32:weight_dtype=bf16,SSRHIP_GEMVM_W16=1
 """
 import argparse
 import dataclasses
@@ -70,7 +72,7 @@ for u in range(max(utts_of.values())):
 kn = DecodeKnobs(top_k=1 if a.greedy else 40, top_p=1.0 if a.greedy else 0.8, temperature=1.0, stop_repetition=2, cfg_coef=1.5, cfg_stride=5,
                  use_cfg=True, text_len=L, n_spans=num_task, seed=2024)
 
-res = {name: {"ms": [], "gemv": [], "attn": [], "sample": [], "tok": None, "w16": 0, "wt16": 0} for name, _ in variants}
+res = {name: {"ms": [], "gemv": [], "attn": [], "sample": [], "tok": None, "w16": 0, "wt16": 0, "wt32": 0} for name, _ in variants}
 for rep in range(a.reps):
     for name, knobs in variants:
         for k in all_knobs:
@@ -91,6 +93,7 @@ for rep in range(a.reps):
         r = res[name]
         r["w16"] = eng.w16_launches_per_step
         r["wt16"] = eng.wt16_launches_per_step
+        r["wt32"] = eng.wt32_launches_per_step
         r["ms"].append(ms)
         r["gemv"].append(eng.time_category("gemv", 50)[0])
         r["attn"].append(eng.time_category("attn", 50)[0])
@@ -112,4 +115,4 @@ for name, knobs in variants:
     print(f"{name:14s} {U:2d} utts x CFG = {2 * U:2d} rows  tok/s {4 * U / (statistics.median(r['ms']) * 1e-3):9.1f}  "
           f"ms/step min {min(r['ms']):.4f} med {statistics.median(r['ms']):.4f}  all {' '.join(f'{v:.4f}' for v in r['ms'])} | "
           f"gemv {min(r['gemv']):.3f} x {r['launches']['gemv']} attn {min(r['attn']):.3f} x {r['launches']['attn']} "
-          f"sample {min(r['sample']):.3f} x {r['launches']['sample']} us{same}   [{dtype_of[name]}, {r['w16']} w16 + {r['wt16']} wt16 launches; {' '.join(f'{k}={v}' for k, v in knobs.items()) or 'defaults'}]")
+          f"sample {min(r['sample']):.3f} x {r['launches']['sample']} us{same}   [{dtype_of[name]}, {r['w16']} w16 + {r['wt16']} wt16 + {r['wt32']} wt32 launches; {' '.join(f'{k}={v}' for k, v in knobs.items()) or 'defaults'}]")

@@ -8,6 +8,8 @@ of the two groupings are identical. The first pass of each grouping (engine buil
 masters (SSRHIP_GEMVM_W16=0) against one that streams the packed bf16 streaming-order copies (SSRHIP_GEMVM_W16=1; DESIGN.md Part I.11):
 the arena and the engine are rebuilt for every arm of every round (the switch is read when an engine is built), one untimed pass, one timed.
   python tools/dp64_group_ab.py --wt16 --reps 2 --out profiles/wt16_dp64_group8.json
+`--wt32` is the same comparison at group 16 = 32 rows (the two-panel step's bf16 stream, DESIGN.md Part I.12; identical tokens asserted):
+  python tools/dp64_group_ab.py --wt32 --reps 2 --out profiles/wt32_dp64_group16.json
 """
 import argparse
 import json
@@ -29,6 +31,7 @@ ap.add_argument("--reps", type=int, default=2)
 ap.add_argument("--groups", default="8,16")
 ap.add_argument("--out", default=None)
 ap.add_argument("--wt16", action="store_true", help="bf16 model, group 8: fp32 masters against the packed bf16 stream of the 16-row step")
+ap.add_argument("--wt32", action="store_true", help="bf16 model, group 16: fp32 masters against the packed bf16 stream of the 32-row step")
 a = ap.parse_args()
 
 dev = torch.device("cuda", 0)
@@ -45,10 +48,11 @@ for i in range(64):
 kw = dict(top_k=1, top_p=1.0, temperature=1.0, stop_repetition=2, cfg_coef=1.5, cfg_stride=5, aug_text=True)
 groups = [int(g) for g in a.groups.split(",")]
 
-if a.wt16:
-    g = groups[0]
-    arms = (("bf16_masters", "0"), ("bf16_wt16", "1"))
-    res = {name: {"decode_ms": [], "tokens": None, "wt16_launches": 0} for name, _ in arms}
+if a.wt16 or a.wt32:
+    kind = "wt32" if a.wt32 else "wt16"
+    g = 16 if a.wt32 else groups[0]
+    arms = (("bf16_masters", "0"), ("bf16_" + kind, "1"))
+    res = {name: {"decode_ms": [], "tokens": None, "launches": 0} for name, _ in arms}
     for rep in range(a.reps):
         for name, sw in arms:
             os.environ["SSRHIP_GEMVM_W16"] = sw
@@ -60,7 +64,7 @@ if a.wt16:
             toks, _ = dp.generate(model, utts, seed=0, group=g, **kw)
             torch.cuda.synchronize()
             res[name]["decode_ms"].append(1000 * (time.perf_counter() - t0))
-            res[name]["wt16_launches"] = next(iter(model._engines.values())).wt16_launches_per_step
+            res[name]["launches"] = getattr(next(iter(model._engines.values())), kind + "_launches_per_step")
             if res[name]["tokens"] is None:
                 res[name]["tokens"] = [t.cpu() for t in toks]
     ref = res["bf16_masters"]["tokens"]
@@ -70,8 +74,8 @@ if a.wt16:
     for name, _ in arms:
         best = min(res[name]["decode_ms"])
         out[name] = {"decode_ms": [round(v, 1) for v in res[name]["decode_ms"]], "codec_tokens_per_s": round(4 * n_new / (best * 1e-3), 1),
-                     "wt16_launches_per_step": res[name]["wt16_launches"]}
-    out["tokens_identical"] = all(torch.equal(x, y) for x, y in zip(res["bf16_wt16"]["tokens"], ref))
+                     kind + "_launches_per_step": res[name]["launches"]}
+    out["tokens_identical"] = all(torch.equal(x, y) for x, y in zip(res["bf16_" + kind]["tokens"], ref))
     assert out["tokens_identical"], "the two bf16 arms must choose the same tokens"
     line = json.dumps(out)
     print(line)

@@ -10,6 +10,10 @@ Beside each figure: the project's chain floor `2.6 us + bytes / 7.3 TB/s` (DESIG
 w_tiled) against the packed bf16 streaming-order copy (`ssrhip_gemv_wt16`) with 8 loads in flight per wave (the default) and with 16
 (`SSRHIP_GEMVM_W16_DEPTH=16`, set by the tool for that arm), activations in the tiled layout as the step keeps them.
     python tools/w16_launch_bench.py --rows 16 --out profiles/wt16_launch_bench_rows16.json
+`--rows 17..32` measures the two-panel step's launches (DESIGN.md Part I.12): the fp32 streaming-order copy against the same packed copy
+through `ssrhip_gemv_wt32`, two panels of tiled activations; beside the byte floors it prints the matrix-core time of the launch,
+`2 * rows_padded * N * K flop / 157.3 TFLOP/s` (rows_padded = 32: both panels are multiplied whole).
+    python tools/w16_launch_bench.py --rows 32 --out profiles/wt32_launch_bench_rows32.json
 """
 import argparse
 import ctypes as C
@@ -39,7 +43,7 @@ H, HD, MAX_PAGES = 16, 128, 6
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--rows", type=int, default=2, choices=[1, 2, 4] + list(range(5, 17)))
+    ap.add_argument("--rows", type=int, default=2, choices=[1, 2, 4] + list(range(5, 33)))
     ap.add_argument("--chain", type=int, default=16)
     ap.add_argument("--replays", type=int, default=30)
     ap.add_argument("--out", default=None)
@@ -49,7 +53,8 @@ def main(argv=None):
     g = torch.Generator(device="cuda").manual_seed(1)
     rows = []
     mc = B > 4                                                    # the matrix-core step: tiled activations, streaming-order weights
-    forms = ("fp32", "wt16", "wt16_depth16") if mc else ("fp32", "w16")
+    forms = ("fp32", "wt32") if B > 16 else ("fp32", "wt16", "wt16_depth16") if mc else ("fp32", "w16")
+    xrows = 32 if B > 16 else 16 if mc else B                     # (tiled: 16 columns per panel, any values)
     for name, G, N, K, pro, act, epi in SHAPES:
         if mc and pro == _lib.PRO_ATTN_COMBINE:
             pro = _lib.PRO_NONE                                   # at 5..32 rows the split-KV merge is a launch of its own
@@ -59,8 +64,8 @@ def main(argv=None):
         if mc:
             masters = [to_streaming_order(m) for m in masters]
         bias = torch.randn(G, N, device=dev, generator=g)
-        x = torch.randn(16 if mc else B, G * K, device=dev, generator=g)       # (tiled: 16 columns, any values)
-        y = torch.zeros(16 if mc else B, ny, device=dev)
+        x = torch.randn(xrows, G * K, device=dev, generator=g)
+        y = torch.zeros(xrows, ny, device=dev)
         pool = torch.zeros(B * MAX_PAGES + 1, 1, 2, H, _lib.PAGE, HD, device=dev)
         table = torch.arange(B * MAX_PAGES, dtype=torch.int32, device=dev).view(B, MAX_PAGES)
         pos = torch.full((B,), 600, dtype=torch.int32, device=dev)
@@ -97,6 +102,9 @@ def main(argv=None):
                     if form == "w16":
                         rc = L.ssrhip_gemv_w16(C.byref(a), packed[i].data_ptr(), _lib.stream_ptr())
                         assert rc == 0, (name, rc, L.ssrhip_last_error())
+                    elif form == "wt32":
+                        rc = L.ssrhip_gemv_wt32(C.byref(a), packed[i].data_ptr(), _lib.stream_ptr())
+                        assert rc == 0, (name, rc, L.ssrhip_last_error())
                     elif form.startswith("wt16"):
                         rc = L.ssrhip_gemv_wt16(C.byref(a), packed[i].data_ptr(), _lib.stream_ptr())
                         assert rc == 0, (name, rc, L.ssrhip_last_error())
@@ -131,6 +139,8 @@ def main(argv=None):
         for form in forms[1:]:
             row[form + "_us"] = round(us[form], 2)
             row[form + "_TBps"] = round(2 * nw / us[form] / 1e6, 2)
+        if B > 16:                                               # two panels of fp32 MFMA work: is the launch bound by bytes or by flops?
+            row["mfma_us"] = round(2 * 32 * nw / 157.3e6, 2)     # us at 157.3 TFLOP/s = 157.3e6 flop per us
         rows.append(row)
         print(json.dumps(rows[-1]), flush=True)
         del masters, packed
