@@ -168,7 +168,8 @@ __global__ __launch_bounds__(512) void gemv_mfma_kernel(const GemvM p) {
 //     a separate code path without the cross-tile refills, so no load is predicated and none is wasted;
 //   * per-tile partial sums of the waves go to LDS once (no barrier inside the row loop); after ONE barrier the waves run the
 //     epilogues of different tiles in parallel, adding the K-slices in wave order (deterministic).
-// The kernel parameter (GemvR), MAXT and the host plan that fills them are in gemv_mfma_tile.h, shared with the 17..32-row kernels.
+// The kernel parameter (GemvR), MAXT, the host plan that fills them, and the pieces the kernels below share with their bf16 and 17..32-row
+// forms (ln_slice / ln_apply, kstep1, kpair1, pair_fold, merge_pair) are in gemv_mfma_tile.h.
 // =====================================================================================================================
 
 // Where a 16-row launch spends its time (round 5, VERDICT r4 item 3: "attribute, do not guess") — the stamps of tools/gemvm_lab.hip on an
@@ -246,7 +247,7 @@ __global__ __launch_bounds__(512) void gemv_rows_xreg_kernel(const GemvR p) {
   MSTAMP(7);
   // what this wave's epilogue (tile `wave`) will need, requested now (behind the first weight loads, used after the last MFMA)
   const bool epi_mine = wave < ntile;
-  const TileEpi epi0 = tile_epilogue_fetch(a, p.hd, grp, row_lo + wave * 16, epi_mine ? ((2 * wave + 1 < nun) ? 16 : 8) : 0, lane, kvpos);
+  const TileEpi epi0 = tile_epilogue_fetch(a, p.hd, grp, row_lo + wave * 16, epi_mine ? tile_rows_of(wave, nun) : 0, lane, kvpos);
   __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
   for (int t = 0; t < SPWX; ++t) asm volatile("" : "+v"(xr[t].x), "+v"(xr[t].y), "+v"(xr[t].z), "+v"(xr[t].w));
@@ -259,41 +260,51 @@ __global__ __launch_bounds__(512) void gemv_rows_xreg_kernel(const GemvR p) {
     // LayerNorm on the register-resident x (gamma / beta folded into W / bias by the caller) with ONE workgroup barrier: every
     // wave computes the two-pass mean / sum of squared deviations of ITS K-slice, the slices are merged with the exact
     // pairwise-update identity  M2 = sum_w M2_w + sum_w n_w (mean_w - mean)^2  (Chan et al.) — as accurate as the reference's
-    // two-pass over the whole row. The first DEP weight loads are in flight meanwhile.
-    const int nval = max(0, min(SPWX, last + 1 - tbase)) * 16;       // floats of K in this wave's slice (uniform)
-    float s = 0.f;
+    // two-pass over the whole row (ln_slice / ln_apply, gemv_mfma_tile.h). The first DEP weight loads are in flight meanwhile.
+    if (DEP != 8) {
+      float mw, q;
+      ln_slice<SPWX>(xr, tbase, last, &mw, &q);
+      if (ks == 0) { red[0][wave][c] = mw; red[1][wave][c] = q; }
+      __syncthreads();
+      ln_apply<SPWX>(xr, red, p.nw, c, tbase, last, K, a.ln_eps);
+    } else {
+      // SSRHIP_GEMVM_DEP8 keeps the same expressions written out (profiles/mfma_rows_refactor_ab.md; re-check with tools/isa_diff.py and a
+      // timed A/B before calling the helpers here)
+      const int nval = max(0, min(SPWX, last + 1 - tbase)) * 16;       // floats of K in this wave's slice (uniform)
+      float s = 0.f;
 #pragma unroll
-    for (int t = 0; t < SPWX; ++t) s += (xr[t].x + xr[t].y) + (xr[t].z + xr[t].w);
-    s = kslot_sum(s);
-    const float mw = nval > 0 ? s / (float)nval : 0.f;
-    float q = 0.f;
+      for (int t = 0; t < SPWX; ++t) s += (xr[t].x + xr[t].y) + (xr[t].z + xr[t].w);
+      s = kslot_sum(s);
+      const float mw = nval > 0 ? s / (float)nval : 0.f;
+      float q = 0.f;
 #pragma unroll
-    for (int t = 0; t < SPWX; ++t) {
-      if (tbase + t <= last) {
-        const float dx = xr[t].x - mw, dy = xr[t].y - mw, dz = xr[t].z - mw, dw = xr[t].w - mw;
-        q += (dx * dx + dy * dy) + (dz * dz + dw * dw);
+      for (int t = 0; t < SPWX; ++t) {
+        if (tbase + t <= last) {
+          const float dx = xr[t].x - mw, dy = xr[t].y - mw, dz = xr[t].z - mw, dw = xr[t].w - mw;
+          q += (dx * dx + dy * dy) + (dz * dz + dw * dw);
+        }
       }
-    }
-    q = kslot_sum(q);
-    if (ks == 0) { red[0][wave][c] = mw; red[1][wave][c] = q; }
-    __syncthreads();
-    float mean = 0.f;
-    for (int v = 0; v < p.nw; ++v) mean += red[0][v][c] * (float)(max(0, min(SPWX, last + 1 - v * SPWX)) * 16);
-    mean /= (float)K;
-    float var = 0.f;
-    for (int v = 0; v < p.nw; ++v) {
-      const float d = red[0][v][c] - mean;
-      var += red[1][v][c] + (float)(max(0, min(SPWX, last + 1 - v * SPWX)) * 16) * d * d;
-    }
-    var /= (float)K;
-    const float rstd = 1.0f / sqrtf(var + a.ln_eps);
+      q = kslot_sum(q);
+      if (ks == 0) { red[0][wave][c] = mw; red[1][wave][c] = q; }
+      __syncthreads();
+      float mean = 0.f;
+      for (int v = 0; v < p.nw; ++v) mean += red[0][v][c] * (float)(max(0, min(SPWX, last + 1 - v * SPWX)) * 16);
+      mean /= (float)K;
+      float var = 0.f;
+      for (int v = 0; v < p.nw; ++v) {
+        const float d = red[0][v][c] - mean;
+        var += red[1][v][c] + (float)(max(0, min(SPWX, last + 1 - v * SPWX)) * 16) * d * d;
+      }
+      var /= (float)K;
+      const float rstd = 1.0f / sqrtf(var + a.ln_eps);
 #pragma unroll
-    for (int t = 0; t < SPWX; ++t) {
-      if (tbase + t <= last) {
-        xr[t].x = (xr[t].x - mean) * rstd;
-        xr[t].y = (xr[t].y - mean) * rstd;
-        xr[t].z = (xr[t].z - mean) * rstd;
-        xr[t].w = (xr[t].w - mean) * rstd;
+      for (int t = 0; t < SPWX; ++t) {
+        if (tbase + t <= last) {
+          xr[t].x = (xr[t].x - mean) * rstd;
+          xr[t].y = (xr[t].y - mean) * rstd;
+          xr[t].z = (xr[t].z - mean) * rstd;
+          xr[t].w = (xr[t].w - mean) * rstd;
+        }
       }
     }
   }
@@ -304,27 +315,14 @@ __global__ __launch_bounds__(512) void gemv_rows_xreg_kernel(const GemvR p) {
 #pragma unroll
     for (int i = 0; i < SPWX / 2; ++i) {
       const float4 wv = w[i], xa = xr[2 * i], xb = xr[2 * i + 1];
-      aA = mfma4(wv.x, xa.x, aA);
-      aB = mfma4(wv.x, xb.x, aB);
-      aA = mfma4(wv.y, xa.y, aA);
-      aB = mfma4(wv.y, xb.y, aB);
-      aA = mfma4(wv.z, xa.z, aA);
-      aB = mfma4(wv.z, xb.z, aB);
-      aA = mfma4(wv.w, xa.w, aA);
-      aB = mfma4(wv.w, xb.w, aB);
+      kpair1(wv, xa, xb, aA, aB);
     }
-    f4v acc;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc[e] = aA[e] + xor32_f(aB[e]);          // rows 0..7 (lanes < 32) = own rows + rows 8..15 of lane + 32
+    const f4v acc = pair_fold(aA, aB);
     MSTAMP(3);
     part[0][wave][lane] = acc;
     __syncthreads();
     MSTAMP(4);
-    if (wave == 0) {
-      f4v sum = part[0][0][lane];
-      for (int v = 1; v < p.nw; ++v) sum += part[0][v][lane];
-      tile_epilogue_finish(a, epi0, sum, p.hd);
-    }
+    merge_pair(a, part[0], p.nw, p.hd, epi0, wave, lane);
     MSTAMP(5);
     return;
   }
@@ -335,10 +333,7 @@ __global__ __launch_bounds__(512) void gemv_rows_xreg_kernel(const GemvR p) {
 #pragma unroll
     for (int t = 0; t < SPWX; ++t) {
       const float4 wv = w[t % DEP], xv = xr[t];
-      a0 = mfma4(wv.x, xv.x, a0);
-      a1 = mfma4(wv.y, xv.y, a1);
-      a0 = mfma4(wv.z, xv.z, a0);
-      a1 = mfma4(wv.w, xv.w, a1);
+      kstep1(wv, xv, a0, a1);
       if (t + DEP < SPWX) w[t % DEP] = ld_nt(wp + min(tbase + t + DEP, last) * wstep);
       else w[t % DEP] = ld_nt(wn + min(tbase + t + DEP - SPWX, last) * wstep);
       __builtin_amdgcn_sched_barrier(0);
@@ -351,10 +346,7 @@ __global__ __launch_bounds__(512) void gemv_rows_xreg_kernel(const GemvR p) {
 #pragma unroll
     for (int t = 0; t < SPWX; ++t) {
       const float4 wv = w[t % DEP], xv = xr[t];
-      a0 = mfma4(wv.x, xv.x, a0);
-      a1 = mfma4(wv.y, xv.y, a1);
-      a0 = mfma4(wv.z, xv.z, a0);
-      a1 = mfma4(wv.w, xv.w, a1);
+      kstep1(wv, xv, a0, a1);
       if (t + DEP < SPWX) w[t % DEP] = ld_nt(wp + min(tbase + t + DEP, last) * wstep);
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -483,10 +475,7 @@ __global__ __launch_bounds__(768) void gemv_rows_edge_kernel(const GemvR p) {
     for (int t = 0; t < SPWX; ++t) {
       const float4 wv = w[i][t], xc = xv;
       if (t + 1 < SPWX) xv = xw[(t + 1) * 64];                          // one k-step ahead (LDS)
-      a0 = mfma4(wv.x, xc.x, a0);
-      a1 = mfma4(wv.y, xc.y, a1);
-      a0 = mfma4(wv.z, xc.z, a0);
-      a1 = mfma4(wv.w, xc.w, a1);
+      kstep1(wv, xc, a0, a1);
     }
     part[(i * 8 + wave) * 64 + lane] = a0 + a1;
   }
@@ -548,14 +537,7 @@ __global__ __launch_bounds__(512) void gemv_rows_stream_kernel(const GemvR p) {
         const float4 wv = wq[i];
         float4 xa = xr[2 * i], xb = xr[2 * i + 1];
         if (kb + 2 * i > last) { xa = make_float4(0.f, 0.f, 0.f, 0.f); xb = xa; }   // steps is even: a pair is in or out as a whole
-        aA = mfma4(wv.x, xa.x, aA);
-        aB = mfma4(wv.x, xb.x, aB);
-        aA = mfma4(wv.y, xa.y, aA);
-        aB = mfma4(wv.y, xb.y, aB);
-        aA = mfma4(wv.z, xa.z, aA);
-        aB = mfma4(wv.z, xb.z, aB);
-        aA = mfma4(wv.w, xa.w, aA);
-        aB = mfma4(wv.w, xb.w, aB);
+        kpair1(wv, xa, xb, aA, aB);
         xr[2 * i] = ld4(xp + min(kbn + 2 * i, last) * xstep);
         xr[2 * i + 1] = ld4(xp + min(kbn + 2 * i + 1, last) * xstep);
         wq[i] = ld_nt(wp + min(kbn + 2 * i, last - 1) * wstep);
@@ -569,28 +551,17 @@ __global__ __launch_bounds__(512) void gemv_rows_stream_kernel(const GemvR p) {
         const float4 wv = wq[i];
         float4 xa = xr[2 * i], xb = xr[2 * i + 1];
         if (kb + 2 * i > last) { xa = make_float4(0.f, 0.f, 0.f, 0.f); xb = xa; }
-        aA = mfma4(wv.x, xa.x, aA);
-        aB = mfma4(wv.x, xb.x, aB);
-        aA = mfma4(wv.y, xa.y, aA);
-        aB = mfma4(wv.y, xb.y, aB);
-        aA = mfma4(wv.z, xa.z, aA);
-        aB = mfma4(wv.z, xb.z, aB);
-        aA = mfma4(wv.w, xa.w, aA);
-        aB = mfma4(wv.w, xb.w, aB);
+        kpair1(wv, xa, xb, aA, aB);
       }
     }
-    f4v acc;
+    f4v acc;                                                              // pair_fold's sum, written out: see profiles/mfma_rows_refactor_ab.md
 #pragma unroll
     for (int e = 0; e < 4; ++e) acc[e] = aA[e] + xor32_f(aB[e]);
     MSTAMP(3);
     part[0][wave][lane] = acc;
     __syncthreads();
     MSTAMP(4);
-    if (wave == 0) {
-      f4v sum = part[0][0][lane];
-      for (int v = 1; v < p.nw; ++v) sum += part[0][v][lane];
-      tile_epilogue_finish(a, epi0, sum, p.hd);
-    }
+    merge_pair(a, part[0], p.nw, p.hd, epi0, wave, lane);
     MSTAMP(5);
     return;
   }
@@ -601,7 +572,7 @@ __global__ __launch_bounds__(512) void gemv_rows_stream_kernel(const GemvR p) {
   for (int i = 0; i < DEP; ++i) w[i] = ld_nt(wp + min(tbase + i, last) * wstep);
   __builtin_amdgcn_sched_barrier(0);
   const bool epi_mine = wave < ntile;
-  const TileEpi epi0 = tile_epilogue_fetch(a, p.hd, grp, row_lo + wave * 16, epi_mine ? ((2 * wave + 1 < nun) ? 16 : 8) : 0, lane, kvpos);
+  const TileEpi epi0 = tile_epilogue_fetch(a, p.hd, grp, row_lo + wave * 16, epi_mine ? tile_rows_of(wave, nun) : 0, lane, kvpos);
   __builtin_amdgcn_sched_barrier(0);
   MSTAMP(1);
   const int total = ntile * ngrp;
@@ -618,10 +589,7 @@ __global__ __launch_bounds__(512) void gemv_rows_stream_kernel(const GemvR p) {
       const float4 wv = w[t];
       float4 xv = xr[t];
       if (kb + t > last) xv = make_float4(0.f, 0.f, 0.f, 0.f);           // uniform: k-steps past the end of K contribute nothing
-      a0 = mfma4(wv.x, xv.x, a0);
-      a1 = mfma4(wv.y, xv.y, a1);
-      a0 = mfma4(wv.z, xv.z, a0);
-      a1 = mfma4(wv.w, xv.w, a1);
+      kstep1(wv, xv, a0, a1);
       const int kk = min(kbn + t, last);
       xr[t] = ld4(xp + kk * xstep);
       w[t] = ld_nt(wn + kk * wstep);
@@ -641,21 +609,18 @@ __global__ __launch_bounds__(512) void gemv_rows_stream_kernel(const GemvR p) {
       const float4 wv = w[t];
       float4 xv = xr[t];
       if (kb + t > last) xv = make_float4(0.f, 0.f, 0.f, 0.f);
-      a0 = mfma4(wv.x, xv.x, a0);
-      a1 = mfma4(wv.y, xv.y, a1);
-      a0 = mfma4(wv.z, xv.z, a0);
-      a1 = mfma4(wv.w, xv.w, a1);
+      kstep1(wv, xv, a0, a1);
     }
     part[ntile - 1][wave][lane] = a0 + a1;
   }
   MSTAMP(3);
   __syncthreads();
   MSTAMP(4);
-  for (int t2 = wave; t2 < ntile; t2 += p.nw) {
-    f4v acc = part[t2][0][lane];
-    for (int v = 1; v < p.nw; ++v) acc += part[t2][v][lane];
-    if (t2 == wave) tile_epilogue_finish(a, epi0, acc, p.hd);
-    else tile_epilogue(a, p.hd, grp, row_lo + t2 * 16, (2 * t2 + 1 < nun) ? 16 : 8, lane, acc);
+  for (int tile = wave; tile < ntile; tile += p.nw) {
+    f4v acc = part[tile][0][lane];
+    for (int v = 1; v < p.nw; ++v) acc += part[tile][v][lane];
+    if (tile == wave) tile_epilogue_finish(a, epi0, acc, p.hd);
+    else tile_epilogue(a, p.hd, grp, row_lo + tile * 16, (2 * tile + 1 < nun) ? 16 : 8, lane, acc);
   }
   MSTAMP(5);
 }

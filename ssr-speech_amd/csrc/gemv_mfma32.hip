@@ -4,7 +4,9 @@
 //   y[b][n] = epi( sum_k pro(x)[b][k] * W[n][k] + bias[n] ),   16 < B <= 32
 //
 // Same structure as the 5..16-row rows-per-workgroup kernels of gemv_mfma.hip (gemv_rows_xreg_kernel / gemv_rows_stream_kernel): rows dealt
-// in 8-row units per workgroup, K split over <= 8 waves, rolling weight requests, the LayerNorm on register-resident x, the split epilogue.
+// in 8-row units per workgroup, K split over <= 8 waves, rolling weight requests, the LayerNorm on register-resident x (ln_slice / ln_apply
+// per panel), the split epilogue; kstep2 / kpair2 / merge_pair2 (gemv_mfma_tile.h) are the two-panel forms of the
+// 16-row kernels' kstep1 / kpair1 / merge_pair.
 // The one difference: the batch is two 16-column panels (include/ssrhip.h SSRHIP_TILED_P) and every weight fragment a lane loads feeds BOTH
 // column tiles — 8 v_mfma_f32_16x16x4_f32 per float4 of W instead of 4 (16 instead of 8 in the k-step-pair form), into two accumulator sets,
 // against x panel 0 and x panel 1. The HBM stream is the 16-row launch's; the matrix work doubles.
@@ -72,7 +74,7 @@ __global__ __launch_bounds__(512) void gemv_rows32_xreg(const GemvR p) {
   }
   __builtin_amdgcn_sched_barrier(0);
   const bool epi_mine = wave < ntile;
-  const int mine_rows = epi_mine ? ((2 * wave + 1 < nun) ? 16 : 8) : 0;
+  const int mine_rows = epi_mine ? tile_rows_of(wave, nun) : 0;
   const TileEpi e0 = tile_epilogue_fetch(a0p, p.hd, grp, row_lo + wave * 16, mine_rows, lane, kvpos0);
   const TileEpi e1 = tile_epilogue_fetch(a1p, p.hd, grp, row_lo + wave * 16, mine_rows, lane, kvpos1);
   __builtin_amdgcn_sched_barrier(0);
@@ -103,12 +105,7 @@ __global__ __launch_bounds__(512) void gemv_rows32_xreg(const GemvR p) {
     part[0][0][wave][lane] = pair_fold(aA0, aB0);
     part[1][0][wave][lane] = pair_fold(aA1, aB1);
     __syncthreads();
-    if (wave == 0) {
-      f4v s0 = part[0][0][0][lane], s1 = part[1][0][0][lane];
-      for (int v = 1; v < p.nw; ++v) { s0 += part[0][0][v][lane]; s1 += part[1][0][v][lane]; }
-      tile_epilogue_finish(a0p, e0, s0, p.hd);
-      tile_epilogue_finish(a1p, e1, s1, p.hd);
-    }
+    merge_pair2(a0p, a1p, part[0][0], part[1][0], p.nw, p.hd, e0, e1, wave, lane);
     return;
   }
   // all tiles but the last: the refills past this tile's k-range fetch the head of the next tile
@@ -220,12 +217,7 @@ __global__ __launch_bounds__(512) void gemv_rows32_stream(const GemvR p) {
     part[0][0][wave][lane] = pair_fold(aA0, aB0);
     part[1][0][wave][lane] = pair_fold(aA1, aB1);
     __syncthreads();
-    if (wave == 0) {
-      f4v s0 = part[0][0][0][lane], s1 = part[1][0][0][lane];
-      for (int v = 1; v < p.nw; ++v) { s0 += part[0][0][v][lane]; s1 += part[1][0][v][lane]; }
-      tile_epilogue_finish(a0p, e0, s0, p.hd);
-      tile_epilogue_finish(a1p, e1, s1, p.hd);
-    }
+    merge_pair2(a0p, a1p, part[0][0], part[1][0], p.nw, p.hd, e0, e1, wave, lane);
     return;
   }
   float4 w[DEP];
@@ -236,7 +228,7 @@ __global__ __launch_bounds__(512) void gemv_rows32_stream(const GemvR p) {
   for (int i = 0; i < DEP; ++i) w[i] = ld_nt(wp + min(tbase + i, last) * wstep);
   __builtin_amdgcn_sched_barrier(0);
   const bool epi_mine = wave < ntile;
-  const int mine_rows = epi_mine ? ((2 * wave + 1 < nun) ? 16 : 8) : 0;
+  const int mine_rows = epi_mine ? tile_rows_of(wave, nun) : 0;
   const TileEpi e0 = tile_epilogue_fetch(a0p, p.hd, grp, row_lo + wave * 16, mine_rows, lane, kvpos0);
   const TileEpi e1 = tile_epilogue_fetch(a1p, p.hd, grp, row_lo + wave * 16, mine_rows, lane, kvpos1);
   __builtin_amdgcn_sched_barrier(0);
@@ -277,16 +269,16 @@ __global__ __launch_bounds__(512) void gemv_rows32_stream(const GemvR p) {
     part[1][ntile - 1][wave][lane] = b0 + b1;
   }
   __syncthreads();
-  for (int t2 = wave; t2 < ntile; t2 += p.nw) {
-    f4v s0 = part[0][t2][0][lane], s1 = part[1][t2][0][lane];
-    for (int v = 1; v < p.nw; ++v) { s0 += part[0][t2][v][lane]; s1 += part[1][t2][v][lane]; }
-    if (t2 == wave) {
+  for (int tile = wave; tile < ntile; tile += p.nw) {
+    f4v s0 = part[0][tile][0][lane], s1 = part[1][tile][0][lane];
+    for (int v = 1; v < p.nw; ++v) { s0 += part[0][tile][v][lane]; s1 += part[1][tile][v][lane]; }
+    if (tile == wave) {
       tile_epilogue_finish(a0p, e0, s0, p.hd);
       tile_epilogue_finish(a1p, e1, s1, p.hd);
     } else {
-      const int rows = (2 * t2 + 1 < nun) ? 16 : 8;
-      tile_epilogue(a0p, p.hd, grp, row_lo + t2 * 16, rows, lane, s0);
-      tile_epilogue(a1p, p.hd, grp, row_lo + t2 * 16, rows, lane, s1);
+      const int rows = (2 * tile + 1 < nun) ? 16 : 8;
+      tile_epilogue(a0p, p.hd, grp, row_lo + tile * 16, rows, lane, s0);
+      tile_epilogue(a1p, p.hd, grp, row_lo + tile * 16, rows, lane, s1);
     }
   }
 }

@@ -7,7 +7,8 @@
 // ensure_wt16_copies): no second packer and no second copy. bf16 -> fp32 is a 16-bit shift (`d << 16` / `d & 0xffff0000`) and exact;
 // activations, accumulation, bias and the KV cache stay fp32; and every kernel below issues EXACTLY the MFMA sequence of its gemv_rows32_*
 // counterpart for the same k-steps: kstep2 / kpair2 per panel on one widened weight fragment, ln_slice / ln_apply per panel with ONE barrier
-// for both, the part[panel][tile][wave][lane] sums in wave order, pair_fold, panel_args with the gemv_mfma_tile.h epilogue per panel — on
+// for both, the part[panel][tile][wave][lane] sums in wave order (pair form: merge_pair2), pair_fold, panel_args with the
+// gemv_mfma_tile.h epilogue per panel, and the launchers' common qualifier gemv_wt_qualify — on
 // the same launch plan (gemv_rows_plan with ln_keeps_x = false). So a launch here equals ssrhip_gemv at the same row count on the fp32
 // streaming-order copy of the rounded master bit for bit (tests/test_gpu_wt32.py compares with torch.equal).
 //
@@ -79,7 +80,7 @@ __global__ __launch_bounds__(512) void wt32_xreg_kernel(const GemvWt16 pw) {
   }
   __builtin_amdgcn_sched_barrier(0);
   const bool epi_mine = wave < ntile;
-  const int mine_rows = epi_mine ? ((2 * wave + 1 < nun) ? 16 : 8) : 0;
+  const int mine_rows = epi_mine ? tile_rows_of(wave, nun) : 0;
   const TileEpi e0 = tile_epilogue_fetch(a0p, p.hd, grp, row_lo + wave * 16, mine_rows, lane, kvpos0);
   const TileEpi e1 = tile_epilogue_fetch(a1p, p.hd, grp, row_lo + wave * 16, mine_rows, lane, kvpos1);
   __builtin_amdgcn_sched_barrier(0);
@@ -116,12 +117,7 @@ __global__ __launch_bounds__(512) void wt32_xreg_kernel(const GemvWt16 pw) {
     part[0][0][wave][lane] = pair_fold(aA0, aB0);
     part[1][0][wave][lane] = pair_fold(aA1, aB1);
     __syncthreads();
-    if (wave == 0) {
-      f4v s0 = part[0][0][0][lane], s1 = part[1][0][0][lane];
-      for (int v = 1; v < p.nw; ++v) { s0 += part[0][0][v][lane]; s1 += part[1][0][v][lane]; }
-      tile_epilogue_finish(a0p, e0, s0, p.hd);
-      tile_epilogue_finish(a1p, e1, s1, p.hd);
-    }
+    merge_pair2(a0p, a1p, part[0][0], part[1][0], p.nw, p.hd, e0, e1, wave, lane);
     return;
   }
   // k-step t of a tile reads load m = 2 (t / 4) + t % 2, half g = (t / 2) % 2. A load is used up after its high half (g = 1) and its
@@ -243,12 +239,7 @@ __global__ __launch_bounds__(512) void wt32_stream_kernel(const GemvWt16 pw) {
     part[0][0][wave][lane] = pair_fold(aA0, aB0);
     part[1][0][wave][lane] = pair_fold(aA1, aB1);
     __syncthreads();
-    if (wave == 0) {
-      f4v s0 = part[0][0][0][lane], s1 = part[1][0][0][lane];
-      for (int v = 1; v < p.nw; ++v) { s0 += part[0][0][v][lane]; s1 += part[1][0][v][lane]; }
-      tile_epilogue_finish(a0p, e0, s0, p.hd);
-      tile_epilogue_finish(a1p, e1, s1, p.hd);
-    }
+    merge_pair2(a0p, a1p, part[0][0], part[1][0], p.nw, p.hd, e0, e1, wave, lane);
     return;
   }
   constexpr int NL = DEP / 2;                     // weight loads per group
@@ -257,7 +248,7 @@ __global__ __launch_bounds__(512) void wt32_stream_kernel(const GemvWt16 pw) {
   for (int i = 0; i < NL; ++i) w[i] = ldw_nt(wp + wt16_off(qbase, i, lastq));
   __builtin_amdgcn_sched_barrier(0);
   const bool epi_mine = wave < ntile;
-  const int mine_rows = epi_mine ? ((2 * wave + 1 < nun) ? 16 : 8) : 0;
+  const int mine_rows = epi_mine ? tile_rows_of(wave, nun) : 0;
   const TileEpi e0 = tile_epilogue_fetch(a0p, p.hd, grp, row_lo + wave * 16, mine_rows, lane, kvpos0);
   const TileEpi e1 = tile_epilogue_fetch(a1p, p.hd, grp, row_lo + wave * 16, mine_rows, lane, kvpos1);
   __builtin_amdgcn_sched_barrier(0);
@@ -300,28 +291,23 @@ __global__ __launch_bounds__(512) void wt32_stream_kernel(const GemvWt16 pw) {
     part[1][ntile - 1][wave][lane] = b0 + b1;
   }
   __syncthreads();
-  for (int t2 = wave; t2 < ntile; t2 += p.nw) {
-    f4v s0 = part[0][t2][0][lane], s1 = part[1][t2][0][lane];
-    for (int v = 1; v < p.nw; ++v) { s0 += part[0][t2][v][lane]; s1 += part[1][t2][v][lane]; }
-    if (t2 == wave) {
+  for (int tile = wave; tile < ntile; tile += p.nw) {
+    f4v s0 = part[0][tile][0][lane], s1 = part[1][tile][0][lane];
+    for (int v = 1; v < p.nw; ++v) { s0 += part[0][tile][v][lane]; s1 += part[1][tile][v][lane]; }
+    if (tile == wave) {
       tile_epilogue_finish(a0p, e0, s0, p.hd);
       tile_epilogue_finish(a1p, e1, s1, p.hd);
     } else {
-      const int rows = (2 * t2 + 1 < nun) ? 16 : 8;
-      tile_epilogue(a0p, p.hd, grp, row_lo + t2 * 16, rows, lane, s0);
-      tile_epilogue(a1p, p.hd, grp, row_lo + t2 * 16, rows, lane, s1);
+      const int rows = (2 * tile + 1 < nun) ? 16 : 8;
+      tile_epilogue(a0p, p.hd, grp, row_lo + tile * 16, rows, lane, s0);
+      tile_epilogue(a1p, p.hd, grp, row_lo + tile * 16, rows, lane, s1);
     }
   }
 }
 
-// 0: `a` qualifies (then *pl is its launch plan), 1: it does not, < 0: contract error. No HIP call before the answer is 0.
+// the packed kernels' contract: the check and the plan of ssrhip_gemv_mfma32_launch
 int wt32_qualify(const ssrhip_gemv_args* a, RowsPlan* pl) {
-  SSR_REQUIRE(a && a->W && a->y, "ssrhip_gemv_wt32: null argument");
-  SSR_REQUIRE(a->N > 0 && a->groups >= 1 && a->K > 0, "ssrhip_gemv_wt32: bad N/K/groups");
-  if (a->B < 17 || a->B > 32 || a->w_tiled != 1 || a->K % 64 != 0) return 1;
-  // the check and the plan of ssrhip_gemv_mfma32_launch: the same refusals, the same grid, waves, K slices and pair decision
-  if (int rc = gemv_rows_check(a, 17, 32, 2048)) return rc;
-  return gemv_rows_plan(a, /*ln_keeps_x=*/false, ssr_num_cu(), ssr_rows_knobs_get(), pl);
+  return gemv_wt_qualify(a, "ssrhip_gemv_wt32", 17, 32, 2048, /*ln_keeps_x=*/false, /*v1_refuses=*/false, pl);
 }
 
 }  // namespace
@@ -336,10 +322,8 @@ extern "C" int ssrhip_gemv_wt32(const ssrhip_gemv_args* a, const uint16_t* Wt16,
   SSR_REQUIRE(a && Wt16, "ssrhip_gemv_wt32: null argument");
   RowsPlan pl;
   if (int rc = wt32_qualify(a, &pl)) return rc;
+  const GemvWt16 q = {pl.r, Wt16};
   hipStream_t s = (hipStream_t)stream;
-  GemvWt16 q;
-  q.r = pl.r;
-  q.w16 = Wt16;
   const GemvR& r = pl.r;
   dim3 grid(r.wgs, a->groups), block(r.nw * 64);
   // the dispatch of ssrhip_gemv_mfma32_launch

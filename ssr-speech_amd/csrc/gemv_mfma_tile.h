@@ -1,7 +1,8 @@
 // gemv_mfma_tile.h — pieces shared by the matrix-core GEMV kernels (gemv_mfma.hip: 5..16 rows, gemv_mfma32.hip: 17..32 rows, and their
 // bf16 weight streams gemv_mfma_w16.hip / gemv_mfma32_w16.hip): the 16x16x4 fp32 MFMA, the k-slot reduction, the per-lane weight pointer of
-// a tile and the split tile epilogue; the two-panel helpers of the 17..32-row kernels; the loads and the widening of the packed bf16 layout;
-// and, for the host, the argument check and the launch plan of the rows-per-workgroup kernels, which every launcher takes from here.
+// a tile and the split tile epilogue; the pieces of the rows-per-workgroup kernels (LayerNorm on register-resident x, the MFMA groups of a
+// k-step and of a k-step pair, the pair form's merge tail) for one panel and for two; the loads and the widening of the packed bf16 layout;
+// and, for the host, the argument check and the launch plan of those kernels and the qualifier of the two bf16 launchers.
 #pragma once
 #include "common.h"
 
@@ -125,6 +126,48 @@ __device__ __forceinline__ const float* tile_wptr(const float* wbase, int row_lo
   return wbase + (size_t)min(rr, N - 1) * K + ks * 4;
 }
 
+// ---- pieces of the rows-per-workgroup kernels, one 16-column panel (5..16 rows: gemv_mfma.hip and its bf16 stream gemv_mfma_w16.hip) ----
+
+// rows of tile `tile` of a workgroup that owns `nun` 8-row units: two units to a 16-row tile, an odd last unit as an 8-row tile
+__device__ __forceinline__ int tile_rows_of(int tile, int nun) { return (2 * tile + 1 < nun) ? 16 : 8; }
+
+// one k-step of a 16-row tile: two accumulators in turn, so that consecutive MFMAs do not depend on each other
+__device__ __forceinline__ void kstep1(const float4 wv, const float4 xv, f4v& a0, f4v& a1) {
+  a0 = mfma4(wv.x, xv.x, a0);
+  a1 = mfma4(wv.y, xv.y, a1);
+  a0 = mfma4(wv.z, xv.z, a0);
+  a1 = mfma4(wv.w, xv.w, a1);
+}
+
+// one k-step PAIR (see gemv_rows_xreg_kernel's PAIR): lanes c < 8 hold the weights of k-step 2i, lanes c >= 8 those of 2i + 1 for the same
+// 8 rows; the MFMAs against xa = x[2i] are right in tile rows 0..7 (aA), those against xb = x[2i + 1] in rows 8..15 (aB)
+__device__ __forceinline__ void kpair1(const float4 wv, const float4 xa, const float4 xb, f4v& aA, f4v& aB) {
+  aA = mfma4(wv.x, xa.x, aA);
+  aB = mfma4(wv.x, xb.x, aB);
+  aA = mfma4(wv.y, xa.y, aA);
+  aB = mfma4(wv.y, xb.y, aB);
+  aA = mfma4(wv.z, xa.z, aA);
+  aB = mfma4(wv.z, xb.z, aB);
+  aA = mfma4(wv.w, xa.w, aA);
+  aB = mfma4(wv.w, xb.w, aB);
+}
+
+__device__ __forceinline__ f4v pair_fold(f4v aA, f4v aB) {
+  f4v acc;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) acc[e] = aA[e] + xor32_f(aB[e]);          // rows 0..7 (lanes < 32) = own rows + rows 8..15 of lane + 32
+  return acc;
+}
+
+// The merge tail of the k-step-pair form (one 8-row unit per workgroup), behind the barrier that completes part[wave][lane]: wave 0 adds
+// the K-slices of the nw waves in wave order (deterministic) and finishes on the epilogue operands `e` it fetched at entry
+__device__ __forceinline__ void merge_pair(const ssrhip_gemv_args& a, const f4v (&part)[8][64], int nw, int hd, const TileEpi& e, int wave, int lane) {
+  if (wave != 0) return;
+  f4v sum = part[0][lane];
+  for (int v = 1; v < nw; ++v) sum += part[v][lane];
+  tile_epilogue_finish(a, e, sum, hd);
+}
+
 // ---- two 16-column panels per launch (17..32 rows): gemv_mfma32.hip and its bf16 stream gemv_mfma32_w16.hip ----
 
 // The launch seen from one 16-column panel: panel 1 is rows 16..B-1 as a (B-16)-row launch, so the 16-row tile epilogue applies unchanged.
@@ -144,7 +187,7 @@ __device__ __forceinline__ const float* panel_xptr(const ssrhip_gemv_args& a, in
   return a.x + (size_t)grp * a.K + (size_t)min(16 * p + c, a.B - 1) * a.x_stride + ks * 4;
 }
 
-// two-pass LayerNorm statistics of one panel's wave slice (the expressions of gemv_rows_xreg_kernel)
+// two-pass LayerNorm statistics of one panel's wave slice (the 16-row kernels call it for their one panel)
 template <int SPWX>
 __device__ __forceinline__ void ln_slice(const float4 (&xr)[SPWX], int tbase, int last, float* mw_out, float* q_out) {
   const int nval = max(0, min(SPWX, last + 1 - tbase)) * 16;
@@ -221,11 +264,14 @@ __device__ __forceinline__ void kpair2(const float4 wv, const float4 xa0, const 
   aB1 = mfma4(wv.w, xb1.w, aB1);
 }
 
-__device__ __forceinline__ f4v pair_fold(f4v aA, f4v aB) {
-  f4v acc;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) acc[e] = aA[e] + xor32_f(aB[e]);          // rows 0..7 (lanes < 32) = own rows + rows 8..15 of lane + 32
-  return acc;
+// merge_pair for two panels: both panels' sums in one wave-order loop, then panel 0's epilogue, then panel 1's
+__device__ __forceinline__ void merge_pair2(const ssrhip_gemv_args& a0p, const ssrhip_gemv_args& a1p, const f4v (&part0)[8][64], const f4v (&part1)[8][64],
+                                            int nw, int hd, const TileEpi& e0, const TileEpi& e1, int wave, int lane) {
+  if (wave != 0) return;
+  f4v s0 = part0[0][lane], s1 = part1[0][lane];
+  for (int v = 1; v < nw; ++v) { s0 += part0[v][lane]; s1 += part1[v][lane]; }
+  tile_epilogue_finish(a0p, e0, s0, hd);
+  tile_epilogue_finish(a1p, e1, s1, hd);
 }
 
 // ---- host: one argument check and one launch plan for the rows-per-workgroup kernels at 5..32 rows ----
@@ -325,6 +371,23 @@ inline int gemv_rows_plan(const ssrhip_gemv_args* a, bool ln_keeps_x, int num_cu
   // every workgroup owns exactly one 8-row unit (out-proj, FFN2) and the weights are in streaming order: k-step pairs per load
   out->pair = a->w_tiled && r.units <= r.wgs && r.steps % 2 == 0 && !knobs.nopair;
   return 0;
+}
+
+// The bf16 weight streams (ssrhip_gemv_wt16 at 5..16 rows, ssrhip_gemv_wt32 at 17..32): does `a` take the packed kernels?
+// 0: it qualifies (then *pl is its launch plan), 1: it does not, < 0: contract error. No HIP call before the answer is 0.
+// `who` is the entry point's name in the error texts; [b_lo, b_hi], ln_kmax, ln_keeps_x as in gemv_rows_check / gemv_rows_plan — the
+// check and the plan of the fp32 launcher at the same row count: the same refusals, the same grid, waves, K slices and pair decision.
+// v1_refuses: SSRHIP_GEMVM_V=1 (the per-tile kernel of 5..16 rows, which has no bf16 form) makes the answer 1.
+inline int gemv_wt_qualify(const ssrhip_gemv_args* a, const char* who, int b_lo, int b_hi, int ln_kmax, bool ln_keeps_x, bool v1_refuses, RowsPlan* pl) {
+  SSR_REQUIRE(a && a->W && a->y, "%s: null argument", who);
+  SSR_REQUIRE(a->N > 0 && a->groups >= 1 && a->K > 0, "%s: bad N/K/groups", who);
+  if (a->B < b_lo || a->B > b_hi || a->w_tiled != 1 || a->K % 64 != 0) return 1;
+  if (v1_refuses) {
+    static const bool v1 = [] { const char* e = getenv("SSRHIP_GEMVM_V"); return e && atoi(e) == 1; }();
+    if (v1) return 1;
+  }
+  if (int rc = gemv_rows_check(a, b_lo, b_hi, ln_kmax)) return rc;
+  return gemv_rows_plan(a, ln_keeps_x, ssr_num_cu(), ssr_rows_knobs_get(), pl);
 }
 
 }  // namespace

@@ -7,7 +7,8 @@
 // high half) and exact; activations, accumulation, bias and the KV cache stay fp32; and every kernel below issues EXACTLY the MFMA sequence
 // of its fp32 counterpart for the same k-steps — the same a0 / a1 (aA / aB) alternation, the same x operand per MFMA, the same LayerNorm
 // statistics per 256-column slice merged in wave order, the same part[tile][wave][lane] sums in wave order, the same xor32 fold of the pair
-// form, the same epilogue (gemv_mfma_tile.h) — on the same launch plan (gemv_rows_plan). So a launch here equals ssrhip_gemv on the fp32
+// form, the same epilogue — by calling the fp32 kernels' own pieces (gemv_mfma_tile.h: ln_slice / ln_apply, kstep1, kpair1, pair_fold, merge_pair)
+// on a widened weight fragment — on the same launch plan (gemv_rows_plan). So a launch here equals ssrhip_gemv on the fp32
 // streaming-order copy of the rounded master bit for bit (tests/test_gpu_wt16.py compares with torch.equal).
 //
 // Layout (include/ssrhip.h SSRHIP_WT16_INDEX): rows in 8-row units (zero-padded), K in QUADS of four k-steps (64 floats; K % 64 == 0).
@@ -86,7 +87,7 @@ __global__ __launch_bounds__(512) void wt16_xreg_kernel(const GemvWt16 pw) {
   __builtin_amdgcn_sched_barrier(0);
   // what this wave's epilogue (tile `wave`) will need, requested now (behind the first weight loads, used after the last MFMA)
   const bool epi_mine = wave < ntile;
-  const TileEpi epi0 = tile_epilogue_fetch(a, p.hd, grp, row_lo + wave * 16, epi_mine ? ((2 * wave + 1 < nun) ? 16 : 8) : 0, lane, kvpos);
+  const TileEpi epi0 = tile_epilogue_fetch(a, p.hd, grp, row_lo + wave * 16, epi_mine ? tile_rows_of(wave, nun) : 0, lane, kvpos);
   __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
   for (int t = 0; t < SPWX; ++t) asm volatile("" : "+v"(xr[t].x), "+v"(xr[t].y), "+v"(xr[t].z), "+v"(xr[t].w));
@@ -95,43 +96,12 @@ __global__ __launch_bounds__(512) void wt16_xreg_kernel(const GemvWt16 pw) {
     if (tbase + t > last) xr[t] = make_float4(0.f, 0.f, 0.f, 0.f);
 
   if (PRO == SSRHIP_PRO_LAYERNORM) {
-    // gemv_rows_xreg_kernel's LayerNorm, expression by expression: per-wave two-pass statistics of the K slice, merged in wave order (Chan)
-    const int nval = max(0, min(SPWX, last + 1 - tbase)) * 16;       // floats of K in this wave's slice (uniform)
-    float s = 0.f;
-#pragma unroll
-    for (int t = 0; t < SPWX; ++t) s += (xr[t].x + xr[t].y) + (xr[t].z + xr[t].w);
-    s = kslot_sum(s);
-    const float mw = nval > 0 ? s / (float)nval : 0.f;
-    float q = 0.f;
-#pragma unroll
-    for (int t = 0; t < SPWX; ++t) {
-      if (tbase + t <= last) {
-        const float dx = xr[t].x - mw, dy = xr[t].y - mw, dz = xr[t].z - mw, dw = xr[t].w - mw;
-        q += (dx * dx + dy * dy) + (dz * dz + dw * dw);
-      }
-    }
-    q = kslot_sum(q);
+    // gemv_rows_xreg_kernel's LayerNorm: per-wave two-pass statistics of the K slice, merged in wave order (Chan)
+    float mw, q;
+    ln_slice<SPWX>(xr, tbase, last, &mw, &q);
     if (ks == 0) { red[0][wave][c] = mw; red[1][wave][c] = q; }
     __syncthreads();
-    float mean = 0.f;
-    for (int v = 0; v < p.nw; ++v) mean += red[0][v][c] * (float)(max(0, min(SPWX, last + 1 - v * SPWX)) * 16);
-    mean /= (float)K;
-    float var = 0.f;
-    for (int v = 0; v < p.nw; ++v) {
-      const float d = red[0][v][c] - mean;
-      var += red[1][v][c] + (float)(max(0, min(SPWX, last + 1 - v * SPWX)) * 16) * d * d;
-    }
-    var /= (float)K;
-    const float rstd = 1.0f / sqrtf(var + a.ln_eps);
-#pragma unroll
-    for (int t = 0; t < SPWX; ++t) {
-      if (tbase + t <= last) {
-        xr[t].x = (xr[t].x - mean) * rstd;
-        xr[t].y = (xr[t].y - mean) * rstd;
-        xr[t].z = (xr[t].z - mean) * rstd;
-        xr[t].w = (xr[t].w - mean) * rstd;
-      }
-    }
+    ln_apply<SPWX>(xr, red, p.nw, c, tbase, last, K, a.ln_eps);
   }
 
   if (PAIR) {
@@ -141,26 +111,13 @@ __global__ __launch_bounds__(512) void wt16_xreg_kernel(const GemvWt16 pw) {
 #pragma unroll
       for (int g = 0; g < 2; ++g) {                                       // the fp32 kernel's pair 2i + g = k-steps (4i + 2g, 4i + 2g + 1)
         const float4 wv = wt16_widen(w[i], g), xa = xr[4 * i + 2 * g], xb = xr[4 * i + 2 * g + 1];
-        aA = mfma4(wv.x, xa.x, aA);
-        aB = mfma4(wv.x, xb.x, aB);
-        aA = mfma4(wv.y, xa.y, aA);
-        aB = mfma4(wv.y, xb.y, aB);
-        aA = mfma4(wv.z, xa.z, aA);
-        aB = mfma4(wv.z, xb.z, aB);
-        aA = mfma4(wv.w, xa.w, aA);
-        aB = mfma4(wv.w, xb.w, aB);
+        kpair1(wv, xa, xb, aA, aB);
       }
     }
-    f4v acc;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc[e] = aA[e] + xor32_f(aB[e]);          // rows 0..7 (lanes < 32) = own rows + rows 8..15 of lane + 32
+    const f4v acc = pair_fold(aA, aB);
     part[0][wave][lane] = acc;
     __syncthreads();
-    if (wave == 0) {
-      f4v sum = part[0][0][lane];
-      for (int v = 1; v < p.nw; ++v) sum += part[0][v][lane];
-      tile_epilogue_finish(a, epi0, sum, p.hd);
-    }
+    merge_pair(a, part[0], p.nw, p.hd, epi0, wave, lane);
     return;
   }
   // k-step t of a tile reads load m = 2 (t / 4) + t % 2, half g = (t / 2) % 2
@@ -172,10 +129,7 @@ __global__ __launch_bounds__(512) void wt16_xreg_kernel(const GemvWt16 pw) {
       for (int t = 0; t < SPWX; ++t) {
         const int m = 2 * (t >> 2) + (t & 1), g = (t >> 1) & 1;
         const float4 wv = wt16_widen(w[tile * LPT + m], g), xv = xr[t];
-        a0 = mfma4(wv.x, xv.x, a0);
-        a1 = mfma4(wv.y, xv.y, a1);
-        a0 = mfma4(wv.z, xv.z, a0);
-        a1 = mfma4(wv.w, xv.w, a1);
+        kstep1(wv, xv, a0, a1);
         __builtin_amdgcn_sched_barrier(0);
       }
       part[tile][wave][lane] = a0 + a1;
@@ -190,10 +144,7 @@ __global__ __launch_bounds__(512) void wt16_xreg_kernel(const GemvWt16 pw) {
     for (int t = 0; t < SPWX; ++t) {
       const int m = 2 * (t >> 2) + (t & 1), g = (t >> 1) & 1;
       const float4 wv = wt16_widen(w[m % DL], g), xv = xr[t];
-      a0 = mfma4(wv.x, xv.x, a0);
-      a1 = mfma4(wv.y, xv.y, a1);
-      a0 = mfma4(wv.z, xv.z, a0);
-      a1 = mfma4(wv.w, xv.w, a1);
+      kstep1(wv, xv, a0, a1);
       if (g == 1) {
         if (m + DL < LPT) w[m % DL] = ldw_nt(wp + wt16_off(qbase, m + DL, lastq));
         else w[m % DL] = ldw_nt(wn + wt16_off(qbase, m + DL - LPT, lastq));
@@ -209,10 +160,7 @@ __global__ __launch_bounds__(512) void wt16_xreg_kernel(const GemvWt16 pw) {
     for (int t = 0; t < SPWX; ++t) {
       const int m = 2 * (t >> 2) + (t & 1), g = (t >> 1) & 1;
       const float4 wv = wt16_widen(w[m % DL], g), xv = xr[t];
-      a0 = mfma4(wv.x, xv.x, a0);
-      a1 = mfma4(wv.y, xv.y, a1);
-      a0 = mfma4(wv.z, xv.z, a0);
-      a1 = mfma4(wv.w, xv.w, a1);
+      kstep1(wv, xv, a0, a1);
       if (g == 1 && m + DL < LPT) w[m % DL] = ldw_nt(wp + wt16_off(qbase, m + DL, lastq));
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -277,14 +225,7 @@ __global__ __launch_bounds__(512) void wt16_stream_kernel(const GemvWt16 pw) {
         const float4 wv = wt16_widen(wq[j >> 1], j & 1);
         float4 xa = xr[2 * j], xb = xr[2 * j + 1];
         if (kb + 2 * j > last) { xa = make_float4(0.f, 0.f, 0.f, 0.f); xb = xa; }   // steps is even: a pair is in or out as a whole
-        aA = mfma4(wv.x, xa.x, aA);
-        aB = mfma4(wv.x, xb.x, aB);
-        aA = mfma4(wv.y, xa.y, aA);
-        aB = mfma4(wv.y, xb.y, aB);
-        aA = mfma4(wv.z, xa.z, aA);
-        aB = mfma4(wv.z, xb.z, aB);
-        aA = mfma4(wv.w, xa.w, aA);
-        aB = mfma4(wv.w, xb.w, aB);
+        kpair1(wv, xa, xb, aA, aB);
         xr[2 * j] = ld4(xp + min(kbn + 2 * j, last) * xstep);
         xr[2 * j + 1] = ld4(xp + min(kbn + 2 * j + 1, last) * xstep);
         if (j & 1) wq[j >> 1] = ldw_nt(wp + min(qn + (j >> 1), lastq) * 512);
@@ -298,26 +239,15 @@ __global__ __launch_bounds__(512) void wt16_stream_kernel(const GemvWt16 pw) {
         const float4 wv = wt16_widen(wq[j >> 1], j & 1);
         float4 xa = xr[2 * j], xb = xr[2 * j + 1];
         if (kb + 2 * j > last) { xa = make_float4(0.f, 0.f, 0.f, 0.f); xb = xa; }
-        aA = mfma4(wv.x, xa.x, aA);
-        aB = mfma4(wv.x, xb.x, aB);
-        aA = mfma4(wv.y, xa.y, aA);
-        aB = mfma4(wv.y, xb.y, aB);
-        aA = mfma4(wv.z, xa.z, aA);
-        aB = mfma4(wv.z, xb.z, aB);
-        aA = mfma4(wv.w, xa.w, aA);
-        aB = mfma4(wv.w, xb.w, aB);
+        kpair1(wv, xa, xb, aA, aB);
       }
     }
-    f4v acc;
+    f4v acc;                                                              // pair_fold's sum, written out as in gemv_rows_stream_kernel<true>
 #pragma unroll
     for (int e = 0; e < 4; ++e) acc[e] = aA[e] + xor32_f(aB[e]);
     part[0][wave][lane] = acc;
     __syncthreads();
-    if (wave == 0) {
-      f4v sum = part[0][0][lane];
-      for (int v = 1; v < p.nw; ++v) sum += part[0][v][lane];
-      tile_epilogue_finish(a, epi0, sum, p.hd);
-    }
+    merge_pair(a, part[0], p.nw, p.hd, epi0, wave, lane);
     return;
   }
   constexpr int NL = DEP / 2;                     // weight loads per group
@@ -329,7 +259,7 @@ __global__ __launch_bounds__(512) void wt16_stream_kernel(const GemvWt16 pw) {
   for (int i = 0; i < NL; ++i) w[i] = ldw_nt(wp + wt16_off(qbase, i, lastq));
   __builtin_amdgcn_sched_barrier(0);
   const bool epi_mine = wave < ntile;
-  const TileEpi epi0 = tile_epilogue_fetch(a, p.hd, grp, row_lo + wave * 16, epi_mine ? ((2 * wave + 1 < nun) ? 16 : 8) : 0, lane, kvpos);
+  const TileEpi epi0 = tile_epilogue_fetch(a, p.hd, grp, row_lo + wave * 16, epi_mine ? tile_rows_of(wave, nun) : 0, lane, kvpos);
   __builtin_amdgcn_sched_barrier(0);
   const int total = ntile * ngrp;
   f4v a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
@@ -346,10 +276,7 @@ __global__ __launch_bounds__(512) void wt16_stream_kernel(const GemvWt16 pw) {
       const float4 wv = wt16_widen(w[m], h);
       float4 xv = xr[t];
       if (kb + t > last) xv = make_float4(0.f, 0.f, 0.f, 0.f);           // uniform: k-steps past the end of K contribute nothing
-      a0 = mfma4(wv.x, xv.x, a0);
-      a1 = mfma4(wv.y, xv.y, a1);
-      a0 = mfma4(wv.z, xv.z, a0);
-      a1 = mfma4(wv.w, xv.w, a1);
+      kstep1(wv, xv, a0, a1);
       xr[t] = ld4(xp + min(kbn + t, last) * xstep);
       if (h == 1) w[m] = ldw_nt(wn + wt16_off(qn, m, lastq));
       __builtin_amdgcn_sched_barrier(0);
@@ -369,19 +296,16 @@ __global__ __launch_bounds__(512) void wt16_stream_kernel(const GemvWt16 pw) {
       const float4 wv = wt16_widen(w[m], h);
       float4 xv = xr[t];
       if (kb + t > last) xv = make_float4(0.f, 0.f, 0.f, 0.f);
-      a0 = mfma4(wv.x, xv.x, a0);
-      a1 = mfma4(wv.y, xv.y, a1);
-      a0 = mfma4(wv.z, xv.z, a0);
-      a1 = mfma4(wv.w, xv.w, a1);
+      kstep1(wv, xv, a0, a1);
     }
     part[ntile - 1][wave][lane] = a0 + a1;
   }
   __syncthreads();
-  for (int t2 = wave; t2 < ntile; t2 += p.nw) {
-    f4v acc = part[t2][0][lane];
-    for (int v = 1; v < p.nw; ++v) acc += part[t2][v][lane];
-    if (t2 == wave) tile_epilogue_finish(a, epi0, acc, p.hd);
-    else tile_epilogue(a, p.hd, grp, row_lo + t2 * 16, (2 * t2 + 1 < nun) ? 16 : 8, lane, acc);
+  for (int tile = wave; tile < ntile; tile += p.nw) {
+    f4v acc = part[tile][0][lane];
+    for (int v = 1; v < p.nw; ++v) acc += part[tile][v][lane];
+    if (tile == wave) tile_epilogue_finish(a, epi0, acc, p.hd);
+    else tile_epilogue(a, p.hd, grp, row_lo + tile * 16, (2 * tile + 1 < nun) ? 16 : 8, lane, acc);
   }
 }
 
@@ -391,15 +315,10 @@ constexpr int WT16_DL = 8;      // weight loads in flight per wave (8 KiB)
 // two tiles each take the all-at-entry form (16 loads = 16 KiB per wave); every other value, and every other launch, is the ring of 8
 bool wt16_depth16() { const char* e = getenv("SSRHIP_GEMVM_W16_DEPTH"); return e && atoi(e) == 16; }
 
-// 0: `a` qualifies (then *pl is its launch plan), 1: it does not, < 0: contract error. No HIP call before the answer is 0.
+// the packed kernels' contract: the check and the plan of ssrhip_gemv_mfma_launch's rows-per-workgroup kernels (SSRHIP_GEMVM_V=1, the
+// per-tile kernel of round 1, has no bf16 form)
 int wt16_qualify(const ssrhip_gemv_args* a, RowsPlan* pl) {
-  SSR_REQUIRE(a && a->W && a->y, "ssrhip_gemv_wt16: null argument");
-  SSR_REQUIRE(a->N > 0 && a->groups >= 1 && a->K > 0, "ssrhip_gemv_wt16: bad N/K/groups");
-  if (a->B < 5 || a->B > 16 || a->w_tiled != 1 || a->K % 64 != 0) return 1;
-  static const bool v1 = [] { const char* e = getenv("SSRHIP_GEMVM_V"); return e && atoi(e) == 1; }();
-  if (v1) return 1;                                                       // the per-tile kernels of round 1 have no bf16 form
-  if (int rc = gemv_rows_check(a, 5, 16, 4096)) return rc;
-  return gemv_rows_plan(a, /*ln_keeps_x=*/true, ssr_num_cu(), ssr_rows_knobs_get(), pl);
+  return gemv_wt_qualify(a, "ssrhip_gemv_wt16", 5, 16, 4096, /*ln_keeps_x=*/true, /*v1_refuses=*/true, pl);
 }
 
 }  // namespace
@@ -414,10 +333,8 @@ extern "C" int ssrhip_gemv_wt16(const ssrhip_gemv_args* a, const uint16_t* Wt16,
   SSR_REQUIRE(a && Wt16, "ssrhip_gemv_wt16: null argument");
   RowsPlan pl;
   if (int rc = wt16_qualify(a, &pl)) return rc;
+  const GemvWt16 q = {pl.r, Wt16};
   hipStream_t s = (hipStream_t)stream;
-  GemvWt16 q;
-  q.r = pl.r;
-  q.w16 = Wt16;
   const GemvR& r = pl.r;
   const bool ln = a->pro == SSRHIP_PRO_LAYERNORM;
   const bool x16 = r.spw == 16;                          // (x in registers) 16 k-steps of it per wave: K <= 2048
