@@ -66,21 +66,31 @@ struct ssrhip_lm {
   void* pair_ws = nullptr;      // granules of the paired GEMV launches (2-row step; SSRHIP_PAIR_WS_BYTES, owned)
   int pair_dev = -1;            // >= 0: this engine holds the pairing slot of that device (released in ssrhip_lm_destroy)
   char pair_why[200] = "";      // why the step pairs / does not pair (ssrhip_lm_pairing)
-  // the bf16 weight stream (ssrhip_lm_set_w16): packed copies of the six families, NULL = that matrix streams its fp32 master
-  std::vector<const uint16_t*> w16[4];      // in_proj, out_proj, ffn1, ffn2 per layer (empty: none)
-  const uint16_t* head1_w16 = nullptr;
-  const uint16_t* head2_w16 = nullptr;
-  int w16_launches = 0;         // launches of the last enqueued step that ran a w16 kernel (ssrhip_lm_w16_launches)
-  // the same at 5..16 rows (ssrhip_lm_set_wt16) and at 17..32 rows (ssrhip_lm_set_wt32; an engine has one row count, so one record):
-  // SSRHIP_WT16_INDEX copies, NULL = that matrix streams its fp32 streaming-order copy
-  std::vector<const uint16_t*> wt16[4];
-  const uint16_t* head1_wt16 = nullptr;
-  const uint16_t* head2_wt16 = nullptr;
-  int wt16_launches = 0;        // launches of the last enqueued step that ran a kernel of gemv_mfma_w16.hip (ssrhip_lm_wt16_launches)
-  int wt32_launches = 0;        // ... of gemv_mfma32_w16.hip (ssrhip_lm_wt32_launches)
+  // the bf16 weight stream: an engine has one row count, so one kind (index into PACKED_STREAMS, -1: none) and one record of packed copies
+  // of the six families, in that kind's order (SSRHIP_W16_INDEX at <= 4 rows, SSRHIP_WT16_INDEX at 5..32); NULL = that matrix streams fp32
+  int pk_kind = -1;
+  std::vector<const uint16_t*> pk[4];       // in_proj, out_proj, ffn1, ffn2 per layer (empty: none)
+  const uint16_t* pk_head1 = nullptr;
+  const uint16_t* pk_head2 = nullptr;
+  int pk_launches = 0;          // launches of the last enqueued step that ran a kernel of pk_kind (ssrhip_lm_{w16,wt16,wt32}_launches)
 };
 
 namespace {
+
+// The three bf16 weight streams, one per row range: the setter's name, its rows (as numbers and as its messages spell them), what its
+// refusal of more rows says, the packed GEMV entry point, whether the engine needs the fp32 streaming-order copies (ssrhip_lm_weights
+// *_wt) and whether taking the record gives the pairing slot back (the pair launches stream fp32 weights).
+struct PackedStream {
+  const char* setter; int lo, hi; const char* rows; const char* only;
+  int (*gemv)(const ssrhip_gemv_args*, const uint16_t*, ssrhip_stream_t);
+  bool needs_wt, unpairs;
+};
+const PackedStream PACKED_STREAMS[3] = {
+    {"ssrhip_lm_set_w16", 1, 4, "<= 4", "the bf16 weight stream exists for the <= 4-row decode step only", ssrhip_gemv_w16, false, true},
+    {"ssrhip_lm_set_wt16", 5, 16, "5..16", "the bf16 weight stream of the matrix-core step exists for 5..16 rows only", ssrhip_gemv_wt16, true, false},
+    {"ssrhip_lm_set_wt32", 17, 32, "17..32", "the bf16 weight stream of the two-panel step exists for 17..32 rows only", ssrhip_gemv_wt32, true, false},
+};
+enum { PK_W16 = 0, PK_WT16 = 1, PK_WT32 = 2 };
 
 enum { CAT_GEMV = 0, CAT_ATTN = 1, CAT_SAMPLE = 2 };
 
@@ -312,8 +322,6 @@ struct StepShapes {
   }
 };
 
-struct W16Pair { const uint16_t* w16; const uint16_t* wt16; };   // a matrix's packed bf16 copies (either may be NULL)
-
 int enqueue_step(ssrhip_lm* lm, hipStream_t s, Timer* tm) {
   const StepShapes sh(lm);
   const ssrhip_lm_dims& d = lm->d;
@@ -333,27 +341,17 @@ int enqueue_step(ssrhip_lm* lm, hipStream_t s, Timer* tm) {
     return ssrhip_gemv_pair(&ga, &gb, lm->pair_ws, bufi, bufn, (ssrhip_stream_t)s);
   };
   // Every single GEMV launch of the step goes through here: the packed bf16 copy of the matrix when the engine has one and the shape
-  // qualifies (ssrhip_gemv_w16 answers 1 without launching when it does not), the fp32 weights otherwise. Same bits either way.
-  // An engine has either kind of packed copy, by its rows: SSRHIP_W16_INDEX at <= 4 (w16), SSRHIP_WT16_INDEX at 5..32 (wt16: the 5..16-row
-  // kernels of gemv_mfma_w16.hip and the two-panel kernels of gemv_mfma32_w16.hip read the same copy).
-  int n_w16 = 0, n_wt16 = 0, n_wt32 = 0;
-  auto gemv_call = [&](const ssrhip_gemv_args& ga, const W16Pair& pk) -> int {
-    if (pk.w16) {
-      const int rc = ssrhip_gemv_w16(&ga, pk.w16, (ssrhip_stream_t)s);
-      if (rc <= 0) { n_w16 += rc == 0; return rc; }
-    }
-    if (pk.wt16 && sh.B > 16) {
-      const int rc = ssrhip_gemv_wt32(&ga, pk.wt16, (ssrhip_stream_t)s);
-      if (rc <= 0) { n_wt32 += rc == 0; return rc; }
-    } else if (pk.wt16 && sh.B > 4) {
-      const int rc = ssrhip_gemv_wt16(&ga, pk.wt16, (ssrhip_stream_t)s);
-      if (rc <= 0) { n_wt16 += rc == 0; return rc; }
+  // qualifies (the packed entry point of the engine's kind answers 1 without launching when it does not), the fp32 weights otherwise.
+  // Same bits either way.
+  int n_pk = 0;
+  auto gemv_call = [&](const ssrhip_gemv_args& ga, const uint16_t* pk) -> int {
+    if (pk) {
+      const int rc = PACKED_STREAMS[lm->pk_kind].gemv(&ga, pk, (ssrhip_stream_t)s);
+      if (rc <= 0) { n_pk += rc == 0; return rc; }
     }
     return ssrhip_gemv(&ga, s);
   };
-  auto w16_of = [&](int family, int l) -> W16Pair {
-    return W16Pair{lm->w16[family].empty() ? nullptr : lm->w16[family][l], lm->wt16[family].empty() ? nullptr : lm->wt16[family][l]};
-  };
+  auto w16_of = [&](int family, int l) -> const uint16_t* { return lm->pk[family].empty() ? nullptr : lm->pk[family][l]; };
   enum { W16_IN = 0, W16_OUT = 1, W16_FFN1 = 2, W16_FFN2 = 3 };
   bool qkv_done = false;                        // this layer's QKV already ran inside the previous layer's pair launch
   // 5..32 rows with enough (row, head) pairs to give every CU one: the fused walk over the pages (no partials, no merge
@@ -415,13 +413,13 @@ int enqueue_step(ssrhip_lm* lm, hipStream_t s, Timer* tm) {
   }
   if (!qkv_done) {
     const ssrhip_gemv_args g = sh.head1_args();
-    STEP_CALL(CAT_GEMV, gemv_call(g, W16Pair{lm->head1_w16, lm->head1_wt16}));
+    STEP_CALL(CAT_GEMV, gemv_call(g, lm->pk_head1));
   }
   const ssrhip_gemv_args h2 = sh.head2_args();
-  STEP_CALL(CAT_GEMV, gemv_call(h2, W16Pair{lm->head2_w16, lm->head2_wt16}));
+  STEP_CALL(CAT_GEMV, gemv_call(h2, lm->pk_head2));
   const ssrhip_sample_args sa = sh.sample_args();
   STEP_CALL(CAT_SAMPLE, ssrhip_sample(&sa, s));
-  if (!tm || tm->only < 0) { lm->w16_launches = n_w16; lm->wt16_launches = n_wt16; lm->wt32_launches = n_wt32; }   // (a category-timing pass enqueues only part of a step)
+  if (!tm || tm->only < 0) lm->pk_launches = n_pk;   // (a category-timing pass enqueues only part of a step)
   return 0;
 }
 
@@ -519,61 +517,39 @@ extern "C" int ssrhip_lm_pairing(const ssrhip_lm* lm, char* why, int32_t why_len
   return lm->pair_ws ? 1 : 0;
 }
 
-extern "C" int ssrhip_lm_set_w16(ssrhip_lm* lm, const ssrhip_lm_w16* w16) {
-  SSR_REQUIRE(lm && w16, "ssrhip_lm_set_w16: null argument");
-  SSR_REQUIRE(lm->b.B <= 4, "ssrhip_lm_set_w16: the bf16 weight stream exists for the <= 4-row decode step only (this engine has %d rows)", lm->b.B);
-  SSR_REQUIRE(!lm->exec, "ssrhip_lm_set_w16: the decode step of this engine is already captured (call it before the first ssrhip_lm_decode)");
-  const uint16_t* const* src[4] = {w16->in_proj_w16, w16->out_proj_w16, w16->ffn1_w16, w16->ffn2_w16};
+// The one body of the three setters: `kind`'s checks, then the record. Rows below the kind's range belong to another kind's setter.
+static int lm_set_packed(ssrhip_lm* lm, const ssrhip_lm_w16* rec, int kind) {
+  const PackedStream& ps = PACKED_STREAMS[kind];
+  SSR_REQUIRE(lm && rec, "%s: null argument", ps.setter);
+  const int B = lm->b.B;
+  for (const PackedStream& o : PACKED_STREAMS)   // the kind that owns these rows
+    SSR_REQUIRE(B >= ps.lo || B > o.hi, "%s: engines of %s rows stream bf16 weights through %s (this engine has %d rows)", ps.setter, o.rows, o.setter, B);
+  SSR_REQUIRE(B <= ps.hi, "%s: %s (this engine has %d rows)", ps.setter, ps.only, B);
+  SSR_REQUIRE(!lm->exec, "%s: the decode step of this engine is already captured (call it before the first ssrhip_lm_decode)", ps.setter);
+  SSR_REQUIRE(!ps.needs_wt || lm->w.in_proj_wt, "%s: this engine was created without the fp32 streaming-order copies (ssrhip_lm_weights *_wt)", ps.setter);
+  const uint16_t* const* src[4] = {rec->in_proj_w16, rec->out_proj_w16, rec->ffn1_w16, rec->ffn2_w16};
   for (int f = 0; f < 4; ++f) {
-    if (src[f]) lm->w16[f].assign(src[f], src[f] + lm->d.n_layer);
-    else lm->w16[f].clear();
+    if (src[f]) lm->pk[f].assign(src[f], src[f] + lm->d.n_layer);
+    else lm->pk[f].clear();
   }
-  lm->head1_w16 = w16->head1_w16;
-  lm->head2_w16 = w16->head2_w16;
-  // the pair launches stream fp32 weights: this engine steps unpaired and gives the device's pairing slot back
-  if (lm->pair_ws) { hipFree(lm->pair_ws); lm->pair_ws = nullptr; }
-  if (lm->pair_dev >= 0) { pair_slot_release(lm->pair_dev); lm->pair_dev = -1; }
-  snprintf(lm->pair_why, sizeof(lm->pair_why), "this engine streams bf16 weights (ssrhip_lm_set_w16): the pair launches exist for fp32 weights only");
-  return 0;
-}
-
-extern "C" int ssrhip_lm_w16_launches(const ssrhip_lm* lm) { return lm ? lm->w16_launches : 0; }
-
-// the SSRHIP_WT16_INDEX record of an engine of 5..32 rows (ssrhip_lm_set_wt16 / ssrhip_lm_set_wt32, each after its own checks)
-static void lm_store_wt16(ssrhip_lm* lm, const ssrhip_lm_w16* wt16) {
-  const uint16_t* const* src[4] = {wt16->in_proj_w16, wt16->out_proj_w16, wt16->ffn1_w16, wt16->ffn2_w16};
-  for (int f = 0; f < 4; ++f) {
-    if (src[f]) lm->wt16[f].assign(src[f], src[f] + lm->d.n_layer);
-    else lm->wt16[f].clear();
+  lm->pk_head1 = rec->head1_w16;
+  lm->pk_head2 = rec->head2_w16;
+  lm->pk_kind = kind;
+  if (ps.unpairs) {   // the pair launches stream fp32 weights: this engine steps unpaired and gives the device's pairing slot back
+    if (lm->pair_ws) { hipFree(lm->pair_ws); lm->pair_ws = nullptr; }
+    if (lm->pair_dev >= 0) { pair_slot_release(lm->pair_dev); lm->pair_dev = -1; }
+    snprintf(lm->pair_why, sizeof(lm->pair_why), "this engine streams bf16 weights (%s): the pair launches exist for fp32 weights only", ps.setter);
   }
-  lm->head1_wt16 = wt16->head1_w16;
-  lm->head2_wt16 = wt16->head2_w16;
-}
-
-extern "C" int ssrhip_lm_set_wt16(ssrhip_lm* lm, const ssrhip_lm_w16* wt16) {
-  SSR_REQUIRE(lm && wt16, "ssrhip_lm_set_wt16: null argument");
-  SSR_REQUIRE(lm->b.B > 4, "ssrhip_lm_set_wt16: engines of <= 4 rows stream bf16 weights through ssrhip_lm_set_w16 (this engine has %d rows)", lm->b.B);
-  SSR_REQUIRE(lm->b.B <= 16, "ssrhip_lm_set_wt16: the bf16 weight stream of the matrix-core step exists for 5..16 rows only (this engine has %d rows)", lm->b.B);
-  SSR_REQUIRE(!lm->exec, "ssrhip_lm_set_wt16: the decode step of this engine is already captured (call it before the first ssrhip_lm_decode)");
-  SSR_REQUIRE(lm->w.in_proj_wt, "ssrhip_lm_set_wt16: this engine was created without the fp32 streaming-order copies (ssrhip_lm_weights *_wt)");
-  lm_store_wt16(lm, wt16);
   return 0;
 }
+static int lm_packed_launches(const ssrhip_lm* lm, int kind) { return lm && lm->pk_kind == kind ? lm->pk_launches : 0; }
 
-extern "C" int ssrhip_lm_wt16_launches(const ssrhip_lm* lm) { return lm ? lm->wt16_launches : 0; }
-
-extern "C" int ssrhip_lm_set_wt32(ssrhip_lm* lm, const ssrhip_lm_w16* wt16) {
-  SSR_REQUIRE(lm && wt16, "ssrhip_lm_set_wt32: null argument");
-  SSR_REQUIRE(lm->b.B > 4, "ssrhip_lm_set_wt32: engines of <= 4 rows stream bf16 weights through ssrhip_lm_set_w16 (this engine has %d rows)", lm->b.B);
-  SSR_REQUIRE(lm->b.B > 16, "ssrhip_lm_set_wt32: engines of 5..16 rows stream bf16 weights through ssrhip_lm_set_wt16 (this engine has %d rows)", lm->b.B);
-  SSR_REQUIRE(lm->b.B <= 32, "ssrhip_lm_set_wt32: the bf16 weight stream of the two-panel step exists for 17..32 rows only (this engine has %d rows)", lm->b.B);
-  SSR_REQUIRE(!lm->exec, "ssrhip_lm_set_wt32: the decode step of this engine is already captured (call it before the first ssrhip_lm_decode)");
-  SSR_REQUIRE(lm->w.in_proj_wt, "ssrhip_lm_set_wt32: this engine was created without the fp32 streaming-order copies (ssrhip_lm_weights *_wt)");
-  lm_store_wt16(lm, wt16);
-  return 0;
-}
-
-extern "C" int ssrhip_lm_wt32_launches(const ssrhip_lm* lm) { return lm ? lm->wt32_launches : 0; }
+extern "C" int ssrhip_lm_set_w16(ssrhip_lm* lm, const ssrhip_lm_w16* w16) { return lm_set_packed(lm, w16, PK_W16); }
+extern "C" int ssrhip_lm_set_wt16(ssrhip_lm* lm, const ssrhip_lm_w16* wt16) { return lm_set_packed(lm, wt16, PK_WT16); }
+extern "C" int ssrhip_lm_set_wt32(ssrhip_lm* lm, const ssrhip_lm_w16* wt16) { return lm_set_packed(lm, wt16, PK_WT32); }
+extern "C" int ssrhip_lm_w16_launches(const ssrhip_lm* lm) { return lm_packed_launches(lm, PK_W16); }
+extern "C" int ssrhip_lm_wt16_launches(const ssrhip_lm* lm) { return lm_packed_launches(lm, PK_WT16); }
+extern "C" int ssrhip_lm_wt32_launches(const ssrhip_lm* lm) { return lm_packed_launches(lm, PK_WT32); }
 
 extern "C" int ssrhip_lm_pair_status(ssrhip_lm* lm, ssrhip_stream_t stream) {
   SSR_REQUIRE(lm, "ssrhip_lm_pair_status: null engine");

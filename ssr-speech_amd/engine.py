@@ -10,6 +10,7 @@ import ctypes as C
 import math
 import os
 import time
+from collections import namedtuple
 from dataclasses import dataclass
 from typing import List, Optional, Sequence
 
@@ -115,6 +116,41 @@ def wt16_streamable(K: int) -> bool:
     return K > 0 and K % 64 == 0
 
 
+# The two packed orders an arena can hold: (pack routine, which inner dimensions get a copy). A matrix's copy of order `o` lives in
+# lay[name + "_" + o] / arena.head{1,2}_<o>, under the flag arena._<o>_ready.
+PACKED_ORDERS = {"w16": (to_w16_order, w16_streamable), "wt16": (to_wt16_order, wt16_streamable)}
+
+
+# One bf16 weight stream of the decode step per row range. `name` is the suffix of DecodeEngine's `stream_<name>` keyword and attribute, of
+# the C setter `ssrhip_lm_set_<name>` and of the counter `ssrhip_lm_<name>_launches`; [lo, hi] its rows (`rows`: as messages spell them);
+# `switch` the environment variable an engine built with `stream_<name>=None` reads and `default` what it means when unset; `order` the
+# packed order (PACKED_ORDERS) its kernels read; `only` what a refusal of more rows says.
+W16Stream = namedtuple("W16Stream", "name lo hi rows switch default order only")
+W16_STREAMS = (
+    W16Stream("w16", 1, 4, "<= 4", "SSRHIP_GEMV_W16", "1", "w16", "the bf16 weight stream exists for the <= 4-row decode step only"),
+    W16Stream("wt16", 5, 16, "5..16", "SSRHIP_GEMVM_W16", WT16_DEFAULT, "wt16", "the bf16 weight stream of the matrix-core step exists for 5..16 rows only"),
+    W16Stream("wt32", 17, 32, "17..32", "SSRHIP_GEMVM_W16", WT32_DEFAULT, "wt16", "the bf16 weight stream of the two-panel step exists for 17..32 rows only"),
+)
+
+
+def resolve_w16_stream(st: W16Stream, rows: int, weight_dtype: str, requested: Optional[bool], env) -> bool:
+    """Does an engine of `rows` rows on an arena of `weight_dtype` run stream `st`? requested None: on iff the arena is bf16, the rows are
+    the stream's and `env[st.switch]` (unset: st.default) does not start with '0'. requested True: ValueError for rows outside the range
+    (named before the dtype is looked at), then for an fp32 arena. `env` is a mapping like os.environ; nothing else is read."""
+    if requested is None:
+        return weight_dtype == "bf16" and st.lo <= rows <= st.hi and env.get(st.switch, st.default)[:1] != "0"
+    if not requested:
+        return False
+    if rows < st.lo:
+        owner = next(o for o in W16_STREAMS if rows <= o.hi)
+        raise ValueError(f"stream_{st.name} is the bf16 weight stream of the {st.rows}-row step; an engine of {rows} rows takes stream_{owner.name}")
+    if rows > st.hi:
+        raise ValueError(f"stream_{st.name}: {st.only} (this engine has {rows} rows)")
+    if weight_dtype != "bf16":
+        raise ValueError(f"stream_{st.name} needs an arena built with weight_dtype='bf16'")
+    return True
+
+
 class LMWeightsArena:
     """Device-resident fp32 weights in the layout the kernels want (one-time repack at load).
 
@@ -182,63 +218,52 @@ class LMWeightsArena:
                     lay[name + "_w"] = rnd(lay[name + "_w"])
             self.head1_w, self.head2_w = rnd(self.head1_w), rnd(self.head2_w)
 
+    def _ensure_packed(self, order: str) -> bool:
+        if self.weight_dtype != "bf16":
+            raise ValueError("packed bf16 copies need an arena built with weight_dtype='bf16' (the masters must hold the rounded values)")
+        if getattr(self, f"_{order}_ready", False):
+            return False
+        to_order, streamable = PACKED_ORDERS[order]
+        pack = lambda Wm: to_order(Wm) if streamable(Wm.shape[-1]) else None
+        for lay in self.layers:
+            for name in W16_FAMILIES:
+                lay[f"{name}_{order}"] = pack(lay[name + "_w"])
+        setattr(self, "head1_" + order, pack(self.head1_w))
+        setattr(self, "head2_" + order, pack(self.head2_w))
+        setattr(self, f"_{order}_ready", True)
+        self.generation += 1
+        return True
+
+    def _packed_struct(self, order: str):
+        w = _lib.LMW16()
+        arrays = {}
+        setattr(self, f"_{order}_arrays", arrays)       # the record points into them
+        for name in W16_FAMILIES:
+            if all(lay[f"{name}_{order}"] is not None for lay in self.layers):
+                arrays[name] = (C.c_void_p * self.L)(*[lay[f"{name}_{order}"].data_ptr() for lay in self.layers])
+                setattr(w, name + "_w16", C.cast(arrays[name], C.POINTER(C.c_void_p)))
+        w.head1_w16, w.head2_w16 = _lib.ptr(getattr(self, "head1_" + order)), _lib.ptr(getattr(self, "head2_" + order))
+        return w
+
     def ensure_w16_copies(self) -> bool:
         """Packed bf16 copies (`to_w16_order`) of the six matrix families for the <= 4-row decode step of a bf16 arena (+2 bytes per
         weight = +1.65 GB at 830M, built once on first use). A family whose inner dimension the kernels do not take (`w16_streamable`,
         e.g. d_model 128) gets none and streams its master. Returns True when the copies were created now."""
-        if self.weight_dtype != "bf16":
-            raise ValueError("packed bf16 copies need an arena built with weight_dtype='bf16' (the masters must hold the rounded values)")
-        if getattr(self, "_w16_ready", False):
-            return False
-        pack = lambda Wm: to_w16_order(Wm) if w16_streamable(Wm.shape[-1]) else None
-        for lay in self.layers:
-            for name in W16_FAMILIES:
-                lay[name + "_w16"] = pack(lay[name + "_w"])
-        self.head1_w16, self.head2_w16 = pack(self.head1_w), pack(self.head2_w)
-        self._w16_ready = True
-        self.generation += 1
-        return True
+        return self._ensure_packed("w16")
 
     def w16_struct(self):
         """ssrhip_lm_w16 of the packed copies (NULL where a family has none)."""
-        w = _lib.LMW16()
-        self._w16_arrays = {}
-        for name in W16_FAMILIES:
-            if all(lay[name + "_w16"] is not None for lay in self.layers):
-                arr = (C.c_void_p * self.L)(*[lay[name + "_w16"].data_ptr() for lay in self.layers])
-                self._w16_arrays[name] = arr
-                setattr(w, name + "_w16", C.cast(arr, C.POINTER(C.c_void_p)))
-        w.head1_w16, w.head2_w16 = _lib.ptr(self.head1_w16), _lib.ptr(self.head2_w16)
-        return w
+        return self._packed_struct("w16")
 
     def ensure_wt16_copies(self) -> bool:
-        """Packed bf16 streaming-order copies (`to_wt16_order`) of the six matrix families for the 5..16-row decode step of a bf16 arena
+        """Packed bf16 streaming-order copies (`to_wt16_order`) of the six matrix families for the 5..32-row decode step of a bf16 arena
         (+2 bytes per weight = +1.65 GB at 830M beside the fp32 streaming copies, built once on first use). A family whose inner dimension
         is no multiple of 64 (`wt16_streamable`) gets none and streams its fp32 streaming-order copy. Returns True when created now."""
-        if self.weight_dtype != "bf16":
-            raise ValueError("packed bf16 copies need an arena built with weight_dtype='bf16' (the masters must hold the rounded values)")
-        if getattr(self, "_wt16_ready", False):
-            return False
-        pack = lambda Wm: to_wt16_order(Wm) if wt16_streamable(Wm.shape[-1]) else None
-        for lay in self.layers:
-            for name in W16_FAMILIES:
-                lay[name + "_wt16"] = pack(lay[name + "_w"])
-        self.head1_wt16, self.head2_wt16 = pack(self.head1_w), pack(self.head2_w)
-        self._wt16_ready = True
-        self.generation += 1
-        return True
+        return self._ensure_packed("wt16")
 
     def wt16_struct(self):
-        """ssrhip_lm_w16 record of the SSRHIP_WT16_INDEX copies for ssrhip_lm_set_wt16 (NULL where a family has none)."""
-        w = _lib.LMW16()
-        self._wt16_arrays = {}
-        for name in W16_FAMILIES:
-            if all(lay[name + "_wt16"] is not None for lay in self.layers):
-                arr = (C.c_void_p * self.L)(*[lay[name + "_wt16"].data_ptr() for lay in self.layers])
-                self._wt16_arrays[name] = arr
-                setattr(w, name + "_w16", C.cast(arr, C.POINTER(C.c_void_p)))
-        w.head1_w16, w.head2_w16 = _lib.ptr(self.head1_wt16), _lib.ptr(self.head2_wt16)
-        return w
+        """ssrhip_lm_w16 record of the SSRHIP_WT16_INDEX copies for ssrhip_lm_set_wt16 / _wt32 (NULL where a family has none)."""
+        return self._packed_struct("wt16")
 
     def ensure_streaming_copies(self) -> bool:
         """Second copy of the six matrices of a decode step in the streaming order of the 5..16-row GEMV (one-time repack; used
@@ -309,13 +334,11 @@ class LMWeightsArena:
         n += self.lnf_w.numel() + self.lnf_b.numel()
         n += self.head1_w.numel() + self.head1_b.numel() + self.head2_w.numel() + self.head2_b.numel()
         n += (self.K + 1) * self.D  # K embedding rows + one pe row
-        half = 0                    # weights that have a packed bf16 copy stream 2 bytes each
-        if getattr(self, "_w16_ready", False):
-            half = sum(lay[name + "_w16"].numel() for lay in self.layers for name in W16_FAMILIES if lay[name + "_w16"] is not None)
-            half += sum(t.numel() for t in (self.head1_w16, self.head2_w16) if t is not None)
-        elif getattr(self, "_wt16_ready", False):   # the 5..16-row copies (their zero-padded rows are not weights)
-            half = sum(lay[name + "_w"].numel() for lay in self.layers for name in W16_FAMILIES if lay[name + "_wt16"] is not None)
-            half += sum(m.numel() for m, t in ((self.head1_w, self.head1_wt16), (self.head2_w, self.head2_wt16)) if t is not None)
+        half = 0                    # weights that have a packed bf16 copy stream 2 bytes each (the copy's zero-padded rows are not weights)
+        order = next((o for o in PACKED_ORDERS if getattr(self, f"_{o}_ready", False)), None)
+        if order is not None:
+            half = sum(lay[name + "_w"].numel() for lay in self.layers for name in W16_FAMILIES if lay[f"{name}_{order}"] is not None)
+            half += sum(m.numel() for m, h in ((self.head1_w, "head1_"), (self.head2_w, "head2_")) if getattr(self, h + order) is not None)
         return 4 * n - 2 * half
 
     def c_struct(self):
@@ -534,41 +557,18 @@ class DecodeEngine:
         self.B = n_utt * self.rows_per_utt
         if self.B not in (1, 2, 4) and not (5 <= self.B <= MAX_ROWS):
             raise ValueError(f"rows B={self.B} not supported by this build (1, 2, 4 or 5..{MAX_ROWS})")
-        if stream_w16 is None:
-            stream_w16 = arena.weight_dtype == "bf16" and self.B <= 4 and os.environ.get("SSRHIP_GEMV_W16", "1")[:1] != "0"
-        elif stream_w16 and self.B > 4:
-            raise ValueError(f"stream_w16: the bf16 weight stream exists for the <= 4-row decode step only (this engine has {self.B} rows)")
-        elif stream_w16 and arena.weight_dtype != "bf16":
-            raise ValueError("stream_w16 needs an arena built with weight_dtype='bf16'")
-        self.stream_w16 = bool(stream_w16)
-        if stream_wt16 is None:
-            stream_wt16 = arena.weight_dtype == "bf16" and 5 <= self.B <= 16 and os.environ.get("SSRHIP_GEMVM_W16", WT16_DEFAULT)[:1] != "0"
-        elif stream_wt16 and self.B <= 4:
-            raise ValueError(f"stream_wt16 is the bf16 weight stream of the 5..16-row step; an engine of {self.B} rows takes stream_w16")
-        elif stream_wt16 and self.B > 16:
-            raise ValueError(f"stream_wt16: the bf16 weight stream of the matrix-core step exists for 5..16 rows only (this engine has {self.B} rows)")
-        elif stream_wt16 and arena.weight_dtype != "bf16":
-            raise ValueError("stream_wt16 needs an arena built with weight_dtype='bf16'")
-        self.stream_wt16 = bool(stream_wt16)
-        if stream_wt32 is None:
-            stream_wt32 = arena.weight_dtype == "bf16" and self.B > 16 and os.environ.get("SSRHIP_GEMVM_W16", WT32_DEFAULT)[:1] != "0"
-        elif stream_wt32 and self.B <= 4:
-            raise ValueError(f"stream_wt32 is the bf16 weight stream of the 17..32-row step; an engine of {self.B} rows takes stream_w16")
-        elif stream_wt32 and self.B <= 16:
-            raise ValueError(f"stream_wt32 is the bf16 weight stream of the 17..32-row step; an engine of {self.B} rows takes stream_wt16")
-        elif stream_wt32 and arena.weight_dtype != "bf16":
-            raise ValueError("stream_wt32 needs an arena built with weight_dtype='bf16'")
-        self.stream_wt32 = bool(stream_wt32)
+        requested = dict(w16=stream_w16, wt16=stream_wt16, wt32=stream_wt32)
+        for st in W16_STREAMS:                    # the row ranges are disjoint: at most one is on
+            setattr(self, "stream_" + st.name, resolve_w16_stream(st, self.B, arena.weight_dtype, requested[st.name], os.environ))
+        self._stream = next((st for st in W16_STREAMS if getattr(self, "stream_" + st.name)), None)
         self.max_pages = (max_seq + PAGE - 1) // PAGE
         self.max_seq = self.max_pages * PAGE
         arena.ensure_positions(self.max_seq)      # every text / audio position of a row is < its sequence capacity
         if self.B > 4:
             arena.ensure_streaming_copies()       # the matrix-core GEMV streams W in its own order
         arena.ensure_split_planes()               # the prefill GEMMs run on the bf16 matrix cores with exactly split operands
-        if self.stream_w16:
-            arena.ensure_w16_copies()             # the <= 4-row step streams packed 2-byte weights
-        if self.stream_wt16 or self.stream_wt32:
-            arena.ensure_wt16_copies()            # the 5..32-row step streams packed 2-byte weights in streaming order
+        if self._stream is not None:
+            arena._ensure_packed(self._stream.order)   # the step streams packed 2-byte weights (at 5..32 rows in streaming order)
         self.max_steps = max_steps
         D, H, L, K = arena.D, arena.H, arena.L, arena.K
         self.hd = D // H
@@ -650,36 +650,31 @@ class DecodeEngine:
         ctx = C.c_void_p()
         _lib.check(self.lib.ssrhip_lm_create(C.byref(d), C.byref(self._w), C.byref(b), C.byref(ctx)), "ssrhip_lm_create")
         self._ctx = ctx
-        if self.stream_w16:                       # before the first step is enqueued or captured; gives the pairing slot back
-            w16 = self.a.w16_struct()
-            _lib.check(self.lib.ssrhip_lm_set_w16(ctx, C.byref(w16)), "ssrhip_lm_set_w16")
-        if self.stream_wt16:                      # before the first step is enqueued or captured
-            wt16 = self.a.wt16_struct()
-            _lib.check(self.lib.ssrhip_lm_set_wt16(ctx, C.byref(wt16)), "ssrhip_lm_set_wt16")
-        if self.stream_wt32:                      # the same record, read by the two-panel kernels
-            wt16 = self.a.wt16_struct()
-            _lib.check(self.lib.ssrhip_lm_set_wt32(ctx, C.byref(wt16)), "ssrhip_lm_set_wt32")
+        if self._stream is not None:              # before the first step is enqueued or captured; stream_w16 gives the pairing slot back
+            rec, setter = self.a._packed_struct(self._stream.order), "ssrhip_lm_set_" + self._stream.name
+            _lib.check(getattr(self.lib, setter)(ctx, C.byref(rec)), setter)
         why = C.create_string_buffer(256)
         self.pairing = bool(self.lib.ssrhip_lm_pairing(ctx, why, 256))
         self.pairing_why = why.value.decode(errors="replace")
+
+    def _launches_per_step(self, name: str) -> int:
+        return 0 if self._ctx is None else int(getattr(self.lib, f"ssrhip_lm_{name}_launches")(self._ctx))
 
     @property
     def w16_launches_per_step(self) -> int:
         """GEMV launches of the last enqueued decode step that ran a bf16-stream kernel (4 * layers + 2 when every family qualifies;
         0 for an engine that streams fp32 weights or has not stepped yet)."""
-        return 0 if self._ctx is None else int(self.lib.ssrhip_lm_w16_launches(self._ctx))
+        return self._launches_per_step("w16")
 
     @property
     def wt16_launches_per_step(self) -> int:
-        """GEMV launches of the last enqueued decode step that ran a kernel of the 5..16-row bf16 weight stream (4 * layers + 2 when every
-        family qualifies; 0 for an engine that streams fp32 weights or has not stepped yet)."""
-        return 0 if self._ctx is None else int(self.lib.ssrhip_lm_wt16_launches(self._ctx))
+        """The same for the kernels of the 5..16-row bf16 weight stream."""
+        return self._launches_per_step("wt16")
 
     @property
     def wt32_launches_per_step(self) -> int:
-        """GEMV launches of the last enqueued decode step that ran a kernel of the 17..32-row bf16 weight stream (4 * layers + 2 when every
-        family qualifies; 0 for an engine that streams fp32 weights or has not stepped yet)."""
-        return 0 if self._ctx is None else int(self.lib.ssrhip_lm_wt32_launches(self._ctx))
+        """The same for the kernels of the 17..32-row bf16 weight stream."""
+        return self._launches_per_step("wt32")
 
     def close(self):
         if self._ctx is not None:

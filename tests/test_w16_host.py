@@ -10,7 +10,7 @@ import torch
 import ssr_speech_amd  # noqa: F401
 from ssr_speech_amd import _lib
 from ssr_speech_amd import weights as W
-from ssr_speech_amd.engine import LMWeightsArena, to_w16_order, w16_streamable
+from ssr_speech_amd.engine import W16_STREAMS, WT16_DEFAULT, WT32_DEFAULT, LMWeightsArena, resolve_w16_stream, to_w16_order, w16_streamable
 
 
 def w16_index(n, k, K):
@@ -119,6 +119,52 @@ def test_set_weight_dtype_switch():
         m.weight_dtype = "fp32"                                             # read-only
     m.set_weight_dtype("fp32")
     assert m.weight_dtype == "fp32"
+
+
+def test_resolve_w16_stream_follows_the_written_rules():
+    """The pure decision behind DecodeEngine's stream_w16 / stream_wt16 / stream_wt32, against the rules as DecodeEngine.__init__ documents
+    them, written out here independently of the table: every row count at a range edge x both arenas x requested None / True / False x the
+    switch unset / "0" / "1", for all three streams."""
+    rules = dict(w16=(1, 4, "SSRHIP_GEMV_W16", "1"), wt16=(5, 16, "SSRHIP_GEMVM_W16", WT16_DEFAULT), wt32=(17, 32, "SSRHIP_GEMVM_W16", WT32_DEFAULT))
+    assert [st.name for st in W16_STREAMS] == list(rules) and WT16_DEFAULT == WT32_DEFAULT == "0"
+    other = dict(SSRHIP_GEMV_W16="SSRHIP_GEMVM_W16", SSRHIP_GEMVM_W16="SSRHIP_GEMV_W16")
+    for st in W16_STREAMS:
+        lo, hi, switch, default = rules[st.name]
+        for rows in (1, 2, 4, 5, 16, 17, 32):
+            for dtype in ("fp32", "bf16"):
+                for value in (None, "0", "1"):
+                    env = {} if value is None else {switch: value}
+                    env[other[switch]] = "0" if value != "0" else "1"          # the other streams' switch is not looked at
+                    case = (st.name, rows, dtype, value)
+                    want = dtype == "bf16" and lo <= rows <= hi and (default if value is None else value)[:1] != "0"
+                    assert resolve_w16_stream(st, rows, dtype, None, env) is want, case
+                    assert resolve_w16_stream(st, rows, dtype, False, env) is False, case
+                    if lo <= rows <= hi and dtype == "bf16":
+                        assert resolve_w16_stream(st, rows, dtype, True, env) is True, case       # asked for: the switch is not read
+                        continue
+                    with pytest.raises(ValueError) as err:
+                        resolve_w16_stream(st, rows, dtype, True, env)
+                    msg = str(err.value)
+                    assert msg.startswith("stream_" + st.name), case
+                    # rows outside the range win over the dtype, and the message names the stream that takes these rows
+                    if rows < lo:
+                        taker = "stream_w16" if rows <= 4 else "stream_wt16"
+                        assert msg.endswith(f"an engine of {rows} rows takes {taker}") and "bf16'" not in msg, (case, msg)
+                    elif rows > hi:
+                        assert msg.endswith(f"only (this engine has {rows} rows)") and "bf16'" not in msg, (case, msg)
+                    else:
+                        assert msg == f"stream_{st.name} needs an arena built with weight_dtype='bf16'", (case, msg)
+    # the messages the engine's callers match on, byte for byte
+    st = {s_.name: s_ for s_ in W16_STREAMS}
+    for name, rows, msg in (("w16", 5, "stream_w16: the bf16 weight stream exists for the <= 4-row decode step only (this engine has 5 rows)"),
+                            ("wt16", 4, "stream_wt16 is the bf16 weight stream of the 5..16-row step; an engine of 4 rows takes stream_w16"),
+                            ("wt16", 17, "stream_wt16: the bf16 weight stream of the matrix-core step exists for 5..16 rows only (this engine has 17 rows)"),
+                            ("wt32", 2, "stream_wt32 is the bf16 weight stream of the 17..32-row step; an engine of 2 rows takes stream_w16"),
+                            ("wt32", 16, "stream_wt32 is the bf16 weight stream of the 17..32-row step; an engine of 16 rows takes stream_wt16")):
+        for dtype in ("fp32", "bf16"):
+            with pytest.raises(ValueError) as err:
+                resolve_w16_stream(st[name], rows, dtype, True, {})
+            assert str(err.value) == msg, (name, rows, dtype)
 
 
 def test_gemv_w16_contract_errors_need_no_gpu():

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import ssr_speech_amd  # noqa: F401
+from helpers_w16 import fake_gemv_args
 from ssr_speech_amd import _lib
 from ssr_speech_amd import weights as W
 from ssr_speech_amd.engine import LMWeightsArena, from_wt16_order, to_streaming_order, to_wt16_order, wt16_streamable
@@ -102,12 +103,8 @@ def test_bf16_arena_builds_the_wt16_copies_once():
     assert w.head1_w16 == a16.head1_wt16.data_ptr() and not w.head2_w16 and w.ffn2_w16[0] == lay["ffn2_wt16"].data_ptr()
 
 
-def _fake_args(B=8, N=512, K=2048, w_tiled=1):
-    a = _lib.GemvArgs()
-    a.W, a.y, a.x = 0x1000, 0x2000, 0x3000                  # never dereferenced: every call below is answered before any launch
-    a.B, a.N, a.K, a.groups, a.x_stride, a.y_stride = B, N, K, 1, K, N
-    a.w_tiled = w_tiled
-    return a
+def _fake_args(B=8, **kw):
+    return fake_gemv_args(B, **kw)
 
 
 def test_gemv_wt16_refusals_need_no_gpu():

@@ -5,17 +5,14 @@ import os
 import re
 
 import ssr_speech_amd  # noqa: F401
+from helpers_w16 import fake_gemv_args
 from ssr_speech_amd import _lib
 
 NEW_SYMBOLS = ("ssrhip_gemv_wt32", "ssrhip_gemv_wt32_applicable", "ssrhip_lm_set_wt32", "ssrhip_lm_wt32_launches")
 
 
-def _fake_args(B=32, N=512, K=2048, w_tiled=1, pro=_lib.PRO_NONE):
-    a = _lib.GemvArgs()
-    a.W, a.y, a.x = 0x1000, 0x2000, 0x3000                  # never dereferenced: every call below is answered before any launch
-    a.B, a.N, a.K, a.groups, a.x_stride, a.y_stride = B, N, K, 1, K, N
-    a.w_tiled, a.pro = w_tiled, pro
-    return a
+def _fake_args(B=32, **kw):
+    return fake_gemv_args(B, **kw)
 
 
 def test_gemv_wt32_refusals_need_no_gpu():

@@ -33,7 +33,7 @@ import torch  # noqa: E402
 import ssr_speech_amd  # noqa: E402,F401
 from ssr_speech_amd import layout as LY  # noqa: E402
 from ssr_speech_amd import weights as W  # noqa: E402
-from ssr_speech_amd.engine import DecodeEngine, DecodeKnobs, LMWeightsArena  # noqa: E402
+from ssr_speech_amd.engine import W16_STREAMS, DecodeEngine, DecodeKnobs, LMWeightsArena  # noqa: E402
 from bench import synth_inputs  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -72,7 +72,7 @@ for u in range(max(utts_of.values())):
 kn = DecodeKnobs(top_k=1 if a.greedy else 40, top_p=1.0 if a.greedy else 0.8, temperature=1.0, stop_repetition=2, cfg_coef=1.5, cfg_stride=5,
                  use_cfg=True, text_len=L, n_spans=num_task, seed=2024)
 
-res = {name: {"ms": [], "gemv": [], "attn": [], "sample": [], "tok": None, "w16": 0, "wt16": 0, "wt32": 0} for name, _ in variants}
+res = {name: {"ms": [], "gemv": [], "attn": [], "sample": [], "tok": None, **{st.name: 0 for st in W16_STREAMS}} for name, _ in variants}
 for rep in range(a.reps):
     for name, knobs in variants:
         for k in all_knobs:
@@ -91,9 +91,8 @@ for rep in range(a.reps):
         n_done = int(eng.states()[0].n_steps)
         tok = eng.generated[0, :n_done].cpu().numpy().copy()
         r = res[name]
-        r["w16"] = eng.w16_launches_per_step
-        r["wt16"] = eng.wt16_launches_per_step
-        r["wt32"] = eng.wt32_launches_per_step
+        for st in W16_STREAMS:
+            r[st.name] = getattr(eng, st.name + "_launches_per_step")
         r["ms"].append(ms)
         r["gemv"].append(eng.time_category("gemv", 50)[0])
         r["attn"].append(eng.time_category("attn", 50)[0])
@@ -115,4 +114,4 @@ for name, knobs in variants:
     print(f"{name:14s} {U:2d} utts x CFG = {2 * U:2d} rows  tok/s {4 * U / (statistics.median(r['ms']) * 1e-3):9.1f}  "
           f"ms/step min {min(r['ms']):.4f} med {statistics.median(r['ms']):.4f}  all {' '.join(f'{v:.4f}' for v in r['ms'])} | "
           f"gemv {min(r['gemv']):.3f} x {r['launches']['gemv']} attn {min(r['attn']):.3f} x {r['launches']['attn']} "
-          f"sample {min(r['sample']):.3f} x {r['launches']['sample']} us{same}   [{dtype_of[name]}, {r['w16']} w16 + {r['wt16']} wt16 + {r['wt32']} wt32 launches; {' '.join(f'{k}={v}' for k, v in knobs.items()) or 'defaults'}]")
+          f"sample {min(r['sample']):.3f} x {r['launches']['sample']} us{same}   [{dtype_of[name]}, {' + '.join(f'{r[st.name]} {st.name}' for st in W16_STREAMS)} launches; {' '.join(f'{k}={v}' for k, v in knobs.items()) or 'defaults'}]")

@@ -24,6 +24,7 @@ import torch  # noqa: E402
 import ssr_speech_amd  # noqa: E402,F401
 from ssr_speech_amd import dp  # noqa: E402
 from ssr_speech_amd import weights as W  # noqa: E402
+from ssr_speech_amd.engine import W16_STREAMS  # noqa: E402
 from ssr_speech_amd.models.ssr import SSR_Speech  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -49,13 +50,14 @@ kw = dict(top_k=1, top_p=1.0, temperature=1.0, stop_repetition=2, cfg_coef=1.5, 
 groups = [int(g) for g in a.groups.split(",")]
 
 if a.wt16 or a.wt32:
-    kind = "wt32" if a.wt32 else "wt16"
+    st = next(s for s in reversed(W16_STREAMS) if getattr(a, s.name, False))      # --wt32 wins over --wt16
+    kind = st.name
     g = 16 if a.wt32 else groups[0]
     arms = (("bf16_masters", "0"), ("bf16_" + kind, "1"))
     res = {name: {"decode_ms": [], "tokens": None, "launches": 0} for name, _ in arms}
     for rep in range(a.reps):
         for name, sw in arms:
-            os.environ["SSRHIP_GEMVM_W16"] = sw
+            os.environ[st.switch] = sw
             model.set_weight_dtype("fp32")
             model.set_weight_dtype("bf16")              # drops the arena and the engines: the next call builds them under this switch
             dp.generate(model, utts[:2 * g], seed=0, group=g, **kw)      # untimed: arena, engine, graph capture

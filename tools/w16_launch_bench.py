@@ -27,7 +27,7 @@ import torch  # noqa: E402
 
 import ssr_speech_amd  # noqa: E402,F401
 from ssr_speech_amd import _lib  # noqa: E402
-from ssr_speech_amd.engine import to_streaming_order, to_w16_order, to_wt16_order  # noqa: E402
+from ssr_speech_amd.engine import PACKED_ORDERS, W16_STREAMS, to_streaming_order  # noqa: E402
 
 # name, G, N, K, prologue, activation, epilogue: the six launches of the 830M step
 SHAPES = [
@@ -52,15 +52,17 @@ def main(argv=None):
     B, dev = opt.rows, torch.device("cuda")
     g = torch.Generator(device="cuda").manual_seed(1)
     rows = []
-    mc = B > 4                                                    # the matrix-core step: tiled activations, streaming-order weights
-    forms = ("fp32", "wt32") if B > 16 else ("fp32", "wt16", "wt16_depth16") if mc else ("fp32", "w16")
+    st = next(s for s in W16_STREAMS if s.lo <= B <= s.hi)        # the bf16 stream of these rows
+    mc = st.order == "wt16"                                       # the matrix-core step: tiled activations, streaming-order weights
+    forms = ("fp32", st.name) + (("wt16_depth16",) if st.name == "wt16" else ())
+    to_packed, gemv_packed = PACKED_ORDERS[st.order][0], getattr(L, "ssrhip_gemv_" + st.name)
     xrows = 32 if B > 16 else 16 if mc else B                     # (tiled: 16 columns per panel, any values)
     for name, G, N, K, pro, act, epi in SHAPES:
         if mc and pro == _lib.PRO_ATTN_COMBINE:
             pro = _lib.PRO_NONE                                   # at 5..32 rows the split-KV merge is a launch of its own
         ny = K if epi == _lib.EPI_QKV_APPEND else G * N
         masters = [(torch.randn(G, N, K, device=dev, generator=g) / K ** 0.5).to(torch.bfloat16).float() for _ in range(opt.chain)]
-        packed = [to_wt16_order(m) if mc else to_w16_order(m) for m in masters]
+        packed = [to_packed(m) for m in masters]
         if mc:
             masters = [to_streaming_order(m) for m in masters]
         bias = torch.randn(G, N, device=dev, generator=g)
@@ -99,17 +101,11 @@ def main(argv=None):
             def chain():
                 for i in range(opt.chain):
                     a = args_of(i)
-                    if form == "w16":
-                        rc = L.ssrhip_gemv_w16(C.byref(a), packed[i].data_ptr(), _lib.stream_ptr())
-                        assert rc == 0, (name, rc, L.ssrhip_last_error())
-                    elif form == "wt32":
-                        rc = L.ssrhip_gemv_wt32(C.byref(a), packed[i].data_ptr(), _lib.stream_ptr())
-                        assert rc == 0, (name, rc, L.ssrhip_last_error())
-                    elif form.startswith("wt16"):
-                        rc = L.ssrhip_gemv_wt16(C.byref(a), packed[i].data_ptr(), _lib.stream_ptr())
-                        assert rc == 0, (name, rc, L.ssrhip_last_error())
-                    else:
+                    if form == "fp32":
                         _lib.check(L.ssrhip_gemv(C.byref(a), _lib.stream_ptr()))
+                    else:
+                        rc = gemv_packed(C.byref(a), packed[i].data_ptr(), _lib.stream_ptr())
+                        assert rc == 0, (name, rc, L.ssrhip_last_error())
             side = torch.cuda.Stream()
             with torch.cuda.stream(side):
                 chain()                                           # module load, first-launch costs
