@@ -307,7 +307,8 @@ typedef struct ssrhip_gemm_args {
    * problem is large enough, N > 64, K % 8 == 0 — the GEMM runs on the bf16 matrix cores with every fp32 operand split EXACTLY into
    * three bf16 pieces and the six largest cross products accumulated in fp32 (csrc/gemm_split.hip): fp32 accuracy (error against an
    * fp64 reference no larger than the fp32 chain's), ~1.3-1.5x the speed, NOT bit-identical to the k-ordered fp32 chain. The codec
-   * passes it (parity bar: waveform tolerance); the LM prefill does not (greedy tokens are compared bit for bit). */
+   * passes it, and so do the LM prefill and ssrhip_lm_score when their weights record carries planes (ssrhip_lm_weights *_ws).
+   * For ssrhip_gemm_w1 (below) the same field holds ONE bf16 plane [N][K]. */
   const uint16_t* W_split;
   /* SSRHIP_ACT_ELU: apply ELU(alpha = 1) LAST — after act, residual, R and the class bias — i.e. store what the consumer would compute
    * on load. For tensors that are only ever read through ELU (SEANet: a residual block's output feeds `ELU -> conv`, seanet.py:137-141,
@@ -318,6 +319,19 @@ int ssrhip_gemm(const ssrhip_gemm_args* a, ssrhip_stream_t stream);
 /* W fp32 [n_elems] -> out bf16 [3][n_elems]: piece p of element i at out[p * n_elems + i], w = w0 + w1 + w2 exactly
  * (w0 = bf16_rne(w), w1 = bf16_rne(w - w0), w2 = bf16_rne(w - w0 - w1)). One-time preparation of a weight matrix for W_split. */
 int ssrhip_split_weights(const float* W, uint16_t* out, int64_t n_elems, ssrhip_stream_t stream);
+/* The split GEMM for a weight matrix whose every value IS a bf16 value (a weight_dtype="bf16" arena's masters): `a->W_split` is ONE bf16
+ * plane [N][K] (the values themselves, 2 bytes per weight), `a->W` is not read. The exact split of such a matrix has two planes of
+ * zeros; this entry runs the three products that remain (a2w0, a1w0, a0w0, in ssrhip_gemm's order) with one W plane in flight, in the
+ * tile shapes ssrhip_gemm would choose, and returns ssrhip_gemm's result on the three planes of the same matrix BIT FOR BIT for finite
+ * activations (a non-finite activation times a zero plane is NaN in the six-product form only). Returns 0 when it launched; 1 when the
+ * call does not qualify and NOTHING was launched — ssrhip_gemm's rule for W_split (N > 64, K % 8 == 0, grid limits, SSRHIP_GEMM_SPLIT
+ * not "0..."), and act_in == SSRHIP_ACT_ELU, which has no one-plane kernel; the caller then calls ssrhip_gemm with W_split = NULL, the
+ * chain a three-plane call that does not qualify takes too; < 0 for a contract error (ssrhip_last_error; e.g. W_split == NULL), before
+ * any HIP call. NEVER hand a one-plane buffer to ssrhip_gemm: it reads three planes, twice the buffer's size past its end. */
+int ssrhip_gemm_w1(const ssrhip_gemm_args* a, ssrhip_stream_t stream);
+/* how many calls of ssrhip_gemm_w1 launched a one-plane kernel (answered 0) in this process so far, through whichever entry (direct,
+ * ssrhip_lm_prefill, ssrhip_lm_score_w1): a caller that expects the one-plane path can tell it from the silent fp32-chain fallback. */
+int64_t ssrhip_gemm_w1_launches(void);
 
 
 /* ------------------------------------------------------------------------------------------------
@@ -506,6 +520,12 @@ int ssrhip_lm_set_wt32(ssrhip_lm* lm, const ssrhip_lm_w16* wt16);
 /* how many GEMV launches of the last enqueued (or captured) decode step ran a kernel of csrc/gemv_mfma32_w16.hip (4 * n_layer + 2 when
  * every family qualifies); the other two counters stay 0 for these engines */
 int ssrhip_lm_wt32_launches(const ssrhip_lm* lm);
+/* on != 0: the *_ws buffers of this engine's ssrhip_lm_weights hold ONE bf16 plane [N][K] each (a bf16 arena: the weight itself) instead
+ * of three; ssrhip_lm_prefill then multiplies through ssrhip_gemm_w1 (and, where that answers 1, through the fp32 chain on the masters).
+ * Same KV cache and x as with the three planes of the same weights, bit for bit. The count is the CALLER's statement about its buffers
+ * and comes from nowhere else (no environment variable is read). Refused (< 0) for an engine created without planes and for one whose
+ * decode step is already captured. */
+int ssrhip_lm_set_prefill_w1(ssrhip_lm* lm, int32_t on);
 /* enqueue `n_steps` decode steps (graph replays when use_graph!=0) */
 int ssrhip_lm_decode(ssrhip_lm* lm, int32_t n_steps, int32_t use_graph, ssrhip_stream_t stream);
 /* prefill R rows ([text || audio] of every sequence, flattened): fills the cache for all layers.
@@ -563,6 +583,9 @@ typedef struct ssrhip_score_args {
 /* Writes nll / rank of every scored row and codebook. Layer GEMMs use the ssrhip_lm_weights split planes when present (same rule as
  * ssrhip_lm_prefill). The workspaces, the scratch pool and the output belong to the caller. */
 int ssrhip_lm_score(const ssrhip_lm_dims* d, const ssrhip_lm_weights* w, const ssrhip_score_args* a, ssrhip_stream_t stream);
+/* ssrhip_lm_score for ONE-plane buffers (ssrhip_gemm_w1): every *_ws of `w` is one bf16 plane [N][K], head1_ws one [K*Hh][D], head2_ws
+ * [K][card][Hh]. Same nll / rank as ssrhip_lm_score on the three planes of the same bf16-valued weights, bit for bit. */
+int ssrhip_lm_score_w1(const ssrhip_lm_dims* d, const ssrhip_lm_weights* w, const ssrhip_score_args* a, ssrhip_stream_t stream);
 /* Cross entropy and rank of M rows of logits [M][ld] (one codebook) against target [M]: one wave64 per row, one pass with an online max and
  * rescaled fp32 exp-sum. nll[m] = logsumexp(row) - row[target]; rank[m] = #{c != target : row[c] > row[target]} (top-10 hit = rank < 10;
  * exact ties at the 10th place count as hits, where torch.topk's order is arbitrary). ld % 4 == 0, card <= ld. */

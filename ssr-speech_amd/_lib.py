@@ -193,6 +193,8 @@ SYMBOLS = [
     ("ssrhip_sample", C.c_int, [C.POINTER(SampleArgs), C.c_void_p]),
     ("ssrhip_gemm", C.c_int, [C.POINTER(GemmArgs), C.c_void_p]),
     ("ssrhip_split_weights", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    ("ssrhip_gemm_w1", C.c_int, [C.POINTER(GemmArgs), C.c_void_p]),
+    ("ssrhip_gemm_w1_launches", C.c_int64, []),
     ("ssrhip_conv_few_out", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_void_p]),
     ("ssrhip_conv_cin1", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_void_p]),
     ("ssrhip_pad_reflect", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p]),
@@ -209,6 +211,8 @@ SYMBOLS = [
     ("ssrhip_lm_prefill", C.c_int, [C.c_void_p, C.POINTER(PrefillArgs), C.c_void_p]),
     ("ssrhip_lm_embed_pending", C.c_int, [C.c_void_p, C.c_void_p]),
     ("ssrhip_lm_score", C.c_int, [C.POINTER(LMDims), C.POINTER(LMWeights), C.POINTER(ScoreArgs), C.c_void_p]),
+    ("ssrhip_lm_score_w1", C.c_int, [C.POINTER(LMDims), C.POINTER(LMWeights), C.POINTER(ScoreArgs), C.c_void_p]),
+    ("ssrhip_lm_set_prefill_w1", C.c_int, [C.c_void_p, C.c_int32]),
     ("ssrhip_xent_rank", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("ssrhip_lm_pairing", C.c_int, [C.c_void_p, C.c_char_p, C.c_int32]),
     ("ssrhip_lm_pair_status", C.c_int, [C.c_void_p, C.c_void_p]),

@@ -60,6 +60,7 @@ struct ssrhip_lm {
   std::vector<const float*> ptrs[16];
   std::vector<const uint16_t*> sptrs[4];
   bool prefill_split = false;   // bf16 planes present and SSRHIP_PREFILL_SPLIT != 0
+  bool prefill_w1 = false;      // ... and they hold ONE plane each (ssrhip_lm_set_prefill_w1: the caller's statement about its buffers)
   hipStream_t cap_stream = nullptr;
   hipGraph_t graph = nullptr;
   hipGraphExec_t exec = nullptr;
@@ -547,6 +548,13 @@ static int lm_packed_launches(const ssrhip_lm* lm, int kind) { return lm && lm->
 extern "C" int ssrhip_lm_set_w16(ssrhip_lm* lm, const ssrhip_lm_w16* w16) { return lm_set_packed(lm, w16, PK_W16); }
 extern "C" int ssrhip_lm_set_wt16(ssrhip_lm* lm, const ssrhip_lm_w16* wt16) { return lm_set_packed(lm, wt16, PK_WT16); }
 extern "C" int ssrhip_lm_set_wt32(ssrhip_lm* lm, const ssrhip_lm_w16* wt16) { return lm_set_packed(lm, wt16, PK_WT32); }
+extern "C" int ssrhip_lm_set_prefill_w1(ssrhip_lm* lm, int32_t on) {
+  SSR_REQUIRE(lm, "ssrhip_lm_set_prefill_w1: null engine");
+  SSR_REQUIRE(!lm->exec, "ssrhip_lm_set_prefill_w1: the decode step of this engine is already captured (call it before the first ssrhip_lm_decode)");
+  SSR_REQUIRE(!on || lm->w.in_proj_ws, "ssrhip_lm_set_prefill_w1: this engine was created without planes (ssrhip_lm_weights *_ws)");
+  lm->prefill_w1 = on != 0;
+  return 0;
+}
 extern "C" int ssrhip_lm_w16_launches(const ssrhip_lm* lm) { return lm_packed_launches(lm, PK_W16); }
 extern "C" int ssrhip_lm_wt16_launches(const ssrhip_lm* lm) { return lm_packed_launches(lm, PK_WT16); }
 extern "C" int ssrhip_lm_wt32_launches(const ssrhip_lm* lm) { return lm_packed_launches(lm, PK_WT32); }
@@ -657,8 +665,22 @@ extern "C" int ssrhip_lm_time_category(ssrhip_lm* lm, int32_t category, int32_t 
 
 // The layer loop over R flattened rows (embedding, then n_layer x [LN1 -> QKV GEMM -> KV scatter -> attention -> out-proj + residual
 // -> LN2 -> FFN1 + ReLU -> FFN2 + residual]), shared by the prefill and the scoring entry. `kv` is the cache the rows write and read;
-// with kv.n_layer == 1 (a scoring scratch pool) every layer uses layer 0 of it. `split`: GEMMs on the bf16 planes of `w`.
-static int lm_layer_loop(const ssrhip_lm_dims& d, const ssrhip_lm_weights& w, bool split, const ssrhip_kv& kv, const ssrhip_prefill_args* p,
+// with kv.n_layer == 1 (a scoring scratch pool) every layer uses layer 0 of it. `planes`: how many bf16 planes each `*_ws` of `w` holds —
+// 0 = GEMMs on the fp32 chain, 3 = ssrhip_gemm on the exact split, 1 = ssrhip_gemm_w1.
+//
+// One GEMM of the LM on `planes` planes at `ws`. One plane: ssrhip_gemm_w1, and where it does not qualify (answer 1) the fp32 chain on the
+// masters — what a three-plane call that does not qualify takes too (ssrhip_gemm never reads a one-plane buffer as three).
+static int lm_gemm(ssrhip_gemm_args& g, int planes, const uint16_t* ws, hipStream_t s) {
+  g.W_split = planes ? ws : nullptr;
+  if (planes == 1) {
+    const int rc = ssrhip_gemm_w1(&g, s);
+    if (rc != 1) return rc;
+    g.W_split = nullptr;
+  }
+  return ssrhip_gemm(&g, s);
+}
+
+static int lm_layer_loop(const ssrhip_lm_dims& d, const ssrhip_lm_weights& w, int planes, const ssrhip_kv& kv, const ssrhip_prefill_args* p,
                          bool tiled_attn, hipStream_t s) {
   const int D = d.d_model, R = p->R;
   const bool one_layer_kv = kv.n_layer == 1;
@@ -674,8 +696,7 @@ static int lm_layer_loop(const ssrhip_lm_dims& d, const ssrhip_lm_weights& w, bo
     memset(&g, 0, sizeof(g));
     g.A = p->xn; g.W = w.in_proj_w[l]; g.bias = w.in_proj_b[l]; g.C = p->qkv;
     g.M = R; g.N = 3 * D; g.K = D; g.lda = D; g.ldc = 3 * D;
-    if (split) g.W_split = w.in_proj_ws[l];
-    if (int rc = ssrhip_gemm(&g, s)) return rc;
+    if (int rc = lm_gemm(g, planes, planes ? w.in_proj_ws[l] : nullptr, s)) return rc;
     if (int rc = ssrhip_kv_scatter(p->qkv, &kv, kl, p->row_seq, p->row_pos, R, s)) return rc;
 
     ssrhip_attn_args at;
@@ -695,20 +716,17 @@ static int lm_layer_loop(const ssrhip_lm_dims& d, const ssrhip_lm_weights& w, bo
     memset(&g, 0, sizeof(g));
     g.A = p->o; g.W = w.out_proj_w[l]; g.bias = w.out_proj_b[l]; g.C = p->x;
     g.M = R; g.N = D; g.K = D; g.lda = D; g.ldc = D; g.residual = 1;
-    if (split) g.W_split = w.out_proj_ws[l];
-    if (int rc = ssrhip_gemm(&g, s)) return rc;
+    if (int rc = lm_gemm(g, planes, planes ? w.out_proj_ws[l] : nullptr, s)) return rc;
 
     if (int rc = ssrhip_layernorm(p->x, w.ln2_w[l], w.ln2_b[l], 1e-5f, p->xn, R, D, s)) return rc;
     memset(&g, 0, sizeof(g));
     g.A = p->xn; g.W = w.ffn1_w[l]; g.bias = w.ffn1_b[l]; g.C = p->h;
     g.M = R; g.N = d.d_ffn; g.K = D; g.lda = D; g.ldc = d.d_ffn; g.act = SSRHIP_ACT_RELU;
-    if (split) g.W_split = w.ffn1_ws[l];
-    if (int rc = ssrhip_gemm(&g, s)) return rc;
+    if (int rc = lm_gemm(g, planes, planes ? w.ffn1_ws[l] : nullptr, s)) return rc;
     memset(&g, 0, sizeof(g));
     g.A = p->h; g.W = w.ffn2_w[l]; g.bias = w.ffn2_b[l]; g.C = p->x;
     g.M = R; g.N = D; g.K = d.d_ffn; g.lda = d.d_ffn; g.ldc = D; g.residual = 1;
-    if (split) g.W_split = w.ffn2_ws[l];
-    if (int rc = ssrhip_gemm(&g, s)) return rc;
+    if (int rc = lm_gemm(g, planes, planes ? w.ffn2_ws[l] : nullptr, s)) return rc;
   }
   return 0;
 }
@@ -719,12 +737,13 @@ extern "C" int ssrhip_lm_prefill(ssrhip_lm* lm, const ssrhip_prefill_args* p, ss
   SSR_REQUIRE(p->x && p->xn && p->qkv && p->o && p->h && (tiled_attn || (p->part_o && p->part_ml)), "ssrhip_lm_prefill: null workspace");
   ssrhip_kv kv = lm->b.kv;
   if (p->table) kv.table = p->table;              // two-phase admission: the rows being filled are not in the decode step's table yet
-  if (int rc = lm_layer_loop(lm->d, lm->w, lm->prefill_split, kv, p, tiled_attn, (hipStream_t)stream)) return rc;
+  if (int rc = lm_layer_loop(lm->d, lm->w, lm->prefill_split ? (lm->prefill_w1 ? 1 : 3) : 0, kv, p, tiled_attn, (hipStream_t)stream)) return rc;
   if (p->no_embed) return 0;
   return ssrhip_lm_embed_pending(lm, stream);
 }
 
-extern "C" int ssrhip_lm_score(const ssrhip_lm_dims* d, const ssrhip_lm_weights* w, const ssrhip_score_args* a, ssrhip_stream_t stream) {
+// the one body of ssrhip_lm_score (np = 3) and ssrhip_lm_score_w1 (np = 1): `np` = planes in every *_ws buffer of `w` and `a`
+static int lm_score(const ssrhip_lm_dims* d, const ssrhip_lm_weights* w, const ssrhip_score_args* a, int np, ssrhip_stream_t stream) {
   SSR_REQUIRE(d && w && a, "ssrhip_lm_score: null argument");
   SSR_REQUIRE(a->tok && a->pos && a->kind && a->row_seq && a->row_pos && a->row_len && a->seq_start && a->score_first && a->score_count &&
               a->target && a->nll && a->rank, "ssrhip_lm_score: null row / target / output array");
@@ -758,7 +777,7 @@ extern "C" int ssrhip_lm_score(const ssrhip_lm_dims* d, const ssrhip_lm_weights*
   p.R = a->R; p.max_splits = (a->max_len + SSRHIP_PAGE - 1) / SSRHIP_PAGE;
   p.x = a->x; p.xn = a->xn; p.qkv = a->qkv; p.o = a->o; p.h = a->h;
   p.seq_start = a->seq_start; p.n_seq = a->n_seq; p.max_len = a->max_len;
-  if (int rc = lm_layer_loop(*d, *w, layer_split, a->kv, &p, true, s)) return rc;
+  if (int rc = lm_layer_loop(*d, *w, layer_split ? np : 0, a->kv, &p, true, s)) return rc;
 
   // final LayerNorm of the scored rows only, gathered by the launch itself: one launch per sequence (its scored rows are contiguous)
   long off = 0;
@@ -775,19 +794,24 @@ extern "C" int ssrhip_lm_score(const ssrhip_lm_dims* d, const ssrhip_lm_weights*
     memset(&g, 0, sizeof(g));
     g.A = a->hs + (size_t)m0 * D; g.W = w->head1_w; g.bias = w->head1_b; g.C = a->head_h;
     g.M = mc; g.N = K * Hh; g.K = D; g.lda = D; g.ldc = K * Hh; g.act = SSRHIP_ACT_GELU_ERF;
-    if (head_split) g.W_split = a->head1_ws;
-    if (int rc = ssrhip_gemm(&g, s)) return rc;
+    if (int rc = lm_gemm(g, head_split ? np : 0, a->head1_ws, s)) return rc;
     for (int k = 0; k < K; ++k) {
       memset(&g, 0, sizeof(g));
       g.A = a->head_h + (size_t)k * Hh; g.W = w->head2_w + (size_t)k * card * Hh; g.bias = w->head2_b + (size_t)k * card; g.C = a->logits;
       g.M = mc; g.N = card; g.K = Hh; g.lda = K * Hh; g.ldc = ldc;
-      if (head_split) g.W_split = a->head2_ws + (size_t)k * 3 * card * Hh;
-      if (int rc = ssrhip_gemm(&g, s)) return rc;
+      if (int rc = lm_gemm(g, head_split ? np : 0, head_split ? a->head2_ws + (size_t)k * np * card * Hh : nullptr, s)) return rc;
       const size_t o = (size_t)k * a->M + m0;
       if (int rc = ssrhip_xent_rank(a->logits, ldc, card, a->target + o, mc, a->nll + o, a->rank + o, stream)) return rc;
     }
   }
   return 0;
+}
+
+extern "C" int ssrhip_lm_score(const ssrhip_lm_dims* d, const ssrhip_lm_weights* w, const ssrhip_score_args* a, ssrhip_stream_t stream) {
+  return lm_score(d, w, a, 3, stream);
+}
+extern "C" int ssrhip_lm_score_w1(const ssrhip_lm_dims* d, const ssrhip_lm_weights* w, const ssrhip_score_args* a, ssrhip_stream_t stream) {
+  return lm_score(d, w, a, 1, stream);
 }
 
 extern "C" int ssrhip_lm_embed_pending(ssrhip_lm* lm, ssrhip_stream_t stream) {

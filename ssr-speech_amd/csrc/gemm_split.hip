@@ -27,6 +27,7 @@
 // LSTM input GEMM 117 -> 168, the codec's batched strided views 91..107 -> 99..141 (the ELU-on-load layers gain least: the
 // staging VALU work, not the matrix pipe, is what they wait for).
 #include <stdlib.h>
+#include <atomic>
 #include "common.h"
 
 namespace {
@@ -76,12 +77,24 @@ constexpr int BN = 128, BK = 32, PITCH = 40;                                // p
 // BM = 128: 2 x 2 waves of 64 x 64 (2 x 2 accumulators); BM = 64: 1 x 4 waves of 64 x 32 (2 x 1) for grids that 128-row tiles would not
 // fill. Per output element both do the same arithmetic (k blocks of 16 in order, the six products in the same order), so a result does
 // not depend on which tile shape — i.e. on which batch size — computed it.
-template <int BM, bool ELU>
-__global__ __launch_bounds__(256, 2) void gemm_split_kernel(const ssrhip_gemm_args a0) {
+//
+// NP = planes of W (DESIGN I.13): 3 = the exact split of an fp32 weight, six products per k block; 1 = a weight that IS a bf16 value (a bf16
+// arena's masters): planes 1 and 2 of its split are zeros, so the three products with them (a0w2, a1w1, a0w1) add sixteen +-0 each to an
+// accumulator that starts at +0 and cannot become -0 under round-to-nearest — they leave it unchanged. The one-plane form leaves them
+// (and the two planes) out and keeps a2w0, a1w0, a0w0 in that order, the k blocks in order, the same tiles and epilogues: the same bits as
+// the three-plane form on the same weights, for FINITE activations (inf x 0 = NaN exists in the six-product form only).
+constexpr int PA3[6] = {2, 0, 1, 1, 0, 0}, PB3[6] = {0, 2, 1, 0, 1, 0};    // a2w0, a0w2, a1w1, a1w0, a0w1, a0w0
+constexpr int PA1[3] = {2, 1, 0};                                           // a2w0, a1w0, a0w0
+template <int NP> constexpr int n_prod() { static_assert(NP == 1 || NP == 3, "W comes as one or three planes"); return NP == 3 ? 6 : 3; }
+template <int NP> constexpr int prod_a(int pq) { return NP == 3 ? PA3[pq] : PA1[pq]; }
+template <int NP> constexpr int prod_b(int pq) { return NP == 3 ? PB3[pq] : 0; }
+
+template <int BM, bool ELU, int NP>
+__device__ __forceinline__ void gemm_split_body(const ssrhip_gemm_args& a0) {
   constexpr int MT = 2, NT = BM == 128 ? 2 : 1;
   constexpr int LA = BM / 32;
   __shared__ __attribute__((aligned(16))) short As[3][BM * PITCH];
-  __shared__ __attribute__((aligned(16))) short Ws[3][BN * PITCH];
+  __shared__ __attribute__((aligned(16))) short Ws[NP][BN * PITCH];
   ssrhip_gemm_args a = a0;
   {   // batched problems: grid.z
     const size_t z = blockIdx.z;
@@ -109,7 +122,7 @@ __global__ __launch_bounds__(256, 2) void gemm_split_kernel(const ssrhip_gemm_ar
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
   float4 ra[LA];
-  bf16x8 rwp[3][2];
+  bf16x8 rwp[NP][2];
   auto gload = [&](int k0) {
     const bool kin = (k0 + lc) < K;
 #pragma unroll
@@ -120,7 +133,7 @@ __global__ __launch_bounds__(256, 2) void gemm_split_kernel(const ssrhip_gemm_ar
     }
     const bool kinw = (k0 + cw) < K;                                        // K % 8 == 0 (checked by the host)
 #pragma unroll
-    for (int q = 0; q < 3; ++q)
+    for (int q = 0; q < NP; ++q)
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         const int n = n0 + lw + 64 * i;
@@ -137,28 +150,30 @@ __global__ __launch_bounds__(256, 2) void gemm_split_kernel(const ssrhip_gemm_ar
       for (int q = 0; q < 3; ++q) *reinterpret_cast<bf16x4*>(&As[q][(lr + 32 * i) * PITCH + lc]) = p[q];
     }
 #pragma unroll
-    for (int q = 0; q < 3; ++q)
+    for (int q = 0; q < NP; ++q)
 #pragma unroll
       for (int i = 0; i < 2; ++i) *reinterpret_cast<bf16x8*>(&Ws[q][(lw + 64 * i) * PITCH + cw]) = rwp[q][i];
   };
   auto mma_tile = [&]() {
 #pragma unroll
     for (int kk = 0; kk < BK; kk += 16) {
-      bf16x8 fa[3][MT], fb[3][NT];
+      bf16x8 fa[3][MT], fb[NP][NT];
 #pragma unroll
       for (int q = 0; q < 3; ++q) {
 #pragma unroll
         for (int i = 0; i < MT; ++i) fa[q][i] = *reinterpret_cast<const bf16x8*>(&As[q][((wm * MT + i) * 32 + li) * PITCH + kk + lh * 8]);
+        if (q < NP) {
 #pragma unroll
-        for (int j = 0; j < NT; ++j) fb[q][j] = *reinterpret_cast<const bf16x8*>(&Ws[q][((wn * NT + j) * 32 + li) * PITCH + kk + lh * 8]);
+          for (int j = 0; j < NT; ++j) fb[q][j] = *reinterpret_cast<const bf16x8*>(&Ws[q][((wn * NT + j) * 32 + li) * PITCH + kk + lh * 8]);
+        }
       }
-      constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};  // a2w0, a0w2, a1w1, a1w0, a0w1, a0w0
 #pragma unroll
-      for (int pq = 0; pq < 6; ++pq)
+      for (int pq = 0; pq < n_prod<NP>(); ++pq)
 #pragma unroll
         for (int i = 0; i < MT; ++i)
 #pragma unroll
-          for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[PA[pq]][i], fb[PB[pq]][j], acc[i][j], 0, 0, 0);
+          for (int j = 0; j < NT; ++j)
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[prod_a<NP>(pq)][i], fb[prod_b<NP>(pq)][j], acc[i][j], 0, 0, 0);
     }
   };
   gload(0);
@@ -198,6 +213,16 @@ __global__ __launch_bounds__(256, 2) void gemm_split_kernel(const ssrhip_gemm_ar
   }
 }
 
+template <int BM, bool ELU>
+__global__ __launch_bounds__(256, 2) void gemm_split_kernel(const ssrhip_gemm_args a0) { gemm_split_body<BM, ELU, 3>(a0); }
+// one W plane (ssrhip_gemm_w1): what the LM's bf16 arenas use — no ELU on load. `__launch_bounds__(256, 4)` where the three-plane twin has
+// (256, 2): the attribute FORCES the tile into 128 VGPRs (tests/test_w1_isa.py holds every one-plane kernel to that); under (256, 2) hipcc
+// takes 156 at BM = 128, so the figure is not won by the code. No scratch either way. At <= 128 VGPRs and 40 KB of LDS more than two
+// workgroups may share a CU. This is the SSRHIP_GEMM_SPLIT_DMA=0 fallback; measured as shipped against the twin (0.50-0.71x its time,
+// profiles/prefill_w1_ab.md), not against a (256, 2) build of itself.
+template <int BM>
+__global__ __launch_bounds__(256, 4) void gemm_w1_kernel(const ssrhip_gemm_args a0) { gemm_split_body<BM, false, 1>(a0); }
+
 // ---- the 128-row tile, second generation (round 3, after the counters in profiles/r03_split_gemm_pmc.md): same tile, same arithmetic
 // per output element (bit-identical results), restructured for latency hiding:
 //   * 8 waves per workgroup (2 x 4, wave tile 64 x 32 = 2 x 1 accumulators), <= 128 VGPRs: two workgroups per CU = FOUR waves per SIMD
@@ -217,7 +242,10 @@ __global__ __launch_bounds__(256, 2) void gemm_split_kernel(const ssrhip_gemm_ar
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 constexpr int DMA_PLANE = 128 * 64;                                   // bytes: one bf16 plane of a 128 x 32 tile
-constexpr int dma_lds(int bm) { return 3 * bm * 64 + 6 * DMA_PLANE; }  // A 3 planes of BM rows + W 2 stages x 3 planes
+// A 3 planes of BM rows + W 2 stages x `np` planes; never less than the 8 x 4 KB the 16-byte epilogue turns its blocks through (the one-plane
+// 64-row tile's stages are smaller than that: 28,672 B)
+constexpr int dma_lds(int bm, int np = 3) { return 3 * bm * 64 + 2 * np * DMA_PLANE > 8 * 4096 ? 3 * bm * 64 + 2 * np * DMA_PLANE : 8 * 4096; }
+static_assert(dma_lds(128) == 73728 && dma_lds(64) == 61440 && dma_lds(128, 1) == 40960 && dma_lds(64, 1) == 32768, "LDS of the DMA kernels");
 
 // BM = 128: waves 2 x 4 of 64 x 32; BM = 64 (grids that 128-row tiles would not fill, half-empty tiles): waves 2 x 4 of 32 x 32. Same
 // arithmetic per output element in both (and in the 4-wave kernels above).
@@ -265,16 +293,16 @@ __device__ __forceinline__ void xcd_tile(const int flags, int& bx, int& by, int&
   bz = (int)(t2 / ny);
 }
 
-template <int BM, bool ELU, int KO = 0, bool TMF = false>
-__global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(4, 4))) void gemm_split_dma_kernel(const ssrhip_gemm_args a0, const int flags) {
+template <int BM, bool ELU, int KO, bool TMF, int NP>
+__device__ __forceinline__ void gemm_split_dma_body(const ssrhip_gemm_args a0, const int flags) {
   const int wide = flags & 1;
   int bx, by, bz;
   xcd_tile(flags, bx, by, bz);
   constexpr int MT = BM / 64, LA = BM / 64, APL = BM * 64;           // accumulators per wave, A loader passes, bytes per A plane
   extern __shared__ __attribute__((aligned(1024))) char ldsb[];
   char* const As = ldsb;                                             // [3][BM][64 B]
-  char* const Wsb = ldsb + 3 * APL;                                  // [2][3][128][64 B]
-  unsigned* const stamps = reinterpret_cast<unsigned*>(ldsb + dma_lds(BM));   // GD_PROF only (the lab adds the bytes)
+  char* const Wsb = ldsb + 3 * APL;                                  // [2][NP][128][64 B]
+  unsigned* const stamps = reinterpret_cast<unsigned*>(ldsb + dma_lds(BM, NP));   // GD_PROF only (the lab adds the bytes)
   auto stamp = [&](int i) {
     if constexpr ((KO & GD_PROF) != 0) {
       if (threadIdx.x == 0 && i < GD_NSTAMP) stamps[i] = (unsigned)wall_clock64();
@@ -323,9 +351,9 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(4, 4))) 
   const int rows_a = min(BM, M - m0), rows_w = min(128, N - n0);
   const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.A + (size_t)m0 * a.lda), 0,
                                                                         (int)(((size_t)(rows_a - 1) * a.lda + K) * 4), 0x00020000);
-  __amdgpu_buffer_rsrc_t rsW[3];
+  __amdgpu_buffer_rsrc_t rsW[NP];
 #pragma unroll
-  for (int q = 0; q < 3; ++q)
+  for (int q = 0; q < NP; ++q)
     rsW[q] = __builtin_amdgcn_make_buffer_rsrc(const_cast<short*>(Wp + (size_t)q * plane + (size_t)n0 * K), 0, (int)((size_t)rows_w * K * 2), 0x00020000);
   unsigned offA[LA];
 #pragma unroll
@@ -348,8 +376,8 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(4, 4))) 
     const bool kin = (k0 + wchunk * 8) < K;                          // K % 8 == 0 (checked by the host)
     const unsigned off = kin ? offW + (unsigned)k0 * 2 : OOB;
 #pragma unroll
-    for (int q = 0; q < 3; ++q)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW[q], (lds_ptr_t)(Wsb + (stage * 3 + q) * DMA_PLANE + wave * 1024), 16, off, 0, 0, 0);
+    for (int q = 0; q < NP; ++q)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW[q], (lds_ptr_t)(Wsb + (stage * NP + q) * DMA_PLANE + wave * 1024), 16, off, 0, 0, 0);
   };
   const int aswz = (((lc >> 3) ^ ((lr >> 2) & 3)) << 4) + ((lc >> 2) & 1) * 8;   // rows lr and lr + 64 share (row >> 2) & 3
   auto store_a = [&]() {
@@ -366,23 +394,22 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(4, 4))) 
   };
   const int fsw = (li >> 2) & 3;
   auto mma_tile = [&](int stage) {
-    constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};  // a2w0, a0w2, a1w1, a1w0, a0w1, a0w0
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int kk = 0; kk < BK; kk += 16) {
       const int coff = (((kk >> 3) + lh) ^ fsw) << 4;
-      bf16x8 fa[3][MT], fb[3];
+      bf16x8 fa[3][MT], fb[NP];
 #pragma unroll
       for (int q = 0; q < 3; ++q) {
 #pragma unroll
         for (int i = 0; i < MT; ++i) fa[q][i] = *reinterpret_cast<const bf16x8*>(As + q * APL + ((wm * MT + i) * 32 + li) * 64 + coff);
-        fb[q] = *reinterpret_cast<const bf16x8*>(Wsb + (stage * 3 + q) * DMA_PLANE + (wn * 32 + li) * 64 + coff);
+        if (q < NP) fb[q] = *reinterpret_cast<const bf16x8*>(Wsb + (stage * NP + q) * DMA_PLANE + (wn * 32 + li) * 64 + coff);
       }
 #pragma unroll
-      for (int pq = 0; pq < 6; ++pq)
+      for (int pq = 0; pq < n_prod<NP>(); ++pq)
 #pragma unroll
         for (int i = 0; i < MT; ++i)
-          if constexpr ((KO & GD_KO_MFMA) == 0) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[PA[pq]][i], fb[PB[pq]], acc[i], 0, 0, 0);
+          if constexpr ((KO & GD_KO_MFMA) == 0) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[prod_a<NP>(pq)][i], fb[prod_b<NP>(pq)], acc[i], 0, 0, 0);
     }
     __builtin_amdgcn_s_setprio(0);
   };
@@ -545,6 +572,16 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(4, 4))) 
   }
 }
 
+template <int BM, bool ELU, int KO = 0, bool TMF = false>
+__global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(4, 4))) void gemm_split_dma_kernel(const ssrhip_gemm_args a0, const int flags) {
+  gemm_split_dma_body<BM, ELU, KO, TMF, 3>(a0, flags);
+}
+// one W plane (ssrhip_gemm_w1): no ELU on load, no time-mask epilogue (a time-masked call takes the general loop); same workgroups per CU
+template <int BM>
+__global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(4, 4))) void gemm_w1_dma_kernel(const ssrhip_gemm_args a0, const int flags) {
+  gemm_split_dma_body<BM, false, 0, false, 1>(a0, flags);
+}
+
 }  // namespace
 
 // true when the split kernel applies to this call (decided by ssrhip_gemm). It depends on the matrix (N, K) and on what the caller
@@ -565,8 +602,10 @@ namespace {
 enum gemm_split_form { GS_DMA128, GS_DMA64, GS_DMA128_TM, GS_4WAVE128, GS_4WAVE64 };
 struct gemm_split_plan { gemm_split_form form; dim3 grid, block; int lds, flags; };      // `flags`: the DMA kernels' flag word
 
-// `xcd` is SSRHIP_GEMM_XCD as of this call (read at every launch: tests flip it inside one process)
-gemm_split_plan plan_gemm_split(const ssrhip_gemm_args* a, const codec_knobs& k, const char* xcd) {
+// `xcd` is SSRHIP_GEMM_XCD as of this call (read at every launch: tests flip it inside one process). `np`: planes of W (3, or 1 for
+// ssrhip_gemm_w1). The form does not depend on it — a one-plane call takes the tile shape its three-plane twin takes — except that the
+// one-plane kernels have no time-mask epilogue.
+gemm_split_plan plan_gemm_split(const ssrhip_gemm_args* a, const codec_knobs& k, const char* xcd, const int np = 3) {
   const unsigned nb = a->batch > 1 ? a->batch : 1;
   const long tiles128 = (long)((a->N + BN - 1) / BN) * ((a->M + 127) / 128) * nb;
   // 128-row tiles when there are enough of them for two workgroups on most CUs — unless they would be half empty: the LSTM's second
@@ -578,14 +617,14 @@ gemm_split_plan plan_gemm_split(const ssrhip_gemm_args* a, const codec_knobs& k,
   // the DMA kernels address a tile through 32-bit buffer offsets: 128 rows of A (and of a W plane) have to stay below 2 GiB
   const bool dma = k.gemm_split_dma && ((size_t)127 * a->lda + a->K) * 4 < 0x7FFFFFF0ull && (size_t)128 * a->K * 2 < 0x7FFFFFF0ull;
   // the transposed convolutions' time mask as a row predicate of the 16-byte epilogue (SSRHIP_EPILOGUE_TM=0: the general per-element loop)
-  const bool tmf = k.epilogue_tm && k.gemm_wide && a->tm_c > 0 && a->N % a->tm_c == 0 && a->tm_c % 4 == 0 && !a->R && !a->residual && !a->rbias &&
+  const bool tmf = np == 3 && k.epilogue_tm && k.gemm_wide && a->tm_c > 0 && a->N % a->tm_c == 0 && a->tm_c % 4 == 0 && !a->R && !a->residual && !a->rbias &&
                    a->ldc % 4 == 0 && a->strideC % 4 == 0 && ((uintptr_t)a->C & 15) == 0 && (long)a->M * (a->N / a->tm_c) < 0x7FFFFFFFL;
   const dim3 grid((a->N + BN - 1) / BN, (a->M + bm - 1) / bm, nb);
   if (!dma) return {bm == 128 ? GS_4WAVE128 : GS_4WAVE64, grid, dim3(256), 0, 0};
-  gemm_split_plan p{bm == 64 ? GS_DMA64 : tmf ? GS_DMA128_TM : GS_DMA128, grid, dim3(512), dma_lds(bm), 0};
+  gemm_split_plan p{bm == 64 ? GS_DMA64 : tmf ? GS_DMA128_TM : GS_DMA128, grid, dim3(512), dma_lds(bm, np), 0};
   // flag word: bit 0 the 16-byte epilogue, bit 1 the XCD-aware tile order ("0...": plain order), bits 8.. its N-tile group width: W tiles
-  // of one group (3 bf16 planes of 128 rows x K) within ~2.5 MB of an XCD's 4 MB L2; "d:<GN>" (d in 1..9) forces the width (lab)
-  const long wtile = 128L * a->K * 6;
+  // of one group (`np` bf16 planes of 128 rows x K) within ~2.5 MB of an XCD's 4 MB L2; "d:<GN>" (d in 1..9) forces the width (lab)
+  const long wtile = 128L * a->K * 2 * np;
   long gn = wtile > 0 ? (2560L * 1024) / wtile : 1;
   if (gn < 1) gn = 1;
   if (gn > 255) gn = 255;
@@ -625,6 +664,37 @@ int ssrhip_gemm_split_launch(const ssrhip_gemm_args* a, hipStream_t s) {
   }
   if (rc) return rc;
   SSR_LAUNCH_CHECK();
+  return 0;
+}
+
+static std::atomic<int64_t> g_w1_launches{0};      // one-plane launches of this process (ssrhip_gemm_w1_launches)
+extern "C" int64_t ssrhip_gemm_w1_launches(void) { return g_w1_launches.load(); }
+
+// One plane of W: see ssrhip.h. Answers like ssrhip_gemv_wt16: 0 launched, 1 does not qualify (nothing launched), < 0 contract error.
+extern "C" int ssrhip_gemm_w1(const ssrhip_gemm_args* a, ssrhip_stream_t stream) {
+  SSR_REQUIRE(a && a->A && a->C, "ssrhip_gemm_w1: null argument");
+  SSR_REQUIRE(a->W_split, "ssrhip_gemm_w1: W_split is NULL (it is the one bf16 plane [N][K] this entry multiplies by)");
+  SSR_REQUIRE(a->M > 0 && a->N > 0 && a->K > 0 && a->K % 4 == 0 && a->lda % 4 == 0, "ssrhip_gemm_w1: K and lda must be multiples of 4");
+  SSR_REQUIRE(!a->rbias || (a->rclass && a->rrep > 0), "ssrhip_gemm_w1: rbias needs rclass and rrep > 0");
+  if (!ssrhip_gemm_split_eligible(a) || a->act_in == SSRHIP_ACT_ELU) return 1;
+  hipStream_t s = (hipStream_t)stream;
+  const gemm_split_plan p = plan_gemm_split(a, ssr_codec_knobs(), getenv("SSRHIP_GEMM_XCD"), 1);
+  ssr_gemm_log(a, p.grid.x, p.grid.y, p.grid.z, 2);
+  switch (p.form) {
+    case GS_DMA128_TM:      // (not planned for one plane)
+    case GS_DMA128:
+      SSR_RAISE_LDS(p.lds, gemm_w1_dma_kernel<128>);
+      hipLaunchKernelGGL((gemm_w1_dma_kernel<128>), p.grid, p.block, p.lds, s, *a, p.flags);
+      break;
+    case GS_DMA64:
+      SSR_RAISE_LDS(p.lds, gemm_w1_dma_kernel<64>);
+      hipLaunchKernelGGL((gemm_w1_dma_kernel<64>), p.grid, p.block, p.lds, s, *a, p.flags);
+      break;
+    case GS_4WAVE128: hipLaunchKernelGGL((gemm_w1_kernel<128>), p.grid, p.block, 0, s, *a); break;
+    case GS_4WAVE64: hipLaunchKernelGGL((gemm_w1_kernel<64>), p.grid, p.block, 0, s, *a); break;
+  }
+  SSR_LAUNCH_CHECK();
+  ++g_w1_launches;
   return 0;
 }
 

@@ -104,6 +104,10 @@ WT16_DEFAULT = "0"
 # The same switch for a 17..32-row engine of a bf16 arena (DecodeEngine stream_wt32=None): "1" = the two-panel step streams the same
 # SSRHIP_WT16_INDEX copies. Decided by the measurement in DESIGN.md Part I.12.
 WT32_DEFAULT = "0"
+# What an unset SSRHIP_PREFILL_W1 means for a bf16 arena: "1" = the prefill / score GEMMs get ONE bf16 plane per matrix (the weight itself,
+# csrc/gemm_split.hip ssrhip_gemm_w1), "0" = the three planes of the exact split (two of them zeros). Decided by the measurement in
+# DESIGN.md Part I.13 (one plane: prefill 10.65 -> 6.69 ms at 598 rows, 42.5 -> 29.5 ms at 4,784 rows, same bits).
+PREFILL_W1_DEFAULT = "1"
 
 
 def w16_streamable(K: int) -> bool:
@@ -149,6 +153,23 @@ def resolve_w16_stream(st: W16Stream, rows: int, weight_dtype: str, requested: O
     if weight_dtype != "bf16":
         raise ValueError(f"stream_{st.name} needs an arena built with weight_dtype='bf16'")
     return True
+
+
+def resolve_prefill_planes(weight_dtype: str, requested: Optional[int], env) -> int:
+    """How many bf16 planes per matrix does an arena of `weight_dtype` build for the prefill / score GEMMs? 0 = none (`env` has
+    SSRHIP_PREFILL_SPLIT starting with '0': the fp32 chain, whatever else is asked), 3 = the exact split of an fp32 value, 1 = the value
+    itself, which only a bf16 arena's masters are. requested None: 1 iff the arena is bf16 and `env["SSRHIP_PREFILL_W1"]` (unset:
+    PREFILL_W1_DEFAULT) does not start with '0'. requested 1 on an fp32 arena: ValueError. `env` is a mapping like os.environ; nothing else
+    is read."""
+    if requested not in (None, 1, 3):
+        raise ValueError(f"split planes come as 1 or 3 per matrix, not {requested!r}")
+    if requested == 1 and weight_dtype != "bf16":
+        raise ValueError("one plane per matrix needs an arena built with weight_dtype='bf16' (an fp32 weight is the sum of three bf16 planes)")
+    if env.get("SSRHIP_PREFILL_SPLIT", "1")[:1] == "0":      # the C side's rule (engine.hip): a value that starts with '0'
+        return 0
+    if requested is not None:
+        return requested
+    return 1 if weight_dtype == "bf16" and env.get("SSRHIP_PREFILL_W1", PREFILL_W1_DEFAULT)[:1] != "0" else 3
 
 
 class LMWeightsArena:
@@ -217,6 +238,11 @@ class LMWeightsArena:
                 for name in W16_FAMILIES:
                     lay[name + "_w"] = rnd(lay[name + "_w"])
             self.head1_w, self.head2_w = rnd(self.head1_w), rnd(self.head2_w)
+        # planes per matrix in every `*_ws` buffer of this arena (3 or 1). It travels WITH the buffers: engines and `score` take it from
+        # here when they hand the buffers to the library, never from the environment — a one-plane buffer read as three runs 2x its
+        # size past its end. Decided once, by whichever of ensure_split_planes / ensure_head_split_planes runs first.
+        self.split_planes = 3
+        self._planes_decided = False
 
     def _ensure_packed(self, order: str) -> bool:
         if self.weight_dtype != "bf16":
@@ -279,41 +305,65 @@ class LMWeightsArena:
         self.generation += 1
         return True
 
-    def ensure_split_planes(self) -> bool:
-        """The four matrices of every layer as three bf16 planes each ([3][N][K], `ssrhip_split_weights`) for the PREFILL GEMMs: fp32
-        operands split exactly, six cross products on the bf16 matrix cores (csrc/gemm_split.hip; +6 bytes per weight = +4.8 GB at 830M,
-        built once on first use). `SSRHIP_PREFILL_SPLIT=0` keeps the prefill on the fp32 FMA chain. Returns True when created now."""
-        if getattr(self, "_ws_ready", False) or os.environ.get("SSRHIP_PREFILL_SPLIT", "1")[:1] == "0":      # the C side's rule (engine.hip): a value that starts with '0' 
+    def _decide_planes(self, planes: Optional[int]) -> int:
+        """The plane count of this arena's `*_ws` buffers: resolved once (SSRHIP_PREFILL_SPLIT / SSRHIP_PREFILL_W1 are read HERE and nowhere
+        else), then fixed. 0 = none are built (now); a later call may still build them."""
+        if self._planes_decided:
+            if planes is not None and planes != self.split_planes:
+                raise ValueError(f"this arena's split planes already come {self.split_planes} per matrix; {planes} asked for")
+            resolve_prefill_planes(self.weight_dtype, planes, {})              # the argument's own checks
+            return 0 if os.environ.get("SSRHIP_PREFILL_SPLIT", "1")[:1] == "0" else self.split_planes
+        n = resolve_prefill_planes(self.weight_dtype, planes, os.environ)
+        if n:
+            self.split_planes, self._planes_decided = n, True
+        return n
+
+    def _planes_of(self, Wm: torch.Tensor) -> torch.Tensor:
+        """int16 [split_planes * numel]: the three planes of the exact split (`ssrhip_split_weights`), or the one plane a bf16-valued
+        master is — `to(bfloat16)` is exact there, no kernel needed."""
+        if self.split_planes == 1:
+            return Wm.to(torch.bfloat16).contiguous().view(torch.int16).reshape(-1)
+        planes = torch.empty(3 * Wm.numel(), dtype=torch.int16, device=Wm.device)
+        _lib.check(_lib.lib().ssrhip_split_weights(Wm.data_ptr(), planes.data_ptr(), Wm.numel(), _lib.stream_ptr()), "ssrhip_split_weights")
+        return planes
+
+    def ensure_split_planes(self, planes: Optional[int] = None) -> bool:
+        """The four matrices of every layer as bf16 planes ([3][N][K], `ssrhip_split_weights`) for the PREFILL GEMMs: fp32 operands split
+        exactly, six cross products on the bf16 matrix cores (csrc/gemm_split.hip; +6 bytes per weight = +4.8 GB at 830M, built once on
+        first use). A bf16 arena with `SSRHIP_PREFILL_W1` on (unset: PREFILL_W1_DEFAULT; `planes=1` asks explicitly, `planes=3` for the
+        split) builds ONE plane [N][K] instead — the weight itself, +2 bytes per weight, three products (ssrhip_gemm_w1), the same
+        results bit for bit; `split_planes` says which. `planes=1` on an fp32 arena raises ValueError. `SSRHIP_PREFILL_SPLIT=0` keeps the
+        prefill on the fp32 FMA chain: no planes at all. Returns True when created now."""
+        if not self._decide_planes(planes) or getattr(self, "_ws_ready", False):
             return False
-        lib = _lib.lib()
         for lay in self.layers:
             for name in ("in_proj", "out_proj", "ffn1", "ffn2"):
-                Wm = lay[name + "_w"]
-                planes = torch.empty(3 * Wm.numel(), dtype=torch.int16, device=Wm.device)
-                _lib.check(lib.ssrhip_split_weights(Wm.data_ptr(), planes.data_ptr(), Wm.numel(), _lib.stream_ptr()), "ssrhip_split_weights")
-                lay[name + "_ws"] = planes
+                lay[name + "_ws"] = self._planes_of(lay[name + "_w"])
         self._ws_ready = True
         self.generation += 1
         return True
 
-    def ensure_head_split_planes(self) -> bool:
-        """The two head matrices as three bf16 planes each for the many-row head GEMMs of `ssrhip_lm_score` (ssrhip_score_args.head1_ws /
-        head2_ws): head1_w [K*Hh][D] as one [3][K*Hh][D], each codebook's head2_w[k] separately, [K][3][card][Hh] (+6 bytes per head
-        weight = +~100 MB at 830M). Not built under `SSRHIP_PREFILL_SPLIT=0`. Returns True when created now. The decode step never reads
+    def ensure_head_split_planes(self, planes: Optional[int] = None) -> bool:
+        """The two head matrices as `split_planes` bf16 planes each for the many-row head GEMMs of `ssrhip_lm_score` / `_score_w1`
+        (ssrhip_score_args.head1_ws / head2_ws): head1_w [K*Hh][D] as one [planes][K*Hh][D], each codebook's head2_w[k] separately,
+        [K][planes][card][Hh] (three planes: +6 bytes per head weight = +~100 MB at 830M). Same plane count as the layer planes (see
+        `ensure_split_planes`); not built under `SSRHIP_PREFILL_SPLIT=0`. Returns True when created now. The decode step never reads
         them, so the engines' pointers do not change."""
-        if getattr(self, "_hs_ready", False) or os.environ.get("SSRHIP_PREFILL_SPLIT", "1")[:1] == "0":
+        if not self._decide_planes(planes) or getattr(self, "_hs_ready", False):
             return False
-        lib = _lib.lib()
-
-        def split(Wm):
-            planes = torch.empty(3 * Wm.numel(), dtype=torch.int16, device=Wm.device)
-            _lib.check(lib.ssrhip_split_weights(Wm.data_ptr(), planes.data_ptr(), Wm.numel(), _lib.stream_ptr()), "ssrhip_split_weights")
-            return planes
-
-        self.head1_ws = split(self.head1_w)
-        self.head2_ws = torch.cat([split(self.head2_w[k]) for k in range(self.K)])
+        self.head1_ws = self._planes_of(self.head1_w)
+        self.head2_ws = torch.cat([self._planes_of(self.head2_w[k]) for k in range(self.K)])
         self._hs_ready = True
         return True
+
+    def split_plane_bytes(self) -> int:
+        """Bytes this arena holds in split planes (layer and head buffers built so far)."""
+        n = 0
+        if getattr(self, "_ws_ready", False):
+            n += sum(lay[name + "_ws"].numel() for lay in self.layers for name in ("in_proj", "out_proj", "ffn1", "ffn2"))
+        if getattr(self, "_hs_ready", False):
+            n += self.head1_ws.numel() + self.head2_ws.numel()
+        return 2 * n
 
     def ensure_positions(self, n: int) -> bool:
         """Grow the sinusoidal table so that positions [0, n) exist, like `SinePositionalEmbedding.extend_pe` does on demand
@@ -621,7 +671,7 @@ class DecodeEngine:
         self._prefill_ws = None
         self._arena_gen = arena.generation
         self.dbg_logits = torch.zeros(n_utt, K, arena.card, **f32) if debug_logits else None
-        self._w = arena.c_struct()
+        self._take_weights()
         self._ctx = None
         self.pair_mode = int(pair_mode)
         self.pairing = False                      # set by _create_ctx: does this engine's step run the pair launches?
@@ -630,6 +680,11 @@ class DecodeEngine:
     # ------------------------------------------------------------------ C structs
     def kv_struct(self):
         return _lib.KV(self.kv_pool.data_ptr(), self.page_table.data_ptr(), self.max_pages, self.a.L, self.a.H, self.hd)
+
+    def _take_weights(self):
+        """The arena's weights record, and WITH it how many planes its `*_ws` buffers hold (0 = the record has none)."""
+        self._w = self.a.c_struct()
+        self.prefill_planes = self.a.split_planes if getattr(self.a, "_ws_ready", False) else 0
 
     def _create_ctx(self):
         if self._ctx is not None:
@@ -653,6 +708,8 @@ class DecodeEngine:
         if self._stream is not None:              # before the first step is enqueued or captured; stream_w16 gives the pairing slot back
             rec, setter = self.a._packed_struct(self._stream.order), "ssrhip_lm_set_" + self._stream.name
             _lib.check(getattr(self.lib, setter)(ctx, C.byref(rec)), setter)
+        if self.prefill_planes == 1:              # the count travels with the arena's buffers (also for the two-phase admission's prefill)
+            _lib.check(self.lib.ssrhip_lm_set_prefill_w1(ctx, 1), "ssrhip_lm_set_prefill_w1")
         why = C.create_string_buffer(256)
         self.pairing = bool(self.lib.ssrhip_lm_pairing(ctx, why, 256))
         self.pairing_why = why.value.decode(errors="replace")
@@ -809,6 +866,12 @@ class DecodeEngine:
     def _prefill_ws_rows(self) -> int:
         return 0 if self._prefill_ws is None else self._prefill_ws["x"].shape[0]
 
+    def _launch_prefill(self, p) -> None:
+        """`ssrhip_lm_prefill` of the argument block `p` on the current stream: the ONE place a prefill is enqueued from (blocking start /
+        admission, and the two-phase admission inside its side-stream context). A measuring tool may wrap this method on an engine instance
+        to put device events around the prefill (tools/prefill_time.py)."""
+        _lib.check(self.lib.ssrhip_lm_prefill(self._ctx, C.byref(p), _lib.stream_ptr()), "ssrhip_lm_prefill")
+
     def _prefill_args(self, pk, views):
         """The prefill workspaces (kept across admissions, grown when a larger prompt arrives) and the argument block of ONE
         `ssrhip_lm_prefill` over the packed rows, whose integer arrays are the first seven staged views. Returns (args, workspaces): the
@@ -860,7 +923,7 @@ class DecodeEngine:
         self._admit_sent.record(torch.cuda.current_stream(dev))
         self._write_slot_records(slots, *self._slot_records(slots, knobs, audio_cols, use_noise))
         if self._arena_gen != a.generation:      # the arena re-allocated a table (position table grown): refresh the pointers
-            self._w = a.c_struct()
+            self._take_weights()
             self._arena_gen = a.generation
             self.close()
         if self._ctx is None:
@@ -869,7 +932,7 @@ class DecodeEngine:
         p, ws = self._prefill_args(pk, views)
         # (the prefill ends by embedding the pending input token of EVERY row into x: for rows in mid-decode that re-writes the
         # very values the sampler's fused embedding left there — same function, same inputs)
-        _lib.check(self.lib.ssrhip_lm_prefill(self._ctx, C.byref(p), _lib.stream_ptr()), "ssrhip_lm_prefill")
+        self._launch_prefill(p)
         self._keep = (ws, idx)                   # alive until the stream has consumed them (the integer arrays live in the engine's workspace)
         return int(pk["tok"].shape[0])
 
@@ -911,7 +974,7 @@ class DecodeEngine:
         # on the SIDE stream, against the warm table, without the closing embedding (x is live decode state)
         p.table, p.no_embed = self.page_table_warm.data_ptr(), 1
         with torch.cuda.stream(side):
-            _lib.check(self.lib.ssrhip_lm_prefill(self._ctx, C.byref(p), _lib.stream_ptr()), "ssrhip_lm_prefill")
+            self._launch_prefill(p)
             done = torch.cuda.Event()
             done.record(side)
         return dict(slots=list(slots), rows_b=rows_b, prefill_done=done, cfgs=cfgs, sts=sts, arm=views[7:], ws=ws)

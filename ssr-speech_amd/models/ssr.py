@@ -273,7 +273,9 @@ class SSR_Speech(nn.Module):
             sa.head_h, sa.logits, sa.head_chunk = ws["head_h"].data_ptr(), ws["logits"].data_ptr(), hc
             if getattr(a, "_hs_ready", False):
                 sa.head1_ws, sa.head2_ws = a.head1_ws.data_ptr(), a.head2_ws.data_ptr()
-            _lib.check(lib.ssrhip_lm_score(C.byref(dims), C.byref(w), C.byref(sa), _lib.stream_ptr()), "ssrhip_lm_score")
+            # the plane count of the arena's buffers picks the entry: a one-plane buffer must never reach the three-plane one
+            entry = "ssrhip_lm_score_w1" if a.split_planes == 1 else "ssrhip_lm_score"
+            _lib.check(getattr(lib, entry)(C.byref(dims), C.byref(w), C.byref(sa), _lib.stream_ptr()), entry)
             nlls.append(nll)
             ranks.append(rank)
             tgts.append(view(7).view(K, M))

@@ -15,7 +15,7 @@ def short(name):
     return "torch:" + name.split("<")[0].split("(")[0][-40:]
 
 
-GEMM_KERNELS = ("gemm_split_dma_kernel", "gemm_split_kernel", "gemm_kernel")
+GEMM_KERNELS = ("gemm_split_dma_kernel", "gemm_split_kernel", "gemm_w1_dma_kernel", "gemm_w1_kernel", "gemm_kernel")
 
 
 def main(path, out=None, gemm_log=None):
@@ -31,7 +31,7 @@ def main(path, out=None, gemm_log=None):
         for sh in shapes:
             by_grid_log[(sh[4], sh[5], sh[6], sh[7])].append(sh[:4])
         for r in gemm_rows:
-            g = (int(r["Grid_Size_X"]) // max(int(r["Workgroup_Size_X"]), 1), int(r["Grid_Size_Y"]), int(r.get("Grid_Size_Z", 1) or 1), 1 if "gemm_split" in r["Kernel_Name"] else 0)
+            g = (int(r["Grid_Size_X"]) // max(int(r["Workgroup_Size_X"]), 1), int(r["Grid_Size_Y"]), int(r.get("Grid_Size_Z", 1) or 1), 2 if "gemm_w1" in r["Kernel_Name"] else 1 if "gemm_split" in r["Kernel_Name"] else 0)   # the log's last column: chain / three planes / one plane
             by_grid_trace[g].append(r)
         for g, rs in by_grid_trace.items():
             if len(by_grid_log.get(g, [])) == len(rs):
