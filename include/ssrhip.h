@@ -41,7 +41,7 @@ const char* ssrhip_last_error(void);
 /* ------------------------------------------------------------------------------------------------
  * Paged KV cache (replaces the dense, re-concatenated `past` tensor: models/ssr.py:685-686,
  * models/modules/activation.py:626-631).
- *   pool  [n_pages][n_layer][2][n_head][SSRHIP_PAGE][head_dim] fp32
+ *   pool  [n_pages][n_layer][2][n_head][SSRHIP_PAGE][head_dim] fp32 (the *16 / *_kv16 entry points: the same layout in 2-byte bf16 entries)
  *   table [n_seq][max_pages] int32 : logical page -> physical page of that sequence (row)
  * ---------------------------------------------------------------------------------------------- */
 typedef struct ssrhip_kv {
@@ -59,7 +59,10 @@ typedef struct ssrhip_kv {
  * ---------------------------------------------------------------------------------------------- */
 enum { SSRHIP_PRO_NONE = 0, SSRHIP_PRO_LAYERNORM = 1, SSRHIP_PRO_ATTN_COMBINE = 2 };
 enum { SSRHIP_ACT_NONE = 0, SSRHIP_ACT_RELU = 1, SSRHIP_ACT_GELU_ERF = 2, SSRHIP_ACT_ELU = 3 };
-enum { SSRHIP_EPI_STORE = 0, SSRHIP_EPI_RESIDUAL = 1, SSRHIP_EPI_QKV_APPEND = 2 };
+/* SSRHIP_EPI_QKV_APPEND16 (5..32 rows only; <= 4 rows answer a contract error): QKV_APPEND into a cache of 2-byte entries — kv.pool
+ * points at bf16 storage of the same layout and element offsets, a K / V value is stored as the upper half of its fp32 bits rounded to
+ * nearest even (torch's .to(bfloat16): overflow to inf, NaN stays NaN); q goes to y as fp32, unchanged. */
+enum { SSRHIP_EPI_STORE = 0, SSRHIP_EPI_RESIDUAL = 1, SSRHIP_EPI_QKV_APPEND = 2, SSRHIP_EPI_QKV_APPEND16 = 3 };
 
 typedef struct ssrhip_gemv_args {
   const float* W;        /* [groups][N][K] row-major (PyTorch Linear.weight layout) */
@@ -213,6 +216,15 @@ int ssrhip_attn_rows(const ssrhip_attn_args* a, float* out /* [R][n_head*head_di
  * of sequence a->row_seq[seq_start[s]] (row_seq == NULL: sequence s), so a SUBSET of an engine's rows can be prefilled. */
 int ssrhip_attn_prefill(const ssrhip_attn_args* a, const int32_t* seq_start, int32_t n_seq, int32_t max_len, float* out,
                         ssrhip_stream_t stream);
+/* The bf16 KV cache (opt-in, 5..32-row engines: ssrhip_lm_set_kv16): the two entries above with a->kv.pool read as 2-byte entries (same
+ * layout and element offsets; an entry is the upper half of an fp32 value) and widened with a 16-bit shift, which is exact. The
+ * arithmetic behind the widening is the fp32 kernels', in their order and with their lane map (a lane's 8-byte load holds the 4 features
+ * its 16-byte load held): the result equals the fp32 entry's on the widened pool bit for bit. q, scores, softmax, accumulation and out
+ * stay fp32. ssrhip_attn_rows_kv16 keeps 2 or 4 pages in flight per workgroup: SSRHIP_ATTN_KV16_DEPTH = 2 | 4, read at every launch
+ * (unset or anything else: 2). */
+int ssrhip_attn_rows_kv16(const ssrhip_attn_args* a, float* out /* [R][n_head*head_dim] */, ssrhip_stream_t stream);
+int ssrhip_attn_prefill_kv16(const ssrhip_attn_args* a, const int32_t* seq_start, int32_t n_seq, int32_t max_len, float* out,
+                             ssrhip_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Token embedding + sinusoidal position: replaces embed_y (models/ssr.py:191-198, :655-660, :757-761),
@@ -428,6 +440,10 @@ int ssrhip_layernorm(const float* x, const float* w, const float* b, float eps, 
  * row_seq[r], position row_pos[r].  (activation.py:626-631 for the prefill rows) */
 int ssrhip_kv_scatter(const float* qkv, const ssrhip_kv* kv, int32_t layer, const int32_t* row_seq,
                       const int32_t* row_pos, int32_t R, ssrhip_stream_t stream);
+/* The same into a cache of 2-byte entries (kv->pool points at bf16 storage, same layout): every value rounded to nearest even like
+ * SSRHIP_EPI_QKV_APPEND16. */
+int ssrhip_kv_scatter16(const float* qkv, const ssrhip_kv* kv, int32_t layer, const int32_t* row_seq,
+                        const int32_t* row_pos, int32_t R, ssrhip_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Decode engine: one LM, B rows; prefill + N decode steps replayed from a captured hipGraph.
@@ -526,6 +542,15 @@ int ssrhip_lm_wt32_launches(const ssrhip_lm* lm);
  * and comes from nowhere else (no environment variable is read). Refused (< 0) for an engine created without planes and for one whose
  * decode step is already captured. */
 int ssrhip_lm_set_prefill_w1(ssrhip_lm* lm, int32_t on);
+/* on != 0: the pool of this engine's ssrhip_lm_buffers.kv holds 2-byte (bf16) entries, same layout and element count — the CALLER's
+ * statement about its buffer. The decode step then appends with SSRHIP_EPI_QKV_APPEND16 and always takes the fused walk
+ * (ssrhip_attn_rows_kv16, also at 5..11 rows x 16 heads; SSRHIP_ATTN_SPLIT is ignored); ssrhip_lm_prefill scatters with
+ * ssrhip_kv_scatter16 and attends with ssrhip_attn_prefill_kv16, and a prefill that cannot take the tiled attention (no seq_start,
+ * SSRHIP_PREFILL_ATTN_ROWWISE) is an error. So every attention of the engine sees bf16-valued K/V, whichever path wrote them.
+ * Refused (< 0) for engines of <= 4 rows, of more than 256 pages per row, and engines whose decode step is already captured. */
+int ssrhip_lm_set_kv16(ssrhip_lm* lm, int32_t on);
+/* how many attention launches of the last enqueued (or captured) decode step ran ssrhip_attn_rows_kv16 (n_layer for a kv16 engine, else 0) */
+int ssrhip_lm_kv16_launches(const ssrhip_lm* lm);
 /* enqueue `n_steps` decode steps (graph replays when use_graph!=0) */
 int ssrhip_lm_decode(ssrhip_lm* lm, int32_t n_steps, int32_t use_graph, ssrhip_stream_t stream);
 /* prefill R rows ([text || audio] of every sequence, flattened): fills the cache for all layers.

@@ -21,7 +21,7 @@ MAX_SILENCE = 8
 
 PRO_NONE, PRO_LAYERNORM, PRO_ATTN_COMBINE = 0, 1, 2
 ACT_NONE, ACT_RELU, ACT_GELU_ERF, ACT_ELU = 0, 1, 2, 3
-EPI_STORE, EPI_RESIDUAL, EPI_QKV_APPEND = 0, 1, 2
+EPI_STORE, EPI_RESIDUAL, EPI_QKV_APPEND, EPI_QKV_APPEND16 = 0, 1, 2, 3
 
 c_f32p = C.POINTER(C.c_float)
 c_i32p = C.POINTER(C.c_int32)
@@ -189,6 +189,8 @@ SYMBOLS = [
     ("ssrhip_attn_combine", C.c_int, [C.POINTER(AttnArgs), C.c_void_p, C.c_void_p]),
     ("ssrhip_attn_rows", C.c_int, [C.POINTER(AttnArgs), C.c_void_p, C.c_void_p]),
     ("ssrhip_attn_prefill", C.c_int, [C.POINTER(AttnArgs), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    ("ssrhip_attn_rows_kv16", C.c_int, [C.POINTER(AttnArgs), C.c_void_p, C.c_void_p]),
+    ("ssrhip_attn_prefill_kv16", C.c_int, [C.POINTER(AttnArgs), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     ("ssrhip_embed", C.c_int, [C.POINTER(EmbedArgs), C.c_void_p]),
     ("ssrhip_sample", C.c_int, [C.POINTER(SampleArgs), C.c_void_p]),
     ("ssrhip_gemm", C.c_int, [C.POINTER(GemmArgs), C.c_void_p]),
@@ -205,6 +207,7 @@ SYMBOLS = [
     ("ssrhip_resblock", C.c_int, [C.POINTER(ResblockArgs), C.c_void_p]),
     ("ssrhip_layernorm", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     ("ssrhip_kv_scatter", C.c_int, [C.c_void_p, C.POINTER(KV), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    ("ssrhip_kv_scatter16", C.c_int, [C.c_void_p, C.POINTER(KV), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     ("ssrhip_lm_create", C.c_int, [C.POINTER(LMDims), C.POINTER(LMWeights), C.POINTER(LMBuffers), C.POINTER(C.c_void_p)]),
     ("ssrhip_lm_destroy", None, [C.c_void_p]),
     ("ssrhip_lm_decode", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
@@ -213,6 +216,8 @@ SYMBOLS = [
     ("ssrhip_lm_score", C.c_int, [C.POINTER(LMDims), C.POINTER(LMWeights), C.POINTER(ScoreArgs), C.c_void_p]),
     ("ssrhip_lm_score_w1", C.c_int, [C.POINTER(LMDims), C.POINTER(LMWeights), C.POINTER(ScoreArgs), C.c_void_p]),
     ("ssrhip_lm_set_prefill_w1", C.c_int, [C.c_void_p, C.c_int32]),
+    ("ssrhip_lm_set_kv16", C.c_int, [C.c_void_p, C.c_int32]),
+    ("ssrhip_lm_kv16_launches", C.c_int, [C.c_void_p]),
     ("ssrhip_xent_rank", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("ssrhip_lm_pairing", C.c_int, [C.c_void_p, C.c_char_p, C.c_int32]),
     ("ssrhip_lm_pair_status", C.c_int, [C.c_void_p, C.c_void_p]),

@@ -24,6 +24,18 @@ namespace {
 #define SSR_ATTN_NT 1
 #endif
 __device__ __forceinline__ float4 ld_kv(const float* p) { return SSR_ATTN_NT ? ld_nt(p) : ld4(p); }
+// The bf16 KV cache (ssrhip_attn_rows_kv16 / ssrhip_attn_prefill_kv16): the same 4 features of a key as 4 two-byte entries, one 8-byte load;
+// they stay packed in registers and are widened (a 16-bit shift: exact) where the fp32 kernels use the float4
+__device__ __forceinline__ uint2 ld_kv(const uint16_t* p) {
+  typedef unsigned v2u __attribute__((ext_vector_type(2)));
+  if (!SSR_ATTN_NT) return *reinterpret_cast<const uint2*>(p);
+  const v2u v = __builtin_nontemporal_load(reinterpret_cast<const v2u*>(p));
+  return make_uint2(v.x, v.y);
+}
+__device__ __forceinline__ float4 kv_f4(const float4 v) { return v; }
+__device__ __forceinline__ float4 kv_f4(const uint2 v) { return bf16x4_widen(v); }
+template <bool KV16> struct kv_types { typedef float elem; typedef float4 vec; };
+template <> struct kv_types<true> { typedef uint16_t elem; typedef uint2 vec; };
 
 template <int HD, bool SEQ, int VAT = -1>   // SEQ: rows carry an explicit sequence id (a.row_seq != NULL: the per-row prefill path); the decode step has none
 __global__ __launch_bounds__(256) void attn_decode_kernel(const ssrhip_attn_args a, const int head_fastest) {   // VAT: see the V requests below
@@ -235,8 +247,13 @@ __global__ __launch_bounds__(64) void attn_combine_kernel(const ssrhip_attn_args
 // Loads are never predicated (see above): keys past the row's length re-read key 0 of the last page and are masked to -inf.
 constexpr int ATTN_ROWS_MAX_PAGES = 256;       // 32,768 positions per row
 
-template <int HD>
+// KV16: a.kv.pool holds 2-byte entries (same element offsets); K/V of a page then take half the registers, so DEPTH = 4 pages in flight fit
+// where the fp32 kernel holds 2. The folds run in page order whatever DEPTH is (a fold of a page past the row's last is masked: no change).
+template <int HD, bool KV16 = false, int DEPTH = 2>
 __global__ __launch_bounds__(512) void attn_rows_kernel(const ssrhip_attn_args a, float* out) {
+  static_assert(DEPTH == 2 || (KV16 && DEPTH == 4), "pages in flight: 2, or 4 with 2-byte entries");
+  typedef typename kv_types<KV16>::elem kv_elem;
+  typedef typename kv_types<KV16>::vec kv_vec;
   constexpr int LPK = HD / 4, KPI = 64 / LPK, NW = 8, KPW = SSRHIP_PAGE / NW, NI = KPW / KPI;
   __shared__ __attribute__((aligned(16))) float sm[NW][HD + 4];
   const int h = blockIdx.x, r = blockIdx.y;
@@ -255,10 +272,10 @@ __global__ __launch_bounds__(512) void attn_rows_kernel(const ssrhip_attn_args a
     pid[b] = (b * 64 < npages) ? a.kv.table[(size_t)seq * a.kv.max_pages + min(b * 64 + lane, npages - 1)] : 0;
   const size_t head_off = (size_t)h * SSRHIP_PAGE * HD, v_off = (size_t)H * SSRHIP_PAGE * HD;
   const size_t page_stride = (size_t)a.kv.n_layer * 2 * H * SSRHIP_PAGE * HD;
-  const float* pool = a.kv.pool + (size_t)a.layer * 2 * H * SSRHIP_PAGE * HD + head_off;
+  const kv_elem* pool = reinterpret_cast<const kv_elem*>(a.kv.pool) + (size_t)a.layer * 2 * H * SSRHIP_PAGE * HD + head_off;
   const float4 q = ld4(a.q + (size_t)r * (a.q_stride ? a.q_stride : H * HD) + h * HD + c4);
 
-  float4 kk[2][NI], vv[2][NI];
+  kv_vec kk[DEPTH][NI], vv[DEPTH][NI];
   float m = -INFINITY, l = 0.f;
   float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
 
@@ -267,7 +284,7 @@ __global__ __launch_bounds__(512) void attn_rows_kernel(const ssrhip_attn_args a
     const int pg_ = min((PG), npages - 1);                                                            \
     const int pb_ = pg_ >> 6;                                                                         \
     const int pv_ = pb_ == 0 ? pid[0] : (pb_ == 1 ? pid[1] : (pb_ == 2 ? pid[2] : pid[3]));           \
-    const float* kp_ = pool + (size_t)__builtin_amdgcn_readlane(pv_, pg_ & 63) * page_stride;         \
+    const kv_elem* kp_ = pool + (size_t)__builtin_amdgcn_readlane(pv_, pg_ & 63) * page_stride;       \
     const int jmax_ = ((PG) < npages) ? min(len - pg_ * SSRHIP_PAGE, SSRHIP_PAGE) - 1 : 0;            \
     _Pragma("unroll") for (int i = 0; i < NI; ++i) {                                                  \
       const int j_ = min(wave * KPW + i * KPI + sub, jmax_);                                          \
@@ -281,7 +298,7 @@ __global__ __launch_bounds__(512) void attn_rows_kernel(const ssrhip_attn_args a
 #define ATTN_FOLD(BUF, PG)                                                                            \
   {                                                                                                   \
     float s_[NI];                                                                                     \
-    _Pragma("unroll") for (int i = 0; i < NI; ++i) s_[i] = dot4(q, kk[BUF][i], 0.f);                  \
+    _Pragma("unroll") for (int i = 0; i < NI; ++i) s_[i] = dot4(q, kv_f4(kk[BUF][i]), 0.f);           \
     _Pragma("unroll") for (int i = 0; i < NI; ++i) s_[i] = (LPK == 32) ? half32_sum(s_[i]) : row16_sum(s_[i]); \
     float mloc_ = -INFINITY;                                                                          \
     _Pragma("unroll") for (int i = 0; i < NI; ++i) {                                                  \
@@ -298,19 +315,35 @@ __global__ __launch_bounds__(512) void attn_rows_kernel(const ssrhip_attn_args a
       _Pragma("unroll") for (int i = 0; i < NI; ++i) {                                                \
         const float p_ = expf(s_[i] - mnew_);                                                         \
         l += p_;                                                                                      \
-        o.x = fmaf(p_, vv[BUF][i].x, o.x); o.y = fmaf(p_, vv[BUF][i].y, o.y);                         \
-        o.z = fmaf(p_, vv[BUF][i].z, o.z); o.w = fmaf(p_, vv[BUF][i].w, o.w);                         \
+        o.x = fmaf(p_, kv_f4(vv[BUF][i]).x, o.x); o.y = fmaf(p_, kv_f4(vv[BUF][i]).y, o.y);           \
+        o.z = fmaf(p_, kv_f4(vv[BUF][i]).z, o.z); o.w = fmaf(p_, kv_f4(vv[BUF][i]).w, o.w);           \
       }                                                                                               \
       m = mnew_;                                                                                      \
     }                                                                                                 \
   }
 
-  ATTN_ISSUE(0, 0)
-  for (int pg = 0; pg < npages; pg += 2) {
-    ATTN_ISSUE(1, pg + 1)
-    ATTN_FOLD(0, pg)
-    ATTN_ISSUE(0, pg + 2)
-    ATTN_FOLD(1, pg + 1)
+  if constexpr (DEPTH == 2) {
+    ATTN_ISSUE(0, 0)
+    for (int pg = 0; pg < npages; pg += 2) {
+      ATTN_ISSUE(1, pg + 1)
+      ATTN_FOLD(0, pg)
+      ATTN_ISSUE(0, pg + 2)
+      ATTN_FOLD(1, pg + 1)
+    }
+  } else {
+    ATTN_ISSUE(0, 0)
+    ATTN_ISSUE(1, 1)
+    ATTN_ISSUE(2, 2)
+    for (int pg = 0; pg < npages; pg += 4) {
+      ATTN_ISSUE(3, pg + 3)
+      ATTN_FOLD(0, pg)
+      ATTN_ISSUE(0, pg + 4)
+      ATTN_FOLD(1, pg + 1)
+      ATTN_ISSUE(1, pg + 5)
+      ATTN_FOLD(2, pg + 2)
+      ATTN_ISSUE(2, pg + 6)
+      ATTN_FOLD(3, pg + 3)
+    }
   }
 #undef ATTN_ISSUE
 #undef ATTN_FOLD
@@ -363,8 +396,11 @@ __global__ __launch_bounds__(512) void attn_rows_kernel(const ssrhip_attn_args a
 // the prompt rows (activation.py:634).
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-template <int HD>
-__global__ __launch_bounds__(256) void attn_prefill_kernel(const ssrhip_attn_args a, const int32_t* __restrict__ seq_start, float* __restrict__ out) {
+// KV16: the tile loader reads 2-byte entries (half the global bytes) and writes the same fp32 LDS tiles; everything behind it is unchanged
+template <int HD, bool KV16>
+__device__ __forceinline__ void attn_prefill_body(const ssrhip_attn_args& a, const int32_t* __restrict__ seq_start, float* __restrict__ out) {
+  typedef typename kv_types<KV16>::elem kv_elem;
+  typedef typename kv_types<KV16>::vec kv_vec;
   constexpr int KT = 32, LDK = HD + 4, F4 = HD / 4, NLD = KT * F4 / 256;     // float4 loads per thread per tile (HD 128: 4, 64: 2)
   constexpr int NJ = HD / 8, NMB = HD / 32;
   __shared__ __attribute__((aligned(16))) float Ks[KT * LDK];
@@ -393,19 +429,19 @@ __global__ __launch_bounds__(256) void attn_prefill_kernel(const ssrhip_attn_arg
   // others keep decoding); without row_seq segment i is sequence i
   const int32_t* tab = a.kv.table + (size_t)(a.row_seq ? a.row_seq[r0] : seq) * a.kv.max_pages;
   const size_t page_stride = (size_t)a.kv.n_layer * 2 * H * SSRHIP_PAGE * HD;
-  const float* pool = a.kv.pool + ((size_t)a.layer * 2 * H + h) * SSRHIP_PAGE * HD;
+  const kv_elem* pool = reinterpret_cast<const kv_elem*>(a.kv.pool) + ((size_t)a.layer * 2 * H + h) * SSRHIP_PAGE * HD;
   const size_t v_off = (size_t)H * SSRHIP_PAGE * HD;
 
-  float4 kreg[NLD], vreg[NLD];
+  kv_vec kreg[NLD], vreg[NLD];
   auto gload = [&](int kt) {                                               // tile kt -> registers (rows past S: clamped, masked later)
     const int key0 = kt * KT;
-    const float* base = pool + (size_t)tab[key0 / SSRHIP_PAGE] * page_stride + (size_t)(key0 % SSRHIP_PAGE) * HD;
+    const kv_elem* base = pool + (size_t)tab[key0 / SSRHIP_PAGE] * page_stride + (size_t)(key0 % SSRHIP_PAGE) * HD;
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
       const int idx = i * 256 + t, row = idx / F4, c4 = idx % F4;
       const int rr = min(row, S - 1 - key0);                               // key0 + row < S (>= 0: key0 <= last query < S)
-      kreg[i] = ld4(base + (size_t)rr * HD + c4 * 4);
-      vreg[i] = ld4(base + v_off + (size_t)rr * HD + c4 * 4);
+      kreg[i] = *reinterpret_cast<const kv_vec*>(base + (size_t)rr * HD + c4 * 4);
+      vreg[i] = *reinterpret_cast<const kv_vec*>(base + v_off + (size_t)rr * HD + c4 * 4);
     }
   };
   f32x16 accO[NMB];
@@ -421,8 +457,8 @@ __global__ __launch_bounds__(256) void attn_prefill_kernel(const ssrhip_attn_arg
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
       const int idx = i * 256 + t, row = idx / F4, c4 = idx % F4;
-      *reinterpret_cast<float4*>(Ks + row * LDK + c4 * 4) = kreg[i];
-      *reinterpret_cast<float4*>(Vs + row * LDK + c4 * 4) = vreg[i];
+      *reinterpret_cast<float4*>(Ks + row * LDK + c4 * 4) = kv_f4(kreg[i]);
+      *reinterpret_cast<float4*>(Vs + row * LDK + c4 * 4) = kv_f4(vreg[i]);
     }
     __syncthreads();
     if (kt + 1 < ntile) gload(kt + 1);                                     // next tile under the MFMAs
@@ -482,6 +518,15 @@ __global__ __launch_bounds__(256) void attn_prefill_kernel(const ssrhip_attn_arg
           make_float4(accO[mb][4 * g] * inv, accO[mb][4 * g + 1] * inv, accO[mb][4 * g + 2] * inv, accO[mb][4 * g + 3] * inv);
 }
 
+template <int HD>
+__global__ __launch_bounds__(256) void attn_prefill_kernel(const ssrhip_attn_args a, const int32_t* __restrict__ seq_start, float* __restrict__ out) {
+  attn_prefill_body<HD, false>(a, seq_start, out);
+}
+template <int HD>
+__global__ __launch_bounds__(256) void attn_prefill_kv16_kernel(const ssrhip_attn_args a, const int32_t* __restrict__ seq_start, float* __restrict__ out) {
+  attn_prefill_body<HD, true>(a, seq_start, out);
+}
+
 int check(const ssrhip_attn_args* a, const char* who) {
   SSR_REQUIRE(a && a->q && a->kv.pool && a->kv.table && a->row_len, "%s: null argument", who);
   SSR_REQUIRE(a->kv.head_dim == 64 || a->kv.head_dim == 128, "%s: head_dim %d not in {64,128}", who, a->kv.head_dim);
@@ -506,12 +551,18 @@ static ssrhip_attn_args row_slice(const ssrhip_attn_args& a, int r0, int n) {
 }
 enum { MAX_GRID_ROWS = 65535 };
 
+// the argument contract of ssrhip_attn_prefill and ssrhip_attn_prefill_kv16
+static int prefill_check(const ssrhip_attn_args* a, const int32_t* seq_start, int32_t n_seq, int32_t max_len, const float* out, const char* who) {
+  SSR_REQUIRE(a && a->q && a->kv.pool && a->kv.table && seq_start && out, "%s: null argument", who);
+  SSR_REQUIRE(a->kv.head_dim == 64 || a->kv.head_dim == 128, "%s: head_dim %d not in {64,128}", who, a->kv.head_dim);
+  SSR_REQUIRE(n_seq > 0 && n_seq <= 65535 && max_len > 0 && a->kv.n_head <= 65535, "%s: bad n_seq / max_len", who);
+  SSR_REQUIRE((a->q_stride ? a->q_stride : a->kv.n_head * a->kv.head_dim) % 4 == 0, "%s: q_stride must be a multiple of 4", who);
+  return 0;
+}
+
 extern "C" int ssrhip_attn_prefill(const ssrhip_attn_args* a, const int32_t* seq_start, int32_t n_seq, int32_t max_len, float* out,
                                    ssrhip_stream_t stream) {
-  SSR_REQUIRE(a && a->q && a->kv.pool && a->kv.table && seq_start && out, "ssrhip_attn_prefill: null argument");
-  SSR_REQUIRE(a->kv.head_dim == 64 || a->kv.head_dim == 128, "ssrhip_attn_prefill: head_dim %d not in {64,128}", a->kv.head_dim);
-  SSR_REQUIRE(n_seq > 0 && n_seq <= 65535 && max_len > 0 && a->kv.n_head <= 65535, "ssrhip_attn_prefill: bad n_seq / max_len");
-  SSR_REQUIRE((a->q_stride ? a->q_stride : a->kv.n_head * a->kv.head_dim) % 4 == 0, "ssrhip_attn_prefill: q_stride must be a multiple of 4");
+  if (int e = prefill_check(a, seq_start, n_seq, max_len, out, "ssrhip_attn_prefill")) return e;
   dim3 grid((max_len + 127) / 128, a->kv.n_head, n_seq);
   if (a->kv.head_dim == 128) hipLaunchKernelGGL(attn_prefill_kernel<128>, grid, dim3(256), 0, (hipStream_t)stream, *a, seq_start, out);
   else hipLaunchKernelGGL(attn_prefill_kernel<64>, grid, dim3(256), 0, (hipStream_t)stream, *a, seq_start, out);
@@ -519,15 +570,52 @@ extern "C" int ssrhip_attn_prefill(const ssrhip_attn_args* a, const int32_t* seq
   return 0;
 }
 
+extern "C" int ssrhip_attn_prefill_kv16(const ssrhip_attn_args* a, const int32_t* seq_start, int32_t n_seq, int32_t max_len, float* out,
+                                        ssrhip_stream_t stream) {
+  if (int e = prefill_check(a, seq_start, n_seq, max_len, out, "ssrhip_attn_prefill_kv16")) return e;
+  dim3 grid((max_len + 127) / 128, a->kv.n_head, n_seq);
+  if (a->kv.head_dim == 128) hipLaunchKernelGGL(attn_prefill_kv16_kernel<128>, grid, dim3(256), 0, (hipStream_t)stream, *a, seq_start, out);
+  else hipLaunchKernelGGL(attn_prefill_kv16_kernel<64>, grid, dim3(256), 0, (hipStream_t)stream, *a, seq_start, out);
+  SSR_LAUNCH_CHECK();
+  return 0;
+}
+
+// the argument contract of ssrhip_attn_rows and ssrhip_attn_rows_kv16
+static int rows_check(const ssrhip_attn_args* a, const float* out, const char* who) {
+  if (int e = check(a, who)) return e;
+  SSR_REQUIRE(out && out != a->q, "%s: out is null or aliases q", who);
+  SSR_REQUIRE(!a->out_tiled || a->R <= 32, "%s: tiled output needs R <= 32", who);
+  SSR_REQUIRE(a->R <= MAX_GRID_ROWS, "%s: R too large", who);
+  SSR_REQUIRE(a->kv.max_pages <= ATTN_ROWS_MAX_PAGES, "%s: more than %d pages per row", who, ATTN_ROWS_MAX_PAGES);
+  return 0;
+}
+
 extern "C" int ssrhip_attn_rows(const ssrhip_attn_args* a, float* out, ssrhip_stream_t stream) {
-  if (int e = check(a, "ssrhip_attn_rows")) return e;
-  SSR_REQUIRE(out && out != a->q, "ssrhip_attn_rows: out is null or aliases q");
-  SSR_REQUIRE(!a->out_tiled || a->R <= 32, "ssrhip_attn_rows: tiled output needs R <= 32");
-  SSR_REQUIRE(a->R <= MAX_GRID_ROWS, "ssrhip_attn_rows: R too large");
-  SSR_REQUIRE(a->kv.max_pages <= ATTN_ROWS_MAX_PAGES, "ssrhip_attn_rows: more than %d pages per row", ATTN_ROWS_MAX_PAGES);
+  if (int e = rows_check(a, out, "ssrhip_attn_rows")) return e;
   dim3 grid(a->kv.n_head, a->R);
   if (a->kv.head_dim == 128) hipLaunchKernelGGL(attn_rows_kernel<128>, grid, dim3(512), 0, (hipStream_t)stream, *a, out);
   else hipLaunchKernelGGL(attn_rows_kernel<64>, grid, dim3(512), 0, (hipStream_t)stream, *a, out);
+  SSR_LAUNCH_CHECK();
+  return 0;
+}
+
+// Pages in flight of the kv16 walk: 2 = the fp32 kernel's structure (the default), 4 = the registers the 2-byte entries free hold two more
+// pages. A/B knob SSRHIP_ATTN_KV16_DEPTH, read at every launch (a captured graph keeps what it was captured with).
+constexpr int ATTN_KV16_DEPTH_DEFAULT = 2;
+
+extern "C" int ssrhip_attn_rows_kv16(const ssrhip_attn_args* a, float* out, ssrhip_stream_t stream) {
+  if (int e = rows_check(a, out, "ssrhip_attn_rows_kv16")) return e;
+  int depth = ATTN_KV16_DEPTH_DEFAULT;
+  if (const char* e = getenv("SSRHIP_ATTN_KV16_DEPTH")) { const int v = atoi(e); if (v == 2 || v == 4) depth = v; }
+  dim3 grid(a->kv.n_head, a->R);
+  hipStream_t s = (hipStream_t)stream;
+  if (a->kv.head_dim == 128) {
+    if (depth == 4) hipLaunchKernelGGL((attn_rows_kernel<128, true, 4>), grid, dim3(512), 0, s, *a, out);
+    else hipLaunchKernelGGL((attn_rows_kernel<128, true, 2>), grid, dim3(512), 0, s, *a, out);
+  } else {
+    if (depth == 4) hipLaunchKernelGGL((attn_rows_kernel<64, true, 4>), grid, dim3(512), 0, s, *a, out);
+    else hipLaunchKernelGGL((attn_rows_kernel<64, true, 2>), grid, dim3(512), 0, s, *a, out);
+  }
   SSR_LAUNCH_CHECK();
   return 0;
 }

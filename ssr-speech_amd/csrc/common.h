@@ -194,6 +194,23 @@ __device__ __forceinline__ float4 ld_nt(const float* p) {
 }
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 
+// ---- the bf16 KV cache: an entry is the upper half of an fp32 value, rounded to nearest even — torch's .to(torch.bfloat16) for finite
+// values and +-inf (a finite value above the largest bf16 carries into the exponent: inf); a NaN keeps its sign and upper payload and gets
+// the quiet bit, so it stays a NaN. Plain integer arithmetic.
+__device__ __forceinline__ unsigned bf16_rne(float f) {
+  const unsigned u = __float_as_uint(f);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x0040u;
+  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+}
+// four rounded entries as they lie in memory: element 0 in the low half of .x
+__device__ __forceinline__ uint2 bf16x4_rne(float a, float b, float c, float d) {
+  return make_uint2(bf16_rne(a) | (bf16_rne(b) << 16), bf16_rne(c) | (bf16_rne(d) << 16));
+}
+// ... and back: a 16-bit shift, exact
+__device__ __forceinline__ float4 bf16x4_widen(const uint2 u) {
+  return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xffff0000u));
+}
+
 // nn.ELU(alpha = 1): v > 0 ? v : exp(v) - 1 with the hardware exponential (v_exp_f32). Absolute error <= 1.2e-7 everywhere (for |v| below
 // 6e-8 the result is 0 instead of v). Rounds 1-3 switched to a degree-6 Taylor polynomial above -0.25 for RELATIVE accuracy near zero;
 // round 4's counters showed what that costs — the fused residual block was VALU-bound, half of its 4,230 VALU instructions per wave and

@@ -74,6 +74,8 @@ struct ssrhip_lm {
   const uint16_t* pk_head1 = nullptr;
   const uint16_t* pk_head2 = nullptr;
   int pk_launches = 0;          // launches of the last enqueued step that ran a kernel of pk_kind (ssrhip_lm_{w16,wt16,wt32}_launches)
+  bool kv16 = false;            // b.kv.pool holds 2-byte entries (ssrhip_lm_set_kv16: the caller's statement about its buffer)
+  int kv16_launches = 0;        // attention launches of the last enqueued step that ran ssrhip_attn_rows_kv16 (ssrhip_lm_kv16_launches)
 };
 
 namespace {
@@ -208,16 +210,17 @@ struct StepShapes {
   // (include/ssrhip.h SSRHIP_TILED_P: one 16-row panel per 16 rows) so that the matrix-core GEMV's operand loads are contiguous KiBs
   const int tiled;
   const bool wt;       // streaming-order weight copies for the matrix-core GEMV (include/ssrhip.h w_tiled)
+  const bool kv16;     // the cache holds 2-byte entries (ssrhip_lm_set_kv16)
   explicit StepShapes(const ssrhip_lm* lm)
       : d(lm->d), w(lm->w), b(lm->b), D(lm->d.d_model), B(lm->b.B), K(lm->d.n_codebooks), Hh(lm->d.head_hidden), tiled(lm->b.B > 4 ? 1 : 0),
-        wt(lm->b.B > 4 && lm->w.in_proj_wt) {}
+        wt(lm->b.B > 4 && lm->w.in_proj_wt), kv16(lm->kv16) {}
   ssrhip_gemv_args qkv_args(int l) const {
     ssrhip_gemv_args g;
     // LN1 + packed QKV projection, q -> b.q, k/v appended in place into the paged cache
     memset(&g, 0, sizeof(g));
     g.W = w.in_proj_w[l]; g.bias = w.in_proj_b[l]; g.x = b.x; g.y = b.q;
     g.B = B; g.N = 3 * D; g.K = D; g.groups = 1; g.x_stride = D; g.y_stride = D;
-    g.pro = SSRHIP_PRO_LAYERNORM; g.act = SSRHIP_ACT_NONE; g.epi = SSRHIP_EPI_QKV_APPEND;
+    g.pro = SSRHIP_PRO_LAYERNORM; g.act = SSRHIP_ACT_NONE; g.epi = kv16 ? SSRHIP_EPI_QKV_APPEND16 : SSRHIP_EPI_QKV_APPEND;
     if (!d.ln_folded) { g.ln_w = w.ln1_w[l]; g.ln_b = w.ln1_b[l]; }
     g.ln_eps = 1e-5f;
     g.kv = b.kv; g.layer = l; g.kv_pos = b.kv_pos;
@@ -357,7 +360,9 @@ int enqueue_step(ssrhip_lm* lm, hipStream_t s, Timer* tm) {
   bool qkv_done = false;                        // this layer's QKV already ran inside the previous layer's pair launch
   // 5..32 rows with enough (row, head) pairs to give every CU one: the fused walk over the pages (no partials, no merge
   // launch); its output goes to b.h (free until FFN1 of this layer) because q is still being read by other workgroups
-  const bool fused_attn = sh.B > 4 && sh.B * d.n_head >= 192 && b.kv.max_pages <= 256 && !getenv_flag("SSRHIP_ATTN_SPLIT");   // 256 pages: the kernel's page-id registers
+  // a bf16 KV cache (ssrhip_lm_set_kv16 checked the rows and the pages) always takes the fused walk: the split kernels read fp32 entries
+  const bool fused_attn = lm->kv16 || (sh.B > 4 && sh.B * d.n_head >= 192 && b.kv.max_pages <= 256 && !getenv_flag("SSRHIP_ATTN_SPLIT"));   // 256 pages: the kernel's page-id registers
+  int n_kv16 = 0;
 
   if (tm) tm->slot = 0;
 
@@ -381,7 +386,8 @@ int enqueue_step(ssrhip_lm* lm, hipStream_t s, Timer* tm) {
     ssrhip_gemv_args op;
     if (fused_attn) {
       at.out_tiled = 1;
-      STEP_CALL(CAT_ATTN, ssrhip_attn_rows(&at, b.h, s));
+      if (lm->kv16) { STEP_CALL(CAT_ATTN, ssrhip_attn_rows_kv16(&at, b.h, s)); n_kv16 += 1; }
+      else STEP_CALL(CAT_ATTN, ssrhip_attn_rows(&at, b.h, s));
       op = sh.outproj_rows_args(l, b.h);
     } else {
       STEP_CALL(CAT_ATTN, ssrhip_attn_decode(&at, s));
@@ -420,7 +426,7 @@ int enqueue_step(ssrhip_lm* lm, hipStream_t s, Timer* tm) {
   STEP_CALL(CAT_GEMV, gemv_call(h2, lm->pk_head2));
   const ssrhip_sample_args sa = sh.sample_args();
   STEP_CALL(CAT_SAMPLE, ssrhip_sample(&sa, s));
-  if (!tm || tm->only < 0) lm->pk_launches = n_pk;   // (a category-timing pass enqueues only part of a step)
+  if (!tm || tm->only < 0) { lm->pk_launches = n_pk; lm->kv16_launches = n_kv16; }   // (a category-timing pass enqueues only part of a step)
   return 0;
 }
 
@@ -555,6 +561,16 @@ extern "C" int ssrhip_lm_set_prefill_w1(ssrhip_lm* lm, int32_t on) {
   lm->prefill_w1 = on != 0;
   return 0;
 }
+extern "C" int ssrhip_lm_set_kv16(ssrhip_lm* lm, int32_t on) {
+  SSR_REQUIRE(lm, "ssrhip_lm_set_kv16: null engine");
+  SSR_REQUIRE(!lm->exec, "ssrhip_lm_set_kv16: the decode step of this engine is already captured (call it before the first ssrhip_lm_decode)");
+  SSR_REQUIRE(!on || lm->b.B > 4, "ssrhip_lm_set_kv16: the bf16 KV cache exists for 5..32 rows only (this engine has %d rows)", lm->b.B);
+  SSR_REQUIRE(!on || lm->b.kv.max_pages <= 256, "ssrhip_lm_set_kv16: the fused attention walk takes at most 256 pages per row (this engine has %d)", lm->b.kv.max_pages);
+  SSR_REQUIRE(!on || !getenv_flag("SSRHIP_PREFILL_ATTN_ROWWISE"), "ssrhip_lm_set_kv16: SSRHIP_PREFILL_ATTN_ROWWISE is set, and the rowwise prefill attention reads fp32 entries");
+  lm->kv16 = on != 0;
+  return 0;
+}
+extern "C" int ssrhip_lm_kv16_launches(const ssrhip_lm* lm) { return lm && lm->kv16 ? lm->kv16_launches : 0; }
 extern "C" int ssrhip_lm_w16_launches(const ssrhip_lm* lm) { return lm_packed_launches(lm, PK_W16); }
 extern "C" int ssrhip_lm_wt16_launches(const ssrhip_lm* lm) { return lm_packed_launches(lm, PK_WT16); }
 extern "C" int ssrhip_lm_wt32_launches(const ssrhip_lm* lm) { return lm_packed_launches(lm, PK_WT32); }
@@ -680,8 +696,9 @@ static int lm_gemm(ssrhip_gemm_args& g, int planes, const uint16_t* ws, hipStrea
   return ssrhip_gemm(&g, s);
 }
 
+// `kv16`: the cache holds 2-byte entries — the rounding scatter and the widening tiled attention (the caller has refused a rowwise prefill).
 static int lm_layer_loop(const ssrhip_lm_dims& d, const ssrhip_lm_weights& w, int planes, const ssrhip_kv& kv, const ssrhip_prefill_args* p,
-                         bool tiled_attn, hipStream_t s) {
+                         bool tiled_attn, bool kv16, hipStream_t s) {
   const int D = d.d_model, R = p->R;
   const bool one_layer_kv = kv.n_layer == 1;
 
@@ -697,7 +714,7 @@ static int lm_layer_loop(const ssrhip_lm_dims& d, const ssrhip_lm_weights& w, in
     g.A = p->xn; g.W = w.in_proj_w[l]; g.bias = w.in_proj_b[l]; g.C = p->qkv;
     g.M = R; g.N = 3 * D; g.K = D; g.lda = D; g.ldc = 3 * D;
     if (int rc = lm_gemm(g, planes, planes ? w.in_proj_ws[l] : nullptr, s)) return rc;
-    if (int rc = ssrhip_kv_scatter(p->qkv, &kv, kl, p->row_seq, p->row_pos, R, s)) return rc;
+    if (int rc = (kv16 ? ssrhip_kv_scatter16 : ssrhip_kv_scatter)(p->qkv, &kv, kl, p->row_seq, p->row_pos, R, s)) return rc;
 
     ssrhip_attn_args at;
     memset(&at, 0, sizeof(at));
@@ -707,7 +724,7 @@ static int lm_layer_loop(const ssrhip_lm_dims& d, const ssrhip_lm_weights& w, in
     at.q = p->qkv; at.q_stride = 3 * D;   // q is the first third of each packed qkv row
     if (tiled_attn) {
       // whole prompts: K/V tiles staged in LDS once per 128 queries, both products on the matrix core, no partials
-      if (int rc = ssrhip_attn_prefill(&at, p->seq_start, p->n_seq, p->max_len, p->o, s)) return rc;
+      if (int rc = (kv16 ? ssrhip_attn_prefill_kv16 : ssrhip_attn_prefill)(&at, p->seq_start, p->n_seq, p->max_len, p->o, s)) return rc;
     } else {
       if (int rc = ssrhip_attn_decode(&at, s)) return rc;
       if (int rc = ssrhip_attn_combine(&at, p->o, s)) return rc;
@@ -734,10 +751,12 @@ static int lm_layer_loop(const ssrhip_lm_dims& d, const ssrhip_lm_weights& w, in
 extern "C" int ssrhip_lm_prefill(ssrhip_lm* lm, const ssrhip_prefill_args* p, ssrhip_stream_t stream) {
   SSR_REQUIRE(lm && p && p->tok && p->pos && p->kind && p->row_seq && p->row_pos && p->row_len, "ssrhip_lm_prefill: null argument");
   const bool tiled_attn = p->seq_start && p->n_seq > 0 && p->max_len > 0 && !getenv_flag("SSRHIP_PREFILL_ATTN_ROWWISE");
+  SSR_REQUIRE(tiled_attn || !lm->kv16, "ssrhip_lm_prefill: an engine with a bf16 KV cache prefills through the tiled attention only (seq_start is missing or "
+              "SSRHIP_PREFILL_ATTN_ROWWISE is set): the rowwise kernels read fp32 entries");
   SSR_REQUIRE(p->x && p->xn && p->qkv && p->o && p->h && (tiled_attn || (p->part_o && p->part_ml)), "ssrhip_lm_prefill: null workspace");
   ssrhip_kv kv = lm->b.kv;
   if (p->table) kv.table = p->table;              // two-phase admission: the rows being filled are not in the decode step's table yet
-  if (int rc = lm_layer_loop(lm->d, lm->w, lm->prefill_split ? (lm->prefill_w1 ? 1 : 3) : 0, kv, p, tiled_attn, (hipStream_t)stream)) return rc;
+  if (int rc = lm_layer_loop(lm->d, lm->w, lm->prefill_split ? (lm->prefill_w1 ? 1 : 3) : 0, kv, p, tiled_attn, lm->kv16, (hipStream_t)stream)) return rc;
   if (p->no_embed) return 0;
   return ssrhip_lm_embed_pending(lm, stream);
 }
@@ -777,7 +796,7 @@ static int lm_score(const ssrhip_lm_dims* d, const ssrhip_lm_weights* w, const s
   p.R = a->R; p.max_splits = (a->max_len + SSRHIP_PAGE - 1) / SSRHIP_PAGE;
   p.x = a->x; p.xn = a->xn; p.qkv = a->qkv; p.o = a->o; p.h = a->h;
   p.seq_start = a->seq_start; p.n_seq = a->n_seq; p.max_len = a->max_len;
-  if (int rc = lm_layer_loop(*d, *w, layer_split ? np : 0, a->kv, &p, true, s)) return rc;
+  if (int rc = lm_layer_loop(*d, *w, layer_split ? np : 0, a->kv, &p, true, false, s)) return rc;
 
   // final LayerNorm of the scored rows only, gathered by the launch itself: one launch per sequence (its scored rows are contiguous)
   long off = 0;

@@ -206,6 +206,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* x, const fl
   }
 }
 
+template <bool KV16 = false>     // KV16: the pool holds 2-byte entries (same element offsets): four rounded values leave as one 8-byte store
 __global__ __launch_bounds__(256) void kv_scatter_kernel(const float* qkv, const ssrhip_kv kv, int layer, const int* row_seq,
                                                          const int* row_pos, int D) {
   const int r = blockIdx.x;
@@ -216,7 +217,8 @@ __global__ __launch_bounds__(256) void kv_scatter_kernel(const float* qkv, const
     const int which = c / D, cc = c % D;
     const float4 v = ld4(qkv + (size_t)r * 3 * D + D + c);
     float* dst = kv_addr(kv, seq, layer, which, cc / hd, pos) + (cc % hd);
-    *reinterpret_cast<float4*>(dst) = v;
+    if constexpr (KV16) *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(kv.pool) + (dst - kv.pool)) = bf16x4_rne(v.x, v.y, v.z, v.w);
+    else *reinterpret_cast<float4*>(dst) = v;
   }
 }
 
@@ -265,7 +267,17 @@ extern "C" int ssrhip_kv_scatter(const float* qkv, const ssrhip_kv* kv, int32_t 
                                  const int32_t* row_pos, int32_t R, ssrhip_stream_t stream) {
   SSR_REQUIRE(qkv && kv && kv->pool && kv->table && row_pos && R > 0, "ssrhip_kv_scatter: bad argument");
   SSR_REQUIRE(kv->head_dim % 4 == 0, "ssrhip_kv_scatter: head_dim must be a multiple of 4");
-  hipLaunchKernelGGL(kv_scatter_kernel, dim3(R), dim3(256), 0, (hipStream_t)stream, qkv, *kv, layer, row_seq, row_pos,
+  hipLaunchKernelGGL(kv_scatter_kernel<false>, dim3(R), dim3(256), 0, (hipStream_t)stream, qkv, *kv, layer, row_seq, row_pos,
+                     kv->n_head * kv->head_dim);
+  SSR_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ssrhip_kv_scatter16(const float* qkv, const ssrhip_kv* kv, int32_t layer, const int32_t* row_seq,
+                                   const int32_t* row_pos, int32_t R, ssrhip_stream_t stream) {
+  SSR_REQUIRE(qkv && kv && kv->pool && kv->table && row_pos && R > 0, "ssrhip_kv_scatter16: bad argument");
+  SSR_REQUIRE(kv->head_dim % 4 == 0, "ssrhip_kv_scatter16: head_dim must be a multiple of 4");
+  hipLaunchKernelGGL(kv_scatter_kernel<true>, dim3(R), dim3(256), 0, (hipStream_t)stream, qkv, *kv, layer, row_seq, row_pos,
                      kv->n_head * kv->head_dim);
   SSR_LAUNCH_CHECK();
   return 0;

@@ -1242,6 +1242,7 @@ extern "C" int ssrhip_gemv_pair_applicable(const ssrhip_gemv_args* a, const ssrh
 extern "C" int ssrhip_gemv_pair(const ssrhip_gemv_args* a, const ssrhip_gemv_args* b, void* ws, int32_t buf, int32_t buf_next, ssrhip_stream_t stream) {
   SSR_REQUIRE(a && b && ws, "ssrhip_gemv_pair: null argument");
   SSR_REQUIRE(buf >= 0 && buf < 3 && buf_next >= 0 && buf_next < 3 && buf != buf_next, "ssrhip_gemv_pair: granule buffers %d -> %d (0..2, different)", buf, buf_next);
+  SSR_REQUIRE(a->epi != SSRHIP_EPI_QKV_APPEND16 && b->epi != SSRHIP_EPI_QKV_APPEND16, "ssrhip_gemv_pair: the 2-byte KV append (EPI_QKV_APPEND16) exists for 5..32 rows only");
   bool merge = false;
   const int nuwb = pair_nuwb(a, b, ssr_num_cu(), &merge);
   if (!nuwb) return 1;

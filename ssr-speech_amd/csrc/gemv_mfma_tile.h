@@ -42,9 +42,12 @@ struct TileEpi {
   int kv_which, kv_cc, kv_pos, kv_page;   // QKV launch, K / V rows (kv_which = 1 | 2): dst is resolved in tile_epilogue_finish
 };
 
+// the QKV launch: K / V rows go to the paged cache, as fp32 (QKV_APPEND) or as rounded 2-byte entries (QKV_APPEND16)
+__host__ __device__ __forceinline__ bool epi_appends(int epi) { return epi == SSRHIP_EPI_QKV_APPEND || epi == SSRHIP_EPI_QKV_APPEND16; }
+
 // kv_pos of this lane's batch column for the QKV launch (0 otherwise): request it BEFORE the x / W loads (see tile_epilogue_fetch)
 __device__ __forceinline__ int tile_kvpos(const ssrhip_gemv_args& a, int lane) {
-  return (a.epi == SSRHIP_EPI_QKV_APPEND) ? a.kv_pos[min(lane & 15, a.B - 1)] : 0;
+  return epi_appends(a.epi) ? a.kv_pos[min(lane & 15, a.B - 1)] : 0;
 }
 
 __device__ __forceinline__ TileEpi tile_epilogue_fetch(const ssrhip_gemv_args& a, int hd, int grp, int row0, int tile_rows, int lane, int kvpos) {
@@ -61,13 +64,13 @@ __device__ __forceinline__ TileEpi tile_epilogue_fetch(const ssrhip_gemv_args& a
   // launch drained its x slice and its first 16 weight loads — twice — before the LayerNorm could start; and a load under a divergent
   // branch makes hipcc wait for it (`vmcnt(0)`) in the OTHER branch before it may reuse the destination register (read off the ISA,
   // round 5; the 2-row kernel had the same disease, csrc/gemv.hip).
-  if (a.epi == SSRHIP_EPI_QKV_APPEND) e.kv_page = a.kv.table[(size_t)min(c, B - 1) * a.kv.max_pages + (kvpos / SSRHIP_PAGE)];
+  if (epi_appends(a.epi)) e.kv_page = a.kv.table[(size_t)min(c, B - 1) * a.kv.max_pages + (kvpos / SSRHIP_PAGE)];
   const bool live = c < B && r0 < N && ks * 4 < tile_rows;
   e.nvalid = live ? min(4, N - r0) : 0;
 #pragma unroll
   for (int j = 0; j < 4; ++j) { e.bias[j] = 0.f; e.res[j] = 0.f; }
   if (!live) return e;
-  if (a.epi == SSRHIP_EPI_QKV_APPEND) {
+  if (epi_appends(a.epi)) {
     const int D = K, which = r0 / D, cc = r0 % D;
     e.kv_which = which;                                                // 0: a q row (plain store below); 1 | 2: resolved in tile_epilogue_finish
     e.kv_cc = cc;
@@ -90,9 +93,11 @@ __device__ __forceinline__ TileEpi tile_epilogue_fetch(const ssrhip_gemv_args& a
 __device__ __forceinline__ void tile_epilogue_finish(const ssrhip_gemv_args& a, const TileEpi& e0, f4v acc, int hd) {
   if (e0.nvalid == 0) return;
   TileEpi e = e0;
+  const bool kv16 = e.kv_which && a.epi == SSRHIP_EPI_QKV_APPEND16;    // a K / V row of a cache of 2-byte entries: same element offset, half the bytes
   if (e.kv_which) {
     const size_t off = ((((size_t)e.kv_page * a.kv.n_layer + a.layer) * 2 + (e.kv_which - 1)) * a.kv.n_head + e.kv_cc / hd) * SSRHIP_PAGE + (e.kv_pos % SSRHIP_PAGE);
-    e.dst = a.kv.pool + off * a.kv.head_dim + (e.kv_cc % hd);
+    const size_t el = off * a.kv.head_dim + (e.kv_cc % hd);
+    e.dst = kv16 ? reinterpret_cast<float*>(reinterpret_cast<uint16_t*>(a.kv.pool) + el) : a.kv.pool + el;
   }
   float v[4] = {acc[0], acc[1], acc[2], acc[3]};
 #pragma unroll
@@ -101,6 +106,10 @@ __device__ __forceinline__ void tile_epilogue_finish(const ssrhip_gemv_args& a, 
     if (a.act == SSRHIP_ACT_RELU) v[j] = fmaxf(v[j], 0.f);
     else if (a.act == SSRHIP_ACT_GELU_ERF) v[j] = 0.5f * v[j] * (1.0f + erff(v[j] * 0.70710678118654752440f));
     v[j] = e.res[j] + v[j];                         // res == 0 unless EPI_RESIDUAL (same operand order as the fused add: y + v)
+  }
+  if (kv16) {     // N == 3K and K % 16 == 0: a K / V lane always holds four rows of one head, at an element offset that is a multiple of 4
+    *reinterpret_cast<uint2*>(e.dst) = bf16x4_rne(v[0], v[1], v[2], v[3]);
+    return;
   }
   if (e.nvalid == 4 && ((reinterpret_cast<size_t>(e.dst) & 15) == 0)) {
     *reinterpret_cast<float4*>(e.dst) = make_float4(v[0], v[1], v[2], v[3]);
@@ -325,12 +334,13 @@ inline int gemv_rows_check(const ssrhip_gemv_args* a, int b_lo, int b_hi, int ln
   SSR_REQUIRE(a->pro == SSRHIP_PRO_NONE || a->pro == SSRHIP_PRO_LAYERNORM,
               "ssrhip_gemv (B>4): the split-KV combine prologue is not fused; run ssrhip_attn_combine first");
   SSR_REQUIRE(a->x, "ssrhip_gemv: x is null");
-  SSR_REQUIRE(!a->y_tiled || (a->N % 4 == 0 && a->epi != SSRHIP_EPI_QKV_APPEND), "ssrhip_gemv: tiled y needs N %% 4 == 0 and is not available for the q output");
+  SSR_REQUIRE(!a->y_tiled || (a->N % 4 == 0 && !epi_appends(a->epi)), "ssrhip_gemv: tiled y needs N %% 4 == 0 and is not available for the q output");
   if (a->pro == SSRHIP_PRO_LAYERNORM) {
     SSR_REQUIRE(a->K <= ln_kmax, "ssrhip_gemv (B=%d): LayerNorm prologue needs K=%d <= %d", a->B, a->K, ln_kmax);
     SSR_REQUIRE(!a->ln_w && !a->ln_b, "ssrhip_gemv (B>4): LayerNorm gamma/beta must be folded into W/bias (ln_w == ln_b == NULL)");
   }
-  if (a->epi == SSRHIP_EPI_QKV_APPEND) {
+  SSR_REQUIRE(a->epi >= SSRHIP_EPI_STORE && a->epi <= SSRHIP_EPI_QKV_APPEND16, "ssrhip_gemv: unknown epilogue %d", a->epi);
+  if (epi_appends(a->epi)) {
     SSR_REQUIRE(a->N == 3 * a->K && a->groups == 1 && a->kv.pool && a->kv.table && a->kv_pos && a->kv.head_dim > 0 && a->kv.head_dim % 4 == 0,
                 "ssrhip_gemv: QKV epilogue needs N==3K and a kv cache");
   }

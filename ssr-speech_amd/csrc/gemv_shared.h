@@ -233,6 +233,7 @@ inline bool seg_plan(const ssrhip_gemv_args* a, int num_cu, bool combine_two_per
 
 // the contract of ssrhip_gemv / ssrhip_gemv_w16 for B in {1,2,4} rows, behind the callers' own null / N / K / groups / B tests
 inline int gemv_small_check(const ssrhip_gemv_args* a, const char* who) {
+  SSR_REQUIRE(a->epi != SSRHIP_EPI_QKV_APPEND16, "%s: the 2-byte KV append (EPI_QKV_APPEND16) exists for 5..32 rows only (B=%d)", who, a->B);
   SSR_REQUIRE(!a->x_tiled && !a->y_tiled && !a->w_tiled, "%s: the tiled activation / weight layouts are for 5..32 rows only", who);
   SSR_REQUIRE(a->pro != SSRHIP_PRO_ATTN_COMBINE || (a->kv.head_dim > 0 && a->K <= 2048 && a->B * (a->K / a->kv.head_dim) <= 256), "%s: combine prologue needs K <= 2048 and B*H <= 256", who);
   SSR_REQUIRE(a->K > 0 && a->K % 4 == 0 && a->K <= 8192, "%s: K=%d must be a multiple of 4, <= 8192", who, a->K);

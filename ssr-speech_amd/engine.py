@@ -155,6 +155,27 @@ def resolve_w16_stream(st: W16Stream, rows: int, weight_dtype: str, requested: O
     return True
 
 
+KV_DTYPES = ("fp32", "bf16")
+KV16_MAX_PAGES = 256          # pages per row the fused attention walk takes (csrc/attn.hip ATTN_ROWS_MAX_PAGES)
+
+
+def resolve_kv_dtype(rows: int, requested: Optional[str], model_default: str = "fp32", max_pages: Optional[int] = None) -> str:
+    """The entry type of the KV cache of an engine of `rows` rows. The bf16 cache exists for the 5..32-row step with at most
+    KV16_MAX_PAGES pages per row. requested "bf16" outside that: ValueError. requested None: `model_default`
+    (SSR_Speech.set_kv_dtype) where the engine can hold it, "fp32" otherwise — the 2-row paths keep fp32 K/V. Nothing else is read."""
+    for what, v in (("kv_dtype", requested), ("model default kv_dtype", model_default)):
+        if v is not None and v not in KV_DTYPES:
+            raise ValueError(f"{what} {v!r} not in {KV_DTYPES}")
+    fits = 5 <= rows <= MAX_ROWS and (max_pages is None or max_pages <= KV16_MAX_PAGES)
+    if requested is None:
+        return model_default if fits else "fp32"
+    if requested == "bf16" and not fits:
+        if not 5 <= rows <= MAX_ROWS:
+            raise ValueError(f"kv_dtype='bf16' exists for engines of 5..{MAX_ROWS} rows (this engine has {rows} rows)")
+        raise ValueError(f"kv_dtype='bf16' takes at most {KV16_MAX_PAGES} pages per row (this engine has {max_pages})")
+    return requested
+
+
 def resolve_prefill_planes(weight_dtype: str, requested: Optional[int], env) -> int:
     """How many bf16 planes per matrix does an arena of `weight_dtype` build for the prefill / score GEMMs? 0 = none (`env` has
     SSRHIP_PREFILL_SPLIT starting with '0': the fp32 chain, whatever else is asked), 3 = the exact split of an fp32 value, 1 = the value
@@ -586,7 +607,8 @@ class DecodeEngine:
 
     def __init__(self, arena: LMWeightsArena, n_utt: int, use_cfg: bool, max_seq: int, max_steps: int, debug_logits: bool = False,
                  pool_pages: Optional[int] = None, page_order: Optional[Sequence[int]] = None, pair_mode: int = 0,
-                 stream_w16: Optional[bool] = None, stream_wt16: Optional[bool] = None, stream_wt32: Optional[bool] = None):
+                 stream_w16: Optional[bool] = None, stream_wt16: Optional[bool] = None, stream_wt32: Optional[bool] = None,
+                 kv_dtype: Optional[str] = None):
         """max_seq: longest sequence (text + audio positions) any ONE row may reach; pool_pages: physical KV pages shared by all
         rows (default rows x pages-per-row, the no-sharing worst case; a batch of short and long utterances needs only the sum
         of their own page counts). pair_mode (2-row engines; include/ssrhip.h ssrhip_lm_buffers): 0 = pair launches if this engine
@@ -596,7 +618,10 @@ class DecodeEngine:
         matrix-core step (ssrhip_lm_set_wt16: SSRHIP_WT16_INDEX copies beside the fp32 streaming-order copies, which stay the fallback);
         None = on when the arena is bf16, the engine has 5..16 rows and `SSRHIP_GEMVM_W16` (read here; unset = WT16_DEFAULT) does not
         start with '0'. stream_wt32: the same for the 17..32-row two-panel step (ssrhip_lm_set_wt32, the same SSRHIP_WT16_INDEX copies); None =
-        on when the arena is bf16, the engine has 17..32 rows and `SSRHIP_GEMVM_W16` (unset = WT32_DEFAULT) does not start with '0'."""
+        on when the arena is bf16, the engine has 17..32 rows and `SSRHIP_GEMVM_W16` (unset = WT32_DEFAULT) does not start with '0'.
+        kv_dtype "bf16" (5..32 rows, at most KV16_MAX_PAGES pages per row; ValueError otherwise): the paged pool holds 2-byte entries —
+        every K / V value rounded to bf16 by whichever path writes it (the step's append, every prefill), widened exactly by every attention;
+        q, scores, softmax and outputs stay fp32 (include/ssrhip.h ssrhip_lm_set_kv16). None = "fp32". Independent of the weight stream."""
         self.lib = _lib.lib()
         self.a = arena
         dev = arena.device
@@ -613,6 +638,7 @@ class DecodeEngine:
         self._stream = next((st for st in W16_STREAMS if getattr(self, "stream_" + st.name)), None)
         self.max_pages = (max_seq + PAGE - 1) // PAGE
         self.max_seq = self.max_pages * PAGE
+        self.kv_dtype = resolve_kv_dtype(self.B, kv_dtype, "fp32", self.max_pages)
         arena.ensure_positions(self.max_seq)      # every text / audio position of a row is < its sequence capacity
         if self.B > 4:
             arena.ensure_streaming_copies()       # the matrix-core GEMV streams W in its own order
@@ -627,7 +653,8 @@ class DecodeEngine:
         n_pages = self.B * self.max_pages if pool_pages is None else int(pool_pages)
         self.pages = PagePool(n_pages, page_order)
         self.scratch_page = n_pages              # one extra page: where the rows of a FINISHED utterance keep (harmlessly) writing
-        self.kv_pool = torch.empty((n_pages + 1) * L * 2 * H * PAGE * self.hd, **f32)
+        self.kv_pool = torch.empty((n_pages + 1) * L * 2 * H * PAGE * self.hd, device=dev,
+                                   dtype=torch.bfloat16 if self.kv_dtype == "bf16" else torch.float32)
         self.page_table = torch.full((self.B, self.max_pages), self.scratch_page, **i32)
         self._table_host = np.full((self.B, self.max_pages), self.scratch_page, dtype=np.int32)
         self._row_pages: List[List[int]] = [[] for _ in range(self.B)]
@@ -708,6 +735,8 @@ class DecodeEngine:
         if self._stream is not None:              # before the first step is enqueued or captured; stream_w16 gives the pairing slot back
             rec, setter = self.a._packed_struct(self._stream.order), "ssrhip_lm_set_" + self._stream.name
             _lib.check(getattr(self.lib, setter)(ctx, C.byref(rec)), setter)
+        if self.kv_dtype == "bf16":               # the pool's entry type travels with the pool (also for the two-phase admission's prefill)
+            _lib.check(self.lib.ssrhip_lm_set_kv16(ctx, 1), "ssrhip_lm_set_kv16")
         if self.prefill_planes == 1:              # the count travels with the arena's buffers (also for the two-phase admission's prefill)
             _lib.check(self.lib.ssrhip_lm_set_prefill_w1(ctx, 1), "ssrhip_lm_set_prefill_w1")
         why = C.create_string_buffer(256)
@@ -716,6 +745,17 @@ class DecodeEngine:
 
     def _launches_per_step(self, name: str) -> int:
         return 0 if self._ctx is None else int(getattr(self.lib, f"ssrhip_lm_{name}_launches")(self._ctx))
+
+    @property
+    def kv_pool_bytes(self) -> int:
+        """Bytes of the paged KV pool this engine holds (half as many with kv_dtype="bf16")."""
+        return self.kv_pool.numel() * self.kv_pool.element_size()
+
+    @property
+    def kv16_launches_per_step(self) -> int:
+        """Attention launches of the last enqueued decode step that read the bf16 KV cache (the layer count for a kv_dtype="bf16" engine,
+        0 otherwise)."""
+        return 0 if self._ctx is None else int(self.lib.ssrhip_lm_kv16_launches(self._ctx))
 
     @property
     def w16_launches_per_step(self) -> int:

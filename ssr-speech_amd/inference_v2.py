@@ -56,6 +56,9 @@ EXTRA_FLAGS = [
     ("--weight_dtype", dict(type=str, choices=["fp32", "bf16"], default="fp32",
                             help="bf16: round the decoder's matrices once to bf16 and stream them as 2-byte weights in the decode step "
                                  "(SSR_Speech.set_weight_dtype); fp32 (default): the checkpoint's weights as they are")),
+    ("--kv_dtype", dict(type=str, choices=["fp32", "bf16"], default="fp32",
+                        help="bf16: decode engines of 5..32 rows (batched synthesis) keep their KV cache in 2-byte bf16 entries "
+                             "(SSR_Speech.set_kv_dtype); fp32 (default): the cache as it is")),
     ("--prompt_end", dict(type=float, default=None, help="--tts: cut the prompt audio at this time in seconds (default --prompt_length)")),
     ("--phoneme_ids", dict(type=str, default=None, help="comma separated phoneme ids of the target transcript (skips espeak)")),
     ("--prompt_phoneme_ids", dict(type=str, default=None, help="comma separated phoneme ids of the prompt transcript")),
@@ -228,6 +231,7 @@ def main(argv=None):
     model = SSR_Speech(ckpt["config"])
     model.load_state_dict(ckpt["model"])
     model.set_weight_dtype(args.weight_dtype)
+    model.set_kv_dtype(args.kv_dtype)
     config = vars(model.args)
     phn2num = ckpt["phn2num"]
     model.to(device)

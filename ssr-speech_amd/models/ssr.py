@@ -23,7 +23,8 @@ import torch.nn as nn
 from .. import _lib
 from .. import layout as LY
 from .. import score as SC
-from ..engine import DEFAULT_GROUP_ROWS, MAX_ROWS, WEIGHT_DTYPES, DecodeEngine, DecodeKnobs, LMWeightsArena, TorchCpuNoiseFeed
+from ..engine import (DEFAULT_GROUP_ROWS, KV_DTYPES, MAX_ROWS, WEIGHT_DTYPES, DecodeEngine, DecodeKnobs, LMWeightsArena, TorchCpuNoiseFeed,
+                      resolve_kv_dtype)
 from ..weights import lm_param_specs
 
 
@@ -114,6 +115,7 @@ class SSR_Speech(nn.Module):
         self._arena: Optional[LMWeightsArena] = None
         self._engines: Dict[tuple, DecodeEngine] = {}
         self._weight_dtype = "fp32"
+        self._kv_dtype = "fp32"
         self.debug_logits = False          # tests: keep the per-step post-edit logits
         self.page_order = None             # tests: permutation deciding which physical KV pages the allocator hands out first
         self.last_run: dict = {}
@@ -156,6 +158,24 @@ class SSR_Speech(nn.Module):
             self._weight_dtype = weight_dtype
             self._invalidate()
 
+    @property
+    def kv_dtype(self) -> str:
+        return self._kv_dtype
+
+    def set_kv_dtype(self, kv_dtype: str) -> None:
+        """"bf16": decode engines of 5..32 rows — `inference_batch`, `dp.generate`, `dp.synthesize`, `run_queue` with 3 or more utterances
+        under CFG — keep their KV cache in 2-byte bf16 entries (engine.DecodeEngine kv_dtype): half the cache memory and half the bytes the
+        attention reads; K / V are rounded once when written, everything else stays fp32. The 2-row paths (`inference`,
+        `inference_stream`) and `score` keep fp32 K / V. "fp32" (the default) restores today's numbers bit for bit. Independent of
+        `set_weight_dtype`. Drops the cached engines."""
+        if kv_dtype not in KV_DTYPES:
+            raise ValueError(f"kv_dtype {kv_dtype!r} not in {KV_DTYPES}")
+        if kv_dtype != self._kv_dtype:
+            self._kv_dtype = kv_dtype
+            for e in self._engines.values():
+                e.close()
+            self._engines = {}
+
     def forward(self, batch):
         raise NotImplementedError("SSR_Speech.forward (training loss, reference models/ssr.py:280-379) is outside the "
                                   "scope of ssr_speech_amd: only the inference hot path is implemented. SSR_Speech.score(batch) "
@@ -196,7 +216,8 @@ class SSR_Speech(nn.Module):
         order = None
         if self.page_order is not None:          # tests: a caller-chosen hand-out order of the physical pages
             order = [p for p in self.page_order if p < pool] if len(self.page_order) >= pool else None
-        eng = DecodeEngine(self._arena, n_utt, use_cfg, cap_seq, cap_steps, debug_logits=self.debug_logits, pool_pages=pool, page_order=order)
+        eng = DecodeEngine(self._arena, n_utt, use_cfg, cap_seq, cap_steps, debug_logits=self.debug_logits, pool_pages=pool, page_order=order,
+                           kv_dtype=resolve_kv_dtype(rows, None, self._kv_dtype, cap_seq // 128))
         self._engines[key] = eng
         return eng
 

@@ -17,6 +17,9 @@ The same at 5..16 rows (DESIGN.md Part I.11; `SSRHIP_GEMVM_W16` is the switch of
   python tools/decode_ab.py --utts 8 --greedy --warmup 180 --steps 100 fp32: bf16_masters:weight_dtype=bf16,SSRHIP_GEMVM_W16=0 bf16_wt16:weight_dtype=bf16,SSRHIP_GEMVM_W16=1
 and at 17..32 rows (DESIGN.md Part I.12; the same switch, `wt32 launches` the counter):
   python tools/decode_ab.py --utts 16 --greedy --warmup 180 --steps 100 fp32: bf16_masters:weight_dtype=bf16,SSRHIP_GEMVM_W16=0 bf16_wt32:weight_dtype=bf16,SSRHIP_GEMVM_W16=1
+A lower-case `kv_dtype=bf16` is not an environment variable either: that variant's engine keeps its KV cache in 2-byte entries (DESIGN.md
+Part I.14; 5..32 rows, `kv16 launches` its counter), independent of `weight_dtype`:
+  python tools/decode_ab.py --utts 16 --greedy --warmup 180 --steps 100 fp32: kv16:kv_dtype=bf16 bf16_wt:weight_dtype=bf16,SSRHIP_GEMVM_W16=1 bf16_wt_kv16:weight_dtype=bf16,SSRHIP_GEMVM_W16=1,kv_dtype=bf16
 """
 import argparse
 import dataclasses
@@ -53,6 +56,7 @@ for v in a.variants:
     utts_of[name] = int(nu) if nu else a.utts
     variants.append((name, dict(kv.split("=", 1) for kv in kn.split(",") if kv)))
 dtype_of = {name: d.pop("weight_dtype", "fp32") for name, d in variants}
+kv_of = {name: d.pop("kv_dtype", "fp32") for name, d in variants}
 all_knobs = sorted({k for _, d in variants for k in d})
 
 dev = torch.device("cuda", 0)
@@ -79,7 +83,8 @@ for rep in range(a.reps):
             os.environ.pop(k, None)
         os.environ.update(knobs)
         U = utts_of[name]
-        eng = DecodeEngine(arenas[dtype_of[name]], U, True, ((L + T0 + total + 8 + 1023) // 1024) * 1024, ((total + 255) // 256) * 256)
+        eng = DecodeEngine(arenas[dtype_of[name]], U, True, ((L + T0 + total + 8 + 1023) // 1024) * 1024, ((total + 255) // 256) * 256,
+                           kv_dtype=kv_of[name])
         eng.start(text_rows[:2 * U], [cated] * U, [dataclasses.replace(kn, seed=2024 + u) for u in range(U)], noise=None)
         torch.cuda.synchronize()
         eng.decode(a.warmup)
@@ -93,6 +98,7 @@ for rep in range(a.reps):
         r = res[name]
         for st in W16_STREAMS:
             r[st.name] = getattr(eng, st.name + "_launches_per_step")
+        r["kv16"] = eng.kv16_launches_per_step
         r["ms"].append(ms)
         r["gemv"].append(eng.time_category("gemv", 50)[0])
         r["attn"].append(eng.time_category("attn", 50)[0])
@@ -114,4 +120,4 @@ for name, knobs in variants:
     print(f"{name:14s} {U:2d} utts x CFG = {2 * U:2d} rows  tok/s {4 * U / (statistics.median(r['ms']) * 1e-3):9.1f}  "
           f"ms/step min {min(r['ms']):.4f} med {statistics.median(r['ms']):.4f}  all {' '.join(f'{v:.4f}' for v in r['ms'])} | "
           f"gemv {min(r['gemv']):.3f} x {r['launches']['gemv']} attn {min(r['attn']):.3f} x {r['launches']['attn']} "
-          f"sample {min(r['sample']):.3f} x {r['launches']['sample']} us{same}   [{dtype_of[name]}, {' + '.join(f'{r[st.name]} {st.name}' for st in W16_STREAMS)} launches; {' '.join(f'{k}={v}' for k, v in knobs.items()) or 'defaults'}]")
+          f"sample {min(r['sample']):.3f} x {r['launches']['sample']} us{same}   [{dtype_of[name]}, kv {kv_of[name]}, {' + '.join(f'{r[st.name]} {st.name}' for st in W16_STREAMS)} + {r['kv16']} kv16 launches; {' '.join(f'{k}={v}' for k, v in knobs.items()) or 'defaults'}]")

@@ -10,6 +10,10 @@ the arena and the engine are rebuilt for every arm of every round (the switch is
   python tools/dp64_group_ab.py --wt16 --reps 2 --out profiles/wt16_dp64_group8.json
 `--wt32` is the same comparison at group 16 = 32 rows (the two-panel step's bf16 stream, DESIGN.md Part I.12; identical tokens asserted):
   python tools/dp64_group_ab.py --wt32 --reps 2 --out profiles/wt32_dp64_group16.json
+`--kv_dtype bf16` compares, at every grouping of --groups, the model with its fp32 KV cache against `set_kv_dtype("bf16")` (DESIGN.md Part
+I.14), the arms alternating within a round; per arm the decode wall times, their median and spread (max - min), and whether the two arms
+chose the same tokens (not expected: the cache type changes the numerics):
+  python tools/dp64_group_ab.py --kv_dtype bf16 --reps 3 --out profiles/kv16_dp64.json
 """
 import argparse
 import json
@@ -33,6 +37,7 @@ ap.add_argument("--groups", default="8,16")
 ap.add_argument("--out", default=None)
 ap.add_argument("--wt16", action="store_true", help="bf16 model, group 8: fp32 masters against the packed bf16 stream of the 16-row step")
 ap.add_argument("--wt32", action="store_true", help="bf16 model, group 16: fp32 masters against the packed bf16 stream of the 32-row step")
+ap.add_argument("--kv_dtype", choices=["fp32", "bf16"], default="fp32", help="bf16: at every grouping, the fp32 KV cache against the bf16 KV cache")
 a = ap.parse_args()
 
 dev = torch.device("cuda", 0)
@@ -79,6 +84,45 @@ if a.wt16 or a.wt32:
                      kind + "_launches_per_step": res[name]["launches"]}
     out["tokens_identical"] = all(torch.equal(x, y) for x, y in zip(res["bf16_" + kind]["tokens"], ref))
     assert out["tokens_identical"], "the two bf16 arms must choose the same tokens"
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    sys.exit(0)
+
+if a.kv_dtype == "bf16":
+    import statistics
+    arms = ("kv_fp32", "kv_bf16")
+    res = {(g, arm): {"decode_ms": [], "tokens": None, "launches": 0} for g in groups for arm in arms}
+    for rep in range(a.reps):
+        for g in groups:
+            for arm in arms:
+                model.set_kv_dtype(arm[3:])             # drops the engines: the next call builds one with this cache type
+                dp.generate(model, utts[:2 * g], seed=0, group=g, **kw)      # untimed: engine, graph capture
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                toks, _ = dp.generate(model, utts, seed=0, group=g, **kw)
+                torch.cuda.synchronize()
+                r = res[(g, arm)]
+                r["decode_ms"].append(1000 * (time.perf_counter() - t0))
+                eng = next(iter(model._engines.values()))
+                r["launches"], r["kv_pool_bytes"] = eng.kv16_launches_per_step, eng.kv_pool_bytes
+                if r["tokens"] is None:
+                    r["tokens"] = [t.cpu() for t in toks]
+    out = {"workload": "bench.py dp64 input on one GPU through dp.generate (decode only, no codec), fp32 weights", "reps": a.reps}
+    for g in groups:
+        o = {"rows_per_engine": 2 * g}
+        for arm in arms:
+            r = res[(g, arm)]
+            n_new = sum(int(t.shape[-1]) - 150 for t in r["tokens"])
+            med = statistics.median(r["decode_ms"])
+            o[arm] = {"decode_ms": [round(v, 1) for v in r["decode_ms"]], "median_ms": round(med, 1), "spread_ms": round(max(r["decode_ms"]) - min(r["decode_ms"]), 1),
+                      "new_frames_total": n_new, "codec_tokens_per_s": round(4 * n_new / (med * 1e-3), 1), "kv16_launches_per_step": r["launches"],
+                      "kv_pool_bytes": r["kv_pool_bytes"]}
+        o["tokens_identical"] = all(torch.equal(x, y) for x, y in zip(res[(g, "kv_fp32")]["tokens"], res[(g, "kv_bf16")]["tokens"]))
+        out[f"group{g}"] = o
     line = json.dumps(out)
     print(line)
     if a.out:
