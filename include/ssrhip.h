@@ -225,6 +225,22 @@ int ssrhip_attn_prefill(const ssrhip_attn_args* a, const int32_t* seq_start, int
 int ssrhip_attn_rows_kv16(const ssrhip_attn_args* a, float* out /* [R][n_head*head_dim] */, ssrhip_stream_t stream);
 int ssrhip_attn_prefill_kv16(const ssrhip_attn_args* a, const int32_t* seq_start, int32_t n_seq, int32_t max_len, float* out,
                              ssrhip_stream_t stream);
+/* ssrhip_attn_rows for rows that SHARE their first pages (the samples of one utterance, opt-in: ssrhip_lm_set_prompt_groups; fp32 entries
+ * only). chunk_head / n_shared are DEVICE arrays of R ints: chunk_head[r] = the lowest row of r's chunk, a chunk being at most
+ * ssrhip_attn_group_members() rows whose first n_shared[head] table entries name the same physical pages (any rows, in any mix of lengths;
+ * the caller's contract: rows past that many naming one head are not computed). One workgroup per (head, chunk) loads K/V of a shared page
+ * once and folds it into every member's own softmax state with that member's q, then walks each member's own pages. The grid is
+ * (n_head, R) whatever the arrays hold — a captured launch keeps working when the arrays are rewritten — and workgroups of non-head rows
+ * exit at once. Identity arrays (chunk_head[r] = r, n_shared[r] = 0) are ssrhip_attn_rows. Every row's result equals ssrhip_attn_rows'
+ * on the same (aliased) table bit for bit: sharing changes which workgroup computes a row, never the order of its arithmetic.
+ * SSRHIP_ATTN_GROUP_MEMBERS = 2 | 4 | 8 (read at every launch; unset or anything else: 2) is the chunk size the kernel is built for. */
+int ssrhip_attn_rows_group(const ssrhip_attn_args* a, const int32_t* chunk_head, const int32_t* n_shared,
+                           float* out /* [R][n_head*head_dim] */, ssrhip_stream_t stream);
+int ssrhip_attn_group_members(void);
+/* the same launch with the chunk size as an argument (2, 4 or 8; anything else is a contract error): for a caller that cut its chunks
+ * once and must not depend on what the environment says at a later launch (the decode engine) */
+int ssrhip_attn_rows_group_m(const ssrhip_attn_args* a, const int32_t* chunk_head, const int32_t* n_shared, int32_t members,
+                             float* out /* [R][n_head*head_dim] */, ssrhip_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Token embedding + sinusoidal position: replaces embed_y (models/ssr.py:191-198, :655-660, :757-761),
@@ -551,6 +567,19 @@ int ssrhip_lm_set_prefill_w1(ssrhip_lm* lm, int32_t on);
 int ssrhip_lm_set_kv16(ssrhip_lm* lm, int32_t on);
 /* how many attention launches of the last enqueued (or captured) decode step ran ssrhip_attn_rows_kv16 (n_layer for a kv16 engine, else 0) */
 int ssrhip_lm_kv16_launches(const ssrhip_lm* lm);
+/* Prompt sharing (opt-in, 5..32-row fp32-cache engines, at most 256 pages per row): two DEVICE arrays of B ints the caller owns and
+ * rewrites between steps (see ssrhip_attn_rows_group), or NULL, NULL for off. Call it before the first ssrhip_lm_decode (the captured step
+ * keeps the pointers). With it set every layer's attention of the decode step is ssrhip_attn_rows_group (also at 5..11 rows x 16 heads,
+ * where the unshared step takes the split kernels; SSRHIP_ATTN_SPLIT is ignored) — the rule ssrhip_lm_set_kv16 uses. The prefill is
+ * untouched: the caller prefills the rows it wants and aliases the others' table entries. */
+int ssrhip_lm_set_prompt_groups(ssrhip_lm* lm, const int32_t* chunk_head, const int32_t* n_shared);
+/* The chunk size the caller cuts its chunks for (2, 4 or 8): every grouped attention launch of this engine's step is built for it, whatever
+ * SSRHIP_ATTN_GROUP_MEMBERS says when a step is enqueued or captured. Without this call it is ssrhip_attn_group_members() at the time of
+ * ssrhip_lm_set_prompt_groups. Refused after capture. ssrhip_lm_group_members reads it back (0 = the engine does not share). */
+int ssrhip_lm_set_group_members(ssrhip_lm* lm, int32_t members);
+int ssrhip_lm_group_members(const ssrhip_lm* lm);
+/* how many attention launches of the last enqueued (or captured) decode step ran ssrhip_attn_rows_group (n_layer with groups set, else 0) */
+int ssrhip_lm_group_launches(const ssrhip_lm* lm);
 /* enqueue `n_steps` decode steps (graph replays when use_graph!=0) */
 int ssrhip_lm_decode(ssrhip_lm* lm, int32_t n_steps, int32_t use_graph, ssrhip_stream_t stream);
 /* prefill R rows ([text || audio] of every sequence, flattened): fills the cache for all layers.

@@ -247,6 +247,83 @@ __global__ __launch_bounds__(64) void attn_combine_kernel(const ssrhip_attn_args
 // Loads are never predicated (see above): keys past the row's length re-read key 0 of the last page and are masked to -inf.
 constexpr int ATTN_ROWS_MAX_PAGES = 256;       // 32,768 positions per row
 
+// The page walk's pieces, shared by attn_rows_kernel and attn_rows_group_kernel (which keeps one (Q, LEN, M, L, O) per member row).
+// They use the enclosing kernel's a, pool, page_stride, v_off, wave, sub, c4, kk, vv and its constants.
+#define ATTN_ISSUE_AT(BUF, PG, PID, NPAGES, LEN)                                                    \
+  {                                                                                                   \
+    const int pg_ = min((PG), (NPAGES) - 1);                                                            \
+    const int pb_ = pg_ >> 6;                                                                         \
+    const int pv_ = pb_ == 0 ? PID[0] : (pb_ == 1 ? PID[1] : (pb_ == 2 ? PID[2] : PID[3]));           \
+    const kv_elem* kp_ = pool + (size_t)__builtin_amdgcn_readlane(pv_, pg_ & 63) * page_stride;       \
+    const int jmax_ = ((PG) < (NPAGES)) ? min((LEN) - pg_ * SSRHIP_PAGE, SSRHIP_PAGE) - 1 : 0;            \
+    _Pragma("unroll") for (int i = 0; i < NI; ++i) {                                                  \
+      const int j_ = min(wave * KPW + i * KPI + sub, jmax_);                                          \
+      kk[BUF][i] = ld_kv(kp_ + (size_t)j_ * HD + c4);                                                  \
+    }                                                                                                 \
+    _Pragma("unroll") for (int i = 0; i < NI; ++i) {                                                  \
+      const int j_ = min(wave * KPW + i * KPI + sub, jmax_);                                          \
+      vv[BUF][i] = ld_kv(kp_ + v_off + (size_t)j_ * HD + c4);                                          \
+    }                                                                                                 \
+  }
+#define ATTN_FOLD_AT(BUF, PG, Q, LEN, M, L, O)                                                      \
+  {                                                                                                   \
+    float s_[NI];                                                                                     \
+    _Pragma("unroll") for (int i = 0; i < NI; ++i) s_[i] = dot4(Q, kv_f4(kk[BUF][i]), 0.f);           \
+    _Pragma("unroll") for (int i = 0; i < NI; ++i) s_[i] = (LPK == 32) ? half32_sum(s_[i]) : row16_sum(s_[i]); \
+    float mloc_ = -INFINITY;                                                                          \
+    _Pragma("unroll") for (int i = 0; i < NI; ++i) {                                                  \
+      const int pos_ = (PG) * SSRHIP_PAGE + wave * KPW + i * KPI + sub;                               \
+      s_[i] = (pos_ < (LEN)) ? s_[i] * a.scale : -INFINITY;                                             \
+      mloc_ = fmaxf(mloc_, s_[i]);                                                                    \
+    }                                                                                                 \
+    if (LPK == 16) mloc_ = fmaxf(mloc_, xor16_f(mloc_));                                              \
+    mloc_ = fmaxf(mloc_, xor32_f(mloc_));                                                             \
+    const float mnew_ = fmaxf(M, mloc_);                                                              \
+    if (mnew_ > -INFINITY) {                                                                          \
+      const float al_ = (M > -INFINITY) ? expf(M - mnew_) : 0.f;                                      \
+      L *= al_; O.x *= al_; O.y *= al_; O.z *= al_; O.w *= al_;                                       \
+      _Pragma("unroll") for (int i = 0; i < NI; ++i) {                                                \
+        const float p_ = expf(s_[i] - mnew_);                                                         \
+        L += p_;                                                                                      \
+        O.x = fmaf(p_, kv_f4(vv[BUF][i]).x, O.x); O.y = fmaf(p_, kv_f4(vv[BUF][i]).y, O.y);           \
+        O.z = fmaf(p_, kv_f4(vv[BUF][i]).z, O.z); O.w = fmaf(p_, kv_f4(vv[BUF][i]).w, O.w);           \
+      }                                                                                               \
+      M = mnew_;                                                                                      \
+    }                                                                                                 \
+  }
+
+// the tail of a (row, head): the KPI key-row groups of a wave share m, so their (l, o) simply add; then the 8 waves' states go through LDS
+#define ATTN_WAVE_SUM(L, O)                                                                           \
+  {                                                                                                   \
+    if (LPK == 16) {                                                                                  \
+      L += xor16_f(L);                                                                                \
+      O.x += xor16_f(O.x); O.y += xor16_f(O.y); O.z += xor16_f(O.z); O.w += xor16_f(O.w);             \
+    }                                                                                                 \
+    L += xor32_f(L);                                                                                  \
+    O.x += xor32_f(O.x); O.y += xor32_f(O.y); O.z += xor32_f(O.z); O.w += xor32_f(O.w);               \
+  }
+// merge of the 8 waves' states in SM by LPK lanes (fixed wave order: deterministic), normalise, store row ROW
+#define ATTN_MERGE_STORE(SM, ROW)                                                                     \
+  {                                                                                                   \
+    float M = -INFINITY;                                                                              \
+    _Pragma("unroll") for (int w = 0; w < NW; ++w) M = fmaxf(M, SM[w][HD]);                           \
+    float L = 0.f;                                                                                    \
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);                                                     \
+    _Pragma("unroll") for (int w = 0; w < NW; ++w) {                                                  \
+      const float mw = SM[w][HD];                                                                     \
+      const float f = (mw > -INFINITY) ? expf(mw - M) : 0.f;                                          \
+      L = fmaf(f, SM[w][HD + 1], L);                                                                  \
+      acc.x = fmaf(f, SM[w][c4 + 0], acc.x);                                                          \
+      acc.y = fmaf(f, SM[w][c4 + 1], acc.y);                                                          \
+      acc.z = fmaf(f, SM[w][c4 + 2], acc.z);                                                          \
+      acc.w = fmaf(f, SM[w][c4 + 3], acc.w);                                                          \
+    }                                                                                                 \
+    const float inv = 1.0f / L;                                                                       \
+    const int e = h * HD + c4;                                                                        \
+    float* dst = a.out_tiled ? out + SSRHIP_TILED_P((ROW), e, H * HD) : out + (size_t)(ROW) * H * HD + e; \
+    *reinterpret_cast<float4*>(dst) = make_float4(acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv); \
+  }
+
 // KV16: a.kv.pool holds 2-byte entries (same element offsets); K/V of a page then take half the registers, so DEPTH = 4 pages in flight fit
 // where the fp32 kernel holds 2. The folds run in page order whatever DEPTH is (a fold of a page past the row's last is masked: no change).
 template <int HD, bool KV16 = false, int DEPTH = 2>
@@ -279,49 +356,8 @@ __global__ __launch_bounds__(512) void attn_rows_kernel(const ssrhip_attn_args a
   float m = -INFINITY, l = 0.f;
   float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
 
-#define ATTN_ISSUE(BUF, PG)                                                                           \
-  {                                                                                                   \
-    const int pg_ = min((PG), npages - 1);                                                            \
-    const int pb_ = pg_ >> 6;                                                                         \
-    const int pv_ = pb_ == 0 ? pid[0] : (pb_ == 1 ? pid[1] : (pb_ == 2 ? pid[2] : pid[3]));           \
-    const kv_elem* kp_ = pool + (size_t)__builtin_amdgcn_readlane(pv_, pg_ & 63) * page_stride;       \
-    const int jmax_ = ((PG) < npages) ? min(len - pg_ * SSRHIP_PAGE, SSRHIP_PAGE) - 1 : 0;            \
-    _Pragma("unroll") for (int i = 0; i < NI; ++i) {                                                  \
-      const int j_ = min(wave * KPW + i * KPI + sub, jmax_);                                          \
-      kk[BUF][i] = ld_kv(kp_ + (size_t)j_ * HD + c4);                                                  \
-    }                                                                                                 \
-    _Pragma("unroll") for (int i = 0; i < NI; ++i) {                                                  \
-      const int j_ = min(wave * KPW + i * KPI + sub, jmax_);                                          \
-      vv[BUF][i] = ld_kv(kp_ + v_off + (size_t)j_ * HD + c4);                                          \
-    }                                                                                                 \
-  }
-#define ATTN_FOLD(BUF, PG)                                                                            \
-  {                                                                                                   \
-    float s_[NI];                                                                                     \
-    _Pragma("unroll") for (int i = 0; i < NI; ++i) s_[i] = dot4(q, kv_f4(kk[BUF][i]), 0.f);           \
-    _Pragma("unroll") for (int i = 0; i < NI; ++i) s_[i] = (LPK == 32) ? half32_sum(s_[i]) : row16_sum(s_[i]); \
-    float mloc_ = -INFINITY;                                                                          \
-    _Pragma("unroll") for (int i = 0; i < NI; ++i) {                                                  \
-      const int pos_ = (PG) * SSRHIP_PAGE + wave * KPW + i * KPI + sub;                               \
-      s_[i] = (pos_ < len) ? s_[i] * a.scale : -INFINITY;                                             \
-      mloc_ = fmaxf(mloc_, s_[i]);                                                                    \
-    }                                                                                                 \
-    if (LPK == 16) mloc_ = fmaxf(mloc_, xor16_f(mloc_));                                              \
-    mloc_ = fmaxf(mloc_, xor32_f(mloc_));                                                             \
-    const float mnew_ = fmaxf(m, mloc_);                                                              \
-    if (mnew_ > -INFINITY) {                                                                          \
-      const float al_ = (m > -INFINITY) ? expf(m - mnew_) : 0.f;                                      \
-      l *= al_; o.x *= al_; o.y *= al_; o.z *= al_; o.w *= al_;                                       \
-      _Pragma("unroll") for (int i = 0; i < NI; ++i) {                                                \
-        const float p_ = expf(s_[i] - mnew_);                                                         \
-        l += p_;                                                                                      \
-        o.x = fmaf(p_, kv_f4(vv[BUF][i]).x, o.x); o.y = fmaf(p_, kv_f4(vv[BUF][i]).y, o.y);           \
-        o.z = fmaf(p_, kv_f4(vv[BUF][i]).z, o.z); o.w = fmaf(p_, kv_f4(vv[BUF][i]).w, o.w);           \
-      }                                                                                               \
-      m = mnew_;                                                                                      \
-    }                                                                                                 \
-  }
-
+#define ATTN_ISSUE(BUF, PG) ATTN_ISSUE_AT(BUF, PG, pid, npages, len)
+#define ATTN_FOLD(BUF, PG) ATTN_FOLD_AT(BUF, PG, q, len, m, l, o)
   if constexpr (DEPTH == 2) {
     ATTN_ISSUE(0, 0)
     for (int pg = 0; pg < npages; pg += 2) {
@@ -347,37 +383,125 @@ __global__ __launch_bounds__(512) void attn_rows_kernel(const ssrhip_attn_args a
   }
 #undef ATTN_ISSUE
 #undef ATTN_FOLD
-  // the KPI key-row groups of the wave share m: their (l, o) simply add
-  if (LPK == 16) {
-    l += xor16_f(l);
-    o.x += xor16_f(o.x); o.y += xor16_f(o.y); o.z += xor16_f(o.z); o.w += xor16_f(o.w);
-  }
-  l += xor32_f(l);
-  o.x += xor32_f(o.x); o.y += xor32_f(o.y); o.z += xor32_f(o.z); o.w += xor32_f(o.w);
+  ATTN_WAVE_SUM(l, o)
   if (lane < LPK) *reinterpret_cast<float4*>(&sm[wave][c4]) = o;
   if (lane == 0) { sm[wave][HD] = m; sm[wave][HD + 1] = l; }
   __syncthreads();
-  if (threadIdx.x < LPK) {
-    float M = -INFINITY;
+  if (threadIdx.x < LPK) ATTN_MERGE_STORE(sm, r)
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The same walk for rows that SHARE their first pages (the samples of one utterance: equal text and prompt audio, so equal prompt
+// K/V, DESIGN.md Part I.15). One 8-wave workgroup per (head, chunk of up to MEMBERS rows whose first n_shared table entries name the
+// same pages): K/V of a shared page are loaded once and folded into every member's own (m, l, o) with that member's q; then the
+// workgroup walks each member's own pages (entries n_shared.. of ITS table row), and merges and stores per member. Every fold, the
+// wave sum, the merge and the store are the macros attn_rows_kernel expands, on the same keys per wave in the same page order: a
+// member's result equals attn_rows_kernel's on the same (aliased) table bit for bit — sharing moves a row to another workgroup, never
+// reorders its arithmetic. (A fold of a page past a row's last is an exact no-op in both kernels: every key masked, p == 0.)
+// chunk_head[r] = the lowest row of r's chunk; the grid is (n_head, R) whatever the arrays hold (a captured graph keeps its grid): a
+// workgroup whose row is not a head exits at once, a head finds its members with one ballot over chunk_head and a scalar bit scan.
+// Members may be any rows (conditional rows are 0, 2, 4, ...), of different lengths and numbers of own pages. n_shared is read at the
+// head and clamped to the FULL pages every member has (row_len / SSRHIP_PAGE), so a shared page is never a member's partial page.
+// Rows beyond the first MEMBERS that name one head are not computed: the host's contract (engine.py plan_prompt_sharing).
+template <int HD, int MEMBERS>
+__global__ __launch_bounds__(512) void attn_rows_group_kernel(const ssrhip_attn_args a, const int32_t* __restrict__ chunk_head,
+                                                              const int32_t* __restrict__ n_shared, float* out) {
+  typedef float kv_elem;
+  typedef float4 kv_vec;
+  constexpr int LPK = HD / 4, KPI = 64 / LPK, NW = 8, KPW = SSRHIP_PAGE / NW, NI = KPW / KPI, DEPTH = 2;
+  __shared__ __attribute__((aligned(16))) float sm[MEMBERS][NW][HD + 4];
+  const int h = blockIdx.x, r0 = blockIdx.y;
+  if (__builtin_amdgcn_readfirstlane(chunk_head[r0]) != r0) return;   // uniform: not a chunk head
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int sub = lane / LPK, c4 = (lane % LPK) * 4;
+  const int H = a.kv.n_head;
+  // the members, in ascending row order (the head is the lowest): lane i looks at row b0 + i, the ballot is scanned bit by bit
+  int mem[MEMBERS];
 #pragma unroll
-    for (int w = 0; w < NW; ++w) M = fmaxf(M, sm[w][HD]);
-    float L = 0.f;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int j = 0; j < MEMBERS; ++j) mem[j] = r0;
+  int nmem = 0;
+  for (int b0 = 0; b0 < a.R; b0 += 64) {
+    const int ch = chunk_head[min(b0 + lane, a.R - 1)];
+    unsigned long long mask = __ballot(b0 + lane < a.R && ch == r0);
+    while (mask && nmem < MEMBERS) {
+      const int row = b0 + __builtin_ctzll(mask);
+      mask &= mask - 1;
 #pragma unroll
-    for (int w = 0; w < NW; ++w) {                                   // fixed wave order: deterministic
-      const float mw = sm[w][HD];
-      const float f = (mw > -INFINITY) ? expf(mw - M) : 0.f;
-      L = fmaf(f, sm[w][HD + 1], L);
-      acc.x = fmaf(f, sm[w][c4 + 0], acc.x);
-      acc.y = fmaf(f, sm[w][c4 + 1], acc.y);
-      acc.z = fmaf(f, sm[w][c4 + 2], acc.z);
-      acc.w = fmaf(f, sm[w][c4 + 3], acc.w);
+      for (int j = 0; j < MEMBERS; ++j) if (nmem == j) mem[j] = row;
+      ++nmem;
     }
-    const float inv = 1.0f / L;
-    const int e = h * HD + c4;
-    float* dst = a.out_tiled ? out + SSRHIP_TILED_P(r, e, H * HD) : out + (size_t)r * H * HD + e;
-    *reinterpret_cast<float4*>(dst) = make_float4(acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv);
   }
+  nmem = __builtin_amdgcn_readfirstlane(nmem);
+  int len[MEMBERS], seq[MEMBERS], npg[MEMBERS];
+  float4 q[MEMBERS], o[MEMBERS];
+  float m[MEMBERS], l[MEMBERS];
+  int ns = __builtin_amdgcn_readfirstlane(n_shared[r0]);
+#pragma unroll
+  for (int j = 0; j < MEMBERS; ++j) {                                 // (slots past nmem repeat the head: loaded, never folded or stored)
+    len[j] = __builtin_amdgcn_readfirstlane(a.row_len[mem[j]]);
+    seq[j] = __builtin_amdgcn_readfirstlane(a.row_seq ? a.row_seq[mem[j]] : mem[j]);
+    npg[j] = (len[j] + SSRHIP_PAGE - 1) / SSRHIP_PAGE;
+    ns = min(ns, len[j] / SSRHIP_PAGE);
+    q[j] = ld4(a.q + (size_t)mem[j] * (a.q_stride ? a.q_stride : H * HD) + h * HD + c4);
+    m[j] = -INFINITY; l[j] = 0.f;
+    o[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  ns = max(ns, 0);
+  const size_t head_off = (size_t)h * SSRHIP_PAGE * HD, v_off = (size_t)H * SSRHIP_PAGE * HD;
+  const size_t page_stride = (size_t)a.kv.n_layer * 2 * H * SSRHIP_PAGE * HD;
+  const kv_elem* pool = reinterpret_cast<const kv_elem*>(a.kv.pool) + (size_t)a.layer * 2 * H * SSRHIP_PAGE * HD + head_off;
+  kv_vec kk[DEPTH][NI], vv[DEPTH][NI];
+  int pid[ATTN_ROWS_MAX_PAGES / 64];                                  // page ids in registers, picked with v_readlane (see attn_rows_kernel)
+
+  // ---- the shared pages, entries [0, ns) of the head's table row: whole pages for every member
+  if (ns > 0) {
+    const int slen = ns * SSRHIP_PAGE;
+#pragma unroll
+    for (int b = 0; b < ATTN_ROWS_MAX_PAGES / 64; ++b)
+      pid[b] = (b * 64 < ns) ? a.kv.table[(size_t)seq[0] * a.kv.max_pages + min(b * 64 + lane, ns - 1)] : 0;
+    ATTN_ISSUE_AT(0, 0, pid, ns, slen)
+    for (int pg = 0; pg < ns; pg += 2) {
+      ATTN_ISSUE_AT(1, pg + 1, pid, ns, slen)
+#pragma unroll
+      for (int j = 0; j < MEMBERS; ++j)
+        if (j < nmem) ATTN_FOLD_AT(0, pg, q[j], len[j], m[j], l[j], o[j])
+      ATTN_ISSUE_AT(0, pg + 2, pid, ns, slen)
+      if (pg + 1 < ns) {                                              // (a shared page is live for every member: beyond ns it must not be folded)
+#pragma unroll
+        for (int j = 0; j < MEMBERS; ++j)
+          if (j < nmem) ATTN_FOLD_AT(1, pg + 1, q[j], len[j], m[j], l[j], o[j])
+      }
+    }
+  }
+  // ---- each member's own pages, entries [ns, its page count) of its own table row: attn_rows_kernel's loop, started at page ns
+#pragma unroll
+  for (int j = 0; j < MEMBERS; ++j) {
+    if (j < nmem) {
+#pragma unroll
+      for (int b = 0; b < ATTN_ROWS_MAX_PAGES / 64; ++b)
+        pid[b] = (b * 64 < npg[j]) ? a.kv.table[(size_t)seq[j] * a.kv.max_pages + min(b * 64 + lane, npg[j] - 1)] : 0;
+      ATTN_ISSUE_AT(0, ns, pid, npg[j], len[j])
+      for (int pg = ns; pg < npg[j]; pg += 2) {
+        ATTN_ISSUE_AT(1, pg + 1, pid, npg[j], len[j])
+        ATTN_FOLD_AT(0, pg, q[j], len[j], m[j], l[j], o[j])
+        ATTN_ISSUE_AT(0, pg + 2, pid, npg[j], len[j])
+        ATTN_FOLD_AT(1, pg + 1, q[j], len[j], m[j], l[j], o[j])
+      }
+    }
+  }
+  // ---- per member: wave sum, the 8 waves' states through LDS (a slab per member: one barrier), merge and store by wave j
+#pragma unroll
+  for (int j = 0; j < MEMBERS; ++j) {
+    if (j < nmem) {
+      ATTN_WAVE_SUM(l[j], o[j])
+      if (lane < LPK) *reinterpret_cast<float4*>(&sm[j][wave][c4]) = o[j];
+      if (lane == 0) { sm[j][wave][HD] = m[j]; sm[j][wave][HD + 1] = l[j]; }
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < MEMBERS; ++j)
+    if (j < nmem && wave == j && lane < LPK) ATTN_MERGE_STORE(sm[j], mem[j])
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -618,6 +742,40 @@ extern "C" int ssrhip_attn_rows_kv16(const ssrhip_attn_args* a, float* out, ssrh
   }
   SSR_LAUNCH_CHECK();
   return 0;
+}
+
+// Workgroup chunk size of ssrhip_attn_rows_group: 2, 4 or 8 member rows per workgroup (each member costs its q and (m, l, o): 10 VGPRs at
+// any head_dim). A/B knob SSRHIP_ATTN_GROUP_MEMBERS, read at every launch (a captured graph keeps what it was captured with).
+// 2 by the launch bench (profiles/share_prompt_ab.md, 32 rows, context 520): the members' own walks run one after the other in ONE
+// workgroup, each a chain of dependent round trips, so larger chunks save bytes and lose more time than the bytes were worth.
+constexpr int ATTN_GROUP_MEMBERS_DEFAULT = 2;
+extern "C" int ssrhip_attn_group_members(void) {
+  if (const char* e = getenv("SSRHIP_ATTN_GROUP_MEMBERS")) { const int v = atoi(e); if (v == 2 || v == 4 || v == 8) return v; }
+  return ATTN_GROUP_MEMBERS_DEFAULT;
+}
+
+// the launch with the chunk size given by the caller (the decode engine: the size ITS chunks were cut for, whatever the knob says now)
+extern "C" int ssrhip_attn_rows_group_m(const ssrhip_attn_args* a, const int32_t* chunk_head, const int32_t* n_shared, int32_t members,
+                                        float* out, ssrhip_stream_t stream) {
+  if (int e = rows_check(a, out, "ssrhip_attn_rows_group")) return e;
+  SSR_REQUIRE(chunk_head && n_shared, "ssrhip_attn_rows_group: null chunk_head / n_shared");
+  SSR_REQUIRE(members == 2 || members == 4 || members == 8, "ssrhip_attn_rows_group: %d members per chunk not in {2,4,8}", members);
+  dim3 grid(a->kv.n_head, a->R);
+  hipStream_t s = (hipStream_t)stream;
+#define GROUP_LAUNCH(HD_, M_) hipLaunchKernelGGL((attn_rows_group_kernel<HD_, M_>), grid, dim3(512), 0, s, *a, chunk_head, n_shared, out)
+  if (a->kv.head_dim == 128) {
+    if (members == 2) GROUP_LAUNCH(128, 2); else if (members == 4) GROUP_LAUNCH(128, 4); else GROUP_LAUNCH(128, 8);
+  } else {
+    if (members == 2) GROUP_LAUNCH(64, 2); else if (members == 4) GROUP_LAUNCH(64, 4); else GROUP_LAUNCH(64, 8);
+  }
+#undef GROUP_LAUNCH
+  SSR_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ssrhip_attn_rows_group(const ssrhip_attn_args* a, const int32_t* chunk_head, const int32_t* n_shared, float* out,
+                                      ssrhip_stream_t stream) {
+  return ssrhip_attn_rows_group_m(a, chunk_head, n_shared, ssrhip_attn_group_members(), out, stream);
 }
 
 extern "C" int ssrhip_attn_decode(const ssrhip_attn_args* a, ssrhip_stream_t stream) {

@@ -76,6 +76,10 @@ struct ssrhip_lm {
   int pk_launches = 0;          // launches of the last enqueued step that ran a kernel of pk_kind (ssrhip_lm_{w16,wt16,wt32}_launches)
   bool kv16 = false;            // b.kv.pool holds 2-byte entries (ssrhip_lm_set_kv16: the caller's statement about its buffer)
   int kv16_launches = 0;        // attention launches of the last enqueued step that ran ssrhip_attn_rows_kv16 (ssrhip_lm_kv16_launches)
+  const int32_t* chunk_head = nullptr;   // prompt sharing (ssrhip_lm_set_prompt_groups): the caller's two device arrays [B], or null = off
+  const int32_t* n_shared = nullptr;
+  int group_members = 0;        // rows per chunk the caller's chunks are cut for (ssrhip_lm_set_group_members; set with the arrays)
+  int group_launches = 0;       // attention launches of the last enqueued step that ran ssrhip_attn_rows_group (ssrhip_lm_group_launches)
 };
 
 namespace {
@@ -361,8 +365,10 @@ int enqueue_step(ssrhip_lm* lm, hipStream_t s, Timer* tm) {
   // 5..32 rows with enough (row, head) pairs to give every CU one: the fused walk over the pages (no partials, no merge
   // launch); its output goes to b.h (free until FFN1 of this layer) because q is still being read by other workgroups
   // a bf16 KV cache (ssrhip_lm_set_kv16 checked the rows and the pages) always takes the fused walk: the split kernels read fp32 entries
-  const bool fused_attn = lm->kv16 || (sh.B > 4 && sh.B * d.n_head >= 192 && b.kv.max_pages <= 256 && !getenv_flag("SSRHIP_ATTN_SPLIT"));   // 256 pages: the kernel's page-id registers
-  int n_kv16 = 0;
+  // prompt groups (ssrhip_lm_set_prompt_groups checked the same things) take the grouped form of the fused walk, by the same rule
+  const bool grouped = lm->chunk_head != nullptr;
+  const bool fused_attn = lm->kv16 || grouped || (sh.B > 4 && sh.B * d.n_head >= 192 && b.kv.max_pages <= 256 && !getenv_flag("SSRHIP_ATTN_SPLIT"));   // 256 pages: the kernel's page-id registers
+  int n_kv16 = 0, n_group = 0;
 
   if (tm) tm->slot = 0;
 
@@ -387,6 +393,7 @@ int enqueue_step(ssrhip_lm* lm, hipStream_t s, Timer* tm) {
     if (fused_attn) {
       at.out_tiled = 1;
       if (lm->kv16) { STEP_CALL(CAT_ATTN, ssrhip_attn_rows_kv16(&at, b.h, s)); n_kv16 += 1; }
+      else if (grouped) { STEP_CALL(CAT_ATTN, ssrhip_attn_rows_group_m(&at, lm->chunk_head, lm->n_shared, lm->group_members, b.h, s)); n_group += 1; }
       else STEP_CALL(CAT_ATTN, ssrhip_attn_rows(&at, b.h, s));
       op = sh.outproj_rows_args(l, b.h);
     } else {
@@ -426,7 +433,7 @@ int enqueue_step(ssrhip_lm* lm, hipStream_t s, Timer* tm) {
   STEP_CALL(CAT_GEMV, gemv_call(h2, lm->pk_head2));
   const ssrhip_sample_args sa = sh.sample_args();
   STEP_CALL(CAT_SAMPLE, ssrhip_sample(&sa, s));
-  if (!tm || tm->only < 0) { lm->pk_launches = n_pk; lm->kv16_launches = n_kv16; }   // (a category-timing pass enqueues only part of a step)
+  if (!tm || tm->only < 0) { lm->pk_launches = n_pk; lm->kv16_launches = n_kv16; lm->group_launches = n_group; }   // (a category-timing pass enqueues only part of a step)
   return 0;
 }
 
@@ -567,10 +574,35 @@ extern "C" int ssrhip_lm_set_kv16(ssrhip_lm* lm, int32_t on) {
   SSR_REQUIRE(!on || lm->b.B > 4, "ssrhip_lm_set_kv16: the bf16 KV cache exists for 5..32 rows only (this engine has %d rows)", lm->b.B);
   SSR_REQUIRE(!on || lm->b.kv.max_pages <= 256, "ssrhip_lm_set_kv16: the fused attention walk takes at most 256 pages per row (this engine has %d)", lm->b.kv.max_pages);
   SSR_REQUIRE(!on || !getenv_flag("SSRHIP_PREFILL_ATTN_ROWWISE"), "ssrhip_lm_set_kv16: SSRHIP_PREFILL_ATTN_ROWWISE is set, and the rowwise prefill attention reads fp32 entries");
+  SSR_REQUIRE(!on || !lm->chunk_head, "ssrhip_lm_set_kv16: this engine shares prompts (ssrhip_lm_set_prompt_groups), and the grouped walk reads fp32 entries");
   lm->kv16 = on != 0;
   return 0;
 }
 extern "C" int ssrhip_lm_kv16_launches(const ssrhip_lm* lm) { return lm && lm->kv16 ? lm->kv16_launches : 0; }
+
+extern "C" int ssrhip_lm_set_prompt_groups(ssrhip_lm* lm, const int32_t* chunk_head, const int32_t* n_shared) {
+  SSR_REQUIRE(lm, "ssrhip_lm_set_prompt_groups: null engine");
+  SSR_REQUIRE(!lm->exec, "ssrhip_lm_set_prompt_groups: the decode step of this engine is already captured (call it before the first ssrhip_lm_decode)");
+  SSR_REQUIRE(!chunk_head == !n_shared, "ssrhip_lm_set_prompt_groups: chunk_head and n_shared come together (both null = off)");
+  const bool on = chunk_head != nullptr;
+  SSR_REQUIRE(!on || lm->b.B > 4, "ssrhip_lm_set_prompt_groups: prompt sharing exists for 5..32 rows only (this engine has %d rows)", lm->b.B);
+  SSR_REQUIRE(!on || lm->b.kv.max_pages <= 256, "ssrhip_lm_set_prompt_groups: the fused attention walk takes at most 256 pages per row (this engine has %d)", lm->b.kv.max_pages);
+  SSR_REQUIRE(!on || !lm->kv16, "ssrhip_lm_set_prompt_groups: an engine with a bf16 KV cache does not share prompts (the grouped walk reads fp32 entries)");
+  lm->chunk_head = chunk_head;
+  lm->n_shared = n_shared;
+  lm->group_members = on ? ssrhip_attn_group_members() : 0;
+  return 0;
+}
+extern "C" int ssrhip_lm_set_group_members(ssrhip_lm* lm, int32_t members) {
+  SSR_REQUIRE(lm, "ssrhip_lm_set_group_members: null engine");
+  SSR_REQUIRE(!lm->exec, "ssrhip_lm_set_group_members: the decode step of this engine is already captured (call it before the first ssrhip_lm_decode)");
+  SSR_REQUIRE(lm->chunk_head, "ssrhip_lm_set_group_members: this engine does not share prompts (ssrhip_lm_set_prompt_groups comes first)");
+  SSR_REQUIRE(members == 2 || members == 4 || members == 8, "ssrhip_lm_set_group_members: %d members per chunk not in {2,4,8}", members);
+  lm->group_members = members;
+  return 0;
+}
+extern "C" int ssrhip_lm_group_members(const ssrhip_lm* lm) { return lm && lm->chunk_head ? lm->group_members : 0; }
+extern "C" int ssrhip_lm_group_launches(const ssrhip_lm* lm) { return lm && lm->chunk_head ? lm->group_launches : 0; }
 extern "C" int ssrhip_lm_w16_launches(const ssrhip_lm* lm) { return lm_packed_launches(lm, PK_W16); }
 extern "C" int ssrhip_lm_wt16_launches(const ssrhip_lm* lm) { return lm_packed_launches(lm, PK_WT16); }
 extern "C" int ssrhip_lm_wt32_launches(const ssrhip_lm* lm) { return lm_packed_launches(lm, PK_WT32); }

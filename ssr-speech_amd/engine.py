@@ -176,6 +176,38 @@ def resolve_kv_dtype(rows: int, requested: Optional[str], model_default: str = "
     return requested
 
 
+def resolve_share_prompt(rows: int, requested: Optional[bool], kv_dtype: str = "fp32") -> bool:
+    """Does an engine of `rows` rows share the prompt's KV pages among equal rows (DESIGN.md Part I.15)? Pure. An explicit True where the
+    grouped attention walk does not exist is a ValueError: at <= 4 rows (the split kernels), and with a bf16 KV cache (the grouped walk
+    reads fp32 entries). None = off: nothing turns it on but the caller."""
+    if not requested:
+        return False
+    if rows <= 4:
+        raise ValueError(f"share_prompt exists for engines of 5..{MAX_ROWS} rows (this engine has {rows} rows)")
+    if kv_dtype == "bf16":
+        raise ValueError("share_prompt does not combine with kv_dtype='bf16' (the grouped attention walk reads fp32 entries)")
+    return True
+
+
+def plan_prompt_sharing(seqs, members: int):
+    """Which rows of ONE admission have the same prompt, and the attention chunks they form. Pure. seqs: (row, text ids, audio columns)
+    triples. Returns (leader, chunks): leader[row] = the lowest row with an equal text AND equal audio columns (the row itself when there
+    is none), chunks = lists of at most `members` rows with one leader, rows ascending, the chunks ordered by their first row; a row
+    without company is a chunk of one. Under CFG the conditional rows of N samples of one utterance are rows 0, 2, 4, ... of one group;
+    their unconditional rows are a second group when their texts are equal and unshared rows when `aug_text` drew each its own."""
+    if members < 1:
+        raise ValueError("members must be >= 1")
+    first, leader, groups = {}, {}, {}
+    for row, text, au in sorted(seqs, key=lambda t: t[0]):
+        t, a = np.ascontiguousarray(np.asarray(text, dtype=np.int64)), np.ascontiguousarray(np.asarray(au, dtype=np.int64))
+        key = (t.shape, t.tobytes(), a.shape, a.tobytes())
+        lead = first.setdefault(key, row)
+        leader[row] = lead
+        groups.setdefault(lead, []).append(row)
+    chunks = [g[i:i + members] for g in groups.values() for i in range(0, len(g), members)]
+    return leader, sorted(chunks, key=lambda c: c[0])
+
+
 def resolve_prefill_planes(weight_dtype: str, requested: Optional[int], env) -> int:
     """How many bf16 planes per matrix does an arena of `weight_dtype` build for the prefill / score GEMMs? 0 = none (`env` has
     SSRHIP_PREFILL_SPLIT starting with '0': the fp32 chain, whatever else is asked), 3 = the exact split of an fp32 value, 1 = the value
@@ -450,7 +482,8 @@ class PagePool:
     """Host-side allocator of the paged KV cache's physical pages (replaces the dense `past` tensor the reference re-concatenates
     every step, models/ssr.py:685-686 / modules/activation.py:626-631). A free list; pages are handed to a row when its
     sequence is about to cross into a new 128-position page and go back when its utterance is done. `order` fixes the order
-    in which an untouched pool hands pages out (tests pass a shuffled one; the kernels only ever see the table)."""
+    in which an untouched pool hands pages out (tests pass a shuffled one; the kernels only ever see the table). A page may have more
+    than one holder (`share`: the prompt pages of rows with the same prompt); it is free again when the last holder gives it back."""
 
     def __init__(self, n_pages: int, order: Optional[Sequence[int]] = None):
         self.n_pages = int(n_pages)
@@ -463,6 +496,7 @@ class PagePool:
     def reset(self):
         self._free = self._order[::-1]          # pop() hands out order[0] first
         self._owner = {}
+        self._holders = {}                      # page -> how many rows hold it (take: 1, share: + 1)
         self.handed_out = []                    # (page, owner) in hand-out order since the last reset (tests / debugging)
 
     @property
@@ -474,15 +508,30 @@ class PagePool:
             raise RuntimeError(f"KV page pool exhausted ({self.n_pages} pages of {PAGE} positions): raise pool_pages")
         p = self._free.pop()
         self._owner[p] = owner
+        self._holders[p] = 1
         self.handed_out.append((p, owner))
         return p
+
+    def share(self, page: int, owner) -> int:
+        """One more holder of a page somebody holds already (its first taker stays its `owner`; the new holder is entered in
+        `handed_out` like a taker)."""
+        if page not in self._owner:
+            raise RuntimeError(f"page {page} shared while nobody holds it")
+        self._holders[page] += 1
+        self.handed_out.append((page, owner))
+        return page
+
+    def holders(self, page: int) -> int:
+        return self._holders.get(page, 0)
 
     def give_back(self, pages: Sequence[int]):
         for p in pages:
             if p not in self._owner:
                 raise RuntimeError(f"page {p} returned twice (or never taken)")
-            del self._owner[p]
-            self._free.append(p)
+            self._holders[p] -= 1
+            if self._holders[p] == 0:
+                del self._owner[p], self._holders[p]
+                self._free.append(p)
 
 
 class IntStaging:
@@ -608,7 +657,7 @@ class DecodeEngine:
     def __init__(self, arena: LMWeightsArena, n_utt: int, use_cfg: bool, max_seq: int, max_steps: int, debug_logits: bool = False,
                  pool_pages: Optional[int] = None, page_order: Optional[Sequence[int]] = None, pair_mode: int = 0,
                  stream_w16: Optional[bool] = None, stream_wt16: Optional[bool] = None, stream_wt32: Optional[bool] = None,
-                 kv_dtype: Optional[str] = None):
+                 kv_dtype: Optional[str] = None, share_prompt: Optional[bool] = None):
         """max_seq: longest sequence (text + audio positions) any ONE row may reach; pool_pages: physical KV pages shared by all
         rows (default rows x pages-per-row, the no-sharing worst case; a batch of short and long utterances needs only the sum
         of their own page counts). pair_mode (2-row engines; include/ssrhip.h ssrhip_lm_buffers): 0 = pair launches if this engine
@@ -621,7 +670,11 @@ class DecodeEngine:
         on when the arena is bf16, the engine has 17..32 rows and `SSRHIP_GEMVM_W16` (unset = WT32_DEFAULT) does not start with '0'.
         kv_dtype "bf16" (5..32 rows, at most KV16_MAX_PAGES pages per row; ValueError otherwise): the paged pool holds 2-byte entries —
         every K / V value rounded to bf16 by whichever path writes it (the step's append, every prefill), widened exactly by every attention;
-        q, scores, softmax and outputs stay fp32 (include/ssrhip.h ssrhip_lm_set_kv16). None = "fp32". Independent of the weight stream."""
+        q, scores, softmax and outputs stay fp32 (include/ssrhip.h ssrhip_lm_set_kv16). None = "fp32". Independent of the weight stream.
+        share_prompt True (5..32 rows, fp32 cache; ValueError otherwise; None = off): rows admitted TOGETHER by `start` / the first fill of
+        `run_queue` with equal text and equal prompt audio (the samples of one utterance) are prefilled once, share the prompt's whole KV
+        pages, and the step's attention reads a shared page once per chunk of rows (include/ssrhip.h ssrhip_lm_set_prompt_groups). Every
+        row computes what it computes unshared, bit for bit. Refills and the two-phase admission (`admit_begin`) never share."""
         self.lib = _lib.lib()
         self.a = arena
         dev = arena.device
@@ -639,6 +692,9 @@ class DecodeEngine:
         self.max_pages = (max_seq + PAGE - 1) // PAGE
         self.max_seq = self.max_pages * PAGE
         self.kv_dtype = resolve_kv_dtype(self.B, kv_dtype, "fp32", self.max_pages)
+        self.share_prompt = resolve_share_prompt(self.B, share_prompt, self.kv_dtype)
+        if self.share_prompt and self.max_pages > KV16_MAX_PAGES:
+            raise ValueError(f"share_prompt takes at most {KV16_MAX_PAGES} pages per row (this engine has {self.max_pages})")
         arena.ensure_positions(self.max_seq)      # every text / audio position of a row is < its sequence capacity
         if self.B > 4:
             arena.ensure_streaming_copies()       # the matrix-core GEMV streams W in its own order
@@ -658,6 +714,13 @@ class DecodeEngine:
         self.page_table = torch.full((self.B, self.max_pages), self.scratch_page, **i32)
         self._table_host = np.full((self.B, self.max_pages), self.scratch_page, dtype=np.int32)
         self._row_pages: List[List[int]] = [[] for _ in range(self.B)]
+        # prompt sharing: chunk_head[r] = the lowest row of r's attention chunk, n_shared[r] (read at the head) = how many leading table
+        # entries the chunk's rows have in common; identity and 0 = no sharing. The device twins are what the captured step reads.
+        self.group_members = int(self.lib.ssrhip_attn_group_members()) if self.share_prompt else 1
+        self._chunk_host = np.stack([np.arange(self.B, dtype=np.int32), np.zeros(self.B, dtype=np.int32)])
+        self.chunk_dev = torch.from_numpy(self._chunk_host.copy()).to(dev) if self.share_prompt else None
+        self._chunks: List[List[int]] = []       # the chunks of more than one row that are live
+        self.prefilled_rows = 0                  # rows the last blocking admission prefilled
         self._kv0 = [0] * self.B                 # sequence length of each row after the prefill
         self._steps_enqueued = 0
         self._admit_step = [0] * n_utt           # value of _steps_enqueued when the slot's current utterance was admitted
@@ -737,6 +800,11 @@ class DecodeEngine:
             _lib.check(getattr(self.lib, setter)(ctx, C.byref(rec)), setter)
         if self.kv_dtype == "bf16":               # the pool's entry type travels with the pool (also for the two-phase admission's prefill)
             _lib.check(self.lib.ssrhip_lm_set_kv16(ctx, 1), "ssrhip_lm_set_kv16")
+        if self.share_prompt:                     # the two arrays' pointers travel with the captured step
+            _lib.check(self.lib.ssrhip_lm_set_prompt_groups(ctx, self.chunk_dev[0].data_ptr(), self.chunk_dev[1].data_ptr()),
+                       "ssrhip_lm_set_prompt_groups")
+            # the step's launches are built for the size THIS engine cuts its chunks to, whatever the knob says when a step is enqueued
+            _lib.check(self.lib.ssrhip_lm_set_group_members(ctx, self.group_members), "ssrhip_lm_set_group_members")
         if self.prefill_planes == 1:              # the count travels with the arena's buffers (also for the two-phase admission's prefill)
             _lib.check(self.lib.ssrhip_lm_set_prefill_w1(ctx, 1), "ssrhip_lm_set_prefill_w1")
         why = C.create_string_buffer(256)
@@ -756,6 +824,11 @@ class DecodeEngine:
         """Attention launches of the last enqueued decode step that read the bf16 KV cache (the layer count for a kv_dtype="bf16" engine,
         0 otherwise)."""
         return 0 if self._ctx is None else int(self.lib.ssrhip_lm_kv16_launches(self._ctx))
+
+    @property
+    def group_launches_per_step(self) -> int:
+        """Attention launches of the last enqueued decode step that ran the grouped walk (the layer count for a share_prompt engine, else 0)."""
+        return self._launches_per_step("group")
 
     @property
     def w16_launches_per_step(self) -> int:
@@ -814,6 +887,8 @@ class DecodeEngine:
         self._table_host[:] = self.scratch_page
         self._table_warm_host[:] = self.scratch_page
         self._row_pages = [[] for _ in range(self.B)]
+        self._chunks = []
+        self._chunk_host[0], self._chunk_host[1] = np.arange(self.B, dtype=np.int32), 0
         self._kv0 = [0] * self.B
         self._steps_enqueued = 0
         self._admit_step = [0] * self.n_utt
@@ -822,11 +897,13 @@ class DecodeEngine:
         self.n_admitted = self.n_refills = 0
 
     # ------------------------------------------------------------------ admission: the steps both forms are made of
-    def _book_admission(self, slots, text_rows, audio_cols, knobs):
+    def _book_admission(self, slots, text_rows, audio_cols, knobs, share: bool = False):
         """Checks the slots (free, their rows without KV pages, every sequence within the engine's capacity: ValueError before anything is
         booked or enqueued), packs the prefill rows of the new sequences — one per engine row b, with b as its seq_id — and books their
         prompt lengths. Returns (rows b, packed rows, the int32 parts of the ONE staged copy: tok[R][4] | pos[R] | kind[R] | seq[R] |
-        rpos[R] | rlen[R] | seq_start[n+1] | next_tok[rows][4] | t0[rows] | kv0[rows] | row index[rows])."""
+        rpos[R] | rlen[R] | seq_start[n+1] | next_tok[rows][4] | t0[rows] | kv0[rows] | row index[rows]).
+        share: only the LEADERS of `plan_prompt_sharing` (and the rows without company) are packed — a follower books its leader's prompt
+        length and is armed like every row; the plan is left in `self._plan` for `admit`."""
         K, rpu = self.a.K, self.rows_per_utt
         assert len(slots) == len(text_rows) == len(audio_cols) == len(knobs) and len(set(slots)) == len(slots)
         seqs = []
@@ -835,11 +912,15 @@ class DecodeEngine:
             for r in range(rpu):
                 assert not self._row_pages[u * rpu + r], "slot still owns KV pages"
                 seqs.append((u * rpu + r, trs[r], au))
-        pk = pack_prefill_rows(seqs, K)
+        self._plan = plan_prompt_sharing(seqs, self.group_members) if share else None
+        packed = [sq for sq in seqs if self._plan[0][sq[0]] == sq[0]] if share else seqs
+        pk = pack_prefill_rows(packed, K)
         if int(pk["lens"].max()) + 1 > self.max_seq:
             raise ValueError("sequence exceeds engine capacity")
         rows_b = [b for b, _, _ in seqs]
-        for b, n in zip(rows_b, pk["lens"]):
+        len_of = {sq[0]: int(n) for sq, n in zip(packed, pk["lens"])}
+        lens = np.asarray([len_of[self._plan[0][b]] if share else len_of[b] for b in rows_b], dtype=pk["lens"].dtype)
+        for b, n in zip(rows_b, lens):
             self._kv0[b] = int(n)
         self.n_admitted += len(slots)
         # first decode input of the new rows: the span-0 mask token at audio position T0 (ssr.py:655-662)
@@ -847,7 +928,7 @@ class DecodeEngine:
         nt[:, :K] = int(self.a.args.mts)
         t0 = np.asarray([np.asarray(au).shape[1] for _, _, au in seqs], dtype=np.int32)
         parts = [pk[k] for k in ("tok", "pos", "kind", "row_seq", "row_pos", "row_len", "seq_start")]
-        return rows_b, pk, parts + [nt, t0, pk["lens"], np.asarray(rows_b, dtype=np.int32)]
+        return rows_b, pk, parts + [nt, t0, lens, np.asarray(rows_b, dtype=np.int32)]
 
     def _slot_records(self, slots, knobs, audio_cols, use_noise: bool):
         """Sampler configuration / initial state of the slots, as the arrays of C records the device reads."""
@@ -944,12 +1025,16 @@ class DecodeEngine:
         the other slots keep decoding: KV pages from the pool, sampler configuration / state, pending input token, and the
         PREFILL of just those rows (the reference prefills one utterance at a time anyway: models/ssr.py:627-642). Everything is
         ordered on the caller's stream between two decode chunks; the captured step graph is untouched (it only holds pointers).
-        text_rows[i]: the 1 (or 2 with CFG) text rows of slot slots[i]; audio_cols[i]: [K, T0]. Returns the prefilled row count."""
+        text_rows[i]: the 1 (or 2 with CFG) text rows of slot slots[i]; audio_cols[i]: [K, T0]. Returns the prefilled row count.
+        A share_prompt engine shares in its FIRST admission since `start` / `run_queue` began (the rows that arrive together): only one
+        row of every group of equal prompts is prefilled, so the count shrinks. Later admissions (refills) never share."""
         a, dev = self.a, self.device
-        rows_b, pk, parts = self._book_admission(slots, text_rows, audio_cols, knobs)
+        share = self.share_prompt and self.n_admitted == 0
+        rows_b, pk, parts = self._book_admission(slots, text_rows, audio_cols, knobs, share)
         for u in slots:
             self._utt_live[u] = True
             self._admit_step[u] = self._steps_enqueued
+        tails = self._share_pages(*self._plan) if share else []
         self._grow_pages(0)                      # pages for the prompts (+ the first decoded position) of the new rows
         stage = self._admit_stage
         total = sum(p_.size for p_ in parts)
@@ -973,6 +1058,14 @@ class DecodeEngine:
         # (the prefill ends by embedding the pending input token of EVERY row into x: for rows in mid-decode that re-writes the
         # very values the sampler's fused embedding left there — same function, same inputs)
         self._launch_prefill(p)
+        if tails:
+            # a prompt that ends inside a page: the follower appends into its OWN page from position n on, and reads the leader's
+            # positions below n there — one contiguous block of the pool per (leader, follower), copied behind the prefill
+            pool = self.kv_pool.view(self.pages.n_pages + 1, -1)
+            for lead, f in tails:
+                e = self._kv0[f] // PAGE
+                pool[int(self._table_host[f, e])].copy_(pool[int(self._table_host[lead, e])])
+        self.prefilled_rows = int(pk["tok"].shape[0])
         self._keep = (ws, idx)                   # alive until the stream has consumed them (the integer arrays live in the engine's workspace)
         return int(pk["tok"].shape[0])
 
@@ -1062,19 +1155,60 @@ class DecodeEngine:
                     self._table_host[b, have] = p
                     changed = more = True
         if changed:
-            self.page_table.copy_(torch.from_numpy(self._table_host))       # pageable source: staged before this call returns
+            self._push_table()                    # pageable source: staged before this call returns
+
+    def _share_pages(self, leader, chunks):
+        """The page side of a sharing admission, before `_grow_pages` hands out what is left: a leader takes the n // PAGE WHOLE pages of
+        its prompt (n = `_kv0`) and every follower holds them too (`PagePool.share`), as the first entries of its table row; the entry
+        behind them (where position n is appended) stays each row's own. Enters the chunks into the two arrays (pushed with the table by
+        `_grow_pages`, which always has a page to hand out here). Returns the (leader, follower) pairs whose prompt ends inside a page."""
+        tails = []
+        for lead in sorted(set(leader.values())):
+            followers = [b for b, l_ in sorted(leader.items()) if l_ == lead and b != lead]
+            ns = self._kv0[lead] // PAGE
+            if not followers:
+                continue
+            for i in range(ns):
+                pg = self.pages.take(lead)
+                self._row_pages[lead].append(pg)
+                self._table_host[lead, i] = pg
+                for f in followers:
+                    self._row_pages[f].append(self.pages.share(pg, f))
+                    self._table_host[f, i] = pg
+            if self._kv0[lead] % PAGE:
+                tails += [(lead, f) for f in followers]
+        # a chunk is worth a workgroup of its own only where it has pages in common
+        self._chunks = [list(c) for c in chunks if len(c) > 1 and self._kv0[c[0]] // PAGE > 0]
+        self._enter_chunks()
+        return tails
+
+    def _enter_chunks(self):
+        self._chunk_host[0], self._chunk_host[1] = np.arange(self.B, dtype=np.int32), 0
+        for c in self._chunks:
+            self._chunk_host[0, c] = c[0]
+            self._chunk_host[1, c[0]] = self._kv0[c[0]] // PAGE
 
     def release_utterance(self, u: int):
         """Utterance u is done: its rows' pages go back to the pool and the rows are pointed at the scratch page (they stay in
-        the lock-step batch and keep appending at a frozen position; nothing reads what they produce)."""
+        the lock-step batch and keep appending at a frozen position; nothing reads what they produce). Rows that shared their prompt
+        leave their chunk (the lowest row that stays becomes its head); a shared page is free when its last holder has let go."""
         if not self._utt_live[u]:
             return
         self._utt_live[u] = False
-        for b in range(u * self.rows_per_utt, (u + 1) * self.rows_per_utt):
+        gone = range(u * self.rows_per_utt, (u + 1) * self.rows_per_utt)
+        for b in gone:
             self.pages.give_back(self._row_pages[b])
             self._row_pages[b] = []
             self._table_host[b, :] = self.scratch_page
+        if self._chunks:
+            self._chunks = [c for c in ([b for b in c if b not in gone] for c in self._chunks) if len(c) > 1]
+            self._enter_chunks()
+        self._push_table()
+
+    def _push_table(self):
         self.page_table.copy_(torch.from_numpy(self._table_host))
+        if self.share_prompt:                     # the chunks travel with the table they describe
+            self.chunk_dev.copy_(torch.from_numpy(self._chunk_host))
 
     # ------------------------------------------------------------------ decode
     def decode(self, n_steps: int, use_graph: bool = True):

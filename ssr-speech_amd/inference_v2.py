@@ -59,6 +59,9 @@ EXTRA_FLAGS = [
     ("--kv_dtype", dict(type=str, choices=["fp32", "bf16"], default="fp32",
                         help="bf16: decode engines of 5..32 rows (batched synthesis) keep their KV cache in 2-byte bf16 entries "
                              "(SSR_Speech.set_kv_dtype); fp32 (default): the cache as it is")),
+    ("--share_prompt", dict(type=int, choices=[0, 1], default=0,
+                            help="1: the --sample_batch_size samples of the utterance are prefilled once and share the prompt's KV pages "
+                                 "(5..32 rows, fp32 cache; fewer rows run unshared); 0 (default): every sample keeps its own copy")),
     ("--prompt_end", dict(type=float, default=None, help="--tts: cut the prompt audio at this time in seconds (default --prompt_length)")),
     ("--phoneme_ids", dict(type=str, default=None, help="comma separated phoneme ids of the target transcript (skips espeak)")),
     ("--prompt_phoneme_ids", dict(type=str, default=None, help="comma separated phoneme ids of the prompt transcript")),
@@ -306,7 +309,7 @@ def main(argv=None):
     if len(seeds) > 1:
         # all samples of the utterance in ONE lock-step decode (same outputs as the reference's sequential loop :331-358)
         seed_everything(seeds[-1])
-        waves = inference_samples(*common, seeds=seeds)
+        waves = inference_samples(*common, seeds=seeds, share_prompt=bool(args.share_prompt))
     else:
         seed_everything(seeds[0])
         waves = [inference_one_sample(*common)]

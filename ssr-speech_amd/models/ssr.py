@@ -24,7 +24,7 @@ from .. import _lib
 from .. import layout as LY
 from .. import score as SC
 from ..engine import (DEFAULT_GROUP_ROWS, KV_DTYPES, MAX_ROWS, WEIGHT_DTYPES, DecodeEngine, DecodeKnobs, LMWeightsArena, TorchCpuNoiseFeed,
-                      resolve_kv_dtype)
+                      resolve_kv_dtype, resolve_share_prompt)
 from ..weights import lm_param_specs
 
 
@@ -182,7 +182,8 @@ class SSR_Speech(nn.Module):
                                   "returns its loss, top-10 accuracy and token counts without autograd.")
 
     # ------------------------------------------------------------------ engine management
-    def _get_engine(self, n_utt: int, use_cfg: bool, need_seq: int, need_steps: int, need_pages: Optional[int] = None) -> DecodeEngine:
+    def _get_engine(self, n_utt: int, use_cfg: bool, need_seq: int, need_steps: int, need_pages: Optional[int] = None,
+                    share_prompt: bool = False) -> DecodeEngine:
         dev = self.device
         if dev.type != "cuda":
             raise RuntimeError("ssr_speech_amd.SSR_Speech.inference needs the model on a ROCm GPU (model.to('cuda')); "
@@ -196,6 +197,9 @@ class SSR_Speech(nn.Module):
                 e.close()
             self._engines = {}
         rows = n_utt * (2 if use_cfg else 1)
+        kv_dtype = resolve_kv_dtype(rows, None, self._kv_dtype, cap_seq // 128)
+        # prompt sharing is the caller's request where the engine can serve it: <= 4 rows, a bf16 cache or more than 256 pages per row run unshared
+        share = bool(share_prompt) and rows > 4 and kv_dtype == "fp32" and cap_seq // 128 <= 256 and resolve_share_prompt(rows, True, kv_dtype)
         # KV pool: `need_pages` = sum over rows of the pages each row can reach (short and long utterances share one pool); never more
         # than rows x pages-per-row
         need = rows * (cap_seq // 128)
@@ -204,12 +208,12 @@ class SSR_Speech(nn.Module):
         order_key = tuple(self.page_order) if self.page_order is not None else None
         # reuse: any resident engine of the same shape whose capacities cover the request (a batch of other lengths must not re-allocate
         # the pool, the noise buffer and re-capture the graph); a caller-chosen page order (tests) pins the pool size exactly
-        for (k_utt, k_cfg, k_seq, k_steps, k_dbg, k_pool, k_order), e in self._engines.items():
-            if (k_utt, k_cfg, k_dbg, k_order) == (n_utt, use_cfg, bool(self.debug_logits), order_key) and k_seq >= cap_seq and k_steps >= cap_steps \
+        for (k_utt, k_cfg, k_seq, k_steps, k_dbg, k_pool, k_order, k_share), e in self._engines.items():
+            if (k_utt, k_cfg, k_dbg, k_order, k_share) == (n_utt, use_cfg, bool(self.debug_logits), order_key, share) and k_seq >= cap_seq and k_steps >= cap_steps \
                     and (k_pool >= need if order_key is None else k_pool == min(rows * (cap_seq // 128), ((need + 7) // 8) * 8)):
                 return e
         pool = min(rows * (cap_seq // 128), ((need + 7) // 8) * 8)
-        key = (n_utt, use_cfg, cap_seq, cap_steps, bool(self.debug_logits), pool, order_key)
+        key = (n_utt, use_cfg, cap_seq, cap_steps, bool(self.debug_logits), pool, order_key, share)
         for e in self._engines.values():         # one engine (KV pool) resident at a time
             e.close()
         self._engines = {}
@@ -217,7 +221,7 @@ class SSR_Speech(nn.Module):
         if self.page_order is not None:          # tests: a caller-chosen hand-out order of the physical pages
             order = [p for p in self.page_order if p < pool] if len(self.page_order) >= pool else None
         eng = DecodeEngine(self._arena, n_utt, use_cfg, cap_seq, cap_steps, debug_logits=self.debug_logits, pool_pages=pool, page_order=order,
-                           kv_dtype=resolve_kv_dtype(rows, None, self._kv_dtype, cap_seq // 128))
+                           kv_dtype=kv_dtype, share_prompt=share)
         self._engines[key] = eng
         return eng
 
@@ -463,7 +467,7 @@ class SSR_Speech(nn.Module):
     def inference_batch(self, utterances, top_k: int = -100, top_p: float = 1.0, temperature: float = 1.0, stop_repetition: int = -1,
                         silence_tokens=(1388, 1898, 131), cfg_coef: float = 1.5, cfg_stride: int = 1, aug_text: bool = False,
                         seed: int = 0, first_index: int = 0, group: Optional[int] = None, use_graph: bool = True, refill: bool = True,
-                        indices: Optional[Sequence[int]] = None):
+                        indices: Optional[Sequence[int]] = None, share_prompt: bool = False):
         """Several independent utterances decoded in lock-step so that one pass over the weights serves all of them
         (the reference is strictly batch-1: `assert y.shape[0] == 1`, ssr.py:559, and loops `--sample_batch_size`
         sequentially, inference_v2.py:331-333).
@@ -473,6 +477,9 @@ class SSR_Speech(nn.Module):
         (per-utterance RNG streams, independent of grouping and of the DP world size); `indices[i]` replaces `first_index + i`
         when the list is a cost-balanced (non-contiguous) shard of a larger job (`dp.generate`).
         `refill=False` (A/B knob, bench): fixed groups of `group` utterances, each decoded until its longest member ends (round 2).
+        `share_prompt=True` (opt-in, DESIGN.md Part I.15): utterances of the FIRST fill with equal text and prompt audio — the samples of
+        one utterance — are prefilled once and share the prompt's KV pages (engine.DecodeEngine share_prompt); same results, bit for bit.
+        Engines of <= 4 rows, or with a bf16 KV cache, run unshared without error.
         Returns a list of the same 4-tuples `inference` returns."""
         K = self.args.n_codebooks
         assert cfg_coef >= 1.0, cfg_coef
@@ -513,7 +520,7 @@ class SSR_Speech(nn.Module):
             n_slots += 1
         # KV pool: at most n_slots utterances are resident at a time -> the n_slots largest page demands bound the concurrent need
         pages_sum = sum(sorted(page_need, reverse=True)[:n_slots])
-        eng = self._get_engine(n_slots, bool(aug_text), seq_max, cap_max + 16, need_pages=pages_sum)
+        eng = self._get_engine(n_slots, bool(aug_text), seq_max, cap_max + 16, need_pages=pages_sum, share_prompt=share_prompt)
         if refill:
             outs = eng.run_queue(jobs, chunk=16, use_graph=use_graph, sampling=not greedy)
         else:

@@ -20,6 +20,12 @@ and at 17..32 rows (DESIGN.md Part I.12; the same switch, `wt32 launches` the co
 A lower-case `kv_dtype=bf16` is not an environment variable either: that variant's engine keeps its KV cache in 2-byte entries (DESIGN.md
 Part I.14; 5..32 rows, `kv16 launches` its counter), independent of `weight_dtype`:
   python tools/decode_ab.py --utts 16 --greedy --warmup 180 --steps 100 fp32: kv16:kv_dtype=bf16 bf16_wt:weight_dtype=bf16,SSRHIP_GEMVM_W16=1 bf16_wt_kv16:weight_dtype=bf16,SSRHIP_GEMVM_W16=1,kv_dtype=bf16
+A lower-case `share_prompt=0|1` (DESIGN.md Part I.15) gives the variant the input of `--sample_batch_size U`: U samples of ONE utterance —
+every conditional row carries utterance 0's text, the unconditional rows keep their own (what `aug_text` draws) — and `share_prompt=1`
+builds its engine with share_prompt=True (one prefill and one set of prompt pages for the conditional rows, the grouped attention walk;
+`group launches` its counter). Both arms print the rows their first fill prefilled, its device time (the prefill and what the admission enqueues behind it: a sharing
+engine's copies of the prompt's partial page) and the KV pages in use:
+  python tools/decode_ab.py --utts 16 --greedy --warmup 180 --steps 100 unshared:share_prompt=0 shared:share_prompt=1
 """
 import argparse
 import dataclasses
@@ -57,6 +63,7 @@ for v in a.variants:
     variants.append((name, dict(kv.split("=", 1) for kv in kn.split(",") if kv)))
 dtype_of = {name: d.pop("weight_dtype", "fp32") for name, d in variants}
 kv_of = {name: d.pop("kv_dtype", "fp32") for name, d in variants}
+share_of = {name: d.pop("share_prompt", None) for name, d in variants}      # None: U utterances; "0" / "1": U samples of utterance 0
 all_knobs = sorted({k for _, d in variants for k in d})
 
 dev = torch.device("cuda", 0)
@@ -84,9 +91,20 @@ for rep in range(a.reps):
         os.environ.update(knobs)
         U = utts_of[name]
         eng = DecodeEngine(arenas[dtype_of[name]], U, True, ((L + T0 + total + 8 + 1023) // 1024) * 1024, ((total + 255) // 256) * 256,
-                           kv_dtype=kv_of[name])
-        eng.start(text_rows[:2 * U], [cated] * U, [dataclasses.replace(kn, seed=2024 + u) for u in range(U)], noise=None)
+                           kv_dtype=kv_of[name], share_prompt=share_of[name] == "1")
+        rows_in = text_rows[:2 * U] if share_of[name] is None else [text_rows[r] if r % 2 else text_rows[0] for r in range(2 * U)]
+        launch, ev = eng._launch_prefill, (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+
+        def timed_prefill(p):                     # a device event in front of the prefill (the wrapper of tools/prefill_time.py) ...
+            ev[0].record()
+            launch(p)
+
+        eng._launch_prefill = timed_prefill
+        n_prefilled = eng.start(rows_in, [cated] * U, [dataclasses.replace(kn, seed=2024 + u) for u in range(U)], noise=None)
+        ev[1].record()                            # ... and one behind everything the admission enqueued after it (a sharing engine's tail-page copies)
         torch.cuda.synchronize()
+        res[name].setdefault("prefill_ms", []).append(ev[0].elapsed_time(ev[1]))
+        res[name]["prefill_rows"] = n_prefilled
         eng.decode(a.warmup)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -99,6 +117,8 @@ for rep in range(a.reps):
         for st in W16_STREAMS:
             r[st.name] = getattr(eng, st.name + "_launches_per_step")
         r["kv16"] = eng.kv16_launches_per_step
+        r["group"] = eng.group_launches_per_step
+        r["pages"] = eng.pages.n_pages - eng.pages.n_free
         r["ms"].append(ms)
         r["gemv"].append(eng.time_category("gemv", 50)[0])
         r["attn"].append(eng.time_category("attn", 50)[0])
@@ -120,4 +140,4 @@ for name, knobs in variants:
     print(f"{name:14s} {U:2d} utts x CFG = {2 * U:2d} rows  tok/s {4 * U / (statistics.median(r['ms']) * 1e-3):9.1f}  "
           f"ms/step min {min(r['ms']):.4f} med {statistics.median(r['ms']):.4f}  all {' '.join(f'{v:.4f}' for v in r['ms'])} | "
           f"gemv {min(r['gemv']):.3f} x {r['launches']['gemv']} attn {min(r['attn']):.3f} x {r['launches']['attn']} "
-          f"sample {min(r['sample']):.3f} x {r['launches']['sample']} us{same}   [{dtype_of[name]}, kv {kv_of[name]}, {' + '.join(f'{r[st.name]} {st.name}' for st in W16_STREAMS)} + {r['kv16']} kv16 launches; {' '.join(f'{k}={v}' for k, v in knobs.items()) or 'defaults'}]")
+          f"sample {min(r['sample']):.3f} x {r['launches']['sample']} us{same}   [{dtype_of[name]}, kv {kv_of[name]}, {' + '.join(f'{r[st.name]} {st.name}' for st in W16_STREAMS)} + {r['kv16']} kv16 + {r['group']} group launches; first fill {r['prefill_rows']} rows in {min(r['prefill_ms']):.2f} ms, {r['pages']} KV pages in use; share_prompt={share_of[name]}; {' '.join(f'{k}={v}' for k, v in knobs.items()) or 'defaults'}]")
