@@ -13,6 +13,7 @@
 // reference builds (models/ssr.py:227-255) is exactly "row r sees positions < row_len[r]".
 #include <stdlib.h>
 #include <algorithm>
+#include <type_traits>
 using std::min;
 #include "common.h"
 
@@ -37,11 +38,51 @@ __device__ __forceinline__ float4 kv_f4(const uint2 v) { return bf16x4_widen(v);
 template <bool KV16> struct kv_types { typedef float elem; typedef float4 vec; };
 template <> struct kv_types<true> { typedef uint16_t elem; typedef uint2 vec; };
 
+// The geometry of NW waves reading one page at head_dim HD, derived here for every kernel below
+template <int HD, int NW>
+struct attn_geom {
+  static constexpr int LPK = HD / 4;             // lanes per key row
+  static constexpr int KPI = 64 / LPK;           // key rows per wave-instruction
+  static constexpr int KPW = SSRHIP_PAGE / NW;   // keys of a page per wave
+  static constexpr int NI = KPW / KPI;           // load instructions for the wave's keys
+};
+// the KPI key-row groups of a wave (lanes with equal c4) share m, so their (l, o) simply add
+template <int LPK>
+__device__ __forceinline__ void attn_wave_sum(float& l, float4& o) {
+  if (LPK == 16) {
+    l += xor16_f(l);
+    o.x += xor16_f(o.x); o.y += xor16_f(o.y); o.z += xor16_f(o.z); o.w += xor16_f(o.w);
+  }
+  l += xor32_f(l);
+  o.x += xor32_f(o.x); o.y += xor32_f(o.y); o.z += xor32_f(o.z); o.w += xor32_f(o.w);
+}
+// merge of the NW waves' states in LDS (row w: the wave's o, then its m and l) by the lane that owns columns c4..c4+3 (fixed wave order:
+// deterministic): the un-normalised state of the whole workgroup
+struct attn_state { float M, L; float4 acc; };
+template <int HD, int NW>
+__device__ __forceinline__ attn_state attn_merge_waves(const float (&sm)[NW][HD + 4], const int c4) {
+  float M = -INFINITY;
+#pragma unroll
+  for (int w = 0; w < NW; ++w) M = fmaxf(M, sm[w][HD]);
+  float L = 0.f;
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+  for (int w = 0; w < NW; ++w) {
+    const float mw = sm[w][HD];
+    const float f = (mw > -INFINITY) ? expf(mw - M) : 0.f;
+    L = fmaf(f, sm[w][HD + 1], L);
+    acc.x = fmaf(f, sm[w][c4 + 0], acc.x);
+    acc.y = fmaf(f, sm[w][c4 + 1], acc.y);
+    acc.z = fmaf(f, sm[w][c4 + 2], acc.z);
+    acc.w = fmaf(f, sm[w][c4 + 3], acc.w);
+  }
+  return attn_state{M, L, acc};
+}
+
 template <int HD, bool SEQ, int VAT = -1>   // SEQ: rows carry an explicit sequence id (a.row_seq != NULL: the per-row prefill path); the decode step has none
 __global__ __launch_bounds__(256) void attn_decode_kernel(const ssrhip_attn_args a, const int head_fastest) {   // VAT: see the V requests below
-  constexpr int LPK = HD / 4;         // lanes per key row
-  constexpr int KPI = 64 / LPK;       // key rows per wave-instruction
-  constexpr int NI = 32 / KPI;        // load instructions for the wave's 32 keys
+  typedef attn_geom<HD, 4> G;
+  constexpr int LPK = G::LPK, KPI = G::KPI, NI = G::NI;   // 4 waves: 32 keys of the page each
   __shared__ __attribute__((aligned(16))) float sm[4][HD + 4];   // row stride keeps float4 stores 16-B aligned
   // Workgroup b runs on XCD b % 8 (observed, for speed only). With the page index as the fastest grid dimension and 8 pages of capacity
   // every workgroup of page p sat on XCD p: a 600-position context used 5 XCDs' L2s and fabric links and left 3 idle. `head_fastest`
@@ -149,36 +190,18 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const ssrhip_attn_args
       o4.w = fmaf(p, vv[i].w, o4.w);
     }
   }
-  // merge the KPI key-row groups of the wave (lanes with equal c4)
-  if (LPK == 16) {
-    l += xor16_f(l);
-    o4.x += xor16_f(o4.x); o4.y += xor16_f(o4.y); o4.z += xor16_f(o4.z); o4.w += xor16_f(o4.w);
-  }
-  l += xor32_f(l);
-  o4.x += xor32_f(o4.x); o4.y += xor32_f(o4.y); o4.z += xor32_f(o4.z); o4.w += xor32_f(o4.w);
+  attn_wave_sum<LPK>(l, o4);
   if (lane < LPK) {
     *reinterpret_cast<float4*>(&sm[wave][c4]) = o4;
   }
   if (lane == 0) { sm[wave][HD] = m; sm[wave][HD + 1] = l; }
   __syncthreads();
-  // 4-wave merge by the first LPK lanes of wave 0 (fixed order)
+  // 4-wave merge by the first LPK lanes of wave 0
   if (threadIdx.x < LPK) {
-    float M = fmaxf(fmaxf(sm[0][HD], sm[1][HD]), fmaxf(sm[2][HD], sm[3][HD]));
-    float L = 0.f;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      const float mw = sm[w][HD];
-      const float f = (mw > -INFINITY) ? expf(mw - M) : 0.f;
-      L = fmaf(f, sm[w][HD + 1], L);
-      acc.x = fmaf(f, sm[w][c4 + 0], acc.x);
-      acc.y = fmaf(f, sm[w][c4 + 1], acc.y);
-      acc.z = fmaf(f, sm[w][c4 + 2], acc.z);
-      acc.w = fmaf(f, sm[w][c4 + 3], acc.w);
-    }
+    const attn_state t = attn_merge_waves<HD, 4>(sm, c4);
     const size_t pi = ((size_t)r * H + h) * a.max_splits + split;
-    *reinterpret_cast<float4*>(a.part_o + pi * HD + c4) = acc;
-    if (threadIdx.x == 0) { a.part_ml[pi * 2] = M; a.part_ml[pi * 2 + 1] = L; }
+    *reinterpret_cast<float4*>(a.part_o + pi * HD + c4) = t.acc;
+    if (threadIdx.x == 0) { a.part_ml[pi * 2] = t.M; a.part_ml[pi * 2 + 1] = t.L; }
   }
 }
 
@@ -247,82 +270,85 @@ __global__ __launch_bounds__(64) void attn_combine_kernel(const ssrhip_attn_args
 // Loads are never predicated (see above): keys past the row's length re-read key 0 of the last page and are masked to -inf.
 constexpr int ATTN_ROWS_MAX_PAGES = 256;       // 32,768 positions per row
 
-// The page walk's pieces, shared by attn_rows_kernel and attn_rows_group_kernel (which keeps one (Q, LEN, M, L, O) per member row).
-// They use the enclosing kernel's a, pool, page_stride, v_off, wave, sub, c4, kk, vv and its constants.
-#define ATTN_ISSUE_AT(BUF, PG, PID, NPAGES, LEN)                                                    \
-  {                                                                                                   \
-    const int pg_ = min((PG), (NPAGES) - 1);                                                            \
-    const int pb_ = pg_ >> 6;                                                                         \
-    const int pv_ = pb_ == 0 ? PID[0] : (pb_ == 1 ? PID[1] : (pb_ == 2 ? PID[2] : PID[3]));           \
-    const kv_elem* kp_ = pool + (size_t)__builtin_amdgcn_readlane(pv_, pg_ & 63) * page_stride;       \
-    const int jmax_ = ((PG) < (NPAGES)) ? min((LEN) - pg_ * SSRHIP_PAGE, SSRHIP_PAGE) - 1 : 0;            \
-    _Pragma("unroll") for (int i = 0; i < NI; ++i) {                                                  \
-      const int j_ = min(wave * KPW + i * KPI + sub, jmax_);                                          \
-      kk[BUF][i] = ld_kv(kp_ + (size_t)j_ * HD + c4);                                                  \
-    }                                                                                                 \
-    _Pragma("unroll") for (int i = 0; i < NI; ++i) {                                                  \
-      const int j_ = min(wave * KPW + i * KPI + sub, jmax_);                                          \
-      vv[BUF][i] = ld_kv(kp_ + v_off + (size_t)j_ * HD + c4);                                          \
-    }                                                                                                 \
+// The page walk's pieces, shared by attn_rows_kernel and attn_rows_group_kernel (which keeps one (q, len, m, l, o) per member row).
+// What the issues and folds of one (workgroup, head) have in common, filled in once in front of the walk:
+template <int HD, int NW, class E>
+struct attn_walk {
+  const E* pool;                    // K of page 0 of this layer and head; page p lies p * page_stride behind it, its V another v_off
+  size_t page_stride, v_off;
+  float scale;
+  int wave, sub, c4;                // the wave, the lane's key row inside one wave-instruction, the lane's 4 columns
+};
+// Request K and V of page pg of a row of npages pages and len positions into one buffer pair. ids = the register of page ids that holds
+// page min(pg, npages - 1) (lane i of register b holds page 64b + i). A page past the last re-reads key 0 of the last page, keys past len
+// the page's last valid key (never predicated, see above).
+template <int HD, int NW, class E, class KV>
+__device__ __forceinline__ void attn_issue(const attn_walk<HD, NW, E>& w, KV (&kk)[attn_geom<HD, NW>::NI], KV (&vv)[attn_geom<HD, NW>::NI], const int pg,
+                                           const int ids, const int npages, const int len) {
+  typedef attn_geom<HD, NW> G;
+  // (the walk's values as locals: with w.pool .. w.c4 written at their uses hipcc orders the waits of nine kernels differently)
+  const E* pool = w.pool; const size_t page_stride = w.page_stride, v_off = w.v_off; const int wave = w.wave, sub = w.sub, c4 = w.c4;
+  const int pg_ = min(pg, npages - 1);
+  const E* kp = pool + (size_t)__builtin_amdgcn_readlane(ids, pg_ & 63) * page_stride;
+  const int jmax = (pg < npages) ? min(len - pg_ * SSRHIP_PAGE, SSRHIP_PAGE) - 1 : 0;
+#pragma unroll
+  for (int i = 0; i < G::NI; ++i) {
+    const int j = min(wave * G::KPW + i * G::KPI + sub, jmax);
+    kk[i] = ld_kv(kp + (size_t)j * HD + c4);
   }
-#define ATTN_FOLD_AT(BUF, PG, Q, LEN, M, L, O)                                                      \
-  {                                                                                                   \
-    float s_[NI];                                                                                     \
-    _Pragma("unroll") for (int i = 0; i < NI; ++i) s_[i] = dot4(Q, kv_f4(kk[BUF][i]), 0.f);           \
-    _Pragma("unroll") for (int i = 0; i < NI; ++i) s_[i] = (LPK == 32) ? half32_sum(s_[i]) : row16_sum(s_[i]); \
-    float mloc_ = -INFINITY;                                                                          \
-    _Pragma("unroll") for (int i = 0; i < NI; ++i) {                                                  \
-      const int pos_ = (PG) * SSRHIP_PAGE + wave * KPW + i * KPI + sub;                               \
-      s_[i] = (pos_ < (LEN)) ? s_[i] * a.scale : -INFINITY;                                             \
-      mloc_ = fmaxf(mloc_, s_[i]);                                                                    \
-    }                                                                                                 \
-    if (LPK == 16) mloc_ = fmaxf(mloc_, xor16_f(mloc_));                                              \
-    mloc_ = fmaxf(mloc_, xor32_f(mloc_));                                                             \
-    const float mnew_ = fmaxf(M, mloc_);                                                              \
-    if (mnew_ > -INFINITY) {                                                                          \
-      const float al_ = (M > -INFINITY) ? expf(M - mnew_) : 0.f;                                      \
-      L *= al_; O.x *= al_; O.y *= al_; O.z *= al_; O.w *= al_;                                       \
-      _Pragma("unroll") for (int i = 0; i < NI; ++i) {                                                \
-        const float p_ = expf(s_[i] - mnew_);                                                         \
-        L += p_;                                                                                      \
-        O.x = fmaf(p_, kv_f4(vv[BUF][i]).x, O.x); O.y = fmaf(p_, kv_f4(vv[BUF][i]).y, O.y);           \
-        O.z = fmaf(p_, kv_f4(vv[BUF][i]).z, O.z); O.w = fmaf(p_, kv_f4(vv[BUF][i]).w, O.w);           \
-      }                                                                                               \
-      M = mnew_;                                                                                      \
-    }                                                                                                 \
+#pragma unroll
+  for (int i = 0; i < G::NI; ++i) {
+    const int j = min(wave * G::KPW + i * G::KPI + sub, jmax);
+    vv[i] = ld_kv(kp + v_off + (size_t)j * HD + c4);
   }
+}
+// The pick of that register stays text, every name a parameter: as a function — the four registers by reference, by value or in a struct —
+// hipcc moves the table loads and the waits of the group kernels (profiles/attn_refactor_ab.md). PID is the int[4] of page-id registers.
+#define ATTN_ISSUE(W, KK, VV, PG, PID, NPAGES, LEN)                                                                  \
+  {                                                                                                                  \
+    const int pb_ = min((PG), (NPAGES) - 1) >> 6;                                                                    \
+    attn_issue(W, KK, VV, PG, pb_ == 0 ? PID[0] : (pb_ == 1 ? PID[1] : (pb_ == 2 ? PID[2] : PID[3])), NPAGES, LEN); \
+  }
+// fold page pg, held in one buffer pair, into a row's running (m, l, o) with that row's q and length: the online softmax
+template <int HD, int NW, class E, class KV>
+__device__ __forceinline__ void attn_fold(const attn_walk<HD, NW, E>& w, const KV (&kk)[attn_geom<HD, NW>::NI], const KV (&vv)[attn_geom<HD, NW>::NI],
+                                          const int pg, const float4 q, const int len, float& m, float& l, float4& o) {
+  typedef attn_geom<HD, NW> G;
+  float s[G::NI];
+#pragma unroll
+  for (int i = 0; i < G::NI; ++i) s[i] = dot4(q, kv_f4(kk[i]), 0.f);
+#pragma unroll
+  for (int i = 0; i < G::NI; ++i) s[i] = (G::LPK == 32) ? half32_sum(s[i]) : row16_sum(s[i]);
+  float mloc = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < G::NI; ++i) {
+    const int pos = pg * SSRHIP_PAGE + w.wave * G::KPW + i * G::KPI + w.sub;
+    s[i] = (pos < len) ? s[i] * w.scale : -INFINITY;
+    mloc = fmaxf(mloc, s[i]);
+  }
+  if (G::LPK == 16) mloc = fmaxf(mloc, xor16_f(mloc));
+  mloc = fmaxf(mloc, xor32_f(mloc));
+  const float mnew = fmaxf(m, mloc);
+  if (mnew > -INFINITY) {
+    const float al = (m > -INFINITY) ? expf(m - mnew) : 0.f;
+    l *= al; o.x *= al; o.y *= al; o.z *= al; o.w *= al;
+#pragma unroll
+    for (int i = 0; i < G::NI; ++i) {
+      const float p = expf(s[i] - mnew);
+      l += p;
+      o.x = fmaf(p, kv_f4(vv[i]).x, o.x); o.y = fmaf(p, kv_f4(vv[i]).y, o.y);
+      o.z = fmaf(p, kv_f4(vv[i]).z, o.z); o.w = fmaf(p, kv_f4(vv[i]).w, o.w);
+    }
+    m = mnew;
+  }
+}
 
-// the tail of a (row, head): the KPI key-row groups of a wave share m, so their (l, o) simply add; then the 8 waves' states go through LDS
-#define ATTN_WAVE_SUM(L, O)                                                                           \
-  {                                                                                                   \
-    if (LPK == 16) {                                                                                  \
-      L += xor16_f(L);                                                                                \
-      O.x += xor16_f(O.x); O.y += xor16_f(O.y); O.z += xor16_f(O.z); O.w += xor16_f(O.w);             \
-    }                                                                                                 \
-    L += xor32_f(L);                                                                                  \
-    O.x += xor32_f(O.x); O.y += xor32_f(O.y); O.z += xor32_f(O.z); O.w += xor32_f(O.w);               \
-  }
-// merge of the 8 waves' states in SM by LPK lanes (fixed wave order: deterministic), normalise, store row ROW
-#define ATTN_MERGE_STORE(SM, ROW)                                                                     \
-  {                                                                                                   \
-    float M = -INFINITY;                                                                              \
-    _Pragma("unroll") for (int w = 0; w < NW; ++w) M = fmaxf(M, SM[w][HD]);                           \
-    float L = 0.f;                                                                                    \
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);                                                     \
-    _Pragma("unroll") for (int w = 0; w < NW; ++w) {                                                  \
-      const float mw = SM[w][HD];                                                                     \
-      const float f = (mw > -INFINITY) ? expf(mw - M) : 0.f;                                          \
-      L = fmaf(f, SM[w][HD + 1], L);                                                                  \
-      acc.x = fmaf(f, SM[w][c4 + 0], acc.x);                                                          \
-      acc.y = fmaf(f, SM[w][c4 + 1], acc.y);                                                          \
-      acc.z = fmaf(f, SM[w][c4 + 2], acc.z);                                                          \
-      acc.w = fmaf(f, SM[w][c4 + 3], acc.w);                                                          \
-    }                                                                                                 \
-    const float inv = 1.0f / L;                                                                       \
-    const int e = h * HD + c4;                                                                        \
-    float* dst = a.out_tiled ? out + SSRHIP_TILED_P((ROW), e, H * HD) : out + (size_t)(ROW) * H * HD + e; \
-    *reinterpret_cast<float4*>(dst) = make_float4(acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv); \
-  }
+// normalise a merged state and store it at dst. The callers write dst out (the row's place in `out`, row-major or SSRHIP_TILED): computed in
+// here, or in one function with the merge, it changes attn_rows_kernel's SGPR count or its tail's load order (profiles/attn_refactor_ab.md)
+__device__ __forceinline__ void attn_store_row(float* dst, const attn_state t) {
+  const float inv = 1.0f / t.L;
+  *reinterpret_cast<float4*>(dst) = make_float4(t.acc.x * inv, t.acc.y * inv, t.acc.z * inv, t.acc.w * inv);
+}
 
 // KV16: a.kv.pool holds 2-byte entries (same element offsets); K/V of a page then take half the registers, so DEPTH = 4 pages in flight fit
 // where the fp32 kernel holds 2. The folds run in page order whatever DEPTH is (a fold of a page past the row's last is masked: no change).
@@ -331,7 +357,7 @@ __global__ __launch_bounds__(512) void attn_rows_kernel(const ssrhip_attn_args a
   static_assert(DEPTH == 2 || (KV16 && DEPTH == 4), "pages in flight: 2, or 4 with 2-byte entries");
   typedef typename kv_types<KV16>::elem kv_elem;
   typedef typename kv_types<KV16>::vec kv_vec;
-  constexpr int LPK = HD / 4, KPI = 64 / LPK, NW = 8, KPW = SSRHIP_PAGE / NW, NI = KPW / KPI;
+  constexpr int NW = 8, LPK = attn_geom<HD, NW>::LPK, NI = attn_geom<HD, NW>::NI;
   __shared__ __attribute__((aligned(16))) float sm[NW][HD + 4];
   const int h = blockIdx.x, r = blockIdx.y;
   const int len = __builtin_amdgcn_readfirstlane(a.row_len[r]);
@@ -349,45 +375,46 @@ __global__ __launch_bounds__(512) void attn_rows_kernel(const ssrhip_attn_args a
     pid[b] = (b * 64 < npages) ? a.kv.table[(size_t)seq * a.kv.max_pages + min(b * 64 + lane, npages - 1)] : 0;
   const size_t head_off = (size_t)h * SSRHIP_PAGE * HD, v_off = (size_t)H * SSRHIP_PAGE * HD;
   const size_t page_stride = (size_t)a.kv.n_layer * 2 * H * SSRHIP_PAGE * HD;
-  const kv_elem* pool = reinterpret_cast<const kv_elem*>(a.kv.pool) + (size_t)a.layer * 2 * H * SSRHIP_PAGE * HD + head_off;
+  const attn_walk<HD, NW, kv_elem> w = {reinterpret_cast<const kv_elem*>(a.kv.pool) + (size_t)a.layer * 2 * H * SSRHIP_PAGE * HD + head_off,
+                                        page_stride, v_off, a.scale, wave, sub, c4};
   const float4 q = ld4(a.q + (size_t)r * (a.q_stride ? a.q_stride : H * HD) + h * HD + c4);
 
   kv_vec kk[DEPTH][NI], vv[DEPTH][NI];
   float m = -INFINITY, l = 0.f;
   float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
 
-#define ATTN_ISSUE(BUF, PG) ATTN_ISSUE_AT(BUF, PG, pid, npages, len)
-#define ATTN_FOLD(BUF, PG) ATTN_FOLD_AT(BUF, PG, q, len, m, l, o)
   if constexpr (DEPTH == 2) {
-    ATTN_ISSUE(0, 0)
+    ATTN_ISSUE(w, kk[0], vv[0], 0, pid, npages, len)
     for (int pg = 0; pg < npages; pg += 2) {
-      ATTN_ISSUE(1, pg + 1)
-      ATTN_FOLD(0, pg)
-      ATTN_ISSUE(0, pg + 2)
-      ATTN_FOLD(1, pg + 1)
+      ATTN_ISSUE(w, kk[1], vv[1], pg + 1, pid, npages, len)
+      attn_fold(w, kk[0], vv[0], pg, q, len, m, l, o);
+      ATTN_ISSUE(w, kk[0], vv[0], pg + 2, pid, npages, len)
+      attn_fold(w, kk[1], vv[1], pg + 1, q, len, m, l, o);
     }
   } else {
-    ATTN_ISSUE(0, 0)
-    ATTN_ISSUE(1, 1)
-    ATTN_ISSUE(2, 2)
+    ATTN_ISSUE(w, kk[0], vv[0], 0, pid, npages, len)
+    ATTN_ISSUE(w, kk[1], vv[1], 1, pid, npages, len)
+    ATTN_ISSUE(w, kk[2], vv[2], 2, pid, npages, len)
     for (int pg = 0; pg < npages; pg += 4) {
-      ATTN_ISSUE(3, pg + 3)
-      ATTN_FOLD(0, pg)
-      ATTN_ISSUE(0, pg + 4)
-      ATTN_FOLD(1, pg + 1)
-      ATTN_ISSUE(1, pg + 5)
-      ATTN_FOLD(2, pg + 2)
-      ATTN_ISSUE(2, pg + 6)
-      ATTN_FOLD(3, pg + 3)
+      ATTN_ISSUE(w, kk[3], vv[3], pg + 3, pid, npages, len)
+      attn_fold(w, kk[0], vv[0], pg, q, len, m, l, o);
+      ATTN_ISSUE(w, kk[0], vv[0], pg + 4, pid, npages, len)
+      attn_fold(w, kk[1], vv[1], pg + 1, q, len, m, l, o);
+      ATTN_ISSUE(w, kk[1], vv[1], pg + 5, pid, npages, len)
+      attn_fold(w, kk[2], vv[2], pg + 2, q, len, m, l, o);
+      ATTN_ISSUE(w, kk[2], vv[2], pg + 6, pid, npages, len)
+      attn_fold(w, kk[3], vv[3], pg + 3, q, len, m, l, o);
     }
   }
-#undef ATTN_ISSUE
-#undef ATTN_FOLD
-  ATTN_WAVE_SUM(l, o)
+  attn_wave_sum<LPK>(l, o);
   if (lane < LPK) *reinterpret_cast<float4*>(&sm[wave][c4]) = o;
   if (lane == 0) { sm[wave][HD] = m; sm[wave][HD + 1] = l; }
   __syncthreads();
-  if (threadIdx.x < LPK) ATTN_MERGE_STORE(sm, r)
+  if (threadIdx.x < LPK) {
+    const attn_state t = attn_merge_waves<HD, NW>(sm, c4);
+    const int e = h * HD + c4;
+    attn_store_row(a.out_tiled ? out + SSRHIP_TILED_P(r, e, H * HD) : out + (size_t)r * H * HD + e, t);
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -408,7 +435,7 @@ __global__ __launch_bounds__(512) void attn_rows_group_kernel(const ssrhip_attn_
                                                               const int32_t* __restrict__ n_shared, float* out) {
   typedef float kv_elem;
   typedef float4 kv_vec;
-  constexpr int LPK = HD / 4, KPI = 64 / LPK, NW = 8, KPW = SSRHIP_PAGE / NW, NI = KPW / KPI, DEPTH = 2;
+  constexpr int NW = 8, LPK = attn_geom<HD, NW>::LPK, NI = attn_geom<HD, NW>::NI, DEPTH = 2;
   __shared__ __attribute__((aligned(16))) float sm[MEMBERS][NW][HD + 4];
   const int h = blockIdx.x, r0 = blockIdx.y;
   if (__builtin_amdgcn_readfirstlane(chunk_head[r0]) != r0) return;   // uniform: not a chunk head
@@ -449,7 +476,8 @@ __global__ __launch_bounds__(512) void attn_rows_group_kernel(const ssrhip_attn_
   ns = max(ns, 0);
   const size_t head_off = (size_t)h * SSRHIP_PAGE * HD, v_off = (size_t)H * SSRHIP_PAGE * HD;
   const size_t page_stride = (size_t)a.kv.n_layer * 2 * H * SSRHIP_PAGE * HD;
-  const kv_elem* pool = reinterpret_cast<const kv_elem*>(a.kv.pool) + (size_t)a.layer * 2 * H * SSRHIP_PAGE * HD + head_off;
+  const attn_walk<HD, NW, kv_elem> w = {reinterpret_cast<const kv_elem*>(a.kv.pool) + (size_t)a.layer * 2 * H * SSRHIP_PAGE * HD + head_off,
+                                        page_stride, v_off, a.scale, wave, sub, c4};
   kv_vec kk[DEPTH][NI], vv[DEPTH][NI];
   int pid[ATTN_ROWS_MAX_PAGES / 64];                                  // page ids in registers, picked with v_readlane (see attn_rows_kernel)
 
@@ -459,17 +487,17 @@ __global__ __launch_bounds__(512) void attn_rows_group_kernel(const ssrhip_attn_
 #pragma unroll
     for (int b = 0; b < ATTN_ROWS_MAX_PAGES / 64; ++b)
       pid[b] = (b * 64 < ns) ? a.kv.table[(size_t)seq[0] * a.kv.max_pages + min(b * 64 + lane, ns - 1)] : 0;
-    ATTN_ISSUE_AT(0, 0, pid, ns, slen)
+    ATTN_ISSUE(w, kk[0], vv[0], 0, pid, ns, slen)
     for (int pg = 0; pg < ns; pg += 2) {
-      ATTN_ISSUE_AT(1, pg + 1, pid, ns, slen)
+      ATTN_ISSUE(w, kk[1], vv[1], pg + 1, pid, ns, slen)
 #pragma unroll
       for (int j = 0; j < MEMBERS; ++j)
-        if (j < nmem) ATTN_FOLD_AT(0, pg, q[j], len[j], m[j], l[j], o[j])
-      ATTN_ISSUE_AT(0, pg + 2, pid, ns, slen)
+        if (j < nmem) attn_fold(w, kk[0], vv[0], pg, q[j], len[j], m[j], l[j], o[j]);
+      ATTN_ISSUE(w, kk[0], vv[0], pg + 2, pid, ns, slen)
       if (pg + 1 < ns) {                                              // (a shared page is live for every member: beyond ns it must not be folded)
 #pragma unroll
         for (int j = 0; j < MEMBERS; ++j)
-          if (j < nmem) ATTN_FOLD_AT(1, pg + 1, q[j], len[j], m[j], l[j], o[j])
+          if (j < nmem) attn_fold(w, kk[1], vv[1], pg + 1, q[j], len[j], m[j], l[j], o[j]);
       }
     }
   }
@@ -480,12 +508,12 @@ __global__ __launch_bounds__(512) void attn_rows_group_kernel(const ssrhip_attn_
 #pragma unroll
       for (int b = 0; b < ATTN_ROWS_MAX_PAGES / 64; ++b)
         pid[b] = (b * 64 < npg[j]) ? a.kv.table[(size_t)seq[j] * a.kv.max_pages + min(b * 64 + lane, npg[j] - 1)] : 0;
-      ATTN_ISSUE_AT(0, ns, pid, npg[j], len[j])
+      ATTN_ISSUE(w, kk[0], vv[0], ns, pid, npg[j], len[j])
       for (int pg = ns; pg < npg[j]; pg += 2) {
-        ATTN_ISSUE_AT(1, pg + 1, pid, npg[j], len[j])
-        ATTN_FOLD_AT(0, pg, q[j], len[j], m[j], l[j], o[j])
-        ATTN_ISSUE_AT(0, pg + 2, pid, npg[j], len[j])
-        ATTN_FOLD_AT(1, pg + 1, q[j], len[j], m[j], l[j], o[j])
+        ATTN_ISSUE(w, kk[1], vv[1], pg + 1, pid, npg[j], len[j])
+        attn_fold(w, kk[0], vv[0], pg, q[j], len[j], m[j], l[j], o[j]);
+        ATTN_ISSUE(w, kk[0], vv[0], pg + 2, pid, npg[j], len[j])
+        attn_fold(w, kk[1], vv[1], pg + 1, q[j], len[j], m[j], l[j], o[j]);
       }
     }
   }
@@ -493,7 +521,7 @@ __global__ __launch_bounds__(512) void attn_rows_group_kernel(const ssrhip_attn_
 #pragma unroll
   for (int j = 0; j < MEMBERS; ++j) {
     if (j < nmem) {
-      ATTN_WAVE_SUM(l[j], o[j])
+      attn_wave_sum<LPK>(l[j], o[j]);
       if (lane < LPK) *reinterpret_cast<float4*>(&sm[j][wave][c4]) = o[j];
       if (lane == 0) { sm[j][wave][HD] = m[j]; sm[j][wave][HD + 1] = l[j]; }
     }
@@ -501,7 +529,11 @@ __global__ __launch_bounds__(512) void attn_rows_group_kernel(const ssrhip_attn_
   __syncthreads();
 #pragma unroll
   for (int j = 0; j < MEMBERS; ++j)
-    if (j < nmem && wave == j && lane < LPK) ATTN_MERGE_STORE(sm[j], mem[j])
+    if (j < nmem && wave == j && lane < LPK) {
+      const attn_state t = attn_merge_waves<HD, NW>(sm[j], c4);
+      const int e = h * HD + c4;
+      attn_store_row(a.out_tiled ? out + SSRHIP_TILED_P(mem[j], e, H * HD) : out + (size_t)mem[j] * H * HD + e, t);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -658,123 +690,123 @@ int check(const ssrhip_attn_args* a, const char* who) {
   return 0;
 }
 
-}  // namespace
+// The A/B knobs of the launchers below, read together at EVERY launch (tests flip them inside one process; a captured graph keeps what it
+// was captured with). A value a knob does not name selects its default.
+constexpr int ATTN_KV16_DEPTH_DEFAULT = 2, ATTN_GROUP_MEMBERS_DEFAULT = 2;
+struct attn_knobs {
+  int vat;             // SSRHIP_ATTN_VAT = -1 | 4 | 12 (profiles/r05_microbench/decode_ab_attn_vat.log), else 8: at head_dim 128 without row_seq only
+  bool head_fastest;   // SSRHIP_ATTN_HEAD_FASTEST=0: round 4's grid order of the split kernel
+  int kv16_depth;      // SSRHIP_ATTN_KV16_DEPTH, pages in flight of the kv16 walk: 2 = the fp32 kernel's structure, 4 = the registers the 2-byte
+                       // entries free hold two more pages
+  int group_members;   // SSRHIP_ATTN_GROUP_MEMBERS, member rows per workgroup of ssrhip_attn_rows_group: 2, 4 or 8 (each costs its q and (m, l, o):
+                       // 10 VGPRs at any head_dim). 2 by the launch bench (profiles/share_prompt_ab.md, 32 rows, context 520): the members' own
+                       // walks run one after the other in ONE workgroup, each a chain of dependent round trips, so larger chunks save bytes and
+                       // lose more time than the bytes were worth
+};
+attn_knobs read_attn_knobs() {
+  const int vat = getenv_int("SSRHIP_ATTN_VAT", 8), depth = getenv_int("SSRHIP_ATTN_KV16_DEPTH", ATTN_KV16_DEPTH_DEFAULT);
+  const int members = getenv_int("SSRHIP_ATTN_GROUP_MEMBERS", ATTN_GROUP_MEMBERS_DEFAULT);
+  attn_knobs k;
+  k.vat = (vat == 4 || vat == 12) ? vat : (vat < 0 ? -1 : 8);
+  k.head_fastest = getenv_on("SSRHIP_ATTN_HEAD_FASTEST", true);
+  k.kv16_depth = (depth == 2 || depth == 4) ? depth : ATTN_KV16_DEPTH_DEFAULT;
+  k.group_members = (members == 2 || members == 4 || members == 8) ? members : ATTN_GROUP_MEMBERS_DEFAULT;
+  return k;
+}
+
+// f(std::integral_constant<int, V>()) for the V among Vs that equals v (the checks in front of a launch leave no other v): a run-time
+// head_dim, depth, member count or VAT becomes the kernel's template argument
+template <int... Vs, class F>
+void dispatch_int(const int v, F&& f) {
+  (void)((v == Vs ? (f(std::integral_constant<int, Vs>()), true) : false) || ...);
+}
 
 // gridDim.z / gridDim.y carry the row index and are limited to 65535: longer row lists (a 16-row prefill has ~4k rows per
-// sequence) are issued in slices of at most 65535 rows, each slice seeing its own sub-arrays.
-static ssrhip_attn_args row_slice(const ssrhip_attn_args& a, int r0, int n) {
+// sequence) are issued in slices of at most 65535 rows, each slice seeing its own sub-arrays (and its rows of *out, where there is one).
+// A slice without row_seq keeps none: its row r would then be sequence r, which the decode launcher refuses; the combine reads none.
+enum { MAX_GRID_ROWS = 65535 };
+ssrhip_attn_args row_slice(const ssrhip_attn_args& a, int r0, int n, float** out = nullptr) {
   ssrhip_attn_args s = a;
   const size_t H = a.kv.n_head, HD = a.kv.head_dim;
   s.q = a.q + (size_t)r0 * (a.q_stride ? a.q_stride : H * HD);
-  s.row_seq = a.row_seq + r0;
+  if (a.row_seq) s.row_seq = a.row_seq + r0;
   s.row_len = a.row_len + r0;
   s.part_o = a.part_o + (size_t)r0 * H * a.max_splits * HD;
   s.part_ml = a.part_ml + (size_t)r0 * H * a.max_splits * 2;
   s.R = n;
+  if (out) *out += (size_t)r0 * H * HD;
   return s;
 }
-enum { MAX_GRID_ROWS = 65535 };
 
-// the argument contract of ssrhip_attn_prefill and ssrhip_attn_prefill_kv16
-static int prefill_check(const ssrhip_attn_args* a, const int32_t* seq_start, int32_t n_seq, int32_t max_len, const float* out, const char* who) {
+// ssrhip_attn_prefill and ssrhip_attn_prefill_kv16: one argument contract, one grid
+int prefill_launch(const bool kv16, const ssrhip_attn_args* a, const int32_t* seq_start, int32_t n_seq, int32_t max_len, float* out, ssrhip_stream_t stream,
+                   const char* who) {
   SSR_REQUIRE(a && a->q && a->kv.pool && a->kv.table && seq_start && out, "%s: null argument", who);
   SSR_REQUIRE(a->kv.head_dim == 64 || a->kv.head_dim == 128, "%s: head_dim %d not in {64,128}", who, a->kv.head_dim);
   SSR_REQUIRE(n_seq > 0 && n_seq <= 65535 && max_len > 0 && a->kv.n_head <= 65535, "%s: bad n_seq / max_len", who);
   SSR_REQUIRE((a->q_stride ? a->q_stride : a->kv.n_head * a->kv.head_dim) % 4 == 0, "%s: q_stride must be a multiple of 4", who);
-  return 0;
-}
-
-extern "C" int ssrhip_attn_prefill(const ssrhip_attn_args* a, const int32_t* seq_start, int32_t n_seq, int32_t max_len, float* out,
-                                   ssrhip_stream_t stream) {
-  if (int e = prefill_check(a, seq_start, n_seq, max_len, out, "ssrhip_attn_prefill")) return e;
-  dim3 grid((max_len + 127) / 128, a->kv.n_head, n_seq);
-  if (a->kv.head_dim == 128) hipLaunchKernelGGL(attn_prefill_kernel<128>, grid, dim3(256), 0, (hipStream_t)stream, *a, seq_start, out);
-  else hipLaunchKernelGGL(attn_prefill_kernel<64>, grid, dim3(256), 0, (hipStream_t)stream, *a, seq_start, out);
+  const dim3 grid((max_len + 127) / 128, a->kv.n_head, n_seq);
+  dispatch_int<64, 128>(a->kv.head_dim, [&](auto HD) {
+    constexpr int hd = decltype(HD)::value;
+    if (kv16) hipLaunchKernelGGL(attn_prefill_kv16_kernel<hd>, grid, dim3(256), 0, (hipStream_t)stream, *a, seq_start, out);
+    else hipLaunchKernelGGL(attn_prefill_kernel<hd>, grid, dim3(256), 0, (hipStream_t)stream, *a, seq_start, out);
+  });
   SSR_LAUNCH_CHECK();
   return 0;
 }
 
-extern "C" int ssrhip_attn_prefill_kv16(const ssrhip_attn_args* a, const int32_t* seq_start, int32_t n_seq, int32_t max_len, float* out,
-                                        ssrhip_stream_t stream) {
-  if (int e = prefill_check(a, seq_start, n_seq, max_len, out, "ssrhip_attn_prefill_kv16")) return e;
-  dim3 grid((max_len + 127) / 128, a->kv.n_head, n_seq);
-  if (a->kv.head_dim == 128) hipLaunchKernelGGL(attn_prefill_kv16_kernel<128>, grid, dim3(256), 0, (hipStream_t)stream, *a, seq_start, out);
-  else hipLaunchKernelGGL(attn_prefill_kv16_kernel<64>, grid, dim3(256), 0, (hipStream_t)stream, *a, seq_start, out);
-  SSR_LAUNCH_CHECK();
-  return 0;
-}
-
-// the argument contract of ssrhip_attn_rows and ssrhip_attn_rows_kv16
-static int rows_check(const ssrhip_attn_args* a, const float* out, const char* who) {
+// ssrhip_attn_rows, ssrhip_attn_rows_kv16 and ssrhip_attn_rows_group_m: one argument contract, one 8-wave workgroup per (head, row)
+enum rows_form { ROWS_FP32, ROWS_KV16, ROWS_GROUP };
+int rows_launch(const rows_form form, const ssrhip_attn_args* a, const int32_t* chunk_head, const int32_t* n_shared, const int32_t members, float* out,
+                ssrhip_stream_t stream, const char* who) {
   if (int e = check(a, who)) return e;
   SSR_REQUIRE(out && out != a->q, "%s: out is null or aliases q", who);
   SSR_REQUIRE(!a->out_tiled || a->R <= 32, "%s: tiled output needs R <= 32", who);
   SSR_REQUIRE(a->R <= MAX_GRID_ROWS, "%s: R too large", who);
   SSR_REQUIRE(a->kv.max_pages <= ATTN_ROWS_MAX_PAGES, "%s: more than %d pages per row", who, ATTN_ROWS_MAX_PAGES);
+  if (form == ROWS_GROUP) {
+    SSR_REQUIRE(chunk_head && n_shared, "%s: null chunk_head / n_shared", who);
+    SSR_REQUIRE(members == 2 || members == 4 || members == 8, "%s: %d members per chunk not in {2,4,8}", who, members);
+  }
+  const dim3 grid(a->kv.n_head, a->R), block(512);
+  const hipStream_t s = (hipStream_t)stream;
+  dispatch_int<64, 128>(a->kv.head_dim, [&](auto HD) {
+    constexpr int hd = decltype(HD)::value;
+    if (form == ROWS_FP32) hipLaunchKernelGGL(attn_rows_kernel<hd>, grid, block, 0, s, *a, out);
+    else if (form == ROWS_KV16)
+      dispatch_int<2, 4>(read_attn_knobs().kv16_depth, [&](auto DEPTH) {
+        hipLaunchKernelGGL((attn_rows_kernel<hd, true, decltype(DEPTH)::value>), grid, block, 0, s, *a, out);
+      });
+    else
+      dispatch_int<2, 4, 8>(members, [&](auto MEMBERS) {
+        hipLaunchKernelGGL((attn_rows_group_kernel<hd, decltype(MEMBERS)::value>), grid, block, 0, s, *a, chunk_head, n_shared, out);
+      });
+  });
+  SSR_LAUNCH_CHECK();
   return 0;
 }
 
+}  // namespace
+
+extern "C" int ssrhip_attn_prefill(const ssrhip_attn_args* a, const int32_t* seq_start, int32_t n_seq, int32_t max_len, float* out, ssrhip_stream_t stream) {
+  return prefill_launch(false, a, seq_start, n_seq, max_len, out, stream, "ssrhip_attn_prefill");
+}
+extern "C" int ssrhip_attn_prefill_kv16(const ssrhip_attn_args* a, const int32_t* seq_start, int32_t n_seq, int32_t max_len, float* out, ssrhip_stream_t stream) {
+  return prefill_launch(true, a, seq_start, n_seq, max_len, out, stream, "ssrhip_attn_prefill_kv16");
+}
 extern "C" int ssrhip_attn_rows(const ssrhip_attn_args* a, float* out, ssrhip_stream_t stream) {
-  if (int e = rows_check(a, out, "ssrhip_attn_rows")) return e;
-  dim3 grid(a->kv.n_head, a->R);
-  if (a->kv.head_dim == 128) hipLaunchKernelGGL(attn_rows_kernel<128>, grid, dim3(512), 0, (hipStream_t)stream, *a, out);
-  else hipLaunchKernelGGL(attn_rows_kernel<64>, grid, dim3(512), 0, (hipStream_t)stream, *a, out);
-  SSR_LAUNCH_CHECK();
-  return 0;
+  return rows_launch(ROWS_FP32, a, nullptr, nullptr, 0, out, stream, "ssrhip_attn_rows");
 }
-
-// Pages in flight of the kv16 walk: 2 = the fp32 kernel's structure (the default), 4 = the registers the 2-byte entries free hold two more
-// pages. A/B knob SSRHIP_ATTN_KV16_DEPTH, read at every launch (a captured graph keeps what it was captured with).
-constexpr int ATTN_KV16_DEPTH_DEFAULT = 2;
-
 extern "C" int ssrhip_attn_rows_kv16(const ssrhip_attn_args* a, float* out, ssrhip_stream_t stream) {
-  if (int e = rows_check(a, out, "ssrhip_attn_rows_kv16")) return e;
-  int depth = ATTN_KV16_DEPTH_DEFAULT;
-  if (const char* e = getenv("SSRHIP_ATTN_KV16_DEPTH")) { const int v = atoi(e); if (v == 2 || v == 4) depth = v; }
-  dim3 grid(a->kv.n_head, a->R);
-  hipStream_t s = (hipStream_t)stream;
-  if (a->kv.head_dim == 128) {
-    if (depth == 4) hipLaunchKernelGGL((attn_rows_kernel<128, true, 4>), grid, dim3(512), 0, s, *a, out);
-    else hipLaunchKernelGGL((attn_rows_kernel<128, true, 2>), grid, dim3(512), 0, s, *a, out);
-  } else {
-    if (depth == 4) hipLaunchKernelGGL((attn_rows_kernel<64, true, 4>), grid, dim3(512), 0, s, *a, out);
-    else hipLaunchKernelGGL((attn_rows_kernel<64, true, 2>), grid, dim3(512), 0, s, *a, out);
-  }
-  SSR_LAUNCH_CHECK();
-  return 0;
+  return rows_launch(ROWS_KV16, a, nullptr, nullptr, 0, out, stream, "ssrhip_attn_rows_kv16");
 }
-
-// Workgroup chunk size of ssrhip_attn_rows_group: 2, 4 or 8 member rows per workgroup (each member costs its q and (m, l, o): 10 VGPRs at
-// any head_dim). A/B knob SSRHIP_ATTN_GROUP_MEMBERS, read at every launch (a captured graph keeps what it was captured with).
-// 2 by the launch bench (profiles/share_prompt_ab.md, 32 rows, context 520): the members' own walks run one after the other in ONE
-// workgroup, each a chain of dependent round trips, so larger chunks save bytes and lose more time than the bytes were worth.
-constexpr int ATTN_GROUP_MEMBERS_DEFAULT = 2;
-extern "C" int ssrhip_attn_group_members(void) {
-  if (const char* e = getenv("SSRHIP_ATTN_GROUP_MEMBERS")) { const int v = atoi(e); if (v == 2 || v == 4 || v == 8) return v; }
-  return ATTN_GROUP_MEMBERS_DEFAULT;
-}
-
+extern "C" int ssrhip_attn_group_members(void) { return read_attn_knobs().group_members; }
 // the launch with the chunk size given by the caller (the decode engine: the size ITS chunks were cut for, whatever the knob says now)
-extern "C" int ssrhip_attn_rows_group_m(const ssrhip_attn_args* a, const int32_t* chunk_head, const int32_t* n_shared, int32_t members,
-                                        float* out, ssrhip_stream_t stream) {
-  if (int e = rows_check(a, out, "ssrhip_attn_rows_group")) return e;
-  SSR_REQUIRE(chunk_head && n_shared, "ssrhip_attn_rows_group: null chunk_head / n_shared");
-  SSR_REQUIRE(members == 2 || members == 4 || members == 8, "ssrhip_attn_rows_group: %d members per chunk not in {2,4,8}", members);
-  dim3 grid(a->kv.n_head, a->R);
-  hipStream_t s = (hipStream_t)stream;
-#define GROUP_LAUNCH(HD_, M_) hipLaunchKernelGGL((attn_rows_group_kernel<HD_, M_>), grid, dim3(512), 0, s, *a, chunk_head, n_shared, out)
-  if (a->kv.head_dim == 128) {
-    if (members == 2) GROUP_LAUNCH(128, 2); else if (members == 4) GROUP_LAUNCH(128, 4); else GROUP_LAUNCH(128, 8);
-  } else {
-    if (members == 2) GROUP_LAUNCH(64, 2); else if (members == 4) GROUP_LAUNCH(64, 4); else GROUP_LAUNCH(64, 8);
-  }
-#undef GROUP_LAUNCH
-  SSR_LAUNCH_CHECK();
-  return 0;
+extern "C" int ssrhip_attn_rows_group_m(const ssrhip_attn_args* a, const int32_t* chunk_head, const int32_t* n_shared, int32_t members, float* out,
+                                        ssrhip_stream_t stream) {
+  return rows_launch(ROWS_GROUP, a, chunk_head, n_shared, members, out, stream, "ssrhip_attn_rows_group");
 }
-
-extern "C" int ssrhip_attn_rows_group(const ssrhip_attn_args* a, const int32_t* chunk_head, const int32_t* n_shared, float* out,
-                                      ssrhip_stream_t stream) {
+extern "C" int ssrhip_attn_rows_group(const ssrhip_attn_args* a, const int32_t* chunk_head, const int32_t* n_shared, float* out, ssrhip_stream_t stream) {
   return ssrhip_attn_rows_group_m(a, chunk_head, n_shared, ssrhip_attn_group_members(), out, stream);
 }
 
@@ -784,24 +816,19 @@ extern "C" int ssrhip_attn_decode(const ssrhip_attn_args* a, ssrhip_stream_t str
   SSR_REQUIRE(a->R <= MAX_GRID_ROWS || a->row_seq, "ssrhip_attn_decode: more than %d rows need an explicit row_seq", MAX_GRID_ROWS);
   for (int r0 = 0; r0 < a->R; r0 += MAX_GRID_ROWS) {
     const int n = min(a->R - r0, (int)MAX_GRID_ROWS);
-    const ssrhip_attn_args s = a->R <= MAX_GRID_ROWS ? *a : row_slice(*a, r0, n);
-    int hf = 1;                                                      // SSRHIP_ATTN_HEAD_FASTEST=0: round 4's grid order (A/B knob, read per call)
-    if (const char* e = getenv("SSRHIP_ATTN_HEAD_FASTEST")) hf = e[0] != '0';
-    dim3 grid(hf ? s.kv.n_head : s.max_splits, hf ? s.max_splits : s.kv.n_head, n);
-    if (s.kv.head_dim == 128) {
-      if (s.row_seq) hipLaunchKernelGGL((attn_decode_kernel<128, true>), grid, dim3(256), 0, (hipStream_t)stream, s, hf);
-      else {
-        int vat = 8;                                                 // SSRHIP_ATTN_VAT = -1 | 4 | 12: A/B knob (profiles/r05_microbench/decode_ab_attn_vat.log), read per call
-        if (const char* e = getenv("SSRHIP_ATTN_VAT")) vat = atoi(e);
-        if (vat == 4) hipLaunchKernelGGL((attn_decode_kernel<128, false, 4>), grid, dim3(256), 0, (hipStream_t)stream, s, hf);
-        else if (vat == 12) hipLaunchKernelGGL((attn_decode_kernel<128, false, 12>), grid, dim3(256), 0, (hipStream_t)stream, s, hf);
-        else if (vat < 0) hipLaunchKernelGGL((attn_decode_kernel<128, false>), grid, dim3(256), 0, (hipStream_t)stream, s, hf);
-        else hipLaunchKernelGGL((attn_decode_kernel<128, false, 8>), grid, dim3(256), 0, (hipStream_t)stream, s, hf);
-      }
-    } else {
-      if (s.row_seq) hipLaunchKernelGGL((attn_decode_kernel<64, true>), grid, dim3(256), 0, (hipStream_t)stream, s, hf);
-      else hipLaunchKernelGGL((attn_decode_kernel<64, false>), grid, dim3(256), 0, (hipStream_t)stream, s, hf);
-    }
+    const ssrhip_attn_args s = row_slice(*a, r0, n);
+    const attn_knobs k = read_attn_knobs();
+    const int hf = k.head_fastest;
+    const dim3 grid(hf ? s.kv.n_head : s.max_splits, hf ? s.max_splits : s.kv.n_head, n);
+    dispatch_int<64, 128>(s.kv.head_dim, [&](auto HD) {
+      constexpr int hd = decltype(HD)::value;
+      if (s.row_seq) hipLaunchKernelGGL((attn_decode_kernel<hd, true>), grid, dim3(256), 0, (hipStream_t)stream, s, hf);
+      else if constexpr (hd == 128)
+        dispatch_int<-1, 4, 8, 12>(k.vat, [&](auto VAT) {
+          hipLaunchKernelGGL((attn_decode_kernel<128, false, decltype(VAT)::value>), grid, dim3(256), 0, (hipStream_t)stream, s, hf);
+        });
+      else hipLaunchKernelGGL((attn_decode_kernel<hd, false>), grid, dim3(256), 0, (hipStream_t)stream, s, hf);
+    });
     SSR_LAUNCH_CHECK();
   }
   return 0;
@@ -811,20 +838,14 @@ extern "C" int ssrhip_attn_combine(const ssrhip_attn_args* a, float* out, ssrhip
   if (int e = check(a, "ssrhip_attn_combine")) return e;
   SSR_REQUIRE(out && a->part_o && a->part_ml, "ssrhip_attn_combine: out or the partial buffers are null");
   SSR_REQUIRE(!a->out_tiled || a->R <= 32, "ssrhip_attn_combine: tiled output needs R <= 32");
-  const size_t D = (size_t)a->kv.n_head * a->kv.head_dim;
   for (int r0 = 0; r0 < a->R; r0 += MAX_GRID_ROWS) {
     const int n = min(a->R - r0, (int)MAX_GRID_ROWS);
-    ssrhip_attn_args s = *a;
     float* o = out;
-    if (a->R > MAX_GRID_ROWS) {            // the combine never reads q / row_seq: only the per-row arrays move
-      s.row_len = a->row_len + r0;
-      s.part_o = a->part_o + (size_t)r0 * a->kv.n_head * a->max_splits * a->kv.head_dim;
-      s.part_ml = a->part_ml + (size_t)r0 * a->kv.n_head * a->max_splits * 2;
-      s.R = n;
-      o = out + (size_t)r0 * D;
-    }
-    if (s.kv.head_dim == 128) hipLaunchKernelGGL(attn_combine_kernel<128>, dim3((s.kv.n_head + 1) / 2, n), dim3(64), 0, (hipStream_t)stream, s, o);
-    else hipLaunchKernelGGL(attn_combine_kernel<64>, dim3((s.kv.n_head + 3) / 4, n), dim3(64), 0, (hipStream_t)stream, s, o);
+    const ssrhip_attn_args s = row_slice(*a, r0, n, &o);
+    dispatch_int<64, 128>(s.kv.head_dim, [&](auto HD) {
+      constexpr int hd = decltype(HD)::value, hpw = 256 / hd;          // heads per one-wave workgroup
+      hipLaunchKernelGGL(attn_combine_kernel<hd>, dim3((s.kv.n_head + hpw - 1) / hpw, n), dim3(64), 0, (hipStream_t)stream, s, o);
+    });
     SSR_LAUNCH_CHECK();
   }
   return 0;

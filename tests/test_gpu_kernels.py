@@ -669,6 +669,64 @@ def test_attention_decode_and_combine(L, hd):
         torch.testing.assert_close(dy.cpu(), F.linear(ref[r0:r0 + 2], Wt), rtol=2e-5, atol=2e-5)
 
 
+@pytest.mark.parametrize("hd", [64, 128])
+def test_attention_decode_launch_variants(L, hd, monkeypatch):
+    """Every arm of the split kernel's launcher: the V-request points SSRHIP_ATTN_VAT = -1 / 4 / 12 (and 0, which is the default 8), the
+    page-fastest grid SSRHIP_ATTN_HEAD_FASTEST=0 and rows with an explicit sequence (row_seq, here the reversed row order). Lengths: one
+    key, a wave boundary, a full page, one key on the next page, the third page. The knobs only move requests and workgroups ("same
+    arithmetic in the same order"), so without row_seq the partials and the combined rows equal the unset launch's bit for bit."""
+    g = torch.Generator().manual_seed(1000 + hd)
+    H, n_layer, max_pages, layer = 2, 2, 3, 1
+    lens = [1, 33, 128, 129, 257]
+    R = len(lens)
+    pool, table = _make_cache(R, max_pages, n_layer, H, hd, g)
+    q = torch.randn(R, H * hd, generator=g)
+
+    def reference(seq_of_row):
+        ref = torch.zeros(R, H * hd)
+        for r, ln in enumerate(lens):
+            for h in range(H):
+                k = _gather(pool, table, seq_of_row[r], layer, 0, h, ln)
+                v = _gather(pool, table, seq_of_row[r], layer, 1, h, ln)
+                o = F.scaled_dot_product_attention(q[r, h * hd:(h + 1) * hd].view(1, 1, 1, hd), k.view(1, 1, ln, hd), v.view(1, 1, ln, hd))
+                ref[r, h * hd:(h + 1) * hd] = o.view(-1)
+        return ref
+
+    own, rev = list(range(R)), list(range(R - 1, -1, -1))
+    refs = {False: reference(own), True: reference(rev)}
+    dpool, dtable, dq = dev(pool), dev(table), dev(q)
+    dlen, dseq = dev(torch.tensor(lens, dtype=torch.int32)), dev(torch.tensor(rev, dtype=torch.int32))
+
+    def launch(env, with_seq):
+        for name in ("SSRHIP_ATTN_VAT", "SSRHIP_ATTN_HEAD_FASTEST"):
+            monkeypatch.delenv(name, raising=False)
+        for name, value in env.items():
+            monkeypatch.setenv(name, value)
+        part_o = torch.full((R * H * max_pages * hd,), float("nan"), device="cuda")      # a workgroup that did not run leaves NaN
+        part_ml = torch.full((R * H * max_pages * 2,), float("nan"), device="cuda")
+        out = torch.full((R, H * hd), float("nan"), device="cuda")
+        a = _lib.AttnArgs()
+        a.q, a.q_stride = dq.data_ptr(), 0
+        a.kv = _lib.KV(dpool.data_ptr(), dtable.data_ptr(), max_pages, n_layer, H, hd)
+        a.layer, a.row_seq, a.row_len, a.R, a.max_splits = layer, dseq.data_ptr() if with_seq else 0, dlen.data_ptr(), R, max_pages
+        a.scale, a.part_o, a.part_ml = 1.0 / math.sqrt(hd), part_o.data_ptr(), part_ml.data_ptr()
+        _lib.check(L.ssrhip_attn_decode(C.byref(a), _lib.stream_ptr()))
+        _lib.check(L.ssrhip_attn_combine(C.byref(a), out.data_ptr(), _lib.stream_ptr()))
+        sync()
+        return part_o.cpu(), part_ml.cpu(), out.cpu()
+
+    bits = lambda t: t.view(torch.int32)                                  # NaN (the pages past a row's last) compares equal to itself
+    base = launch({}, False)
+    torch.testing.assert_close(base[2], refs[False], rtol=2e-5, atol=2e-5)
+    for env in ({"SSRHIP_ATTN_VAT": "-1"}, {"SSRHIP_ATTN_VAT": "4"}, {"SSRHIP_ATTN_VAT": "12"}, {"SSRHIP_ATTN_VAT": "0"},
+                {"SSRHIP_ATTN_HEAD_FASTEST": "0"}):
+        got = launch(env, False)
+        torch.testing.assert_close(got[2], refs[False], rtol=2e-5, atol=2e-5, msg=lambda m: f"{env}: {m}")
+        for name, x, y in zip(("part_o", "part_ml", "out"), got, base):
+            assert torch.equal(bits(x), bits(y)), (env, name)
+    torch.testing.assert_close(launch({}, True)[2], refs[True], rtol=2e-5, atol=2e-5)
+
+
 def test_attention_rows_beyond_64_pages(L):
     """ssrhip_attn_rows keeps a row's page ids in 4 VGPRs (64 pages each, picked with v_readlane): contexts that cross the 64-,
     128- and 192-page register boundaries (8,192 / 16,384 / 24,576 positions), a shuffled table, both register-pair parities of

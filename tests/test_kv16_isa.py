@@ -2,15 +2,10 @@
 scratch, the K / V loads of the two attention kernels are 8-byte vector loads (half the bytes of the fp32 kernels' 16-byte loads, the same
 number of them), and their VGPR counts are printed and held below what their workgroup sizes allow."""
 import os
-import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ssr-speech_amd", "csrc")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+from helpers_isa import HIPCC, compile_unit, kernel_meta, sym as _sym, body as _body, loads as _loads
 
 pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 
@@ -22,43 +17,14 @@ PREFILL32 = {hd: f"attn_prefill_kernelILi{hd}E" for hd in (64, 128)}
 SCATTER16 = "kv_scatter_kernelILb1E"
 
 
-def _compile(tmp, name):
-    out = tmp / (name + ".s")
-    cmd = [HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", f"-I{ROOT}/include", f"-I{CSRC}", "-ffp-contract=off", "-S", "--cuda-device-only",
-           os.path.join(CSRC, name + ".hip"), "-o", str(out)]
-    subprocess.run(cmd, check=True, capture_output=True, timeout=600)
-    return open(out).read()
-
-
 @pytest.fixture(scope="module")
-def asm(tmp_path_factory):
-    tmp = tmp_path_factory.mktemp("isa")
-    return {name: _compile(tmp, name) for name in ("attn", "gemm")}
+def asm():
+    return {name: compile_unit(name) for name in ("attn", "gemm")}
 
 
 def _kernel_meta(asm):
-    """symbol -> (vgpr_count, private_segment_fixed_size) from the .amdhsa metadata"""
-    meta = {}
-    for m in re.finditer(r"^  - \.agpr_count:.*?(?=^  - \.agpr_count:|^amdhsa\.target:)", asm, re.S | re.M):
-        t = m.group(0)
-        g = lambda key: int(re.search(key + r":\s+(\d+)", t).group(1))
-        meta[re.search(r"\.name:\s+(\S+)", t).group(1)] = (g(r"\.vgpr_count"), g(r"\.private_segment_fixed_size"))
-    return meta
-
-
-def _body(asm, symbol):
-    start = asm.index("\n" + symbol + ":")
-    return asm[start:asm.index(".Lfunc_end", start)]
-
-
-def _sym(meta, piece):
-    found = [k for k in meta if piece in k]
-    assert len(found) == 1, (piece, found)
-    return found[0]
-
-
-def _loads(body, width):
-    return len(re.findall(rf"^\s+global_load_dword{width}\b", body, re.M))
+    """symbol -> (vgpr_count, private_segment_fixed_size)"""
+    return {name: counts[:2] for name, counts in kernel_meta(asm).items()}
 
 
 def test_new_kernels_use_no_scratch_and_their_vgprs_fit(asm):

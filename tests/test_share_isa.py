@@ -2,15 +2,10 @@
 no instantiation uses scratch, each stays within the 256 VGPRs a 512-thread workgroup allows, and K / V arrive in 16-byte vector loads,
 as many per issue site as in the ungrouped kernel. The counts are printed; profiles/share_isa.md holds them."""
 import os
-import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ssr-speech_amd", "csrc")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+from helpers_isa import HIPCC, compile_unit, kernel_meta as _kernel_meta, sym as _sym, body as _body, loads as _loads
 
 pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 
@@ -20,37 +15,8 @@ ROWS32 = {hd: f"attn_rows_kernelILi{hd}ELb0ELi2E" for hd in HDS}
 
 
 @pytest.fixture(scope="module")
-def asm(tmp_path_factory):
-    out = tmp_path_factory.mktemp("isa") / "attn.s"
-    cmd = [HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", f"-I{ROOT}/include", f"-I{CSRC}", "-ffp-contract=off", "-S", "--cuda-device-only",
-           os.path.join(CSRC, "attn.hip"), "-o", str(out)]
-    subprocess.run(cmd, check=True, capture_output=True, timeout=600)
-    return open(out).read()
-
-
-def _kernel_meta(asm):
-    """symbol -> (vgpr_count, private_segment_fixed_size, group_segment_fixed_size) from the .amdhsa metadata"""
-    meta = {}
-    for m in re.finditer(r"^  - \.agpr_count:.*?(?=^  - \.agpr_count:|^amdhsa\.target:)", asm, re.S | re.M):
-        t = m.group(0)
-        g = lambda key: int(re.search(key + r":\s+(\d+)", t).group(1))
-        meta[re.search(r"\.name:\s+(\S+)", t).group(1)] = (g(r"\.vgpr_count"), g(r"\.private_segment_fixed_size"), g(r"\.group_segment_fixed_size"))
-    return meta
-
-
-def _sym(meta, piece):
-    found = [k for k in meta if piece in k]
-    assert len(found) == 1, (piece, found)
-    return found[0]
-
-
-def _body(asm, symbol):
-    start = asm.index("\n" + symbol + ":")
-    return asm[start:asm.index(".Lfunc_end", start)]
-
-
-def _loads(body, width):
-    return len(re.findall(rf"^\s+global_load_dword{width}\b", body, re.M))
+def asm():
+    return compile_unit("attn")
 
 
 def test_every_instantiation_exists_without_scratch_within_256_vgprs(asm):
