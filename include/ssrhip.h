@@ -310,6 +310,19 @@ typedef struct ssrhip_sample_args {
 
 int ssrhip_sample(const ssrhip_sample_args* a, ssrhip_stream_t stream);
 
+/* The batched stream's hand-off from the sampler to the codec (DESIGN.md Part I.16): for utterance u < n_utt, generated frame f in
+ * [f0[u], f1[u]) and codebook k < K,
+ *     codes_out[u][k][col0[u] + f] = generated[u][step0[u] + f + k][k]
+ * — the delay pattern undone (revert_pattern_sequence, models/ssr.py:438-464) — as the [B][K][cap] int32 block ssrhip_rvq_decode
+ * reads. An id outside [0, bins) is stored clamped and sets *flag = 1 (never cleared here: the caller zeroes it once and reads it after
+ * every launch). The ranges are one int32 table [4][n_utt] = step0 | f0 | f1 | col0, given twice: `ranges_host` is checked here before
+ * any HIP call (f0 <= f1, every step < max_steps, every column < cap), `ranges_dev` is the copy the kernel reads (pushed by the caller
+ * ahead of this call on the same stream, as the page table is) and checks again. One launch whatever n_utt is; none when every range
+ * is empty. generated = [n_utt][max_steps][K], the sampler's buffer. */
+int ssrhip_stream_gather(const int32_t* generated, int32_t n_utt, int32_t max_steps, int32_t K, const int32_t* ranges_host,
+                         const int32_t* ranges_dev, int32_t* codes_out, int32_t B, int32_t cap, int32_t bins, int32_t* flag,
+                         ssrhip_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Dense fp32 GEMM on the matrix cores (v_mfma_f32_32x32x2_f32, exact fp32 FMA chain) for the
  * prefill rows and the codec:  C[M][N] = epi( A[M][K] . W[N][K]^T + bias[N] ), act/residual as GEMV.

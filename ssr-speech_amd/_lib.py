@@ -196,6 +196,8 @@ SYMBOLS = [
     ("ssrhip_attn_rows_group_m", C.c_int, [C.POINTER(AttnArgs), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     ("ssrhip_embed", C.c_int, [C.POINTER(EmbedArgs), C.c_void_p]),
     ("ssrhip_sample", C.c_int, [C.POINTER(SampleArgs), C.c_void_p]),
+    ("ssrhip_stream_gather", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                       C.c_int32, C.c_void_p, C.c_void_p]),
     ("ssrhip_gemm", C.c_int, [C.POINTER(GemmArgs), C.c_void_p]),
     ("ssrhip_split_weights", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     ("ssrhip_gemm_w1", C.c_int, [C.POINTER(GemmArgs), C.c_void_p]),

@@ -15,6 +15,7 @@ import math
 import os
 from typing import List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from .. import _lib
@@ -813,6 +814,13 @@ class WMEncodecModel:
         of one pass over the layers behind the LSTM."""
         return DecodeStream(self, int(max_frames), int(max_window))
 
+    def decode_stream_batch(self, prompt_lens: Sequence[int], max_new_frames: int, max_window: int = 16) -> "BatchDecodeStream":
+        """`decode_stream` for B utterances whose frames are generated in lock-step: item u has a prompt of prompt_lens[u] frames
+        (`push_prompts`, never returned) and at most `max_new_frames` generated ones; `advance(new_frames, ended)` returns, per item, the
+        samples that have become final. Per item the concatenation is `decode` of that item's codes at batch 1, without its prompt part,
+        within the bound that holds a batched decode to the batch-1 one. Every buffer is allocated here (`BatchDecodeStream`)."""
+        return BatchDecodeStream(self, [int(p) for p in prompt_lens], int(max_new_frames), int(max_window))
+
     # ------------------------------------------------------------------ ragged batches (items of different lengths in one pass)
     # cost model of one dense pass over a bucket, in microseconds per frame of its longest item: every frame is one LSTM time step
     # of each layer (a latency-bound launch whose cost hardly depends on the batch) + the convolutions' share per item
@@ -1187,3 +1195,360 @@ class DecodeStream:
             self._stage1(True)
             self._stage2(True)
         return self._out(a)
+
+
+# ----------------------------------------------------------------------------- streamed decode of a lock-step batch (DESIGN.md Part I.16)
+def batch_align_plan(prompt_lens: Sequence[int], pl0: int) -> dict:
+    """The one time axis of a `BatchDecodeStream`: item u's frame t lives in row off[u] + t with off[u] = pl0 + (P_max - P_u), so every
+    prompt ENDS at row E = pl0 + P_max and generated frame j of every item is row E + j. `zero[u]` = the rows [0, off[u]) in front of
+    item u's first frame, whose LSTM input and skip input are zeroed so that its state is exactly zero when its first frame arrives."""
+    lens = [int(p) for p in prompt_lens]
+    if not lens or min(lens) < 1:
+        raise ValueError(f"decode_stream_batch needs at least one item and a prompt of at least one frame each, got {lens}")
+    p_max = max(lens)
+    off = [int(pl0) + p_max - p for p in lens]
+    return dict(off=off, E=int(pl0) + p_max, zero=[(0, o) for o in off])
+
+
+def batch_stage1_range(n1: int, tops: Sequence[int], ended: Sequence[bool], closed: Sequence[bool], lookahead: int) -> Tuple[int, int]:
+    """The rows [a, b) ONE batched stage-1 call (first convolution + LSTM, all items) advances over. tops[u] = the row behind item u's
+    last arrived frame. A live item allows the rows whose look-ahead has arrived, tops[u] - lookahead; the call goes as far as every live
+    item allows. An item that has ended adds no limit (behind its end its rows are not read by anyone): it is CLOSED by the first call
+    with b >= tops[u]. When no live item is left the call runs to the last end."""
+    live = [t - int(lookahead) for t, e in zip(tops, ended) if not e]
+    if live:
+        b = min(live)
+    else:
+        b = max([t for t, c in zip(tops, closed) if not c], default=n1)
+    return int(n1), max(int(b), int(n1))
+
+
+def batch_window_item(off: int, E: int, n2: int, top: int, n1: int, closed: bool, margins: Tuple[int, int], max_window: int, hop: int,
+                      few_min_t: int, few_eligible: bool):
+    """The next stage-2 window of ONE item of the batch, in rows, decided exactly as `DecodeStream._stage2` decides it for that item alone:
+    -> (c0, c1, lo, hi, few) or None (nothing to emit yet). off = the item's first row, n2 = the row its output has reached (>= E: the
+    prompt is never emitted), top = the row behind its last arrived frame, n1 = the row stage 1 has reached, closed = the item has ended
+    and stage 1 has passed its end (`top` is then a true edge: the layers' own padding, no margin). `few`: does `decode` of the whole
+    item run its last layer as the few-output kernel — unknown (None -> wait) while the item is short and may still grow."""
+    frames = top - off
+    if not few_eligible:
+        few = False
+    elif frames * hop >= few_min_t:
+        few = True
+    else:
+        few = False if closed else None
+    if few is None:
+        return None
+    n = top if closed else min(n1, top)
+    limit = n if closed else n - margins[1]
+    c0 = max(n2, E)
+    if c0 >= limit:
+        return None
+    c1 = min(c0 + max_window, limit)
+    lo, hi = stream_window(c0 - off, c1 - off, n - off, margins)
+    return c0, c1, lo + off, hi + off, few
+
+
+def batch_window_groups(wins: Sequence[Optional[tuple]]) -> Tuple[Optional[tuple], List[int], List[int]]:
+    """Which items run their next window in ONE batched call: the items whose windows agree (same rows, same core, same last-layer
+    kernel) — the largest such set, when it has at least two members; the others run alone. An item whose prompt is shorter than the
+    left margin disagrees at its first window (the window would cross its first frame, a true edge), an item that has ended at its last.
+    -> (the batched window or None, its members, the items that run alone)."""
+    by_key: dict = {}
+    for u, w in enumerate(wins):
+        if w is not None:
+            by_key.setdefault(w, []).append(u)
+    if not by_key:
+        return None, [], []
+    key = max(by_key, key=lambda k: (len(by_key[k]), [-v for v in k[:4]]))
+    if len(by_key[key]) < 2:
+        return None, [], sorted(u for us in by_key.values() for u in us)
+    return key, by_key[key], sorted(u for k, us in by_key.items() if k != key for u in us)
+
+
+class _TMView(TM):
+    """A window of rows of a larger [B][rows][C] buffer, read in place: the items are `bstride` elements apart, not rows * C."""
+
+    def __init__(self, data: torch.Tensor, T: int, bstride: int, device):
+        super().__init__(int(data.shape[0]), T, int(data.shape[2]), 1, 1, device, data=data, keep_halo=True)
+        self._bstride = int(bstride)
+
+    @property
+    def bstride(self) -> int:
+        return self._bstride
+
+
+class BatchDecodeStream:
+    """`WMEncodecModel.decode_stream_batch`: the decoders of B utterances that are generated in lock-step, advanced together as their
+    frames arrive — `DecodeStream` (one utterance, B = 1) with every per-poll operation as ONE dense batched call of the same kernels.
+
+    One aligned time axis (`batch_align_plan`): item u's frame t is row off_u + t of buffers [B][rows][C]; the prompts all end at row E,
+    generated frame j of every item is row E + j. Per `advance`: one `ssrhip_rvq_decode` with B items, the first convolution's GEMM with
+    batch = B, `_lstm_in_gemm` / `_lstm_steps` with B items over a common [a, b) (`batch_stage1_range`), and the layers behind the LSTM
+    over a TM(B, ...) view with a common window (`batch_window_groups`). No arithmetic kernel is new or changed.
+
+    A row in front of an item's first frame must leave its LSTM state exactly zero. The rows [0, off_u) of every layer's `gin` and of the
+    skip input `y0` are zeroed ahead of that layer's step call; then with h = c = 0 and a zero pre-activation every gate sees 0:
+    c' = sigmoid(0) * 0 + sigmoid(0) * tanh(0) = 0 and h' = sigmoid(0) * tanh(0) = 0 exactly (tanh(0) = 0 and x * 0 = 0 are exact in
+    fp32, whatever the kernel's sigmoid returns for 0), the written row is h' + skip = 0, or ELU(0) = 0, and the next layer's input rows
+    are zero again. By induction the state entering row off_u is the h = c = 0 a batch-1 decode starts from (tests/test_gpu_stream_batch.py).
+
+    An item that ends gets its right edge — zero rows, or its own reflected rows, behind its last frame in `z` — ahead of the batched
+    stage-1 call that passes its end; its stage-1 rows from the end on are zeroed after that call and its last windows run alone (stage 2
+    has no state). Later batched calls write junk into a finished item's rows, which nothing reads. B stays constant for the life of the
+    stream: `ssrhip_lstm_layer` chooses its kernel by B, and an item's values must not change kernel mid-utterance.
+
+    Everything runs on the caller's stream; every buffer — also those of the largest batched window and of a B = 1 window, each found by
+    one dry pass — is allocated here, so create the stream before the decode engine's first launch."""
+
+    def __init__(self, model: WMEncodecModel, prompt_lens: Sequence[int], max_new_frames: int, max_window: int):
+        cfg, dev = model.cfg, model.device
+        if max_new_frames < 1 or max_window < 1:
+            raise ValueError("decode_stream_batch needs max_new_frames >= 1 and max_window >= 1")
+        nodes = model.decoder.nodes
+        self.m, self.max_new, self.max_window = model, int(max_new_frames), int(max_window)
+        self.hop = int(math.prod(cfg.ratios))
+        self.conv0: _Conv = nodes[0][2]
+        self.lstm: Optional[_Lstm] = nodes[1][2] if nodes[1][1] == "lstm" else None
+        self.tail = nodes[2:] if self.lstm is not None else nodes[1:]
+        c0 = self.conv0
+        if not (nodes[0][1] == "conv" and c0.s == 1 and c0.Cin > 1 and c0.Cout > 4 and self.tail and self.tail[0][1] == "convtr"):
+            raise NotImplementedError("decode_stream_batch: the decoder does not start with a stride-1 convolution into a transposed convolution")
+        self.pl0, self.pr0 = c0.pl, c0.pr
+        plan = batch_align_plan(prompt_lens, self.pl0)
+        self.prompt_lens = [int(p) for p in prompt_lens]
+        self.off, self.E = plan["off"], plan["E"]
+        self.B = B = len(self.off)
+        self.margins = stream_margins(cfg)
+        self.reflect = cfg.pad_mode == "reflect"
+        if self.reflect and min(self.prompt_lens) <= max(self.pl0, self.pr0):
+            raise ValueError(f"decode_stream_batch: with reflect padding every prompt must be longer than the first convolution's padding "
+                             f"({max(self.pl0, self.pr0)} frames), got {self.prompt_lens}")
+        last = nodes[-1][2]
+        self._few_eligible = bool(last.Cout <= 4 and last.s == 1 and last.Cin % 8 == 0 and not model.force_few_out)
+        f32 = dict(dtype=torch.float32, device=dev)
+        K, D, C0 = cfg.n_q, cfg.dimension, c0.Cout
+        self.R = R = self.E + self.max_new                             # rows of the common time axis
+        self.codes = torch.zeros(B * K * max(max(self.prompt_lens), self.max_new), dtype=torch.int32, device=dev)
+        self.z = TM(B, R - self.pl0, D, self.pl0, self.pr0, dev, data=torch.zeros(B, R + self.pr0, D, **f32))    # data row == row
+        self.s1 = TM(B, R, C0, 1, 1, dev, data=torch.zeros(B, R + 2, C0, **f32))
+        self.s1.elu = bool(model.elu_on_store and self.lstm is not None)
+        if self.lstm is not None:
+            L, nl = self.lstm, len(self.lstm.layers)
+            assert L.C == C0
+            self.y0 = torch.zeros(B, R, C0, **f32)
+            self.gins = [torch.zeros(B, R, 4 * C0, **f32) for _ in range(nl)]
+            self.hbufs = [torch.zeros(2, (B + 15) // 16 * 16, C0, **f32) for _ in range(nl)]
+            self.cbufs = [torch.zeros(B, C0, **f32) for _ in range(nl)]
+            self.mids = [torch.zeros(B, R, C0, **f32) for _ in range(nl - 1)]
+            split = model._lstm_use_split(L, B)
+            self.hsplits = [torch.zeros(2 * ((B + 63) // 64) * 64 * C0 * 3, dtype=torch.int16, device=dev) if (split and L.split[l] is not None)
+                            else None for l in range(nl)]
+        self.wav = torch.zeros(B, 1, self.max_new * self.hop, **f32)
+        self.top = [self.off[u] for u in range(B)]                     # row behind item u's last arrived frame
+        self.ended = [False] * B
+        self.closed = [False] * B                                      # ended, and stage 1 has passed the end
+        self.n1 = 0                                                    # rows whose stage-1 output is final (live items)
+        self.n2 = [self.E] * B                                         # row item u's samples have reached
+        self.primed = False
+        self.windows = self.windows_batched = 0
+        # stage 2: the buffers of the largest batched window and of the largest B = 1 window, each by one dry pass (no launch)
+        self.pool_b, self.pool_1 = _WindowPool(), _WindowPool()
+        real, model.lib = model.lib, _NoLaunch()
+        try:
+            n = min(R, self.max_window + self.margins[0] + self.margins[1])
+            self._tail_pass(0, n, None)
+            self._tail_pass(0, n, 0)
+        finally:
+            model.lib = real
+        self.pool_b.frozen = self.pool_1.frozen = True
+        torch.cuda.current_stream(dev).synchronize()                  # the fills above are done before anything else is enqueued
+
+    # ------------------------------------------------------------------ the pieces
+    def _tail_pass(self, lo: int, hi: int, item: Optional[int]) -> TM:
+        """The layers behind the LSTM over the stage-1 rows [lo, hi), read in place: of every item (`item` None: one batched call per
+        layer) or of one."""
+        m, s1 = self.m, self.s1
+        if item is None:
+            x, pool = _TMView(s1.data[:, lo: hi + 2], hi - lo, s1.bstride, m.device), self.pool_b
+        else:
+            x, pool = TM(1, hi - lo, s1.C, 1, 1, m.device, data=s1.data[item: item + 1, lo: hi + 2], keep_halo=True), self.pool_1
+        x.elu = s1.elu
+        pool.at = 0
+        m._tm_pool = pool
+        try:
+            return m._run(self.tail, x)
+        finally:
+            m._tm_pool = None
+
+    def _item_ptr(self, t: torch.Tensor, u: int, row: int) -> int:
+        return t.data_ptr() + 4 * (u * t.stride(0) + row * t.stride(1))
+
+    def _right_edge(self, u: int, upto: int):
+        """Item u has ended at row top[u]: behind it `z` holds the layer's own padding — zeros, or the item's reflected rows — whatever
+        a batched dequantiser call has written there (the rows [top[u], upto) may hold junk)."""
+        z, end = self.z, self.top[u]
+        if upto > end:
+            z.data[u, end: upto].zero_()
+        if self.reflect:
+            self.m._call("ssrhip_pad_reflect", self._item_ptr(z.data, u, self.off[u] - self.pl0), 1, end - self.off[u], self.pl0, self.pr0, z.C,
+                         z.bstride)
+
+    def _stage1(self):
+        m, z, c0, B, R = self.m, self.z, self.conv0, self.B, self.R
+        a, b = batch_stage1_range(self.n1, self.top, self.ended, self.closed, self.pr0)
+        b = min(b, R)
+        if b > a:
+            D, C0 = z.C, c0.Cout
+            ca = max(a, self.pl0)                                     # row r of the convolution reads the rows [r - pl0, r + pr0] of z
+            dst = self.y0 if self.lstm is not None else self.s1.data[:, 1:]
+            dst_bs = R * C0 if self.lstm is not None else self.s1.bstride
+            if b > ca:
+                m._gemm(z.base + 4 * (ca - self.pl0) * D, c0.W, c0.b, self._item_ptr(dst, 0, ca), b - ca, C0, c0.k * c0.Cin, c0.s * c0.Cin, C0,
+                        act_in=m._act_in(bool(c0.act_in), z), batch=B, sA=z.bstride, sC=dst_bs)
+            front = [(u, min(b, self.off[u])) for u in range(B) if a < self.off[u]]      # rows in front of an item's first frame
+            for u, e in front:
+                dst[u, a:e].zero_()
+            if self.lstm is not None:
+                L, nl = self.lstm, len(self.lstm.layers)
+                for l in range(nl):
+                    src = self.y0 if l == 0 else self.mids[l - 1]
+                    m._lstm_in_gemm(L, l, src.data_ptr(), R * C0, self.gins[l], B, R, a, b)
+                    for u, e in front:
+                        self.gins[l][u, a:e].zero_()                  # zero pre-activation from h = c = 0: the state stays exactly zero
+                    out_ptr = self.s1.interior if l == nl - 1 else self.mids[l].data_ptr()
+                    out_bs = self.s1.bstride if l == nl - 1 else R * C0
+                    m._lstm_steps(L, l, self.gins[l], self.hbufs[l], self.cbufs[l], self.hsplits[l], out_ptr, out_bs,
+                                  (self.y0.data_ptr() if l == nl - 1 else 0), R * C0, B, R, a, b, self.s1.elu and l == nl - 1)
+        for u in range(B):
+            if self.ended[u] and not self.closed[u] and self.top[u] <= b:
+                if b > self.top[u]:
+                    self.s1.data[u, 1 + self.top[u]: 1 + b].zero_()   # the zero row the last window's transposed convolution reads
+                self.closed[u] = True
+        self.n1 = b
+
+    def _stage2(self):
+        m, hop, E = self.m, self.hop, self.E
+        while True:
+            wins = [batch_window_item(self.off[u], E, self.n2[u], self.top[u], self.n1, self.closed[u], self.margins, self.max_window, hop,
+                                      m.FEW_OUT_MIN_T, self._few_eligible) for u in range(self.B)]
+            key, members, alone = batch_window_groups(wins)
+            if key is None and not alone:
+                return
+            runs = ([(key, None, members)] if key is not None else []) + [(wins[u], u, [u]) for u in alone]
+            for (c0, c1, lo, hi, few), item, who in runs:
+                m._stream_few_out = few
+                try:
+                    y = self._tail_pass(lo, hi, item)
+                finally:
+                    m._stream_few_out = False
+                assert y.C == 1 and y.padL == 0 and y.T == (hi - lo) * hop
+                flat = y.data.view(y.B, -1)
+                s0, s1_, d0, d1 = (c0 - lo) * hop, (c1 - lo) * hop, (c0 - E) * hop, (c1 - E) * hop
+                if item is None and len(who) == self.B:
+                    self.wav[:, 0, d0:d1].copy_(flat[:, s0:s1_])
+                else:
+                    for u in who:
+                        self.wav[u, 0, d0:d1].copy_(flat[u if item is None else 0, s0:s1_])
+                self.windows += 1
+                self.windows_batched += int(item is None)
+                for u in who:
+                    self.n2[u] = c1
+
+    def _dequant(self, n: int, row: int):
+        z, cfg = self.z, self.m.cfg
+        self.m._call("ssrhip_rvq_decode", self.codes.data_ptr(), self.m.codebooks.data_ptr(), self._item_ptr(z.data, 0, row), self.B, n, z.C,
+                     cfg.n_q, cfg.bins, z.bstride)
+
+    def _stage_codes(self, codes: Sequence[torch.Tensor], counts: Sequence[int], n: int, right: bool):
+        """The block [B][K][n] the dequantiser reads, from host-checked codes (tests, and the prompts): item u's `counts[u]` columns at
+        the left of the block, or at its right; the other columns hold id 0."""
+        K, bins = self.m.cfg.n_q, self.m.cfg.bins
+        block = np.zeros((self.B, K, n), dtype=np.int32)
+        for u, (c, k) in enumerate(zip(codes, counts)):
+            if k == 0:
+                continue
+            c = c.detach().reshape(K, -1).cpu().numpy()
+            if c.shape[1] != k:
+                raise ValueError(f"item {u}: {k} frames announced, {c.shape[1]} given")
+            if c.min() < 0 or c.max() >= bins:
+                raise IndexError("index out of range in self")        # what F.embedding raises in the reference (core_vq.py:175)
+            block[u, :, (n - k if right else 0): (n if right else k)] = c
+        self.codes[: block.size].view(self.B, K, n).copy_(torch.from_numpy(block))
+
+    # ------------------------------------------------------------------ public
+    @torch.no_grad()
+    def push_prompts(self, codes: Sequence[torch.Tensor]) -> None:
+        """codes[u]: [K, P_u] (or [1, K, P_u]) — the prompts, range-checked here, once, before the stream's first launch. They run
+        through stage 1 (the LSTM state has to pass through them) and are never returned."""
+        if self.primed:
+            raise RuntimeError("BatchDecodeStream.push_prompts called twice")
+        if len(codes) != self.B:
+            raise ValueError(f"{self.B} prompts expected, got {len(codes)}")
+        p_max = max(self.prompt_lens)
+        self._stage_codes(codes, self.prompt_lens, p_max, right=True)
+        self.primed = True
+        self._dequant(p_max, self.pl0)
+        z = self.z
+        for u in range(self.B):
+            if self.off[u] > self.pl0:
+                z.data[u, self.pl0: self.off[u]].zero_()               # id 0 dequantised in front of the item's first frame
+            if self.reflect:
+                self.m._call("ssrhip_pad_reflect", self._item_ptr(z.data, u, self.off[u] - self.pl0), 1, self.prompt_lens[u], self.pl0, 0, z.C,
+                             z.bstride)
+            self.top[u] = self.E
+        self._stage1()
+
+    @torch.no_grad()
+    def advance(self, new_frames: Sequence[int], ended: Sequence[bool], codes: Optional[Sequence[torch.Tensor]] = None,
+                flag: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
+        """The next generated frames: new_frames[u] of item u, which has `ended[u]` with them. Lock-step: every item that goes on gets the
+        same number of frames, an item that ends here at most that many, an item that had ended none. The frames are in `self.codes`, the
+        stream's own int32 buffer, as a [B][K][n] block (n = max(new_frames), item u's in its first new_frames[u] columns) that a producer
+        filled on the device (`ssrhip_stream_gather`; `flag`: the device word it sets for an id outside the codebook — read once, after
+        everything is enqueued, IndexError before any sample is returned) — or they are given as `codes[u]` [K, new_frames[u]] and checked
+        on the host. Returns, per item, the samples that have become final: [1, 1, m * hop] views of item u's row of the one output buffer."""
+        if not self.primed:
+            raise RuntimeError("BatchDecodeStream.advance before push_prompts")
+        B = self.B
+        new = [int(v) for v in new_frames]
+        if len(new) != B or len(ended) != B:
+            raise ValueError(f"{B} items expected")
+        n = max(new)
+        for u in range(B):
+            if self.ended[u] and new[u]:
+                raise ValueError(f"item {u} has ended and gets {new[u]} more frames")
+            if not self.ended[u] and not ended[u] and new[u] != n:
+                raise ValueError(f"lock-step: item {u} goes on with {new[u]} new frames while another item gets {n}")
+            if self.top[u] + new[u] > self.R:
+                raise ValueError(f"item {u}: more than max_new_frames = {self.max_new} generated frames")
+        a = list(self.n2)
+        live_top = [self.top[u] for u in range(B) if not self.ended[u]]
+        if n:
+            row = live_top[0]
+            assert all(t == row for t in live_top)
+            if codes is not None:
+                self._stage_codes(codes, new, n, right=False)
+            self._dequant(n, row)
+            for u in range(B):
+                if not self.ended[u]:
+                    self.top[u] = row + new[u]
+                    self.ended[u] = bool(ended[u])
+            for u in range(B):
+                if self.ended[u] and not self.closed[u]:
+                    self._right_edge(u, row + n)
+        else:
+            for u in range(B):
+                if not self.ended[u] and ended[u]:
+                    self.ended[u] = True
+                    self._right_edge(u, self.top[u])
+        self._stage1()
+        self._stage2()
+        if flag is not None and int(flag.item()):
+            raise IndexError("index out of range in self")
+        hop, E = self.hop, self.E
+        return [self.wav[u: u + 1, :, (a[u] - E) * hop: (self.n2[u] - E) * hop] for u in range(B)]
+
+    @property
+    def finished(self) -> bool:
+        return all(self.closed) and all(self.n2[u] >= self.top[u] for u in range(self.B))

@@ -583,7 +583,58 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(const ssrhip_sam
   STAMP(8);
 }
 
+// ---- the batched stream's hand-off: the frames of `generated` that have become final, per utterance, with the delay pattern undone
+// (codebook k of frame f sits in step f + k: revert_pattern_sequence, models/ssr.py:438-464), written as the [B][K][cap] block the
+// dequantiser reads. One launch serves every utterance: blockIdx.y = utterance, 64 frames x K codebooks per workgroup, lane = frame
+// so that the stores of one codebook are contiguous. rng = [4][n_utt]: step0 | f0 | f1 | col0. The launcher has checked the host copy
+// of the ranges; the kernel checks the device copy again and skips what falls outside, so a stale table can never store out of bounds.
+constexpr int GATHER_FRAMES = 64;
+
+__global__ __launch_bounds__(GATHER_FRAMES * SSRHIP_MAX_CODEBOOKS) void stream_gather_kernel(
+    const int* __restrict__ generated, int n_utt, int max_steps, int K, const int* __restrict__ rng, int* __restrict__ codes_out, int cap,
+    int bins, int* flag) {
+  const int u = blockIdx.y;
+  const int k = threadIdx.x / GATHER_FRAMES;
+  if (k >= K) return;
+  const int step0 = rng[u], f0 = rng[n_utt + u], f1 = rng[2 * n_utt + u], col0 = rng[3 * n_utt + u];
+  const int f = f0 + blockIdx.x * GATHER_FRAMES + threadIdx.x % GATHER_FRAMES;
+  if (f < f0 || f >= f1) return;
+  const long step = (long)step0 + f + k, col = (long)col0 + f;
+  if (step < 0 || step >= max_steps || col < 0 || col >= cap) return;
+  int v = generated[((size_t)u * max_steps + step) * K + k];
+  if (v < 0 || v >= bins) {                            // what F.embedding refuses in the reference (core_vq.py:175): the host raises for it
+    v = v < 0 ? 0 : bins - 1;                          // ... and the dequantiser, which runs before the host looks, reads inside the codebook
+    *flag = 1;
+  }
+  codes_out[((size_t)u * K + k) * cap + col] = v;
+}
+
 }  // namespace
+
+extern "C" int ssrhip_stream_gather(const int32_t* generated, int32_t n_utt, int32_t max_steps, int32_t K, const int32_t* ranges_host,
+                                    const int32_t* ranges_dev, int32_t* codes_out, int32_t B, int32_t cap, int32_t bins, int32_t* flag,
+                                    ssrhip_stream_t stream) {
+  SSR_REQUIRE(generated && ranges_host && ranges_dev && codes_out && flag, "ssrhip_stream_gather: null argument");
+  SSR_REQUIRE(K >= 1 && K <= SSRHIP_MAX_CODEBOOKS, "ssrhip_stream_gather: K=%d", K);
+  SSR_REQUIRE(n_utt >= 1 && n_utt <= B && B <= 65535 && max_steps >= 1 && cap >= 1 && bins >= 1,
+              "ssrhip_stream_gather: bad n_utt=%d / B=%d / max_steps=%d / cap=%d / bins=%d", n_utt, B, max_steps, cap, bins);
+  int most = 0;
+  for (int u = 0; u < n_utt; ++u) {
+    const long step0 = ranges_host[u], f0 = ranges_host[n_utt + u], f1 = ranges_host[2 * n_utt + u], col0 = ranges_host[3 * n_utt + u];
+    SSR_REQUIRE(f0 >= 0 && f0 <= f1, "ssrhip_stream_gather: utterance %d has the frame range [%ld, %ld)", u, f0, f1);
+    if (f1 == f0) continue;
+    SSR_REQUIRE(step0 >= 0 && step0 + f1 - 1 + K - 1 < max_steps, "ssrhip_stream_gather: utterance %d reads step %ld of %d", u,
+                step0 + f1 - 1 + K - 1, max_steps);
+    SSR_REQUIRE(col0 + f0 >= 0 && col0 + f1 <= cap, "ssrhip_stream_gather: utterance %d writes the columns [%ld, %ld) of %d", u, col0 + f0,
+                col0 + f1, cap);
+    if (f1 - f0 > most) most = (int)(f1 - f0);
+  }
+  if (most == 0) return 0;                             // nothing became final at this poll
+  hipLaunchKernelGGL(stream_gather_kernel, dim3((most + GATHER_FRAMES - 1) / GATHER_FRAMES, n_utt), dim3(GATHER_FRAMES * SSRHIP_MAX_CODEBOOKS),
+                     0, (hipStream_t)stream, generated, n_utt, max_steps, K, ranges_dev, codes_out, cap, bins, flag);
+  SSR_LAUNCH_CHECK();
+  return 0;
+}
 
 extern "C" int ssrhip_embed(const ssrhip_embed_args* a, ssrhip_stream_t stream) {
   SSR_REQUIRE(a && a->audio_emb && a->pe && a->tok && a->pos && a->out, "ssrhip_embed: null argument");

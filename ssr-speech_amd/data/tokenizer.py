@@ -178,6 +178,14 @@ class AudioTokenizer:
             raise ValueError("decode_stream: the watermarked decode (use_watermark=True) is not streamed; use wmdecode on the finished frames")
         return self.codec.decode_stream(max_frames, max_window)
 
+    def decode_stream_batch(self, prompt_lens: Sequence[int], max_new_frames: int, max_window: int = 16, use_watermark: bool = False):
+        """`decode_stream` for B utterances generated in lock-step (`WMEncodecModel.decode_stream_batch`): `push_prompts(codes)`, then
+        `advance(new_frames, ended)` per poll returns every item's new samples; per item their concatenation equals `decode` of that
+        item's generated part behind its own prompt (within the batch-1 / batched bound of `decode_batch`)."""
+        if use_watermark:
+            raise ValueError("decode_stream_batch: the watermarked decode (use_watermark=True) is not streamed; use wmdecode_batch on the finished frames")
+        return self.codec.decode_stream_batch(prompt_lens, max_new_frames, max_window)
+
     def wmdecode(self, frames: torch.Tensor, marks: torch.Tensor, wav: torch.Tensor, scale: torch.Tensor):
         # the reference discards the detector output here (tokenizer.py:133): skip computing it
         out, _ = self.codec.wmdecode(frames.to(self.device), marks.to(self.device), wav.to(self.device), scale, with_mark=False)

@@ -1333,6 +1333,18 @@ class DecodeEngine:
 
         jobs[i]: {text_rows: [row0(, row1)], audio_cols: [K, T0], knobs: DecodeKnobs, gen: torch.Generator | None (sampling),
         cap: max steps of this utterance}. Returns a list of (SamplerState, generated int64 [n_steps, K]) in job order."""
+        it = self.iter_queue(jobs, chunk, use_graph, sampling)
+        while True:
+            try:
+                next(it)
+            except StopIteration as done:
+                return done.value
+
+    def iter_queue(self, jobs: Sequence[dict], chunk: int = 16, use_graph: bool = True, sampling: bool = False):
+        """`run_queue` as a generator: yields `(states, slot_job)` after every poll — the sampler states read there and, per slot, the
+        job it runs (None: idle) — before the finished utterances are collected; the rows the states count exist on the device and the
+        pair-launch check has passed. The consumer's work runs between two chunks on the caller's stream. `StopIteration.value` is the
+        list `run_queue` returns; the generator has to be consumed to its end (the noise feed is put back there)."""
         n_jobs = len(jobs)
         results: List[Optional[tuple]] = [None] * n_jobs
         if n_jobs == 0:
@@ -1444,6 +1456,7 @@ class DecodeEngine:
             states = self.states()                              # blocks until the enqueued chunk has finished
             if ci == 1:
                 self.t_first_chunk = time.perf_counter()
+            yield states, list(slot_job)
             freed = []
             for u in in_flight:
                 st, j = states[u], slot_job[u]

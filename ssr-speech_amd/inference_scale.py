@@ -192,3 +192,74 @@ def inference_one_sample_stream(model, model_args, phn2num, text_tokenizer, audi
     chunk = codec.finish()
     if chunk.shape[-1]:
         yield chunk
+
+
+def _stream_batch(model, audio_tokenizer, utterances, cfg_coef, cfg_stride, aug_text, decode_config, seed):
+    """The batched stream behind `inference_batch_stream` / `inference_samples_stream`: `SSR_Speech.inference_batch_stream` gathers every
+    poll's final frames on the device into the codec stream's own block, `BatchDecodeStream.advance` turns them into samples."""
+    held = {}
+
+    def before_start(info):
+        # the codec stream allocates everything NOW, ahead of the engine's first launch; the gather writes straight into its block
+        held["codec"] = audio_tokenizer.decode_stream_batch(info["prompt_lens"], info["max_new_frames"])
+        return held["codec"].codes
+
+    frames = model.inference_batch_stream(utterances, top_k=decode_config["top_k"], top_p=decode_config["top_p"],
+                                          temperature=decode_config["temperature"], stop_repetition=decode_config["stop_repetition"],
+                                          cfg_coef=cfg_coef, cfg_stride=cfg_stride, aug_text=aug_text, seed=seed,
+                                          bins=int(audio_tokenizer.codec.cfg.bins), before_start=before_start)
+    for inc in frames:
+        codec = held["codec"]
+        if inc.kept:
+            codec.push_prompts(inc.codes)                                     # the prompts only warm the LSTM state up: never yielded
+            continue
+        # the flag is read once per poll, after the poll's codec work is enqueued, and raises before any sample of the poll leaves
+        for i, chunk in enumerate(codec.advance(inc.counts, inc.ended, flag=frames.flag)):
+            if chunk.shape[-1]:
+                yield i, chunk
+    if frames.results is None:
+        raise RuntimeError("generation did not finish")
+
+
+@torch.no_grad()
+def inference_batch_stream(model, model_args, phn2num, text_tokenizer, audio_tokenizer, utterances, cfg_coef, cfg_stride, aug_text,
+                           use_watermark, device, decode_config, seed: int = 0):
+    """Zero-shot TTS of several utterances decoded in lock-step AND streamed (DESIGN.md Part I.16): a generator of
+    `(index, chunk [1, 1, n])` — waveform chunks of utterance `index`, views of one buffer, handed out after every 16-step poll of the
+    engine while the group still decodes. utterances[i] = {audio_fn, target_text}: the prompt is the whole file, as `--tts` passes it.
+    Per utterance the concatenated chunks are `inference_one_sample(..., tts=True)` under `torch.manual_seed(seed + i)` (same tokens;
+    samples within the bound that holds a batched codec pass to the batch-1 one). The prompt is never yielded. One fixed group:
+    `len(utterances) x rows <= 32`, no refill; speech edits, a larger group and `use_watermark=True` are ValueErrors that name
+    `inference_batch` + `render_many`, raised before any launch."""
+    if use_watermark:
+        raise ValueError("inference_batch_stream: the watermarked decode (use_watermark=True) is not streamed; use inference_batch + render_many")
+    K = int(model_args.n_codebooks)
+    jobs = []
+    for u in utterances:
+        prompt_frames, scale = _prompt_codes(audio_tokenizer, u["audio_fn"], K)
+        if scale is not None:
+            raise AssertionError("renormalize=False codec: scale must be None")
+        T = int(prompt_frames.shape[1])
+        jobs.append({"x": _phoneme_ids(text_tokenizer, phn2num, u["target_text"]), "y": prompt_frames,
+                     "mask_interval": torch.tensor([[[T, T]]], dtype=torch.long)})
+    yield from _stream_batch(model, audio_tokenizer, jobs, cfg_coef, cfg_stride, aug_text, decode_config, seed)
+
+
+@torch.no_grad()
+def inference_samples_stream(model, model_args, phn2num, text_tokenizer, audio_tokenizer, audio_fn, prompt_text, target_text, mask_interval,
+                             cfg_coef, cfg_stride, aug_text, aug_context, use_watermark, tts, device, decode_config, seeds):
+    """`inference_samples` as a generator of `(sample index, chunk [1, 1, n])`: the N samples of ONE utterance decoded in lock-step and
+    streamed (`inference_batch_stream`). Sample i's concatenated chunks are `inference_one_sample` after `torch.manual_seed(seeds[i])`.
+    `--tts` only: a speech edit, `use_watermark=True` or more samples than one engine pass holds raise ValueError before any launch."""
+    if use_watermark:
+        raise ValueError("inference_samples_stream: the watermarked decode (use_watermark=True) is not streamed; use inference_samples")
+    if not tts:
+        raise ValueError("inference_samples_stream: only zero-shot TTS (--tts) is streamed; use inference_samples for a speech edit")
+    seeds = [int(s) for s in seeds]
+    assert seeds == list(range(seeds[0], seeds[0] + len(seeds))), "seeds must be consecutive (seed + sample index)"
+    K = int(model_args.n_codebooks)
+    prompt_frames, scale = _prompt_codes(audio_tokenizer, audio_fn, K)
+    if scale is not None:
+        raise AssertionError("renormalize=False codec: scale must be None")
+    one = {"x": _phoneme_ids(text_tokenizer, phn2num, target_text), "y": prompt_frames, "mask_interval": mask_interval.unsqueeze(0)}
+    yield from _stream_batch(model, audio_tokenizer, [one] * len(seeds), cfg_coef, cfg_stride, aug_text, decode_config, seeds[0])

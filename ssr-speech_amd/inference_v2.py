@@ -62,6 +62,9 @@ EXTRA_FLAGS = [
     ("--share_prompt", dict(type=int, choices=[0, 1], default=0,
                             help="1: the --sample_batch_size samples of the utterance are prefilled once and share the prompt's KV pages "
                                  "(5..32 rows, fp32 cache; fewer rows run unshared); 0 (default): every sample keeps its own copy")),
+    ("--stream_dir", dict(type=str, default=None,
+                          help="--tts with --sample_batch_size N: stream the lock-step samples (inference_samples_stream) and append each "
+                               "sample's chunks, as they arrive, to DIR/{savename}_new_seed{seed}.f32 (raw float32 samples, one file per sample)")),
     ("--prompt_end", dict(type=float, default=None, help="--tts: cut the prompt audio at this time in seconds (default --prompt_length)")),
     ("--phoneme_ids", dict(type=str, default=None, help="comma separated phoneme ids of the target transcript (skips espeak)")),
     ("--prompt_phoneme_ids", dict(type=str, default=None, help="comma separated phoneme ids of the prompt transcript")),
@@ -69,6 +72,21 @@ EXTRA_FLAGS = [
                                                      "orig_transcript, prompt_end}; all of them are decoded in lock-step (sharded over the ranks of a "
                                                      "torchrun job) and rendered in one ragged codec pass per rank")),
 ]
+
+
+def _stream_samples_to(stream_dir: str, savename: str, seeds, chunks):
+    """--stream_dir: append every chunk to its sample's file as it arrives; returns the whole waveforms for the usual .wav files."""
+    os.makedirs(stream_dir, exist_ok=True)
+    paths = [os.path.join(stream_dir, f"{savename}_new_seed{s_}.f32") for s_ in seeds]
+    for p_ in paths:
+        open(p_, "wb").close()
+    parts = [[] for _ in seeds]
+    for i, chunk in chunks:
+        host = chunk.detach().cpu().contiguous()
+        with open(paths[i], "ab") as f:
+            f.write(host.numpy().tobytes())
+        parts[i].append(host)
+    return [torch.cat(p_, -1) if p_ else torch.zeros(1, 1, 0) for p_ in parts]
 
 
 def edit_spans(spans, sub_amount: float, audio_dur: float, codec_sr: int, max_n_spans: int = 3, threshold: float = 0.2):
@@ -224,7 +242,7 @@ def main(argv=None):
     args = parse_args(argv)
     seed_everything(args.seed)
     from .data.tokenizer import AudioTokenizer, TextTokenizer, read_wav, write_wav
-    from .inference_scale import inference_one_sample, inference_samples
+    from .inference_scale import inference_one_sample, inference_samples, inference_samples_stream
     from .models.ssr import SSR_Speech
 
     if int(os.environ.get("WORLD_SIZE", "1")) > 1 and torch.cuda.is_available():        # torchrun: this rank's GPU before anything is allocated
@@ -306,7 +324,11 @@ def main(argv=None):
     common = (model, argparse.Namespace(**config), phn2num, text_tokenizer, audio_tokenizer, audio_fn, prompt_text, target_text, mask_interval,
               args.cfg_coef, args.cfg_stride, args.aug_text, args.aug_context, args.use_watermark, args.tts, device, decode_config)
     seeds = [args.seed + num for num in range(args.sample_batch_size)]               # :331-332: sample `num` runs under seed + num
-    if len(seeds) > 1:
+    if args.stream_dir is not None:
+        # the samples in ONE lock-step decode, their audio written while they decode (--tts only; DESIGN.md Part I.16)
+        seed_everything(seeds[-1])
+        waves = _stream_samples_to(args.stream_dir, args.savename, seeds, inference_samples_stream(*common, seeds=seeds))
+    elif len(seeds) > 1:
         # all samples of the utterance in ONE lock-step decode (same outputs as the reference's sequential loop :331-358)
         seed_everything(seeds[-1])
         waves = inference_samples(*common, seeds=seeds, share_prompt=bool(args.share_prompt))

@@ -248,3 +248,47 @@ class FrameAssembler:
         o = self.out_len
         res, marks = np.concatenate(self._codes, 1)[:, o:], np.concatenate(self._marks)[o:]
         return res, marks, [(a - o, b - o) for a, b in self._masks], [(a - o, b - o) for a, b in self.nmi]
+
+
+# ----------------------------------------------------------------------------- the batched stream (DESIGN.md Part I.16): host arithmetic only
+def check_stream_batch(y_lens: Sequence[int], mask_intervals: Sequence[np.ndarray], rows_per_utt: int, max_rows: int,
+                       use_watermark: bool = False) -> List[int]:
+    """Which calls `SSR_Speech.inference_batch_stream` serves: zero-shot TTS utterances — ONE generated span that ends the utterance,
+    behind ONE kept interval — that fit one engine pass, decoded without the watermark. Anything else is a ValueError naming the call to
+    use instead, raised before any library call. Returns the prompt lengths (frames of the kept interval)."""
+    if use_watermark:
+        raise ValueError("the batched stream does not run the watermarked decode (use_watermark=True): use inference_batch + render_many")
+    n = len(y_lens)
+    if n < 1 or n * int(rows_per_utt) > int(max_rows):
+        raise ValueError(f"the batched stream decodes one fixed lock-step group: {n} utterances x {rows_per_utt} rows do not fit one engine "
+                         f"pass of {max_rows} rows; use inference_batch (it refills)")
+    prompts = []
+    for i, (T, mi) in enumerate(zip(y_lens, mask_intervals)):
+        mi = np.asarray(mi, dtype=np.int64).reshape(-1, 2)
+        if mi.shape[0] != 1:
+            raise ValueError(f"utterance {i}: the batched stream takes one generated span, got {mi.shape[0]} (a speech edit): use inference_batch")
+        a, b = int(mi[0, 0]), int(mi[0, 1])
+        if b != int(T) or not 0 <= a <= b:
+            raise ValueError(f"utterance {i}: the span [{a}, {b}) does not end the utterance of {int(T)} frames (a speech edit leaves a second "
+                             f"kept interval): use inference_batch")
+        prompts.append(a)
+    return prompts
+
+
+def final_generated_frames(n_rows: int, ended: bool, end_row: int, K: int) -> int:
+    """How many generated frames of a ONE-span utterance are final when `n_rows` generated rows exist — `FrameAssembler`'s rule without
+    the rows themselves: frame t needs the rows 0 .. t + K - 1, and the first `eog` of codebook 0 sits exactly K rows before the span's
+    end (the cascade), so it can only be met once the span has ended at row `end_row` — then the frames are the end_row - K in front of it."""
+    return max(int(end_row) - K, 0) if ended else max(int(n_rows) - K + 1, 0)
+
+
+def stream_gather_ranges(released: Sequence[int], states: Sequence[Tuple[int, bool, int]], K: int) -> np.ndarray:
+    """The table `ssrhip_stream_gather` reads at one poll, int32 [4][n] = step0 | f0 | f1 | col0: utterance u has `released[u]` frames
+    out already, states[u] = (n_steps, span ended, span_end[0]); its new frames [f0, f1) go to the columns [0, f1 - f0) of the poll's block."""
+    n = len(released)
+    t = np.zeros((4, n), dtype=np.int32)
+    for u, (rel, (n_rows, ended, end_row)) in enumerate(zip(released, states)):
+        f1 = max(final_generated_frames(n_rows, ended, end_row, K), int(rel))
+        t[:, u] = (0, int(rel), f1, -int(rel))
+    return t
+

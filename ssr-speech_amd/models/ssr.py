@@ -14,7 +14,7 @@ import ctypes as C
 import logging
 import time
 from argparse import Namespace
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -82,6 +82,89 @@ class InferenceStream:
                 yield from on_device(asm.feed(rows, int(st.span), list(st.span_end)))
             self.result = m._end_inference(run, st, asm.rows)
             return self.result
+
+
+class BatchFrames(NamedTuple):
+    """One release of `SSR_Speech.inference_batch_stream`. `kept`: the prompts — `codes` is the list of the utterances' kept frames,
+    [K, P_u] int64 on the device; else the generated frames that became final at one poll — `codes` is ONE int32 device block
+    [n_utt][K][n] with utterance u's `counts[u]` new frames in its first columns (a view of a buffer the next poll overwrites).
+    `ended[u]`: utterance u is complete with these frames."""
+    kept: bool
+    counts: List[int]
+    ended: List[bool]
+    codes: object
+
+
+class BatchInferenceStream:
+    """Iterator returned by `SSR_Speech.inference_batch_stream`; `.results` is set when it is exhausted, `.flag` is the device word the
+    gather sets for an id outside [0, bins) (read it once per poll, after the poll's consumer work is enqueued:
+    `BatchDecodeStream.advance(flag=)` does), `.polls` counts the polls so far."""
+
+    def __init__(self, model: "SSR_Speech", utterances, kw: dict, use_graph: bool, bins: Optional[int], before_start):
+        a = model.args
+        rows = 2 if kw["aug_text"] else 1
+        # the refusals, before anything reaches the library
+        self.prompt_lens = LY.check_stream_batch([int(u["y"].shape[1]) for u in utterances], [u["mask_interval"][0].detach().cpu().numpy() for u in utterances],
+                                                 rows, MAX_ROWS)
+        self.model, self.results, self.polls, self.flag = model, None, 0, None
+        self.bins = int(a.audio_vocab_size if bins is None else bins)
+        self._it = self._run(utterances, kw, use_graph, before_start)
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        return next(self._it)
+
+    def _run(self, utterances, kw, use_graph, before_start):
+        m = self.model
+        with torch.no_grad():
+            K, dev, n = m.args.n_codebooks, m.device, len(utterances)
+            setup = m._begin_batch(utterances, kw["top_k"], kw["top_p"], kw["temperature"], kw["stop_repetition"], kw["silence_tokens"],
+                                   kw["cfg_coef"], kw["cfg_stride"], kw["aug_text"], kw["seed"], kw["first_index"], kw["indices"], n, False)
+            eng, chunk = setup["eng"], 16
+            # every buffer ahead of the engine's first launch: the poll's block, the range table, the flag
+            block = before_start(dict(n_utt=n, K=K, prompt_lens=list(self.prompt_lens), max_new_frames=setup["cap_max"])) \
+                if before_start is not None else None
+            if block is None:
+                block = torch.zeros(n * K * chunk, dtype=torch.int32, device=dev)
+            if block.dtype != torch.int32 or block.numel() < n * K * chunk or not block.is_contiguous():
+                raise ValueError("inference_batch_stream: the gather needs a contiguous int32 device buffer of n_utt * K * 16 ids")
+            ranges_dev = torch.zeros(4 * n, dtype=torch.int32, device=dev)
+            self.flag = torch.zeros(1, dtype=torch.int32, device=dev)
+            lib = _lib.lib()
+            yield BatchFrames(True, list(self.prompt_lens), [False] * n,
+                              [u["y"][0, :p].transpose(1, 0).to(dev) for u, p in zip(utterances, self.prompt_lens)])
+            released, over = [0] * n, [False] * n
+            it = eng.iter_queue(setup["jobs"], chunk=chunk, use_graph=use_graph, sampling=kw["top_k"] != 1)
+            while True:
+                try:
+                    states, slot_job = next(it)
+                except StopIteration as fin:
+                    outs = fin.value
+                    break
+                self.polls += 1
+                # the first fill puts job u into slot u, and a fixed group is never refilled: slot u IS utterance u until it ends
+                # (a slot the queue has parked — its utterance ran into its step cap — releases nothing more and ends: `results` raises)
+                parked = [not over[u] and slot_job[u] != u for u in range(n)]
+                sts = [(int(states[u].n_steps), bool(states[u].span >= 1), int(states[u].span_end[0])) if not (over[u] or parked[u])
+                       else (0, True, released[u] + K) for u in range(n)]
+                table = LY.stream_gather_ranges(released, sts, K)
+                counts = [int(table[2, u] - table[1, u]) for u in range(n)]
+                ended = [bool(not over[u] and (parked[u] or states[u].done)) for u in range(n)]
+                width = max(counts)
+                if width:
+                    ranges_dev.copy_(torch.from_numpy(table.reshape(-1)))       # pushed the way the page table is
+                    _lib.check(lib.ssrhip_stream_gather(eng.generated.data_ptr(), n, int(eng.generated.shape[1]), K, table.ctypes.data,
+                                                        ranges_dev.data_ptr(), block.data_ptr(), n, width, self.bins, self.flag.data_ptr(),
+                                                        _lib.stream_ptr()), "ssrhip_stream_gather")
+                for u in range(n):
+                    released[u] += counts[u]
+                    over[u] = over[u] or ended[u]
+                if width or any(ended):
+                    yield BatchFrames(False, counts, ended, block[: n * K * width].view(n, K, width) if width else None)
+            self.results = m._batch_results(setup, outs)
+            return self.results
 
 
 class SSR_Speech(nn.Module):
@@ -481,16 +564,32 @@ class SSR_Speech(nn.Module):
         one utterance — are prefilled once and share the prompt's KV pages (engine.DecodeEngine share_prompt); same results, bit for bit.
         Engines of <= 4 rows, or with a bf16 KV cache, run unshared without error.
         Returns a list of the same 4-tuples `inference` returns."""
+        setup = self._begin_batch(utterances, top_k, top_p, temperature, stop_repetition, silence_tokens, cfg_coef, cfg_stride, aug_text,
+                                  seed, first_index, indices, group, share_prompt)
+        if setup is None:
+            return []
+        jobs, eng, n_slots = setup["jobs"], setup["eng"], setup["n_slots"]
+        greedy = top_k == 1
+        if refill:
+            outs = eng.run_queue(jobs, chunk=16, use_graph=use_graph, sampling=not greedy)
+        else:
+            outs = []
+            for g0 in range(0, len(jobs), n_slots):
+                outs += eng.run_queue(jobs[g0: g0 + n_slots], chunk=16, use_graph=use_graph, sampling=not greedy)
+        return self._batch_results(setup, outs)
+
+    def _begin_batch(self, utterances, top_k, top_p, temperature, stop_repetition, silence_tokens, cfg_coef, cfg_stride, aug_text,
+                     seed, first_index, indices, group, share_prompt) -> Optional[dict]:
+        """What `inference_batch` and `inference_batch_stream` do before the decode loop: the job list (per-utterance RNG stream, text rows,
+        prompt layout, step cap), the KV page demand and the engine lookup. None for an empty list."""
         K = self.args.n_codebooks
         assert cfg_coef >= 1.0, cfg_coef
         rows = 2 if aug_text else 1
         if group is None:
             group = DEFAULT_GROUP_ROWS // rows     # 16 rows per engine pass: 8 utterances with CFG (SURVEY §8d config 4); up to 32 on request
         assert 1 <= group * rows <= MAX_ROWS, (group, rows)
-        dev = self.device
-        greedy = top_k == 1
         if not utterances:
-            return []
+            return None
         jobs, metas, page_need = [], [], []
         cap_max, seq_max = 1, 1
         for j, u in enumerate(utterances):
@@ -521,12 +620,11 @@ class SSR_Speech(nn.Module):
         # KV pool: at most n_slots utterances are resident at a time -> the n_slots largest page demands bound the concurrent need
         pages_sum = sum(sorted(page_need, reverse=True)[:n_slots])
         eng = self._get_engine(n_slots, bool(aug_text), seq_max, cap_max + 16, need_pages=pages_sum, share_prompt=share_prompt)
-        if refill:
-            outs = eng.run_queue(jobs, chunk=16, use_graph=use_graph, sampling=not greedy)
-        else:
-            outs = []
-            for g0 in range(0, len(jobs), n_slots):
-                outs += eng.run_queue(jobs[g0: g0 + n_slots], chunk=16, use_graph=use_graph, sampling=not greedy)
+        return dict(jobs=jobs, metas=metas, n_slots=n_slots, eng=eng, cap_max=cap_max)
+
+    def _batch_results(self, setup: dict, outs) -> list:
+        """The 4-tuples `inference_batch` returns, from what `DecodeEngine.run_queue` returns."""
+        jobs, metas, dev = setup["jobs"], setup["metas"], self.device
         results = []
         for j, (st, gen) in enumerate(outs):
             if st.done != 1:
@@ -537,3 +635,24 @@ class SSR_Speech(nn.Module):
             res, marks, masks, nmi_out = LY.assemble(y_np, spans, nmi, self.args)
             results.append((torch.from_numpy(res).unsqueeze(0).to(dev), torch.from_numpy(marks).unsqueeze(0), masks, nmi_out))
         return results
+
+    @torch.no_grad()
+    def inference_batch_stream(self, utterances, top_k: int = -100, top_p: float = 1.0, temperature: float = 1.0, stop_repetition: int = -1,
+                               silence_tokens=(1388, 1898, 131), cfg_coef: float = 1.5, cfg_stride: int = 1, aug_text: bool = False,
+                               seed: int = 0, first_index: int = 0, use_graph: bool = True, indices: Optional[Sequence[int]] = None,
+                               *, bins: Optional[int] = None, before_start=None) -> "BatchInferenceStream":
+        """`inference_batch` of ONE fixed lock-step group that hands the frames out while the decode loop still runs (DESIGN.md Part I.16).
+        Zero-shot TTS utterances only (one generated span that ends the utterance, behind one kept interval), `n_utt x rows <= MAX_ROWS`,
+        no refill; anything else is a ValueError raised before any launch. Same parity contract as `inference_batch`.
+
+        Returns an iterator of `BatchFrames`: first the prompts (`kept`), then after every 16-step poll the generated frames of every
+        utterance that can no longer change (`layout.FrameAssembler`'s rule per utterance), gathered on the device by ONE
+        `ssrhip_stream_gather` launch into a [n_utt][K][n] int32 block — the tokens never visit the host. When exhausted, `.results` is
+        exactly the list `inference_batch` returns. Nothing runs before the first `next()`.
+        `bins`: ids outside [0, bins) are an error (default: `audio_vocab_size`). `before_start(info)` is called ahead of the engine's first
+        launch with dict(n_utt, K, prompt_lens, max_new_frames); it may return the int32 device buffer to gather into
+        (`BatchDecodeStream.codes`), else the stream allocates its own."""
+        return BatchInferenceStream(self, utterances, dict(top_k=top_k, top_p=top_p, temperature=temperature, stop_repetition=stop_repetition,
+                                                           silence_tokens=silence_tokens, cfg_coef=cfg_coef, cfg_stride=cfg_stride,
+                                                           aug_text=aug_text, seed=seed, first_index=first_index, indices=indices),
+                                    use_graph, bins, before_start)

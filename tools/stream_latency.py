@@ -5,7 +5,11 @@ host time to the first yielded chunk (after a stream synchronize on it), that ch
 codec launches per stage-2 window. One JSON line on stdout; `--out FILE` also writes it there.
 `--weight_dtype bf16` measures the bf16 weight stream (`SSR_Speech.set_weight_dtype`); the output also carries the real-time factor
 (wall time / seconds of audio) of both paths.
-Usage: python tools/stream_latency.py [--weight_dtype bf16] [--out profiles/stream_latency_830m.json]"""
+`--utts N` measures the BATCHED stream instead (DESIGN.md Part I.16): N samples of that utterance in one lock-step group under CFG,
+`inference_samples_stream` against `inference_batch(refill=False, group=N)` + `render_many` in the same process, same warm-up and
+rounds; it reports the host time to the first chunk of the FIRST and of the LAST utterance (after a stream synchronize), both arms'
+total wall time (median and spread of the rounds), the polls and the codec launches per run.
+Usage: python tools/stream_latency.py [--weight_dtype bf16] [--utts 8] [--out profiles/stream_latency_830m.json]"""
 import argparse
 import json
 import os
@@ -19,7 +23,8 @@ import torch  # noqa: E402
 import ssr_speech_amd  # noqa: E402,F401
 from ssr_speech_amd import weights as W  # noqa: E402
 from ssr_speech_amd.data.tokenizer import AudioTokenizer, write_wav  # noqa: E402
-from ssr_speech_amd.inference_scale import inference_one_sample, inference_one_sample_stream  # noqa: E402
+from ssr_speech_amd.inference_scale import (_phoneme_ids, _prompt_codes, inference_one_sample, inference_one_sample_stream,  # noqa: E402
+                                            inference_samples_stream, render_many)
 from ssr_speech_amd.models.ssr import SSR_Speech  # noqa: E402
 
 DEMO_PROMPT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "demo_5895_34622_000026_000002_160f.wav")
@@ -35,6 +40,7 @@ def main(argv=None):
     ap.add_argument("--out", default=None)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--weight_dtype", choices=["fp32", "bf16"], default="fp32")
+    ap.add_argument("--utts", type=int, default=0, help="N > 0: the batched stream of N utterances against inference_batch + render_many")
     opt = ap.parse_args(argv)
     dev = torch.device("cuda")
     args_lm = W.lm_args_830m()
@@ -67,6 +73,8 @@ def main(argv=None):
     call = (model, argparse.Namespace(**vars(args_lm)), phn2num, CharPhonemizer(), tok, fn, prompt_text, target_text, mi, 1.5, 5, True, False,
             False, True, dev, decode_config)
     codec = tok.codec
+    if opt.utts > 0:
+        return batched(opt, model, args_lm, tok, call, phn2num, fn, target_text, mi)
 
     def one_pass(seed):
         torch.manual_seed(seed)
@@ -155,6 +163,75 @@ def main(argv=None):
         "codec_launches_per_16_frame_push": per_push,
         "synchronized_pushes": {"summed_ms": round(spent["push_ms"], 2), "calls": spent["calls"], "run_total_ms": round(timed_run["total_ms"], 2)},
         "all_bit_identical": all(r["stream"]["bit_identical"] for r in rounds),
+    }
+    line = json.dumps(out)
+    print(line)
+    if opt.out:
+        with open(opt.out, "w") as f:
+            f.write(json.dumps(out, indent=1) + "\n")
+    return 0
+
+
+def batched(opt, model, args_lm, tok, call, phn2num, fn, target_text, mi):
+    """--utts N: `inference_samples_stream` against `inference_batch(refill=False, group=N)` + `render_many`"""
+    n, codec = opt.utts, tok.codec
+    decode_config, K = call[-1], int(args_lm.n_codebooks)
+
+    def one_pass(seed):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        prompt_frames, scale = _prompt_codes(tok, fn, K)
+        one = {"x": _phoneme_ids(CharPhonemizer(), phn2num, target_text), "y": prompt_frames, "mask_interval": mi.unsqueeze(0)}
+        results = model.inference_batch([one] * n, top_k=decode_config["top_k"], top_p=decode_config["top_p"], temperature=decode_config["temperature"],
+                                        stop_repetition=decode_config["stop_repetition"], cfg_coef=1.5, cfg_stride=5, aug_text=True, seed=seed,
+                                        group=n, refill=False)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        waves = render_many(tok, results, scale, fn, False, True)
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        return waves, dict(total_ms=1000 * (t2 - t0), lm_ms=1000 * (t1 - t0), render_ms=1000 * (t2 - t1),
+                           frames=[int(r[0].shape[-1]) for r in results], audio_s=sum(w.shape[-1] for w in waves) / 16000.0)
+
+    def streamed(seed):
+        torch.cuda.synchronize()
+        n0 = codec.n_launches
+        t0 = time.perf_counter()
+        parts, first = [[] for _ in range(n)], {}
+        for i, chunk in inference_samples_stream(*call, seeds=list(range(seed, seed + n))):
+            if i not in first and (not first or len(first) == n - 1):      # the first chunk of the first and of the last utterance
+                torch.cuda.current_stream().synchronize()
+            first.setdefault(i, 1000 * (time.perf_counter() - t0))
+            parts[i].append(chunk)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        waves = [torch.cat(p, -1) for p in parts]
+        eng = next(iter(model._engines.values()))
+        return waves, dict(total_ms=1000 * (t1 - t0), first_chunk_first_utt_ms=min(first.values()), first_chunk_last_utt_ms=max(first.values()),
+                           first_chunk_samples=int(parts[0][0].shape[-1]), chunks=sum(len(p) for p in parts), polls=eng._steps_enqueued // 16,
+                           codec_launches=codec.n_launches - n0, audio_s=sum(w.shape[-1] for w in waves) / 16000.0)
+
+    one_pass(1)
+    streamed(1)
+    rounds = []
+    for r in range(opt.rounds):
+        wa, a = one_pass(1 + 100 * r)
+        wb, b = streamed(1 + 100 * r)
+        b["max_abs_diff"] = max(float((x - y).abs().max()) if x.shape == y.shape else float("inf") for x, y in zip(wa, wb))
+        rounds.append({"one_pass": a, "stream": b})
+    med = lambda xs: sorted(xs)[len(xs) // 2]
+    col = lambda arm, key: [r[arm][key] for r in rounds]
+    out = {
+        "tool": "tools/stream_latency.py --utts", "utts": n, "weight_dtype": opt.weight_dtype,
+        "shape": f"830M LM, full codec (8,5,4,2), {n} samples x CFG of the 160-frame demo prompt, 67 phonemes, sampled, CFG stride 5",
+        "rounds": rounds,
+        "median": {k: round(med(col(arm, key)), 2) for k, arm, key in (
+            ("one_pass_total_ms", "one_pass", "total_ms"), ("one_pass_lm_ms", "one_pass", "lm_ms"), ("one_pass_render_ms", "one_pass", "render_ms"),
+            ("stream_total_ms", "stream", "total_ms"), ("stream_first_chunk_first_utt_ms", "stream", "first_chunk_first_utt_ms"),
+            ("stream_first_chunk_last_utt_ms", "stream", "first_chunk_last_utt_ms"))},
+        "spread": {"one_pass_total_ms": round(max(col("one_pass", "total_ms")) - min(col("one_pass", "total_ms")), 2),
+                   "stream_total_ms": round(max(col("stream", "total_ms")) - min(col("stream", "total_ms")), 2)},
+        "max_abs_diff": max(col("stream", "max_abs_diff")),
     }
     line = json.dumps(out)
     print(line)
