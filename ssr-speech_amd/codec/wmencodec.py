@@ -10,6 +10,7 @@ reflected) so that the im2col matrix of a Conv1d is a *view* (row t = k consecut
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 import os
@@ -309,8 +310,8 @@ class WMEncodecModel:
         self.lib = _lib.lib()
         self.fuse_resblock = True            # tests switch it off to compare with the two-GEMM path
         self.force_few_out = False           # tests: take the few-output-channel kernel also for short inputs
-        self._stream_few_out = False         # set while a `DecodeStream` window runs whose whole utterance takes that kernel
-        self._tm_pool = None                 # set while a `DecodeStream` window runs: where `_alloc_for` takes its buffers from
+        self._stream_few_out = False         # `_stream_pass`: a stream's window whose whole utterance takes that kernel is running
+        self._tm_pool = None                 # `_stream_pass`: where `_alloc_for` takes its buffers from while a stream's window runs
         for attr, switch, unset, parse in _ENV_KNOBS:
             setattr(self, attr, parse(os.environ.get(switch, unset)))
         self._plane_cache = {}
@@ -526,6 +527,17 @@ class WMEncodecModel:
         if self._tm_pool is not None:                # a `DecodeStream` window: its buffers exist since the stream was created
             return self._tm_pool.take(B, T, Cc, pl, pr, self.device)
         return TM(B, T, Cc, pl, pr, self.device, lens)
+
+    @contextlib.contextmanager
+    def _stream_pass(self, pool: "_WindowPool", few: bool):
+        """While one stage-2 window of a stream runs (`_StreamCore._tail_pass`): `_alloc_for` hands out the stream's own buffers, from the
+        pool's first on, and with `few` the last layer runs as the few-output kernel whatever the window's length."""
+        pool.at = 0
+        self._tm_pool, self._stream_few_out = pool, bool(few)
+        try:
+            yield
+        finally:
+            self._tm_pool, self._stream_few_out = None, False
 
     # ------------------------------------------------------------------ nodes
     def _act_in(self, wants_elu: bool, x: TM) -> int:
@@ -987,7 +999,7 @@ class WMEncodecModel:
 
 
 class _WindowPool:
-    """The activation buffers of a `DecodeStream` window: allocated once, by a dry pass over the largest window, and handed out again in
+    """The activation buffers of a stream's stage-2 window: allocated once, by a dry pass over the largest window, and handed out again in
     the same order for every later window (`WMEncodecModel._alloc_for`)."""
 
     def __init__(self):
@@ -1005,89 +1017,173 @@ class _WindowPool:
         return TM(B, T, Cc, padL, padR, device, data=flat[:n].view(B, padL + T + padR, Cc))
 
 
-class DecodeStream:
-    """`WMEncodecModel.decode_stream`: the decoder of one utterance (B = 1), advanced as its frames arrive.
+class _TMView(TM):
+    """A window of rows of a larger [B][rows][C] buffer, read in place: the items are `bstride` elements apart, not rows * C."""
 
-    Stage 1 — dequantiser, first convolution, LSTM + skip — runs once over every frame: the convolution over the frames whose
-    look-ahead (`stream_lookahead`) has arrived, the LSTM behind it as `ssrhip_lstm_layer` calls that continue (`t_begin` > 0) on the
-    stream's own `gin` / `hbuf` / `cbuf`. Stage 2 — everything behind the LSTM — runs over windows of stage-1 output with the margins
-    of `stream_margins` on either side, whose samples are dropped; an end of the utterance is a true edge (the layers' own padding, no
-    margin). Frames nearer to the current end than look-ahead + margin wait for more frames or for `finish()`. Every launch is the one
-    `decode` issues for the same layer, over fewer rows, on the caller's stream; where a launcher chooses by length (`_conv`'s
-    few-output kernel from `FEW_OUT_MIN_T` rows on) the stream waits until the whole utterance's choice is known and takes it."""
+    def __init__(self, data: torch.Tensor, T: int, bstride: int, device):
+        super().__init__(int(data.shape[0]), T, int(data.shape[2]), 1, 1, device, data=data, keep_halo=True)
+        self._bstride = int(bstride)
 
-    def __init__(self, model: WMEncodecModel, max_frames: int, max_window: int):
-        cfg, dev = model.cfg, model.device
-        if max_frames < 1 or max_window < 1:
-            raise ValueError("decode_stream needs max_frames >= 1 and max_window >= 1")
-        nodes = model.decoder.nodes
-        self.m, self.cap, self.max_window = model, max_frames, max_window
+    @property
+    def bstride(self) -> int:
+        return self._bstride
+
+
+class _StreamCore:
+    """What `DecodeStream` and `BatchDecodeStream` share: the decoder cut in two, the buffers of both halves, and every launch over them.
+
+    Stage 1 — dequantiser, first convolution, LSTM + skip — runs once over every row: the convolution's GEMM over the rows whose
+    look-ahead has arrived, the LSTM behind it as `ssrhip_lstm_layer` calls that continue (`t_begin` > 0) on the stream's own `gin` /
+    `hbuf` / `cbuf`. Stage 2 — everything behind the LSTM — runs over windows of stage-1 output, read in place, into buffers that one
+    dry pass over the largest window allocated. Every launch is the one `decode` issues for the same layer, over fewer rows, on the
+    caller's stream.
+
+    The core counts ROWS of a time axis [B][rows]; which frame of which item lives in which row is the derived class's business
+    (`DecodeStream`: frame t is row t; `BatchDecodeStream`: `batch_align_plan`). The one thing it has to be told is `conv_row0`, the first
+    row the convolution computes: the convolution's row r reads the rows [r - conv_row0, r - conv_row0 + pl0 + pr0] of `z.data`."""
+
+    def __init__(self, model: WMEncodecModel, entry: str, max_window: int):
+        cfg, nodes = model.cfg, model.decoder.nodes
+        self.m, self.max_window = model, max_window
         self.hop = int(math.prod(cfg.ratios))
         self.conv0: _Conv = nodes[0][2]
         self.lstm: Optional[_Lstm] = nodes[1][2] if nodes[1][1] == "lstm" else None
         self.tail = nodes[2:] if self.lstm is not None else nodes[1:]
         c0 = self.conv0
         if not (nodes[0][1] == "conv" and c0.s == 1 and c0.Cin > 1 and c0.Cout > 4 and self.tail and self.tail[0][1] == "convtr"):
-            raise NotImplementedError("decode_stream: the decoder does not start with a stride-1 convolution into a transposed convolution")
-        self.pl0, self.pr0 = c0.pads(max_frames)                      # stride 1: no length-dependent extra padding
-        assert (self.pl0, self.pr0) == (c0.pl, c0.pr)
+            raise NotImplementedError(f"{entry}: the decoder does not start with a stride-1 convolution into a transposed convolution")
+        self.pl0, self.pr0 = c0.pl, c0.pr                             # stride 1: no length-dependent extra padding
         self.margins = stream_margins(cfg)
         self.reflect = cfg.pad_mode == "reflect"
         last = nodes[-1][2]
         self._few_eligible = last.Cout <= 4 and last.s == 1 and last.Cin % 8 == 0       # `_conv`'s conditions on the layer itself
+
+    def _allocate(self, B: int, rows: int, conv_row0: int, out_frames: int):
+        """Every buffer of both stages, for B items of `rows` rows each, and `wav` for `out_frames` frames per item. Zero-filled: halo
+        rows, and rows behind an item's last frame, must read as zeros."""
+        m, c0 = self.m, self.conv0
+        dev, D, C0 = m.device, m.cfg.dimension, c0.Cout
         f32 = dict(dtype=torch.float32, device=dev)
-        K, D, C0 = cfg.n_q, cfg.dimension, c0.Cout
-        # stage 1 (zero-filled: halo rows, and rows behind the last frame, must read as zeros)
-        self.codes = torch.zeros(K * max_frames, dtype=torch.int32, device=dev)
-        self.lohi = torch.zeros(2, dtype=torch.int32, device=dev)
-        self.z = TM(1, max_frames, D, self.pl0, self.pr0, dev, data=torch.zeros(1, self.pl0 + max_frames + self.pr0, D, **f32))
-        self.s1 = TM(1, max_frames, C0, 1, 1, dev, data=torch.zeros(1, max_frames + 2, C0, **f32))      # what the first convtr reads
-        self.s1.elu = bool(model.elu_on_store and self.lstm is not None)
+        self.B, self.rows, self.conv_row0 = B, rows, conv_row0
+        self.z = TM(B, rows - conv_row0, D, self.pl0, self.pr0, dev, data=torch.zeros(B, self.pl0 + rows - conv_row0 + self.pr0, D, **f32))
+        self.s1 = TM(B, rows, C0, 1, 1, dev, data=torch.zeros(B, rows + 2, C0, **f32))      # what the first convtr reads
+        self.s1.elu = bool(m.elu_on_store and self.lstm is not None)
+        # the item stride of `s1` as the stage-1 launches are given it. One item: nothing multiplies it by anything but 0, and
+        # `DecodeStream` has always passed the plain rows * C0 of its other buffers
+        self._s1_bs = self.s1.bstride if B > 1 else rows * C0
         if self.lstm is not None:
             L, nl = self.lstm, len(self.lstm.layers)
             assert L.C == C0
-            self.y0 = torch.zeros(1, max_frames, C0, **f32)
-            self.gins = [torch.zeros(1, max_frames, 4 * C0, **f32) for _ in range(nl)]
-            self.hbufs = [torch.zeros(2, 16, C0, **f32) for _ in range(nl)]
-            self.cbufs = [torch.zeros(1, C0, **f32) for _ in range(nl)]
-            self.mids = [torch.zeros(1, max_frames, C0, **f32) for _ in range(nl - 1)]
-            split = model._lstm_use_split(L, 1)
-            self.hsplits = [torch.zeros(2 * 64 * C0 * 3, dtype=torch.int16, device=dev) if (split and L.split[l] is not None) else None
-                            for l in range(nl)]
-        self.wav = torch.zeros(1, 1, max_frames * self.hop, **f32)
+            self.y0 = torch.zeros(B, rows, C0, **f32)
+            self.gins = [torch.zeros(B, rows, 4 * C0, **f32) for _ in range(nl)]
+            self.hbufs = [torch.zeros(2, (B + 15) // 16 * 16, C0, **f32) for _ in range(nl)]
+            self.cbufs = [torch.zeros(B, C0, **f32) for _ in range(nl)]
+            self.mids = [torch.zeros(B, rows, C0, **f32) for _ in range(nl - 1)]
+            split = m._lstm_use_split(L, B)
+            self.hsplits = [torch.zeros(2 * ((B + 63) // 64) * 64 * C0 * 3, dtype=torch.int16, device=dev) if (split and L.split[l] is not None)
+                            else None for l in range(nl)]
+        self.wav = torch.zeros(B, 1, out_frames * self.hop, **f32)
+        self.n1 = 0                                                    # rows whose stage-1 output is final
+        self.windows = self.windows_batched = 0                        # stage-2 passes so far; those of them over every item at once
+        # stage 2: the buffers of the largest window — an interior one of max_window frames — of all B items at once (B > 1) and of one
+        # item, each by one dry pass (no launch)
+        self.pool_b, self.pool_1 = (_WindowPool() if B > 1 else None), _WindowPool()
+        real, m.lib = m.lib, _NoLaunch()
+        try:
+            n = min(rows, self.max_window + self.margins[0] + self.margins[1])
+            if B > 1:
+                self._tail_pass(0, n, None)
+                self.pool_b.frozen = True
+            self._tail_pass(0, n, 0)
+            self.pool_1.frozen = True
+        finally:
+            m.lib = real
+        torch.cuda.current_stream(dev).synchronize()                  # the fills above are done before anything else is enqueued
+
+    def _tail_pass(self, lo: int, hi: int, item: Optional[int], few: bool = False) -> TM:
+        """The layers behind the LSTM over the stage-1 rows [lo, hi), read in place (the rows next to the window are its halo: a true
+        neighbour, or the zero row an end of the utterance needs): of every item (`item` None: one batched call per layer) or of one.
+        `few`: the last layer runs as the few-output kernel, as `decode` of the whole utterance runs it."""
+        m, s1 = self.m, self.s1
+        if item is None:
+            x, pool = _TMView(s1.data[:, lo: hi + 2], hi - lo, s1.bstride, m.device), self.pool_b
+        else:
+            x, pool = TM(1, hi - lo, s1.C, 1, 1, m.device, data=s1.data[item: item + 1, lo: hi + 2], keep_halo=True), self.pool_1
+        x.elu = s1.elu
+        with m._stream_pass(pool, few):
+            return m._run(self.tail, x)
+
+    def _stage1_rows(self, a: int, b: int, front=()):
+        """Stage 1 over the rows [a, b) of every item, a = `n1`: the first convolution's GEMM over those of them it computes, then per LSTM
+        layer `_lstm_in_gemm` and `_lstm_steps`. `front` = (item, e) pairs: the rows [a, e) lie in front of that item's first frame — the
+        skip input and every layer's `gin` are zeroed there, so that the item's LSTM state stays exactly zero (`BatchDecodeStream`)."""
+        m, z, c0, s1, B, rows = self.m, self.z, self.conv0, self.s1, self.B, self.rows
+        D, C0, L = z.C, c0.Cout, self.lstm
+        bs = rows * C0                                                # item stride of y0 / mids
+        dst, dst_bs = (self.y0, bs) if L is not None else (s1.data[:, 1:], self._s1_bs)
+        ca = max(a, self.conv_row0)
+        if b > ca:                                                    # `_conv`'s GEMM: row t of the im2col view starts at z's row t - conv_row0
+            m._gemm(z.base + 4 * (ca - self.conv_row0) * D, c0.W, c0.b, dst.data_ptr() + 4 * ca * C0, b - ca, C0, c0.k * c0.Cin, c0.s * c0.Cin, C0,
+                    act_in=m._act_in(bool(c0.act_in), z), batch=B, sA=z.bstride, sC=dst_bs)
+        for u, e in front:
+            dst[u, a:e].zero_()
+        nl = len(L.layers) if L is not None else 0
+        for l in range(nl):
+            src, last = (self.y0 if l == 0 else self.mids[l - 1]), l == nl - 1
+            m._lstm_in_gemm(L, l, src.data_ptr(), bs, self.gins[l], B, rows, a, b)
+            for u, e in front:
+                self.gins[l][u, a:e].zero_()                          # zero pre-activation from h = c = 0: the state stays exactly zero
+            m._lstm_steps(L, l, self.gins[l], self.hbufs[l], self.cbufs[l], self.hsplits[l], (s1.interior if last else self.mids[l].data_ptr()),
+                          (self._s1_bs if last else bs), (self.y0.data_ptr() if last else 0), bs, B, rows, a, b, s1.elu and last)
+        self.n1 = b
+
+    def _window_rule(self) -> tuple:
+        """What `batch_window_item` takes behind an item's own state: (margins, max_window, hop, few_min_t, few_eligible)"""
+        m = self.m          # (`force_few_out`: `_conv` takes the few-output kernel whatever the rule says, so the rule waits for nothing)
+        return self.margins, self.max_window, self.hop, m.FEW_OUT_MIN_T, self._few_eligible and not m.force_few_out
+
+    def _run_window(self, win: tuple, item: Optional[int], who: Sequence[int], row0: int):
+        """One stage-2 pass over the window `win` — of every item (`item` None) or of one — and the copy of its core [c0, c1) into `wav`
+        for the items `who`; `row0` = the row of `wav`'s first frame."""
+        (c0, c1, lo, hi, few), hop = win, self.hop
+        y = self._tail_pass(lo, hi, item, few)
+        assert y.C == 1 and y.padL == 0 and y.T == (hi - lo) * hop
+        flat = y.data.view(y.B, -1)
+        s0, s1_, d0, d1 = (c0 - lo) * hop, (c1 - lo) * hop, (c0 - row0) * hop, (c1 - row0) * hop
+        if item is None and len(who) == self.B:
+            self.wav[:, 0, d0:d1].copy_(flat[:, s0:s1_])
+        else:
+            for u in who:
+                self.wav[u, 0, d0:d1].copy_(flat[u if item is None else 0, s0:s1_])
+        self.windows += 1
+        self.windows_batched += int(item is None)
+
+
+class DecodeStream(_StreamCore):
+    """`WMEncodecModel.decode_stream`: the decoder of one utterance (B = 1), advanced as its frames arrive — `_StreamCore` with frame t in
+    row t.
+
+    Stage 1 runs over the frames whose look-ahead (`stream_lookahead`) has arrived. Stage 2 runs over windows of stage-1 output with the
+    margins of `stream_margins` on either side, whose samples are dropped; an end of the utterance is a true edge (the layers' own
+    padding, no margin). Frames nearer to the current end than look-ahead + margin wait for more frames or for `finish()`. Where a
+    launcher chooses by length (`_conv`'s few-output kernel from `FEW_OUT_MIN_T` rows on) the stream waits until the whole utterance's
+    choice is known and takes it (`batch_window_item`, the one window rule of both streams)."""
+
+    def __init__(self, model: WMEncodecModel, max_frames: int, max_window: int):
+        if max_frames < 1 or max_window < 1:
+            raise ValueError("decode_stream needs max_frames >= 1 and max_window >= 1")
+        super().__init__(model, "decode_stream", max_window)
+        self.cap = max_frames
+        self.codes = torch.zeros(model.cfg.n_q * max_frames, dtype=torch.int32, device=model.device)
+        self.lohi = torch.zeros(2, dtype=torch.int32, device=model.device)
         self.n_pushed = 0          # frames whose codes have arrived
-        self.n1 = 0                # frames whose stage-1 output is final
         self.n2 = 0                # frames whose samples have been written (and, from `emit_from` on, returned)
         self.emit_from: Optional[int] = None
         self.finished = False
-        self.windows = 0           # stage-2 passes so far
-        # stage 2: the buffers of the largest window, allocated by a dry pass (no launch) — an interior window of max_window frames
-        self.pool = _WindowPool()
-        real, model.lib = model.lib, _NoLaunch()
-        try:
-            n = min(max_frames, max_window + self.margins[0] + self.margins[1])
-            self._tail_pass(0, n)
-        finally:
-            model.lib = real
-        self.pool.frozen = True
-        torch.cuda.current_stream(dev).synchronize()                  # the fills above are done before anything else is enqueued
-
-    def _tail_pass(self, lo: int, hi: int) -> TM:
-        """The layers behind the LSTM over the stage-1 frames [lo, hi), read in place (the rows next to the window are its halo: a true
-        neighbour, or the zero row an end of the utterance needs)."""
-        m, s1 = self.m, self.s1
-        x = TM(1, hi - lo, s1.C, 1, 1, m.device, data=s1.data[:, lo: hi + 2], keep_halo=True)
-        x.elu = s1.elu
-        self.pool.at = 0
-        m._tm_pool = self.pool
-        try:
-            return m._run(self.tail, x)
-        finally:
-            m._tm_pool = None
+        self._allocate(1, max_frames, 0, max_frames)
 
     def _stage1(self, final: bool):
-        m, z, c0 = self.m, self.z, self.conv0
-        n, D = self.n_pushed, z.C
+        m, z, n = self.m, self.z, self.n_pushed
         ready = n if final else n - self.pr0
         if self.reflect and not final and n <= max(self.pl0, self.pr0):
             ready = 0                                                 # reflect padding of so short an input depends on its length
@@ -1096,53 +1192,21 @@ class DecodeStream:
             return
         if self.reflect:                                             # (constant padding: the zero rows the buffer was created with)
             if final:
-                m._call("ssrhip_pad_reflect", z.base, 1, n, self.pl0, self.pr0, D, z.bstride)
+                m._call("ssrhip_pad_reflect", z.base, 1, n, self.pl0, self.pr0, z.C, z.bstride)
             elif a == 0:
-                m._call("ssrhip_pad_reflect", z.base, 1, n, self.pl0, 0, D, z.bstride)
-        C0 = c0.Cout
-        dst = self.y0.data_ptr() if self.lstm is not None else self.s1.interior
-        # `_conv`'s GEMM over the rows [a, b): row t of the im2col view starts at padded row t
-        m._gemm(z.base + 4 * a * D, c0.W, c0.b, dst + 4 * a * C0, b - a, C0, c0.k * c0.Cin, c0.s * c0.Cin, C0, act_in=m._act_in(bool(c0.act_in), z),
-                batch=1, sA=z.bstride, sC=self.cap * C0)
-        if self.lstm is not None:
-            L, nl, T = self.lstm, len(self.lstm.layers), self.cap
-            for l in range(nl):
-                src = self.y0 if l == 0 else self.mids[l - 1]
-                m._lstm_in_gemm(L, l, src.data_ptr(), T * C0, self.gins[l], 1, T, a, b)
-                out_ptr = self.s1.interior if l == nl - 1 else self.mids[l].data_ptr()
-                m._lstm_steps(L, l, self.gins[l], self.hbufs[l], self.cbufs[l], self.hsplits[l], out_ptr, T * C0,
-                              (self.y0.data_ptr() if l == nl - 1 else 0), T * C0, 1, T, a, b, self.s1.elu and l == nl - 1)
-        self.n1 = b
-
-    def _few_out(self, final: bool) -> Optional[bool]:
-        """Does `decode` of the whole utterance run its last layer as the few-output kernel? None: not known yet."""
-        m = self.m
-        if not self._few_eligible or m.force_few_out:
-            return False                                              # (forced: `_conv` takes it whatever this says)
-        if self.n_pushed * self.hop >= m.FEW_OUT_MIN_T:
-            return True
-        return False if final else None
+                m._call("ssrhip_pad_reflect", z.base, 1, n, self.pl0, 0, z.C, z.bstride)
+        self._stage1_rows(a, b)
 
     def _stage2(self, final: bool):
         if self.emit_from is None:
             return
-        few = self._few_out(final)
-        if few is None:
-            return
-        limit = self.n_pushed if final else self.n1 - self.margins[1]
-        m = self.m
-        while self.n2 < limit:
-            c0, c1 = self.n2, min(self.n2 + self.max_window, limit)
-            lo, hi = stream_window(c0, c1, self.n1, self.margins)
-            m._stream_few_out = few
-            try:
-                y = self._tail_pass(lo, hi)
-            finally:
-                m._stream_few_out = False
-            assert y.C == 1 and y.padL == 0 and y.T == (hi - lo) * self.hop
-            self.wav[0, 0, c0 * self.hop: c1 * self.hop].copy_(y.data.view(-1)[(c0 - lo) * self.hop: (c1 - lo) * self.hop])
-            self.windows += 1
-            self.n2 = c1
+        rule = self._window_rule()
+        while True:                                                   # one item: off = 0, E = emit_from, top = n_pushed, closed = final
+            win = batch_window_item(0, self.emit_from, self.n2, self.n_pushed, self.n1, final, *rule)
+            if win is None:
+                return
+            self._run_window(win, 0, [0], 0)
+            self.n2 = win[1]
 
     def _out(self, a: int) -> torch.Tensor:
         return self.wav[:, :, a * self.hop: self.n2 * self.hop]
@@ -1225,7 +1289,8 @@ def batch_stage1_range(n1: int, tops: Sequence[int], ended: Sequence[bool], clos
 
 def batch_window_item(off: int, E: int, n2: int, top: int, n1: int, closed: bool, margins: Tuple[int, int], max_window: int, hop: int,
                       few_min_t: int, few_eligible: bool):
-    """The next stage-2 window of ONE item of the batch, in rows, decided exactly as `DecodeStream._stage2` decides it for that item alone:
+    """The next stage-2 window of ONE item, in rows — the window rule of both streams (a `DecodeStream` is the
+    item with off = 0, E = its first emitted frame, top = the frames pushed, closed = `finish()` was called):
     -> (c0, c1, lo, hi, few) or None (nothing to emit yet). off = the item's first row, n2 = the row its output has reached (>= E: the
     prompt is never emitted), top = the row behind its last arrived frame, n1 = the row stage 1 has reached, closed = the item has ended
     and stage 1 has passed its end (`top` is then a true edge: the layers' own padding, no margin). `few`: does `decode` of the whole
@@ -1266,21 +1331,9 @@ def batch_window_groups(wins: Sequence[Optional[tuple]]) -> Tuple[Optional[tuple
     return key, by_key[key], sorted(u for k, us in by_key.items() if k != key for u in us)
 
 
-class _TMView(TM):
-    """A window of rows of a larger [B][rows][C] buffer, read in place: the items are `bstride` elements apart, not rows * C."""
-
-    def __init__(self, data: torch.Tensor, T: int, bstride: int, device):
-        super().__init__(int(data.shape[0]), T, int(data.shape[2]), 1, 1, device, data=data, keep_halo=True)
-        self._bstride = int(bstride)
-
-    @property
-    def bstride(self) -> int:
-        return self._bstride
-
-
-class BatchDecodeStream:
+class BatchDecodeStream(_StreamCore):
     """`WMEncodecModel.decode_stream_batch`: the decoders of B utterances that are generated in lock-step, advanced together as their
-    frames arrive — `DecodeStream` (one utterance, B = 1) with every per-poll operation as ONE dense batched call of the same kernels.
+    frames arrive — `_StreamCore` with B items: every per-poll operation of `DecodeStream` as ONE dense batched call of the same kernels.
 
     One aligned time axis (`batch_align_plan`): item u's frame t is row off_u + t of buffers [B][rows][C]; the prompts all end at row E,
     generated frame j of every item is row E + j. Per `advance`: one `ssrhip_rvq_decode` with B items, the first convolution's GEMM with
@@ -1302,85 +1355,27 @@ class BatchDecodeStream:
     one dry pass — is allocated here, so create the stream before the decode engine's first launch."""
 
     def __init__(self, model: WMEncodecModel, prompt_lens: Sequence[int], max_new_frames: int, max_window: int):
-        cfg, dev = model.cfg, model.device
         if max_new_frames < 1 or max_window < 1:
             raise ValueError("decode_stream_batch needs max_new_frames >= 1 and max_window >= 1")
-        nodes = model.decoder.nodes
-        self.m, self.max_new, self.max_window = model, int(max_new_frames), int(max_window)
-        self.hop = int(math.prod(cfg.ratios))
-        self.conv0: _Conv = nodes[0][2]
-        self.lstm: Optional[_Lstm] = nodes[1][2] if nodes[1][1] == "lstm" else None
-        self.tail = nodes[2:] if self.lstm is not None else nodes[1:]
-        c0 = self.conv0
-        if not (nodes[0][1] == "conv" and c0.s == 1 and c0.Cin > 1 and c0.Cout > 4 and self.tail and self.tail[0][1] == "convtr"):
-            raise NotImplementedError("decode_stream_batch: the decoder does not start with a stride-1 convolution into a transposed convolution")
-        self.pl0, self.pr0 = c0.pl, c0.pr
+        super().__init__(model, "decode_stream_batch", int(max_window))
+        self.max_new = int(max_new_frames)
         plan = batch_align_plan(prompt_lens, self.pl0)
         self.prompt_lens = [int(p) for p in prompt_lens]
         self.off, self.E = plan["off"], plan["E"]
-        self.B = B = len(self.off)
-        self.margins = stream_margins(cfg)
-        self.reflect = cfg.pad_mode == "reflect"
+        B = len(self.off)
         if self.reflect and min(self.prompt_lens) <= max(self.pl0, self.pr0):
             raise ValueError(f"decode_stream_batch: with reflect padding every prompt must be longer than the first convolution's padding "
                              f"({max(self.pl0, self.pr0)} frames), got {self.prompt_lens}")
-        last = nodes[-1][2]
-        self._few_eligible = bool(last.Cout <= 4 and last.s == 1 and last.Cin % 8 == 0 and not model.force_few_out)
-        f32 = dict(dtype=torch.float32, device=dev)
-        K, D, C0 = cfg.n_q, cfg.dimension, c0.Cout
-        self.R = R = self.E + self.max_new                             # rows of the common time axis
-        self.codes = torch.zeros(B * K * max(max(self.prompt_lens), self.max_new), dtype=torch.int32, device=dev)
-        self.z = TM(B, R - self.pl0, D, self.pl0, self.pr0, dev, data=torch.zeros(B, R + self.pr0, D, **f32))    # data row == row
-        self.s1 = TM(B, R, C0, 1, 1, dev, data=torch.zeros(B, R + 2, C0, **f32))
-        self.s1.elu = bool(model.elu_on_store and self.lstm is not None)
-        if self.lstm is not None:
-            L, nl = self.lstm, len(self.lstm.layers)
-            assert L.C == C0
-            self.y0 = torch.zeros(B, R, C0, **f32)
-            self.gins = [torch.zeros(B, R, 4 * C0, **f32) for _ in range(nl)]
-            self.hbufs = [torch.zeros(2, (B + 15) // 16 * 16, C0, **f32) for _ in range(nl)]
-            self.cbufs = [torch.zeros(B, C0, **f32) for _ in range(nl)]
-            self.mids = [torch.zeros(B, R, C0, **f32) for _ in range(nl - 1)]
-            split = model._lstm_use_split(L, B)
-            self.hsplits = [torch.zeros(2 * ((B + 63) // 64) * 64 * C0 * 3, dtype=torch.int16, device=dev) if (split and L.split[l] is not None)
-                            else None for l in range(nl)]
-        self.wav = torch.zeros(B, 1, self.max_new * self.hop, **f32)
-        self.top = [self.off[u] for u in range(B)]                     # row behind item u's last arrived frame
+        self.codes = torch.zeros(B * model.cfg.n_q * max(max(self.prompt_lens), self.max_new), dtype=torch.int32, device=model.device)
+        self.top = list(self.off)                                      # row behind item u's last arrived frame
         self.ended = [False] * B
         self.closed = [False] * B                                      # ended, and stage 1 has passed the end
-        self.n1 = 0                                                    # rows whose stage-1 output is final (live items)
         self.n2 = [self.E] * B                                         # row item u's samples have reached
         self.primed = False
-        self.windows = self.windows_batched = 0
-        # stage 2: the buffers of the largest batched window and of the largest B = 1 window, each by one dry pass (no launch)
-        self.pool_b, self.pool_1 = _WindowPool(), _WindowPool()
-        real, model.lib = model.lib, _NoLaunch()
-        try:
-            n = min(R, self.max_window + self.margins[0] + self.margins[1])
-            self._tail_pass(0, n, None)
-            self._tail_pass(0, n, 0)
-        finally:
-            model.lib = real
-        self.pool_b.frozen = self.pool_1.frozen = True
-        torch.cuda.current_stream(dev).synchronize()                  # the fills above are done before anything else is enqueued
+        # rows of the common time axis: E + max_new. Data row == row, so the convolution's first row is pl0
+        self._allocate(B, self.E + self.max_new, self.pl0, self.max_new)
 
     # ------------------------------------------------------------------ the pieces
-    def _tail_pass(self, lo: int, hi: int, item: Optional[int]) -> TM:
-        """The layers behind the LSTM over the stage-1 rows [lo, hi), read in place: of every item (`item` None: one batched call per
-        layer) or of one."""
-        m, s1 = self.m, self.s1
-        if item is None:
-            x, pool = _TMView(s1.data[:, lo: hi + 2], hi - lo, s1.bstride, m.device), self.pool_b
-        else:
-            x, pool = TM(1, hi - lo, s1.C, 1, 1, m.device, data=s1.data[item: item + 1, lo: hi + 2], keep_halo=True), self.pool_1
-        x.elu = s1.elu
-        pool.at = 0
-        m._tm_pool = pool
-        try:
-            return m._run(self.tail, x)
-        finally:
-            m._tm_pool = None
-
     def _item_ptr(self, t: torch.Tensor, u: int, row: int) -> int:
         return t.data_ptr() + 4 * (u * t.stride(0) + row * t.stride(1))
 
@@ -1395,65 +1390,28 @@ class BatchDecodeStream:
                          z.bstride)
 
     def _stage1(self):
-        m, z, c0, B, R = self.m, self.z, self.conv0, self.B, self.R
         a, b = batch_stage1_range(self.n1, self.top, self.ended, self.closed, self.pr0)
-        b = min(b, R)
+        b = min(b, self.rows)
         if b > a:
-            D, C0 = z.C, c0.Cout
-            ca = max(a, self.pl0)                                     # row r of the convolution reads the rows [r - pl0, r + pr0] of z
-            dst = self.y0 if self.lstm is not None else self.s1.data[:, 1:]
-            dst_bs = R * C0 if self.lstm is not None else self.s1.bstride
-            if b > ca:
-                m._gemm(z.base + 4 * (ca - self.pl0) * D, c0.W, c0.b, self._item_ptr(dst, 0, ca), b - ca, C0, c0.k * c0.Cin, c0.s * c0.Cin, C0,
-                        act_in=m._act_in(bool(c0.act_in), z), batch=B, sA=z.bstride, sC=dst_bs)
-            front = [(u, min(b, self.off[u])) for u in range(B) if a < self.off[u]]      # rows in front of an item's first frame
-            for u, e in front:
-                dst[u, a:e].zero_()
-            if self.lstm is not None:
-                L, nl = self.lstm, len(self.lstm.layers)
-                for l in range(nl):
-                    src = self.y0 if l == 0 else self.mids[l - 1]
-                    m._lstm_in_gemm(L, l, src.data_ptr(), R * C0, self.gins[l], B, R, a, b)
-                    for u, e in front:
-                        self.gins[l][u, a:e].zero_()                  # zero pre-activation from h = c = 0: the state stays exactly zero
-                    out_ptr = self.s1.interior if l == nl - 1 else self.mids[l].data_ptr()
-                    out_bs = self.s1.bstride if l == nl - 1 else R * C0
-                    m._lstm_steps(L, l, self.gins[l], self.hbufs[l], self.cbufs[l], self.hsplits[l], out_ptr, out_bs,
-                                  (self.y0.data_ptr() if l == nl - 1 else 0), R * C0, B, R, a, b, self.s1.elu and l == nl - 1)
-        for u in range(B):
+            # (front: the rows in front of an item's first frame)
+            self._stage1_rows(a, b, [(u, min(b, self.off[u])) for u in range(self.B) if a < self.off[u]])
+        for u in range(self.B):
             if self.ended[u] and not self.closed[u] and self.top[u] <= b:
                 if b > self.top[u]:
                     self.s1.data[u, 1 + self.top[u]: 1 + b].zero_()   # the zero row the last window's transposed convolution reads
                 self.closed[u] = True
-        self.n1 = b
 
     def _stage2(self):
-        m, hop, E = self.m, self.hop, self.E
+        rule = self._window_rule()
         while True:
-            wins = [batch_window_item(self.off[u], E, self.n2[u], self.top[u], self.n1, self.closed[u], self.margins, self.max_window, hop,
-                                      m.FEW_OUT_MIN_T, self._few_eligible) for u in range(self.B)]
+            wins = [batch_window_item(self.off[u], self.E, self.n2[u], self.top[u], self.n1, self.closed[u], *rule) for u in range(self.B)]
             key, members, alone = batch_window_groups(wins)
             if key is None and not alone:
                 return
-            runs = ([(key, None, members)] if key is not None else []) + [(wins[u], u, [u]) for u in alone]
-            for (c0, c1, lo, hi, few), item, who in runs:
-                m._stream_few_out = few
-                try:
-                    y = self._tail_pass(lo, hi, item)
-                finally:
-                    m._stream_few_out = False
-                assert y.C == 1 and y.padL == 0 and y.T == (hi - lo) * hop
-                flat = y.data.view(y.B, -1)
-                s0, s1_, d0, d1 = (c0 - lo) * hop, (c1 - lo) * hop, (c0 - E) * hop, (c1 - E) * hop
-                if item is None and len(who) == self.B:
-                    self.wav[:, 0, d0:d1].copy_(flat[:, s0:s1_])
-                else:
-                    for u in who:
-                        self.wav[u, 0, d0:d1].copy_(flat[u if item is None else 0, s0:s1_])
-                self.windows += 1
-                self.windows_batched += int(item is None)
+            for win, item, who in ([(key, None, members)] if key is not None else []) + [(wins[u], u, [u]) for u in alone]:
+                self._run_window(win, item, who, self.E)
                 for u in who:
-                    self.n2[u] = c1
+                    self.n2[u] = win[1]
 
     def _dequant(self, n: int, row: int):
         z, cfg = self.z, self.m.cfg
@@ -1520,7 +1478,7 @@ class BatchDecodeStream:
                 raise ValueError(f"item {u} has ended and gets {new[u]} more frames")
             if not self.ended[u] and not ended[u] and new[u] != n:
                 raise ValueError(f"lock-step: item {u} goes on with {new[u]} new frames while another item gets {n}")
-            if self.top[u] + new[u] > self.R:
+            if self.top[u] + new[u] > self.rows:
                 raise ValueError(f"item {u}: more than max_new_frames = {self.max_new} generated frames")
         a = list(self.n2)
         live_top = [self.top[u] for u in range(B) if not self.ended[u]]

@@ -276,6 +276,25 @@ def test_a_prompt_shorter_than_the_left_margin_takes_its_first_window_alone():
         assert got[u].shape == want.shape and err <= 2e-5, (u, err)
 
 
+@pytest.mark.parametrize("name", ["tiny_const", "tiny_reflect", "r8542_c128"])
+def test_a_batch_of_one_item_is_decode_stream_bit_for_bit(name):
+    """The two streams are one core: a `BatchDecodeStream` with ONE item (prompt 5 frames, 20 generated frames in polls of 7, ended with
+    the last poll) returns the bits of a `DecodeStream` given the prompt as an `emit=False` prefix and the same frames in pushes of 7.
+    Same kernels at B = 1, the same window rule, and the rows in front of the item's first frame leave the LSTM state exactly zero."""
+    import test_gpu_stream as GS
+    cfg, _, m = GS._codec(name)
+    P, G = 5, 20
+    codes = torch.randint(0, cfg.bins, (1, cfg.n_q, P + G), generator=torch.Generator().manual_seed(55))
+    one = m.decode_stream(P + G + 2)
+    assert one.push(codes[..., :P].cuda(), emit=False).shape == (1, 1, 0)
+    chunks = [one.push(codes[..., t: t + 7].cuda()) for t in range(P, P + G, 7)] + [one.finish()]
+    want = torch.cat(chunks, -1).clone()
+    got, st, calls = _stream(m, [codes], 1, 7, (P,), (G,))
+    assert st.B == 1 and len(calls) == 3 and st.windows_batched == 0
+    assert got[0].shape == want.shape == (1, 1, G * cfg.hop)
+    assert torch.equal(got[0], want), f"max |batch of one - DecodeStream| = {float((got[0] - want).abs().max()):.3g}"
+
+
 def test_batch_decode_stream_refuses_what_decode_refuses():
     cfg, _, m = _codec("constant")
     st = m.decode_stream_batch((5, 9), 8)

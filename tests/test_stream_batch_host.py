@@ -173,6 +173,97 @@ def test_window_rule_per_item_and_who_runs_together():
     assert WM.batch_window_groups([a, a, ended]) == (a, [0, 1], [2])        # an ended item's last window runs alone
 
 
+# ----------------------------------------------------------------------------------------------- one window rule for both streams
+class _OneUtterance:
+    """The host state of a `DecodeStream`: an `emit=False` prefix, pushes, finish(). `n1` follows the stage-1 readiness rule."""
+
+    def __init__(self, pr0):
+        self.pr0, self.n_pushed, self.n1, self.n2, self.emit_from = pr0, 0, 0, 0, None
+
+    def arrive(self, n, emit, final):
+        if (emit or final) and self.emit_from is None:
+            self.emit_from = self.n2 = self.n_pushed
+        self.n_pushed += n
+        self.n1 = max(self.n1, self.n_pushed if final else self.n_pushed - self.pr0)
+
+
+def _windows_before_the_core(s, final, margins, max_window, hop, few_min_t, few_eligible, force_few_out):
+    """`DecodeStream._stage2` and `._few_out` as they were before both streams took their windows from `batch_window_item`"""
+    out = []
+    if s.emit_from is None:
+        return out
+    if not few_eligible or force_few_out:
+        few = False
+    elif s.n_pushed * hop >= few_min_t:
+        few = True
+    else:
+        few = False if final else None
+    if few is None:
+        return out
+    limit = s.n_pushed if final else s.n1 - margins[1]
+    while s.n2 < limit:
+        c0, c1 = s.n2, min(s.n2 + max_window, limit)
+        lo, hi = WM.stream_window(c0, c1, s.n1, margins)
+        out.append((c0, c1, lo, hi, few))
+        s.n2 = c1
+    return out
+
+
+def _windows_by_the_batch_rule(s, final, margins, max_window, hop, few_min_t, few_eligible, force_few_out):
+    """the same decision as `DecodeStream._stage2` takes it now: the item with off = 0, E = emit_from, top = n_pushed, closed = final"""
+    out = []
+    while s.emit_from is not None:
+        w = WM.batch_window_item(off=0, E=s.emit_from, n2=s.n2, top=s.n_pushed, n1=s.n1, closed=final, margins=margins, max_window=max_window,
+                                 hop=hop, few_min_t=few_min_t, few_eligible=few_eligible and not force_few_out)
+        if w is None:
+            break
+        out.append(w)
+        s.n2 = w[1]
+    return out
+
+
+def _windows_by_decode_stream(s, final, margins, max_window, hop, few_min_t, few_eligible, force_few_out):
+    """... and `DecodeStream._stage2` itself, on an instance that has the host state only and records the windows it would run"""
+    st, out = object.__new__(WM.DecodeStream), []
+    st.m = SimpleNamespace(FEW_OUT_MIN_T=few_min_t, force_few_out=force_few_out)
+    st.margins, st.max_window, st.hop, st._few_eligible = margins, max_window, hop, few_eligible
+    st.n_pushed, st.n1, st.n2, st.emit_from = s.n_pushed, s.n1, s.n2, s.emit_from
+    st._run_window = lambda win, item, who, row0: out.append(win) if (item, who, row0) == (0, [0], 0) else out.append("not item 0")
+    st._stage2(final)
+    s.n2 = st.n2
+    return out
+
+
+@pytest.mark.parametrize("ratios", [(4, 3, 2, 2), (8, 5, 4, 2)])
+def test_decode_stream_takes_the_windows_it_took_before_from_the_batch_rule(ratios):
+    cfg = W.CodecConfig(dimension=64, n_filters=8, ratios=ratios, bins=64)
+    margins, pr0, hop = WM.stream_margins(cfg), WM.stream_lookahead(cfg), cfg.hop
+    assert margins == {(4, 3, 2, 2): (2, 2), (8, 5, 4, 2): (1, 1)}[ratios] and pr0 == 3
+    cases = windows = waited = 0
+    for T in (1, 2, 5, 6, 17, 61):
+        for prefix in (0, 20):
+            total = prefix + T
+            # the last layer's kernel is known from the first frame on / from the middle on / with the very last frame / at finish() only
+            for few_min_t in (1, total * hop // 2 + 1, total * hop, total * hop + 1):
+                for push, max_window, eligible, force in [(p, w, e, f) for p in (1, 7, 16, 10 ** 6) for w in (1, 7, 16) for e in (False, True)
+                                                          for f in (False, True)]:
+                    rule = (margins, max_window, hop, few_min_t, eligible, force)
+                    runs = [(_OneUtterance(pr0), fn) for fn in (_windows_before_the_core, _windows_by_the_batch_rule, _windows_by_decode_stream)]
+                    events = ([(prefix, False, False)] if prefix else []) + [(min(push, T - t), True, False) for t in range(0, T, push)] + [(0, True, True)]
+                    for n, emit, final in events:
+                        got = []
+                        for s, fn in runs:
+                            s.arrive(n, emit, final)
+                            got.append((fn(s, final, *rule), s.n2))
+                        assert got[0] == got[1] == got[2], (T, prefix, few_min_t, push, max_window, eligible, force, (n, emit, final), got)
+                        assert all(w[0] >= prefix and w[1] - w[0] <= max_window for w in got[0][0])
+                        windows += len(got[0][0])
+                        waited += int(not final and not got[0][0] and runs[0][0].n1 - margins[1] > runs[0][0].n2)
+                    assert runs[0][0].n2 == total == runs[1][0].n2 == runs[2][0].n2
+                    cases += 1
+    assert cases == 6 * 2 * 4 * 4 * 3 * 2 * 2 and windows > cases and waited > 0      # (waited: polls held back for the last layer's kernel)
+
+
 # ----------------------------------------------------------------------------------------------- refusals, before any library call
 def _utt(T=9, mi=None, L=5):
     return {"x": torch.zeros(1, L, dtype=torch.long), "y": torch.zeros(1, T, K, dtype=torch.long),
