@@ -578,6 +578,55 @@ class IntStaging:
         return [self.dev[o:o + p.size] for o, p in zip(offs, parts)]
 
 
+def noise_segments(drawn: Sequence[int], slots: Sequence[int], chunk: int, limit: int):
+    """Which steps' noise to draw next: per slot u of `slots`, in order, (u, off, n) = its next `chunk` steps from off = drawn[u], cut
+    at `limit`; slots that have reached the limit are left out."""
+    segs = [(u, drawn[u], min(chunk, limit - drawn[u])) for u in slots]
+    return [s for s in segs if s[2] > 0]
+
+
+class NoiseUploader:
+    """The host-noise pipeline of a sampled run: draw a chunk of steps through a `TorchCpuNoiseFeed` into pinned staging memory and send it
+    to `noise[u, off:off + n]` on a copy stream while the GPU decodes the chunk before (a 16-step chunk is ~14 ms of GPU time at 830M, its
+    draws ~3 ms of host time). Three staging buffers [n_utt, chunk, K, card]: the chunk's index & 1 is the steady-state ring, 2 holds the
+    first chunk of newly admitted slots. A buffer's `free` event (its last upload has finished) outlives the run, as the buffer does: the
+    next run's first `send` into it waits for the previous run's last look-ahead."""
+
+    def __init__(self, noise: torch.Tensor, chunk: int):
+        self.noise, self.chunk = noise, chunk
+        self.bufs = [torch.empty(noise.shape[0], chunk, *noise.shape[2:], dtype=torch.float32).pin_memory() for _ in range(3)]
+        self.stream = torch.cuda.Stream(noise.device)
+        self.free: List[Optional[torch.cuda.Event]] = [None] * 3
+        self.feed, self.pending = None, []                      # pending: the uploads the next decode has to wait for
+
+    def begin(self, feed: "TorchCpuNoiseFeed"):
+        self.feed, self.pending = feed, []
+
+    @staticmethod
+    def fill(feed: "TorchCpuNoiseFeed", buf: torch.Tensor, slots: Sequence[int], chunk: int, limit: int):
+        """The host half: draw the segments `noise_segments` names into buf[u, :n] (CPU, pinned or not); returns them."""
+        segs = noise_segments(feed.drawn, slots, chunk, limit)
+        for u, _, n in segs:
+            feed.draw(u, buf[u, :n])
+        return segs
+
+    def send(self, buf_i: int, slots: Sequence[int], limit: int):
+        """Draw the next chunk of `slots` (steps below `limit`) into staging buffer buf_i and send it; `wait` orders a stream after it."""
+        if self.free[buf_i] is not None:
+            self.free[buf_i].synchronize()                      # the upload that last used this staging buffer has finished
+        segs = self.fill(self.feed, self.bufs[buf_i], slots, self.chunk, limit)
+        with torch.cuda.stream(self.stream):
+            for u, off, n in segs:
+                self.noise[u, off:off + n].copy_(self.bufs[buf_i][u, :n], non_blocking=True)
+        self.free[buf_i] = self.stream.record_event()
+        self.pending.append(self.free[buf_i])
+
+    def wait(self, stream):
+        for ev in self.pending:
+            stream.wait_event(ev)
+        self.pending = []
+
+
 class TorchCpuNoiseFeed:
     """The Exp(1) tensors `torch.multinomial(probs[K, card], 1)` draws on the CPU — one `exponential_` of the logits' shape per
     decode step (reference models/ssr.py:85 via :713/:732; checked in oracle/make_golden.py::make_sampler) — produced a chunk of
@@ -754,8 +803,8 @@ class DecodeEngine:
         # ONE persistent buffer for host-drawn sampling noise: its pointer is baked into the captured graph, so generations
         # with / without host noise reuse the same context (ssrhip_sampler_cfg.use_noise selects per utterance)
         self.noise = torch.empty(n_utt, max_steps, K, arena.card, **f32)
-        self._pinned = None
-        self._copy_stream = None
+        self._uploader: Optional[NoiseUploader] = None         # host-noise pipeline of sampled runs, kept across runs
+        self._feed, self._polled = None, False                 # the current run's noise feed (None: no host noise); has it been polled?
         self._admit_stage = IntStaging()          # one-copy staging of a blocking admission's integer arrays ...
         self._admit_sent = None                   # ... and the event of its last copy
         self._prefill_ws = None
@@ -1249,8 +1298,7 @@ class DecodeEngine:
     def run_to_completion(self, chunk: int = 16, use_graph: bool = True, max_total: Optional[int] = None,
                           feed: Optional[TorchCpuNoiseFeed] = None, on_chunk=None):
         """Decode in chunks of `chunk` steps until every utterance reports done (the flags are polled once per chunk).
-        With `feed`, the host draws the NEXT chunk's sampling noise into pinned memory and uploads it on a copy stream while
-        the GPU runs the current chunk (a 16-step chunk is ~14 ms of GPU time at 830M; its draws ~3 ms of host time).
+        With `feed`, the host draws and uploads the NEXT chunk's sampling noise while the GPU runs the current chunk (`NoiseUploader`).
         `on_chunk(states)` is called after every poll with the states read there (`iter_chunks` is the same loop as a generator)."""
         states = None
         for states in self.iter_chunks(chunk, use_graph, max_total, feed):
@@ -1265,63 +1313,49 @@ class DecodeEngine:
         the noise feed is put back (`feed.finish`) when the loop ends, so a sampled run has to be consumed to its end."""
         total = 0
         limit = self.max_steps if max_total is None else min(max_total, self.max_steps)
-        dev = self.device
-        main = torch.cuda.current_stream(dev) if feed is not None else None
-        live = [True] * self.n_utt
-        ready = None
-        if feed is not None:
-            K, card = self.a.K, self.a.card
-            if self._pinned is None or self._pinned[0].shape[1] != chunk:
-                self._pinned = [torch.empty(self.n_utt, chunk, K, card, dtype=torch.float32).pin_memory() for _ in range(2)]
-                self._copy_stream = torch.cuda.Stream(dev)
-            slot_free = [None, None]
-
-            def stage(ci: int, s0: int, s1: int):
-                """draw + upload the noise of steps [s0, s1) (chunk index ci); returns the event the decode must wait for"""
-                buf = self._pinned[ci & 1]
-                if slot_free[ci & 1] is not None:
-                    slot_free[ci & 1].synchronize()            # the upload that last used this staging slot has finished
-                for u in range(self.n_utt):
-                    if live[u]:
-                        feed.draw(u, buf[u, : s1 - s0])
-                with torch.cuda.stream(self._copy_stream):
-                    self.noise[:, s0:s1].copy_(buf[:, : s1 - s0], non_blocking=True)
-                    ev = torch.cuda.Event()
-                    ev.record(self._copy_stream)
-                slot_free[ci & 1] = ev
-                return ev
-
-            ready = stage(0, 0, min(chunk, limit))             # overlaps with the prefill `start()` enqueued
-        ci = 0
+        live = list(range(self.n_utt))
+        up = self._begin_run(chunk, feed)
+        if up:
+            up.send(0, live, limit)                             # overlaps with the prefill `start()` enqueued
         states = None
         while total < limit:
             n = min(chunk, limit - total)
-            if ready is not None:
-                main.wait_event(ready)
+            if up:
+                up.wait(torch.cuda.current_stream(self.device))
             self.decode(n, use_graph)
             total += n
-            if feed is not None and total < limit:
-                ready = stage(ci + 1, total, min(total + chunk, limit))      # host works while the GPU decodes chunk ci
-            ci += 1
-            states = self.states()                              # blocks until chunk ci-1 has finished
-            if ci == 1:
-                self.t_first_chunk = time.perf_counter()        # first `chunk` frames exist (bench: time to first frames)
-            live = [not s_.done for s_ in states]
-            for u in range(self.n_utt):
-                if not live[u]:
+            if up and total < limit:
+                up.send(total // chunk & 1, live, limit)        # host draws the next chunk while the GPU runs this one
+            states = self._poll()                               # blocks until that chunk has finished
+            live = [u for u, s_ in enumerate(states) if not s_.done]
+            for u, s_ in enumerate(states):
+                if s_.done:
                     self.release_utterance(u)
-            last = not any(live) or total >= limit
-            if last and feed is not None:
-                for u, s_ in enumerate(states):
-                    feed.finish(u, int(s_.n_steps))
+            if not live or total >= limit:
+                break
             yield states
-            if last:
-                return
-        states = self.states()                                  # a limit of 0 steps: nothing was decoded
+        states = states or self.states()                        # a limit of 0 steps: nothing was decoded
         if feed is not None:
             for u, s_ in enumerate(states):
                 feed.finish(u, int(s_.n_steps))
         yield states
+
+    def _begin_run(self, chunk: int, feed: Optional[TorchCpuNoiseFeed]) -> Optional[NoiseUploader]:
+        """A decode loop starts: not polled yet and, with a feed, the engine's one uploader (rebuilt only when `chunk` changes) on it"""
+        self._polled, self._feed = False, feed
+        if feed is None:
+            return None
+        if self._uploader is None or self._uploader.chunk != chunk:
+            self._uploader = NoiseUploader(self.noise, chunk)
+        self._uploader.begin(feed)
+        return self._uploader
+
+    def _poll(self) -> List[_lib.SamplerState]:
+        """`states()`; a run's first poll is when its first `chunk` frames exist (bench: time to first frames)"""
+        states = self.states()
+        if not self._polled:
+            self._polled, self.t_first_chunk = True, time.perf_counter()
+        return states
 
     # ------------------------------------------------------------------ continuous batching
     def run_queue(self, jobs: Sequence[dict], chunk: int = 16, use_graph: bool = True, sampling: bool = False):
@@ -1349,41 +1383,14 @@ class DecodeEngine:
         results: List[Optional[tuple]] = [None] * n_jobs
         if n_jobs == 0:
             return results
-        dev = self.device
-        K, card = self.a.K, self.a.card
         slot_job: List[Optional[int]] = [None] * self.n_utt
         local: List[int] = [0] * self.n_utt           # steps enqueued for the slot's current utterance
         # longest (by its step cap) first: the utterances that will run longest start earliest and the short ones fill the slots freed
         # towards the end — the tail with a few long utterances on a mostly idle engine shrinks (simulated on the bench's ragged queue:
         # 344 -> 327 chunks). Which utterance sits in which slot when does not change any result.
         pending = sorted(range(n_jobs), key=lambda j: -int(jobs[j]["cap"])) if n_jobs > self.n_utt else list(range(n_jobs))
-        feed = TorchCpuNoiseFeed([None] * self.n_utt, K, card) if sampling else None
-        main = torch.cuda.current_stream(dev)
-        if sampling and (self._pinned is None or self._pinned[0].shape[1] != chunk or len(self._pinned) < 3):
-            self._pinned = [torch.empty(self.n_utt, chunk, K, card, dtype=torch.float32).pin_memory() for _ in range(3)]
-            self._copy_stream = torch.cuda.Stream(dev)
-        slot_free = [None, None, None]
-        waits: List[torch.cuda.Event] = []
-
-        def upload(buf_i: int, slots: Sequence[int]):
-            """draw the next `chunk` steps of `slots` into staging buffer buf_i and send them to noise[u, local[u] : +chunk]"""
-            buf = self._pinned[buf_i]
-            if slot_free[buf_i] is not None:
-                slot_free[buf_i].synchronize()
-            todo = []
-            for u in slots:
-                n = min(chunk, self.max_steps - feed.drawn[u])
-                if n > 0:
-                    off = feed.drawn[u]
-                    feed.draw(u, buf[u, :n])
-                    todo.append((u, off, n))
-            with torch.cuda.stream(self._copy_stream):
-                for u, off, n in todo:
-                    self.noise[u, off:off + n].copy_(buf[u, :n], non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record(self._copy_stream)
-            slot_free[buf_i] = ev
-            return ev
+        feed = TorchCpuNoiseFeed([None] * self.n_utt, self.a.K, self.a.card) if sampling else None
+        up = self._begin_run(chunk, feed)
 
         # Two-phase admission (VERDICT r4 item 4) is built, bit-exact and OFF by default: on the bench's ragged queue (64 utterances through 8
         # slots, 56 refills) it measured 19,785 codec-tokens/s against 19,930 for the blocking form, same token CRC
@@ -1404,10 +1411,10 @@ class DecodeEngine:
             for u, j in zip(slots, take):
                 slot_job[u] = j
                 local[u] = 0
-                if sampling:
+                if up:
                     feed.reset_slot(u, jobs[j].get("gen"))
-            if sampling:
-                waits.append(upload(2, slots))                 # the new utterances' first chunk, before their first step
+            if up:
+                up.send(2, slots, self.max_steps)               # the new utterances' first chunk, before their first step
 
         def admit_into(slots: Sequence[int]):
             """blocking admission (the first fill; refills with SSRHIP_ADMIT_TWO_PHASE=0): prefill on the decode stream"""
@@ -1431,68 +1438,40 @@ class DecodeEngine:
         self._write_slot_records(range(self.n_utt), sts=idle)
         self.page_table.copy_(torch.from_numpy(self._table_host))
         admit_into(list(range(self.n_utt)))
-        ci = 0
-        ready = None
         warm = None                                             # handle of the slots being prefilled on the side stream
-        in_flight: List[int] = []                               # slots stepping in the chunk that is enqueued and not yet polled
 
         def enqueue_chunk():
-            nonlocal waits, ready, ci, in_flight
-            for ev in waits:
-                main.wait_event(ev)
-            waits = []
-            if ready is not None:
-                main.wait_event(ready)
-            in_flight = [u for u in range(self.n_utt) if slot_job[u] is not None]
+            """one more chunk for the slots that run a job; returns them: the slots stepping in the chunk that is enqueued and not yet polled"""
+            if up:
+                up.wait(torch.cuda.current_stream(self.device))
+            stepping = [u for u in range(self.n_utt) if slot_job[u] is not None]
             self.decode(chunk, use_graph)
-            for u in in_flight:
+            for u in stepping:
                 local[u] += chunk
-            if sampling:
-                ready = upload(ci & 1, in_flight)               # host draws the next chunk while the GPU runs this one
-            ci += 1
+            if up:
+                up.send(self._steps_enqueued // chunk & 1, stepping, self.max_steps)     # the host draws while the GPU runs this chunk
+            return stepping
 
-        enqueue_chunk()
+        in_flight = enqueue_chunk()
         while True:
-            states = self.states()                              # blocks until the enqueued chunk has finished
-            if ci == 1:
-                self.t_first_chunk = time.perf_counter()
+            states = self._poll()                               # blocks until the enqueued chunk has finished
             yield states, list(slot_job)
-            freed = []
             for u in in_flight:
-                st, j = states[u], slot_job[u]
+                j = slot_job[u]
                 cap_j = min(int(jobs[j]["cap"]), self.max_steps)
-                over = local[u] >= cap_j
-                if st.done or over:
-                    n = int(st.n_steps)
-                    if st.done and n > cap_j:
-                        # the flags are polled every `chunk` steps: an utterance may finish up to chunk - 1 steps past ITS OWN cap before the
-                        # poll sees it. The fixed-group path bounded every member by the group's cap; here the bound is per utterance, and a
-                        # result longer than its cap is the same failure as not finishing (the caller raises on done != 1).
-                        st.done = 2
-                    gen = self.tokens(u, n)
-                    snap = _lib.SamplerState.from_buffer_copy(bytes(st))
-                    results[j] = (snap, gen)
-                    if sampling:
-                        feed.finish(u, n)
-                    if not st.done:                             # ran into its cap without finishing: park the slot (the caller raises)
-                        parked = (_lib.SamplerState * 1)(_lib.SamplerState.from_buffer_copy(bytes(st)))
-                        parked[0].done = 1
-                        self._write_slot_records([u], sts=parked)
-                    self.release_utterance(u)
+                if states[u].done or local[u] >= cap_j:
+                    results[j] = self._collect(u, states[u], cap_j)
                     slot_job[u] = None
-                    freed.append(u)
-            in_flight = []
             # the slots whose prefill was started one poll ago join the batch now (their prefill had a whole chunk to finish)
             if warm is not None:
                 self.admit_finish(warm[0])
                 now_running(warm[0]["slots"], warm[1])
                 warm = None
             free_slots = [u for u in range(self.n_utt) if slot_job[u] is None]
-            any_live = any(j is not None for j in slot_job)
-            if two_phase and any_live:
+            if two_phase and any(j is not None for j in slot_job):
                 # keep the GPU busy FIRST: the next chunk of the live rows is enqueued before the host prepares the admission, whose
                 # prefill then overlaps that chunk on the side stream
-                enqueue_chunk()
+                in_flight = enqueue_chunk()
                 if free_slots and pending:
                     self.n_refills += min(len(free_slots), len(pending))
                     warm = begin_into(free_slots)
@@ -1502,8 +1481,28 @@ class DecodeEngine:
                 admit_into(free_slots)
             if not any(j is not None for j in slot_job):
                 break
-            enqueue_chunk()
+            in_flight = enqueue_chunk()
         return results
+
+    def _collect(self, u: int, st, cap_j: int):
+        """Slot u's utterance finished, or ran into its cap of cap_j steps, at the poll that read `st`: its (state snapshot, generated
+        int64 [n_steps, K]); the slot's noise stream is put back, its pages are released and the slot is left parked."""
+        n = int(st.n_steps)
+        if st.done and n > cap_j:
+            # the flags are polled every `chunk` steps: an utterance may finish up to chunk - 1 steps past ITS OWN cap before the
+            # poll sees it. The fixed-group path bounded every member by the group's cap; here the bound is per utterance, and a
+            # result longer than its cap is the same failure as not finishing (the caller raises on done != 1).
+            st.done = 2
+        gen = self.tokens(u, n)
+        snap = _lib.SamplerState.from_buffer_copy(bytes(st))
+        if self._feed is not None:
+            self._feed.finish(u, n)
+        if not st.done:                                         # ran into its cap without finishing: park the slot (the caller raises)
+            parked = (_lib.SamplerState * 1)(_lib.SamplerState.from_buffer_copy(bytes(st)))
+            parked[0].done = 1
+            self._write_slot_records([u], sts=parked)
+        self.release_utterance(u)
+        return snap, gen
 
     def time_kernels(self, n_steps: int):
         """Event-timed eager steps: list of (kind, avg_us) per launch slot of one decode step

@@ -547,3 +547,45 @@ def test_run_queue_parks_an_utterance_that_exceeds_its_cap_and_keeps_serving_the
                           u["mask_interval"].cuda(), kvcache=1, aug_text=True, top_k=1, top_p=1.0, temperature=1.0, stop_repetition=2,
                           silence_tokens=[3, 7, 11], cfg_coef=1.5, cfg_stride=2)
         assert one[0].shape[-1] == u["y"].shape[1] + int(st.n_steps) - 4, i          # generated frames = steps - 3 delay columns - 1 eog column
+
+
+def test_sampled_batch1_runs_around_a_sampled_queue_keep_the_generator_contract():
+    """The host-noise pipeline across runs of one model: a sampled batch-1 run cut at 21 steps (chunks of 16 and 5), a sampled queue of
+    three utterances through ONE slot (two refills, the admission staging buffer, the one-slot engine reused where it is large enough),
+    then the first run again. The global generator ends after exactly `steps` per-step draws, each queue result equals its batch-1 run
+    seeded seed + i, and the repeat is bit-equal to the first run, generator state included."""
+    args = W.lm_args_tiny(d_model=128, nhead=2, layers=2, vocab=64)
+    m = _model(args, 71)
+    g = torch.Generator().manual_seed(16)
+    utts = [dict(x=torch.randint(0, 30, (1, L), generator=g), y=torch.randint(0, 64, (1, T, 4), generator=g),
+                 mask_interval=torch.LongTensor([[[T, T]]])) for (L, T) in [(9, 14), (6, 10), (8, 12)]]
+    kw = dict(top_k=12, top_p=0.9, temperature=1.0, stop_repetition=2, silence_tokens=[3, 7, 11], cfg_coef=1.5, cfg_stride=2, aug_text=True)
+    seed = 900
+
+    def one(i, **more):
+        u = utts[i]
+        L = u["x"].shape[1]
+        torch.manual_seed(seed + i)
+        out = m.inference(u["x"].cuda(), torch.LongTensor([L]), u["x"].cuda(), torch.LongTensor([L]), u["y"].cuda(), u["y"].cuda(),
+                          u["mask_interval"].cuda(), kvcache=1, **kw, **more)
+        return out, int(m.last_run["steps"]), torch.get_rng_state()
+
+    def same(a, b):
+        return (a is None and b is None) or (torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) and a[2] == b[2] and a[3] == b[3])
+
+    first, steps, state = one(0, max_new_steps=21)
+    print(f"batch-1 run cut at 21 steps: {steps} steps, finished: {first is not None}")
+    assert 0 < steps <= 21
+    K, card = args.n_codebooks, next(iter(m._engines.values())).a.card
+    torch.manual_seed(seed)
+    torch.randint(0, m.n_text_tokens, (1, utts[0]["x"].shape[1]))
+    for _ in range(steps):
+        torch.empty(K, card).exponential_(1)
+    assert torch.equal(state, torch.get_rng_state())
+
+    batch = m.inference_batch(utts, seed=seed, group=1, **kw)
+    for i in range(3):
+        assert same(batch[i], one(i)[0]), i
+
+    again, steps2, state2 = one(0, max_new_steps=21)
+    assert same(again, first) and steps2 == steps and torch.equal(state2, state)

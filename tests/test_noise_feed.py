@@ -2,12 +2,12 @@
 step in the reference (models/ssr.py:85). It must (a) produce the same numbers as per-step draws, whatever the chunking,
 (b) leave the generator where the reference leaves it after exactly n steps, (c) behave the same for the global generator
 and for a private `torch.Generator` seeded alike (the contract of `inference_batch`: row i == a batch-1 run after
-`torch.manual_seed(seed + i)`)."""
+`torch.manual_seed(seed + i)`). Below: `noise_segments` and the draw half of `NoiseUploader`, through which both decode loops use it."""
 import pytest
 import torch
 
 import ssr_speech_amd  # noqa: F401
-from ssr_speech_amd.engine import TorchCpuNoiseFeed
+from ssr_speech_amd.engine import NoiseUploader, TorchCpuNoiseFeed, noise_segments
 
 K, CARD = 4, 2056
 
@@ -103,3 +103,81 @@ def test_self_check_and_the_per_step_fallback(monkeypatch):
         feed2.draw(0, torch.empty(c, K, CARD))
     feed2.finish(0, 40)
     assert torch.equal(torch.rand(2), ref_next)
+
+
+# ---------------------------------------------------------------- which steps the decode loops draw next: `noise_segments`
+@pytest.mark.parametrize("chunk", [1, 4, 16])
+def test_noise_segments_equal_the_lock_step_loops_rule(chunk):
+    """`iter_chunks` drew steps [total, min(total + chunk, limit)) of every live slot, and nothing once total >= limit; a live slot has
+    drawn exactly the steps enqueued so far."""
+    for limit in range(41):
+        for total in range(0, limit + chunk, chunk):
+            for mask in range(8):
+                live = [u for u in range(3) if mask >> u & 1]
+                drawn = [total if u in live else 5 for u in range(3)]              # what a dead slot has drawn does not matter
+                want = [(u, total, min(total + chunk, limit) - total) for u in live] if total < limit else []
+                assert noise_segments(drawn, live, chunk, limit) == want, (limit, total, live)
+
+
+@pytest.mark.parametrize("max_steps", [16, 21, 48])
+@pytest.mark.parametrize("chunk", [1, 4, 16])
+def test_noise_segments_equal_the_queue_loops_rule(chunk, max_steps):
+    """`iter_queue` drew min(chunk, max_steps - drawn[u]) steps from drawn[u] per slot, skipping a slot with nothing left."""
+    for d0 in range(max_steps + 1):
+        for d1 in range(max_steps + 1):
+            drawn = [d0, 7, d1]
+            want = []
+            for u in (2, 0):
+                n = min(chunk, max_steps - drawn[u])
+                if n > 0:
+                    want.append((u, drawn[u], n))
+            assert noise_segments(drawn, [2, 0], chunk, max_steps) == want, (d0, d1)
+
+
+def test_uploader_draw_half_through_a_reset_and_an_early_finish():
+    """`NoiseUploader.fill` (what `send` does before the copy, here on an unpinned buffer): slot 0 on the global generator runs 11 of a
+    limit of 21 steps and finishes early; slot 1 finishes its first utterance after 6 steps, is reset to another generator mid-run and
+    runs that one for 9. Every segment holds per-step [K, card] draws and every generator ends after exactly n_taken of them."""
+    k, card, chunk, limit = 2, 8, 4, 21
+    step = lambda n, g: torch.stack([torch.empty(k, card).exponential_(1, generator=g) for _ in range(n)])
+    taken = {"global": 11, "a": 6, "b": 9}
+    torch.manual_seed(77)
+    want = {"global": step(24, None)}
+    torch.manual_seed(77)
+    step(taken["global"], None)
+    want_state = {"global": torch.get_rng_state()}
+    for name, seed in (("a", 5), ("b", 6)):
+        want[name] = step(24, torch.Generator().manual_seed(seed))
+        ref = torch.Generator().manual_seed(seed)
+        step(taken[name], ref)
+        want_state[name] = ref.get_state()
+
+    gens = {"a": torch.Generator().manual_seed(5), "b": torch.Generator().manual_seed(6)}
+    torch.manual_seed(77)
+    feed = TorchCpuNoiseFeed([None, gens["a"]], k, card)
+    bufs = [torch.full((2, chunk, k, card), -1.0) for _ in range(3)]
+    owner = ["global", "a"]
+
+    def fill(buf_i, slots):
+        segs = NoiseUploader.fill(feed, bufs[buf_i], slots, chunk, limit)
+        for u, off, n in segs:
+            assert torch.equal(bufs[buf_i][u, :n], want[owner[u]][off:off + n]), (owner[u], off, n)
+        return segs
+
+    assert fill(2, [0, 1]) == [(0, 0, 4), (1, 0, 4)]                   # the admission buffer, then the ring
+    assert fill(0, [0, 1]) == [(0, 4, 4), (1, 4, 4)]
+    assert fill(1, [0, 1]) == [(0, 8, 4), (1, 8, 4)]                   # drawn ahead of slot 1's stop at 6
+    feed.finish(1, taken["a"])
+    assert torch.equal(gens["a"].get_state(), want_state["a"])
+    feed.reset_slot(1, gens["b"])
+    owner[1] = "b"
+    assert fill(2, [1]) == [(1, 0, 4)]
+    assert fill(0, [0, 1]) == [(0, 12, 4), (1, 4, 4)]
+    assert fill(1, [0, 1]) == [(0, 16, 4), (1, 8, 4)]
+    assert fill(0, [0, 1]) == [(0, 20, 1), (1, 12, 4)]                 # slot 0 is cut at the limit
+    assert fill(1, [0, 1]) == [(1, 16, 4)]                             # ... and left out beyond it
+    feed.finish(0, taken["global"])
+    feed.finish(1, taken["b"])
+    assert torch.equal(torch.get_rng_state(), want_state["global"])
+    assert torch.equal(gens["b"].get_state(), want_state["b"])
+    assert torch.equal(gens["a"].get_state(), want_state["a"])         # untouched by the slot's second utterance
