@@ -71,6 +71,8 @@ __device__ __forceinline__ uint32_t hash32(uint32_t x) {
   return x;
 }
 
+__device__ __forceinline__ int elem_index(int e, int sub, int lane) { return e * 256 + sub * 64 + lane; }   // the logit in slot e of a lane
+
 template <class T>
 __device__ __forceinline__ T suffix_excl(T v, int lane) {   // sum of v over lanes > lane
   T inc = v;
@@ -101,6 +103,49 @@ struct SelShared {
   int overflow;
 };
 
+// This wave's histogram copy, emptied (MODE 0: 256 counts, MODE 1: 256 masses).
+template <int MODE>
+__device__ __forceinline__ void hist_clear(SelShared& sh, int k, int sub, int lane) {
+  unsigned long long* mine64 = sh.hist[k][sub];
+  unsigned* mine32 = reinterpret_cast<unsigned*>(mine64);
+  if (MODE == 0) { for (int j = lane; j < 256; j += 64) mine32[j] = 0u; }
+  else { for (int j = lane; j < 256; j += 64) mine64[j] = 0ull; }
+}
+
+// The scanning wave's work, bins 4*lane .. 4*lane+3: add the WPC copies, take the sum of the bins above each bin (starting from `base`)
+// and locate the bin that holds `limit`. MODE 0: the limit-th largest falls into the bin with above < limit <= above + c. MODE 1: the
+// running mass from the top first exceeds limit in the bin with above <= limit < above + c. Publishes found / bin for the codebook and
+// returns the lane's bin 0..3 (at most one lane's is >= 0; -1: not mine) with `above` = count / mass in the bins above it.
+template <int MODE>
+__device__ __forceinline__ int scan_bins(SelShared& sh, int k, int lane, unsigned long long base, unsigned long long limit,
+                                         unsigned long long& above) {
+  unsigned long long c[4] = {0ull, 0ull, 0ull, 0ull};
+#pragma unroll
+  for (int w = 0; w < WPC; ++w)
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      c[j] += (MODE == 0) ? (unsigned long long)reinterpret_cast<unsigned*>(sh.hist[k][w])[lane * 4 + j] : sh.hist[k][w][lane * 4 + j];
+  const unsigned long long a3 = base + suffix_excl<unsigned long long>(c[0] + c[1] + c[2] + c[3], lane);
+  const unsigned long long a2 = a3 + c[3], a1 = a2 + c[2], a0 = a1 + c[1];
+  int f = -1;
+  above = 0;
+  if (MODE == 0) {
+    if (limit > a3 && limit <= a3 + c[3]) { f = 3; above = a3; }
+    else if (limit > a2 && limit <= a2 + c[2]) { f = 2; above = a2; }
+    else if (limit > a1 && limit <= a1 + c[1]) { f = 1; above = a1; }
+    else if (limit > a0 && limit <= a0 + c[0]) { f = 0; above = a0; }
+  } else {
+    if (a3 <= limit && limit < a3 + c[3]) { f = 3; above = a3; }
+    else if (a2 <= limit && limit < a2 + c[2]) { f = 2; above = a2; }
+    else if (a1 <= limit && limit < a1 + c[1]) { f = 1; above = a1; }
+    else if (a0 <= limit && limit < a0 + c[0]) { f = 0; above = a0; }
+  }
+  const unsigned long long bal = __ballot(f >= 0);
+  if (lane == 0) sh.found[k] = bal ? 1 : 0;
+  if (f >= 0) sh.bin[k] = (unsigned)(lane * 4 + f);          // exactly one lane
+  return f;
+}
+
 // MODE 0: key of the kk-th largest valid key (valid keys != 0).  MODE 1: smallest key t with mass(keys > t) <= lim (0: keep all).
 template <int MODE>
 __device__ __forceinline__ uint32_t radix_select(const uint32_t (&key)[MAXE], const float (&p)[MAXE], unsigned kk, float lim, bool active,
@@ -114,8 +159,7 @@ __device__ __forceinline__ uint32_t radix_select(const uint32_t (&key)[MAXE], co
     const int shift = 24 - 8 * pass;
     unsigned long long* mine64 = sh.hist[k][sub];
     unsigned* mine32 = reinterpret_cast<unsigned*>(mine64);
-    if (MODE == 0) { for (int j = lane; j < 256; j += 64) mine32[j] = 0u; }
-    else { for (int j = lane; j < 256; j += 64) mine64[j] = 0ull; }
+    hist_clear<MODE>(sh, k, sub, lane);
     __syncthreads();
     if (active && !keep_all) {
 #pragma unroll
@@ -128,35 +172,10 @@ __device__ __forceinline__ uint32_t radix_select(const uint32_t (&key)[MAXE], co
       }
     }
     __syncthreads();
-    if (sub == 0 && active && !keep_all) {          // this codebook's scanning wave: bins 4*lane .. 4*lane+3
-      unsigned long long c[4] = {0ull, 0ull, 0ull, 0ull};
-#pragma unroll
-      for (int w = 0; w < WPC; ++w)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          c[j] += (MODE == 0) ? (unsigned long long)reinterpret_cast<unsigned*>(sh.hist[k][w])[lane * 4 + j] : sh.hist[k][w][lane * 4 + j];
-      const unsigned long long base = (MODE == 0) ? 0ull : carry;
-      const unsigned long long a3 = base + suffix_excl<unsigned long long>(c[0] + c[1] + c[2] + c[3], lane);
-      const unsigned long long a2 = a3 + c[3], a1 = a2 + c[2], a0 = a1 + c[1];
-      int f = -1;
-      unsigned long long above = 0;
-      if (MODE == 0) {       // need-th largest falls into the bucket with above < need <= above + c
-        if (carry > a3 && carry <= a3 + c[3]) { f = 3; above = a3; }
-        else if (carry > a2 && carry <= a2 + c[2]) { f = 2; above = a2; }
-        else if (carry > a1 && carry <= a1 + c[1]) { f = 1; above = a1; }
-        else if (carry > a0 && carry <= a0 + c[0]) { f = 0; above = a0; }
-      } else {               // running mass from the top first exceeds lim in the bucket with above <= lim < above + c
-        if (a3 <= limfx && limfx < a3 + c[3]) { f = 3; above = a3; }
-        else if (a2 <= limfx && limfx < a2 + c[2]) { f = 2; above = a2; }
-        else if (a1 <= limfx && limfx < a1 + c[1]) { f = 1; above = a1; }
-        else if (a0 <= limfx && limfx < a0 + c[0]) { f = 0; above = a0; }
-      }
-      const unsigned long long bal = __ballot(f >= 0);
-      if (lane == 0) sh.found[k] = bal ? 1 : 0;
-      if (f >= 0) {          // exactly one lane
-        sh.bin[k] = (unsigned)(lane * 4 + f);
-        sh.carry[k] = (MODE == 0) ? (carry - above) : above;
-      }
+    if (sub == 0 && active && !keep_all) {          // this codebook's scanning wave; the mass above the bucket carries over
+      unsigned long long above;
+      const int f = scan_bins<MODE>(sh, k, lane, (MODE == 0) ? 0ull : carry, (MODE == 0) ? carry : limfx, above);
+      if (f >= 0) sh.carry[k] = (MODE == 0) ? (carry - above) : above;
     }
     __syncthreads();
     if (active && !keep_all) {
@@ -188,8 +207,7 @@ __device__ __forceinline__ uint32_t bin_select(const uint32_t (&key)[MAXE], cons
   const unsigned long long limfx = (unsigned long long)((double)lim * (double)SC);
   unsigned long long* mine64 = sh.hist[k][sub];
   unsigned* mine32 = reinterpret_cast<unsigned*>(mine64);
-  if (MODE == 0) { for (int j = lane; j < 256; j += 64) mine32[j] = 0u; }
-  else { for (int j = lane; j < 256; j += 64) mine64[j] = 0ull; }
+  hist_clear<MODE>(sh, k, sub, lane);
   if (threadIdx.x == 0) sh.overflow = force_radix;
   if (sub == 0 && lane == 0) { sh.ncand[k] = 0; sh.result[k] = 0u; }
   if (MODE == 0) STAMP(9);
@@ -214,35 +232,10 @@ __device__ __forceinline__ uint32_t bin_select(const uint32_t (&key)[MAXE], cons
   }
   __syncthreads();
   if (MODE == 0) STAMP(11);
-  if (sub == 0 && active) {          // scanning wave: bins 4*lane .. 4*lane+3, from the top
-    unsigned long long c[4] = {0ull, 0ull, 0ull, 0ull};
-#pragma unroll
-    for (int w = 0; w < WPC; ++w)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        c[j] += (MODE == 0) ? (unsigned long long)reinterpret_cast<unsigned*>(sh.hist[k][w])[lane * 4 + j] : sh.hist[k][w][lane * 4 + j];
-    const unsigned long long a3 = suffix_excl<unsigned long long>(c[0] + c[1] + c[2] + c[3], lane);
-    const unsigned long long a2 = a3 + c[3], a1 = a2 + c[2], a0 = a1 + c[1];
-    const unsigned long long need = (unsigned long long)kk;
-    int f = -1;
-    unsigned long long above = 0;
-    if (MODE == 0) {
-      if (need > a3 && need <= a3 + c[3]) { f = 3; above = a3; }
-      else if (need > a2 && need <= a2 + c[2]) { f = 2; above = a2; }
-      else if (need > a1 && need <= a1 + c[1]) { f = 1; above = a1; }
-      else if (need > a0 && need <= a0 + c[0]) { f = 0; above = a0; }
-    } else {
-      if (a3 <= limfx && limfx < a3 + c[3]) { f = 3; above = a3; }
-      else if (a2 <= limfx && limfx < a2 + c[2]) { f = 2; above = a2; }
-      else if (a1 <= limfx && limfx < a1 + c[1]) { f = 1; above = a1; }
-      else if (a0 <= limfx && limfx < a0 + c[0]) { f = 0; above = a0; }
-    }
-    const unsigned long long bal = __ballot(f >= 0);
-    if (lane == 0) sh.found[k] = bal ? 1 : 0;
-    if (f >= 0) {
-      sh.bin[k] = (unsigned)(lane * 4 + f);
-      sh.carry[k] = above;             // count / mass in the bins above the selected one
-    }
+  if (sub == 0 && active) {          // scanning wave, from the top
+    unsigned long long above;
+    const int f = scan_bins<MODE>(sh, k, lane, 0ull, (MODE == 0) ? (unsigned long long)kk : limfx, above);
+    if (f >= 0) sh.carry[k] = above;   // count / mass in the bins above the selected one
   }
   __syncthreads();
   if (MODE == 0) STAMP(12);
@@ -300,6 +293,64 @@ __device__ __forceinline__ uint32_t bin_select(const uint32_t (&key)[MAXE], cons
   return (found && !fallback) ? sh.result[k] : 0u;
 }
 
+// bin_select, and radix_select when the workgroup fell back (a value bin with more than MAXC elements, or the test knob).
+template <int MODE>
+__device__ __forceinline__ uint32_t select_threshold(const uint32_t (&key)[MAXE], const float (&p)[MAXE], const float (&l)[MAXE], float lo,
+                                                     float scale, unsigned kk, float lim, bool active, SelShared& sh, int k, int sub, int lane,
+                                                     int force_radix) {
+  bool fallback;
+  uint32_t t = bin_select<MODE>(key, p, l, lo, scale, kk, lim, active, sh, k, sub, lane, force_radix, fallback);
+  if (fallback) t = radix_select<MODE>(key, p, kk, lim, active, sh, k, sub, lane);                 // workgroup-uniform
+  return t;
+}
+
+// ---- one value per wave -> one value per codebook, over an LDS record of one slot per wave: lane 0 of each wave stores its wave-uniform
+// value, barrier, the codebook's threads combine the WPC values, barrier (the record is free for the next combine). All 16 waves call
+// every combine; the waves of codebooks k >= K (!active) only take part in the barriers and keep their value.
+typedef float CbF[SSRHIP_MAX_CODEBOOKS][WPC];
+typedef int CbI[SSRHIP_MAX_CODEBOOKS][WPC];
+
+__device__ __forceinline__ float cb_max(CbF& f, float v, int k, int sub, int lane, bool active) {
+  if (lane == 0 && active) f[k][sub] = v;
+  __syncthreads();
+  if (active) v = fmaxf(fmaxf(f[k][0], f[k][1]), fmaxf(f[k][2], f[k][3]));
+  __syncthreads();
+  return v;
+}
+
+__device__ __forceinline__ void cb_minmax(CbF& f, CbF& g, float& lo, float& hi, int k, int sub, int lane, bool active) {
+  if (lane == 0 && active) { f[k][sub] = lo; g[k][sub] = hi; }
+  __syncthreads();
+  if (active) {
+    lo = fminf(fminf(f[k][0], f[k][1]), fminf(f[k][2], f[k][3]));
+    hi = fmaxf(fmaxf(g[k][0], g[k][1]), fmaxf(g[k][2], g[k][3]));
+  }
+  __syncthreads();
+}
+
+__device__ __forceinline__ float cb_sum(CbF& f, float v, int k, int sub, int lane, bool active) {   // always in this order: the mass is compared as bits
+  if (lane == 0 && active) f[k][sub] = v;
+  __syncthreads();
+  if (active) v = (f[k][0] + f[k][1]) + (f[k][2] + f[k][3]);
+  __syncthreads();
+  return v;
+}
+
+// largest value, lowest index on ties; `reader`: the threads that need the result. RELEASE = false leaves the closing barrier to the caller.
+template <bool RELEASE>
+__device__ __forceinline__ void cb_argmax(CbF& f, CbI& i, float& v, int& idx, int k, int sub, int lane, bool active, bool reader) {
+  if (lane == 0 && active) { f[k][sub] = v; i[k][sub] = idx; }
+  __syncthreads();
+  if (reader) {
+    v = f[k][0];
+    idx = i[k][0];
+#pragma unroll
+    for (int w = 1; w < WPC; ++w)
+      if (f[k][w] > v || (f[k][w] == v && i[k][w] < idx)) { v = f[k][w]; idx = i[k][w]; }
+  }
+  if (RELEASE) __syncthreads();
+}
+
 __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(const ssrhip_sample_args a, const int force_radix) {
   __shared__ SelShared sel;
   __shared__ float sh_f[SSRHIP_MAX_CODEBOOKS][WPC];
@@ -355,14 +406,14 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(const ssrhip_sam
   float l[MAXE], lun[MAXE];
 #pragma unroll
   for (int e = 0; e < MAXE; ++e) {
-    const int i = e * 256 + sub * 64 + lane;
+    const int i = elem_index(e, sub, lane);
     const int ic = (i < card) ? i : 0;
     l[e] = lc[ic];
     lun[e] = guided ? lu[ic] : 0.f;
   }
 #pragma unroll
   for (int e = 0; e < MAXE; ++e) {
-    const int i = e * 256 + sub * 64 + lane;
+    const int i = elem_index(e, sub, lane);
     float v = guided ? __fadd_rn(__fmul_rn(c_coef, l[e]), __fmul_rn(c_om, lun[e])) : l[e];
     const bool special = (i == c_eos) | (i == c_sos) | ((i >= c_mts) & (i < c_mts_end));
     v = special ? -10000.f : v;
@@ -376,7 +427,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(const ssrhip_sam
     float* dbg = a.dbg_logits + ((size_t)u * K + k) * card;
 #pragma unroll
     for (int e = 0; e < MAXE; ++e) {
-      const int i = e * 256 + sub * 64 + lane;
+      const int i = elem_index(e, sub, lane);
       if (i < card) dbg[i] = l[e];
     }
   }
@@ -388,20 +439,9 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(const ssrhip_sam
   mx = wave_max(mx);
   int am = 0x7fffffff;
 #pragma unroll
-  for (int e = 0; e < MAXE; ++e) if (l[e] == mx) am = min(am, e * 256 + sub * 64 + lane);
+  for (int e = 0; e < MAXE; ++e) if (l[e] == mx) am = min(am, elem_index(e, sub, lane));
   am = wave_min_i(am);
-  if (lane == 0 && active) { sh_f[k][sub] = mx; sh_i[k][sub] = am; }
-  __syncthreads();
-  if (active) {
-    float m2 = sh_f[k][0];
-    int a2 = sh_i[k][0];
-#pragma unroll
-    for (int w = 1; w < WPC; ++w)
-      if (sh_f[k][w] > m2 || (sh_f[k][w] == m2 && sh_i[k][w] < a2)) { m2 = sh_f[k][w]; a2 = sh_i[k][w]; }
-    mx = m2;
-    am = a2;
-  }
-  __syncthreads();
+  cb_argmax<true>(sh_f, sh_i, mx, am, k, sub, lane, active, active);
   // ---- temperature (:80-81): true division, like the reference
   if (c_temp != 1.0f) {
 #pragma unroll
@@ -409,15 +449,12 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(const ssrhip_sam
     float m3 = -INFINITY;
 #pragma unroll
     for (int e = 0; e < MAXE; ++e) m3 = fmaxf(m3, l[e]);
-    m3 = wave_max(m3);
-    if (lane == 0 && active) sh_f[k][sub] = m3;
-    __syncthreads();
-    if (active) mx = fmaxf(fmaxf(sh_f[k][0], sh_f[k][1]), fmaxf(sh_f[k][2], sh_f[k][3]));
-    __syncthreads();
+    m3 = cb_max(sh_f, wave_max(m3), k, sub, lane, active);
+    if (active) mx = m3;
   }
   uint32_t key[MAXE];
 #pragma unroll
-  for (int e = 0; e < MAXE; ++e) key[e] = (active && (e * 256 + sub * 64 + lane) < card) ? okey(l[e]) : 0u;   // 0 = padding
+  for (int e = 0; e < MAXE; ++e) key[e] = (active && elem_index(e, sub, lane) < card) ? okey(l[e]) : 0u;   // 0 = padding
   const uint32_t kmax = okey(mx);
   // range of the ordinary logits of this codebook (for bin_select's value bins)
   float vlo = INFINITY, vhi = -INFINITY;
@@ -429,13 +466,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(const ssrhip_sam
   }
   vlo = -wave_max(-vlo);
   vhi = wave_max(vhi);
-  if (lane == 0 && active) { sh_f[k][sub] = vlo; sh_g[k][sub] = vhi; }
-  __syncthreads();
-  if (active) {
-    vlo = fminf(fminf(sh_f[k][0], sh_f[k][1]), fminf(sh_f[k][2], sh_f[k][3]));
-    vhi = fmaxf(fmaxf(sh_g[k][0], sh_g[k][1]), fmaxf(sh_g[k][2], sh_g[k][3]));
-  }
-  __syncthreads();
+  cb_minmax(sh_f, sh_g, vlo, vhi, k, sub, lane, active);
   const float vscale = (vhi > vlo) ? 253.0f / (vhi - vlo) : 0.f;
   float p[MAXE];
 #pragma unroll
@@ -446,11 +477,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(const ssrhip_sam
   if (c_topk > 0) {   // uniform
     const int kk = min(max(c_topk, 1), card);
     if (kk == 1) thr = kmax;
-    else if (kk < card) {
-      bool fb;
-      thr = bin_select<0>(key, p, l, vlo, vscale, (unsigned)kk, 0.f, active, sel, kc, sub, lane, force_radix, fb);
-      if (fb) thr = radix_select<0>(key, p, (unsigned)kk, 0.f, active, sel, kc, sub, lane);          // workgroup-uniform
-    }
+    else if (kk < card) thr = select_threshold<0>(key, p, l, vlo, vscale, (unsigned)kk, 0.f, active, sel, kc, sub, lane, force_radix);
   }
   STAMP(3);
   // ---- softmax numerators over the kept set, then top-p (:46-67)
@@ -460,15 +487,9 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(const ssrhip_sam
     p[e] = (key[e] != 0u && key[e] >= thr) ? __expf(l[e] - mx) : 0.f;
     Z += p[e];
   }
-  Z = wave_sum(Z);
-  if (lane == 0 && active) sh_f[k][sub] = Z;
-  __syncthreads();
-  if (active) Z = (sh_f[k][0] + sh_f[k][1]) + (sh_f[k][2] + sh_f[k][3]);
-  __syncthreads();
+  Z = cb_sum(sh_f, wave_sum(Z), k, sub, lane, active);
   if (c_topp < 1.0f) {   // uniform
-    bool fb;
-    uint32_t tp = bin_select<1>(key, p, l, vlo, vscale, 0u, c_topp * Z, active, sel, kc, sub, lane, force_radix, fb);
-    if (fb) tp = radix_select<1>(key, p, 0u, c_topp * Z, active, sel, kc, sub, lane);                // workgroup-uniform
+    const uint32_t tp = select_threshold<1>(key, p, l, vlo, vscale, 0u, c_topp * Z, active, sel, kc, sub, lane, force_radix);
     if (tp > thr) {
       thr = tp;
 #pragma unroll
@@ -485,7 +506,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(const ssrhip_sam
     int bi = 0x7fffffff;
 #pragma unroll
     for (int e = 0; e < MAXE; ++e) {
-      const int i = e * 256 + sub * 64 + lane;
+      const int i = elem_index(e, sub, lane);
       float q;
       if (nz) q = nz[(key[e] != 0u) ? i : 0];                       // wave-uniform branch
       else {
@@ -497,18 +518,13 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(const ssrhip_sam
       best = better ? sc : best;
       bi = better ? i : bi;
     }
-    const float wb = wave_max(best);
+    float wb = wave_max(best);
     bi = (best == wb) ? bi : 0x7fffffff;
     bi = wave_min_i(bi);
-    if (lane == 0 && active) { sh_f[k][sub] = wb; sh_i[k][sub] = bi; }
-    __syncthreads();
-    if (active && sub == 0 && lane == 0) {
-      float b2 = sh_f[k][0];
-      int i2 = sh_i[k][0];
-#pragma unroll
-      for (int w = 1; w < WPC; ++w)
-        if (sh_f[k][w] > b2 || (sh_f[k][w] == b2 && sh_i[k][w] < i2)) { b2 = sh_f[k][w]; i2 = sh_i[k][w]; }
-      sh_sample[k] = i2;
+    const bool first = active && sub == 0 && lane == 0;              // one thread per codebook hands the draw to the state machine
+    cb_argmax<false>(sh_f, sh_i, wb, bi, k, sub, lane, active, first);   // the barrier behind STAMP(5) frees the record
+    if (first) {
+      sh_sample[k] = bi;
       if (k == 0) sh_argmax0 = am;
     }
   }

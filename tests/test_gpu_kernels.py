@@ -1249,6 +1249,150 @@ def test_sampler_filter_golden(L, golden_dir):
                     assert got[3, row] == want[row], (k, p, trial, row)
 
 
+SENTINEL = -77
+
+
+def _sampler_steps(L, args, knobs, logits_seq, noise, *, text_len, audio_pos0, max_steps, embed=None, preset_done=()):
+    """ssrhip_sample on len(knobs) utterances with CFG (two rows each), one launch per entry of logits_seq ([2 n_utt, K, card] each);
+    noise is [n_utt, max_steps, K, card]. embed = (D, out_tiled, audio_emb [K, card, D], pe): the fused embedding writes x, and after every
+    step a separate ssrhip_embed launch embeds the next_tok / next_pos the sampler left (rows of utterances in preset_done, which hold the
+    sentinel, are fed token 0 / position 0 there) into x_ref. Every output buffer starts filled with SENTINEL, kv_pos with values of its
+    own. Returns one dict of host copies per step: generated, state (bytes), next_tok, next_pos, kv_pos, row_len, dbg, x, x_ref."""
+    K, n_utt = args.n_codebooks, len(knobs)
+    card = args.audio_vocab_size + args.n_special + args.max_n_spans
+    B = 2 * n_utt
+    cfgs, sts = (_lib.SamplerCfg * n_utt)(), (_lib.SamplerState * n_utt)()
+    for u, kn in enumerate(knobs):
+        c, st = cfgs[u], sts[u]
+        c.top_k, c.top_p, c.temperature, c.stop_repetition = kn["top_k"], kn["top_p"], kn["temperature"], kn["stop_repetition"]
+        c.cfg_coef, c.cfg_one_minus, c.cfg_stride, c.use_cfg = kn["cfg_coef"], 1 - kn["cfg_coef"], kn["cfg_stride"], 1
+        c.n_silence = len(kn["silence_tokens"])
+        for i, t in enumerate(kn["silence_tokens"]):
+            c.silence[i] = t
+        c.text_len, c.n_spans, c.max_steps, c.use_noise = text_len, 1, max_steps, 1
+        c.empty_token, c.eog, c.eos, c.sos, c.mts, c.max_n_spans = args.empty_token, args.eog, args.eos, args.sos, args.mts, args.max_n_spans
+        st.num_cfg_tag, st.prev_token, st.audio_pos, st.done = 1, -1, audio_pos0, int(u in preset_done)
+        for i in range(3):
+            st.span_end[i] = st.pad[i] = SENTINEL
+    dcfg = torch.frombuffer(bytearray(bytes(cfgs)), dtype=torch.uint8).cuda()
+    dst = torch.frombuffer(bytearray(bytes(sts)), dtype=torch.uint8).cuda()
+    dnoise = dev(noise)
+    full = lambda *shape, dtype=torch.int32: torch.full(shape, SENTINEL, dtype=dtype, device="cuda")
+    gen, next_tok, next_pos, row_len = full(n_utt, max_steps, K), full(B, 4), full(B), full(B)
+    kv_pos = torch.arange(5, 5 + B, dtype=torch.int32, device="cuda")
+    dbg = full(n_utt, K, card, dtype=torch.float32)
+    a = _lib.SampleArgs()
+    a.n_utt, a.K, a.card, a.cfg, a.state, a.noise = n_utt, K, card, dcfg.data_ptr(), dst.data_ptr(), dnoise.data_ptr()
+    a.generated, a.next_tok, a.next_pos, a.kv_pos, a.row_len, a.dbg_logits = gen.data_ptr(), next_tok.data_ptr(), next_pos.data_ptr(), kv_pos.data_ptr(), row_len.data_ptr(), dbg.data_ptr()
+    x = x_ref = None
+    if embed is not None:
+        D, out_tiled, audio_emb, pe = embed
+        dae, dpe = dev(audio_emb), dev(pe)
+        x, x_ref = full(16, D, dtype=torch.float32), full(16, D, dtype=torch.float32)
+        e = a.embed
+        e.audio_emb, e.pe, e.alpha_audio, e.R, e.D, e.K, e.card, e.out, e.out_tiled = dae.data_ptr(), dpe.data_ptr(), 0.7, B, D, K, card, x.data_ptr(), out_tiled
+        dead = torch.tensor([r // 2 in preset_done for r in range(B)], device="cuda")
+    out = []
+    for lg in logits_seq:
+        dl = dev(lg)
+        a.logits = dl.data_ptr()
+        _lib.check(L.ssrhip_sample(C.byref(a), _lib.stream_ptr()))
+        sync()
+        if embed is not None:
+            tok = torch.where(dead[:, None], torch.zeros_like(next_tok), next_tok).contiguous()
+            pos = torch.where(dead, torch.zeros_like(next_pos), next_pos).contiguous()
+            e2 = _lib.EmbedArgs()
+            e2.audio_emb, e2.pe, e2.alpha_audio, e2.R, e2.D, e2.K, e2.card, e2.out_tiled = dae.data_ptr(), dpe.data_ptr(), 0.7, B, D, K, card, out_tiled
+            e2.tok, e2.pos, e2.out = tok.data_ptr(), pos.data_ptr(), x_ref.data_ptr()
+            _lib.check(L.ssrhip_embed(C.byref(e2), _lib.stream_ptr()))
+            sync()
+        out.append(dict(generated=gen.cpu(), state=dst.cpu().numpy().tobytes(), next_tok=next_tok.cpu(), next_pos=next_pos.cpu(), kv_pos=kv_pos.cpu(),
+                        row_len=row_len.cpu(), dbg=dbg.cpu(), x=None if x is None else x.cpu(), x_ref=None if x is None else x_ref.cpu()))
+    return out
+
+
+_FUSED_KNOBS = [dict(top_k=1, top_p=1.0, temperature=1.0), dict(top_k=12, top_p=0.8, temperature=1.0), dict(top_k=0, top_p=0.7, temperature=2.0)]
+_FUSED_SCRIPTS = {}
+
+
+def _fused_embed_script(card, D, S=8):
+    """Scripted logits / noise of three utterances as in test_sampler_state_machine_matches_oracle, embedding tables, and the oracle's
+    tokens of every utterance run alone. Made once per shape and shared (read-only) by the cases below."""
+    if (card, D) in _FUSED_SCRIPTS:
+        return _FUSED_SCRIPTS[card, D]
+    args = W.lm_args_tiny() if card == 72 else W.lm_args_830m()
+    K = args.n_codebooks
+    assert card == args.audio_vocab_size + args.n_special + args.max_n_spans
+    sil = [3, 7, 11] if card == 72 else [1388, 1898, 131]
+    knobs = [dict(kn, stop_repetition=2, silence_tokens=sil, cfg_coef=1.5, cfg_stride=3) for kn in _FUSED_KNOBS]
+    g = torch.Generator().manual_seed(card)
+    text_len, audio_pos0, max_steps = 100, 8, S + 4            # no stop rule and no step cap inside the S steps: every step is live
+    logits = torch.randn(S, len(knobs), 2, K, 1, card, generator=g) * 2.0
+    logits[..., args.eog] -= 30.0                               # keep the scripted run going
+    noise = torch.empty(len(knobs), max_steps, K, card).exponential_(1, generator=g)
+    audio_emb = torch.randn(K, card, D, generator=g)
+    pe = torch.randn(audio_pos0 + S + 2, D, generator=g)
+    ref = []
+    for u, kn in enumerate(knobs):
+        st, toks = O.SpanState(), []
+        for s in range(S):
+            smp = O.step_logits_to_samples(logits[s, u].clone(), st, args, audio_pos0 + s + 1, text_len, aug_text=True, noise=noise[u, s], **kn)
+            toks.append(smp.squeeze(-1).clone())
+        assert st.num_eog == 0
+        ref.append(torch.stack(toks).int())
+    seq = [logits[s].squeeze(3).reshape(2 * len(knobs), K, card) for s in range(S)]
+    _FUSED_SCRIPTS[card, D] = (args, knobs, seq, noise, audio_emb, pe, ref, text_len, audio_pos0, max_steps)
+    return _FUSED_SCRIPTS[card, D]
+
+
+def _embed_row(buf, r, D, out_tiled):
+    """Row r of a [16, D] activation buffer as a view (SSRHIP_TILED: feature k of row b at ((k / 4) * 16 + b) * 4 + k % 4)."""
+    return buf.view(D // 4, 16, 4)[:, r, :] if out_tiled else buf[r]
+
+
+# card 72 leaves one element slot of a lane partly filled and the others empty, card 2056 = 8 * 256 + 8 fills all nine, the last partly:
+# the smallest sizes that reach both ends of the kernel's per-lane loops
+@pytest.mark.parametrize("preset_done", [False, True])
+@pytest.mark.parametrize("out_tiled", [0, 1])
+@pytest.mark.parametrize("card,D", [(72, 128), (2056, 2048)])
+def test_sampler_fused_embed_equals_embed_launch(L, card, D, out_tiled, preset_done):
+    """The hand-off at the sampler's tail, state -> next tokens -> embed_row: three utterances with CFG (six rows), each with knobs of its
+    own, eight steps. Per utterance the tokens are the oracle's run of that utterance alone; after each step the fused x rows equal, bit
+    for bit, what a separate ssrhip_embed launch writes from the next_tok / next_pos the sampler left; kv_pos / row_len advance by one per
+    live row. preset_done: utterance 1 starts with state.done = 1 and nothing of it may be touched."""
+    args, knobs, seq, noise, audio_emb, pe, ref, text_len, audio_pos0, max_steps = _fused_embed_script(card, D)
+    K, S, n_utt = args.n_codebooks, len(seq), len(knobs)
+    done = (1,) if preset_done else ()
+    steps = _sampler_steps(L, args, knobs, seq, noise, text_len=text_len, audio_pos0=audio_pos0, max_steps=max_steps,
+                           embed=(D, out_tiled, audio_emb, pe), preset_done=done)
+    for s, o in enumerate(steps):
+        states = (_lib.SamplerState * n_utt).from_buffer_copy(o["state"])
+        for u in range(n_utt):
+            st, rows = states[u], (2 * u, 2 * u + 1)
+            assert list(st.span_end) == [SENTINEL] * 3 and list(st.pad) == [SENTINEL] * 3
+            if u in done:
+                assert (st.done, st.n_steps, st.audio_pos, st.num_gen, st.num_cfg_tag, st.prev_token) == (1, 0, audio_pos0, 0, 1, -1)
+                assert (o["generated"][u] == SENTINEL).all() and (o["dbg"][u] == SENTINEL).all()
+                for r in rows:
+                    assert (o["next_tok"][r] == SENTINEL).all() and o["next_pos"][r] == SENTINEL and o["row_len"][r] == SENTINEL
+                    assert o["kv_pos"][r] == 5 + r
+                    assert (_embed_row(o["x"], r, D, out_tiled) == SENTINEL).all()
+                continue
+            assert (st.done, st.n_steps, st.audio_pos, st.span) == (0, s + 1, audio_pos0 + s + 1, 0)
+            assert torch.equal(o["generated"][u, : s + 1], ref[u][: s + 1]), (u, s)
+            assert (o["generated"][u, s + 1:] == SENTINEL).all()
+            for r in rows:
+                assert o["next_tok"][r].tolist() == ref[u][s].tolist() + [0] * (4 - K) and o["next_pos"][r] == audio_pos0 + s + 1
+                assert o["kv_pos"][r] == 5 + r + s + 1 and o["row_len"][r] == 5 + r + s + 2
+                got, want = _embed_row(o["x"], r, D, out_tiled), _embed_row(o["x_ref"], r, D, out_tiled)
+                assert torch.equal(got.contiguous().view(torch.int32), want.contiguous().view(torch.int32)), (u, s, r)
+        live = [r for r in range(2 * n_utt) if r // 2 not in done]
+        mask = torch.ones(16, D, dtype=torch.bool)                  # nothing outside the live rows is written
+        for r in live:
+            _embed_row(mask, r, D, out_tiled)[:] = False
+        assert (o["x"][mask] == SENTINEL).all()
+
+
 def test_gemm_split_result_of_an_item_does_not_depend_on_the_batch(L):
     """The split GEMM picks 64- or 128-row tiles by the size of the grid (i.e. by the batch); per output element both do the same
     arithmetic, so item 0 of a batch of 12 (128-row tiles) must be BIT-identical to the same item computed alone (64-row tiles)."""
