@@ -278,6 +278,33 @@ def stream_window(c0: int, c1: int, n: int, margins: Tuple[int, int]) -> Tuple[i
     return max(0, c0 - margins[0]), min(n, c1 + margins[1])
 
 
+def skip_stream_margins(cfg: CodecConfig) -> Tuple[int, int]:
+    """(left, right) margin, in frames, a window of the watermark decoder's skip-encoder CHAIN — its first convolution, then per ratio a
+    residual block and a strided convolution, up to and including the last strided one (seanet.py:113-150) — needs so that its three
+    high-rate taps and its frame-rate rows are computed from true samples only: the receptive field walked from the frame-rate rows back
+    to the samples, as `stream_margins` walks the decoder's. (L, R) = rows of context a layer's outputs need on either side; a strided
+    convolution (kernel 2s, paddings (pl, pr)) maps output o to the inputs [o s - pl, o s + s + pr), so its input needs L s + pl rows in
+    front and R s + pr behind; a stride-1 convolution adds its paddings. A tap's own field lies inside that of the rows behind it."""
+    L = R = 0
+    for s in cfg.ratios:                                             # the encoder applies reversed(ratios): walked backwards
+        pl, pr = _conv_pads(2 * s, s)
+        L, R = L * s + pl, R * s + pr
+        for _ in range(cfg.n_residual_layers):
+            for k in (1, cfg.residual_kernel_size):
+                pl, pr = _conv_pads(k, 1)
+                L, R = L + pl, R + pr
+    pl, pr = _conv_pads(cfg.kernel_size, 1)
+    hop = int(math.prod(cfg.ratios))
+    return -(-(L + pl) // hop), -(-(R + pr) // hop)
+
+
+def wm_stream_holdback(cfg: CodecConfig) -> int:
+    """Frames that must exist behind a frame before its watermarked samples are final (`WMDecodeStream`): the skip-encoder chain's right
+    margin, the look-ahead of the skip encoder's last convolution (behind its LSTM), the look-ahead of the decoder's first convolution,
+    and the right margin of the layers behind the decoder's LSTM. The two forward-only LSTMs add nothing."""
+    return skip_stream_margins(cfg)[1] + _conv_pads(cfg.last_kernel_size, 1)[1] + stream_lookahead(cfg) + stream_margins(cfg)[1]
+
+
 # the three truth rules of the switches below (kept apart: "" counts as on for the first, as off for the second)
 _not0 = lambda v: v != "0"                                             # noqa: E731
 _on = lambda v: v not in ("", "0")                                     # noqa: E731
@@ -833,6 +860,14 @@ class WMEncodecModel:
         within the bound that holds a batched decode to the batch-1 one. Every buffer is allocated here (`BatchDecodeStream`)."""
         return BatchDecodeStream(self, [int(p) for p in prompt_lens], int(max_new_frames), int(max_window))
 
+    def wmdecode_stream(self, max_frames: int, max_window: int = 16) -> "WMDecodeStream":
+        """`wmdecode(..., with_mark=False)` of ONE utterance in pieces, while its frames are still being generated:
+        `push(codes [1, K, n], labels [n], audio [1, 1, n * hop] | None)` returns the watermarked samples that have become final,
+        `finish()` the rest; their concatenation is bit-identical to `wmdecode` of all the inputs. Every buffer is allocated here, for up
+        to `max_frames` frames (create the stream before the decode engine's first launch); `max_window` = frames of one pass over the
+        skip encoder's convolutions, and of one pass over the decoder's layers behind its LSTM."""
+        return WMDecodeStream(self, int(max_frames), int(max_window))
+
     # ------------------------------------------------------------------ ragged batches (items of different lengths in one pass)
     # cost model of one dense pass over a bucket, in microseconds per frame of its longest item: every frame is one LSTM time step
     # of each layer (a latency-bound launch whose cost hardly depends on the batch) + the convolutions' share per item
@@ -1042,8 +1077,9 @@ class _StreamCore:
     (`DecodeStream`: frame t is row t; `BatchDecodeStream`: `batch_align_plan`). The one thing it has to be told is `conv_row0`, the first
     row the convolution computes: the convolution's row r reads the rows [r - conv_row0, r - conv_row0 + pl0 + pr0] of `z.data`."""
 
-    def __init__(self, model: WMEncodecModel, entry: str, max_window: int):
-        cfg, nodes = model.cfg, model.decoder.nodes
+    def __init__(self, model: WMEncodecModel, entry: str, max_window: int, nodes: Optional[List[tuple]] = None):
+        """`nodes`: the decoder to stream (`WMDecodeStream`: the watermark decoder's); None = `model.decoder`'s."""
+        cfg, nodes = model.cfg, (model.decoder.nodes if nodes is None else nodes)
         self.m, self.max_window = model, max_window
         self.hop = int(math.prod(cfg.ratios))
         self.conv0: _Conv = nodes[0][2]
@@ -1258,6 +1294,229 @@ class DecodeStream(_StreamCore):
         if self.n_pushed:
             self._stage1(True)
             self._stage2(True)
+        return self._out(a)
+
+
+# ----------------------------------------------------------------------------- streamed watermarked decode (DESIGN.md Part I.17)
+class WMDecodeStream(DecodeStream):
+    """`WMEncodecModel.wmdecode_stream`: `_wmdecode_dense` of one utterance (B = 1, no detector pass), advanced as its frames arrive.
+    Frame t is row t of every frame-rate buffer. Per `push`, in this order, each stage as far as its input allows:
+
+      track   the kept-audio samples of the new frames, copied into a zero-filled [max_frames * hop] buffer (None = silence);
+      chain   the skip encoder's convolutions up to its last strided one, over windows of the track with `skip_stream_margins` on either
+              side (an end of the utterance is a true edge): the cores of the three high-rate taps go into whole-utterance buffers —
+              STORED, not recomputed per decoder window — and the frame-rate rows into `p`;
+      LSTM    the skip encoder's, as continuation calls over the new rows of `p` (`ssrhip_lstm_layer`, t_begin > 0) into `u`;
+      tap 4   the skip encoder's last convolution over the rows of `u` whose look-ahead has arrived;
+      z       wm_proj0(ELU(tap 4), label) + dequantised codes — `_concat_proj(0, ...)`'s GEMM over those rows, into the decoder's input;
+      stage 1 the decoder's first convolution and LSTM (`_stage1_rows`);
+      stage 2 windows of the layers behind it (`batch_window_item`), `_concat_proj(j)` behind each of the first three transposed
+              convolutions with the label and tap pointers at the window's first row.
+
+    So a frame's samples leave once `wm_stream_holdback` further frames exist. With reflect padding a frame-rate convolution whose input
+    is not yet longer than its padding waits (the padding of so short an input depends on its length). Every launch is the one
+    `wmdecode` issues for the same layer, over fewer rows, on the caller's stream; everything is allocated here."""
+
+    def __init__(self, model: WMEncodecModel, max_frames: int, max_window: int):
+        if max_frames < 1 or max_window < 1:
+            raise ValueError("wmdecode_stream needs max_frames >= 1 and max_window >= 1")
+        if not model.has_wm:
+            raise ValueError("wmdecode_stream: this codec has no watermark decoder")
+        cfg, dev = model.cfg, model.device
+        r = list(cfg.ratios)
+        senc, dec = model.skip_encoder, model.wmdecoder
+        rest = senc.slice_nodes(11, None)
+        if len(r) != 4 or [n[1] for n in rest] != ["conv", "lstm", "conv"] or [n[1] for n in dec.nodes[:3]] != ["conv", "lstm", "convtr"]:
+            raise NotImplementedError("wmdecode_stream: the watermark decoder's slicing (seanet.py:560-591) is written for 4 ratios and an LSTM")
+        _StreamCore.__init__(self, model, "wmdecode_stream", max_window, nodes=dec.nodes)       # (not DecodeStream's: other buffers)
+        # the skip encoder, cut as `_wmdecode_dense` cuts it; its last slice once more, around the LSTM
+        self.ch_head = senc.slice_nodes(0, 2)
+        self.ch_cuts = [senc.slice_nodes(lo, hi) for lo, hi in ((2, 5), (5, 8), (8, 11))]
+        self.ch_last, self.sk_lstm_node, self.sk_conv = rest[0], rest[1], rest[2][2]
+        self.sk_lstm: _Lstm = rest[1][2]
+        c = self.sk_conv
+        if not (c.s == 1 and c.Cin == self.sk_lstm.C and c.Cout > 4):
+            raise NotImplementedError("wmdecode_stream: the skip encoder does not end with a stride-1 convolution behind its LSTM")
+        self.smargins = skip_stream_margins(cfg)
+        self.holdback = wm_stream_holdback(cfg)
+        self.reps = [r[0] * r[1] * r[2], r[0] * r[1], r[0]]          # rows per frame of the taps, in the chain's order
+        # the decoder behind its LSTM, cut where the taps enter: [convtr] | [res, convtr] | [res, convtr] | [res, convtr, res, conv]
+        dn = [dec.slice_nodes(lo, hi) for lo, hi in ((0, 4), (4, 7), (7, 10), (10, None))]
+        self.dn = [dn[0][2:]] + dn[1:]
+        assert [n for part in self.dn for n in part] == list(self.tail)
+        self.cap = cap = max_frames
+        hop, D, Cs = self.hop, cfg.dimension, self.sk_lstm.C
+        f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
+        self.codes = torch.zeros(cfg.n_q * cap, **i32)
+        self.lab = torch.zeros(1, cap, **i32)
+        self.lohi = torch.zeros(4, **i32)
+        self.track = torch.zeros(cap * hop, **f32)
+        self.q = torch.zeros(cap, D, **f32)                           # the dequantised codes
+        self.taps = [torch.zeros(1, cap * rep, part[-1][2][1].Cout, **f32) for part, rep in zip(self.ch_cuts, self.reps)]
+        self.p = torch.zeros(1, cap, Cs, **f32)                       # the chain's frame-rate rows: what the skip encoder's LSTM reads
+        nl = len(self.sk_lstm.layers)
+        self.sk_gins = [torch.zeros(1, cap, 4 * Cs, **f32) for _ in range(nl)]
+        self.sk_hbufs = [torch.zeros(2, 16, Cs, **f32) for _ in range(nl)]
+        self.sk_cbufs = [torch.zeros(1, Cs, **f32) for _ in range(nl)]
+        self.sk_mids = [torch.zeros(1, cap, Cs, **f32) for _ in range(nl - 1)]
+        split = model._lstm_use_split(self.sk_lstm, 1)
+        self.sk_hsplits = [torch.zeros(2 * 64 * Cs * 3, dtype=torch.int16, device=dev) if (split and self.sk_lstm.split[l] is not None) else None
+                           for l in range(nl)]
+        self.u = TM(1, cap, Cs, c.pl, c.pr, dev, data=torch.zeros(1, c.pl + cap + c.pr, Cs, **f32))     # LSTM + skip: what `sk_conv` reads
+        self.u.elu = bool(model.elu_on_store and c.act_in)
+        self.tap4 = torch.zeros(1, cap, c.Cout, **f32)
+        self.n_pushed = 0          # frames that have arrived
+        self.nA = 0                # frames the chain and the skip encoder's LSTM have reached
+        self.nC = 0                # frames whose tap 4 and decoder input `z` are final
+        self.n2 = 0
+        self.emit_from: Optional[int] = None
+        self.finished = False
+        # the chain's window buffers by a dry pass over its largest window; those of stage 2 likewise, in `_allocate`
+        self.pool_c = _WindowPool()
+        self.tap_elu = [False] * 3
+        real, model.lib = model.lib, _NoLaunch()
+        try:
+            taps, _ = self._chain_pass(0, min(cap, max_window + self.smargins[0] + self.smargins[1]))
+            self.tap_elu = [t.elu for t in taps]
+            self.pool_c.frozen = True
+        finally:
+            model.lib = real
+        self._allocate(1, cap, 0, cap)
+
+    # ------------------------------------------------------------------ the skip encoder
+    def _chain_pass(self, lo: int, hi: int) -> Tuple[List[TM], TM]:
+        """The skip encoder's convolutions over the track's frames [lo, hi), as `_wmdecode_dense` runs them over a waveform of that
+        length -> (the three taps, the frame-rate rows in front of the LSTM), in the chain pool's buffers."""
+        m, hop = self.m, self.hop
+        with m._stream_pass(self.pool_c, False):
+            x = m._input_tm(self.track[lo * hop: hi * hop].view(1, 1, -1), self.ch_head[0])
+            z = m._run(self.ch_head, x, after=self.ch_cuts[0][0])
+            taps = []
+            for i, part in enumerate(self.ch_cuts):
+                z = m._run(part, z, after=(self.ch_cuts[i + 1][0] if i + 1 < len(self.ch_cuts) else self.ch_last))
+                taps.append(z)
+            return taps, m._run([self.ch_last], z, after=self.sk_lstm_node)
+
+    def _chain(self, final: bool):
+        """Chain windows over the frames whose right margin has arrived, then the skip encoder's LSTM over the new rows."""
+        m, n, a = self.m, self.n_pushed, self.nA
+        limit = n if final else n - self.smargins[1]
+        while self.nA < limit:
+            c0, c1 = self.nA, min(self.nA + self.max_window, limit)
+            lo, hi = stream_window(c0, c1, n, self.smargins)
+            taps, rows = self._chain_pass(lo, hi)
+            for buf, t, rep in zip(self.taps + [self.p], taps + [rows], self.reps + [1]):
+                buf[0, c0 * rep: c1 * rep].copy_(t.interior_view()[0, (c0 - lo) * rep: (c1 - lo) * rep])
+            self.nA = c1
+        b = self.nA
+        if b == a:
+            return
+        L, cap, u = self.sk_lstm, self.cap, self.u
+        nl, bs = len(L.layers), cap * L.C
+        for l in range(nl):
+            src, last = (self.p if l == 0 else self.sk_mids[l - 1]), l == nl - 1
+            m._lstm_in_gemm(L, l, src.data_ptr(), bs, self.sk_gins[l], 1, cap, a, b)
+            m._lstm_steps(L, l, self.sk_gins[l], self.sk_hbufs[l], self.sk_cbufs[l], self.sk_hsplits[l],
+                          (u.interior if last else self.sk_mids[l].data_ptr()), bs, (self.p.data_ptr() if last else 0), bs, 1, cap, a, b,
+                          u.elu and last)
+
+    def _edge_rows(self, buf: TM, n: int, done: int, final: bool) -> int:
+        """How far a stride-1 convolution over `buf` (halo = its paddings) can go when the rows [0, n) of its input exist and `done` are
+        computed: to n less its look-ahead, or to n at the utterance's end — `DecodeStream._stage1`'s rule. Reflect padding: the halo rows
+        the new outputs read are written here (the left ones with the first output, the right ones at the end)."""
+        ready = n if final else n - buf.padR
+        if self.reflect and not final and n <= max(buf.padL, buf.padR):
+            ready = 0                                                 # reflect padding of so short an input depends on its length
+        ready = max(ready, done)
+        if ready > done and self.reflect:
+            if final:
+                self.m._call("ssrhip_pad_reflect", buf.base, 1, n, buf.padL, buf.padR, buf.C, buf.bstride)
+            elif done == 0:
+                self.m._call("ssrhip_pad_reflect", buf.base, 1, n, buf.padL, 0, buf.C, buf.bstride)
+        return ready
+
+    def _decoder_input(self, final: bool):
+        """Tap 4 (`_conv` of the skip encoder's last convolution) and `z` (`_concat_proj(0, ...)`) over the rows whose look-ahead in
+        `u` has arrived."""
+        m, u, c, z = self.m, self.u, self.sk_conv, self.z
+        a, b = self.nC, self._edge_rows(u, self.nA, self.nC, final)
+        if b == a:
+            return
+        m._gemm(u.base + 4 * a * u.C, c.W, c.b, self.tap4.data_ptr() + 4 * a * c.Cout, b - a, c.Cout, c.k * c.Cin, c.s * c.Cin, c.Cout,
+                act_in=m._act_in(bool(c.act_in), u), batch=1, sA=u.bstride, sC=self.cap * c.Cout)
+        pj, (Wa, cls) = m.wm_proj[0], m.wm_cls[0]
+        Cs, D = int(Wa.shape[1]), z.C
+        assert Cs == c.Cout and pj.Cout == D
+        m._gemm(self.tap4.data_ptr() + 4 * a * Cs, Wa, pj.b, z.interior + 4 * a * D, b - a, D, Cs, Cs, D, act_in=_lib.ACT_ELU,
+                R=self.q.data_ptr() + 4 * a * D, ldr=D, batch=1, sA=self.cap * Cs, sC=z.bstride, sR=self.cap * D,
+                rowcls=(cls, self.lab[:, a:b], 1))
+        self.nC = b
+
+    def _stage1(self, final: bool):
+        self._chain(final)
+        self._decoder_input(final)
+        a, b = self.n1, self._edge_rows(self.z, self.nC, self.n1, final)
+        if b > a:
+            self._stage1_rows(a, b)
+
+    def _tail_pass(self, lo: int, hi: int, item: Optional[int], few: bool = False) -> TM:
+        """`_StreamCore._tail_pass` with the taps: `_concat_proj(j)` behind each of the first three transposed convolutions, reading the
+        stored tap's rows of the window in place and the labels from the window's first frame on."""
+        m, s1 = self.m, self.s1
+        assert item == 0
+        x = TM(1, hi - lo, s1.C, 1, 1, m.device, data=s1.data[:, lo: hi + 2], keep_halo=True)
+        x.elu = s1.elu
+        with m._stream_pass(self.pool_1, few):
+            y = m._run(self.dn[0], x, after=None)
+            for j in (1, 2, 3):
+                tap, rep = self.taps[3 - j], self.reps[3 - j]
+                skip = TM(1, (hi - lo) * rep, int(tap.shape[2]), 0, 0, m.device, data=tap[:, lo * rep: hi * rep], keep_halo=True)
+                skip.elu = self.tap_elu[3 - j]
+                y = m._run(self.dn[j], m._concat_proj(j, skip, self.lab[:, lo:hi], rep, y, self.dn[j][0]), after=None)
+            return y
+
+    # ------------------------------------------------------------------ public
+    @torch.no_grad()
+    def push(self, codes: torch.Tensor, labels: torch.Tensor, audio: Optional[torch.Tensor] = None, emit: bool = True) -> torch.Tensor:
+        """The next n frames (n may be 0): codes [1, K, n], labels [n] or [1, n] (0 kept / 1 generated), audio [1, 1, n * hop] — the
+        kept-audio track under these frames; None = silence, what `kept_audio_track` puts under generated frames. Returns the samples
+        that became final, [1, 1, m * hop] (a view of the stream's output buffer; m may be 0). `emit=False` (only in front of every
+        emitted frame): the frames pass through both LSTMs and are never returned."""
+        if self.finished:
+            raise RuntimeError("WMDecodeStream.push after finish()")
+        cfg, hop = self.m.cfg, self.hop
+        assert codes.dim() == 3 and codes.shape[0] == 1 and codes.shape[1] == cfg.n_q, tuple(codes.shape)
+        n, at = int(codes.shape[-1]), self.n_pushed
+        if labels.numel() != n or (audio is not None and audio.numel() != n * hop):
+            raise ValueError(f"WMDecodeStream: {n} frames need {n} labels and {n * hop} samples, got {tuple(labels.shape)} / "
+                             f"{None if audio is None else tuple(audio.shape)}")
+        if at + n > self.cap:
+            raise ValueError(f"WMDecodeStream: {at} + {n} frames exceed max_frames = {self.cap}")
+        if not emit and self.emit_from is not None:
+            raise ValueError("WMDecodeStream: emit=False frames must come before every emitted frame")
+        if emit and self.emit_from is None:
+            self.emit_from = self.n2 = at
+        a = self.n2
+        if n == 0:
+            return self._out(a)
+        c32, l32 = self.codes[: cfg.n_q * n].view(1, cfg.n_q, n), self.lab[:, at: at + n]
+        c32.copy_(codes)
+        l32.copy_(labels.reshape(1, n))
+        # the range checks `wmdecode` makes (`_codes32`, `_labels32`), before the ids index the codebooks and the class-bias table
+        for i, t in enumerate((c32, l32)):
+            torch.amin(t, dim=tuple(range(t.dim())), out=self.lohi[2 * i])
+            torch.amax(t, dim=tuple(range(t.dim())), out=self.lohi[2 * i + 1])
+        c_lo, c_hi, l_lo, l_hi = self.lohi.tolist()
+        if c_hi >= cfg.bins or c_lo < 0 or l_hi >= self.m.wm_table.shape[0] or l_lo < 0:
+            raise IndexError("index out of range in self")
+        if audio is not None:
+            self.track[at * hop: (at + n) * hop].copy_(audio.reshape(-1))
+        D = self.q.shape[1]
+        self.m._call("ssrhip_rvq_decode", c32.data_ptr(), self.m.codebooks.data_ptr(), self.q.data_ptr() + 4 * at * D, 1, n, D, cfg.n_q,
+                     cfg.bins, self.cap * D)
+        self.n_pushed += n
+        self._stage1(False)
+        self._stage2(False)
         return self._out(a)
 
 

@@ -173,10 +173,16 @@ class AudioTokenizer:
     def decode_stream(self, max_frames: int, max_window: int = 16, use_watermark: bool = False):
         """`decode` in pieces while the frames are still being generated (`WMEncodecModel.decode_stream`): `push(frames [1, K, n],
         emit=True)` / `finish()` return waveform chunks whose concatenation is bit-identical to `decode` of all the frames. The
-        watermarked decode is not streamed: `wmdecode` runs its skip encoder over the kept-audio track of the WHOLE utterance."""
+        watermarked decode has a stream of its own, `wmdecode_stream`: its `push` also takes the labels and the kept-audio track."""
         if use_watermark:
-            raise ValueError("decode_stream: the watermarked decode (use_watermark=True) is not streamed; use wmdecode on the finished frames")
+            raise ValueError("decode_stream: the watermarked decode (use_watermark=True) is streamed by wmdecode_stream, not here")
         return self.codec.decode_stream(max_frames, max_window)
+
+    def wmdecode_stream(self, max_frames: int, max_window: int = 16):
+        """`wmdecode` in pieces while the frames are still being generated (`WMEncodecModel.wmdecode_stream`): `push(frames [1, K, n],
+        marks [n], wav [1, 1, n * hop] | None, emit=True)` / `finish()` return waveform chunks whose concatenation is bit-identical to
+        `wmdecode` of all the frames, marks and the whole kept-audio track (None = silence under generated frames)."""
+        return self.codec.wmdecode_stream(max_frames, max_window)
 
     def decode_stream_batch(self, prompt_lens: Sequence[int], max_new_frames: int, max_window: int = 16, use_watermark: bool = False):
         """`decode_stream` for B utterances generated in lock-step (`WMEncodecModel.decode_stream_batch`): `push_prompts(codes)`, then

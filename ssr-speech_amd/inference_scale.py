@@ -153,15 +153,10 @@ def inference_one_sample(model, model_args, phn2num, text_tokenizer, audio_token
 
 
 @torch.no_grad()
-def inference_one_sample_stream(model, model_args, phn2num, text_tokenizer, audio_tokenizer, audio_fn, prompt_text, target_text, mask_interval,
-                                cfg_coef, cfg_stride, aug_text, aug_context, use_watermark, tts, device, decode_config):
-    """`inference_one_sample` as a generator of waveform chunks [1, 1, n] (views of one buffer), handed out while the AR decode still
-    runs: `SSR_Speech.inference_stream` releases the frames that are final after every 16-step poll, `AudioTokenizer.decode_stream`
-    turns them into samples. The concatenation of the chunks is bit-identical to `inference_one_sample` with the same inputs and seed.
-    For `tts` the prompt (the first kept interval) only warms the codec's LSTM state up and is never yielded. The watermarked decode is
-    not streamed (`use_watermark=True` raises ValueError): its skip encoder reads the kept-audio track of the whole utterance."""
-    if use_watermark:
-        raise ValueError("inference_one_sample_stream: the watermarked decode (use_watermark=True) is not streamed; use inference_one_sample")
+def _stream_setup(make_codec, model, model_args, phn2num, text_tokenizer, audio_tokenizer, audio_fn, prompt_text, target_text, mask_interval,
+                  cfg_coef, cfg_stride, aug_text, device, decode_config):
+    """What the single-utterance streams share: the codec stream `make_codec(max_frames)` — it allocates everything NOW, ahead of the
+    engine's first launch — and the `SSR_Speech.inference_stream` that feeds it (nothing of it runs before its first `next()`)."""
     K = int(model_args.n_codebooks)
     target_ids = _phoneme_ids(text_tokenizer, phn2num, target_text)
     prompt_ids = _phoneme_ids(text_tokenizer, phn2num, prompt_text)
@@ -170,9 +165,9 @@ def inference_one_sample_stream(model, model_args, phn2num, text_tokenizer, audi
         raise AssertionError("renormalize=False codec: scale must be None")
     n_spans = int(mask_interval.reshape(-1, 2).shape[0])
     # the most frames the result can have: the prompt's + the decode's step cap (models/ssr.py `cap`: a span ends at the latest when the
-    # audio is 10x the text, + K + 1 eog steps each). The codec stream allocates everything NOW, ahead of the engine's first launch.
+    # audio is 10x the text, + K + 1 eog steps each)
     max_frames = int(prompt_frames.shape[1]) + 10 * int(target_ids.shape[1]) + 2 + n_spans * (K + 1)
-    codec = audio_tokenizer.decode_stream(max_frames)
+    codec = make_codec(max_frames)
     on_dev = lambda t: t.to(device)
     frames = model.inference_stream(
         on_dev(target_ids), on_dev(torch.tensor([target_ids.shape[1]])), on_dev(prompt_ids), on_dev(torch.tensor([prompt_ids.shape[1]])),
@@ -180,10 +175,78 @@ def inference_one_sample_stream(model, model_args, phn2num, text_tokenizer, audi
         top_k=decode_config["top_k"], top_p=decode_config["top_p"], temperature=decode_config["temperature"],
         stop_repetition=decode_config["stop_repetition"], kvcache=decode_config["kvcache"],
         cfg_coef=cfg_coef, cfg_stride=cfg_stride, aug_text=aug_text)
+    return codec, frames
+
+
+@torch.no_grad()
+def inference_one_sample_stream(model, model_args, phn2num, text_tokenizer, audio_tokenizer, audio_fn, prompt_text, target_text, mask_interval,
+                                cfg_coef, cfg_stride, aug_text, aug_context, use_watermark, tts, device, decode_config):
+    """`inference_one_sample` as a generator of waveform chunks [1, 1, n] (views of one buffer), handed out while the AR decode still
+    runs: `SSR_Speech.inference_stream` releases the frames that are final after every 16-step poll, `AudioTokenizer.decode_stream`
+    turns them into samples. The concatenation of the chunks is bit-identical to `inference_one_sample` with the same inputs and seed.
+    For `tts` the prompt (the first kept interval) only warms the codec's LSTM state up and is never yielded. The watermarked decode is
+    streamed by `inference_one_sample_wmstream`; here `use_watermark=True` raises ValueError."""
+    if use_watermark:
+        raise ValueError("inference_one_sample_stream: the watermarked decode (use_watermark=True) is streamed by inference_one_sample_wmstream")
+    codec, frames = _stream_setup(audio_tokenizer.decode_stream, model, model_args, phn2num, text_tokenizer, audio_tokenizer, audio_fn, prompt_text,
+                                  target_text, mask_interval, cfg_coef, cfg_stride, aug_text, device, decode_config)
     first = True
     for inc in frames:
         # the first increment is the first kept interval: for `tts` the prompt, which `inference_one_sample` cuts off (:85-86)
         chunk = codec.push(inc.codes.unsqueeze(0), emit=not (tts and first and inc.kept))
+        first = False
+        if chunk.shape[-1]:
+            yield chunk
+    if frames.result is None:
+        raise RuntimeError("generation did not finish")
+    chunk = codec.finish()
+    if chunk.shape[-1]:
+        yield chunk
+
+
+def kept_sources(non_mask_intervals: Sequence, crop: int = 0) -> list:
+    """The frames of the ORIGINAL audio under the kept `FrameIncrement`s of a stream, in their order: the i-th kept interval is
+    `non_mask_intervals[i]` — the mapping of `kept_audio_track`, which reads the result's intervals: shifted by the `aug_context` crop and
+    cut at 0. An empty interval releases no increment and has no entry."""
+    out = []
+    for s, e in non_mask_intervals:
+        s, e = max(int(s) - int(crop), 0), int(e) - int(crop)
+        if e > s:
+            out.append((s, e))
+    return out
+
+
+@torch.no_grad()
+def inference_one_sample_wmstream(model, model_args, phn2num, text_tokenizer, audio_tokenizer, audio_fn, prompt_text, target_text, mask_interval,
+                                  cfg_coef, cfg_stride, aug_text, aug_context, use_watermark, tts, device, decode_config):
+    """`inference_one_sample(..., use_watermark=True)` as a generator of waveform chunks [1, 1, n] (views of one buffer), handed out while
+    the AR decode still runs, for zero-shot TTS and for speech edits: `AudioTokenizer.wmdecode_stream` is pushed every increment's
+    codes and marks and, under a kept increment, the original audio of that kept interval (`kept_sources`; silence under generated
+    frames) — the rows `kept_audio_track` would put there. The concatenation of the chunks is bit-identical to `inference_one_sample`
+    with the same inputs and seed. A falsy `use_watermark` is `inference_one_sample_stream`."""
+    if not use_watermark:
+        yield from inference_one_sample_stream(model, model_args, phn2num, text_tokenizer, audio_tokenizer, audio_fn, prompt_text, target_text,
+                                               mask_interval, cfg_coef, cfg_stride, aug_text, aug_context, use_watermark, tts, device, decode_config)
+        return
+    codec, frames = _stream_setup(audio_tokenizer.wmdecode_stream, model, model_args, phn2num, text_tokenizer, audio_tokenizer, audio_fn,
+                                  prompt_text, target_text, mask_interval, cfg_coef, cfg_stride, aug_text, device, decode_config)
+    # the original audio, zero-extended to whole frames as `_watermark_inputs` extends it: uploaded once, ahead of the first launch
+    wav, _sr = read_wav(audio_fn) if isinstance(audio_fn, str) else (audio_fn, None)
+    short = -wav.shape[-1] % HOP
+    if short:
+        wav = F.pad(wav, (0, short))
+    orig = wav.reshape(1, 1, -1).to(audio_tokenizer.device, torch.float32)
+    sources, first = None, True
+    for inc in frames:
+        if sources is None:
+            sources = iter(kept_sources(frames.non_mask_intervals, frames.crop))
+        audio, n = None, int(inc.codes.shape[-1])
+        if inc.kept:
+            s, e = next(sources, (0, 0))
+            if e - s != n:
+                raise ValueError(f"kept interval changed length: {n} frames released for the original frames [{s},{e})")
+            audio = orig[..., s * HOP: e * HOP]
+        chunk = codec.push(inc.codes.unsqueeze(0), torch.as_tensor(inc.marks, dtype=torch.int32), audio, emit=not (tts and first and inc.kept))
         first = False
         if chunk.shape[-1]:
             yield chunk

@@ -40,10 +40,13 @@ def _set_param(root: nn.Module, dotted: str, p: nn.Parameter):
 
 class InferenceStream:
     """Iterator returned by `SSR_Speech.inference_stream`; `.result` is set when it is exhausted, `.steps_enqueued` is how many decode
-    steps the engine has been given so far."""
+    steps the engine has been given so far. From the first `next()` on, `.non_mask_intervals` holds the kept intervals on the ORIGINAL
+    frame axis and `.crop` the frames dropped in front (`aug_context`): where a kept increment's frames come from
+    (`inference_scale.kept_sources`)."""
 
     def __init__(self, model: "SSR_Speech", setup_args: tuple, use_graph: bool):
         self.model, self.result, self.steps_enqueued = model, None, 0
+        self.non_mask_intervals, self.crop = None, 0
         self._it = self._run(setup_args, use_graph)
 
     def __iter__(self):
@@ -60,6 +63,7 @@ class InferenceStream:
             run = m._begin_inference(*setup_args, before_start=lambda n: held.update(buf=torch.empty(K * n, dtype=torch.int64, device=m.device)))
             eng, buf = run["eng"], held["buf"]
             asm = LY.FrameAssembler(run["y_np"], run["nmi"], m.args, run["out_len"] if run["aug_context"] else 0)
+            self.non_mask_intervals, self.crop = list(asm.nmi), asm.out_len
             at = 0
 
             def on_device(incs):

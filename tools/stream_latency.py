@@ -9,7 +9,11 @@ codec launches per stage-2 window. One JSON line on stdout; `--out FILE` also wr
 `inference_samples_stream` against `inference_batch(refill=False, group=N)` + `render_many` in the same process, same warm-up and
 rounds; it reports the host time to the first chunk of the FIRST and of the LAST utterance (after a stream synchronize), both arms'
 total wall time (median and spread of the rounds), the polls and the codec launches per run.
-Usage: python tools/stream_latency.py [--weight_dtype bf16] [--utts 8] [--out profiles/stream_latency_830m.json]"""
+`--use_watermark` measures the WATERMARKED stream (DESIGN.md Part I.17): one-pass `inference_one_sample(use_watermark=True)`,
+`inference_one_sample_wmstream` and, for scale, the un-watermarked stream, same warm-up and rounds; it reports the first audio at the
+caller, the total wall time of the three, the chunks, the codec's library calls per 16-frame push, the hold-back in frames and whether
+every round was bit-identical.
+Usage: python tools/stream_latency.py [--weight_dtype bf16] [--utts 8 | --use_watermark] [--out profiles/stream_latency_830m.json]"""
 import argparse
 import json
 import os
@@ -24,7 +28,7 @@ import ssr_speech_amd  # noqa: E402,F401
 from ssr_speech_amd import weights as W  # noqa: E402
 from ssr_speech_amd.data.tokenizer import AudioTokenizer, write_wav  # noqa: E402
 from ssr_speech_amd.inference_scale import (_phoneme_ids, _prompt_codes, inference_one_sample, inference_one_sample_stream,  # noqa: E402
-                                            inference_samples_stream, render_many)
+                                            inference_one_sample_wmstream, inference_samples_stream, render_many)
 from ssr_speech_amd.models.ssr import SSR_Speech  # noqa: E402
 
 DEMO_PROMPT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "demo_5895_34622_000026_000002_160f.wav")
@@ -41,6 +45,7 @@ def main(argv=None):
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--weight_dtype", choices=["fp32", "bf16"], default="fp32")
     ap.add_argument("--utts", type=int, default=0, help="N > 0: the batched stream of N utterances against inference_batch + render_many")
+    ap.add_argument("--use_watermark", action="store_true", help="the watermarked stream against one-pass inference_one_sample(use_watermark=True)")
     opt = ap.parse_args(argv)
     dev = torch.device("cuda")
     args_lm = W.lm_args_830m()
@@ -76,7 +81,7 @@ def main(argv=None):
     if opt.utts > 0:
         return batched(opt, model, args_lm, tok, call, phn2num, fn, target_text, mi)
 
-    def one_pass(seed):
+    def one_pass(seed, call=call):
         torch.manual_seed(seed)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -87,13 +92,13 @@ def main(argv=None):
         return wav, dict(total_ms=1000 * (t1 - t0), first_16_frames_ms=1000 * (lr["t_first_chunk"] - t0), steps=int(lr["steps"]),
                          lm_ms=1000 * (lr["t_end"] - lr["t_start"]), audio_s=wav.shape[-1] / 16000.0)
 
-    def streamed(seed):
+    def streamed(seed, gen=inference_one_sample_stream, call=call):
         torch.manual_seed(seed)
         torch.cuda.synchronize()
         n0 = codec.n_launches
         t0 = time.perf_counter()
         chunks, first_ms = [], None
-        for chunk in inference_one_sample_stream(*call):
+        for chunk in gen(*call):
             if first_ms is None:
                 torch.cuda.current_stream().synchronize()
                 first_ms = 1000 * (time.perf_counter() - t0)
@@ -106,6 +111,8 @@ def main(argv=None):
                          first_16_frames_ms=1000 * (lr["t_first_chunk"] - t0), chunks=len(chunks), steps=int(lr["steps"]),
                          lm_ms=1000 * (lr["t_end"] - lr["t_start"]), codec_launches=codec.n_launches - n0, audio_s=wav.shape[-1] / 16000.0)
 
+    if opt.use_watermark:
+        return watermarked(opt, model, codec, ccfg, call, one_pass, streamed)
     one_pass(1)
     streamed(1)
     rounds = []
@@ -163,6 +170,63 @@ def main(argv=None):
         "codec_launches_per_16_frame_push": per_push,
         "synchronized_pushes": {"summed_ms": round(spent["push_ms"], 2), "calls": spent["calls"], "run_total_ms": round(timed_run["total_ms"], 2)},
         "all_bit_identical": all(r["stream"]["bit_identical"] for r in rounds),
+    }
+    line = json.dumps(out)
+    print(line)
+    if opt.out:
+        with open(opt.out, "w") as f:
+            f.write(json.dumps(out, indent=1) + "\n")
+    return 0
+
+
+def watermarked(opt, model, codec, ccfg, call, one_pass, streamed):
+    """--use_watermark: `inference_one_sample_wmstream` against one-pass `inference_one_sample(use_watermark=True)`, and the
+    un-watermarked stream for scale; `one_pass(seed, call)` / `streamed(seed, gen, call)` are main's timed runs"""
+    from ssr_speech_amd.codec.wmencodec import wm_stream_holdback
+    call_wm = call[:13] + (True,) + call[14:]
+    arms = (("one_pass", lambda s: one_pass(s, call_wm)), ("wmstream", lambda s: streamed(s, inference_one_sample_wmstream, call_wm)),
+            ("stream", lambda s: streamed(s)))
+    for _, run in arms:
+        run(1)
+    rounds = []
+    for r in range(opt.rounds):
+        got = {name: run(1 + r) for name, run in arms}
+        row = {name: stats for name, (_, stats) in got.items()}
+        wa, wb = got["one_pass"][0], got["wmstream"][0]
+        row["wmstream"]["bit_identical"] = bool(wa.shape == wb.shape and torch.equal(wa, wb))
+        rounds.append(row)
+    # launches of one 16-frame push in the middle of an utterance, counted on streams of their own
+    dev = codec.device
+    codes = torch.zeros(1, ccfg.n_q, 64, dtype=torch.long, device=dev)
+    marks, wav = torch.ones(64, dtype=torch.long, device=dev), torch.zeros(1, 1, 64 * 320, device=dev)
+    per_push = {}
+    for name, st, args in (("wmstream", codec.wmdecode_stream(64), lambda a, b: (codes[..., a:b], marks[a:b], wav[..., a * 320: b * 320])),
+                           ("stream", codec.decode_stream(64), lambda a, b: (codes[..., a:b],))):
+        st.push(*args(0, 24))
+        n0, w0 = codec.n_launches, st.windows
+        st.push(*args(24, 40))
+        per_push[name] = dict(launches=codec.n_launches - n0, windows=st.windows - w0)
+        st.finish()
+    torch.cuda.synchronize()
+    med = lambda xs: sorted(xs)[len(xs) // 2]
+    col = lambda arm, key: [r[arm][key] for r in rounds]
+    out = {
+        "tool": "tools/stream_latency.py --use_watermark", "weight_dtype": opt.weight_dtype,
+        "shape": "830M LM, full codec (8,5,4,2), 160-frame demo prompt, 67 phonemes, sampled, CFG stride 5, watermarked decode",
+        "rounds": rounds,
+        "median": {
+            "one_pass_total_ms": round(med(col("one_pass", "total_ms")), 2),
+            "wmstream_total_ms": round(med(col("wmstream", "total_ms")), 2),
+            "wmstream_first_chunk_ms": round(med(col("wmstream", "first_chunk_ms")), 2),
+            "stream_total_ms": round(med(col("stream", "total_ms")), 2),
+            "stream_first_chunk_ms": round(med(col("stream", "first_chunk_ms")), 2),
+        },
+        "wmstream_chunks": col("wmstream", "chunks"),
+        "wmstream_first_chunk_samples": rounds[0]["wmstream"]["first_chunk_samples"],
+        "codec_launches_per_16_frame_push": per_push,
+        "codec_launches_per_run": {"wmstream": med(col("wmstream", "codec_launches")), "stream": med(col("stream", "codec_launches"))},
+        "holdback_frames": wm_stream_holdback(ccfg),
+        "all_bit_identical": all(r["wmstream"]["bit_identical"] for r in rounds),
     }
     line = json.dumps(out)
     print(line)
