@@ -123,6 +123,26 @@ int ssrhip_gemv(const ssrhip_gemv_args* a, ssrhip_stream_t stream);
 int ssrhip_gemv_w16(const ssrhip_gemv_args* a, const uint16_t* W16, ssrhip_stream_t stream);
 int ssrhip_gemv_w16_applicable(const ssrhip_gemv_args* a);
 
+/* Packed OCP e4m3 weight layout of the opt-in e4m3 weight stream (<= 4 rows, csrc/gemv_w8.hip; K % 1024 == 0). The unit is the fp32
+ * segment kernels' (row, 1024-element segment of K) = 1 KiB = one wave-level load; lane l's 16 bytes sit at byte l*16 of the unit and hold
+ * that lane's four float4 of the fp32 kernel in order: dword i holds elements i*256 + 4l .. 4l+3 of the segment. Byte index of W[n][k]:
+ *   r = k % 1024:   (n*(K/1024) + k/1024)*1024 + ((r % 256)/4)*16 + (r/256)*4 + k%4
+ * A group's matrix takes N*K bytes; groups follow each other. Each byte is a finite OCP e4m3 code (torch.float8_e4m3fn; 0x7f / 0xff never
+ * occur); the weight is code * scale[n], scale[n] = 2^e one fp32 per output row (per group: scale[g*N + n]). */
+#define SSRHIP_W8_INDEX(n, k, K) \
+  (((size_t)(n) * ((size_t)(K) / 1024) + (size_t)(k) / 1024) * 1024 + ((((k) % 1024) % 256) / 4) * 16 + (((k) % 1024) / 256) * 4 + (k) % 4)
+
+/* ssrhip_gemv(a) streaming the PACKED e4m3 codes `W8` (SSRHIP_W8_INDEX) and the per-row power-of-two scales `scale` [groups][N] instead of
+ * a->W. a->W must hold exactly code * scale (the fp32 "master" q * 2^e); the result is then BIT-IDENTICAL to ssrhip_gemv(a): the codes are
+ * widened in registers (v_cvt_pk_f32_fp8, exact), every sum runs in the order of the fp32 kernel, and each (row, segment) partial sum is
+ * multiplied by scale[n] where it is parked — a power of two commutes with every fp32 rounding as long as no intermediate value is
+ * subnormal or overflows (the caveat: operands of that size round differently on the two sides).
+ *   returns 0 = launched, 1 = `a` does not qualify and NOTHING was launched (call ssrhip_gemv(a)), < 0 = contract error.
+ *   Qualifies exactly when ssrhip_gemv_w16 does. SSRHIP_GEMV_W8_DEPTH (read at every call): units in flight per wave of the straight-line
+ *   form, 2 | 4 | 8 (= every unit at entry); 0 = never that form. */
+int ssrhip_gemv_w8(const ssrhip_gemv_args* a, const uint8_t* W8, const float* scale, ssrhip_stream_t stream);
+int ssrhip_gemv_w8_applicable(const ssrhip_gemv_args* a);
+
 /* Packed bf16 weight layout of the bf16 weight stream at 5..16 rows (csrc/gemv_mfma_w16.hip; K % 64 == 0): the streaming order
  * SSRHIP_WTILED_INDEX in 2-byte weights. Rows in 8-row units (the last unit zero-padded), K in QUADS of four 16-float k-steps. With
  *   n = 8u + c,  k = 64q + 16j + 4ks + e,  h = j % 2,  g = j / 2
@@ -549,6 +569,27 @@ typedef struct ssrhip_lm_w16 {
 int ssrhip_lm_set_w16(ssrhip_lm* lm, const ssrhip_lm_w16* w16);
 /* how many GEMV launches of the last enqueued (or captured) decode step ran a bf16-stream kernel (4 * n_layer + 2 when every family qualifies) */
 int ssrhip_lm_w16_launches(const ssrhip_lm* lm);
+/* The opt-in e4m3 weight stream of the <= 4-row decode step: packed codes (SSRHIP_W8_INDEX) and per-row scales of the six matrix
+ * families, device pointers; the per-layer fields are HOST arrays of n_layer entries (copied by ssrhip_lm_set_w8). Codes and scales of a
+ * family come together; a NULL pair means that family streams its fp32 master. The masters in ssrhip_lm_weights must hold code * scale
+ * (ssrhip_gemv_w8). Twelve pointers; the record has no index in ssrhip_sizeof, its size comes back through ssrhip_lm_w8_sizeof. */
+typedef struct ssrhip_lm_w8 {
+  const uint8_t* const* in_proj_w8; const uint8_t* const* out_proj_w8; const uint8_t* const* ffn1_w8; const uint8_t* const* ffn2_w8;
+  const float* const* in_proj_s; const float* const* out_proj_s; const float* const* ffn1_s; const float* const* ffn2_s;
+  const uint8_t* head1_w8; const uint8_t* head2_w8;
+  const float* head1_s; const float* head2_s;
+} ssrhip_lm_w8;
+int ssrhip_lm_w8_sizeof(void);
+/* Hand the engine the packed codes and scales: from now on every GEMV launch of its decode step whose family has them and whose shape
+ * qualifies (ssrhip_gemv_w8) streams 1-byte weights; the others run ssrhip_gemv on the masters. Same tokens, bit for bit, as the same engine
+ * without this call. To be called before the first decode step is enqueued or captured; refused (< 0) afterwards, for engines of more than
+ * 4 rows, where another packed stream is already set (ssrhip_lm_set_w16 and its kin, and the reverse), and for a family with codes but no
+ * scales. The pair launches read fp32 weights: the engine gives its device's pairing slot back and steps unpaired (ssrhip_lm_pairing then
+ * reports 0 and names the e4m3 stream). Prefill and scoring read the masters and are not affected. */
+int ssrhip_lm_set_w8(ssrhip_lm* lm, const ssrhip_lm_w8* w8);
+/* how many GEMV launches of the last enqueued (or captured) decode step ran a kernel of csrc/gemv_w8.hip (4 * n_layer + 2 when every family
+ * qualifies); a counter of its own: the bf16 streams' counters stay 0 for these engines */
+int ssrhip_lm_w8_launches(const ssrhip_lm* lm);
 /* The same for the 5..16-row decode step: the record's pointers are SSRHIP_WT16_INDEX copies of the six families (NULL field / NULL entry:
  * that family streams the fp32 streaming-order copy of its master). From now on every GEMV launch of the step tries ssrhip_gemv_wt16 first
  * and falls back to ssrhip_gemv; same tokens, bit for bit; the step stays one captured graph. Refused (< 0) for engines of <= 4 rows (they

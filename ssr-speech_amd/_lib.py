@@ -169,6 +169,13 @@ class LMW16(C.Structure):
                 ("head1_w16", C.c_void_p), ("head2_w16", C.c_void_p)]
 
 
+class LMW8(C.Structure):
+    """ssrhip_lm_w8: twelve pointers. Not in ABI_STRUCTS (ssrhip_sizeof knows no index for it): `lib()` checks it through ssrhip_lm_w8_sizeof."""
+    _fields_ = [("in_proj_w8", _PP), ("out_proj_w8", _PP), ("ffn1_w8", _PP), ("ffn2_w8", _PP),
+                ("in_proj_s", _PP), ("out_proj_s", _PP), ("ffn1_s", _PP), ("ffn2_s", _PP),
+                ("head1_w8", C.c_void_p), ("head2_w8", C.c_void_p), ("head1_s", C.c_void_p), ("head2_s", C.c_void_p)]
+
+
 # every symbol include/ssrhip.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("ssrhip_version", C.c_int, []),
@@ -177,6 +184,8 @@ SYMBOLS = [
     ("ssrhip_gemv", C.c_int, [C.POINTER(GemvArgs), C.c_void_p]),
     ("ssrhip_gemv_w16", C.c_int, [C.POINTER(GemvArgs), C.c_void_p, C.c_void_p]),
     ("ssrhip_gemv_w16_applicable", C.c_int, [C.POINTER(GemvArgs)]),
+    ("ssrhip_gemv_w8", C.c_int, [C.POINTER(GemvArgs), C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("ssrhip_gemv_w8_applicable", C.c_int, [C.POINTER(GemvArgs)]),
     ("ssrhip_gemv_wt16", C.c_int, [C.POINTER(GemvArgs), C.c_void_p, C.c_void_p]),
     ("ssrhip_gemv_wt16_applicable", C.c_int, [C.POINTER(GemvArgs)]),
     ("ssrhip_gemv_wt32", C.c_int, [C.POINTER(GemvArgs), C.c_void_p, C.c_void_p]),
@@ -232,6 +241,9 @@ SYMBOLS = [
     ("ssrhip_lm_pair_status", C.c_int, [C.c_void_p, C.c_void_p]),
     ("ssrhip_lm_set_w16", C.c_int, [C.c_void_p, C.POINTER(LMW16)]),
     ("ssrhip_lm_w16_launches", C.c_int, [C.c_void_p]),
+    ("ssrhip_lm_w8_sizeof", C.c_int, []),
+    ("ssrhip_lm_set_w8", C.c_int, [C.c_void_p, C.POINTER(LMW8)]),
+    ("ssrhip_lm_w8_launches", C.c_int, [C.c_void_p]),
     ("ssrhip_lm_set_wt16", C.c_int, [C.c_void_p, C.POINTER(LMW16)]),
     ("ssrhip_lm_wt16_launches", C.c_int, [C.c_void_p]),
     ("ssrhip_lm_set_wt32", C.c_int, [C.c_void_p, C.POINTER(LMW16)]),
@@ -282,6 +294,8 @@ def lib():
     for i, st in enumerate(ABI_STRUCTS):
         if L.ssrhip_sizeof(i) != C.sizeof(st):
             raise SsrHipUnavailable(f"ABI mismatch: sizeof({st.__name__}) = {C.sizeof(st)} but the library says {L.ssrhip_sizeof(i)}")
+    if L.ssrhip_lm_w8_sizeof() != C.sizeof(LMW8):
+        raise SsrHipUnavailable(f"ABI mismatch: sizeof(LMW8) = {C.sizeof(LMW8)} but the library says {L.ssrhip_lm_w8_sizeof()}")
     _lib = L
     return L
 

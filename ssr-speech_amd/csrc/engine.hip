@@ -73,7 +73,12 @@ struct ssrhip_lm {
   std::vector<const uint16_t*> pk[4];       // in_proj, out_proj, ffn1, ffn2 per layer (empty: none)
   const uint16_t* pk_head1 = nullptr;
   const uint16_t* pk_head2 = nullptr;
-  int pk_launches = 0;          // launches of the last enqueued step that ran a kernel of pk_kind (ssrhip_lm_{w16,wt16,wt32}_launches)
+  int pk_launches = 0;          // launches of the last enqueued step that ran a kernel of pk_kind (ssrhip_lm_{w16,wt16,wt32,w8}_launches)
+  // the e4m3 weight stream (pk_kind == PK_W8, <= 4 rows): codes in SSRHIP_W8_INDEX order and, travelling next to them, the per-row scales
+  std::vector<const uint8_t*> pk8[4];
+  std::vector<const float*> pk8s[4];
+  const uint8_t* pk8_head1 = nullptr; const uint8_t* pk8_head2 = nullptr;
+  const float* pk8s_head1 = nullptr; const float* pk8s_head2 = nullptr;
   bool kv16 = false;            // b.kv.pool holds 2-byte entries (ssrhip_lm_set_kv16: the caller's statement about its buffer)
   int kv16_launches = 0;        // attention launches of the last enqueued step that ran ssrhip_attn_rows_kv16 (ssrhip_lm_kv16_launches)
   const int32_t* chunk_head = nullptr;   // prompt sharing (ssrhip_lm_set_prompt_groups): the caller's two device arrays [B], or null = off
@@ -97,7 +102,10 @@ const PackedStream PACKED_STREAMS[3] = {
     {"ssrhip_lm_set_wt16", 5, 16, "5..16", "the bf16 weight stream of the matrix-core step exists for 5..16 rows only", ssrhip_gemv_wt16, true, false},
     {"ssrhip_lm_set_wt32", 17, 32, "17..32", "the bf16 weight stream of the two-panel step exists for 17..32 rows only", ssrhip_gemv_wt32, true, false},
 };
-enum { PK_W16 = 0, PK_WT16 = 1, PK_WT32 = 2 };
+enum { PK_W16 = 0, PK_WT16 = 1, PK_WT32 = 2, PK_W8 = 3 };   // PK_W8: the fourth packed kind, the e4m3 stream (ssrhip_lm_set_w8; codes AND scales,
+                                                            // so its entry point has another signature and it has no row in PACKED_STREAMS)
+// what a launch of one family streams instead of its fp32 master: a 2-byte copy (the bf16 kinds) or codes + scales (PK_W8); all NULL = nothing
+struct PackedRef { const uint16_t* w16; const uint8_t* w8; const float* sc; };
 
 enum { CAT_GEMV = 0, CAT_ATTN = 1, CAT_SAMPLE = 2 };
 
@@ -352,14 +360,18 @@ int enqueue_step(ssrhip_lm* lm, hipStream_t s, Timer* tm) {
   // qualifies (the packed entry point of the engine's kind answers 1 without launching when it does not), the fp32 weights otherwise.
   // Same bits either way.
   int n_pk = 0;
-  auto gemv_call = [&](const ssrhip_gemv_args& ga, const uint16_t* pk) -> int {
-    if (pk) {
-      const int rc = PACKED_STREAMS[lm->pk_kind].gemv(&ga, pk, (ssrhip_stream_t)s);
+  auto gemv_call = [&](const ssrhip_gemv_args& ga, const PackedRef pk) -> int {
+    if (pk.w16 || pk.w8) {
+      const int rc = pk.w8 ? ssrhip_gemv_w8(&ga, pk.w8, pk.sc, (ssrhip_stream_t)s) : PACKED_STREAMS[lm->pk_kind].gemv(&ga, pk.w16, (ssrhip_stream_t)s);
       if (rc <= 0) { n_pk += rc == 0; return rc; }
     }
     return ssrhip_gemv(&ga, s);
   };
-  auto w16_of = [&](int family, int l) -> const uint16_t* { return lm->pk[family].empty() ? nullptr : lm->pk[family][l]; };
+  auto w16_of = [&](int family, int l) -> PackedRef {
+    if (lm->pk_kind == PK_W8) return lm->pk8[family].empty() ? PackedRef{nullptr, nullptr, nullptr} : PackedRef{nullptr, lm->pk8[family][l], lm->pk8s[family][l]};
+    return PackedRef{lm->pk[family].empty() ? nullptr : lm->pk[family][l], nullptr, nullptr};
+  };
+  const PackedRef pk_h1 = {lm->pk_head1, lm->pk8_head1, lm->pk8s_head1}, pk_h2 = {lm->pk_head2, lm->pk8_head2, lm->pk8s_head2};
   enum { W16_IN = 0, W16_OUT = 1, W16_FFN1 = 2, W16_FFN2 = 3 };
   bool qkv_done = false;                        // this layer's QKV already ran inside the previous layer's pair launch
   // 5..32 rows with enough (row, head) pairs to give every CU one: the fused walk over the pages (no partials, no merge
@@ -427,10 +439,10 @@ int enqueue_step(ssrhip_lm* lm, hipStream_t s, Timer* tm) {
   }
   if (!qkv_done) {
     const ssrhip_gemv_args g = sh.head1_args();
-    STEP_CALL(CAT_GEMV, gemv_call(g, lm->pk_head1));
+    STEP_CALL(CAT_GEMV, gemv_call(g, pk_h1));
   }
   const ssrhip_gemv_args h2 = sh.head2_args();
-  STEP_CALL(CAT_GEMV, gemv_call(h2, lm->pk_head2));
+  STEP_CALL(CAT_GEMV, gemv_call(h2, pk_h2));
   const ssrhip_sample_args sa = sh.sample_args();
   STEP_CALL(CAT_SAMPLE, ssrhip_sample(&sa, s));
   if (!tm || tm->only < 0) { lm->pk_launches = n_pk; lm->kv16_launches = n_kv16; lm->group_launches = n_group; }   // (a category-timing pass enqueues only part of a step)
@@ -540,6 +552,7 @@ static int lm_set_packed(ssrhip_lm* lm, const ssrhip_lm_w16* rec, int kind) {
     SSR_REQUIRE(B >= ps.lo || B > o.hi, "%s: engines of %s rows stream bf16 weights through %s (this engine has %d rows)", ps.setter, o.rows, o.setter, B);
   SSR_REQUIRE(B <= ps.hi, "%s: %s (this engine has %d rows)", ps.setter, ps.only, B);
   SSR_REQUIRE(!lm->exec, "%s: the decode step of this engine is already captured (call it before the first ssrhip_lm_decode)", ps.setter);
+  SSR_REQUIRE(lm->pk_kind != PK_W8, "%s: this engine already streams e4m3 weights (ssrhip_lm_set_w8); an engine has one packed stream", ps.setter);
   SSR_REQUIRE(!ps.needs_wt || lm->w.in_proj_wt, "%s: this engine was created without the fp32 streaming-order copies (ssrhip_lm_weights *_wt)", ps.setter);
   const uint16_t* const* src[4] = {rec->in_proj_w16, rec->out_proj_w16, rec->ffn1_w16, rec->ffn2_w16};
   for (int f = 0; f < 4; ++f) {
@@ -557,6 +570,40 @@ static int lm_set_packed(ssrhip_lm* lm, const ssrhip_lm_w16* rec, int kind) {
   return 0;
 }
 static int lm_packed_launches(const ssrhip_lm* lm, int kind) { return lm && lm->pk_kind == kind ? lm->pk_launches : 0; }
+
+extern "C" int ssrhip_lm_w8_sizeof(void) { return (int)sizeof(ssrhip_lm_w8); }
+// The fourth packed kind: the checks of lm_set_packed for the <= 4-row step, then codes and scales side by side.
+extern "C" int ssrhip_lm_set_w8(ssrhip_lm* lm, const ssrhip_lm_w8* rec) {
+  SSR_REQUIRE(lm && rec, "ssrhip_lm_set_w8: null argument");
+  const int B = lm->b.B;
+  SSR_REQUIRE(B <= 4, "ssrhip_lm_set_w8: the e4m3 weight stream exists for the <= 4-row decode step only (this engine has %d rows)", B);
+  SSR_REQUIRE(!lm->exec, "ssrhip_lm_set_w8: the decode step of this engine is already captured (call it before the first ssrhip_lm_decode)");
+  SSR_REQUIRE(lm->pk_kind < 0 || lm->pk_kind == PK_W8, "ssrhip_lm_set_w8: this engine already streams bf16 weights (%s); an engine has one packed stream",
+              lm->pk_kind >= 0 && lm->pk_kind < PK_W8 ? PACKED_STREAMS[lm->pk_kind].setter : "");
+  const uint8_t* const* src[4] = {rec->in_proj_w8, rec->out_proj_w8, rec->ffn1_w8, rec->ffn2_w8};
+  const float* const* scl[4] = {rec->in_proj_s, rec->out_proj_s, rec->ffn1_s, rec->ffn2_s};
+  for (int f = 0; f < 4; ++f) SSR_REQUIRE(!src[f] == !scl[f], "ssrhip_lm_set_w8: codes and scales of a family come together (family %d)", f);
+  SSR_REQUIRE(!rec->head1_w8 == !rec->head1_s && !rec->head2_w8 == !rec->head2_s, "ssrhip_lm_set_w8: codes and scales of a head matrix come together");
+  for (int f = 0; f < 4; ++f) {
+    if (src[f]) {
+      for (int l = 0; l < lm->d.n_layer; ++l)
+        SSR_REQUIRE(src[f][l] && scl[f][l], "ssrhip_lm_set_w8: null codes or scales (family %d, layer %d)", f, l);
+    }
+  }
+  for (int f = 0; f < 4; ++f) {
+    if (src[f]) { lm->pk8[f].assign(src[f], src[f] + lm->d.n_layer); lm->pk8s[f].assign(scl[f], scl[f] + lm->d.n_layer); }
+    else { lm->pk8[f].clear(); lm->pk8s[f].clear(); }
+  }
+  lm->pk8_head1 = rec->head1_w8; lm->pk8s_head1 = rec->head1_s;
+  lm->pk8_head2 = rec->head2_w8; lm->pk8s_head2 = rec->head2_s;
+  lm->pk_kind = PK_W8;
+  // the pair launches stream fp32 weights: this engine steps unpaired and gives the device's pairing slot back
+  if (lm->pair_ws) { hipFree(lm->pair_ws); lm->pair_ws = nullptr; }
+  if (lm->pair_dev >= 0) { pair_slot_release(lm->pair_dev); lm->pair_dev = -1; }
+  snprintf(lm->pair_why, sizeof(lm->pair_why), "this engine streams e4m3 weights (ssrhip_lm_set_w8): the pair launches exist for fp32 weights only");
+  return 0;
+}
+extern "C" int ssrhip_lm_w8_launches(const ssrhip_lm* lm) { return lm_packed_launches(lm, PK_W8); }
 
 extern "C" int ssrhip_lm_set_w16(ssrhip_lm* lm, const ssrhip_lm_w16* w16) { return lm_set_packed(lm, w16, PK_W16); }
 extern "C" int ssrhip_lm_set_wt16(ssrhip_lm* lm, const ssrhip_lm_w16* wt16) { return lm_set_packed(lm, wt16, PK_WT16); }

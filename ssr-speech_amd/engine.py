@@ -96,8 +96,59 @@ def from_wt16_order(P: torch.Tensor, N: int) -> torch.Tensor:
     return Wb[..., :N, :].to(torch.float32).contiguous()
 
 
+def to_w8_order(Q: torch.Tensor) -> torch.Tensor:
+    """[.., N, K] 1-byte codes (K % 1024 == 0) -> the packed order of the <= 4-row e4m3 weight stream (include/ssrhip.h SSRHIP_W8_INDEX), same
+    shape and dtype: per (row, 1024-element segment) ONE KiB-sized wave load, lane l's 16 bytes holding the fp32 kernel's four float4 of
+    that lane in order. One permute; nothing is rounded here (the codes come from `quantize_e4m3` / `e4m3_codes`)."""
+    *lead, N, K = Q.shape
+    assert K % 1024 == 0 and Q.element_size() == 1, (K, Q.dtype)
+    n = len(lead)
+    return Q.reshape(*lead, N, K // 1024, 4, 64, 4).permute(*range(n), n, n + 1, n + 3, n + 2, n + 4).contiguous().reshape(*lead, N, K)   # [n][segment][i][lane][k % 4] -> [..][lane][i][..]
+
+
+def from_w8_order(P: torch.Tensor) -> torch.Tensor:
+    """Inverse of `to_w8_order`: the packed codes [.., N, K] -> the codes in [n][k] order."""
+    *lead, N, K = P.shape
+    n = len(lead)
+    return P.reshape(*lead, N, K // 1024, 64, 4, 4).permute(*range(n), n, n + 1, n + 3, n + 2, n + 4).contiguous().reshape(*lead, N, K)
+
+
+E4M3_MAX = 448.0              # the largest finite OCP e4m3 value (torch.float8_e4m3fn): 0.875 * 2^9
+
+
+def quantize_e4m3(W: torch.Tensor):
+    """[.., N, K] fp32 -> (codes uint8 [.., N, K], scale fp32 [.., N]): per output row the smallest integer e with amax <= 448 * 2^e (exactly,
+    from `torch.frexp`: amax = m * 2^x, m in [0.5, 1): e = x - 9 if m <= 0.875 else x - 8; a row of zeros takes e = 0; clamped to
+    [-100, 100]), scale = 2^e, codes = ldexp(W, -e) rounded to OCP e4m3 (nearest, ties to even). |ldexp(W, -e)| <= 448 by construction, so
+    the NaN codes 0x7f / 0xff never occur. A non-finite weight or one with |w| >= 2^100 raises ValueError. The weight the model then
+    computes with is codes.view(float8_e4m3fn).float() * scale, exactly (`e4m3_master`)."""
+    W = W.to(torch.float32)
+    if not bool(torch.isfinite(W).all()):
+        raise ValueError("quantize_e4m3: non-finite weight")
+    amax = W.abs().amax(dim=-1)
+    if bool((amax >= 2.0 ** 100).any()):
+        raise ValueError("quantize_e4m3: |weight| >= 2^100")
+    m, x = torch.frexp(amax)
+    e = torch.where(m <= 0.875, x - 9, x - 8)
+    e = torch.where(amax == 0, torch.zeros_like(e), e).clamp(-100, 100)
+    scale = torch.ldexp(torch.ones_like(amax), e)
+    return e4m3_codes(W, scale), scale
+
+
+def e4m3_codes(W: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """The codes of `quantize_e4m3` for given power-of-two scales [.., N]: W / scale (exact) rounded to e4m3. On a master it is the exact inverse
+    of `e4m3_master`."""
+    return (W * (1.0 / scale).unsqueeze(-1)).to(torch.float8_e4m3fn).view(torch.uint8)
+
+
+def e4m3_master(codes: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """codes * scale as fp32 [.., N, K]: exact (an e4m3 value has 4 significant bits, the scale is a power of two), and bf16-representable."""
+    return (codes.view(torch.float8_e4m3fn).to(torch.float32) * scale.unsqueeze(-1)).contiguous()
+
+
 W16_FAMILIES = ("in_proj", "out_proj", "ffn1", "ffn2")      # per layer; plus head1 and head2
-WEIGHT_DTYPES = ("fp32", "bf16")
+WEIGHT_DTYPES = ("fp32", "bf16", "e4m3")
+BF16_VALUED = ("bf16", "e4m3")      # arenas whose masters are bf16-representable (an e4m3 value times a power of two is)
 # What an unset SSRHIP_GEMVM_W16 means for a 5..16-row engine of a bf16 arena (DecodeEngine stream_wt16=None): "1" = stream the
 # SSRHIP_WT16_INDEX copies, "0" = stream the fp32 streaming-order masters. Decided by the measurement in DESIGN.md Part I.11.
 WT16_DEFAULT = "0"
@@ -135,6 +186,22 @@ W16_STREAMS = (
     W16Stream("wt16", 5, 16, "5..16", "SSRHIP_GEMVM_W16", WT16_DEFAULT, "wt16", "the bf16 weight stream of the matrix-core step exists for 5..16 rows only"),
     W16Stream("wt32", 17, 32, "17..32", "SSRHIP_GEMVM_W16", WT32_DEFAULT, "wt16", "the bf16 weight stream of the two-panel step exists for 17..32 rows only"),
 )
+
+
+def resolve_w8_stream(rows: int, weight_dtype: str, requested: Optional[bool], env) -> bool:
+    """Does an engine of `rows` rows on an arena of `weight_dtype` run the e4m3 weight stream (DecodeEngine stream_w8)? requested None: on
+    iff the arena is e4m3, the engine has <= 4 rows and `env["SSRHIP_GEMV_W8"]` (unset: on) does not start with '0'. requested True:
+    ValueError at more than 4 rows (named before the dtype is looked at), then for any other arena. `env` is a mapping like os.environ;
+    nothing else is read."""
+    if requested is None:
+        return weight_dtype == "e4m3" and rows <= 4 and env.get("SSRHIP_GEMV_W8", "1")[:1] != "0"
+    if not requested:
+        return False
+    if rows > 4:
+        raise ValueError(f"stream_w8: the e4m3 weight stream exists for the <= 4-row decode step only (this engine has {rows} rows)")
+    if weight_dtype != "e4m3":
+        raise ValueError("stream_w8 needs an arena built with weight_dtype='e4m3'")
+    return True
 
 
 def resolve_w16_stream(st: W16Stream, rows: int, weight_dtype: str, requested: Optional[bool], env) -> bool:
@@ -211,18 +278,18 @@ def plan_prompt_sharing(seqs, members: int):
 def resolve_prefill_planes(weight_dtype: str, requested: Optional[int], env) -> int:
     """How many bf16 planes per matrix does an arena of `weight_dtype` build for the prefill / score GEMMs? 0 = none (`env` has
     SSRHIP_PREFILL_SPLIT starting with '0': the fp32 chain, whatever else is asked), 3 = the exact split of an fp32 value, 1 = the value
-    itself, which only a bf16 arena's masters are. requested None: 1 iff the arena is bf16 and `env["SSRHIP_PREFILL_W1"]` (unset:
+    itself, which only a bf16-valued arena's masters are ("bf16", "e4m3"). requested None: 1 iff the arena is bf16-valued and `env["SSRHIP_PREFILL_W1"]` (unset:
     PREFILL_W1_DEFAULT) does not start with '0'. requested 1 on an fp32 arena: ValueError. `env` is a mapping like os.environ; nothing else
     is read."""
     if requested not in (None, 1, 3):
         raise ValueError(f"split planes come as 1 or 3 per matrix, not {requested!r}")
-    if requested == 1 and weight_dtype != "bf16":
+    if requested == 1 and weight_dtype not in BF16_VALUED:
         raise ValueError("one plane per matrix needs an arena built with weight_dtype='bf16' (an fp32 weight is the sum of three bf16 planes)")
     if env.get("SSRHIP_PREFILL_SPLIT", "1")[:1] == "0":      # the C side's rule (engine.hip): a value that starts with '0'
         return 0
     if requested is not None:
         return requested
-    return 1 if weight_dtype == "bf16" and env.get("SSRHIP_PREFILL_W1", PREFILL_W1_DEFAULT)[:1] != "0" else 3
+    return 1 if weight_dtype in BF16_VALUED and env.get("SSRHIP_PREFILL_W1", PREFILL_W1_DEFAULT)[:1] != "0" else 3
 
 
 class LMWeightsArena:
@@ -231,7 +298,13 @@ class LMWeightsArena:
     weight_dtype="bf16": the six matrix families of the decode step (in_proj / out_proj / ffn1 / ffn2 per layer, head1, head2) are rounded
     ONCE to bf16 (nearest even) as the arena holds them, i.e. after the LayerNorm fold, and kept as fp32 "masters" in the usual fields:
     prefill, score, the streaming-order copies and the split planes all read the same rounded values. `ensure_w16_copies` adds the
-    packed 2-byte copies the <= 4-row decode step streams. Biases, embeddings and the position table stay fp32."""
+    packed 2-byte copies the <= 4-row decode step streams. Biases, embeddings and the position table stay fp32.
+
+    weight_dtype="e4m3": the same six families are quantised ONCE (`quantize_e4m3`: OCP e4m3 codes and one power-of-two scale per output
+    row, per group for head2), after the LayerNorm fold; the masters hold codes * scale, which is bf16-representable, so the arena is
+    `bf16_valued` and every rule made for bf16 masters applies to it. The scales stay with the arena (lay[name + "_w8s"], head{1,2}_w8s);
+    `ensure_w8_copies` adds the packed 1-byte codes the <= 4-row decode step streams. The rounding is coarse: 2.6 % relative rms of the
+    weights against 0.17 % for bf16. Biases carry W beta from the UNROUNDED weights."""
 
     def __init__(self, args, sd: dict, device, max_pos: int = 8192, weight_dtype: str = "fp32"):
         if weight_dtype not in WEIGHT_DTYPES:
@@ -285,6 +358,15 @@ class LMWeightsArena:
         self.head1_b = (h1b.double() + h1w.double() @ bet.double()).to(torch.float32).contiguous()
         self.head2_w = torch.stack([g(f"predict_layer.{k}.2.weight") for k in range(self.K)]).contiguous()
         self.head2_b = torch.stack([g(f"predict_layer.{k}.2.bias") for k in range(self.K)]).contiguous()
+        if weight_dtype == "e4m3":
+            def quant(t):
+                q, sc = quantize_e4m3(t)
+                return e4m3_master(q, sc), sc.contiguous()
+            for lay in self.layers:
+                for name in W16_FAMILIES:
+                    lay[name + "_w"], lay[name + "_w8s"] = quant(lay[name + "_w"])
+            self.head1_w, self.head1_w8s = quant(self.head1_w)
+            self.head2_w, self.head2_w8s = quant(self.head2_w)
         if weight_dtype == "bf16":
             rnd = lambda t: t.to(torch.bfloat16).to(torch.float32).contiguous()
             for lay in self.layers:
@@ -297,8 +379,14 @@ class LMWeightsArena:
         self.split_planes = 3
         self._planes_decided = False
 
+    @property
+    def bf16_valued(self) -> bool:
+        """Is every master of the six matrix families bf16-representable ("bf16": rounded to it; "e4m3": 4 significant bits times 2^e)?
+        The one-plane prefill / score GEMM, the packed 2-byte streaming copies and their switches ask this, not the dtype's name."""
+        return self.weight_dtype in BF16_VALUED
+
     def _ensure_packed(self, order: str) -> bool:
-        if self.weight_dtype != "bf16":
+        if not self.bf16_valued:
             raise ValueError("packed bf16 copies need an arena built with weight_dtype='bf16' (the masters must hold the rounded values)")
         if getattr(self, f"_{order}_ready", False):
             return False
@@ -333,6 +421,39 @@ class LMWeightsArena:
     def w16_struct(self):
         """ssrhip_lm_w16 of the packed copies (NULL where a family has none)."""
         return self._packed_struct("w16")
+
+    def ensure_w8_copies(self) -> bool:
+        """Packed e4m3 codes (`to_w8_order` of `e4m3_codes(master, scale)`, exact) of the six matrix families for the <= 4-row decode step of
+        an e4m3 arena (+1 byte per weight = +0.82 GB at 830M beside the scales, built once on first use). A family whose inner dimension
+        the kernels do not take (`w16_streamable`, e.g. d_model 128) gets none and streams its master. Returns True when created now."""
+        if self.weight_dtype != "e4m3":
+            raise ValueError("packed e4m3 codes need an arena built with weight_dtype='e4m3' (the masters must hold codes * scale)")
+        if getattr(self, "_w8_ready", False):
+            return False
+        pack = lambda Wm, sc: to_w8_order(e4m3_codes(Wm, sc)) if w16_streamable(Wm.shape[-1]) else None
+        for lay in self.layers:
+            for name in W16_FAMILIES:
+                lay[name + "_w8"] = pack(lay[name + "_w"], lay[name + "_w8s"])
+        self.head1_w8 = pack(self.head1_w, self.head1_w8s)
+        self.head2_w8 = pack(self.head2_w, self.head2_w8s)
+        self._w8_ready = True
+        self.generation += 1
+        return True
+
+    def w8_struct(self):
+        """ssrhip_lm_w8 of the packed codes and their scales (NULL pairs where a family has no packed copy)."""
+        w = _lib.LMW8()
+        arrays = self._w8_arrays = {}                   # the record points into them
+        for name in W16_FAMILIES:
+            if all(lay[name + "_w8"] is not None for lay in self.layers):
+                for suffix, field in (("_w8", name + "_w8"), ("_w8s", name + "_s")):
+                    arrays[field] = (C.c_void_p * self.L)(*[lay[name + suffix].data_ptr() for lay in self.layers])
+                    setattr(w, field, C.cast(arrays[field], C.POINTER(C.c_void_p)))
+        for h in ("head1", "head2"):
+            if getattr(self, h + "_w8") is not None:
+                setattr(w, h + "_w8", getattr(self, h + "_w8").data_ptr())
+                setattr(w, h + "_s", getattr(self, h + "_w8s").data_ptr())
+        return w
 
     def ensure_wt16_copies(self) -> bool:
         """Packed bf16 streaming-order copies (`to_wt16_order`) of the six matrix families for the 5..32-row decode step of a bf16 arena
@@ -433,7 +554,7 @@ class LMWeightsArena:
         """Algorithmic weight bytes one decode step must stream."""
         n = 0
         for lay in self.layers:
-            n += sum(t.numel() for k, t in lay.items() if not k.endswith(("_wt", "_ws", "_w16", "_wt16")))     # incl. the (now constant) LayerNorm vectors, as SURVEY §8d counts them
+            n += sum(t.numel() for k, t in lay.items() if not k.endswith(("_wt", "_ws", "_w16", "_wt16", "_w8", "_w8s")))     # incl. the (now constant) LayerNorm vectors, as SURVEY §8d counts them
         n += self.lnf_w.numel() + self.lnf_b.numel()
         n += self.head1_w.numel() + self.head1_b.numel() + self.head2_w.numel() + self.head2_b.numel()
         n += (self.K + 1) * self.D  # K embedding rows + one pe row
@@ -442,6 +563,10 @@ class LMWeightsArena:
         if order is not None:
             half = sum(lay[name + "_w"].numel() for lay in self.layers for name in W16_FAMILIES if lay[f"{name}_{order}"] is not None)
             half += sum(m.numel() for m, h in ((self.head1_w, "head1_"), (self.head2_w, "head2_")) if getattr(self, h + order) is not None)
+        if getattr(self, "_w8_ready", False):       # a family with packed e4m3 codes streams 1 byte per weight and one fp32 scale per output row
+            fams = [(lay[name + "_w"], lay[name + "_w8"], lay[name + "_w8s"]) for lay in self.layers for name in W16_FAMILIES]
+            fams += [(self.head1_w, self.head1_w8, self.head1_w8s), (self.head2_w, self.head2_w8, self.head2_w8s)]
+            return 4 * n - sum(3 * m.numel() - 4 * sc.numel() for m, q, sc in fams if q is not None)
         return 4 * n - 2 * half
 
     def c_struct(self):
@@ -706,7 +831,7 @@ class DecodeEngine:
     def __init__(self, arena: LMWeightsArena, n_utt: int, use_cfg: bool, max_seq: int, max_steps: int, debug_logits: bool = False,
                  pool_pages: Optional[int] = None, page_order: Optional[Sequence[int]] = None, pair_mode: int = 0,
                  stream_w16: Optional[bool] = None, stream_wt16: Optional[bool] = None, stream_wt32: Optional[bool] = None,
-                 kv_dtype: Optional[str] = None, share_prompt: Optional[bool] = None):
+                 kv_dtype: Optional[str] = None, share_prompt: Optional[bool] = None, stream_w8: Optional[bool] = None):
         """max_seq: longest sequence (text + audio positions) any ONE row may reach; pool_pages: physical KV pages shared by all
         rows (default rows x pages-per-row, the no-sharing worst case; a batch of short and long utterances needs only the sum
         of their own page counts). pair_mode (2-row engines; include/ssrhip.h ssrhip_lm_buffers): 0 = pair launches if this engine
@@ -717,6 +842,10 @@ class DecodeEngine:
         None = on when the arena is bf16, the engine has 5..16 rows and `SSRHIP_GEMVM_W16` (read here; unset = WT16_DEFAULT) does not
         start with '0'. stream_wt32: the same for the 17..32-row two-panel step (ssrhip_lm_set_wt32, the same SSRHIP_WT16_INDEX copies); None =
         on when the arena is bf16, the engine has 17..32 rows and `SSRHIP_GEMVM_W16` (unset = WT32_DEFAULT) does not start with '0'.
+        An e4m3 arena is bf16-valued: at 5..32 rows it takes stream_wt16 / stream_wt32 under the same switches. stream_w8: the <= 4-row decode
+        step streams the arena's packed e4m3 codes and scales (include/ssrhip.h ssrhip_lm_set_w8; needs an e4m3 arena and <= 4 rows, steps
+        unpaired); None = on when the arena is e4m3, the engine has <= 4 rows and `SSRHIP_GEMV_W8` (read here) does not start with '0'; off,
+        such an engine streams its fp32 masters and may pair. stream_w8=True with stream_w16=True is a ValueError.
         kv_dtype "bf16" (5..32 rows, at most KV16_MAX_PAGES pages per row; ValueError otherwise): the paged pool holds 2-byte entries —
         every K / V value rounded to bf16 by whichever path writes it (the step's append, every prefill), widened exactly by every attention;
         q, scores, softmax and outputs stay fp32 (include/ssrhip.h ssrhip_lm_set_kv16). None = "fp32". Independent of the weight stream.
@@ -735,8 +864,13 @@ class DecodeEngine:
         if self.B not in (1, 2, 4) and not (5 <= self.B <= MAX_ROWS):
             raise ValueError(f"rows B={self.B} not supported by this build (1, 2, 4 or 5..{MAX_ROWS})")
         requested = dict(w16=stream_w16, wt16=stream_wt16, wt32=stream_wt32)
+        if stream_w8 and stream_w16:
+            raise ValueError("stream_w8 and stream_w16 are two weight streams of the <= 4-row step; an engine takes one")
+        self.stream_w8 = resolve_w8_stream(self.B, arena.weight_dtype, stream_w8, os.environ)
         for st in W16_STREAMS:                    # the row ranges are disjoint: at most one is on
-            setattr(self, "stream_" + st.name, resolve_w16_stream(st, self.B, arena.weight_dtype, requested[st.name], os.environ))
+            # the 2-byte copies of the matrix-core step serve every bf16-valued arena; the <= 4-row bf16 stream is the bf16 arena's own
+            dtype = "bf16" if (st.lo > 4 and arena.bf16_valued) else arena.weight_dtype
+            setattr(self, "stream_" + st.name, resolve_w16_stream(st, self.B, dtype, requested[st.name], os.environ))
         self._stream = next((st for st in W16_STREAMS if getattr(self, "stream_" + st.name)), None)
         self.max_pages = (max_seq + PAGE - 1) // PAGE
         self.max_seq = self.max_pages * PAGE
@@ -750,6 +884,8 @@ class DecodeEngine:
         arena.ensure_split_planes()               # the prefill GEMMs run on the bf16 matrix cores with exactly split operands
         if self._stream is not None:
             arena._ensure_packed(self._stream.order)   # the step streams packed 2-byte weights (at 5..32 rows in streaming order)
+        if self.stream_w8:
+            arena.ensure_w8_copies()              # the step streams packed 1-byte codes and their scales
         self.max_steps = max_steps
         D, H, L, K = arena.D, arena.H, arena.L, arena.K
         self.hd = D // H
@@ -847,6 +983,9 @@ class DecodeEngine:
         if self._stream is not None:              # before the first step is enqueued or captured; stream_w16 gives the pairing slot back
             rec, setter = self.a._packed_struct(self._stream.order), "ssrhip_lm_set_" + self._stream.name
             _lib.check(getattr(self.lib, setter)(ctx, C.byref(rec)), setter)
+        if self.stream_w8:                        # the fourth packed kind; gives the pairing slot back like stream_w16
+            rec8 = self.a.w8_struct()
+            _lib.check(self.lib.ssrhip_lm_set_w8(ctx, C.byref(rec8)), "ssrhip_lm_set_w8")
         if self.kv_dtype == "bf16":               # the pool's entry type travels with the pool (also for the two-phase admission's prefill)
             _lib.check(self.lib.ssrhip_lm_set_kv16(ctx, 1), "ssrhip_lm_set_kv16")
         if self.share_prompt:                     # the two arrays' pointers travel with the captured step
@@ -884,6 +1023,12 @@ class DecodeEngine:
         """GEMV launches of the last enqueued decode step that ran a bf16-stream kernel (4 * layers + 2 when every family qualifies;
         0 for an engine that streams fp32 weights or has not stepped yet)."""
         return self._launches_per_step("w16")
+
+    @property
+    def w8_launches_per_step(self) -> int:
+        """GEMV launches of the last enqueued decode step that ran an e4m3-stream kernel (4 * layers + 2 when every family qualifies; 0 for
+        an engine that streams other weights or has not stepped yet)."""
+        return self._launches_per_step("w8")
 
     @property
     def wt16_launches_per_step(self) -> int:

@@ -53,9 +53,11 @@ EXTRA_FLAGS = [
     ("--mask_end", dict(type=float, default=None, help="edit span end in seconds (speech editing)")),
     ("--mask_spans", dict(type=str, default=None, help="speech editing with up to max_n_spans (3) edits: 'a-b,c-d[,e-f]' in seconds — what the "
                                                        "reference derives from the word alignment of the edited transcript (one span per edit)")),
-    ("--weight_dtype", dict(type=str, choices=["fp32", "bf16"], default="fp32",
+    ("--weight_dtype", dict(type=str, choices=["fp32", "bf16", "e4m3"], default="fp32",
                             help="bf16: round the decoder's matrices once to bf16 and stream them as 2-byte weights in the decode step "
-                                 "(SSR_Speech.set_weight_dtype); fp32 (default): the checkpoint's weights as they are")),
+                                 "(SSR_Speech.set_weight_dtype); e4m3: quantise them once to OCP e4m3 codes with a power-of-two scale per "
+                                 "output row and stream 1-byte weights (a coarse format: 2.6 %% rms rounding error); fp32 (default): the "
+                                 "checkpoint's weights as they are")),
     ("--kv_dtype", dict(type=str, choices=["fp32", "bf16"], default="fp32",
                         help="bf16: decode engines of 5..32 rows (batched synthesis) keep their KV cache in 2-byte bf16 entries "
                              "(SSR_Speech.set_kv_dtype); fp32 (default): the cache as it is")),

@@ -26,6 +26,9 @@ builds its engine with share_prompt=True (one prefill and one set of prompt page
 `group launches` its counter). Both arms print the rows their first fill prefilled, its device time (the prefill and what the admission enqueues behind it: a sharing
 engine's copies of the prompt's partial page) and the KV pages in use:
   python tools/decode_ab.py --utts 16 --greedy --warmup 180 --steps 100 unshared:share_prompt=0 shared:share_prompt=1
+`weight_dtype=e4m3` builds a third arena (DESIGN.md Part I.18: OCP e4m3 codes with a power-of-two scale per row; 3.3 + 0.82 GB); `w8 launches`
+is the counter of its <= 4-row stream, `SSRHIP_GEMV_W8=0` streams its fp32 masters instead, `SSRHIP_GEMV_W8_DEPTH` picks the ring:
+  python tools/decode_ab.py --reps 4 fp32_paired: bf16_w16:weight_dtype=bf16 e4m3_masters:weight_dtype=e4m3,SSRHIP_GEMV_W8=0 e4m3_w8:weight_dtype=e4m3
 """
 import argparse
 import dataclasses
@@ -116,6 +119,7 @@ for rep in range(a.reps):
         r = res[name]
         for st in W16_STREAMS:
             r[st.name] = getattr(eng, st.name + "_launches_per_step")
+        r["w8"] = eng.w8_launches_per_step
         r["kv16"] = eng.kv16_launches_per_step
         r["group"] = eng.group_launches_per_step
         r["pages"] = eng.pages.n_pages - eng.pages.n_free
@@ -140,4 +144,4 @@ for name, knobs in variants:
     print(f"{name:14s} {U:2d} utts x CFG = {2 * U:2d} rows  tok/s {4 * U / (statistics.median(r['ms']) * 1e-3):9.1f}  "
           f"ms/step min {min(r['ms']):.4f} med {statistics.median(r['ms']):.4f}  all {' '.join(f'{v:.4f}' for v in r['ms'])} | "
           f"gemv {min(r['gemv']):.3f} x {r['launches']['gemv']} attn {min(r['attn']):.3f} x {r['launches']['attn']} "
-          f"sample {min(r['sample']):.3f} x {r['launches']['sample']} us{same}   [{dtype_of[name]}, kv {kv_of[name]}, {' + '.join(f'{r[st.name]} {st.name}' for st in W16_STREAMS)} + {r['kv16']} kv16 + {r['group']} group launches; first fill {r['prefill_rows']} rows in {min(r['prefill_ms']):.2f} ms, {r['pages']} KV pages in use; share_prompt={share_of[name]}; {' '.join(f'{k}={v}' for k, v in knobs.items()) or 'defaults'}]")
+          f"sample {min(r['sample']):.3f} x {r['launches']['sample']} us{same}   [{dtype_of[name]}, kv {kv_of[name]}, {' + '.join(f'{r[st.name]} {st.name}' for st in W16_STREAMS)} + {r['w8']} w8 + {r['kv16']} kv16 + {r['group']} group launches; first fill {r['prefill_rows']} rows in {min(r['prefill_ms']):.2f} ms, {r['pages']} KV pages in use; share_prompt={share_of[name]}; {' '.join(f'{k}={v}' for k, v in knobs.items()) or 'defaults'}]")

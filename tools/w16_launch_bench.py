@@ -14,6 +14,11 @@ w_tiled) against the packed bf16 streaming-order copy (`ssrhip_gemv_wt16`) with 
 through `ssrhip_gemv_wt32`, two panels of tiled activations; beside the byte floors it prints the matrix-core time of the launch,
 `2 * rows_padded * N * K flop / 157.3 TFLOP/s` (rows_padded = 32: both panels are multiplied whole).
     python tools/w16_launch_bench.py --rows 32 --out profiles/wt32_launch_bench_rows32.json
+`--stream w8` (1, 2 or 4 rows; DESIGN.md Part I.18) measures the e4m3 weight stream (`ssrhip_gemv_w8`: 1-byte codes and a power-of-two
+scale per row) in the same process: the fp32 launch on the masters codes * scale, the bf16 stream on the same (bf16-representable)
+masters, and the e4m3 stream with the straight-line form's ring at 2, 4 and every unit (`SSRHIP_GEMV_W8_DEPTH` = 2 | 4 | 8, set by the
+tool per arm) and with the generic form only (0); floor of the 1-byte launch = 2.6 us + (codes + scales) / 7.3 TB/s.
+    python tools/w16_launch_bench.py --stream w8 --rows 2 --out profiles/w8_launch_bench_rows2.json
 """
 import argparse
 import ctypes as C
@@ -27,7 +32,7 @@ import torch  # noqa: E402
 
 import ssr_speech_amd  # noqa: E402,F401
 from ssr_speech_amd import _lib  # noqa: E402
-from ssr_speech_amd.engine import PACKED_ORDERS, W16_STREAMS, to_streaming_order  # noqa: E402
+from ssr_speech_amd.engine import PACKED_ORDERS, W16_STREAMS, e4m3_master, quantize_e4m3, to_streaming_order, to_w8_order  # noqa: E402
 
 # name, G, N, K, prologue, activation, epilogue: the six launches of the 830M step
 SHAPES = [
@@ -47,14 +52,19 @@ def main(argv=None):
     ap.add_argument("--chain", type=int, default=16)
     ap.add_argument("--replays", type=int, default=30)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--stream", default="w16", choices=["w16", "w8"], help="w16: the bf16 stream of --rows (default); w8: the e4m3 stream (<= 4 rows)")
     opt = ap.parse_args(argv)
+    if opt.stream == "w8" and opt.rows > 4:
+        ap.error("--stream w8 exists for 1, 2 or 4 rows")
+    w8 = opt.stream == "w8"
+    W8_DEPTHS = {"w8_depth2": "2", "w8_depth4": "4", "w8_depth8": "8", "w8_generic": "0"}
     L = _lib.lib()
     B, dev = opt.rows, torch.device("cuda")
     g = torch.Generator(device="cuda").manual_seed(1)
     rows = []
     st = next(s for s in W16_STREAMS if s.lo <= B <= s.hi)        # the bf16 stream of these rows
     mc = st.order == "wt16"                                       # the matrix-core step: tiled activations, streaming-order weights
-    forms = ("fp32", st.name) + (("wt16_depth16",) if st.name == "wt16" else ())
+    forms = ("fp32", st.name) + (("wt16_depth16",) if st.name == "wt16" else ()) + (tuple(W8_DEPTHS) if w8 else ())
     to_packed, gemv_packed = PACKED_ORDERS[st.order][0], getattr(L, "ssrhip_gemv_" + st.name)
     xrows = 32 if B > 16 else 16 if mc else B                     # (tiled: 16 columns per panel, any values)
     for name, G, N, K, pro, act, epi in SHAPES:
@@ -62,6 +72,11 @@ def main(argv=None):
             pro = _lib.PRO_NONE                                   # at 5..32 rows the split-KV merge is a launch of its own
         ny = K if epi == _lib.EPI_QKV_APPEND else G * N
         masters = [(torch.randn(G, N, K, device=dev, generator=g) / K ** 0.5).to(torch.bfloat16).float() for _ in range(opt.chain)]
+        if w8:                                                    # masters = codes * scale: bf16-representable, so the bf16 arm streams the same values
+            quant = [quantize_e4m3(m) for m in masters]
+            masters = [e4m3_master(q, sc) for q, sc in quant]
+            packed8, scales = [to_w8_order(q) for q, _ in quant], [sc.contiguous() for _, sc in quant]
+            del quant
         packed = [to_packed(m) for m in masters]
         if mc:
             masters = [to_streaming_order(m) for m in masters]
@@ -97,12 +112,19 @@ def main(argv=None):
                 os.environ["SSRHIP_GEMVM_W16_DEPTH"] = "16"           # read at every launch, i.e. while the chain is captured
             else:
                 os.environ.pop("SSRHIP_GEMVM_W16_DEPTH", None)
+            if form in W8_DEPTHS:
+                os.environ["SSRHIP_GEMV_W8_DEPTH"] = W8_DEPTHS[form]  # read at every launch too
+            else:
+                os.environ.pop("SSRHIP_GEMV_W8_DEPTH", None)
 
             def chain():
                 for i in range(opt.chain):
                     a = args_of(i)
                     if form == "fp32":
                         _lib.check(L.ssrhip_gemv(C.byref(a), _lib.stream_ptr()))
+                    elif form in W8_DEPTHS:
+                        rc = L.ssrhip_gemv_w8(C.byref(a), packed8[i].data_ptr(), scales[i].data_ptr(), _lib.stream_ptr())
+                        assert rc == 0, (name, rc, L.ssrhip_last_error())
                     else:
                         rc = gemv_packed(C.byref(a), packed[i].data_ptr(), _lib.stream_ptr())
                         assert rc == 0, (name, rc, L.ssrhip_last_error())
@@ -130,18 +152,23 @@ def main(argv=None):
         floor = lambda nbytes: 2.6 + nbytes / 7.3e6                # us: 7.3 TB/s = 7.3e6 bytes per us
         nw = G * N * K
         os.environ.pop("SSRHIP_GEMVM_W16_DEPTH", None)
+        os.environ.pop("SSRHIP_GEMV_W8_DEPTH", None)
         row = dict(shape=name, G=G, N=N, K=K, rows=B, fp32_us=round(us["fp32"], 2), fp32_floor_us=round(floor(4 * nw), 2),
                    fp32_TBps=round(4 * nw / us["fp32"] / 1e6, 2), w16_floor_us=round(floor(2 * nw), 2))
+        if w8:
+            row["w8_floor_us"] = round(floor(nw + 4 * G * N), 2)
         for form in forms[1:]:
             row[form + "_us"] = round(us[form], 2)
-            row[form + "_TBps"] = round(2 * nw / us[form] / 1e6, 2)
+            row[form + "_TBps"] = round(((nw + 4 * G * N) if form in W8_DEPTHS else 2 * nw) / us[form] / 1e6, 2)
         if B > 16:                                               # two panels of fp32 MFMA work: is the launch bound by bytes or by flops?
             row["mfma_us"] = round(2 * 32 * nw / 157.3e6, 2)     # us at 157.3 TFLOP/s = 157.3e6 flop per us
         rows.append(row)
         print(json.dumps(rows[-1]), flush=True)
         del masters, packed
+        if w8:
+            del packed8, scales
         torch.cuda.empty_cache()
-    out = dict(tool="tools/w16_launch_bench.py", chain=opt.chain, replays=opt.replays, depth_knob=os.environ.get("SSRHIP_GEMV_W16_DEPTH", "unset"), shapes=rows)
+    out = dict(tool="tools/w16_launch_bench.py", stream=opt.stream, chain=opt.chain, replays=opt.replays, depth_knob=os.environ.get("SSRHIP_GEMV_W16_DEPTH", "unset"), shapes=rows)
     if opt.out:
         with open(opt.out, "w") as f:
             f.write(json.dumps(out, indent=1) + "\n")

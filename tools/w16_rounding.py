@@ -1,10 +1,12 @@
-"""What rounding the decode step's matrices to bf16 does to the 830M model's outputs, with the synthetic weights (no real checkpoint: this
-characterises the feature, it does not judge quality).
-  * greedy decode of bench.py's config-2 input by an fp32 engine and a bf16 engine side by side: maximum and mean |difference| of the
-    post-edit logits per step, for as long as both have chosen the same tokens (the histories are then identical: teacher-forced by
-    agreement), up to --steps; the step at which the tokens first differ, if they do;
-  * `SSR_Speech.score` loss / top-10 accuracy of both on tools/score_bench.py's batch.
-    python tools/w16_rounding.py [--steps 20] [--utts 16] [--out FILE]"""
+"""What rounding the decode step's matrices to bf16, or quantising them to e4m3 (DESIGN.md Part I.18), does to the 830M model's outputs, with
+the synthetic weights (no real checkpoint: this characterises the feature, it does not judge quality and sets no bar).
+  * greedy decode of bench.py's config-2 input by an fp32 engine and an engine of each `--dtypes` arm side by side: maximum and mean
+    |difference| of the post-edit logits per step, for as long as both have chosen the same tokens (the histories are then identical:
+    teacher-forced by agreement), up to --steps; the step at which the tokens first differ, if they do, and how many of the --steps
+    steps chose the same tokens as fp32 (behind the first difference the histories differ too);
+  * `SSR_Speech.score` loss (summed and per token) / top-10 accuracy of every arm on tools/score_bench.py's batch.
+The result has one entry per arm, under the arm's name.
+    python tools/w16_rounding.py [--steps 20] [--utts 16] [--dtypes bf16,e4m3] [--out FILE]"""
 import argparse
 import json
 import os
@@ -29,7 +31,9 @@ def main(argv=None):
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--utts", type=int, default=16)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--dtypes", default="bf16,e4m3", help="the arms compared with fp32, comma separated")
     opt = ap.parse_args(argv)
+    arms = tuple(d for d in opt.dtypes.split(",") if d)
     dev = torch.device("cuda", 0)
     args = W.lm_args_830m()
     sd = W.lm_state_dict(args, seed=0, device=dev)
@@ -39,7 +43,7 @@ def main(argv=None):
     kn = DecodeKnobs(top_k=1, top_p=1.0, temperature=1.0, stop_repetition=2, cfg_coef=1.5, cfg_stride=5, use_cfg=True, text_len=L,
                      n_spans=num_task, seed=2024)
     trace = {}
-    for dt in ("fp32", "bf16"):
+    for dt in ("fp32",) + arms:
         arena = LMWeightsArena(args, sd, dev, weight_dtype=dt)
         eng = DecodeEngine(arena, 1, True, 1024, 256, debug_logits=True)
         eng.start([x[0].numpy(), unc[0].numpy()], [cated], [kn])
@@ -52,25 +56,30 @@ def main(argv=None):
         eng.close()
         del eng, arena
         torch.cuda.empty_cache()
-    (l32, t32), (l16, t16) = trace["fp32"], trace["bf16"]
-    agree = 0
-    while agree < opt.steps and np.array_equal(t32[agree], t16[agree]):
-        agree += 1
-    n_cmp = min(agree + 1, opt.steps)                            # the step of the first disagreement still saw the same history
-    fin = torch.isfinite(l32[:n_cmp]) & torch.isfinite(l16[:n_cmp])
-    d = (l32[:n_cmp] - l16[:n_cmp]).abs()[fin]
-    out = dict(tool="tools/w16_rounding.py", steps=opt.steps, steps_with_identical_history=n_cmp, first_token_difference_at_step=(agree if agree < opt.steps else None),
-               logit_abs_diff_max=float(d.max()), logit_abs_diff_mean=float(d.mean()), logit_abs_mean=float(l32[:n_cmp][fin].abs().mean()))
+    l32, t32 = trace["fp32"]
+    out = dict(tool="tools/w16_rounding.py", steps=opt.steps)
+    for dt in arms:
+        l16, t16 = trace[dt]
+        agree = 0
+        while agree < opt.steps and np.array_equal(t32[agree], t16[agree]):
+            agree += 1
+        n_cmp = min(agree + 1, opt.steps)                        # the step of the first disagreement still saw the same history
+        fin = torch.isfinite(l32[:n_cmp]) & torch.isfinite(l16[:n_cmp])
+        d = (l32[:n_cmp] - l16[:n_cmp]).abs()[fin]
+        out[dt] = dict(steps_with_identical_history=n_cmp, first_token_difference_at_step=(agree if agree < opt.steps else None),
+                       steps_with_the_tokens_of_fp32=sum(bool(np.array_equal(t32[s], t16[s])) for s in range(opt.steps)),
+                       logit_abs_diff_max=float(d.max()), logit_abs_diff_mean=float(d.mean()), logit_abs_mean=float(l32[:n_cmp][fin].abs().mean()))
     from score_bench import make_batch  # noqa: E402
     m = SSR_Speech(args)
     m.load_state_dict({k: v.cpu() for k, v in sd.items()})
     del sd
     m = m.to(dev).eval()
     batch = make_batch(m.args, opt.utts)
-    for dt in ("fp32", "bf16"):
+    for dt in ("fp32",) + arms:
         m.set_weight_dtype(dt)
         r = m.score(batch)
-        out[f"score_{dt}"] = dict(loss=float(r["loss"]), top10acc=float(r["top10acc"]), ntoken=float(r["effective_ntoken"]))
+        out[f"score_{dt}"] = dict(loss=float(r["loss"]), loss_per_token=float(r["loss"]) / float(r["effective_ntoken"]), top10acc=float(r["top10acc"]),
+                                  ntoken=float(r["effective_ntoken"]))
     line = json.dumps(out)
     print(line)
     if opt.out:
