@@ -198,6 +198,21 @@ int ssrhip_gemv_pair_applicable(const ssrhip_gemv_args* a, const ssrhip_gemv_arg
 int ssrhip_gemv_pair(const ssrhip_gemv_args* a, const ssrhip_gemv_args* b, void* ws, int32_t buf, int32_t buf_next, ssrhip_stream_t stream);
 int ssrhip_gemv_pair_status(const void* ws, ssrhip_stream_t stream);
 
+/* ssrhip_gemv_pair(a, b, ...) streaming the PACKED bf16 copies `Wa16` / `Wb16` (SSRHIP_W16_INDEX) of a->W / b->W instead of the masters
+ * (csrc/gemv_pair_w16.hip w16_pair_kernel / w16_pair_merge_kernel; DESIGN.md Part I.19). The hand-off is ssrhip_gemv_pair's own: the same
+ * barriers, edge role, granules, workspace (SSRHIP_PAIR_WS_BYTES), buffer cycle (ssrhip_pair_buffer) and give-up flag
+ * (ssrhip_gemv_pair_status); only the bytes the streaming waves read change. a->W / b->W must hold exactly the values the copies store
+ * (ssrhip_gemv_w16); the result is then BIT-IDENTICAL to ssrhip_gemv_w16(a, Wa16) followed by ssrhip_gemv_w16(b, Wb16), and to
+ * ssrhip_gemv_pair(a, b) on the masters.
+ *   returns 0 = launched, 1 = does not qualify and NOTHING was launched, < 0 = contract error (a null pointer, granule buffers outside
+ *   0..2 or equal, EPI_QKV_APPEND16); the answer comes before any HIP call.
+ *   Qualifies iff ssrhip_gemv_pair_applicable(a, b) (shapes, >= 256 CUs, no CU mask, SSRHIP_GEMV_PAIR = 0 / 1 / 2 as there) AND
+ *   ssrhip_gemv_w16_applicable(a) and (b) (SSRHIP_GEMV_SEG=0 turns it off) AND the occupancy calculator places at least one workgroup of
+ *   every bf16 pair kernel on a CU (asked once per process). SSRHIP_GEMV_PAIR_EARLY acts as on ssrhip_gemv_pair. */
+int ssrhip_gemv_pair_w16(const ssrhip_gemv_args* a, const ssrhip_gemv_args* b, const uint16_t* Wa16, const uint16_t* Wb16, void* ws,
+                         int32_t buf, int32_t buf_next, ssrhip_stream_t stream);
+int ssrhip_gemv_pair_w16_applicable(const ssrhip_gemv_args* a, const ssrhip_gemv_args* b);
+
 /* ------------------------------------------------------------------------------------------------
  * Single-query attention over the paged cache, split over pages (one workgroup per page):
  * replaces F.scaled_dot_product_attention at activation.py:634 for tgt_len==1 (and, row by row,
@@ -564,11 +579,24 @@ typedef struct ssrhip_lm_w16 {
 /* Hand the engine the packed copies: from now on every GEMV launch of its decode step whose family has one and whose shape qualifies
  * (ssrhip_gemv_w16) streams 2-byte weights; the others run ssrhip_gemv on the masters. Same tokens, bit for bit, as the same engine without
  * this call. To be called before the first decode step is enqueued or captured; refused (< 0) afterwards and for engines of more than 4
- * rows. The pair launches read fp32 weights: an engine that holds its device's pairing slot gives it back and steps unpaired
- * (ssrhip_lm_pairing then reports 0 and names the bf16 stream). Prefill and scoring read the masters and are not affected. */
+ * rows. The default pair launches read fp32 weights: an engine that holds its device's pairing slot gives it back and steps unpaired
+ * (ssrhip_lm_pairing then reports 0 and names the bf16 stream) unless ssrhip_lm_set_w16_pair, below, opts in to the pair launches over the
+ * packed copies. Prefill and scoring read the masters and are not affected. */
 int ssrhip_lm_set_w16(ssrhip_lm* lm, const ssrhip_lm_w16* w16);
 /* how many GEMV launches of the last enqueued (or captured) decode step ran a bf16-stream kernel (4 * n_layer + 2 when every family qualifies) */
 int ssrhip_lm_w16_launches(const ssrhip_lm* lm);
+
+/* Opt-in: pair launches over the bf16 weight stream (ssrhip_gemv_pair_w16). Accepted only on a 2-row engine that has ssrhip_lm_set_w16
+ * set, before the step is captured (< 0 otherwise). on = 1 repeats ssrhip_lm_create's pairing decision for this engine: pair_mode 1
+ * refuses, the step's own descriptors are put to ssrhip_gemv_pair_w16_applicable, the device's pairing slot is taken unless pair_mode is 2,
+ * the workspace is allocated and zeroed. An engine that cannot pair returns 0 all the same and steps unpaired (ssrhip_lm_pairing says why);
+ * one that can reports ssrhip_lm_pairing = 1 with a text that names the bf16 pair launches. A pair whose two matrices do not both have
+ * packed copies runs as two single launches. on = 0 gives slot and workspace back. Same tokens, bit for bit, either way. */
+int ssrhip_lm_set_w16_pair(ssrhip_lm* lm, int on);
+/* pair launches of the last enqueued step that ran a w16_pair* kernel (2 * n_layer when every family has a packed copy; ssrhip_lm_w16_launches
+ * keeps counting the SINGLE bf16 launches: then 2, layer 0's QKV and the second head Linear where it has a copy); 0 for other engines */
+int ssrhip_lm_w16_pair_launches(const ssrhip_lm* lm);
+
 /* The opt-in e4m3 weight stream of the <= 4-row decode step: packed codes (SSRHIP_W8_INDEX) and per-row scales of the six matrix
  * families, device pointers; the per-layer fields are HOST arrays of n_layer entries (copied by ssrhip_lm_set_w8). Codes and scales of a
  * family come together; a NULL pair means that family streams its fp32 master. The masters in ssrhip_lm_weights must hold code * scale

@@ -94,7 +94,7 @@ template <int B> struct SegCS { static constexpr int v = (B <= 2) ? 6 : 2; };   
 // ---- device pieces of the segment kernels. Every kernel calls them at the program point where its own copy used to stand: the order of
 // the loads against the weight requests is part of the tuning. Each was taken over only where hipcc's registers, memory
 // operations and wait counts stayed as they were (profiles/seg_gemv_refactor_ab.md); the split-KV merge prologue did not pass in any
-// form and stays written out in its three kernels (gemv_seg_kernel, gemv_pair_merge_kernel, w16_seg_kernel).
+// form and stays written out in its four kernels (gemv_seg_kernel, gemv_pair_merge_kernel, w16_seg_kernel, w16_pair_merge_kernel).
 
 // bias / residual of the (row n, batch row b) a thread finalises: the wave's OLDEST loads (gemv_seg_kernel explains why)
 __device__ __forceinline__ RowEpi seg_epi_fetch(const ssrhip_gemv_args& a, int g, int n, int b) {

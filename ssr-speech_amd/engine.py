@@ -222,6 +222,30 @@ def resolve_w16_stream(st: W16Stream, rows: int, weight_dtype: str, requested: O
     return True
 
 
+# What an unset SSRHIP_GEMV_W16_PAIR means for a 2-row engine that streams w16 (DecodeEngine pair_w16=None): "1" = its step runs the pair
+# launches over the packed copies (include/ssrhip.h ssrhip_lm_set_w16_pair), "0" = it steps unpaired. DESIGN.md Part I.19.
+W16_PAIR_DEFAULT = "0"
+
+
+def resolve_w16_pair(rows: int, stream_w16: bool, pair_mode: int, requested: Optional[bool], env) -> bool:
+    """Does an engine of `rows` rows ask for pair launches over its bf16 weight stream (DecodeEngine pair_w16)? requested None: on iff the
+    engine has 2 rows, streams w16, pair_mode is not 1 and `env["SSRHIP_GEMV_W16_PAIR"]` (unset: W16_PAIR_DEFAULT) does not start with '0'.
+    requested True: ValueError at another row count (named first), then without stream_w16, then with pair_mode 1. Whether the engine then
+    GETS to pair (device, pairing slot) is the library's decision (`DecodeEngine.pairing`). `env` is a mapping like os.environ; nothing
+    else is read."""
+    if requested is None:
+        return rows == 2 and bool(stream_w16) and pair_mode != 1 and env.get("SSRHIP_GEMV_W16_PAIR", W16_PAIR_DEFAULT)[:1] != "0"
+    if not requested:
+        return False
+    if rows != 2:
+        raise ValueError(f"pair_w16: pair launches exist for the 2-row decode step only (this engine has {rows} rows)")
+    if not stream_w16:
+        raise ValueError("pair_w16 needs an engine that streams bf16 weights (stream_w16)")
+    if pair_mode == 1:
+        raise ValueError("pair_w16 with pair_mode=1: the caller switched pair launches off")
+    return True
+
+
 KV_DTYPES = ("fp32", "bf16")
 KV16_MAX_PAGES = 256          # pages per row the fused attention walk takes (csrc/attn.hip ATTN_ROWS_MAX_PAGES)
 
@@ -831,7 +855,8 @@ class DecodeEngine:
     def __init__(self, arena: LMWeightsArena, n_utt: int, use_cfg: bool, max_seq: int, max_steps: int, debug_logits: bool = False,
                  pool_pages: Optional[int] = None, page_order: Optional[Sequence[int]] = None, pair_mode: int = 0,
                  stream_w16: Optional[bool] = None, stream_wt16: Optional[bool] = None, stream_wt32: Optional[bool] = None,
-                 kv_dtype: Optional[str] = None, share_prompt: Optional[bool] = None, stream_w8: Optional[bool] = None):
+                 kv_dtype: Optional[str] = None, share_prompt: Optional[bool] = None, stream_w8: Optional[bool] = None,
+                 pair_w16: Optional[bool] = None):
         """max_seq: longest sequence (text + audio positions) any ONE row may reach; pool_pages: physical KV pages shared by all
         rows (default rows x pages-per-row, the no-sharing worst case; a batch of short and long utterances needs only the sum
         of their own page counts). pair_mode (2-row engines; include/ssrhip.h ssrhip_lm_buffers): 0 = pair launches if this engine
@@ -846,6 +871,9 @@ class DecodeEngine:
         step streams the arena's packed e4m3 codes and scales (include/ssrhip.h ssrhip_lm_set_w8; needs an e4m3 arena and <= 4 rows, steps
         unpaired); None = on when the arena is e4m3, the engine has <= 4 rows and `SSRHIP_GEMV_W8` (read here) does not start with '0'; off,
         such an engine streams its fp32 masters and may pair. stream_w8=True with stream_w16=True is a ValueError.
+        pair_w16 (2-row engines that stream w16; `resolve_w16_pair`): the step runs the pair launches over the packed copies
+        (include/ssrhip.h ssrhip_lm_set_w16_pair) if the library lets this engine pair (`pairing`, `pairing_why`); None = on when
+        `SSRHIP_GEMV_W16_PAIR` (read here; unset = W16_PAIR_DEFAULT) does not start with '0'. Same tokens, bit for bit, either way.
         kv_dtype "bf16" (5..32 rows, at most KV16_MAX_PAGES pages per row; ValueError otherwise): the paged pool holds 2-byte entries —
         every K / V value rounded to bf16 by whichever path writes it (the step's append, every prefill), widened exactly by every attention;
         q, scores, softmax and outputs stay fp32 (include/ssrhip.h ssrhip_lm_set_kv16). None = "fp32". Independent of the weight stream.
@@ -949,6 +977,7 @@ class DecodeEngine:
         self._take_weights()
         self._ctx = None
         self.pair_mode = int(pair_mode)
+        self.pair_w16 = resolve_w16_pair(self.B, self.stream_w16, self.pair_mode, pair_w16, os.environ)
         self.pairing = False                      # set by _create_ctx: does this engine's step run the pair launches?
         self.pairing_why = ""
 
@@ -983,6 +1012,8 @@ class DecodeEngine:
         if self._stream is not None:              # before the first step is enqueued or captured; stream_w16 gives the pairing slot back
             rec, setter = self.a._packed_struct(self._stream.order), "ssrhip_lm_set_" + self._stream.name
             _lib.check(getattr(self.lib, setter)(ctx, C.byref(rec)), setter)
+            if self.pair_w16 and self.pair_mode != 1:     # (check_pairs sets pair_mode 1 after a give-up: that engine steps unpaired)
+                _lib.check(self.lib.ssrhip_lm_set_w16_pair(ctx, 1), "ssrhip_lm_set_w16_pair")
         if self.stream_w8:                        # the fourth packed kind; gives the pairing slot back like stream_w16
             rec8 = self.a.w8_struct()
             _lib.check(self.lib.ssrhip_lm_set_w8(ctx, C.byref(rec8)), "ssrhip_lm_set_w8")
@@ -1023,6 +1054,12 @@ class DecodeEngine:
         """GEMV launches of the last enqueued decode step that ran a bf16-stream kernel (4 * layers + 2 when every family qualifies;
         0 for an engine that streams fp32 weights or has not stepped yet)."""
         return self._launches_per_step("w16")
+
+    @property
+    def w16_pair_launches_per_step(self) -> int:
+        """Pair launches of the last enqueued decode step that streamed packed bf16 weights (2 * layers when every family has a packed
+        copy; `w16_launches_per_step` then counts the two single launches left). 0 for an engine that does not pair its bf16 stream."""
+        return self._launches_per_step("w16_pair")
 
     @property
     def w8_launches_per_step(self) -> int:
