@@ -213,6 +213,22 @@ int ssrhip_gemv_pair_w16(const ssrhip_gemv_args* a, const ssrhip_gemv_args* b, c
                          int32_t buf, int32_t buf_next, ssrhip_stream_t stream);
 int ssrhip_gemv_pair_w16_applicable(const ssrhip_gemv_args* a, const ssrhip_gemv_args* b);
 
+/* ssrhip_gemv_pair(a, b, ...) streaming the PACKED e4m3 codes `Wa8` / `Wb8` (SSRHIP_W8_INDEX) with the per-row scales `scale_a` [a->N] /
+ * `scale_b` [b->N] (powers of two) instead of the masters (csrc/gemv_pair_w8.hip w8_pair_kernel / w8_pair_merge_kernel; DESIGN.md Part
+ * I.20). The hand-off is ssrhip_gemv_pair's own: the same barriers, edge role, granules, workspace (SSRHIP_PAIR_WS_BYTES), buffer cycle
+ * (ssrhip_pair_buffer) and give-up flag (ssrhip_gemv_pair_status); only the bytes the streaming waves read change, and every partial sum
+ * is multiplied by its row's scale where it is parked. a->W / b->W must hold exactly code * scale (ssrhip_gemv_w8); the result is then
+ * BIT-IDENTICAL to ssrhip_gemv_w8(a, Wa8, scale_a) followed by ssrhip_gemv_w8(b, Wb8, scale_b), and to ssrhip_gemv_pair(a, b) on the
+ * masters (the caveat of ssrhip_gemv_w8 about subnormal partial sums applies).
+ *   returns 0 = launched, 1 = does not qualify and NOTHING was launched, < 0 = contract error (a null pointer, granule buffers outside
+ *   0..2 or equal, EPI_QKV_APPEND16); the answer comes before any HIP call.
+ *   Qualifies iff ssrhip_gemv_pair_applicable(a, b) (shapes, >= 256 CUs, no CU mask, SSRHIP_GEMV_PAIR = 0 / 1 / 2 as there) AND
+ *   ssrhip_gemv_w8_applicable(a) and (b) (SSRHIP_GEMV_SEG=0 turns it off) AND the occupancy calculator places at least one workgroup of
+ *   every e4m3 pair kernel on a CU (asked once per process). SSRHIP_GEMV_PAIR_EARLY acts as on ssrhip_gemv_pair. */
+int ssrhip_gemv_pair_w8(const ssrhip_gemv_args* a, const ssrhip_gemv_args* b, const uint8_t* Wa8, const float* scale_a, const uint8_t* Wb8,
+                        const float* scale_b, void* ws, int32_t buf, int32_t buf_next, ssrhip_stream_t stream);
+int ssrhip_gemv_pair_w8_applicable(const ssrhip_gemv_args* a, const ssrhip_gemv_args* b);
+
 /* ------------------------------------------------------------------------------------------------
  * Single-query attention over the paged cache, split over pages (one workgroup per page):
  * replaces F.scaled_dot_product_attention at activation.py:634 for tgt_len==1 (and, row by row,
@@ -612,12 +628,24 @@ int ssrhip_lm_w8_sizeof(void);
  * qualifies (ssrhip_gemv_w8) streams 1-byte weights; the others run ssrhip_gemv on the masters. Same tokens, bit for bit, as the same engine
  * without this call. To be called before the first decode step is enqueued or captured; refused (< 0) afterwards, for engines of more than
  * 4 rows, where another packed stream is already set (ssrhip_lm_set_w16 and its kin, and the reverse), and for a family with codes but no
- * scales. The pair launches read fp32 weights: the engine gives its device's pairing slot back and steps unpaired (ssrhip_lm_pairing then
- * reports 0 and names the e4m3 stream). Prefill and scoring read the masters and are not affected. */
+ * scales. The default pair launches read fp32 weights: the engine gives its device's pairing slot back and steps unpaired (ssrhip_lm_pairing
+ * then reports 0 and names the e4m3 stream) unless ssrhip_lm_set_w8_pair, below, opts in to the pair launches over the codes. Prefill and
+ * scoring read the masters and are not affected. */
 int ssrhip_lm_set_w8(ssrhip_lm* lm, const ssrhip_lm_w8* w8);
 /* how many GEMV launches of the last enqueued (or captured) decode step ran a kernel of csrc/gemv_w8.hip (4 * n_layer + 2 when every family
  * qualifies); a counter of its own: the bf16 streams' counters stay 0 for these engines */
 int ssrhip_lm_w8_launches(const ssrhip_lm* lm);
+/* Opt-in: pair launches over the e4m3 weight stream (ssrhip_gemv_pair_w8); ssrhip_lm_set_w16_pair's twin. Accepted only on a 2-row engine
+ * that has ssrhip_lm_set_w8 set, before the step is captured (< 0 otherwise). on = 1 repeats ssrhip_lm_create's pairing decision for this
+ * engine: pair_mode 1 refuses, the step's own descriptors are put to ssrhip_gemv_pair_w8_applicable, the device's pairing slot is taken
+ * unless pair_mode is 2, the workspace is allocated and zeroed. An engine that cannot pair returns 0 all the same and steps unpaired
+ * (ssrhip_lm_pairing says why); one that can reports ssrhip_lm_pairing = 1 with a text that names the e4m3 pair launches. A pair whose two
+ * matrices do not both have codes and scales runs as two single launches. on = 0 gives slot and workspace back (the state
+ * ssrhip_lm_set_w8 left). Same tokens, bit for bit, either way. */
+int ssrhip_lm_set_w8_pair(ssrhip_lm* lm, int on);
+/* pair launches of the last enqueued step that ran a w8_pair* kernel (2 * n_layer when every family has codes; ssrhip_lm_w8_launches keeps
+ * counting the SINGLE e4m3 launches: then 2, layer 0's QKV and the second head Linear); 0 for other engines */
+int ssrhip_lm_w8_pair_launches(const ssrhip_lm* lm);
 /* The same for the 5..16-row decode step: the record's pointers are SSRHIP_WT16_INDEX copies of the six families (NULL field / NULL entry:
  * that family streams the fp32 streaming-order copy of its master). From now on every GEMV launch of the step tries ssrhip_gemv_wt16 first
  * and falls back to ssrhip_gemv; same tokens, bit for bit; the step stays one captured graph. Refused (< 0) for engines of <= 4 rows (they

@@ -67,8 +67,9 @@ struct ssrhip_lm {
   void* pair_ws = nullptr;      // granules of the paired GEMV launches (2-row step; SSRHIP_PAIR_WS_BYTES, owned)
   int pair_dev = -1;            // >= 0: this engine holds the pairing slot of that device (released in ssrhip_lm_destroy)
   char pair_why[200] = "";      // why the step pairs / does not pair (ssrhip_lm_pairing)
-  bool w16_pair = false;        // the pair launches of this engine stream its packed bf16 copies (ssrhip_lm_set_w16_pair; pk_kind == PK_W16)
-  int w16_pair_launches = 0;    // pair launches of the last enqueued step that ran a w16_pair* kernel (ssrhip_lm_w16_pair_launches)
+  bool pk_pair = false;         // the pair launches of this engine stream its packed weights: the bf16 copies (ssrhip_lm_set_w16_pair; pk_kind ==
+                                // PK_W16) or the e4m3 codes and scales (ssrhip_lm_set_w8_pair; PK_W8)
+  int pk_pair_launches = 0;     // pair launches of the last enqueued step that ran a w16_pair* / w8_pair* kernel (ssrhip_lm_{w16,w8}_pair_launches)
   // the bf16 weight stream: an engine has one row count, so one kind (index into PACKED_STREAMS, -1: none) and one record of packed copies
   // of the six families, in that kind's order (SSRHIP_W16_INDEX at <= 4 rows, SSRHIP_WT16_INDEX at 5..32); NULL = that matrix streams fp32
   int pk_kind = -1;
@@ -327,12 +328,14 @@ struct StepShapes {
     return sa;
   }
   // which launches of the 2-row step qualify for the pair forms, and how many pair launches a step then has (0: fewer than 2 -> none)
-  // w16: the question goes to the pair launches over packed bf16 weights (ssrhip_gemv_pair_w16_applicable); which of a step's pairs then
-  // have packed copies of both matrices is enqueue_step's part
-  int pair_plan(bool* qkv, bool* head, bool* ffn1, bool w16 = false) const {
+  // packed_kind PK_W16 / PK_W8: the question goes to the pair launches over packed bf16 weights / e4m3 codes (ssrhip_gemv_pair_w16_applicable,
+  // ssrhip_gemv_pair_w8_applicable), -1: to the fp32 forms; which of a step's pairs then have packed copies of both matrices is
+  // enqueue_step's part
+  int pair_plan(bool* qkv, bool* head, bool* ffn1, int packed_kind = -1) const {
     *qkv = *head = *ffn1 = false;
     if (B != 2) return 0;
-    int (*const applicable)(const ssrhip_gemv_args*, const ssrhip_gemv_args*) = w16 ? ssrhip_gemv_pair_w16_applicable : ssrhip_gemv_pair_applicable;
+    int (*const applicable)(const ssrhip_gemv_args*, const ssrhip_gemv_args*) =
+        packed_kind == PK_W16 ? ssrhip_gemv_pair_w16_applicable : packed_kind == PK_W8 ? ssrhip_gemv_pair_w8_applicable : ssrhip_gemv_pair_applicable;
     const ssrhip_gemv_args fa = ffn2_args(0);
     if (d.n_layer > 1) { const ssrhip_gemv_args qa = qkv_args(1); *qkv = applicable(&fa, &qa) != 0; }
     { const ssrhip_gemv_args ha = head1_args(); *head = applicable(&fa, &ha) != 0; }
@@ -352,19 +355,26 @@ int enqueue_step(ssrhip_lm* lm, hipStream_t s, Timer* tm) {
   // prologue) and FFN1 (gemv_pair_merge_kernel): attention, pair, pair per layer. The pairs of a step use the three granule buffers of
   // lm->pair_ws cyclically: pair i uses buffer i % 3 and resets the buffer of pair (i + 1) % n — closed over the step, so that graph
   // replays (and eager steps) always find their buffer reset by the launch before them; with n % 3 == 1 the last pair takes buffer 1.
-  // An engine that pairs its bf16 stream (ssrhip_lm_set_w16_pair) hands the same pairs to ssrhip_gemv_pair_w16 — those whose TWO matrices
-  // have packed copies; a pair that lacks one runs as two single launches. n_pairs is the count actually launched: the buffer cycle
-  // closes over exactly these.
+  // An engine that pairs its packed stream (ssrhip_lm_set_w16_pair, ssrhip_lm_set_w8_pair) hands the same pairs to the packed entry of its
+  // kind, ssrhip_gemv_pair_w16 or ssrhip_gemv_pair_w8 — those whose TWO matrices have packed copies; a pair that lacks one runs as two
+  // single launches. n_pairs is the count actually launched: the buffer cycle closes over exactly these.
   enum { W16_IN = 0, W16_OUT = 1, W16_FFN1 = 2, W16_FFN2 = 3 };
-  const bool wp = lm->w16_pair && lm->pair_ws && lm->pk_kind == PK_W16;
+  const bool wp = lm->pk_pair && lm->pair_ws && (lm->pk_kind == PK_W16 || lm->pk_kind == PK_W8);
+  const bool wp8 = wp && lm->pk_kind == PK_W8;
   bool pair_qkv = false, pair_head = false, pair_ffn1 = false;
-  int n_pairs = lm->pair_ws ? sh.pair_plan(&pair_qkv, &pair_head, &pair_ffn1, wp) : 0;
-  auto packed = [&](int family, int l) -> const uint16_t* { return lm->pk[family].empty() ? nullptr : lm->pk[family][l]; };
-  auto ffn1_pairs = [&](int l) { return pair_ffn1 && (!wp || (packed(W16_OUT, l) && packed(W16_FFN1, l))); };
+  int n_pairs = lm->pair_ws ? sh.pair_plan(&pair_qkv, &pair_head, &pair_ffn1, wp ? lm->pk_kind : -1) : 0;
+  // what a launch of (family, layer) streams instead of its fp32 master, in the engine's kind
+  auto w16_of = [&](int family, int l) -> PackedRef {
+    if (lm->pk_kind == PK_W8) return lm->pk8[family].empty() ? PackedRef{nullptr, nullptr, nullptr} : PackedRef{nullptr, lm->pk8[family][l], lm->pk8s[family][l]};
+    return PackedRef{lm->pk[family].empty() ? nullptr : lm->pk[family][l], nullptr, nullptr};
+  };
+  const PackedRef pk_h1 = {lm->pk_head1, lm->pk8_head1, lm->pk8s_head1}, pk_h2 = {lm->pk_head2, lm->pk8_head2, lm->pk8s_head2};
+  auto packed = [&](const PackedRef r) { return r.w16 || r.w8; };
+  auto ffn1_pairs = [&](int l) { return pair_ffn1 && (!wp || (packed(w16_of(W16_OUT, l)) && packed(w16_of(W16_FFN1, l)))); };
   auto ffn2_pairs = [&](int l) {
     const bool last = l == d.n_layer - 1;
     if (!(last ? pair_head : pair_qkv)) return false;
-    return !wp || (packed(W16_FFN2, l) && (last ? lm->pk_head1 : packed(W16_IN, l + 1)));
+    return !wp || (packed(w16_of(W16_FFN2, l)) && packed(last ? pk_h1 : w16_of(W16_IN, l + 1)));
   };
   if (wp) {
     n_pairs = 0;
@@ -372,14 +382,16 @@ int enqueue_step(ssrhip_lm* lm, hipStream_t s, Timer* tm) {
     if (n_pairs < 2) { pair_qkv = pair_head = pair_ffn1 = false; n_pairs = 0; }
   }
   int pair_i = 0, n_wp = 0;
-  // the launch (a, b) that pair_plan found applicable, on this pair's granule buffer; wa16 / wb16: the packed copies (wp only)
-  auto pair_call = [&](const ssrhip_gemv_args& ga, const ssrhip_gemv_args& gb, const uint16_t* wa16, const uint16_t* wb16) {
+  // the launch (a, b) that pair_plan found applicable, on this pair's granule buffer; pa / pb: the packed copies (wp only)
+  auto pair_call = [&](const ssrhip_gemv_args& ga, const ssrhip_gemv_args& gb, const PackedRef pa, const PackedRef pb) {
     const int bufi = ssrhip_pair_buffer(pair_i, n_pairs), bufn = ssrhip_pair_buffer((pair_i + 1) % n_pairs, n_pairs);
     pair_i += 1;
     if (wp) {
-      const int rc = ssrhip_gemv_pair_w16(&ga, &gb, wa16, wb16, lm->pair_ws, bufi, bufn, (ssrhip_stream_t)s);
+      const int rc = wp8 ? ssrhip_gemv_pair_w8(&ga, &gb, pa.w8, pa.sc, pb.w8, pb.sc, lm->pair_ws, bufi, bufn, (ssrhip_stream_t)s)
+                         : ssrhip_gemv_pair_w16(&ga, &gb, pa.w16, pb.w16, lm->pair_ws, bufi, bufn, (ssrhip_stream_t)s);
       n_wp += rc == 0;
-      if (rc == 1) ssrhip_set_error("ssrhip_lm_decode: a pair the plan accepted was refused by ssrhip_gemv_pair_w16 (%s)", ssrhip_gemv_pair_w16_why());
+      if (rc == 1) ssrhip_set_error("ssrhip_lm_decode: a pair the plan accepted was refused by %s (%s)", wp8 ? "ssrhip_gemv_pair_w8" : "ssrhip_gemv_pair_w16",
+                                    wp8 ? ssrhip_gemv_pair_w8_why() : ssrhip_gemv_pair_w16_why());
       return rc == 1 ? -1 : rc;
     }
     return ssrhip_gemv_pair(&ga, &gb, lm->pair_ws, bufi, bufn, (ssrhip_stream_t)s);
@@ -395,11 +407,6 @@ int enqueue_step(ssrhip_lm* lm, hipStream_t s, Timer* tm) {
     }
     return ssrhip_gemv(&ga, s);
   };
-  auto w16_of = [&](int family, int l) -> PackedRef {
-    if (lm->pk_kind == PK_W8) return lm->pk8[family].empty() ? PackedRef{nullptr, nullptr, nullptr} : PackedRef{nullptr, lm->pk8[family][l], lm->pk8s[family][l]};
-    return PackedRef{lm->pk[family].empty() ? nullptr : lm->pk[family][l], nullptr, nullptr};
-  };
-  const PackedRef pk_h1 = {lm->pk_head1, lm->pk8_head1, lm->pk8s_head1}, pk_h2 = {lm->pk_head2, lm->pk8_head2, lm->pk8s_head2};
   bool qkv_done = false;                        // this layer's QKV already ran inside the previous layer's pair launch
   // 5..32 rows with enough (row, head) pairs to give every CU one: the fused walk over the pages (no partials, no merge
   // launch); its output goes to b.h (free until FFN1 of this layer) because q is still being read by other workgroups
@@ -448,7 +455,7 @@ int enqueue_step(ssrhip_lm* lm, hipStream_t s, Timer* tm) {
     }
     const ssrhip_gemv_args f1 = sh.ffn1_args(l);
     if (ffn1_pairs(l)) {                          // out-projection + FFN1 as one launch (2 rows)
-      STEP_CALL(CAT_GEMV, pair_call(op, f1, packed(W16_OUT, l), packed(W16_FFN1, l)));
+      STEP_CALL(CAT_GEMV, pair_call(op, f1, w16_of(W16_OUT, l), w16_of(W16_FFN1, l)));
     } else {
       STEP_CALL(CAT_GEMV, gemv_call(op, w16_of(W16_OUT, l)));
       STEP_CALL(CAT_GEMV, gemv_call(f1, w16_of(W16_FFN1, l)));
@@ -458,7 +465,7 @@ int enqueue_step(ssrhip_lm* lm, hipStream_t s, Timer* tm) {
     const ssrhip_gemv_args f2 = sh.ffn2_args(l);
     const bool last = l == d.n_layer - 1;
     if (ffn2_pairs(l)) {
-      STEP_CALL(CAT_GEMV, pair_call(f2, last ? sh.head1_args() : sh.qkv_args(l + 1), packed(W16_FFN2, l), last ? lm->pk_head1 : packed(W16_IN, l + 1)));
+      STEP_CALL(CAT_GEMV, pair_call(f2, last ? sh.head1_args() : sh.qkv_args(l + 1), w16_of(W16_FFN2, l), last ? pk_h1 : w16_of(W16_IN, l + 1)));
       qkv_done = true;                          // (after the last layer: the head MLP's first launch)
     } else {
       STEP_CALL(CAT_GEMV, gemv_call(f2, w16_of(W16_FFN2, l)));
@@ -472,7 +479,7 @@ int enqueue_step(ssrhip_lm* lm, hipStream_t s, Timer* tm) {
   STEP_CALL(CAT_GEMV, gemv_call(h2, pk_h2));
   const ssrhip_sample_args sa = sh.sample_args();
   STEP_CALL(CAT_SAMPLE, ssrhip_sample(&sa, s));
-  if (!tm || tm->only < 0) { lm->pk_launches = n_pk; lm->w16_pair_launches = n_wp; lm->kv16_launches = n_kv16; lm->group_launches = n_group; }   // (a category-timing pass enqueues only part of a step)
+  if (!tm || tm->only < 0) { lm->pk_launches = n_pk; lm->pk_pair_launches = n_wp; lm->kv16_launches = n_kv16; lm->group_launches = n_group; }   // (a category-timing pass enqueues only part of a step)
   return 0;
 }
 
@@ -593,7 +600,7 @@ static int lm_set_packed(ssrhip_lm* lm, const ssrhip_lm_w16* rec, int kind) {
                       // (ssrhip_lm_set_w16_pair may take it again for the pair launches over the packed copies)
     if (lm->pair_ws) { hipFree(lm->pair_ws); lm->pair_ws = nullptr; }
     if (lm->pair_dev >= 0) { pair_slot_release(lm->pair_dev); lm->pair_dev = -1; }
-    lm->w16_pair = false;
+    lm->pk_pair = false;
     snprintf(lm->pair_why, sizeof(lm->pair_why), "this engine streams bf16 weights (%s): its pair launches are an opt-in (ssrhip_lm_set_w16_pair, 2 rows)", ps.setter);
   }
   return 0;
@@ -626,10 +633,12 @@ extern "C" int ssrhip_lm_set_w8(ssrhip_lm* lm, const ssrhip_lm_w8* rec) {
   lm->pk8_head1 = rec->head1_w8; lm->pk8s_head1 = rec->head1_s;
   lm->pk8_head2 = rec->head2_w8; lm->pk8s_head2 = rec->head2_s;
   lm->pk_kind = PK_W8;
-  // the pair launches stream fp32 weights: this engine steps unpaired and gives the device's pairing slot back
+  // the default pair launches stream fp32 weights: this engine steps unpaired and gives the device's pairing slot back
+  // (ssrhip_lm_set_w8_pair may take it again for the pair launches over the codes)
   if (lm->pair_ws) { hipFree(lm->pair_ws); lm->pair_ws = nullptr; }
   if (lm->pair_dev >= 0) { pair_slot_release(lm->pair_dev); lm->pair_dev = -1; }
-  snprintf(lm->pair_why, sizeof(lm->pair_why), "this engine streams e4m3 weights (ssrhip_lm_set_w8): the pair launches exist for fp32 weights only");
+  lm->pk_pair = false;
+  snprintf(lm->pair_why, sizeof(lm->pair_why), "this engine streams e4m3 weights (ssrhip_lm_set_w8): its pair launches are an opt-in (ssrhip_lm_set_w8_pair, 2 rows)");
   return 0;
 }
 extern "C" int ssrhip_lm_w8_launches(const ssrhip_lm* lm) { return lm_packed_launches(lm, PK_W8); }
@@ -681,29 +690,33 @@ extern "C" int ssrhip_lm_group_members(const ssrhip_lm* lm) { return lm && lm->c
 extern "C" int ssrhip_lm_group_launches(const ssrhip_lm* lm) { return lm && lm->chunk_head ? lm->group_launches : 0; }
 extern "C" int ssrhip_lm_w16_launches(const ssrhip_lm* lm) { return lm_packed_launches(lm, PK_W16); }
 
-// Pair launches over the packed bf16 copies (csrc/gemv_pair_w16.hip). on = 1 repeats ssrhip_lm_create's pairing decision for this engine,
-// with the question put to ssrhip_gemv_pair_w16_applicable; on = 0 gives everything back (the state ssrhip_lm_set_w16 left).
-extern "C" int ssrhip_lm_set_w16_pair(ssrhip_lm* lm, int on) {
-  SSR_REQUIRE(lm, "ssrhip_lm_set_w16_pair: null engine");
-  SSR_REQUIRE(!lm->exec, "ssrhip_lm_set_w16_pair: the decode step of this engine is already captured (call it before the first ssrhip_lm_decode)");
-  SSR_REQUIRE(lm->b.B == 2, "ssrhip_lm_set_w16_pair: pair launches exist for the 2-row step only (this engine has %d rows)", lm->b.B);
-  SSR_REQUIRE(lm->pk_kind == PK_W16, "ssrhip_lm_set_w16_pair: this engine does not stream bf16 weights (ssrhip_lm_set_w16 comes first)");
+// Pair launches over the packed weights of the engine's kind: the bf16 copies (csrc/gemv_pair_w16.hip) or the e4m3 codes and scales
+// (csrc/gemv_pair_w8.hip). on = 1 repeats ssrhip_lm_create's pairing decision for this engine, with the question put to the kind's
+// _applicable; on = 0 gives everything back (the state the stream's setter left). One body, the names of the kind in a record.
+struct PackedPair { int kind; const char* setter; const char* stream_setter; const char* fmt; const char* entry; const char* (*why)(); };
+const PackedPair PAIR_W16 = {PK_W16, "ssrhip_lm_set_w16_pair", "ssrhip_lm_set_w16", "bf16", "ssrhip_gemv_pair_w16", ssrhip_gemv_pair_w16_why};
+const PackedPair PAIR_W8 = {PK_W8, "ssrhip_lm_set_w8_pair", "ssrhip_lm_set_w8", "e4m3", "ssrhip_gemv_pair_w8", ssrhip_gemv_pair_w8_why};
+static int lm_set_packed_pair(ssrhip_lm* lm, int on, const PackedPair& pp) {
+  SSR_REQUIRE(lm, "%s: null engine", pp.setter);
+  SSR_REQUIRE(!lm->exec, "%s: the decode step of this engine is already captured (call it before the first ssrhip_lm_decode)", pp.setter);
+  SSR_REQUIRE(lm->b.B == 2, "%s: pair launches exist for the 2-row step only (this engine has %d rows)", pp.setter, lm->b.B);
+  SSR_REQUIRE(lm->pk_kind == pp.kind, "%s: this engine does not stream %s weights (%s comes first)", pp.setter, pp.fmt, pp.stream_setter);
   if (lm->pair_ws) { hipFree(lm->pair_ws); lm->pair_ws = nullptr; }
   if (lm->pair_dev >= 0) { pair_slot_release(lm->pair_dev); lm->pair_dev = -1; }
-  lm->w16_pair = false;
+  lm->pk_pair = false;
   if (!on) {
-    snprintf(lm->pair_why, sizeof(lm->pair_why), "this engine streams bf16 weights (ssrhip_lm_set_w16) and its bf16 pair launches are switched off (ssrhip_lm_set_w16_pair)");
+    snprintf(lm->pair_why, sizeof(lm->pair_why), "this engine streams %s weights (%s) and its %s pair launches are switched off (%s)", pp.fmt, pp.stream_setter, pp.fmt, pp.setter);
     return 0;
   }
   const int pair_mode = lm->b.pair_mode;
   if (pair_mode == 1) { snprintf(lm->pair_why, sizeof(lm->pair_why), "switched off by the caller (pair_mode 1)"); return 0; }
   bool pq, ph, pf;
-  if (StepShapes(lm).pair_plan(&pq, &ph, &pf, true) == 0) { snprintf(lm->pair_why, sizeof(lm->pair_why), "%s", ssrhip_gemv_pair_w16_why()); return 0; }
+  if (StepShapes(lm).pair_plan(&pq, &ph, &pf, pp.kind) == 0) { snprintf(lm->pair_why, sizeof(lm->pair_why), "%s", pp.why()); return 0; }
   if (pair_mode != 2) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) dev = -1;
     if (!pair_slot_acquire(dev, lm->pair_why, sizeof(lm->pair_why))) {
-      fprintf(stderr, "ssrhip: this 2-row decode engine steps WITHOUT bf16 pair launches (same tokens): %s\n", lm->pair_why);
+      fprintf(stderr, "ssrhip: this 2-row decode engine steps WITHOUT %s pair launches (same tokens): %s\n", pp.fmt, lm->pair_why);
       return 0;
     }
     lm->pair_dev = dev;
@@ -711,15 +724,19 @@ extern "C" int ssrhip_lm_set_w16_pair(ssrhip_lm* lm, int on) {
   if (hipMalloc(&lm->pair_ws, SSRHIP_PAIR_WS_BYTES) != hipSuccess || hipMemset(lm->pair_ws, 0, SSRHIP_PAIR_WS_BYTES) != hipSuccess) {
     if (lm->pair_ws) { hipFree(lm->pair_ws); lm->pair_ws = nullptr; }
     if (lm->pair_dev >= 0) { pair_slot_release(lm->pair_dev); lm->pair_dev = -1; }
-    ssrhip_set_error("ssrhip_lm_set_w16_pair: allocating the pair workspace failed");
+    ssrhip_set_error("%s: allocating the pair workspace failed", pp.setter);
     return -1;
   }
-  lm->w16_pair = true;
-  snprintf(lm->pair_why, sizeof(lm->pair_why), pair_mode == 2 ? "bf16 pair launches (ssrhip_gemv_pair_w16), forced on by the caller (pair_mode 2: no slot, no guard)"
-                                                              : "bf16 pair launches (ssrhip_gemv_pair_w16): this engine holds the pairing slot of its device");
+  lm->pk_pair = true;
+  snprintf(lm->pair_why, sizeof(lm->pair_why), pair_mode == 2 ? "%s pair launches (%s), forced on by the caller (pair_mode 2: no slot, no guard)"
+                                                              : "%s pair launches (%s): this engine holds the pairing slot of its device", pp.fmt, pp.entry);
   return 0;
 }
-extern "C" int ssrhip_lm_w16_pair_launches(const ssrhip_lm* lm) { return lm && lm->w16_pair ? lm->w16_pair_launches : 0; }
+static int lm_packed_pair_launches(const ssrhip_lm* lm, int kind) { return lm && lm->pk_pair && lm->pk_kind == kind ? lm->pk_pair_launches : 0; }
+extern "C" int ssrhip_lm_set_w16_pair(ssrhip_lm* lm, int on) { return lm_set_packed_pair(lm, on, PAIR_W16); }
+extern "C" int ssrhip_lm_w16_pair_launches(const ssrhip_lm* lm) { return lm_packed_pair_launches(lm, PK_W16); }
+extern "C" int ssrhip_lm_set_w8_pair(ssrhip_lm* lm, int on) { return lm_set_packed_pair(lm, on, PAIR_W8); }
+extern "C" int ssrhip_lm_w8_pair_launches(const ssrhip_lm* lm) { return lm_packed_pair_launches(lm, PK_W8); }
 extern "C" int ssrhip_lm_wt16_launches(const ssrhip_lm* lm) { return lm_packed_launches(lm, PK_WT16); }
 extern "C" int ssrhip_lm_wt32_launches(const ssrhip_lm* lm) { return lm_packed_launches(lm, PK_WT32); }
 

@@ -246,6 +246,30 @@ def resolve_w16_pair(rows: int, stream_w16: bool, pair_mode: int, requested: Opt
     return True
 
 
+# The same for a 2-row engine that streams w8 (DecodeEngine pair_w8=None) and SSRHIP_GEMV_W8_PAIR: "1" = its step runs the pair launches
+# over the e4m3 codes and scales (include/ssrhip.h ssrhip_lm_set_w8_pair), "0" = it steps unpaired. DESIGN.md Part I.20.
+W8_PAIR_DEFAULT = "0"
+
+
+def resolve_w8_pair(rows: int, stream_w8: bool, pair_mode: int, requested: Optional[bool], env) -> bool:
+    """Does an engine of `rows` rows ask for pair launches over its e4m3 weight stream (DecodeEngine pair_w8)? requested None: on iff the
+    engine has 2 rows, streams w8, pair_mode is not 1 and `env["SSRHIP_GEMV_W8_PAIR"]` (unset: W8_PAIR_DEFAULT) does not start with '0'.
+    requested True: ValueError at another row count (named first), then without stream_w8, then with pair_mode 1. Whether the engine then
+    GETS to pair (device, pairing slot) is the library's decision (`DecodeEngine.pairing`). `env` is a mapping like os.environ; nothing
+    else is read."""
+    if requested is None:
+        return rows == 2 and bool(stream_w8) and pair_mode != 1 and env.get("SSRHIP_GEMV_W8_PAIR", W8_PAIR_DEFAULT)[:1] != "0"
+    if not requested:
+        return False
+    if rows != 2:
+        raise ValueError(f"pair_w8: pair launches exist for the 2-row decode step only (this engine has {rows} rows)")
+    if not stream_w8:
+        raise ValueError("pair_w8 needs an engine that streams e4m3 weights (stream_w8)")
+    if pair_mode == 1:
+        raise ValueError("pair_w8 with pair_mode=1: the caller switched pair launches off")
+    return True
+
+
 KV_DTYPES = ("fp32", "bf16")
 KV16_MAX_PAGES = 256          # pages per row the fused attention walk takes (csrc/attn.hip ATTN_ROWS_MAX_PAGES)
 
@@ -856,7 +880,7 @@ class DecodeEngine:
                  pool_pages: Optional[int] = None, page_order: Optional[Sequence[int]] = None, pair_mode: int = 0,
                  stream_w16: Optional[bool] = None, stream_wt16: Optional[bool] = None, stream_wt32: Optional[bool] = None,
                  kv_dtype: Optional[str] = None, share_prompt: Optional[bool] = None, stream_w8: Optional[bool] = None,
-                 pair_w16: Optional[bool] = None):
+                 pair_w16: Optional[bool] = None, pair_w8: Optional[bool] = None):
         """max_seq: longest sequence (text + audio positions) any ONE row may reach; pool_pages: physical KV pages shared by all
         rows (default rows x pages-per-row, the no-sharing worst case; a batch of short and long utterances needs only the sum
         of their own page counts). pair_mode (2-row engines; include/ssrhip.h ssrhip_lm_buffers): 0 = pair launches if this engine
@@ -869,11 +893,13 @@ class DecodeEngine:
         on when the arena is bf16, the engine has 17..32 rows and `SSRHIP_GEMVM_W16` (unset = WT32_DEFAULT) does not start with '0'.
         An e4m3 arena is bf16-valued: at 5..32 rows it takes stream_wt16 / stream_wt32 under the same switches. stream_w8: the <= 4-row decode
         step streams the arena's packed e4m3 codes and scales (include/ssrhip.h ssrhip_lm_set_w8; needs an e4m3 arena and <= 4 rows, steps
-        unpaired); None = on when the arena is e4m3, the engine has <= 4 rows and `SSRHIP_GEMV_W8` (read here) does not start with '0'; off,
+        unpaired unless pair_w8 opts in); None = on when the arena is e4m3, the engine has <= 4 rows and `SSRHIP_GEMV_W8` (read here) does not start with '0'; off,
         such an engine streams its fp32 masters and may pair. stream_w8=True with stream_w16=True is a ValueError.
         pair_w16 (2-row engines that stream w16; `resolve_w16_pair`): the step runs the pair launches over the packed copies
         (include/ssrhip.h ssrhip_lm_set_w16_pair) if the library lets this engine pair (`pairing`, `pairing_why`); None = on when
         `SSRHIP_GEMV_W16_PAIR` (read here; unset = W16_PAIR_DEFAULT) does not start with '0'. Same tokens, bit for bit, either way.
+        pair_w8 (2-row engines that stream w8; `resolve_w8_pair`): the same over the e4m3 codes and scales (ssrhip_lm_set_w8_pair); None = on
+        when `SSRHIP_GEMV_W8_PAIR` (read here; unset = W8_PAIR_DEFAULT) does not start with '0'. Same tokens, bit for bit, either way.
         kv_dtype "bf16" (5..32 rows, at most KV16_MAX_PAGES pages per row; ValueError otherwise): the paged pool holds 2-byte entries —
         every K / V value rounded to bf16 by whichever path writes it (the step's append, every prefill), widened exactly by every attention;
         q, scores, softmax and outputs stay fp32 (include/ssrhip.h ssrhip_lm_set_kv16). None = "fp32". Independent of the weight stream.
@@ -978,6 +1004,7 @@ class DecodeEngine:
         self._ctx = None
         self.pair_mode = int(pair_mode)
         self.pair_w16 = resolve_w16_pair(self.B, self.stream_w16, self.pair_mode, pair_w16, os.environ)
+        self.pair_w8 = resolve_w8_pair(self.B, self.stream_w8, self.pair_mode, pair_w8, os.environ)
         self.pairing = False                      # set by _create_ctx: does this engine's step run the pair launches?
         self.pairing_why = ""
 
@@ -1017,6 +1044,8 @@ class DecodeEngine:
         if self.stream_w8:                        # the fourth packed kind; gives the pairing slot back like stream_w16
             rec8 = self.a.w8_struct()
             _lib.check(self.lib.ssrhip_lm_set_w8(ctx, C.byref(rec8)), "ssrhip_lm_set_w8")
+            if self.pair_w8 and self.pair_mode != 1:      # (as for pair_w16: after a give-up the engine steps unpaired)
+                _lib.check(self.lib.ssrhip_lm_set_w8_pair(ctx, 1), "ssrhip_lm_set_w8_pair")
         if self.kv_dtype == "bf16":               # the pool's entry type travels with the pool (also for the two-phase admission's prefill)
             _lib.check(self.lib.ssrhip_lm_set_kv16(ctx, 1), "ssrhip_lm_set_kv16")
         if self.share_prompt:                     # the two arrays' pointers travel with the captured step
@@ -1066,6 +1095,12 @@ class DecodeEngine:
         """GEMV launches of the last enqueued decode step that ran an e4m3-stream kernel (4 * layers + 2 when every family qualifies; 0 for
         an engine that streams other weights or has not stepped yet)."""
         return self._launches_per_step("w8")
+
+    @property
+    def w8_pair_launches_per_step(self) -> int:
+        """Pair launches of the last enqueued decode step that streamed e4m3 codes (2 * layers when every family has codes;
+        `w8_launches_per_step` then counts the two single launches left). 0 for an engine that does not pair its e4m3 stream."""
+        return self._launches_per_step("w8_pair")
 
     @property
     def wt16_launches_per_step(self) -> int:

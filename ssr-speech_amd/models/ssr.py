@@ -25,7 +25,7 @@ from .. import _lib
 from .. import layout as LY
 from .. import score as SC
 from ..engine import (DEFAULT_GROUP_ROWS, KV_DTYPES, MAX_ROWS, WEIGHT_DTYPES, DecodeEngine, DecodeKnobs, LMWeightsArena, TorchCpuNoiseFeed,
-                      W16_STREAMS, resolve_kv_dtype, resolve_share_prompt, resolve_w16_pair, resolve_w16_stream)
+                      W16_STREAMS, resolve_kv_dtype, resolve_share_prompt, resolve_w16_pair, resolve_w16_stream, resolve_w8_pair, resolve_w8_stream)
 from ..weights import lm_param_specs
 
 
@@ -301,12 +301,14 @@ class SSR_Speech(nn.Module):
         # the pool, the noise buffer and re-capture the graph); a caller-chosen page order (tests) pins the pool size exactly
         # pair launches over the bf16 weight stream: the engine reads SSRHIP_GEMV_W16_PAIR when it is built; the answer is part of the key
         w16_pair = resolve_w16_pair(rows, resolve_w16_stream(W16_STREAMS[0], rows, self._arena.weight_dtype, None, os.environ), 0, None, os.environ)
-        for (k_utt, k_cfg, k_seq, k_steps, k_dbg, k_pool, k_order, k_share, k_wp), e in self._engines.items():
-            if (k_utt, k_cfg, k_dbg, k_order, k_share, k_wp) == (n_utt, use_cfg, bool(self.debug_logits), order_key, share, w16_pair) and k_seq >= cap_seq and k_steps >= cap_steps \
+        # ... and so is SSRHIP_GEMV_W8_PAIR's for the e4m3 stream
+        w8_pair = resolve_w8_pair(rows, resolve_w8_stream(rows, self._arena.weight_dtype, None, os.environ), 0, None, os.environ)
+        for (k_utt, k_cfg, k_seq, k_steps, k_dbg, k_pool, k_order, k_share, k_wp, k_wp8), e in self._engines.items():
+            if (k_utt, k_cfg, k_dbg, k_order, k_share, k_wp, k_wp8) == (n_utt, use_cfg, bool(self.debug_logits), order_key, share, w16_pair, w8_pair) and k_seq >= cap_seq and k_steps >= cap_steps \
                     and (k_pool >= need if order_key is None else k_pool == min(rows * (cap_seq // 128), ((need + 7) // 8) * 8)):
                 return e
         pool = min(rows * (cap_seq // 128), ((need + 7) // 8) * 8)
-        key = (n_utt, use_cfg, cap_seq, cap_steps, bool(self.debug_logits), pool, order_key, share, w16_pair)
+        key = (n_utt, use_cfg, cap_seq, cap_steps, bool(self.debug_logits), pool, order_key, share, w16_pair, w8_pair)
         for e in self._engines.values():         # one engine (KV pool) resident at a time
             e.close()
         self._engines = {}
