@@ -374,6 +374,32 @@ int ssrhip_stream_gather(const int32_t* generated, int32_t n_utt, int32_t max_st
                          const int32_t* ranges_dev, int32_t* codes_out, int32_t B, int32_t cap, int32_t bins, int32_t* flag,
                          ssrhip_stream_t stream);
 
+/* The opt-in device-side source of the sampler's noise (DESIGN.md Part I.21; csrc/noise.hip): one launch writes the Exp(1) draws of up to
+ * SSRHIP_NOISE_MAX_SEGMENTS segments — steps [first_step, first_step + n_steps) of utterance slot `slot`, drawn from the utterance's
+ * 64-bit seed (seed_lo, seed_hi) — into noise[n_utt][max_steps][K][card], the buffer ssrhip_sampler_cfg.use_noise = 1 makes the
+ * sampler read. The stream: Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85), key = (seed_lo,
+ * seed_hi), counter = (b, t, 0x6e6f6973, 0) for block b of step t; word j of the block is element e = 4b + j of the step's flattened
+ * [K][card] tensor (the last block is used partly when K * card % 4 != 0). A word w gives n = w >> 9, u = (n + 0.5) * 2^-23 (exact in
+ * fp32) and the value -logf(u), in [5.96e-8, 16.64]. A value depends on (seed, t, e) only. `words` (optional, tests): a buffer of the
+ * same shape that receives the raw word of every element written. The whole record travels by value in the kernel's arguments: no device
+ * table, no copy. Contract errors (a null pointer, more than SSRHIP_NOISE_MAX_SEGMENTS segments, a negative range, a segment that ends
+ * past max_steps, a slot >= n_utt) return < 0 before any HIP call. The record has no index in ssrhip_sizeof: its size comes back
+ * through ssrhip_noise_sizeof. */
+#define SSRHIP_NOISE_MAX_SEGMENTS 32
+typedef struct ssrhip_noise_segment {
+  int32_t slot, first_step, n_steps;
+  uint32_t seed_lo, seed_hi;
+} ssrhip_noise_segment;
+typedef struct ssrhip_noise_args {
+  float* noise;            /* [n_utt][max_steps][K][card] */
+  uint32_t* words;         /* optional, same shape: the raw Philox word of each element written */
+  int32_t n_utt, max_steps, K, card;
+  int32_t n_seg;
+  ssrhip_noise_segment seg[SSRHIP_NOISE_MAX_SEGMENTS];
+} ssrhip_noise_args;
+int ssrhip_noise_sizeof(void);
+int ssrhip_noise_philox(const ssrhip_noise_args* a, ssrhip_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Dense fp32 GEMM on the matrix cores (v_mfma_f32_32x32x2_f32, exact fp32 FMA chain) for the
  * prefill rows and the codec:  C[M][N] = epi( A[M][K] . W[N][K]^T + bias[N] ), act/residual as GEMV.

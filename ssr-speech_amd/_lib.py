@@ -176,6 +176,19 @@ class LMW8(C.Structure):
                 ("head1_w8", C.c_void_p), ("head2_w8", C.c_void_p), ("head1_s", C.c_void_p), ("head2_s", C.c_void_p)]
 
 
+NOISE_MAX_SEGMENTS = 32    # include/ssrhip.h SSRHIP_NOISE_MAX_SEGMENTS
+
+
+class NoiseSegment(C.Structure):
+    _fields_ = [("slot", C.c_int32), ("first_step", C.c_int32), ("n_steps", C.c_int32), ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32)]
+
+
+class NoiseArgs(C.Structure):
+    """ssrhip_noise_args. Not in ABI_STRUCTS (ssrhip_sizeof knows no index for it): `lib()` checks it through ssrhip_noise_sizeof."""
+    _fields_ = [("noise", C.c_void_p), ("words", C.c_void_p), ("n_utt", C.c_int32), ("max_steps", C.c_int32), ("K", C.c_int32),
+                ("card", C.c_int32), ("n_seg", C.c_int32), ("seg", NoiseSegment * NOISE_MAX_SEGMENTS)]
+
+
 # every symbol include/ssrhip.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("ssrhip_version", C.c_int, []),
@@ -211,6 +224,8 @@ SYMBOLS = [
     ("ssrhip_sample", C.c_int, [C.POINTER(SampleArgs), C.c_void_p]),
     ("ssrhip_stream_gather", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                        C.c_int32, C.c_void_p, C.c_void_p]),
+    ("ssrhip_noise_sizeof", C.c_int, []),
+    ("ssrhip_noise_philox", C.c_int, [C.POINTER(NoiseArgs), C.c_void_p]),
     ("ssrhip_gemm", C.c_int, [C.POINTER(GemmArgs), C.c_void_p]),
     ("ssrhip_split_weights", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     ("ssrhip_gemm_w1", C.c_int, [C.POINTER(GemmArgs), C.c_void_p]),
@@ -304,6 +319,8 @@ def lib():
             raise SsrHipUnavailable(f"ABI mismatch: sizeof({st.__name__}) = {C.sizeof(st)} but the library says {L.ssrhip_sizeof(i)}")
     if L.ssrhip_lm_w8_sizeof() != C.sizeof(LMW8):
         raise SsrHipUnavailable(f"ABI mismatch: sizeof(LMW8) = {C.sizeof(LMW8)} but the library says {L.ssrhip_lm_w8_sizeof()}")
+    if L.ssrhip_noise_sizeof() != C.sizeof(NoiseArgs):
+        raise SsrHipUnavailable(f"ABI mismatch: sizeof(NoiseArgs) = {C.sizeof(NoiseArgs)} but the library says {L.ssrhip_noise_sizeof()}")
     _lib = L
     return L
 

@@ -291,6 +291,20 @@ def resolve_kv_dtype(rows: int, requested: Optional[str], model_default: str = "
     return requested
 
 
+SAMPLING_RNGS = ("torch_cpu", "philox")
+
+
+def resolve_sampling_rng(requested: Optional[str], model_default: str = "torch_cpu") -> str:
+    """Where a sampled run's multinomial noise comes from (DESIGN.md Part I.21). "torch_cpu": the host draws torch's CPU stream
+    (`TorchCpuNoiseFeed`, `NoiseUploader`) — the reference's tokens from the seed alone; "philox": a counter-based generator on the device
+    writes it (`PhiloxNoise`) — seed -> same tokens whatever the batch, no host draw. requested None: `model_default`
+    (SSR_Speech.set_sampling_rng). A name outside SAMPLING_RNGS is a ValueError. Nothing else is read."""
+    for what, v in (("sampling_rng", requested), ("model default sampling_rng", model_default)):
+        if v is not None and v not in SAMPLING_RNGS:
+            raise ValueError(f"{what} {v!r} not in {SAMPLING_RNGS}")
+    return model_default if requested is None else requested
+
+
 def resolve_share_prompt(rows: int, requested: Optional[bool], kv_dtype: str = "fp32") -> bool:
     """Does an engine of `rows` rows share the prompt's KV pages among equal rows (DESIGN.md Part I.15)? Pure. An explicit True where the
     grouped attention walk does not exist is a ValueError: at <= 4 rows (the split kernels), and with a bf16 KV cache (the grouped walk
@@ -853,8 +867,9 @@ class TorchCpuNoiseFeed:
                 out[i].exponential_(1, generator=self.gens[u])
         self.drawn[u] += out.shape[0]
 
-    def reset_slot(self, u: int, generator):
-        """Slot u now serves another utterance with its own generator (continuous batching): forget the old stream's bookkeeping."""
+    def reset_slot(self, u: int, generator, seed: int = 0):
+        """Slot u now serves another utterance with its own generator (continuous batching): forget the old stream's bookkeeping.
+        (`seed` is what `PhiloxNoise` takes from the same call; this stream IS the generator.)"""
         self.gens[u] = generator
         self.marks[u] = []
         self.drawn[u] = 0
@@ -871,6 +886,78 @@ class TorchCpuNoiseFeed:
                 for _ in range(n_taken - s0):
                     torch.empty(self.K, self.card).exponential_(1, generator=self.gens[u])
         self.drawn[u] = n_taken
+
+
+def philox_fill(noise: torch.Tensor, segs: Sequence[tuple], words: Optional[torch.Tensor] = None):
+    """Enqueue, on the current stream, the device-side draws of `segs` = (slot, first_step, n_steps, seed) into `noise`
+    [n_utt, max_steps, K, card] (include/ssrhip.h ssrhip_noise_philox; one launch per _lib.NOISE_MAX_SEGMENTS segments). `words`
+    (tests): an int32 tensor of the same shape that receives the raw Philox words."""
+    n_utt, max_steps, K, card = noise.shape
+    assert noise.dtype == torch.float32 and noise.is_contiguous(), (noise.dtype, noise.stride())
+    assert words is None or (words.dtype == torch.int32 and words.is_contiguous() and words.shape == noise.shape)
+    for i in range(0, len(segs), _lib.NOISE_MAX_SEGMENTS):
+        part = segs[i:i + _lib.NOISE_MAX_SEGMENTS]
+        a = _lib.NoiseArgs()
+        a.noise, a.words = noise.data_ptr(), _lib.ptr(words)
+        a.n_utt, a.max_steps, a.K, a.card, a.n_seg = int(n_utt), int(max_steps), int(K), int(card), len(part)
+        for s, (u, off, n, seed) in zip(a.seg, part):
+            s.slot, s.first_step, s.n_steps = int(u), int(off), int(n)
+            s.seed_lo, s.seed_hi = int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF
+        _lib.check(_lib.lib().ssrhip_noise_philox(C.byref(a), _lib.stream_ptr()), "ssrhip_noise_philox")
+
+
+class PhiloxNoise:
+    """The device-side noise source of a sampled run (sampling_rng "philox", DESIGN.md Part I.21): feed and uploader in one object, with the
+    interface the decode loops use for `TorchCpuNoiseFeed` and `NoiseUploader` — `begin`, `send`, `wait`, `reset_slot`, `finish`, `drawn`.
+    `send` enqueues ONE kernel on the current (decode) stream that writes the Exp(1) draws of the next chunk of steps into
+    `noise[u, off:off + n]`; stream order does the rest, so `wait` and the staging-buffer index mean nothing here. No host draw, no pinned
+    staging, no copy stream, no generator to rewind: `finish` only takes back the count of steps drawn ahead of the stop.
+    seeds[u] is slot u's utterance seed (`DecodeKnobs.seed`); a value depends on (seed, step, element) only — not on the slot, the batch,
+    the chunking or a refill. `launch(segments)` (tests: a fake) receives the list of (slot, first_step, n_steps, seed)."""
+
+    on_device = True
+
+    def __init__(self, seeds: Sequence[int], launch=None):
+        self.seeds = [int(s) for s in seeds]
+        self.drawn = [0] * len(self.seeds)
+        self.noise, self.chunk, self.launch = None, 16, launch
+
+    def bind(self, noise: Optional[torch.Tensor], chunk: int) -> "PhiloxNoise":
+        """A decode loop starts (`DecodeEngine._begin_run`): the buffer to write and the chunk of steps per `send`"""
+        self.noise, self.chunk = noise, chunk
+        if self.launch is None:
+            self.launch = lambda segs: philox_fill(self.noise, segs)
+        return self
+
+    def begin(self, feed=None):
+        pass
+
+    def send(self, buf_i: int, slots: Sequence[int], limit: int):
+        """Enqueue the draws of the next chunk of `slots` (steps below `limit`); `buf_i` is ignored: nothing is staged."""
+        segs = noise_segments(self.drawn, slots, self.chunk, limit)
+        if segs:
+            self.launch([(u, off, n, self.seeds[u]) for u, off, n in segs])
+        for u, _, n in segs:
+            self.drawn[u] += n
+
+    def wait(self, stream):
+        pass
+
+    def reset_slot(self, u: int, generator=None, seed: int = 0):
+        """Slot u now serves another utterance: its seed, and its steps count from 0 again."""
+        self.seeds[u] = int(seed)
+        self.drawn[u] = 0
+
+    def finish(self, u: int, n_taken: int):
+        if n_taken < self.drawn[u]:
+            self.drawn[u] = n_taken
+
+
+def make_noise_feed(sampling_rng: str, n_slots: int, K: int, card: int):
+    """The noise source of a sampled queue run over `n_slots` utterance slots whose jobs arrive later (`reset_slot`)"""
+    if resolve_sampling_rng(sampling_rng) == "philox":
+        return PhiloxNoise([0] * n_slots)
+    return TorchCpuNoiseFeed([None] * n_slots, K, card)
 
 
 class DecodeEngine:
@@ -1515,7 +1602,8 @@ class DecodeEngine:
     def run_to_completion(self, chunk: int = 16, use_graph: bool = True, max_total: Optional[int] = None,
                           feed: Optional[TorchCpuNoiseFeed] = None, on_chunk=None):
         """Decode in chunks of `chunk` steps until every utterance reports done (the flags are polled once per chunk).
-        With `feed`, the host draws and uploads the NEXT chunk's sampling noise while the GPU runs the current chunk (`NoiseUploader`).
+        With `feed`, the host draws and uploads the NEXT chunk's sampling noise while the GPU runs the current chunk (`NoiseUploader`);
+        a `PhiloxNoise` as `feed` writes it on the device instead, between two chunks on this stream.
         `on_chunk(states)` is called after every poll with the states read there (`iter_chunks` is the same loop as a generator)."""
         states = None
         for states in self.iter_chunks(chunk, use_graph, max_total, feed):
@@ -1557,11 +1645,14 @@ class DecodeEngine:
                 feed.finish(u, int(s_.n_steps))
         yield states
 
-    def _begin_run(self, chunk: int, feed: Optional[TorchCpuNoiseFeed]) -> Optional[NoiseUploader]:
-        """A decode loop starts: not polled yet and, with a feed, the engine's one uploader (rebuilt only when `chunk` changes) on it"""
+    def _begin_run(self, chunk: int, feed):
+        """A decode loop starts: not polled yet and, with a feed, the engine's one uploader (rebuilt only when `chunk` changes) on it. A
+        `PhiloxNoise` is its own uploader: it writes `noise` on the decode stream, and nothing is built for it."""
         self._polled, self._feed = False, feed
         if feed is None:
             return None
+        if getattr(feed, "on_device", False):
+            return feed.bind(self.noise, chunk)
         if self._uploader is None or self._uploader.chunk != chunk:
             self._uploader = NoiseUploader(self.noise, chunk)
         self._uploader.begin(feed)
@@ -1583,7 +1674,8 @@ class DecodeEngine:
         after the other (inference_v2.py:331-333); the result of each job does not depend on what shares the engine with it.
 
         jobs[i]: {text_rows: [row0(, row1)], audio_cols: [K, T0], knobs: DecodeKnobs, gen: torch.Generator | None (sampling),
-        cap: max steps of this utterance}. Returns a list of (SamplerState, generated int64 [n_steps, K]) in job order."""
+        cap: max steps of this utterance, rng: "torch_cpu" | "philox" (sampling; optional, one value per queue: with "philox" the noise is
+        drawn on the device from knobs.seed and `gen` is not consumed)}. Returns a list of (SamplerState, generated int64 [n_steps, K]) in job order."""
         it = self.iter_queue(jobs, chunk, use_graph, sampling)
         while True:
             try:
@@ -1606,7 +1698,11 @@ class DecodeEngine:
         # towards the end — the tail with a few long utterances on a mostly idle engine shrinks (simulated on the bench's ragged queue:
         # 344 -> 327 chunks). Which utterance sits in which slot when does not change any result.
         pending = sorted(range(n_jobs), key=lambda j: -int(jobs[j]["cap"])) if n_jobs > self.n_utt else list(range(n_jobs))
-        feed = TorchCpuNoiseFeed([None] * self.n_utt, self.a.K, self.a.card) if sampling else None
+        # the noise source is the run's: every job names the same one ("rng", SAMPLING_RNGS; absent = "torch_cpu")
+        rngs = sorted({j.get("rng", "torch_cpu") for j in jobs})
+        if len(rngs) != 1:
+            raise ValueError(f"the jobs of one queue name different sampling noise sources: {rngs}")
+        feed = make_noise_feed(rngs[0], self.n_utt, self.a.K, self.a.card) if sampling else None
         up = self._begin_run(chunk, feed)
 
         # Two-phase admission is built, bit-exact and OFF by default: on the bench's ragged queue (64 utterances through 8
@@ -1629,7 +1725,7 @@ class DecodeEngine:
                 slot_job[u] = j
                 local[u] = 0
                 if up:
-                    feed.reset_slot(u, jobs[j].get("gen"))
+                    feed.reset_slot(u, jobs[j].get("gen"), jobs[j]["knobs"].seed)
             if up:
                 up.send(2, slots, self.max_steps)               # the new utterances' first chunk, before their first step
 

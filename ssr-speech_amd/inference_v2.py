@@ -67,6 +67,10 @@ EXTRA_FLAGS = [
     ("--stream_dir", dict(type=str, default=None,
                           help="--tts with --sample_batch_size N: stream the lock-step samples (inference_samples_stream) and append each "
                                "sample's chunks, as they arrive, to DIR/{savename}_new_seed{seed}.f32 (raw float32 samples, one file per sample)")),
+    ("--sampling_rng", dict(type=str, choices=["torch_cpu", "philox"], default="torch_cpu",
+                            help="philox: sampled runs take their multinomial noise from a counter-based generator on the device, keyed by "
+                                 "the seed (SSR_Speech.set_sampling_rng): no host draw, other tokens than torch_cpu; torch_cpu (default): "
+                                 "torch's CPU stream, the reference's tokens from the seed")),
     ("--prompt_end", dict(type=float, default=None, help="--tts: cut the prompt audio at this time in seconds (default --prompt_length)")),
     ("--phoneme_ids", dict(type=str, default=None, help="comma separated phoneme ids of the target transcript (skips espeak)")),
     ("--prompt_phoneme_ids", dict(type=str, default=None, help="comma separated phoneme ids of the prompt transcript")),
@@ -255,6 +259,7 @@ def main(argv=None):
     model.load_state_dict(ckpt["model"])
     model.set_weight_dtype(args.weight_dtype)
     model.set_kv_dtype(args.kv_dtype)
+    model.set_sampling_rng(args.sampling_rng)
     config = vars(model.args)
     phn2num = ckpt["phn2num"]
     model.to(device)

@@ -24,8 +24,8 @@ import torch.nn as nn
 from .. import _lib
 from .. import layout as LY
 from .. import score as SC
-from ..engine import (DEFAULT_GROUP_ROWS, KV_DTYPES, MAX_ROWS, WEIGHT_DTYPES, DecodeEngine, DecodeKnobs, LMWeightsArena, TorchCpuNoiseFeed,
-                      W16_STREAMS, resolve_kv_dtype, resolve_share_prompt, resolve_w16_pair, resolve_w16_stream, resolve_w8_pair, resolve_w8_stream)
+from ..engine import (DEFAULT_GROUP_ROWS, KV_DTYPES, MAX_ROWS, WEIGHT_DTYPES, DecodeEngine, DecodeKnobs, LMWeightsArena, PhiloxNoise, SAMPLING_RNGS,
+                      TorchCpuNoiseFeed, W16_STREAMS, resolve_kv_dtype, resolve_sampling_rng, resolve_share_prompt, resolve_w16_pair, resolve_w16_stream, resolve_w8_pair, resolve_w8_stream)
 from ..weights import lm_param_specs
 
 
@@ -204,6 +204,7 @@ class SSR_Speech(nn.Module):
         self._engines: Dict[tuple, DecodeEngine] = {}
         self._weight_dtype = "fp32"
         self._kv_dtype = "fp32"
+        self._sampling_rng = "torch_cpu"
         self.debug_logits = False          # tests: keep the per-step post-edit logits
         self.page_order = None             # tests: permutation deciding which physical KV pages the allocator hands out first
         self.last_run: dict = {}
@@ -266,6 +267,24 @@ class SSR_Speech(nn.Module):
             for e in self._engines.values():
                 e.close()
             self._engines = {}
+
+    @property
+    def sampling_rng(self) -> str:
+        return self._sampling_rng
+
+    def set_sampling_rng(self, sampling_rng: str) -> None:
+        """Where the multinomial noise of SAMPLED runs (`top_k != 1`) comes from (DESIGN.md Part I.21). "torch_cpu" (the default): the host
+        draws torch's CPU stream and uploads it beside the decode — the reference's tokens from the seed alone. "philox": a counter-based
+        generator on the device (engine.PhiloxNoise, csrc/noise.hip) writes it on the decode stream from the utterance's seed — no host
+        draw, no pinned staging, no copy stream; other tokens than "torch_cpu", and the batch contract by construction: result i of
+        `inference_batch(seed=s)` equals `inference()` of utterance i alone after `torch.manual_seed(s + i)`, for any `group`, with and
+        without refill, at any DP world size. Every path honours it — `inference`, `inference_stream`, `inference_batch`,
+        `inference_batch_stream`, `inference_samples*`, `dp.generate`, `dp.synthesize`; an explicit `noise=` argument still wins; greedy runs
+        ignore it. Under "philox" the CPU generator is consumed by the `aug_text` draw of the unconditional text only, so after a run it
+        is NOT where the reference leaves it. A property of a run, not of an engine: nothing is dropped or rebuilt."""
+        if sampling_rng not in SAMPLING_RNGS:
+            raise ValueError(f"sampling_rng {sampling_rng!r} not in {SAMPLING_RNGS}")
+        self._sampling_rng = sampling_rng
 
     def forward(self, batch):
         raise NotImplementedError("SSR_Speech.forward (training loss, reference models/ssr.py:280-379) is outside the "
@@ -515,7 +534,8 @@ class SSR_Speech(nn.Module):
         elif not greedy:
             # reproduce the reference's CPU sampling stream: torch.multinomial(probs[K,card], 1) draws one Exp(1) tensor of that
             # shape per step from the global generator (after the uncond_x draw above) — streamed in 16 steps at a time beside the decode
-            feed = TorchCpuNoiseFeed([None], K, eng.a.card)
+            # ... or, under sampling_rng "philox", written on the device from knobs.seed, 16 steps at a time on the decode stream
+            feed = PhiloxNoise([knobs.seed]) if resolve_sampling_rng(None, self._sampling_rng) == "philox" else TorchCpuNoiseFeed([None], K, eng.a.card)
             eng.start(text_rows, [cated], [knobs], host_noise=True)
         else:
             eng.start(text_rows, [cated], [knobs])
@@ -622,7 +642,7 @@ class SSR_Speech(nn.Module):
             kn = DecodeKnobs(top_k=top_k, top_p=top_p, temperature=temperature, stop_repetition=stop_repetition,
                              silence_tokens=tuple(int(s) for s in silence_tokens), cfg_coef=cfg_coef, cfg_stride=cfg_stride,
                              use_cfg=bool(aug_text), text_len=L, n_spans=num_task, seed=seed + gi)
-            jobs.append(dict(text_rows=text_rows, audio_cols=cated, knobs=kn, gen=rng, cap=cap))
+            jobs.append(dict(text_rows=text_rows, audio_cols=cated, knobs=kn, gen=rng, cap=cap, rng=self._sampling_rng))
             metas.append((y_np, nmi, num_task))
         # Utterance slots of ONE engine, refilled as utterances finish (continuous batching): a finished utterance's rows take the next
         # pending utterance at the following 16-step poll instead of idling until the longest member of a fixed group ends.
