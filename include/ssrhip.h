@@ -173,6 +173,29 @@ int ssrhip_gemv_wt16_applicable(const ssrhip_gemv_args* a);
 int ssrhip_gemv_wt32(const ssrhip_gemv_args* a, const uint16_t* Wt16, ssrhip_stream_t stream);
 int ssrhip_gemv_wt32_applicable(const ssrhip_gemv_args* a);
 
+/* Packed OCP e4m3 weight layout of the e4m3 weight stream at 5..16 rows (csrc/gemv_mfma_w8.hip; K % 128 == 0): SSRHIP_WT16_INDEX in 1-byte
+ * codes. Rows in 8-row units (the last unit zero-padded: code 0x00), K in OCTETS of eight 16-float k-steps. With
+ *   n = 8u + c,  k = 128o + 16j + 4ks + e,  h = j % 2,  g = j / 2
+ * the byte index of the code of W[n][k] is ((u*(K/128) + o)*2 + h)*512 + (ks*8 + c)*16 + g*4 + e: the 512-byte block (u, o, h) holds, at
+ * 16-byte piece ks*8 + c, as dword g the four codes of k-step 8o + 2g + h. The layout does not depend on the kernel form the launch plan
+ * picks: the plain form (lanes c >= 8 = the next unit) reads blocks h = 0 and h = 1 of an octet as two wave-level loads of two 512-byte runs
+ * each, the k-step-pair form (lanes c >= 8 = the other k-step of a pair) reads both blocks of (u, o) as ONE contiguous KiB. A group's matrix
+ * takes ceil(N/8)*8*K bytes; groups follow each other. Each byte is a finite OCP e4m3 code (torch.float8_e4m3fn; 0x7f / 0xff never occur);
+ * the weight is code * scale[n], scale[n] = 2^e one fp32 per output row (per group: scale[g*N + n]; the scales of ssrhip_gemv_w8). */
+#define SSRHIP_WT8_INDEX(n, k, K) \
+  (((((size_t)(n) / 8) * ((size_t)(K) / 128) + (size_t)(k) / 128) * 2 + (((k) % 128) / 16) % 2) * 512 + ((((k) % 16) / 4) * 8 + (n) % 8) * 16 + ((((k) % 128) / 16) / 2) * 4 + (k) % 4)
+
+/* ssrhip_gemv(a) for 5..16 rows streaming the PACKED e4m3 codes `Wt8` (SSRHIP_WT8_INDEX) and the per-row power-of-two scales `scale`
+ * [groups][N] instead of a->W. `a` is the call as ssrhip_gemv takes it, with a->w_tiled = 1 and a->W = the fp32 streaming-order copy of
+ * code * scale (the fp32 "master"); the result is then BIT-IDENTICAL to ssrhip_gemv(a): the same launch plan, the codes widened in registers
+ * (v_cvt_pk_f32_fp8, exact) and multiplied by their row's scale BEFORE the MFMA (exact: that product is the master), every MFMA and every
+ * sum in the order of the fp32 kernel. No caveat about subnormal partial sums applies (ssrhip_gemv_w8 scales sums; this one scales weights).
+ *   returns 0 = launched, 1 = `a` does not qualify and NOTHING was launched (call ssrhip_gemv(a)), < 0 = contract error (decided before
+ *   any HIP call). Qualifies: 5 <= B <= 16, w_tiled == 1, K % 128 == 0, the arguments ssrhip_gemv accepts at these rows, and the
+ *   rows-per-workgroup kernels selected (SSRHIP_GEMVM_V != 1). SSRHIP_GEMVM_WPC / _NOPAIR act as on ssrhip_gemv. */
+int ssrhip_gemv_wt8(const ssrhip_gemv_args* a, const uint8_t* Wt8, const float* scale, ssrhip_stream_t stream);
+int ssrhip_gemv_wt8_applicable(const ssrhip_gemv_args* a);
+
 /* Two consecutive launches of the 2-row decode step as ONE: `a` = a GEMV with the residual epilogue and `b` = the LayerNorm + Linear that
  * reads a's output, with the all-to-all edge between them inside the launch (csrc/gemv.hip gemv_pair_kernel / gemv_pair_merge_kernel:
  * tagged 8-byte granules, write-through stores, one gather round trip). Two forms:
@@ -653,7 +676,7 @@ int ssrhip_lm_w8_sizeof(void);
 /* Hand the engine the packed codes and scales: from now on every GEMV launch of its decode step whose family has them and whose shape
  * qualifies (ssrhip_gemv_w8) streams 1-byte weights; the others run ssrhip_gemv on the masters. Same tokens, bit for bit, as the same engine
  * without this call. To be called before the first decode step is enqueued or captured; refused (< 0) afterwards, for engines of more than
- * 4 rows, where another packed stream is already set (ssrhip_lm_set_w16 and its kin, and the reverse), and for a family with codes but no
+ * 4 rows (5..16 rows have ssrhip_lm_set_wt8), where another packed stream is already set (ssrhip_lm_set_w16 and its kin, and the reverse), and for a family with codes but no
  * scales. The default pair launches read fp32 weights: the engine gives its device's pairing slot back and steps unpaired (ssrhip_lm_pairing
  * then reports 0 and names the e4m3 stream) unless ssrhip_lm_set_w8_pair, below, opts in to the pair launches over the codes. Prefill and
  * scoring read the masters and are not affected. */
@@ -688,6 +711,15 @@ int ssrhip_lm_set_wt32(ssrhip_lm* lm, const ssrhip_lm_w16* wt16);
 /* how many GEMV launches of the last enqueued (or captured) decode step ran a kernel of csrc/gemv_mfma32_w16.hip (4 * n_layer + 2 when
  * every family qualifies); the other two counters stay 0 for these engines */
 int ssrhip_lm_wt32_launches(const ssrhip_lm* lm);
+/* The e4m3 weight stream of the 5..16-row decode step: the record is the one ssrhip_lm_set_w8 takes, with the codes in SSRHIP_WT8_INDEX
+ * order (scales unchanged; a NULL pair = that family streams the fp32 streaming-order copy of its master). Every GEMV launch of the step
+ * tries ssrhip_gemv_wt8 first and falls back to ssrhip_gemv; same tokens, bit for bit; the step stays one captured graph. Refused (< 0) for
+ * engines of <= 4 rows (the error names ssrhip_lm_set_w8) and of more than 16 rows, engines already captured, engines created without the
+ * fp32 streaming-order copies, engines that already have another packed stream, and for a family with codes but no scales. */
+int ssrhip_lm_set_wt8(ssrhip_lm* lm, const ssrhip_lm_w8* wt8);
+/* how many GEMV launches of the last enqueued (or captured) decode step ran a kernel of csrc/gemv_mfma_w8.hip (4 * n_layer + 2 when every
+ * family qualifies); a counter of its own: every other stream's counter stays 0 for these engines */
+int ssrhip_lm_wt8_launches(const ssrhip_lm* lm);
 /* on != 0: the *_ws buffers of this engine's ssrhip_lm_weights hold ONE bf16 plane [N][K] each (a bf16 arena: the weight itself) instead
  * of three; ssrhip_lm_prefill then multiplies through ssrhip_gemm_w1 (and, where that answers 1, through the fp32 chain on the masters).
  * Same KV cache and x as with the three planes of the same weights, bit for bit. The count is the CALLER's statement about its buffers

@@ -201,6 +201,8 @@ SYMBOLS = [
     ("ssrhip_gemv_w8_applicable", C.c_int, [C.POINTER(GemvArgs)]),
     ("ssrhip_gemv_wt16", C.c_int, [C.POINTER(GemvArgs), C.c_void_p, C.c_void_p]),
     ("ssrhip_gemv_wt16_applicable", C.c_int, [C.POINTER(GemvArgs)]),
+    ("ssrhip_gemv_wt8", C.c_int, [C.POINTER(GemvArgs), C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("ssrhip_gemv_wt8_applicable", C.c_int, [C.POINTER(GemvArgs)]),
     ("ssrhip_gemv_wt32", C.c_int, [C.POINTER(GemvArgs), C.c_void_p, C.c_void_p]),
     ("ssrhip_gemv_wt32_applicable", C.c_int, [C.POINTER(GemvArgs)]),
     ("ssrhip_pair_buffer", C.c_int, [C.c_int32, C.c_int32]),
@@ -269,6 +271,8 @@ SYMBOLS = [
     ("ssrhip_lm_w8_pair_launches", C.c_int, [C.c_void_p]),
     ("ssrhip_lm_set_wt16", C.c_int, [C.c_void_p, C.POINTER(LMW16)]),
     ("ssrhip_lm_wt16_launches", C.c_int, [C.c_void_p]),
+    ("ssrhip_lm_set_wt8", C.c_int, [C.c_void_p, C.POINTER(LMW8)]),
+    ("ssrhip_lm_wt8_launches", C.c_int, [C.c_void_p]),
     ("ssrhip_lm_set_wt32", C.c_int, [C.c_void_p, C.POINTER(LMW16)]),
     ("ssrhip_lm_wt32_launches", C.c_int, [C.c_void_p]),
     ("ssrhip_debug_occupy", C.c_int, [C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),

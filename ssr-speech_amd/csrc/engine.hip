@@ -76,8 +76,9 @@ struct ssrhip_lm {
   std::vector<const uint16_t*> pk[4];       // in_proj, out_proj, ffn1, ffn2 per layer (empty: none)
   const uint16_t* pk_head1 = nullptr;
   const uint16_t* pk_head2 = nullptr;
-  int pk_launches = 0;          // launches of the last enqueued step that ran a kernel of pk_kind (ssrhip_lm_{w16,wt16,wt32,w8}_launches)
-  // the e4m3 weight stream (pk_kind == PK_W8, <= 4 rows): codes in SSRHIP_W8_INDEX order and, travelling next to them, the per-row scales
+  int pk_launches = 0;          // launches of the last enqueued step that ran a kernel of pk_kind (ssrhip_lm_{w16,wt16,wt32,w8,wt8}_launches)
+  // the e4m3 weight streams (pk_kind == PK_W8, <= 4 rows: codes in SSRHIP_W8_INDEX order; PK_WT8, 5..16 rows: SSRHIP_WT8_INDEX order) and,
+  // travelling next to the codes, the per-row scales
   std::vector<const uint8_t*> pk8[4];
   std::vector<const float*> pk8s[4];
   const uint8_t* pk8_head1 = nullptr; const uint8_t* pk8_head2 = nullptr;
@@ -105,8 +106,10 @@ const PackedStream PACKED_STREAMS[3] = {
     {"ssrhip_lm_set_wt16", 5, 16, "5..16", "the bf16 weight stream of the matrix-core step exists for 5..16 rows only", ssrhip_gemv_wt16, true, false},
     {"ssrhip_lm_set_wt32", 17, 32, "17..32", "the bf16 weight stream of the two-panel step exists for 17..32 rows only", ssrhip_gemv_wt32, true, false},
 };
-enum { PK_W16 = 0, PK_WT16 = 1, PK_WT32 = 2, PK_W8 = 3 };   // PK_W8: the fourth packed kind, the e4m3 stream (ssrhip_lm_set_w8; codes AND scales,
-                                                            // so its entry point has another signature and it has no row in PACKED_STREAMS)
+enum { PK_W16 = 0, PK_WT16 = 1, PK_WT32 = 2, PK_W8 = 3, PK_WT8 = 4 };   // PK_W8 / PK_WT8: the e4m3 streams of <= 4 rows (ssrhip_lm_set_w8) and of
+                                                            // 5..16 rows (ssrhip_lm_set_wt8): codes AND scales, so their entry points have
+                                                            // another signature and they have no row in PACKED_STREAMS
+inline bool pk_codes(int kind) { return kind == PK_W8 || kind == PK_WT8; }
 // what a launch of one family streams instead of its fp32 master: a 2-byte copy (the bf16 kinds) or codes + scales (PK_W8); all NULL = nothing
 struct PackedRef { const uint16_t* w16; const uint8_t* w8; const float* sc; };
 
@@ -365,7 +368,7 @@ int enqueue_step(ssrhip_lm* lm, hipStream_t s, Timer* tm) {
   int n_pairs = lm->pair_ws ? sh.pair_plan(&pair_qkv, &pair_head, &pair_ffn1, wp ? lm->pk_kind : -1) : 0;
   // what a launch of (family, layer) streams instead of its fp32 master, in the engine's kind
   auto w16_of = [&](int family, int l) -> PackedRef {
-    if (lm->pk_kind == PK_W8) return lm->pk8[family].empty() ? PackedRef{nullptr, nullptr, nullptr} : PackedRef{nullptr, lm->pk8[family][l], lm->pk8s[family][l]};
+    if (pk_codes(lm->pk_kind)) return lm->pk8[family].empty() ? PackedRef{nullptr, nullptr, nullptr} : PackedRef{nullptr, lm->pk8[family][l], lm->pk8s[family][l]};
     return PackedRef{lm->pk[family].empty() ? nullptr : lm->pk[family][l], nullptr, nullptr};
   };
   const PackedRef pk_h1 = {lm->pk_head1, lm->pk8_head1, lm->pk8s_head1}, pk_h2 = {lm->pk_head2, lm->pk8_head2, lm->pk8s_head2};
@@ -402,7 +405,9 @@ int enqueue_step(ssrhip_lm* lm, hipStream_t s, Timer* tm) {
   int n_pk = 0;
   auto gemv_call = [&](const ssrhip_gemv_args& ga, const PackedRef pk) -> int {
     if (pk.w16 || pk.w8) {
-      const int rc = pk.w8 ? ssrhip_gemv_w8(&ga, pk.w8, pk.sc, (ssrhip_stream_t)s) : PACKED_STREAMS[lm->pk_kind].gemv(&ga, pk.w16, (ssrhip_stream_t)s);
+      const int rc = !pk.w8                   ? PACKED_STREAMS[lm->pk_kind].gemv(&ga, pk.w16, (ssrhip_stream_t)s)
+                     : lm->pk_kind == PK_WT8 ? ssrhip_gemv_wt8(&ga, pk.w8, pk.sc, (ssrhip_stream_t)s)      // 5..16 rows (B > 4: it answers 1 otherwise)
+                                             : ssrhip_gemv_w8(&ga, pk.w8, pk.sc, (ssrhip_stream_t)s);
       if (rc <= 0) { n_pk += rc == 0; return rc; }
     }
     return ssrhip_gemv(&ga, s);
@@ -586,7 +591,8 @@ static int lm_set_packed(ssrhip_lm* lm, const ssrhip_lm_w16* rec, int kind) {
     SSR_REQUIRE(B >= ps.lo || B > o.hi, "%s: engines of %s rows stream bf16 weights through %s (this engine has %d rows)", ps.setter, o.rows, o.setter, B);
   SSR_REQUIRE(B <= ps.hi, "%s: %s (this engine has %d rows)", ps.setter, ps.only, B);
   SSR_REQUIRE(!lm->exec, "%s: the decode step of this engine is already captured (call it before the first ssrhip_lm_decode)", ps.setter);
-  SSR_REQUIRE(lm->pk_kind != PK_W8, "%s: this engine already streams e4m3 weights (ssrhip_lm_set_w8); an engine has one packed stream", ps.setter);
+  SSR_REQUIRE(!pk_codes(lm->pk_kind), "%s: this engine already streams e4m3 weights (%s); an engine has one packed stream", ps.setter,
+              lm->pk_kind == PK_WT8 ? "ssrhip_lm_set_wt8" : "ssrhip_lm_set_w8");
   SSR_REQUIRE(!ps.needs_wt || lm->w.in_proj_wt, "%s: this engine was created without the fp32 streaming-order copies (ssrhip_lm_weights *_wt)", ps.setter);
   const uint16_t* const* src[4] = {rec->in_proj_w16, rec->out_proj_w16, rec->ffn1_w16, rec->ffn2_w16};
   for (int f = 0; f < 4; ++f) {
@@ -608,22 +614,29 @@ static int lm_set_packed(ssrhip_lm* lm, const ssrhip_lm_w16* rec, int kind) {
 static int lm_packed_launches(const ssrhip_lm* lm, int kind) { return lm && lm->pk_kind == kind ? lm->pk_launches : 0; }
 
 extern "C" int ssrhip_lm_w8_sizeof(void) { return (int)sizeof(ssrhip_lm_w8); }
-// The fourth packed kind: the checks of lm_set_packed for the <= 4-row step, then codes and scales side by side.
-extern "C" int ssrhip_lm_set_w8(ssrhip_lm* lm, const ssrhip_lm_w8* rec) {
-  SSR_REQUIRE(lm && rec, "ssrhip_lm_set_w8: null argument");
+// The e4m3 kinds: the checks of lm_set_packed for the kind's rows (PK_W8: <= 4, PK_WT8: 5..16), then codes and scales side by side.
+static int lm_set_codes(ssrhip_lm* lm, const ssrhip_lm_w8* rec, int kind) {
+  const char* who = kind == PK_WT8 ? "ssrhip_lm_set_wt8" : "ssrhip_lm_set_w8";
+  SSR_REQUIRE(lm && rec, "%s: null argument", who);
   const int B = lm->b.B;
-  SSR_REQUIRE(B <= 4, "ssrhip_lm_set_w8: the e4m3 weight stream exists for the <= 4-row decode step only (this engine has %d rows)", B);
-  SSR_REQUIRE(!lm->exec, "ssrhip_lm_set_w8: the decode step of this engine is already captured (call it before the first ssrhip_lm_decode)");
-  SSR_REQUIRE(lm->pk_kind < 0 || lm->pk_kind == PK_W8, "ssrhip_lm_set_w8: this engine already streams bf16 weights (%s); an engine has one packed stream",
+  if (kind == PK_W8) {
+    SSR_REQUIRE(B <= 4, "ssrhip_lm_set_w8: the e4m3 weight stream exists for the <= 4-row decode step only (this engine has %d rows; engines of 5..16 rows take ssrhip_lm_set_wt8)", B);
+  } else {
+    SSR_REQUIRE(B > 4, "ssrhip_lm_set_wt8: engines of <= 4 rows stream e4m3 weights through ssrhip_lm_set_w8 (this engine has %d rows)", B);
+    SSR_REQUIRE(B <= 16, "ssrhip_lm_set_wt8: the e4m3 weight stream of the matrix-core step exists for 5..16 rows only (this engine has %d rows; engines of 17..32 rows stream 2-byte copies through ssrhip_lm_set_wt32)", B);
+  }
+  SSR_REQUIRE(!lm->exec, "%s: the decode step of this engine is already captured (call it before the first ssrhip_lm_decode)", who);
+  SSR_REQUIRE(lm->pk_kind < 0 || lm->pk_kind == kind, "%s: this engine already streams bf16 weights (%s); an engine has one packed stream", who,
               lm->pk_kind >= 0 && lm->pk_kind < PK_W8 ? PACKED_STREAMS[lm->pk_kind].setter : "");
+  SSR_REQUIRE(kind != PK_WT8 || lm->w.in_proj_wt, "%s: this engine was created without the fp32 streaming-order copies (ssrhip_lm_weights *_wt)", who);
   const uint8_t* const* src[4] = {rec->in_proj_w8, rec->out_proj_w8, rec->ffn1_w8, rec->ffn2_w8};
   const float* const* scl[4] = {rec->in_proj_s, rec->out_proj_s, rec->ffn1_s, rec->ffn2_s};
-  for (int f = 0; f < 4; ++f) SSR_REQUIRE(!src[f] == !scl[f], "ssrhip_lm_set_w8: codes and scales of a family come together (family %d)", f);
-  SSR_REQUIRE(!rec->head1_w8 == !rec->head1_s && !rec->head2_w8 == !rec->head2_s, "ssrhip_lm_set_w8: codes and scales of a head matrix come together");
+  for (int f = 0; f < 4; ++f) SSR_REQUIRE(!src[f] == !scl[f], "%s: codes and scales of a family come together (family %d)", who, f);
+  SSR_REQUIRE(!rec->head1_w8 == !rec->head1_s && !rec->head2_w8 == !rec->head2_s, "%s: codes and scales of a head matrix come together", who);
   for (int f = 0; f < 4; ++f) {
     if (src[f]) {
       for (int l = 0; l < lm->d.n_layer; ++l)
-        SSR_REQUIRE(src[f][l] && scl[f][l], "ssrhip_lm_set_w8: null codes or scales (family %d, layer %d)", f, l);
+        SSR_REQUIRE(src[f][l] && scl[f][l], "%s: null codes or scales (family %d, layer %d)", who, f, l);
     }
   }
   for (int f = 0; f < 4; ++f) {
@@ -632,7 +645,8 @@ extern "C" int ssrhip_lm_set_w8(ssrhip_lm* lm, const ssrhip_lm_w8* rec) {
   }
   lm->pk8_head1 = rec->head1_w8; lm->pk8s_head1 = rec->head1_s;
   lm->pk8_head2 = rec->head2_w8; lm->pk8s_head2 = rec->head2_s;
-  lm->pk_kind = PK_W8;
+  lm->pk_kind = kind;
+  if (kind == PK_WT8) return 0;   // engines of more than 4 rows never pair
   // the default pair launches stream fp32 weights: this engine steps unpaired and gives the device's pairing slot back
   // (ssrhip_lm_set_w8_pair may take it again for the pair launches over the codes)
   if (lm->pair_ws) { hipFree(lm->pair_ws); lm->pair_ws = nullptr; }
@@ -641,6 +655,9 @@ extern "C" int ssrhip_lm_set_w8(ssrhip_lm* lm, const ssrhip_lm_w8* rec) {
   snprintf(lm->pair_why, sizeof(lm->pair_why), "this engine streams e4m3 weights (ssrhip_lm_set_w8): its pair launches are an opt-in (ssrhip_lm_set_w8_pair, 2 rows)");
   return 0;
 }
+extern "C" int ssrhip_lm_set_w8(ssrhip_lm* lm, const ssrhip_lm_w8* rec) { return lm_set_codes(lm, rec, PK_W8); }
+extern "C" int ssrhip_lm_set_wt8(ssrhip_lm* lm, const ssrhip_lm_w8* rec) { return lm_set_codes(lm, rec, PK_WT8); }
+extern "C" int ssrhip_lm_wt8_launches(const ssrhip_lm* lm) { return lm_packed_launches(lm, PK_WT8); }
 extern "C" int ssrhip_lm_w8_launches(const ssrhip_lm* lm) { return lm_packed_launches(lm, PK_W8); }
 
 extern "C" int ssrhip_lm_set_w16(ssrhip_lm* lm, const ssrhip_lm_w16* w16) { return lm_set_packed(lm, w16, PK_W16); }

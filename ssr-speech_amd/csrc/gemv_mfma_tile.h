@@ -1,5 +1,5 @@
 // gemv_mfma_tile.h — pieces shared by the matrix-core GEMV kernels (gemv_mfma.hip: 5..16 rows, gemv_mfma32.hip: 17..32 rows, and their
-// bf16 weight streams gemv_mfma_w16.hip / gemv_mfma32_w16.hip): the 16x16x4 fp32 MFMA, the k-slot reduction, the per-lane weight pointer of
+// bf16 weight streams gemv_mfma_w16.hip / gemv_mfma32_w16.hip, and the e4m3 stream gemv_mfma_w8.hip): the 16x16x4 fp32 MFMA, the k-slot reduction, the per-lane weight pointer of
 // a tile and the split tile epilogue; the pieces of the rows-per-workgroup kernels (LayerNorm on register-resident x, the MFMA groups of a
 // k-step and of a k-step pair, the pair form's merge tail) for one panel and for two; the loads and the widening of the packed bf16 layout;
 // and, for the host, the argument check and the launch plan of those kernels and the qualifier of the two bf16 launchers.
@@ -383,15 +383,17 @@ inline int gemv_rows_plan(const ssrhip_gemv_args* a, bool ln_keeps_x, int num_cu
   return 0;
 }
 
-// The bf16 weight streams (ssrhip_gemv_wt16 at 5..16 rows, ssrhip_gemv_wt32 at 17..32): does `a` take the packed kernels?
+// The packed weight streams (bf16: ssrhip_gemv_wt16 at 5..16 rows, ssrhip_gemv_wt32 at 17..32; e4m3: ssrhip_gemv_wt8 at 5..16): does `a` take the packed kernels?
 // 0: it qualifies (then *pl is its launch plan), 1: it does not, < 0: contract error. No HIP call before the answer is 0.
 // `who` is the entry point's name in the error texts; [b_lo, b_hi], ln_kmax, ln_keeps_x as in gemv_rows_check / gemv_rows_plan — the
 // check and the plan of the fp32 launcher at the same row count: the same refusals, the same grid, waves, K slices and pair decision.
 // v1_refuses: SSRHIP_GEMVM_V=1 (the per-tile kernel of 5..16 rows, which has no bf16 form) makes the answer 1.
-inline int gemv_wt_qualify(const ssrhip_gemv_args* a, const char* who, int b_lo, int b_hi, int ln_kmax, bool ln_keeps_x, bool v1_refuses, RowsPlan* pl) {
+// k_mult: the packed layout's block of K (64 floats = a quad of k-steps for bf16; the e4m3 stream of gemv_mfma_w8.hip passes 128, an octet).
+inline int gemv_wt_qualify(const ssrhip_gemv_args* a, const char* who, int b_lo, int b_hi, int ln_kmax, bool ln_keeps_x, bool v1_refuses, RowsPlan* pl,
+                           int k_mult = 64) {
   SSR_REQUIRE(a && a->W && a->y, "%s: null argument", who);
   SSR_REQUIRE(a->N > 0 && a->groups >= 1 && a->K > 0, "%s: bad N/K/groups", who);
-  if (a->B < b_lo || a->B > b_hi || a->w_tiled != 1 || a->K % 64 != 0) return 1;
+  if (a->B < b_lo || a->B > b_hi || a->w_tiled != 1 || a->K % k_mult != 0) return 1;
   if (v1_refuses) {
     static const bool v1 = [] { const char* e = getenv("SSRHIP_GEMVM_V"); return e && atoi(e) == 1; }();
     if (v1) return 1;

@@ -113,6 +113,29 @@ def from_w8_order(P: torch.Tensor) -> torch.Tensor:
     return P.reshape(*lead, N, K // 1024, 64, 4, 4).permute(*range(n), n, n + 1, n + 3, n + 2, n + 4).contiguous().reshape(*lead, N, K)
 
 
+def to_wt8_order(Q: torch.Tensor) -> torch.Tensor:
+    """[.., N, K] 1-byte codes (K % 128 == 0) -> the packed order of the 5..16-row e4m3 weight stream (include/ssrhip.h SSRHIP_WT8_INDEX),
+    [.., ceil(N/8)*8, K] of the same dtype: rows in 8-row units (padded with code 0), K in octets of eight k-steps; the 512-byte block
+    (unit, octet, h) holds at 16-byte piece ks*8 + c, as dword g, the four codes of k-step 8o + 2g + h. One permute; nothing is rounded."""
+    *lead, N, K = Q.shape
+    assert K % 128 == 0 and Q.element_size() == 1, (K, Q.dtype)
+    U = (N + 7) // 8
+    if U * 8 != N:
+        Q = torch.cat([Q, Q.new_zeros(*lead, U * 8 - N, K)], dim=-2)
+    n = len(lead)
+    Qr = Q.reshape(*lead, U, 8, K // 128, 4, 2, 4, 4)                            # [u][c][o][g][h][ks][e]
+    return Qr.permute(*range(n), n, n + 2, n + 4, n + 5, n + 1, n + 3, n + 6).contiguous().reshape(*lead, U * 8, K)
+
+
+def from_wt8_order(P: torch.Tensor, N: int) -> torch.Tensor:
+    """Inverse of `to_wt8_order`: the packed codes [.., ceil(N/8)*8, K] -> the codes [.., N, K] in [n][k] order."""
+    *lead, NP, K = P.shape
+    U = NP // 8
+    n = len(lead)
+    Qr = P.reshape(*lead, U, K // 128, 2, 4, 8, 4, 4)                            # [u][o][h][ks][c][g][e]
+    return Qr.permute(*range(n), n, n + 4, n + 1, n + 5, n + 2, n + 3, n + 6).reshape(*lead, NP, K)[..., :N, :].contiguous()
+
+
 E4M3_MAX = 448.0              # the largest finite OCP e4m3 value (torch.float8_e4m3fn): 0.875 * 2^9
 
 
@@ -169,6 +192,35 @@ def w16_streamable(K: int) -> bool:
 def wt16_streamable(K: int) -> bool:
     """Can a matrix with this inner dimension have a SSRHIP_WT16_INDEX copy (whole quads of four k-steps)?"""
     return K > 0 and K % 64 == 0
+
+
+def wt8_streamable(K: int) -> bool:
+    """Can a matrix with this inner dimension have a SSRHIP_WT8_INDEX copy (whole octets of eight k-steps)?"""
+    return K > 0 and K % 128 == 0
+
+
+# What an unset SSRHIP_GEMVM_W8 means for a 5..16-row engine of an e4m3 arena (DecodeEngine stream_wt8=None): "1" = stream the
+# SSRHIP_WT8_INDEX codes and the scales, "0" = stream what such an engine streams without them (the fp32 streaming-order masters, or the
+# 2-byte copies under SSRHIP_GEMVM_W16). Decided by the measurement in DESIGN.md Part I.22.
+WT8_DEFAULT = "0"
+
+
+def resolve_wt8_stream(rows: int, weight_dtype: str, requested: Optional[bool], env) -> bool:
+    """Does an engine of `rows` rows on an arena of `weight_dtype` run the e4m3 weight stream of the matrix-core step (DecodeEngine
+    stream_wt8)? requested None: on iff the arena is e4m3, the engine has 5..16 rows and `env["SSRHIP_GEMVM_W8"]` (unset: WT8_DEFAULT)
+    does not start with '0'. requested True: ValueError at <= 4 rows (it names stream_w8), at more than 16 rows, then for any other arena.
+    `env` is a mapping like os.environ; nothing else is read."""
+    if requested is None:
+        return weight_dtype == "e4m3" and 5 <= rows <= 16 and env.get("SSRHIP_GEMVM_W8", WT8_DEFAULT)[:1] != "0"
+    if not requested:
+        return False
+    if rows <= 4:
+        raise ValueError(f"stream_wt8 is the e4m3 weight stream of the 5..16-row step; an engine of {rows} rows takes stream_w8")
+    if rows > 16:
+        raise ValueError(f"stream_wt8: the e4m3 weight stream of the matrix-core step exists for 5..16 rows only (this engine has {rows} rows)")
+    if weight_dtype != "e4m3":
+        raise ValueError("stream_wt8 needs an arena built with weight_dtype='e4m3'")
+    return True
 
 
 # The two packed orders an arena can hold: (pack routine, which inner dimensions get a copy). A matrix's copy of order `o` lives in
@@ -504,18 +556,46 @@ class LMWeightsArena:
 
     def w8_struct(self):
         """ssrhip_lm_w8 of the packed codes and their scales (NULL pairs where a family has no packed copy)."""
+        return self._codes_struct("_w8")
+
+    def _codes_struct(self, codes: str):
+        """ssrhip_lm_w8 whose code pointers are the arena's `<family><codes>` tensors ("_w8": SSRHIP_W8_INDEX order, "_wt8": SSRHIP_WT8_INDEX)"""
         w = _lib.LMW8()
-        arrays = self._w8_arrays = {}                   # the record points into them
+        arrays = {}
+        setattr(self, codes + "_arrays", arrays)        # the record points into them
         for name in W16_FAMILIES:
-            if all(lay[name + "_w8"] is not None for lay in self.layers):
-                for suffix, field in (("_w8", name + "_w8"), ("_w8s", name + "_s")):
+            if all(lay[name + codes] is not None for lay in self.layers):
+                for suffix, field in ((codes, name + "_w8"), ("_w8s", name + "_s")):
                     arrays[field] = (C.c_void_p * self.L)(*[lay[name + suffix].data_ptr() for lay in self.layers])
                     setattr(w, field, C.cast(arrays[field], C.POINTER(C.c_void_p)))
         for h in ("head1", "head2"):
-            if getattr(self, h + "_w8") is not None:
-                setattr(w, h + "_w8", getattr(self, h + "_w8").data_ptr())
+            if getattr(self, h + codes) is not None:
+                setattr(w, h + "_w8", getattr(self, h + codes).data_ptr())
                 setattr(w, h + "_s", getattr(self, h + "_w8s").data_ptr())
         return w
+
+    def ensure_wt8_copies(self) -> bool:
+        """Packed e4m3 codes in streaming order (`to_wt8_order` of `e4m3_codes(master, scale)`, exact) of the six matrix families for the
+        5..16-row decode step of an e4m3 arena (+1 byte per weight = +0.82 GB at 830M beside the scales and the fp32 streaming copies, built
+        once on first use). A family whose inner dimension is no multiple of 128 (`wt8_streamable`) gets none and streams its fp32
+        streaming-order copy. Returns True when created now."""
+        if self.weight_dtype != "e4m3":
+            raise ValueError("packed e4m3 codes need an arena built with weight_dtype='e4m3' (the masters must hold codes * scale)")
+        if getattr(self, "_wt8_ready", False):
+            return False
+        pack = lambda Wm, sc: to_wt8_order(e4m3_codes(Wm, sc)) if wt8_streamable(Wm.shape[-1]) else None
+        for lay in self.layers:
+            for name in W16_FAMILIES:
+                lay[name + "_wt8"] = pack(lay[name + "_w"], lay[name + "_w8s"])
+        self.head1_wt8 = pack(self.head1_w, self.head1_w8s)
+        self.head2_wt8 = pack(self.head2_w, self.head2_w8s)
+        self._wt8_ready = True
+        self.generation += 1
+        return True
+
+    def wt8_struct(self):
+        """ssrhip_lm_w8 of the SSRHIP_WT8_INDEX codes and their scales for ssrhip_lm_set_wt8 (NULL pairs where a family has no packed copy)."""
+        return self._codes_struct("_wt8")
 
     def ensure_wt16_copies(self) -> bool:
         """Packed bf16 streaming-order copies (`to_wt16_order`) of the six matrix families for the 5..32-row decode step of a bf16 arena
@@ -616,7 +696,7 @@ class LMWeightsArena:
         """Algorithmic weight bytes one decode step must stream."""
         n = 0
         for lay in self.layers:
-            n += sum(t.numel() for k, t in lay.items() if not k.endswith(("_wt", "_ws", "_w16", "_wt16", "_w8", "_w8s")))     # incl. the (now constant) LayerNorm vectors, as SURVEY §8d counts them
+            n += sum(t.numel() for k, t in lay.items() if not k.endswith(("_wt", "_ws", "_w16", "_wt16", "_w8", "_w8s", "_wt8")))     # incl. the (now constant) LayerNorm vectors, as SURVEY §8d counts them
         n += self.lnf_w.numel() + self.lnf_b.numel()
         n += self.head1_w.numel() + self.head1_b.numel() + self.head2_w.numel() + self.head2_b.numel()
         n += (self.K + 1) * self.D  # K embedding rows + one pe row
@@ -625,9 +705,10 @@ class LMWeightsArena:
         if order is not None:
             half = sum(lay[name + "_w"].numel() for lay in self.layers for name in W16_FAMILIES if lay[f"{name}_{order}"] is not None)
             half += sum(m.numel() for m, h in ((self.head1_w, "head1_"), (self.head2_w, "head2_")) if getattr(self, h + order) is not None)
-        if getattr(self, "_w8_ready", False):       # a family with packed e4m3 codes streams 1 byte per weight and one fp32 scale per output row
-            fams = [(lay[name + "_w"], lay[name + "_w8"], lay[name + "_w8s"]) for lay in self.layers for name in W16_FAMILIES]
-            fams += [(self.head1_w, self.head1_w8, self.head1_w8s), (self.head2_w, self.head2_w8, self.head2_w8s)]
+        codes = next((o for o in ("_w8", "_wt8") if getattr(self, o + "_ready", False)), None)
+        if codes is not None:                       # a family with packed e4m3 codes streams 1 byte per weight and one fp32 scale per output row
+            fams = [(lay[name + "_w"], lay[name + codes], lay[name + "_w8s"]) for lay in self.layers for name in W16_FAMILIES]
+            fams += [(self.head1_w, getattr(self, "head1" + codes), self.head1_w8s), (self.head2_w, getattr(self, "head2" + codes), self.head2_w8s)]
             return 4 * n - sum(3 * m.numel() - 4 * sc.numel() for m, q, sc in fams if q is not None)
         return 4 * n - 2 * half
 
@@ -967,7 +1048,7 @@ class DecodeEngine:
                  pool_pages: Optional[int] = None, page_order: Optional[Sequence[int]] = None, pair_mode: int = 0,
                  stream_w16: Optional[bool] = None, stream_wt16: Optional[bool] = None, stream_wt32: Optional[bool] = None,
                  kv_dtype: Optional[str] = None, share_prompt: Optional[bool] = None, stream_w8: Optional[bool] = None,
-                 pair_w16: Optional[bool] = None, pair_w8: Optional[bool] = None):
+                 pair_w16: Optional[bool] = None, pair_w8: Optional[bool] = None, stream_wt8: Optional[bool] = None):
         """max_seq: longest sequence (text + audio positions) any ONE row may reach; pool_pages: physical KV pages shared by all
         rows (default rows x pages-per-row, the no-sharing worst case; a batch of short and long utterances needs only the sum
         of their own page counts). pair_mode (2-row engines; include/ssrhip.h ssrhip_lm_buffers): 0 = pair launches if this engine
@@ -982,6 +1063,11 @@ class DecodeEngine:
         step streams the arena's packed e4m3 codes and scales (include/ssrhip.h ssrhip_lm_set_w8; needs an e4m3 arena and <= 4 rows, steps
         unpaired unless pair_w8 opts in); None = on when the arena is e4m3, the engine has <= 4 rows and `SSRHIP_GEMV_W8` (read here) does not start with '0'; off,
         such an engine streams its fp32 masters and may pair. stream_w8=True with stream_w16=True is a ValueError.
+        stream_wt8 (`resolve_wt8_stream`): the 5..16-row matrix-core step streams the arena's e4m3 codes in SSRHIP_WT8_INDEX order and their
+        scales (include/ssrhip.h ssrhip_lm_set_wt8; needs an e4m3 arena and 5..16 rows; the fp32 streaming-order copies stay the fallback);
+        None = on when the arena is e4m3, the engine has 5..16 rows and `SSRHIP_GEMVM_W8` (read here; unset = WT8_DEFAULT) does not start
+        with '0'. An engine whose stream_wt8 resolves on leaves stream_wt16 off unless it was asked for; stream_wt8=True with
+        stream_wt16=True is a ValueError. Same tokens, bit for bit, as the same arena's masters.
         pair_w16 (2-row engines that stream w16; `resolve_w16_pair`): the step runs the pair launches over the packed copies
         (include/ssrhip.h ssrhip_lm_set_w16_pair) if the library lets this engine pair (`pairing`, `pairing_why`); None = on when
         `SSRHIP_GEMV_W16_PAIR` (read here; unset = W16_PAIR_DEFAULT) does not start with '0'. Same tokens, bit for bit, either way.
@@ -1008,6 +1094,11 @@ class DecodeEngine:
         if stream_w8 and stream_w16:
             raise ValueError("stream_w8 and stream_w16 are two weight streams of the <= 4-row step; an engine takes one")
         self.stream_w8 = resolve_w8_stream(self.B, arena.weight_dtype, stream_w8, os.environ)
+        if stream_wt8 and stream_wt16:
+            raise ValueError("stream_wt8 and stream_wt16 are two weight streams of the 5..16-row step; an engine takes one")
+        self.stream_wt8 = resolve_wt8_stream(self.B, arena.weight_dtype, stream_wt8, os.environ)
+        if self.stream_wt8 and stream_wt16 is None:
+            requested["wt16"] = False             # the 1-byte stream takes the step; the 2-byte copies are not built
         for st in W16_STREAMS:                    # the row ranges are disjoint: at most one is on
             # the 2-byte copies of the matrix-core step serve every bf16-valued arena; the <= 4-row bf16 stream is the bf16 arena's own
             dtype = "bf16" if (st.lo > 4 and arena.bf16_valued) else arena.weight_dtype
@@ -1027,6 +1118,8 @@ class DecodeEngine:
             arena._ensure_packed(self._stream.order)   # the step streams packed 2-byte weights (at 5..32 rows in streaming order)
         if self.stream_w8:
             arena.ensure_w8_copies()              # the step streams packed 1-byte codes and their scales
+        if self.stream_wt8:
+            arena.ensure_wt8_copies()             # the same in the streaming order of the matrix-core step
         self.max_steps = max_steps
         D, H, L, K = arena.D, arena.H, arena.L, arena.K
         self.hd = D // H
@@ -1133,6 +1226,9 @@ class DecodeEngine:
             _lib.check(self.lib.ssrhip_lm_set_w8(ctx, C.byref(rec8)), "ssrhip_lm_set_w8")
             if self.pair_w8 and self.pair_mode != 1:      # (as for pair_w16: after a give-up the engine steps unpaired)
                 _lib.check(self.lib.ssrhip_lm_set_w8_pair(ctx, 1), "ssrhip_lm_set_w8_pair")
+        if self.stream_wt8:                       # the e4m3 stream of the 5..16-row step (no pairing at these rows)
+            rec8 = self.a.wt8_struct()
+            _lib.check(self.lib.ssrhip_lm_set_wt8(ctx, C.byref(rec8)), "ssrhip_lm_set_wt8")
         if self.kv_dtype == "bf16":               # the pool's entry type travels with the pool (also for the two-phase admission's prefill)
             _lib.check(self.lib.ssrhip_lm_set_kv16(ctx, 1), "ssrhip_lm_set_kv16")
         if self.share_prompt:                     # the two arrays' pointers travel with the captured step
@@ -1188,6 +1284,12 @@ class DecodeEngine:
         """Pair launches of the last enqueued decode step that streamed e4m3 codes (2 * layers when every family has codes;
         `w8_launches_per_step` then counts the two single launches left). 0 for an engine that does not pair its e4m3 stream."""
         return self._launches_per_step("w8_pair")
+
+    @property
+    def wt8_launches_per_step(self) -> int:
+        """GEMV launches of the last enqueued decode step that ran a kernel of the 5..16-row e4m3 weight stream (4 * layers + 2 when every
+        family qualifies; 0 for an engine that streams other weights or has not stepped yet)."""
+        return self._launches_per_step("wt8")
 
     @property
     def wt16_launches_per_step(self) -> int:

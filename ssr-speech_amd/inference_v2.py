@@ -56,7 +56,8 @@ EXTRA_FLAGS = [
     ("--weight_dtype", dict(type=str, choices=["fp32", "bf16", "e4m3"], default="fp32",
                             help="bf16: round the decoder's matrices once to bf16 and stream them as 2-byte weights in the decode step "
                                  "(SSR_Speech.set_weight_dtype); e4m3: quantise them once to OCP e4m3 codes with a power-of-two scale per "
-                                 "output row and stream 1-byte weights (a coarse format: 2.6 %% rms rounding error); fp32 (default): the "
+                                 "output row and stream 1-byte weights (a coarse format: 2.6 %% rms rounding error; engines of <= 4 rows stream them, "
+                                 "batched engines of 5..16 rows with SSRHIP_GEMVM_W8=1); fp32 (default): the "
                                  "checkpoint's weights as they are")),
     ("--kv_dtype", dict(type=str, choices=["fp32", "bf16"], default="fp32",
                         help="bf16: decode engines of 5..32 rows (batched synthesis) keep their KV cache in 2-byte bf16 entries "

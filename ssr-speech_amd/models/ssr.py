@@ -241,7 +241,8 @@ class SSR_Speech(nn.Module):
         `inference_stream`, `inference_batch`, `score`, `dp.*` — computes with the rounded values; engines of <= 4 rows stream them as
         2-byte weights. "e4m3": the same families are quantised once to OCP e4m3 codes with one power-of-two scale per output row
         (engine.quantize_e4m3; a COARSE format: 2.6 % relative rms rounding error of the weights against 0.17 % for bf16); every path computes
-        with codes * scale, engines of <= 4 rows stream the 1-byte codes (`SSRHIP_GEMV_W8=0`: their fp32 masters), and whatever serves a
+        with codes * scale, engines of <= 4 rows stream the 1-byte codes (`SSRHIP_GEMV_W8=0`: their fp32 masters), engines of 5..16 rows
+        stream them when `SSRHIP_GEMVM_W8=1` opts in (engine.DecodeEngine stream_wt8; off by default, same tokens), and whatever serves a
         bf16 model's rounded weights (one-plane prefill / score, the 5..32-row streaming copies) serves these too. "fp32" (the default)
         restores today's numbers bit for bit: the arena is rebuilt from `state_dict()`. Drops the arena and the cached engines."""
         if weight_dtype not in WEIGHT_DTYPES:

@@ -29,6 +29,9 @@ engine's copies of the prompt's partial page) and the KV pages in use:
 `weight_dtype=e4m3` builds a third arena (DESIGN.md Part I.18: OCP e4m3 codes with a power-of-two scale per row; 3.3 + 0.82 GB); `w8 launches`
 is the counter of its <= 4-row stream, `SSRHIP_GEMV_W8=0` streams its fp32 masters instead, `SSRHIP_GEMV_W8_DEPTH` picks the ring:
   python tools/decode_ab.py --reps 4 fp32_paired: bf16_w16:weight_dtype=bf16 e4m3_masters:weight_dtype=e4m3,SSRHIP_GEMV_W8=0 e4m3_w8:weight_dtype=e4m3
+The e4m3 weight stream at 5..16 rows (DESIGN.md Part I.22; `SSRHIP_GEMVM_W8=1` is the opt-in, `wt8 launches` the counter; an arm is also
+compared with the first arm on the same weights and cache, here `e4m3_masters`):
+  python tools/decode_ab.py --utts 8 --greedy --warmup 180 --steps 100 --reps 4 fp32: e4m3_masters:weight_dtype=e4m3,SSRHIP_GEMVM_W16=0 e4m3_wt16:weight_dtype=e4m3,SSRHIP_GEMVM_W16=1 e4m3_wt8:weight_dtype=e4m3,SSRHIP_GEMVM_W8=1
 Pair launches over the bf16 weight stream (DESIGN.md Part I.19; `SSRHIP_GEMV_W16_PAIR=1` is the opt-in, `w16 pair launches` the counter,
 `pairing` whether the arm's engine held the pairing slot):
   python tools/decode_ab.py --reps 4 fp32: bf16_w16:weight_dtype=bf16 bf16_w16_pair:weight_dtype=bf16,SSRHIP_GEMV_W16_PAIR=1
@@ -126,6 +129,7 @@ for rep in range(a.reps):
         for st in W16_STREAMS:
             r[st.name] = getattr(eng, st.name + "_launches_per_step")
         r["w8"] = eng.w8_launches_per_step
+        r["wt8"] = eng.wt8_launches_per_step
         r["w16_pair"] = eng.w16_pair_launches_per_step
         r["w8_pair"] = eng.w8_pair_launches_per_step
         r["pairing"] = eng.pairing
@@ -150,8 +154,11 @@ print(f"# {a.steps} timed steps after {a.warmup} (context {L + T0 + a.warmup} ..
 for name, knobs in variants:
     r = res[name]
     same = "" if r["tok"] is None or res[base]["tok"] is None else f"  tokens == {base}: {bool(np.array_equal(r['tok'], res[base]['tok']))}"
+    twin = next(n for n, _ in variants if (dtype_of[n], kv_of[n], utts_of[n]) == (dtype_of[name], kv_of[name], utts_of[name]))   # the first arm on the same weights and cache
+    if twin not in (name, base) and r["tok"] is not None:
+        same += f"  tokens == {twin}: {bool(np.array_equal(r['tok'], res[twin]['tok']))}"
     U = utts_of[name]
     print(f"{name:14s} {U:2d} utts x CFG = {2 * U:2d} rows  tok/s {4 * U / (statistics.median(r['ms']) * 1e-3):9.1f}  "
           f"ms/step min {min(r['ms']):.4f} med {statistics.median(r['ms']):.4f}  all {' '.join(f'{v:.4f}' for v in r['ms'])} | "
           f"gemv {min(r['gemv']):.3f} x {r['launches']['gemv']} attn {min(r['attn']):.3f} x {r['launches']['attn']} "
-          f"sample {min(r['sample']):.3f} x {r['launches']['sample']} us{same}   [{dtype_of[name]}, kv {kv_of[name]}, {' + '.join(f'{r[st.name]} {st.name}' for st in W16_STREAMS)} + {r['w8']} w8 + {r['w16_pair']} w16 pair + {r['w8_pair']} w8 pair + {r['kv16']} kv16 + {r['group']} group launches; first fill {r['prefill_rows']} rows in {min(r['prefill_ms']):.2f} ms, {r['pages']} KV pages in use; share_prompt={share_of[name]}; pairing={r['pairing']}; {' '.join(f'{k}={v}' for k, v in knobs.items()) or 'defaults'}]")
+          f"sample {min(r['sample']):.3f} x {r['launches']['sample']} us{same}   [{dtype_of[name]}, kv {kv_of[name]}, {' + '.join(f'{r[st.name]} {st.name}' for st in W16_STREAMS)} + {r['w8']} w8 + {r['wt8']} wt8 + {r['w16_pair']} w16 pair + {r['w8_pair']} w8 pair + {r['kv16']} kv16 + {r['group']} group launches; first fill {r['prefill_rows']} rows in {min(r['prefill_ms']):.2f} ms, {r['pages']} KV pages in use; share_prompt={share_of[name]}; pairing={r['pairing']}; {' '.join(f'{k}={v}' for k, v in knobs.items()) or 'defaults'}]")

@@ -10,6 +10,10 @@ the arena and the engine are rebuilt for every arm of every round (the switch is
   python tools/dp64_group_ab.py --wt16 --reps 2 --out profiles/wt16_dp64_group8.json
 `--wt32` is the same comparison at group 16 = 32 rows (the two-panel step's bf16 stream, DESIGN.md Part I.12; identical tokens asserted):
   python tools/dp64_group_ab.py --wt32 --reps 2 --out profiles/wt32_dp64_group16.json
+`--wt8` compares, at group 8 = 16 rows, three arms of an e4m3 model (DESIGN.md Part I.22): the fp32 streaming-order masters
+(SSRHIP_GEMVM_W16=0), the 2-byte copies (SSRHIP_GEMVM_W16=1) and the 1-byte codes (SSRHIP_GEMVM_W8=1); per arm the decode wall times, their
+median and spread (max - min); identical tokens asserted:
+  python tools/dp64_group_ab.py --wt8 --reps 3 --out profiles/wt8_dp64_group8.json
 `--kv_dtype bf16` compares, at every grouping of --groups, the model with its fp32 KV cache against `set_kv_dtype("bf16")` (DESIGN.md Part
 I.14), the arms alternating within a round; per arm the decode wall times, their median and spread (max - min), and whether the two arms
 chose the same tokens (not expected: the cache type changes the numerics):
@@ -37,6 +41,7 @@ ap.add_argument("--groups", default="8,16")
 ap.add_argument("--out", default=None)
 ap.add_argument("--wt16", action="store_true", help="bf16 model, group 8: fp32 masters against the packed bf16 stream of the 16-row step")
 ap.add_argument("--wt32", action="store_true", help="bf16 model, group 16: fp32 masters against the packed bf16 stream of the 32-row step")
+ap.add_argument("--wt8", action="store_true", help="e4m3 model, group 8: fp32 masters against the 2-byte and the 1-byte stream of the 16-row step")
 ap.add_argument("--kv_dtype", choices=["fp32", "bf16"], default="fp32", help="bf16: at every grouping, the fp32 KV cache against the bf16 KV cache")
 a = ap.parse_args()
 
@@ -84,6 +89,47 @@ if a.wt16 or a.wt32:
                      kind + "_launches_per_step": res[name]["launches"]}
     out["tokens_identical"] = all(torch.equal(x, y) for x, y in zip(res["bf16_" + kind]["tokens"], ref))
     assert out["tokens_identical"], "the two bf16 arms must choose the same tokens"
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    sys.exit(0)
+
+if a.wt8:
+    import statistics
+    g = 8
+    arms = (("e4m3_masters", {"SSRHIP_GEMVM_W16": "0"}), ("e4m3_wt16", {"SSRHIP_GEMVM_W16": "1"}), ("e4m3_wt8", {"SSRHIP_GEMVM_W8": "1"}))
+    res = {name: {"decode_ms": [], "tokens": None} for name, _ in arms}
+    for rep in range(a.reps):
+        for name, env in arms:
+            for k in ("SSRHIP_GEMVM_W16", "SSRHIP_GEMVM_W8"):
+                os.environ.pop(k, None)
+            os.environ.update(env)
+            model.set_weight_dtype("fp32")
+            model.set_weight_dtype("e4m3")              # drops the arena and the engines: the next call builds them under these switches
+            dp.generate(model, utts[:2 * g], seed=0, group=g, **kw)      # untimed: arena, engine, graph capture
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            toks, _ = dp.generate(model, utts, seed=0, group=g, **kw)
+            torch.cuda.synchronize()
+            res[name]["decode_ms"].append(1000 * (time.perf_counter() - t0))
+            eng = next(iter(model._engines.values()))
+            res[name]["launches"] = {"wt16": eng.wt16_launches_per_step, "wt8": eng.wt8_launches_per_step}
+            if res[name]["tokens"] is None:
+                res[name]["tokens"] = [t.cpu() for t in toks]
+    ref = res["e4m3_masters"]["tokens"]
+    n_new = sum(int(t.shape[-1]) - 150 for t in ref)
+    out = {"workload": "bench.py dp64 input on one GPU through dp.generate (decode only, no codec), e4m3 weights", "group": g,
+           "rows_per_engine": 2 * g, "new_frames_total": n_new, "reps": a.reps}
+    for name, _ in arms:
+        ms = res[name]["decode_ms"]
+        med = statistics.median(ms)
+        out[name] = {"decode_ms": [round(v, 1) for v in ms], "median_ms": round(med, 1), "spread_ms": round(max(ms) - min(ms), 1),
+                     "codec_tokens_per_s": round(4 * n_new / (med * 1e-3), 1), "launches_per_step": res[name]["launches"]}
+    out["tokens_identical"] = all(torch.equal(x, y) for name, _ in arms[1:] for x, y in zip(res[name]["tokens"], ref))
+    assert out["tokens_identical"], "the three e4m3 arms must choose the same tokens"
     line = json.dumps(out)
     print(line)
     if a.out:

@@ -10,6 +10,11 @@ Beside each figure: the project's chain floor `2.6 us + bytes / 7.3 TB/s` (DESIG
 w_tiled) against the packed bf16 streaming-order copy (`ssrhip_gemv_wt16`) with 8 loads in flight per wave (the default) and with 16
 (`SSRHIP_GEMVM_W16_DEPTH=16`, set by the tool for that arm), activations in the tiled layout as the step keeps them.
     python tools/w16_launch_bench.py --rows 16 --out profiles/wt16_launch_bench_rows16.json
+At these rows the masters are e4m3-valued (codes * scale, bf16-representable), and a fourth arm streams the 1-byte codes in
+SSRHIP_WT8_INDEX order with their scales (`ssrhip_gemv_wt8`, DESIGN.md Part I.22). Beside it: its chain floor
+`2.6 us + (codes + scales) / 7.3 TB/s`, the matrix-core time of the launch `2 * 16 * N * K flop / 157.3 TFLOP/s` (the panel is multiplied
+whole), and which of the two is larger (`wt8_bound_by`: "bytes" or "matrix").
+    python tools/w16_launch_bench.py --rows 16 --out profiles/wt8_launch_bench_rows16.json
 `--rows 17..32` measures the two-panel step's launches (DESIGN.md Part I.12): the fp32 streaming-order copy against the same packed copy
 through `ssrhip_gemv_wt32`, two panels of tiled activations; beside the byte floors it prints the matrix-core time of the launch,
 `2 * rows_padded * N * K flop / 157.3 TFLOP/s` (rows_padded = 32: both panels are multiplied whole).
@@ -32,7 +37,7 @@ import torch  # noqa: E402
 
 import ssr_speech_amd  # noqa: E402,F401
 from ssr_speech_amd import _lib  # noqa: E402
-from ssr_speech_amd.engine import PACKED_ORDERS, W16_STREAMS, e4m3_master, quantize_e4m3, to_streaming_order, to_w8_order  # noqa: E402
+from ssr_speech_amd.engine import PACKED_ORDERS, W16_STREAMS, e4m3_master, quantize_e4m3, to_streaming_order, to_w8_order, to_wt8_order  # noqa: E402
 
 # name, G, N, K, prologue, activation, epilogue: the six launches of the 830M step
 SHAPES = [
@@ -64,7 +69,8 @@ def main(argv=None):
     rows = []
     st = next(s for s in W16_STREAMS if s.lo <= B <= s.hi)        # the bf16 stream of these rows
     mc = st.order == "wt16"                                       # the matrix-core step: tiled activations, streaming-order weights
-    forms = ("fp32", st.name) + (("wt16_depth16",) if st.name == "wt16" else ()) + (tuple(W8_DEPTHS) if w8 else ())
+    wt8 = st.name == "wt16"                                       # 5..16 rows: the e4m3 stream of the matrix-core step is a fourth arm
+    forms = ("fp32", st.name) + (("wt16_depth16", "wt8") if wt8 else ()) + (tuple(W8_DEPTHS) if w8 else ())
     to_packed, gemv_packed = PACKED_ORDERS[st.order][0], getattr(L, "ssrhip_gemv_" + st.name)
     xrows = 32 if B > 16 else 16 if mc else B                     # (tiled: 16 columns per panel, any values)
     for name, G, N, K, pro, act, epi in SHAPES:
@@ -72,10 +78,10 @@ def main(argv=None):
             pro = _lib.PRO_NONE                                   # at 5..32 rows the split-KV merge is a launch of its own
         ny = K if epi == _lib.EPI_QKV_APPEND else G * N
         masters = [(torch.randn(G, N, K, device=dev, generator=g) / K ** 0.5).to(torch.bfloat16).float() for _ in range(opt.chain)]
-        if w8:                                                    # masters = codes * scale: bf16-representable, so the bf16 arm streams the same values
+        if w8 or wt8:                                             # masters = codes * scale: bf16-representable, so the bf16 arm streams the same values
             quant = [quantize_e4m3(m) for m in masters]
             masters = [e4m3_master(q, sc) for q, sc in quant]
-            packed8, scales = [to_w8_order(q) for q, _ in quant], [sc.contiguous() for _, sc in quant]
+            packed8, scales = [(to_wt8_order if wt8 else to_w8_order)(q) for q, _ in quant], [sc.contiguous() for _, sc in quant]
             del quant
         packed = [to_packed(m) for m in masters]
         if mc:
@@ -122,6 +128,9 @@ def main(argv=None):
                     a = args_of(i)
                     if form == "fp32":
                         _lib.check(L.ssrhip_gemv(C.byref(a), _lib.stream_ptr()))
+                    elif form == "wt8":
+                        rc = L.ssrhip_gemv_wt8(C.byref(a), packed8[i].data_ptr(), scales[i].data_ptr(), _lib.stream_ptr())
+                        assert rc == 0, (name, rc, L.ssrhip_last_error())
                     elif form in W8_DEPTHS:
                         rc = L.ssrhip_gemv_w8(C.byref(a), packed8[i].data_ptr(), scales[i].data_ptr(), _lib.stream_ptr())
                         assert rc == 0, (name, rc, L.ssrhip_last_error())
@@ -159,13 +168,17 @@ def main(argv=None):
             row["w8_floor_us"] = round(floor(nw + 4 * G * N), 2)
         for form in forms[1:]:
             row[form + "_us"] = round(us[form], 2)
-            row[form + "_TBps"] = round(((nw + 4 * G * N) if form in W8_DEPTHS else 2 * nw) / us[form] / 1e6, 2)
+            row[form + "_TBps"] = round(((nw + 4 * G * N) if form in W8_DEPTHS or form == "wt8" else 2 * nw) / us[form] / 1e6, 2)
+        if wt8:                                                  # one panel of fp32 MFMA work against 1-byte weights: bytes or flops?
+            row["wt8_floor_us"] = round(floor(nw + 4 * G * N), 2)
+            row["mfma_us"] = round(2 * 16 * nw / 157.3e6, 2)
+            row["wt8_bound_by"] = "matrix" if row["mfma_us"] > (nw + 4 * G * N) / 7.3e6 else "bytes"
         if B > 16:                                               # two panels of fp32 MFMA work: is the launch bound by bytes or by flops?
             row["mfma_us"] = round(2 * 32 * nw / 157.3e6, 2)     # us at 157.3 TFLOP/s = 157.3e6 flop per us
         rows.append(row)
         print(json.dumps(rows[-1]), flush=True)
         del masters, packed
-        if w8:
+        if w8 or wt8:
             del packed8, scales
         torch.cuda.empty_cache()
     out = dict(tool="tools/w16_launch_bench.py", stream=opt.stream, chain=opt.chain, replays=opt.replays, depth_knob=os.environ.get("SSRHIP_GEMV_W16_DEPTH", "unset"), shapes=rows)
