@@ -299,6 +299,15 @@ int ssrhip_attn_prefill(const ssrhip_attn_args* a, const int32_t* seq_start, int
 int ssrhip_attn_rows_kv16(const ssrhip_attn_args* a, float* out /* [R][n_head*head_dim] */, ssrhip_stream_t stream);
 int ssrhip_attn_prefill_kv16(const ssrhip_attn_args* a, const int32_t* seq_start, int32_t n_seq, int32_t max_len, float* out,
                              ssrhip_stream_t stream);
+/* ssrhip_attn_decode over a 2-byte pool, for the <= 4-row decode step (opt-in: ssrhip_lm_set_kv16_small). The position row_len[r] - 1 of
+ * every row — the one this step's QKV launch appended — is NOT in the pool yet: the launch wrote it, fp32, into the landing cache `land`
+ * [R][1][2][n_head][SSRHIP_PAGE][head_dim], a->layer's K / V at position a->layer of row r's page. Every workgroup reads its (row, head)'s
+ * landing entry, rounds it to bf16 (nearest even) and uses the ROUNDED values for that position, whatever the pool holds there; the
+ * workgroup of the page that owns the position stores the rounded entries into the pool (8 bytes per lane) for later steps. `land` is
+ * not written. part_o / part_ml equal ssrhip_attn_decode's on the widened pool with the rounded landing entry at row_len[r] - 1, bit for
+ * bit. Same grid, SSRHIP_ATTN_VAT and SSRHIP_ATTN_HEAD_FASTEST as ssrhip_attn_decode, a->prefetch honoured. a->row_seq must be NULL
+ * (row r is sequence r), a->layer < SSRHIP_PAGE, R <= 65535; every contract error is answered before any HIP call. */
+int ssrhip_attn_decode_kv16(const ssrhip_attn_args* a, const float* land, ssrhip_stream_t stream);
 /* ssrhip_attn_rows for rows that SHARE their first pages (the samples of one utterance, opt-in: ssrhip_lm_set_prompt_groups; fp32 entries
  * only). chunk_head / n_shared are DEVICE arrays of R ints: chunk_head[r] = the lowest row of r's chunk, a chunk being at most
  * ssrhip_attn_group_members() rows whose first n_shared[head] table entries name the same physical pages (any rows, in any mix of lengths;
@@ -733,8 +742,22 @@ int ssrhip_lm_set_prefill_w1(ssrhip_lm* lm, int32_t on);
  * SSRHIP_PREFILL_ATTN_ROWWISE) is an error. So every attention of the engine sees bf16-valued K/V, whichever path wrote them.
  * Refused (< 0) for engines of <= 4 rows, of more than 256 pages per row, and engines whose decode step is already captured. */
 int ssrhip_lm_set_kv16(ssrhip_lm* lm, int32_t on);
-/* how many attention launches of the last enqueued (or captured) decode step ran ssrhip_attn_rows_kv16 (n_layer for a kv16 engine, else 0) */
+/* how many attention launches of the last enqueued (or captured) decode step ran ssrhip_attn_rows_kv16 — or, at <= 4 rows,
+ * ssrhip_attn_decode_kv16 (n_layer for an engine with a 2-byte cache, else 0) */
 int ssrhip_lm_kv16_launches(const ssrhip_lm* lm);
+/* The same statement for engines of 1, 2 or 4 rows (opt-in, DESIGN.md Part I.23): the pool of ssrhip_lm_buffers.kv holds 2-byte entries,
+ * and the caller hands over three DEVICE buffers it owns and has filled ONCE:
+ *   land        [B][1][2][n_head][SSRHIP_PAGE][head_dim] fp32 — a one-layer cache of B pages in the pool's layout (contents: anything);
+ *   land_table  [B] int32, land_table[b] = b;
+ *   land_pos    [n_layer][B] int32, land_pos[l * B + b] = l.
+ * The QKV launch of layer l keeps SSRHIP_EPI_QKV_APPEND — no GEMV or pair kernel knows of this — with a descriptor that names the landing
+ * cache: kv = {land, land_table, max_pages 1, n_layer 1, n_head, head_dim}, layer 0, kv_pos = land_pos + l * B, so layer l's K / V of row b
+ * land at position l of page b. The attention launch is ssrhip_attn_decode_kv16, which rounds them once and promotes them into the pool.
+ * ssrhip_lm_prefill scatters with ssrhip_kv_scatter16 and attends with ssrhip_attn_prefill_kv16 (tiled only, as for ssrhip_lm_set_kv16).
+ * Nothing changes between steps, so the captured step replays. NULL, NULL, NULL: off. Refused (< 0) for engines of more than 4 rows
+ * (they take ssrhip_lm_set_kv16), of more than SSRHIP_PAGE layers, with SSRHIP_PREFILL_ATTN_ROWWISE set, after the step is captured, and
+ * for one pointer without the others. */
+int ssrhip_lm_set_kv16_small(ssrhip_lm* lm, float* land, const int32_t* land_table, const int32_t* land_pos);
 /* Prompt sharing (opt-in, 5..32-row fp32-cache engines, at most 256 pages per row): two DEVICE arrays of B ints the caller owns and
  * rewrites between steps (see ssrhip_attn_rows_group), or NULL, NULL for off. Call it before the first ssrhip_lm_decode (the captured step
  * keeps the pointers). With it set every layer's attention of the decode step is ssrhip_attn_rows_group (also at 5..11 rows x 16 heads,

@@ -219,6 +219,7 @@ SYMBOLS = [
     ("ssrhip_attn_prefill", C.c_int, [C.POINTER(AttnArgs), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     ("ssrhip_attn_rows_kv16", C.c_int, [C.POINTER(AttnArgs), C.c_void_p, C.c_void_p]),
     ("ssrhip_attn_prefill_kv16", C.c_int, [C.POINTER(AttnArgs), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    ("ssrhip_attn_decode_kv16", C.c_int, [C.POINTER(AttnArgs), C.c_void_p, C.c_void_p]),
     ("ssrhip_attn_rows_group", C.c_int, [C.POINTER(AttnArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("ssrhip_attn_group_members", C.c_int, []),
     ("ssrhip_attn_rows_group_m", C.c_int, [C.POINTER(AttnArgs), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
@@ -253,6 +254,7 @@ SYMBOLS = [
     ("ssrhip_lm_set_prefill_w1", C.c_int, [C.c_void_p, C.c_int32]),
     ("ssrhip_lm_set_kv16", C.c_int, [C.c_void_p, C.c_int32]),
     ("ssrhip_lm_kv16_launches", C.c_int, [C.c_void_p]),
+    ("ssrhip_lm_set_kv16_small", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("ssrhip_lm_set_prompt_groups", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ("ssrhip_lm_group_launches", C.c_int, [C.c_void_p]),
     ("ssrhip_lm_set_group_members", C.c_int, [C.c_void_p, C.c_int32]),

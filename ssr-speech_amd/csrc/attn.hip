@@ -33,6 +33,11 @@ __device__ __forceinline__ uint2 ld_kv(const uint16_t* p) {
   const v2u v = __builtin_nontemporal_load(reinterpret_cast<const v2u*>(p));
   return make_uint2(v.x, v.y);
 }
+// the same load at a 32-bit BYTE offset from a workgroup-uniform base (attn_decode_kernel's 2-byte form): the request takes the base from
+// scalar registers and one VGPR of offset where a 64-bit lane address takes two — 16 K and 16 V rows in flight cost 32 registers less
+__device__ __forceinline__ uint2 ld_kv_at(const uint16_t* base, const unsigned byte_off) {
+  return ld_kv(reinterpret_cast<const uint16_t*>(reinterpret_cast<const char*>(base) + byte_off));
+}
 __device__ __forceinline__ float4 kv_f4(const float4 v) { return v; }
 __device__ __forceinline__ float4 kv_f4(const uint2 v) { return bf16x4_widen(v); }
 template <bool KV16> struct kv_types { typedef float elem; typedef float4 vec; };
@@ -79,8 +84,19 @@ __device__ __forceinline__ attn_state attn_merge_waves(const float (&sm)[NW][HD 
   return attn_state{M, L, acc};
 }
 
-template <int HD, bool SEQ, int VAT = -1>   // SEQ: rows carry an explicit sequence id (a.row_seq != NULL: the per-row prefill path); the decode step has none
-__global__ __launch_bounds__(256) void attn_decode_kernel(const ssrhip_attn_args a, const int head_fastest) {   // VAT: see the V requests below
+// KV16 (ssrhip_attn_decode_kv16, the <= 4-row step of an engine with a bf16 cache, DESIGN.md Part I.23): a.kv.pool holds 2-byte entries (same element
+// offsets), a lane's 8-byte load holds the 4 features its 16-byte load held, kept packed and widened where they are folded. The position
+// this step's QKV launch appended, row_len[r] - 1, is not in the pool yet: the launch wrote it, fp32, into the landing cache `land`
+// [R][1][2][n_head][SSRHIP_PAGE][HD], layer l at position l of row r's page. Every workgroup requests its (row, head)'s landing entry beside q
+// (the address is arithmetic on kernel arguments: no scalar round trip in front of it), rounds it to nearest even and takes the ROUNDED
+// values wherever its key index is len - 1 - base — the clamped lanes included — so nothing the pool holds at that position (stale, or
+// never written) reaches the arithmetic; the one workgroup that owns the position (split == (len - 1) / SSRHIP_PAGE) stores the rounded 8
+// bytes into the pool for the steps to come. No other workgroup of the launch touches these entries. `land` is not read otherwise.
+template <int HD, bool SEQ, int VAT = -1, bool KV16 = false>   // SEQ: rows carry an explicit sequence id (a.row_seq != NULL: the per-row prefill path); the decode step has none
+__global__ __launch_bounds__(256) void attn_decode_kernel(const ssrhip_attn_args a, const int head_fastest, const float* land) {   // VAT: see the V requests below
+  static_assert(!(KV16 && SEQ), "the landing cache belongs to the decode step: row r is sequence r");
+  typedef typename kv_types<KV16>::elem kv_elem;
+  typedef typename kv_types<KV16>::vec kv_vec;
   typedef attn_geom<HD, 4> G;
   constexpr int LPK = G::LPK, KPI = G::KPI, NI = G::NI;   // 4 waves: 32 keys of the page each
   __shared__ __attribute__((aligned(16))) float sm[4][HD + 4];   // row stride keeps float4 stores 16-B aligned
@@ -109,6 +125,13 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const ssrhip_attn_args
   const int page = SEQ ? c_tab[(size_t)c_seq[r] * a.kv.max_pages + split]      // rows mapped to another sequence: one more round trip
                        : c_tab[(size_t)r * a.kv.max_pages + split];            // the row's own sequence (decode step): together with its length
   const float4 q = ld4(a.q + (size_t)r * (a.q_stride ? a.q_stride : H * HD) + h * HD + c4);
+  [[maybe_unused]] float4 lk4, lv4;   // KV16: this (row, head)'s landing entry, K and V
+  if constexpr (KV16) {
+    const float* lk = land + ((((size_t)r * 2 + 0) * H + h) * SSRHIP_PAGE + a.layer) * HD + c4;
+    lk4 = ld4(lk);
+    lv4 = ld4(lk + (size_t)H * SSRHIP_PAGE * HD);
+  }
+  [[maybe_unused]] float pfj = 0.f;   // KV16: where the prefetch touches land (see there)
   if (!SEQ && a.prefetch) {
     // Round 6: this launch is latency-bound (a few dependent round trips for 10 MB of K / V) and most of its workgroups at short contexts
     // have nothing to do at all, while the launch behind it starts by streaming 64 KB of W_o per CU from HBM. Workgroup i touches the
@@ -118,18 +141,27 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const ssrhip_attn_args
     if (wg < 256u) {
       const float* pf = a.prefetch + (size_t)wg * a.prefetch_floats + threadIdx.x * 4;
       for (int i = 0; i < a.prefetch_floats; i += 1024) {
-        float4 junk;
-        asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(junk) : "v"(pf + i) : "memory");
+        if constexpr (KV16) {
+          // the same touch, into registers that stay LIVE until the first K row has arrived (`pfj` is an operand of the statement that
+          // consumes the landing entry below). The statement of the fp32 instantiations hides its load from the compiler, which is then
+          // free to reuse the destination while the load is in flight; in this instantiation it did, for the K rows' addresses (read off
+          // the ISA), and the late data sent those requests anywhere. Requests return in order: once a K row is here, so is every touch.
+          // One dword per lane touches the same cache lines as the 16 bytes (the lanes are 16 bytes apart) and keeps one register, not four.
+          asm volatile("global_load_dword %0, %1, off" : "+v"(pfj) : "v"(pf + i) : "memory");
+        } else {
+          float4 junk;
+          asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(junk) : "v"(pf + i) : "memory");
+        }
       }
     }
   }
   asm volatile("; row length and page id arrive together" :: "s"(len), "s"(page));
   const int base = split * SSRHIP_PAGE;
   if (base >= len) return;            // uniform per block
-  const float* kp = a.kv.pool + ((((size_t)page * a.kv.n_layer + a.layer) * 2 + 0) * H + h) * SSRHIP_PAGE * HD;
-  const float* vp = kp + (size_t)H * SSRHIP_PAGE * HD;
+  const kv_elem* kp = reinterpret_cast<const kv_elem*>(a.kv.pool) + ((((size_t)page * a.kv.n_layer + a.layer) * 2 + 0) * H + h) * SSRHIP_PAGE * HD;
+  const kv_elem* vp = kp + (size_t)H * SSRHIP_PAGE * HD;
 
-  float4 kk[NI], vv[NI];
+  kv_vec kk[NI], vv[NI];
   float s[NI];
   // unconditional loads: keys beyond the row's length are read from the last valid key of the page instead (their scores are
   // masked to -inf below, so p == 0 and the duplicate V rows add nothing). Predicated loads would make hipcc drain the
@@ -138,8 +170,34 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const ssrhip_attn_args
 #pragma unroll
   for (int i = 0; i < NI; ++i) {
     const int j = min(wave * 32 + i * KPI + sub, jmax);
-    kk[i] = ld_kv(kp + (size_t)j * HD + c4);
+    if constexpr (KV16) kk[i] = ld_kv_at(kp, (unsigned)(j * HD + c4) * 2u);
+    else kk[i] = ld_kv(kp + (size_t)j * HD + c4);
   }
+  // KV16: the appended position's index in this page (>= SSRHIP_PAGE: another workgroup's page) and its rounded entries. K and V of key
+  // i as the arithmetic sees them: the rounded landing entry where the lane's (clamped) key index is that position, the pool's otherwise.
+  // The landing entry was requested in front of the K rows and is consumed once the first K row has arrived (the empty statement ties it
+  // to kk[0]; requests return in order, so it waits for nothing the first score does not wait for): left alone, hipcc hoists the rounding
+  // — and with it a wait for the landing entry — above the first K request (read off the ISA): one more round trip in a row.
+  const int jl = len - 1 - base;
+  [[maybe_unused]] kv_vec lk16, lv16;
+  if constexpr (KV16) {
+    asm volatile("; the landing entry is consumed behind the first K row"
+                 : "+v"(lk4.x), "+v"(lk4.y), "+v"(lk4.z), "+v"(lk4.w), "+v"(lv4.x), "+v"(lv4.y), "+v"(lv4.z), "+v"(lv4.w), "+v"(kk[0].x), "+v"(pfj));
+    lk16 = bf16x4_rne(lk4.x, lk4.y, lk4.z, lk4.w);
+    lv16 = bf16x4_rne(lv4.x, lv4.y, lv4.z, lv4.w);
+  }
+  // (in the owning workgroup jl == jmax: key i of this lane is the appended position, itself or clamped onto it, from its first index at or
+  // past jmax on; one compare with a constant per key)
+  const int first_landed = (jl == jmax) ? (jmax - wave * 32 - sub + KPI - 1) / KPI : NI;
+  auto landed = [&](const int i) { return i >= first_landed; };
+  auto key = [&](const int i) {
+    if constexpr (KV16) return kv_f4(make_uint2(landed(i) ? lk16.x : kk[i].x, landed(i) ? lk16.y : kk[i].y));
+    else return kk[i];
+  };
+  auto val = [&](const int i) {
+    if constexpr (KV16) return kv_f4(make_uint2(landed(i) ? lv16.x : vv[i].x, landed(i) ? lv16.y : vv[i].y));
+    else return vv[i];
+  };
   // VAT >= 0: the V rows are requested when VAT of the wave's NI K rows have been consumed — pinned with scheduling fences; -1 leaves the
   // order to hipcc (which keeps ~10 K requests in flight and asks for the V rows behind the LAST K row, see below). Measured at head_dim
   // 128 on the 830M step, same box, alternating engines (profiles/r05_microbench/decode_ab_attn_vat.log): hipcc 6.84 us per launch,
@@ -148,13 +206,14 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const ssrhip_attn_args
   if constexpr (VAT >= 0) {
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int i = 0; i < VAT; ++i) s[i] = dot4(q, kk[i], 0.f);
+    for (int i = 0; i < VAT; ++i) s[i] = dot4(q, key(i), 0.f);
     __builtin_amdgcn_sched_barrier(0);
   }
 #pragma unroll
   for (int i = 0; i < NI; ++i) {
     const int j = min(wave * 32 + i * KPI + sub, jmax);
-    vv[i] = ld_kv(vp + (size_t)j * HD + c4);
+    if constexpr (KV16) vv[i] = ld_kv_at(vp, (unsigned)(j * HD + c4) * 2u);
+    else vv[i] = ld_kv(vp + (size_t)j * HD + c4);
   }
   if constexpr (VAT >= 0) __builtin_amdgcn_sched_barrier(0);
   // What hipcc makes of the two loops above (read off the ISA, round 5; rounds 1-4 believed all 2 NI requests fly together): its
@@ -164,7 +223,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const ssrhip_attn_args
   // decode_ab.log, variants r4sched / pin) — SLOWER: with K first the score / softmax arithmetic runs under the V rows' flight, while 64 KB
   // + 64 KB requested at once arrive together behind one CU's 64 B/clk port and leave nothing to overlap. The compiler's order stays.
 #pragma unroll
-  for (int i = (VAT >= 0 ? VAT : 0); i < NI; ++i) s[i] = dot4(q, kk[i], 0.f);
+  for (int i = (VAT >= 0 ? VAT : 0); i < NI; ++i) s[i] = dot4(q, key(i), 0.f);
   // reduce each s[i] over the LPK lanes of its key row (DPP row rotations + permlane16_swap: no LDS)
 #pragma unroll
   for (int i = 0; i < NI; ++i) s[i] = (LPK == 32) ? half32_sum(s[i]) : row16_sum(s[i]);
@@ -183,11 +242,19 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const ssrhip_attn_args
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
       const float p = expf(s[i] - m);   // exp(-inf) == 0 for masked keys
+      const float4 v4 = val(i);
       l += p;
-      o4.x = fmaf(p, vv[i].x, o4.x);
-      o4.y = fmaf(p, vv[i].y, o4.y);
-      o4.z = fmaf(p, vv[i].z, o4.z);
-      o4.w = fmaf(p, vv[i].w, o4.w);
+      o4.x = fmaf(p, v4.x, o4.x);
+      o4.y = fmaf(p, v4.y, o4.y);
+      o4.z = fmaf(p, v4.z, o4.z);
+      o4.w = fmaf(p, v4.w, o4.w);
+    }
+  }
+  if constexpr (KV16) {
+    // the workgroup that owns the appended position promotes it: the rounded 8 bytes per lane into the pool, behind every load of this wave
+    if (jl < SSRHIP_PAGE && wave == 0 && sub == 0) {
+      *reinterpret_cast<uint2*>(const_cast<kv_elem*>(kp) + (size_t)jl * HD + c4) = lk16;
+      *reinterpret_cast<uint2*>(const_cast<kv_elem*>(vp) + (size_t)jl * HD + c4) = lv16;
     }
   }
   attn_wave_sum<LPK>(l, o4);
@@ -822,15 +889,37 @@ extern "C" int ssrhip_attn_decode(const ssrhip_attn_args* a, ssrhip_stream_t str
     const dim3 grid(hf ? s.kv.n_head : s.max_splits, hf ? s.max_splits : s.kv.n_head, n);
     dispatch_int<64, 128>(s.kv.head_dim, [&](auto HD) {
       constexpr int hd = decltype(HD)::value;
-      if (s.row_seq) hipLaunchKernelGGL((attn_decode_kernel<hd, true>), grid, dim3(256), 0, (hipStream_t)stream, s, hf);
+      if (s.row_seq) hipLaunchKernelGGL((attn_decode_kernel<hd, true>), grid, dim3(256), 0, (hipStream_t)stream, s, hf, nullptr);
       else if constexpr (hd == 128)
         dispatch_int<-1, 4, 8, 12>(k.vat, [&](auto VAT) {
-          hipLaunchKernelGGL((attn_decode_kernel<128, false, decltype(VAT)::value>), grid, dim3(256), 0, (hipStream_t)stream, s, hf);
+          hipLaunchKernelGGL((attn_decode_kernel<128, false, decltype(VAT)::value>), grid, dim3(256), 0, (hipStream_t)stream, s, hf, nullptr);
         });
-      else hipLaunchKernelGGL((attn_decode_kernel<hd, false>), grid, dim3(256), 0, (hipStream_t)stream, s, hf);
+      else hipLaunchKernelGGL((attn_decode_kernel<hd, false>), grid, dim3(256), 0, (hipStream_t)stream, s, hf, nullptr);
     });
     SSR_LAUNCH_CHECK();
   }
+  return 0;
+}
+
+// The split kernel over a 2-byte pool with the landing cache of the <= 4-row step (attn_decode_kernel<HD, false, VAT, true>): the grid, the
+// VAT choice and the grid order of ssrhip_attn_decode. Every contract error is answered before any HIP call.
+extern "C" int ssrhip_attn_decode_kv16(const ssrhip_attn_args* a, const float* land, ssrhip_stream_t stream) {
+  if (int e = check(a, "ssrhip_attn_decode_kv16")) return e;
+  SSR_REQUIRE(a->part_o && a->part_ml, "ssrhip_attn_decode_kv16: null partial buffers");
+  SSR_REQUIRE(land, "ssrhip_attn_decode_kv16: null landing cache");
+  SSR_REQUIRE(!a->row_seq, "ssrhip_attn_decode_kv16: row_seq must be NULL (row r is sequence r: the landing cache has one page per row)");
+  SSR_REQUIRE(a->R <= MAX_GRID_ROWS, "ssrhip_attn_decode_kv16: more than %d rows", MAX_GRID_ROWS);
+  SSR_REQUIRE(a->layer >= 0 && a->layer < SSRHIP_PAGE && a->layer < a->kv.n_layer,
+              "ssrhip_attn_decode_kv16: layer %d outside the cache's %d layers or the landing page's %d positions", a->layer, a->kv.n_layer, SSRHIP_PAGE);
+  const attn_knobs k = read_attn_knobs();
+  const int hf = k.head_fastest;
+  const dim3 grid(hf ? a->kv.n_head : a->max_splits, hf ? a->max_splits : a->kv.n_head, a->R);
+  if (a->kv.head_dim == 128)
+    dispatch_int<-1, 4, 8, 12>(k.vat, [&](auto VAT) {
+      hipLaunchKernelGGL((attn_decode_kernel<128, false, decltype(VAT)::value, true>), grid, dim3(256), 0, (hipStream_t)stream, *a, hf, land);
+    });
+  else hipLaunchKernelGGL((attn_decode_kernel<64, false, -1, true>), grid, dim3(256), 0, (hipStream_t)stream, *a, hf, land);
+  SSR_LAUNCH_CHECK();
   return 0;
 }
 

@@ -84,7 +84,13 @@ struct ssrhip_lm {
   const uint8_t* pk8_head1 = nullptr; const uint8_t* pk8_head2 = nullptr;
   const float* pk8s_head1 = nullptr; const float* pk8s_head2 = nullptr;
   bool kv16 = false;            // b.kv.pool holds 2-byte entries (ssrhip_lm_set_kv16: the caller's statement about its buffer)
-  int kv16_launches = 0;        // attention launches of the last enqueued step that ran ssrhip_attn_rows_kv16 (ssrhip_lm_kv16_launches)
+  int kv16_launches = 0;        // attention launches of the last enqueued step that read 2-byte entries: ssrhip_attn_rows_kv16, or
+                                // ssrhip_attn_decode_kv16 at <= 4 rows (ssrhip_lm_kv16_launches)
+  // the bf16 cache of the <= 4-row step (ssrhip_lm_set_kv16_small: the caller's statement about its buffers; all null = off): b.kv.pool holds
+  // 2-byte entries, the QKV launch appends fp32 into the landing cache and the attention launch promotes from there
+  float* land = nullptr;                 // [B][1][2][n_head][SSRHIP_PAGE][head_dim] fp32: layer l at position l of row b's page
+  const int32_t* land_table = nullptr;   // [B]: land_table[b] = b
+  const int32_t* land_pos = nullptr;     // [n_layer][B]: land_pos[l * B + b] = l
   const int32_t* chunk_head = nullptr;   // prompt sharing (ssrhip_lm_set_prompt_groups): the caller's two device arrays [B], or null = off
   const int32_t* n_shared = nullptr;
   int group_members = 0;        // rows per chunk the caller's chunks are cut for (ssrhip_lm_set_group_members; set with the arrays)
@@ -228,10 +234,13 @@ struct StepShapes {
   // (include/ssrhip.h SSRHIP_TILED_P: one 16-row panel per 16 rows) so that the matrix-core GEMV's operand loads are contiguous KiBs
   const int tiled;
   const bool wt;       // streaming-order weight copies for the matrix-core GEMV (include/ssrhip.h w_tiled)
-  const bool kv16;     // the cache holds 2-byte entries (ssrhip_lm_set_kv16)
+  const bool kv16;     // the cache holds 2-byte entries and the QKV launch appends them (ssrhip_lm_set_kv16, 5..32 rows)
+  float* const land;   // <= 4 rows with a 2-byte cache (ssrhip_lm_set_kv16_small): the QKV launch appends fp32 into this landing cache
+  const int32_t* const land_table;
+  const int32_t* const land_pos;
   explicit StepShapes(const ssrhip_lm* lm)
       : d(lm->d), w(lm->w), b(lm->b), D(lm->d.d_model), B(lm->b.B), K(lm->d.n_codebooks), Hh(lm->d.head_hidden), tiled(lm->b.B > 4 ? 1 : 0),
-        wt(lm->b.B > 4 && lm->w.in_proj_wt), kv16(lm->kv16) {}
+        wt(lm->b.B > 4 && lm->w.in_proj_wt), kv16(lm->kv16), land(lm->land), land_table(lm->land_table), land_pos(lm->land_pos) {}
   ssrhip_gemv_args qkv_args(int l) const {
     ssrhip_gemv_args g;
     // LN1 + packed QKV projection, q -> b.q, k/v appended in place into the paged cache
@@ -242,6 +251,13 @@ struct StepShapes {
     if (!d.ln_folded) { g.ln_w = w.ln1_w[l]; g.ln_b = w.ln1_b[l]; }
     g.ln_eps = 1e-5f;
     g.kv = b.kv; g.layer = l; g.kv_pos = b.kv_pos;
+    if (land) {
+      // the landing cache is a one-layer cache of B pages in the pool's layout whose row b owns page b; layer l appends at position l of it.
+      // Every append form computes its address from (kv, layer, kv_pos) alone, so the launch — single, segment or pair, any weight
+      // stream — is the fp32 engine's with another destination
+      g.kv.pool = land; g.kv.table = land_table; g.kv.max_pages = 1; g.kv.n_layer = 1;
+      g.layer = 0; g.kv_pos = land_pos + (size_t)l * B;
+    }
     g.x_tiled = tiled;                         // q stays row-major for the attention kernel
     if (wt) { g.W = w.in_proj_wt[l]; g.w_tiled = 1; }
     return g;
@@ -448,7 +464,8 @@ int enqueue_step(ssrhip_lm* lm, hipStream_t s, Timer* tm) {
       else STEP_CALL(CAT_ATTN, ssrhip_attn_rows(&at, b.h, s));
       op = sh.outproj_rows_args(l, b.h);
     } else {
-      STEP_CALL(CAT_ATTN, ssrhip_attn_decode(&at, s));
+      if (lm->land) { STEP_CALL(CAT_ATTN, ssrhip_attn_decode_kv16(&at, lm->land, s)); n_kv16 += 1; }   // <= 4 rows (the setter checked)
+      else STEP_CALL(CAT_ATTN, ssrhip_attn_decode(&at, s));
       if (sh.B > 4) {
         // the combine is its own small launch; q is dead after the attention, reuse it
         at.out_tiled = 1;
@@ -680,7 +697,24 @@ extern "C" int ssrhip_lm_set_kv16(ssrhip_lm* lm, int32_t on) {
   lm->kv16 = on != 0;
   return 0;
 }
-extern "C" int ssrhip_lm_kv16_launches(const ssrhip_lm* lm) { return lm && lm->kv16 ? lm->kv16_launches : 0; }
+extern "C" int ssrhip_lm_kv16_launches(const ssrhip_lm* lm) { return lm && (lm->kv16 || lm->land) ? lm->kv16_launches : 0; }
+// The bf16 cache of the <= 4-row step: b.kv.pool holds 2-byte entries, and the three buffers are the landing cache of the QKV launch's
+// append (StepShapes::qkv_args) that ssrhip_attn_decode_kv16 promotes from. All three null: off.
+extern "C" int ssrhip_lm_set_kv16_small(ssrhip_lm* lm, float* land, const int32_t* land_table, const int32_t* land_pos) {
+  SSR_REQUIRE(lm, "ssrhip_lm_set_kv16_small: null engine");
+  SSR_REQUIRE(!lm->exec, "ssrhip_lm_set_kv16_small: the decode step of this engine is already captured (call it before the first ssrhip_lm_decode)");
+  SSR_REQUIRE(!land == !land_table && !land == !land_pos, "ssrhip_lm_set_kv16_small: land, land_table and land_pos come together (all null = off)");
+  const bool on = land != nullptr;
+  SSR_REQUIRE(!on || lm->b.B <= 4, "ssrhip_lm_set_kv16_small: the landing cache exists for the <= 4-row decode step only (this engine has %d rows; engines of "
+              "5..32 rows take ssrhip_lm_set_kv16)", lm->b.B);
+  SSR_REQUIRE(!on || lm->d.n_layer <= SSRHIP_PAGE, "ssrhip_lm_set_kv16_small: layer l lands at position l of a row's landing page, which holds %d (this engine has %d layers)",
+              SSRHIP_PAGE, lm->d.n_layer);
+  SSR_REQUIRE(!on || !getenv_flag("SSRHIP_PREFILL_ATTN_ROWWISE"), "ssrhip_lm_set_kv16_small: SSRHIP_PREFILL_ATTN_ROWWISE is set, and the rowwise prefill attention reads fp32 entries");
+  lm->land = land;
+  lm->land_table = land_table;
+  lm->land_pos = land_pos;
+  return 0;
+}
 
 extern "C" int ssrhip_lm_set_prompt_groups(ssrhip_lm* lm, const int32_t* chunk_head, const int32_t* n_shared) {
   SSR_REQUIRE(lm, "ssrhip_lm_set_prompt_groups: null engine");
@@ -933,12 +967,13 @@ static int lm_layer_loop(const ssrhip_lm_dims& d, const ssrhip_lm_weights& w, in
 extern "C" int ssrhip_lm_prefill(ssrhip_lm* lm, const ssrhip_prefill_args* p, ssrhip_stream_t stream) {
   SSR_REQUIRE(lm && p && p->tok && p->pos && p->kind && p->row_seq && p->row_pos && p->row_len, "ssrhip_lm_prefill: null argument");
   const bool tiled_attn = p->seq_start && p->n_seq > 0 && p->max_len > 0 && !getenv_flag("SSRHIP_PREFILL_ATTN_ROWWISE");
-  SSR_REQUIRE(tiled_attn || !lm->kv16, "ssrhip_lm_prefill: an engine with a bf16 KV cache prefills through the tiled attention only (seq_start is missing or "
+  const bool kv16 = lm->kv16 || lm->land;         // the pool holds 2-byte entries, whichever step fills it later
+  SSR_REQUIRE(tiled_attn || !kv16, "ssrhip_lm_prefill: an engine with a bf16 KV cache prefills through the tiled attention only (seq_start is missing or "
               "SSRHIP_PREFILL_ATTN_ROWWISE is set): the rowwise kernels read fp32 entries");
   SSR_REQUIRE(p->x && p->xn && p->qkv && p->o && p->h && (tiled_attn || (p->part_o && p->part_ml)), "ssrhip_lm_prefill: null workspace");
   ssrhip_kv kv = lm->b.kv;
   if (p->table) kv.table = p->table;              // two-phase admission: the rows being filled are not in the decode step's table yet
-  if (int rc = lm_layer_loop(lm->d, lm->w, lm->prefill_split ? (lm->prefill_w1 ? 1 : 3) : 0, kv, p, tiled_attn, lm->kv16, (hipStream_t)stream)) return rc;
+  if (int rc = lm_layer_loop(lm->d, lm->w, lm->prefill_split ? (lm->prefill_w1 ? 1 : 3) : 0, kv, p, tiled_attn, kv16, (hipStream_t)stream)) return rc;
   if (p->no_embed) return 0;
   return ssrhip_lm_embed_pending(lm, stream);
 }

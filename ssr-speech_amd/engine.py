@@ -343,6 +343,32 @@ def resolve_kv_dtype(rows: int, requested: Optional[str], model_default: str = "
     return requested
 
 
+# What an unset SSRHIP_ATTN_KV16_SMALL means for an engine of <= 4 rows whose wanted cache type is "bf16" (DecodeEngine kv16_small=None):
+# "1" = it holds the 2-byte cache through the landing cache (include/ssrhip.h ssrhip_lm_set_kv16_small), "0" = the rule of
+# `resolve_kv_dtype` stands: its K / V stay fp32. DESIGN.md Part I.23.
+KV16_SMALL_DEFAULT = "0"
+KV16_SMALL_MAX_LAYERS = 128   # layer l lands at position l of a row's landing page (SSRHIP_PAGE positions)
+
+
+def resolve_kv16_small(rows: int, kv_requested: Optional[str], model_default: str, requested: Optional[bool], env) -> bool:
+    """Does an engine of `rows` rows hold a bf16 KV cache through the landing cache of the 1/2/4-row step (DecodeEngine kv16_small)? The
+    wanted cache type is `kv_requested`, or `model_default` (SSR_Speech.set_kv_dtype) when that is None. requested None: on iff the engine
+    has <= 4 rows, the wanted type is "bf16" and `env["SSRHIP_ATTN_KV16_SMALL"]` (unset: KV16_SMALL_DEFAULT) does not start with '0'.
+    requested True: ValueError at more than 4 rows (named first), then when the wanted type is "fp32". When the answer is yes the engine's
+    kv_dtype is "bf16" and `resolve_kv_dtype` is not asked. `env` is a mapping like os.environ; nothing else is read."""
+    wanted = model_default if kv_requested is None else kv_requested
+    if requested is None:
+        return rows <= 4 and wanted == "bf16" and env.get("SSRHIP_ATTN_KV16_SMALL", KV16_SMALL_DEFAULT)[:1] != "0"
+    if not requested:
+        return False
+    if rows > 4:
+        raise ValueError(f"kv16_small: the landing cache exists for the 1/2/4-row decode step only (this engine has {rows} rows; "
+                         f"engines of 5..{MAX_ROWS} rows take kv_dtype='bf16')")
+    if wanted != "bf16":
+        raise ValueError(f"kv16_small needs the bf16 cache type (kv_dtype='bf16' or SSR_Speech.set_kv_dtype('bf16')), not {wanted!r}")
+    return True
+
+
 SAMPLING_RNGS = ("torch_cpu", "philox")
 
 
@@ -1048,7 +1074,8 @@ class DecodeEngine:
                  pool_pages: Optional[int] = None, page_order: Optional[Sequence[int]] = None, pair_mode: int = 0,
                  stream_w16: Optional[bool] = None, stream_wt16: Optional[bool] = None, stream_wt32: Optional[bool] = None,
                  kv_dtype: Optional[str] = None, share_prompt: Optional[bool] = None, stream_w8: Optional[bool] = None,
-                 pair_w16: Optional[bool] = None, pair_w8: Optional[bool] = None, stream_wt8: Optional[bool] = None):
+                 pair_w16: Optional[bool] = None, pair_w8: Optional[bool] = None, stream_wt8: Optional[bool] = None,
+                 kv16_small: Optional[bool] = None):
         """max_seq: longest sequence (text + audio positions) any ONE row may reach; pool_pages: physical KV pages shared by all
         rows (default rows x pages-per-row, the no-sharing worst case; a batch of short and long utterances needs only the sum
         of their own page counts). pair_mode (2-row engines; include/ssrhip.h ssrhip_lm_buffers): 0 = pair launches if this engine
@@ -1079,7 +1106,12 @@ class DecodeEngine:
         share_prompt True (5..32 rows, fp32 cache; ValueError otherwise; None = off): rows admitted TOGETHER by `start` / the first fill of
         `run_queue` with equal text and equal prompt audio (the samples of one utterance) are prefilled once, share the prompt's whole KV
         pages, and the step's attention reads a shared page once per chunk of rows (include/ssrhip.h ssrhip_lm_set_prompt_groups). Every
-        row computes what it computes unshared, bit for bit. Refills and the two-phase admission (`admit_begin`) never share."""
+        row computes what it computes unshared, bit for bit. Refills and the two-phase admission (`admit_begin`) never share.
+        kv16_small (1, 2 or 4 rows; `resolve_kv16_small`, DESIGN.md Part I.23): the bf16 cache for the split-KV step — the pool holds 2-byte
+        entries, the QKV launch appends fp32 into a small landing cache (`kv_landing_bytes`) and the attention launch rounds the new position
+        once and promotes it into the pool (include/ssrhip.h ssrhip_lm_set_kv16_small). None = on when the engine has <= 4 rows, kv_dtype
+        is "bf16" and `SSRHIP_ATTN_KV16_SMALL` (read here; unset = KV16_SMALL_DEFAULT) does not start with '0'; with it on, kv_dtype "bf16"
+        is not a ValueError at these rows. Every weight stream and launch form works unchanged; at most KV16_SMALL_MAX_LAYERS layers."""
         self.lib = _lib.lib()
         self.a = arena
         dev = arena.device
@@ -1106,7 +1138,10 @@ class DecodeEngine:
         self._stream = next((st for st in W16_STREAMS if getattr(self, "stream_" + st.name)), None)
         self.max_pages = (max_seq + PAGE - 1) // PAGE
         self.max_seq = self.max_pages * PAGE
-        self.kv_dtype = resolve_kv_dtype(self.B, kv_dtype, "fp32", self.max_pages)
+        self.kv16_small = resolve_kv16_small(self.B, kv_dtype, "fp32", kv16_small, os.environ)
+        if self.kv16_small and arena.L > KV16_SMALL_MAX_LAYERS:
+            raise ValueError(f"kv16_small takes at most {KV16_SMALL_MAX_LAYERS} layers (this model has {arena.L})")
+        self.kv_dtype = "bf16" if self.kv16_small else resolve_kv_dtype(self.B, kv_dtype, "fp32", self.max_pages)
         self.share_prompt = resolve_share_prompt(self.B, share_prompt, self.kv_dtype)
         if self.share_prompt and self.max_pages > KV16_MAX_PAGES:
             raise ValueError(f"share_prompt takes at most {KV16_MAX_PAGES} pages per row (this engine has {self.max_pages})")
@@ -1130,6 +1165,11 @@ class DecodeEngine:
         self.scratch_page = n_pages              # one extra page: where the rows of a FINISHED utterance keep (harmlessly) writing
         self.kv_pool = torch.empty((n_pages + 1) * L * 2 * H * PAGE * self.hd, device=dev,
                                    dtype=torch.bfloat16 if self.kv_dtype == "bf16" else torch.float32)
+        # kv16_small: the QKV launch's fp32 landing cache [B][1][2][H][PAGE][hd], its page table (row b owns page b) and the positions the
+        # layers append at (layer l: position l) — written here, once; the captured step only holds their pointers
+        self.kv_land = torch.zeros(self.B * 2 * H * PAGE * self.hd, **f32) if self.kv16_small else None
+        self.kv_land_table = torch.arange(self.B, **i32) if self.kv16_small else None
+        self.kv_land_pos = torch.arange(L, **i32).repeat_interleave(self.B).contiguous() if self.kv16_small else None
         self.page_table = torch.full((self.B, self.max_pages), self.scratch_page, **i32)
         self._table_host = np.full((self.B, self.max_pages), self.scratch_page, dtype=np.int32)
         self._row_pages: List[List[int]] = [[] for _ in range(self.B)]
@@ -1229,7 +1269,10 @@ class DecodeEngine:
         if self.stream_wt8:                       # the e4m3 stream of the 5..16-row step (no pairing at these rows)
             rec8 = self.a.wt8_struct()
             _lib.check(self.lib.ssrhip_lm_set_wt8(ctx, C.byref(rec8)), "ssrhip_lm_set_wt8")
-        if self.kv_dtype == "bf16":               # the pool's entry type travels with the pool (also for the two-phase admission's prefill)
+        if self.kv16_small:                       # <= 4 rows: the 2-byte pool and the landing cache of the QKV launch's append
+            _lib.check(self.lib.ssrhip_lm_set_kv16_small(ctx, self.kv_land.data_ptr(), self.kv_land_table.data_ptr(), self.kv_land_pos.data_ptr()),
+                       "ssrhip_lm_set_kv16_small")
+        elif self.kv_dtype == "bf16":             # the pool's entry type travels with the pool (also for the two-phase admission's prefill)
             _lib.check(self.lib.ssrhip_lm_set_kv16(ctx, 1), "ssrhip_lm_set_kv16")
         if self.share_prompt:                     # the two arrays' pointers travel with the captured step
             _lib.check(self.lib.ssrhip_lm_set_prompt_groups(ctx, self.chunk_dev[0].data_ptr(), self.chunk_dev[1].data_ptr()),
@@ -1249,6 +1292,11 @@ class DecodeEngine:
     def kv_pool_bytes(self) -> int:
         """Bytes of the paged KV pool this engine holds (half as many with kv_dtype="bf16")."""
         return self.kv_pool.numel() * self.kv_pool.element_size()
+
+    @property
+    def kv_landing_bytes(self) -> int:
+        """Bytes of the fp32 landing cache a kv16_small engine holds beside its pool (rows x 2 x d_model x 128 x 4; 0 otherwise)."""
+        return 0 if self.kv_land is None else self.kv_land.numel() * self.kv_land.element_size()
 
     @property
     def kv16_launches_per_step(self) -> int:

@@ -25,7 +25,7 @@ from .. import _lib
 from .. import layout as LY
 from .. import score as SC
 from ..engine import (DEFAULT_GROUP_ROWS, KV_DTYPES, MAX_ROWS, WEIGHT_DTYPES, DecodeEngine, DecodeKnobs, LMWeightsArena, PhiloxNoise, SAMPLING_RNGS,
-                      TorchCpuNoiseFeed, W16_STREAMS, resolve_kv_dtype, resolve_sampling_rng, resolve_share_prompt, resolve_w16_pair, resolve_w16_stream, resolve_w8_pair, resolve_w8_stream)
+                      TorchCpuNoiseFeed, W16_STREAMS, resolve_kv16_small, resolve_kv_dtype, resolve_sampling_rng, resolve_share_prompt, resolve_w16_pair, resolve_w16_stream, resolve_w8_pair, resolve_w8_stream)
 from ..weights import lm_param_specs
 
 
@@ -259,7 +259,8 @@ class SSR_Speech(nn.Module):
         """"bf16": decode engines of 5..32 rows — `inference_batch`, `dp.generate`, `dp.synthesize`, `run_queue` with 3 or more utterances
         under CFG — keep their KV cache in 2-byte bf16 entries (engine.DecodeEngine kv_dtype): half the cache memory and half the bytes the
         attention reads; K / V are rounded once when written, everything else stays fp32. The 2-row paths (`inference`,
-        `inference_stream`) and `score` keep fp32 K / V. "fp32" (the default) restores today's numbers bit for bit. Independent of
+        `inference_stream`) keep fp32 K / V unless `SSRHIP_ATTN_KV16_SMALL=1` opts engines of 1, 2 or 4 rows in (engine.resolve_kv16_small,
+        DESIGN.md Part I.23); `score` keeps fp32 K / V. "fp32" (the default) restores today's numbers bit for bit. Independent of
         `set_weight_dtype`. Drops the cached engines."""
         if kv_dtype not in KV_DTYPES:
             raise ValueError(f"kv_dtype {kv_dtype!r} not in {KV_DTYPES}")
@@ -308,7 +309,9 @@ class SSR_Speech(nn.Module):
                 e.close()
             self._engines = {}
         rows = n_utt * (2 if use_cfg else 1)
-        kv_dtype = resolve_kv_dtype(rows, None, self._kv_dtype, cap_seq // 128)
+        # the bf16 cache of the 1/2/4-row step: the engine reads SSRHIP_ATTN_KV16_SMALL when it is built; the answer is part of the key
+        kv16_small = resolve_kv16_small(rows, None, self._kv_dtype, None, os.environ)
+        kv_dtype = "bf16" if kv16_small else resolve_kv_dtype(rows, None, self._kv_dtype, cap_seq // 128)
         # prompt sharing is the caller's request where the engine can serve it: <= 4 rows, a bf16 cache or more than 256 pages per row run unshared
         share = bool(share_prompt) and rows > 4 and kv_dtype == "fp32" and cap_seq // 128 <= 256 and resolve_share_prompt(rows, True, kv_dtype)
         # KV pool: `need_pages` = sum over rows of the pages each row can reach (short and long utterances share one pool); never more
@@ -323,12 +326,12 @@ class SSR_Speech(nn.Module):
         w16_pair = resolve_w16_pair(rows, resolve_w16_stream(W16_STREAMS[0], rows, self._arena.weight_dtype, None, os.environ), 0, None, os.environ)
         # ... and so is SSRHIP_GEMV_W8_PAIR's for the e4m3 stream
         w8_pair = resolve_w8_pair(rows, resolve_w8_stream(rows, self._arena.weight_dtype, None, os.environ), 0, None, os.environ)
-        for (k_utt, k_cfg, k_seq, k_steps, k_dbg, k_pool, k_order, k_share, k_wp, k_wp8), e in self._engines.items():
-            if (k_utt, k_cfg, k_dbg, k_order, k_share, k_wp, k_wp8) == (n_utt, use_cfg, bool(self.debug_logits), order_key, share, w16_pair, w8_pair) and k_seq >= cap_seq and k_steps >= cap_steps \
+        for (k_utt, k_cfg, k_seq, k_steps, k_dbg, k_pool, k_order, k_share, k_wp, k_wp8, k_kvs), e in self._engines.items():
+            if (k_utt, k_cfg, k_dbg, k_order, k_share, k_wp, k_wp8, k_kvs) == (n_utt, use_cfg, bool(self.debug_logits), order_key, share, w16_pair, w8_pair, kv16_small) and k_seq >= cap_seq and k_steps >= cap_steps \
                     and (k_pool >= need if order_key is None else k_pool == min(rows * (cap_seq // 128), ((need + 7) // 8) * 8)):
                 return e
         pool = min(rows * (cap_seq // 128), ((need + 7) // 8) * 8)
-        key = (n_utt, use_cfg, cap_seq, cap_steps, bool(self.debug_logits), pool, order_key, share, w16_pair, w8_pair)
+        key = (n_utt, use_cfg, cap_seq, cap_steps, bool(self.debug_logits), pool, order_key, share, w16_pair, w8_pair, kv16_small)
         for e in self._engines.values():         # one engine (KV pool) resident at a time
             e.close()
         self._engines = {}
@@ -336,7 +339,7 @@ class SSR_Speech(nn.Module):
         if self.page_order is not None:          # tests: a caller-chosen hand-out order of the physical pages
             order = [p for p in self.page_order if p < pool] if len(self.page_order) >= pool else None
         eng = DecodeEngine(self._arena, n_utt, use_cfg, cap_seq, cap_steps, debug_logits=self.debug_logits, pool_pages=pool, page_order=order,
-                           kv_dtype=kv_dtype, share_prompt=share)
+                           kv_dtype=kv_dtype, share_prompt=share, kv16_small=kv16_small)
         self._engines[key] = eng
         return eng
 

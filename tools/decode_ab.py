@@ -37,6 +37,9 @@ Pair launches over the bf16 weight stream (DESIGN.md Part I.19; `SSRHIP_GEMV_W16
   python tools/decode_ab.py --reps 4 fp32: bf16_w16:weight_dtype=bf16 bf16_w16_pair:weight_dtype=bf16,SSRHIP_GEMV_W16_PAIR=1
 Pair launches over the e4m3 weight stream (DESIGN.md Part I.20; `SSRHIP_GEMV_W8_PAIR=1` is the opt-in, `w8 pair launches` the counter):
   python tools/decode_ab.py --reps 4 fp32: e4m3_w8:weight_dtype=e4m3 e4m3_w8_pair:weight_dtype=e4m3,SSRHIP_GEMV_W8_PAIR=1
+A lower-case `kv16_small=1` (DESIGN.md Part I.23; 1, 2 or 4 rows) builds the arm's engine with kv_dtype="bf16", kv16_small=True: the 2-byte
+cache behind the landing cache of the split-KV step (`kv16 launches` its counter, `attn` its per-launch time), under any weight stream:
+  python tools/decode_ab.py --reps 4 --warmup 180 --steps 100 fp32: fp32_kv16:kv16_small=1 e4m3_pair:weight_dtype=e4m3,SSRHIP_GEMV_W8_PAIR=1 e4m3_pair_kv16:weight_dtype=e4m3,SSRHIP_GEMV_W8_PAIR=1,kv16_small=1
 """
 import argparse
 import dataclasses
@@ -75,6 +78,8 @@ for v in a.variants:
     variants.append((name, dict(kv.split("=", 1) for kv in kn.split(",") if kv)))
 dtype_of = {name: d.pop("weight_dtype", "fp32") for name, d in variants}
 kv_of = {name: d.pop("kv_dtype", "fp32") for name, d in variants}
+small_of = {name: d.pop("kv16_small", "0") == "1" for name, d in variants}
+kv_of = {name: "bf16" if small_of[name] else kv for name, kv in kv_of.items()}
 share_of = {name: d.pop("share_prompt", None) for name, d in variants}      # None: U utterances; "0" / "1": U samples of utterance 0
 all_knobs = sorted({k for _, d in variants for k in d})
 
@@ -103,7 +108,7 @@ for rep in range(a.reps):
         os.environ.update(knobs)
         U = utts_of[name]
         eng = DecodeEngine(arenas[dtype_of[name]], U, True, ((L + T0 + total + 8 + 1023) // 1024) * 1024, ((total + 255) // 256) * 256,
-                           kv_dtype=kv_of[name], share_prompt=share_of[name] == "1")
+                           kv_dtype=kv_of[name], share_prompt=share_of[name] == "1", kv16_small=True if small_of[name] else None)
         rows_in = text_rows[:2 * U] if share_of[name] is None else [text_rows[r] if r % 2 else text_rows[0] for r in range(2 * U)]
         launch, ev = eng._launch_prefill, (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
 
@@ -161,4 +166,4 @@ for name, knobs in variants:
     print(f"{name:14s} {U:2d} utts x CFG = {2 * U:2d} rows  tok/s {4 * U / (statistics.median(r['ms']) * 1e-3):9.1f}  "
           f"ms/step min {min(r['ms']):.4f} med {statistics.median(r['ms']):.4f}  all {' '.join(f'{v:.4f}' for v in r['ms'])} | "
           f"gemv {min(r['gemv']):.3f} x {r['launches']['gemv']} attn {min(r['attn']):.3f} x {r['launches']['attn']} "
-          f"sample {min(r['sample']):.3f} x {r['launches']['sample']} us{same}   [{dtype_of[name]}, kv {kv_of[name]}, {' + '.join(f'{r[st.name]} {st.name}' for st in W16_STREAMS)} + {r['w8']} w8 + {r['wt8']} wt8 + {r['w16_pair']} w16 pair + {r['w8_pair']} w8 pair + {r['kv16']} kv16 + {r['group']} group launches; first fill {r['prefill_rows']} rows in {min(r['prefill_ms']):.2f} ms, {r['pages']} KV pages in use; share_prompt={share_of[name]}; pairing={r['pairing']}; {' '.join(f'{k}={v}' for k, v in knobs.items()) or 'defaults'}]")
+          f"sample {min(r['sample']):.3f} x {r['launches']['sample']} us{same}   [{dtype_of[name]}, kv {kv_of[name]}, {' + '.join(f'{r[st.name]} {st.name}' for st in W16_STREAMS)} + {r['w8']} w8 + {r['wt8']} wt8 + {r['w16_pair']} w16 pair + {r['w8_pair']} w8 pair + {r['kv16']} kv16 + {r['group']} group launches; kv16_small={int(small_of[name])}; first fill {r['prefill_rows']} rows in {min(r['prefill_ms']):.2f} ms, {r['pages']} KV pages in use; share_prompt={share_of[name]}; pairing={r['pairing']}; {' '.join(f'{k}={v}' for k, v in knobs.items()) or 'defaults'}]")
