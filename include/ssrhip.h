@@ -252,6 +252,23 @@ int ssrhip_gemv_pair_w8(const ssrhip_gemv_args* a, const ssrhip_gemv_args* b, co
                         const float* scale_b, void* ws, int32_t buf, int32_t buf_next, ssrhip_stream_t stream);
 int ssrhip_gemv_pair_w8_applicable(const ssrhip_gemv_args* a, const ssrhip_gemv_args* b);
 
+/* ssrhip_gemv_pair(a, b, ...) for the 4-ROW decode step (two utterances x CFG, four without), fp32 weights (csrc/gemv_pair4.hip
+ * pair4_kernel / pair4_merge_kernel; DESIGN.md Part I.24). The hand-off is ssrhip_gemv_pair's in kind — tagged 8-byte granules, three
+ * buffers cycled by ssrhip_pair_buffer, every launch resets the next one's, a time-bounded spin with a give-up flag — at granule index
+ * n * 4 + row, 8192 granules per buffer: the workspace is SSRHIP_PAIR4_WS_BYTES, zeroed once by the caller, and is NOT interchangeable with
+ * a 2-row workspace. Results are BIT-IDENTICAL to ssrhip_gemv(a) followed by ssrhip_gemv(b) at B = 4.
+ *   returns 0 = launched, 1 = does not qualify and NOTHING was launched, < 0 = contract error (a null pointer, granule buffers outside
+ *   0..2 or equal, EPI_QKV_APPEND16); the answer comes before any HIP call.
+ *   Qualifies iff a->B == b->B == 4 AND ssrhip_gemv_pair_applicable's rules hold for the same two descriptors at 2 rows (shapes, >= 256
+ *   CUs, no CU mask, SSRHIP_GEMV_PAIR = 0 / 1 / 2 as there) AND, for the merge form, 4 * n_head * max_splits floats fit 16 KB of LDS AND the
+ *   occupancy calculator places at least one workgroup of every 4-row pair kernel on a CU (asked once per process).
+ *   ssrhip_gemv_pair4_status is ssrhip_gemv_pair_status for a workspace of this size: 1 ONCE after a give-up, the workspace re-zeroed.
+ * ssrhip_gemv_pair, ssrhip_gemv_pair_w16 and ssrhip_gemv_pair_w8 keep answering 1 for B = 4. */
+#define SSRHIP_PAIR4_WS_BYTES (3 * 8192 * 8 + 64)
+int ssrhip_gemv_pair4_applicable(const ssrhip_gemv_args* a, const ssrhip_gemv_args* b);
+int ssrhip_gemv_pair4(const ssrhip_gemv_args* a, const ssrhip_gemv_args* b, void* ws, int32_t buf, int32_t buf_next, ssrhip_stream_t stream);
+int ssrhip_gemv_pair4_status(const void* ws, ssrhip_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Single-query attention over the paged cache, split over pages (one workgroup per page):
  * replaces F.scaled_dot_product_attention at activation.py:634 for tgt_len==1 (and, row by row,
@@ -704,6 +721,15 @@ int ssrhip_lm_set_w8_pair(ssrhip_lm* lm, int on);
 /* pair launches of the last enqueued step that ran a w8_pair* kernel (2 * n_layer when every family has codes; ssrhip_lm_w8_launches keeps
  * counting the SINGLE e4m3 launches: then 2, layer 0's QKV and the second head Linear); 0 for other engines */
 int ssrhip_lm_w8_pair_launches(const ssrhip_lm* lm);
+/* Opt-in: pair launches for the 4-ROW step over the fp32 weights (ssrhip_gemv_pair4). Accepted only on a 4-row engine that streams no
+ * packed weights, before the step is captured (< 0 otherwise). on = 1 repeats ssrhip_lm_create's pairing decision for this engine: pair_mode
+ * 1 refuses, the step's own descriptors are put to ssrhip_gemv_pair4_applicable, the device's pairing slot is taken unless pair_mode is 2,
+ * the workspace (SSRHIP_PAIR4_WS_BYTES) is allocated and zeroed. An engine that cannot pair returns 0 all the same and steps unpaired
+ * (ssrhip_lm_pairing says why); one that can reports ssrhip_lm_pairing = 1 with a text that names the 4-row pair launches. on = 0 gives
+ * slot and workspace back. Same tokens, bit for bit, either way. ssrhip_lm_pair_status covers this workspace too. */
+int ssrhip_lm_set_pair4(ssrhip_lm* lm, int on);
+/* pair launches of the last enqueued step that ran a pair4* kernel (2 * n_layer when both forms apply); 0 for other engines */
+int ssrhip_lm_pair4_launches(const ssrhip_lm* lm);
 /* The same for the 5..16-row decode step: the record's pointers are SSRHIP_WT16_INDEX copies of the six families (NULL field / NULL entry:
  * that family streams the fp32 streaming-order copy of its master). From now on every GEMV launch of the step tries ssrhip_gemv_wt16 first
  * and falls back to ssrhip_gemv; same tokens, bit for bit; the step stays one captured graph. Refused (< 0) for engines of <= 4 rows (they

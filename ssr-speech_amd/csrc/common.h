@@ -12,6 +12,7 @@ void ssrhip_set_error(const char* fmt, ...);
 const char* ssrhip_gemv_pair_why();      // gemv.hip: why the last pair-applicability question on this thread was answered with no
 const char* ssrhip_gemv_pair_w16_why();  // gemv_pair_w16.hip: the same for ssrhip_gemv_pair_w16_applicable
 const char* ssrhip_gemv_pair_w8_why();   // gemv_pair_w8.hip: the same for ssrhip_gemv_pair_w8_applicable
+const char* ssrhip_gemv_pair4_why();     // gemv_pair4.hip: the same for ssrhip_gemv_pair4_applicable
 
 #define SSR_REQUIRE(cond, ...)            \
   do {                                    \

@@ -69,6 +69,8 @@ struct ssrhip_lm {
   char pair_why[200] = "";      // why the step pairs / does not pair (ssrhip_lm_pairing)
   bool pk_pair = false;         // the pair launches of this engine stream its packed weights: the bf16 copies (ssrhip_lm_set_w16_pair; pk_kind ==
                                 // PK_W16) or the e4m3 codes and scales (ssrhip_lm_set_w8_pair; PK_W8)
+  bool pair4 = false;           // 4-row engine: the step runs the 4-row pair launches (ssrhip_lm_set_pair4; pair_ws then has SSRHIP_PAIR4_WS_BYTES)
+  int pair4_launches = 0;       // pair launches of the last enqueued step that ran a pair4* kernel (ssrhip_lm_pair4_launches)
   int pk_pair_launches = 0;     // pair launches of the last enqueued step that ran a w16_pair* / w8_pair* kernel (ssrhip_lm_{w16,w8}_pair_launches)
   // the bf16 weight stream: an engine has one row count, so one kind (index into PACKED_STREAMS, -1: none) and one record of packed copies
   // of the six families, in that kind's order (SSRHIP_W16_INDEX at <= 4 rows, SSRHIP_WT16_INDEX at 5..32); NULL = that matrix streams fp32
@@ -112,6 +114,7 @@ const PackedStream PACKED_STREAMS[3] = {
     {"ssrhip_lm_set_wt16", 5, 16, "5..16", "the bf16 weight stream of the matrix-core step exists for 5..16 rows only", ssrhip_gemv_wt16, true, false},
     {"ssrhip_lm_set_wt32", 17, 32, "17..32", "the bf16 weight stream of the two-panel step exists for 17..32 rows only", ssrhip_gemv_wt32, true, false},
 };
+enum { PK_PAIR4 = -2 };   // not a packed stream: StepShapes::pair_plan's name for the 4-row pair launches over fp32 weights
 enum { PK_W16 = 0, PK_WT16 = 1, PK_WT32 = 2, PK_W8 = 3, PK_WT8 = 4 };   // PK_W8 / PK_WT8: the e4m3 streams of <= 4 rows (ssrhip_lm_set_w8) and of
                                                             // 5..16 rows (ssrhip_lm_set_wt8): codes AND scales, so their entry points have
                                                             // another signature and they have no row in PACKED_STREAMS
@@ -349,12 +352,12 @@ struct StepShapes {
   // which launches of the 2-row step qualify for the pair forms, and how many pair launches a step then has (0: fewer than 2 -> none)
   // packed_kind PK_W16 / PK_W8: the question goes to the pair launches over packed bf16 weights / e4m3 codes (ssrhip_gemv_pair_w16_applicable,
   // ssrhip_gemv_pair_w8_applicable), -1: to the fp32 forms; which of a step's pairs then have packed copies of both matrices is
-  // enqueue_step's part
+  // enqueue_step's part. PK_PAIR4: the 4-row step, the question goes to ssrhip_gemv_pair4_applicable (fp32 weights)
   int pair_plan(bool* qkv, bool* head, bool* ffn1, int packed_kind = -1) const {
     *qkv = *head = *ffn1 = false;
-    if (B != 2) return 0;
+    if (B != (packed_kind == PK_PAIR4 ? 4 : 2)) return 0;
     int (*const applicable)(const ssrhip_gemv_args*, const ssrhip_gemv_args*) =
-        packed_kind == PK_W16 ? ssrhip_gemv_pair_w16_applicable : packed_kind == PK_W8 ? ssrhip_gemv_pair_w8_applicable : ssrhip_gemv_pair_applicable;
+        packed_kind == PK_PAIR4 ? ssrhip_gemv_pair4_applicable : packed_kind == PK_W16 ? ssrhip_gemv_pair_w16_applicable : packed_kind == PK_W8 ? ssrhip_gemv_pair_w8_applicable : ssrhip_gemv_pair_applicable;
     const ssrhip_gemv_args fa = ffn2_args(0);
     if (d.n_layer > 1) { const ssrhip_gemv_args qa = qkv_args(1); *qkv = applicable(&fa, &qa) != 0; }
     { const ssrhip_gemv_args ha = head1_args(); *head = applicable(&fa, &ha) != 0; }
@@ -381,7 +384,8 @@ int enqueue_step(ssrhip_lm* lm, hipStream_t s, Timer* tm) {
   const bool wp = lm->pk_pair && lm->pair_ws && (lm->pk_kind == PK_W16 || lm->pk_kind == PK_W8);
   const bool wp8 = wp && lm->pk_kind == PK_W8;
   bool pair_qkv = false, pair_head = false, pair_ffn1 = false;
-  int n_pairs = lm->pair_ws ? sh.pair_plan(&pair_qkv, &pair_head, &pair_ffn1, wp ? lm->pk_kind : -1) : 0;
+  const bool p4 = lm->pair4 && lm->pair_ws;     // the 4-row step's pair launches (ssrhip_lm_set_pair4): same plan, same cycle, ssrhip_gemv_pair4
+  int n_pairs = lm->pair_ws ? sh.pair_plan(&pair_qkv, &pair_head, &pair_ffn1, p4 ? PK_PAIR4 : wp ? lm->pk_kind : -1) : 0;
   // what a launch of (family, layer) streams instead of its fp32 master, in the engine's kind
   auto w16_of = [&](int family, int l) -> PackedRef {
     if (pk_codes(lm->pk_kind)) return lm->pk8[family].empty() ? PackedRef{nullptr, nullptr, nullptr} : PackedRef{nullptr, lm->pk8[family][l], lm->pk8s[family][l]};
@@ -400,7 +404,7 @@ int enqueue_step(ssrhip_lm* lm, hipStream_t s, Timer* tm) {
     for (int l = 0; l < d.n_layer; ++l) n_pairs += (ffn1_pairs(l) ? 1 : 0) + (ffn2_pairs(l) ? 1 : 0);
     if (n_pairs < 2) { pair_qkv = pair_head = pair_ffn1 = false; n_pairs = 0; }
   }
-  int pair_i = 0, n_wp = 0;
+  int pair_i = 0, n_wp = 0, n_p4 = 0;
   // the launch (a, b) that pair_plan found applicable, on this pair's granule buffer; pa / pb: the packed copies (wp only)
   auto pair_call = [&](const ssrhip_gemv_args& ga, const ssrhip_gemv_args& gb, const PackedRef pa, const PackedRef pb) {
     const int bufi = ssrhip_pair_buffer(pair_i, n_pairs), bufn = ssrhip_pair_buffer((pair_i + 1) % n_pairs, n_pairs);
@@ -411,6 +415,12 @@ int enqueue_step(ssrhip_lm* lm, hipStream_t s, Timer* tm) {
       n_wp += rc == 0;
       if (rc == 1) ssrhip_set_error("ssrhip_lm_decode: a pair the plan accepted was refused by %s (%s)", wp8 ? "ssrhip_gemv_pair_w8" : "ssrhip_gemv_pair_w16",
                                     wp8 ? ssrhip_gemv_pair_w8_why() : ssrhip_gemv_pair_w16_why());
+      return rc == 1 ? -1 : rc;
+    }
+    if (p4) {
+      const int rc = ssrhip_gemv_pair4(&ga, &gb, lm->pair_ws, bufi, bufn, (ssrhip_stream_t)s);
+      n_p4 += rc == 0;
+      if (rc == 1) ssrhip_set_error("ssrhip_lm_decode: a pair the plan accepted was refused by ssrhip_gemv_pair4 (%s)", ssrhip_gemv_pair4_why());
       return rc == 1 ? -1 : rc;
     }
     return ssrhip_gemv_pair(&ga, &gb, lm->pair_ws, bufi, bufn, (ssrhip_stream_t)s);
@@ -451,7 +461,7 @@ int enqueue_step(ssrhip_lm* lm, hipStream_t s, Timer* tm) {
     // out-projection slice the merge pair launch behind it starts with (include/ssrhip.h ssrhip_attn_args.prefetch). Measured: the attention
     // launch pays for the 16.8 MB (6.55 -> 8.80 us) and the pair launch gains nothing (18.33 vs 18.35 us): 0.7477 -> 0.7707 ms/step
     // (profiles/r06_microbench/decode_ab_attn_prefetch.log). Like every cross-launch prefetch tried since round 1, it loses.
-    if (pair_ffn1 && sh.D % 256 == 0 && getenv("SSRHIP_ATTN_PREFETCH") && getenv("SSRHIP_ATTN_PREFETCH")[0] == '1') {
+    if (pair_ffn1 && !p4 && sh.D % 256 == 0 && getenv("SSRHIP_ATTN_PREFETCH") && getenv("SSRHIP_ATTN_PREFETCH")[0] == '1') {
       at.prefetch = lm->w.out_proj_w[l];
       at.prefetch_floats = (sh.D / 256) * sh.D;              // workgroup i of the pair launch owns rows [8 i, 8 i + 8) of W_o [D][D]
     }
@@ -501,7 +511,7 @@ int enqueue_step(ssrhip_lm* lm, hipStream_t s, Timer* tm) {
   STEP_CALL(CAT_GEMV, gemv_call(h2, pk_h2));
   const ssrhip_sample_args sa = sh.sample_args();
   STEP_CALL(CAT_SAMPLE, ssrhip_sample(&sa, s));
-  if (!tm || tm->only < 0) { lm->pk_launches = n_pk; lm->pk_pair_launches = n_wp; lm->kv16_launches = n_kv16; lm->group_launches = n_group; }   // (a category-timing pass enqueues only part of a step)
+  if (!tm || tm->only < 0) { lm->pk_launches = n_pk; lm->pk_pair_launches = n_wp; lm->pair4_launches = n_p4; lm->kv16_launches = n_kv16; lm->group_launches = n_group; }   // (a category-timing pass enqueues only part of a step)
   return 0;
 }
 
@@ -608,6 +618,7 @@ static int lm_set_packed(ssrhip_lm* lm, const ssrhip_lm_w16* rec, int kind) {
     SSR_REQUIRE(B >= ps.lo || B > o.hi, "%s: engines of %s rows stream bf16 weights through %s (this engine has %d rows)", ps.setter, o.rows, o.setter, B);
   SSR_REQUIRE(B <= ps.hi, "%s: %s (this engine has %d rows)", ps.setter, ps.only, B);
   SSR_REQUIRE(!lm->exec, "%s: the decode step of this engine is already captured (call it before the first ssrhip_lm_decode)", ps.setter);
+  SSR_REQUIRE(!lm->pair4, "%s: this engine runs the 4-row pair launches over fp32 weights (ssrhip_lm_set_pair4); switch them off first", ps.setter);
   SSR_REQUIRE(!pk_codes(lm->pk_kind), "%s: this engine already streams e4m3 weights (%s); an engine has one packed stream", ps.setter,
               lm->pk_kind == PK_WT8 ? "ssrhip_lm_set_wt8" : "ssrhip_lm_set_w8");
   SSR_REQUIRE(!ps.needs_wt || lm->w.in_proj_wt, "%s: this engine was created without the fp32 streaming-order copies (ssrhip_lm_weights *_wt)", ps.setter);
@@ -643,6 +654,7 @@ static int lm_set_codes(ssrhip_lm* lm, const ssrhip_lm_w8* rec, int kind) {
     SSR_REQUIRE(B <= 16, "ssrhip_lm_set_wt8: the e4m3 weight stream of the matrix-core step exists for 5..16 rows only (this engine has %d rows; engines of 17..32 rows stream 2-byte copies through ssrhip_lm_set_wt32)", B);
   }
   SSR_REQUIRE(!lm->exec, "%s: the decode step of this engine is already captured (call it before the first ssrhip_lm_decode)", who);
+  SSR_REQUIRE(!lm->pair4, "%s: this engine runs the 4-row pair launches over fp32 weights (ssrhip_lm_set_pair4); switch them off first", who);
   SSR_REQUIRE(lm->pk_kind < 0 || lm->pk_kind == kind, "%s: this engine already streams bf16 weights (%s); an engine has one packed stream", who,
               lm->pk_kind >= 0 && lm->pk_kind < PK_W8 ? PACKED_STREAMS[lm->pk_kind].setter : "");
   SSR_REQUIRE(kind != PK_WT8 || lm->w.in_proj_wt, "%s: this engine was created without the fp32 streaming-order copies (ssrhip_lm_weights *_wt)", who);
@@ -788,12 +800,57 @@ extern "C" int ssrhip_lm_set_w16_pair(ssrhip_lm* lm, int on) { return lm_set_pac
 extern "C" int ssrhip_lm_w16_pair_launches(const ssrhip_lm* lm) { return lm_packed_pair_launches(lm, PK_W16); }
 extern "C" int ssrhip_lm_set_w8_pair(ssrhip_lm* lm, int on) { return lm_set_packed_pair(lm, on, PAIR_W8); }
 extern "C" int ssrhip_lm_w8_pair_launches(const ssrhip_lm* lm) { return lm_packed_pair_launches(lm, PK_W8); }
+
+// Pair launches of the 4-row step over the fp32 weights (csrc/gemv_pair4.hip). on = 1 repeats ssrhip_lm_create's pairing decision for this
+// engine with the question put to ssrhip_gemv_pair4_applicable; on = 0 gives slot and workspace back.
+extern "C" int ssrhip_lm_set_pair4(ssrhip_lm* lm, int on) {
+  SSR_REQUIRE(lm, "ssrhip_lm_set_pair4: null engine");
+  SSR_REQUIRE(!lm->exec, "ssrhip_lm_set_pair4: the decode step of this engine is already captured (call it before the first ssrhip_lm_decode)");
+  SSR_REQUIRE(lm->b.B == 4, "ssrhip_lm_set_pair4: the 4-row pair launches exist for the 4-row step only (this engine has %d rows)", lm->b.B);
+  SSR_REQUIRE(lm->pk_kind < 0, "ssrhip_lm_set_pair4: this engine streams packed weights; the 4-row pair launches read the fp32 masters");
+  if (lm->pair_ws) { hipFree(lm->pair_ws); lm->pair_ws = nullptr; }
+  if (lm->pair_dev >= 0) { pair_slot_release(lm->pair_dev); lm->pair_dev = -1; }
+  lm->pair4 = false;
+  if (!on) {
+    snprintf(lm->pair_why, sizeof(lm->pair_why), "the 4-row pair launches of this engine are switched off (ssrhip_lm_set_pair4)");
+    return 0;
+  }
+  const int pair_mode = lm->b.pair_mode;
+  if (pair_mode == 1) { snprintf(lm->pair_why, sizeof(lm->pair_why), "switched off by the caller (pair_mode 1)"); return 0; }
+  bool pq, ph, pf;
+  if (StepShapes(lm).pair_plan(&pq, &ph, &pf, PK_PAIR4) == 0) {
+    const char* why = ssrhip_gemv_pair4_why();
+    snprintf(lm->pair_why, sizeof(lm->pair_why), "%s", why[0] ? why : "fewer than two launches of the step qualify for the 4-row pair forms");
+    return 0;
+  }
+  if (pair_mode != 2) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) dev = -1;
+    if (!pair_slot_acquire(dev, lm->pair_why, sizeof(lm->pair_why))) {
+      fprintf(stderr, "ssrhip: this 4-row decode engine steps WITHOUT its 4-row pair launches (same tokens): %s\n", lm->pair_why);
+      return 0;
+    }
+    lm->pair_dev = dev;
+  }
+  if (hipMalloc(&lm->pair_ws, SSRHIP_PAIR4_WS_BYTES) != hipSuccess || hipMemset(lm->pair_ws, 0, SSRHIP_PAIR4_WS_BYTES) != hipSuccess) {
+    if (lm->pair_ws) { hipFree(lm->pair_ws); lm->pair_ws = nullptr; }
+    if (lm->pair_dev >= 0) { pair_slot_release(lm->pair_dev); lm->pair_dev = -1; }
+    ssrhip_set_error("ssrhip_lm_set_pair4: allocating the pair workspace failed");
+    return -1;
+  }
+  lm->pair4 = true;
+  snprintf(lm->pair_why, sizeof(lm->pair_why), pair_mode == 2 ? "4-row pair launches (ssrhip_gemv_pair4), forced on by the caller (pair_mode 2: no slot, no guard)"
+                                                              : "4-row pair launches (ssrhip_gemv_pair4): this engine holds the pairing slot of its device");
+  return 0;
+}
+extern "C" int ssrhip_lm_pair4_launches(const ssrhip_lm* lm) { return lm && lm->pair4 ? lm->pair4_launches : 0; }
 extern "C" int ssrhip_lm_wt16_launches(const ssrhip_lm* lm) { return lm_packed_launches(lm, PK_WT16); }
 extern "C" int ssrhip_lm_wt32_launches(const ssrhip_lm* lm) { return lm_packed_launches(lm, PK_WT32); }
 
 extern "C" int ssrhip_lm_pair_status(ssrhip_lm* lm, ssrhip_stream_t stream) {
   SSR_REQUIRE(lm, "ssrhip_lm_pair_status: null engine");
   if (!lm->pair_ws) return 0;
+  if (lm->pair4) return ssrhip_gemv_pair4_status(lm->pair_ws, stream);   // the 4-row workspace is twice the size
   return ssrhip_gemv_pair_status(lm->pair_ws, stream);
 }
 
