@@ -8,6 +8,7 @@ import math
 import torch
 import torch.nn.functional as F
 
+import helpers_conditioning as HC
 from helpers_w16 import LAYER, N_LAYER, PAD, POISON, STEPS, TOL, H, HD, LAYERS, _trace, kv_pool  # noqa: F401
 from ssr_speech_amd import _lib
 from ssr_speech_amd import weights as W
@@ -72,15 +73,19 @@ def quantized_weights(name, G, N, K, seed):
     return master, packed, scale.contiguous(), unpacked
 
 
-def check_launch(L, B, G, N, K, pro, act, epi, kv_pos=(130, 7, 383, 256), max_pages=3):
+def check_launch(L, B, G, N, K, pro, act, epi, kv_pos=(130, 7, 383, 256), max_pages=3, x=None, part_ml=None):
     """ssrhip_gemv_w8 on codes + scales against ssrhip_gemv on the master: the same bits in the whole output buffer (pad included) and the
-    whole KV pool, then against torch fp64 on the UNPACKED PACKED BUFFER times the scales, which does not depend on the fp32 kernel."""
+    whole KV pool, then against torch fp64 on the UNPACKED PACKED BUFFER times the scales, which does not depend on the fp32 kernel.
+    x / part_ml: as in helpers_w16.check_launch (ill-conditioned draws; the fp64 bound then follows helpers_conditioning's rule)."""
+    x_given, part_ml_given = x, part_ml
     seed = B * 100003 + N * 7 + K + pro
     g = torch.Generator().manual_seed(seed)
     Wf, packed, scale, Wu = quantized_weights("w16.", G, N, K, seed)
     bias = torch.randn(G, N, generator=g).cuda()
     qkv, combine = epi == _lib.EPI_QKV_APPEND, pro == _lib.PRO_ATTN_COMBINE
     x = (torch.randn(B, G * K, generator=g) * 1.5 + 0.3).cuda()
+    if x_given is not None:
+        x = x_given.reshape(B, G * K).cuda()
     ny = K if qkv else G * N
     yv = (torch.randn(B, ny, generator=g) if epi == _lib.EPI_RESIDUAL else torch.full((B, ny), POISON)).cuda()
     xbuf = x.reshape(-1).clone()
@@ -95,6 +100,8 @@ def check_launch(L, B, G, N, K, pro, act, epi, kv_pos=(130, 7, 383, 256), max_pa
         lens = torch.tensor(lens_l, dtype=torch.int32).cuda()
         part_o = torch.randn(B, H, max_pages, HD, generator=g)
         part_ml = torch.stack([torch.randn(B, H, max_pages, generator=g) * 2, torch.rand(B, H, max_pages, generator=g) + 0.5], dim=-1).contiguous()
+        if part_ml_given is not None:
+            part_ml = part_ml_given.clone()
         pages = [(n + _lib.PAGE - 1) // _lib.PAGE for n in lens_l]
         for b in range(B):
             part_o[b, :, pages[b]:] = float("nan")
@@ -160,10 +167,17 @@ def check_launch(L, B, G, N, K, pro, act, epi, kv_pos=(130, 7, 383, 256), max_pa
     else:
         err = float((got.double() - ref).abs().max())
     print(f"B={B} G={G} N={N} K={K} pro={pro}: max |w8 - fp64| = {err:.3e}")
+    tol = TOL
+    if x_given is not None or part_ml_given is not None:
+        y_res = yv if epi == _lib.EPI_RESIDUAL else None
+        if combine:
+            tol = HC.gemv_chain_tol(TOL, Wu, bias, act, y_res, part_o=part_o, part_ml=part_ml, lens=lens_l)
+        else:
+            tol = HC.gemv_chain_tol(TOL, Wu, bias, act, y_res, x=x, ln=pro == _lib.PRO_LAYERNORM)
     if combine:
-        torch.testing.assert_close(got, ref.float(), rtol=TOL, atol=TOL)
+        torch.testing.assert_close(got, ref.float(), rtol=tol, atol=tol)
     else:
-        assert err < TOL, err
+        assert err < tol, err
 
 
 def check_refusal(L, B, N, K):

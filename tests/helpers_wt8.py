@@ -8,6 +8,7 @@ import functools
 import torch
 import torch.nn.functional as F
 
+import helpers_conditioning as HC
 from helpers_w16 import HD, LAYER, LAYERS, N_LAYER, PAD, POISON, STEPS, TOL, H, _trace, from_tiled, kv_pool, to_tiled  # noqa: F401
 from ssr_speech_amd import _lib
 from ssr_speech_amd import weights as W
@@ -58,18 +59,22 @@ def gemv_args(Wf, bias, xbuf, y, B, G, N, K, ny, pro, act, epi, tiled, y_tiled, 
     return a
 
 
-def check_launch(L, B, G, N, K, pro, act, epi, tiled, kv_pos, max_pages=2, spread=False):
+def check_launch(L, B, G, N, K, pro, act, epi, tiled, kv_pos, max_pages=2, spread=False, x=None):
     """ssrhip_gemv_wt8 on codes + scales against ssrhip_gemv on the fp32 streaming-order copy of code * scale: the same bits in the whole
     output buffer (poisoned rows and pad included) and the whole KV pool; then both against torch fp64 on the UNPACKED PACKED BUFFER TIMES
     THE SCALES, which does not depend on the fp32 kernel, within helpers_w16.TOL. spread: the bound of row n is TOL * max(1, f_n), f_n the
     power of two the row was multiplied by — a power of two scales every product, sum and rounding error of the row's dot product exactly,
-    while the roundings of the bias / residual additions stay at the size of the O(1) result (hence not below TOL for f_n < 1)."""
+    while the roundings of the bias / residual additions stay at the size of the O(1) result (hence not below TOL for f_n < 1).
+    x [B, G*K] (CPU): as in helpers_w16.check_launch (ill-conditioned rows; the fp64 bound then follows helpers_conditioning's rule)."""
+    x_given = x
     seed = B * 100003 + N * 7 + K + pro
     g = torch.Generator().manual_seed(seed)
     Wf, packed, scale, Wu, bias = shape_weights(G, N, K, spread)
     qkv = epi == _lib.EPI_QKV_APPEND
     y_tiled = tiled and not qkv                                            # the q output of the QKV launch is always row-major
     x = (torch.randn(B, G * K, generator=g) * 1.5 + 0.3).cuda()
+    if x_given is not None:
+        x = x_given.reshape(B, G * K).cuda()
     ny = K if qkv else G * N
     yv = (torch.randn(B, ny, generator=g) if epi == _lib.EPI_RESIDUAL else torch.full((B, ny), POISON)).cuda()
     xbuf = to_tiled(x) if tiled else x.reshape(-1).clone()
@@ -127,8 +132,11 @@ def check_launch(L, B, G, N, K, pro, act, epi, tiled, kv_pos, max_pages=2, sprea
         errs[name] = err
     print(f"B={B} G={G} N={N} K={K} pro={pro} tiled={tiled} spread={spread}: max |wt8 - fp64| = {errs['wt8']:.3e}, max |fp32 - fp64| = {errs['fp32']:.3e}"
           + (" (relative to max(1, row factor))" if spread else ""))
-    assert errs["fp32"] < TOL, errs
-    assert errs["wt8"] < TOL, errs
+    tol = TOL
+    if x_given is not None:
+        tol = HC.gemv_chain_tol(TOL, Wu, bias, act, yv if epi == _lib.EPI_RESIDUAL else None, x=x, ln=pro == _lib.PRO_LAYERNORM)
+    assert errs["fp32"] < tol, errs
+    assert errs["wt8"] < tol, errs
 
 
 def check_refusal(L, B, N, K):

@@ -374,6 +374,19 @@ def test_gemv_pair_launch_is_bit_identical_to_the_two_launches(L):
     the 830M step's shape family — LN + QKV with the K/V append (N = 6144), LN + head-MLP1 + GELU (4096), LN + FFN1 + ReLU (8192) — a
     chain of 7 pairs (the three granule buffers cycled the way the engine cycles them, closed over the chain and replayed twice: stale
     tags would show) must leave the residual stream, the consumer's output and the cache BIT-identical to 14 separate ssrhip_gemv calls."""
+    _gemv_pair_chains(L)
+
+
+@pytest.mark.parametrize("rows,partials", [("offset", "wide"), ("step", "late_peak")])
+def test_gemv_pair_launch_is_bit_identical_on_ill_conditioned_inputs(L, rows, partials):
+    """The chains of the test above with the residual stream starting at rows with a large common offset / a step between the LayerNorm's
+    slices, and merge partials whose maxima spread over +-180 / peak at 150 on a row's last page (tests/helpers_conditioning.py)."""
+    _gemv_pair_chains(L, rows=rows, partials=partials)
+
+
+def _gemv_pair_chains(L, rows=None, partials=None):
+    """rows / partials: names of helpers_conditioning.ln_rows / ml_cases that replace today's draws of x0 / part_ml"""
+    import helpers_conditioning as HC
     if torch.cuda.get_device_properties(0).multi_processor_count < 256:
         pytest.skip("the pair launch needs 256 CUs")
     B, D, F = 2, 2048, 8192
@@ -386,6 +399,8 @@ def test_gemv_pair_launch_is_bit_identical_to_the_two_launches(L):
         bn = torch.randn(N, generator=g).cuda()
         h = (torch.randn(B, F, generator=g) * 0.7).cuda()
         x0 = (torch.randn(B, D, generator=g) * 1.5 + 0.3)
+        if rows is not None:
+            x0 = HC.ln_rows(B, D, N)[rows]
         H, hd, n_layer, max_pages = 16, 128, 2, 4
         table = torch.tensor([[5, 2, 7, 1], [0, 6, 3, 4]], dtype=torch.int32, device="cuda")
         pos = torch.tensor([130, 300], dtype=torch.int32, device="cuda")
@@ -435,12 +450,16 @@ def test_gemv_pair_launch_is_bit_identical_to_the_two_launches(L):
         b1 = torch.randn(F, generator=g).cuda()
         part_o = torch.randn(B, H, MS, hd, generator=g).cuda()
         part_ml = torch.stack([torch.randn(B, H, MS, generator=g) * 2, torch.rand(B, H, MS, generator=g) + 0.5], dim=-1).contiguous().cuda()
+        if partials is not None:
+            part_ml = HC.ml_cases(B, H, MS, lens, MS)[partials].cuda()
         for b_ in range(B):                                          # beyond the row's pages the buffers hold garbage the kernel must not use
             n = (lens[b_] + _lib.PAGE - 1) // _lib.PAGE
             part_o[b_, :, n:] = float("nan")
             part_ml[b_, :, n:] = float("nan")
         dlen = torch.tensor(lens, dtype=torch.int32, device="cuda")
         x0 = (torch.randn(B, D, generator=g) * 1.5 + 0.3)
+        if rows is not None:
+            x0 = HC.ln_rows(B, D, MS)[rows]
         res = {}
         for form in ("two", "pair"):
             x = x0.clone().cuda()

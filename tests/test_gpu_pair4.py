@@ -14,6 +14,7 @@ import pytest
 import torch
 
 import ssr_speech_amd  # noqa: F401
+import helpers_conditioning as HC
 from ssr_speech_amd import _lib
 from ssr_speech_amd.engine import PAIR4_WS_BYTES, DecodeEngine, LMWeightsArena
 from ssr_speech_amd.models.ssr import SSR_Speech
@@ -91,11 +92,14 @@ def _ffn2_args(weights, h, x, y, N, ny, act, epi):
     return a, b
 
 
-def _ffn2_chain(L, weights, N, act, epi, n_pairs, reps, seed):
-    """FFN2 + residual | LN + consumer, n_pairs pairs on the cycled granule buffers, replayed `reps` times, both forms"""
+def _ffn2_chain(L, weights, N, act, epi, n_pairs, reps, seed, x=None):
+    """FFN2 + residual | LN + consumer, n_pairs pairs on the cycled granule buffers, replayed `reps` times, both forms;
+    x [B, D] (CPU) replaces today's draw of the residual stream the chain starts from"""
     g = torch.Generator().manual_seed(seed)
     h = (torch.randn(B, F, generator=g) * 0.7).cuda()
     x0 = (torch.randn(B, D, generator=g) * 1.5 + 0.3).cuda()
+    if x is not None:
+        x0 = x.cuda()
     table = torch.randperm(B * MAX_PAGES, generator=g).view(B, MAX_PAGES).to(torch.int32).cuda()      # shuffled physical pages
     # one row on the last slot of a page, one on the first slot of a page, two mid-page
     pos = torch.tensor([_lib.PAGE - 1, 2 * _lib.PAGE, 130, 300], dtype=torch.int32, device="cuda")
@@ -143,6 +147,12 @@ def test_the_smallest_cycle_of_two_pairs_replayed_three_times(L, weights):
 def test_merge_form_is_bit_identical_to_the_two_launches(L, weights, MS, lens):
     """split-KV merge + out-projection + residual | LN + FFN1 + ReLU. Rows of <= 2 pages (the two prefetched pages alone), of more (the
     late loads), a length of 1, an odd max_splits; NaN beyond each row's pages; 5 pairs replayed twice. (The form has no early units.)"""
+    _merge_both_forms(L, weights, MS, lens)
+
+
+def _merge_both_forms(L, weights, MS, lens, part_ml=None):
+    """the chain of the test above; part_ml [B, H, MS, 2] (CPU, NaN beyond each row's pages) replaces today's draw of the partials"""
+    part_ml_given = part_ml
     g = torch.Generator().manual_seed(MS + lens[0])
     part_o = torch.randn(B, H, MS, HD, generator=g)
     part_ml = torch.stack([torch.randn(B, H, MS, generator=g) * 2, torch.rand(B, H, MS, generator=g) + 0.5], dim=-1).contiguous()
@@ -150,6 +160,8 @@ def test_merge_form_is_bit_identical_to_the_two_launches(L, weights, MS, lens):
         n = (lens[r] + _lib.PAGE - 1) // _lib.PAGE
         part_o[r, :, n:] = float("nan")
         part_ml[r, :, n:] = float("nan")
+    if part_ml_given is not None:
+        part_ml = part_ml_given
     part_o, part_ml = part_o.cuda(), part_ml.cuda()
     dlen = torch.tensor(lens, dtype=torch.int32, device="cuda")
     x0 = (torch.randn(B, D, generator=g) * 1.5 + 0.3).cuda()
@@ -175,6 +187,21 @@ def test_merge_form_is_bit_identical_to_the_two_launches(L, weights, MS, lens):
         assert bool((x[B * D:] == POISON).all()) and bool((y[B * F:] == POISON).all()), form
         res[form] = (x.cpu().numpy(), y.cpu().numpy())
     _compare(res, ("merge", MS, lens))
+
+
+@pytest.mark.parametrize("rows", ["offset", "step"])
+def test_ffn2_form_is_bit_identical_on_ill_conditioned_rows(L, weights, rows):
+    """FFN2 + residual | LN + head-MLP1 + GELU with the residual stream starting at rows with a large common offset / a step between
+    the LayerNorm's slices (tests/helpers_conditioning.py): the same bitwise comparison with the two launches"""
+    res, _ = _ffn2_chain(L, weights, 4096, _lib.ACT_GELU_ERF, _lib.EPI_STORE, 7, 2, 4096, x=HC.ln_rows(B, D, 4096)[rows])
+    _compare(res, "head1/" + rows)
+
+
+@pytest.mark.parametrize("partials", ["wide", "late_peak"])
+def test_merge_form_is_bit_identical_on_wide_partials(L, weights, partials):
+    """the merge form with partial maxima spread over +-180 / a peak of 150 on each row's last page; 8, 2, 3 and 5 pages"""
+    MS, lens = 8, [1000, 129, 300, 640]
+    _merge_both_forms(L, weights, MS, lens, part_ml=HC.ml_cases(B, H, MS, lens, 8)[partials])
 
 
 @pytest.mark.parametrize("case", ["B=2", "N=5120", "SSRHIP_GEMV_PAIR=0", "tiled"])

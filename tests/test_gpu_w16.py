@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import ssr_speech_amd  # noqa: F401
+import helpers_conditioning as HC
 import helpers_w16 as H
 from helpers_w16 import L, arena16, tiny2048  # noqa: F401  (module-scoped fixtures)
 from helpers_w16 import LAYERS, _same, _utterance
@@ -41,6 +42,23 @@ GROW = (4, 6)                 # prompt lengths of the engine-level tests: 9 + 4u
 @pytest.mark.parametrize("G,N,K,pro,act,epi", SHAPES)
 def test_w16_launch_is_bit_identical_to_the_fp32_launch_on_the_rounded_weights(L, B, G, N, K, pro, act, epi):
     H.check_launch(L, W16, B, G, N, K, pro, act, epi)
+
+
+@pytest.mark.parametrize("B", [1, 2, 4])
+@pytest.mark.parametrize("rows", ["offset", "step"])
+def test_w16_launch_is_bit_identical_on_ill_conditioned_rows(L, B, rows):
+    """LayerNorm + head-MLP1 + GELU at K = 2048 on rows with a large common offset / a step between slices (helpers_conditioning.ln_rows)"""
+    G, N, K, pro, act, epi = SHAPES[2]
+    H.check_launch(L, W16, B, G, N, K, pro, act, epi, x=HC.ln_rows(B, K, B)[rows])
+
+
+@pytest.mark.parametrize("B", [1, 2, 4])
+@pytest.mark.parametrize("partials", ["wide", "late_peak"])
+def test_w16_launch_is_bit_identical_on_wide_merge_partials(L, B, partials):
+    """the split-KV merge prologue with partial maxima spread over +-180 / a peak of 150 on the row's last page (helpers_conditioning.ml_cases)"""
+    G, N, K, pro, act, epi = SHAPES[4]
+    part_ml = HC.ml_cases(B, H.H, W16.max_pages, [300, 129, 384, 1][:B], B)[partials]     # the row lengths check_launch merges
+    H.check_launch(L, W16, B, G, N, K, pro, act, epi, part_ml=part_ml)
 
 
 def test_w16_refuses_a_shape_it_does_not_take_and_launches_nothing(L):

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import ssr_speech_amd  # noqa: F401
+import helpers_conditioning as HC
 import helpers_w8 as H8
 from helpers_w16 import L, arena16, tiny2048  # noqa: F401  (module-scoped fixtures)
 from helpers_w16 import LAYERS, _prompts, _same, _utterance
@@ -76,6 +77,21 @@ def test_the_arena_quantises_on_the_gpu_as_on_the_cpu(tiny2048, arena8):
 @pytest.mark.parametrize("G,N,K,pro,act,epi", SHAPES)
 def test_w8_launch_is_bit_identical_to_the_fp32_launch_on_the_masters(L, B, G, N, K, pro, act, epi):
     H8.check_launch(L, B, G, N, K, pro, act, epi)
+
+
+@pytest.mark.parametrize("B", [1, 2, 4])
+@pytest.mark.parametrize("rows", ["offset", "step"])
+def test_w8_launch_is_bit_identical_on_ill_conditioned_rows(L, B, rows):
+    G, N, K, pro, act, epi = SHAPES[2]                                        # LayerNorm + head-MLP1 + GELU, K = 2048
+    H8.check_launch(L, B, G, N, K, pro, act, epi, x=HC.ln_rows(B, K, B)[rows])
+
+
+@pytest.mark.parametrize("B", [1, 2, 4])
+@pytest.mark.parametrize("partials", ["wide", "late_peak"])
+def test_w8_launch_is_bit_identical_on_wide_merge_partials(L, B, partials):
+    G, N, K, pro, act, epi = SHAPES[4]                                        # split-KV merge + out-projection + residual
+    part_ml = HC.ml_cases(B, H8.H, 3, [300, 129, 384, 1][:B], B)[partials]           # check_launch's pages and row lengths
+    H8.check_launch(L, B, G, N, K, pro, act, epi, part_ml=part_ml)
 
 
 @pytest.mark.parametrize("depth", ["0", "2", "8"])

@@ -20,6 +20,7 @@ import pytest
 import torch
 
 import ssr_speech_amd  # noqa: F401
+import helpers_conditioning as HC
 from ssr_speech_amd import _lib
 from ssr_speech_amd.engine import DecodeEngine, LMWeightsArena, e4m3_master, quantize_e4m3, to_w8_order
 from ssr_speech_amd.models.ssr import SSR_Speech
@@ -113,9 +114,16 @@ def _compare(res, what):
 def test_ffn2_form_is_bit_identical_three_ways(L, weights, name, N, act, epi):
     """FFN2 + residual | LN + consumer: 7 pairs on the cycled granule buffers, replayed twice (stale tags would show). Residual stream,
     consumer output (pads included) and the whole KV pool: pair_w8 == two w8 launches == the fp32 pair on the masters."""
+    _ffn2_three_ways(L, weights, name, N, act, epi)
+
+
+def _ffn2_three_ways(L, weights, name, N, act, epi, x=None):
+    """the chain of the test above; x [B, D] (CPU) replaces today's draw of the residual stream the chain starts from"""
     g = torch.Generator().manual_seed(N)
     h = (torch.randn(B, F, generator=g) * 0.7).cuda()
     x0 = (torch.randn(B, D, generator=g) * 1.5 + 0.3).cuda()
+    if x is not None:
+        x0 = x.cuda()
     table = torch.randperm(B * MAX_PAGES, generator=g).view(B, MAX_PAGES).to(torch.int32).cuda()      # shuffled physical pages
     pos = torch.tensor([130, 300], dtype=torch.int32, device="cuda")
     qkv = epi == _lib.EPI_QKV_APPEND
@@ -153,6 +161,12 @@ def test_ffn2_form_is_bit_identical_three_ways(L, weights, name, N, act, epi):
 def test_merge_form_is_bit_identical_three_ways(L, weights, monkeypatch, MS, lens, early):
     """split-KV merge + out-projection + residual | LN + FFN1 + ReLU: contexts of 8 / 2 pages (beyond the 6 prefetched ones / short),
     3 / 5 pages, an odd max_splits; NaN beyond each row's pages; 5 pairs replayed twice; with B's early units and without."""
+    _merge_three_ways(L, weights, monkeypatch, MS, lens, early)
+
+
+def _merge_three_ways(L, weights, monkeypatch, MS, lens, early, part_ml=None):
+    """the chain of the test above; part_ml [B, H, MS, 2] (CPU, NaN beyond each row's pages) replaces today's draw of the partials"""
+    part_ml_given = part_ml
     if early is None:
         monkeypatch.delenv("SSRHIP_GEMV_PAIR_EARLY", raising=False)
     else:
@@ -164,6 +178,8 @@ def test_merge_form_is_bit_identical_three_ways(L, weights, monkeypatch, MS, len
         n = (lens[r] + _lib.PAGE - 1) // _lib.PAGE
         part_o[r, :, n:] = float("nan")
         part_ml[r, :, n:] = float("nan")
+    if part_ml_given is not None:
+        part_ml = part_ml_given
     part_o, part_ml = part_o.cuda(), part_ml.cuda()
     dlen = torch.tensor(lens, dtype=torch.int32, device="cuda")
     x0 = (torch.randn(B, D, generator=g) * 1.5 + 0.3).cuda()
@@ -189,6 +205,20 @@ def test_merge_form_is_bit_identical_three_ways(L, weights, monkeypatch, MS, len
         assert bool((x[B * D:] == POISON).all()) and bool((y[B * F:] == POISON).all()), form
         res[form] = (x.cpu().numpy(), y.cpu().numpy())
     _compare(res, ("merge", MS, lens, early))
+
+
+@pytest.mark.parametrize("rows", ["offset", "step"])
+def test_ffn2_form_is_bit_identical_on_ill_conditioned_rows(L, weights, rows):
+    """FFN2 + residual | LN + head-MLP1 + GELU with the residual stream starting at rows with a large common offset / a step between
+    the LayerNorm's slices (tests/helpers_conditioning.py): the same three-way bitwise comparison"""
+    _ffn2_three_ways(L, weights, "head1/" + rows, 4096, _lib.ACT_GELU_ERF, _lib.EPI_STORE, x=HC.ln_rows(B, D, 4096)[rows])
+
+
+@pytest.mark.parametrize("partials", ["wide", "late_peak"])
+def test_merge_form_is_bit_identical_on_wide_partials(L, weights, monkeypatch, partials):
+    """the merge form with partial maxima spread over +-180 / a peak of 150 on each row's last page, 8 and 2 pages"""
+    MS, lens = 8, [1000, 129]
+    _merge_three_ways(L, weights, monkeypatch, MS, lens, None, part_ml=HC.ml_cases(B, H, MS, lens, 8)[partials])
 
 
 @pytest.mark.parametrize("case", ["B=4", "N=5120", "SSRHIP_GEMV_PAIR=0", "SSRHIP_GEMV_SEG=0"])

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import ssr_speech_amd  # noqa: F401
+import helpers_conditioning as HC
 import helpers_w16 as H
 from helpers_w16 import L, arena16, tiny2048  # noqa: F401  (module-scoped fixtures)
 from helpers_w16 import LAYERS, _same, _utterance
@@ -47,6 +48,15 @@ GROW = (4, 6)                 # prompt lengths of the engine-level tests: 9 + 4u
 @pytest.mark.parametrize("G,N,K,pro,act,epi", SHAPES)
 def test_wt16_launch_is_bit_identical_to_the_fp32_launch_on_the_rounded_weights(L, B, G, N, K, pro, act, epi, tiled):
     H.check_launch(L, WT16, B, G, N, K, pro, act, epi, tiled)
+
+
+@pytest.mark.parametrize("tiled", [0, 1], ids=["rowmajor", "tiled"])
+@pytest.mark.parametrize("B", [5, 16])
+@pytest.mark.parametrize("rows", ["offset", "step"])
+def test_wt16_launch_is_bit_identical_on_ill_conditioned_rows(L, B, rows, tiled):
+    """LayerNorm + head-MLP1 + GELU at K = 2048 on rows with a large common offset / a step between slices (helpers_conditioning.ln_rows)"""
+    G, N, K, pro, act, epi = SHAPES[2]
+    H.check_launch(L, WT16, B, G, N, K, pro, act, epi, tiled, x=HC.ln_rows(B, K, B)[rows])
 
 
 @pytest.mark.parametrize("N,act,epi", [(6144, _lib.ACT_NONE, _lib.EPI_QKV_APPEND), (8192, _lib.ACT_RELU, _lib.EPI_STORE)], ids=["qkv", "ffn1"])

@@ -14,6 +14,7 @@ import pytest
 import torch
 
 import ssr_speech_amd  # noqa: F401
+import helpers_conditioning as HC
 import helpers_w16 as H
 from helpers_w16 import L, arena16, tiny2048  # noqa: F401  (module-scoped fixtures)
 from helpers_w16 import LAYERS, _same, _utterance
@@ -51,6 +52,15 @@ GROW = (2, 3)                 # prompt lengths of the engine-level tests: 9 + 2u
 @pytest.mark.parametrize("G,N,K,pro,act,epi", SHAPES)
 def test_wt32_launch_is_bit_identical_to_the_fp32_launch_on_the_rounded_weights(L, B, G, N, K, pro, act, epi, tiled):
     H.check_launch(L, WT32, B, G, N, K, pro, act, epi, tiled)
+
+
+@pytest.mark.parametrize("tiled", [0, 1], ids=["rowmajor", "tiled"])
+@pytest.mark.parametrize("B", [17, 32])
+@pytest.mark.parametrize("rows", ["offset", "step"])
+def test_wt32_launch_is_bit_identical_on_ill_conditioned_rows(L, B, rows, tiled):
+    """LayerNorm + head-MLP1 + GELU at K = 2048 on rows with a large common offset / a step between slices (helpers_conditioning.ln_rows)"""
+    G, N, K, pro, act, epi = SHAPES[2]
+    H.check_launch(L, WT32, B, G, N, K, pro, act, epi, tiled, x=HC.ln_rows(B, K, B)[rows])
 
 
 def test_wt32_refuses_a_shape_it_does_not_take_and_launches_nothing(L):

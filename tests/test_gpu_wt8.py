@@ -14,6 +14,7 @@ import torch
 import torch.nn.functional as F
 
 import ssr_speech_amd  # noqa: F401
+import helpers_conditioning as HC
 import helpers_w16 as H
 import helpers_wt8 as H8
 from helpers_w16 import L, arena16, tiny2048  # noqa: F401  (module-scoped fixtures)
@@ -60,6 +61,15 @@ def arena8(tiny2048):
 @pytest.mark.parametrize("G,N,K,pro,act,epi", SHAPES)
 def test_wt8_launch_is_bit_identical_to_the_fp32_launch_on_code_times_scale(L, B, G, N, K, pro, act, epi, tiled):
     H8.check_launch(L, B, G, N, K, pro, act, epi, tiled, KV_POS)
+
+
+@pytest.mark.parametrize("tiled", [0, 1], ids=["rowmajor", "tiled"])
+@pytest.mark.parametrize("B", [5, 16])
+@pytest.mark.parametrize("rows", ["offset", "step"])
+def test_wt8_launch_is_bit_identical_on_ill_conditioned_rows(L, B, rows, tiled):
+    """LayerNorm + head-MLP1 + GELU at K = 2048 on rows with a large common offset / a step between slices (helpers_conditioning.ln_rows)"""
+    G, N, K, pro, act, epi = (1, 4096, 2048, LN, _lib.ACT_GELU_ERF, _lib.EPI_STORE)
+    H8.check_launch(L, B, G, N, K, pro, act, epi, tiled, KV_POS, x=HC.ln_rows(B, K, B)[rows])
 
 
 # ------------------------------------------------------------------------------------------ 2. scale placement
