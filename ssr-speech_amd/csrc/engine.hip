@@ -171,6 +171,39 @@ void pair_slot_release(int dev) {
   if (sl.fd >= 0) { flock(sl.fd, LOCK_UN); close(sl.fd); sl.fd = -1; }
 }
 
+// give pairing back: the workspace, the device's slot and both "this engine's step pairs its ..." flags (a caller that pairs again sets its own)
+void lm_unpair(ssrhip_lm* lm) {
+  if (lm->pair_ws) { hipFree(lm->pair_ws); lm->pair_ws = nullptr; }
+  if (lm->pair_dev >= 0) { pair_slot_release(lm->pair_dev); lm->pair_dev = -1; }
+  lm->pk_pair = lm->pair4 = false;
+}
+
+// What differs between the pairing decisions of ssrhip_lm_create (fp32, 2 rows), ssrhip_lm_set_w16_pair / ssrhip_lm_set_w8_pair and
+// ssrhip_lm_set_pair4: whom StepShapes::pair_plan asks, the workspace, where the refusal is read and the texts.
+struct PairSpec {
+  int kind; size_t ws_bytes;      // pair_plan's packed_kind (-1: the fp32 forms of 2 rows); SSRHIP_PAIR_WS_BYTES or SSRHIP_PAIR4_WS_BYTES
+  const char* (*why)();           // the refusal of the kind's _applicable ...
+  const char* no_reason;          // ... and what is said when it left none (null: the empty text stands)
+  const char* who;                // the entry point an allocation failure names
+  const char* slot_taken;         // the stderr line when another chain holds the device's slot (%s: who holds it)
+  const char* forced; const char* holds;   // pair_why of an engine that pairs: pair_mode 2 / with the slot
+};
+const PairSpec PAIRSPEC_FP32 = {-1, SSRHIP_PAIR_WS_BYTES, ssrhip_gemv_pair_why, nullptr, "ssrhip_lm_create",
+                                "ssrhip: this 2-row decode engine steps WITHOUT pair launches (same tokens, ~5 %% slower): %s\n",
+                                "forced on by the caller (pair_mode 2: no slot, no guard)", "this engine holds the pairing slot of its device"};
+const PairSpec PAIRSPEC_W16 = {PK_W16, SSRHIP_PAIR_WS_BYTES, ssrhip_gemv_pair_w16_why, nullptr, "ssrhip_lm_set_w16_pair",
+                               "ssrhip: this 2-row decode engine steps WITHOUT bf16 pair launches (same tokens): %s\n",
+                               "bf16 pair launches (ssrhip_gemv_pair_w16), forced on by the caller (pair_mode 2: no slot, no guard)",
+                               "bf16 pair launches (ssrhip_gemv_pair_w16): this engine holds the pairing slot of its device"};
+const PairSpec PAIRSPEC_W8 = {PK_W8, SSRHIP_PAIR_WS_BYTES, ssrhip_gemv_pair_w8_why, nullptr, "ssrhip_lm_set_w8_pair",
+                              "ssrhip: this 2-row decode engine steps WITHOUT e4m3 pair launches (same tokens): %s\n",
+                              "e4m3 pair launches (ssrhip_gemv_pair_w8), forced on by the caller (pair_mode 2: no slot, no guard)",
+                              "e4m3 pair launches (ssrhip_gemv_pair_w8): this engine holds the pairing slot of its device"};
+const PairSpec PAIRSPEC_PAIR4 = {PK_PAIR4, SSRHIP_PAIR4_WS_BYTES, ssrhip_gemv_pair4_why, "fewer than two launches of the step qualify for the 4-row pair forms",
+                                 "ssrhip_lm_set_pair4", "ssrhip: this 4-row decode engine steps WITHOUT its 4-row pair launches (same tokens): %s\n",
+                                 "4-row pair launches (ssrhip_gemv_pair4), forced on by the caller (pair_mode 2: no slot, no guard)",
+                                 "4-row pair launches (ssrhip_gemv_pair4): this engine holds the pairing slot of its device"};
+
 __global__ void occupy_kernel(long long ticks, int lds_floats, int* started) {
   extern __shared__ float occ[];
   for (int i = threadIdx.x; i < lds_floats; i += blockDim.x) occ[i] = (float)i;
@@ -515,6 +548,37 @@ int enqueue_step(ssrhip_lm* lm, hipStream_t s, Timer* tm) {
   return 0;
 }
 
+// The pairing decision, once: may the step of this engine run pair launches of the spec's kind? Everything was given back before
+// (lm_unpair, or a new engine). 1: it pairs — workspace allocated and zeroed (every tag invalid), the device's slot held unless pair_mode
+// is 2 — and the caller sets the flag of its kind; 0: it does not, lm->pair_why says why; -1: the allocation failed (nothing is held).
+int lm_take_pairing(ssrhip_lm* lm, const PairSpec& sp) {
+  const int pair_mode = lm->b.pair_mode;
+  if (pair_mode == 1) { snprintf(lm->pair_why, sizeof(lm->pair_why), "switched off by the caller (pair_mode 1)"); return 0; }
+  // does the step pair at all (shapes, CU count, occupancy, CU mask, SSRHIP_GEMV_PAIR) ...
+  bool pq, ph, pf;
+  if (StepShapes(lm).pair_plan(&pq, &ph, &pf, sp.kind) == 0) {
+    const char* why = sp.why();
+    snprintf(lm->pair_why, sizeof(lm->pair_why), "%s", (why[0] || !sp.no_reason) ? why : sp.no_reason);
+    return 0;
+  }
+  if (pair_mode != 2) {   // ... and may THIS engine do it? A refusal the user did not ask for: say it once on stderr
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) dev = -1;
+    if (!pair_slot_acquire(dev, lm->pair_why, sizeof(lm->pair_why))) {
+      fprintf(stderr, sp.slot_taken, lm->pair_why);
+      return 0;
+    }
+    lm->pair_dev = dev;
+  }
+  if (hipMalloc(&lm->pair_ws, sp.ws_bytes) != hipSuccess || hipMemset(lm->pair_ws, 0, sp.ws_bytes) != hipSuccess) {
+    lm_unpair(lm);
+    ssrhip_set_error("%s: allocating the pair workspace failed", sp.who);
+    return -1;
+  }
+  snprintf(lm->pair_why, sizeof(lm->pair_why), "%s", pair_mode == 2 ? sp.forced : sp.holds);
+  return 1;
+}
+
 }  // namespace
 
 extern "C" int ssrhip_lm_create(const ssrhip_lm_dims* d, const ssrhip_lm_weights* w, const ssrhip_lm_buffers* b, ssrhip_lm** out) {
@@ -567,37 +631,9 @@ extern "C" int ssrhip_lm_create(const ssrhip_lm_dims* d, const ssrhip_lm_weights
   { const char* e = getenv("SSRHIP_PREFILL_SPLIT"); lm->prefill_split = has_ws && !(e && e[0] == '0'); }
   if (b->B != 2) {
     snprintf(lm->pair_why, sizeof(lm->pair_why), "pair launches exist for the 2-row step only (this engine has %d rows)", b->B);
-  } else {
-    // does the 2-row step pair at all (shapes, CU count, occupancy, CU mask, SSRHIP_GEMV_PAIR), and may THIS engine do it?
-    bool want = b->pair_mode != 1;
-    bool loud = false;                                              // a refusal the user did not ask for: say it once on stderr
-    if (!want) snprintf(lm->pair_why, sizeof(lm->pair_why), "switched off by the caller (pair_mode 1)");
-    if (want) {
-      bool pq, ph, pf;
-      if (StepShapes(lm).pair_plan(&pq, &ph, &pf) == 0) {
-        want = false;
-        snprintf(lm->pair_why, sizeof(lm->pair_why), "%s", ssrhip_gemv_pair_why());
-      }
-    }
-    if (want && b->pair_mode != 2) {
-      int dev = 0;
-      if (hipGetDevice(&dev) != hipSuccess) dev = -1;
-      if (pair_slot_acquire(dev, lm->pair_why, sizeof(lm->pair_why))) lm->pair_dev = dev;
-      else { want = false; loud = true; }
-    }
-    if (want) {                                   // granules + give-up flag of the paired GEMV launches (zeroed: every tag invalid)
-      if (hipMalloc(&lm->pair_ws, SSRHIP_PAIR_WS_BYTES) != hipSuccess || hipMemset(lm->pair_ws, 0, SSRHIP_PAIR_WS_BYTES) != hipSuccess) {
-        if (lm->pair_ws) hipFree(lm->pair_ws);
-        if (lm->pair_dev >= 0) pair_slot_release(lm->pair_dev);
-        delete lm;
-        ssrhip_set_error("ssrhip_lm_create: allocating the pair workspace failed");
-        return -1;
-      }
-      snprintf(lm->pair_why, sizeof(lm->pair_why), b->pair_mode == 2 ? "forced on by the caller (pair_mode 2: no slot, no guard)"
-                                                                     : "this engine holds the pairing slot of its device");
-    } else if (loud) {
-      fprintf(stderr, "ssrhip: this 2-row decode engine steps WITHOUT pair launches (same tokens, ~5 %% slower): %s\n", lm->pair_why);
-    }
+  } else if (lm_take_pairing(lm, PAIRSPEC_FP32) < 0) {
+    delete lm;
+    return -1;
   }
   *out = lm;
   return 0;
@@ -632,9 +668,7 @@ static int lm_set_packed(ssrhip_lm* lm, const ssrhip_lm_w16* rec, int kind) {
   lm->pk_kind = kind;
   if (ps.unpairs) {   // the default pair launches stream fp32 weights: this engine steps unpaired and gives the device's pairing slot back
                       // (ssrhip_lm_set_w16_pair may take it again for the pair launches over the packed copies)
-    if (lm->pair_ws) { hipFree(lm->pair_ws); lm->pair_ws = nullptr; }
-    if (lm->pair_dev >= 0) { pair_slot_release(lm->pair_dev); lm->pair_dev = -1; }
-    lm->pk_pair = false;
+    lm_unpair(lm);
     snprintf(lm->pair_why, sizeof(lm->pair_why), "this engine streams bf16 weights (%s): its pair launches are an opt-in (ssrhip_lm_set_w16_pair, 2 rows)", ps.setter);
   }
   return 0;
@@ -678,9 +712,7 @@ static int lm_set_codes(ssrhip_lm* lm, const ssrhip_lm_w8* rec, int kind) {
   if (kind == PK_WT8) return 0;   // engines of more than 4 rows never pair
   // the default pair launches stream fp32 weights: this engine steps unpaired and gives the device's pairing slot back
   // (ssrhip_lm_set_w8_pair may take it again for the pair launches over the codes)
-  if (lm->pair_ws) { hipFree(lm->pair_ws); lm->pair_ws = nullptr; }
-  if (lm->pair_dev >= 0) { pair_slot_release(lm->pair_dev); lm->pair_dev = -1; }
-  lm->pk_pair = false;
+  lm_unpair(lm);
   snprintf(lm->pair_why, sizeof(lm->pair_why), "this engine streams e4m3 weights (ssrhip_lm_set_w8): its pair launches are an opt-in (ssrhip_lm_set_w8_pair, 2 rows)");
   return 0;
 }
@@ -756,44 +788,22 @@ extern "C" int ssrhip_lm_w16_launches(const ssrhip_lm* lm) { return lm_packed_la
 // Pair launches over the packed weights of the engine's kind: the bf16 copies (csrc/gemv_pair_w16.hip) or the e4m3 codes and scales
 // (csrc/gemv_pair_w8.hip). on = 1 repeats ssrhip_lm_create's pairing decision for this engine, with the question put to the kind's
 // _applicable; on = 0 gives everything back (the state the stream's setter left). One body, the names of the kind in a record.
-struct PackedPair { int kind; const char* setter; const char* stream_setter; const char* fmt; const char* entry; const char* (*why)(); };
-const PackedPair PAIR_W16 = {PK_W16, "ssrhip_lm_set_w16_pair", "ssrhip_lm_set_w16", "bf16", "ssrhip_gemv_pair_w16", ssrhip_gemv_pair_w16_why};
-const PackedPair PAIR_W8 = {PK_W8, "ssrhip_lm_set_w8_pair", "ssrhip_lm_set_w8", "e4m3", "ssrhip_gemv_pair_w8", ssrhip_gemv_pair_w8_why};
+struct PackedPair { int kind; const char* setter; const char* stream_setter; const char* fmt; const PairSpec& spec; };
+const PackedPair PAIR_W16 = {PK_W16, "ssrhip_lm_set_w16_pair", "ssrhip_lm_set_w16", "bf16", PAIRSPEC_W16};
+const PackedPair PAIR_W8 = {PK_W8, "ssrhip_lm_set_w8_pair", "ssrhip_lm_set_w8", "e4m3", PAIRSPEC_W8};
 static int lm_set_packed_pair(ssrhip_lm* lm, int on, const PackedPair& pp) {
   SSR_REQUIRE(lm, "%s: null engine", pp.setter);
   SSR_REQUIRE(!lm->exec, "%s: the decode step of this engine is already captured (call it before the first ssrhip_lm_decode)", pp.setter);
   SSR_REQUIRE(lm->b.B == 2, "%s: pair launches exist for the 2-row step only (this engine has %d rows)", pp.setter, lm->b.B);
   SSR_REQUIRE(lm->pk_kind == pp.kind, "%s: this engine does not stream %s weights (%s comes first)", pp.setter, pp.fmt, pp.stream_setter);
-  if (lm->pair_ws) { hipFree(lm->pair_ws); lm->pair_ws = nullptr; }
-  if (lm->pair_dev >= 0) { pair_slot_release(lm->pair_dev); lm->pair_dev = -1; }
-  lm->pk_pair = false;
+  lm_unpair(lm);
   if (!on) {
     snprintf(lm->pair_why, sizeof(lm->pair_why), "this engine streams %s weights (%s) and its %s pair launches are switched off (%s)", pp.fmt, pp.stream_setter, pp.fmt, pp.setter);
     return 0;
   }
-  const int pair_mode = lm->b.pair_mode;
-  if (pair_mode == 1) { snprintf(lm->pair_why, sizeof(lm->pair_why), "switched off by the caller (pair_mode 1)"); return 0; }
-  bool pq, ph, pf;
-  if (StepShapes(lm).pair_plan(&pq, &ph, &pf, pp.kind) == 0) { snprintf(lm->pair_why, sizeof(lm->pair_why), "%s", pp.why()); return 0; }
-  if (pair_mode != 2) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = -1;
-    if (!pair_slot_acquire(dev, lm->pair_why, sizeof(lm->pair_why))) {
-      fprintf(stderr, "ssrhip: this 2-row decode engine steps WITHOUT %s pair launches (same tokens): %s\n", pp.fmt, lm->pair_why);
-      return 0;
-    }
-    lm->pair_dev = dev;
-  }
-  if (hipMalloc(&lm->pair_ws, SSRHIP_PAIR_WS_BYTES) != hipSuccess || hipMemset(lm->pair_ws, 0, SSRHIP_PAIR_WS_BYTES) != hipSuccess) {
-    if (lm->pair_ws) { hipFree(lm->pair_ws); lm->pair_ws = nullptr; }
-    if (lm->pair_dev >= 0) { pair_slot_release(lm->pair_dev); lm->pair_dev = -1; }
-    ssrhip_set_error("%s: allocating the pair workspace failed", pp.setter);
-    return -1;
-  }
-  lm->pk_pair = true;
-  snprintf(lm->pair_why, sizeof(lm->pair_why), pair_mode == 2 ? "%s pair launches (%s), forced on by the caller (pair_mode 2: no slot, no guard)"
-                                                              : "%s pair launches (%s): this engine holds the pairing slot of its device", pp.fmt, pp.entry);
-  return 0;
+  const int rc = lm_take_pairing(lm, pp.spec);
+  lm->pk_pair = rc == 1;
+  return rc < 0 ? -1 : 0;
 }
 static int lm_packed_pair_launches(const ssrhip_lm* lm, int kind) { return lm && lm->pk_pair && lm->pk_kind == kind ? lm->pk_pair_launches : 0; }
 extern "C" int ssrhip_lm_set_w16_pair(ssrhip_lm* lm, int on) { return lm_set_packed_pair(lm, on, PAIR_W16); }
@@ -808,40 +818,14 @@ extern "C" int ssrhip_lm_set_pair4(ssrhip_lm* lm, int on) {
   SSR_REQUIRE(!lm->exec, "ssrhip_lm_set_pair4: the decode step of this engine is already captured (call it before the first ssrhip_lm_decode)");
   SSR_REQUIRE(lm->b.B == 4, "ssrhip_lm_set_pair4: the 4-row pair launches exist for the 4-row step only (this engine has %d rows)", lm->b.B);
   SSR_REQUIRE(lm->pk_kind < 0, "ssrhip_lm_set_pair4: this engine streams packed weights; the 4-row pair launches read the fp32 masters");
-  if (lm->pair_ws) { hipFree(lm->pair_ws); lm->pair_ws = nullptr; }
-  if (lm->pair_dev >= 0) { pair_slot_release(lm->pair_dev); lm->pair_dev = -1; }
-  lm->pair4 = false;
+  lm_unpair(lm);
   if (!on) {
     snprintf(lm->pair_why, sizeof(lm->pair_why), "the 4-row pair launches of this engine are switched off (ssrhip_lm_set_pair4)");
     return 0;
   }
-  const int pair_mode = lm->b.pair_mode;
-  if (pair_mode == 1) { snprintf(lm->pair_why, sizeof(lm->pair_why), "switched off by the caller (pair_mode 1)"); return 0; }
-  bool pq, ph, pf;
-  if (StepShapes(lm).pair_plan(&pq, &ph, &pf, PK_PAIR4) == 0) {
-    const char* why = ssrhip_gemv_pair4_why();
-    snprintf(lm->pair_why, sizeof(lm->pair_why), "%s", why[0] ? why : "fewer than two launches of the step qualify for the 4-row pair forms");
-    return 0;
-  }
-  if (pair_mode != 2) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = -1;
-    if (!pair_slot_acquire(dev, lm->pair_why, sizeof(lm->pair_why))) {
-      fprintf(stderr, "ssrhip: this 4-row decode engine steps WITHOUT its 4-row pair launches (same tokens): %s\n", lm->pair_why);
-      return 0;
-    }
-    lm->pair_dev = dev;
-  }
-  if (hipMalloc(&lm->pair_ws, SSRHIP_PAIR4_WS_BYTES) != hipSuccess || hipMemset(lm->pair_ws, 0, SSRHIP_PAIR4_WS_BYTES) != hipSuccess) {
-    if (lm->pair_ws) { hipFree(lm->pair_ws); lm->pair_ws = nullptr; }
-    if (lm->pair_dev >= 0) { pair_slot_release(lm->pair_dev); lm->pair_dev = -1; }
-    ssrhip_set_error("ssrhip_lm_set_pair4: allocating the pair workspace failed");
-    return -1;
-  }
-  lm->pair4 = true;
-  snprintf(lm->pair_why, sizeof(lm->pair_why), pair_mode == 2 ? "4-row pair launches (ssrhip_gemv_pair4), forced on by the caller (pair_mode 2: no slot, no guard)"
-                                                              : "4-row pair launches (ssrhip_gemv_pair4): this engine holds the pairing slot of its device");
-  return 0;
+  const int rc = lm_take_pairing(lm, PAIRSPEC_PAIR4);
+  lm->pair4 = rc == 1;
+  return rc < 0 ? -1 : 0;
 }
 extern "C" int ssrhip_lm_pair4_launches(const ssrhip_lm* lm) { return lm && lm->pair4 ? lm->pair4_launches : 0; }
 extern "C" int ssrhip_lm_wt16_launches(const ssrhip_lm* lm) { return lm_packed_launches(lm, PK_WT16); }
@@ -868,8 +852,7 @@ extern "C" void ssrhip_lm_destroy(ssrhip_lm* lm) {
   if (lm->exec) hipGraphExecDestroy(lm->exec);
   if (lm->graph) hipGraphDestroy(lm->graph);
   if (lm->cap_stream) hipStreamDestroy(lm->cap_stream);
-  if (lm->pair_ws) hipFree(lm->pair_ws);
-  if (lm->pair_dev >= 0) pair_slot_release(lm->pair_dev);
+  lm_unpair(lm);
   delete lm;
 }
 

@@ -26,7 +26,7 @@
 #include <stdlib.h>
 #include "common.h"
 #include "gemv_shared.h"
-#include "gemv_pair.h"
+#include "gemv_pair_host.h"
 
 namespace {
 
@@ -729,62 +729,9 @@ __global__ __launch_bounds__(SEG_TH, 2) void gemv_segu_kernel(const GemvK p) {
 // flag (ssrhip_gemv_pair_status) and raises. The launch needs all its 256 workgroups resident at the same time: true on an otherwise
 // idle or ordinarily busy GPU (other kernels finish and make room), NOT when a second pair launch of another stream / process holds
 // half the CUs at the same moment — one decode chain per device, or SSRHIP_GEMV_PAIR=0.
-// (the PAIR_* constants, PairK, pair_sweep8 and the edge role pair_edge_role<SA, NPRE> live in gemv_pair.h: gemv_pair_w16.hip shares them)
-// ---- the streaming role from barrier (1) on: B = LayerNorm + Linear on x' (gemv_segu_kernel<2, PRO_LAYERNORM, NUWB, 4>, operation for operation)
-// EARLY (round 6, the merge form only): B's units 0 .. EARLY - 1 were requested at kernel ENTRY into the ring slots A does not use
-// (unit j lives in w[(j + EARLY) % DEPTH]); what is requested here starts behind them. Same arithmetic, same order of operations.
-// PFX = units in flight behind barrier (1b), i.e. in front of the gather's loads (PAIR_PF = 3 for the forms without early units).
-template <int NUWB, int EARLY = 0, int PFX = PAIR_PF>
-__device__ __forceinline__ void pair_stream_b(const PairK& p, int t, int lane, int wave, float4 (&xr)[2][4], float4 (&w)[PAIR_DEPTH][4],
-                                              const RowEpi& efinB, float* partB, float* aux, const float* xs, const size_t* kvoff) {
-  constexpr int B = 2, DEPTH = PAIR_DEPTH, PF = PFX, SB = 2, SHB = 1, RB = NUWB * SEG_NW / SB;
-  static_assert(PFX >= EARLY && PFX <= PAIR_DEPTH, "units requested at (1b) start behind the early ones and fit the ring");
-  static_assert(EARLY == 0 || EARLY == 2, "ring slots 2 and 3 are the ones the merge form's A phase leaves free");
-  const ssrhip_gemv_args& bb = p.b.a;
-  const int rB0 = (int)blockIdx.x * RB, segB = wave & (SB - 1);
-  const int bfin = t % B, rfinB = min(t / B, RB - 1), nfinB = rB0 + rfinB;
-  const float* WgB = bb.W + (size_t)rB0 * bb.K + segB * SEG + lane * 4;
-  __syncthreads();                                                  // (1b) wave 8 has issued the publish
-  // B's first units: PF of them now, the rest behind the gather
-#pragma unroll
-  for (int j = EARLY; j < PF; ++j)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) w[(j + EARLY) % DEPTH][i] = ld_nt(WgB + (size_t)((wave + SEG_NW * j) >> SHB) * bb.K + i * 256);
-  __syncthreads();                                                  // (2) x' is in LDS
-  seg_load_x<B>(xr, xs, PAIR_D, segB, lane);
-#pragma unroll
-  for (int j = PF; j < DEPTH; ++j)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) w[(j + EARLY) % DEPTH][i] = ld_nt(WgB + (size_t)((wave + SEG_NW * j) >> SHB) * bb.K + i * 256);
-  seg_layernorm<B>(xr, aux, SB, bb.K, bb.ln_eps, wave, lane);       // its barrier is (3)
-  // units
-#pragma unroll
-  for (int j = 0; j < NUWB; ++j) {
-    float4 (&wj)[4] = w[(j + EARLY) % DEPTH];
-    float acc[B][2];
-#pragma unroll
-    for (int b = 0; b < B; ++b) acc[b][0] = acc[b][1] = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-#pragma unroll
-      for (int b = 0; b < B; ++b) acc[b][i & 1] = dot4(wj[i], xr[b][i], acc[b][i & 1]);
-      if (j + DEPTH < NUWB) {
-        __builtin_amdgcn_sched_barrier(0);
-        wj[i] = ld_nt(WgB + (size_t)((wave + SEG_NW * (j + DEPTH)) >> SHB) * bb.K + i * 256);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    seg_park<B>(acc, partB, wave + SEG_NW * j, lane);
-  }
-  __syncthreads();                                                  // (4)
-  if (t < RB * B) {
-    // K / V append addresses: resolved by the edge role (wave 9) while this role streamed — the kv_pos -> page table -> pool chain costs
-    // the streaming waves nothing here (in gemv_segu_kernel it is two scalar round trips per wave under the first units' latency)
-    float* kvb[2] = {bb.kv.pool + kvoff[bfin * 2], bb.kv.pool + kvoff[bfin * 2 + 1]};
-    seg_finish_row<B>(p.b, 0, partB, SB, rfinB, nfinB, bfin, efinB, kvb);
-  }
-}
-
+// (the PAIR_* constants, PairK, pair_sweep8 and the edge role pair_edge_role<B, SA, NPRE> live in gemv_pair.h: every pair unit shares them)
+// The streaming role's phases (pair_stream_a, pair_merge_request, pair_units, pair_stream_b) live there too, written once for the three
+// weight streams and both row counts; this file instantiates them with WsF32 (gemv_wstream.h): gemv_segu_kernel<2, .., 4>'s operations.
 // The two ROLES are the two arms of ONE (wave-uniform) branch and every barrier is written in both arms. A first form — a series of
 // `if (wave < 8)` blocks with joins in between — made hipcc's wait-count pass merge the "block skipped" path into every join: the first use
 // of a unit requested two blocks earlier was guarded by `s_waitcnt vmcnt(4 * PF - 1)` instead of vmcnt(15) (B's phase ran with 8 loads in
@@ -817,33 +764,12 @@ __global__ __launch_bounds__(PAIR_TH, 2) void gemv_pair_kernel(const PairK p) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) xr[b][i] = ld4(a.x + (size_t)b * a.x_stride + wave * SEG + (i * 64 + lane) * 4);
     float4 w[DEPTH][4];
-#pragma unroll
-    for (int j = 0; j < DEPTH; ++j)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) w[j][i] = ld_nt(WgA + (size_t)((wave + SEG_NW * j) >> SHA) * a.K + i * 256);
     // ---- 2. A's units
-#pragma unroll
-    for (int j = 0; j < NUWA; ++j) {
-      float4 (&wj)[4] = w[j % DEPTH];
-      float acc[B][2];
-#pragma unroll
-      for (int b = 0; b < B; ++b) acc[b][0] = acc[b][1] = 0.f;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-#pragma unroll
-        for (int b = 0; b < B; ++b) acc[b][i & 1] = dot4(wj[i], xr[b][i], acc[b][i & 1]);
-        if (j + DEPTH < NUWA) {
-          __builtin_amdgcn_sched_barrier(0);
-          wj[i] = ld_nt(WgA + (size_t)((wave + SEG_NW * (j + DEPTH)) >> SHA) * a.K + i * 256);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-      seg_park<B>(acc, partA, wave + SEG_NW * j, lane);
-    }
+    pair_stream_a<WsF32, B, NUWA, SHA>(WgA, a.K, w, xr, NoScales(), partA, wave, lane);
     __syncthreads();                                                // (1) A's partial sums are parked
-    pair_stream_b<NUWB>(p, t, lane, wave, xr, w, efinB, partB, aux, xs, kvoff);
+    pair_stream_b<WsF32, B, NUWB, 0, PAIR_PF>(p, bb.W, NoScales(), t, lane, wave, xr, w, efinB, partB, aux, xs, kvoff);
   } else {
-    pair_edge_role<SA, 0>(p, wave - SEG_NW, lane, partA, xs, kvoff);
+    pair_edge_role<B, SA, 0>(p, wave - SEG_NW, lane, partA, xs, kvoff);
   }
 }
 
@@ -856,7 +782,7 @@ __global__ __launch_bounds__(PAIR_TH, 2) void gemv_pair_kernel(const PairK p) {
 template <int NUWB, int EARLY = 0, int PFX = PAIR_PF>
 __global__ __launch_bounds__(PAIR_TH, 2) void gemv_pair_merge_kernel(const PairK p) {
   constexpr int B = 2, DEPTH = PAIR_DEPTH, SEG_CS = SegCS<B>::v;
-  constexpr int RA = 8, SA = 2, SHA = 1;                           // A: 8 rows per workgroup, K = 2048 = 2 segments, 16 units = 2 per wave
+  constexpr int RA = 8, SA = 2;                                    // A: 8 rows per workgroup, K = 2048 = 2 segments, 16 units = 2 per wave (SHA = 1)
   constexpr int RB = NUWB * SEG_NW / 2;
   extern __shared__ __attribute__((aligned(16))) float wtab[];     // [B * H][max_splits] merge weights
   __shared__ float partA[RA * SA * B];
@@ -868,7 +794,7 @@ __global__ __launch_bounds__(PAIR_TH, 2) void gemv_pair_merge_kernel(const PairK
   const ssrhip_gemv_args& bb = p.b.a;
   const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
   if (wave >= SEG_NW) {
-    pair_edge_role<SA, 2>(p, wave - SEG_NW, lane, partA, xs, kvoff);
+    pair_edge_role<B, SA, 2>(p, wave - SEG_NW, lane, partA, xs, kvoff);
   } else {
     const int K = a.K, rA0 = (int)blockIdx.x * RA, seg = wave & (SA - 1);
     const float* WgA = a.W + (size_t)rA0 * K + seg * SEG + lane * 4;
@@ -897,18 +823,7 @@ __global__ __launch_bounds__(PAIR_TH, 2) void gemv_pair_merge_kernel(const PairK
     }
     // ---- 2. the wave's two units of A, both now
     float4 w[DEPTH][4];
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) w[j][i] = ld_nt(WgA + (size_t)((wave + SEG_NW * j) >> SHA) * K + i * 256);
-    if constexpr (EARLY == 2) {
-      // B's units 0 and 1 (pair_stream_b's addresses: SB = 2 segments per row, unit u = row (wave + 8 u) / 2 of this workgroup's RB rows)
-      const float* WgB = bb.W + (size_t)((int)blockIdx.x * RB) * bb.K + (wave & 1) * SEG + lane * 4;
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) w[2 + j][i] = ld_nt(WgB + (size_t)((wave + SEG_NW * j) >> 1) * bb.K + i * 256);
-    }
+    pair_merge_request<WsF32, NUWB, EARLY>(WgA, K, bb.W, bb.K, w, wave, lane);
     // ---- 3. merge, under the latency of the units. EVERY thread computes the softmax-merge weights of (row, head) = t % (B * H), threads
     // 0 .. B * H - 1 store them: inside an `if (t < B * H)` hipcc sinks the (m, l) loads into the branch, behind the weight requests, and
     // their first use drains the whole queue (read off the ISA; in gemv_seg_kernel the same source keeps them in front)
@@ -967,7 +882,8 @@ __global__ __launch_bounds__(PAIR_TH, 2) void gemv_pair_merge_kernel(const PairK
     for (int b = 0; b < B; ++b)
 #pragma unroll
       for (int i = 0; i < 4; ++i) xr[b][i] = *reinterpret_cast<const float4*>(xs + b * K + seg * SEG + (i * 64 + lane) * 4);
-    // ---- 4. A's two units
+    // ---- 4. A's two units, written out: through pair_units (gemv_pair.h), which the bf16 and e4m3 merge kernels call here, hipcc drops one
+    // s_waitcnt lgkmcnt between the LDS reads of x and the first fmacs (profiles/pair_refactor_ab.md)
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       float acc[B][2];
@@ -986,7 +902,7 @@ __global__ __launch_bounds__(PAIR_TH, 2) void gemv_pair_merge_kernel(const PairK
       if (lane < B) partA[(wave + SEG_NW * j) * B + lane] = mine;
     }
     __syncthreads();                                                // (1) A's partial sums are parked
-    pair_stream_b<NUWB, EARLY, PFX>(p, t, lane, wave, xr, w, efinB, partB, aux, xs, kvoff);
+    pair_stream_b<WsF32, B, NUWB, EARLY, PFX>(p, bb.W, NoScales(), t, lane, wave, xr, w, efinB, partB, aux, xs, kvoff);
   }
 }
 
@@ -1077,6 +993,9 @@ extern "C" void ssrhip_debug_gemv_prof(void* dev_ptr) { g_gemv_prof = (long long
 static thread_local char g_pair_why[200] = "";
 const char* ssrhip_gemv_pair_why() { return g_pair_why; }          // why the last pair_nuwb on this thread said no (engine.hip reports it)
 
+static PairForm<PairK> g_pair_form = {{gemv_pair_kernel<4>, gemv_pair_kernel<6>, gemv_pair_kernel<8>}, gemv_pair_merge_kernel<8, 2>, gemv_pair_merge_kernel<8, 0>,
+                                      false, "pair", 16 * 1024, false, nullptr, ""};
+
 // Can a pair kernel keep 256 workgroups resident on THIS device at all? (the CU count alone ignores CU masks and occupancy.)
 // Asked once per process: the occupancy calculator must place at least one workgroup of every pair instantiation on a CU (12 waves,
 // their registers and LDS), the device must report >= 256 CUs and no CU mask may be set in the environment (the attribute counts
@@ -1092,16 +1011,7 @@ static const char* pair_device_refusal(int num_cu) {
     const char* e = getenv(name);
     if (e && e[0]) { snprintf(buf, sizeof(buf), "%s is set: fewer CUs than the device reports may be usable", name); return verdict = buf; }
   }
-  int nb[4] = {0, 0, 0, 0};
-  hipError_t e0 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb[0], gemv_pair_kernel<4>, PAIR_TH, 0);
-  hipError_t e1 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb[1], gemv_pair_kernel<6>, PAIR_TH, 0);
-  hipError_t e2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb[2], gemv_pair_kernel<8>, PAIR_TH, 0);
-  hipError_t e3 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb[3], gemv_pair_merge_kernel<8, 2>, PAIR_TH, 16 * 1024);
-  if (e0 != hipSuccess || e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || nb[0] < 1 || nb[1] < 1 || nb[2] < 1 || nb[3] < 1) {
-    snprintf(buf, sizeof(buf), "the occupancy calculator places %d / %d / %d / %d workgroups of the pair kernels on a CU (need >= 1 each)", nb[0], nb[1], nb[2], nb[3]);
-    return verdict = buf;
-  }
-  return verdict = nullptr;
+  return verdict = pair_occupancy_refusal(g_pair_form);
 }
 
 static int pair_nuwb(const ssrhip_gemv_args* a, const ssrhip_gemv_args* b, int num_cu, bool* merge) {
@@ -1144,55 +1054,26 @@ extern "C" int ssrhip_pair_buffer(int32_t i, int32_t n) {
   return (i == n - 1 && n % 3 == 1) ? 1 : i % 3;
 }
 
+int ssrhip_gemv_pair_plan(const ssrhip_gemv_args* a, const ssrhip_gemv_args* b, bool* merge) { return pair_nuwb(a, b, ssr_num_cu(), merge); }
+
 extern "C" int ssrhip_gemv_pair_applicable(const ssrhip_gemv_args* a, const ssrhip_gemv_args* b) {
   if (!a || !b) return 0;
   bool merge;
-  return pair_nuwb(a, b, ssr_num_cu(), &merge) != 0;
+  return ssrhip_gemv_pair_plan(a, b, &merge) != 0;
 }
 
 extern "C" int ssrhip_gemv_pair(const ssrhip_gemv_args* a, const ssrhip_gemv_args* b, void* ws, int32_t buf, int32_t buf_next, ssrhip_stream_t stream) {
-  SSR_REQUIRE(a && b && ws, "ssrhip_gemv_pair: null argument");
-  SSR_REQUIRE(buf >= 0 && buf < 3 && buf_next >= 0 && buf_next < 3 && buf != buf_next, "ssrhip_gemv_pair: granule buffers %d -> %d (0..2, different)", buf, buf_next);
-  SSR_REQUIRE(a->epi != SSRHIP_EPI_QKV_APPEND16 && b->epi != SSRHIP_EPI_QKV_APPEND16, "ssrhip_gemv_pair: the 2-byte KV append (EPI_QKV_APPEND16) exists for 5..32 rows only");
+  if (int rc = pair_entry_check("ssrhip_gemv_pair", a, b, ws != nullptr, buf, buf_next)) return rc;
   bool merge = false;
-  const int nuwb = pair_nuwb(a, b, ssr_num_cu(), &merge);
+  const int nuwb = ssrhip_gemv_pair_plan(a, b, &merge);
   if (!nuwb) return 1;
   PairK p;
-  seg_fill(&p.a, a, merge ? 2 : 8, 256);                            // one workgroup per CU: 8 rows of A, N / 256 rows of B
-  seg_fill(&p.b, b, 2, 256);
-  unsigned long long* gran = (unsigned long long*)ws;
-  p.gran = gran + (size_t)buf * PAIR_GRAN;
-  p.gran_next = gran + (size_t)buf_next * PAIR_GRAN;
-  p.gave_up = (int*)(gran + 3 * (size_t)PAIR_GRAN);
-  hipStream_t s = (hipStream_t)stream;
-  if (merge) {
-    const size_t sm = ((size_t)2 * (a->K / a->kv.head_dim) * a->max_splits * sizeof(float) + 15) / 16 * 16;
-    const char* ee = getenv("SSRHIP_GEMV_PAIR_EARLY");             // read at every call (graph capture): A/B inside one process
-    // 0 = round 5's order. (With the early units in place, FOUR units in flight behind (1b) measured 0.759 ms/step and TWO — nothing between
-    // the publish and the gather — 0.767 against 0.745-0.748 for three: PFX stays PAIR_PF; profiles/r06_microbench/decode_ab_pair_early_pf*.log.)
-    if (ee && ee[0] == '0') hipLaunchKernelGGL((gemv_pair_merge_kernel<8, 0>), dim3(256), dim3(PAIR_TH), sm, s, p);
-    else hipLaunchKernelGGL((gemv_pair_merge_kernel<8, 2>), dim3(256), dim3(PAIR_TH), sm, s, p);
-  } else if (nuwb == 4) hipLaunchKernelGGL((gemv_pair_kernel<4>), dim3(256), dim3(PAIR_TH), 0, s, p);
-  else if (nuwb == 6) hipLaunchKernelGGL((gemv_pair_kernel<6>), dim3(256), dim3(PAIR_TH), 0, s, p);
-  else hipLaunchKernelGGL((gemv_pair_kernel<8>), dim3(256), dim3(PAIR_TH), 0, s, p);
-  SSR_LAUNCH_CHECK();
-  return 0;
+  pair_fill(p, a, b, merge, ws, buf, buf_next, PAIR_GRAN);
+  return pair_launch(g_pair_form, p, merge, nuwb, 2, a, (hipStream_t)stream);
 }
 
 extern "C" int ssrhip_gemv_pair_status(const void* ws, ssrhip_stream_t stream) {
-  SSR_REQUIRE(ws, "ssrhip_gemv_pair_status: null workspace");
-  int flag = 0;
-  if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) { ssrhip_set_error("ssrhip_gemv_pair_status: stream synchronize failed"); return -1; }
-  if (hipMemcpy(&flag, (const char*)ws + 3 * (size_t)PAIR_GRAN * 8, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) {
-    ssrhip_set_error("ssrhip_gemv_pair_status: copy failed");
-    return -1;
-  }
-  if (flag) {
-    // reported once; tags and flag back to "nothing published" so that a chain restarted from its first launch (after a new prefill) is
-    // valid again (the stream is idle: it was synchronised above)
-    if (hipMemset(const_cast<void*>(ws), 0, SSRHIP_PAIR_WS_BYTES) != hipSuccess) { ssrhip_set_error("ssrhip_gemv_pair_status: re-zeroing the workspace failed"); return -1; }
-  }
-  return flag ? 1 : 0;
+  return pair_status(ws, SSRHIP_PAIR_WS_BYTES, 3 * (size_t)PAIR_GRAN * 8, "ssrhip_gemv_pair_status", stream);
 }
 
 extern "C" int ssrhip_gemv(const ssrhip_gemv_args* a, ssrhip_stream_t stream) {

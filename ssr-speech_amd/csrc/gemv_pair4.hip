@@ -3,7 +3,7 @@
 // gemv.hip's pair launches (gemv_pair_kernel / gemv_pair_merge_kernel: TWO consecutive GEMVs of the step in ONE launch, the all-to-all edge
 // between them inside the launch) at four batch rows. Same structure: 256 workgroups, one per CU, 8 streaming waves + 4 edge waves, the two
 // roles the two arms of ONE wave-uniform branch with every barrier written in both arms; the hand-off is gemv_pair.h's protocol with
-// 8192 granules per buffer (gemv_pair4.h). Two forms:
+// 8192 granules per buffer (pair_edge_role<4, SA, NPRE>), the streaming phases are gemv_pair.h's with the WsF32 policy. Two forms:
 //   * pair4_kernel<NUWB>:        A = FFN2 + residual (K = 8192, N = 2048), B = folded LayerNorm + Linear, N in {4096, 6144, 8192}
 //                                (head-MLP1 with GELU, QKV with the K / V append, FFN1 with ReLU);
 //   * pair4_merge_kernel<NUWB>:  A = split-KV merge prologue + out-projection + residual (K = 2048), B = FFN1.
@@ -17,62 +17,13 @@
 #include <stdlib.h>
 #include "common.h"
 #include "gemv_shared.h"
-#include "gemv_pair4.h"
+#include "gemv_pair_host.h"
 
 namespace {
 
 constexpr int PAIR4_DEPTH = 4;   // units in the ring of a streaming wave
+static_assert(PAIR4_DEPTH == PAIR_DEPTH, "gemv_pair.h's streaming phases are written for a ring of PAIR_DEPTH units");
 constexpr int PAIR4_PF = 3;      // of B's first units, those posted behind barrier (1b), in front of the gather's loads (gemv.hip: PAIR_PF)
-
-// ---- the streaming role from barrier (1) on: B = LayerNorm + Linear on x' (gemv_seg_kernel<4, PRO_LAYERNORM, false>, operation for operation)
-template <int NUWB>
-__device__ __forceinline__ void pair4_stream_b(const PairK& p, int t, int lane, int wave, float4 (&xr)[PAIR4_B][4], float4 (&w)[PAIR4_DEPTH][4],
-                                               const RowEpi& efinB, float* partB, float* aux, const float* xs, const size_t* kvoff) {
-  constexpr int B = PAIR4_B, DEPTH = PAIR4_DEPTH, PF = (PAIR4_PF < NUWB ? PAIR4_PF : NUWB), SB = 2, SHB = 1, RB = NUWB * SEG_NW / SB;
-  static_assert(DEPTH <= NUWB, "units in flight");
-  const ssrhip_gemv_args& bb = p.b.a;
-  const int rB0 = (int)blockIdx.x * RB, segB = wave & (SB - 1);
-  const int bfin = t % B, rfinB = min(t / B, RB - 1), nfinB = rB0 + rfinB;
-  const float* WgB = bb.W + (size_t)rB0 * bb.K + segB * SEG + lane * 4;
-  __syncthreads();                                                  // (1b) wave 8 has issued the publish
-  // B's first units: PF of them now, the rest behind the gather
-#pragma unroll
-  for (int j = 0; j < PF; ++j)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) w[j % DEPTH][i] = ld_nt(WgB + (size_t)((wave + SEG_NW * j) >> SHB) * bb.K + i * 256);
-  __syncthreads();                                                  // (2) x' is in LDS
-  seg_load_x<B>(xr, xs, PAIR_D, segB, lane);
-#pragma unroll
-  for (int j = PF; j < DEPTH; ++j)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) w[j % DEPTH][i] = ld_nt(WgB + (size_t)((wave + SEG_NW * j) >> SHB) * bb.K + i * 256);
-  seg_layernorm<B>(xr, aux, SB, bb.K, bb.ln_eps, wave, lane);       // its barrier is (3)
-  // units
-#pragma unroll
-  for (int j = 0; j < NUWB; ++j) {
-    float4 (&wj)[4] = w[j % DEPTH];
-    float acc[B][2];
-#pragma unroll
-    for (int b = 0; b < B; ++b) acc[b][0] = acc[b][1] = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-#pragma unroll
-      for (int b = 0; b < B; ++b) acc[b][i & 1] = dot4(wj[i], xr[b][i], acc[b][i & 1]);
-      if (j + DEPTH < NUWB) {
-        __builtin_amdgcn_sched_barrier(0);
-        wj[i] = ld_nt(WgB + (size_t)((wave + SEG_NW * (j + DEPTH)) >> SHB) * bb.K + i * 256);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    seg_park<B>(acc, partB, wave + SEG_NW * j, lane);
-  }
-  __syncthreads();                                                  // (4)
-  if (t < RB * B) {
-    // K / V append addresses: resolved by the edge role (wave 9) while this role streamed
-    float* kvb[2] = {bb.kv.pool + kvoff[bfin * 2], bb.kv.pool + kvoff[bfin * 2 + 1]};
-    seg_finish_row<B>(p.b, 0, partB, SB, rfinB, nfinB, bfin, efinB, kvb);
-  }
-}
 
 // A = FFN2 + residual (K = 8192): 8 rows per workgroup, wave w owns segment w of every row (unit j = row j), as gemv_seg_kernel<4, PRO_NONE,
 // false> orders a row's units
@@ -102,33 +53,12 @@ __global__ __launch_bounds__(PAIR_TH) void pair4_kernel(const PairK p) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) xr[b][i] = ld4(a.x + (size_t)b * a.x_stride + wave * SEG + (i * 64 + lane) * 4);
     float4 w[DEPTH][4];
-#pragma unroll
-    for (int j = 0; j < DEPTH; ++j)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) w[j][i] = ld_nt(WgA + (size_t)((wave + SEG_NW * j) >> SHA) * a.K + i * 256);
     // ---- 2. A's units
-#pragma unroll
-    for (int j = 0; j < NUWA; ++j) {
-      float4 (&wj)[4] = w[j % DEPTH];
-      float acc[B][2];
-#pragma unroll
-      for (int b = 0; b < B; ++b) acc[b][0] = acc[b][1] = 0.f;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-#pragma unroll
-        for (int b = 0; b < B; ++b) acc[b][i & 1] = dot4(wj[i], xr[b][i], acc[b][i & 1]);
-        if (j + DEPTH < NUWA) {
-          __builtin_amdgcn_sched_barrier(0);
-          wj[i] = ld_nt(WgA + (size_t)((wave + SEG_NW * (j + DEPTH)) >> SHA) * a.K + i * 256);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-      seg_park<B>(acc, partA, wave + SEG_NW * j, lane);
-    }
+    pair_stream_a<WsF32, B, NUWA, SHA>(WgA, a.K, w, xr, NoScales(), partA, wave, lane);
     __syncthreads();                                                // (1) A's partial sums are parked
-    pair4_stream_b<NUWB>(p, t, lane, wave, xr, w, efinB, partB, aux, xs, kvoff);
+    pair_stream_b<WsF32, B, NUWB, 0, PAIR4_PF>(p, bb.W, NoScales(), t, lane, wave, xr, w, efinB, partB, aux, xs, kvoff);
   } else {
-    pair4_edge_role<SA, 0>(p, wave - SEG_NW, lane, partA, xs, kvoff);
+    pair_edge_role<B, SA, 0>(p, wave - SEG_NW, lane, partA, xs, kvoff);
   }
 }
 
@@ -139,7 +69,7 @@ __global__ __launch_bounds__(PAIR_TH) void pair4_kernel(const PairK p) {
 template <int NUWB>
 __global__ __launch_bounds__(PAIR_TH) void pair4_merge_kernel(const PairK p) {
   constexpr int B = PAIR4_B, DEPTH = PAIR4_DEPTH, SEG_CS = SegCS<B>::v;
-  constexpr int RA = 8, SA = 2, SHA = 1;                           // A: 8 rows per workgroup, K = 2048 = 2 segments, 16 units = 2 per wave
+  constexpr int RA = 8, SA = 2;                                    // A: 8 rows per workgroup, K = 2048 = 2 segments, 16 units = 2 per wave (SHA = 1)
   constexpr int RB = NUWB * SEG_NW / 2;
   extern __shared__ __attribute__((aligned(16))) float wtab[];     // [B * H][max_splits] merge weights
   __shared__ float partA[RA * SA * B];
@@ -151,7 +81,7 @@ __global__ __launch_bounds__(PAIR_TH) void pair4_merge_kernel(const PairK p) {
   const ssrhip_gemv_args& bb = p.b.a;
   const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
   if (wave >= SEG_NW) {
-    pair4_edge_role<SA, 2>(p, wave - SEG_NW, lane, partA, xs, kvoff);
+    pair_edge_role<B, SA, 2>(p, wave - SEG_NW, lane, partA, xs, kvoff);
   } else {
     const int K = a.K, rA0 = (int)blockIdx.x * RA, seg = wave & (SA - 1);
     const float* WgA = a.W + (size_t)rA0 * K + seg * SEG + lane * 4;
@@ -180,10 +110,7 @@ __global__ __launch_bounds__(PAIR_TH) void pair4_merge_kernel(const PairK p) {
     }
     // ---- 2. the wave's two units of A, both now
     float4 w[DEPTH][4];
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) w[j][i] = ld_nt(WgA + (size_t)((wave + SEG_NW * j) >> SHA) * K + i * 256);
+    pair_merge_request<WsF32, NUWB, 0>(WgA, K, bb.W, bb.K, w, wave, lane);
     // ---- 3. merge, under the latency of the units. EVERY thread computes the softmax-merge weights of (row, head) = t % (B * H), threads
     // 0 .. B * H - 1 store them (gemv_pair_merge_kernel explains why)
     {
@@ -241,7 +168,8 @@ __global__ __launch_bounds__(PAIR_TH) void pair4_merge_kernel(const PairK p) {
     __syncthreads();                                                // (A2)
     float4 xr[B][4];
     seg_load_x<B>(xr, xs, K, seg, lane);
-    // ---- 4. A's two units
+    // ---- 4. A's two units, written out: through pair_units (gemv_pair.h) hipcc swaps an LDS read of x' with a weight request behind
+    // barrier (2) and adds two waits (profiles/pair_refactor_ab.md)
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       float acc[B][2];
@@ -254,50 +182,32 @@ __global__ __launch_bounds__(PAIR_TH) void pair4_merge_kernel(const PairK p) {
       seg_park<B>(acc, partA, wave + SEG_NW * j, lane);
     }
     __syncthreads();                                                // (1) A's partial sums are parked
-    pair4_stream_b<NUWB>(p, t, lane, wave, xr, w, efinB, partB, aux, xs, kvoff);
+    pair_stream_b<WsF32, B, NUWB, 0, PAIR4_PF>(p, bb.W, NoScales(), t, lane, wave, xr, w, efinB, partB, aux, xs, kvoff);
   }
 }
 
 constexpr size_t PAIR4_WTAB_MAX = 16 * 1024;   // merge weights in dynamic LDS, next to ~34 KB of static buffers
 
 thread_local char g_pair4_why[200] = "";
-
-// Can a CU take a workgroup of every 4-row instantiation (12 waves, their registers and 33-50 KB of LDS)? Asked once per process, as
-// gemv.hip's pair_device_refusal does for the 2-row forms (CU count and CU masks are its part: ssrhip_gemv_pair_applicable asks them first).
-const char* pair4_device_refusal() {
-  static const char* verdict = nullptr;
-  static bool asked = false;
-  if (asked) return verdict;
-  asked = true;
-  static char buf[200];
-  int nb[4] = {0, 0, 0, 0};
-  hipError_t e0 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb[0], pair4_kernel<4>, PAIR_TH, 0);
-  hipError_t e1 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb[1], pair4_kernel<6>, PAIR_TH, 0);
-  hipError_t e2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb[2], pair4_kernel<8>, PAIR_TH, 0);
-  hipError_t e3 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb[3], pair4_merge_kernel<8>, PAIR_TH, PAIR4_WTAB_MAX);
-  if (e0 != hipSuccess || e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || nb[0] < 1 || nb[1] < 1 || nb[2] < 1 || nb[3] < 1) {
-    snprintf(buf, sizeof(buf), "the occupancy calculator places %d / %d / %d / %d workgroups of the 4-row pair kernels on a CU (need >= 1 each)", nb[0], nb[1], nb[2], nb[3]);
-    return verdict = buf;
-  }
-  return verdict = nullptr;
-}
+PairForm<PairK> g_pair4_form = {{pair4_kernel<4>, pair4_kernel<6>, pair4_kernel<8>}, pair4_merge_kernel<8>, nullptr, false, "4-row pair", PAIR4_WTAB_MAX, false, nullptr, ""};
 
 // ssrhip_gemv_pair_applicable's rules with B == 4: the 2-row question is put with the row count set to 2 (shapes, >= 256 CUs, no CU mask,
-// SSRHIP_GEMV_PAIR = 0 / 1 / 2), then what four rows change — the merge's (row, head) table and its LDS — and the occupancy of the new kernels
-bool pair4_qualifies(const ssrhip_gemv_args* a, const ssrhip_gemv_args* b) {
-  auto no = [](const char* why) { snprintf(g_pair4_why, sizeof(g_pair4_why), "%s", why); return false; };
-  if (a->B != PAIR4_B || b->B != PAIR4_B) return no("not a 4-row launch (the 4-row pair kernels take B = 4 only)");
+// SSRHIP_GEMV_PAIR = 0 / 1 / 2), then what four rows change — the merge's (row, head) table and its LDS — and the occupancy of the 4-row
+// kernels (33-50 KB of LDS). Units per wave of B, or 0 with the reason in g_pair4_why.
+int pair4_plan(const ssrhip_gemv_args* a, const ssrhip_gemv_args* b, bool* merge) {
+  if (a->B != PAIR4_B || b->B != PAIR4_B) return pair_refuse(g_pair4_why, "not a 4-row launch (the 4-row pair kernels take B = 4 only)");
   ssrhip_gemv_args a2 = *a, b2 = *b;
   a2.B = b2.B = 2;
-  if (!ssrhip_gemv_pair_applicable(&a2, &b2)) return no(ssrhip_gemv_pair_why());
-  if (a->pro == SSRHIP_PRO_ATTN_COMBINE) {
+  const int nuwb = ssrhip_gemv_pair_plan(&a2, &b2, merge);
+  if (!nuwb) return pair_refuse(g_pair4_why, ssrhip_gemv_pair_why());
+  if (*merge) {
     const int H = a->K / a->kv.head_dim;
-    if (PAIR4_B * H > SEG_TH) return no("merge form: more than 512 (row, head) pairs");
-    if ((size_t)PAIR4_B * H * a->max_splits * sizeof(float) > PAIR4_WTAB_MAX) return no("merge weights exceed 16 KB of LDS (context too long for the 4-row merge form)");
+    if (PAIR4_B * H > SEG_TH) return pair_refuse(g_pair4_why, "merge form: more than 512 (row, head) pairs");
+    if ((size_t)PAIR4_B * H * a->max_splits * sizeof(float) > PAIR4_WTAB_MAX) return pair_refuse(g_pair4_why, "merge weights exceed 16 KB of LDS (context too long for the 4-row merge form)");
   }
-  if (const char* why = pair4_device_refusal()) return no(why);
+  if (const char* why = pair_occupancy_refusal(g_pair4_form)) return pair_refuse(g_pair4_why, why);
   g_pair4_why[0] = 0;
-  return true;
+  return nuwb;
 }
 
 }  // namespace
@@ -306,44 +216,20 @@ const char* ssrhip_gemv_pair4_why() { return g_pair4_why; }   // why the last qu
 
 extern "C" int ssrhip_gemv_pair4_applicable(const ssrhip_gemv_args* a, const ssrhip_gemv_args* b) {
   if (!a || !b) return 0;
-  return pair4_qualifies(a, b) ? 1 : 0;
+  bool merge;
+  return pair4_plan(a, b, &merge) ? 1 : 0;
 }
 
 extern "C" int ssrhip_gemv_pair4(const ssrhip_gemv_args* a, const ssrhip_gemv_args* b, void* ws, int32_t buf, int32_t buf_next, ssrhip_stream_t stream) {
-  SSR_REQUIRE(a && b && ws, "ssrhip_gemv_pair4: null argument");
-  SSR_REQUIRE(buf >= 0 && buf < 3 && buf_next >= 0 && buf_next < 3 && buf != buf_next, "ssrhip_gemv_pair4: granule buffers %d -> %d (0..2, different)", buf, buf_next);
-  SSR_REQUIRE(a->epi != SSRHIP_EPI_QKV_APPEND16 && b->epi != SSRHIP_EPI_QKV_APPEND16, "ssrhip_gemv_pair4: the 2-byte KV append (EPI_QKV_APPEND16) exists for 5..32 rows only");
-  if (!pair4_qualifies(a, b)) return 1;
-  const bool merge = a->pro == SSRHIP_PRO_ATTN_COMBINE;
-  const int nuwb = (b->N / 256) * 2 / SEG_NW;
+  if (int rc = pair_entry_check("ssrhip_gemv_pair4", a, b, ws != nullptr, buf, buf_next)) return rc;
+  bool merge = false;
+  const int nuwb = pair4_plan(a, b, &merge);
+  if (!nuwb) return 1;
   PairK p;
-  seg_fill(&p.a, a, merge ? 2 : 8, 256);                            // one workgroup per CU: 8 rows of A, N / 256 rows of B
-  seg_fill(&p.b, b, 2, 256);
-  unsigned long long* gran = (unsigned long long*)ws;
-  p.gran = gran + (size_t)buf * PAIR4_GRAN;
-  p.gran_next = gran + (size_t)buf_next * PAIR4_GRAN;
-  p.gave_up = (int*)(gran + 3 * (size_t)PAIR4_GRAN);
-  hipStream_t s = (hipStream_t)stream;
-  if (merge) {
-    const size_t sm = ((size_t)PAIR4_B * (a->K / a->kv.head_dim) * a->max_splits * sizeof(float) + 15) / 16 * 16;
-    hipLaunchKernelGGL((pair4_merge_kernel<8>), dim3(256), dim3(PAIR_TH), sm, s, p);
-  } else if (nuwb == 4) hipLaunchKernelGGL((pair4_kernel<4>), dim3(256), dim3(PAIR_TH), 0, s, p);
-  else if (nuwb == 6) hipLaunchKernelGGL((pair4_kernel<6>), dim3(256), dim3(PAIR_TH), 0, s, p);
-  else hipLaunchKernelGGL((pair4_kernel<8>), dim3(256), dim3(PAIR_TH), 0, s, p);
-  SSR_LAUNCH_CHECK();
-  return 0;
+  pair_fill(p, a, b, merge, ws, buf, buf_next, PAIR4_GRAN);
+  return pair_launch(g_pair4_form, p, merge, nuwb, PAIR4_B, a, (hipStream_t)stream);
 }
 
-extern "C" int ssrhip_gemv_pair4_status(const void* ws, ssrhip_stream_t stream) {
-  SSR_REQUIRE(ws, "ssrhip_gemv_pair4_status: null workspace");
-  int flag = 0;
-  if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) { ssrhip_set_error("ssrhip_gemv_pair4_status: stream synchronize failed"); return -1; }
-  if (hipMemcpy(&flag, (const char*)ws + 3 * (size_t)PAIR4_GRAN * 8, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) {
-    ssrhip_set_error("ssrhip_gemv_pair4_status: copy failed");
-    return -1;
-  }
-  if (flag) {   // reported once; tags and flag back to "nothing published" (ssrhip_gemv_pair_status, at this workspace's size)
-    if (hipMemset(const_cast<void*>(ws), 0, SSRHIP_PAIR4_WS_BYTES) != hipSuccess) { ssrhip_set_error("ssrhip_gemv_pair4_status: re-zeroing the workspace failed"); return -1; }
-  }
-  return flag ? 1 : 0;
+extern "C" int ssrhip_gemv_pair4_status(const void* ws, ssrhip_stream_t stream) {   // ssrhip_gemv_pair_status at this workspace's size
+  return pair_status(ws, SSRHIP_PAIR4_WS_BYTES, 3 * (size_t)PAIR4_GRAN * 8, "ssrhip_gemv_pair4_status", stream);
 }

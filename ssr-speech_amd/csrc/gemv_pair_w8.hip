@@ -7,7 +7,7 @@
 // granule protocol, workspace and buffer cycle. Only the bytes waves 0-7 stream change, how they are widened (v_cvt_pk_f32_fp8, exact) and
 // one multiply where a partial sum is parked:
 //   w8_pair_kernel<NUWB>           A = FFN2 (K = 8192), the streaming of w8_segu_kernel<2, PRO_NONE, 8, 4>;
-//                                  B = QKV / head-MLP1 / FFN1, pair_stream_b's sequence with w8_segu_kernel<2, PRO_LAYERNORM, NUWB, 4>'s arithmetic
+//                                  B = QKV / head-MLP1 / FFN1, pair_stream_b<WsE4, ..>: w8_segu_kernel<2, PRO_LAYERNORM, NUWB, 4>'s arithmetic
 //   w8_pair_merge_kernel<8, EARLY> A = split-KV merge + out-projection (K = 2048), w8_seg_kernel<2, PRO_ATTN_COMBINE> at one workgroup
 //                                  per CU; B = FFN1; EARLY = 2: B's first two units requested at entry into the ring slots A leaves free
 // Each phase runs the fmaf / wave_sum sequence of the w8 kernel it mirrors and multiplies the (row, segment) partial sum by the row's
@@ -24,12 +24,15 @@
 // Units in flight are the fp32 / bf16 forms' COUNTS — ring 4, PF 3, EARLY 2 — at a quarter / half the bytes each: one 16-byte load per
 // unit and lane. -DSSR_W8_PAIR_PF=4 builds the lab form with all four units behind barrier (1b); it is not shipped and not measured.
 //
-// The edge role (pair_edge_role<SA, NPRE>), the sweep, PairK, the PAIR_* constants and the time-bounded spin are gemv.hip's own, shared
-// through csrc/gemv_pair.h: they are weight-agnostic.
+// This file holds what is specific to the e4m3 stream: the kernels' entry text with the scale requests, the kernel argument with codes and
+// scales and the form's table, "why" text and applicability question. Everything else is shared: the edge role (pair_edge_role<B, SA,
+// NPRE>), the sweep, PairK, the PAIR_* constants and the streaming phases (pair_stream_a, pair_merge_request, pair_units, pair_stream_b) in
+// csrc/gemv_pair.h, instantiated here with the WsE4 policy of csrc/gemv_wstream.h (its load_scales / fence are the scales-at-entry hook),
+// which also holds gemv_w8.hip's widening; the host side in csrc/gemv_pair_host.h (profiles/pair_refactor_ab.md).
 #include <stdlib.h>
 #include "common.h"
 #include "gemv_shared.h"
-#include "gemv_pair.h"
+#include "gemv_pair_host.h"
 
 namespace {
 
@@ -38,40 +41,6 @@ namespace {
 #endif
 constexpr int W8_PAIR_PF = SSR_W8_PAIR_PF;   // units posted behind barrier (1b); the lab macro overrides the fp32 forms' count
 
-// ---- gemv_w8.hip's widening once more (it lives in that file's anonymous namespace, and that file stays as it is)
-typedef unsigned w8_v4u __attribute__((ext_vector_type(4)));
-typedef float w8_v2f __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ w8_v4u ld16_nt(const uint8_t* p) { return __builtin_nontemporal_load(reinterpret_cast<const w8_v4u*>(p)); }
-// the float4 of one dword: code m sits in byte m
-__device__ __forceinline__ float4 w8_wide(const unsigned d) {
-  const w8_v2f lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)d, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)d, true);
-  return make_float4(lo.x, lo.y, hi.x, hi.y);
-}
-// one unit against the lane's x: gemv_seg_kernel's `acc[b][i & 1] = dot4(w[i], xr[b][i], acc[b][i & 1])` for i = 0..3
-template <int B>
-__device__ __forceinline__ void w8_unit(const w8_v4u u, const float4 (&xr)[B][4], float (&acc)[B][2]) {
-  const float4 w0 = w8_wide(u.x), w1 = w8_wide(u.y), w2 = w8_wide(u.z), w3 = w8_wide(u.w);
-#pragma unroll
-  for (int b = 0; b < B; ++b) acc[b][0] = dot4(w0, xr[b][0], acc[b][0]);
-#pragma unroll
-  for (int b = 0; b < B; ++b) acc[b][1] = dot4(w1, xr[b][1], acc[b][1]);
-#pragma unroll
-  for (int b = 0; b < B; ++b) acc[b][0] = dot4(w2, xr[b][2], acc[b][0]);
-#pragma unroll
-  for (int b = 0; b < B; ++b) acc[b][1] = dot4(w3, xr[b][3], acc[b][1]);
-}
-// one unit done: seg_park with the row's scale applied to the partial sum that is parked (u = local_row * S + seg)
-template <int B>
-__device__ __forceinline__ void w8_park(const float (&acc)[B][2], float sc, float* part, int u, int lane) {
-  float mine = 0.f;
-#pragma unroll
-  for (int b = 0; b < B; ++b) {
-    const float sum = wave_sum(acc[b][0] + acc[b][1]);
-    if (lane == b) mine = sum;
-  }
-  if (lane < B) part[lane + u * B] = mine * sc;
-}
-
 struct W8PairK {
   PairK k;
   const uint8_t* Wa8;     // A's codes [2048][K_A] in SSRHIP_W8_INDEX order
@@ -79,61 +48,6 @@ struct W8PairK {
   const uint8_t* Wb8;     // B's codes [N_B][2048]
   const float* sb;        // B's scales [N_B]
 };
-
-// the NUWB scales of this wave's units of B: unit j works on row (wave + 8 j) / 2 of the workgroup's RB rows (SB = 2 segments per row)
-template <int NUWB>
-__device__ __forceinline__ void w8_pair_scales_b(const W8PairK& q, int wave, float (&scB)[NUWB]) {
-  constexpr int RB = NUWB * SEG_NW / 2;
-  const float* Sg = q.sb + (size_t)((int)blockIdx.x * RB);
-#pragma unroll
-  for (int j = 0; j < NUWB; ++j) scB[j] = Sg[(wave + SEG_NW * j) >> 1];
-}
-
-// ---- the streaming role from barrier (1) on: pair_stream_b's sequence over packed codes — B = LayerNorm + Linear on x'
-// (w8_segu_kernel<2, PRO_LAYERNORM, NUWB, 4>'s arithmetic). EARLY / PFX as in gemv.hip: unit j lives in w[(j + EARLY) % DEPTH].
-template <int NUWB, int EARLY = 0, int PFX = W8_PAIR_PF>
-__device__ __forceinline__ void w8_pair_stream_b(const W8PairK& q, int t, int lane, int wave, float4 (&xr)[2][4], w8_v4u (&w)[PAIR_DEPTH],
-                                                 const float (&scB)[NUWB], const RowEpi& efinB, float* partB, float* aux, const float* xs,
-                                                 const size_t* kvoff) {
-  constexpr int B = 2, DEPTH = PAIR_DEPTH, PF = PFX, SB = 2, SHB = 1, RB = NUWB * SEG_NW / SB;
-  static_assert(PFX >= EARLY && PFX <= PAIR_DEPTH, "units requested at (1b) start behind the early ones and fit the ring");
-  static_assert(EARLY == 0 || EARLY == 2, "ring slots 2 and 3 are the ones the merge form's A phase leaves free");
-  const PairK& p = q.k;
-  const ssrhip_gemv_args& bb = p.b.a;
-  const int rB0 = (int)blockIdx.x * RB, segB = wave & (SB - 1);
-  const int bfin = t % B, rfinB = min(t / B, RB - 1), nfinB = rB0 + rfinB;
-  const uint8_t* WgB = q.Wb8 + (size_t)rB0 * bb.K + segB * SEG + lane * 16;
-  __syncthreads();                                                  // (1b) wave 8 has issued the publish
-  // B's first units: PF of them now, the rest behind the gather
-#pragma unroll
-  for (int j = EARLY; j < PF; ++j) w[(j + EARLY) % DEPTH] = ld16_nt(WgB + (size_t)((wave + SEG_NW * j) >> SHB) * bb.K);
-  __syncthreads();                                                  // (2) x' is in LDS
-  seg_load_x<B>(xr, xs, PAIR_D, segB, lane);
-#pragma unroll
-  for (int j = PF; j < DEPTH; ++j) w[(j + EARLY) % DEPTH] = ld16_nt(WgB + (size_t)((wave + SEG_NW * j) >> SHB) * bb.K);
-  seg_layernorm<B>(xr, aux, SB, bb.K, bb.ln_eps, wave, lane);       // its barrier is (3)
-  // units
-#pragma unroll
-  for (int j = 0; j < NUWB; ++j) {
-    w8_v4u& wj = w[(j + EARLY) % DEPTH];
-    float acc[B][2];
-#pragma unroll
-    for (int b = 0; b < B; ++b) acc[b][0] = acc[b][1] = 0.f;
-    w8_unit<B>(wj, xr, acc);
-    if (j + DEPTH < NUWB) {
-      __builtin_amdgcn_sched_barrier(0);                            // use, THEN overwrite in place
-      wj = ld16_nt(WgB + (size_t)((wave + SEG_NW * (j + DEPTH)) >> SHB) * bb.K);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    w8_park<B>(acc, scB[j], partB, wave + SEG_NW * j, lane);
-  }
-  __syncthreads();                                                  // (4)
-  if (t < RB * B) {
-    // K / V append addresses: resolved by the edge role (wave 9) while this role streamed
-    float* kvb[2] = {bb.kv.pool + kvoff[bfin * 2], bb.kv.pool + kvoff[bfin * 2 + 1]};
-    seg_finish_row<B>(p.b, 0, partB, SB, rfinB, nfinB, bfin, efinB, kvb);
-  }
-}
 
 // The two ROLES are the two arms of ONE (wave-uniform) branch and every barrier is written in both arms (gemv.hip says what the other
 // form cost). A = FFN2 + residual (K = 8192): w8_segu_kernel<2, PRO_NONE, 8, 4> — 8 units per wave, a ring of 4, one 16-byte load per unit.
@@ -161,32 +75,16 @@ __global__ __launch_bounds__(PAIR_TH, 2) void w8_pair_kernel(const W8PairK q) {
     float4 xr[B][4];
     seg_load_x<B>(xr, a.x, (size_t)a.x_stride, wave, lane);
     float scA[NUWA], scB[NUWB];
-#pragma unroll
-    for (int j = 0; j < NUWA; ++j) scA[j] = q.sa[rA0 + ((wave + SEG_NW * j) >> SHA)];
-    w8_pair_scales_b<NUWB>(q, wave, scB);
-    __builtin_amdgcn_sched_barrier(0);                              // the scales are requested BEFORE any code: the scheduler must not swap them
+    WsE4::load_scales<NUWA, SHA>(scA, q.sa, rA0, wave);
+    WsE4::load_scales<NUWB, 1>(scB, q.sb + (size_t)((int)blockIdx.x * RB), 0, wave);
+    WsE4::fence();                                                  // the scales are requested BEFORE any code: the scheduler must not swap them
     w8_v4u w[DEPTH];
-#pragma unroll
-    for (int j = 0; j < DEPTH; ++j) w[j] = ld16_nt(WgA + (size_t)((wave + SEG_NW * j) >> SHA) * a.K);
     // ---- 2. A's units
-#pragma unroll
-    for (int j = 0; j < NUWA; ++j) {
-      w8_v4u& wj = w[j % DEPTH];
-      float acc[B][2];
-#pragma unroll
-      for (int b = 0; b < B; ++b) acc[b][0] = acc[b][1] = 0.f;
-      w8_unit<B>(wj, xr, acc);
-      if (j + DEPTH < NUWA) {
-        __builtin_amdgcn_sched_barrier(0);
-        wj = ld16_nt(WgA + (size_t)((wave + SEG_NW * (j + DEPTH)) >> SHA) * a.K);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      w8_park<B>(acc, scA[j], partA, wave + SEG_NW * j, lane);
-    }
+    pair_stream_a<WsE4, B, NUWA, SHA>(WgA, a.K, w, xr, scA, partA, wave, lane);
     __syncthreads();                                                // (1) A's scaled partial sums are parked
-    w8_pair_stream_b<NUWB>(q, t, lane, wave, xr, w, scB, efinB, partB, aux, xs, kvoff);
+    pair_stream_b<WsE4, B, NUWB, 0, W8_PAIR_PF>(p, q.Wb8, scB, t, lane, wave, xr, w, efinB, partB, aux, xs, kvoff);
   } else {
-    pair_edge_role<SA, 0>(p, wave - SEG_NW, lane, partA, xs, kvoff);
+    pair_edge_role<B, SA, 0>(p, wave - SEG_NW, lane, partA, xs, kvoff);
   }
 }
 
@@ -210,7 +108,7 @@ __global__ __launch_bounds__(PAIR_TH, 2) void w8_pair_merge_kernel(const W8PairK
   const ssrhip_gemv_args& bb = p.b.a;
   const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
   if (wave >= SEG_NW) {
-    pair_edge_role<SA, 2>(p, wave - SEG_NW, lane, partA, xs, kvoff);
+    pair_edge_role<B, SA, 2>(p, wave - SEG_NW, lane, partA, xs, kvoff);
   } else {
     const int K = a.K, rA0 = (int)blockIdx.x * RA, seg = wave & (SA - 1);
     const uint8_t* WgA = q.Wa8 + (size_t)rA0 * K + seg * SEG + lane * 16;
@@ -238,19 +136,11 @@ __global__ __launch_bounds__(PAIR_TH, 2) void w8_pair_merge_kernel(const W8PairK
     }
     // ---- 2. every scale the wave will need (A's two rows, then B's NUWB), then the wave's two units of A, both now
     float scA[2], scB[NUWB];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) scA[j] = q.sa[rA0 + ((wave + SEG_NW * j) >> SHA)];
-    w8_pair_scales_b<NUWB>(q, wave, scB);
-    __builtin_amdgcn_sched_barrier(0);                              // the scales are requested BEFORE any code: the scheduler must not swap them
+    WsE4::load_scales<2, SHA>(scA, q.sa, rA0, wave);
+    WsE4::load_scales<NUWB, 1>(scB, q.sb + (size_t)((int)blockIdx.x * RB), 0, wave);
+    WsE4::fence();                                                  // the scales are requested BEFORE any code: the scheduler must not swap them
     w8_v4u w[DEPTH];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) w[j] = ld16_nt(WgA + (size_t)((wave + SEG_NW * j) >> SHA) * K);
-    if constexpr (EARLY == 2) {
-      // B's units 0 and 1 (w8_pair_stream_b's addresses: SB = 2 segments per row, unit u = row (wave + 8 u) / 2 of this workgroup's RB rows)
-      const uint8_t* WgB = q.Wb8 + (size_t)((int)blockIdx.x * RB) * bb.K + (wave & 1) * SEG + lane * 16;
-#pragma unroll
-      for (int j = 0; j < 2; ++j) w[2 + j] = ld16_nt(WgB + (size_t)((wave + SEG_NW * j) >> 1) * bb.K);
-    }
+    pair_merge_request<WsE4, NUWB, EARLY>(WgA, K, q.Wb8, bb.K, w, wave, lane);
     // ---- 3. merge, under the latency of the units
     {
       const int tt = t % (B * H);
@@ -305,51 +195,20 @@ __global__ __launch_bounds__(PAIR_TH, 2) void w8_pair_merge_kernel(const W8PairK
     float4 xr[B][4];
     seg_load_x<B>(xr, xs, K, seg, lane);
     // ---- 4. A's two units
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      float acc[B][2];
-#pragma unroll
-      for (int b = 0; b < B; ++b) acc[b][0] = acc[b][1] = 0.f;
-      w8_unit<B>(w[j], xr, acc);
-      w8_park<B>(acc, scA[j], partA, wave + SEG_NW * j, lane);
-    }
+    pair_units<WsE4, B, 2, SHA, 0>(WgA, K, w, xr, scA, partA, wave, lane);
     __syncthreads();                                                // (1) A's scaled partial sums are parked
-    w8_pair_stream_b<NUWB, EARLY, PFX>(q, t, lane, wave, xr, w, scB, efinB, partB, aux, xs, kvoff);
+    pair_stream_b<WsE4, B, NUWB, EARLY, PFX>(p, q.Wb8, scB, t, lane, wave, xr, w, efinB, partB, aux, xs, kvoff);
   }
 }
 
 thread_local char g_w8_pair_why[200] = "";
+PairForm<W8PairK> g_w8_pair_form = {{w8_pair_kernel<4>, w8_pair_kernel<6>, w8_pair_kernel<8>}, w8_pair_merge_kernel<8, 2>, w8_pair_merge_kernel<8, 0>,
+                                    true, "e4m3 pair", 16 * 1024, false, nullptr, ""};
 
-// Can the new instantiations keep a workgroup on a CU? Asked once per process, as gemv.hip's pair_device_refusal does for the fp32 forms
-// (which ssrhip_gemv_pair_applicable has asked before this is reached: CU count and CU masks are its part).
-const char* w8_pair_device_refusal() {
-  static const char* verdict = nullptr;
-  static bool asked = false;
-  if (asked) return verdict;
-  asked = true;
-  static char buf[200];
-  int nb[5] = {0, 0, 0, 0, 0};
-  hipError_t e0 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb[0], w8_pair_kernel<4>, PAIR_TH, 0);
-  hipError_t e1 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb[1], w8_pair_kernel<6>, PAIR_TH, 0);
-  hipError_t e2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb[2], w8_pair_kernel<8>, PAIR_TH, 0);
-  hipError_t e3 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb[3], w8_pair_merge_kernel<8, 2>, PAIR_TH, 16 * 1024);
-  hipError_t e4 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb[4], w8_pair_merge_kernel<8, 0>, PAIR_TH, 16 * 1024);
-  if (e0 != hipSuccess || e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess || nb[0] < 1 || nb[1] < 1 || nb[2] < 1 || nb[3] < 1 || nb[4] < 1) {
-    snprintf(buf, sizeof(buf), "the occupancy calculator places %d / %d / %d / %d / %d workgroups of the e4m3 pair kernels on a CU (need >= 1 each)", nb[0], nb[1], nb[2], nb[3], nb[4]);
-    return verdict = buf;
-  }
-  return verdict = nullptr;
-}
-
-// ssrhip_gemv_pair_applicable (shapes, >= 256 CUs, no CU mask, SSRHIP_GEMV_PAIR) AND ssrhip_gemv_w8_applicable for both launches
-// (SSRHIP_GEMV_SEG=0 turns it off) AND a CU takes every instantiation
-bool w8_pair_qualifies(const ssrhip_gemv_args* a, const ssrhip_gemv_args* b) {
-  auto no = [](const char* why) { snprintf(g_w8_pair_why, sizeof(g_w8_pair_why), "%s", why); return false; };
-  if (!ssrhip_gemv_pair_applicable(a, b)) return no(ssrhip_gemv_pair_why());
-  if (!ssrhip_gemv_w8_applicable(a) || !ssrhip_gemv_w8_applicable(b)) return no("the e4m3 weight stream does not take these launches (ssrhip_gemv_w8_applicable; SSRHIP_GEMV_SEG=0 turns it off)");
-  if (const char* why = w8_pair_device_refusal()) return no(why);
-  g_w8_pair_why[0] = 0;
-  return true;
+// units per wave of B, or 0 with the reason in g_w8_pair_why (gemv_pair_host.h pair_packed_plan)
+int w8_pair_plan(const ssrhip_gemv_args* a, const ssrhip_gemv_args* b, bool* merge) {
+  return pair_packed_plan(g_w8_pair_form, g_w8_pair_why, a, b, ssrhip_gemv_w8_applicable,
+                          "the e4m3 weight stream does not take these launches (ssrhip_gemv_w8_applicable; SSRHIP_GEMV_SEG=0 turns it off)", merge);
 }
 
 }  // namespace
@@ -358,39 +217,21 @@ const char* ssrhip_gemv_pair_w8_why() { return g_w8_pair_why; }   // why the las
 
 extern "C" int ssrhip_gemv_pair_w8_applicable(const ssrhip_gemv_args* a, const ssrhip_gemv_args* b) {
   if (!a || !b) return 0;
-  return w8_pair_qualifies(a, b) ? 1 : 0;
+  bool merge;
+  return w8_pair_plan(a, b, &merge) ? 1 : 0;
 }
 
 extern "C" int ssrhip_gemv_pair_w8(const ssrhip_gemv_args* a, const ssrhip_gemv_args* b, const uint8_t* Wa8, const float* scale_a, const uint8_t* Wb8,
                                    const float* scale_b, void* ws, int32_t buf, int32_t buf_next, ssrhip_stream_t stream) {
-  SSR_REQUIRE(a && b && Wa8 && scale_a && Wb8 && scale_b && ws, "ssrhip_gemv_pair_w8: null argument");
-  SSR_REQUIRE(buf >= 0 && buf < 3 && buf_next >= 0 && buf_next < 3 && buf != buf_next, "ssrhip_gemv_pair_w8: granule buffers %d -> %d (0..2, different)", buf, buf_next);
-  SSR_REQUIRE(a->epi != SSRHIP_EPI_QKV_APPEND16 && b->epi != SSRHIP_EPI_QKV_APPEND16, "ssrhip_gemv_pair_w8: the 2-byte KV append (EPI_QKV_APPEND16) exists for 5..32 rows only");
-  if (!w8_pair_qualifies(a, b)) return 1;
-  // what pair_nuwb (gemv.hip) derived for the pair it accepted
-  const bool merge = a->pro == SSRHIP_PRO_ATTN_COMBINE;
-  const int nuwb = (b->N / 256) * 2 / SEG_NW;
+  if (int rc = pair_entry_check("ssrhip_gemv_pair_w8", a, b, Wa8 && scale_a && Wb8 && scale_b && ws, buf, buf_next)) return rc;
+  bool merge = false;
+  const int nuwb = w8_pair_plan(a, b, &merge);
+  if (!nuwb) return 1;
   W8PairK q;
-  PairK& p = q.k;
-  seg_fill(&p.a, a, merge ? 2 : 8, 256);                            // one workgroup per CU: 8 rows of A, N / 256 rows of B
-  seg_fill(&p.b, b, 2, 256);
-  unsigned long long* gran = (unsigned long long*)ws;
-  p.gran = gran + (size_t)buf * PAIR_GRAN;
-  p.gran_next = gran + (size_t)buf_next * PAIR_GRAN;
-  p.gave_up = (int*)(gran + 3 * (size_t)PAIR_GRAN);
+  pair_fill(q.k, a, b, merge, ws, buf, buf_next, PAIR_GRAN);
   q.Wa8 = Wa8;
   q.sa = scale_a;
   q.Wb8 = Wb8;
   q.sb = scale_b;
-  hipStream_t s = (hipStream_t)stream;
-  if (merge) {
-    const size_t sm = ((size_t)2 * (a->K / a->kv.head_dim) * a->max_splits * sizeof(float) + 15) / 16 * 16;
-    const char* ee = getenv("SSRHIP_GEMV_PAIR_EARLY");             // read at every call (graph capture), as on the fp32 and bf16 forms
-    if (ee && ee[0] == '0') hipLaunchKernelGGL((w8_pair_merge_kernel<8, 0>), dim3(256), dim3(PAIR_TH), sm, s, q);
-    else hipLaunchKernelGGL((w8_pair_merge_kernel<8, 2>), dim3(256), dim3(PAIR_TH), sm, s, q);
-  } else if (nuwb == 4) hipLaunchKernelGGL((w8_pair_kernel<4>), dim3(256), dim3(PAIR_TH), 0, s, q);
-  else if (nuwb == 6) hipLaunchKernelGGL((w8_pair_kernel<6>), dim3(256), dim3(PAIR_TH), 0, s, q);
-  else hipLaunchKernelGGL((w8_pair_kernel<8>), dim3(256), dim3(PAIR_TH), 0, s, q);
-  SSR_LAUNCH_CHECK();
-  return 0;
+  return pair_launch(g_w8_pair_form, q, merge, nuwb, 2, a, (hipStream_t)stream);
 }

@@ -23,31 +23,9 @@
 #include <stdlib.h>
 #include "common.h"
 #include "gemv_shared.h"
+#include "gemv_wstream.h"
 
 namespace {
-
-typedef unsigned w16_v4u __attribute__((ext_vector_type(4)));
-
-// 8 packed bf16 of a streamed-once weight row: non-temporal 16-byte load (global_load_dwordx4 ... nt)
-__device__ __forceinline__ w16_v4u ld16_nt(const uint16_t* p) { return __builtin_nontemporal_load(reinterpret_cast<const w16_v4u*>(p)); }
-
-// the two float4 of one 16-byte piece: element 2m sits in the low half of dword m (shift), element 2m + 1 in the high half (mask)
-__device__ __forceinline__ float4 w16_lo(const w16_v4u u) {
-  return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xffff0000u));
-}
-__device__ __forceinline__ float4 w16_hi(const w16_v4u u) {
-  return make_float4(__uint_as_float(u.z << 16), __uint_as_float(u.z & 0xffff0000u), __uint_as_float(u.w << 16), __uint_as_float(u.w & 0xffff0000u));
-}
-
-// piece j (j = 0, 1) of a unit against the lane's x: gemv_seg_kernel's `acc[b][i & 1] = dot4(w[i], xr[b][i], acc[b][i & 1])` for i = 2j, 2j + 1
-template <int B>
-__device__ __forceinline__ void w16_piece(const w16_v4u u, int j, const float4 (&xr)[B][4], float (&acc)[B][2]) {
-  const float4 w0 = w16_lo(u), w1 = w16_hi(u);
-#pragma unroll
-  for (int b = 0; b < B; ++b) acc[b][0] = dot4(w0, xr[b][2 * j], acc[b][0]);
-#pragma unroll
-  for (int b = 0; b < B; ++b) acc[b][1] = dot4(w1, xr[b][2 * j + 1], acc[b][1]);
-}
 
 struct W16K {
   GemvK k;

@@ -26,46 +26,9 @@
 #include <stdlib.h>
 #include "common.h"
 #include "gemv_shared.h"
+#include "gemv_wstream.h"
 
 namespace {
-
-typedef unsigned w8_v4u __attribute__((ext_vector_type(4)));
-typedef float w8_v2f __attribute__((ext_vector_type(2)));
-
-// 16 codes of a streamed-once weight row: non-temporal 16-byte load (global_load_dwordx4 ... nt)
-__device__ __forceinline__ w8_v4u ld16_nt(const uint8_t* p) { return __builtin_nontemporal_load(reinterpret_cast<const w8_v4u*>(p)); }
-
-// the float4 of one dword: code m sits in byte m (v_cvt_pk_f32_fp8 widens bytes 0, 1 or, with the word select, bytes 2, 3)
-__device__ __forceinline__ float4 w8_wide(const unsigned d) {
-  const w8_v2f lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)d, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)d, true);
-  return make_float4(lo.x, lo.y, hi.x, hi.y);
-}
-
-// one unit against the lane's x: gemv_seg_kernel's `acc[b][i & 1] = dot4(w[i], xr[b][i], acc[b][i & 1])` for i = 0..3
-template <int B>
-__device__ __forceinline__ void w8_unit(const w8_v4u u, const float4 (&xr)[B][4], float (&acc)[B][2]) {
-  const float4 w0 = w8_wide(u.x), w1 = w8_wide(u.y), w2 = w8_wide(u.z), w3 = w8_wide(u.w);
-#pragma unroll
-  for (int b = 0; b < B; ++b) acc[b][0] = dot4(w0, xr[b][0], acc[b][0]);
-#pragma unroll
-  for (int b = 0; b < B; ++b) acc[b][1] = dot4(w1, xr[b][1], acc[b][1]);
-#pragma unroll
-  for (int b = 0; b < B; ++b) acc[b][0] = dot4(w2, xr[b][2], acc[b][0]);
-#pragma unroll
-  for (int b = 0; b < B; ++b) acc[b][1] = dot4(w3, xr[b][3], acc[b][1]);
-}
-
-// one unit done: seg_park with the row's scale applied to the partial sum that is parked (u = local_row * S + seg)
-template <int B>
-__device__ __forceinline__ void w8_park(const float (&acc)[B][2], float sc, float* part, int u, int lane) {
-  float mine = 0.f;
-#pragma unroll
-  for (int b = 0; b < B; ++b) {
-    const float sum = wave_sum(acc[b][0] + acc[b][1]);
-    if (lane == b) mine = sum;
-  }
-  if (lane < B) part[lane + u * B] = mine * sc;
-}
 
 struct W8K {
   GemvK k;
