@@ -269,6 +269,28 @@ int ssrhip_gemv_pair4_applicable(const ssrhip_gemv_args* a, const ssrhip_gemv_ar
 int ssrhip_gemv_pair4(const ssrhip_gemv_args* a, const ssrhip_gemv_args* b, void* ws, int32_t buf, int32_t buf_next, ssrhip_stream_t stream);
 int ssrhip_gemv_pair4_status(const void* ws, ssrhip_stream_t stream);
 
+/* ssrhip_gemv_pair4(a, b, ...) streaming the PACKED copies of a->W / b->W instead of the masters (csrc/gemv_pair4_pk.hip; DESIGN.md Part
+ * I.26): the bf16 copies `Wa16` / `Wb16` (SSRHIP_W16_INDEX), or the e4m3 codes `Wa8` / `Wb8` (SSRHIP_W8_INDEX) with the per-row scales
+ * `scale_a` [a->N] / `scale_b` [b->N]. The hand-off is ssrhip_gemv_pair4's own — granule index n * 4 + row, the workspace
+ * (SSRHIP_PAIR4_WS_BYTES), the buffer cycle (ssrhip_pair_buffer) and the give-up poll (ssrhip_gemv_pair4_status) — only the bytes the
+ * streaming waves read change; with e4m3 every partial sum is multiplied by its row's scale where it is parked. The masters must hold
+ * exactly the values the copies store (ssrhip_gemv_w16), or code * scale (ssrhip_gemv_w8); the result is then BIT-IDENTICAL to two
+ * ssrhip_gemv_w16 (ssrhip_gemv_w8) launches at B = 4 and to ssrhip_gemv_pair4(a, b) on the masters (the caveat of ssrhip_gemv_w8 about
+ * subnormal partial sums applies).
+ *   returns 0 = launched, 1 = does not qualify and NOTHING was launched, < 0 = contract error (a null pointer, granule buffers outside
+ *   0..2 or equal, EPI_QKV_APPEND16); the answer comes before any HIP call.
+ *   Qualifies iff the shape rules of ssrhip_gemv_pair4_applicable hold (B == 4; the 2-row question on the same descriptors: shapes, >= 256
+ *   CUs, no CU mask, SSRHIP_GEMV_PAIR = 0 / 1 / 2; <= 512 (row, head) pairs and merge weights within 16 KB of LDS) AND the stream's own
+ *   ssrhip_gemv_w16_applicable / ssrhip_gemv_w8_applicable takes (a) and (b) (SSRHIP_GEMV_SEG=0 turns it off) AND the occupancy calculator
+ *   places at least one workgroup of every kernel of the form on a CU (asked once per process). SSRHIP_GEMV_PAIR_EARLY=0 selects the merge
+ *   form without early units, as on ssrhip_gemv_pair_w16. */
+int ssrhip_gemv_pair4_w16_applicable(const ssrhip_gemv_args* a, const ssrhip_gemv_args* b);
+int ssrhip_gemv_pair4_w16(const ssrhip_gemv_args* a, const ssrhip_gemv_args* b, const uint16_t* Wa16, const uint16_t* Wb16, void* ws,
+                          int32_t buf, int32_t buf_next, ssrhip_stream_t stream);
+int ssrhip_gemv_pair4_w8_applicable(const ssrhip_gemv_args* a, const ssrhip_gemv_args* b);
+int ssrhip_gemv_pair4_w8(const ssrhip_gemv_args* a, const ssrhip_gemv_args* b, const uint8_t* Wa8, const float* scale_a, const uint8_t* Wb8,
+                         const float* scale_b, void* ws, int32_t buf, int32_t buf_next, ssrhip_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Single-query attention over the paged cache, split over pages (one workgroup per page):
  * replaces F.scaled_dot_product_attention at activation.py:634 for tgt_len==1 (and, row by row,
@@ -730,6 +752,17 @@ int ssrhip_lm_w8_pair_launches(const ssrhip_lm* lm);
 int ssrhip_lm_set_pair4(ssrhip_lm* lm, int on);
 /* pair launches of the last enqueued step that ran a pair4* kernel (2 * n_layer when both forms apply); 0 for other engines */
 int ssrhip_lm_pair4_launches(const ssrhip_lm* lm);
+/* Opt-in: pair launches for the 4-ROW step over the engine's PACKED stream (ssrhip_gemv_pair4_w16 / ssrhip_gemv_pair4_w8). Accepted only on
+ * a 4-row engine that has ssrhip_lm_set_w16 or ssrhip_lm_set_w8 set, before the step is captured (< 0 otherwise). on = 1 repeats
+ * ssrhip_lm_create's pairing decision for this engine: pair_mode 1 refuses, the step's own descriptors are put to the kind's _applicable,
+ * the device's pairing slot is taken unless pair_mode is 2, the workspace (SSRHIP_PAIR4_WS_BYTES) is allocated and zeroed. An engine that
+ * cannot pair returns 0 all the same and steps unpaired (ssrhip_lm_pairing says why); one that can reports ssrhip_lm_pairing = 1 with a
+ * text that names the form. A pair whose two matrices do not both have packed copies runs as two single launches. on = 0 gives slot and
+ * workspace back (the state the stream's setter left). Same tokens, bit for bit, either way. ssrhip_lm_pair_status covers this workspace too. */
+int ssrhip_lm_set_pair4_pk(ssrhip_lm* lm, int on);
+/* pair launches of the last enqueued step that ran a kernel of csrc/gemv_pair4_pk.hip (2 * n_layer when every family has packed copies;
+ * the stream's own counter keeps counting the SINGLE packed launches: then 2); 0 for other engines */
+int ssrhip_lm_pair4_pk_launches(const ssrhip_lm* lm);
 /* The same for the 5..16-row decode step: the record's pointers are SSRHIP_WT16_INDEX copies of the six families (NULL field / NULL entry:
  * that family streams the fp32 streaming-order copy of its master). From now on every GEMV launch of the step tries ssrhip_gemv_wt16 first
  * and falls back to ssrhip_gemv; same tokens, bit for bit; the step stays one captured graph. Refused (< 0) for engines of <= 4 rows (they

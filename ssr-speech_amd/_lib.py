@@ -216,6 +216,10 @@ SYMBOLS = [
     ("ssrhip_gemv_pair4_applicable", C.c_int, [C.POINTER(GemvArgs), C.POINTER(GemvArgs)]),
     ("ssrhip_gemv_pair4", C.c_int, [C.POINTER(GemvArgs), C.POINTER(GemvArgs), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     ("ssrhip_gemv_pair4_status", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("ssrhip_gemv_pair4_w16_applicable", C.c_int, [C.POINTER(GemvArgs), C.POINTER(GemvArgs)]),
+    ("ssrhip_gemv_pair4_w16", C.c_int, [C.POINTER(GemvArgs), C.POINTER(GemvArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    ("ssrhip_gemv_pair4_w8_applicable", C.c_int, [C.POINTER(GemvArgs), C.POINTER(GemvArgs)]),
+    ("ssrhip_gemv_pair4_w8", C.c_int, [C.POINTER(GemvArgs), C.POINTER(GemvArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     ("ssrhip_attn_decode", C.c_int, [C.POINTER(AttnArgs), C.c_void_p]),
     ("ssrhip_attn_combine", C.c_int, [C.POINTER(AttnArgs), C.c_void_p, C.c_void_p]),
     ("ssrhip_attn_rows", C.c_int, [C.POINTER(AttnArgs), C.c_void_p, C.c_void_p]),
@@ -276,6 +280,8 @@ SYMBOLS = [
     ("ssrhip_lm_w8_pair_launches", C.c_int, [C.c_void_p]),
     ("ssrhip_lm_set_pair4", C.c_int, [C.c_void_p, C.c_int]),
     ("ssrhip_lm_pair4_launches", C.c_int, [C.c_void_p]),
+    ("ssrhip_lm_set_pair4_pk", C.c_int, [C.c_void_p, C.c_int]),
+    ("ssrhip_lm_pair4_pk_launches", C.c_int, [C.c_void_p]),
     ("ssrhip_lm_set_wt16", C.c_int, [C.c_void_p, C.POINTER(LMW16)]),
     ("ssrhip_lm_wt16_launches", C.c_int, [C.c_void_p]),
     ("ssrhip_lm_set_wt8", C.c_int, [C.c_void_p, C.POINTER(LMW8)]),

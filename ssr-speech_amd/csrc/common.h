@@ -13,6 +13,8 @@ const char* ssrhip_gemv_pair_why();      // gemv.hip: why the last pair-applicab
 const char* ssrhip_gemv_pair_w16_why();  // gemv_pair_w16.hip: the same for ssrhip_gemv_pair_w16_applicable
 const char* ssrhip_gemv_pair_w8_why();   // gemv_pair_w8.hip: the same for ssrhip_gemv_pair_w8_applicable
 const char* ssrhip_gemv_pair4_why();     // gemv_pair4.hip: the same for ssrhip_gemv_pair4_applicable
+const char* ssrhip_gemv_pair4_w16_why(); // gemv_pair4_pk.hip: the same for ssrhip_gemv_pair4_w16_applicable
+const char* ssrhip_gemv_pair4_w8_why();  // gemv_pair4_pk.hip: the same for ssrhip_gemv_pair4_w8_applicable
 
 #define SSR_REQUIRE(cond, ...)            \
   do {                                    \

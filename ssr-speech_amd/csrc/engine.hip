@@ -71,6 +71,9 @@ struct ssrhip_lm {
                                 // PK_W16) or the e4m3 codes and scales (ssrhip_lm_set_w8_pair; PK_W8)
   bool pair4 = false;           // 4-row engine: the step runs the 4-row pair launches (ssrhip_lm_set_pair4; pair_ws then has SSRHIP_PAIR4_WS_BYTES)
   int pair4_launches = 0;       // pair launches of the last enqueued step that ran a pair4* kernel (ssrhip_lm_pair4_launches)
+  bool pair4_pk = false;        // 4-row engine with a packed stream (pk_kind PK_W16 / PK_W8): the step runs the 4-row pair launches over it
+                                // (ssrhip_lm_set_pair4_pk; pair_ws then has SSRHIP_PAIR4_WS_BYTES)
+  int pair4_pk_launches = 0;    // pair launches of the last enqueued step that ran a kernel of gemv_pair4_pk.hip (ssrhip_lm_pair4_pk_launches)
   int pk_pair_launches = 0;     // pair launches of the last enqueued step that ran a w16_pair* / w8_pair* kernel (ssrhip_lm_{w16,w8}_pair_launches)
   // the bf16 weight stream: an engine has one row count, so one kind (index into PACKED_STREAMS, -1: none) and one record of packed copies
   // of the six families, in that kind's order (SSRHIP_W16_INDEX at <= 4 rows, SSRHIP_WT16_INDEX at 5..32); NULL = that matrix streams fp32
@@ -115,6 +118,7 @@ const PackedStream PACKED_STREAMS[3] = {
     {"ssrhip_lm_set_wt32", 17, 32, "17..32", "the bf16 weight stream of the two-panel step exists for 17..32 rows only", ssrhip_gemv_wt32, true, false},
 };
 enum { PK_PAIR4 = -2 };   // not a packed stream: StepShapes::pair_plan's name for the 4-row pair launches over fp32 weights
+enum { PK_PAIR4_W16 = -3, PK_PAIR4_W8 = -4 };   // ... and for the 4-row pair launches over the packed bf16 copies / the e4m3 codes
 enum { PK_W16 = 0, PK_WT16 = 1, PK_WT32 = 2, PK_W8 = 3, PK_WT8 = 4 };   // PK_W8 / PK_WT8: the e4m3 streams of <= 4 rows (ssrhip_lm_set_w8) and of
                                                             // 5..16 rows (ssrhip_lm_set_wt8): codes AND scales, so their entry points have
                                                             // another signature and they have no row in PACKED_STREAMS
@@ -175,11 +179,11 @@ void pair_slot_release(int dev) {
 void lm_unpair(ssrhip_lm* lm) {
   if (lm->pair_ws) { hipFree(lm->pair_ws); lm->pair_ws = nullptr; }
   if (lm->pair_dev >= 0) { pair_slot_release(lm->pair_dev); lm->pair_dev = -1; }
-  lm->pk_pair = lm->pair4 = false;
+  lm->pk_pair = lm->pair4 = lm->pair4_pk = false;
 }
 
-// What differs between the pairing decisions of ssrhip_lm_create (fp32, 2 rows), ssrhip_lm_set_w16_pair / ssrhip_lm_set_w8_pair and
-// ssrhip_lm_set_pair4: whom StepShapes::pair_plan asks, the workspace, where the refusal is read and the texts.
+// What differs between the pairing decisions of ssrhip_lm_create (fp32, 2 rows), ssrhip_lm_set_w16_pair / ssrhip_lm_set_w8_pair,
+// ssrhip_lm_set_pair4 and ssrhip_lm_set_pair4_pk: whom StepShapes::pair_plan asks, the workspace, where the refusal is read and the texts.
 struct PairSpec {
   int kind; size_t ws_bytes;      // pair_plan's packed_kind (-1: the fp32 forms of 2 rows); SSRHIP_PAIR_WS_BYTES or SSRHIP_PAIR4_WS_BYTES
   const char* (*why)();           // the refusal of the kind's _applicable ...
@@ -203,6 +207,14 @@ const PairSpec PAIRSPEC_PAIR4 = {PK_PAIR4, SSRHIP_PAIR4_WS_BYTES, ssrhip_gemv_pa
                                  "ssrhip_lm_set_pair4", "ssrhip: this 4-row decode engine steps WITHOUT its 4-row pair launches (same tokens): %s\n",
                                  "4-row pair launches (ssrhip_gemv_pair4), forced on by the caller (pair_mode 2: no slot, no guard)",
                                  "4-row pair launches (ssrhip_gemv_pair4): this engine holds the pairing slot of its device"};
+const PairSpec PAIRSPEC_PAIR4_W16 = {PK_PAIR4_W16, SSRHIP_PAIR4_WS_BYTES, ssrhip_gemv_pair4_w16_why, "fewer than two launches of the step qualify for the 4-row bf16 pair forms",
+                                     "ssrhip_lm_set_pair4_pk", "ssrhip: this 4-row decode engine steps WITHOUT its 4-row bf16 pair launches (same tokens): %s\n",
+                                     "4-row bf16 pair launches (ssrhip_gemv_pair4_w16), forced on by the caller (pair_mode 2: no slot, no guard)",
+                                     "4-row bf16 pair launches (ssrhip_gemv_pair4_w16): this engine holds the pairing slot of its device"};
+const PairSpec PAIRSPEC_PAIR4_W8 = {PK_PAIR4_W8, SSRHIP_PAIR4_WS_BYTES, ssrhip_gemv_pair4_w8_why, "fewer than two launches of the step qualify for the 4-row e4m3 pair forms",
+                                    "ssrhip_lm_set_pair4_pk", "ssrhip: this 4-row decode engine steps WITHOUT its 4-row e4m3 pair launches (same tokens): %s\n",
+                                    "4-row e4m3 pair launches (ssrhip_gemv_pair4_w8), forced on by the caller (pair_mode 2: no slot, no guard)",
+                                    "4-row e4m3 pair launches (ssrhip_gemv_pair4_w8): this engine holds the pairing slot of its device"};
 
 __global__ void occupy_kernel(long long ticks, int lds_floats, int* started) {
   extern __shared__ float occ[];
@@ -385,12 +397,15 @@ struct StepShapes {
   // which launches of the 2-row step qualify for the pair forms, and how many pair launches a step then has (0: fewer than 2 -> none)
   // packed_kind PK_W16 / PK_W8: the question goes to the pair launches over packed bf16 weights / e4m3 codes (ssrhip_gemv_pair_w16_applicable,
   // ssrhip_gemv_pair_w8_applicable), -1: to the fp32 forms; which of a step's pairs then have packed copies of both matrices is
-  // enqueue_step's part. PK_PAIR4: the 4-row step, the question goes to ssrhip_gemv_pair4_applicable (fp32 weights)
+  // enqueue_step's part. PK_PAIR4: the 4-row step, the question goes to ssrhip_gemv_pair4_applicable (fp32 weights); PK_PAIR4_W16 /
+  // PK_PAIR4_W8: the 4-row step over a packed stream (ssrhip_gemv_pair4_w16_applicable, ssrhip_gemv_pair4_w8_applicable)
   int pair_plan(bool* qkv, bool* head, bool* ffn1, int packed_kind = -1) const {
     *qkv = *head = *ffn1 = false;
-    if (B != (packed_kind == PK_PAIR4 ? 4 : 2)) return 0;
+    const bool four = packed_kind == PK_PAIR4 || packed_kind == PK_PAIR4_W16 || packed_kind == PK_PAIR4_W8;
+    if (B != (four ? 4 : 2)) return 0;
     int (*const applicable)(const ssrhip_gemv_args*, const ssrhip_gemv_args*) =
-        packed_kind == PK_PAIR4 ? ssrhip_gemv_pair4_applicable : packed_kind == PK_W16 ? ssrhip_gemv_pair_w16_applicable : packed_kind == PK_W8 ? ssrhip_gemv_pair_w8_applicable : ssrhip_gemv_pair_applicable;
+        packed_kind == PK_PAIR4 ? ssrhip_gemv_pair4_applicable : packed_kind == PK_PAIR4_W16 ? ssrhip_gemv_pair4_w16_applicable : packed_kind == PK_PAIR4_W8 ? ssrhip_gemv_pair4_w8_applicable
+        : packed_kind == PK_W16 ? ssrhip_gemv_pair_w16_applicable : packed_kind == PK_W8 ? ssrhip_gemv_pair_w8_applicable : ssrhip_gemv_pair_applicable;
     const ssrhip_gemv_args fa = ffn2_args(0);
     if (d.n_layer > 1) { const ssrhip_gemv_args qa = qkv_args(1); *qkv = applicable(&fa, &qa) != 0; }
     { const ssrhip_gemv_args ha = head1_args(); *head = applicable(&fa, &ha) != 0; }
@@ -412,13 +427,15 @@ int enqueue_step(ssrhip_lm* lm, hipStream_t s, Timer* tm) {
   // replays (and eager steps) always find their buffer reset by the launch before them; with n % 3 == 1 the last pair takes buffer 1.
   // An engine that pairs its packed stream (ssrhip_lm_set_w16_pair, ssrhip_lm_set_w8_pair) hands the same pairs to the packed entry of its
   // kind, ssrhip_gemv_pair_w16 or ssrhip_gemv_pair_w8 — those whose TWO matrices have packed copies; a pair that lacks one runs as two
-  // single launches. n_pairs is the count actually launched: the buffer cycle closes over exactly these.
+  // single launches. n_pairs is the count actually launched: the buffer cycle closes over exactly these. A 4-row engine that pairs its
+  // packed stream (ssrhip_lm_set_pair4_pk) does the same with ssrhip_gemv_pair4_w16 / ssrhip_gemv_pair4_w8.
   enum { W16_IN = 0, W16_OUT = 1, W16_FFN1 = 2, W16_FFN2 = 3 };
-  const bool wp = lm->pk_pair && lm->pair_ws && (lm->pk_kind == PK_W16 || lm->pk_kind == PK_W8);
+  const bool wp = (lm->pk_pair || lm->pair4_pk) && lm->pair_ws && (lm->pk_kind == PK_W16 || lm->pk_kind == PK_W8);
   const bool wp8 = wp && lm->pk_kind == PK_W8;
+  const bool wp4 = wp && lm->pair4_pk;          // ... at 4 rows (ssrhip_lm_set_pair4_pk): the same rule for a pair that lacks a packed copy
   bool pair_qkv = false, pair_head = false, pair_ffn1 = false;
   const bool p4 = lm->pair4 && lm->pair_ws;     // the 4-row step's pair launches (ssrhip_lm_set_pair4): same plan, same cycle, ssrhip_gemv_pair4
-  int n_pairs = lm->pair_ws ? sh.pair_plan(&pair_qkv, &pair_head, &pair_ffn1, p4 ? PK_PAIR4 : wp ? lm->pk_kind : -1) : 0;
+  int n_pairs = lm->pair_ws ? sh.pair_plan(&pair_qkv, &pair_head, &pair_ffn1, p4 ? PK_PAIR4 : wp4 ? (wp8 ? PK_PAIR4_W8 : PK_PAIR4_W16) : wp ? lm->pk_kind : -1) : 0;
   // what a launch of (family, layer) streams instead of its fp32 master, in the engine's kind
   auto w16_of = [&](int family, int l) -> PackedRef {
     if (pk_codes(lm->pk_kind)) return lm->pk8[family].empty() ? PackedRef{nullptr, nullptr, nullptr} : PackedRef{nullptr, lm->pk8[family][l], lm->pk8s[family][l]};
@@ -437,11 +454,19 @@ int enqueue_step(ssrhip_lm* lm, hipStream_t s, Timer* tm) {
     for (int l = 0; l < d.n_layer; ++l) n_pairs += (ffn1_pairs(l) ? 1 : 0) + (ffn2_pairs(l) ? 1 : 0);
     if (n_pairs < 2) { pair_qkv = pair_head = pair_ffn1 = false; n_pairs = 0; }
   }
-  int pair_i = 0, n_wp = 0, n_p4 = 0;
+  int pair_i = 0, n_wp = 0, n_p4 = 0, n_p4pk = 0;
   // the launch (a, b) that pair_plan found applicable, on this pair's granule buffer; pa / pb: the packed copies (wp only)
   auto pair_call = [&](const ssrhip_gemv_args& ga, const ssrhip_gemv_args& gb, const PackedRef pa, const PackedRef pb) {
     const int bufi = ssrhip_pair_buffer(pair_i, n_pairs), bufn = ssrhip_pair_buffer((pair_i + 1) % n_pairs, n_pairs);
     pair_i += 1;
+    if (wp4) {
+      const int rc = wp8 ? ssrhip_gemv_pair4_w8(&ga, &gb, pa.w8, pa.sc, pb.w8, pb.sc, lm->pair_ws, bufi, bufn, (ssrhip_stream_t)s)
+                         : ssrhip_gemv_pair4_w16(&ga, &gb, pa.w16, pb.w16, lm->pair_ws, bufi, bufn, (ssrhip_stream_t)s);
+      n_p4pk += rc == 0;
+      if (rc == 1) ssrhip_set_error("ssrhip_lm_decode: a pair the plan accepted was refused by %s (%s)", wp8 ? "ssrhip_gemv_pair4_w8" : "ssrhip_gemv_pair4_w16",
+                                    wp8 ? ssrhip_gemv_pair4_w8_why() : ssrhip_gemv_pair4_w16_why());
+      return rc == 1 ? -1 : rc;
+    }
     if (wp) {
       const int rc = wp8 ? ssrhip_gemv_pair_w8(&ga, &gb, pa.w8, pa.sc, pb.w8, pb.sc, lm->pair_ws, bufi, bufn, (ssrhip_stream_t)s)
                          : ssrhip_gemv_pair_w16(&ga, &gb, pa.w16, pb.w16, lm->pair_ws, bufi, bufn, (ssrhip_stream_t)s);
@@ -544,7 +569,7 @@ int enqueue_step(ssrhip_lm* lm, hipStream_t s, Timer* tm) {
   STEP_CALL(CAT_GEMV, gemv_call(h2, pk_h2));
   const ssrhip_sample_args sa = sh.sample_args();
   STEP_CALL(CAT_SAMPLE, ssrhip_sample(&sa, s));
-  if (!tm || tm->only < 0) { lm->pk_launches = n_pk; lm->pk_pair_launches = n_wp; lm->pair4_launches = n_p4; lm->kv16_launches = n_kv16; lm->group_launches = n_group; }   // (a category-timing pass enqueues only part of a step)
+  if (!tm || tm->only < 0) { lm->pk_launches = n_pk; lm->pk_pair_launches = n_wp; lm->pair4_launches = n_p4; lm->pair4_pk_launches = n_p4pk; lm->kv16_launches = n_kv16; lm->group_launches = n_group; }   // (a category-timing pass enqueues only part of a step)
   return 0;
 }
 
@@ -828,13 +853,35 @@ extern "C" int ssrhip_lm_set_pair4(ssrhip_lm* lm, int on) {
   return rc < 0 ? -1 : 0;
 }
 extern "C" int ssrhip_lm_pair4_launches(const ssrhip_lm* lm) { return lm && lm->pair4 ? lm->pair4_launches : 0; }
+
+// Pair launches of the 4-row step over the engine's packed stream (csrc/gemv_pair4_pk.hip): the bf16 copies or the e4m3 codes and scales.
+// on = 1 repeats ssrhip_lm_create's pairing decision for this engine with the question put to the kind's _applicable; on = 0 gives slot
+// and workspace back (the state the stream's setter left).
+extern "C" int ssrhip_lm_set_pair4_pk(ssrhip_lm* lm, int on) {
+  SSR_REQUIRE(lm, "ssrhip_lm_set_pair4_pk: null engine");
+  SSR_REQUIRE(!lm->exec, "ssrhip_lm_set_pair4_pk: the decode step of this engine is already captured (call it before the first ssrhip_lm_decode)");
+  SSR_REQUIRE(lm->b.B == 4, "ssrhip_lm_set_pair4_pk: the 4-row pair launches exist for the 4-row step only (this engine has %d rows)", lm->b.B);
+  SSR_REQUIRE(lm->pk_kind == PK_W16 || lm->pk_kind == PK_W8, "ssrhip_lm_set_pair4_pk: this engine streams no packed weights (ssrhip_lm_set_w16 or ssrhip_lm_set_w8 comes first; "
+              "ssrhip_lm_set_pair4 pairs the fp32 masters)");
+  const bool w8 = lm->pk_kind == PK_W8;
+  lm_unpair(lm);
+  if (!on) {
+    snprintf(lm->pair_why, sizeof(lm->pair_why), "this engine streams %s weights and its 4-row %s pair launches are switched off (ssrhip_lm_set_pair4_pk)", w8 ? "e4m3" : "bf16",
+             w8 ? "e4m3" : "bf16");
+    return 0;
+  }
+  const int rc = lm_take_pairing(lm, w8 ? PAIRSPEC_PAIR4_W8 : PAIRSPEC_PAIR4_W16);
+  lm->pair4_pk = rc == 1;
+  return rc < 0 ? -1 : 0;
+}
+extern "C" int ssrhip_lm_pair4_pk_launches(const ssrhip_lm* lm) { return lm && lm->pair4_pk ? lm->pair4_pk_launches : 0; }
 extern "C" int ssrhip_lm_wt16_launches(const ssrhip_lm* lm) { return lm_packed_launches(lm, PK_WT16); }
 extern "C" int ssrhip_lm_wt32_launches(const ssrhip_lm* lm) { return lm_packed_launches(lm, PK_WT32); }
 
 extern "C" int ssrhip_lm_pair_status(ssrhip_lm* lm, ssrhip_stream_t stream) {
   SSR_REQUIRE(lm, "ssrhip_lm_pair_status: null engine");
   if (!lm->pair_ws) return 0;
-  if (lm->pair4) return ssrhip_gemv_pair4_status(lm->pair_ws, stream);   // the 4-row workspace is twice the size
+  if (lm->pair4 || lm->pair4_pk) return ssrhip_gemv_pair4_status(lm->pair_ws, stream);   // the 4-row workspace is twice the size
   return ssrhip_gemv_pair_status(lm->pair_ws, stream);
 }
 

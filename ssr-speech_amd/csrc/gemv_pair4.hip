@@ -186,25 +186,15 @@ __global__ __launch_bounds__(PAIR_TH) void pair4_merge_kernel(const PairK p) {
   }
 }
 
-constexpr size_t PAIR4_WTAB_MAX = 16 * 1024;   // merge weights in dynamic LDS, next to ~34 KB of static buffers
-
 thread_local char g_pair4_why[200] = "";
 PairForm<PairK> g_pair4_form = {{pair4_kernel<4>, pair4_kernel<6>, pair4_kernel<8>}, pair4_merge_kernel<8>, nullptr, false, "4-row pair", PAIR4_WTAB_MAX, false, nullptr, ""};
 
-// ssrhip_gemv_pair_applicable's rules with B == 4: the 2-row question is put with the row count set to 2 (shapes, >= 256 CUs, no CU mask,
-// SSRHIP_GEMV_PAIR = 0 / 1 / 2), then what four rows change — the merge's (row, head) table and its LDS — and the occupancy of the 4-row
-// kernels (33-50 KB of LDS). Units per wave of B, or 0 with the reason in g_pair4_why.
+// ssrhip_gemv_pair_applicable's rules with B == 4: the shape rules of the 4-row forms (gemv_pair_host.h pair4_shape_plan: the 2-row
+// question with the row count set to 2, then the merge's (row, head) table and its LDS) and the occupancy of the 4-row kernels
+// (33-50 KB of LDS). Units per wave of B, or 0 with the reason in g_pair4_why.
 int pair4_plan(const ssrhip_gemv_args* a, const ssrhip_gemv_args* b, bool* merge) {
-  if (a->B != PAIR4_B || b->B != PAIR4_B) return pair_refuse(g_pair4_why, "not a 4-row launch (the 4-row pair kernels take B = 4 only)");
-  ssrhip_gemv_args a2 = *a, b2 = *b;
-  a2.B = b2.B = 2;
-  const int nuwb = ssrhip_gemv_pair_plan(&a2, &b2, merge);
-  if (!nuwb) return pair_refuse(g_pair4_why, ssrhip_gemv_pair_why());
-  if (*merge) {
-    const int H = a->K / a->kv.head_dim;
-    if (PAIR4_B * H > SEG_TH) return pair_refuse(g_pair4_why, "merge form: more than 512 (row, head) pairs");
-    if ((size_t)PAIR4_B * H * a->max_splits * sizeof(float) > PAIR4_WTAB_MAX) return pair_refuse(g_pair4_why, "merge weights exceed 16 KB of LDS (context too long for the 4-row merge form)");
-  }
+  const int nuwb = pair4_shape_plan(g_pair4_why, a, b, merge);
+  if (!nuwb) return 0;
   if (const char* why = pair_occupancy_refusal(g_pair4_form)) return pair_refuse(g_pair4_why, why);
   g_pair4_why[0] = 0;
   return nuwb;

@@ -1,6 +1,7 @@
-// gemv_pair_host.h — the host side of the pair launches, once for the four forms (fp32 at 2 rows: gemv.hip; packed bf16: gemv_pair_w16.hip;
-// e4m3 codes: gemv_pair_w8.hip; fp32 at 4 rows: gemv_pair4.hip): the argument checks of an entry point, the launch descriptor, the table of
-// a form's kernels with the launch through it, the occupancy question, the packed forms' applicability question and the give-up poll.
+// gemv_pair_host.h — the host side of the pair launches, once for every form (fp32 at 2 rows: gemv.hip; packed bf16: gemv_pair_w16.hip;
+// e4m3 codes: gemv_pair_w8.hip; fp32 at 4 rows: gemv_pair4.hip; packed at 4 rows: gemv_pair4_pk.hip): the argument checks of an entry
+// point, the launch descriptor, the table of a form's kernels with the launch through it, the occupancy question, the packed forms'
+// applicability question, the 4-row forms' shape rules and the give-up poll.
 // What a form keeps to itself: its kernels, its table, its thread-local "why" text and what its question adds to the 2-row one.
 #pragma once
 #include <stdlib.h>
@@ -97,6 +98,25 @@ int pair_packed_plan(PairForm<Q>& f, char (&why)[200], const ssrhip_gemv_args* a
   if (!stream_applicable(a) || !stream_applicable(b)) return pair_refuse(why, stream_refusal);
   if (const char* w = pair_occupancy_refusal(f)) return pair_refuse(why, w);
   why[0] = 0;
+  return nuwb;
+}
+
+constexpr size_t PAIR4_WTAB_MAX = 16 * 1024;   // 4 rows: merge weights in dynamic LDS, next to ~34 KB of static buffers
+
+// The shape part of every 4-row question (fp32: gemv_pair4.hip; packed: gemv_pair4_pk.hip): B == 4, then the 2-row question put with the
+// row count set to 2 (shapes, >= 256 CUs, no CU mask, SSRHIP_GEMV_PAIR = 0 / 1 / 2), then what four rows change — the merge's (row,
+// head) table and its LDS. Units per wave of B (`why` untouched), or 0 with the reason in `why`.
+inline int pair4_shape_plan(char (&why)[200], const ssrhip_gemv_args* a, const ssrhip_gemv_args* b, bool* merge) {
+  if (a->B != PAIR4_B || b->B != PAIR4_B) return pair_refuse(why, "not a 4-row launch (the 4-row pair kernels take B = 4 only)");
+  ssrhip_gemv_args a2 = *a, b2 = *b;
+  a2.B = b2.B = 2;
+  const int nuwb = ssrhip_gemv_pair_plan(&a2, &b2, merge);
+  if (!nuwb) return pair_refuse(why, ssrhip_gemv_pair_why());
+  if (*merge) {
+    const int H = a->K / a->kv.head_dim;
+    if (PAIR4_B * H > SEG_TH) return pair_refuse(why, "merge form: more than 512 (row, head) pairs");
+    if ((size_t)PAIR4_B * H * a->max_splits * sizeof(float) > PAIR4_WTAB_MAX) return pair_refuse(why, "merge weights exceed 16 KB of LDS (context too long for the 4-row merge form)");
+  }
   return nuwb;
 }
 

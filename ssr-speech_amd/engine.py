@@ -348,6 +348,31 @@ def resolve_pair4(rows: int, stream_w16: bool, stream_w8: bool, pair_mode: int, 
     return True
 
 
+# What an unset SSRHIP_GEMV_PAIR4_PK means for a 4-row engine that streams packed weights, w16 or w8 (DecodeEngine pair4_pk=None): "1" = its
+# step runs the 4-row pair launches over the packed stream (include/ssrhip.h ssrhip_lm_set_pair4_pk), "0" = it steps with the single packed
+# launches. DESIGN.md Part I.26.
+PAIR4_PK_DEFAULT = "0"
+
+
+def resolve_pair4_pk(rows: int, stream_w16: bool, stream_w8: bool, pair_mode: int, requested: Optional[bool], env) -> bool:
+    """Does an engine of `rows` rows ask for the 4-row pair launches over its packed weight stream (DecodeEngine pair4_pk)? requested None:
+    on iff the engine has 4 rows, streams w16 or w8, pair_mode is not 1 and `env["SSRHIP_GEMV_PAIR4_PK"]` (unset: PAIR4_PK_DEFAULT) does
+    not start with '0'. requested True: ValueError at another row count (named first), then without a packed stream, then with pair_mode
+    1. Whether the engine then GETS to pair (device, pairing slot) is the library's decision (`DecodeEngine.pairing`). `env` is a mapping
+    like os.environ; nothing else is read."""
+    if requested is None:
+        return rows == 4 and bool(stream_w16 or stream_w8) and pair_mode != 1 and env.get("SSRHIP_GEMV_PAIR4_PK", PAIR4_PK_DEFAULT)[:1] != "0"
+    if not requested:
+        return False
+    if rows != 4:
+        raise ValueError(f"pair4_pk: the 4-row pair launches exist for the 4-row decode step only (this engine has {rows} rows)")
+    if not (stream_w16 or stream_w8):
+        raise ValueError("pair4_pk needs an engine that streams packed weights (stream_w16 or stream_w8); pair4 pairs the fp32 masters")
+    if pair_mode == 1:
+        raise ValueError("pair4_pk with pair_mode=1: the caller switched pair launches off")
+    return True
+
+
 KV_DTYPES = ("fp32", "bf16")
 KV16_MAX_PAGES = 256          # pages per row the fused attention walk takes (csrc/attn.hip ATTN_ROWS_MAX_PAGES)
 
@@ -1101,7 +1126,7 @@ class DecodeEngine:
                  stream_w16: Optional[bool] = None, stream_wt16: Optional[bool] = None, stream_wt32: Optional[bool] = None,
                  kv_dtype: Optional[str] = None, share_prompt: Optional[bool] = None, stream_w8: Optional[bool] = None,
                  pair_w16: Optional[bool] = None, pair_w8: Optional[bool] = None, stream_wt8: Optional[bool] = None,
-                 kv16_small: Optional[bool] = None, pair4: Optional[bool] = None):
+                 kv16_small: Optional[bool] = None, pair4: Optional[bool] = None, pair4_pk: Optional[bool] = None):
         """max_seq: longest sequence (text + audio positions) any ONE row may reach; pool_pages: physical KV pages shared by all
         rows (default rows x pages-per-row, the no-sharing worst case; a batch of short and long utterances needs only the sum
         of their own page counts). pair_mode (2-row engines; include/ssrhip.h ssrhip_lm_buffers): 0 = pair launches if this engine
@@ -1140,7 +1165,10 @@ class DecodeEngine:
         is not a ValueError at these rows. Every weight stream and launch form works unchanged; at most KV16_SMALL_MAX_LAYERS layers.
         pair4 (4-row engines that stream their fp32 masters; `resolve_pair4`, DESIGN.md Part I.24): the step runs the 4-row pair launches
         (include/ssrhip.h ssrhip_lm_set_pair4) if the library lets this engine pair (`pairing`, `pairing_why`); None = on when
-        `SSRHIP_GEMV_PAIR4` (read here; unset = PAIR4_DEFAULT) does not start with '0'. Same tokens, bit for bit, either way."""
+        `SSRHIP_GEMV_PAIR4` (read here; unset = PAIR4_DEFAULT) does not start with '0'. Same tokens, bit for bit, either way.
+        pair4_pk (4-row engines that stream w16 or w8; `resolve_pair4_pk`, DESIGN.md Part I.26): the step runs the 4-row pair launches over
+        the packed stream (include/ssrhip.h ssrhip_lm_set_pair4_pk) if the library lets this engine pair; None = on when
+        `SSRHIP_GEMV_PAIR4_PK` (read here; unset = PAIR4_PK_DEFAULT) does not start with '0'. Same tokens, bit for bit, either way."""
         self.lib = _lib.lib()
         self.a = arena
         dev = arena.device
@@ -1255,6 +1283,7 @@ class DecodeEngine:
         self.pair_w16 = resolve_w16_pair(self.B, self.stream_w16, self.pair_mode, pair_w16, os.environ)
         self.pair_w8 = resolve_w8_pair(self.B, self.stream_w8, self.pair_mode, pair_w8, os.environ)
         self.pair4 = resolve_pair4(self.B, self.stream_w16, self.stream_w8, self.pair_mode, pair4, os.environ)
+        self.pair4_pk = resolve_pair4_pk(self.B, self.stream_w16, self.stream_w8, self.pair_mode, pair4_pk, os.environ)
         self.pairing = False                      # set by _create_ctx: does this engine's step run the pair launches?
         self.pairing_why = ""
 
@@ -1298,6 +1327,8 @@ class DecodeEngine:
                 _lib.check(self.lib.ssrhip_lm_set_w8_pair(ctx, 1), "ssrhip_lm_set_w8_pair")
         if self.pair4 and self.pair_mode != 1:    # the 4-row step's pair launches over the fp32 masters (after a give-up: unpaired)
             _lib.check(self.lib.ssrhip_lm_set_pair4(ctx, 1), "ssrhip_lm_set_pair4")
+        if self.pair4_pk and self.pair_mode != 1:     # ... over the packed stream set above (after a give-up: unpaired)
+            _lib.check(self.lib.ssrhip_lm_set_pair4_pk(ctx, 1), "ssrhip_lm_set_pair4_pk")
         if self.stream_wt8:                       # the e4m3 stream of the 5..16-row step (no pairing at these rows)
             rec8 = self.a.wt8_struct()
             _lib.check(self.lib.ssrhip_lm_set_wt8(ctx, C.byref(rec8)), "ssrhip_lm_set_wt8")
@@ -1370,6 +1401,12 @@ class DecodeEngine:
         """Pair launches of the last enqueued decode step that ran a 4-row pair kernel (2 * layers when both forms apply). 0 for an engine
         that does not run the 4-row pair launches."""
         return self._launches_per_step("pair4")
+
+    @property
+    def pair4_pk_launches_per_step(self) -> int:
+        """Pair launches of the last enqueued decode step that ran a 4-row pair kernel over packed weights (2 * layers when every family has
+        a packed copy; the stream's own counter then counts the two single launches left). 0 for an engine that does not run them."""
+        return self._launches_per_step("pair4_pk")
 
     @property
     def wt8_launches_per_step(self) -> int:

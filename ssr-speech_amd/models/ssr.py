@@ -25,7 +25,7 @@ from .. import _lib
 from .. import layout as LY
 from .. import score as SC
 from ..engine import (DEFAULT_GROUP_ROWS, KV_DTYPES, MAX_ROWS, WEIGHT_DTYPES, DecodeEngine, DecodeKnobs, LMWeightsArena, PhiloxNoise, SAMPLING_RNGS,
-                      TorchCpuNoiseFeed, W16_STREAMS, resolve_kv16_small, resolve_kv_dtype, resolve_pair4, resolve_sampling_rng, resolve_share_prompt, resolve_w16_pair, resolve_w16_stream, resolve_w8_pair, resolve_w8_stream)
+                      TorchCpuNoiseFeed, W16_STREAMS, resolve_kv16_small, resolve_kv_dtype, resolve_pair4, resolve_pair4_pk, resolve_sampling_rng, resolve_share_prompt, resolve_w16_pair, resolve_w16_stream, resolve_w8_pair, resolve_w8_stream)
 from ..weights import lm_param_specs
 
 
@@ -329,12 +329,15 @@ class SSR_Speech(nn.Module):
         # ... and SSRHIP_GEMV_PAIR4's for the 4-row step over the fp32 masters
         pair4 = resolve_pair4(rows, resolve_w16_stream(W16_STREAMS[0], rows, self._arena.weight_dtype, None, os.environ),
                               resolve_w8_stream(rows, self._arena.weight_dtype, None, os.environ), 0, None, os.environ)
-        for (k_utt, k_cfg, k_seq, k_steps, k_dbg, k_pool, k_order, k_share, k_wp, k_wp8, k_kvs, k_p4), e in self._engines.items():
-            if (k_utt, k_cfg, k_dbg, k_order, k_share, k_wp, k_wp8, k_kvs, k_p4) == (n_utt, use_cfg, bool(self.debug_logits), order_key, share, w16_pair, w8_pair, kv16_small, pair4) and k_seq >= cap_seq and k_steps >= cap_steps \
+        # ... and SSRHIP_GEMV_PAIR4_PK's for the 4-row step over a packed stream
+        pair4_pk = resolve_pair4_pk(rows, resolve_w16_stream(W16_STREAMS[0], rows, self._arena.weight_dtype, None, os.environ),
+                                    resolve_w8_stream(rows, self._arena.weight_dtype, None, os.environ), 0, None, os.environ)
+        for (k_utt, k_cfg, k_seq, k_steps, k_dbg, k_pool, k_order, k_share, k_wp, k_wp8, k_kvs, k_p4, k_p4pk), e in self._engines.items():
+            if (k_utt, k_cfg, k_dbg, k_order, k_share, k_wp, k_wp8, k_kvs, k_p4, k_p4pk) == (n_utt, use_cfg, bool(self.debug_logits), order_key, share, w16_pair, w8_pair, kv16_small, pair4, pair4_pk) and k_seq >= cap_seq and k_steps >= cap_steps \
                     and (k_pool >= need if order_key is None else k_pool == min(rows * (cap_seq // 128), ((need + 7) // 8) * 8)):
                 return e
         pool = min(rows * (cap_seq // 128), ((need + 7) // 8) * 8)
-        key = (n_utt, use_cfg, cap_seq, cap_steps, bool(self.debug_logits), pool, order_key, share, w16_pair, w8_pair, kv16_small, pair4)
+        key = (n_utt, use_cfg, cap_seq, cap_steps, bool(self.debug_logits), pool, order_key, share, w16_pair, w8_pair, kv16_small, pair4, pair4_pk)
         for e in self._engines.values():         # one engine (KV pool) resident at a time
             e.close()
         self._engines = {}

@@ -39,6 +39,8 @@ Pair launches over the e4m3 weight stream (DESIGN.md Part I.20; `SSRHIP_GEMV_W8_
   python tools/decode_ab.py --reps 4 fp32: e4m3_w8:weight_dtype=e4m3 e4m3_w8_pair:weight_dtype=e4m3,SSRHIP_GEMV_W8_PAIR=1
 Pair launches of the 4-row step over the fp32 weights (DESIGN.md Part I.24; `SSRHIP_GEMV_PAIR4=1` is the opt-in, `pair4` the counter):
   python tools/decode_ab.py --utts 2 --warmup 180 --steps 100 --reps 4 unpaired: pair4:SSRHIP_GEMV_PAIR4=1
+Pair launches of the 4-row step over the packed streams (DESIGN.md Part I.26; `SSRHIP_GEMV_PAIR4_PK=1` is the opt-in, `pair4 pk` the counter):
+  python tools/decode_ab.py --utts 2 --warmup 180 --steps 100 --reps 4 bf16:weight_dtype=bf16 bf16_pk:weight_dtype=bf16,SSRHIP_GEMV_PAIR4_PK=1 e4m3:weight_dtype=e4m3 e4m3_pk:weight_dtype=e4m3,SSRHIP_GEMV_PAIR4_PK=1
 A lower-case `kv16_small=1` (DESIGN.md Part I.23; 1, 2 or 4 rows) builds the arm's engine with kv_dtype="bf16", kv16_small=True: the 2-byte
 cache behind the landing cache of the split-KV step (`kv16 launches` its counter, `attn` its per-launch time), under any weight stream:
   python tools/decode_ab.py --reps 4 --warmup 180 --steps 100 fp32: fp32_kv16:kv16_small=1 e4m3_pair:weight_dtype=e4m3,SSRHIP_GEMV_W8_PAIR=1 e4m3_pair_kv16:weight_dtype=e4m3,SSRHIP_GEMV_W8_PAIR=1,kv16_small=1
@@ -140,6 +142,7 @@ for rep in range(a.reps):
         r["w16_pair"] = eng.w16_pair_launches_per_step
         r["w8_pair"] = eng.w8_pair_launches_per_step
         r["pair4"] = eng.pair4_launches_per_step
+        r["pair4_pk"] = eng.pair4_pk_launches_per_step
         r["pairing"] = eng.pairing
         r["kv16"] = eng.kv16_launches_per_step
         r["group"] = eng.group_launches_per_step
@@ -169,4 +172,4 @@ for name, knobs in variants:
     print(f"{name:14s} {U:2d} utts x CFG = {2 * U:2d} rows  tok/s {4 * U / (statistics.median(r['ms']) * 1e-3):9.1f}  "
           f"ms/step min {min(r['ms']):.4f} med {statistics.median(r['ms']):.4f}  all {' '.join(f'{v:.4f}' for v in r['ms'])} | "
           f"gemv {min(r['gemv']):.3f} x {r['launches']['gemv']} attn {min(r['attn']):.3f} x {r['launches']['attn']} "
-          f"sample {min(r['sample']):.3f} x {r['launches']['sample']} us{same}   [{dtype_of[name]}, kv {kv_of[name]}, {' + '.join(f'{r[st.name]} {st.name}' for st in W16_STREAMS)} + {r['w8']} w8 + {r['wt8']} wt8 + {r['w16_pair']} w16 pair + {r['w8_pair']} w8 pair + {r['pair4']} pair4 + {r['kv16']} kv16 + {r['group']} group launches; kv16_small={int(small_of[name])}; first fill {r['prefill_rows']} rows in {min(r['prefill_ms']):.2f} ms, {r['pages']} KV pages in use; share_prompt={share_of[name]}; pairing={r['pairing']}; {' '.join(f'{k}={v}' for k, v in knobs.items()) or 'defaults'}]")
+          f"sample {min(r['sample']):.3f} x {r['launches']['sample']} us{same}   [{dtype_of[name]}, kv {kv_of[name]}, {' + '.join(f'{r[st.name]} {st.name}' for st in W16_STREAMS)} + {r['w8']} w8 + {r['wt8']} wt8 + {r['w16_pair']} w16 pair + {r['w8_pair']} w8 pair + {r['pair4']} pair4 + {r['pair4_pk']} pair4 pk + {r['kv16']} kv16 + {r['group']} group launches; kv16_small={int(small_of[name])}; first fill {r['prefill_rows']} rows in {min(r['prefill_ms']):.2f} ms, {r['pages']} KV pages in use; share_prompt={share_of[name]}; pairing={r['pairing']}; {' '.join(f'{k}={v}' for k, v in knobs.items()) or 'defaults'}]")
