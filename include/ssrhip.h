@@ -431,6 +431,15 @@ typedef struct ssrhip_sample_args {
 } ssrhip_sample_args;
 
 int ssrhip_sample(const ssrhip_sample_args* a, ssrhip_stream_t stream);
+/* ssrhip_sample, and the log-probability of every token it generates (DESIGN.md Part I.27): for utterance u, its step s and codebook k,
+ *     logp[(u * max_steps + s) * K + k] = z[t] - logsumexp(z over all card entries)          (natural log, fp32)
+ * where z = the logits handed to the reference's topk_sampling (after the CFG combine, the special-token edits and the silence penalty,
+ * before top-k / top-p) divided by the temperature, and t = generated[u][s][k]. NaN where the state machine, not the draw, decided t:
+ * the start-of-span delay (num_gen < K-1 and k > num_gen), the eog cascade (num_eog > 0 and k <= num_eog) and the stop rule
+ * (num_eog == 0, k == 0 and argmax == eog or audio_pos + 1 > 10 * text_len), by the state at kernel entry; NaN also where t is no index of
+ * the card (nothing to draw from: every logit NaN). An utterance that is done writes nothing; a live one writes all K values of its step. Same tokens, state and next-step inputs as ssrhip_sample; one more workgroup-wide sum and, without the fused embed,
+ * one more barrier. `logp` is a DEVICE buffer [n_utt][max_steps][K] of the caller's; NULL is an argument error. */
+int ssrhip_sample_logp(const ssrhip_sample_args* a, float* logp, ssrhip_stream_t stream);
 
 /* The batched stream's hand-off from the sampler to the codec (DESIGN.md Part I.16): for utterance u < n_utt, generated frame f in
  * [f0[u], f1[u]) and codebook k < K,
@@ -804,6 +813,12 @@ int ssrhip_lm_set_kv16(ssrhip_lm* lm, int32_t on);
 /* how many attention launches of the last enqueued (or captured) decode step ran ssrhip_attn_rows_kv16 — or, at <= 4 rows,
  * ssrhip_attn_decode_kv16 (n_layer for an engine with a 2-byte cache, else 0) */
 int ssrhip_lm_kv16_launches(const ssrhip_lm* lm);
+/* logp != NULL: the decode step of this engine ends in ssrhip_sample_logp with this DEVICE buffer [n_utt][max_steps][K] of the caller's
+ * (n_utt and max_steps as its sampler reads them), at every row count; NULL: back to ssrhip_sample. Opt-in: an engine that never calls
+ * this runs the step it ran before. Refused (< 0) once the decode step is captured. */
+int ssrhip_lm_set_logprobs(ssrhip_lm* lm, float* logp);
+/* 1: the step of this engine writes per-token log-probabilities (ssrhip_lm_set_logprobs), 0: it does not */
+int ssrhip_lm_logprobs(const ssrhip_lm* lm);
 /* The same statement for engines of 1, 2 or 4 rows (opt-in, DESIGN.md Part I.23): the pool of ssrhip_lm_buffers.kv holds 2-byte entries,
  * and the caller hands over three DEVICE buffers it owns and has filled ONCE:
  *   land        [B][1][2][n_head][SSRHIP_PAGE][head_dim] fp32 — a one-layer cache of B pages in the pool's layout (contents: anything);

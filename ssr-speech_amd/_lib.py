@@ -232,6 +232,7 @@ SYMBOLS = [
     ("ssrhip_attn_rows_group_m", C.c_int, [C.POINTER(AttnArgs), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     ("ssrhip_embed", C.c_int, [C.POINTER(EmbedArgs), C.c_void_p]),
     ("ssrhip_sample", C.c_int, [C.POINTER(SampleArgs), C.c_void_p]),
+    ("ssrhip_sample_logp", C.c_int, [C.POINTER(SampleArgs), C.c_void_p, C.c_void_p]),
     ("ssrhip_stream_gather", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                        C.c_int32, C.c_void_p, C.c_void_p]),
     ("ssrhip_noise_sizeof", C.c_int, []),
@@ -261,6 +262,8 @@ SYMBOLS = [
     ("ssrhip_lm_set_prefill_w1", C.c_int, [C.c_void_p, C.c_int32]),
     ("ssrhip_lm_set_kv16", C.c_int, [C.c_void_p, C.c_int32]),
     ("ssrhip_lm_kv16_launches", C.c_int, [C.c_void_p]),
+    ("ssrhip_lm_set_logprobs", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("ssrhip_lm_logprobs", C.c_int, [C.c_void_p]),
     ("ssrhip_lm_set_kv16_small", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("ssrhip_lm_set_prompt_groups", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ("ssrhip_lm_group_launches", C.c_int, [C.c_void_p]),

@@ -9,6 +9,7 @@
 //   (<= 34 per lane), top-k / top-p thresholds are found by bisection on the order-preserving integer
 //   image of the logits (ballot+popcount for counts, fixed-order DPP wave sums for mass) — no sort, no
 //   atomics, bit-reproducible.  No host round trip per step.
+// ssrhip_sample_logp: the same launch, which also writes the log-probability of every token it generates (sample_kernel<true>).
 #include <stdlib.h>
 #include "common.h"
 
@@ -351,7 +352,28 @@ __device__ __forceinline__ void cb_argmax(CbF& f, CbI& i, float& v, int& idx, in
   if (RELEASE) __syncthreads();
 }
 
-__global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(const ssrhip_sample_args a, const int force_radix) {
+// The LOGP output of one step: `fin` = the K tokens the state machine wrote and its forced mask, published before the barrier the caller
+// has just passed. The one lane that holds the logit of codebook k's token stores l - mx - log(sum exp(l - mx)); a forced position gets
+// NaN from the first lane of the codebook (its token need not be one any lane would pick), and so does a token outside the card (the
+// draw's "nothing to draw from": every logit NaN), so that every position of a live utterance is written. Plain vector stores.
+__device__ __forceinline__ void logp_store(float* out, const int* fin, const float (&l)[MAXE], float mx, float lse, int k, int sub, int lane,
+                                           bool active, int card) {
+  if (!active) return;
+  const int t = fin[k];
+  if (((fin[SSRHIP_MAX_CODEBOOKS] >> k) & 1) || (unsigned)t >= (unsigned)card) {
+    if (sub == 0 && lane == 0) out[k] = __builtin_nanf("");
+    return;
+  }
+#pragma unroll
+  for (int e = 0; e < MAXE; ++e)
+    if (elem_index(e, sub, lane) == t) out[k] = (l[e] - mx) - lse;
+}
+
+// LOGP (ssrhip_sample_logp, DESIGN.md Part I.27): also write the log-probability of every token this step generates, under the softmax
+// of the edited, temperature-scaled logits BEFORE top-k / top-p, to logp[u][step][k] — NaN where the state machine, not the draw,
+// decided the token. Everything it adds sits behind `if constexpr`: the false instantiation is the kernel ssrhip_sample launches.
+template <bool LOGP>
+__global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(const ssrhip_sample_args a, const int force_radix, float* const logp) {
   __shared__ SelShared sel;
   __shared__ float sh_f[SSRHIP_MAX_CODEBOOKS][WPC];
   __shared__ float sh_g[SSRHIP_MAX_CODEBOOKS][WPC];
@@ -359,6 +381,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(const ssrhip_sam
   __shared__ int sh_sample[SSRHIP_MAX_CODEBOOKS];
   __shared__ int sh_argmax0;
   __shared__ int sh_next[SSRHIP_MAX_CODEBOOKS + 2];   // next tokens, next audio pos, live flag
+  __shared__ int sh_fin[SSRHIP_MAX_CODEBOOKS + 1];    // LOGP: the tokens written to `generated`, forced mask (bit k: codebook k)
   const int u = blockIdx.x;
   const ssrhip_sampler_cfg& c = a.cfg[u];
   ssrhip_sampler_state& st = a.state[u];
@@ -488,6 +511,13 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(const ssrhip_sam
     Z += p[e];
   }
   Z = cb_sum(sh_f, wave_sum(Z), k, sub, lane, active);
+  float lse = 0.f;        // LOGP: log of the sum of exp(l - mx) over the whole card (accurate expf / logf: this is an output, not a draw)
+  if constexpr (LOGP) {
+    float za = 0.f;
+#pragma unroll
+    for (int e = 0; e < MAXE; ++e) za += (key[e] != 0u) ? expf(l[e] - mx) : 0.f;
+    lse = logf(cb_sum(sh_f, wave_sum(za), k, sub, lane, active));
+  }
   if (c_topp < 1.0f) {   // uniform
     const uint32_t tp = select_threshold<1>(key, p, l, vlo, vscale, 0u, c_topp * Z, active, sel, kc, sub, lane, force_radix);
     if (tp > thr) {
@@ -536,6 +566,16 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(const ssrhip_sam
     int s[SSRHIP_MAX_CODEBOOKS];
     for (int j = 0; j < K; ++j) s[j] = sh_sample[j];
     int ne_og = num_eog, cs = consec, pt = prev_token;
+    if constexpr (LOGP) {
+      // forced by the RULE, never by comparing the token with the draw: start-of-span delay | eog cascade | stop rule
+      int forced = 0;
+      for (int j = 0; j < K; ++j) {
+        const bool f = (num_gen < K - 1 && j > num_gen) || (num_eog > 0 && j <= num_eog) ||
+                       (num_eog == 0 && j == 0 && (sh_argmax0 == c_eog || (st_audio_pos + 1) > c_textlen * 10));
+        forced |= f ? (1 << j) : 0;
+      }
+      sh_fin[SSRHIP_MAX_CODEBOOKS] = forced;
+    }
     if (num_eog > 0) {
       for (int j = 0; j < num_eog; ++j) s[j] = c_empty;
       s[num_eog] = c_eog;
@@ -554,6 +594,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(const ssrhip_sam
     if (c_usecfg) st.num_cfg_tag = (cfg_tag == c_stride) ? 1 : cfg_tag + 1;
     int* gen = a.generated + ((size_t)u * c_maxsteps + step) * K;
     for (int j = 0; j < K; ++j) gen[j] = s[j];
+    if constexpr (LOGP) { for (int j = 0; j < K; ++j) sh_fin[j] = s[j]; }
     st.n_steps = step + 1;
     st.num_gen = num_gen + 1;
     st.num_eog = ne_og;
@@ -592,9 +633,13 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(const ssrhip_sam
   // ---- fused embedding of the next input row(s) (ssr.py:757-763): saves a launch per step
   if (a.embed.out) {
     __syncthreads();
+    if constexpr (LOGP) logp_store(logp + ((size_t)u * c_maxsteps + step) * K, sh_fin, l, mx, lse, k, sub, lane, active, card);   // shares the barrier
     if (sh_next[SSRHIP_MAX_CODEBOOKS + 1]) {
       for (int rr = 0; rr < rows; ++rr) embed_row(a.embed, row0 + rr, 1, sh_next[SSRHIP_MAX_CODEBOOKS], sh_next, threadIdx.x, SAMPLE_THREADS);
     }
+  } else if constexpr (LOGP) {
+    __syncthreads();
+    logp_store(logp + ((size_t)u * c_maxsteps + step) * K, sh_fin, l, mx, lse, k, sub, lane, active, card);
   }
   STAMP(8);
 }
@@ -661,15 +706,29 @@ extern "C" int ssrhip_embed(const ssrhip_embed_args* a, ssrhip_stream_t stream) 
   return 0;
 }
 
-extern "C" int ssrhip_sample(const ssrhip_sample_args* a, ssrhip_stream_t stream) {
+namespace {
+
+// ssrhip_sample (logp == nullptr: the kernel without the output) and ssrhip_sample_logp: one argument check, one launch
+int sample_launch(const ssrhip_sample_args* a, float* logp, ssrhip_stream_t stream, const char* who) {
   SSR_REQUIRE(a && a->logits && a->cfg && a->state && a->generated && a->next_tok && a->next_pos && a->kv_pos && a->row_len,
-              "ssrhip_sample: null argument");
-  SSR_REQUIRE(a->K >= 1 && a->K <= SSRHIP_MAX_CODEBOOKS, "ssrhip_sample: K=%d", a->K);
-  SSR_REQUIRE(a->card > 0 && a->card <= 64 * WPC * MAXE, "ssrhip_sample: card=%d exceeds %d", a->card, 64 * WPC * MAXE);
+              "%s: null argument", who);
+  SSR_REQUIRE(a->K >= 1 && a->K <= SSRHIP_MAX_CODEBOOKS, "%s: K=%d", who, a->K);
+  SSR_REQUIRE(a->card > 0 && a->card <= 64 * WPC * MAXE, "%s: card=%d exceeds %d", who, a->card, 64 * WPC * MAXE);
   if (a->embed.out) SSR_REQUIRE(a->embed.audio_emb && a->embed.pe && a->embed.D % 4 == 0 && a->embed.K == a->K && a->embed.card == a->card,
-                                "ssrhip_sample: fused embed needs audio_emb, pe, matching K/card");
+                                "%s: fused embed needs audio_emb, pe, matching K/card", who);
   const char* e = getenv("SSRHIP_SAMPLE_RADIX");          // test knob: always take the radix-select path (value baked in at graph capture)
-  hipLaunchKernelGGL(sample_kernel, dim3(a->n_utt), dim3(SAMPLE_THREADS), 0, (hipStream_t)stream, *a, (e && atoi(e)) ? 1 : 0);
+  const int force_radix = (e && atoi(e)) ? 1 : 0;
+  if (logp) hipLaunchKernelGGL(sample_kernel<true>, dim3(a->n_utt), dim3(SAMPLE_THREADS), 0, (hipStream_t)stream, *a, force_radix, logp);
+  else hipLaunchKernelGGL(sample_kernel<false>, dim3(a->n_utt), dim3(SAMPLE_THREADS), 0, (hipStream_t)stream, *a, force_radix, (float*)nullptr);
   SSR_LAUNCH_CHECK();
   return 0;
+}
+
+}  // namespace
+
+extern "C" int ssrhip_sample(const ssrhip_sample_args* a, ssrhip_stream_t stream) { return sample_launch(a, nullptr, stream, "ssrhip_sample"); }
+
+extern "C" int ssrhip_sample_logp(const ssrhip_sample_args* a, float* logp, ssrhip_stream_t stream) {
+  SSR_REQUIRE(logp, "ssrhip_sample_logp: null logp buffer");
+  return sample_launch(a, logp, stream, "ssrhip_sample_logp");
 }

@@ -100,6 +100,7 @@ struct ssrhip_lm {
   const int32_t* n_shared = nullptr;
   int group_members = 0;        // rows per chunk the caller's chunks are cut for (ssrhip_lm_set_group_members; set with the arrays)
   int group_launches = 0;       // attention launches of the last enqueued step that ran ssrhip_attn_rows_group (ssrhip_lm_group_launches)
+  float* logp = nullptr;        // the step ends in ssrhip_sample_logp with this buffer of the caller's (ssrhip_lm_set_logprobs; null = off)
 };
 
 namespace {
@@ -568,7 +569,7 @@ int enqueue_step(ssrhip_lm* lm, hipStream_t s, Timer* tm) {
   const ssrhip_gemv_args h2 = sh.head2_args();
   STEP_CALL(CAT_GEMV, gemv_call(h2, pk_h2));
   const ssrhip_sample_args sa = sh.sample_args();
-  STEP_CALL(CAT_SAMPLE, ssrhip_sample(&sa, s));
+  STEP_CALL(CAT_SAMPLE, lm->logp ? ssrhip_sample_logp(&sa, lm->logp, s) : ssrhip_sample(&sa, s));
   if (!tm || tm->only < 0) { lm->pk_launches = n_pk; lm->pk_pair_launches = n_wp; lm->pair4_launches = n_p4; lm->pair4_pk_launches = n_p4pk; lm->kv16_launches = n_kv16; lm->group_launches = n_group; }   // (a category-timing pass enqueues only part of a step)
   return 0;
 }
@@ -784,6 +785,15 @@ extern "C" int ssrhip_lm_set_kv16_small(ssrhip_lm* lm, float* land, const int32_
   lm->land_pos = land_pos;
   return 0;
 }
+
+// Per-token log-probabilities (DESIGN.md Part I.27): with a buffer set, enqueue_step ends in ssrhip_sample_logp. Null: off.
+extern "C" int ssrhip_lm_set_logprobs(ssrhip_lm* lm, float* logp) {
+  SSR_REQUIRE(lm, "ssrhip_lm_set_logprobs: null engine");
+  SSR_REQUIRE(!lm->exec, "ssrhip_lm_set_logprobs: the decode step of this engine is already captured (call it before the first ssrhip_lm_decode)");
+  lm->logp = logp;
+  return 0;
+}
+extern "C" int ssrhip_lm_logprobs(const ssrhip_lm* lm) { return (lm && lm->logp) ? 1 : 0; }
 
 extern "C" int ssrhip_lm_set_prompt_groups(ssrhip_lm* lm, const int32_t* chunk_head, const int32_t* n_shared) {
   SSR_REQUIRE(lm, "ssrhip_lm_set_prompt_groups: null engine");

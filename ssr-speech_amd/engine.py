@@ -1126,7 +1126,8 @@ class DecodeEngine:
                  stream_w16: Optional[bool] = None, stream_wt16: Optional[bool] = None, stream_wt32: Optional[bool] = None,
                  kv_dtype: Optional[str] = None, share_prompt: Optional[bool] = None, stream_w8: Optional[bool] = None,
                  pair_w16: Optional[bool] = None, pair_w8: Optional[bool] = None, stream_wt8: Optional[bool] = None,
-                 kv16_small: Optional[bool] = None, pair4: Optional[bool] = None, pair4_pk: Optional[bool] = None):
+                 kv16_small: Optional[bool] = None, pair4: Optional[bool] = None, pair4_pk: Optional[bool] = None,
+                 logprobs: bool = False):
         """max_seq: longest sequence (text + audio positions) any ONE row may reach; pool_pages: physical KV pages shared by all
         rows (default rows x pages-per-row, the no-sharing worst case; a batch of short and long utterances needs only the sum
         of their own page counts). pair_mode (2-row engines; include/ssrhip.h ssrhip_lm_buffers): 0 = pair launches if this engine
@@ -1168,7 +1169,11 @@ class DecodeEngine:
         `SSRHIP_GEMV_PAIR4` (read here; unset = PAIR4_DEFAULT) does not start with '0'. Same tokens, bit for bit, either way.
         pair4_pk (4-row engines that stream w16 or w8; `resolve_pair4_pk`, DESIGN.md Part I.26): the step runs the 4-row pair launches over
         the packed stream (include/ssrhip.h ssrhip_lm_set_pair4_pk) if the library lets this engine pair; None = on when
-        `SSRHIP_GEMV_PAIR4_PK` (read here; unset = PAIR4_PK_DEFAULT) does not start with '0'. Same tokens, bit for bit, either way."""
+        `SSRHIP_GEMV_PAIR4_PK` (read here; unset = PAIR4_PK_DEFAULT) does not start with '0'. Same tokens, bit for bit, either way.
+        logprobs (DESIGN.md Part I.27; no environment switch): the step's sampler also writes the log-probability of every token it
+        generates (include/ssrhip.h ssrhip_sample_logp; NaN where the state machine decided the token) into an fp32 buffer beside
+        `generated`, read with `logprobs()`; `run_queue` leaves one array per job in `queue_logprobs`. Same tokens, bit for bit; at every
+        row count. False: no buffer, and the step this engine ran before."""
         self.lib = _lib.lib()
         self.a = arena
         dev = arena.device
@@ -1267,6 +1272,9 @@ class DecodeEngine:
         self.cfg_dev = torch.zeros(n_utt * C.sizeof(_lib.SamplerCfg), dtype=torch.uint8, device=dev)
         self.state_dev = torch.zeros(n_utt * C.sizeof(_lib.SamplerState), dtype=torch.uint8, device=dev)
         self.generated = torch.zeros(n_utt, max_steps, K, **i32)
+        self.want_logprobs = bool(logprobs)
+        self.logp = torch.full((n_utt, max_steps, K), float("nan"), **f32) if self.want_logprobs else None
+        self.queue_logprobs: List[np.ndarray] = []   # run_queue with logprobs: float32 [n_steps, K] per job, in job order
         # ONE persistent buffer for host-drawn sampling noise: its pointer is baked into the captured graph, so generations
         # with / without host noise reuse the same context (ssrhip_sampler_cfg.use_noise selects per utterance)
         self.noise = torch.empty(n_utt, max_steps, K, arena.card, **f32)
@@ -1344,6 +1352,8 @@ class DecodeEngine:
             _lib.check(self.lib.ssrhip_lm_set_group_members(ctx, self.group_members), "ssrhip_lm_set_group_members")
         if self.prefill_planes == 1:              # the count travels with the arena's buffers (also for the two-phase admission's prefill)
             _lib.check(self.lib.ssrhip_lm_set_prefill_w1(ctx, 1), "ssrhip_lm_set_prefill_w1")
+        if self.want_logprobs:                    # the step ends in ssrhip_sample_logp; the buffer's pointer travels with the captured step
+            _lib.check(self.lib.ssrhip_lm_set_logprobs(ctx, self.logp.data_ptr()), "ssrhip_lm_set_logprobs")
         why = C.create_string_buffer(256)
         self.pairing = bool(self.lib.ssrhip_lm_pairing(ctx, why, 256))
         self.pairing_why = why.value.decode(errors="replace")
@@ -1824,6 +1834,16 @@ class DecodeEngine:
         self.check_pairs()
         return out
 
+    def logprobs(self, u: int, n: int, start: int = 0) -> np.ndarray:
+        """The log-probabilities of the generated steps [start, n) of slot u as float32 [n - start, K], NaN where the state machine
+        decided the token (include/ssrhip.h ssrhip_sample_logp) — `tokens()` for an engine built with logprobs=True, after the same
+        pair-launch check."""
+        if self.logp is None:
+            raise RuntimeError("this engine was built without logprobs=True: its step does not write log-probabilities")
+        out = self.logp[u, start:n].cpu().numpy()
+        self.check_pairs()
+        return out
+
     def run_to_completion(self, chunk: int = 16, use_graph: bool = True, max_total: Optional[int] = None,
                           feed: Optional[TorchCpuNoiseFeed] = None, on_chunk=None):
         """Decode in chunks of `chunk` steps until every utterance reports done (the flags are polled once per chunk).
@@ -1915,6 +1935,7 @@ class DecodeEngine:
         list `run_queue` returns; the generator has to be consumed to its end (the noise feed is put back there)."""
         n_jobs = len(jobs)
         results: List[Optional[tuple]] = [None] * n_jobs
+        self.queue_logprobs = [None] * n_jobs if self.want_logprobs else []   # filled where the tokens are collected, in job order
         if n_jobs == 0:
             return results
         slot_job: List[Optional[int]] = [None] * self.n_utt
@@ -1998,6 +2019,8 @@ class DecodeEngine:
                 j = slot_job[u]
                 cap_j = min(int(jobs[j]["cap"]), self.max_steps)
                 if states[u].done or local[u] >= cap_j:
+                    if self.want_logprobs:                      # the same rows as the tokens, at the same poll, before a refill's start
+                        self.queue_logprobs[j] = self.logprobs(u, int(states[u].n_steps))
                     results[j] = self._collect(u, states[u], cap_j)
                     slot_job[u] = None
             # the slots whose prefill was started one poll ago join the batch now (their prefill had a whole chunk to finish)

@@ -97,13 +97,16 @@ def render_many(audio_tokenizer, results: Sequence[tuple], scale, audio_fns, use
 @torch.no_grad()
 def inference_samples(model, model_args, phn2num, text_tokenizer, audio_tokenizer, audio_fn, prompt_text, target_text, mask_interval,
                       cfg_coef, cfg_stride, aug_text, aug_context, use_watermark, tts, device, decode_config, seeds,
-                      share_prompt: bool = False):
+                      share_prompt: bool = False, return_scores: bool = False):
     """`--sample_batch_size N` in one pass: the N samples of ONE utterance (seeds `seeds[i]`) decoded in lock-step through
     `SSR_Speech.inference_batch`, so the weights stream once per step for all of them (the reference loops them one after the
     other, `inference_v2.py:331-358`). Sample i is bit-identical to `inference_one_sample` called after
     `torch.manual_seed(seeds[i])`: the prompt is encoded once (it is the same for every sample) and every sample keeps its
     own RNG stream. `seeds` must be consecutive integers. Returns the list of waveforms [1, 1, n_i].
-    `share_prompt=True` (opt-in): the samples share one prefill and the prompt's KV pages (`SSR_Speech.inference_batch`); same waveforms."""
+    `share_prompt=True` (opt-in): the samples share one prefill and the prompt's KV pages (`SSR_Speech.inference_batch`); same waveforms.
+    `return_scores=True` (opt-in, DESIGN.md Part I.27): returns `(waveforms, scores)`, the same waveforms and, for sample i,
+    scores[i] = dict(seed, mean_logprob, total_logprob, count, frames) — how probable the model found the tokens it drew for that sample
+    (`layout.TokenLogprobs` of `inference_batch(return_logprobs=True)`; `frames` = generated frames of the sample), to rank the samples by."""
     seeds = [int(s) for s in seeds]
     assert seeds == list(range(seeds[0], seeds[0] + len(seeds))), "seeds must be consecutive (seed + sample index)"
     K = int(model_args.n_codebooks)
@@ -113,11 +116,17 @@ def inference_samples(model, model_args, phn2num, text_tokenizer, audio_tokenize
     t0 = time.perf_counter()
     results = model.inference_batch([one] * len(seeds), top_k=decode_config["top_k"], top_p=decode_config["top_p"],
                                     temperature=decode_config["temperature"], stop_repetition=decode_config["stop_repetition"],
-                                    cfg_coef=cfg_coef, cfg_stride=cfg_stride, aug_text=aug_text, seed=seeds[0], share_prompt=share_prompt)
+                                    cfg_coef=cfg_coef, cfg_stride=cfg_stride, aug_text=aug_text, seed=seeds[0], share_prompt=share_prompt,
+                                    return_logprobs=bool(return_scores))
     log.info("AR decode of %d samples in lock-step: %.3f s", len(seeds), time.perf_counter() - t0)
     # all samples through the codec in one ragged pass (they differ in length; each keeps its own halo): same waveforms as one
     # `_render` per sample, which is what the reference's loop does (inference_v2.py:331-358)
-    return render_many(audio_tokenizer, results, scale, audio_fn, bool(use_watermark), bool(tts))
+    waves = render_many(audio_tokenizer, [r[:4] for r in results], scale, audio_fn, bool(use_watermark), bool(tts))
+    if not return_scores:
+        return waves
+    scores = [dict(seed=s_, mean_logprob=float(r[4].mean), total_logprob=float(r[4].total), count=int(r[4].count), frames=int(r[1].sum()))
+              for s_, r in zip(seeds, results)]
+    return waves, scores
 
 
 @torch.no_grad()

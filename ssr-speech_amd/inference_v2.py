@@ -9,6 +9,9 @@ Outputs follow the reference: `{output_dir}/{savename}_new_seed{seed+num}.wav` (
 from __future__ import annotations
 
 import argparse
+import json
+import logging
+import math
 import os
 import random
 import shutil
@@ -68,6 +71,10 @@ EXTRA_FLAGS = [
     ("--stream_dir", dict(type=str, default=None,
                           help="--tts with --sample_batch_size N: stream the lock-step samples (inference_samples_stream) and append each "
                                "sample's chunks, as they arrive, to DIR/{savename}_new_seed{seed}.f32 (raw float32 samples, one file per sample)")),
+    ("--rank_samples", dict(action="store_true",
+                            help="score the --sample_batch_size samples by the log-probability the model gave the tokens it drew (lock-step "
+                                 "path, inference_samples(return_scores=True)): the same wavs, plus {savename}_scores.json — one record per "
+                                 "sample (seed, mean_logprob, total_logprob, count, frames), best mean_logprob first")),
     ("--sampling_rng", dict(type=str, choices=["torch_cpu", "philox"], default="torch_cpu",
                             help="philox: sampled runs take their multinomial noise from a counter-based generator on the device, keyed by "
                                  "the seed (SSR_Speech.set_sampling_rng): no host draw, other tokens than torch_cpu; torch_cpu (default): "
@@ -140,6 +147,14 @@ def build_parser() -> argparse.ArgumentParser:
     for flag, kw in REFERENCE_FLAGS + EXTRA_FLAGS:
         p.add_argument(flag, **kw)
     return p
+
+
+def write_scores(path: str, scores) -> None:
+    """--rank_samples: the samples' scores as JSON, best mean_logprob first (a sample without a drawn token, NaN, last)."""
+    ranked = sorted(scores, key=lambda r: (math.isnan(r["mean_logprob"]), 0.0 if math.isnan(r["mean_logprob"]) else -r["mean_logprob"]))
+    with open(path, "w") as f:
+        json.dump([{k: (None if isinstance(v, float) and math.isnan(v) else v) for k, v in r.items()} for r in ranked], f, indent=1)   # NaN -> null
+    logging.getLogger(__name__).info("ranked %d samples by mean log-probability: best seed %d (%.4f) -> %s", len(ranked), ranked[0]["seed"], ranked[0]["mean_logprob"], path)
 
 
 def parse_args(argv=None):
@@ -332,14 +347,19 @@ def main(argv=None):
     common = (model, argparse.Namespace(**config), phn2num, text_tokenizer, audio_tokenizer, audio_fn, prompt_text, target_text, mask_interval,
               args.cfg_coef, args.cfg_stride, args.aug_text, args.aug_context, args.use_watermark, args.tts, device, decode_config)
     seeds = [args.seed + num for num in range(args.sample_batch_size)]               # :331-332: sample `num` runs under seed + num
+    if args.stream_dir is not None and args.rank_samples:
+        raise SystemExit("--rank_samples scores the samples of the lock-step path; the streamed path (--stream_dir) has no scores")
     if args.stream_dir is not None:
         # the samples in ONE lock-step decode, their audio written while they decode (--tts only; DESIGN.md Part I.16)
         seed_everything(seeds[-1])
         waves = _stream_samples_to(args.stream_dir, args.savename, seeds, inference_samples_stream(*common, seeds=seeds))
-    elif len(seeds) > 1:
+    elif len(seeds) > 1 or args.rank_samples:
         # all samples of the utterance in ONE lock-step decode (same outputs as the reference's sequential loop :331-358)
         seed_everything(seeds[-1])
-        waves = inference_samples(*common, seeds=seeds, share_prompt=bool(args.share_prompt))
+        waves = inference_samples(*common, seeds=seeds, share_prompt=bool(args.share_prompt), return_scores=bool(args.rank_samples))
+        if args.rank_samples:
+            waves, scores = waves
+            write_scores(os.path.join(args.output_dir, f"{args.savename}_scores.json"), scores)
     else:
         seed_everything(seeds[0])
         waves = [inference_one_sample(*common)]

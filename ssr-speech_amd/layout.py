@@ -7,7 +7,8 @@ Restates, vectorised:
   undelay       <- revert_pattern_sequence              (models/ssr.py:438-464)
   assemble      <- the tail of inference()              (models/ssr.py:776-812)
   FrameAssembler   `assemble` in increments: the frames of the result that are already final while the decode loop still runs
-and `pack_prefill_rows`, the flattened [text || audio] rows every prefill launch of the library reads.
+and `pack_prefill_rows`, the flattened [text || audio] rows every prefill launch of the library reads; `assemble_logprobs` / `TokenLogprobs`:
+`assemble` for the per-token log-probabilities of an engine built with logprobs=True.
 """
 from __future__ import annotations
 
@@ -129,6 +130,48 @@ def assemble(y: np.ndarray, spans: Sequence[np.ndarray], non_mask_intervals, arg
         masks.append((tmp, tmp + le - ls))
         marks += [0] * (le - ls)
     return np.concatenate(res, 1), np.asarray(marks, dtype=np.int64), masks, list(non_mask_intervals)
+
+
+class TokenLogprobs(NamedTuple):
+    """Per-token log-probabilities of one generated utterance (DESIGN.md Part I.27), NumPy arrays on the host. A value is the natural-log
+    probability of the generated token under the softmax of the logits the sampler drew from — after the CFG combine, the special-token
+    edits, the silence penalty and the temperature, before top-k / top-p — and NaN where the state machine, not the draw, decided the
+    token (start-of-span delay, eog cascade, stop rule).
+      steps  float32 [n_steps, K]: step order, delay pattern in place;
+      frames float32 [1, K, T]: aligned with the `res` of the same result (delay pattern undone, every span where `assemble` puts it,
+             the `aug_context` crop applied); NaN at kept frames. Every finite entry of `steps` is in `frames` with one exception per
+             span: an eog that codebook 0 DREW (no stop rule fired) has a value in `steps`, and sits in the eog column `assemble` drops;
+      count / total / mean: how many entries of `steps` are not NaN, their sum (accumulated in fp64), total / count (NaN when count == 0)
+             — over `steps`, so a drawn eog is counted."""
+    steps: np.ndarray
+    frames: np.ndarray
+    count: int
+    total: float
+    mean: float
+
+
+def assemble_logprobs(steps: np.ndarray, span_end: Sequence[int], y_len: int, non_mask_intervals, out_len: int = 0) -> TokenLogprobs:
+    """`assemble` for the per-step log-probabilities: steps [n_steps, K] in step order, span_end[i] = the step count at which span i
+    ended, y_len = T of the `y` that `assemble` gets. What `assemble` does to the tokens of a span (delay pattern undone, eog column
+    dropped) is done to their values; kept frames are NaN; `out_len` frames are dropped in front (the `aug_context` crop)."""
+    steps = np.ascontiguousarray(np.asarray(steps, dtype=np.float32))
+    K = steps.shape[1]
+    nan = lambda n: np.full((K, n), np.nan, dtype=np.float32)
+    ends = [0] + [int(e) for e in span_end]
+    parts = []
+    for i, (s, e) in enumerate(non_mask_intervals[: len(ends) - 1]):
+        pat = steps[ends[i]:ends[i + 1]].T                  # [K, S]
+        T = max(pat.shape[1] - (K - 1), 0)
+        gen = np.stack([pat[q, q:q + T] for q in range(K)])[:, :-1] if T else nan(0)
+        parts += [nan(e - s), gen]
+    ls, le = non_mask_intervals[-1]
+    if y_len != le + 1:                 # `assemble`'s closing segment, quirk included
+        parts.append(nan(le - ls))
+    frames = np.concatenate(parts, 1)[None, :, int(out_len):]
+    ok = ~np.isnan(steps)
+    count = int(ok.sum())
+    total = float(steps[ok].astype(np.float64).sum())
+    return TokenLogprobs(steps, np.ascontiguousarray(frames), count, total, total / count if count else float("nan"))
 
 
 class FrameIncrement(NamedTuple):

@@ -28,6 +28,8 @@ from ..engine import (DEFAULT_GROUP_ROWS, KV_DTYPES, MAX_ROWS, WEIGHT_DTYPES, De
                       TorchCpuNoiseFeed, W16_STREAMS, resolve_kv16_small, resolve_kv_dtype, resolve_pair4, resolve_pair4_pk, resolve_sampling_rng, resolve_share_prompt, resolve_w16_pair, resolve_w16_stream, resolve_w8_pair, resolve_w8_stream)
 from ..weights import lm_param_specs
 
+TokenLogprobs = LY.TokenLogprobs          # the fifth element of `inference(..., return_logprobs=True)` results
+
 
 def _set_param(root: nn.Module, dotted: str, p: nn.Parameter):
     mod = root
@@ -295,7 +297,7 @@ class SSR_Speech(nn.Module):
 
     # ------------------------------------------------------------------ engine management
     def _get_engine(self, n_utt: int, use_cfg: bool, need_seq: int, need_steps: int, need_pages: Optional[int] = None,
-                    share_prompt: bool = False) -> DecodeEngine:
+                    share_prompt: bool = False, logprobs: bool = False) -> DecodeEngine:
         dev = self.device
         if dev.type != "cuda":
             raise RuntimeError("ssr_speech_amd.SSR_Speech.inference needs the model on a ROCm GPU (model.to('cuda')); "
@@ -332,12 +334,12 @@ class SSR_Speech(nn.Module):
         # ... and SSRHIP_GEMV_PAIR4_PK's for the 4-row step over a packed stream
         pair4_pk = resolve_pair4_pk(rows, resolve_w16_stream(W16_STREAMS[0], rows, self._arena.weight_dtype, None, os.environ),
                                     resolve_w8_stream(rows, self._arena.weight_dtype, None, os.environ), 0, None, os.environ)
-        for (k_utt, k_cfg, k_seq, k_steps, k_dbg, k_pool, k_order, k_share, k_wp, k_wp8, k_kvs, k_p4, k_p4pk), e in self._engines.items():
-            if (k_utt, k_cfg, k_dbg, k_order, k_share, k_wp, k_wp8, k_kvs, k_p4, k_p4pk) == (n_utt, use_cfg, bool(self.debug_logits), order_key, share, w16_pair, w8_pair, kv16_small, pair4, pair4_pk) and k_seq >= cap_seq and k_steps >= cap_steps \
+        for (k_utt, k_cfg, k_seq, k_steps, k_dbg, k_pool, k_order, k_share, k_wp, k_wp8, k_kvs, k_p4, k_p4pk, k_lp), e in self._engines.items():
+            if (k_utt, k_cfg, k_dbg, k_order, k_share, k_wp, k_wp8, k_kvs, k_p4, k_p4pk, k_lp) == (n_utt, use_cfg, bool(self.debug_logits), order_key, share, w16_pair, w8_pair, kv16_small, pair4, pair4_pk, bool(logprobs)) and k_seq >= cap_seq and k_steps >= cap_steps \
                     and (k_pool >= need if order_key is None else k_pool == min(rows * (cap_seq // 128), ((need + 7) // 8) * 8)):
                 return e
         pool = min(rows * (cap_seq // 128), ((need + 7) // 8) * 8)
-        key = (n_utt, use_cfg, cap_seq, cap_steps, bool(self.debug_logits), pool, order_key, share, w16_pair, w8_pair, kv16_small, pair4, pair4_pk)
+        key = (n_utt, use_cfg, cap_seq, cap_steps, bool(self.debug_logits), pool, order_key, share, w16_pair, w8_pair, kv16_small, pair4, pair4_pk, bool(logprobs))
         for e in self._engines.values():         # one engine (KV pool) resident at a time
             e.close()
         self._engines = {}
@@ -345,7 +347,7 @@ class SSR_Speech(nn.Module):
         if self.page_order is not None:          # tests: a caller-chosen hand-out order of the physical pages
             order = [p for p in self.page_order if p < pool] if len(self.page_order) >= pool else None
         eng = DecodeEngine(self._arena, n_utt, use_cfg, cap_seq, cap_steps, debug_logits=self.debug_logits, pool_pages=pool, page_order=order,
-                           kv_dtype=kv_dtype, share_prompt=share, kv16_small=kv16_small)
+                           kv_dtype=kv_dtype, share_prompt=share, kv16_small=kv16_small, logprobs=bool(logprobs))
         self._engines[key] = eng
         return eng
 
@@ -465,22 +467,35 @@ class SSR_Speech(nn.Module):
         uncond_x: Optional[torch.Tensor] = None,
         max_new_steps: Optional[int] = None,
         use_graph: bool = True,
+        return_logprobs: bool = False,
     ):
         """Same contract as the reference's `SSR_Speech.inference` (models/ssr.py:504-812).
 
         `kvcache` is accepted and ignored (the engine always keeps a paged KV cache; the reference
         produces identical tokens for kvcache 0/1).  Keyword-only extras (not in the reference):
         `noise` [steps,K,card] Exp(1) draws replacing the multinomial generator draw, `uncond_x`
-        overriding the random CFG text (ssr.py:574), `max_new_steps` (tests), `use_graph`."""
+        overriding the random CFG text (ssr.py:574), `max_new_steps` (tests), `use_graph`, and
+        `return_logprobs` (DESIGN.md Part I.27): the result is the same 4-tuple plus a fifth element,
+        `layout.TokenLogprobs` — the log-probability of every generated token, per step and aligned
+        with `res`, NaN where the state machine decided the token. Same tokens, bit for bit; the
+        decode engine of such a call is built with `logprobs=True` (a model that never asks never
+        builds one). The streaming iterators and `dp.generate` do not take the keyword."""
         run = self._begin_inference(x, x_lens, prompt_x, prompt, y, mask_interval, top_k, top_p, temperature, stop_repetition, silence_tokens,
-                                    cfg_coef, cfg_stride, aug_text, aug_context, cfg_pretrained, noise, uncond_x, max_new_steps)
+                                    cfg_coef, cfg_stride, aug_text, aug_context, cfg_pretrained, noise, uncond_x, max_new_steps,
+                                    logprobs=return_logprobs)
         eng = run["eng"]
         states = eng.run_to_completion(chunk=16, use_graph=use_graph, max_total=run["cap"], feed=run["feed"])
         st = states[0]
-        return self._end_inference(run, st, eng.tokens(0, int(st.n_steps)))
+        n = int(st.n_steps)
+        out = self._end_inference(run, st, eng.tokens(0, n))
+        if not return_logprobs or out is None:
+            return out
+        return out + (LY.assemble_logprobs(eng.logprobs(0, n), [st.span_end[i] for i in range(run["num_task"])], run["y_np"].shape[1], run["nmi"],
+                                           run["out_len"] if run["aug_context"] else 0),)
 
     def _begin_inference(self, x, x_lens, prompt_x, prompt, y, mask_interval, top_k, top_p, temperature, stop_repetition, silence_tokens,
-                         cfg_coef, cfg_stride, aug_text, aug_context, cfg_pretrained, noise, uncond_x, max_new_steps, before_start=None) -> dict:
+                         cfg_coef, cfg_stride, aug_text, aug_context, cfg_pretrained, noise, uncond_x, max_new_steps, before_start=None,
+                         logprobs: bool = False) -> dict:
         """Everything `inference` does before the decode loop (shared with `inference_stream`): argument checks, prompt layout, engine,
         prefill. `before_start(n)` is called ahead of the engine's first launch with the most frames the result can have. Returns what
         the loop and `_end_inference` need."""
@@ -531,7 +546,7 @@ class SSR_Speech(nn.Module):
         cap = max(10 * L + 2 - T0, 1) + num_task * (K + 1)
         if max_new_steps is not None:
             cap = min(cap, max_new_steps)
-        eng = self._get_engine(1, bool(aug_text), L + T0 + cap + 8, cap)
+        eng = self._get_engine(1, bool(aug_text), L + T0 + cap + 8, cap, logprobs=logprobs)
         knobs = DecodeKnobs(top_k=top_k, top_p=top_p, temperature=temperature, stop_repetition=stop_repetition,
                             silence_tokens=tuple(int(s) for s in silence_tokens), cfg_coef=cfg_coef, cfg_stride=cfg_stride,
                             use_cfg=bool(aug_text), text_len=L, n_spans=num_task, seed=int(torch.initial_seed()))
@@ -592,7 +607,7 @@ class SSR_Speech(nn.Module):
     def inference_batch(self, utterances, top_k: int = -100, top_p: float = 1.0, temperature: float = 1.0, stop_repetition: int = -1,
                         silence_tokens=(1388, 1898, 131), cfg_coef: float = 1.5, cfg_stride: int = 1, aug_text: bool = False,
                         seed: int = 0, first_index: int = 0, group: Optional[int] = None, use_graph: bool = True, refill: bool = True,
-                        indices: Optional[Sequence[int]] = None, share_prompt: bool = False):
+                        indices: Optional[Sequence[int]] = None, share_prompt: bool = False, *, return_logprobs: bool = False):
         """Several independent utterances decoded in lock-step so that one pass over the weights serves all of them
         (the reference is strictly batch-1: `assert y.shape[0] == 1`, ssr.py:559, and loops `--sample_batch_size`
         sequentially, inference_v2.py:331-333).
@@ -605,23 +620,27 @@ class SSR_Speech(nn.Module):
         `share_prompt=True` (opt-in, DESIGN.md Part I.15): utterances of the FIRST fill with equal text and prompt audio — the samples of
         one utterance — are prefilled once and share the prompt's KV pages (engine.DecodeEngine share_prompt); same results, bit for bit.
         Engines of <= 4 rows, or with a bf16 KV cache, run unshared without error.
+        `return_logprobs=True` (keyword-only, DESIGN.md Part I.27): every result gets a fifth element, the `layout.TokenLogprobs` of that
+        utterance, as in `inference`; same tokens. `inference_batch_stream` and `dp.generate` do not take the keyword.
         Returns a list of the same 4-tuples `inference` returns."""
         setup = self._begin_batch(utterances, top_k, top_p, temperature, stop_repetition, silence_tokens, cfg_coef, cfg_stride, aug_text,
-                                  seed, first_index, indices, group, share_prompt)
+                                  seed, first_index, indices, group, share_prompt, logprobs=return_logprobs)
         if setup is None:
             return []
         jobs, eng, n_slots = setup["jobs"], setup["eng"], setup["n_slots"]
         greedy = top_k == 1
         if refill:
             outs = eng.run_queue(jobs, chunk=16, use_graph=use_graph, sampling=not greedy)
+            lps = list(eng.queue_logprobs)
         else:
-            outs = []
+            outs, lps = [], []
             for g0 in range(0, len(jobs), n_slots):
                 outs += eng.run_queue(jobs[g0: g0 + n_slots], chunk=16, use_graph=use_graph, sampling=not greedy)
-        return self._batch_results(setup, outs)
+                lps += list(eng.queue_logprobs)
+        return self._batch_results(setup, outs, lps if return_logprobs else None)
 
     def _begin_batch(self, utterances, top_k, top_p, temperature, stop_repetition, silence_tokens, cfg_coef, cfg_stride, aug_text,
-                     seed, first_index, indices, group, share_prompt) -> Optional[dict]:
+                     seed, first_index, indices, group, share_prompt, logprobs: bool = False) -> Optional[dict]:
         """What `inference_batch` and `inference_batch_stream` do before the decode loop: the job list (per-utterance RNG stream, text rows,
         prompt layout, step cap), the KV page demand and the engine lookup. None for an empty list."""
         K = self.args.n_codebooks
@@ -661,11 +680,12 @@ class SSR_Speech(nn.Module):
             n_slots += 1
         # KV pool: at most n_slots utterances are resident at a time -> the n_slots largest page demands bound the concurrent need
         pages_sum = sum(sorted(page_need, reverse=True)[:n_slots])
-        eng = self._get_engine(n_slots, bool(aug_text), seq_max, cap_max + 16, need_pages=pages_sum, share_prompt=share_prompt)
+        eng = self._get_engine(n_slots, bool(aug_text), seq_max, cap_max + 16, need_pages=pages_sum, share_prompt=share_prompt, logprobs=logprobs)
         return dict(jobs=jobs, metas=metas, n_slots=n_slots, eng=eng, cap_max=cap_max)
 
-    def _batch_results(self, setup: dict, outs) -> list:
-        """The 4-tuples `inference_batch` returns, from what `DecodeEngine.run_queue` returns."""
+    def _batch_results(self, setup: dict, outs, lps=None) -> list:
+        """The 4-tuples `inference_batch` returns, from what `DecodeEngine.run_queue` returns; with `lps` (the engine's `queue_logprobs`,
+        one array per job) each gets its `TokenLogprobs` as a fifth element."""
         jobs, metas, dev = setup["jobs"], setup["metas"], self.device
         results = []
         for j, (st, gen) in enumerate(outs):
@@ -675,14 +695,17 @@ class SSR_Speech(nn.Module):
             ends = [0] + [st.span_end[i] for i in range(num_task)]
             spans = [gen[ends[i]:ends[i + 1]] for i in range(num_task)]
             res, marks, masks, nmi_out = LY.assemble(y_np, spans, nmi, self.args)
-            results.append((torch.from_numpy(res).unsqueeze(0).to(dev), torch.from_numpy(marks).unsqueeze(0), masks, nmi_out))
+            out = (torch.from_numpy(res).unsqueeze(0).to(dev), torch.from_numpy(marks).unsqueeze(0), masks, nmi_out)
+            if lps is not None:
+                out += (LY.assemble_logprobs(lps[j], ends[1:], y_np.shape[1], nmi),)
+            results.append(out)
         return results
 
     @torch.no_grad()
     def inference_batch_stream(self, utterances, top_k: int = -100, top_p: float = 1.0, temperature: float = 1.0, stop_repetition: int = -1,
                                silence_tokens=(1388, 1898, 131), cfg_coef: float = 1.5, cfg_stride: int = 1, aug_text: bool = False,
                                seed: int = 0, first_index: int = 0, use_graph: bool = True, indices: Optional[Sequence[int]] = None,
-                               *, bins: Optional[int] = None, before_start=None) -> "BatchInferenceStream":
+                               *, bins: Optional[int] = None, before_start=None, return_logprobs: bool = False) -> "BatchInferenceStream":
         """`inference_batch` of ONE fixed lock-step group that hands the frames out while the decode loop still runs (DESIGN.md Part I.16).
         Zero-shot TTS utterances only (one generated span that ends the utterance, behind one kept interval), `n_utt x rows <= MAX_ROWS`,
         no refill; anything else is a ValueError raised before any launch. Same parity contract as `inference_batch`.
@@ -693,7 +716,11 @@ class SSR_Speech(nn.Module):
         exactly the list `inference_batch` returns. Nothing runs before the first `next()`.
         `bins`: ids outside [0, bins) are an error (default: `audio_vocab_size`). `before_start(info)` is called ahead of the engine's first
         launch with dict(n_utt, K, prompt_lens, max_new_frames); it may return the int32 device buffer to gather into
-        (`BatchDecodeStream.codes`), else the stream allocates its own."""
+        (`BatchDecodeStream.codes`), else the stream allocates its own.
+        `return_logprobs` is `inference_batch`'s keyword, here for signature parity only (this signature follows `inference_batch`'s) and
+        not served: True is a ValueError naming the call to use instead. Serve it whole or not at all."""
+        if return_logprobs:
+            raise ValueError("the batched stream hands out frames, not log-probabilities: use inference_batch(..., return_logprobs=True)")
         return BatchInferenceStream(self, utterances, dict(top_k=top_k, top_p=top_p, temperature=temperature, stop_repetition=stop_repetition,
                                                            silence_tokens=silence_tokens, cfg_coef=cfg_coef, cfg_stride=cfg_stride,
                                                            aug_text=aug_text, seed=seed, first_index=first_index, indices=indices),

@@ -44,6 +44,10 @@ Pair launches of the 4-row step over the packed streams (DESIGN.md Part I.26; `S
 A lower-case `kv16_small=1` (DESIGN.md Part I.23; 1, 2 or 4 rows) builds the arm's engine with kv_dtype="bf16", kv16_small=True: the 2-byte
 cache behind the landing cache of the split-KV step (`kv16 launches` its counter, `attn` its per-launch time), under any weight stream:
   python tools/decode_ab.py --reps 4 --warmup 180 --steps 100 fp32: fp32_kv16:kv16_small=1 e4m3_pair:weight_dtype=e4m3,SSRHIP_GEMV_W8_PAIR=1 e4m3_pair_kv16:weight_dtype=e4m3,SSRHIP_GEMV_W8_PAIR=1,kv16_small=1
+A lower-case `logprobs=1` (DESIGN.md Part I.27; any row count) builds the arm's engine with logprobs=True: the step's sampler launch is
+ssrhip_sample_logp (`sample` its per-launch time; the arm also prints how many log-probabilities of utterance 0 are not NaN, and their mean):
+  python tools/decode_ab.py --reps 4 --warmup 180 --steps 100 default: logprobs:logprobs=1
+  python tools/decode_ab.py --utts 8 --reps 4 --warmup 180 --steps 100 default: logprobs:logprobs=1
 """
 import argparse
 import dataclasses
@@ -84,6 +88,7 @@ dtype_of = {name: d.pop("weight_dtype", "fp32") for name, d in variants}
 kv_of = {name: d.pop("kv_dtype", "fp32") for name, d in variants}
 small_of = {name: d.pop("kv16_small", "0") == "1" for name, d in variants}
 kv_of = {name: "bf16" if small_of[name] else kv for name, kv in kv_of.items()}
+logp_of = {name: d.pop("logprobs", "0") == "1" for name, d in variants}
 share_of = {name: d.pop("share_prompt", None) for name, d in variants}      # None: U utterances; "0" / "1": U samples of utterance 0
 all_knobs = sorted({k for _, d in variants for k in d})
 
@@ -112,7 +117,7 @@ for rep in range(a.reps):
         os.environ.update(knobs)
         U = utts_of[name]
         eng = DecodeEngine(arenas[dtype_of[name]], U, True, ((L + T0 + total + 8 + 1023) // 1024) * 1024, ((total + 255) // 256) * 256,
-                           kv_dtype=kv_of[name], share_prompt=share_of[name] == "1", kv16_small=True if small_of[name] else None)
+                           kv_dtype=kv_of[name], share_prompt=share_of[name] == "1", kv16_small=True if small_of[name] else None, logprobs=logp_of[name])
         rows_in = text_rows[:2 * U] if share_of[name] is None else [text_rows[r] if r % 2 else text_rows[0] for r in range(2 * U)]
         launch, ev = eng._launch_prefill, (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
 
@@ -147,6 +152,8 @@ for rep in range(a.reps):
         r["kv16"] = eng.kv16_launches_per_step
         r["group"] = eng.group_launches_per_step
         r["pages"] = eng.pages.n_pages - eng.pages.n_free
+        lp = eng.logprobs(0, n_done) if logp_of[name] else np.full((0, 4), np.nan)
+        r["logp"] = f"{int((~np.isnan(lp)).sum())} of {lp.size} finite, mean {np.nanmean(lp) if lp.size else float('nan'):.4f}"
         r["ms"].append(ms)
         r["gemv"].append(eng.time_category("gemv", 50)[0])
         r["attn"].append(eng.time_category("attn", 50)[0])
@@ -172,4 +179,4 @@ for name, knobs in variants:
     print(f"{name:14s} {U:2d} utts x CFG = {2 * U:2d} rows  tok/s {4 * U / (statistics.median(r['ms']) * 1e-3):9.1f}  "
           f"ms/step min {min(r['ms']):.4f} med {statistics.median(r['ms']):.4f}  all {' '.join(f'{v:.4f}' for v in r['ms'])} | "
           f"gemv {min(r['gemv']):.3f} x {r['launches']['gemv']} attn {min(r['attn']):.3f} x {r['launches']['attn']} "
-          f"sample {min(r['sample']):.3f} x {r['launches']['sample']} us{same}   [{dtype_of[name]}, kv {kv_of[name]}, {' + '.join(f'{r[st.name]} {st.name}' for st in W16_STREAMS)} + {r['w8']} w8 + {r['wt8']} wt8 + {r['w16_pair']} w16 pair + {r['w8_pair']} w8 pair + {r['pair4']} pair4 + {r['pair4_pk']} pair4 pk + {r['kv16']} kv16 + {r['group']} group launches; kv16_small={int(small_of[name])}; first fill {r['prefill_rows']} rows in {min(r['prefill_ms']):.2f} ms, {r['pages']} KV pages in use; share_prompt={share_of[name]}; pairing={r['pairing']}; {' '.join(f'{k}={v}' for k, v in knobs.items()) or 'defaults'}]")
+          f"sample {min(r['sample']):.3f} x {r['launches']['sample']} us{same}   [{dtype_of[name]}, kv {kv_of[name]}, {' + '.join(f'{r[st.name]} {st.name}' for st in W16_STREAMS)} + {r['w8']} w8 + {r['wt8']} wt8 + {r['w16_pair']} w16 pair + {r['w8_pair']} w8 pair + {r['pair4']} pair4 + {r['pair4_pk']} pair4 pk + {r['kv16']} kv16 + {r['group']} group launches; kv16_small={int(small_of[name])}; logprobs={int(logp_of[name])} ({r['logp']}); first fill {r['prefill_rows']} rows in {min(r['prefill_ms']):.2f} ms, {r['pages']} KV pages in use; share_prompt={share_of[name]}; pairing={r['pairing']}; {' '.join(f'{k}={v}' for k, v in knobs.items()) or 'defaults'}]")
