@@ -205,172 +205,136 @@ def wt8_streamable(K: int) -> bool:
 WT8_DEFAULT = "0"
 
 
-def resolve_wt8_stream(rows: int, weight_dtype: str, requested: Optional[bool], env) -> bool:
-    """Does an engine of `rows` rows on an arena of `weight_dtype` run the e4m3 weight stream of the matrix-core step (DecodeEngine
-    stream_wt8)? requested None: on iff the arena is e4m3, the engine has 5..16 rows and `env["SSRHIP_GEMVM_W8"]` (unset: WT8_DEFAULT)
-    does not start with '0'. requested True: ValueError at <= 4 rows (it names stream_w8), at more than 16 rows, then for any other arena.
-    `env` is a mapping like os.environ; nothing else is read."""
-    if requested is None:
-        return weight_dtype == "e4m3" and 5 <= rows <= 16 and env.get("SSRHIP_GEMVM_W8", WT8_DEFAULT)[:1] != "0"
-    if not requested:
-        return False
-    if rows <= 4:
-        raise ValueError(f"stream_wt8 is the e4m3 weight stream of the 5..16-row step; an engine of {rows} rows takes stream_w8")
-    if rows > 16:
-        raise ValueError(f"stream_wt8: the e4m3 weight stream of the matrix-core step exists for 5..16 rows only (this engine has {rows} rows)")
-    if weight_dtype != "e4m3":
-        raise ValueError("stream_wt8 needs an arena built with weight_dtype='e4m3'")
-    return True
-
-
-# The two packed orders an arena can hold: (pack routine, which inner dimensions get a copy). A matrix's copy of order `o` lives in
-# lay[name + "_" + o] / arena.head{1,2}_<o>, under the flag arena._<o>_ready.
+# The packed orders an arena can hold: (pack routine, which inner dimensions get a copy). A matrix's copy of order `o` lives in
+# lay[name + "_" + o] / arena.head{1,2}_<o>, under the flag arena._<o>_ready. PACKED_ORDERS: 2-byte copies of the masters of a bf16-valued
+# arena; CODE_ORDERS: the 1-byte codes of an e4m3 arena (`e4m3_codes(master, scale)`, exact), read beside the arena's scales.
 PACKED_ORDERS = {"w16": (to_w16_order, w16_streamable), "wt16": (to_wt16_order, wt16_streamable)}
+CODE_ORDERS = {"w8": (to_w8_order, w16_streamable), "wt8": (to_wt8_order, wt8_streamable)}
 
 
-# One bf16 weight stream of the decode step per row range. `name` is the suffix of DecodeEngine's `stream_<name>` keyword and attribute, of
-# the C setter `ssrhip_lm_set_<name>` and of the counter `ssrhip_lm_<name>_launches`; [lo, hi] its rows (`rows`: as messages spell them);
-# `switch` the environment variable an engine built with `stream_<name>=None` reads and `default` what it means when unset; `order` the
-# packed order (PACKED_ORDERS) its kernels read; `only` what a refusal of more rows says.
-W16Stream = namedtuple("W16Stream", "name lo hi rows switch default order only")
-W16_STREAMS = (
-    W16Stream("w16", 1, 4, "<= 4", "SSRHIP_GEMV_W16", "1", "w16", "the bf16 weight stream exists for the <= 4-row decode step only"),
-    W16Stream("wt16", 5, 16, "5..16", "SSRHIP_GEMVM_W16", WT16_DEFAULT, "wt16", "the bf16 weight stream of the matrix-core step exists for 5..16 rows only"),
-    W16Stream("wt32", 17, 32, "17..32", "SSRHIP_GEMVM_W16", WT32_DEFAULT, "wt16", "the bf16 weight stream of the two-panel step exists for 17..32 rows only"),
+# One weight stream of the decode step per format and row range. `name` is the suffix of DecodeEngine's `stream_<name>` keyword and
+# attribute, of the C setter `ssrhip_lm_set_<name>` and of the counter `ssrhip_lm_<name>_launches`; [lo, hi] its rows (`rows`: as messages
+# spell them); `switch` the environment variable an engine built with `stream_<name>=None` reads and `default` what it means when unset;
+# `order` the packed order (PACKED_ORDERS / CODE_ORDERS) its kernels read; `only` what a refusal of more rows says; `fmt` the format word
+# of its messages, which is the arena dtype `resolve_stream` asks for; `arenas` the arena dtypes that can serve it — the 2-byte copies of
+# the matrix-core step serve every bf16-valued arena, the <= 4-row bf16 stream is the bf16 arena's own. Same tokens, bit for bit, as the
+# same arena's masters, for every entry. An engine takes one: the row ranges of one format are disjoint, a w8 and a w16 (wt8 and wt16)
+# request together are a ValueError, and a stream_wt8 that resolves on turns an unrequested wt16 off (the 1-byte stream takes the step).
+Stream = namedtuple("Stream", "name lo hi rows switch default order only fmt arenas")
+STREAMS = (
+    Stream("w16", 1, 4, "<= 4", "SSRHIP_GEMV_W16", "1", "w16", "the bf16 weight stream exists for the <= 4-row decode step only", "bf16", ("bf16",)),
+    Stream("wt16", 5, 16, "5..16", "SSRHIP_GEMVM_W16", WT16_DEFAULT, "wt16", "the bf16 weight stream of the matrix-core step exists for 5..16 rows only", "bf16", BF16_VALUED),
+    Stream("wt32", 17, 32, "17..32", "SSRHIP_GEMVM_W16", WT32_DEFAULT, "wt16", "the bf16 weight stream of the two-panel step exists for 17..32 rows only", "bf16", BF16_VALUED),
+    Stream("w8", 1, 4, "<= 4", "SSRHIP_GEMV_W8", "1", "w8", "the e4m3 weight stream exists for the <= 4-row decode step only", "e4m3", ("e4m3",)),
+    Stream("wt8", 5, 16, "5..16", "SSRHIP_GEMVM_W8", WT8_DEFAULT, "wt8", "the e4m3 weight stream of the matrix-core step exists for 5..16 rows only", "e4m3", ("e4m3",)),
 )
+W16Stream, W16_STREAMS = Stream, STREAMS[:3]      # the bf16 entries, under the names they had before the e4m3 ones joined the table
+STREAM_OF = {st.name: st for st in STREAMS}
 
 
-def resolve_w8_stream(rows: int, weight_dtype: str, requested: Optional[bool], env) -> bool:
-    """Does an engine of `rows` rows on an arena of `weight_dtype` run the e4m3 weight stream (DecodeEngine stream_w8)? requested None: on
-    iff the arena is e4m3, the engine has <= 4 rows and `env["SSRHIP_GEMV_W8"]` (unset: on) does not start with '0'. requested True:
-    ValueError at more than 4 rows (named before the dtype is looked at), then for any other arena. `env` is a mapping like os.environ;
-    nothing else is read."""
+def resolve_stream(st: Stream, rows: int, weight_dtype: str, requested: Optional[bool], env) -> bool:
+    """Does an engine of `rows` rows on an arena of `weight_dtype` run stream `st`? requested None: on iff the arena is of the stream's
+    format, the rows are the stream's and `env[st.switch]` (unset: st.default) does not start with '0'. requested True: ValueError for rows
+    outside the range (named before the dtype is looked at; below it, the message names the stream of the same format that takes these
+    rows), then for another arena. `env` is a mapping like os.environ; nothing else is read."""
     if requested is None:
-        return weight_dtype == "e4m3" and rows <= 4 and env.get("SSRHIP_GEMV_W8", "1")[:1] != "0"
-    if not requested:
-        return False
-    if rows > 4:
-        raise ValueError(f"stream_w8: the e4m3 weight stream exists for the <= 4-row decode step only (this engine has {rows} rows)")
-    if weight_dtype != "e4m3":
-        raise ValueError("stream_w8 needs an arena built with weight_dtype='e4m3'")
-    return True
-
-
-def resolve_w16_stream(st: W16Stream, rows: int, weight_dtype: str, requested: Optional[bool], env) -> bool:
-    """Does an engine of `rows` rows on an arena of `weight_dtype` run stream `st`? requested None: on iff the arena is bf16, the rows are
-    the stream's and `env[st.switch]` (unset: st.default) does not start with '0'. requested True: ValueError for rows outside the range
-    (named before the dtype is looked at), then for an fp32 arena. `env` is a mapping like os.environ; nothing else is read."""
-    if requested is None:
-        return weight_dtype == "bf16" and st.lo <= rows <= st.hi and env.get(st.switch, st.default)[:1] != "0"
+        return weight_dtype == st.fmt and st.lo <= rows <= st.hi and env.get(st.switch, st.default)[:1] != "0"
     if not requested:
         return False
     if rows < st.lo:
-        owner = next(o for o in W16_STREAMS if rows <= o.hi)
-        raise ValueError(f"stream_{st.name} is the bf16 weight stream of the {st.rows}-row step; an engine of {rows} rows takes stream_{owner.name}")
+        owner = next(o for o in STREAMS if o.fmt == st.fmt and rows <= o.hi)
+        raise ValueError(f"stream_{st.name} is the {st.fmt} weight stream of the {st.rows}-row step; an engine of {rows} rows takes stream_{owner.name}")
     if rows > st.hi:
         raise ValueError(f"stream_{st.name}: {st.only} (this engine has {rows} rows)")
-    if weight_dtype != "bf16":
-        raise ValueError(f"stream_{st.name} needs an arena built with weight_dtype='bf16'")
+    if weight_dtype != st.fmt:
+        raise ValueError(f"stream_{st.name} needs an arena built with weight_dtype='{st.fmt}'")
     return True
 
 
-# What an unset SSRHIP_GEMV_W16_PAIR means for a 2-row engine that streams w16 (DecodeEngine pair_w16=None): "1" = its step runs the pair
-# launches over the packed copies (include/ssrhip.h ssrhip_lm_set_w16_pair), "0" = it steps unpaired. DESIGN.md Part I.19.
+def resolve_w16_stream(st: Stream, rows: int, weight_dtype: str, requested: Optional[bool], env) -> bool:
+    """`resolve_stream` under the name it had when the table held the bf16 streams only (DecodeEngine stream_w16 / stream_wt16 / stream_wt32)."""
+    return resolve_stream(st, rows, weight_dtype, requested, env)
+
+
+def resolve_w8_stream(rows: int, weight_dtype: str, requested: Optional[bool], env) -> bool:
+    """`resolve_stream` for the e4m3 stream of the <= 4-row step (DecodeEngine stream_w8)."""
+    return resolve_stream(STREAM_OF["w8"], rows, weight_dtype, requested, env)
+
+
+def resolve_wt8_stream(rows: int, weight_dtype: str, requested: Optional[bool], env) -> bool:
+    """`resolve_stream` for the e4m3 stream of the 5..16-row matrix-core step (DecodeEngine stream_wt8)."""
+    return resolve_stream(STREAM_OF["wt8"], rows, weight_dtype, requested, env)
+
+
+# What an unset switch of a pair form means (DecodeEngine pair_w16 / pair_w8 / pair4 / pair4_pk = None): "1" = the step runs that form's
+# pair launches, "0" = it steps with its single launches. DESIGN.md Parts I.19, I.20, I.24, I.26.
 W16_PAIR_DEFAULT = "0"
+W8_PAIR_DEFAULT = "0"
+PAIR4_DEFAULT = "0"
+PAIR4_PK_DEFAULT = "0"
+PAIR4_WS_BYTES = 3 * 8192 * 8 + 64      # include/ssrhip.h SSRHIP_PAIR4_WS_BYTES: three buffers of 4 x 2048 granules + the give-up flag
+
+# One opt-in pair-launch form of the decode step per row count and weight stream. `name` is DecodeEngine's keyword and attribute; `c_name` the
+# suffix of the C setter `ssrhip_lm_set_<c_name>` and of the counter `ssrhip_lm_<c_name>_launches`; `rows` the one row count it exists for; `switch`
+# the environment variable an engine built with `<name>=None` reads and `default` what it means when unset; `fits(stream)` whether the
+# form pairs an engine whose stream is `stream` (a Stream, None: the fp32 masters); `only` what a refusal of another row count says and
+# `needs(stream)` what a refusal of the stream says. Whether an engine that asks then GETS to pair (device, pairing slot) is the library's
+# decision (`DecodeEngine.pairing`, `pairing_why`). Same tokens, bit for bit, either way.
+PairForm = namedtuple("PairForm", "name c_name rows switch default fits only needs")
+PAIR_FORMS = (
+    PairForm("pair_w16", "w16_pair", 2, "SSRHIP_GEMV_W16_PAIR", W16_PAIR_DEFAULT, lambda st: st is STREAM_OF["w16"],
+             "pair launches exist for the 2-row decode step only",
+             lambda st: "pair_w16 needs an engine that streams bf16 weights (stream_w16)"),
+    PairForm("pair_w8", "w8_pair", 2, "SSRHIP_GEMV_W8_PAIR", W8_PAIR_DEFAULT, lambda st: st is STREAM_OF["w8"],
+             "pair launches exist for the 2-row decode step only",
+             lambda st: "pair_w8 needs an engine that streams e4m3 weights (stream_w8)"),
+    PairForm("pair4", "pair4", 4, "SSRHIP_GEMV_PAIR4", PAIR4_DEFAULT, lambda st: st is None,
+             "the 4-row pair launches exist for the 4-row decode step only",
+             lambda st: f"pair4: the 4-row pair launches read fp32 weights (this engine streams {st.fmt} weights: stream_{st.name})"),
+    PairForm("pair4_pk", "pair4_pk", 4, "SSRHIP_GEMV_PAIR4_PK", PAIR4_PK_DEFAULT, lambda st: st is not None,
+             "the 4-row pair launches exist for the 4-row decode step only",
+             lambda st: "pair4_pk needs an engine that streams packed weights (stream_w16 or stream_w8); pair4 pairs the fp32 masters"),
+)
+PAIR_OF = {pf.name: pf for pf in PAIR_FORMS}
+
+
+def resolve_pair(pf: PairForm, rows: int, stream: Optional[Stream], pair_mode: int, requested: Optional[bool], env) -> bool:
+    """Does an engine of `rows` rows whose weight stream is `stream` ask for pair form `pf`? requested None: on iff the rows are the
+    form's, the stream fits, pair_mode is not 1 and `env[pf.switch]` (unset: pf.default) does not start with '0'. requested True: ValueError
+    at another row count (named first), then for a stream that does not fit, then with pair_mode 1. `env` is a mapping like os.environ;
+    nothing else is read."""
+    if requested is None:
+        return rows == pf.rows and pf.fits(stream) and pair_mode != 1 and env.get(pf.switch, pf.default)[:1] != "0"
+    if not requested:
+        return False
+    if rows != pf.rows:
+        raise ValueError(f"{pf.name}: {pf.only} (this engine has {rows} rows)")
+    if not pf.fits(stream):
+        raise ValueError(pf.needs(stream))
+    if pair_mode == 1:
+        raise ValueError(f"{pf.name} with pair_mode=1: the caller switched pair launches off")
+    return True
+
+
+def _small_stream(stream_w16: bool, stream_w8: bool = False) -> Optional[Stream]:
+    """The stream of a <= 4-row engine from the two flags the four functions below take; each of them is `resolve_pair` for one form."""
+    return STREAM_OF["w16"] if stream_w16 else STREAM_OF["w8"] if stream_w8 else None
 
 
 def resolve_w16_pair(rows: int, stream_w16: bool, pair_mode: int, requested: Optional[bool], env) -> bool:
-    """Does an engine of `rows` rows ask for pair launches over its bf16 weight stream (DecodeEngine pair_w16)? requested None: on iff the
-    engine has 2 rows, streams w16, pair_mode is not 1 and `env["SSRHIP_GEMV_W16_PAIR"]` (unset: W16_PAIR_DEFAULT) does not start with '0'.
-    requested True: ValueError at another row count (named first), then without stream_w16, then with pair_mode 1. Whether the engine then
-    GETS to pair (device, pairing slot) is the library's decision (`DecodeEngine.pairing`). `env` is a mapping like os.environ; nothing
-    else is read."""
-    if requested is None:
-        return rows == 2 and bool(stream_w16) and pair_mode != 1 and env.get("SSRHIP_GEMV_W16_PAIR", W16_PAIR_DEFAULT)[:1] != "0"
-    if not requested:
-        return False
-    if rows != 2:
-        raise ValueError(f"pair_w16: pair launches exist for the 2-row decode step only (this engine has {rows} rows)")
-    if not stream_w16:
-        raise ValueError("pair_w16 needs an engine that streams bf16 weights (stream_w16)")
-    if pair_mode == 1:
-        raise ValueError("pair_w16 with pair_mode=1: the caller switched pair launches off")
-    return True
-
-
-# The same for a 2-row engine that streams w8 (DecodeEngine pair_w8=None) and SSRHIP_GEMV_W8_PAIR: "1" = its step runs the pair launches
-# over the e4m3 codes and scales (include/ssrhip.h ssrhip_lm_set_w8_pair), "0" = it steps unpaired. DESIGN.md Part I.20.
-W8_PAIR_DEFAULT = "0"
+    return resolve_pair(PAIR_OF["pair_w16"], rows, _small_stream(stream_w16), pair_mode, requested, env)
 
 
 def resolve_w8_pair(rows: int, stream_w8: bool, pair_mode: int, requested: Optional[bool], env) -> bool:
-    """Does an engine of `rows` rows ask for pair launches over its e4m3 weight stream (DecodeEngine pair_w8)? requested None: on iff the
-    engine has 2 rows, streams w8, pair_mode is not 1 and `env["SSRHIP_GEMV_W8_PAIR"]` (unset: W8_PAIR_DEFAULT) does not start with '0'.
-    requested True: ValueError at another row count (named first), then without stream_w8, then with pair_mode 1. Whether the engine then
-    GETS to pair (device, pairing slot) is the library's decision (`DecodeEngine.pairing`). `env` is a mapping like os.environ; nothing
-    else is read."""
-    if requested is None:
-        return rows == 2 and bool(stream_w8) and pair_mode != 1 and env.get("SSRHIP_GEMV_W8_PAIR", W8_PAIR_DEFAULT)[:1] != "0"
-    if not requested:
-        return False
-    if rows != 2:
-        raise ValueError(f"pair_w8: pair launches exist for the 2-row decode step only (this engine has {rows} rows)")
-    if not stream_w8:
-        raise ValueError("pair_w8 needs an engine that streams e4m3 weights (stream_w8)")
-    if pair_mode == 1:
-        raise ValueError("pair_w8 with pair_mode=1: the caller switched pair launches off")
-    return True
-
-
-# What an unset SSRHIP_GEMV_PAIR4 means for a 4-row engine that streams its fp32 masters (DecodeEngine pair4=None): "1" = its step runs the
-# 4-row pair launches (include/ssrhip.h ssrhip_lm_set_pair4), "0" = it steps with the ordinary launches. DESIGN.md Part I.24.
-PAIR4_DEFAULT = "0"
-PAIR4_WS_BYTES = 3 * 8192 * 8 + 64      # include/ssrhip.h SSRHIP_PAIR4_WS_BYTES: three buffers of 4 x 2048 granules + the give-up flag
+    return resolve_pair(PAIR_OF["pair_w8"], rows, _small_stream(False, stream_w8), pair_mode, requested, env)
 
 
 def resolve_pair4(rows: int, stream_w16: bool, stream_w8: bool, pair_mode: int, requested: Optional[bool], env) -> bool:
-    """Does an engine of `rows` rows ask for the 4-row pair launches (DecodeEngine pair4)? requested None: on iff the engine has 4 rows,
-    streams no packed weights (neither w16 nor w8), pair_mode is not 1 and `env["SSRHIP_GEMV_PAIR4"]` (unset: PAIR4_DEFAULT) does not
-    start with '0'. requested True: ValueError at another row count (named first), then with a packed stream, then with pair_mode 1.
-    Whether the engine then GETS to pair (device, pairing slot) is the library's decision (`DecodeEngine.pairing`). `env` is a mapping
-    like os.environ; nothing else is read."""
-    if requested is None:
-        return rows == 4 and not stream_w16 and not stream_w8 and pair_mode != 1 and env.get("SSRHIP_GEMV_PAIR4", PAIR4_DEFAULT)[:1] != "0"
-    if not requested:
-        return False
-    if rows != 4:
-        raise ValueError(f"pair4: the 4-row pair launches exist for the 4-row decode step only (this engine has {rows} rows)")
-    if stream_w16 or stream_w8:
-        raise ValueError(f"pair4: the 4-row pair launches read fp32 weights (this engine streams {'bf16' if stream_w16 else 'e4m3'} weights: "
-                         f"{'stream_w16' if stream_w16 else 'stream_w8'})")
-    if pair_mode == 1:
-        raise ValueError("pair4 with pair_mode=1: the caller switched pair launches off")
-    return True
-
-
-# What an unset SSRHIP_GEMV_PAIR4_PK means for a 4-row engine that streams packed weights, w16 or w8 (DecodeEngine pair4_pk=None): "1" = its
-# step runs the 4-row pair launches over the packed stream (include/ssrhip.h ssrhip_lm_set_pair4_pk), "0" = it steps with the single packed
-# launches. DESIGN.md Part I.26.
-PAIR4_PK_DEFAULT = "0"
+    return resolve_pair(PAIR_OF["pair4"], rows, _small_stream(stream_w16, stream_w8), pair_mode, requested, env)
 
 
 def resolve_pair4_pk(rows: int, stream_w16: bool, stream_w8: bool, pair_mode: int, requested: Optional[bool], env) -> bool:
-    """Does an engine of `rows` rows ask for the 4-row pair launches over its packed weight stream (DecodeEngine pair4_pk)? requested None:
-    on iff the engine has 4 rows, streams w16 or w8, pair_mode is not 1 and `env["SSRHIP_GEMV_PAIR4_PK"]` (unset: PAIR4_PK_DEFAULT) does
-    not start with '0'. requested True: ValueError at another row count (named first), then without a packed stream, then with pair_mode
-    1. Whether the engine then GETS to pair (device, pairing slot) is the library's decision (`DecodeEngine.pairing`). `env` is a mapping
-    like os.environ; nothing else is read."""
-    if requested is None:
-        return rows == 4 and bool(stream_w16 or stream_w8) and pair_mode != 1 and env.get("SSRHIP_GEMV_PAIR4_PK", PAIR4_PK_DEFAULT)[:1] != "0"
-    if not requested:
-        return False
-    if rows != 4:
-        raise ValueError(f"pair4_pk: the 4-row pair launches exist for the 4-row decode step only (this engine has {rows} rows)")
-    if not (stream_w16 or stream_w8):
-        raise ValueError("pair4_pk needs an engine that streams packed weights (stream_w16 or stream_w8); pair4 pairs the fp32 masters")
-    if pair_mode == 1:
-        raise ValueError("pair4_pk with pair_mode=1: the caller switched pair launches off")
-    return True
+    return resolve_pair(PAIR_OF["pair4_pk"], rows, _small_stream(stream_w16, stream_w8), pair_mode, requested, env)
 
 
 KV_DTYPES = ("fp32", "bf16")
@@ -445,6 +409,55 @@ def resolve_share_prompt(rows: int, requested: Optional[bool], kv_dtype: str = "
     if kv_dtype == "bf16":
         raise ValueError("share_prompt does not combine with kv_dtype='bf16' (the grouped attention walk reads fp32 entries)")
     return True
+
+
+# Everything an engine decides before it allocates. `stream`: the one weight stream that is on (a STREAMS entry; None: the fp32 masters);
+# `pair`: the one pair form asked for (a PAIR_FORMS entry; None: none); `max_pages`: pages per row.
+DecodePlan = namedtuple("DecodePlan", "rows stream pair pair_mode kv_dtype kv16_small share_prompt logprobs max_pages")
+STREAM_KEYWORDS = tuple("stream_" + st.name for st in STREAMS)
+PAIR_KEYWORDS = tuple(pf.name for pf in PAIR_FORMS)
+
+
+def resolve_decode_plan(rows: int, weight_dtype: str, n_layers: int, max_seq: int, env, pair_mode: int = 0, kv_dtype: Optional[str] = None,
+                        share_prompt: Optional[bool] = None, kv16_small: Optional[bool] = None, logprobs: bool = False,
+                        kv_default: str = "fp32", **requested) -> DecodePlan:
+    """The plan of an engine of `rows` rows and `max_seq` positions per row on an arena of `weight_dtype` with `n_layers` layers.
+    `requested`: the stream_* and pair* keywords of DecodeEngine.__init__ (STREAM_KEYWORDS, PAIR_KEYWORDS; absent = None); `kv_default`: the
+    model's cache type (SSR_Speech.set_kv_dtype), which stands where `kv_dtype` is None. The cross rules, in the order they refuse: the rows;
+    two streams of one step asked for together; each stream's own rule (`resolve_stream`; a wt8 that resolves on turns an unrequested wt16
+    off, and refuses a requested one); `resolve_kv16_small` and its layer cap — when it says yes the cache is "bf16" and `resolve_kv_dtype`
+    is not asked; `resolve_share_prompt` and its page cap; each pair form's rule (`resolve_pair`). Pure: reads its arguments and `env`
+    (a mapping like os.environ), nothing else."""
+    unknown = set(requested) - set(STREAM_KEYWORDS + PAIR_KEYWORDS)
+    if unknown:
+        raise TypeError(f"resolve_decode_plan: unknown request {sorted(unknown)}")
+    if rows not in (1, 2, 4) and not (5 <= rows <= MAX_ROWS):
+        raise ValueError(f"rows B={rows} not supported by this build (1, 2, 4 or 5..{MAX_ROWS})")
+    ask = {st.name: requested.get("stream_" + st.name) for st in STREAMS}
+    two = "stream_{0.name} and stream_{1.name} are two weight streams of the {0.rows}-row step; an engine takes one"
+    on = []
+    for st in STREAMS[3:] + STREAMS[:3]:      # the e4m3 streams first: wt8's answer decides an unrequested wt16
+        twin = next((o for o in STREAMS[:3] if st.fmt == "e4m3" and (o.lo, o.hi) == (st.lo, st.hi)), None)      # the bf16 stream of its rows
+        if twin and ask[st.name] and ask[twin.name]:
+            raise ValueError(two.format(st, twin))
+        if st.name == "wt16" and STREAM_OF["wt8"] in on and ask["wt16"] is None:
+            continue                          # the 1-byte stream takes the step; the 2-byte copies are not built
+        if resolve_stream(st, rows, st.fmt if weight_dtype in st.arenas else weight_dtype, ask[st.name], env):
+            on.append(st)
+    if len(on) > 1:                           # stream_wt16=True against a switched-on wt8: the library takes one packed stream
+        raise ValueError(two.format(*on))
+    stream = on[0] if on else None
+    max_pages = (max_seq + PAGE - 1) // PAGE
+    small = resolve_kv16_small(rows, kv_dtype, kv_default, kv16_small, env)
+    if small and n_layers > KV16_SMALL_MAX_LAYERS:
+        raise ValueError(f"kv16_small takes at most {KV16_SMALL_MAX_LAYERS} layers (this model has {n_layers})")
+    kv = "bf16" if small else resolve_kv_dtype(rows, kv_dtype, kv_default, max_pages)
+    share = resolve_share_prompt(rows, share_prompt, kv)
+    if share and max_pages > KV16_MAX_PAGES:
+        raise ValueError(f"share_prompt takes at most {KV16_MAX_PAGES} pages per row (this engine has {max_pages})")
+    pair_mode = int(pair_mode)
+    pairs = [pf for pf in PAIR_FORMS if resolve_pair(pf, rows, stream, pair_mode, requested.get(pf.name), env)]      # at most one fits
+    return DecodePlan(rows, stream, pairs[0] if pairs else None, pair_mode, kv, small, share, bool(logprobs), max_pages)
 
 
 def plan_prompt_sharing(seqs, members: int):
@@ -613,66 +626,65 @@ class LMWeightsArena:
         """ssrhip_lm_w16 of the packed copies (NULL where a family has none)."""
         return self._packed_struct("w16")
 
+    def _ensure_codes(self, order: str) -> bool:
+        if self.weight_dtype != "e4m3":
+            raise ValueError("packed e4m3 codes need an arena built with weight_dtype='e4m3' (the masters must hold codes * scale)")
+        if getattr(self, f"_{order}_ready", False):
+            return False
+        to_order, streamable = CODE_ORDERS[order]
+        pack = lambda Wm, sc: to_order(e4m3_codes(Wm, sc)) if streamable(Wm.shape[-1]) else None
+        for lay in self.layers:
+            for name in W16_FAMILIES:
+                lay[f"{name}_{order}"] = pack(lay[name + "_w"], lay[name + "_w8s"])
+        setattr(self, "head1_" + order, pack(self.head1_w, self.head1_w8s))
+        setattr(self, "head2_" + order, pack(self.head2_w, self.head2_w8s))
+        setattr(self, f"_{order}_ready", True)
+        self.generation += 1
+        return True
+
+    def _codes_struct(self, order: str):
+        """ssrhip_lm_w8 whose code pointers are the arena's `<family>_<order>` tensors ("w8": SSRHIP_W8_INDEX order, "wt8": SSRHIP_WT8_INDEX)"""
+        w = _lib.LMW8()
+        arrays = {}
+        setattr(self, f"_{order}_arrays", arrays)       # the record points into them
+        for name in W16_FAMILIES:
+            if all(lay[f"{name}_{order}"] is not None for lay in self.layers):
+                for suffix, field in (("_" + order, name + "_w8"), ("_w8s", name + "_s")):
+                    arrays[field] = (C.c_void_p * self.L)(*[lay[name + suffix].data_ptr() for lay in self.layers])
+                    setattr(w, field, C.cast(arrays[field], C.POINTER(C.c_void_p)))
+        for h in ("head1", "head2"):
+            if getattr(self, f"{h}_{order}") is not None:
+                setattr(w, h + "_w8", getattr(self, f"{h}_{order}").data_ptr())
+                setattr(w, h + "_s", getattr(self, h + "_w8s").data_ptr())
+        return w
+
+    def ensure_order(self, order: str) -> bool:
+        """Build the copies of a Stream's `order` (PACKED_ORDERS / CODE_ORDERS) once; True when they were created now."""
+        return (self._ensure_packed if order in PACKED_ORDERS else self._ensure_codes)(order)
+
+    def order_struct(self, order: str):
+        """The C record of that order's copies: ssrhip_lm_w16 (PACKED_ORDERS) or ssrhip_lm_w8 (CODE_ORDERS)."""
+        return (self._packed_struct if order in PACKED_ORDERS else self._codes_struct)(order)
+
     def ensure_w8_copies(self) -> bool:
         """Packed e4m3 codes (`to_w8_order` of `e4m3_codes(master, scale)`, exact) of the six matrix families for the <= 4-row decode step of
         an e4m3 arena (+1 byte per weight = +0.82 GB at 830M beside the scales, built once on first use). A family whose inner dimension
         the kernels do not take (`w16_streamable`, e.g. d_model 128) gets none and streams its master. Returns True when created now."""
-        if self.weight_dtype != "e4m3":
-            raise ValueError("packed e4m3 codes need an arena built with weight_dtype='e4m3' (the masters must hold codes * scale)")
-        if getattr(self, "_w8_ready", False):
-            return False
-        pack = lambda Wm, sc: to_w8_order(e4m3_codes(Wm, sc)) if w16_streamable(Wm.shape[-1]) else None
-        for lay in self.layers:
-            for name in W16_FAMILIES:
-                lay[name + "_w8"] = pack(lay[name + "_w"], lay[name + "_w8s"])
-        self.head1_w8 = pack(self.head1_w, self.head1_w8s)
-        self.head2_w8 = pack(self.head2_w, self.head2_w8s)
-        self._w8_ready = True
-        self.generation += 1
-        return True
+        return self._ensure_codes("w8")
 
     def w8_struct(self):
         """ssrhip_lm_w8 of the packed codes and their scales (NULL pairs where a family has no packed copy)."""
-        return self._codes_struct("_w8")
-
-    def _codes_struct(self, codes: str):
-        """ssrhip_lm_w8 whose code pointers are the arena's `<family><codes>` tensors ("_w8": SSRHIP_W8_INDEX order, "_wt8": SSRHIP_WT8_INDEX)"""
-        w = _lib.LMW8()
-        arrays = {}
-        setattr(self, codes + "_arrays", arrays)        # the record points into them
-        for name in W16_FAMILIES:
-            if all(lay[name + codes] is not None for lay in self.layers):
-                for suffix, field in ((codes, name + "_w8"), ("_w8s", name + "_s")):
-                    arrays[field] = (C.c_void_p * self.L)(*[lay[name + suffix].data_ptr() for lay in self.layers])
-                    setattr(w, field, C.cast(arrays[field], C.POINTER(C.c_void_p)))
-        for h in ("head1", "head2"):
-            if getattr(self, h + codes) is not None:
-                setattr(w, h + "_w8", getattr(self, h + codes).data_ptr())
-                setattr(w, h + "_s", getattr(self, h + "_w8s").data_ptr())
-        return w
+        return self._codes_struct("w8")
 
     def ensure_wt8_copies(self) -> bool:
-        """Packed e4m3 codes in streaming order (`to_wt8_order` of `e4m3_codes(master, scale)`, exact) of the six matrix families for the
-        5..16-row decode step of an e4m3 arena (+1 byte per weight = +0.82 GB at 830M beside the scales and the fp32 streaming copies, built
-        once on first use). A family whose inner dimension is no multiple of 128 (`wt8_streamable`) gets none and streams its fp32
+        """The same in streaming order (`to_wt8_order`) for the 5..16-row decode step (+0.82 GB at 830M beside the scales and the fp32
+        streaming copies). A family whose inner dimension is no multiple of 128 (`wt8_streamable`) gets none and streams its fp32
         streaming-order copy. Returns True when created now."""
-        if self.weight_dtype != "e4m3":
-            raise ValueError("packed e4m3 codes need an arena built with weight_dtype='e4m3' (the masters must hold codes * scale)")
-        if getattr(self, "_wt8_ready", False):
-            return False
-        pack = lambda Wm, sc: to_wt8_order(e4m3_codes(Wm, sc)) if wt8_streamable(Wm.shape[-1]) else None
-        for lay in self.layers:
-            for name in W16_FAMILIES:
-                lay[name + "_wt8"] = pack(lay[name + "_w"], lay[name + "_w8s"])
-        self.head1_wt8 = pack(self.head1_w, self.head1_w8s)
-        self.head2_wt8 = pack(self.head2_w, self.head2_w8s)
-        self._wt8_ready = True
-        self.generation += 1
-        return True
+        return self._ensure_codes("wt8")
 
     def wt8_struct(self):
         """ssrhip_lm_w8 of the SSRHIP_WT8_INDEX codes and their scales for ssrhip_lm_set_wt8 (NULL pairs where a family has no packed copy)."""
-        return self._codes_struct("_wt8")
+        return self._codes_struct("wt8")
 
     def ensure_wt16_copies(self) -> bool:
         """Packed bf16 streaming-order copies (`to_wt16_order`) of the six matrix families for the 5..32-row decode step of a bf16 arena
@@ -1128,52 +1140,20 @@ class DecodeEngine:
                  pair_w16: Optional[bool] = None, pair_w8: Optional[bool] = None, stream_wt8: Optional[bool] = None,
                  kv16_small: Optional[bool] = None, pair4: Optional[bool] = None, pair4_pk: Optional[bool] = None,
                  logprobs: bool = False):
-        """max_seq: longest sequence (text + audio positions) any ONE row may reach; pool_pages: physical KV pages shared by all
-        rows (default rows x pages-per-row, the no-sharing worst case; a batch of short and long utterances needs only the sum
-        of their own page counts). pair_mode (2-row engines; include/ssrhip.h ssrhip_lm_buffers): 0 = pair launches if this engine
-        gets its device's pairing slot, 1 = never, 2 = always (tests of the give-up path). stream_w16: the decode step streams the arena's
-        packed bf16 copies (include/ssrhip.h ssrhip_lm_set_w16; needs a bf16 arena and <= 4 rows, steps unpaired); None = on when the arena
-        is bf16, the engine has <= 4 rows and `SSRHIP_GEMV_W16` (read here) does not start with '0'. stream_wt16: the same for the 5..16-row
-        matrix-core step (ssrhip_lm_set_wt16: SSRHIP_WT16_INDEX copies beside the fp32 streaming-order copies, which stay the fallback);
-        None = on when the arena is bf16, the engine has 5..16 rows and `SSRHIP_GEMVM_W16` (read here; unset = WT16_DEFAULT) does not
-        start with '0'. stream_wt32: the same for the 17..32-row two-panel step (ssrhip_lm_set_wt32, the same SSRHIP_WT16_INDEX copies); None =
-        on when the arena is bf16, the engine has 17..32 rows and `SSRHIP_GEMVM_W16` (unset = WT32_DEFAULT) does not start with '0'.
-        An e4m3 arena is bf16-valued: at 5..32 rows it takes stream_wt16 / stream_wt32 under the same switches. stream_w8: the <= 4-row decode
-        step streams the arena's packed e4m3 codes and scales (include/ssrhip.h ssrhip_lm_set_w8; needs an e4m3 arena and <= 4 rows, steps
-        unpaired unless pair_w8 opts in); None = on when the arena is e4m3, the engine has <= 4 rows and `SSRHIP_GEMV_W8` (read here) does not start with '0'; off,
-        such an engine streams its fp32 masters and may pair. stream_w8=True with stream_w16=True is a ValueError.
-        stream_wt8 (`resolve_wt8_stream`): the 5..16-row matrix-core step streams the arena's e4m3 codes in SSRHIP_WT8_INDEX order and their
-        scales (include/ssrhip.h ssrhip_lm_set_wt8; needs an e4m3 arena and 5..16 rows; the fp32 streaming-order copies stay the fallback);
-        None = on when the arena is e4m3, the engine has 5..16 rows and `SSRHIP_GEMVM_W8` (read here; unset = WT8_DEFAULT) does not start
-        with '0'. An engine whose stream_wt8 resolves on leaves stream_wt16 off unless it was asked for; stream_wt8=True with
-        stream_wt16=True is a ValueError. Same tokens, bit for bit, as the same arena's masters.
-        pair_w16 (2-row engines that stream w16; `resolve_w16_pair`): the step runs the pair launches over the packed copies
-        (include/ssrhip.h ssrhip_lm_set_w16_pair) if the library lets this engine pair (`pairing`, `pairing_why`); None = on when
-        `SSRHIP_GEMV_W16_PAIR` (read here; unset = W16_PAIR_DEFAULT) does not start with '0'. Same tokens, bit for bit, either way.
-        pair_w8 (2-row engines that stream w8; `resolve_w8_pair`): the same over the e4m3 codes and scales (ssrhip_lm_set_w8_pair); None = on
-        when `SSRHIP_GEMV_W8_PAIR` (read here; unset = W8_PAIR_DEFAULT) does not start with '0'. Same tokens, bit for bit, either way.
-        kv_dtype "bf16" (5..32 rows, at most KV16_MAX_PAGES pages per row; ValueError otherwise): the paged pool holds 2-byte entries —
-        every K / V value rounded to bf16 by whichever path writes it (the step's append, every prefill), widened exactly by every attention;
-        q, scores, softmax and outputs stay fp32 (include/ssrhip.h ssrhip_lm_set_kv16). None = "fp32". Independent of the weight stream.
-        share_prompt True (5..32 rows, fp32 cache; ValueError otherwise; None = off): rows admitted TOGETHER by `start` / the first fill of
-        `run_queue` with equal text and equal prompt audio (the samples of one utterance) are prefilled once, share the prompt's whole KV
-        pages, and the step's attention reads a shared page once per chunk of rows (include/ssrhip.h ssrhip_lm_set_prompt_groups). Every
-        row computes what it computes unshared, bit for bit. Refills and the two-phase admission (`admit_begin`) never share.
-        kv16_small (1, 2 or 4 rows; `resolve_kv16_small`, DESIGN.md Part I.23): the bf16 cache for the split-KV step — the pool holds 2-byte
-        entries, the QKV launch appends fp32 into a small landing cache (`kv_landing_bytes`) and the attention launch rounds the new position
-        once and promotes it into the pool (include/ssrhip.h ssrhip_lm_set_kv16_small). None = on when the engine has <= 4 rows, kv_dtype
-        is "bf16" and `SSRHIP_ATTN_KV16_SMALL` (read here; unset = KV16_SMALL_DEFAULT) does not start with '0'; with it on, kv_dtype "bf16"
-        is not a ValueError at these rows. Every weight stream and launch form works unchanged; at most KV16_SMALL_MAX_LAYERS layers.
-        pair4 (4-row engines that stream their fp32 masters; `resolve_pair4`, DESIGN.md Part I.24): the step runs the 4-row pair launches
-        (include/ssrhip.h ssrhip_lm_set_pair4) if the library lets this engine pair (`pairing`, `pairing_why`); None = on when
-        `SSRHIP_GEMV_PAIR4` (read here; unset = PAIR4_DEFAULT) does not start with '0'. Same tokens, bit for bit, either way.
-        pair4_pk (4-row engines that stream w16 or w8; `resolve_pair4_pk`, DESIGN.md Part I.26): the step runs the 4-row pair launches over
-        the packed stream (include/ssrhip.h ssrhip_lm_set_pair4_pk) if the library lets this engine pair; None = on when
-        `SSRHIP_GEMV_PAIR4_PK` (read here; unset = PAIR4_PK_DEFAULT) does not start with '0'. Same tokens, bit for bit, either way.
-        logprobs (DESIGN.md Part I.27; no environment switch): the step's sampler also writes the log-probability of every token it
-        generates (include/ssrhip.h ssrhip_sample_logp; NaN where the state machine decided the token) into an fp32 buffer beside
-        `generated`, read with `logprobs()`; `run_queue` leaves one array per job in `queue_logprobs`. Same tokens, bit for bit; at every
-        row count. False: no buffer, and the step this engine ran before."""
+        """max_seq: longest sequence (text + audio positions) any ONE row may reach.
+        pool_pages: physical KV pages shared by all rows (default rows x pages-per-row, the no-sharing worst case; a batch of short and
+        long utterances needs only the sum of their own page counts).
+        pair_mode (include/ssrhip.h ssrhip_lm_buffers): 0 = pair launches if this engine gets its device's pairing slot, 1 = never,
+        2 = always (tests of the give-up path).
+        stream_w16 / stream_wt16 / stream_wt32 / stream_w8 / stream_wt8: the step streams that entry of STREAMS; None = its switch decides.
+        pair_w16 / pair_w8 / pair4 / pair4_pk: the step asks for that entry of PAIR_FORMS; None = its switch decides.
+        kv_dtype: "bf16" = the paged pool holds 2-byte entries (`resolve_kv_dtype`: 5..32 rows; include/ssrhip.h ssrhip_lm_set_kv16); None = "fp32".
+        kv16_small: the bf16 cache of the 1/2/4-row step behind a landing cache (`resolve_kv16_small`, `kv_landing_bytes`, DESIGN.md Part I.23).
+        share_prompt: rows admitted TOGETHER with equal text and prompt audio are prefilled once and share the prompt's whole KV pages
+        (`resolve_share_prompt`, DESIGN.md Part I.15); refills and the two-phase admission (`admit_begin`) never share. None = off.
+        logprobs: the sampler also writes every generated token's log-probability (`logprobs()`, `queue_logprobs`; DESIGN.md Part I.27).
+        All of them are decided by `resolve_decode_plan` (the switches are read there, from os.environ) before anything is allocated;
+        `self.plan` keeps the answer. Every choice gives the same tokens, bit for bit, on the same arena and cache type."""
         self.lib = _lib.lib()
         self.a = arena
         dev = arena.device
@@ -1182,41 +1162,17 @@ class DecodeEngine:
         self.use_cfg = use_cfg
         self.rows_per_utt = 2 if use_cfg else 1
         self.B = n_utt * self.rows_per_utt
-        if self.B not in (1, 2, 4) and not (5 <= self.B <= MAX_ROWS):
-            raise ValueError(f"rows B={self.B} not supported by this build (1, 2, 4 or 5..{MAX_ROWS})")
-        requested = dict(w16=stream_w16, wt16=stream_wt16, wt32=stream_wt32)
-        if stream_w8 and stream_w16:
-            raise ValueError("stream_w8 and stream_w16 are two weight streams of the <= 4-row step; an engine takes one")
-        self.stream_w8 = resolve_w8_stream(self.B, arena.weight_dtype, stream_w8, os.environ)
-        if stream_wt8 and stream_wt16:
-            raise ValueError("stream_wt8 and stream_wt16 are two weight streams of the 5..16-row step; an engine takes one")
-        self.stream_wt8 = resolve_wt8_stream(self.B, arena.weight_dtype, stream_wt8, os.environ)
-        if self.stream_wt8 and stream_wt16 is None:
-            requested["wt16"] = False             # the 1-byte stream takes the step; the 2-byte copies are not built
-        for st in W16_STREAMS:                    # the row ranges are disjoint: at most one is on
-            # the 2-byte copies of the matrix-core step serve every bf16-valued arena; the <= 4-row bf16 stream is the bf16 arena's own
-            dtype = "bf16" if (st.lo > 4 and arena.bf16_valued) else arena.weight_dtype
-            setattr(self, "stream_" + st.name, resolve_w16_stream(st, self.B, dtype, requested[st.name], os.environ))
-        self._stream = next((st for st in W16_STREAMS if getattr(self, "stream_" + st.name)), None)
-        self.max_pages = (max_seq + PAGE - 1) // PAGE
+        self.plan = resolve_decode_plan(self.B, arena.weight_dtype, arena.L, max_seq, os.environ, pair_mode, kv_dtype, share_prompt, kv16_small, logprobs,
+                                        stream_w16=stream_w16, stream_wt16=stream_wt16, stream_wt32=stream_wt32, stream_w8=stream_w8,
+                                        stream_wt8=stream_wt8, pair_w16=pair_w16, pair_w8=pair_w8, pair4=pair4, pair4_pk=pair4_pk)
+        self.max_pages = self.plan.max_pages
         self.max_seq = self.max_pages * PAGE
-        self.kv16_small = resolve_kv16_small(self.B, kv_dtype, "fp32", kv16_small, os.environ)
-        if self.kv16_small and arena.L > KV16_SMALL_MAX_LAYERS:
-            raise ValueError(f"kv16_small takes at most {KV16_SMALL_MAX_LAYERS} layers (this model has {arena.L})")
-        self.kv_dtype = "bf16" if self.kv16_small else resolve_kv_dtype(self.B, kv_dtype, "fp32", self.max_pages)
-        self.share_prompt = resolve_share_prompt(self.B, share_prompt, self.kv_dtype)
-        if self.share_prompt and self.max_pages > KV16_MAX_PAGES:
-            raise ValueError(f"share_prompt takes at most {KV16_MAX_PAGES} pages per row (this engine has {self.max_pages})")
         arena.ensure_positions(self.max_seq)      # every text / audio position of a row is < its sequence capacity
         if self.B > 4:
             arena.ensure_streaming_copies()       # the matrix-core GEMV streams W in its own order
         arena.ensure_split_planes()               # the prefill GEMMs run on the bf16 matrix cores with exactly split operands
         if self._stream is not None:
-            arena._ensure_packed(self._stream.order)   # the step streams packed 2-byte weights (at 5..32 rows in streaming order)
-        if self.stream_w8:
-            arena.ensure_w8_copies()              # the step streams packed 1-byte codes and their scales
-        if self.stream_wt8:
-            arena.ensure_wt8_copies()             # the same in the streaming order of the matrix-core step
+            arena.ensure_order(self._stream.order)    # the step streams packed 2-byte weights or 1-byte codes and their scales
         self.max_steps = max_steps
         D, H, L, K = arena.D, arena.H, arena.L, arena.K
         self.hd = D // H
@@ -1272,7 +1228,6 @@ class DecodeEngine:
         self.cfg_dev = torch.zeros(n_utt * C.sizeof(_lib.SamplerCfg), dtype=torch.uint8, device=dev)
         self.state_dev = torch.zeros(n_utt * C.sizeof(_lib.SamplerState), dtype=torch.uint8, device=dev)
         self.generated = torch.zeros(n_utt, max_steps, K, **i32)
-        self.want_logprobs = bool(logprobs)
         self.logp = torch.full((n_utt, max_steps, K), float("nan"), **f32) if self.want_logprobs else None
         self.queue_logprobs: List[np.ndarray] = []   # run_queue with logprobs: float32 [n_steps, K] per job, in job order
         # ONE persistent buffer for host-drawn sampling noise: its pointer is baked into the captured graph, so generations
@@ -1287,11 +1242,6 @@ class DecodeEngine:
         self.dbg_logits = torch.zeros(n_utt, K, arena.card, **f32) if debug_logits else None
         self._take_weights()
         self._ctx = None
-        self.pair_mode = int(pair_mode)
-        self.pair_w16 = resolve_w16_pair(self.B, self.stream_w16, self.pair_mode, pair_w16, os.environ)
-        self.pair_w8 = resolve_w8_pair(self.B, self.stream_w8, self.pair_mode, pair_w8, os.environ)
-        self.pair4 = resolve_pair4(self.B, self.stream_w16, self.stream_w8, self.pair_mode, pair4, os.environ)
-        self.pair4_pk = resolve_pair4_pk(self.B, self.stream_w16, self.stream_w8, self.pair_mode, pair4_pk, os.environ)
         self.pairing = False                      # set by _create_ctx: does this engine's step run the pair launches?
         self.pairing_why = ""
 
@@ -1323,23 +1273,12 @@ class DecodeEngine:
         ctx = C.c_void_p()
         _lib.check(self.lib.ssrhip_lm_create(C.byref(d), C.byref(self._w), C.byref(b), C.byref(ctx)), "ssrhip_lm_create")
         self._ctx = ctx
-        if self._stream is not None:              # before the first step is enqueued or captured; stream_w16 gives the pairing slot back
-            rec, setter = self.a._packed_struct(self._stream.order), "ssrhip_lm_set_" + self._stream.name
+        if self._stream is not None:              # before the first step is enqueued or captured; a <= 4-row stream gives the pairing slot back
+            rec, setter = self.a.order_struct(self._stream.order), "ssrhip_lm_set_" + self._stream.name
             _lib.check(getattr(self.lib, setter)(ctx, C.byref(rec)), setter)
-            if self.pair_w16 and self.pair_mode != 1:     # (check_pairs sets pair_mode 1 after a give-up: that engine steps unpaired)
-                _lib.check(self.lib.ssrhip_lm_set_w16_pair(ctx, 1), "ssrhip_lm_set_w16_pair")
-        if self.stream_w8:                        # the fourth packed kind; gives the pairing slot back like stream_w16
-            rec8 = self.a.w8_struct()
-            _lib.check(self.lib.ssrhip_lm_set_w8(ctx, C.byref(rec8)), "ssrhip_lm_set_w8")
-            if self.pair_w8 and self.pair_mode != 1:      # (as for pair_w16: after a give-up the engine steps unpaired)
-                _lib.check(self.lib.ssrhip_lm_set_w8_pair(ctx, 1), "ssrhip_lm_set_w8_pair")
-        if self.pair4 and self.pair_mode != 1:    # the 4-row step's pair launches over the fp32 masters (after a give-up: unpaired)
-            _lib.check(self.lib.ssrhip_lm_set_pair4(ctx, 1), "ssrhip_lm_set_pair4")
-        if self.pair4_pk and self.pair_mode != 1:     # ... over the packed stream set above (after a give-up: unpaired)
-            _lib.check(self.lib.ssrhip_lm_set_pair4_pk(ctx, 1), "ssrhip_lm_set_pair4_pk")
-        if self.stream_wt8:                       # the e4m3 stream of the 5..16-row step (no pairing at these rows)
-            rec8 = self.a.wt8_struct()
-            _lib.check(self.lib.ssrhip_lm_set_wt8(ctx, C.byref(rec8)), "ssrhip_lm_set_wt8")
+        if self.plan.pair is not None and self.pair_mode != 1:    # (check_pairs sets pair_mode 1 after a give-up: that engine steps unpaired)
+            setter = "ssrhip_lm_set_" + self.plan.pair.c_name     # over the stream set above, or the fp32 masters (pair4)
+            _lib.check(getattr(self.lib, setter)(ctx, 1), setter)
         if self.kv16_small:                       # <= 4 rows: the 2-byte pool and the landing cache of the QKV launch's append
             _lib.check(self.lib.ssrhip_lm_set_kv16_small(ctx, self.kv_land.data_ptr(), self.kv_land_table.data_ptr(), self.kv_land_pos.data_ptr()),
                        "ssrhip_lm_set_kv16_small")
@@ -1358,7 +1297,7 @@ class DecodeEngine:
         self.pairing = bool(self.lib.ssrhip_lm_pairing(ctx, why, 256))
         self.pairing_why = why.value.decode(errors="replace")
 
-    def _launches_per_step(self, name: str) -> int:
+    def _launches_per_step(self, name: str) -> int:       # the `<name>_launches_per_step` properties (COUNTERS, below the class)
         return 0 if self._ctx is None else int(getattr(self.lib, f"ssrhip_lm_{name}_launches")(self._ctx))
 
     @property
@@ -1370,69 +1309,6 @@ class DecodeEngine:
     def kv_landing_bytes(self) -> int:
         """Bytes of the fp32 landing cache a kv16_small engine holds beside its pool (rows x 2 x d_model x 128 x 4; 0 otherwise)."""
         return 0 if self.kv_land is None else self.kv_land.numel() * self.kv_land.element_size()
-
-    @property
-    def kv16_launches_per_step(self) -> int:
-        """Attention launches of the last enqueued decode step that read the bf16 KV cache (the layer count for a kv_dtype="bf16" engine,
-        0 otherwise)."""
-        return 0 if self._ctx is None else int(self.lib.ssrhip_lm_kv16_launches(self._ctx))
-
-    @property
-    def group_launches_per_step(self) -> int:
-        """Attention launches of the last enqueued decode step that ran the grouped walk (the layer count for a share_prompt engine, else 0)."""
-        return self._launches_per_step("group")
-
-    @property
-    def w16_launches_per_step(self) -> int:
-        """GEMV launches of the last enqueued decode step that ran a bf16-stream kernel (4 * layers + 2 when every family qualifies;
-        0 for an engine that streams fp32 weights or has not stepped yet)."""
-        return self._launches_per_step("w16")
-
-    @property
-    def w16_pair_launches_per_step(self) -> int:
-        """Pair launches of the last enqueued decode step that streamed packed bf16 weights (2 * layers when every family has a packed
-        copy; `w16_launches_per_step` then counts the two single launches left). 0 for an engine that does not pair its bf16 stream."""
-        return self._launches_per_step("w16_pair")
-
-    @property
-    def w8_launches_per_step(self) -> int:
-        """GEMV launches of the last enqueued decode step that ran an e4m3-stream kernel (4 * layers + 2 when every family qualifies; 0 for
-        an engine that streams other weights or has not stepped yet)."""
-        return self._launches_per_step("w8")
-
-    @property
-    def w8_pair_launches_per_step(self) -> int:
-        """Pair launches of the last enqueued decode step that streamed e4m3 codes (2 * layers when every family has codes;
-        `w8_launches_per_step` then counts the two single launches left). 0 for an engine that does not pair its e4m3 stream."""
-        return self._launches_per_step("w8_pair")
-
-    @property
-    def pair4_launches_per_step(self) -> int:
-        """Pair launches of the last enqueued decode step that ran a 4-row pair kernel (2 * layers when both forms apply). 0 for an engine
-        that does not run the 4-row pair launches."""
-        return self._launches_per_step("pair4")
-
-    @property
-    def pair4_pk_launches_per_step(self) -> int:
-        """Pair launches of the last enqueued decode step that ran a 4-row pair kernel over packed weights (2 * layers when every family has
-        a packed copy; the stream's own counter then counts the two single launches left). 0 for an engine that does not run them."""
-        return self._launches_per_step("pair4_pk")
-
-    @property
-    def wt8_launches_per_step(self) -> int:
-        """GEMV launches of the last enqueued decode step that ran a kernel of the 5..16-row e4m3 weight stream (4 * layers + 2 when every
-        family qualifies; 0 for an engine that streams other weights or has not stepped yet)."""
-        return self._launches_per_step("wt8")
-
-    @property
-    def wt16_launches_per_step(self) -> int:
-        """The same for the kernels of the 5..16-row bf16 weight stream."""
-        return self._launches_per_step("wt16")
-
-    @property
-    def wt32_launches_per_step(self) -> int:
-        """The same for the kernels of the 17..32-row bf16 weight stream."""
-        return self._launches_per_step("wt32")
 
     def close(self):
         if self._ctx is not None:
@@ -1814,7 +1690,7 @@ class DecodeEngine:
             return
         rc = self.lib.ssrhip_lm_pair_status(self._ctx, _lib.stream_ptr())
         if rc == 1:
-            self.pair_mode = 1
+            self.plan = self.plan._replace(pair_mode=1)
             self._create_ctx()                    # destroys the context (gives the slot back), new one steps with the ordinary launches
             raise RuntimeError("a paired GEMV launch of the decode step gave up waiting for its other workgroups (another kernel held CUs "
                                "for about a second): every token since the last poll is invalid and the utterances in flight must be "
@@ -2090,3 +1966,34 @@ class DecodeEngine:
         _lib.check(self.lib.ssrhip_lm_time_category(self._ctx, ("gemv", "attn", "sample").index(kind), int(n_replays),
                                                     _lib.stream_ptr(), C.byref(us), C.byref(n)), "ssrhip_lm_time_category")
         return float(us.value), int(n.value)
+
+
+# DecodeEngine's read-only views of its plan: `stream_<name>` / `<pair form>` = is that entry the plan's; the rest are the plan's fields.
+for _st in STREAMS:
+    setattr(DecodeEngine, "stream_" + _st.name, property(lambda self, _st=_st: self.plan.stream is _st))
+for _pf in PAIR_FORMS:
+    setattr(DecodeEngine, _pf.name, property(lambda self, _pf=_pf: self.plan.pair is _pf))
+for _name, _field in (("_stream", "stream"), ("pair_mode", "pair_mode"), ("kv_dtype", "kv_dtype"), ("kv16_small", "kv16_small"),
+                      ("share_prompt", "share_prompt"), ("want_logprobs", "logprobs")):
+    setattr(DecodeEngine, _name, property(lambda self, _field=_field: getattr(self.plan, _field)))
+
+# DecodeEngine's `<name>_launches_per_step` properties: what `ssrhip_lm_<name>_launches` counted in the last enqueued decode step (0 for an
+# engine that has not stepped yet).
+COUNTERS = (
+    ("kv16", "Attention launches that read the bf16 KV cache (the layer count for a kv_dtype=\"bf16\" engine, 0 otherwise)."),
+    ("group", "Attention launches that ran the grouped walk (the layer count for a share_prompt engine, else 0)."),
+    ("w16", "GEMV launches that ran a bf16-stream kernel (4 * layers + 2 when every family qualifies; 0 for an engine that streams fp32 weights)."),
+    ("w16_pair", "Pair launches that streamed packed bf16 weights (2 * layers when every family has a packed copy; `w16_launches_per_step` then "
+                 "counts the two single launches left). 0 for an engine that does not pair its bf16 stream."),
+    ("w8", "GEMV launches that ran an e4m3-stream kernel (4 * layers + 2 when every family qualifies; 0 for an engine that streams other weights)."),
+    ("w8_pair", "Pair launches that streamed e4m3 codes (2 * layers when every family has codes; `w8_launches_per_step` then counts the two "
+                "single launches left). 0 for an engine that does not pair its e4m3 stream."),
+    ("pair4", "Pair launches that ran a 4-row pair kernel (2 * layers when both forms apply). 0 for an engine that does not run them."),
+    ("pair4_pk", "Pair launches that ran a 4-row pair kernel over packed weights (2 * layers when every family has a packed copy; the stream's "
+                 "own counter then counts the two single launches left). 0 for an engine that does not run them."),
+    ("wt8", "GEMV launches that ran a kernel of the 5..16-row e4m3 weight stream (4 * layers + 2 when every family qualifies)."),
+    ("wt16", "The same for the kernels of the 5..16-row bf16 weight stream."),
+    ("wt32", "The same for the kernels of the 17..32-row bf16 weight stream."),
+)
+for _name, _doc in COUNTERS:
+    setattr(DecodeEngine, _name + "_launches_per_step", property(lambda self, _name=_name: self._launches_per_step(_name), doc=_doc))

@@ -24,11 +24,51 @@ import torch.nn as nn
 from .. import _lib
 from .. import layout as LY
 from .. import score as SC
-from ..engine import (DEFAULT_GROUP_ROWS, KV_DTYPES, MAX_ROWS, WEIGHT_DTYPES, DecodeEngine, DecodeKnobs, LMWeightsArena, PhiloxNoise, SAMPLING_RNGS,
-                      TorchCpuNoiseFeed, W16_STREAMS, resolve_kv16_small, resolve_kv_dtype, resolve_pair4, resolve_pair4_pk, resolve_sampling_rng, resolve_share_prompt, resolve_w16_pair, resolve_w16_stream, resolve_w8_pair, resolve_w8_stream)
+from ..engine import (DEFAULT_GROUP_ROWS, KV16_MAX_PAGES, KV_DTYPES, MAX_ROWS, PAIR_FORMS, SAMPLING_RNGS, STREAMS, WEIGHT_DTYPES, DecodeEngine,
+                      DecodeKnobs, DecodePlan, LMWeightsArena, PhiloxNoise, TorchCpuNoiseFeed, resolve_decode_plan, resolve_sampling_rng)
 from ..weights import lm_param_specs
 
 TokenLogprobs = LY.TokenLogprobs          # the fifth element of `inference(..., return_logprobs=True)` results
+
+
+class EngineKey(NamedTuple):
+    """What `SSR_Speech._get_engine` files a DecodeEngine under: its plan (built as the engine builds it, so every switch the plan reads
+    is part of the key), its shape and its capacities. `pool`: the KV pages the engine holds — of a request, the pages it needs;
+    `exact_pool`: the pool an engine built for this request gets."""
+    plan: DecodePlan
+    n_utt: int
+    use_cfg: bool
+    debug: bool
+    page_order: Optional[tuple]
+    cap_seq: int
+    cap_steps: int
+    pool: int
+    exact_pool: int
+
+    def covers(self, want: "EngineKey") -> bool:
+        """Does the engine filed under this key serve the request `want`? The same decisions and shape, and capacities that cover it.
+        `max_pages` follows the capacity and `kv_dtype` may (a bf16 cache has a page cap): an engine built larger serves as it was built.
+        A caller-chosen page order (tests) pins the pool size exactly."""
+        same = lambda k: (k.plan._replace(max_pages=0, kv_dtype=""), k.n_utt, k.use_cfg, k.debug, k.page_order)
+        return same(self) == same(want) and self.cap_seq >= want.cap_seq and self.cap_steps >= want.cap_steps \
+            and (self.pool >= want.pool if want.page_order is None else self.pool == want.exact_pool)
+
+
+def engine_key(weight_dtype: str, n_layers: int, kv_default: str, n_utt: int, use_cfg: bool, cap_seq: int, cap_steps: int, env,
+               need_pages: Optional[int] = None, share_prompt: bool = False, logprobs: bool = False, debug: bool = False,
+               page_order: Optional[Sequence[int]] = None) -> EngineKey:
+    """The key of the engine `_get_engine` wants: the plan of an engine nobody asked anything of (every request None: the switches in
+    `env` and the model's cache type decide) plus the caller's logprobs and, where the engine can serve it, prompt sharing — <= 4 rows, a
+    bf16 cache or more than KV16_MAX_PAGES pages per row run unshared. Pure."""
+    rows = n_utt * (2 if use_cfg else 1)
+    plan = resolve_decode_plan(rows, weight_dtype, n_layers, cap_seq, env, logprobs=logprobs, kv_default=kv_default)
+    if share_prompt and rows > 4 and plan.kv_dtype == "fp32" and plan.max_pages <= KV16_MAX_PAGES:
+        plan = plan._replace(share_prompt=True)
+    # KV pool: `need_pages` = sum over rows of the pages each row can reach (short and long utterances share one pool); never more
+    # than rows x pages-per-row
+    need = rows * plan.max_pages if need_pages is None else min(rows * plan.max_pages, int(need_pages))
+    return EngineKey(plan, n_utt, bool(use_cfg), bool(debug), tuple(page_order) if page_order is not None else None, cap_seq, cap_steps, need,
+                     min(rows * plan.max_pages, ((need + 7) // 8) * 8))
 
 
 def _set_param(root: nn.Module, dotted: str, p: nn.Parameter):
@@ -310,44 +350,23 @@ class SSR_Speech(nn.Module):
             for e in self._engines.values():
                 e.close()
             self._engines = {}
-        rows = n_utt * (2 if use_cfg else 1)
-        # the bf16 cache of the 1/2/4-row step: the engine reads SSRHIP_ATTN_KV16_SMALL when it is built; the answer is part of the key
-        kv16_small = resolve_kv16_small(rows, None, self._kv_dtype, None, os.environ)
-        kv_dtype = "bf16" if kv16_small else resolve_kv_dtype(rows, None, self._kv_dtype, cap_seq // 128)
-        # prompt sharing is the caller's request where the engine can serve it: <= 4 rows, a bf16 cache or more than 256 pages per row run unshared
-        share = bool(share_prompt) and rows > 4 and kv_dtype == "fp32" and cap_seq // 128 <= 256 and resolve_share_prompt(rows, True, kv_dtype)
-        # KV pool: `need_pages` = sum over rows of the pages each row can reach (short and long utterances share one pool); never more
-        # than rows x pages-per-row
-        need = rows * (cap_seq // 128)
-        if need_pages is not None:
-            need = min(need, int(need_pages))
-        order_key = tuple(self.page_order) if self.page_order is not None else None
+        want = engine_key(self._arena.weight_dtype, self._arena.L, self._kv_dtype, n_utt, use_cfg, cap_seq, cap_steps, os.environ, need_pages=need_pages,
+                          share_prompt=share_prompt, logprobs=logprobs, debug=self.debug_logits, page_order=self.page_order)
         # reuse: any resident engine of the same shape whose capacities cover the request (a batch of other lengths must not re-allocate
-        # the pool, the noise buffer and re-capture the graph); a caller-chosen page order (tests) pins the pool size exactly
-        # pair launches over the bf16 weight stream: the engine reads SSRHIP_GEMV_W16_PAIR when it is built; the answer is part of the key
-        w16_pair = resolve_w16_pair(rows, resolve_w16_stream(W16_STREAMS[0], rows, self._arena.weight_dtype, None, os.environ), 0, None, os.environ)
-        # ... and so is SSRHIP_GEMV_W8_PAIR's for the e4m3 stream
-        w8_pair = resolve_w8_pair(rows, resolve_w8_stream(rows, self._arena.weight_dtype, None, os.environ), 0, None, os.environ)
-        # ... and SSRHIP_GEMV_PAIR4's for the 4-row step over the fp32 masters
-        pair4 = resolve_pair4(rows, resolve_w16_stream(W16_STREAMS[0], rows, self._arena.weight_dtype, None, os.environ),
-                              resolve_w8_stream(rows, self._arena.weight_dtype, None, os.environ), 0, None, os.environ)
-        # ... and SSRHIP_GEMV_PAIR4_PK's for the 4-row step over a packed stream
-        pair4_pk = resolve_pair4_pk(rows, resolve_w16_stream(W16_STREAMS[0], rows, self._arena.weight_dtype, None, os.environ),
-                                    resolve_w8_stream(rows, self._arena.weight_dtype, None, os.environ), 0, None, os.environ)
-        for (k_utt, k_cfg, k_seq, k_steps, k_dbg, k_pool, k_order, k_share, k_wp, k_wp8, k_kvs, k_p4, k_p4pk, k_lp), e in self._engines.items():
-            if (k_utt, k_cfg, k_dbg, k_order, k_share, k_wp, k_wp8, k_kvs, k_p4, k_p4pk, k_lp) == (n_utt, use_cfg, bool(self.debug_logits), order_key, share, w16_pair, w8_pair, kv16_small, pair4, pair4_pk, bool(logprobs)) and k_seq >= cap_seq and k_steps >= cap_steps \
-                    and (k_pool >= need if order_key is None else k_pool == min(rows * (cap_seq // 128), ((need + 7) // 8) * 8)):
+        # the pool, the noise buffer and re-capture the graph)
+        for key, e in self._engines.items():
+            if key.covers(want):
                 return e
-        pool = min(rows * (cap_seq // 128), ((need + 7) // 8) * 8)
-        key = (n_utt, use_cfg, cap_seq, cap_steps, bool(self.debug_logits), pool, order_key, share, w16_pair, w8_pair, kv16_small, pair4, pair4_pk, bool(logprobs))
         for e in self._engines.values():         # one engine (KV pool) resident at a time
             e.close()
         self._engines = {}
+        key, plan = want._replace(pool=want.exact_pool), want.plan
         order = None
         if self.page_order is not None:          # tests: a caller-chosen hand-out order of the physical pages
-            order = [p for p in self.page_order if p < pool] if len(self.page_order) >= pool else None
-        eng = DecodeEngine(self._arena, n_utt, use_cfg, cap_seq, cap_steps, debug_logits=self.debug_logits, pool_pages=pool, page_order=order,
-                           kv_dtype=kv_dtype, share_prompt=share, kv16_small=kv16_small, logprobs=bool(logprobs))
+            order = [p for p in self.page_order if p < key.pool] if len(self.page_order) >= key.pool else None
+        eng = DecodeEngine(self._arena, n_utt, use_cfg, cap_seq, cap_steps, debug_logits=self.debug_logits, pool_pages=key.pool, page_order=order,
+                           kv_dtype=plan.kv_dtype, share_prompt=plan.share_prompt, kv16_small=plan.kv16_small, logprobs=plan.logprobs,
+                           **{"stream_" + st.name: plan.stream is st for st in STREAMS}, **{pf.name: plan.pair is pf for pf in PAIR_FORMS})
         self._engines[key] = eng
         return eng
 

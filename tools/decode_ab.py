@@ -65,7 +65,7 @@ import torch  # noqa: E402
 import ssr_speech_amd  # noqa: E402,F401
 from ssr_speech_amd import layout as LY  # noqa: E402
 from ssr_speech_amd import weights as W  # noqa: E402
-from ssr_speech_amd.engine import W16_STREAMS, DecodeEngine, DecodeKnobs, LMWeightsArena  # noqa: E402
+from ssr_speech_amd.engine import COUNTERS, W16_STREAMS, DecodeEngine, DecodeKnobs, LMWeightsArena  # noqa: E402
 from bench import synth_inputs  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -140,17 +140,9 @@ for rep in range(a.reps):
         n_done = int(eng.states()[0].n_steps)
         tok = eng.generated[0, :n_done].cpu().numpy().copy()
         r = res[name]
-        for st in W16_STREAMS:
-            r[st.name] = getattr(eng, st.name + "_launches_per_step")
-        r["w8"] = eng.w8_launches_per_step
-        r["wt8"] = eng.wt8_launches_per_step
-        r["w16_pair"] = eng.w16_pair_launches_per_step
-        r["w8_pair"] = eng.w8_pair_launches_per_step
-        r["pair4"] = eng.pair4_launches_per_step
-        r["pair4_pk"] = eng.pair4_pk_launches_per_step
+        for counter, _ in COUNTERS:
+            r[counter] = getattr(eng, counter + "_launches_per_step")
         r["pairing"] = eng.pairing
-        r["kv16"] = eng.kv16_launches_per_step
-        r["group"] = eng.group_launches_per_step
         r["pages"] = eng.pages.n_pages - eng.pages.n_free
         lp = eng.logprobs(0, n_done) if logp_of[name] else np.full((0, 4), np.nan)
         r["logp"] = f"{int((~np.isnan(lp)).sum())} of {lp.size} finite, mean {np.nanmean(lp) if lp.size else float('nan'):.4f}"
