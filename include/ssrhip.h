@@ -454,6 +454,30 @@ int ssrhip_stream_gather(const int32_t* generated, int32_t n_utt, int32_t max_st
                          const int32_t* ranges_dev, int32_t* codes_out, int32_t B, int32_t cap, int32_t bins, int32_t* flag,
                          ssrhip_stream_t stream);
 
+/* The batched watermarked stream's row mover (DESIGN.md Part I.29; csrc/stream_rows.hip): ONE launch executes a table of up to
+ * SSRHIP_STREAM_ROWS_MAX_OPS operations on fp32 buffers. Op i, for r < rows and c < width:
+ *     mode 0:  dst[r * dst_ld + c] = 0                                  (src is never read)
+ *     mode 1:  dst[r * dst_ld + c] = src[r * src_ld + c]
+ * dst_ld / src_ld are floats per row step; src_ld may be negative or 0 (a reflected edge is a copy that walks its source backwards).
+ * Copies and zeros only: the result is exact. An op whose rows all start on 16-byte boundaries and hold a multiple of 4 floats
+ * (both pointers, both steps, the width) moves 16 bytes per lane, any other op 4 bytes per lane. The table is given twice, as
+ * ssrhip_stream_gather's: `ops_host` is checked here before any HIP call — 0 <= n_ops <= SSRHIP_STREAM_ROWS_MAX_OPS, counts >= 0,
+ * mode 0 or 1, |dst_ld| >= width where rows > 1, and no op's dst range may overlap another op's dst range or any op's src range
+ * (its own included; ranges are compared as bounding address intervals) — and sizes the grid; `ops_dev` is the copy the kernel reads,
+ * pushed by the caller ahead of this call on the same stream. Returns 0 on launch, 0 without a launch when every op is empty, < 0 with
+ * ssrhip_last_error on a contract error. The record has no index in ssrhip_sizeof: its size comes back through
+ * ssrhip_stream_rows_sizeof. */
+#define SSRHIP_STREAM_ROWS_MAX_OPS 64
+typedef struct ssrhip_rows_op {
+  float* dst;
+  const float* src;        /* mode 1 only */
+  int64_t dst_ld, src_ld;  /* floats per row step */
+  int32_t rows, width;
+  int32_t mode, reserved_;
+} ssrhip_rows_op;
+int ssrhip_stream_rows_sizeof(void);
+int ssrhip_stream_rows(const ssrhip_rows_op* ops_host, const ssrhip_rows_op* ops_dev, int32_t n_ops, ssrhip_stream_t stream);
+
 /* The opt-in device-side source of the sampler's noise (DESIGN.md Part I.21; csrc/noise.hip): one launch writes the Exp(1) draws of up to
  * SSRHIP_NOISE_MAX_SEGMENTS segments — steps [first_step, first_step + n_steps) of utterance slot `slot`, drawn from the utterance's
  * 64-bit seed (seed_lo, seed_hi) — into noise[n_utt][max_steps][K][card], the buffer ssrhip_sampler_cfg.use_noise = 1 makes the

@@ -189,6 +189,15 @@ class NoiseArgs(C.Structure):
                 ("card", C.c_int32), ("n_seg", C.c_int32), ("seg", NoiseSegment * NOISE_MAX_SEGMENTS)]
 
 
+STREAM_ROWS_MAX_OPS = 64   # include/ssrhip.h SSRHIP_STREAM_ROWS_MAX_OPS
+
+
+class RowsOp(C.Structure):
+    """ssrhip_rows_op. Not in ABI_STRUCTS (ssrhip_sizeof knows no index for it): `lib()` checks it through ssrhip_stream_rows_sizeof."""
+    _fields_ = [("dst", C.c_void_p), ("src", C.c_void_p), ("dst_ld", C.c_int64), ("src_ld", C.c_int64), ("rows", C.c_int32),
+                ("width", C.c_int32), ("mode", C.c_int32), ("reserved_", C.c_int32)]
+
+
 # every symbol include/ssrhip.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("ssrhip_version", C.c_int, []),
@@ -235,6 +244,8 @@ SYMBOLS = [
     ("ssrhip_sample_logp", C.c_int, [C.POINTER(SampleArgs), C.c_void_p, C.c_void_p]),
     ("ssrhip_stream_gather", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                        C.c_int32, C.c_void_p, C.c_void_p]),
+    ("ssrhip_stream_rows_sizeof", C.c_int, []),
+    ("ssrhip_stream_rows", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     ("ssrhip_noise_sizeof", C.c_int, []),
     ("ssrhip_noise_philox", C.c_int, [C.POINTER(NoiseArgs), C.c_void_p]),
     ("ssrhip_gemm", C.c_int, [C.POINTER(GemmArgs), C.c_void_p]),
@@ -341,6 +352,8 @@ def lib():
         raise SsrHipUnavailable(f"ABI mismatch: sizeof(LMW8) = {C.sizeof(LMW8)} but the library says {L.ssrhip_lm_w8_sizeof()}")
     if L.ssrhip_noise_sizeof() != C.sizeof(NoiseArgs):
         raise SsrHipUnavailable(f"ABI mismatch: sizeof(NoiseArgs) = {C.sizeof(NoiseArgs)} but the library says {L.ssrhip_noise_sizeof()}")
+    if L.ssrhip_stream_rows_sizeof() != C.sizeof(RowsOp):
+        raise SsrHipUnavailable(f"ABI mismatch: sizeof(RowsOp) = {C.sizeof(RowsOp)} but the library says {L.ssrhip_stream_rows_sizeof()}")
     _lib = L
     return L
 

@@ -14,7 +14,7 @@ import contextlib
 import ctypes as C
 import math
 import os
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -516,7 +516,9 @@ class WMEncodecModel:
         a.strideA, a.strideC, a.strideR = sA, sC, sR
         a.tm_c, a.tm_lo, a.tm_hi = tm
         if rowcls is not None:           # (class bias [n_class][N], class ids int32 [batch][n], rows per id)
-            a.rbias, a.rclass, a.rrep, a.rclass_stride = rowcls[0].data_ptr(), rowcls[1].data_ptr(), int(rowcls[2]), int(rowcls[1].shape[1])
+            # (the ids' item stride: shape[1] for a dense [batch][n]; a batched stream hands in a window of columns of a wider array)
+            a.rbias, a.rclass, a.rrep = rowcls[0].data_ptr(), rowcls[1].data_ptr(), int(rowcls[2])
+            a.rclass_stride = int(rowcls[1].stride(0)) if batch > 1 else int(rowcls[1].shape[1])
         self._call("ssrhip_gemm", C.byref(a))
 
     def _fill_pads(self, buf: TM, structural_zero: bool = False):
@@ -867,6 +869,15 @@ class WMEncodecModel:
         to `max_frames` frames (create the stream before the decode engine's first launch); `max_window` = frames of one pass over the
         skip encoder's convolutions, and of one pass over the decoder's layers behind its LSTM."""
         return WMDecodeStream(self, int(max_frames), int(max_window))
+
+    def wmdecode_stream_batch(self, prompt_lens: Sequence[int], max_new_frames: int, max_window: int = 16) -> "BatchWMDecodeStream":
+        """`wmdecode_stream` for B utterances whose frames are generated in lock-step as zero-shot TTS: item u has a prompt of
+        prompt_lens[u] frames (`push_prompts(codes, audio)`: label 0, its original audio in the kept-audio track; never returned) and at
+        most `max_new_frames` generated ones (label 1, silence); `advance(new_frames, ended)` returns, per item, the watermarked samples
+        that have become final. Per item the concatenation is `wmdecode(..., with_mark=False)` of that item at batch 1, without its
+        prompt part, within the bound that holds a batched decode to the batch-1 one. Every buffer is allocated here
+        (`BatchWMDecodeStream`)."""
+        return BatchWMDecodeStream(self, [int(p) for p in prompt_lens], int(max_new_frames), int(max_window))
 
     # ------------------------------------------------------------------ ragged batches (items of different lengths in one pass)
     # cost model of one dense pass over a bucket, in microseconds per frame of its longest item: every frame is one LSTM time step
@@ -1298,6 +1309,35 @@ class DecodeStream(_StreamCore):
 
 
 # ----------------------------------------------------------------------------- streamed watermarked decode (DESIGN.md Part I.17)
+def _wm_stream_cut(st: "_StreamCore", model: WMEncodecModel, entry: str, max_window: int):
+    """What the watermarked streams (`WMDecodeStream`, `BatchWMDecodeStream`) share ahead of their buffers: `_StreamCore` over the
+    watermark decoder's nodes, the skip encoder cut as `_wmdecode_dense` cuts it, the margins and the rows per frame of the taps."""
+    if not model.has_wm:
+        raise ValueError(f"{entry}: this codec has no watermark decoder")
+    cfg = model.cfg
+    r = list(cfg.ratios)
+    senc, dec = model.skip_encoder, model.wmdecoder
+    rest = senc.slice_nodes(11, None)
+    if len(r) != 4 or [n[1] for n in rest] != ["conv", "lstm", "conv"] or [n[1] for n in dec.nodes[:3]] != ["conv", "lstm", "convtr"]:
+        raise NotImplementedError(f"{entry}: the watermark decoder's slicing (seanet.py:560-591) is written for 4 ratios and an LSTM")
+    _StreamCore.__init__(st, model, entry, max_window, nodes=dec.nodes)       # (not DecodeStream's: other buffers)
+    # the skip encoder, cut as `_wmdecode_dense` cuts it; its last slice once more, around the LSTM
+    st.ch_head = senc.slice_nodes(0, 2)
+    st.ch_cuts = [senc.slice_nodes(lo, hi) for lo, hi in ((2, 5), (5, 8), (8, 11))]
+    st.ch_last, st.sk_lstm_node, st.sk_conv = rest[0], rest[1], rest[2][2]
+    st.sk_lstm = rest[1][2]
+    c = st.sk_conv
+    if not (c.s == 1 and c.Cin == st.sk_lstm.C and c.Cout > 4):
+        raise NotImplementedError(f"{entry}: the skip encoder does not end with a stride-1 convolution behind its LSTM")
+    st.smargins = skip_stream_margins(cfg)
+    st.holdback = wm_stream_holdback(cfg)
+    st.reps = [r[0] * r[1] * r[2], r[0] * r[1], r[0]]          # rows per frame of the taps, in the chain's order
+    # the decoder behind its LSTM, cut where the taps enter: [convtr] | [res, convtr] | [res, convtr] | [res, convtr, res, conv]
+    dn = [dec.slice_nodes(lo, hi) for lo, hi in ((0, 4), (4, 7), (7, 10), (10, None))]
+    st.dn = [dn[0][2:]] + dn[1:]
+    assert [n for part in st.dn for n in part] == list(st.tail)
+
+
 class WMDecodeStream(DecodeStream):
     """`WMEncodecModel.wmdecode_stream`: `_wmdecode_dense` of one utterance (B = 1, no detector pass), advanced as its frames arrive.
     Frame t is row t of every frame-rate buffer. Per `push`, in this order, each stage as far as its input allows:
@@ -1320,30 +1360,8 @@ class WMDecodeStream(DecodeStream):
     def __init__(self, model: WMEncodecModel, max_frames: int, max_window: int):
         if max_frames < 1 or max_window < 1:
             raise ValueError("wmdecode_stream needs max_frames >= 1 and max_window >= 1")
-        if not model.has_wm:
-            raise ValueError("wmdecode_stream: this codec has no watermark decoder")
-        cfg, dev = model.cfg, model.device
-        r = list(cfg.ratios)
-        senc, dec = model.skip_encoder, model.wmdecoder
-        rest = senc.slice_nodes(11, None)
-        if len(r) != 4 or [n[1] for n in rest] != ["conv", "lstm", "conv"] or [n[1] for n in dec.nodes[:3]] != ["conv", "lstm", "convtr"]:
-            raise NotImplementedError("wmdecode_stream: the watermark decoder's slicing (seanet.py:560-591) is written for 4 ratios and an LSTM")
-        _StreamCore.__init__(self, model, "wmdecode_stream", max_window, nodes=dec.nodes)       # (not DecodeStream's: other buffers)
-        # the skip encoder, cut as `_wmdecode_dense` cuts it; its last slice once more, around the LSTM
-        self.ch_head = senc.slice_nodes(0, 2)
-        self.ch_cuts = [senc.slice_nodes(lo, hi) for lo, hi in ((2, 5), (5, 8), (8, 11))]
-        self.ch_last, self.sk_lstm_node, self.sk_conv = rest[0], rest[1], rest[2][2]
-        self.sk_lstm: _Lstm = rest[1][2]
-        c = self.sk_conv
-        if not (c.s == 1 and c.Cin == self.sk_lstm.C and c.Cout > 4):
-            raise NotImplementedError("wmdecode_stream: the skip encoder does not end with a stride-1 convolution behind its LSTM")
-        self.smargins = skip_stream_margins(cfg)
-        self.holdback = wm_stream_holdback(cfg)
-        self.reps = [r[0] * r[1] * r[2], r[0] * r[1], r[0]]          # rows per frame of the taps, in the chain's order
-        # the decoder behind its LSTM, cut where the taps enter: [convtr] | [res, convtr] | [res, convtr] | [res, convtr, res, conv]
-        dn = [dec.slice_nodes(lo, hi) for lo, hi in ((0, 4), (4, 7), (7, 10), (10, None))]
-        self.dn = [dn[0][2:]] + dn[1:]
-        assert [n for part in self.dn for n in part] == list(self.tail)
+        _wm_stream_cut(self, model, "wmdecode_stream", max_window)
+        cfg, dev, c = model.cfg, model.device, self.sk_conv
         self.cap = cap = max_frames
         hop, D, Cs = self.hop, cfg.dimension, self.sk_lstm.C
         f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
@@ -1769,3 +1787,439 @@ class BatchDecodeStream(_StreamCore):
     @property
     def finished(self) -> bool:
         return all(self.closed) and all(self.n2[u] >= self.top[u] for u in range(self.B))
+
+
+# ----------------------------------------------------------------------------- streamed watermarked decode of a lock-step batch (DESIGN.md Part I.29)
+class RowOp(NamedTuple):
+    """One entry of an `ssrhip_stream_rows` table, in FLOATS from the start of its destination / source buffer (the stream adds the
+    buffers' addresses): `rows` rows of `width` floats, `dst_ld` / `src_ld` floats apart; mode 0 zeroes, mode 1 copies."""
+    dst: int
+    src: int
+    rows: int
+    width: int
+    dst_ld: int
+    src_ld: int
+    mode: int
+
+
+def rows_front_zero(offs: Sequence[int], a: int, b: int, item_rows: int, C: int) -> List[RowOp]:
+    """Zero the rows [a, min(b, off_u)) of every item u of a [B][item_rows][C] buffer: the part of a batched call over the rows [a, b)
+    that lies in front of the item's first frame."""
+    return [RowOp((u * item_rows + a) * C, 0, min(b, o) - a, C, C, 0, 0) for u, o in enumerate(offs) if a < min(b, o)]
+
+
+def rows_right_edge(u: int, end: int, pad: int, reflect: bool, item_rows: int, C: int) -> RowOp:
+    """Item u has ended at row `end`: the `pad` rows behind it hold the consuming convolution's own padding — zeros, or the item's
+    rows mirrored at its last one (row end + i <- row end - 2 - i: a copy that walks its source backwards)."""
+    d = (u * item_rows + end) * C
+    return RowOp(d, d - 2 * C, pad, C, C, -C, 1) if reflect else RowOp(d, 0, pad, C, C, 0, 0)
+
+
+def rows_left_edge(u: int, off: int, pad: int, item_rows: int, C: int) -> RowOp:
+    """Reflect padding in front of item u's first row `off`: row off - pad + j <- row off + pad - j."""
+    return RowOp((u * item_rows + off - pad) * C, (u * item_rows + off + pad) * C, pad, C, C, -C, 1)
+
+
+def rows_core_copy(pairs: Sequence[Tuple[int, int]], c0: int, c1: int, lo: int, rep: int, C: int, dst_item: int, src_item: int,
+                   src_pad: int = 0) -> List[RowOp]:
+    """A window's core into a whole-utterance buffer: for (item u, slot j of the window's buffer) in `pairs`, the rows
+    [c0 rep, c1 rep) of item u of dst [B][...][C] (`dst_item` floats per item) <- the rows from src_pad + (c0 - lo) rep on of slot j
+    (`src_item` floats per slot). The core is contiguous on both sides. Every item in its own slot, in order: ONE op whose "rows"
+    are the items."""
+    n, d0, s0 = (c1 - c0) * rep * C, c0 * rep * C, (src_pad + (c0 - lo) * rep) * C
+    if len(pairs) > 1 and all(u == j == i for i, (u, j) in enumerate(pairs)):
+        return [RowOp(d0, s0, len(pairs), n, dst_item, src_item, 1)]
+    return [RowOp(u * dst_item + d0, j * src_item + s0, 1, n, dst_item, src_item, 1) for u, j in pairs]
+
+
+def chain_window_item(off: int, nA: int, top: int, ended: bool, margins: Tuple[int, int], max_window: int):
+    """The next skip-encoder chain window of ONE item of a `BatchWMDecodeStream`, in rows -> (c0, c1, lo, hi), ("skip", c1) when the
+    whole core lies in front of the item's first frame (nothing to compute), or None (nothing to do yet). off = the item's first row,
+    nA = the row its chain has reached, top = the row behind its last arrived frame; an item that has `ended` runs to `top`, a true
+    edge, a live one to top less the right margin. A window that would reach in front of `off` is cut there: a true edge too."""
+    limit = top if ended else top - margins[1]
+    if nA >= limit:
+        return None
+    c1 = min(nA + max_window, limit)
+    if c1 <= off:
+        return ("skip", c1)
+    c0 = max(nA, off)
+    return c0, c1, max(off, c0 - margins[0]), min(top, c1 + margins[1])
+
+
+class _TMRows(TM):
+    """Rows of a larger [B][rows][C] buffer without halo, read in place: the items are `bstride` elements apart."""
+
+    def __init__(self, data: torch.Tensor, bstride: int, device):
+        super().__init__(int(data.shape[0]), int(data.shape[1]), int(data.shape[2]), 0, 0, device, data=data, keep_halo=True)
+        self._bstride = int(bstride)
+
+    @property
+    def bstride(self) -> int:
+        return self._bstride
+
+
+class _RowOpTable:
+    """The tables of a stream's `ssrhip_stream_rows` launches: filled on the host (pinned memory), pushed to the device copy on the
+    caller's stream without waiting for it, launched. A ring of slots, each with an event that says its push has been read: a slot is
+    written again only after that. Created with the stream; nothing is allocated later."""
+    SLOTS = 32
+
+    def __init__(self, model: WMEncodecModel):
+        self.m = model
+        size = _lib.STREAM_ROWS_MAX_OPS * C.sizeof(_lib.RowsOp)
+        self.host = torch.zeros(self.SLOTS, size, dtype=torch.uint8).pin_memory()
+        self.dev = torch.zeros(self.SLOTS, size, dtype=torch.uint8, device=model.device)
+        self.recs = [(_lib.RowsOp * _lib.STREAM_ROWS_MAX_OPS).from_address(self.host[i].data_ptr()) for i in range(self.SLOTS)]
+        self.events = [torch.cuda.Event() for _ in range(self.SLOTS)]
+        self.used = [False] * self.SLOTS
+        self.slot, self.n, self.launches = 0, 0, 0
+
+    @staticmethod
+    def _inside(at: int, ld: int, rows: int, width: int, buf: torch.Tensor) -> bool:
+        last = (rows - 1) * ld
+        return at + min(last, 0) >= 0 and at + max(last, 0) + width <= buf.numel()
+
+    def add(self, ops: Sequence[RowOp], dst: torch.Tensor, src: Optional[torch.Tensor] = None):
+        """`ops` with their offsets turned into addresses: dst / src = the (dense) buffers the offsets count from. An op that would
+        leave its buffer is an error here, before anything is launched."""
+        for op in ops:
+            if op.rows <= 0 or op.width <= 0:
+                continue
+            if not self._inside(op.dst, op.dst_ld, op.rows, op.width, dst) or (op.mode and not self._inside(op.src, op.src_ld, op.rows, op.width, src)):
+                raise RuntimeError(f"BatchWMDecodeStream: the row operation {tuple(op)} leaves its buffer")
+            if self.n == _lib.STREAM_ROWS_MAX_OPS:
+                self.launch()
+            if self.n == 0 and self.used[self.slot]:
+                self.events[self.slot].synchronize()                   # the slot's last push has left the host
+            r = self.recs[self.slot][self.n]
+            r.dst, r.src = dst.data_ptr() + 4 * op.dst, (src.data_ptr() + 4 * op.src if op.mode else 0)
+            r.dst_ld, r.src_ld, r.rows, r.width, r.mode, r.reserved_ = op.dst_ld, op.src_ld, op.rows, op.width, op.mode, 0
+            self.n += 1
+
+    def launch(self):
+        """One launch for everything added since the last one (none when nothing was)."""
+        if self.n == 0:
+            return
+        i, size = self.slot, self.n * C.sizeof(_lib.RowsOp)
+        self.dev[i, :size].copy_(self.host[i, :size], non_blocking=True)
+        self.events[i].record(torch.cuda.current_stream(self.m.device))
+        self.used[i] = True
+        self.m._call("ssrhip_stream_rows", self.host[i].data_ptr(), self.dev[i].data_ptr(), self.n)
+        self.slot, self.n = (i + 1) % self.SLOTS, 0
+        self.launches += 1
+
+
+class BatchWMDecodeStream(BatchDecodeStream):
+    """`WMEncodecModel.wmdecode_stream_batch`: the watermarked decode (`wmdecode(..., with_mark=False)`) of B utterances that are
+    generated in lock-step as zero-shot TTS — `WMDecodeStream`'s seven steps on `BatchDecodeStream`'s aligned axis, each step ONE dense
+    batched call of the kernel `WMDecodeStream` calls for it.
+
+    The axis (`batch_align_plan` with F = the larger left padding of the two frame-rate convolutions in front): item u's frame t is
+    row off_u + t of every frame-rate buffer [B][rows][C]; the prompts end at row E, generated frame j of every item is row E + j. The
+    kept-audio track holds item u's original audio under its prompt and silence from row E on; the label is 0 below E and 1 from E on.
+
+    Per `advance`: the dequantiser into `q`; chain windows (`chain_window_item`, grouped by `batch_window_groups`) whose cores go into
+    the whole-utterance taps and `p`; the skip encoder's LSTM over a common row range (`batch_stage1_range`) into `u`; tap 4 and `z`
+    (two GEMMs with batch = B); the decoder's first convolution and LSTM; stage-2 windows with `_concat_proj` reading the stored taps
+    in place. What is per item — the zero rows in front of a short prompt (`p`, `y0` and all four `gin`s: with biases in the skip
+    encoder the chain over a zero track is not zero), an ended item's right edges in `u`, `z` and `s1`, the reflected rows, the cores
+    of the taps and of the output — is a table of row operations executed by ONE `ssrhip_stream_rows` launch per stage.
+
+    An item that ends runs its last chain windows alone (its end is a true edge of the track); behind its end `u` and `z` get the
+    consuming convolution's own padding after every batched call that wrote there, until that convolution has passed the end; its last
+    stage-2 windows run alone. Later batched calls write junk behind a finished item's end, which nothing reads. B stays constant.
+
+    Everything runs on the caller's stream and is allocated here: create the stream before the decode engine's first launch."""
+
+    def __init__(self, model: WMEncodecModel, prompt_lens: Sequence[int], max_new_frames: int, max_window: int):
+        if max_new_frames < 1 or max_window < 1:
+            raise ValueError("wmdecode_stream_batch needs max_new_frames >= 1 and max_window >= 1")
+        _wm_stream_cut(self, model, "wmdecode_stream_batch", int(max_window))
+        cfg, dev, c = model.cfg, model.device, self.sk_conv
+        self.max_new = int(max_new_frames)
+        self.front = max(c.pl, self.pl0)
+        plan = batch_align_plan(prompt_lens, self.front)
+        self.prompt_lens = [int(p) for p in prompt_lens]
+        self.off, self.E = plan["off"], plan["E"]
+        B = len(self.off)
+        need = self.smargins[1] + max(c.pl, c.pr) + max(self.pl0, self.pr0)
+        if self.reflect and min(self.prompt_lens) <= need:
+            raise ValueError(f"wmdecode_stream_batch: with reflect padding every prompt must be longer than the chain's right margin plus "
+                             f"the paddings of the two frame-rate convolutions ({need} frames), got {self.prompt_lens}")
+        rows = self.E + self.max_new
+        hop, D, Cs = self.hop, cfg.dimension, self.sk_lstm.C
+        f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
+        self.codes = torch.zeros(B * cfg.n_q * max(max(self.prompt_lens), self.max_new), **i32)
+        self.lab = torch.zeros(B, rows, **i32)
+        self.lab[:, self.E:] = 1
+        self.track = torch.zeros(B, rows * hop, **f32)
+        self.q = torch.zeros(B, rows, D, **f32)                        # the dequantised codes
+        self.taps = [torch.zeros(B, rows * rep, part[-1][2][1].Cout, **f32) for part, rep in zip(self.ch_cuts, self.reps)]
+        self.p = torch.zeros(B, rows, Cs, **f32)                       # the chain's frame-rate rows: what the skip encoder's LSTM reads
+        nl = len(self.sk_lstm.layers)
+        self.sk_gins = [torch.zeros(B, rows, 4 * Cs, **f32) for _ in range(nl)]
+        self.sk_hbufs = [torch.zeros(2, (B + 15) // 16 * 16, Cs, **f32) for _ in range(nl)]
+        self.sk_cbufs = [torch.zeros(B, Cs, **f32) for _ in range(nl)]
+        self.sk_mids = [torch.zeros(B, rows, Cs, **f32) for _ in range(nl - 1)]
+        split = model._lstm_use_split(self.sk_lstm, B)
+        self.sk_hsplits = [torch.zeros(2 * ((B + 63) // 64) * 64 * Cs * 3, dtype=torch.int16, device=dev)
+                           if (split and self.sk_lstm.split[l] is not None) else None for l in range(nl)]
+        # LSTM + skip, what `sk_conv` reads: data row == row, the rows in front of an item's first frame are its left halo
+        self.u = TM(B, rows - c.pl, Cs, c.pl, c.pr, dev, data=torch.zeros(B, rows + c.pr, Cs, **f32))
+        self.u.elu = bool(model.elu_on_store and c.act_in)
+        self.tap4 = torch.zeros(B, rows, c.Cout, **f32)
+        self.ops = _RowOpTable(model)
+        self.top = list(self.off)                                      # row behind item u's last arrived frame
+        self.ended = [False] * B
+        self.nA = [self.front] * B                                     # row item u's chain has reached
+        self.nL = 0                                                    # row the skip encoder's LSTM has reached
+        self.nC = self.front                                           # row tap 4 and `z` have reached
+        self.closedL, self.closedC, self.closed = [False] * B, [False] * B, [False] * B     # ended, and that stage has passed the end
+        self.n2 = [self.E] * B
+        self.primed = False
+        self.chain_windows = self.chain_windows_batched = 0
+        # the chain's window buffers, of all B items at once and of one item, each by a dry pass over its largest window; those of
+        # stage 2 likewise, in `_allocate`
+        self.B, self.rows = B, rows
+        self.pool_cb, self.pool_c1 = (_WindowPool() if B > 1 else None), _WindowPool()
+        self.tap_elu = [False] * 3
+        real, model.lib = model.lib, _NoLaunch()
+        try:
+            n = min(rows, self.max_window + self.smargins[0] + self.smargins[1])
+            for item, pool in ((None, self.pool_cb), (0, self.pool_c1)):
+                if pool is not None:
+                    taps, _ = self._chain_pass(0, n, item)
+                    self.tap_elu = [t.elu for t in taps]
+                    pool.frozen = True
+        finally:
+            model.lib = real
+        self._allocate(B, rows, self.pl0, self.max_new)
+
+    @property
+    def tap_bytes(self) -> int:
+        """Bytes of the three whole-utterance tap buffers, all items"""
+        return sum(t.numel() * 4 for t in self.taps)
+
+    # ------------------------------------------------------------------ the pieces
+    def _chain_pass(self, lo: int, hi: int, item: Optional[int]) -> Tuple[List[TM], TM]:
+        """`WMDecodeStream._chain_pass` over the track's rows [lo, hi) of every item (`item` None) or of one."""
+        m, hop = self.m, self.hop
+        who = slice(None) if item is None else slice(item, item + 1)
+        with m._stream_pass(self.pool_cb if item is None else self.pool_c1, False):
+            x = m._input_tm(self.track[who, lo * hop: hi * hop].unsqueeze(1), self.ch_head[0])
+            z = m._run(self.ch_head, x, after=self.ch_cuts[0][0])
+            taps = []
+            for i, part in enumerate(self.ch_cuts):
+                z = m._run(part, z, after=(self.ch_cuts[i + 1][0] if i + 1 < len(self.ch_cuts) else self.ch_last))
+                taps.append(z)
+            return taps, m._run([self.ch_last], z, after=self.sk_lstm_node)
+
+    def _chain(self):
+        """Chain windows as far as every item allows: the items whose windows agree in ONE batched pass, the others alone (a window cut
+        at an item's first frame, an ended item's last windows)."""
+        B, ops = self.B, self.ops
+        while True:
+            wins = [chain_window_item(self.off[u], self.nA[u], self.top[u], self.ended[u], self.smargins, self.max_window) for u in range(B)]
+            skipped = False
+            for u, w in enumerate(wins):
+                if w is not None and w[0] == "skip":                  # the whole core lies in front of the item's first frame
+                    self.nA[u], wins[u], skipped = w[1], None, True
+            key, members, alone = batch_window_groups(wins)
+            if key is None and not alone:
+                if skipped:
+                    continue
+                return
+            for win, item, who in ([(key, None, members)] if key is not None else []) + [(wins[u], u, [u]) for u in alone]:
+                c0, c1, lo, hi = win
+                taps, rows = self._chain_pass(lo, hi, item)
+                pairs = [(u, u if item is None else 0) for u in who]
+                for buf, t, rep in zip(self.taps + [self.p], taps + [rows], self.reps + [1]):
+                    ops.add(rows_core_copy(pairs, c0, c1, lo, rep, t.C, buf.stride(0), t.bstride, t.padL), buf, t.data)
+                ops.launch()                                           # before the next window takes the pool's buffers
+                for u in who:
+                    self.nA[u] = c1
+                self.chain_windows += 1
+                self.chain_windows_batched += int(item is None)
+
+    def _lstm_rows(self, L: _Lstm, src: torch.Tensor, gins, hbufs, cbufs, hsplits, mids, out_ptr: int, out_bs: int, out_elu: bool, a: int, b: int):
+        """The rows [a, b) of every item through the layers of one LSTM (+ skip): `_StreamCore._stage1_rows`' loop, with the rows in front
+        of an item's first frame — the skip input `src` and every layer's `gin` — zeroed by one row-op launch ahead of each step call,
+        so that the item's state stays exactly zero (`BatchDecodeStream`)."""
+        m, B, rows, ops = self.m, self.B, self.rows, self.ops
+        bs, nl = rows * L.C, len(L.layers)
+        for l in range(nl):
+            x, last = (src if l == 0 else mids[l - 1]), l == nl - 1
+            m._lstm_in_gemm(L, l, x.data_ptr(), bs, gins[l], B, rows, a, b)
+            if l == 0:
+                ops.add(rows_front_zero(self.off, a, b, rows, L.C), src)
+            ops.add(rows_front_zero(self.off, a, b, rows, 4 * L.C), gins[l])
+            ops.launch()
+            m._lstm_steps(L, l, gins[l], hbufs[l], cbufs[l], hsplits[l], (out_ptr if last else mids[l].data_ptr()), (out_bs if last else bs),
+                          (src.data_ptr() if last else 0), bs, B, rows, a, b, out_elu and last)
+
+    def _edges(self, buf: TM, a: int, b: int, closed_in: Sequence[bool], closed_out: Sequence[bool], zero_front: bool):
+        """After a batched call has written the rows [a, b) of `buf` (data row == row; halo = the consuming convolution's paddings): an
+        item whose first frame lies in [a, b) gets that convolution's padding in front of it (zeros — `zero_front`, where the producer
+        does not leave them — or its reflected rows), an item that has ended (`closed_in`: the producer has passed its end) and whose
+        end the consumer has not passed (`closed_out`) gets it behind its end. One launch."""
+        ops, rows_b, Cc = self.ops, buf.rows, buf.C
+        for u in range(self.B):
+            off, end = self.off[u], self.top[u]
+            if self.reflect and a <= off < b:
+                assert b > off + buf.padL, (u, a, b, off)             # (the prompt lengths the constructor accepts see to it)
+                ops.add([rows_left_edge(u, off, buf.padL, rows_b, Cc)], buf.data, buf.data)
+            if closed_in[u] and not closed_out[u]:
+                ops.add([rows_right_edge(u, end, buf.padR, self.reflect, rows_b, Cc)], buf.data, buf.data)
+        if zero_front and not self.reflect:
+            ops.add(rows_front_zero(self.off, a, b, rows_b, Cc), buf.data)
+        ops.launch()
+
+    def _skip_lstm(self):
+        done = [self.ended[u] and self.nA[u] >= self.top[u] for u in range(self.B)]
+        a, b = batch_stage1_range(self.nL, [self.top[u] if done[u] else self.nA[u] for u in range(self.B)], done, self.closedL, 0)
+        b = min(b, self.rows)
+        if b > a:
+            u_ = self.u
+            self._lstm_rows(self.sk_lstm, self.p, self.sk_gins, self.sk_hbufs, self.sk_cbufs, self.sk_hsplits, self.sk_mids, u_.base, u_.bstride,
+                            u_.elu, a, b)
+            self.nL = b
+        for u in range(self.B):
+            self.closedL[u] = self.closedL[u] or (done[u] and self.top[u] <= self.nL)
+        self._edges(self.u, a, b, self.closedL, self.closedC, False)  # (in front the LSTM has written the zeros its zero state gives)
+
+    def _decoder_input(self):
+        """Tap 4 and `z` over a common row range: `WMDecodeStream._decoder_input` with batch = B."""
+        m, u_, c, z, B, rows = self.m, self.u, self.sk_conv, self.z, self.B, self.rows
+        a, b = batch_stage1_range(self.nC, [self.top[u] if self.closedL[u] else self.nL for u in range(B)], self.closedL, self.closedC, c.pr)
+        b = min(b, rows)
+        if b > a:
+            m._gemm(u_.base + 4 * (a - c.pl) * u_.C, c.W, c.b, self.tap4.data_ptr() + 4 * a * c.Cout, b - a, c.Cout, c.k * c.Cin, c.s * c.Cin, c.Cout,
+                    act_in=m._act_in(bool(c.act_in), u_), batch=B, sA=u_.bstride, sC=rows * c.Cout)
+            pj, (Wa, cls) = m.wm_proj[0], m.wm_cls[0]
+            Cs, D = int(Wa.shape[1]), z.C
+            assert Cs == c.Cout and pj.Cout == D
+            m._gemm(self.tap4.data_ptr() + 4 * a * Cs, Wa, pj.b, z.base + 4 * a * D, b - a, D, Cs, Cs, D, act_in=_lib.ACT_ELU,
+                    R=self.q.data_ptr() + 4 * a * D, ldr=D, batch=B, sA=rows * Cs, sC=z.bstride, sR=rows * D, rowcls=(cls, self.lab[:, a:b], 1))
+            self.nC = b
+        for u in range(B):
+            self.closedC[u] = self.closedC[u] or (self.closedL[u] and self.top[u] <= self.nC)
+        self._edges(z, a, b, self.closedC, self.closed, True)
+
+    def _stage1(self):
+        B, s1 = self.B, self.s1
+        a, b = batch_stage1_range(self.n1, [self.top[u] if self.closedC[u] else self.nC for u in range(B)], self.closedC, self.closed, self.pr0)
+        b = min(b, self.rows)
+        if b > a:
+            m, z, c0 = self.m, self.z, self.conv0
+            ca = max(a, self.conv_row0)
+            if b > ca:
+                m._gemm(z.base + 4 * (ca - self.conv_row0) * z.C, c0.W, c0.b, self.y0.data_ptr() + 4 * ca * c0.Cout, b - ca, c0.Cout, c0.k * c0.Cin,
+                        c0.s * c0.Cin, c0.Cout, act_in=m._act_in(bool(c0.act_in), z), batch=B, sA=z.bstride, sC=self.rows * c0.Cout)
+            self._lstm_rows(self.lstm, self.y0, self.gins, self.hbufs, self.cbufs, self.hsplits, self.mids, s1.interior, self._s1_bs, s1.elu, a, b)
+            self.n1 = b
+        for u in range(B):
+            if self.closedC[u] and not self.closed[u] and self.top[u] <= self.n1:
+                # the zero row the last window's transposed convolution reads
+                self.ops.add([RowOp((u * s1.rows + 1 + self.top[u]) * s1.C, 0, self.n1 - self.top[u], s1.C, s1.C, 0, 0)], s1.data)
+                self.closed[u] = True
+        self.ops.launch()
+
+    def _tail_pass(self, lo: int, hi: int, item: Optional[int], few: bool = False) -> TM:
+        """`WMDecodeStream._tail_pass` over the rows [lo, hi) of every item (`item` None) or of one: the stored taps' rows of the window
+        and the labels from the window's first row on, read in place."""
+        m, s1 = self.m, self.s1
+        who = slice(None) if item is None else slice(item, item + 1)
+        x = _TMView(s1.data[who, lo: hi + 2], hi - lo, s1.bstride, m.device)
+        x.elu = s1.elu
+        with m._stream_pass(self.pool_b if item is None else self.pool_1, few):
+            y = m._run(self.dn[0], x, after=None)
+            for j in (1, 2, 3):
+                tap, rep = self.taps[3 - j], self.reps[3 - j]
+                skip = _TMRows(tap[who, lo * rep: hi * rep], tap.stride(0), m.device)
+                skip.elu = self.tap_elu[3 - j]
+                y = m._run(self.dn[j], m._concat_proj(j, skip, self.lab[who, lo:hi], rep, y, self.dn[j][0]), after=None)
+            return y
+
+    def _run_window(self, win: tuple, item: Optional[int], who: Sequence[int], row0: int):
+        """`_StreamCore._run_window` with the cores copied by one row-op launch."""
+        (c0, c1, lo, hi, few), hop = win, self.hop
+        y = self._tail_pass(lo, hi, item, few)
+        assert y.C == 1 and y.padL == 0 and y.T == (hi - lo) * hop
+        self.ops.add(rows_core_copy([(u, u if item is None else 0) for u in who], c0 - row0, c1 - row0, lo - row0, hop, 1, self.wav.stride(0),
+                                    y.bstride), self.wav, y.data)
+        self.ops.launch()
+        self.windows += 1
+        self.windows_batched += int(item is None)
+
+    def _advance_all(self):
+        self._chain()
+        self._skip_lstm()
+        self._decoder_input()
+        self._stage1()
+        self._stage2()
+
+    def _dequant(self, n: int, row: int):
+        q, cfg = self.q, self.m.cfg
+        self.m._call("ssrhip_rvq_decode", self.codes.data_ptr(), self.m.codebooks.data_ptr(), self._item_ptr(q, 0, row), self.B, n, q.shape[2],
+                     cfg.n_q, cfg.bins, q.stride(0))
+
+    # ------------------------------------------------------------------ public
+    @torch.no_grad()
+    def push_prompts(self, codes: Sequence[torch.Tensor], audio: Sequence[torch.Tensor]) -> None:
+        """codes[u]: [K, P_u] (or [1, K, P_u]), range-checked here; audio[u]: the ORIGINAL audio under item u's prompt, at most
+        P_u * hop samples (any shape; a shorter one is zero-extended to whole frames, as the one-pass call extends it). The prompts pass
+        through the skip-encoder chain, both LSTMs and the decoder's first convolution and are never returned."""
+        if self.primed:
+            raise RuntimeError("BatchWMDecodeStream.push_prompts called twice")
+        if len(codes) != self.B or len(audio) != self.B:
+            raise ValueError(f"{self.B} prompts and {self.B} audio tracks expected, got {len(codes)} / {len(audio)}")
+        hop = self.hop
+        for u, w in enumerate(audio):
+            if w.numel() > self.prompt_lens[u] * hop:
+                raise ValueError(f"item {u}: {w.numel()} samples under a prompt of {self.prompt_lens[u]} frames ({self.prompt_lens[u] * hop} samples)")
+        p_max = max(self.prompt_lens)
+        self._stage_codes(codes, self.prompt_lens, p_max, right=True)
+        self.primed = True
+        for u, w in enumerate(audio):
+            self.track[u, self.off[u] * hop: self.off[u] * hop + w.numel()].copy_(w.reshape(-1))
+        self._dequant(p_max, self.front)
+        self.top = [self.E] * self.B
+        self._advance_all()
+
+    @torch.no_grad()
+    def advance(self, new_frames: Sequence[int], ended: Sequence[bool], codes: Optional[Sequence[torch.Tensor]] = None,
+                flag: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
+        """`BatchDecodeStream.advance`: the next generated frames (silence in the kept-audio track, label 1) -> per item the watermarked
+        samples that have become final, [1, 1, m * hop] views of item u's row of the one output buffer."""
+        if not self.primed:
+            raise RuntimeError("BatchWMDecodeStream.advance before push_prompts")
+        B = self.B
+        new = [int(v) for v in new_frames]
+        if len(new) != B or len(ended) != B:
+            raise ValueError(f"{B} items expected")
+        n = max(new)
+        for u in range(B):
+            if self.ended[u] and new[u]:
+                raise ValueError(f"item {u} has ended and gets {new[u]} more frames")
+            if not self.ended[u] and not ended[u] and new[u] != n:
+                raise ValueError(f"lock-step: item {u} goes on with {new[u]} new frames while another item gets {n}")
+            if self.top[u] + new[u] > self.rows:
+                raise ValueError(f"item {u}: more than max_new_frames = {self.max_new} generated frames")
+        a = list(self.n2)
+        live_top = [self.top[u] for u in range(B) if not self.ended[u]]
+        if n:
+            row = live_top[0]
+            assert all(t == row for t in live_top)
+            if codes is not None:
+                self._stage_codes(codes, new, n, right=False)
+            self._dequant(n, row)
+        for u in range(B):
+            if not self.ended[u]:
+                self.top[u] += new[u]
+                self.ended[u] = bool(ended[u])
+        self._advance_all()
+        if flag is not None and int(flag.item()):
+            raise IndexError("index out of range in self")
+        hop, E = self.hop, self.E
+        return [self.wav[u: u + 1, :, (a[u] - E) * hop: (self.n2[u] - E) * hop] for u in range(B)]

@@ -192,6 +192,13 @@ class AudioTokenizer:
             raise ValueError("decode_stream_batch: the watermarked decode (use_watermark=True) is not streamed; use wmdecode_batch on the finished frames")
         return self.codec.decode_stream_batch(prompt_lens, max_new_frames, max_window)
 
+    def wmdecode_stream_batch(self, prompt_lens: Sequence[int], max_new_frames: int, max_window: int = 16):
+        """`wmdecode_stream` for B utterances generated in lock-step as zero-shot TTS (`WMEncodecModel.wmdecode_stream_batch`):
+        `push_prompts(codes, audio)` — audio[u] = the original audio under item u's prompt — then `advance(new_frames, ended)` per poll
+        returns every item's new watermarked samples; per item their concatenation equals `wmdecode` of that item (label 0 and its
+        audio under the prompt, label 1 and silence behind it) at batch 1, cut to the generated part."""
+        return self.codec.wmdecode_stream_batch(prompt_lens, max_new_frames, max_window)
+
     def wmdecode(self, frames: torch.Tensor, marks: torch.Tensor, wav: torch.Tensor, scale: torch.Tensor):
         # the reference discards the detector output here (tokenizer.py:133): skip computing it
         out, _ = self.codec.wmdecode(frames.to(self.device), marks.to(self.device), wav.to(self.device), scale, with_mark=False)

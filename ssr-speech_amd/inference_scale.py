@@ -266,24 +266,46 @@ def inference_one_sample_wmstream(model, model_args, phn2num, text_tokenizer, au
         yield chunk
 
 
-def _stream_batch(model, audio_tokenizer, utterances, cfg_coef, cfg_stride, aug_text, decode_config, seed):
-    """The batched stream behind `inference_batch_stream` / `inference_samples_stream`: `SSR_Speech.inference_batch_stream` gathers every
-    poll's final frames on the device into the codec stream's own block, `BatchDecodeStream.advance` turns them into samples."""
+def _orig_audio(audio_fn, device) -> torch.Tensor:
+    """The original audio under a prompt, zero-extended to whole frames as `_watermark_inputs` extends it, on the device: [n]"""
+    wav, _sr = read_wav(audio_fn) if isinstance(audio_fn, str) else (audio_fn, None)
+    short = -wav.shape[-1] % HOP
+    if short:
+        wav = F.pad(wav, (0, short))
+    return wav.reshape(-1).to(device, torch.float32)
+
+
+def _stream_batch(model, audio_tokenizer, utterances, cfg_coef, cfg_stride, aug_text, decode_config, seed, audio_fns=None):
+    """The batched stream behind `inference_batch_stream` / `inference_samples_stream` and their watermarked twins:
+    `SSR_Speech.inference_batch_stream` gathers every poll's final frames on the device into the codec stream's own block,
+    `BatchDecodeStream.advance` turns them into samples. `audio_fns` (one path / [1, n] tensor per utterance): the watermarked decode —
+    `SSR_Speech.inference_batch_wmstream` feeds a `BatchWMDecodeStream`, whose prompts take the original audio beside their codes."""
     held = {}
+    wm = audio_fns is not None
 
     def before_start(info):
         # the codec stream allocates everything NOW, ahead of the engine's first launch; the gather writes straight into its block
-        held["codec"] = audio_tokenizer.decode_stream_batch(info["prompt_lens"], info["max_new_frames"])
+        make = audio_tokenizer.wmdecode_stream_batch if wm else audio_tokenizer.decode_stream_batch
+        held["codec"] = make(info["prompt_lens"], info["max_new_frames"])
+        if wm:                                                               # the original audio: uploaded once, here; one upload per file
+            up, held["audio"] = {}, []
+            for fn, p in zip(audio_fns, info["prompt_lens"]):
+                key = fn if isinstance(fn, str) else id(fn)
+                if key not in up:
+                    up[key] = _orig_audio(fn, audio_tokenizer.device)
+                held["audio"].append(up[key][: p * HOP])
         return held["codec"].codes
 
-    frames = model.inference_batch_stream(utterances, top_k=decode_config["top_k"], top_p=decode_config["top_p"],
-                                          temperature=decode_config["temperature"], stop_repetition=decode_config["stop_repetition"],
-                                          cfg_coef=cfg_coef, cfg_stride=cfg_stride, aug_text=aug_text, seed=seed,
-                                          bins=int(audio_tokenizer.codec.cfg.bins), before_start=before_start)
+    start = model.inference_batch_wmstream if wm else model.inference_batch_stream
+    frames = start(utterances, top_k=decode_config["top_k"], top_p=decode_config["top_p"],
+                   temperature=decode_config["temperature"], stop_repetition=decode_config["stop_repetition"],
+                   cfg_coef=cfg_coef, cfg_stride=cfg_stride, aug_text=aug_text, seed=seed,
+                   bins=int(audio_tokenizer.codec.cfg.bins), before_start=before_start)
     for inc in frames:
         codec = held["codec"]
         if inc.kept:
-            codec.push_prompts(inc.codes)                                     # the prompts only warm the LSTM state up: never yielded
+            # the prompts only warm the LSTM state up: never yielded
+            codec.push_prompts(inc.codes, held["audio"]) if wm else codec.push_prompts(inc.codes)
             continue
         # the flag is read once per poll, after the poll's codec work is enqueued, and raises before any sample of the poll leaves
         for i, chunk in enumerate(codec.advance(inc.counts, inc.ended, flag=frames.flag)):
@@ -335,3 +357,55 @@ def inference_samples_stream(model, model_args, phn2num, text_tokenizer, audio_t
         raise AssertionError("renormalize=False codec: scale must be None")
     one = {"x": _phoneme_ids(text_tokenizer, phn2num, target_text), "y": prompt_frames, "mask_interval": mask_interval.unsqueeze(0)}
     yield from _stream_batch(model, audio_tokenizer, [one] * len(seeds), cfg_coef, cfg_stride, aug_text, decode_config, seeds[0])
+
+
+@torch.no_grad()
+def inference_batch_wmstream(model, model_args, phn2num, text_tokenizer, audio_tokenizer, utterances, cfg_coef, cfg_stride, aug_text,
+                             use_watermark, device, decode_config, seed: int = 0):
+    """`inference_batch_stream` with the watermarked decode (DESIGN.md Part I.29): a generator of `(index, chunk [1, 1, n])` whose
+    chunks, per utterance, are `inference_one_sample(..., use_watermark=True, tts=True)` under `torch.manual_seed(seed + i)` (same
+    tokens; samples within the bound that holds a batched codec pass to the batch-1 one). Each utterance's original audio is uploaded
+    once, ahead of the engine's first launch; `AudioTokenizer.wmdecode_stream_batch` puts it under the prompt and silence under the
+    generated frames. One fixed group, zero-shot TTS only; a refusal names `inference_batch` + `render_many(use_watermark=True)`. A falsy
+    `use_watermark` is `inference_batch_stream`."""
+    if not use_watermark:
+        yield from inference_batch_stream(model, model_args, phn2num, text_tokenizer, audio_tokenizer, utterances, cfg_coef, cfg_stride, aug_text,
+                                          use_watermark, device, decode_config, seed=seed)
+        return
+    K = int(model_args.n_codebooks)
+    jobs = []
+    for u in utterances:
+        prompt_frames, scale = _prompt_codes(audio_tokenizer, u["audio_fn"], K)
+        if scale is not None:
+            raise AssertionError("renormalize=False codec: scale must be None")
+        T = int(prompt_frames.shape[1])
+        jobs.append({"x": _phoneme_ids(text_tokenizer, phn2num, u["target_text"]), "y": prompt_frames,
+                     "mask_interval": torch.tensor([[[T, T]]], dtype=torch.long)})
+    yield from _stream_batch(model, audio_tokenizer, jobs, cfg_coef, cfg_stride, aug_text, decode_config, seed,
+                             audio_fns=[u["audio_fn"] for u in utterances])
+
+
+@torch.no_grad()
+def inference_samples_wmstream(model, model_args, phn2num, text_tokenizer, audio_tokenizer, audio_fn, prompt_text, target_text, mask_interval,
+                               cfg_coef, cfg_stride, aug_text, aug_context, use_watermark, tts, device, decode_config, seeds):
+    """`inference_samples(..., use_watermark=True)` as a generator of `(sample index, chunk [1, 1, n])`: the N samples of ONE utterance
+    decoded in lock-step, watermarked and streamed (`inference_batch_wmstream`). Sample i's concatenated chunks are
+    `inference_one_sample(..., use_watermark=True)` after `torch.manual_seed(seeds[i])`. `--tts` only: a speech edit or more samples
+    than one engine pass holds raise ValueError before any launch. A falsy `use_watermark` is `inference_samples_stream`."""
+    if not use_watermark:
+        yield from inference_samples_stream(model, model_args, phn2num, text_tokenizer, audio_tokenizer, audio_fn, prompt_text, target_text,
+                                            mask_interval, cfg_coef, cfg_stride, aug_text, aug_context, use_watermark, tts, device, decode_config,
+                                            seeds)
+        return
+    if not tts:
+        raise ValueError("inference_samples_wmstream: only zero-shot TTS (--tts) is streamed; use inference_samples(use_watermark=True) for a "
+                         "speech edit")
+    seeds = [int(s) for s in seeds]
+    assert seeds == list(range(seeds[0], seeds[0] + len(seeds))), "seeds must be consecutive (seed + sample index)"
+    K = int(model_args.n_codebooks)
+    prompt_frames, scale = _prompt_codes(audio_tokenizer, audio_fn, K)
+    if scale is not None:
+        raise AssertionError("renormalize=False codec: scale must be None")
+    one = {"x": _phoneme_ids(text_tokenizer, phn2num, target_text), "y": prompt_frames, "mask_interval": mask_interval.unsqueeze(0)}
+    yield from _stream_batch(model, audio_tokenizer, [one] * len(seeds), cfg_coef, cfg_stride, aug_text, decode_config, seeds[0],
+                             audio_fns=[audio_fn] * len(seeds))

@@ -69,7 +69,8 @@ EXTRA_FLAGS = [
                             help="1: the --sample_batch_size samples of the utterance are prefilled once and share the prompt's KV pages "
                                  "(5..32 rows, fp32 cache; fewer rows run unshared); 0 (default): every sample keeps its own copy")),
     ("--stream_dir", dict(type=str, default=None,
-                          help="--tts with --sample_batch_size N: stream the lock-step samples (inference_samples_stream) and append each "
+                          help="--tts with --sample_batch_size N: stream the lock-step samples (inference_samples_stream; with --use_watermark "
+                               "inference_samples_wmstream) and append each "
                                "sample's chunks, as they arrive, to DIR/{savename}_new_seed{seed}.f32 (raw float32 samples, one file per sample)")),
     ("--rank_samples", dict(action="store_true",
                             help="score the --sample_batch_size samples by the log-probability the model gave the tokens it drew (lock-step "
@@ -264,7 +265,7 @@ def main(argv=None):
     args = parse_args(argv)
     seed_everything(args.seed)
     from .data.tokenizer import AudioTokenizer, TextTokenizer, read_wav, write_wav
-    from .inference_scale import inference_one_sample, inference_samples, inference_samples_stream
+    from .inference_scale import inference_one_sample, inference_samples, inference_samples_wmstream
     from .models.ssr import SSR_Speech
 
     if int(os.environ.get("WORLD_SIZE", "1")) > 1 and torch.cuda.is_available():        # torchrun: this rank's GPU before anything is allocated
@@ -350,9 +351,10 @@ def main(argv=None):
     if args.stream_dir is not None and args.rank_samples:
         raise SystemExit("--rank_samples scores the samples of the lock-step path; the streamed path (--stream_dir) has no scores")
     if args.stream_dir is not None:
-        # the samples in ONE lock-step decode, their audio written while they decode (--tts only; DESIGN.md Part I.16)
+        # the samples in ONE lock-step decode, their audio written while they decode (--tts only; DESIGN.md Part I.16; with
+        # --use_watermark the watermarked stream of Part I.29, which without the flag hands on to its un-watermarked twin)
         seed_everything(seeds[-1])
-        waves = _stream_samples_to(args.stream_dir, args.savename, seeds, inference_samples_stream(*common, seeds=seeds))
+        waves = _stream_samples_to(args.stream_dir, args.savename, seeds, inference_samples_wmstream(*common, seeds=seeds))
     elif len(seeds) > 1 or args.rank_samples:
         # all samples of the utterance in ONE lock-step decode (same outputs as the reference's sequential loop :331-358)
         seed_everything(seeds[-1])

@@ -318,6 +318,19 @@ def check_stream_batch(y_lens: Sequence[int], mask_intervals: Sequence[np.ndarra
     return prompts
 
 
+def check_wmstream_batch(y_lens: Sequence[int], mask_intervals: Sequence[np.ndarray], rows_per_utt: int, max_rows: int) -> List[int]:
+    """Which calls `SSR_Speech.inference_batch_wmstream` serves: what `check_stream_batch` accepts, decoded WITH the watermark (the
+    batched watermarked stream puts silence under generated frames and labels the prompt 0, the rest 1: zero-shot TTS). The other rules
+    hold — TTS only, one engine pass, no refill — and a refusal names the watermarked call to use instead. Returns the prompt lengths."""
+    try:
+        return check_stream_batch(y_lens, mask_intervals, rows_per_utt, max_rows)
+    except ValueError as e:
+        msg = str(e).replace("the batched stream", "the batched watermarked stream")
+        if "watermarked" not in msg:
+            msg = "the batched watermarked stream: " + msg
+        raise ValueError(msg.replace("use inference_batch", "use inference_batch + render_many(use_watermark=True)")) from None
+
+
 def final_generated_frames(n_rows: int, ended: bool, end_row: int, K: int) -> int:
     """How many generated frames of a ONE-span utterance are final when `n_rows` generated rows exist — `FrameAssembler`'s rule without
     the rows themselves: frame t needs the rows 0 .. t + K - 1, and the first `eog` of codebook 0 sits exactly K rows before the span's

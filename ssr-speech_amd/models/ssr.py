@@ -147,12 +147,13 @@ class BatchInferenceStream:
     gather sets for an id outside [0, bins) (read it once per poll, after the poll's consumer work is enqueued:
     `BatchDecodeStream.advance(flag=)` does), `.polls` counts the polls so far."""
 
-    def __init__(self, model: "SSR_Speech", utterances, kw: dict, use_graph: bool, bins: Optional[int], before_start):
+    def __init__(self, model: "SSR_Speech", utterances, kw: dict, use_graph: bool, bins: Optional[int], before_start, watermark: bool = False):
         a = model.args
         rows = 2 if kw["aug_text"] else 1
-        # the refusals, before anything reaches the library
-        self.prompt_lens = LY.check_stream_batch([int(u["y"].shape[1]) for u in utterances], [u["mask_interval"][0].detach().cpu().numpy() for u in utterances],
-                                                 rows, MAX_ROWS)
+        # the refusals, before anything reaches the library (`watermark`: the same rules, with refusals that name the watermarked calls)
+        check = LY.check_wmstream_batch if watermark else LY.check_stream_batch
+        self.prompt_lens = check([int(u["y"].shape[1]) for u in utterances], [u["mask_interval"][0].detach().cpu().numpy() for u in utterances],
+                                 rows, MAX_ROWS)
         self.model, self.results, self.polls, self.flag = model, None, 0, None
         self.bins = int(a.audio_vocab_size if bins is None else bins)
         self._it = self._run(utterances, kw, use_graph, before_start)
@@ -744,3 +745,16 @@ class SSR_Speech(nn.Module):
                                                            silence_tokens=silence_tokens, cfg_coef=cfg_coef, cfg_stride=cfg_stride,
                                                            aug_text=aug_text, seed=seed, first_index=first_index, indices=indices),
                                     use_graph, bins, before_start)
+
+    def inference_batch_wmstream(self, utterances, top_k: int = -100, top_p: float = 1.0, temperature: float = 1.0, stop_repetition: int = -1,
+                                 silence_tokens=(1388, 1898, 131), cfg_coef: float = 1.5, cfg_stride: int = 1, aug_text: bool = False,
+                                 seed: int = 0, first_index: int = 0, use_graph: bool = True, indices: Optional[Sequence[int]] = None,
+                                 *, bins: Optional[int] = None, before_start=None) -> "BatchInferenceStream":
+        """`inference_batch_stream` for a consumer that decodes WITH the watermark (DESIGN.md Part I.29): the same iterator of
+        `BatchFrames`, the same tokens and `.results`; the rules are `layout.check_wmstream_batch`'s — zero-shot TTS only, one engine
+        pass, no refill — and a refusal names `inference_batch` + `render_many(use_watermark=True)`. `before_start(info)` is where
+        `BatchWMDecodeStream` is created (`inference_scale.inference_batch_wmstream`)."""
+        return BatchInferenceStream(self, utterances, dict(top_k=top_k, top_p=top_p, temperature=temperature, stop_repetition=stop_repetition,
+                                                           silence_tokens=silence_tokens, cfg_coef=cfg_coef, cfg_stride=cfg_stride,
+                                                           aug_text=aug_text, seed=seed, first_index=first_index, indices=indices),
+                                    use_graph, bins, before_start, watermark=True)

@@ -13,7 +13,11 @@ total wall time (median and spread of the rounds), the polls and the codec launc
 `inference_one_sample_wmstream` and, for scale, the un-watermarked stream, same warm-up and rounds; it reports the first audio at the
 caller, the total wall time of the three, the chunks, the codec's library calls per 16-frame push, the hold-back in frames and whether
 every round was bit-identical.
-Usage: python tools/stream_latency.py [--weight_dtype bf16] [--utts 8 | --use_watermark] [--out profiles/stream_latency_830m.json]"""
+`--utts N --use_watermark` measures the BATCHED WATERMARKED stream (DESIGN.md Part I.29): `inference_samples_wmstream` against
+`inference_samples(use_watermark=True)` in the same process, same warm-up and rounds; it reports the host time to the first chunk of
+every utterance, both arms' total wall time, the codec's library calls per poll in which every utterance is live (and how many of them
+are row-op launches) and the bytes of the stream's tap buffers.
+Usage: python tools/stream_latency.py [--weight_dtype bf16] [--utts 8] [--use_watermark] [--out profiles/stream_latency_830m.json]"""
 import argparse
 import json
 import os
@@ -28,7 +32,8 @@ import ssr_speech_amd  # noqa: E402,F401
 from ssr_speech_amd import weights as W  # noqa: E402
 from ssr_speech_amd.data.tokenizer import AudioTokenizer, write_wav  # noqa: E402
 from ssr_speech_amd.inference_scale import (_phoneme_ids, _prompt_codes, inference_one_sample, inference_one_sample_stream,  # noqa: E402
-                                            inference_one_sample_wmstream, inference_samples_stream, render_many)
+                                            inference_one_sample_wmstream, inference_samples, inference_samples_stream,
+                                            inference_samples_wmstream, render_many)
 from ssr_speech_amd.models.ssr import SSR_Speech  # noqa: E402
 
 DEMO_PROMPT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "demo_5895_34622_000026_000002_160f.wav")
@@ -78,6 +83,8 @@ def main(argv=None):
     call = (model, argparse.Namespace(**vars(args_lm)), phn2num, CharPhonemizer(), tok, fn, prompt_text, target_text, mi, 1.5, 5, True, False,
             False, True, dev, decode_config)
     codec = tok.codec
+    if opt.utts > 0 and opt.use_watermark:
+        return batched_watermarked(opt, model, tok, call)
     if opt.utts > 0:
         return batched(opt, model, args_lm, tok, call, phn2num, fn, target_text, mi)
 
@@ -296,6 +303,88 @@ def batched(opt, model, args_lm, tok, call, phn2num, fn, target_text, mi):
         "spread": {"one_pass_total_ms": round(max(col("one_pass", "total_ms")) - min(col("one_pass", "total_ms")), 2),
                    "stream_total_ms": round(max(col("stream", "total_ms")) - min(col("stream", "total_ms")), 2)},
         "max_abs_diff": max(col("stream", "max_abs_diff")),
+    }
+    line = json.dumps(out)
+    print(line)
+    if opt.out:
+        with open(opt.out, "w") as f:
+            f.write(json.dumps(out, indent=1) + "\n")
+    return 0
+
+
+def batched_watermarked(opt, model, tok, call):
+    """--utts N --use_watermark: `inference_samples_wmstream` against `inference_samples(use_watermark=True)`"""
+    from ssr_speech_amd.codec.wmencodec import BatchWMDecodeStream, wm_stream_holdback
+    n, codec = opt.utts, tok.codec
+    call_wm = call[:13] + (True,) + call[14:]
+    seen = {"polls": [], "tap_bytes": None, "rows": None}
+    real_advance = BatchWMDecodeStream.advance
+
+    def counted(self, new_frames, ended, *a, **k):
+        n0, o0, live = codec.n_launches, self.ops.launches, not any(self.ended) and not any(ended)
+        out = real_advance(self, new_frames, ended, *a, **k)
+        seen["polls"].append((live, codec.n_launches - n0, self.ops.launches - o0))
+        seen["tap_bytes"], seen["rows"] = self.tap_bytes, self.rows
+        return out
+
+    def one_pass(seed):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        waves = inference_samples(*call_wm, seeds=list(range(seed, seed + n)))
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        return waves, dict(total_ms=1000 * (t1 - t0), frames=[int(w.shape[-1]) // 320 for w in waves], audio_s=sum(w.shape[-1] for w in waves) / 16000.0)
+
+    def streamed(seed):
+        torch.cuda.synchronize()
+        seen["polls"] = []
+        n0 = codec.n_launches
+        t0 = time.perf_counter()
+        parts, first = [[] for _ in range(n)], {}
+        for i, chunk in inference_samples_wmstream(*call_wm, seeds=list(range(seed, seed + n))):
+            if i not in first and (not first or len(first) == n - 1):      # the first chunk of the first and of the last utterance
+                torch.cuda.current_stream().synchronize()
+            first.setdefault(i, 1000 * (time.perf_counter() - t0))
+            parts[i].append(chunk)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        waves = [torch.cat(p, -1) for p in parts]
+        live = [p for p in seen["polls"] if p[0]]
+        return waves, dict(total_ms=1000 * (t1 - t0), first_chunk_ms=[round(first[i], 2) for i in range(n)],
+                           first_chunk_first_utt_ms=min(first.values()), first_chunk_last_utt_ms=max(first.values()),
+                           first_chunk_samples=int(parts[0][0].shape[-1]), chunks=sum(len(p) for p in parts), polls=len(seen["polls"]),
+                           codec_launches=codec.n_launches - n0, live_poll_calls=sorted({p[1] for p in live}),
+                           live_poll_row_op_launches=sorted({p[2] for p in live}), audio_s=sum(w.shape[-1] for w in waves) / 16000.0)
+
+    BatchWMDecodeStream.advance = counted
+    try:
+        one_pass(1)
+        streamed(1)
+        rounds = []
+        for r in range(opt.rounds):
+            wa, a = one_pass(1 + 100 * r)
+            wb, b = streamed(1 + 100 * r)
+            b["max_abs_diff"] = max(float((x - y).abs().max()) if x.shape == y.shape else float("inf") for x, y in zip(wa, wb))
+            rounds.append({"one_pass": a, "wmstream": b})
+    finally:
+        BatchWMDecodeStream.advance = real_advance
+    med = lambda xs: sorted(xs)[len(xs) // 2]
+    col = lambda arm, key: [r[arm][key] for r in rounds]
+    out = {
+        "tool": "tools/stream_latency.py --utts --use_watermark", "utts": n, "weight_dtype": opt.weight_dtype,
+        "shape": f"830M LM, full codec (8,5,4,2), {n} samples x CFG of the 160-frame demo prompt, 67 phonemes, sampled, CFG stride 5, watermarked decode",
+        "rounds": rounds,
+        "median": {k: round(med(col(arm, key)), 2) for k, arm, key in (
+            ("one_pass_total_ms", "one_pass", "total_ms"), ("wmstream_total_ms", "wmstream", "total_ms"),
+            ("wmstream_first_chunk_first_utt_ms", "wmstream", "first_chunk_first_utt_ms"),
+            ("wmstream_first_chunk_last_utt_ms", "wmstream", "first_chunk_last_utt_ms"))},
+        "median_first_chunk_ms_per_utt": [round(med([r["wmstream"]["first_chunk_ms"][i] for r in rounds]), 2) for i in range(n)],
+        "spread": {"one_pass_total_ms": round(max(col("one_pass", "total_ms")) - min(col("one_pass", "total_ms")), 2),
+                   "wmstream_total_ms": round(max(col("wmstream", "total_ms")) - min(col("wmstream", "total_ms")), 2)},
+        "library_calls_per_live_poll": rounds[-1]["wmstream"]["live_poll_calls"],
+        "row_op_launches_per_live_poll": rounds[-1]["wmstream"]["live_poll_row_op_launches"],
+        "tap_buffer_bytes": seen["tap_bytes"], "rows_per_item": seen["rows"], "holdback_frames": wm_stream_holdback(codec.cfg),
+        "max_abs_diff": max(col("wmstream", "max_abs_diff")),
     }
     line = json.dumps(out)
     print(line)
