@@ -554,6 +554,15 @@ int ssrhip_gemm_w1(const ssrhip_gemm_args* a, ssrhip_stream_t stream);
 /* how many calls of ssrhip_gemm_w1 launched a one-plane kernel (answered 0) in this process so far, through whichever entry (direct,
  * ssrhip_lm_prefill, ssrhip_lm_score_w1): a caller that expects the one-plane path can tell it from the silent fp32-chain fallback. */
 int64_t ssrhip_gemm_w1_launches(void);
+/* ssrhip_gemm_w1 for the codec's bf16-rounded weights (WMEncodecModel weight_dtype="bf16"): the same contract — W_split is ONE bf16 plane
+ * [N][K]; 0 launched, 1 does not qualify and nothing was launched, < 0 contract error before any HIP call — and the same bits as
+ * ssrhip_gemm on the three planes of the same matrix, but it also launches a one-plane kernel for act_in == SSRHIP_ACT_ELU and takes the
+ * time-mask-folded 16-byte epilogue under exactly the conditions a three-plane call takes it. It answers 1 only where ssrhip_gemm's rule
+ * for W_split fails. Plan, tile order, k-block order and product order (a2w0, a1w0, a0w0) are those of the three-plane call. */
+int ssrhip_codec_gemm_w1(const ssrhip_gemm_args* a, ssrhip_stream_t stream);
+/* how many calls of ssrhip_codec_gemm_w1 and ssrhip_resblock_w1 launched a one-plane kernel (answered 0) in this process so far;
+ * ssrhip_gemm_w1_launches does not count them. */
+int64_t ssrhip_codec_w1_launches(void);
 
 
 /* ------------------------------------------------------------------------------------------------
@@ -641,6 +650,13 @@ typedef struct ssrhip_resblock_args {
   const uint16_t* w3_split; const uint16_t* w1_split;
 } ssrhip_resblock_args;
 int ssrhip_resblock(const ssrhip_resblock_args* a, ssrhip_stream_t stream);
+/* The DMA kernel of ssrhip_resblock for matrices whose every value IS a bf16 value: w3_split and w1_split (both required) hold ONE bf16
+ * plane each — [C/2][3*C], and [C][C/2] in the permuted column order above — and w3 / w1 are not read. Three products per k block
+ * instead of six, a third of the weight bytes through LDS; ssrhip_resblock's result on the three planes of the same matrices BIT FOR BIT
+ * for finite activations. Returns 0 when it launched; 1, launching nothing, where ssrhip_resblock would not take the DMA kernel (C not
+ * in {64, 128}, SSRHIP_GEMM_SPLIT=0, SSRHIP_RESBLOCK_DMA=0): the caller then calls ssrhip_resblock WITHOUT planes; < 0 for a contract
+ * error (a NULL plane), before any HIP call. NEVER hand a one-plane buffer to ssrhip_resblock. Counted by ssrhip_codec_w1_launches. */
+int ssrhip_resblock_w1(const ssrhip_resblock_args* a, ssrhip_stream_t stream);
 
 /* LayerNorm over rows (transformer.py:58-75) */
 int ssrhip_layernorm(const float* x, const float* w, const float* b, float eps, float* y, int32_t R, int32_t D,

@@ -132,9 +132,18 @@ def _fold_wn(sd, pfx: str, which: str) -> Tuple[torch.Tensor, torch.Tensor]:
     return torch._weight_norm(sd[k + "weight_v"], sd[k + "weight_g"], 0), sd[k + "bias"]
 
 
+CODEC_WEIGHT_DTYPES = ("fp32", "bf16")
+
+
+def _round_w(w: torch.Tensor, wdt: str) -> torch.Tensor:
+    """A folded weight matrix as the model keeps it: with "bf16" every value rounded once (nearest even) to a bf16 value, kept in fp32."""
+    return w.to(torch.bfloat16).to(torch.float32) if wdt == "bf16" else w
+
+
 class _Conv:
-    def __init__(self, sd, pfx, stride, act_in, dev):
+    def __init__(self, sd, pfx, stride, act_in, dev, wdt="fp32"):
         w, b = _fold_wn(sd, pfx, "conv")
+        w = _round_w(w, wdt)                         # behind the weight-norm fold, in front of everything derived from the matrix
         self.Cout, self.Cin, self.k = w.shape
         self.s = stride
         self.act_in = act_in
@@ -154,8 +163,9 @@ class _Conv:
 
 
 class _ConvTr:
-    def __init__(self, sd, pfx, stride, dev):
+    def __init__(self, sd, pfx, stride, dev, wdt="fp32"):
         w, b = _fold_wn(sd, pfx, "convtr")          # [Cin][Cout][k]
+        w = _round_w(w, wdt)
         self.Cin, self.Cout, self.k = w.shape
         self.s = stride
         assert self.k == 2 * stride, "SEANet uses kernel = 2*stride for its transposed convolutions"
@@ -187,10 +197,10 @@ def pack_lstm_whh_planes(planes: torch.Tensor) -> torch.Tensor:
 
 
 class _Lstm:
-    def __init__(self, sd, pfx, layers, dev):
+    def __init__(self, sd, pfx, layers, dev, wdt="fp32"):
         self.layers = []
         for l in range(layers):
-            wih, whh = sd[pfx + f"lstm.weight_ih_l{l}"], sd[pfx + f"lstm.weight_hh_l{l}"]
+            wih, whh = _round_w(sd[pfx + f"lstm.weight_ih_l{l}"], wdt), _round_w(sd[pfx + f"lstm.weight_hh_l{l}"], wdt)
             bias = sd[pfx + f"lstm.bias_ih_l{l}"] + sd[pfx + f"lstm.bias_hh_l{l}"]
             self.layers.append((wih.contiguous().to(dev), whh.contiguous().to(dev), bias.contiguous().to(dev)))
         self.C = self.layers[0][1].shape[1]
@@ -208,33 +218,33 @@ class _Lstm:
 class _SeaNet:
     """One nn.Sequential of the reference (SEANetEncoder.model / SEANetDecoder.model), as a list of fused nodes."""
 
-    def __init__(self, sd, pfx: str, cfg: CodecConfig, decoder: bool, dev):
+    def __init__(self, sd, pfx: str, cfg: CodecConfig, decoder: bool, dev, wdt: str = "fp32"):
         self.cfg, self.dev = cfg, dev
         # (model index of the node's first module, kind, obj, model index of the module whose OUTPUT the node produces)
         self.nodes: List[tuple] = []
         i = 0
         if not decoder:                  # seanet.py:113-150
-            self.nodes.append((i, "conv", _Conv(sd, f"{pfx}model.{i}.", 1, 0, dev), i))
+            self.nodes.append((i, "conv", _Conv(sd, f"{pfx}model.{i}.", 1, 0, dev, wdt), i))
             i += 1
             for r in reversed(cfg.ratios):
-                self.nodes.append((i, "res", (_Conv(sd, f"{pfx}model.{i}.block.1.", 1, 1, dev), _Conv(sd, f"{pfx}model.{i}.block.3.", 1, 1, dev)), i))
-                self.nodes.append((i + 1, "conv", _Conv(sd, f"{pfx}model.{i + 2}.", r, 1, dev), i + 2))      # ELU (i+1) folded in
+                self.nodes.append((i, "res", (_Conv(sd, f"{pfx}model.{i}.block.1.", 1, 1, dev, wdt), _Conv(sd, f"{pfx}model.{i}.block.3.", 1, 1, dev, wdt)), i))
+                self.nodes.append((i + 1, "conv", _Conv(sd, f"{pfx}model.{i + 2}.", r, 1, dev, wdt), i + 2))      # ELU (i+1) folded in
                 i += 3
             if cfg.lstm:
-                self.nodes.append((i, "lstm", _Lstm(sd, f"{pfx}model.{i}.", cfg.lstm, dev), i))
+                self.nodes.append((i, "lstm", _Lstm(sd, f"{pfx}model.{i}.", cfg.lstm, dev, wdt), i))
                 i += 1
-            self.nodes.append((i, "conv", _Conv(sd, f"{pfx}model.{i + 1}.", 1, 1, dev), i + 1))
+            self.nodes.append((i, "conv", _Conv(sd, f"{pfx}model.{i + 1}.", 1, 1, dev, wdt), i + 1))
         else:                            # seanet.py:209-254
-            self.nodes.append((i, "conv", _Conv(sd, f"{pfx}model.{i}.", 1, 0, dev), i))
+            self.nodes.append((i, "conv", _Conv(sd, f"{pfx}model.{i}.", 1, 0, dev, wdt), i))
             i += 1
             if cfg.lstm:
-                self.nodes.append((i, "lstm", _Lstm(sd, f"{pfx}model.{i}.", cfg.lstm, dev), i))
+                self.nodes.append((i, "lstm", _Lstm(sd, f"{pfx}model.{i}.", cfg.lstm, dev, wdt), i))
                 i += 1
             for r in cfg.ratios:
-                self.nodes.append((i, "convtr", _ConvTr(sd, f"{pfx}model.{i + 1}.", r, dev), i + 1))      # ELU (i) folded in
-                self.nodes.append((i + 2, "res", (_Conv(sd, f"{pfx}model.{i + 2}.block.1.", 1, 1, dev), _Conv(sd, f"{pfx}model.{i + 2}.block.3.", 1, 1, dev)), i + 2))
+                self.nodes.append((i, "convtr", _ConvTr(sd, f"{pfx}model.{i + 1}.", r, dev, wdt), i + 1))      # ELU (i) folded in
+                self.nodes.append((i + 2, "res", (_Conv(sd, f"{pfx}model.{i + 2}.block.1.", 1, 1, dev, wdt), _Conv(sd, f"{pfx}model.{i + 2}.block.3.", 1, 1, dev, wdt)), i + 2))
                 i += 3
-            self.nodes.append((i, "conv", _Conv(sd, f"{pfx}model.{i + 1}.", 1, 1, dev), i + 1))
+            self.nodes.append((i, "conv", _Conv(sd, f"{pfx}model.{i + 1}.", 1, 1, dev, wdt), i + 1))
 
     def slice_nodes(self, lo: int, hi: Optional[int]):
         return [n for n in self.nodes if n[0] >= lo and (hi is None or n[0] < hi)]
@@ -325,11 +335,20 @@ _ENV_KNOBS = (
     ("presize", "SSRHIP_CODEC_PRESIZE", "1", _on),                 # the sizing passes of `_sized`; 0 is the A/B arm of tools/race_trials.py
     # channel counts whose residual block runs as one kernel: 64 and 128 pay, 256 / 512 lose to two GEMM launches
     ("fuse_channels", "SSRHIP_RESBLOCK_FUSE", "64,128", _ints),
+    # a weight_dtype="bf16" model: ONE bf16 plane per matrix and the one-plane kernels (three products per k block); 0: three planes of the
+    # rounded weights through the six-product kernels — the same bits (DESIGN.md Part I.30). Ignored for weight_dtype="fp32"
+    ("codec_w1", "SSRHIP_CODEC_W1", "1", _not0),
 )
 
 
 class WMEncodecModel:
-    def __init__(self, cfg: CodecConfig, state_dict: dict, device):
+    def __init__(self, cfg: CodecConfig, state_dict: dict, device, *, weight_dtype: str = "fp32"):
+        """`weight_dtype="bf16"`: every convolution, transposed-convolution and LSTM weight matrix is rounded once to a bf16 value (kept in
+        fp32) behind the weight-norm fold; biases, codebooks and the label table stay fp32. The model is then the fp32 codec on the rounded
+        weights whatever kernel a shape takes, and its GEMMs and residual blocks run one weight plane (DESIGN.md Part I.30)."""
+        if weight_dtype not in CODEC_WEIGHT_DTYPES:
+            raise ValueError(f"weight_dtype {weight_dtype!r} not in {CODEC_WEIGHT_DTYPES}")
+        self.weight_dtype = weight_dtype
         self.cfg = cfg
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -351,15 +370,16 @@ class WMEncodecModel:
         self.n_launches = 0                  # library entry points called so far, dry passes included (tools/stream_latency.py)
         sd = {k: v.detach().to(torch.float32).cpu() for k, v in state_dict.items()}
         dev = self.device
-        self.encoder = _SeaNet(sd, "encoder.", cfg, False, dev)
-        self.decoder = _SeaNet(sd, "decoder.", cfg, True, dev)
+        wdt = weight_dtype
+        self.encoder = _SeaNet(sd, "encoder.", cfg, False, dev, wdt)
+        self.decoder = _SeaNet(sd, "decoder.", cfg, True, dev, wdt)
         self.has_wm = "wmdecoder.wm_embed.weight" in sd
         if self.has_wm:
-            self.wmdecoder = _SeaNet(sd, "wmdecoder.", cfg, True, dev)
-            self.skip_encoder = _SeaNet(sd, "wmdecoder.skip_encoder.", cfg, False, dev)
-            self.wm_encoder = _SeaNet(sd, "wmdecoder.wm_encoder.", cfg, False, dev)
-            self.wm_proj = [_Conv(sd, f"wmdecoder.wm_proj{j}.1.", 1, 1, dev) for j in range(4)]
-            self.wm_predictor = _Conv(sd, "wmdecoder.wm_predictor.1.", 1, 1, dev)
+            self.wmdecoder = _SeaNet(sd, "wmdecoder.", cfg, True, dev, wdt)
+            self.skip_encoder = _SeaNet(sd, "wmdecoder.skip_encoder.", cfg, False, dev, wdt)
+            self.wm_encoder = _SeaNet(sd, "wmdecoder.wm_encoder.", cfg, False, dev, wdt)
+            self.wm_proj = [_Conv(sd, f"wmdecoder.wm_proj{j}.1.", 1, 1, dev, wdt) for j in range(4)]
+            self.wm_predictor = _Conv(sd, "wmdecoder.wm_predictor.1.", 1, 1, dev, wdt)
             w = sd["wmdecoder.wm_embed.weight"]                       # nn.Embedding(2, D/16, max_norm=True) (seanet.py:503)
             norm = w.norm(p=2, dim=1, keepdim=True)
             self.wm_table = torch.where(norm > 1.0, w * (1.0 / (norm + 1e-7)), w).contiguous().to(dev)
@@ -458,6 +478,21 @@ class WMEncodecModel:
         return run()
 
     # ------------------------------------------------------------------ low-level launches
+    @property
+    def one_plane(self) -> bool:
+        """One bf16 plane per matrix and the one-plane entries: a bf16-rounded model with `codec_w1` on."""
+        return self.weight_dtype == "bf16" and bool(self.codec_w1)
+
+    def _call_w1(self, name: str, a) -> bool:
+        """A one-plane entry (`ssrhip_codec_gemm_w1`, `ssrhip_resblock_w1`) on the current stream: False when it answered 1 — nothing was
+        launched and the caller takes the fp32 path on the rounded masters, WITHOUT planes."""
+        self.n_launches += 1
+        rc = getattr(self.lib, name)(C.byref(a), _lib.stream_ptr())
+        if rc == 1:
+            return False
+        _lib.check(rc, name)
+        return True
+
     def _call(self, name: str, *args):
         """One library launch on the current stream. The entry point is looked up at call time: `_sized` swaps `self.lib` for its dry pass
         and tests wrap it."""
@@ -466,17 +501,24 @@ class WMEncodecModel:
 
     def _planes(self, W: torch.Tensor) -> Optional[torch.Tensor]:
         """bf16 planes [3][N][K] of a weight matrix for the split GEMM (csrc/gemm_split.hip: the fp32 operand as the exact sum of three
-        bf16 pieces), made once per matrix on the device; None when the split path is switched off or the shape can never take it."""
+        bf16 pieces), made once per matrix on the device; None when the split path is switched off or the shape can never take it.
+        A `one_plane` model keeps ONE plane [N][K] — the rounded matrix as bfloat16 — which only the one-plane entries may be given: the
+        plane count is part of the cache key."""
         if not self.split_gemm or W.dim() != 2 or W.shape[0] <= 64 or W.shape[1] % 8 != 0:
             return None
-        key = W.data_ptr()
+        n = 1 if self.one_plane else 3
+        key = (W.data_ptr(), n)
         hit = self._plane_cache.get(key)
         if hit is None:
-            hit = self._plane_cache[key] = self._split_planes(W)
+            hit = self._plane_cache[key] = self._split_planes(W, n)
         return hit
 
-    def _split_planes(self, W: torch.Tensor) -> torch.Tensor:
-        """bf16 planes [3][N][K] of any fp32 matrix (uncached: for callers that repack them, e.g. pack_lstm_whh_planes)"""
+    def _split_planes(self, W: torch.Tensor, n: int = 3) -> torch.Tensor:
+        """bf16 planes [3][N][K] of any fp32 matrix (uncached: for callers that repack them, e.g. pack_lstm_whh_planes); n = 1: the one
+        plane [N][K] of a matrix of bf16 values"""
+        if n == 1:
+            assert self.weight_dtype == "bf16", "one plane holds a matrix of bf16 values only"
+            return W.to(torch.bfloat16).contiguous()
         out = torch.empty(3, W.shape[0], W.shape[1], dtype=torch.int16, device=W.device)
         self._call("ssrhip_split_weights", W.data_ptr(), out.data_ptr(), W.numel())
         return out
@@ -487,8 +529,16 @@ class WMEncodecModel:
         Made once per block on the device; None when the split path is off."""
         if not self.split_gemm or c3.Cin not in (64, 128):
             return None
-        key = ("res", c3.W.data_ptr(), c1.W.data_ptr())
+        n = 1 if self.one_plane else 3
+        key = ("res", c3.W.data_ptr(), c1.W.data_ptr(), n)
         hit = self._plane_cache.get(key)
+        if hit is None and n == 1:            # one plane each: the rounded matrices as bfloat16, W1 in the same column order
+            Hh = c3.Cout
+            kp = torch.arange(Hh, device=c1.W.device)
+            j, g, i = kp // 16, (kp // 8) % 2, kp % 8
+            perm = 16 * j + (i % 4) + 8 * (i // 4) + 4 * g
+            hit = (c3.W.reshape(Hh, -1).to(torch.bfloat16).contiguous(), c1.W.reshape(c1.Cout, Hh)[:, perm].to(torch.bfloat16).contiguous())
+            self._plane_cache[key] = hit
         if hit is None:
             Hh = c3.Cout
             kp = torch.arange(Hh, device=c1.W.device)
@@ -519,6 +569,10 @@ class WMEncodecModel:
             # (the ids' item stride: shape[1] for a dense [batch][n]; a batched stream hands in a window of columns of a wider array)
             a.rbias, a.rclass, a.rrep = rowcls[0].data_ptr(), rowcls[1].data_ptr(), int(rowcls[2])
             a.rclass_stride = int(rowcls[1].stride(0)) if batch > 1 else int(rowcls[1].shape[1])
+        if planes is not None and planes.dim() == 2:      # one plane: its own entry; on answer 1 the fp32 chain on the rounded master
+            if self._call_w1("ssrhip_codec_gemm_w1", a):
+                return
+            a.W_split = 0
         self._call("ssrhip_gemm", C.byref(a))
 
     def _fill_pads(self, buf: TM, structural_zero: bool = False):
@@ -626,7 +680,12 @@ class WMEncodecModel:
             planes = self._resblock_planes(c3, c1)
             if planes is not None:
                 a.w3_split, a.w1_split = planes[0].data_ptr(), planes[1].data_ptr()
-            self._call("ssrhip_resblock", C.byref(a))
+            if planes is not None and planes[0].dtype == torch.bfloat16:      # one plane each: its own entry; on answer 1, no planes
+                if not self._call_w1("ssrhip_resblock_w1", a):
+                    a.w3_split = a.w1_split = 0
+                    self._call("ssrhip_resblock", C.byref(a))
+            else:
+                self._call("ssrhip_resblock", C.byref(a))
             out.elu = post_elu
             self._fill_pads(out, structural_zero=(nxt is not None and nxt[1] == "convtr"))
             return out

@@ -71,6 +71,9 @@ struct codec_knobs {
   bool lstm_nowide = getenv_set("SSRHIP_LSTM_NOWIDE");
   int gemm_big = getenv_int("SSRHIP_GEMM_BIG", 0), reschain_big = getenv_int("SSRHIP_RESCHAIN_BIG", 0);   // experiments: larger tiles / row blocks
   int resblock_ring = getenv_int("SSRHIP_RESBLOCK_RING", 2);         // any value other than 2 takes the ring-of-4 kernels
+  // the one-plane residual block (ssrhip_resblock_w1) follows the same switch but defaults to the ring of 4: with 32 C-byte tiles the deeper
+  // ring costs no workgroup per CU (DESIGN.md Part I.30)
+  int resblock_w1_ring = getenv_int("SSRHIP_RESBLOCK_RING", 4);
 };
 inline const codec_knobs& ssr_codec_knobs() { static const codec_knobs k; return k; }
 

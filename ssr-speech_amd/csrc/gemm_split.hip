@@ -582,6 +582,15 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(4, 4))) 
   gemm_split_dma_body<BM, false, 0, false, 1>(a0, flags);
 }
 
+// one W plane for the codec's bf16-rounded weights (ssrhip_codec_gemm_w1, DESIGN I.30): the forms gemm_w1_* leave out — ELU on load and
+// the time mask folded into the 16-byte epilogue. Same bodies, same register budgets as the kernels above.
+template <int BM, bool ELU, bool TMF = false>
+__global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(4, 4))) void codec_w1_dma_kernel(const ssrhip_gemm_args a0, const int flags) {
+  gemm_split_dma_body<BM, ELU, 0, TMF, 1>(a0, flags);
+}
+template <int BM, bool ELU>
+__global__ __launch_bounds__(256, 4) void codec_w1_kernel(const ssrhip_gemm_args a0) { gemm_split_body<BM, ELU, 1>(a0); }
+
 }  // namespace
 
 // true when the split kernel applies to this call (decided by ssrhip_gemm). It depends on the matrix (N, K) and on what the caller
@@ -603,9 +612,9 @@ enum gemm_split_form { GS_DMA128, GS_DMA64, GS_DMA128_TM, GS_4WAVE128, GS_4WAVE6
 struct gemm_split_plan { gemm_split_form form; dim3 grid, block; int lds, flags; };      // `flags`: the DMA kernels' flag word
 
 // `xcd` is SSRHIP_GEMM_XCD as of this call (read at every launch: tests flip it inside one process). `np`: planes of W (3, or 1 for
-// ssrhip_gemm_w1). The form does not depend on it — a one-plane call takes the tile shape its three-plane twin takes — except that the
-// one-plane kernels have no time-mask epilogue.
-gemm_split_plan plan_gemm_split(const ssrhip_gemm_args* a, const codec_knobs& k, const char* xcd, const int np = 3) {
+// ssrhip_gemm_w1 and ssrhip_codec_gemm_w1). The form does not depend on it — a one-plane call takes the tile shape its three-plane twin
+// takes — except that ssrhip_gemm_w1's kernels have no time-mask epilogue; ssrhip_codec_gemm_w1's have (`tm_np1`).
+gemm_split_plan plan_gemm_split(const ssrhip_gemm_args* a, const codec_knobs& k, const char* xcd, const int np = 3, const bool tm_np1 = false) {
   const unsigned nb = a->batch > 1 ? a->batch : 1;
   const long tiles128 = (long)((a->N + BN - 1) / BN) * ((a->M + 127) / 128) * nb;
   // 128-row tiles when there are enough of them for two workgroups on most CUs — unless they would be half empty: the LSTM's second
@@ -617,7 +626,7 @@ gemm_split_plan plan_gemm_split(const ssrhip_gemm_args* a, const codec_knobs& k,
   // the DMA kernels address a tile through 32-bit buffer offsets: 128 rows of A (and of a W plane) have to stay below 2 GiB
   const bool dma = k.gemm_split_dma && ((size_t)127 * a->lda + a->K) * 4 < 0x7FFFFFF0ull && (size_t)128 * a->K * 2 < 0x7FFFFFF0ull;
   // the transposed convolutions' time mask as a row predicate of the 16-byte epilogue (SSRHIP_EPILOGUE_TM=0: the general per-element loop)
-  const bool tmf = np == 3 && k.epilogue_tm && k.gemm_wide && a->tm_c > 0 && a->N % a->tm_c == 0 && a->tm_c % 4 == 0 && !a->R && !a->residual && !a->rbias &&
+  const bool tmf = (np == 3 || tm_np1) && k.epilogue_tm && k.gemm_wide && a->tm_c > 0 && a->N % a->tm_c == 0 && a->tm_c % 4 == 0 && !a->R && !a->residual && !a->rbias &&
                    a->ldc % 4 == 0 && a->strideC % 4 == 0 && ((uintptr_t)a->C & 15) == 0 && (long)a->M * (a->N / a->tm_c) < 0x7FFFFFFFL;
   const dim3 grid((a->N + BN - 1) / BN, (a->M + bm - 1) / bm, nb);
   if (!dma) return {bm == 128 ? GS_4WAVE128 : GS_4WAVE64, grid, dim3(256), 0, 0};
@@ -695,6 +704,66 @@ extern "C" int ssrhip_gemm_w1(const ssrhip_gemm_args* a, ssrhip_stream_t stream)
   }
   SSR_LAUNCH_CHECK();
   ++g_w1_launches;
+  return 0;
+}
+
+static std::atomic<int64_t> g_codec_w1_launches{0};      // one-plane launches through ssrhip_codec_gemm_w1 / ssrhip_resblock_w1
+extern "C" int64_t ssrhip_codec_w1_launches(void) { return g_codec_w1_launches.load(); }
+void ssr_codec_w1_count(void) { ++g_codec_w1_launches; }      // resblock_split.hip
+
+namespace {
+template <int BM, bool ELU, bool TM>
+int launch_codec_w1_dma(const gemm_split_plan& p, const ssrhip_gemm_args* a, hipStream_t s) {
+  SSR_RAISE_LDS(p.lds, codec_w1_dma_kernel<BM, ELU, TM>);
+  hipLaunchKernelGGL((codec_w1_dma_kernel<BM, ELU, TM>), p.grid, p.block, p.lds, s, *a, p.flags);
+  return 0;
+}
+}  // namespace
+
+// One plane of W with the codec's forms: see ssrhip.h. The plan, tile order, k-block order and product order (a2w0, a1w0, a0w0) of the
+// three-plane call of the same arguments.
+extern "C" int ssrhip_codec_gemm_w1(const ssrhip_gemm_args* a, ssrhip_stream_t stream) {
+  SSR_REQUIRE(a && a->A && a->C, "ssrhip_codec_gemm_w1: null argument");
+  SSR_REQUIRE(a->W_split, "ssrhip_codec_gemm_w1: W_split is NULL (it is the one bf16 plane [N][K] this entry multiplies by)");
+  SSR_REQUIRE(a->M > 0 && a->N > 0 && a->K > 0 && a->K % 4 == 0 && a->lda % 4 == 0, "ssrhip_codec_gemm_w1: K and lda must be multiples of 4");
+  SSR_REQUIRE(!a->rbias || (a->rclass && a->rrep > 0), "ssrhip_codec_gemm_w1: rbias needs rclass and rrep > 0");
+  if (!ssrhip_gemm_split_eligible(a)) return 1;
+  hipStream_t s = (hipStream_t)stream;
+  const gemm_split_plan p = plan_gemm_split(a, ssr_codec_knobs(), getenv("SSRHIP_GEMM_XCD"), 1, true);
+  ssr_gemm_log(a, p.grid.x, p.grid.y, p.grid.z, 2);
+  const bool elu = a->act_in == SSRHIP_ACT_ELU;
+  int rc = 0;
+  switch (p.form) {      // without ELU on load and time mask: the kernels ssrhip_gemm_w1 launches
+    case GS_DMA128_TM:
+      if (elu) rc = launch_codec_w1_dma<128, true, true>(p, a, s);
+      else rc = launch_codec_w1_dma<128, false, true>(p, a, s);
+      break;
+    case GS_DMA128:
+      if (elu) rc = launch_codec_w1_dma<128, true, false>(p, a, s);
+      else {
+        SSR_RAISE_LDS(p.lds, gemm_w1_dma_kernel<128>);
+        hipLaunchKernelGGL((gemm_w1_dma_kernel<128>), p.grid, p.block, p.lds, s, *a, p.flags);
+      }
+      break;
+    case GS_DMA64:
+      if (elu) rc = launch_codec_w1_dma<64, true, false>(p, a, s);
+      else {
+        SSR_RAISE_LDS(p.lds, gemm_w1_dma_kernel<64>);
+        hipLaunchKernelGGL((gemm_w1_dma_kernel<64>), p.grid, p.block, p.lds, s, *a, p.flags);
+      }
+      break;
+    case GS_4WAVE128:
+      if (elu) hipLaunchKernelGGL((codec_w1_kernel<128, true>), p.grid, p.block, 0, s, *a);
+      else hipLaunchKernelGGL((gemm_w1_kernel<128>), p.grid, p.block, 0, s, *a);
+      break;
+    case GS_4WAVE64:
+      if (elu) hipLaunchKernelGGL((codec_w1_kernel<64, true>), p.grid, p.block, 0, s, *a);
+      else hipLaunchKernelGGL((gemm_w1_kernel<64>), p.grid, p.block, 0, s, *a);
+      break;
+  }
+  if (rc) return rc;
+  SSR_LAUNCH_CHECK();
+  ++g_codec_w1_launches;
   return 0;
 }
 
