@@ -141,7 +141,7 @@ __device__ __forceinline__ void combine_issue(const GemvK& p, CombineRegs<B>& r,
 #pragma unroll
     for (int i = 0; i < CS / 2; ++i) {
       if (2 * i + 1 < MS) {
-        r.ml[i] = (2 * i < n) ? ld4(ml + 4 * i) : make_float4(-INFINITY, 0.f, -INFINITY, 0.f);
+        r.ml[i] = (2 * i < n) ? ld4(ml + 4 * i) : make_float4(-INFINITY, 0.f, -INFINITY, 0.f);   // odd n < MS: the upper half is page n, which this step did not write (combine_finish guards it)
       } else {                                                       // odd max_splits: the last pair has no partner (never read past the block)
         const float2 v = (2 * i < n) ? *reinterpret_cast<const float2*>(ml + 4 * i) : make_float2(-INFINITY, 0.f);
         r.ml[i] = make_float4(v.x, v.y, -INFINITY, 0.f);
@@ -172,7 +172,7 @@ __device__ __forceinline__ void combine_finish(const GemvK& p, CombineRegs<B>& r
     const float* ml = p.a.part_ml + (size_t)t * MS * 2;
     float M = -INFINITY;
 #pragma unroll
-    for (int i = 0; i < CS / 2; ++i) M = fmaxf(M, fmaxf(r.ml[i].x, r.ml[i].z));
+    for (int i = 0; i < CS / 2; ++i) M = fmaxf(M, fmaxf(r.ml[i].x, (2 * i + 1 < n) ? r.ml[i].z : -INFINITY));   // .x is -inf from 2 * i >= n on; .z may be a dead page
     for (int s2 = CS; s2 < n; ++s2) M = fmaxf(M, ml[2 * s2]);
     float den = 0.f;
 #pragma unroll

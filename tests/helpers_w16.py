@@ -12,6 +12,7 @@ import torch
 import torch.nn.functional as F
 
 import helpers_conditioning as HC
+import helpers_poison as HP
 from ssr_speech_amd import _lib
 from ssr_speech_amd import layout as LY
 from ssr_speech_amd import weights as W
@@ -92,12 +93,14 @@ def kv_pool(B, max_pages, qkv):
     return torch.full((B * max_pages + 1, N_LAYER, 2, H, _lib.PAGE, HD) if qkv else (1,), POISON, device="cuda")
 
 
-def check_launch(L, st, B, G, N, K, pro, act, epi, tiled=0, x=None, part_ml=None):
+def check_launch(L, st, B, G, N, K, pro, act, epi, tiled=0, x=None, part_ml=None, lens=None, dead=float("nan")):
     """ssrhip_gemv_<st.name> on the packed copy against ssrhip_gemv on the fp32 weights: the same bits in the whole output buffer (poisoned
     rows and pad included) and the whole KV pool, then both against torch fp64 on the UNPACKED PACKED BUFFER, which does not depend on the
     fp32 kernel. The page table is shuffled; a QKV launch may have written nothing but its rows' appended positions.
     x [B, G*K] / part_ml [B, H, max_pages, 2] (CPU) replace the default draws (tests/helpers_conditioning.py: ill-conditioned rows and
-    partials); the fp64 bound then follows that file's rule, max(TOL, M * the fp32 reference's own error), the bitwise assertions stay."""
+    partials); the fp64 bound then follows that file's rule, max(TOL, M * the fp32 reference's own error), the bitwise assertions stay.
+    lens (B lengths) / dead (a tests/helpers_poison.py fill) replace the merge prologue's row lengths and what its dead pages hold.
+    Returns the packed launch's whole output buffer."""
     x_given, part_ml_given = x, part_ml
     seed = B * 100003 + N * 7 + K + pro
     g = torch.Generator().manual_seed(seed)
@@ -118,16 +121,14 @@ def check_launch(L, st, B, G, N, K, pro, act, epi, tiled=0, x=None, part_ml=None
     pos_l = st.kv_pos[:B]
     pos = torch.tensor(pos_l, dtype=torch.int32).cuda()
     if combine:                                                           # the split-KV merge prologue (<= 4 rows): partials instead of x
-        lens_l = [300, 129, 384, 1][:B]                                   # 3, 2, 3 and 1 pages of partials
+        lens_l = [300, 129, 384, 1][:B] if lens is None else list(lens)  # 3, 2, 3 and 1 pages of partials
         lens = torch.tensor(lens_l, dtype=torch.int32).cuda()
         part_o = torch.randn(B, H, st.max_pages, HD, generator=g)
         part_ml = torch.stack([torch.randn(B, H, st.max_pages, generator=g) * 2, torch.rand(B, H, st.max_pages, generator=g) + 0.5], dim=-1).contiguous()
         if part_ml_given is not None:
             part_ml = part_ml_given.clone()
         pages = [(n + _lib.PAGE - 1) // _lib.PAGE for n in lens_l]
-        for b in range(B):                                                # beyond a row's pages the buffers hold what the kernel must not use
-            part_o[b, :, pages[b]:] = float("nan")
-            part_ml[b, :, pages[b]:] = float("nan")
+        HP.fill_dead(part_o, part_ml, lens_l, dead)                       # beyond a row's pages the buffers hold what the kernel must not use
         d_po, d_pml = part_o.cuda(), part_ml.cuda()
 
     def run(use_packed):
@@ -212,6 +213,7 @@ def check_launch(L, st, B, G, N, K, pro, act, epi, tiled=0, x=None, part_ml=None
         torch.testing.assert_close(y16[:n_y].view(B, ny), ref.float(), rtol=tol, atol=tol)
     else:
         assert errs[st.name] < tol, errs
+    return y16
 
 
 def check_refusal(L, st, B, N, K):

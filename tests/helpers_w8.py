@@ -9,6 +9,7 @@ import torch
 import torch.nn.functional as F
 
 import helpers_conditioning as HC
+import helpers_poison as HP
 from helpers_w16 import LAYER, N_LAYER, PAD, POISON, STEPS, TOL, H, HD, LAYERS, _trace, kv_pool  # noqa: F401
 from ssr_speech_amd import _lib
 from ssr_speech_amd import weights as W
@@ -73,10 +74,11 @@ def quantized_weights(name, G, N, K, seed):
     return master, packed, scale.contiguous(), unpacked
 
 
-def check_launch(L, B, G, N, K, pro, act, epi, kv_pos=(130, 7, 383, 256), max_pages=3, x=None, part_ml=None):
+def check_launch(L, B, G, N, K, pro, act, epi, kv_pos=(130, 7, 383, 256), max_pages=3, x=None, part_ml=None, lens=None, dead=float("nan")):
     """ssrhip_gemv_w8 on codes + scales against ssrhip_gemv on the master: the same bits in the whole output buffer (pad included) and the
     whole KV pool, then against torch fp64 on the UNPACKED PACKED BUFFER times the scales, which does not depend on the fp32 kernel.
-    x / part_ml: as in helpers_w16.check_launch (ill-conditioned draws; the fp64 bound then follows helpers_conditioning's rule)."""
+    x / part_ml: as in helpers_w16.check_launch (ill-conditioned draws; the fp64 bound then follows helpers_conditioning's rule).
+    lens / dead: as there (the merge prologue's row lengths, the fill of its dead pages). Returns the packed launch's whole output buffer."""
     x_given, part_ml_given = x, part_ml
     seed = B * 100003 + N * 7 + K + pro
     g = torch.Generator().manual_seed(seed)
@@ -96,16 +98,14 @@ def check_launch(L, B, G, N, K, pro, act, epi, kv_pos=(130, 7, 383, 256), max_pa
     pos_l = list(kv_pos[:B])
     pos = torch.tensor(pos_l, dtype=torch.int32).cuda()
     if combine:
-        lens_l = [300, 129, 384, 1][:B]
+        lens_l = [300, 129, 384, 1][:B] if lens is None else list(lens)
         lens = torch.tensor(lens_l, dtype=torch.int32).cuda()
         part_o = torch.randn(B, H, max_pages, HD, generator=g)
         part_ml = torch.stack([torch.randn(B, H, max_pages, generator=g) * 2, torch.rand(B, H, max_pages, generator=g) + 0.5], dim=-1).contiguous()
         if part_ml_given is not None:
             part_ml = part_ml_given.clone()
         pages = [(n + _lib.PAGE - 1) // _lib.PAGE for n in lens_l]
-        for b in range(B):
-            part_o[b, :, pages[b]:] = float("nan")
-            part_ml[b, :, pages[b]:] = float("nan")
+        HP.fill_dead(part_o, part_ml, lens_l, dead)
         d_po, d_pml = part_o.cuda(), part_ml.cuda()
 
     def run(use_packed):
@@ -178,6 +178,7 @@ def check_launch(L, B, G, N, K, pro, act, epi, kv_pos=(130, 7, 383, 256), max_pa
         torch.testing.assert_close(got, ref.float(), rtol=tol, atol=tol)
     else:
         assert err < tol, err
+    return y8
 
 
 def check_refusal(L, B, N, K):

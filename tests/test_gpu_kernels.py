@@ -441,59 +441,77 @@ def _gemv_pair_chains(L, rows=None, partials=None):
             assert np.abs(res["two"][2]).sum() > 0
     # ---- the other pair of the step: split-KV merge + out-projection + residual, then LN + FFN1 + ReLU (gemv_pair_merge_kernel); contexts of
     # 8 / 2 pages (beyond the 6 prefetched ones / short) and 3 / 5 pages, odd max_splits too
-    H, hd = 16, 128
     for MS, lens in ((8, [1000, 129]), (8, [300, 640]), (7, [7 * _lib.PAGE, 1])):
-        g = torch.Generator().manual_seed(MS + lens[0])
-        Wo = [(torch.randn(D, D, generator=g) / math.sqrt(D)).cuda() for _ in range(2)]
-        bo = torch.randn(D, generator=g).cuda()
-        W1 = [(torch.randn(F, D, generator=g) / math.sqrt(D)).cuda() for _ in range(2)]
-        b1 = torch.randn(F, generator=g).cuda()
-        part_o = torch.randn(B, H, MS, hd, generator=g).cuda()
-        part_ml = torch.stack([torch.randn(B, H, MS, generator=g) * 2, torch.rand(B, H, MS, generator=g) + 0.5], dim=-1).contiguous().cuda()
-        if partials is not None:
-            part_ml = HC.ml_cases(B, H, MS, lens, MS)[partials].cuda()
-        for b_ in range(B):                                          # beyond the row's pages the buffers hold garbage the kernel must not use
-            n = (lens[b_] + _lib.PAGE - 1) // _lib.PAGE
-            part_o[b_, :, n:] = float("nan")
-            part_ml[b_, :, n:] = float("nan")
-        dlen = torch.tensor(lens, dtype=torch.int32, device="cuda")
-        x0 = (torch.randn(B, D, generator=g) * 1.5 + 0.3)
-        if rows is not None:
-            x0 = HC.ln_rows(B, D, MS)[rows]
-        res = {}
-        for form in ("two", "pair"):
-            x = x0.clone().cuda()
-            y = torch.zeros(B, F, device="cuda")
-            n_pairs = 5
-            buf = lambda i: 1 if (i == n_pairs - 1 and n_pairs % 3 == 1) else i % 3
-            for rep in range(2):
-                for i in range(n_pairs):
-                    a = _lib.GemvArgs()
-                    a.W, a.bias, a.y = Wo[i % 2].data_ptr(), bo.data_ptr(), x.data_ptr()
-                    a.B, a.N, a.K, a.groups, a.x_stride, a.y_stride = B, D, D, 1, D, D
-                    a.pro, a.act, a.epi = _lib.PRO_ATTN_COMBINE, 0, _lib.EPI_RESIDUAL
-                    a.part_o, a.part_ml, a.max_splits, a.row_len = part_o.data_ptr(), part_ml.data_ptr(), MS, dlen.data_ptr()
-                    a.kv = _lib.KV(0, 0, MS, 1, H, hd)
-                    b = _lib.GemvArgs()
-                    b.W, b.bias, b.x, b.y = W1[i % 2].data_ptr(), b1.data_ptr(), x.data_ptr(), y.data_ptr()
-                    b.B, b.N, b.K, b.groups, b.x_stride, b.y_stride = B, F, D, 1, D, F
-                    b.pro, b.act, b.epi, b.ln_eps = 1, 1, 0, 1e-5
-                    assert L.ssrhip_gemv_pair_applicable(C.byref(a), C.byref(b)) == 1
-                    if form == "two":
-                        _lib.check(L.ssrhip_gemv(C.byref(a), _lib.stream_ptr()))
-                        _lib.check(L.ssrhip_gemv(C.byref(b), _lib.stream_ptr()))
-                    else:
-                        rc = L.ssrhip_gemv_pair(C.byref(a), C.byref(b), ws.data_ptr(), buf(i), buf((i + 1) % n_pairs), _lib.stream_ptr())
-                        assert rc == 0, rc
-            torch.cuda.synchronize()
-            res[form] = (x.cpu().numpy(), y.cpu().numpy())
-        assert L.ssrhip_gemv_pair_status(ws.data_ptr(), _lib.stream_ptr()) == 0
-        for k, (got, want) in enumerate(zip(res["pair"], res["two"])):
-            assert np.isfinite(want).all()
-            assert np.array_equal(got, want), ("merge", MS, lens, k, float(np.abs(got - want).max()))
+        _gemv_pair_merge_chains(L, ws, MS, lens, rows, partials)
     # shapes that do not qualify are refused, nothing is launched
     a = _lib.GemvArgs(); b = _lib.GemvArgs()
     assert L.ssrhip_gemv_pair_applicable(C.byref(a), C.byref(b)) == 0
+
+
+def _gemv_pair_merge_mats(seed):
+    """(generator, out-projections, bias, FFN1 matrices, bias) of one merge chain, in the chain's order of draws"""
+    D, F = 2048, 8192
+    g = torch.Generator().manual_seed(seed)
+    Wo = [(torch.randn(D, D, generator=g) / math.sqrt(D)).cuda() for _ in range(2)]
+    bo = torch.randn(D, generator=g).cuda()
+    W1 = [(torch.randn(F, D, generator=g) / math.sqrt(D)).cuda() for _ in range(2)]
+    b1 = torch.randn(F, generator=g).cuda()
+    return g, Wo, bo, W1, b1
+
+
+def _gemv_pair_merge_chains(L, ws, MS, lens, rows=None, partials=None, dead=float("nan"), mats=None):
+    """The merge half of _gemv_pair_chains for one (max_splits, lengths): 5 pairs replayed twice, both forms, whole buffers equal.
+    dead: the tests/helpers_poison.py fill of the pages beyond each row; mats: _gemv_pair_merge_mats drawn by the caller (kept across
+    calls; the partials then come from a generator of their own). Returns the two forms' (x, y)."""
+    import helpers_conditioning as HC
+    import helpers_poison as HP
+    B, D, F, H, hd = 2, 2048, 8192, 16, 128
+    if mats is None:
+        g, Wo, bo, W1, b1 = _gemv_pair_merge_mats(MS + lens[0])
+    else:
+        (_, Wo, bo, W1, b1), g = mats, torch.Generator().manual_seed(MS + lens[0])
+    part_o = torch.randn(B, H, MS, hd, generator=g)
+    part_ml = torch.stack([torch.randn(B, H, MS, generator=g) * 2, torch.rand(B, H, MS, generator=g) + 0.5], dim=-1).contiguous()
+    if partials is not None:
+        part_ml = HC.ml_cases(B, H, MS, lens, MS)[partials]
+    HP.fill_dead(part_o, part_ml, lens, dead)                    # beyond the row's pages the buffers hold garbage the kernel must not use
+    part_o, part_ml = part_o.cuda(), part_ml.cuda()
+    dlen = torch.tensor(lens, dtype=torch.int32, device="cuda")
+    x0 = (torch.randn(B, D, generator=g) * 1.5 + 0.3)
+    if rows is not None:
+        x0 = HC.ln_rows(B, D, MS)[rows]
+    res = {}
+    for form in ("two", "pair"):
+        x = x0.clone().cuda()
+        y = torch.zeros(B, F, device="cuda")
+        n_pairs = 5
+        buf = lambda i: 1 if (i == n_pairs - 1 and n_pairs % 3 == 1) else i % 3
+        for rep in range(2):
+            for i in range(n_pairs):
+                a = _lib.GemvArgs()
+                a.W, a.bias, a.y = Wo[i % 2].data_ptr(), bo.data_ptr(), x.data_ptr()
+                a.B, a.N, a.K, a.groups, a.x_stride, a.y_stride = B, D, D, 1, D, D
+                a.pro, a.act, a.epi = _lib.PRO_ATTN_COMBINE, 0, _lib.EPI_RESIDUAL
+                a.part_o, a.part_ml, a.max_splits, a.row_len = part_o.data_ptr(), part_ml.data_ptr(), MS, dlen.data_ptr()
+                a.kv = _lib.KV(0, 0, MS, 1, H, hd)
+                b = _lib.GemvArgs()
+                b.W, b.bias, b.x, b.y = W1[i % 2].data_ptr(), b1.data_ptr(), x.data_ptr(), y.data_ptr()
+                b.B, b.N, b.K, b.groups, b.x_stride, b.y_stride = B, F, D, 1, D, F
+                b.pro, b.act, b.epi, b.ln_eps = 1, 1, 0, 1e-5
+                assert L.ssrhip_gemv_pair_applicable(C.byref(a), C.byref(b)) == 1
+                if form == "two":
+                    _lib.check(L.ssrhip_gemv(C.byref(a), _lib.stream_ptr()))
+                    _lib.check(L.ssrhip_gemv(C.byref(b), _lib.stream_ptr()))
+                else:
+                    rc = L.ssrhip_gemv_pair(C.byref(a), C.byref(b), ws.data_ptr(), buf(i), buf((i + 1) % n_pairs), _lib.stream_ptr())
+                    assert rc == 0, rc
+        torch.cuda.synchronize()
+        res[form] = (x.cpu().numpy(), y.cpu().numpy())
+    assert L.ssrhip_gemv_pair_status(ws.data_ptr(), _lib.stream_ptr()) == 0
+    for k, (got, want) in enumerate(zip(res["pair"], res["two"])):
+        assert np.isfinite(want).all()
+        assert np.array_equal(got, want), ("merge", MS, lens, k, float(np.abs(got - want).max()))
+    return res
 
 
 def _lib_pair_ws_bytes():

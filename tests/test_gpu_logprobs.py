@@ -386,6 +386,98 @@ def test_off_means_off():
     assert len(call()) == 4 and next(iter(m._engines.values())).logp is None               # and back: the flag is part of the engine's key
 
 
+# ---------------------------------------------------------------------------------------------------------------- a reused engine
+def _two_utterances():
+    """The sample-score test's model and two utterances for it: 15 and 35 phonemes behind prompts of 20 and 17 frames (the length rule
+    lets them generate 131 and 334 steps). Under CFG they are the 4 rows of one engine; rows of 36 and 53 positions that generate past
+    position 128, into the second page of their caches."""
+    from test_gpu_stream_batch import FakePhonemizer, PHN2NUM, _pipeline
+    args, m, _ = _pipeline()
+    g = torch.Generator().manual_seed(27)
+    utts = []
+    for text, T in (("hello world again", 20), ("a much longer line of text to read out loud", 17)):
+        utts.append({"x": S._phoneme_ids(FakePhonemizer(), PHN2NUM, text), "y": torch.randint(0, args.audio_vocab_size, (1, T, 4), generator=g),
+                     "mask_interval": torch.LongTensor([[[T, T]]])})
+    return args, m, utts
+
+
+def _assert_same_bits(runs, names):
+    """runs: one tuple of arrays per decode; every decode equals the first one bit for bit"""
+    for i, run in enumerate(runs[1:], 1):
+        for name, got, want in zip(names, run, runs[0]):
+            got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
+            assert got.shape == want.shape, (i, name)
+            same = got.view(np.int32) == want.view(np.int32) if got.dtype == np.float32 else got == want
+            assert same.all(), (f"decode {i} against decode 0", name, int((~same).sum()), "of", same.size)
+
+
+def test_a_hand_stepped_decode_does_not_depend_on_what_its_engine_decoded_before():
+    """ONE engine, two utterances under CFG (4 rows: the row-per-wave merge prologue, d_model 128), fixed noise, 110 single steps, four
+    times over; before the fourth, `part_ml` — the buffer DESIGN.md Part I.27 traced the difference to — is filled with 3.0e38. The
+    logits handed to the sampler after every step, the tokens and the log-probabilities of all four decodes are the same bits."""
+    from ssr_speech_amd.engine import DecodeEngine, DecodeKnobs, LMWeightsArena
+    args, m, utts = _two_utterances()
+    arena = LMWeightsArena(args, m.state_dict(), torch.device("cuda"))
+    K, steps = args.n_codebooks, 110
+    g = torch.Generator().manual_seed(28)
+    rows, cols, knobs = [], [], []
+    for u, ut in enumerate(utts):
+        Lx = ut["x"].shape[1]
+        cated, _, num_task, _ = LY.build_layout(ut["y"][0].T.numpy(), ut["mask_interval"][0].numpy(), args)
+        rows += [ut["x"][0].numpy(), torch.randint(0, args.text_vocab_size + 1, (Lx,), generator=g).numpy()]
+        cols.append(cated)
+        knobs.append(DecodeKnobs(top_k=40, top_p=0.8, temperature=1.0, stop_repetition=2, silence_tokens=(3, 7, 11), cfg_coef=1.5, cfg_stride=2,
+                                 use_cfg=True, text_len=Lx, n_spans=num_task, seed=11 + u))
+    noise = torch.empty(2, steps, K, arena.card).exponential_(1, generator=g).cuda()
+    eng = DecodeEngine(arena, 2, True, 256, 128, debug_logits=True, logprobs=True)
+    assert eng.B == 4 and eng.max_pages >= 2
+
+    def decode():
+        eng.start(rows, cols, knobs, noise=noise)
+        logits = []
+        for _ in range(steps):
+            eng.decode(1, use_graph=True)
+            torch.cuda.synchronize()
+            logits.append(eng.dbg_logits.clone())
+        assert int(eng.row_len.min()) > _lib.PAGE and not any(s.done for s in eng.states())       # every row crossed into its second page
+        return (torch.stack(logits).cpu().numpy(), np.stack([eng.tokens(u, steps) for u in range(2)]),
+                np.stack([eng.logprobs(u, steps) for u in range(2)]))
+
+    try:
+        runs = [decode() for _ in range(3)]
+        eng.part_ml.fill_(3.0e38)
+        runs.append(decode())
+    finally:
+        eng.close()
+    assert np.isfinite(runs[0][0]).any() and np.isfinite(runs[0][2]).any()
+    _assert_same_bits(runs, ("logits", "tokens", "logprobs"))
+
+
+def test_a_queued_decode_does_not_depend_on_what_its_engine_decoded_before():
+    """The same through `inference_batch` (`run_queue`, the host's noise feed, 16-step chunks, graph replay): four calls on the engine
+    the first one built, `part_ml` filled with 3.0e38 before the fourth. Tokens, log-probabilities and the last step's logits."""
+    args, m, utts = _two_utterances()
+    kw = dict(top_k=40, top_p=0.8, temperature=1, stop_repetition=2, cfg_coef=1.5, cfg_stride=2, aug_text=True, seed=11, return_logprobs=True)
+    before = m.debug_logits
+    m.debug_logits = True
+    try:
+        runs, engines = [], []
+        for i in range(4):
+            if i == 3:
+                engines[0].part_ml.fill_(3.0e38)
+            res = m.inference_batch(utts, **kw)
+            eng = next(iter(m._engines.values()))
+            engines.append(eng)
+            torch.cuda.synchronize()
+            runs.append(tuple(r[0].cpu().numpy() for r in res) + tuple(r[4].steps for r in res) + (eng.dbg_logits.cpu().numpy(),))
+        assert all(e is engines[0] for e in engines) and engines[0].B == 4
+        for u, ut in enumerate(utts):                                     # each utterance generated into the second page of its cache
+            assert ut["x"].shape[1] + ut["y"].shape[1] + runs[0][2 + u].shape[0] > _lib.PAGE
+    finally:
+        m.debug_logits = before
+    _assert_same_bits(runs, ("res0", "res1", "logprobs0", "logprobs1", "last logits"))
+
+
 # ---------------------------------------------------------------------------------------------------------------- the samples
 def test_sample_scores_rank_the_samples_of_one_utterance(tmp_path):
     from test_gpu_stream_batch import FakePhonemizer, PHN2NUM, _pipeline
@@ -397,23 +489,15 @@ def test_sample_scores_rank_the_samples_of_one_utterance(tmp_path):
     call = (m, margs, PHN2NUM, FakePhonemizer(), tok, fn, "hello world", "hello world again", torch.LongTensor([[20, 20]]), 1.5, 2, True, False,
             False, True, "cuda", dc)
     seeds = [11, 12]
-
-    def fresh_engine():
-        """The next decode builds its engine anew. A decode's logits are a function of its inputs and of how many decodes its engine has
-        run before (DESIGN.md Part I.27, Open): two decodes that are each the first of their engine give the same bits."""
-        for e in m._engines.values():
-            e.close()
-        m._engines = {}
-
+    # every decode below reuses the engine of the one before it where the shapes allow: a decode's bits do not depend on what its engine
+    # decoded before (DESIGN.md Part I.27; the tests above hold the engine to that)
     plain = S.inference_samples(*call, seeds=seeds)
-    fresh_engine()
     waves, scores = S.inference_samples(*call, seeds=seeds, return_scores=True)
     assert len(waves) == len(plain) == len(scores) == 2
     for w, p in zip(waves, plain):
         assert w.shape == p.shape and torch.equal(w.view(torch.int32), p.view(torch.int32))
     y, _ = S._prompt_codes(tok, fn, 4)
     one = {"x": S._phoneme_ids(FakePhonemizer(), PHN2NUM, "hello world again"), "y": y, "mask_interval": torch.LongTensor([[[20, 20]]])}
-    fresh_engine()
     res = m.inference_batch([one] * 2, top_k=40, top_p=0.8, temperature=1, stop_repetition=2, cfg_coef=1.5, cfg_stride=2, aug_text=True,
                             seed=11, return_logprobs=True)
     for i, (sc, r) in enumerate(zip(scores, res)):

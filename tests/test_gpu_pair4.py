@@ -15,6 +15,7 @@ import torch
 
 import ssr_speech_amd  # noqa: F401
 import helpers_conditioning as HC
+import helpers_poison as HP
 from ssr_speech_amd import _lib
 from ssr_speech_amd.engine import PAIR4_WS_BYTES, DecodeEngine, LMWeightsArena
 from ssr_speech_amd.models.ssr import SSR_Speech
@@ -150,18 +151,16 @@ def test_merge_form_is_bit_identical_to_the_two_launches(L, weights, MS, lens):
     _merge_both_forms(L, weights, MS, lens)
 
 
-def _merge_both_forms(L, weights, MS, lens, part_ml=None):
-    """the chain of the test above; part_ml [B, H, MS, 2] (CPU, NaN beyond each row's pages) replaces today's draw of the partials"""
+def _merge_both_forms(L, weights, MS, lens, part_ml=None, dead=float("nan")):
+    """the chain of the test above; part_ml [B, H, MS, 2] (CPU, NaN beyond each row's pages) replaces today's draw of the partials;
+    dead: the tests/helpers_poison.py fill of the pages beyond each row. Returns the forms' whole output buffers."""
     part_ml_given = part_ml
     g = torch.Generator().manual_seed(MS + lens[0])
     part_o = torch.randn(B, H, MS, HD, generator=g)
     part_ml = torch.stack([torch.randn(B, H, MS, generator=g) * 2, torch.rand(B, H, MS, generator=g) + 0.5], dim=-1).contiguous()
-    for r in range(B):                                           # beyond the row's pages the buffers hold what the kernel must not use
-        n = (lens[r] + _lib.PAGE - 1) // _lib.PAGE
-        part_o[r, :, n:] = float("nan")
-        part_ml[r, :, n:] = float("nan")
     if part_ml_given is not None:
-        part_ml = part_ml_given
+        part_ml = part_ml_given.clone()
+    HP.fill_dead(part_o, part_ml, lens, dead)                    # beyond the row's pages the buffers hold what the kernel must not use
     part_o, part_ml = part_o.cuda(), part_ml.cuda()
     dlen = torch.tensor(lens, dtype=torch.int32, device="cuda")
     x0 = (torch.randn(B, D, generator=g) * 1.5 + 0.3).cuda()
@@ -187,6 +186,7 @@ def _merge_both_forms(L, weights, MS, lens, part_ml=None):
         assert bool((x[B * D:] == POISON).all()) and bool((y[B * F:] == POISON).all()), form
         res[form] = (x.cpu().numpy(), y.cpu().numpy())
     _compare(res, ("merge", MS, lens))
+    return res
 
 
 @pytest.mark.parametrize("rows", ["offset", "step"])

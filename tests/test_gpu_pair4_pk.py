@@ -20,6 +20,7 @@ import torch
 
 import ssr_speech_amd  # noqa: F401
 import helpers_conditioning as HC
+import helpers_poison as HP
 from ssr_speech_amd import _lib
 from ssr_speech_amd.engine import PAIR4_WS_BYTES, DecodeEngine, LMWeightsArena
 from ssr_speech_amd.models.ssr import SSR_Speech
@@ -192,9 +193,10 @@ def test_the_smallest_cycle_of_two_pairs_replayed_three_times(L, stream):
     assert int((res["pk"][2] != POISON).sum()) == 2 * B * N_LAYER * D
 
 
-def _merge_three_ways(lib, stream, monkeypatch, MS, lens, early, part_ml=None, wkey=None):
+def _merge_three_ways(lib, stream, monkeypatch, MS, lens, early, part_ml=None, wkey=None, dead=float("nan")):
     """split-KV merge + out-projection + residual | LN + FFN1 + ReLU, 5 pairs replayed twice, all three forms; part_ml [B, H, MS, 2] (CPU,
-    NaN beyond each row's pages) replaces today's draw of the partials"""
+    NaN beyond each row's pages) replaces today's draw of the partials;
+    dead: the tests/helpers_poison.py fill of the pages beyond each row. Returns the forms' whole output buffers."""
     weights = _weights(wkey or stream)
     part_ml_given = part_ml
     if early is None:
@@ -204,12 +206,9 @@ def _merge_three_ways(lib, stream, monkeypatch, MS, lens, early, part_ml=None, w
     g = torch.Generator().manual_seed(MS + lens[0])
     part_o = torch.randn(B, H, MS, HD, generator=g)
     part_ml = torch.stack([torch.randn(B, H, MS, generator=g) * 2, torch.rand(B, H, MS, generator=g) + 0.5], dim=-1).contiguous()
-    for r in range(B):                                           # beyond the row's pages the buffers hold what the kernel must not use
-        n = (lens[r] + _lib.PAGE - 1) // _lib.PAGE
-        part_o[r, :, n:] = float("nan")
-        part_ml[r, :, n:] = float("nan")
     if part_ml_given is not None:
-        part_ml = part_ml_given
+        part_ml = part_ml_given.clone()
+    HP.fill_dead(part_o, part_ml, lens, dead)                    # beyond the row's pages the buffers hold what the kernel must not use
     part_o, part_ml = part_o.cuda(), part_ml.cuda()
     dlen = torch.tensor(lens, dtype=torch.int32, device="cuda")
     x0 = (torch.randn(B, D, generator=g) * 1.5 + 0.3).cuda()
@@ -235,6 +234,7 @@ def _merge_three_ways(lib, stream, monkeypatch, MS, lens, early, part_ml=None, w
         assert bool((x[B * D:] == POISON).all()) and bool((y[B * F:] == POISON).all()), form
         res[form] = (x.cpu().numpy(), y.cpu().numpy())
     _compare(res, (stream, "merge", MS, lens, early))
+    return res
 
 
 @pytest.mark.parametrize("early", [None, "0"])
