@@ -625,6 +625,21 @@ typedef struct ssrhip_lstm_args {
   const uint16_t* w_split; uint16_t* hsplit;
 } ssrhip_lstm_args;
 int ssrhip_lstm_layer(const ssrhip_lstm_args* a, ssrhip_stream_t stream);
+/* The split-operand step of ssrhip_lstm_layer for a recurrent matrix whose every value IS a bf16 value (WMEncodecModel
+ * weight_dtype="bf16"): `a->w_split` is ONE bf16 plane in fragment order, [C/16][4][KS][2][64][8] — the slice q = 0 of the three-plane
+ * layout above, a third of its bytes — and `a->hsplit` is the three-plane path's workspace, byte for byte (h is an fp32 activation and keeps
+ * its three pieces). Three products per accumulator and k-step instead of six (csrc/lstm_w1.hip). ssrhip_lstm_layer's contract and time
+ * windows: a call with t_begin == 0 zeroes both hsplit buffers, a later window continues from them; out / cbuf / hsplit are those of
+ * ssrhip_lstm_layer on the three planes of the same matrix BIT FOR BIT, so windows of one sequence may alternate between the two entries.
+ * Returns 0 when it launched; 1, launching nothing, where ssrhip_lstm_layer would not take the split step (C % 128 != 0, C > 4096,
+ * B < 32, or the small-batch shapes B <= 4 with C in {256,512,1024,2048}): the caller then calls ssrhip_lstm_layer with
+ * w_split = hsplit = NULL; < 0 for a contract error (a null argument, w_split and hsplit not both set, a bad window), before any HIP
+ * call. SSRHIP_LSTM_W1_DEPTH=8 (read at every call) keeps eight k-steps in flight instead of four where C % 512 == 0. NEVER hand a
+ * one-plane buffer to ssrhip_lstm_layer: it reads three planes, twice the buffer's size past its end. */
+int ssrhip_lstm_layer_w1(const ssrhip_lstm_args* a, ssrhip_stream_t stream);
+/* how many one-plane STEP kernels ssrhip_lstm_layer_w1 has launched in this process so far (one per time step of every call that
+ * answered 0); ssrhip_codec_w1_launches does not count them. */
+int64_t ssrhip_lstm_w1_launches(void);
 /* residual vector quantisation (quantization/core_vq.py:164-179, 382-400): emb [B][T][D] time-major;
  * codebooks [n_q][bins][D]; e2 [n_q][bins] = |e|^2; codes int32 [B][n_q][T] */
 int ssrhip_rvq_encode(const float* emb, const float* codebooks, const float* e2, int32_t* codes, int32_t B, int32_t T,

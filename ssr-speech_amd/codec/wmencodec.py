@@ -196,6 +196,19 @@ def pack_lstm_whh_planes(planes: torch.Tensor) -> torch.Tensor:
     return x.permute(0, 1, 2, 3, 5, 6, 4, 7).contiguous()         # ub, w, s, mb, q, lh, li, e
 
 
+def pack_lstm_whh_plane(W: torch.Tensor) -> torch.Tensor:
+    """A recurrent matrix of bf16 values, [4C][C] bfloat16 -> the ONE plane `csrc/lstm_w1.hip` streams (`ssrhip_lstm_layer_w1`):
+        out[ub][w][s][mb][lh][li][e] = W[g C + 16 ub + u][w C/4 + 16 s + 8 lh + e]      with 32 mb + li = 16 g + u,
+    the slice q = 0 of `pack_lstm_whh_planes` of the matrix's exact split, whose planes 1 and 2 are zeros. Needs C % 64 == 0."""
+    rows, Cc = W.shape
+    assert W.dtype == torch.bfloat16 and rows == 4 * Cc and Cc % 64 == 0, (W.dtype, W.shape)
+    ks = Cc // 64
+    x = W.reshape(4, Cc // 16, 16, 4, ks, 2, 8)                   # g, ub, u, w, s, lh, e
+    x = x.permute(1, 3, 4, 0, 2, 5, 6)                            # ub, w, s, g, u, lh, e
+    x = x.reshape(Cc // 16, 4, ks, 2, 32, 2, 8)                   # (g, u) -> m = 16 g + u = 32 mb + li
+    return x.permute(0, 1, 2, 3, 5, 4, 6).contiguous()            # ub, w, s, mb, lh, li, e
+
+
 class _Lstm:
     def __init__(self, sd, pfx, layers, dev, wdt="fp32"):
         self.layers = []
@@ -338,6 +351,11 @@ _ENV_KNOBS = (
     # a weight_dtype="bf16" model: ONE bf16 plane per matrix and the one-plane kernels (three products per k block); 0: three planes of the
     # rounded weights through the six-product kernels — the same bits (DESIGN.md Part I.30). Ignored for weight_dtype="fp32"
     ("codec_w1", "SSRHIP_CODEC_W1", "1", _not0),
+    # ... and its LSTM recurrence: ONE plane of W_hh in fragment order through `ssrhip_lstm_layer_w1` (csrc/lstm_w1.hip: three products per
+    # k-step, a third of the W_hh bytes); 0: three planes of the rounded W_hh through the six-product step — the same bits (DESIGN.md
+    # Part I.31: 9.6 against 11.8 us per step at 256 items, 7 % of a 256 x 30 s pass). Ignored unless the model is `one_plane` and
+    # `lstm_split` is on
+    ("lstm_w1", "SSRHIP_LSTM_W1", "1", _not0),
 )
 
 
@@ -416,7 +434,14 @@ class WMEncodecModel:
                     for l, (wih, whh, _) in enumerate(obj.layers):
                         self._planes(wih)
                         if self.lstm_split and obj.C % 128 == 0 and obj.split[l] is None:
-                            obj.split[l] = pack_lstm_whh_planes(self._split_planes(whh))
+                            if self.lstm_one_plane:      # bfloat16: `_lstm_steps` tells the two packs apart by their dtype
+                                # == pack_lstm_whh_plane(whh.to(bfloat16)): plane 0 of the three-plane pack (planes 1 and 2 of a rounded
+                                # matrix are zeros). Cut out of the three-plane temporaries, which then go back to the caching allocator:
+                                # construction requests what it requested before, and the pool it leaves to the passes is no smaller
+                                # (a pass covered by an earlier envelope of `_sized` has no dry pass of its own and lives on that pool)
+                                obj.split[l] = pack_lstm_whh_planes(self._split_planes(whh))[:, :, :, :, 0].contiguous().view(torch.bfloat16)
+                            else:
+                                obj.split[l] = pack_lstm_whh_planes(self._split_planes(whh))
         if self.has_wm:
             for Wa, _ in self.wm_cls:
                 self._planes(Wa)
@@ -482,6 +507,11 @@ class WMEncodecModel:
     def one_plane(self) -> bool:
         """One bf16 plane per matrix and the one-plane entries: a bf16-rounded model with `codec_w1` on."""
         return self.weight_dtype == "bf16" and bool(self.codec_w1)
+
+    @property
+    def lstm_one_plane(self) -> bool:
+        """W_hh as one plane and the one-plane recurrence step: a `one_plane` model with `lstm_split` and `lstm_w1` on."""
+        return self.one_plane and bool(self.lstm_split) and bool(self.lstm_w1)
 
     def _call_w1(self, name: str, a) -> bool:
         """A one-plane entry (`ssrhip_codec_gemm_w1`, `ssrhip_resblock_w1`) on the current stream: False when it answered 1 — nothing was
@@ -722,6 +752,12 @@ class WMEncodecModel:
         a.gin_bstride, a.out_bstride, a.skip_bstride = T * 4 * Cc, out_bs, skip_bs
         a.t_begin, a.t_end = t0, t1
         a.out_act = _lib.ACT_ELU if out_elu else 0
+        # the entry follows the BUFFER held (bfloat16 = the one-plane pack, int16 = three planes), never the knob: a one-plane buffer in the
+        # three-plane entry would be read twice its size past its end
+        if hsplit is not None and L.split[l].dtype == torch.bfloat16:
+            if self._call_w1("ssrhip_lstm_layer_w1", a):
+                return
+            a.w_split = a.hsplit = 0          # answered 1: the fp32 pipe on the rounded W_hh, what a three-plane model runs at such a shape
         self._call("ssrhip_lstm_layer", C.byref(a))
 
     def _lstm(self, L: _Lstm, x: TM, nxt, post_elu: bool = False) -> TM:

@@ -19,37 +19,9 @@
 //         piece q of h[64 bg + 32 nb + li][w C/4 + 16 s + 8 lh + e]
 // with KS = C/64 k-steps of 16 per wave. The producing thread of h[b][j] splits it and stores the three 2-byte pieces at their fragment
 // positions, so the next step reads its B operand with no staging at all. fp32 h is not kept (`hbuf` is unused on this path).
-#include <stdlib.h>
-#include "common.h"
+#include "lstm_split_step.h"      // everything of the step outside its k-loop, shared with csrc/lstm_w1.hip
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bfx2 __attribute__((ext_vector_type(2)));
-
-constexpr int LS_TH = 256, LS_BN = 64, LS_UN = 16, LS_PS = 65;         // threads, batch rows / hidden units per workgroup, LDS row stride (floats)
-constexpr int ls_lds() { return 4 * LS_BN * LS_PS * 4; }               // four partial tiles [n][m], rows padded to 65: conflict-free stores
-
-__device__ __forceinline__ float sigmoid_(float v) { return 1.0f / (1.0f + expf(-v)); }
-
-// index (in uint16 units) of the KiB block (64 lanes x 8 bf16) of `hsplit` / `w_split`: [outer][wave][kstep][block][plane]
-__device__ __forceinline__ size_t frag_block(int outer, int wave, int ks, int s, int blk, int q) {
-  return (((((size_t)outer * 4 + wave) * ks + s) * 2 + blk) * 3 + q) * 512;
-}
-
-// exact three-way split of one value (gemm_split.hip's split4, one lane wide)
-__device__ __forceinline__ void split1(float v, unsigned short (&p)[3]) {
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    const f32x2 r = {v, 0.f};
-    const bfx2 b = __builtin_convertvector(r, bfx2);                  // v_cvt_pk_bf16_f32 (RNE)
-    const unsigned bits = __builtin_bit_cast(unsigned, b) & 0xFFFFu;
-    p[q] = (unsigned short)bits;
-    v -= __builtin_bit_cast(float, bits << 16);
-  }
-}
 
 template <int DEPTH>
 __global__ __launch_bounds__(LS_TH, 1) void lstm_step_split_kernel(const ssrhip_lstm_args a, const int t, const unsigned short* __restrict__ hp,
@@ -57,22 +29,10 @@ __global__ __launch_bounds__(LS_TH, 1) void lstm_step_split_kernel(const ssrhip_
   constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};   // w2h0, w0h2, w1h1, w1h0, w0h1, w0h0 (smallest first, as gemm_split.hip)
   extern __shared__ __attribute__((aligned(16))) float part[];           // [4 waves][64 n][LS_PS]
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int li = lane & 31, lh = lane >> 5;
-  const int ub = blockIdx.x, bg = blockIdx.y, C = a.C;
+  const int ub = blockIdx.x, bg = blockIdx.y;
 
-  // ---- what the finishing phase needs, requested first: thread p = tid + 256 i finishes unit u = p % 16 of batch row bl = p / 16
-  // (16 consecutive lanes = 16 consecutive hidden units of one item: 64-byte runs of gin / c / skip / out)
-  float pg[4][4], pc[4], ps[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int p = tid + LS_TH * i, u = p & 15, bl = p >> 4;
-    const int b = min(bg * LS_BN + bl, a.B - 1), j = ub * LS_UN + u;
-    const float* gin = a.gin + (size_t)b * a.gin_bstride + (size_t)t * 4 * C + j;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) pg[i][g] = gin[(size_t)g * C];
-    pc[i] = (t == 0) ? 0.f : a.cbuf[(size_t)b * C + j];
-    ps[i] = a.skip ? a.skip[(size_t)b * a.skip_bstride + (size_t)t * C + j] : 0.f;
-  }
+  ls_requests rq;
+  ls_request(a, t, tid, ub, bg, rq);            // gin / c / skip of the finishing phase, requested first
 
   // ---- the K loop: DEPTH k-steps of operands in flight (12 KiB-loads each), 24 MFMAs per k-step
   const unsigned short* wsrc = reinterpret_cast<const unsigned short*>(a.w_split) + frag_block(ub, wave, KS, 0, 0, 0) + lane * 8;
@@ -117,45 +77,7 @@ __global__ __launch_bounds__(LS_TH, 1) void lstm_step_split_kernel(const ssrhip_
     }
   }
 
-  // ---- the four partial tiles meet in LDS: part[wave][n][m]; accumulator register r of block (mb, nb) = D[32 mb + (r&3) + 8(r>>2) + 4 lh][32 nb + li]
-  float* mine = part + (size_t)wave * LS_BN * LS_PS;
-#pragma unroll
-  for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-    for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) mine[(nb * 32 + li) * LS_PS + mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh] = acc[mb][nb][r];
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int p = tid + LS_TH * i, u = p & 15, bl = p >> 4;
-    const int b = bg * LS_BN + bl, j = ub * LS_UN + u;
-    float gt[4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const float* src = part + (size_t)bl * LS_PS + g * 16 + u;
-      gt[g] = ((src[0] + src[LS_BN * LS_PS]) + (src[2 * LS_BN * LS_PS] + src[3 * LS_BN * LS_PS])) + pg[i][g];     // fixed order: deterministic
-    }
-    if (b < a.B) {
-      const float cn = sigmoid_(gt[1]) * pc[i] + sigmoid_(gt[0]) * tanhf(gt[2]);
-      const float hv = sigmoid_(gt[3]) * tanhf(cn);
-      a.cbuf[(size_t)b * C + j] = cn;
-      float o = hv + ps[i];                                            // y = lstm(x) + x on the last layer (lstm.py:21-23); ps == 0 otherwise
-      if (a.out_act == SSRHIP_ACT_ELU) o = elu1(o);
-      a.out[(size_t)b * a.out_bstride + (size_t)t * C + j] = o;
-      // h_t[b][j] as the next step's B operand: k = j -> wave j / (C/4), k-step (j % (C/4)) / 16, lane half (j % 16) / 8, element j % 8
-      unsigned short pcs[3];
-      split1(hv, pcs);
-      const int kq = C >> 2, w2 = j / kq, s2 = (j % kq) >> 4, lh2 = (j >> 3) & 1, e2 = j & 7;
-      unsigned short* dst = hn + frag_block(bg, w2, KS, s2, bl >> 5, 0) + (lh2 * 32 + (bl & 31)) * 8 + e2;
-#pragma unroll
-      for (int q = 0; q < 3; ++q) dst[q * 512] = pcs[q];
-    }
-  }
-}
-
-__global__ __launch_bounds__(256) void zero_u32_kernel(unsigned* p, long n) {
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) p[i] = 0u;
+  ls_finish(a, t, tid, wave, ub, bg, acc, part, rq, hn, KS);
 }
 
 }  // namespace

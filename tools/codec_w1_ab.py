@@ -1,9 +1,11 @@
-"""The bf16-rounded codec's A/B (DESIGN.md Part I.30): three arms of the full-size wmencodec (synthetic weights) in ONE process, in
-alternating rounds, median and spread (max - min) over the rounds:
+"""The bf16-rounded codec's A/B (DESIGN.md Parts I.30 and I.31): four models of the full-size wmencodec (synthetic weights) in ONE process,
+in alternating rounds, median and spread (max - min) over the rounds:
 
     F   weight_dtype="fp32"                          three planes of the fp32 weights, six products per k block
     B   weight_dtype="bf16", SSRHIP_CODEC_W1=0       three planes of the rounded weights (same kernels as F)
-    A   weight_dtype="bf16"                          one plane, three products per k block (the same bits as B, checked here)
+    A0  weight_dtype="bf16", SSRHIP_LSTM_W1=0        one plane in the GEMMs and residual blocks, three planes of W_hh in the LSTM step
+    A   weight_dtype="bf16", SSRHIP_LSTM_W1=1        ... and one plane of W_hh in the LSTM step (the same bits as A0 and B, checked here)
+    A8  the model A with SSRHIP_LSTM_W1_DEPTH=8 in the environment while it runs: eight k-steps in flight in the one-plane LSTM step
 
 Workloads: `encode` / `decode` / `wmdecode(with_mark=False)` of B clips x seconds (config 5's shape is 256x30; on an out-of-memory error the
 batch is halved), and a per-launch table — the GEMM shapes VERDICT r6 names and the residual blocks at 64 / 128 channels, three-plane
@@ -46,9 +48,31 @@ def build_arms():
         arms["B"] = WMEncodecModel(cfg, sd, "cuda", weight_dtype="bf16")
     finally:
         del os.environ["SSRHIP_CODEC_W1"]
-    arms["A"] = WMEncodecModel(cfg, sd, "cuda", weight_dtype="bf16")
-    assert arms["A"].one_plane and not arms["B"].one_plane
+    assert "SSRHIP_LSTM_W1" not in os.environ and "SSRHIP_LSTM_W1_DEPTH" not in os.environ, "the arms set the switches themselves"
+    for name, knob in (("A0", "0"), ("A", "1")):
+        os.environ["SSRHIP_LSTM_W1"] = knob
+        try:
+            arms[name] = WMEncodecModel(cfg, sd, "cuda", weight_dtype="bf16")
+        finally:
+            del os.environ["SSRHIP_LSTM_W1"]
+    arms["A8"] = arms["A"]                                           # the same model; `ARM_ENV` holds what differs while it runs
+    assert arms["A"].one_plane and arms["A0"].one_plane and not arms["B"].one_plane
+    assert arms["A"].lstm_one_plane and not arms["A0"].lstm_one_plane
     return cfg, arms
+
+
+ARM_ENV = {"A8": {"SSRHIP_LSTM_W1_DEPTH": "8"}}                      # read by the library at every ssrhip_lstm_layer_w1 call
+ORDER = ("F", "B", "A0", "A", "A8")
+
+
+def run_arm(name, fn, m):
+    env = ARM_ENV.get(name, {})
+    os.environ.update(env)
+    try:
+        return fn(m)
+    finally:
+        for k in env:
+            del os.environ[k]
 
 
 def plane_bytes(m):
@@ -73,10 +97,15 @@ def workload(cfg, arms, B, secs, rounds):
     entries = {"encode": lambda m: m.encode(wav)[0], "decode": lambda m: m.decode(codes),
                "wmdecode": lambda m: m.wmdecode(codes, marks, wav[..., : Tf * cfg.hop], with_mark=False)[0]}
     got = {}
+    L = _lib.lib()
+    steps = {}
     for name, m in arms.items():                                     # untimed: sizing passes, the allocator holds the blocks
-        got[name] = {e: fn(m).clone() for e, fn in entries.items()}
-    same = all(torch.equal(got["A"][e], got["B"][e]) for e in entries)
-    say(f"### {B} x {secs:g} s  ({Tf} frames per clip; A == B bit for bit on all three entries: {same})")
+        n0 = L.ssrhip_lstm_w1_launches()
+        got[name] = {e: run_arm(name, fn, m).clone() for e, fn in entries.items()}
+        steps[name] = L.ssrhip_lstm_w1_launches() - n0
+    same = all(torch.equal(got[n][e], got["B"][e]) for e in entries for n in ("A0", "A", "A8"))
+    say(f"### {B} x {secs:g} s  ({Tf} frames per clip; A0 == A == A8 == B bit for bit on all three entries: {same})")
+    say(f"  one-plane LSTM step launches in the untimed pass: " + ", ".join(f"{n} {steps[n]}" for n in ORDER))
     for e in ("decode", "wmdecode"):
         a, f = got["A"][e].double(), got["F"][e].double()
         say(f"  {e}: relative rms difference A vs F = {float((a - f).pow(2).mean().sqrt() / f.pow(2).mean().sqrt()):.4e}")
@@ -84,19 +113,22 @@ def workload(cfg, arms, B, secs, rounds):
     del got
     ms = {n: {e: [] for e in entries} for n in arms}
     for r in range(rounds):
-        for name in (("F", "B", "A") if r % 2 == 0 else ("A", "B", "F")):
+        for name in (ORDER if r % 2 == 0 else ORDER[::-1]):
             for e, fn in entries.items():
-                t, out = timed(lambda: fn(arms[name]))
+                t, out = timed(lambda: run_arm(name, fn, arms[name]))
                 ms[name][e].append(t)
                 del out
-    say("| entry | F fp32 ms (spread) | B bf16 x3 ms (spread) | A bf16 x1 ms (spread) | A / B | A / F |")
-    say("|---|---|---|---|---|---|")
+    say("| entry | F fp32 ms (spread) | B bf16 x3 ms (spread) | A0 bf16 x1, LSTM x3 ms (spread) | A bf16 x1 ms (spread) | A8 ms (spread) | A0 / B | A / A0 | A8 / A0 | A / F |")
+    say("|---|---|---|---|---|---|---|---|---|---|")
     for e in entries:
         med = {n: statistics.median(ms[n][e]) for n in arms}
         sp = {n: max(ms[n][e]) - min(ms[n][e]) for n in arms}
-        say(f"| {e} | {med['F']:.2f} ({sp['F']:.2f}) | {med['B']:.2f} ({sp['B']:.2f}) | {med['A']:.2f} ({sp['A']:.2f}) | "
-            f"{med['A'] / med['B']:.3f} | {med['A'] / med['F']:.3f} |")
-    say(f"  rounds = {rounds}, arms alternate F B A / A B F; mallocs_in_flight A = {arms['A'].mallocs_in_flight}")
+        say(f"| {e} | " + " | ".join(f"{med[n]:.2f} ({sp[n]:.2f})" for n in ORDER) +
+            f" | {med['A0'] / med['B']:.3f} | {med['A'] / med['A0']:.3f} | {med['A8'] / med['A0']:.3f} | {med['A'] / med['F']:.3f} |")
+        for n in ("A", "A8"):                                        # the gate of DESIGN.md Part I.31: below A0 by more than the larger spread
+            gap, noise = med["A0"] - med[n], max(sp["A0"], sp[n])
+            say(f"  gate {e}: A0 - {n} = {gap:.2f} ms against the larger spread {noise:.2f} ms -> {'met' if gap > noise else ('no difference' if abs(gap) <= noise else 'LOSES')}")
+    say(f"  rounds = {rounds}, arms alternate {' '.join(ORDER)} / reversed; mallocs_in_flight A = {arms['A'].mallocs_in_flight}, A0 = {arms['A0'].mallocs_in_flight}")
     say()
 
 
@@ -207,7 +239,8 @@ def main():
     say()
     if opt.workloads:
         cfg, arms = build_arms()
-        say(f"plane bytes: F {plane_bytes(arms['F']) / 2**20:.1f} MiB, B {plane_bytes(arms['B']) / 2**20:.1f} MiB, A {plane_bytes(arms['A']) / 2**20:.1f} MiB")
+        say(f"plane bytes: F {plane_bytes(arms['F']) / 2**20:.1f} MiB, B {plane_bytes(arms['B']) / 2**20:.1f} MiB, A0 {plane_bytes(arms['A0']) / 2**20:.1f} MiB, "
+            f"A {plane_bytes(arms['A']) / 2**20:.1f} MiB (W_hh packs are not in the plane cache: a third as large in A as in A0)")
         say()
         for wl in opt.workloads.split(","):
             B, secs = int(wl.split("x")[0]), float(wl.split("x")[1])
