@@ -563,6 +563,16 @@ int ssrhip_codec_gemm_w1(const ssrhip_gemm_args* a, ssrhip_stream_t stream);
 /* how many calls of ssrhip_codec_gemm_w1 and ssrhip_resblock_w1 launched a one-plane kernel (answered 0) in this process so far;
  * ssrhip_gemm_w1_launches does not count them. */
 int64_t ssrhip_codec_w1_launches(void);
+/* ssrhip_codec_gemm_w1 with the activation operand ROUNDED to bf16 (nearest even) where that entry splits it in three — behind ELU on
+ * load where act_in == SSRHIP_ACT_ELU (WMEncodecModel weight_dtype="bf16", act_dtype="bf16"): one product a0w0 per k block, one A plane
+ * in LDS. Its twin's contract — W_split is ONE bf16 plane [N][K]; 0 launched, 1 does not qualify and nothing was launched, under exactly
+ * the twin's conditions, < 0 contract error before any HIP call — and its plan, tile order, k-block order and epilogues: accumulation,
+ * bias, residual, ELU on store, time mask and class bias in fp32. On activations that already are bf16 values (and act_in NONE) the twin's
+ * result BIT FOR BIT. */
+int ssrhip_codec_gemm_a1(const ssrhip_gemm_args* a, ssrhip_stream_t stream);
+/* how many calls of ssrhip_codec_gemm_a1 and ssrhip_resblock_a1 launched a kernel (answered 0) in this process so far; the other
+ * counters do not count them. */
+int64_t ssrhip_codec_a1_launches(void);
 
 
 /* ------------------------------------------------------------------------------------------------
@@ -672,6 +682,10 @@ int ssrhip_resblock(const ssrhip_resblock_args* a, ssrhip_stream_t stream);
  * in {64, 128}, SSRHIP_GEMM_SPLIT=0, SSRHIP_RESBLOCK_DMA=0): the caller then calls ssrhip_resblock WITHOUT planes; < 0 for a contract
  * error (a NULL plane), before any HIP call. NEVER hand a one-plane buffer to ssrhip_resblock. Counted by ssrhip_codec_w1_launches. */
 int ssrhip_resblock_w1(const ssrhip_resblock_args* a, ssrhip_stream_t stream);
+/* ssrhip_resblock_w1 with both activation operands ROUNDED to bf16 (nearest even) where that entry splits them in three: ELU(x), and
+ * ELU(H + b3) between the two stages. One product per k block in both stages; the residual x is added back in fp32. Its twin's arguments,
+ * answers (0 / 1 under exactly its conditions / < 0 before any HIP call) and ring default. Counted by ssrhip_codec_a1_launches. */
+int ssrhip_resblock_a1(const ssrhip_resblock_args* a, ssrhip_stream_t stream);
 
 /* LayerNorm over rows (transformer.py:58-75) */
 int ssrhip_layernorm(const float* x, const float* w, const float* b, float eps, float* y, int32_t R, int32_t D,

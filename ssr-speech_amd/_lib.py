@@ -255,6 +255,9 @@ SYMBOLS = [
     ("ssrhip_codec_gemm_w1", C.c_int, [C.POINTER(GemmArgs), C.c_void_p]),
     ("ssrhip_codec_w1_launches", C.c_int64, []),
     ("ssrhip_resblock_w1", C.c_int, [C.POINTER(ResblockArgs), C.c_void_p]),
+    ("ssrhip_codec_gemm_a1", C.c_int, [C.POINTER(GemmArgs), C.c_void_p]),
+    ("ssrhip_resblock_a1", C.c_int, [C.POINTER(ResblockArgs), C.c_void_p]),
+    ("ssrhip_codec_a1_launches", C.c_int64, []),
     ("ssrhip_conv_few_out", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_void_p]),
     ("ssrhip_conv_cin1", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_void_p]),
     ("ssrhip_pad_reflect", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p]),

@@ -133,6 +133,7 @@ def _fold_wn(sd, pfx: str, which: str) -> Tuple[torch.Tensor, torch.Tensor]:
 
 
 CODEC_WEIGHT_DTYPES = ("fp32", "bf16")
+CODEC_ACT_DTYPES = ("fp32", "bf16")
 
 
 def _round_w(w: torch.Tensor, wdt: str) -> torch.Tensor:
@@ -359,14 +360,32 @@ _ENV_KNOBS = (
 )
 
 
+def _codec_w1_env() -> bool:
+    """The `codec_w1` switch as the environment has it now (what `WMEncodecModel.__init__` will read)."""
+    _, switch, unset, parse = next(k for k in _ENV_KNOBS if k[0] == "codec_w1")
+    return bool(parse(os.environ.get(switch, unset)))
+
+
 class WMEncodecModel:
-    def __init__(self, cfg: CodecConfig, state_dict: dict, device, *, weight_dtype: str = "fp32"):
+    def __init__(self, cfg: CodecConfig, state_dict: dict, device, *, weight_dtype: str = "fp32", act_dtype: str = "fp32"):
         """`weight_dtype="bf16"`: every convolution, transposed-convolution and LSTM weight matrix is rounded once to a bf16 value (kept in
         fp32) behind the weight-norm fold; biases, codebooks and the label table stay fp32. The model is then the fp32 codec on the rounded
-        weights whatever kernel a shape takes, and its GEMMs and residual blocks run one weight plane (DESIGN.md Part I.30)."""
+        weights whatever kernel a shape takes, and its GEMMs and residual blocks run one weight plane (DESIGN.md Part I.30).
+
+        `act_dtype="bf16"` (with `weight_dtype="bf16"` and `codec_w1` on only): every matrix product that takes a one-plane entry rounds its
+        activation operand to bf16 (nearest even) where it is split in three today and keeps one product per k block; accumulation,
+        epilogues and the activations in memory stay fp32 (DESIGN.md Part I.32). Which layers round is a property of the layer, not of
+        the batch, window or stream an item is computed in."""
         if weight_dtype not in CODEC_WEIGHT_DTYPES:
             raise ValueError(f"weight_dtype {weight_dtype!r} not in {CODEC_WEIGHT_DTYPES}")
+        if act_dtype not in CODEC_ACT_DTYPES:
+            raise ValueError(f"act_dtype {act_dtype!r} not in {CODEC_ACT_DTYPES}")
+        if act_dtype == "bf16" and weight_dtype != "bf16":
+            raise ValueError("act_dtype='bf16' needs weight_dtype='bf16' (bf16 activations against fp32 weights have no kernel)")
+        if act_dtype == "bf16" and not _codec_w1_env():
+            raise ValueError("act_dtype='bf16' needs the one-plane kernels: SSRHIP_CODEC_W1=0 switches them off")
         self.weight_dtype = weight_dtype
+        self.act_dtype = act_dtype
         self.cfg = cfg
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -509,13 +528,18 @@ class WMEncodecModel:
         return self.weight_dtype == "bf16" and bool(self.codec_w1)
 
     @property
+    def bf16_acts(self) -> bool:
+        """The one-plane entries with the activation operand rounded to bf16: a `one_plane` model built with `act_dtype="bf16"`."""
+        return self.one_plane and self.act_dtype == "bf16"
+
+    @property
     def lstm_one_plane(self) -> bool:
         """W_hh as one plane and the one-plane recurrence step: a `one_plane` model with `lstm_split` and `lstm_w1` on."""
         return self.one_plane and bool(self.lstm_split) and bool(self.lstm_w1)
 
     def _call_w1(self, name: str, a) -> bool:
-        """A one-plane entry (`ssrhip_codec_gemm_w1`, `ssrhip_resblock_w1`) on the current stream: False when it answered 1 — nothing was
-        launched and the caller takes the fp32 path on the rounded masters, WITHOUT planes."""
+        """A one-plane entry (`ssrhip_codec_gemm_w1`, `ssrhip_resblock_w1`, their `_a1` forms) on the current stream: False when it
+        answered 1 — nothing was launched and the caller takes the fp32 path on the rounded masters, WITHOUT planes."""
         self.n_launches += 1
         rc = getattr(self.lib, name)(C.byref(a), _lib.stream_ptr())
         if rc == 1:
@@ -600,7 +624,7 @@ class WMEncodecModel:
             a.rbias, a.rclass, a.rrep = rowcls[0].data_ptr(), rowcls[1].data_ptr(), int(rowcls[2])
             a.rclass_stride = int(rowcls[1].stride(0)) if batch > 1 else int(rowcls[1].shape[1])
         if planes is not None and planes.dim() == 2:      # one plane: its own entry; on answer 1 the fp32 chain on the rounded master
-            if self._call_w1("ssrhip_codec_gemm_w1", a):
+            if self._call_w1("ssrhip_codec_gemm_a1" if self.bf16_acts else "ssrhip_codec_gemm_w1", a):
                 return
             a.W_split = 0
         self._call("ssrhip_gemm", C.byref(a))
@@ -711,7 +735,7 @@ class WMEncodecModel:
             if planes is not None:
                 a.w3_split, a.w1_split = planes[0].data_ptr(), planes[1].data_ptr()
             if planes is not None and planes[0].dtype == torch.bfloat16:      # one plane each: its own entry; on answer 1, no planes
-                if not self._call_w1("ssrhip_resblock_w1", a):
+                if not self._call_w1("ssrhip_resblock_a1" if self.bf16_acts else "ssrhip_resblock_w1", a):
                     a.w3_split = a.w1_split = 0
                     self._call("ssrhip_resblock", C.byref(a))
             else:

@@ -63,6 +63,23 @@ __device__ __forceinline__ void split4(const float4 v, bf16x4 (&out)[3]) {
   }
 }
 
+// the first piece alone (bf16 activations, DESIGN I.32): the nearest-even conversion split4 starts with, nothing behind it
+__device__ __forceinline__ void round4(const float4 v, bf16x4& out) {
+  const f32x2 r[2] = {{v.x, v.y}, {v.z, v.w}};
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const unsigned bits = __builtin_bit_cast(unsigned, __builtin_convertvector(r[h], bfx2));     // v_cvt_pk_bf16_f32 (RNE)
+    out[2 * h] = (short)(bits & 0xFFFFu);
+    out[2 * h + 1] = (short)(bits >> 16);
+  }
+}
+// NA pieces of 4 consecutive k-values: 3 = the exact split, 1 = the value rounded to bf16
+template <int NA>
+__device__ __forceinline__ void pieces4(const float4 v, bf16x4 (&out)[NA]) {
+  if constexpr (NA == 3) split4(v, out);
+  else round4(v, out[0]);
+}
+
 __global__ __launch_bounds__(256) void split_weights_kernel(const float* __restrict__ W, short* __restrict__ out, size_t n_elems) {
   for (size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n_elems; i += (size_t)gridDim.x * blockDim.x * 4) {
     bf16x4 p[3];
@@ -85,15 +102,23 @@ constexpr int BN = 128, BK = 32, PITCH = 40;                                // p
 // the three-plane form on the same weights, for FINITE activations (inf x 0 = NaN exists in the six-product form only).
 constexpr int PA3[6] = {2, 0, 1, 1, 0, 0}, PB3[6] = {0, 2, 1, 0, 1, 0};    // a2w0, a0w2, a1w1, a1w0, a0w1, a0w0
 constexpr int PA1[3] = {2, 1, 0};                                           // a2w0, a1w0, a0w0
-template <int NP> constexpr int n_prod() { static_assert(NP == 1 || NP == 3, "W comes as one or three planes"); return NP == 3 ? 6 : 3; }
-template <int NP> constexpr int prod_a(int pq) { return NP == 3 ? PA3[pq] : PA1[pq]; }
+//
+// NA = pieces of A (DESIGN I.32): 3 = the exact split of an fp32 activation; 1 (with NP = 1 only: a `weight_dtype="bf16"` codec that asked
+// for `act_dtype="bf16"`) = the activation ROUNDED to bf16 where it was split — the first piece alone, one A plane in LDS, one product
+// a0w0 per k block. The same tiles, k-block order and epilogues; for an activation that already is a bf16 value the same bits as NA = 3
+// (its pieces 1 and 2 are zeros).
+template <int NP, int NA = 3> constexpr int n_prod() {
+  static_assert((NP == 1 || NP == 3) && (NA == 3 || (NA == 1 && NP == 1)), "W comes as one or three planes; one piece of A goes with one plane of W");
+  return NA == 1 ? 1 : NP == 3 ? 6 : 3;
+}
+template <int NP, int NA = 3> constexpr int prod_a(int pq) { return NA == 1 ? 0 : NP == 3 ? PA3[pq] : PA1[pq]; }
 template <int NP> constexpr int prod_b(int pq) { return NP == 3 ? PB3[pq] : 0; }
 
-template <int BM, bool ELU, int NP>
+template <int BM, bool ELU, int NP, int NA = 3>
 __device__ __forceinline__ void gemm_split_body(const ssrhip_gemm_args& a0) {
   constexpr int MT = 2, NT = BM == 128 ? 2 : 1;
   constexpr int LA = BM / 32;
-  __shared__ __attribute__((aligned(16))) short As[3][BM * PITCH];
+  __shared__ __attribute__((aligned(16))) short As[NA][BM * PITCH];
   __shared__ __attribute__((aligned(16))) short Ws[NP][BN * PITCH];
   ssrhip_gemm_args a = a0;
   {   // batched problems: grid.z
@@ -144,10 +169,10 @@ __device__ __forceinline__ void gemm_split_body(const ssrhip_gemm_args& a0) {
   auto lds_store = [&]() {
 #pragma unroll
     for (int i = 0; i < LA; ++i) {
-      bf16x4 p[3];
-      split4(ra[i], p);
+      bf16x4 p[NA];
+      pieces4<NA>(ra[i], p);
 #pragma unroll
-      for (int q = 0; q < 3; ++q) *reinterpret_cast<bf16x4*>(&As[q][(lr + 32 * i) * PITCH + lc]) = p[q];
+      for (int q = 0; q < NA; ++q) *reinterpret_cast<bf16x4*>(&As[q][(lr + 32 * i) * PITCH + lc]) = p[q];
     }
 #pragma unroll
     for (int q = 0; q < NP; ++q)
@@ -157,9 +182,9 @@ __device__ __forceinline__ void gemm_split_body(const ssrhip_gemm_args& a0) {
   auto mma_tile = [&]() {
 #pragma unroll
     for (int kk = 0; kk < BK; kk += 16) {
-      bf16x8 fa[3][MT], fb[NP][NT];
+      bf16x8 fa[NA][MT], fb[NP][NT];
 #pragma unroll
-      for (int q = 0; q < 3; ++q) {
+      for (int q = 0; q < NA; ++q) {
 #pragma unroll
         for (int i = 0; i < MT; ++i) fa[q][i] = *reinterpret_cast<const bf16x8*>(&As[q][((wm * MT + i) * 32 + li) * PITCH + kk + lh * 8]);
         if (q < NP) {
@@ -168,12 +193,12 @@ __device__ __forceinline__ void gemm_split_body(const ssrhip_gemm_args& a0) {
         }
       }
 #pragma unroll
-      for (int pq = 0; pq < n_prod<NP>(); ++pq)
+      for (int pq = 0; pq < n_prod<NP, NA>(); ++pq)
 #pragma unroll
         for (int i = 0; i < MT; ++i)
 #pragma unroll
           for (int j = 0; j < NT; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[prod_a<NP>(pq)][i], fb[prod_b<NP>(pq)][j], acc[i][j], 0, 0, 0);
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[prod_a<NP, NA>(pq)][i], fb[prod_b<NP>(pq)][j], acc[i][j], 0, 0, 0);
     }
   };
   gload(0);
@@ -242,10 +267,11 @@ __global__ __launch_bounds__(256, 4) void gemm_w1_kernel(const ssrhip_gemm_args 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 constexpr int DMA_PLANE = 128 * 64;                                   // bytes: one bf16 plane of a 128 x 32 tile
-// A 3 planes of BM rows + W 2 stages x `np` planes; never less than the 8 x 4 KB the 16-byte epilogue turns its blocks through (the one-plane
-// 64-row tile's stages are smaller than that: 28,672 B)
-constexpr int dma_lds(int bm, int np = 3) { return 3 * bm * 64 + 2 * np * DMA_PLANE > 8 * 4096 ? 3 * bm * 64 + 2 * np * DMA_PLANE : 8 * 4096; }
+// A `na` planes of BM rows + W 2 stages x `np` planes; never less than the 8 x 4 KB the 16-byte epilogue turns its blocks through (the one-plane
+// 64-row tile's stages are smaller than that: 28,672 B; with one A plane both tiles' are: 24,576 and 20,480 B)
+constexpr int dma_lds(int bm, int np = 3, int na = 3) { return na * bm * 64 + 2 * np * DMA_PLANE > 8 * 4096 ? na * bm * 64 + 2 * np * DMA_PLANE : 8 * 4096; }
 static_assert(dma_lds(128) == 73728 && dma_lds(64) == 61440 && dma_lds(128, 1) == 40960 && dma_lds(64, 1) == 32768, "LDS of the DMA kernels");
+static_assert(dma_lds(128, 1, 1) == 32768 && dma_lds(64, 1, 1) == 32768, "LDS of the DMA kernels with one A plane");
 
 // BM = 128: waves 2 x 4 of 64 x 32; BM = 64 (grids that 128-row tiles would not fill, half-empty tiles): waves 2 x 4 of 32 x 32. Same
 // arithmetic per output element in both (and in the 4-wave kernels above).
@@ -293,16 +319,16 @@ __device__ __forceinline__ void xcd_tile(const int flags, int& bx, int& by, int&
   bz = (int)(t2 / ny);
 }
 
-template <int BM, bool ELU, int KO, bool TMF, int NP>
+template <int BM, bool ELU, int KO, bool TMF, int NP, int NA = 3>
 __device__ __forceinline__ void gemm_split_dma_body(const ssrhip_gemm_args a0, const int flags) {
   const int wide = flags & 1;
   int bx, by, bz;
   xcd_tile(flags, bx, by, bz);
   constexpr int MT = BM / 64, LA = BM / 64, APL = BM * 64;           // accumulators per wave, A loader passes, bytes per A plane
   extern __shared__ __attribute__((aligned(1024))) char ldsb[];
-  char* const As = ldsb;                                             // [3][BM][64 B]
-  char* const Wsb = ldsb + 3 * APL;                                  // [2][NP][128][64 B]
-  unsigned* const stamps = reinterpret_cast<unsigned*>(ldsb + dma_lds(BM, NP));   // GD_PROF only (the lab adds the bytes)
+  char* const As = ldsb;                                             // [NA][BM][64 B]
+  char* const Wsb = ldsb + NA * APL;                                 // [2][NP][128][64 B]
+  unsigned* const stamps = reinterpret_cast<unsigned*>(ldsb + dma_lds(BM, NP, NA));   // GD_PROF only (the lab adds the bytes)
   auto stamp = [&](int i) {
     if constexpr ((KO & GD_PROF) != 0) {
       if (threadIdx.x == 0 && i < GD_NSTAMP) stamps[i] = (unsigned)wall_clock64();
@@ -386,10 +412,10 @@ __device__ __forceinline__ void gemm_split_dma_body(const ssrhip_gemm_args a0, c
     for (int i = 0; i < LA; ++i) {
       float4 v = ra[i];
       if (ELU) { v.x = elu1(v.x); v.y = elu1(v.y); v.z = elu1(v.z); v.w = elu1(v.w); }
-      bf16x4 p[3];
-      split4(v, p);
+      bf16x4 p[NA];
+      pieces4<NA>(v, p);
 #pragma unroll
-      for (int q = 0; q < 3; ++q) *reinterpret_cast<bf16x4*>(As + q * APL + (lr + 64 * i) * 64 + aswz) = p[q];
+      for (int q = 0; q < NA; ++q) *reinterpret_cast<bf16x4*>(As + q * APL + (lr + 64 * i) * 64 + aswz) = p[q];
     }
   };
   const int fsw = (li >> 2) & 3;
@@ -398,18 +424,18 @@ __device__ __forceinline__ void gemm_split_dma_body(const ssrhip_gemm_args a0, c
 #pragma unroll
     for (int kk = 0; kk < BK; kk += 16) {
       const int coff = (((kk >> 3) + lh) ^ fsw) << 4;
-      bf16x8 fa[3][MT], fb[NP];
+      bf16x8 fa[NA][MT], fb[NP];
 #pragma unroll
-      for (int q = 0; q < 3; ++q) {
+      for (int q = 0; q < NA; ++q) {
 #pragma unroll
         for (int i = 0; i < MT; ++i) fa[q][i] = *reinterpret_cast<const bf16x8*>(As + q * APL + ((wm * MT + i) * 32 + li) * 64 + coff);
         if (q < NP) fb[q] = *reinterpret_cast<const bf16x8*>(Wsb + (stage * NP + q) * DMA_PLANE + (wn * 32 + li) * 64 + coff);
       }
 #pragma unroll
-      for (int pq = 0; pq < n_prod<NP>(); ++pq)
+      for (int pq = 0; pq < n_prod<NP, NA>(); ++pq)
 #pragma unroll
         for (int i = 0; i < MT; ++i)
-          if constexpr ((KO & GD_KO_MFMA) == 0) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[prod_a<NP>(pq)][i], fb[prod_b<NP>(pq)], acc[i], 0, 0, 0);
+          if constexpr ((KO & GD_KO_MFMA) == 0) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[prod_a<NP, NA>(pq)][i], fb[prod_b<NP>(pq)], acc[i], 0, 0, 0);
     }
     __builtin_amdgcn_s_setprio(0);
   };
@@ -591,6 +617,15 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(4, 4))) 
 template <int BM, bool ELU>
 __global__ __launch_bounds__(256, 4) void codec_w1_kernel(const ssrhip_gemm_args a0) { gemm_split_body<BM, ELU, 1>(a0); }
 
+// one W plane and ONE A plane (ssrhip_codec_gemm_a1, DESIGN I.32): the activation rounded to bf16 where the kernels above split it, one
+// product per k block. Every form ssrhip_codec_gemm_w1 dispatches, the ones it borrows from ssrhip_gemm_w1 included. Same launch bounds.
+template <int BM, bool ELU, bool TMF = false>
+__global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(4, 4))) void codec_a1_dma_kernel(const ssrhip_gemm_args a0, const int flags) {
+  gemm_split_dma_body<BM, ELU, 0, TMF, 1, 1>(a0, flags);
+}
+template <int BM, bool ELU>
+__global__ __launch_bounds__(256, 4) void codec_a1_kernel(const ssrhip_gemm_args a0) { gemm_split_body<BM, ELU, 1, 1>(a0); }
+
 }  // namespace
 
 // true when the split kernel applies to this call (decided by ssrhip_gemm). It depends on the matrix (N, K) and on what the caller
@@ -764,6 +799,56 @@ extern "C" int ssrhip_codec_gemm_w1(const ssrhip_gemm_args* a, ssrhip_stream_t s
   if (rc) return rc;
   SSR_LAUNCH_CHECK();
   ++g_codec_w1_launches;
+  return 0;
+}
+
+static std::atomic<int64_t> g_codec_a1_launches{0};      // launches through ssrhip_codec_gemm_a1 / ssrhip_resblock_a1
+extern "C" int64_t ssrhip_codec_a1_launches(void) { return g_codec_a1_launches.load(); }
+void ssr_codec_a1_count(void) { ++g_codec_a1_launches; }      // resblock_split.hip
+
+namespace {
+// the DMA kernels with one A plane take 32 KB of LDS whatever the tile (dma_lds(BM, 1, 1), below the 64 KB a kernel gets unasked): the
+// plan's figure is the one-plane call's
+template <int BM, bool ELU, bool TM>
+int launch_codec_a1_dma(const gemm_split_plan& p, const ssrhip_gemm_args* a, hipStream_t s) {
+  constexpr int lds = dma_lds(BM, 1, 1);
+  hipLaunchKernelGGL((codec_a1_dma_kernel<BM, ELU, TM>), p.grid, p.block, lds, s, *a, p.flags);
+  return 0;
+}
+template <int BM, bool TM = false>
+int launch_codec_a1(const bool dma, const gemm_split_plan& p, const ssrhip_gemm_args* a, hipStream_t s) {
+  const bool elu = a->act_in == SSRHIP_ACT_ELU;
+  if (dma) return elu ? launch_codec_a1_dma<BM, true, TM>(p, a, s) : launch_codec_a1_dma<BM, false, TM>(p, a, s);
+  if constexpr (!TM) {
+    if (elu) hipLaunchKernelGGL((codec_a1_kernel<BM, true>), p.grid, p.block, 0, s, *a);
+    else hipLaunchKernelGGL((codec_a1_kernel<BM, false>), p.grid, p.block, 0, s, *a);
+  }
+  return 0;
+}
+}  // namespace
+
+// One plane of W, one of A: see ssrhip.h. ssrhip_codec_gemm_w1's contract, conditions and plan (tile order, k-block order); the product
+// list is a0w0.
+extern "C" int ssrhip_codec_gemm_a1(const ssrhip_gemm_args* a, ssrhip_stream_t stream) {
+  SSR_REQUIRE(a && a->A && a->C, "ssrhip_codec_gemm_a1: null argument");
+  SSR_REQUIRE(a->W_split, "ssrhip_codec_gemm_a1: W_split is NULL (it is the one bf16 plane [N][K] this entry multiplies by)");
+  SSR_REQUIRE(a->M > 0 && a->N > 0 && a->K > 0 && a->K % 4 == 0 && a->lda % 4 == 0, "ssrhip_codec_gemm_a1: K and lda must be multiples of 4");
+  SSR_REQUIRE(!a->rbias || (a->rclass && a->rrep > 0), "ssrhip_codec_gemm_a1: rbias needs rclass and rrep > 0");
+  if (!ssrhip_gemm_split_eligible(a)) return 1;
+  hipStream_t s = (hipStream_t)stream;
+  const gemm_split_plan p = plan_gemm_split(a, ssr_codec_knobs(), getenv("SSRHIP_GEMM_XCD"), 1, true);
+  ssr_gemm_log(a, p.grid.x, p.grid.y, p.grid.z, 2);
+  int rc = 0;
+  switch (p.form) {
+    case GS_DMA128_TM: rc = launch_codec_a1<128, true>(true, p, a, s); break;
+    case GS_DMA128: rc = launch_codec_a1<128>(true, p, a, s); break;
+    case GS_DMA64: rc = launch_codec_a1<64>(true, p, a, s); break;
+    case GS_4WAVE128: rc = launch_codec_a1<128>(false, p, a, s); break;
+    case GS_4WAVE64: rc = launch_codec_a1<64>(false, p, a, s); break;
+  }
+  if (rc) return rc;
+  SSR_LAUNCH_CHECK();
+  ++g_codec_a1_launches;
   return 0;
 }
 

@@ -39,6 +39,16 @@ typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 __device__ __forceinline__ float elu_r(float v) { return elu1(v); }         // the codec's one ELU (common.h: hardware exponential, |error| <= 1.2e-7)
 
+// the first piece alone: the value rounded (nearest even) to bf16   (gemm_split.hip round4)
+__device__ __forceinline__ void round4r(const float4 v, bf16x4& out) {
+  const f32x2 r[2] = {{v.x, v.y}, {v.z, v.w}};
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const unsigned bits = __builtin_bit_cast(unsigned, __builtin_convertvector(r[h], bfx2));
+    out[2 * h] = (short)(bits & 0xFFFFu);
+    out[2 * h + 1] = (short)(bits >> 16);
+  }
+}
 // exact three-way split of 4 consecutive values: piece p of element e in out[p][e]   (gemm_split.hip)
 __device__ __forceinline__ void split4r(const float4 v, bf16x4 (&out)[3]) {
   f32x2 r[2] = {{v.x, v.y}, {v.z, v.w}};
@@ -57,6 +67,12 @@ __device__ __forceinline__ void split4r(const float4 v, bf16x4 (&out)[3]) {
     }
   }
 }
+// NA pieces of 4 consecutive values: 3 = the exact split, 1 = the value rounded to bf16
+template <int NA>
+__device__ __forceinline__ void pieces4r(const float4 v, bf16x4 (&out)[NA]) {
+  if constexpr (NA == 3) split4r(v, out);
+  else round4r(v, out[0]);
+}
 
 constexpr int RB_BM = 128, RB_TH = 256, RB_NW = 4;        // time steps per workgroup, threads, waves
 constexpr int RB_ER = RB_BM + 2 + 2;                      // rows of the ELU(x) tile (130 used; padded to a multiple of 4 for the swizzle period)
@@ -65,10 +81,15 @@ constexpr int RB_EP = RB_ER * 64;                         // bytes per bf16 plan
 constexpr int rb_wtile(int CC, int NP = 3) { return 32 * NP * CC; }
 constexpr int NS1X(int CC) { return 3 * (CC / 32); }
 // weight tiles in LDS = RING: the one in use + RING - 1 in flight (a 32-wide step is ~0.3 us of MFMAs, an L2 -> LDS DMA ~1 us)
-// (the ELU(x) tile is the activation operand: three planes whatever the weights are)
-constexpr int rb_lds(int CC, int RING, int NP = 3) { return 3 * RB_EP + RING * rb_wtile(CC, NP); }
+// (the ELU(x) tile is the activation operand: three planes whatever the weights are — or ONE, `NA` = 1, where the activation is rounded to
+// bf16 instead of split: DESIGN I.32. The 16-byte epilogue turns its blocks through 4 KB per wave at the front of the tile's region, so
+// the region is never smaller than that: the ring behind it may still be read by a slower wave)
+constexpr int rb_eregion(int NA = 3) { return NA * RB_EP > RB_NW * 4096 ? NA * RB_EP : RB_NW * 4096; }
+constexpr int rb_lds(int CC, int RING, int NP = 3, int NA = 3) { return rb_eregion(NA) + RING * rb_wtile(CC, NP); }
 static_assert(rb_lds(128, 2) == 49920 && rb_lds(128, 4) == 74496 && rb_lds(64, 2) == 37632 && rb_lds(64, 4) == 49920, "LDS of the three-plane kernels");
 static_assert(rb_lds(128, 2, 1) == 33536 && rb_lds(128, 4, 1) == 41728 && rb_lds(64, 2, 1) == 29440 && rb_lds(64, 4, 1) == 33536, "LDS of the one-plane kernels");
+static_assert(rb_eregion() == 3 * RB_EP && rb_eregion(1) == 16384, "the ELU(x) tile's region");
+static_assert(rb_lds(128, 2, 1, 1) == 24576 && rb_lds(128, 4, 1, 1) == 32768 && rb_lds(64, 2, 1, 1) == 20480 && rb_lds(64, 4, 1, 1) == 24576, "LDS of the one-piece kernels");
 typedef int i32x4r __attribute__((ext_vector_type(4)));
 
 // LDS-DMA as inline asm: with the builtin hipcc applies its conservative alias rule — every ds_read behind an LDS-DMA first waits for
@@ -107,6 +128,7 @@ __device__ unsigned* g_rb_prof = nullptr;                 // [sampled workgroup]
 
 #define RB_KERNEL resblock_split_dma_kernel      // three planes per matrix: the exact split of fp32 weights (ssrhip_resblock)
 #define RB_NP 3
+#define RB_NA 3
 #include "resblock_split_kernel.h"
 #undef RB_KERNEL
 #undef RB_NP
@@ -116,7 +138,15 @@ __device__ unsigned* g_rb_prof = nullptr;                 // [sampled workgroup]
 #define RB_NP 1
 #include "resblock_split_kernel.h"
 #undef RB_KERNEL
+// one plane per matrix and ONE piece per activation (ssrhip_resblock_a1, DESIGN I.32): ELU(x) and ELU(H + b3) rounded to bf16 where the
+// kernels above split them, one product per k block in both stages; 20-32 KB of LDS
+#undef RB_NA
+#define RB_NA 1
+#define RB_KERNEL resblock_a1_dma_kernel
+#include "resblock_split_kernel.h"
+#undef RB_KERNEL
 #undef RB_NP
+#undef RB_NA
 
 }  // namespace
 
@@ -163,5 +193,28 @@ extern "C" int ssrhip_resblock_w1(const ssrhip_resblock_args* a, ssrhip_stream_t
   else hipLaunchKernelGGL((resblock_w1_dma_kernel<64, 4>), grid, dim3(RB_TH), rb_lds(64, 4, 1), s, *a, wide);
   SSR_LAUNCH_CHECK();
   ssr_codec_w1_count();
+  return 0;
+}
+
+void ssr_codec_a1_count(void);      // gemm_split.hip: the bf16-activation launch counter (ssrhip_codec_a1_launches)
+
+// One plane per matrix, one piece per activation: see ssrhip.h. ssrhip_resblock_w1's contract, conditions and ring default.
+extern "C" int ssrhip_resblock_a1(const ssrhip_resblock_args* a, ssrhip_stream_t stream) {
+  SSR_REQUIRE(a && a->x && a->y && a->b3 && a->b1, "ssrhip_resblock_a1: null argument");
+  SSR_REQUIRE(a->w3_split && a->w1_split, "ssrhip_resblock_a1: w3_split and w1_split (one bf16 plane each) are both required");
+  SSR_REQUIRE(a->B > 0 && a->B <= 65535 && a->T > 0, "ssrhip_resblock_a1: bad B / T");
+  const codec_knobs& k = ssr_codec_knobs();
+  if (!(a->C == 64 || a->C == 128) || !k.gemm_split || !k.resblock_dma) return 1;
+  SSR_REQUIRE((size_t)(a->T + 2) * a->C * 4 < 0x7FFFFFF0ull, "ssrhip_resblock_a1: item too long");
+  hipStream_t s = (hipStream_t)stream;
+  dim3 grid((a->T + RB_BM - 1) / RB_BM, a->B);
+  const int wide = k.resblock_wide;
+  if (k.resblock_w1_ring == 2) {
+    if (a->C == 128) hipLaunchKernelGGL((resblock_a1_dma_kernel<128, 2>), grid, dim3(RB_TH), rb_lds(128, 2, 1, 1), s, *a, wide);
+    else hipLaunchKernelGGL((resblock_a1_dma_kernel<64, 2>), grid, dim3(RB_TH), rb_lds(64, 2, 1, 1), s, *a, wide);
+  } else if (a->C == 128) hipLaunchKernelGGL((resblock_a1_dma_kernel<128, 4>), grid, dim3(RB_TH), rb_lds(128, 4, 1, 1), s, *a, wide);
+  else hipLaunchKernelGGL((resblock_a1_dma_kernel<64, 4>), grid, dim3(RB_TH), rb_lds(64, 4, 1, 1), s, *a, wide);
+  SSR_LAUNCH_CHECK();
+  ssr_codec_a1_count();
   return 0;
 }

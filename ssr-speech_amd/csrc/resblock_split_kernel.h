@@ -1,5 +1,5 @@
 // resblock_split_kernel.h — the body of resblock_split.hip's DMA kernel, included once per plane count:
-//   #define RB_KERNEL <kernel name>   and   #define RB_NP <planes of W3 / W1: 3 or 1>
+//   #define RB_KERNEL <kernel name>,   #define RB_NP <planes of W3 / W1: 3 or 1>   and   #define RB_NA <pieces of an activation: 3 or 1>
 // The plane count is a compile-time constant of the kernel and not a template parameter of a shared `__device__` body because the
 // three-plane kernels must stay what they were: inlined into a wrapper kernel, hipcc peels the channel-tile loop of the same source
 // differently (312 matrix instructions at C = 128 where the kernel written out has 240; tests/test_codec_w1_isa.py pins the counts).
@@ -10,10 +10,16 @@
 // activation pieces 2, 1, 0 against plane 0 in the order the six-product list visits them: the same bits on the same weights for finite
 // activations. A weight tile is then 32 C bytes = C/32 KiB-DMAs (one per wave at C = 128; at C = 64 waves 2 and 3 repeat the last KiB), so
 // CNT = 1 and every hand-counted wait below shrinks with it; the ELU(x) tile — the activation operand — keeps its three planes.
+// NA = pieces of an activation (DESIGN I.32): 3 = the exact split; 1 (with NP = 1 only) = ELU(x) and ELU(H + b3) ROUNDED to bf16 where they
+// were split: the ELU(x) tile is one plane, hf one piece per k16 step, one product per k block in both stages. The hand-counted waits
+// count vector-memory operations — the weight DMA (CNT per wave and tile) and the NEL float4 loads of x — and neither depends on NA: the
+// arguments of wait_vm are what they are for NA = 3. The epilogue's 4 KB per wave no longer fit inside the tile (8,448 B): its region
+// is padded to them (rb_eregion), so no wave's blocks reach the ring, which a slower wave may still be reading.
 template <int CC, int RB_RING, int KO = 0>
 __global__ __launch_bounds__(RB_TH, 2) void RB_KERNEL(const ssrhip_resblock_args a, const int wide) {
   constexpr int NP = RB_NP;
-  static_assert(NP == 1 || NP == 3, "W3 / W1 come as one or three planes");
+  constexpr int NA = RB_NA;
+  static_assert((NP == 1 || NP == 3) && (NA == 3 || (NA == 1 && NP == 1)), "W3 / W1 come as one or three planes; one activation piece goes with one plane");
   constexpr int HH = CC / 2, NHB = HH / 32, NCT = CC / 32, NNB = CC / 32, NJ = HH / 16;
   constexpr int NS1 = NCT * 3;                             // weight tiles: NS1 of W3 (channel tile, tap), then NJ of W1
   constexpr int WT = rb_wtile(CC, NP), NIT = NP * HH / 16; // DMA instructions per tile (1 KiB each): NP planes x HH/16 (= NP x CC/32)
@@ -21,11 +27,12 @@ __global__ __launch_bounds__(RB_TH, 2) void RB_KERNEL(const ssrhip_resblock_args
   constexpr int NU = NS1X(CC) + HH / 16;                   // weight tiles in all
   constexpr int K3 = 3 * CC;
   constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};   // a2b0, a0b2, a1b1, a1b0, a0b1, a0b0 (smallest first)
-  constexpr int NPQ = NP == 3 ? 6 : 3, P1[6] = {2, 1, 0, 0, 0, 0};        // one plane: the activation's pieces 2, 1, 0 against plane 0
+  constexpr int NPQ = NA == 1 ? 1 : NP == 3 ? 6 : 3;                     // one plane: the activation's pieces 2, 1, 0 against plane 0;
+  constexpr int P1[6] = {NA == 3 ? 2 : 0, NA == 3 ? 1 : 0, 0, 0, 0, 0};  // one piece: a0b0 alone
   extern __shared__ __attribute__((aligned(1024))) char lds[];
-  char* const Es = lds;                                    // [3][RB_ER][64 B]
-  char* const Wb = lds + 3 * RB_EP;                        // [RB_RING][WT]
-  unsigned* const stamps = reinterpret_cast<unsigned*>(lds + rb_lds(CC, RB_RING, NP));      // RB_PROF only (the lab adds the bytes)
+  char* const Es = lds;                                    // [NA][RB_ER][64 B]
+  char* const Wb = lds + rb_eregion(NA);                   // [RB_RING][WT]
+  unsigned* const stamps = reinterpret_cast<unsigned*>(lds + rb_lds(CC, RB_RING, NP, NA));      // RB_PROF only (the lab adds the bytes)
   auto stamp = [&](int i) {
     if constexpr ((KO & RB_PROF) != 0) {
       if (threadIdx.x == 0) stamps[i] = (unsigned)wall_clock64();
@@ -105,11 +112,11 @@ __global__ __launch_bounds__(RB_TH, 2) void RB_KERNEL(const ssrhip_resblock_args
       const int idx = min(t + RB_TH * i, 130 * 8 - 1);
       const int row = idx >> 3, c4 = idx & 7;
       const float4 v = make_float4(elu_r(er[i].x), elu_r(er[i].y), elu_r(er[i].z), elu_r(er[i].w));
-      bf16x4 p[3];
-      split4r(v, p);
+      bf16x4 p[NA];
+      pieces4r<NA>(v, p);
       const int off = row * 64 + (((c4 >> 1) ^ ((row >> 2) & 3)) << 4) + (c4 & 1) * 8;
 #pragma unroll
-      for (int q = 0; q < 3; ++q) *reinterpret_cast<bf16x4*>(Es + q * RB_EP + off) = p[q];
+      for (int q = 0; q < NA; ++q) *reinterpret_cast<bf16x4*>(Es + q * RB_EP + off) = p[q];
     }
   };
 
@@ -119,7 +126,7 @@ __global__ __launch_bounds__(RB_TH, 2) void RB_KERNEL(const ssrhip_resblock_args
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc1[hb][r] = 0.f;
   f32x16 acc2[NNB];
-  bf16x8 hf[3][NJ];                                        // stage-2 A operand: ELU(H + b3) of this lane's time step, split, in k' order
+  bf16x8 hf[NA][NJ];                                       // stage-2 A operand: ELU(H + b3) of this lane's time step, split, in k' order
 
   e_load(0);
   // b3 of the hidden channels this lane's accumulator registers hold, requested NOW: a load between the stages would make the compiler
@@ -133,6 +140,13 @@ __global__ __launch_bounds__(RB_TH, 2) void RB_KERNEL(const ssrhip_resblock_args
   for (int u0 = 0; u0 < RB_RING - 1; ++u0) dma_tile(u0);
   // ---- stage 1, transposed: acc1[hb][h][m] += W3[h][k] . E[m + tap][k]; a runtime loop over the channel tiles (a fully unrolled
   // 16-step loop was refused by the compiler and left the register arrays in scratch), the three taps of a tile unrolled
+  // One piece: the body is a third of the twin's, and left alone hipcc unrolls all NCT channel tiles (64 matrix instructions at C = 128
+  // where a third of the twin's text is 40, 16 LDS-DMA loads for its 11). The factor below gives the twin's shape back — two tiles in the
+  // text at C = 128, one at C = 64 — which tests/test_codec_a1_isa.py compares instruction for instruction.
+#if RB_NA == 1
+  constexpr int CT_UNROLL = CC == 128 ? 2 : 1;
+#pragma unroll CT_UNROLL
+#endif
   for (int ct = 0; ct < NCT; ++ct) {
 #pragma unroll
     for (int tap = 0; tap < 3; ++tap) {
@@ -156,9 +170,9 @@ __global__ __launch_bounds__(RB_TH, 2) void RB_KERNEL(const ssrhip_resblock_args
 #pragma unroll
       for (int kk = 0; kk < 32; kk += 16) {
         const int cidx = (kk >> 3) + lh;
-        bf16x8 fb[3], fa[NP][NHB];
+        bf16x8 fb[NA], fa[NP][NHB];
 #pragma unroll
-        for (int q = 0; q < 3; ++q) {
+        for (int q = 0; q < NA; ++q) {
           fb[q] = *reinterpret_cast<const bf16x8*>(Es + q * RB_EP + erow * 64 + ((cidx ^ ((erow >> 2) & 3)) << 4));
           if (q < NP) {
 #pragma unroll
@@ -191,11 +205,11 @@ __global__ __launch_bounds__(RB_TH, 2) void RB_KERNEL(const ssrhip_resblock_args
         const int r = half * 8 + i;
         v[i] = elu_r(acc1[hb][r] + b3r[hb][r]);
       }
-      bf16x4 p0[3], p1[3];
-      split4r(make_float4(v[0], v[1], v[2], v[3]), p0);
-      split4r(make_float4(v[4], v[5], v[6], v[7]), p1);
+      bf16x4 p0[NA], p1[NA];
+      pieces4r<NA>(make_float4(v[0], v[1], v[2], v[3]), p0);
+      pieces4r<NA>(make_float4(v[4], v[5], v[6], v[7]), p1);
 #pragma unroll
-      for (int q = 0; q < 3; ++q) hf[q][2 * hb + half] = __builtin_shufflevector(p0[q], p1[q], 0, 1, 2, 3, 4, 5, 6, 7);
+      for (int q = 0; q < NA; ++q) hf[q][2 * hb + half] = __builtin_shufflevector(p0[q], p1[q], 0, 1, 2, 3, 4, 5, 6, 7);
     }
 #pragma unroll
   for (int nb = 0; nb < NNB; ++nb)

@@ -147,7 +147,7 @@ class AudioTokenizer:
     """EnCodec audio (data/tokenizer.py:99-138)."""
 
     def __init__(self, device: Any = None, signature=None, *, config: Optional[CodecConfig] = None, state_dict: Optional[dict] = None,
-                 weight_dtype: str = "fp32") -> None:
+                 weight_dtype: str = "fp32", act_dtype: str = "fp32") -> None:
         if signature is not None:
             config, state_dict = load_codec_checkpoint(signature)
         if config is None or state_dict is None:
@@ -157,7 +157,8 @@ class AudioTokenizer:
             if torch.cuda.is_available():
                 device = torch.device("cuda:0")
         self._device = torch.device(device)
-        self.codec = WMEncodecModel(config, state_dict, self._device, weight_dtype=weight_dtype)      # "bf16": the bf16-rounded codec
+        # weight_dtype "bf16": the bf16-rounded codec; act_dtype "bf16" (with it only): bf16 activation operands in its one-plane kernels
+        self.codec = WMEncodecModel(config, state_dict, self._device, weight_dtype=weight_dtype, act_dtype=act_dtype)
         self.sample_rate = self.codec.sample_rate
         self.channels = self.codec.channels
 

@@ -56,6 +56,10 @@ EXTRA_FLAGS = [
     ("--mask_end", dict(type=float, default=None, help="edit span end in seconds (speech editing)")),
     ("--mask_spans", dict(type=str, default=None, help="speech editing with up to max_n_spans (3) edits: 'a-b,c-d[,e-f]' in seconds — what the "
                                                        "reference derives from the word alignment of the edited transcript (one span per edit)")),
+    ("--codec_act_dtype", dict(type=str, choices=["fp32", "bf16"], default="fp32",
+                               help="bf16 (with --codec_weight_dtype bf16 only): the codec's one-plane GEMMs and residual blocks round their "
+                                    "activation operand to bf16 too, one matrix product per k block instead of three "
+                                    "(AudioTokenizer(act_dtype=...)); fp32 (default): activations as exact three-way splits")),
     ("--codec_weight_dtype", dict(type=str, choices=["fp32", "bf16"], default="fp32",
                                   help="bf16: round the codec's convolution and LSTM matrices once to bf16 values; its GEMMs and residual "
                                        "blocks then run one weight plane, half the matrix instructions (AudioTokenizer(weight_dtype=...)); "
@@ -285,7 +289,8 @@ def main(argv=None):
     phn2num = ckpt["phn2num"]
     model.to(device)
     model.eval()
-    audio_tokenizer = AudioTokenizer(device=device, signature=args.codec_path, weight_dtype=args.codec_weight_dtype)        # :205
+    audio_tokenizer = AudioTokenizer(device=device, signature=args.codec_path, weight_dtype=args.codec_weight_dtype,
+                                     act_dtype=args.codec_act_dtype)        # :205
 
     if args.manifest is not None:
         import torch.distributed as dist

@@ -1,4 +1,4 @@
-"""The bf16-rounded codec's A/B (DESIGN.md Parts I.30 and I.31): four models of the full-size wmencodec (synthetic weights) in ONE process,
+"""The bf16-rounded codec's A/B (DESIGN.md Parts I.30, I.31 and I.32): five models of the full-size wmencodec (synthetic weights) in ONE process,
 in alternating rounds, median and spread (max - min) over the rounds:
 
     F   weight_dtype="fp32"                          three planes of the fp32 weights, six products per k block
@@ -6,11 +6,12 @@ in alternating rounds, median and spread (max - min) over the rounds:
     A0  weight_dtype="bf16", SSRHIP_LSTM_W1=0        one plane in the GEMMs and residual blocks, three planes of W_hh in the LSTM step
     A   weight_dtype="bf16", SSRHIP_LSTM_W1=1        ... and one plane of W_hh in the LSTM step (the same bits as A0 and B, checked here)
     A8  the model A with SSRHIP_LSTM_W1_DEPTH=8 in the environment while it runs: eight k-steps in flight in the one-plane LSTM step
+    R   the model A built with act_dtype="bf16": activation operands rounded to bf16, one product per k block (OTHER bits than A: reported)
 
 Workloads: `encode` / `decode` / `wmdecode(with_mark=False)` of B clips x seconds (config 5's shape is 256x30; on an out-of-memory error the
 batch is halved), and a per-launch table — the GEMM shapes VERDICT r6 names and the residual blocks at 64 / 128 channels, three-plane
-against one-plane entry on the same rounded matrix, us and fp32-equivalent TFLOP/s next to the matrix ceiling (2,500 / 6 for six
-products, 2,500 / 3 for three).
+against one-plane entry against bf16-activation entry on the same rounded matrix, us and fp32-equivalent TFLOP/s next to the matrix
+ceiling (2,500 / 6 for six products, 2,500 / 3 for three, 2,500 for one).
 
 Usage: python tools/codec_w1_ab.py [--workloads 256x30,8x10] [--rounds 4] [--launches 1] [--out profiles/codec_w1_ab.md]"""
 import argparse
@@ -56,13 +57,15 @@ def build_arms():
         finally:
             del os.environ["SSRHIP_LSTM_W1"]
     arms["A8"] = arms["A"]                                           # the same model; `ARM_ENV` holds what differs while it runs
+    arms["R"] = WMEncodecModel(cfg, sd, "cuda", weight_dtype="bf16", act_dtype="bf16")
+    assert arms["R"].bf16_acts and arms["R"].lstm_one_plane and not arms["A"].bf16_acts
     assert arms["A"].one_plane and arms["A0"].one_plane and not arms["B"].one_plane
     assert arms["A"].lstm_one_plane and not arms["A0"].lstm_one_plane
     return cfg, arms
 
 
 ARM_ENV = {"A8": {"SSRHIP_LSTM_W1_DEPTH": "8"}}                      # read by the library at every ssrhip_lstm_layer_w1 call
-ORDER = ("F", "B", "A0", "A", "A8")
+ORDER = ("F", "B", "A0", "A", "A8", "R")
 
 
 def run_arm(name, fn, m):
@@ -98,11 +101,11 @@ def workload(cfg, arms, B, secs, rounds):
                "wmdecode": lambda m: m.wmdecode(codes, marks, wav[..., : Tf * cfg.hop], with_mark=False)[0]}
     got = {}
     L = _lib.lib()
-    steps = {}
+    steps, a1 = {}, {}
     for name, m in arms.items():                                     # untimed: sizing passes, the allocator holds the blocks
-        n0 = L.ssrhip_lstm_w1_launches()
+        n0, r0 = L.ssrhip_lstm_w1_launches(), L.ssrhip_codec_a1_launches()
         got[name] = {e: run_arm(name, fn, m).clone() for e, fn in entries.items()}
-        steps[name] = L.ssrhip_lstm_w1_launches() - n0
+        steps[name], a1[name] = L.ssrhip_lstm_w1_launches() - n0, L.ssrhip_codec_a1_launches() - r0
     same = all(torch.equal(got[n][e], got["B"][e]) for e in entries for n in ("A0", "A", "A8"))
     say(f"### {B} x {secs:g} s  ({Tf} frames per clip; A0 == A == A8 == B bit for bit on all three entries: {same})")
     say(f"  one-plane LSTM step launches in the untimed pass: " + ", ".join(f"{n} {steps[n]}" for n in ORDER))
@@ -110,6 +113,11 @@ def workload(cfg, arms, B, secs, rounds):
         a, f = got["A"][e].double(), got["F"][e].double()
         say(f"  {e}: relative rms difference A vs F = {float((a - f).pow(2).mean().sqrt() / f.pow(2).mean().sqrt()):.4e}")
     say(f"  encode: {float((got['A']['encode'] != got['F']['encode']).double().mean()) * 100:.2f} % of the RVQ codes differ between A and F")
+    say(f"  bf16-activation launches in the untimed pass: " + ", ".join(f"{n} {a1[n]}" for n in ORDER))
+    for e in ("decode", "wmdecode"):
+        r, a = got["R"][e].double(), got["A"][e].double()
+        say(f"  {e}: relative rms difference R vs A = {float((r - a).pow(2).mean().sqrt() / a.pow(2).mean().sqrt()):.4e}")
+    say(f"  encode: {float((got['R']['encode'] != got['A']['encode']).double().mean()) * 100:.2f} % of the RVQ codes differ between R and A")
     del got
     ms = {n: {e: [] for e in entries} for n in arms}
     for r in range(rounds):
@@ -118,13 +126,17 @@ def workload(cfg, arms, B, secs, rounds):
                 t, out = timed(lambda: run_arm(name, fn, arms[name]))
                 ms[name][e].append(t)
                 del out
-    say("| entry | F fp32 ms (spread) | B bf16 x3 ms (spread) | A0 bf16 x1, LSTM x3 ms (spread) | A bf16 x1 ms (spread) | A8 ms (spread) | A0 / B | A / A0 | A8 / A0 | A / F |")
-    say("|---|---|---|---|---|---|---|---|---|---|")
+    say("| entry | F fp32 ms (spread) | B bf16 x3 ms (spread) | A0 bf16 x1, LSTM x3 ms (spread) | A bf16 x1 ms (spread) | A8 ms (spread) | R bf16 acts ms (spread) | A0 / B | A / A0 | A8 / A0 | A / F | R / A |")
+    say("|---|---|---|---|---|---|---|---|---|---|---|---|")
     for e in entries:
         med = {n: statistics.median(ms[n][e]) for n in arms}
         sp = {n: max(ms[n][e]) - min(ms[n][e]) for n in arms}
         say(f"| {e} | " + " | ".join(f"{med[n]:.2f} ({sp[n]:.2f})" for n in ORDER) +
-            f" | {med['A0'] / med['B']:.3f} | {med['A'] / med['A0']:.3f} | {med['A8'] / med['A0']:.3f} | {med['A'] / med['F']:.3f} |")
+            f" | {med['A0'] / med['B']:.3f} | {med['A'] / med['A0']:.3f} | {med['A8'] / med['A0']:.3f} | {med['A'] / med['F']:.3f} | {med['R'] / med['A']:.3f} |")
+        # the gate of DESIGN.md Part I.32 (I.11's rule): R below A by more than A's spread and by at least 1 %
+        gap = med["A"] - med["R"]
+        say(f"  gate {e}: A - R = {gap:.2f} ms ({gap / med['A'] * 100:.1f} %) against A's spread {sp['A']:.2f} ms -> "
+            f"{'met' if gap > sp['A'] and gap >= 0.01 * med['A'] else ('LOSES' if -gap > sp['A'] else 'no difference')}")
         for n in ("A", "A8"):                                        # the gate of DESIGN.md Part I.31: below A0 by more than the larger spread
             gap, noise = med["A0"] - med[n], max(sp["A0"], sp[n])
             say(f"  gate {e}: A0 - {n} = {gap:.2f} ms against the larger spread {noise:.2f} ms -> {'met' if gap > noise else ('no difference' if abs(gap) <= noise else 'LOSES')}")
@@ -163,10 +175,11 @@ def gemm_launch(L, M, N, K, batch, act_in, tm_c=0, rounds=4, reps=5):
         a.W_split = planes.data_ptr()
         _lib.check(entry(C.byref(a), _lib.stream_ptr()))
 
-    us = {"x3": [], "x1": []}
+    entry = {"x3": (L.ssrhip_gemm, three), "x1": (L.ssrhip_codec_gemm_w1, one), "a1": (L.ssrhip_codec_gemm_a1, one)}
+    us = {k: [] for k in entry}
     for r in range(rounds):
-        for arm in (("x3", "x1") if r % 2 == 0 else ("x1", "x3")):
-            us[arm].append(event_us((lambda: run(L.ssrhip_gemm, three)) if arm == "x3" else (lambda: run(L.ssrhip_codec_gemm_w1, one)), reps))
+        for arm in (tuple(entry) if r % 2 == 0 else tuple(entry)[::-1]):
+            us[arm].append(event_us(lambda: run(*entry[arm]), reps))
     flop = 2.0 * M * N * K * batch
     return us, flop
 
@@ -195,10 +208,11 @@ def resblock_launch(L, Cc, T, B, rounds=4, reps=5):
         a.w3_split, a.w1_split = planes[0].data_ptr(), planes[1].data_ptr()
         _lib.check(entry(C.byref(a), _lib.stream_ptr()))
 
-    us = {"x3": [], "x1": []}
+    entry = {"x3": (L.ssrhip_resblock, (p3, p1)), "x1": (L.ssrhip_resblock_w1, (o3, o1)), "a1": (L.ssrhip_resblock_a1, (o3, o1))}
+    us = {k: [] for k in entry}
     for r in range(rounds):
-        for arm in (("x3", "x1") if r % 2 == 0 else ("x1", "x3")):
-            us[arm].append(event_us((lambda: run(L.ssrhip_resblock, (p3, p1))) if arm == "x3" else (lambda: run(L.ssrhip_resblock_w1, (o3, o1))), reps))
+        for arm in (tuple(entry) if r % 2 == 0 else tuple(entry)[::-1]):
+            us[arm].append(event_us(lambda: run(*entry[arm]), reps))
     flop = 2.0 * B * T * (Hh * 3 * Cc + Cc * Hh)
     return us, flop
 
@@ -206,24 +220,25 @@ def resblock_launch(L, Cc, T, B, rounds=4, reps=5):
 def launch_table(B):
     L = _lib.lib()
     ELU = _lib.ACT_ELU
-    say(f"### per launch, batch {B} (three-plane entry on the rounded matrix = what arms F and B launch; one-plane entry = arm A)")
+    say(f"### per launch, batch {B} (three-plane entry on the rounded matrix = what arms F and B launch; one-plane entry = arm A; bf16-activation entry = arm R)")
     say(f"ring of the residual-block kernels: SSRHIP_RESBLOCK_RING={os.environ.get('SSRHIP_RESBLOCK_RING', 'unset (three planes: 2, one plane: 4)')}")
-    say(f"| launch | x3 us (spread) | x3 TFLOP/s (of {PEAK / 6:.0f}) | x1 us (spread) | x1 TFLOP/s (of {PEAK / 3:.0f}) | x1 / x3 |")
-    say("|---|---|---|---|---|---|")
+    say(f"| launch | x3 us (spread) | x3 TFLOP/s (of {PEAK / 6:.0f}) | x1 us (spread) | x1 TFLOP/s (of {PEAK / 3:.0f}) | x1 / x3 | a1 us (spread) | a1 TFLOP/s (of {PEAK:.0f}) | a1 / x1 |")
+    say("|---|---|---|---|---|---|---|---|---|")
+
+    def row(name, us, flop):
+        m3, m1, ma = (statistics.median(us[k]) for k in ("x3", "x1", "a1"))
+        sp = {k: max(us[k]) - min(us[k]) for k in us}
+        say(f"| {name} | {m3:.0f} ({sp['x3']:.0f}) | {flop / m3 / 1e6:.0f} | {m1:.0f} ({sp['x1']:.0f}) | {flop / m1 / 1e6:.0f} | {m1 / m3:.3f} | "
+            f"{ma:.0f} ({sp['a1']:.0f}) | {flop / ma / 1e6:.0f} | {ma / m1:.3f} |")
+
     # M x N x K: the decoder's transposed convolutions (ELU on load, time mask) and the encoder's strided ones at config 5's lengths
     shapes = [("12001x1280x1024 convtr s5", 12001, 1280, 1024, ELU, 256), ("1501x8192x2048 convtr s8", 1501, 8192, 2048, ELU, 1024),
               ("1500x1024x8192 conv s8", 1500, 1024, 8192, ELU, 0), ("12000x512x2560 conv s5", 12000, 512, 2560, ELU, 0),
               ("60001x512x512 convtr s4", 60001, 512, 512, ELU, 128), ("1500x2048x512 lstm in", 1500, 2048, 512, 0, 0)]
     for name, M, N, K, act_in, tm_c in shapes:
-        us, flop = gemm_launch(L, M, N, K, B, act_in, tm_c)
-        m3, m1 = statistics.median(us["x3"]), statistics.median(us["x1"])
-        say(f"| gemm {name} x{B} | {m3:.0f} ({max(us['x3']) - min(us['x3']):.0f}) | {flop / m3 / 1e6:.0f} | {m1:.0f} ({max(us['x1']) - min(us['x1']):.0f}) | "
-            f"{flop / m1 / 1e6:.0f} | {m1 / m3:.3f} |")
+        row(f"gemm {name} x{B}", *gemm_launch(L, M, N, K, B, act_in, tm_c))
     for Cc, T in ((64, 480000), (128, 240000)):
-        us, flop = resblock_launch(L, Cc, T, B)
-        m3, m1 = statistics.median(us["x3"]), statistics.median(us["x1"])
-        say(f"| resblock C={Cc} T={T} x{B} | {m3:.0f} ({max(us['x3']) - min(us['x3']):.0f}) | {flop / m3 / 1e6:.0f} | {m1:.0f} ({max(us['x1']) - min(us['x1']):.0f}) | "
-            f"{flop / m1 / 1e6:.0f} | {m1 / m3:.3f} |")
+        row(f"resblock C={Cc} T={T} x{B}", *resblock_launch(L, Cc, T, B))
     say()
 
 

@@ -50,6 +50,7 @@ def main(argv=None):
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--weight_dtype", choices=["fp32", "bf16"], default="fp32")
     ap.add_argument("--codec_weight_dtype", choices=["fp32", "bf16"], default="fp32", help="the codec's weights (DESIGN.md Part I.30; SSRHIP_CODEC_W1=0: three planes)")
+    ap.add_argument("--codec_act_dtype", choices=["fp32", "bf16"], default="fp32", help="bf16 (with --codec_weight_dtype bf16): bf16 activation operands (DESIGN.md Part I.32)")
     ap.add_argument("--utts", type=int, default=0, help="N > 0: the batched stream of N utterances against inference_batch + render_many")
     ap.add_argument("--use_watermark", action="store_true", help="the watermarked stream against one-pass inference_one_sample(use_watermark=True)")
     opt = ap.parse_args(argv)
@@ -66,7 +67,8 @@ def main(argv=None):
     model = model.to(dev).eval()
     model.set_weight_dtype(opt.weight_dtype)
     ccfg = W.codec_config_full()
-    tok = AudioTokenizer(device=dev, config=ccfg, state_dict=W.codec_state_dict(ccfg, seed=0), weight_dtype=opt.codec_weight_dtype)
+    tok = AudioTokenizer(device=dev, config=ccfg, state_dict=W.codec_state_dict(ccfg, seed=0), weight_dtype=opt.codec_weight_dtype,
+                         act_dtype=opt.codec_act_dtype)
     g = torch.Generator().manual_seed(7)
     n_prompt = 160
     noise_prompt = torch.randn(1, n_prompt * 320, generator=g) * 0.1
